@@ -2,17 +2,29 @@
 """bench.py — the driver's measurement contract for the int4-WOQ decode hot path.
 
   python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W --full     (the same headline, then everything else below)
+  python bench.py ... --dump-outputs DIR                   (also DIR/<name>.npy: what the last timed step computed)
+
+A plain run is lean: set-up, warm-up, the K timed steps, the outputs when asked for, the line. Its line carries the
+contract's scalars and the headline's own HBM figures, nothing that needs a run of its own. `--full` adds what is
+measured or checked beside the headline: the CPU baseline, the 128-step value and the other launch modes, the
+dominant kernel's roofline, the prompt pass, logits parity against the CPU oracle and the other BASELINE configurations
+(`extra_configs`); `--no-cpu-baseline`, `--no-extra`, `--no-70b`, `--no-parity` and `--prefill-seqs 0` thin it out.
+`--dump-outputs DIR` writes, after the timed steps, what a caller of the timed decode path receives from it:
+`logits.npy` (the last timed step's logits over the whole vocabulary, float32) and `tokens.npy` (the greedy tokens of the
+K timed steps, float64). Weights and prompt are drawn from fixed seeds, so the same arguments give the same inputs in
+every run and two builds can be compared output for output.
 
 A "step" is one batch-1 greedy decode token, weights synthetic (random-init, no checkpoints / network) and resident in
 HBM when the timed region starts; barrier + synchronize on both sides, max over ranks, ONE JSON line from rank 0.
 The K timed steps are K replays of the captured hipGraph on the current stream (token / position chained on the device,
 no host work per token); `--eager` times ONE eager burst instead (woq_engine_steps: K x ~131 launches back to back) — the
 same device time since round 4 found and removed what made graph replays ~1 us per kernel boundary slower (cross-stream
-event waits in front of the replay, profiles/r04ab_stream_mode_probe.txt); the N = 1 line reports both (`launch_modes`).
+event waits in front of the replay, profiles/r04ab_stream_mode_probe.txt); an N = 1 --full line reports both (`launch_modes`).
 
 Which workload (`--workload auto`, the default):
   * N = 1 on a one-GPU box  -> BASELINE.json configs[1]: Llama-2-7B int4 sym g128 (the configuration the metric is
-    quoted on). The same line carries `extra_configs`: configs[2] decode (g32 asym) and its 32 x 2048 prompt pass,
+    quoted on). Under --full the line carries `extra_configs`: configs[2] decode (g32 asym) and its 32 x 2048 prompt pass,
     configs[4] (Mistral-7B shape, fp8 KV, 8k context, chunked 4 x 2048 prompt pass), and configs[3]'s single-GPU point
     (Llama-2-70B on one GPU); `parity` (logits of the measured 32-layer model against the CPU oracle on the same
     (q, scale, zp)), `roofline`, `cpu_baseline`.
@@ -21,7 +33,7 @@ Which workload (`--workload auto`, the default):
     SURVEY.md §8(e)). The exchange runs on the device over xGMI as kernels of the native step (csrc/woq_comm.hip) after a
     start-up self-test; if that fails on this node the run falls back to host-issued RCCL all-reduces and says so.
   * N = 1 on a multi-GPU node (the first point of the driver's 1/2/4/8 sweep) -> the same 70B model on one GPU, so
-    that the sweep's N = 1 value is the strong-scaling base; the 7B number rides along in `extra_configs`.
+    that the sweep's N = 1 value is the strong-scaling base; under --full the 7B number rides along (`headline_7b`).
 
 The stdout line is <= 6 KB (`compact_line`): the contract's scalars, `config`, `dtype`, `roofline`, `cpu_baseline`,
 `prefill` / `parity` as numbers, `configs_summary`. Everything else (extra_configs, launch_modes, prose, per-config
@@ -195,6 +207,39 @@ def emit(out):
             except OSError:
                 pass
     print(compact_line(out), flush=True)
+
+
+DUMP_LIMIT = 64 << 20  # bytes, all of --dump-outputs together
+
+
+def decode_outputs(eng, steps, logits=None, native=True):
+    """What the timed decode path hands its caller, read right after the timed region: the last step's logits (`logits`
+    when given: the row gathered over tensor-parallel ranks) and the greedy tokens of the `steps` timed steps from the
+    engine's token log (slot p = the token of the step that fed position p; ids are exact in float64). The host-driven
+    tensor-parallel fallback (`native` False) keeps no token log: there the last token alone."""
+    import numpy as np
+
+    row = (eng.logits[:eng.cfg.vocab] if logits is None else logits).float().cpu().numpy()
+    if native:
+        end = int(eng.pos.item())
+        toks = eng.token_log()[end - steps:end].cpu().numpy()
+    else:
+        toks = eng.token.cpu().numpy()
+    return {"logits": row.astype(np.float32), "tokens": toks.astype(np.float64)}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array (float32 / float64 only), at most DUMP_LIMIT bytes in all."""
+    import numpy as np
+
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes is over the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def configs_summary(out):
@@ -910,6 +955,15 @@ def tp_point(args, cfg, rank, world, dist, steps, warmup, as_extra=False):
             raise RuntimeError("tensor-parallel exchange reported a timeout during the timed region")
         if not agree:
             raise RuntimeError("tensor-parallel ranks disagree on the greedy token")
+    outputs = None
+    if args.dump_outputs and not as_extra:
+        row = None
+        if dist is not None:  # a collective: every rank takes part, rank 0 writes
+            from intel_extension_for_transformers_amd.runtime.tp import gather_logits
+
+            row = gather_logits(eng.logits[:eng.cfg.vocab], cfg["vocab"])
+        if rank == 0:
+            outputs = decode_outputs(eng, steps, logits=row, native=native)
     tok_s = steps / elapsed
     wbytes = algorithmic_bytes_per_token(cfg, tp=world) * n_layers // cfg["layers"]
     point = {
@@ -925,8 +979,10 @@ def tp_point(args, cfg, rank, world, dist, steps, warmup, as_extra=False):
         "token_exchanges_per_token": 1 if world > 1 else 0, "allreduce_bytes": cfg["hidden"] * 4,
         "allreduce_transport": transport, "hipgraph": use_graph, "ranks_agree_on_token": agree,
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         point["roofline_gemv"] = gemv_roofline(eng)
+    if outputs is not None:
+        point["outputs"] = outputs
     if as_extra:
         point = dict(config="configs[3] single-GPU point: " + point.pop("workload"), **point)
     del eng, dec, comm
@@ -945,6 +1001,51 @@ def spawn_command(gpus, env, argv):
             "--master-addr", "127.0.0.1", "--master-port", port, os.path.abspath(__file__)] + list(argv)
 
 
+def full_7b(args, cfg, eng, out, elapsed, use_graph, run, max_ctx, want_prefill):
+    """--full, one GPU: what the line carries beside the headline, measured on the headline's engine right after its
+    timed region — the 128-step value, the other launch modes, the roofline, the prompt pass and the parity checks."""
+    import torch
+
+    tok_s = args.steps / elapsed
+    value_128 = tok_s
+    if args.steps != 128 and max_ctx >= args.prompt + args.warmup + 128 + 8:
+        # the driver runs 20 steps; the 128-step value of the same engine rides along (contexts grow to ~180 positions:
+        # the one-workgroup-per-head attention of the fused launch is context-linear, VERDICT r04 item 8)
+        feed_prompt(eng, cfg["vocab"], args.prompt)
+        value_128 = 128 / timed(run, 128, args.warmup, torch.cuda.synchronize, condition=None)
+    # the other way of issuing the same steps, same engine, same prompt, right after the headline
+    feed_prompt(eng, cfg["vocab"], args.prompt)
+    if not use_graph:
+        eng.capture(greedy=True)
+    other = eng.run if use_graph else eng.replay_graph
+    el2 = timed(other, args.steps, args.warmup, torch.cuda.synchronize, condition=(eng, None))
+    feed_prompt(eng, cfg["vocab"], args.prompt)
+    eng.capture(greedy=True)
+    el3 = timed(eng.replay_graph_round3, args.steps, args.warmup, torch.cuda.synchronize, condition=(eng, None))
+    out["value_128_steps"] = value_128
+    out["launch_modes"] = {
+        "eager_bursts_tokens_per_s": args.steps / (el2 if use_graph else elapsed),
+        "hipgraph_replay_tokens_per_s": args.steps / (elapsed if use_graph else el2),
+        "hipgraph_replay_behind_cross_stream_waits_tokens_per_s": args.steps / el3,
+        "headline": "hipgraph_replay" if use_graph else "eager_bursts",
+        "note": "the same kernels and device-side token chain either way, and the same device time since the "
+                "graph is launched on the caller's stream: through round 3 it was replayed on the engine's "
+                "capture stream behind cross-stream event waits, which cost every kernel boundary ~1 us "
+                "(1.17 vs 1.04 ms per token; profiles/r04g_graph_vs_eager_steps.txt found the gap, "
+                "profiles/r04ab_stream_mode_probe.txt its cause). Eager bursts cost ~0.34 ms of host launch "
+                "calls per token, issued ahead of the device; graph replays none"}
+    out["roofline"] = gemv_roofline(eng, read_traffic())
+    if want_prefill:
+        out["prefill"] = prefill_measure(eng, cfg, args.prefill_seqs, args.prefill_len, label=", same int4 g128 weights")
+    if not args.no_parity:
+        out["parity"] = {"decode": parity_check(eng, cfg)}
+        if want_prefill:
+            pp, timing = prefill_gemm_check(eng, cfg, args.prefill_seqs * args.prefill_len)
+            out["parity"]["prefill"] = pp
+            out["prefill"]["dominant_gemm"] = timing
+        out["fused_attention_launch"] = {"in_use": eng.uses_fused_attn(), "engine_status": eng.status()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -953,12 +1054,18 @@ def main():
     ap.add_argument("--prompt", type=int, default=32, help="positions already in the KV cache when timing starts")
     ap.add_argument("--layers", type=int, default=0, help="override the layer count (marks the line REDUCED)")
     ap.add_argument("--workload", choices=["auto", "7b", "70b"], default="auto")
-    ap.add_argument("--prefill-seqs", type=int, default=4, help="sequences in the main line's prompt-pass object (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: CPU baseline, 128-step value, launch "
+                         "modes, roofline, prompt pass, parity, extra_configs (a plain run measures the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (logits, tokens)")
+    ap.add_argument("--prefill-seqs", type=int, default=4,
+                    help="sequences in the main line's prompt-pass object (--full; 0 = skip)")
     ap.add_argument("--prefill-len", type=int, default=2048)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_configs (configs[2], [3] single GPU, [4])")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without extra_configs (configs[2], [3] single GPU, [4])")
     ap.add_argument("--no-70b", action="store_true", help="skip the 70B single-GPU point of extra_configs")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity checks")
     ap.add_argument("--no-structures", action="store_true", help="(no-op since round 6: the persistent launch left the library)")
     ap.add_argument("--graph", action="store_true", help="(the default: replays of the captured hipGraph on the current stream)")
     ap.add_argument("--no-graph", "--eager", dest="no_graph", action="store_true",
@@ -983,9 +1090,12 @@ def main():
                              "needs %d (the N > 1 line is configs[3], Llama-2-70B at tensor-parallel degree N: unmeasured "
                              "on hardware until a node runs it)" % (args.gpus, seen, args.gpus))
     respawn = spawn_command(args.gpus, os.environ, sys.argv[1:])
-    if respawn is not None:  # plain `python bench.py --gpus N`, N > 1: become torch.distributed.run's N ranks
+    if respawn is not None:  # plain `python bench.py --gpus N`, N > 1: torch.distributed.run's N ranks, as a child
+        import subprocess
+
         sys.stdout.flush()
-        os.execvpe(respawn[0], respawn, dict(os.environ, MASTER_ADDR=os.environ.get("MASTER_ADDR", "127.0.0.1")))
+        env = dict(os.environ, MASTER_ADDR=os.environ.get("MASTER_ADDR", "127.0.0.1"))
+        sys.exit(subprocess.call(respawn, env=env))
 
     import torch
 
@@ -1025,6 +1135,8 @@ def main():
     if workload == "70b":
         p = tp_point(args, LLAMA2_70B, rank, world, dist, args.steps, args.warmup)
         if rank == 0:
+            if "outputs" in p:
+                dump_outputs(args.dump_outputs, p.pop("outputs"))
             out = dict(base, value=p["tokens_per_s"], ms_per_step=p["ms_per_token"], scaling="strong",
                        data="synthetic (random-init int4 weights of the Llama-2-70B shape, random prompt ids)",
                        config={"workload": p["workload"], "global_batch": 1, "parallelism": "tp%d" % world,
@@ -1033,14 +1145,16 @@ def main():
                                "token_exchanges_per_token": p["token_exchanges_per_token"],
                                "allreduce_bytes": p["allreduce_bytes"], "allreduce_transport": p["allreduce_transport"],
                                "hipgraph": p["hipgraph"], "visible_gpus": torch.cuda.device_count()},
-                       hbm_gbps_per_gpu=p["hbm_gbps_per_gpu"], hbm_frac_of_peak_end_to_end=p["hbm_frac_per_gpu"],
-                       roofline=dict(p["roofline_gemv"], traffic=None))
+                       hbm_gbps_per_gpu=p["hbm_gbps_per_gpu"], hbm_frac_of_peak_end_to_end=p["hbm_frac_per_gpu"])
+            if "roofline_gemv" in p:
+                out["roofline"] = dict(p["roofline_gemv"], traffic=None)
             out["note"] = ("`value` is Llama-2-70B at tensor-parallel degree %d: the strong-scaling curve of BASELINE "
                            "configs[3] (the 7B batch-1 path of the metric's name does not shard, SURVEY.md §8(e))" % world)
             if world == 1:
                 out["note"] += ("; this is the curve's N = 1 base on a multi-GPU node — the headline configuration "
-                                "(configs[1], Llama-2-7B, what BENCH_rNN.json's `value` is) rides along as `headline_7b`")
-            if world == 1 and not args.no_extra:  # first point of a sweep on a multi-GPU node: the 7B headline rides along
+                                "(configs[1], Llama-2-7B, what BENCH_rNN.json's `value` is) rides along as `headline_7b` "
+                                "under --full")
+            if world == 1 and args.full and not args.no_extra:  # first point of a multi-GPU node's sweep: the 7B headline too
                 eng = build_engine(LLAMA2_7B, max_ctx=512)
                 feed_prompt(eng, LLAMA2_7B["vocab"], args.prompt)
                 e7 = decode_entry("configs[1] Llama-2-7B int4 sym g128, batch-1 decode", LLAMA2_7B, eng, args.steps,
@@ -1062,13 +1176,16 @@ def main():
     # ---- configs[1]: Llama-2-7B int4 sym g128, one GPU --------------------------------------------------------------
     cfg = dict(LLAMA2_7B, layers=args.layers or LLAMA2_7B["layers"])
     cpu = None
-    if not args.no_cpu_baseline and not args.counters_run:  # host-only leg first: the rest of the run keeps the GPU busy
+    if args.full and not args.no_cpu_baseline and not args.counters_run:  # host-only leg first: the rest keeps the GPU busy
         cpu = cpu_baseline(LLAMA2_7B)
     max_ctx = 1 << max(9, (args.prompt + args.warmup + max(args.steps, 128) + 8).bit_length())
-    want_prefill = args.prefill_seqs > 0 and not args.counters_run
-    if want_prefill:
+    # the engine is sized for the prompt pass whether or not this run measures it (--full): the headline's decode steps
+    # run on the same engine either way
+    sized_for_prefill = args.prefill_seqs > 0 and not args.counters_run
+    want_prefill = sized_for_prefill and args.full
+    if sized_for_prefill:
         max_ctx = max(max_ctx, args.prefill_len)
-    eng = build_engine(cfg, max_ctx=max_ctx, max_batch=max(1, args.prefill_seqs) if want_prefill else 1,
+    eng = build_engine(cfg, max_ctx=max_ctx, max_batch=max(1, args.prefill_seqs) if sized_for_prefill else 1,
                        layers=cfg["layers"])
     feed_prompt(eng, cfg["vocab"], args.prompt)
     use_graph = not args.no_graph and not args.counters_run
@@ -1090,32 +1207,9 @@ def main():
     elapsed = timed(run, args.steps, args.warmup, torch.cuda.synchronize, condition=(eng, None))
     timed_region = list(LAST_TIMED_REGION)
     conditioning = dict(LAST_CONDITIONING)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, decode_outputs(eng, args.steps))
     tok_s = args.steps / elapsed
-    value_128 = tok_s
-    if args.steps != 128 and max_ctx >= args.prompt + args.warmup + 128 + 8:
-        # the driver runs 20 steps; the 128-step value of the same engine rides along (contexts grow to ~180 positions:
-        # the one-workgroup-per-head attention of the fused launch is context-linear)
-        feed_prompt(eng, cfg["vocab"], args.prompt)
-        value_128 = 128 / timed(run, 128, args.warmup, torch.cuda.synchronize, condition=None)
-    # the other way of issuing the same steps, same engine, same prompt, right after the headline
-    feed_prompt(eng, cfg["vocab"], args.prompt)
-    if not use_graph:
-        eng.capture(greedy=True)
-    other = eng.run if use_graph else eng.replay_graph
-    el2 = timed(other, args.steps, args.warmup, torch.cuda.synchronize, condition=(eng, None))
-    feed_prompt(eng, cfg["vocab"], args.prompt)
-    eng.capture(greedy=True)
-    el3 = timed(eng.replay_graph_round3, args.steps, args.warmup, torch.cuda.synchronize, condition=(eng, None))
-    launch_modes = {"eager_bursts_tokens_per_s": args.steps / (el2 if use_graph else elapsed),
-                    "hipgraph_replay_tokens_per_s": args.steps / (elapsed if use_graph else el2),
-                    "hipgraph_replay_behind_cross_stream_waits_tokens_per_s": args.steps / el3,
-                    "headline": "hipgraph_replay" if use_graph else "eager_bursts",
-                    "note": "the same kernels and device-side token chain either way, and the same device time since the "
-                            "graph is launched on the caller's stream: through round 3 it was replayed on the engine's "
-                            "capture stream behind cross-stream event waits, which cost every kernel boundary ~1 us "
-                            "(1.17 vs 1.04 ms per token; profiles/r04g_graph_vs_eager_steps.txt found the gap, "
-                            "profiles/r04ab_stream_mode_probe.txt its cause). Eager bursts cost ~0.34 ms of host launch "
-                            "calls per token, issued ahead of the device; graph replays none"}
     qbytes = algorithmic_bytes_per_token(cfg)
     out = dict(base, value=tok_s, ms_per_step=elapsed * 1e3 / args.steps, scaling="weak",
                data="synthetic (random-init int4 weights of the Llama-2-7B shape, random prompt ids)",
@@ -1123,29 +1217,21 @@ def main():
                                    "lm_head fp16 unquantised, KV fp16%s"
                                    % (args.prompt, "" if cfg["layers"] == 32 else " [REDUCED to %d layers]" % cfg["layers"]),
                        "global_batch": 1, "parallelism": "single GPU", "hipgraph": use_graph},
-               value_128_steps=value_128,
-               timed_region_unix=timed_region, clock_conditioning=conditioning, launch_modes=launch_modes,
+               timed_region_unix=timed_region, clock_conditioning=conditioning,
                hbm_gbps_quantized_weight_stream=qbytes * tok_s / 1e9,
                hbm_frac_of_peak_end_to_end=qbytes * tok_s / 1e9 / HBM_PEAK_GBPS,
-               hbm_frac_of_measured_copy_ceiling_end_to_end=qbytes * tok_s / 1e9 / HBM_COPY_GBPS,
-               roofline=gemv_roofline(eng, read_traffic()))
-    if want_prefill:
-        out["prefill"] = prefill_measure(eng, cfg, args.prefill_seqs, args.prefill_len, label=", same int4 g128 weights")
-    if not args.no_parity:
-        out["parity"] = {"decode": parity_check(eng, cfg)}
-        if want_prefill:
-            pp, timing = prefill_gemm_check(eng, cfg, args.prefill_seqs * args.prefill_len)
-            out["parity"]["prefill"] = pp
-            out["prefill"]["dominant_gemm"] = timing
-        out["fused_attention_launch"] = {"in_use": eng.uses_fused_attn(), "engine_status": eng.status()}
+               hbm_frac_of_measured_copy_ceiling_end_to_end=qbytes * tok_s / 1e9 / HBM_COPY_GBPS)
+    if args.full:
+        full_7b(args, cfg, eng, out, elapsed, use_graph, run, max_ctx, want_prefill)
     del eng
     free_gpu()
-    if not args.no_parity and want_prefill:
-        out["parity"]["prefill"]["attention"] = prefill_attention_check(cfg, args.prefill_seqs, args.prefill_len)
-    if not args.no_extra:
-        out["extra_configs"] = extra_configs(args)
-    if cpu is not None:
-        out["cpu_baseline"] = cpu
+    if args.full:
+        if not args.no_parity and want_prefill:
+            out["parity"]["prefill"]["attention"] = prefill_attention_check(cfg, args.prefill_seqs, args.prefill_len)
+        if not args.no_extra:
+            out["extra_configs"] = extra_configs(args)
+        if cpu is not None:
+            out["cpu_baseline"] = cpu
     out["configs_summary"] = configs_summary(out)
     emit(out)
 

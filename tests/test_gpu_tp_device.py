@@ -214,26 +214,29 @@ def _free_port():
 
 
 @pytest.mark.parametrize("graph,plain", [(False, False), (True, False), (True, True)])
-def test_bench_py_multi_rank_line_on_one_gpu(graph, plain):
+def test_bench_py_multi_rank_line_on_one_gpu(graph, plain, tmp_path):
     """The driver's N > 1 command — `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
     127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` — end to end with two ranks on this one GPU
     (WOQ_BENCH_BACKEND=gloo: RCCL refuses two ranks per device; the device exchange does not need it): process-group
     set-up, the 70B-shaped shards (2 layers here), the device communicator's self-test, eager bursts (default) and the
     captured graph with the all-reduce kernels inside, rank agreement on the greedy token, and ONE JSON line from rank 0
-    with the contract's keys. So that the driver's first multi-GPU run cannot fail on plumbing."""
+    with the contract's keys. So that the driver's first multi-GPU run cannot fail on plumbing.
+    `--full` for the line's roofline; `--dump-outputs`: the last step's logits gathered over both ranks, and its greedy
+    token among the timed steps' tokens."""
     import json
     import subprocess
 
     env = dict(os.environ, WOQ_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-           "--warmup", "2", "--layers", "2", "--condition-ms", "20"] + ([] if graph else ["--eager"])
+           "--warmup", "2", "--layers", "2", "--condition-ms", "20", "--full", "--dump-outputs", str(tmp_path)]
+    cmd += [] if graph else ["--eager"]
     if plain:  # `python bench.py --gpus 2` with no launcher around it: bench.py becomes the two ranks itself
         env = dict(env, MASTER_PORT=str(_free_port()))
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
             env.pop(k, None)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-               "--layers", "2", "--condition-ms", "20"]
+               "--layers", "2", "--condition-ms", "20", "--full", "--dump-outputs", str(tmp_path)]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -246,3 +249,6 @@ def test_bench_py_multi_rank_line_on_one_gpu(graph, plain):
     assert d["config"]["parallelism"] == "tp2" and d["config"]["hipgraph"] == graph
     assert d["config"]["process_group_ranks"] == 2 and d["config"]["rccl_ranks_verified"] == 2
     assert "device one-shot all-reduce" in d["config"]["allreduce_transport"], d["config"]["allreduce_transport"]
+    logits, tokens = np.load(tmp_path / "logits.npy"), np.load(tmp_path / "tokens.npy")
+    assert logits.dtype == np.float32 and logits.shape == (32000,) and np.isfinite(logits).all()
+    assert tokens.dtype == np.float64 and tokens.shape == (6,) and int(tokens[-1]) == int(logits.argmax())
