@@ -46,6 +46,12 @@ WOQ_API int woq_engine_set_time_eager(woq_engine* e, int on);
  * call_ms = pack pass + GEMM. */
 WOQ_API int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, int reps, void* stream, float* gemm_ms,
                                          float* call_ms);
+/* forms of the most recent prefill-GEMM launches (launch_gemm_f16), oldest first, process-wide, at most 64 kept:
+ * copies min(n, cap) of them into forms[], returns n, and empties the log (forms == NULL / cap == 0: just empties).
+ * Each form is a bit set (mirrored in _lib.py GEMM_FORM_*): 1 fragment-image kernel (nf4 / fp4 / fp8 weights), 2 K slices
+ * (split-K), 4 three-product fp32-class form, 8 hand-scheduled K loop, 16 half-tile ring layout, 32 256-row tiles,
+ * 64 raw-A rows. Lets a test assert which kernel its shape ran. */
+WOQ_API int woq_gemm_form_log(int* forms, int cap);
 
 #ifdef __cplusplus
 }

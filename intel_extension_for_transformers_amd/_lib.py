@@ -80,8 +80,11 @@ EXPORTS = [
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
     "woq_engine_set_attn_chunk", "woq_engine_attn_chunk", "woq_engine_time_gemv", "woq_engine_time_gemv_mask",
-    "woq_engine_time_twin", "woq_engine_set_time_eager", "woq_engine_time_prefill_gemm",
+    "woq_engine_time_twin", "woq_engine_set_time_eager", "woq_engine_time_prefill_gemm", "woq_gemm_form_log",
 ]
+# woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
+GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
+GEMM_FORM_RING, GEMM_FORM_TALL, GEMM_FORM_RAW = 16, 32, 64
 
 _lib = None
 
@@ -150,6 +153,7 @@ def lib():
     L.woq_engine_time_twin.argtypes = [vp, ci, ci, vp, ctypes.POINTER(cf)]
     L.woq_engine_set_tp_options.argtypes = [vp, ci, ci]
     L.woq_engine_time_prefill_gemm.argtypes = [vp, ci, ci, ci, vp, ctypes.POINTER(cf), ctypes.POINTER(cf)]
+    L.woq_gemm_form_log.argtypes = [ctypes.POINTER(ci), ci]
     L.woq_comm_create.argtypes = [ci, ci, cs, ctypes.POINTER(vp)]
     L.woq_comm_handle.argtypes = [vp, vp, cs]
     L.woq_comm_connect.argtypes = [vp, vp, ctypes.POINTER(ci)]
@@ -165,6 +169,14 @@ def lib():
     L.woq_engine_token_log_ptr.argtypes = [vp]
     _lib = L
     return L
+
+
+def gemm_form_log():
+    """The forms (GEMM_FORM_* bit sets) of the prefill-GEMM launches since the last call, oldest first (at most 64
+    kept); empties the log."""
+    buf = (ctypes.c_int * 64)()
+    n = lib().woq_gemm_form_log(buf, 64)
+    return list(buf[:min(n, 64)])
 
 
 def check(rc):

@@ -41,12 +41,37 @@
 #include <mutex>
 #include <type_traits>
 
+#include "../../include/woq_hip_experimental.h"
 #include "woq_device.h"
 #include "woq_launch.h"
 
 namespace woq {
 static hipEvent_t g_gemm_ev0 = nullptr, g_gemm_ev1 = nullptr;
 
+// forms of the recent launch_gemm_f16 calls (woq_gemm_form_log, include/woq_hip_experimental.h; bits mirrored in
+// _lib.py): what the selector picked, so that a test can tell which kernel its shape ran
+enum : int {
+  GEMM_FORM_FRAG = 1,        // fragment-image kernel (table / fp8 weights)
+  GEMM_FORM_SPLITK = 2,      // K slices
+  GEMM_FORM_FP32 = 4,        // three-product fp32-class form
+  GEMM_FORM_HANDSCHED = 8,   // hand-scheduled K loop (woq_gemm_f16p.h / woq_gemm_f16t.h)
+  GEMM_FORM_RING = 16,       // half-tile ring layout
+  GEMM_FORM_TALL = 32,       // 256-row tiles (woq_gemm_f16t.h)
+  GEMM_FORM_RAW = 64,        // raw-A rows
+};
+constexpr size_t FORM_LOG_CAP = 64;
+static std::mutex g_form_mu;
+static int g_form_log[FORM_LOG_CAP];
+static size_t g_form_n = 0;  // entries held (<= FORM_LOG_CAP), oldest first
+
+static void log_gemm_form(int form) {
+  std::lock_guard<std::mutex> lock(g_form_mu);
+  if (g_form_n == FORM_LOG_CAP) {  // full: the oldest entry goes
+    std::copy(g_form_log + 1, g_form_log + FORM_LOG_CAP, g_form_log);
+    --g_form_n;
+  }
+  g_form_log[g_form_n++] = form;
+}
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -908,12 +933,14 @@ static int launch_f16frag_t(GemmF16Args& a, hipStream_t st) {
 #include "woq_gemm_f16p.h"
 #include "woq_gemm_f16t.h"
 
+// `form` (host side, not a kernel argument): ORs in GEMM_FORM_HANDSCHED / _RING / _TALL for the kernel it picks
 template <int SMODE, bool ASYM, bool S32, int NP>
-static int launch_f16_t(GemmF16Args& a, hipStream_t st) {
+static int launch_f16_t(GemmF16Args& a, hipStream_t st, int& form) {
   auto kern = gemm_f16s_kernel<SMODE, ASYM, S32, NP, 2>;
   bool ring = false;
 #if WOQ_GEMM_HANDSCHED
   if (NP == 1 && (a.tiles_k & 1) == 0 && a.kper == 0) {  // (K slices run the kernel above: its K loop takes a range)  // (its K loop runs two K steps per trip; odd tile counts keep the kernel above)
+    form |= GEMM_FORM_HANDSCHED;
     // (the ring form needs <= 168 VGPRs for its third workgroup per CU; group-32 asymmetric blobs with fp32 scales do
     // not fit without spills and stay on the two-tile form)
     constexpr bool ring_fits = !(SMODE == 1 && ASYM && S32);
@@ -928,6 +955,7 @@ static int launch_f16_t(GemmF16Args& a, hipStream_t st) {
     if (!ring)
       kern = a.act_raw ? WOQ_PICK(true, false) : WOQ_PICK(false, false);
 #undef WOQ_PICK
+    if (ring) form |= GEMM_FORM_RING;
   }
 #endif
   int LDS = ring ? 3 * (FTILE_BYTES / 2) : 2 * FTILE_BYTES * (NP == 1 ? 1 : 2);
@@ -947,6 +975,7 @@ static int launch_f16_t(GemmF16Args& a, hipStream_t st) {
     // against 82 us for the 128-row tiles, profiles/r06h_*)
     if (tall_ok && ring && a.M >= tall_rows && ((a.nb_m + 1) / 2) * a.nb_n >= tall_wgs && (tall_raw || !a.act_raw)) {
       tall = true;
+      form |= GEMM_FORM_TALL;
 #define WOQ_PICK_T(RAW_)                                                                   \
   (S32 ? gemm_f16t_kernel<SMODE, ASYM, 2, RAW_>                                            \
        : (a.scale_type == WOQ_BF16 ? gemm_f16t_kernel<SMODE, ASYM, 1, RAW_> : gemm_f16t_kernel<SMODE, ASYM, 0, RAW_>))
@@ -1123,6 +1152,8 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   const int sm = (int)h.scale_mode;
   const bool s32 = h.scale_type == WOQ_F32;
   int rc = 1;
+  int form = (frag ? GEMM_FORM_FRAG : 0) | (kper ? GEMM_FORM_SPLITK : 0) | (fp32_class ? GEMM_FORM_FP32 : 0) |
+             (raw ? GEMM_FORM_RAW : 0);
   if (frag) {
     DeqFragArgs d;
     d.q = a.q, d.q_lo = (const u32x4*)fp8_lo, d.scales = a.scales, d.scale_type = a.scale_type, d.scale_mode = sm, d.n_groups = h.n_groups;
@@ -1132,10 +1163,10 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
     hipLaunchKernelGGL(deq_frag_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, d);
     rc = fp32_class ? launch_f16frag_t<3>(a, st) : launch_f16frag_t<1>(a, st);
   } else {
-#define WOQ_F16_CASE(SM, AS)                                                                   \
-  if (sm == SM && asym == AS)                                                                   \
-    rc = fp32_class ? (s32 ? launch_f16_t<SM, AS, true, 3>(a, st) : launch_f16_t<SM, AS, false, 3>(a, st))  \
-                    : (s32 ? launch_f16_t<SM, AS, true, 1>(a, st) : launch_f16_t<SM, AS, false, 1>(a, st));
+#define WOQ_F16_CASE(SM, AS)                                                                                  \
+  if (sm == SM && asym == AS)                                                                                 \
+    rc = fp32_class ? (s32 ? launch_f16_t<SM, AS, true, 3>(a, st, form) : launch_f16_t<SM, AS, false, 3>(a, st, form)) \
+                    : (s32 ? launch_f16_t<SM, AS, true, 1>(a, st, form) : launch_f16_t<SM, AS, false, 1>(a, st, form));
   WOQ_F16_CASE(0, false)
   WOQ_F16_CASE(0, true)
   WOQ_F16_CASE(1, false)
@@ -1151,6 +1182,7 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   }
   if (g_gemm_ev1) hipEventRecord(g_gemm_ev1, st);
   if (mine) scratch_release(w, total, own, st);
+  if (rc == 0) log_gemm_form(form);
   return rc;
 }
 
@@ -1162,3 +1194,11 @@ void set_gemm_time_events(hipEvent_t before, hipEvent_t after) {
 }
 
 }  // namespace woq
+
+extern "C" WOQ_API int woq_gemm_form_log(int* forms, int cap) {
+  std::lock_guard<std::mutex> lock(woq::g_form_mu);
+  const int n = (int)woq::g_form_n;
+  if (forms != nullptr && cap > 0) std::copy(woq::g_form_log, woq::g_form_log + std::min(n, cap), forms);
+  woq::g_form_n = 0;
+  return n;
+}

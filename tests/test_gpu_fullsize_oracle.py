@@ -224,10 +224,12 @@ def _sampled_rows(M, n, rng):
 @pytest.mark.parametrize("group,asym", [(128, False), (32, True)])
 @pytest.mark.parametrize("act_dtype", [torch.float32, torch.float16])
 def test_prefill_gemm_at_measured_size_vs_oracle(name, K, N, group, asym, act_dtype, M=8192):
-    """The prompt pass's one-product MFMA GEMM (compute "bf16": hand-scheduled ring kernel, 8 x 8 super-tile mapping
-    live from M = 1024, fp16 rows fetched raw) at the M the bench line measures, every Llama-2-7B projection, both
-    BASELINE quantisation variants: 64 sampled rows against oracle.woq_linear on the same blob. The reference's own
-    test compares at m = 256 (qbits_ut/test_weightonly.py:51-88); bound 2e-3 * rowmax (fp16-operand products)."""
+    """The prompt pass's one-product MFMA GEMM (compute "bf16") at the M the bench line measures, every Llama-2-7B
+    projection, both BASELINE quantisation variants: fp32 rows run the 256-row tiles (csrc/woq_gemm_f16t.h, packed A),
+    fp16 rows the 128-row ring kernel fetching them raw (raw-A 256-row tiles are off by default); 8 x 8 super-tile
+    mapping. 64 sampled rows against oracle.woq_linear on the same blob. The reference's own test compares at m = 256
+    (qbits_ut/test_weightonly.py:51-88); bound 2e-3 * rowmax (fp16-operand products)."""
+    from intel_extension_for_transformers_amd import _lib as L
     from intel_extension_for_transformers_amd import qbits
 
     rng = np.random.default_rng(K + N + group + M)
@@ -239,8 +241,11 @@ def test_prefill_gemm_at_measured_size_vs_oracle(name, K, N, group, asym, act_dt
     g = torch.Generator(device="cuda").manual_seed(K + M)
     x = torch.randn(M, K, generator=g, device="cuda", dtype=torch.float32).to(act_dtype)
     out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.float32)
+    L.gemm_form_log()
     qbits.woq_linear(x, blob, torch.empty(0), out, "bf16", "int4_clip", "fp16", asym)
     torch.cuda.synchronize()
+    ring = L.GEMM_FORM_HANDSCHED | L.GEMM_FORM_RING
+    assert L.gemm_form_log() == [ring | (L.GEMM_FORM_RAW if act_dtype == torch.float16 else L.GEMM_FORM_TALL)]
     assert not torch.isnan(out).any(), "output elements left unwritten"
     rows = _sampled_rows(M, 64, rng)
     got = out[rows].cpu().numpy()
@@ -252,14 +257,19 @@ def test_prefill_gemm_at_measured_size_vs_oracle(name, K, N, group, asym, act_dt
 @pytest.mark.parametrize("M", [2048, 2148, 2213, 4096 + 129])
 @pytest.mark.parametrize("group,asym", [(128, False), (32, True)])
 @pytest.mark.parametrize("act_dtype", [torch.float32, torch.float16])
-def test_prefill_gemm_256_row_tiles_ragged_rows_vs_oracle(M, group, asym, act_dtype):
+def test_prefill_gemm_256_row_tiles_ragged_rows_vs_oracle(M, group, asym, act_dtype, N=384):
     """Round 6: from 2048 rows the one-product GEMM runs 256-row workgroup tiles (csrc/woq_gemm_f16t.h: two 128-row
-    half-tile images per LDS slot, packed and raw-A forms). Row counts that end inside the first image of the last
+    half-tile images per LDS slot) once ceil(row blocks / 2) x column blocks >= 1024. At N = 384 (3 column blocks)
+    these row counts stay on the 128-row ring kernel; the N = 22016 twin below (172 column blocks) runs the 256-row
+    tiles with fp32 rows. fp16 rows take the ring kernel raw at both widths (raw-A 256-row tiles are off by default).
+    Row counts that end inside the first image of the last
     workgroup (2148: its second image does not exist and is clamped), inside its second image (2213), on a tile edge
-    (2048) and one past a 128-row edge (4225); EVERY row against oracle.woq_linear, NaN-poisoned output first."""
+    (2048) and one past a 128-row edge (4225); EVERY row against oracle.linear_rows, NaN-poisoned output first, the
+    kernel form asserted."""
+    from intel_extension_for_transformers_amd import _lib as L
     from intel_extension_for_transformers_amd import qbits
 
-    K, N = 512, 384
+    K = 512
     rng = np.random.default_rng(M + group)
     q, s, z = _host_qsz(rng, K, N, group, asym)
     e8, e32 = torch.empty(0, dtype=torch.int8), torch.empty(0, dtype=torch.int32)
@@ -269,13 +279,25 @@ def test_prefill_gemm_256_row_tiles_ragged_rows_vs_oracle(M, group, asym, act_dt
     g = torch.Generator(device="cuda").manual_seed(M)
     x = torch.randn(M, K, generator=g, device="cuda", dtype=torch.float32).to(act_dtype)
     out = torch.full((M + 3, N), float("nan"), device="cuda", dtype=torch.float32)  # three guard rows behind the result
+    L.gemm_form_log()
     qbits.woq_linear(x, blob, torch.empty(0), out[:M], "bf16", "int4_clip", "fp16", asym)
     torch.cuda.synchronize()
+    ring = L.GEMM_FORM_HANDSCHED | L.GEMM_FORM_RING
+    raw = act_dtype == torch.float16
+    assert L.gemm_form_log() == [ring | (L.GEMM_FORM_RAW if raw else L.GEMM_FORM_TALL if N == 22016 else 0)]
     assert not torch.isnan(out[:M]).any(), "output elements left unwritten"
     assert torch.isnan(out[M:]).all(), "rows past M were written"
-    ref = orc.woq_linear(x.float().cpu().numpy(), blob.cpu().numpy().view(np.uint8))
+    ref = orc.linear_rows(x.float().cpu().numpy(), blob.cpu().numpy().view(np.uint8))
     rel = (np.abs(out[:M].cpu().numpy() - ref).max(axis=1) / np.abs(ref).max(axis=1)).max()
     assert rel <= 2e-3, (M, group, asym, str(act_dtype), float(rel))
+
+
+@pytest.mark.parametrize("M", [2048, 2148, 2213, 4096 + 129])
+@pytest.mark.parametrize("group,asym", [(128, False), (32, True)])
+@pytest.mark.parametrize("act_dtype", [torch.float32, torch.float16])
+def test_prefill_gemm_256_row_tiles_ragged_rows_n22016_vs_oracle(M, group, asym, act_dtype):
+    """The test above at the gate/up width N = 22016, where fp32 rows select the 256-row kernel at these row counts."""
+    test_prefill_gemm_256_row_tiles_ragged_rows_vs_oracle(M, group, asym, act_dtype, N=22016)
 
 
 @pytest.mark.parametrize("group,asym", [(128, False), (32, True)])
