@@ -110,21 +110,13 @@ int woq_device_count(void) {
 static int linear_int4(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
                        const float* bias, void* out, int out_dtype, int ldo, int M, const float* residual, int ld_res,
                        hipStream_t st) {
-  static const bool gemm_as_gemv = getenv("WOQ_GEMM_AS_GEMV") != nullptr;  // A/B switches for tests
-  static const bool gemv_as_gemm = getenv("WOQ_GEMV_AS_GEMM") != nullptr;
   // 4-bit table weights (nf4 / fp4): M <= 8 the generic fp32 kernel (rows in chunks of 4); above, the MFMA GEMM over a
   // pre-dequantised fragment image of the weight (woq_gemm_f16.hip: deq_frag_kernel + gemm_f16frag_kernel)
-  static const bool table_generic = getenv("WOQ_TABLE_GENERIC") != nullptr;  // A/B switch: the round-2 behaviour
   // int4: up to 16 rows stay on the decode GEMV (four MFMA row sets over one pass of the weights, woq_gemv_i8.hip): the
   // MFMA GEMM has one 128-row block and a third of the chip's workgroups there (53-93 us at M = 16 for the Llama-2-7B
-  // projections against 14-44 us). WOQ_GEMV_MAX_ROWS=8 gives the round-2 seam back (same-box A/B runs).
-  static const int gemv_rows = [] {
-    const char* e = getenv("WOQ_GEMV_MAX_ROWS");
-    const int v = e ? atoi(e) : 16;
-    return v >= 1 && v <= 16 ? v : 16;
-  }();
-  const int seam = is_table_type(h.weight_type) ? 8 : gemv_rows;
-  if ((M > seam || gemv_as_gemm) && !gemm_as_gemv && !(is_table_type(h.weight_type) && (table_generic || M <= 8)))
+  // projections against 14-44 us).
+  const int seam = is_table_type(h.weight_type) ? 8 : 16;
+  if (M > seam)
     return launch_gemm_f16(act, act_dtype, lda, blob, h, bias, out, out_dtype, ldo, M, nullptr, 0.f, residual, ld_res, 0,
                            nullptr, h.compute_type == WOQ_C_FP32 ? 1 : 0, st);
   return launch_gemv_from_header(act, act_dtype, lda, blob, h, bias, out, out_dtype, ldo, M, nullptr, 0.f, residual,
@@ -167,8 +159,7 @@ int woq_linear(const void* act_dev, int act_dtype, int lda, const void* blob_dev
                               hdr->compute_type, hdr->off_shuffle != 0) == 0, "QBits: corrupt fp8 header");
     const uint8_t* bhi = (const uint8_t*)blob_dev + hdr->off_q;
     const uint8_t* blo = (const uint8_t*)blob_dev + hdr->off_scale;
-    static const bool fp8_generic = getenv("WOQ_TABLE_GENERIC") != nullptr;  // A/B switch: the round-2 behaviour
-    if (M > 8 && !fp8_generic)  // the MFMA GEMM over a pre-dequantised fragment image (woq_gemm_f16.hip)
+    if (M > 8)  // the MFMA GEMM over a pre-dequantised fragment image (woq_gemm_f16.hip)
       rc = launch_gemm_f16(act_dev, act_dtype, lda, bhi, hi, bias_dev, out_dev, out_dtype, ldo, M, nullptr, 0.f, nullptr, 0,
                            0, nullptr, hdr->compute_type == WOQ_C_FP32 ? 1 : 0, st, blo + lo.off_q, hdr->weight_type);
     else

@@ -6,12 +6,10 @@
 #include "woq_device.h"
 #include "woq_xq.h"
 
-// polling interval of a wave that re-reads its granules, in units of 64 clocks (A/B builds: r06ap)
-#ifndef WOQ_ATTN_POLL_SLEEP
-#define WOQ_ATTN_POLL_SLEEP 2
-#endif
-
 namespace woq {
+
+// polling interval of a wave that re-reads its granules, in units of 64 clocks (0 / 2 / 8 measured alike: r06ap)
+constexpr int ATTN_POLL_SLEEP = 2;
 
 // Single-query attention for one new token: one workgroup (4 waves) per query head.
 //   qkv: fp32 [(heads + 2*kv_heads) * HD] un-rotated projections of the new token.
@@ -59,18 +57,19 @@ struct AttnGranule {
 // (part_g) and finalise the head's XQ blocks themselves (woq_attn_merge.h, all-to-all merge; at most 16 slices here).
 constexpr int ATTN_A2A_MAX_SLICES = 16;
 
-// Who runs the body. AttnWgEnv: a 256-thread workgroup of its own (the standalone and the fused launches) — thread ids
-// are the workgroup's, the two meeting points are workgroup barriers, the result leaves as fp32 (+ its XQ block).
-// The persistent token kernel (woq_persist.hip) runs the body on four of its consumer waves with its own environment:
-// sub-workgroup meeting points on an LDS counter (its loader wave never reaches an s_barrier) and tagged granules out.
-struct AttnWgEnv {
-  float* out;
-  XqPtrs xo;
-  XqPub pub;
-  __device__ __forceinline__ int tid() const { return (int)threadIdx.x; }
-  __device__ __forceinline__ void sync() const { __syncthreads(); }
+// One 256-thread workgroup runs the body (the standalone and the fused launches): the two meeting points are workgroup
+// barriers, the result leaves as fp32 in `out` (+ its XQ block in `xo`, published through `pub` when an o_proj
+// workgroup of the same launch may be waiting for it).
+// `h`: query head of this workgroup, `slice` / `n_slices`: its part of the cached positions (SPLIT), `sm`: LDS base
+template <typename KV, int HD, bool SPLIT, typename SRC>
+__device__ __forceinline__ void attn_decode_body(float* sm, int h, int slice, int n_slices, const SRC& src,
+                                                 KV* __restrict__ kcache, KV* __restrict__ vcache,
+                                                 const int32_t* __restrict__ pos_p, const float* __restrict__ cs,
+                                                 const float* __restrict__ sn, int heads, int kv_heads, int window,
+                                                 int spw, float* __restrict__ out, const XqPtrs& xo,
+                                                 const XqPub& pub = XqPub{nullptr, 0u}) {
   // value `idx` of the attention output; called by whole 16-lane rows (idx & 15 == lane & 15)
-  __device__ __forceinline__ void put(float v, int idx) const {
+  auto put = [=](float v, int idx) {
     out[idx] = v;
     if (xo.limbs != nullptr) {  // the o_proj GEMV's XQ input: one block per 16-lane row
       if (pub.flag != nullptr)  // an o_proj workgroup of the SAME launch may be waiting for this block
@@ -78,22 +77,13 @@ struct AttnWgEnv {
       else
         xq_emit16<false>(v, xo, idx >> 4, idx & 15, pub);
     }
-  }
-};
-
-// `h`: query head of this workgroup, `slice` / `n_slices`: its part of the cached positions (SPLIT), `sm`: LDS base
-template <typename KV, int HD, bool SPLIT, typename SRC, typename ENV>
-__device__ __forceinline__ void attn_decode_env(float* sm, int h, int slice, int n_slices, const SRC& src,
-                                                KV* __restrict__ kcache, KV* __restrict__ vcache,
-                                                const int32_t* __restrict__ pos_p, const float* __restrict__ cs,
-                                                const float* __restrict__ sn, int heads, int kv_heads, int window,
-                                                int spw, float* __restrict__ out, const ENV& env) {
+  };
   typedef typename KvVec8<KV>::type kv8;
   constexpr int half = HD / 2;
   constexpr int DPL = HD / 4;   // dims per lane in the score phase (4 lanes per position)
   constexpr int LPR = HD / 8;   // lanes per row in the P.V phase
   constexpr int GP = 64 / LPR;  // positions per wave per P.V pass
-  const int tid = env.tid(), lane = tid & 63;
+  const int tid = (int)threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rep = heads / kv_heads, kh = h / rep;
   const int apos = pos_p[0];  // absolute position of the new token = number of cached positions
@@ -187,7 +177,7 @@ __device__ __forceinline__ void attn_decode_env(float* sm, int h, int slice, int
           if (lane == 0) atomicOr(src.status, 1);
           break;
         }
-        __builtin_amdgcn_s_sleep(WOQ_ATTN_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(ATTN_POLL_SLEEP);
       }
     } else {
       qa = src.qkv[oq], qb = src.qkv[oq + half];
@@ -220,7 +210,7 @@ __device__ __forceinline__ void attn_decode_env(float* sm, int h, int slice, int
             if (lane == 0) atomicOr(src.status, 1);
             break;
           }
-          __builtin_amdgcn_s_sleep(WOQ_ATTN_POLL_SLEEP);
+          __builtin_amdgcn_s_sleep(ATTN_POLL_SLEEP);
         }
       } else {
         ka = src.qkv[ok], kb = src.qkv[ok + half];
@@ -251,7 +241,7 @@ __device__ __forceinline__ void attn_decode_env(float* sm, int h, int slice, int
     }
   }
   if constexpr (SRC::granules)
-    env.sync();  // q is wave 0's to give
+    __syncthreads();  // q is wave 0's to give
   else
     __builtin_amdgcn_wave_barrier();
   // ---- scores of this wave's cached positions ----
@@ -380,7 +370,7 @@ __device__ __forceinline__ void attn_decode_env(float* sm, int h, int slice, int
   if constexpr (SRC::granules) {
     if (has_new) new_position();  // wave 0: the launch's k / v strips are the last thing this workgroup waits for
   }
-  env.sync();
+  __syncthreads();
   // ---- merge the four waves' partials ----
   if (tid < HD) {
     const float m0 = ml[0], m1 = ml[1], m2 = ml[2], m3 = ml[3];
@@ -407,7 +397,7 @@ __device__ __forceinline__ void attn_decode_env(float* sm, int h, int slice, int
         st_agent(pml + 1, den);
       }
     } else {
-      env.put(o / den, h * HD + tid);  // tid < HD is a whole number of 16-lane rows
+      put(o / den, h * HD + tid);  // tid < HD is a whole number of 16-lane rows
     }
   }
   if constexpr (SPLIT && SRC::granules) {
@@ -415,19 +405,8 @@ __device__ __forceinline__ void attn_decode_env(float* sm, int h, int slice, int
     const int R = wid * 4 + (lane >> 4), b = slice + R * n_slices;
     if (wid < 2 && slice < HD / 16)  // (wave-uniform: some row of this wave has a block)
       attn_a2a_finalize<HD, ATTN_A2A_MAX_SLICES>(AttnA2A{src.part_g, src.tag, src.status}, h, b, n_slices,
-                                                 b < HD / 16, [&](float v, int idx) { env.put(v, idx); });
+                                                 b < HD / 16, put);
   }
-}
-
-template <typename KV, int HD, bool SPLIT, typename SRC>
-__device__ __forceinline__ void attn_decode_body(float* sm, int h, int slice, int n_slices, const SRC& src,
-                                                 KV* __restrict__ kcache, KV* __restrict__ vcache,
-                                                 const int32_t* __restrict__ pos_p, const float* __restrict__ cs,
-                                                 const float* __restrict__ sn, int heads, int kv_heads, int window,
-                                                 int spw, float* __restrict__ out, const XqPtrs& xo,
-                                                 const XqPub& pub = XqPub{nullptr, 0u}) {
-  attn_decode_env<KV, HD, SPLIT>(sm, h, slice, n_slices, src, kcache, vcache, pos_p, cs, sn, heads, kv_heads, window,
-                                 spw, out, AttnWgEnv{out, xo, pub});
 }
 
 }  // namespace woq

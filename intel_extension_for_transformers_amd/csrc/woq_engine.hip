@@ -115,10 +115,10 @@ struct woq_engine {
   // the same step captured `graph_unroll` times in a row (the token / position chain lives on the device, so k steps are
   // one valid graph): a burst of n replays launches n / k of these and n % k single steps. Each hipGraphLaunch costs the
   // device a few us between tokens (eager bursts read +0.6 % over one-step replays, profiles/r05z_*); 8 steps per launch
-  // amortise it. WOQ_ENGINE_GRAPH_UNROLL=1 turns it off.
+  // amortise it.
   hipGraph_t graph_k = nullptr;
   hipGraphExec_t exec_k = nullptr;
-  int graph_unroll = 8;
+  static constexpr int graph_unroll = 8;
   woq_allreduce_fn allreduce = nullptr;
   void* allreduce_user = nullptr;
   // XQ decode path (woq_xq.h): activations travel between the step's kernels as limb blocks written by the
@@ -215,16 +215,6 @@ const woq::CommDev* woq_engine::tp_push() const {
 
 static const XqPtrs kNoXq = {nullptr, nullptr, nullptr};
 
-// WOQ_ENGINE_SKIP=<bit mask>: leave launches out of the XQ decode step — timing experiments only (the step's results
-// are then meaningless). bit 0 qkv, 1 attention, 2 o_proj, 3 gate/up, 4 down_proj, 5 head.
-static int engine_skip_mask() {
-  static const int m = [] {
-    const char* s = getenv("WOQ_ENGINE_SKIP");
-    return s ? atoi(s) : 0;
-  }();
-  return m;
-}
-
 // one batch-1 projection over an XQ vector
 static int engine_gemv_xq(woq_engine* e, const XqPtrs& xin, const void* blob, const woq_blob_header& h, float* out,
                           const float* ssq_in, const float* residual, int epi, const XqPtrs& xo,
@@ -249,10 +239,9 @@ static int engine_row_parallel_xq(woq_engine* e, const XqPtrs& xin, const void* 
 static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
   const woq_engine_config& c = e->cfg;
   const woq_layer_weights& w = e->layers[l];
-  const int skip = engine_skip_mask();
   int rc = 0;
   const int ns = e->attn_splits > 1 ? e->attn_splits : 1;  // context slices (round 6: attention workgroups of the fused launch)
-  if (!(skip & 3) && e->fused_attn_applies(w.qkv_hdr)) {
+  if (e->fused_attn_applies(w.qkv_hdr)) {
     rc = launch_gemv_xq_attn(e->xq_hidden, w.qkv_blob, w.qkv_hdr, e->qkv_g, e->ssq_part, c.rms_eps, e->step_seq, l,
                              e->fuse_status, e->kcache + (size_t)l * e->kv_layer_bytes,
                              e->vcache + (size_t)l * e->kv_layer_bytes,
@@ -260,20 +249,17 @@ static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
                              e->xq_attn, st, ns, e->attn_part_g);  // (slices merge among themselves: no combine launch)
     if (rc) return rc;
   } else {
-    if (!(skip & 1))
-      rc = engine_gemv_xq(e, e->xq_hidden, w.qkv_blob, w.qkv_hdr, e->qkv, e->ssq_part, nullptr, 0, kNoXq, nullptr,
-                          nullptr, st);
+    rc = engine_gemv_xq(e, e->xq_hidden, w.qkv_blob, w.qkv_hdr, e->qkv, e->ssq_part, nullptr, 0, kNoXq, nullptr,
+                        nullptr, st);
     if (rc) return rc;
     const AttnA2A a2a{e->attn_part_g, 0u, e->fuse_status};
-    if (!(skip & 2))
-      rc = launch_attn_decode(e->qkv, e->kcache + (size_t)l * e->kv_layer_bytes,
-                              e->vcache + (size_t)l * e->kv_layer_bytes, c.kv_dtype, e->pos, e->cs, e->sn, c.heads,
-                              c.kv_heads, c.head_dim, c.max_ctx, e->window, e->attn, e->attn_splits, e->attn_grouped,
-                              e->attn_part, e->xq_attn, st, e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk,
-                              e->grouped_a2a_ok() ? &a2a : nullptr, e->step_seq, l);
+    rc = launch_attn_decode(e->qkv, e->kcache + (size_t)l * e->kv_layer_bytes,
+                            e->vcache + (size_t)l * e->kv_layer_bytes, c.kv_dtype, e->pos, e->cs, e->sn, c.heads,
+                            c.kv_heads, c.head_dim, c.max_ctx, e->window, e->attn, e->attn_splits, e->attn_grouped,
+                            e->attn_part, e->xq_attn, st, e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk,
+                            e->grouped_a2a_ok() ? &a2a : nullptr, e->step_seq, l);
     if (rc) return rc;
   }
-  if (skip & 4) return 0;
   // hidden += attn . W_o ; the new hidden leaves as the MLP's XQ input (times ln2) with its sums of squares
   return engine_row_parallel_xq(e, e->xq_attn, w.o_blob, w.o_hdr, e->xq_hidden, w.ln2, e->ssq_part, st);
 }
@@ -281,13 +267,9 @@ static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
 static int engine_mlp_block_xq(woq_engine* e, int l, hipStream_t st) {
   const woq_engine_config& c = e->cfg;
   const woq_layer_weights& w = e->layers[l];
-  const int skip = engine_skip_mask();
-  int rc = 0;
-  if (!(skip & 8))
-    rc = engine_gemv_xq(e, e->xq_hidden, w.gate_up_blob, w.gate_up_hdr, nullptr, e->ssq_part, nullptr, 1, e->xq_act,
-                        nullptr, nullptr, st);
+  const int rc = engine_gemv_xq(e, e->xq_hidden, w.gate_up_blob, w.gate_up_hdr, nullptr, e->ssq_part, nullptr, 1,
+                                e->xq_act, nullptr, nullptr, st);
   if (rc) return rc;
-  if (skip & 16) return 0;
   const bool last = l + 1 == c.layers;  // the last layer's output feeds the head, which reads fp32
   return engine_row_parallel_xq(e, e->xq_act, w.down_blob, w.down_hdr, last ? kNoXq : e->xq_hidden,
                                 last ? nullptr : e->layers[l + 1].ln1, last ? nullptr : e->ssq_part, st);
@@ -335,11 +317,10 @@ static int engine_mlp_block(woq_engine* e, int l, hipStream_t st) {
 // fuse_next: this step's greedy argmax and the NEXT step's embedding kernel as one launch (steps chained inside one
 // captured graph; one GPU, greedy) — woq_ops.hip argmax_embed_kernel
 static bool engine_can_fuse_next(const woq_engine* e, int greedy) {
-  return greedy && e->cfg.tp_size <= 1 && e->comm == nullptr && !(engine_skip_mask() & 32);
+  return greedy && e->cfg.tp_size <= 1 && e->comm == nullptr;
 }
 static int engine_head(woq_engine* e, int greedy, hipStream_t st, bool fuse_next = false) {
   const woq_engine_config& c = e->cfg;
-  if (engine_skip_mask() & 32) return 0;
   launch_lm_head(e->hidden, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, e->logits,
                  greedy ? e->am_val : nullptr, greedy ? e->am_idx : nullptr, st);
   if (fuse_next) {
@@ -926,17 +907,12 @@ int woq_engine_capture(woq_engine* e, int greedy, void* stream) {
   if (rc) return rc;
   WOQ_HIP(ce);
   WOQ_HIP(hipGraphInstantiate(&e->exec, e->graph, nullptr, nullptr, 0));
-  {
-    const char* gu = getenv("WOQ_ENGINE_GRAPH_UNROLL");
-    if (gu) e->graph_unroll = std::max(1, std::min(32, atoi(gu)));
-  }
   // k chained steps as one graph — greedy chains only (a non-greedy step leaves the next token to the host) and never
   // with a host-side all-reduce callback in the step
-  if (greedy && e->graph_unroll > 1) {
+  if (greedy) {
     WOQ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    // interior token boundaries of the chain: argmax + next embedding in one launch (WOQ_ENGINE_FUSE_TAIL=0: off)
-    static const bool fuse_tail = !(getenv("WOQ_ENGINE_FUSE_TAIL") && getenv("WOQ_ENGINE_FUSE_TAIL")[0] == '0');
-    const bool fuse = fuse_tail && engine_can_fuse_next(e, greedy);
+    // interior token boundaries of the chain: argmax + next embedding in one launch
+    const bool fuse = engine_can_fuse_next(e, greedy);
     for (int i = 0; i < e->graph_unroll && rc == 0; ++i)
       rc = engine_step_impl(e, greedy, st, fuse ? ((i > 0 ? 1 : 0) | (i + 1 < e->graph_unroll ? 2 : 0)) : 0);
     ce = hipStreamEndCapture(st, &e->graph_k);

@@ -106,9 +106,6 @@ struct GemmF16Args {
   int ldp;
 };
 
-#ifndef WOQ_GEMM_HANDSCHED  // 1: the hand-scheduled K loop (woq_gemm_f16p.h) for NP = 1; 0: hipcc's schedule (A/B runs)
-#define WOQ_GEMM_HANDSCHED 1
-#endif
 constexpr int FBM = 128;
 constexpr int FTILE_BYTES = 128 * 128 * 2;
 
@@ -938,8 +935,9 @@ template <int SMODE, bool ASYM, bool S32, int NP>
 static int launch_f16_t(GemmF16Args& a, hipStream_t st, int& form) {
   auto kern = gemm_f16s_kernel<SMODE, ASYM, S32, NP, 2>;
   bool ring = false;
-#if WOQ_GEMM_HANDSCHED
-  if (NP == 1 && (a.tiles_k & 1) == 0 && a.kper == 0) {  // (K slices run the kernel above: its K loop takes a range)  // (its K loop runs two K steps per trip; odd tile counts keep the kernel above)
+  // the hand-scheduled K loop (woq_gemm_f16p.h) runs two K steps per trip: odd tile counts, and K slices (the kernel
+  // above takes a K range), keep the kernel above
+  if (NP == 1 && (a.tiles_k & 1) == 0 && a.kper == 0) {
     form |= GEMM_FORM_HANDSCHED;
     // (the ring form needs <= 168 VGPRs for its third workgroup per CU; group-32 asymmetric blobs with fp32 scales do
     // not fit without spills and stay on the two-tile form)
@@ -957,22 +955,20 @@ static int launch_f16_t(GemmF16Args& a, hipStream_t st, int& form) {
 #undef WOQ_PICK
     if (ring) form |= GEMM_FORM_RING;
   }
-#endif
   int LDS = ring ? 3 * (FTILE_BYTES / 2) : 2 * FTILE_BYTES * (NP == 1 ? 1 : 2);
   // round 6: 256-row workgroup tiles (woq_gemm_f16t.h) — the ring layout's half-tile images (or the raw rows), twice the
   // rows per wave, half the weight unpack per MFMA. From 2048 rows (below that the 128-row tiles fill the chip better);
   // WOQ_GEMM_TALL=0: off (A/B runs).
   [[maybe_unused]] bool tall = false;
-#if WOQ_GEMM_HANDSCHED
   if constexpr (NP == 1 && !(SMODE == 1 && ASYM && S32)) {
     static const bool tall_ok = !(getenv("WOQ_GEMM_TALL") && getenv("WOQ_GEMM_TALL")[0] == '0');
-    static const int tall_rows = getenv("WOQ_GEMM_TALL_ROWS") ? atoi(getenv("WOQ_GEMM_TALL_ROWS")) : 2048;
+    constexpr int tall_rows = 2048;
     // raw-A calls (o / down of the prompt pass) keep the 128-row ring kernel: alone they gain 2-7 % on 256-row tiles, inside
     // the engine's pass they lose (0.4915 vs 0.4975 with them on, profiles/r06i_*); WOQ_GEMM_TALL_RAW=1 turns them on
     static const bool tall_raw = getenv("WOQ_GEMM_TALL_RAW") && getenv("WOQ_GEMM_TALL_RAW")[0] == '1';
-    static const int tall_wgs = getenv("WOQ_GEMM_TALL_WGS") ? atoi(getenv("WOQ_GEMM_TALL_WGS")) : 1024;
     // enough 256-row workgroups for two full rounds of the chip's 512 slots (M = 2048 x N = 4096 is 256 of them: 132 us
     // against 82 us for the 128-row tiles, profiles/r06h_*)
+    constexpr int tall_wgs = 1024;
     if (tall_ok && ring && a.M >= tall_rows && ((a.nb_m + 1) / 2) * a.nb_n >= tall_wgs && (tall_raw || !a.act_raw)) {
       tall = true;
       form |= GEMM_FORM_TALL;
@@ -987,7 +983,6 @@ static int launch_f16_t(GemmF16Args& a, hipStream_t st, int& form) {
       LDS = 2 * FTILE_BYTES;
     }
   }
-#endif
   static const void* attr_set[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   static std::mutex attr_mu;  // (host threads launching concurrently)
@@ -1072,14 +1067,13 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   // split-K: a call of one or two row blocks launches a few dozen workgroups on 256 CUs (M = 64: o / down 32, qkv 96,
   // gate / up 172 — 43-93 us per call); K slices bring the grid to ~512 workgroups, one round at two per CU. Each
   // slice keeps >= 4 K tiles, an even count.
-  static const bool split_ok = !(getenv("WOQ_GEMM_SPLITK") && getenv("WOQ_GEMM_SPLITK")[0] == '0');
   int kper = 0, nz = 1;
   {
     const int wgs = a.nb_m * a.nb_n;
     // (measured on the Llama-2-7B prompt pass, 32 layers: 32 / 64 / 128 tokens 8.9 -> 5.6, 9.1 -> 6.0, 9.4 -> 6.6 ms;
     // at 512 tokens slicing the 128-workgroup o / down calls LOSES 10 %: the slices run the compiler-scheduled kernel
     // and pay the partials' round trip, so beyond one row block only really small grids are sliced)
-    if (split_ok && !frag && wgs <= (a.nb_m == 1 ? 256 : 64) && a.tiles_k >= 8) {
+    if (!frag && wgs <= (a.nb_m == 1 ? 256 : 64) && a.tiles_k >= 8) {
       int want = std::min(16, std::max(2, 512 / wgs));
       kper = std::max(4, ((a.tiles_k + want - 1) / want + 1) & ~1);
       nz = (a.tiles_k + kper - 1) / kper;
@@ -1111,16 +1105,14 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
 
   // raw-A form: fp16 rows that need no gather, no RMSNorm and no rescale go to the hand-scheduled kernel as they are
   // (the o_proj / down_proj calls of the prompt pass); only the column scales are computed here
-  static const bool raw_ok = !(getenv("WOQ_GEMM_RAW_A") && getenv("WOQ_GEMM_RAW_A")[0] == '0');
-  const bool raw = WOQ_GEMM_HANDSCHED && raw_ok && !frag && !kper && !fp32_class && act_dtype == WOQ_F16 && norm_w == nullptr &&
+  const bool raw = !frag && !kper && !fp32_class && act_dtype == WOQ_F16 && norm_w == nullptr &&
                    h.off_shuffle == 0 && (h.K & 127) == 0 && ((h.Kpad / WOQ_TILE_K) & 1) == 0 && (lda & 7) == 0 &&
                    (((uintptr_t)act) & 15) == 0 && (size_t)M * lda * 2 < ((size_t)1 << 32);
   a.act_raw = raw ? act : nullptr;
   a.lda = lda;
   if (raw) a.rs = nullptr;
-  static const bool ring_ok = !(getenv("WOQ_GEMM_RING") && getenv("WOQ_GEMM_RING")[0] == '0');
   const bool ring_fits = !(h.scale_mode == 1 && a.zp != nullptr && h.scale_type == WOQ_F32);  // (launch_f16_t: VGPRs)
-  a.ring = (WOQ_GEMM_HANDSCHED && ring_ok && ring_fits && !frag && !kper && !fp32_class && ((h.Kpad / WOQ_TILE_K) & 1) == 0) ? 1 : 0;
+  a.ring = (ring_fits && !frag && !kper && !fp32_class && ((h.Kpad / WOQ_TILE_K) & 1) == 0) ? 1 : 0;
 
   PackF16Args p;
   p.planes = planes;

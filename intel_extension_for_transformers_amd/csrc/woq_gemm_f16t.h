@@ -23,27 +23,12 @@
 //   weights of tile kt + 2 requested, P3B (+ LDS-DMA of q1 + 2 -> slot 1).
 #pragma once
 // (included inside namespace woq)
-// development knock-outs (timing only, results are then garbage): bit 0 no LDS-DMA in the loop, bit 1 no workgroup
-// barriers in the loop, bit 2 no dequantisation VALU, bit 3 no vmcnt waits in the loop
-#ifndef WOQ_T_KNOCK
-#define WOQ_T_KNOCK 0
-#endif
 
 #define WOQ_T_RD(i) "ds_read_b128 %[a" WOQ_S_(i) "], %[ad] offset:%[ob]+2048*" WOQ_S_(i) "\n\t"
 // dequantisation of ONE fragment (blob word w -> q0..q3), the two element orders of woq_gemm_f16p.h
 #define WOQ_T_DB(k, src, m, g) "v_bitop3_b32 %[q" WOQ_S_(k) "], %[" src "], %[" g "], %[" m "] bitop3:0x6c\n\t"
 #define WOQ_T_DA(k, n) "v_pk_add_f16 %[q" WOQ_S_(k) "], %[q" WOQ_S_(k) "], %[" n "] op_sel_hi:[1,0]\n\t"
 #define WOQ_T_DM(k) "v_pk_mul_f16 %[q" WOQ_S_(k) "], %[q" WOQ_S_(k) "], %[r] op_sel_hi:[1,0]\n\t"
-#if WOQ_T_KNOCK & 4
-#define WOQ_T_V_P0 "v_mov_b32 %[y], 0\n\tv_mov_b32 %[q0], 0\n\tv_mov_b32 %[q1], 0\n\tv_mov_b32 %[q2], 0\n\tv_mov_b32 %[q3], 0\n\t"
-#define WOQ_T_V_P1 ""
-#define WOQ_T_V_P2 ""
-#define WOQ_T_V_P3 ""
-#define WOQ_T_V_P4 ""
-#define WOQ_T_V_P5 ""
-#define WOQ_T_V_P6 ""
-#define WOQ_T_V_P7 ""
-#else
 // packed-A order: 13 operations over the eight pairs
 #define WOQ_T_V_P0 "v_lshrrev_b32 %[y], 8, %[w]\n\t" WOQ_T_DB(0, "w", "ml", "gl")
 #define WOQ_T_V_P1 WOQ_T_DB(1, "w", "mh", "gh") WOQ_T_DB(2, "y", "ml", "gl")
@@ -53,7 +38,6 @@
 #define WOQ_T_V_P5 WOQ_T_DM(1)
 #define WOQ_T_V_P6 WOQ_T_DM(2)
 #define WOQ_T_V_P7 WOQ_T_DM(3)
-#endif
 // raw-A order: 14 operations
 #define WOQ_T_V_R0 "v_perm_b32 %[y], %[w], %[w], %[s1]\n\tv_perm_b32 %[z], %[w], %[w], %[s2]\n\t"
 #define WOQ_T_V_R1 WOQ_T_DB(0, "y", "ml", "gl") WOQ_T_DB(1, "z", "ml", "gl")
@@ -82,7 +66,7 @@
 // acc: the sixteen accumulators of this block's eight row tiles; af: their A fragments on entry (possibly in flight),
 // on exit the next block's (in flight), read from LDS address `ad` + OB + 2048 i; bc0 / bc1: this part's weight
 // fragments; bn: ONE fragment of the next part, dequantised here from the blob word w with scales f.
-// DMA: 1 = this block carries the eight LDS-DMA pieces of a half-tile; 2 (packed form, WOQ_T_SPLIT_DMA) = the four
+// DMA: 1 = this block carries the eight LDS-DMA pieces of a half-tile; 2 (packed form, WOQ_TSTEP_SPLIT) = the four
 // pieces of ONE 128-row image (g0 / m0a: its source and LDS base), one per two pairs.
 template <int OB, int DMA, bool RAW>
 __device__ __forceinline__ void gemm_tblock(float4_t (&acc)[8][2], h8 (&af)[8], const u32x4& bc0, const u32x4& bc1,
@@ -100,7 +84,7 @@ __device__ __forceinline__ void gemm_tblock(float4_t (&acc)[8][2], h8 (&af)[8], 
 #define WOQ_T_INPUTS                                                                                                 \
   [b0] "v"(bc0), [b1] "v"(bc1), [ad] "v"(ad), [ob] "n"(OB), [w] "v"(w), [ml] "s"(k.ml), [mh] "s"(k.mh),            \
       [gl] "v"(k.gl), [gh] "v"(k.gh), [r] "v"(f.r), [nl] "v"(f.nl), [nh] "v"(f.nh)
-  if constexpr (DMA == 1 && !RAW && !(WOQ_T_KNOCK & 1)) {
+  if constexpr (DMA == 1 && !RAW) {
     uint32_t keep;
     asm volatile("s_mov_b32 %[km], m0\n\t" WOQ_TBLOCK_TEXT(
                      P, "s_mov_b32 m0, %[m0a]\n\ts_nop 0\n\t" WOQ_DMA0("g0", 0), WOQ_DMA0("g0", 1024),
@@ -109,7 +93,7 @@ __device__ __forceinline__ void gemm_tblock(float4_t (&acc)[8][2], h8 (&af)[8], 
                  : WOQ_T_OPERANDS, [km] "=&s"(keep)
                  : WOQ_T_INPUTS, [gv] "v"(gv), [g0] "s"(g0), [g1] "s"(g1), [m0a] "s"(m0a), [m0b] "s"(m0b)
                  : "memory");
-  } else if constexpr (DMA == 2 && !RAW && !(WOQ_T_KNOCK & 1)) {
+  } else if constexpr (DMA == 2 && !RAW) {
     uint32_t keep;
     asm volatile("s_mov_b32 %[km], m0\n\t" WOQ_TBLOCK_TEXT(P, "s_mov_b32 m0, %[m0a]\n\ts_nop 0\n\t" WOQ_DMA0("g0", 0), "",
                                                            WOQ_DMA0("g0", 1024), "", WOQ_DMA0("g0", 2048), "",
@@ -117,7 +101,7 @@ __device__ __forceinline__ void gemm_tblock(float4_t (&acc)[8][2], h8 (&af)[8], 
                  : WOQ_T_OPERANDS, [km] "=&s"(keep)
                  : WOQ_T_INPUTS, [gv] "v"(gv), [g0] "s"(g0), [m0a] "s"(m0a)
                  : "memory");
-  } else if constexpr (DMA == 1 && RAW && !(WOQ_T_KNOCK & 1)) {
+  } else if constexpr (DMA == 1 && RAW) {
     uint32_t keep;
     asm volatile("s_mov_b32 %[km], m0\n\t" WOQ_TBLOCK_TEXT(R, "s_mov_b32 m0, %[m0a]\n\ts_nop 0\n\t" WOQ_T_DMAR(0, "0x400"),
                                                            WOQ_T_DMAR(1, "0x400"), WOQ_T_DMAR(2, "0x400"),
@@ -363,16 +347,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f16t_kernel(GemmF16Args a) {
   for (int rt = 0; rt < 8; ++rt) af[rt] = *(const h8*)(fsm + rt * 2048 + (a_adp0 - lds0));
   dequant_first();
 
-#if WOQ_T_KNOCK & 8
-#define WOQ_T_WAIT_BAR() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-#define WOQ_T_WAIT_BAR() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-#if WOQ_T_KNOCK & 2
-#define WOQ_T_BARRIER()
-#else
-#define WOQ_T_BARRIER() __syncthreads();
-#endif
   // One K step. Weight word j of a tile = its part j. bq[set]: set 0 holds the fragments of even parts, set 1 of odd.
 #define WOQ_TSTEP_ALL(BCUR, FCUR, BNXT, FNXT, KT)                                                                           \
   {                                                                                                                    \
@@ -385,9 +359,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16t_kernel(GemmF16Args a) {
     /* part 1 (slot 0): next = part 2 (slot 1), word 2 */                                                               \
     gemm_tblock<HT, 0, RAW>(accA, af, bfrag(1, 0), bfrag(1, 1), bq[0][0], a_adp(1, 0), BCUR.wv[0][2], pk,           \
                                 FCUR[0][NS - 1], 0, nullptr, nullptr, 0, 0, ro);                                        \
-    WOQ_T_WAIT_BAR() /* q1 (my pieces) landed; my reads of slot 0 done */                                               \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); /* q1 (my pieces) landed; my reads of slot 0 done */    \
     tie_b(BNXT);                                                                                                        \
-    WOQ_T_BARRIER() /* X: q1 complete, slot 0 free */                                                                   \
+    __syncthreads(); /* X: q1 complete, slot 0 free */                                                                  \
     gemm_tblock<0, 1, RAW>(accB, af, bfrag(1, 0), bfrag(1, 1), bq[0][1], a_adp(0, 1), BCUR.wv[1][2], pk,             \
                               FCUR[1][NS - 1], lane16, srcA(min(q0 + 2, qlast)), srcB(min(q0 + 2, qlast)), dma_dst,     \
                               dma_dst + HT, ro);                                                                        \
@@ -400,8 +374,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16t_kernel(GemmF16Args a) {
     prep(BNXT, FNXT);                                                                                                   \
     gemm_tblock<HT, 0, RAW>(accA, af, bfrag(1, 0), bfrag(1, 1), bq[0][0], a_adp(1, 1), BNXT.wv[0][0], pk,           \
                                 FNXT[0][0], 0, nullptr, nullptr, 0, 0, ro);                                             \
-    WOQ_T_WAIT_BAR() /* q0 + 2 landed; my reads of slot 1 done */                                                       \
-    WOQ_T_BARRIER() /* Y: q0 + 2 complete, slot 1 free */                                                               \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); /* q0 + 2 landed; my reads of slot 1 done */            \
+    __syncthreads(); /* Y: q0 + 2 complete, slot 1 free */                                                              \
     load_b(min((KT) + 2, last), BCUR);                                                                                  \
     gemm_tblock<0, 1, RAW>(accB, af, bfrag(1, 0), bfrag(1, 1), bq[0][1], a_adp(0, 0), BNXT.wv[1][0], pk,             \
                               FNXT[1][0], lane16, srcA(min(q0 + 3, qlast)), srcB(min(q0 + 3, qlast)), dma_dst + SLOT,   \
@@ -420,9 +394,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16t_kernel(GemmF16Args a) {
     /* part 1 (slot 0): next = part 2 (slot 1), word 2 */                                                               \
     gemm_tblock<HT, 0, RAW>(accA, af, bfrag(1, 0), bfrag(1, 1), bq[0][0], a_adp(1, 0), BCUR.wv[0][2], pk,           \
                                 FCUR[0][NS - 1], 0, nullptr, nullptr, 0, 0, ro);                                        \
-    WOQ_T_WAIT_BAR() /* q1 (my pieces) landed; my reads of slot 0 done */                                               \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); /* q1 (my pieces) landed; my reads of slot 0 done */    \
     tie_b(BNXT);                                                                                                        \
-    WOQ_T_BARRIER() /* X: q1 complete, slot 0 free */                                                                   \
+    __syncthreads(); /* X: q1 complete, slot 0 free */                                                                  \
     gemm_tblock<0, 2, RAW>(accB, af, bfrag(1, 0), bfrag(1, 1), bq[0][1], a_adp(0, 1), BCUR.wv[1][2], pk,                \
                            FCUR[1][NS - 1], lane16, srcA(min(q0 + 2, qlast)), nullptr, dma_dst, 0, ro);                 \
     /* part 2 (slot 1): next = part 3, word 3 */                                                                        \
@@ -434,16 +408,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f16t_kernel(GemmF16Args a) {
     prep(BNXT, FNXT);                                                                                                   \
     gemm_tblock<HT, 0, RAW>(accA, af, bfrag(1, 0), bfrag(1, 1), bq[0][0], a_adp(1, 1), BNXT.wv[0][0], pk,           \
                                 FNXT[0][0], 0, nullptr, nullptr, 0, 0, ro);                                             \
-    WOQ_T_WAIT_BAR() /* q0 + 2 landed; my reads of slot 1 done */                                                       \
-    WOQ_T_BARRIER() /* Y: q0 + 2 complete, slot 1 free */                                                               \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); /* q0 + 2 landed; my reads of slot 1 done */            \
+    __syncthreads(); /* Y: q0 + 2 complete, slot 1 free */                                                              \
     load_b(min((KT) + 2, last), BCUR);                                                                                  \
     gemm_tblock<0, 2, RAW>(accB, af, bfrag(1, 0), bfrag(1, 1), bq[0][1], a_adp(0, 0), BNXT.wv[1][0], pk,                \
                            FNXT[1][0], lane16, srcA(min(q0 + 3, qlast)), nullptr, dma_dst + SLOT, 0, ro);               \
   }
-#ifndef WOQ_T_SPLIT_DMA  // A/B builds: tools/mkvariant_gemm.sh nosplit -DWOQ_T_SPLIT_DMA=0 (+1.1 % on the dominant GEMM, r06j)
-#define WOQ_T_SPLIT_DMA 1
-#endif
-  if constexpr (WOQ_T_SPLIT_DMA && !RAW) {
+  // the packed form splits its LDS-DMA (+1.1 % on the dominant GEMM against WOQ_TSTEP_ALL, r06j)
+  if constexpr (!RAW) {
     for (int kt = 0; kt < a.tiles_k; kt += 2) {  // tiles_k is even
       WOQ_TSTEP_SPLIT(B0, F0, B1, F1, kt)
       WOQ_TSTEP_SPLIT(B1, F1, B0, F0, kt + 1)

@@ -231,9 +231,8 @@ int launch_gemv_from_header(const void* act, int act_dtype, int lda, const void*
                             const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w,
                             float eps, const float* residual, int ld_res, int epi, int nt, hipStream_t st) {
   (void)nt;
-  static const bool force_generic = getenv("WOQ_GEMV_GENERIC") != nullptr;  // A/B switch for tests
   const size_t esz_a = act_dtype == WOQ_F32 ? 4 : 2, esz_o = out_dtype == WOQ_F32 ? 4 : 2;
-  int rows = force_generic ? 0 : gemv_tile_max_rows(act, act_dtype, lda, h, norm_w, epi, out_dtype);
+  int rows = gemv_tile_max_rows(act, act_dtype, lda, h, norm_w, epi, out_dtype);
   const bool tile = rows > 0 && !(h.off_shuffle != 0 && M > 1);  // act-order blobs: the tile kernel's gather form is batch-1
   if (!tile) {
     rows = GEN_MAXM;

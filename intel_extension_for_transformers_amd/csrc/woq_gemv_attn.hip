@@ -1,7 +1,7 @@
 // woq_gemv_attn.hip — [RMSNorm + qkv GEMV] and [RoPE + KV append + single-query attention] of a decode step in ONE
 // launch (round 3). Reference path replaced: qbits.cpp:113-140 at M = 1 followed by stock HF eager attention on the CPU.
 //
-// Why. Inside the captured decode step every launch costs ~2 us before it does anything (tools/xq_probe.hip: an empty
+// Why. Inside the captured decode step every launch costs ~2 us before it does anything (measured with an empty
 // kernel on the same grid, hipGraph replay: 1.7-2.4 us), and the batch-1 attention launch is a latency chain of 32
 // workgroups that costs 5.0 us per layer in place (profiles/r03g_skip_masks.txt) — most of it waiting for its own
 // first requests (position, cos / sin row, K / V rows) after the boundary. The qkv -> attention edge is the one edge of
@@ -45,20 +45,12 @@ struct FusedAttnArgs {
   unsigned long long* part_g;  // ns > 1: the slices' partials as tagged granules (woq_attn_decode.h attn_part_granule)
 };
 
-#ifndef WOQ_XQS_DEPTH
-#define WOQ_XQS_DEPTH 4
-#endif
 constexpr int FUSED_TPW = 8;
 // Round 6: the q strips of the fused launch are given the WHOLE slice as their window (8 tiles per wave up front) and the
 // k / v strips a shallower one, so that q lands while k / v are still streaming: the attention workgroups then run
 // everything over the cache on q alone (woq_attn_decode.h) and only the new position's score and value stand behind
-// the launch's last strips. A/B builds: -DWOQ_FUSED_DQ=4 -DWOQ_FUSED_DKV=4 is the round-5 order of arrival.
-#ifndef WOQ_FUSED_DQ
-#define WOQ_FUSED_DQ 8
-#endif
-#ifndef WOQ_FUSED_DKV
-#define WOQ_FUSED_DKV 1
-#endif
+// the launch's last strips. (Depth 4 for both is the round-5 order of arrival.)
+constexpr int FUSED_DQ = 8, FUSED_DKV = 1;
 // the fused launch's 14th argument dword: tpg_shift | flags << 8 | strips << 16 — the strip workgroups come first in the
 // grid, one attention workgroup per head behind them — so that the role test needs nothing but preloaded arguments
 // (gridDim is a hidden argument: it lives in the argument segment too)
@@ -101,11 +93,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void g
   }
   // (the K range always starts at tile 0 here: the kt_off slot of the preloaded dwords carries the number of q strips)
   if ((int)blockIdx.x < n_q_strips)
-    gemv_xqs_body<FUSED_TPW, 1, WOQ_FUSED_DQ, SMODE, ASYM, S32, true>(smem_raw, q, scales, xlimbs, xu, tiles_k, 0, base_tiles,
+    gemv_xqs_body<FUSED_TPW, 1, FUSED_DQ, SMODE, ASYM, S32, true>(smem_raw, q, scales, xlimbs, xu, tiles_k, 0, base_tiles,
                                                                      rem_tiles, n_groups, tpg_flags & 0xff,
                                                                      (tpg_flags >> 8) & 0xff, 4, xqs_late_ptr());
   else
-    gemv_xqs_body<FUSED_TPW, 1, WOQ_FUSED_DKV, SMODE, ASYM, S32, true>(smem_raw, q, scales, xlimbs, xu, tiles_k, 0, base_tiles,
+    gemv_xqs_body<FUSED_TPW, 1, FUSED_DKV, SMODE, ASYM, S32, true>(smem_raw, q, scales, xlimbs, xu, tiles_k, 0, base_tiles,
                                                                       rem_tiles, n_groups, tpg_flags & 0xff,
                                                                       (tpg_flags >> 8) & 0xff, 4, xqs_late_ptr());
 }

@@ -40,10 +40,7 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t make_rsrc(const void* p, int bytes) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, bytes, 0x00020000);
 }
-#ifndef WOQ_AUX_NT  // A/B builds: tools/mkvariant_xq.sh <name> -DWOQ_AUX_NT=0 (default cache policy on the weight stream)
-#define WOQ_AUX_NT 2
-#endif
-constexpr int AUX_NT = WOQ_AUX_NT;  // non-temporal: streamed-once weights
+constexpr int AUX_NT = 2;  // non-temporal: streamed-once weights
 
 // three limb sums (D rows 4m..4m+2) + sum of 16*q (row 4m+3) of one lane -> the exact integer
 // sum_k 16 q_k (Q_k - 2^22) rounded once to fp32, Q = 23-bit offset-binary activation:
@@ -73,15 +70,11 @@ struct LutArgs {
 template <int NDIG>
 __device__ __forceinline__ void lut_quad(const LutArgs& L, uint32_t idx, uint32_t (&out)[NDIG]) {
   const uint32_t sel = idx & 0x07070707u;
-#ifndef WOQ_LUT_ARITH_MASK
   // 0xff in every byte whose code is >= 8, from v_perm_b32's constant selectors: 0x05 picks byte 1 of the (zero) high
-  // source, 0x0d yields 0xff (ISA: selector 12 = 0x00, above = 0xff). Two instructions; the arithmetic form below takes
-  // three: +1.7 % / +2.1 % tokens/s for three / two planes at the 7B shape (profiles/r04ae_last_tree_summary.txt)
+  // source, 0x0d yields 0xff (ISA: selector 12 = 0x00, above = 0xff). Two instructions; the arithmetic form
+  // ((m8 << 5) - (m8 >> 3)) takes three: +1.7 % / +2.1 % tokens/s for three / two planes at the 7B shape
+  // (profiles/r04ae_last_tree_summary.txt)
   const uint32_t mask = __builtin_amdgcn_perm(0u, 0u, (idx & 0x08080808u) | 0x05050505u);
-#else
-  const uint32_t m8 = idx & 0x08080808u;
-  const uint32_t mask = (m8 << 5) - (m8 >> 3);
-#endif
 #pragma unroll
   for (int j = 0; j < NDIG; ++j) {
     const uint32_t lo = __builtin_amdgcn_perm(L.d[j][1], L.d[j][0], sel);  // {hi:lo} = table bytes 7..0

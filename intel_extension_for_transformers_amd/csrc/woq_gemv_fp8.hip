@@ -376,8 +376,7 @@ static bool fp8_geometry(int tiles_k, int& nw, int& tpw) {
 
 // Does the fp8-MFMA kernel take this call? `hi` = the HI plane's header (scales; the LO plane has the same geometry).
 bool gemv_fp8_mfma_supported(const void* act, int act_dtype, int lda, const woq_blob_header& hi) {
-  static const bool off = getenv("WOQ_FP8_GENERIC") != nullptr;  // A/B switch: the lookup kernel
-  if (off || hi.off_shuffle != 0 || hi.off_zp != 0 || hi.scale_mode > 1 || (hi.K & 3) != 0 || (lda & 3) != 0 ||
+  if (hi.off_shuffle != 0 || hi.off_zp != 0 || hi.scale_mode > 1 || (hi.K & 3) != 0 || (lda & 3) != 0 ||
       (((uintptr_t)act) & (act_dtype == WOQ_F32 ? 15 : 7)) != 0)
     return false;
   // scale_mode 0: per-128 groups or one group per column; scale_mode 1 (round 5): one scale per 32-k block (groups 32 / 64 / 96)

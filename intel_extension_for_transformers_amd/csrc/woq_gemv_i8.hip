@@ -32,7 +32,7 @@
 //  * a wave issues its activation-row loads first (they come back from L2 first: loads return in order), then
 //    all scale / zero-point loads and ALL of its weight tiles (buffer_load_dwordx4 nt, straight to VGPRs): the
 //    CU's miss queue holds ~16 KiB, so the wave may wait at issue, but queueing everything before the staging
-//    measured +2.3 % tokens/s over keeping only four tiles in flight (WOQ_PF below); every wait is a counted vmcnt;
+//    measured +2.3 % tokens/s over keeping only four tiles in flight (below); every wait is a counted vmcnt;
 //  * while the weights fly, the wave stages ONLY ITS OWN K slice of the activation rows into a wave-private
 //    LDS strip — no workgroup barrier, no full-vector dependency: RMSNorm is separable
 //    (out = rsqrt(mean(x^2)+eps) * (W . (x*g)): every wave adds its slice's sum of squares to the reduction
@@ -49,40 +49,6 @@
 
 #include "woq_gemv_common.h"
 
-// Probe hooks (tools/gemv_probe.hip compiles this file with WOQ_PROBE, plus WOQ_PROBE_STAMPS for the per-stage
-// timeline — the stamps cost ~300 cycles each, so timings are taken without them). Nothing in the product build.
-#ifdef WOQ_PROBE
-extern int g_probe_flags;
-#define WOQ_SKIP(bit) ((flags >> (bit)) & 1)  // experiment switches (bits 4..9 of flags)
-#else
-#define WOQ_SKIP(bit) false
-#endif
-#ifdef WOQ_PROBE_STAMPS
-extern __device__ unsigned long long* g_probe;
-#define WOQ_STAMP(k)                                                              \
-  do {                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    if (g_probe && lane == 0) {                                                   \
-      unsigned long long* slot_ = g_probe + ((size_t)blockIdx.x * 16 + wid) * 32; \
-      slot_[(k)] = clock64();                                                     \
-      if ((k) == 0) slot_[31] = wall_clock64();                                   \
-    }                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-  } while (0)
-#else
-#define WOQ_STAMP(k)
-#endif
-
-// weight-tile loads issued before the activation staging (the rest follow one per consumed tile, or right after the
-// staging with WOQ_REST_EARLY). Measured on the Llama-2-7B decode (tokens/s): 4 -> 721, 8 -> 729, 16 = everything up
-// front -> 740, 8 + rest-early -> 744 (= 16 for every projection but gate/up), 4 + rest-early -> 719: the earlier
-// the whole wave's loads are queued the better, even when the CU's miss queue makes the wave wait at issue.
-#ifndef WOQ_PF
-#define WOQ_PF 16
-#endif
-#ifndef WOQ_REST_EARLY
-#define WOQ_REST_EARLY 0
-#endif
 namespace woq {
 
 
@@ -167,7 +133,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
   const bool norm = norm_w != nullptr;
   const bool bf = (flags & 1) != 0, silu = (flags & 2) != 0;
   const int v16 = lane * 16;
-  WOQ_STAMP(0);
 
   // the thread's residual element (batch-1 form), fetched up front through a descriptor that is empty when
   // there is no residual: no branch, and the epilogue does not end on a dependent global load
@@ -187,12 +152,12 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
   const int xdt = (flags >> 2) & 3;
   auto load_row = [&](size_t row_off, float4_t (&xv)[XJ]) {
     if (xdt == 0) {
-      const rsrc_t rx = make_rsrc((const float*)x + row_off + kbase, WOQ_SKIP(7) ? 0 : xlen * 4);
+      const rsrc_t rx = make_rsrc((const float*)x + row_off + kbase, xlen * 4);
 #pragma unroll
       for (int j = 0; j < XJ; ++j)
         xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, v16 + j * 1024, 0, 0));
     } else {
-      const rsrc_t rx = make_rsrc((const uint16_t*)x + row_off + kbase, WOQ_SKIP(7) ? 0 : xlen * 2);
+      const rsrc_t rx = make_rsrc((const uint16_t*)x + row_off + kbase, xlen * 2);
 #pragma unroll
       for (int j = 0; j < XJ; ++j) {
         const uint2 r = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rx, lane * 8 + j * 512, 0, 0));
@@ -217,7 +182,7 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
     for (int j = 0; j < XJ; ++j) idv[j] = __builtin_amdgcn_raw_buffer_load_b128(ri, v16 + j * 1024, 0, 0);
     // chunk c = tid + j * threads (four elements each): K / 4 chunks <= XJ per thread (tiles <= nw * TPW)
     const int nthr = (int)blockDim.x;
-    const rsrc_t rxa = make_rsrc(x, WOQ_SKIP(7) ? 0 : K * (xdt == 0 ? 4 : 2));
+    const rsrc_t rxa = make_rsrc(x, K * (xdt == 0 ? 4 : 2));
     const rsrc_t rga = make_rsrc(norm ? (const void*)norm_w : x, norm ? K * 4 : 0);
 #pragma unroll
     for (int j = 0; j < XJ; ++j) {
@@ -243,9 +208,8 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
     for (int j = 0; j < XJ; ++j)
       gv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rg, v16 + j * 1024, 0, 0));
   }
-  WOQ_STAMP(1);
 
-  // ---- 1. scales / zero points, then the first PF weight tiles ----
+  // ---- 1. scales / zero points, then all of the weight tiles ----
   u32x4 w[CB][TPW];
   typename RawSc<SMODE, S32>::type rsc[CB][TPW];
   uint32_t rzp[CB][TPW];
@@ -281,8 +245,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
       }
     }
   }
-  WOQ_STAMP(2);
-  constexpr int PF = WOQ_PF;
   rsrc_t rq[CB];
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb)
@@ -291,9 +253,12 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
     const int t = i / CB, cb = i % CB;
     w[cb][t] = __builtin_amdgcn_raw_buffer_load_b128(rq[cb], v16 + t * 1024, kt0 * 1024, AUX_NT);
   };
+  // every tile of the wave, before the activation staging. Measured on the Llama-2-7B decode (tokens/s) against fewer up
+  // front and the rest one per consumed tile: 4 -> 721, 8 -> 729, 16 = everything up front -> 740, 8 + the rest right
+  // after the staging -> 744 (= 16 for every projection but gate/up), 4 + the rest after the staging -> 719: the
+  // earlier the whole wave's loads are queued the better, even when the CU's miss queue makes the wave wait at issue.
 #pragma unroll
-  for (int i = 0; i < PF && i < CB * TPW; ++i) issue_w(i);
-  WOQ_STAMP(3);
+  for (int i = 0; i < CB * TPW; ++i) issue_w(i);
 
   float ss_coop = 0.f;  // act-order: this wave's share of sum x^2 over the whole vector (any partition sums to the same)
   if constexpr (SHUF) {
@@ -375,7 +340,7 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
   __builtin_amdgcn_wave_barrier();
   my_ss = 0.f, my_unsc = 0.f;
   if (rs == 0) {
-    if (!WOQ_SKIP(5)) stage_row(0, xv0);
+    stage_row(0, xv0);
     if constexpr (SHUF) {
       if (lane == 0) my_ss = ss_coop;  // the gathered slice holds x * g, not x: the RMSNorm sum comes from the copy pass
     }
@@ -394,11 +359,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
   if (lane < TSETM) ssq[((size_t)rs * nw + wid) * TSETM + lane] = my_ss;
   // the strip, zero and ones blocks are wave-private and LDS executes one wave's accesses in order: no barrier
   __builtin_amdgcn_wave_barrier();
-  WOQ_STAMP(4);
-  if constexpr (WOQ_REST_EARLY) {
-#pragma unroll
-    for (int i = PF; i < CB * TPW; ++i) issue_w(i);
-  }
 
   // ---- 3. inner products, tiles in arrival order ----
   // A rows: MFMA row r = lane & 15 -> activation row r >> 2, part r & 3 (limb 0..2 | ones). D: lane group kq
@@ -433,16 +393,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
   float prev_sc = 0.f, prev_zc = 0.f;
   int prev_cb = 0;
   bool have_prev = false;
-  if (WOQ_SKIP(6)) {
-    uint32_t acc_ = 0;
-#pragma unroll
-    for (int i = PF; i < CB * TPW; ++i) issue_w(i);
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-      for (int t = 0; t < TPW; ++t) acc_ |= w[cb][t].x | w[cb][t].y | w[cb][t].z | w[cb][t].w;
-    tot[0] = acc_ == 0x1234567u ? 1.f : 0.f;
-  } else
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
     if constexpr (NDIG > 0 && !M1) {
@@ -462,7 +412,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
       }
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
-        if (!WOQ_REST_EARLY && t * CB + cb + PF < CB * TPW) issue_w(t * CB + cb + PF);
         const u32x4 wv = w[cb][t];
         if constexpr (NDIG > 0) {  // table weights: one MFMA pair per digit plane, recombined most significant first
           i32x4 b0[NB], b1[NB];
@@ -509,7 +458,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
         if constexpr (ASYM) sx = limb_combine(__builtin_amdgcn_mfma_i32_16x16x64_i8(av, b_ones, izero, 0, 0, 0));
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
-          if (h == 0 && !WOQ_REST_EARLY && t * CB + cb + PF < CB * TPW) issue_w(t * CB + cb + PF);
           const u32x4 wv = w[cb][t];
           const uint32_t w0 = h == 0 ? wv.x : wv.z, w1 = h == 0 ? wv.y : wv.w;
           float f = half_dot(av, w0, w1);
@@ -547,7 +495,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
       }
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
-        if (!WOQ_REST_EARLY && t * CB + cb + PF < CB * TPW) issue_w(t * CB + cb + PF);
         const u32x4 wv = w[cb][t];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -578,7 +525,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
         }
       }
     }
-    if (t == 0) WOQ_STAMP(5);
   }
   if (have_prev) tot[prev_cb] = fmaf(prev_sc, limb_combine(prev_d) + prev_zc, tot[prev_cb]);
   if constexpr (M1 && SMODE == 1) {  // lane quarter 1 holds the odd 32-k groups' sums: fold them into quarter 0
@@ -591,14 +537,8 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
     if (!M1 || lane < 16)
       slab[(((size_t)rs * nw + wid) * CB + cb) * 64 + lane] = tot[cb] * (NDIG > 0 ? unsc * lut.wmul : unsc);
   }
-  WOQ_STAMP(6);
-  if (WOQ_SKIP(8)) {
-    if (lane < 16 && wid == 0) ((float*)out)[(int)blockIdx.x * 16 + lane] = tot[0];
-    return;
-  }
   }  // row sets
   __syncthreads();
-  WOQ_STAMP(7);
 
   // ---- 4. finish: sum over waves, RMSNorm factor, bias, SiLU*mul, residual, store ----
   const int ncb = silu ? 1 : CB;
@@ -638,7 +578,6 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
       store_f32(out, (size_t)e_m * ldo + n, out_dtype, v);
     }
   }
-  WOQ_STAMP(8);
 }
 
 struct TileLaunch {
@@ -767,11 +706,7 @@ int gemv_tile_k_chunks(int tiles_k, int cb, int smode, bool chainable) {
 // geometry pick: nw waves x tpw tiles cover tiles_k (8 tiles = 8 KiB per wave per column tile; 4 for short K so
 // that a workgroup still has a few waves). Returns false when this kernel does not take the shape (K > 16384).
 bool gemv_tile_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw) {
-  static const int force4 = [] {  // WOQ_TILE_TPW4=<max tiles_k>: 4 tiles per wave up to that K (timing experiments)
-    const char* s = getenv("WOQ_TILE_TPW4");
-    return s ? atoi(s) : 0;
-  }();
-  tpw = (tiles_k > 16 && !(cb == 2 && smode == 1) && tiles_k > force4) ? 8 : 4;  // per-32 scales x 2 column tiles: register budget
+  tpw = (tiles_k > 16 && !(cb == 2 && smode == 1)) ? 8 : 4;  // per-32 scales x 2 column tiles: register budget
   nw = (tiles_k + tpw - 1) / tpw;
   return nw <= (cb * tpw > 8 ? 8 : (smode == 1 ? 12 : 16));  // the kernel's __launch_bounds__
 }
@@ -782,11 +717,9 @@ bool gemv_tile_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw) {
 // woq_gemv.hip.
 int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_header& h, const float* norm_w,
                        int epi, int out_dtype) {
-  static const bool table_generic = getenv("WOQ_TABLE_GENERIC") != nullptr;  // A/B switch: round 3's fp32 VALU kernel
-  const bool table = is_table_type(h.weight_type) && h.off_zp == 0 && !table_generic;
+  const bool table = is_table_type(h.weight_type) && h.off_zp == 0;
   // act-order (g_idx) blobs: one int4 row per launch through the gather form (round 5); more rows keep the generic kernel
-  static const bool shuf_generic = getenv("WOQ_SHUFFLE_GENERIC") != nullptr;  // A/B switch: the fp32 VALU kernel
-  if (h.off_shuffle != 0 && (h.weight_type != WOQ_W_INT4_CLIP || shuf_generic)) return 0;
+  if (h.off_shuffle != 0 && h.weight_type != WOQ_W_INT4_CLIP) return 0;
   if ((h.weight_type != WOQ_W_INT4_CLIP && !table) || (h.K & 3) != 0 || (lda & 3) != 0 ||
       (((uintptr_t)act) & (act_dtype == WOQ_F32 ? 15 : 7)) != 0 || (((uintptr_t)norm_w) & 15) != 0)
     return 0;
@@ -800,12 +733,7 @@ int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_h
     const int tpg = h.group / WOQ_TILE_K;
     if (tpg < 1 || (tpg & (tpg - 1)) != 0) return 0;  // tiles per group must be a power of two
   }
-  static const int cap = [] {  // WOQ_TILE_MAXM=4: one row set per launch (the round-2 behaviour; same-box A/B runs)
-    const char* s = getenv("WOQ_TILE_MAXM");
-    const int v = s ? atoi(s) : TMAXM;
-    return v >= 1 && v <= TMAXM ? v : TMAXM;
-  }();
-  int m = h.off_shuffle != 0 ? 1 : cap;
+  int m = h.off_shuffle != 0 ? 1 : TMAXM;
   const size_t extra = h.off_shuffle != 0 ? (size_t)h.K * 4 + 16 : 0;  // the act-order form's copy of the vector
   while (m > 0 && tile_lds_bytes(m, nw, tpw, cb) + extra > 150 * 1024) --m;
   return m;
@@ -847,9 +775,6 @@ int launch_gemv_tile(const void* act, int act_dtype, int lda, int M, const void*
             (act_dtype == WOQ_F16 ? 4 : (act_dtype == WOQ_BF16 ? 8 : 0));
   a.ndig = lut_args_for(h.weight_type, h.compute_type, a.lut);
   a.shuffle = h.off_shuffle ? (const int32_t*)(b + h.off_shuffle) : nullptr;
-#ifdef WOQ_PROBE
-  a.flags |= ::g_probe_flags;
-#endif
   const int tiles_n = h.Npad / WOQ_TILE_N;
   const int cb = epi == 1 ? 2 : 1;
   if (epi == 1 && (tiles_n & 1)) return woq::fail("QBits: fused gate/up weight needs an even number of column tiles");

@@ -1,9 +1,8 @@
 // woq_gemv_xq.hip — host side of the batch-1 decode GEMV over an XQ activation vector (kernel: woq_gemv_xqs.h) and
 // the standalone fp32 -> XQ conversion. Reference path replaced: qbits.cpp:113-140 (woq_linear at M = 1).
-// The round-2 kernel (every tile requested up front, offset-binary limbs) lives on as the timing twin of
-// tools/xq_probe.hip (tools/xq_r02_twin.h); same-box A/B in profiles/r03*_xq_probe.txt.
+// It replaced the round-2 kernel (every tile requested up front, offset-binary limbs); same-box A/B in
+// profiles/r03*_xq_probe.txt.
 #include <algorithm>
-#include <cstdlib>
 
 #include "woq_gemv_common.h"
 #ifdef WOQ_XQS_STAMPS  // measurement build only (tools/xqs_stamps.py): per-(workgroup, wave) wall-clock stamps of the stages
@@ -42,23 +41,17 @@ struct XqLaunch {
   int ndig;
 };
 
-// window depth by tiles per wave (tools/xq_probe.hip grid, profiles/r03c_xq_probe.txt)
+// window depth by tiles per wave (profiles/r03c_xq_probe.txt)
 // round 6 (profiles/r06ad_gemv_occupancy_and_window.txt): 6 — same-box A/Bs on the round-6 kernel read 4 / 6 / 8 -> 993.5 / 1001.5 / 992.6 tokens/s and
 // 4 / 5 / 7 -> 999.8 / 1002.7 / 1003.2 (round 4 had measured no difference); it only reaches the 8-tile waves (o, down)
-#ifndef WOQ_XQS_DEPTH  // A/B builds: tools/mkvariant_xq.sh -DWOQ_XQS_DEPTH=4 | 8 (all of a wave's tiles up front)
-#define WOQ_XQS_DEPTH 6
-#endif
-template <int TPW>
-struct XqsDepth {
-  static constexpr int value = TPW >= WOQ_XQS_DEPTH ? WOQ_XQS_DEPTH : TPW;
-};
+constexpr int XQ_WINDOW_DEPTH = 6;
 
 template <int TPW, int CB, int SMODE, bool ASYM, bool S32, int NDIG>
 static int launch_xq_t(const XqLaunch& a, hipStream_t st) {
   typedef XqsLds<TPW, CB, SMODE, ASYM, S32> L;
   const size_t lds = L::total(a.nw);
   if (lds > 160 * 1024) return woq::fail("QBits: XQ GEMV geometry does not fit LDS");
-  auto kern = gemv_xqs_kernel<TPW, CB, XqsDepth<TPW>::value, SMODE, ASYM, S32, NDIG>;
+  auto kern = gemv_xqs_kernel<TPW, CB, (TPW < XQ_WINDOW_DEPTH ? TPW : XQ_WINDOW_DEPTH), SMODE, ASYM, S32, NDIG>;
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -107,29 +100,10 @@ static int launch_xq_sm(const XqLaunch& a, int smode, bool asym, bool s32, hipSt
 }
 
 // Geometry: nw waves x tpw tiles cover a K range of tiles_k tiles. Measured per projection of the Llama-2-7B layer
-// (tools/xq_probe.hip, profiles/r03c_xq_probe.txt): 8 tiles per wave for single column tiles with long K, 4 for the
-// fused gate/up pairs (twice the bytes per tile step) and short K. WOQ_XQ_TPW=4|8 forces one (timing experiments).
+// (profiles/r03c_xq_probe.txt): 8 tiles per wave for single column tiles with long K, 4 for the fused gate/up pairs
+// (twice the bytes per tile step) and short K.
 static bool xq_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw, int ndig = 0) {
-  static const int forced = [] {
-    const char* s = getenv("WOQ_XQ_TPW");
-    return s ? atoi(s) : 0;
-  }();
   tpw = (tiles_k > 16 && cb == 1) ? 8 : 4;
-  if (forced == 4 || (forced == 8 && !(cb == 2 && smode == 1))) tpw = forced;
-  // WOQ_XQ_TPW_SHORT=4|8: single column tiles with K <= 4096 only (o_proj and the stand-alone qkv of Llama-2-7B) —
-  // one workgroup per CU there, so more, shorter waves are the other way to hide latency (A/B runs)
-  static const int forced_short = [] {
-    const char* s = getenv("WOQ_XQ_TPW_SHORT");
-    return s ? atoi(s) : 0;
-  }();
-  if (cb == 1 && tiles_k <= 32 && (forced_short == 4 || forced_short == 8)) tpw = forced_short;
-#ifdef WOQ_XQ_TPW6
-  static const int forced_long = [] {
-    const char* s = getenv("WOQ_XQ_TPW_LONG");
-    return s ? atoi(s) : 0;
-  }();
-  if (cb == 1 && tiles_k > 32 && tiles_k <= 96 && forced_long == 6 && ndig == 0) tpw = 6;
-#endif
   const bool wide = cb == 2 && ndig == 3;  // table weights, three digit planes, column-tile pairs: 512-thread launches
   if (wide && tiles_k > 32 && smode == 0) tpw = 8;
   nw = (tiles_k + tpw - 1) / tpw;
@@ -218,13 +192,7 @@ int launch_gemv_xq(const XqPtrs& xin, const void* blob, const woq_blob_header& h
     if (cb == 2)
       rc = tpw == 4 ? launch_xq_sm<4, 2>(a, smode, asym, s32, st) : launch_xq_sm<8, 2>(a, smode, asym, s32, st);
     else
-#ifdef WOQ_XQ_TPW6  // A/B build (tools/mkvariant_xq.sh t6 -DWOQ_XQ_TPW6=1, WOQ_XQ_TPW_LONG=6): 6-tile waves for long K
-      rc = tpw == 6   ? launch_xq_sm<6, 1>(a, smode, asym, s32, st)
-           : tpw == 4 ? launch_xq_sm<4, 1>(a, smode, asym, s32, st)
-                      : launch_xq_sm<8, 1>(a, smode, asym, s32, st);
-#else
       rc = tpw == 4 ? launch_xq_sm<4, 1>(a, smode, asym, s32, st) : launch_xq_sm<8, 1>(a, smode, asym, s32, st);
-#endif
     if (rc) return rc;
   }
   return 0;

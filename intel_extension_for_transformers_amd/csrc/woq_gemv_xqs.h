@@ -5,7 +5,7 @@
 // int32 sums on v_mfma_i32_16x16x64_i8, one fp32 recombination per 16-k block, group scale (and zero point) applied
 // per block, fp32 across blocks.
 //
-// What round 3 changed, and the measurement behind each change (tools/xq_probe.hip, profiles/r03b_xq_knockouts.txt):
+// What round 3 changed, and the measurement behind each change (profiles/r03b_xq_knockouts.txt):
 // the round-2 kernel with every load's descriptor emptied — no memory traffic at all — still took 5.0 us per qkv
 // launch, exactly what a load-only twin takes WITH the traffic, and its bare skeleton (no traffic, no arithmetic, no
 // epilogue) 3.6 us. The kernel was bound by its own instruction stream: ~300 instructions of per-wave set-up and ~50
@@ -54,55 +54,20 @@ extern __device__ unsigned long long* g_xqs_probe;
   } while (0)
 #endif
 
-// experiment switches of the probe build (tools/xq_probe.hip, -DWOQ_XQS_KNOBS): bits 4.. of `flags` knock out one
-// stage each by emptying its buffer descriptors or skipping its arithmetic. Nothing in the product build.
-#ifdef WOQ_XQS_KNOBS
-#define WOQ_XK(bit) (((flags) >> (bit)) & 1)
-#else
-#define WOQ_XK(bit) false
-#endif
+namespace woq {
 
-// how many of the first D weight tiles a wave requests BEFORE its small (L2-resident) requests; the rest follow them.
-// Returns are in order, so whatever is in front of the limbs delays the first MFMA (tools/xq_probe.hip: A/B builds).
 // polling interval of a wave that waits for its input blocks inside a chained launch, in units of 64 clocks: pollers
 // share the memory pipe with the streaming producers (MI355X_MICROARCH.md, polling-cost)
-#ifndef WOQ_CHAIN_SLEEP
-#define WOQ_CHAIN_SLEEP 8
-#endif
+constexpr int CHAIN_SLEEP = 8;
+// how many of the first D weight tiles a wave requests BEFORE its small (L2-resident) requests; the rest follow them.
+// Returns are in order, so whatever is in front of the limbs delays the first MFMA.
 // Round 6 re-measured them on the round-6 kernel (profiles/r06ad_gemv_occupancy_and_window.txt, same-box A/Bs): single
 // column tiles 2 -> 1 (0 / 1 / 2 / 4 / 6: 998 / 1005 / 1001 / 987 / 981 tokens/s), the gate/up pairs all of the window -> 0,
 // the small requests first (0 / 1 / 2 beside singles at 1: 1016 / 1005 / 1000); the fused launch's q strips stay at 1
 // (0 / 1 / 2: 995 / 998 / 997) and its one-tile k / v strips go to 0 (1003 vs 998)
-#ifndef WOQ_XQS_PRE
-#define WOQ_XQS_PRE 1
-#endif
-#ifndef WOQ_XQS_PRE_PAIR
-#define WOQ_XQS_PRE_PAIR 0
-#endif
-#ifndef WOQ_XQS_PRE_Q
-#define WOQ_XQS_PRE_Q 1
-#endif
-#ifndef WOQ_XQS_PRE_KV
-#define WOQ_XQS_PRE_KV 0
-#endif
-// 1: no workgroup barrier behind the stream — every wave leaves its partial sums in the slab and bumps an LDS counter,
-// the wave that arrives LAST runs the epilogue at once (A/B builds: tools/mkvariant_xq.sh last -DWOQ_XQS_LAST=1;
-// record: profiles/r06c_*)
-// A/B builds (tools/mkvariant_xq.sh): the scale / zero-point requests in front of the limb requests; their cache policy
-#ifndef WOQ_XQS_SC_FIRST
-#define WOQ_XQS_SC_FIRST 0
-#endif
-#ifndef WOQ_XQS_SC_AUX
-#define WOQ_XQS_SC_AUX 0
-#endif
-#ifndef WOQ_XQS_LAST
-#define WOQ_XQS_LAST 0
-#endif
-#ifndef WOQ_XQS_GU_WAVES  // A/B builds: -DWOQ_XQS_GU_WAVES=1 = the compiler's own choice (82 registers, five waves per SIMD)
-#define WOQ_XQS_GU_WAVES 6
-#endif
-
-namespace woq {
+constexpr int XQS_PRE = 1, XQS_PRE_PAIR = 0, XQS_PRE_Q = 1, XQS_PRE_KV = 0;
+// waves per SIMD of the int4 gate/up pairs (gemv_xqs_kernel); 1 = the compiler's own choice (82 registers, five waves)
+constexpr int XQS_GU_WAVES = 6;
 
 // LDS: [zero block 256, shared: every wave writes the same zeros before it reads them][per wave: limb strip TPW x 384 |
 // u | sx | scale slices | zero-point slices][slab nw x CB x 16 f32][64 f32 scratch]
@@ -211,11 +176,11 @@ __device__ __forceinline__ void gemv_xqs_body(
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb)
     rq[cb] = make_rsrc(q + (size_t)(bx * CB + cb) * tiles_k * 64,
-                       WOQ_XK(8) ? 0 : uni(min(kt0 + cnt, tiles_k) * 1024));
-  // weight tiles requested in front of the small requests (WOQ_XQS_PRE* above): one for single column tiles and the fused
+                       uni(min(kt0 + cnt, tiles_k) * 1024));
+  // weight tiles requested in front of the small requests (XQS_PRE* above): one for single column tiles and the fused
   // launch's q strips, none for the gate/up pairs and the one-tile-deep k / v strips (round 3 had two / all of the window:
   // profiles/r03i_xq_issue_order.txt; re-measured on the round-6 kernel: profiles/r06ad_gemv_occupancy_and_window.txt)
-  constexpr int PRE_WANT = CB == 2 ? WOQ_XQS_PRE_PAIR : !FUSED ? WOQ_XQS_PRE : D == 1 ? WOQ_XQS_PRE_KV : WOQ_XQS_PRE_Q;
+  constexpr int PRE_WANT = CB == 2 ? XQS_PRE_PAIR : !FUSED ? XQS_PRE : D == 1 ? XQS_PRE_KV : XQS_PRE_Q;
   constexpr int PRE = CHAIN_IN ? DD : (PRE_WANT < DD ? PRE_WANT : DD);
 #pragma unroll
   for (int t = 0; t < PRE; ++t)
@@ -228,7 +193,7 @@ __device__ __forceinline__ void gemv_xqs_body(
   constexpr int XP = (L::STRIP + 1023) / 1024;  // 1-KiB pieces per limb strip
   constexpr int UL = (TPW * 8 + 63) / 64;       // block factors per lane (8 blocks per tile)
   constexpr int AUX_IN = CHAIN_IN ? 16 : 0;     // sc1: agent-scope loads of data another workgroup just published
-  const int nblk = WOQ_XK(5) ? 0 : uni(max(0, min(cnt * 8, tiles_k * 8 - kt0 * 8)));
+  const int nblk = uni(max(0, min(cnt * 8, tiles_k * 8 - kt0 * 8)));
   if constexpr (CHAIN_IN) {
     // the blocks of this wave's K slice, one flag per lane and pass; the weight requests above are already in flight
     const unsigned int* f = chain.in_flag + (size_t)kt0 * 8;
@@ -244,7 +209,7 @@ __device__ __forceinline__ void gemv_xqs_body(
         if (lane == 0 && chain.status != nullptr) atomicOr(chain.status, 1);
         break;
       }
-      __builtin_amdgcn_s_sleep(WOQ_CHAIN_SLEEP);
+      __builtin_amdgcn_s_sleep(CHAIN_SLEEP);
     }
   }
   u32x4 xl[XP];
@@ -255,8 +220,7 @@ __device__ __forceinline__ void gemv_xqs_body(
   int g0 = 0;
   if constexpr (SMODE == 0) g0 = min(kt0 >> tpg_shift, n_groups - 1);
   auto req_x = [&]() {
-    const rsrc_t rl =
-        make_rsrc(xlimbs + (size_t)kt0 * 384, WOQ_XK(4) ? 0 : uni(max(0, min(cnt, tiles_k - kt0)) * 384));
+    const rsrc_t rl = make_rsrc(xlimbs + (size_t)kt0 * 384, uni(max(0, min(cnt, tiles_k - kt0)) * 384));
 #pragma unroll
     for (int j = 0; j < XP; ++j) xl[j] = __builtin_amdgcn_raw_buffer_load_b128(rl, v16 + j * 1024, 0, AUX_IN);
   // block factors of the slice: lane L holds blocks kt0 * 8 + L (+ 64 ...) (8 blocks per tile; reads past the slice
@@ -281,27 +245,20 @@ __device__ __forceinline__ void gemv_xqs_body(
     const int tn = bx * CB + cb;
     rsrc_t rs, rz;
     if constexpr (SMODE == 0) {
-      rs = make_rsrc((const char*)scales + ((size_t)tn * n_groups + g0) * 16 * ESZ,
-                     WOQ_XK(5) ? 0 : uni((n_groups - g0) * 16 * ESZ));
+      rs = make_rsrc((const char*)scales + ((size_t)tn * n_groups + g0) * 16 * ESZ, uni((n_groups - g0) * 16 * ESZ));
       rz = make_rsrc(zp + ((size_t)tn * n_groups + g0) * 16, uni((n_groups - g0) * 16));
     } else {
       const int left = uni(max(0, tiles_k - kt0));
-      rs = make_rsrc((const char*)scales + ((size_t)tn * tiles_k + kt0) * 64 * ESZ, WOQ_XK(5) ? 0 : left * 64 * ESZ);
+      rs = make_rsrc((const char*)scales + ((size_t)tn * tiles_k + kt0) * 64 * ESZ, left * 64 * ESZ);
       rz = make_rsrc(zp + ((size_t)tn * tiles_k + kt0) * 64, left * 64);
     }
 #pragma unroll
-    for (int j = 0; j < NSP; ++j) sl[cb][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, v16 + j * 1024, 0, WOQ_XQS_SC_AUX);
-    if constexpr (ASYM) zl[cb] = __builtin_amdgcn_raw_buffer_load_b128(rz, v16, 0, WOQ_XQS_SC_AUX);
+    for (int j = 0; j < NSP; ++j) sl[cb][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, v16 + j * 1024, 0, 0);
+    if constexpr (ASYM) zl[cb] = __builtin_amdgcn_raw_buffer_load_b128(rz, v16, 0, 0);
   }
   };
-#if WOQ_XQS_SC_FIRST
-  req_s();
-  __builtin_amdgcn_sched_barrier(0);
-  req_x();
-#else
   req_x();
   req_s();
-#endif
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int t = PRE; t < DD; ++t)
@@ -319,7 +276,7 @@ __device__ __forceinline__ void gemv_xqs_body(
   const CommDev* tp = nullptr;
   XqPtrs xo = {nullptr, nullptr, nullptr};
   unsigned int fused_tag = 0u;
-  if (wid == 0 || WOQ_XQS_LAST) {  // (the rejected last-arriver form: any wave may run the epilogue)
+  if (wid == 0) {
     residual = late->residual, next_norm_w = late->next_norm_w, ssq_in = late->ssq_in, bias = late->bias;
     n_ssq = late->n_ssq, N = late->N, K = late->K, eps = late->eps;
     out = late->out, ssq_out = late->ssq_out, tp = late->tp;
@@ -342,16 +299,16 @@ __device__ __forceinline__ void gemv_xqs_body(
   if (wid == 0) {
     const int n0 = bx * 16;
     const int nlive = uni(max(0, min((silu ? (N >> 1) : N) - n0, 16)));
-    if (residual != nullptr && !WOQ_XK(5)) {
+    if (residual != nullptr) {
       const rsrc_t rr = make_rsrc(residual + n0, nlive * 4);
       e_res = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, min(lane, 15) * 4, 0, 0));
     }
-    if (next_norm_w != nullptr && !WOQ_XK(5)) {
+    if (next_norm_w != nullptr) {
       const rsrc_t rg = make_rsrc(next_norm_w + n0, nlive * 4);
       g_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, min(lane, 15) * 4, 0, 0));
     }
     if (ssq_in != nullptr) {
-      const rsrc_t rs = make_rsrc(ssq_in, WOQ_XK(5) ? 0 : n_ssq * 4);
+      const rsrc_t rs = make_rsrc(ssq_in, n_ssq * 4);
       ssq_v[0] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, v16, 0, 0));
 #pragma unroll
       for (int j = 1; j < 4; ++j) {
@@ -387,11 +344,6 @@ __device__ __forceinline__ void gemv_xqs_body(
       if (v16 < L::ZPB) *(u32x4*)(wbase + L::O_ZP + cb * L::ZPB + v16) = zl[cb];
   }
   __builtin_amdgcn_wave_barrier();
-#if WOQ_XQS_LAST
-  // red[1]: arrival counter, zero before any wave can bump it (LDS-only barrier: the weight window stays in flight)
-  if (tid == 0) ((unsigned int*)red)[1] = 0u;
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
   // A-operand addresses: MFMA row r = lane & 15 -> quarter e = r >> 2, digit p = r & 3 (row 4 e + 3 stays zero);
   // a row is live in lane quarter kq == e only, everything else reads the zero block
   const int i16 = lane & 15, kq = lane >> 4;
@@ -425,10 +377,6 @@ __device__ __forceinline__ void gemv_xqs_body(
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
       const u32x4 wv = w[cb][t];
-      if (WOQ_XK(6)) {  // probe: consume the tile, no arithmetic
-        tot[cb] += __uint_as_float((wv.x ^ wv.y) ^ (wv.z ^ wv.w));
-        continue;
-      }
       const unsigned char* scp = wbase + L::O_SC + cb * L::SCB;
       const unsigned char* zpp = wbase + L::O_ZP + cb * L::ZPB;
       float f0, f1;
@@ -489,10 +437,6 @@ __device__ __forceinline__ void gemv_xqs_body(
     __builtin_amdgcn_sched_barrier(0x38f);
   }
   WOQ_XQS_STAMP(4);
-  if (WOQ_XK(7)) {  // probe: no cross-wave sum, no epilogue
-    if (lane < 16 && out) out[bx * 16 + lane] = tot[0] + tot[CB - 1];
-    return;
-  }
   // the four lane quarters hold the four blocks' shares of each column
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb) {
@@ -506,34 +450,11 @@ __device__ __forceinline__ void gemv_xqs_body(
     const float s = wave_sum_dpp((t4.x + t4.y) + (t4.z + t4.w));
     if (lane == 0) red[0] = s;
   }
-#if WOQ_XQS_LAST
-  if (wid == 0 && lane < 16) {  // what the epilogue lanes need from wave 0's registers: in LDS before wave 0 arrives
-    red[16 + lane] = e_res;
-    red[32 + lane] = g_next;
-  }
-  asm volatile("" ::: "memory");
-  unsigned int arrived = 0u;
-  if (lane == 0) {
-    typedef __attribute__((address_space(3))) unsigned int lds_u32;
-    arrived = __hip_atomic_fetch_add((lds_u32*)((unsigned int*)red + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  asm volatile("" ::: "memory");
-  const bool finisher = uni((int)arrived) == nw - 1;  // LDS runs a wave's operations in order: the counter is behind the row
-  if (finisher) {
-    e_res = red[16 + (lane & 15)];
-    g_next = red[32 + (lane & 15)];
-  }
-  const int tid_e = finisher ? lane : 64;
-#else
   __syncthreads();
-  const int tid_e = tid;
-#endif
   WOQ_XQS_STAMP(5);
 
-  // ---- 5. finish (lanes 0..15 of wave 0 | of the last wave to arrive): sum over waves, RMSNorm factor, bias, SiLU*mul,
-  // residual, store, XQ ----
-  if (tid_e < 16) {
-    const int tid = tid_e;
+  // ---- 5. finish (lanes 0..15 of wave 0): sum over waves, RMSNorm factor, bias, SiLU*mul, residual, store, XQ ----
+  if (tid < 16) {
     float v = 0.f, up = 0.f;
 #pragma unroll 4
     for (int w2 = 0; w2 < nw; ++w2) {
@@ -593,7 +514,7 @@ __device__ __forceinline__ void gemv_xqs_body(
 // per CU, i.e. the whole grid resident in one round; at 82 registers the compiler stopped two short of that)
 template <int TPW, int CB, int D, int SMODE, bool ASYM, bool S32, int NDIG>
 __global__ __launch_bounds__((CB * TPW > 8 || (CB == 2 && NDIG == 3)) ? 512 : 1024)
-__attribute__((amdgpu_waves_per_eu((CB == 2 && TPW == 4 && NDIG == 0 && SMODE == 0 && !ASYM && !S32) ? WOQ_XQS_GU_WAVES : 1)))
+__attribute__((amdgpu_waves_per_eu((CB == 2 && TPW == 4 && NDIG == 0 && SMODE == 0 && !ASYM && !S32) ? XQS_GU_WAVES : 1)))
 void gemv_xqs_kernel(
     const u32x4* __restrict__ q, const void* __restrict__ scales, const uint8_t* __restrict__ xlimbs,
     const float* __restrict__ xu, int tiles_k, int kt_off, int base_tiles, int rem_tiles, int n_groups, int tpg_flags,

@@ -153,10 +153,7 @@ template <int HD>
 __host__ __device__ constexpr int attn_lds_bytes() { return AKT * HD * 2 + HD * AVRB; }
 
 template <int KVD, int HD>
-#ifndef WOQ_ATTN_LB
-#define WOQ_ATTN_LB 2
-#endif
-__global__ __launch_bounds__(256, WOQ_ATTN_LB) void attn_prefill_kernel(const _Float16* __restrict__ qkv, int T, int start,
+__global__ __launch_bounds__(256, 2) void attn_prefill_kernel(const _Float16* __restrict__ qkv, int T, int start,
                                                               int heads, int kv_heads, const void* __restrict__ kcache,
                                                               const void* __restrict__ vcache, size_t seq_stride_elems,
                                                               _Float16* __restrict__ out, int n_qblocks, int window,
@@ -784,22 +781,14 @@ static int launch_attn_prefill_t(const _Float16* qkv, int n_seq, int T, int star
                                  int window, hipStream_t st) {
   auto k = attn_prefill_kernel<KVD, HD>;
   const int nqb = (T + AQB - 1) / AQB;
-  static const bool xcd_map = [] {  // WOQ_ATTN_XCD=0: the 3-D order (same-box A/B runs)
-    const char* e = getenv("WOQ_ATTN_XCD");
-    return !(e && e[0] == '0');
-  }();
   const long long total = (long long)nqb * heads * n_seq;
-  const dim3 grid = (xcd_map && (heads & 7) == 0 && total < (1ll << 31)) ? dim3((unsigned)total)
+  const dim3 grid = ((heads & 7) == 0 && total < (1ll << 31)) ? dim3((unsigned)total)
                                                                         : dim3((unsigned)nqb, (unsigned)heads, (unsigned)n_seq);
   // s_setprio 1 around the two MFMA phases of a tile: the MFMAs of one workgroup outrank the softmax VALU of the other
   // workgroup on the same SIMD, so the two fall into alternating phases instead of queueing behind each other. Same
-  // box, 8 layers at 4 x 2048: 24.42 -> 24.30 ms (attention -5 %, profiles/r03as); WOQ_ATTN_PRIO=0 turns it off.
-  static const int prio = [] {
-    const char* e = getenv("WOQ_ATTN_PRIO");
-    return e ? atoi(e) : 1;
-  }();
+  // box, 8 layers at 4 x 2048: 24.42 -> 24.30 ms (attention -5 %, profiles/r03as). Always on: prio = 1.
   hipLaunchKernelGGL(k, grid, dim3(256), attn_lds_bytes<HD>(), st, qkv, T, start, heads, kv_heads, kcache, vcache,
-                     seq_stride_elems, out, nqb, window, prio);
+                     seq_stride_elems, out, nqb, window, 1);
   return 0;
 }
 

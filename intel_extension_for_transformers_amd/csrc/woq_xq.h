@@ -65,8 +65,8 @@ __device__ __forceinline__ int row16_sum_i32(int v) {
   return v + WOQ_DPP_I32(v, 0x140);
 }
 
-// In-launch hand-off of an XQ vector (round 3, the chained launches — tools/rejected/woq_gemv_chain.hip — and the persistent launch): a consumer workgroup of the
-// SAME launch may be waiting for block `blk`. The producer then stores the block write-through (agent-scope stores
+// In-launch hand-off of an XQ vector (round 3; its users, the chained and the persistent launches, left the library:
+// tools/rejected/woq_gemv_chain.hip, tools/rejected/woq_persist.hip): a consumer workgroup of the SAME launch may be waiting for block `blk`. The producer then stores the block write-through (agent-scope stores
 // never stay in this XCD's L2 alone), drains them, and only then stores the block's flag word = the (step, vector) tag;
 // the consumer polls the flags of its K slice and reads the blocks with agent-scope loads afterwards
 // (cdna_hip_programming.md Guideline 16, form R1). flag == nullptr: plain stores, the consumer is a later launch.

@@ -1,5 +1,5 @@
-"""M = 5..8 rows: two launches of the tile GEMV (weights streamed twice) against the MFMA GEMM (streamed once).
-Run twice: default and WOQ_GEMV_AS_GEMM=1. Development tool."""
+"""Per-call time of woq_linear at 4..17 rows around the seam between the tile GEMV (up to 16 rows as MFMA row sets over
+one pass of the weights) and the MFMA GEMM. Development tool."""
 import os
 import sys
 import time
@@ -28,5 +28,4 @@ for name, K, N in shapes:
             for b in blobs:
                 qbits.woq_linear(x, b, torch.empty(0), out, "bf16", "int4_clip", "fp16", False)
         torch.cuda.synchronize()
-        print("%-8s M=%2d  %7.2f us per call  (WOQ_GEMV_AS_GEMM=%s)" % (
-            name, M, (time.perf_counter() - t0) / 80 * 1e6, os.environ.get("WOQ_GEMV_AS_GEMM", "0")))
+        print("%-8s M=%2d  %7.2f us per call" % (name, M, (time.perf_counter() - t0) / 80 * 1e6))

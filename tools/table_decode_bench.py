@@ -81,11 +81,8 @@ if __name__ == "__main__":
     ap.add_argument("--group", type=int, default=128, help="group size of the per-projection timings (fp8: 128 / 64 / 32)")
     ap.add_argument("--types", default="int4_clip,nf4,nf4:bf16,fp4_e2m1,fp4_e2m1_bnb")
     args = ap.parse_args()
-    mode = "generic fp32 VALU kernel" if os.environ.get("WOQ_TABLE_GENERIC") else "digit-plane MFMA kernel"
-    if os.environ.get("WOQ_FP8_GENERIC"):
-        mode += "; fp8: lookup kernel"
     for wname in args.types.split(","):
-        row = {"weight_dtype": wname, "table_types_on": mode}
+        row = {"weight_dtype": wname}
         for name, (K, N) in SHAPES.items():
             row[name] = {"M=%d" % M: round(time_linear(wname, K, N, M, group=args.group), 2) for M in (1, 4, 8)}
         print(json.dumps(row), flush=True)

@@ -1,5 +1,6 @@
 """Stage stamps of the product decode GEMV (csrc/woq_gemv_xqs.h, WOQ_XQS_STAMP 0..6) inside the engine's own launches.
-Needs a library whose woq_gemv_xq.hip was compiled with -DWOQ_XQS_STAMPS (tools/visits/r06c.sh builds it):
+Needs a library whose woq_gemv_xq.hip was compiled with -DWOQ_XQS_STAMPS; tools/mkvariant_xq.sh builds it:
+    tools/mkvariant_xq.sh stamps -DWOQ_XQS_STAMPS
     WOQ_HIP_LIB=tools/lib_xq_stamps.so python tools/xqs_stamps.py
 For each projection: one pass of that projection over all 32 layers of a Llama-2-7B-shaped engine, back to back (the
 engine's woq_engine_time_gemv_mask); the stamps left in the buffer are those of the LAST launch. Per stage: the median /
