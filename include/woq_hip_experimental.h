@@ -52,6 +52,27 @@ WOQ_API int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, i
  * (split-K), 4 three-product fp32-class form, 8 hand-scheduled K loop, 16 half-tile ring layout, 32 256-row tiles,
  * 64 raw-A rows. Lets a test assert which kernel its shape ran. */
 WOQ_API int woq_gemm_form_log(int* forms, int cap);
+/* Test entry points: the attention launches of the engine on caller-owned buffers, each forwarding to the engine's own
+ * launcher unchanged (tests/test_gpu_attention_kernels.py). Caches [sequence][position][kv head][head_dim] in kv_dtype
+ * (WOQ_F16 | WOQ_BF16 | WOQ_FP8_E4M3), `seq_stride_elems` elements between sequences; cos / sin fp32 [position][head_dim / 2].
+ * rope_append: qkv fp16 [n_seq * T][(heads + 2 kv_heads) * head_dim], q rotated in place, rotated k and v appended at
+ * positions start .. start + T - 1. attn_prefill: causal attention of the chunk's q rows over cache positions
+ * [0, start + row], `window` > 0 = sliding window; out fp16 [n_seq * T][heads * head_dim]. */
+WOQ_API int woq_probe_rope_append(void* qkv, int n_seq, int T, int start, int heads, int kv_heads, int head_dim,
+                                  const float* cos_dev, const float* sin_dev, void* kcache, void* vcache, int kv_dtype,
+                                  size_t seq_stride_elems, void* stream);
+WOQ_API int woq_probe_attn_prefill(const void* qkv, int n_seq, int T, int start, int heads, int kv_heads, int head_dim,
+                                   const void* kcache, const void* vcache, int kv_dtype, size_t seq_stride_elems,
+                                   void* out, int window, void* stream);
+/* one decode step's attention: qkv fp32 [(heads + 2 kv_heads) * head_dim] un-rotated, `pos_dev` = device int32 position
+ * of the new token (k / v appended there), caches [max_ctx][kv_heads][head_dim], out fp32 [heads * head_dim].
+ * splits > 1: context slices merged by the combine launch (merge 0) or by the last slice to arrive (merge 1, zeroed
+ * counters); grouped != 0: the grouped-query matrix-core form where it applies, chunk_fixed as in
+ * woq_engine_set_attn_chunk. The partial buffer and counters are allocated and freed on `stream`; no state is kept. */
+WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos_dev,
+                                  const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
+                                  int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
+                                  float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -81,6 +81,7 @@ EXPORTS = [
 EXPERIMENTAL_EXPORTS = [
     "woq_engine_set_attn_chunk", "woq_engine_attn_chunk", "woq_engine_time_gemv", "woq_engine_time_gemv_mask",
     "woq_engine_time_twin", "woq_engine_set_time_eager", "woq_engine_time_prefill_gemm", "woq_gemm_form_log",
+    "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -154,6 +155,9 @@ def lib():
     L.woq_engine_set_tp_options.argtypes = [vp, ci, ci]
     L.woq_engine_time_prefill_gemm.argtypes = [vp, ci, ci, ci, vp, ctypes.POINTER(cf), ctypes.POINTER(cf)]
     L.woq_gemm_form_log.argtypes = [ctypes.POINTER(ci), ci]
+    L.woq_probe_rope_append.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, cs, vp]
+    L.woq_probe_attn_prefill.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, cs, vp, ci, vp]
+    L.woq_probe_attn_decode.argtypes = [vp, vp, vp, ci, vp, vp, vp] + [ci] * 9 + [vp, vp]
     L.woq_comm_create.argtypes = [ci, ci, cs, ctypes.POINTER(vp)]
     L.woq_comm_handle.argtypes = [vp, vp, cs]
     L.woq_comm_connect.argtypes = [vp, vp, ctypes.POINTER(ci)]
@@ -177,6 +181,37 @@ def gemm_form_log():
     buf = (ctypes.c_int * 64)()
     n = lib().woq_gemm_form_log(buf, 64)
     return list(buf[:min(n, 64)])
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def probe_rope_append(qkv, n_seq, T, start, heads, kv_heads, head_dim, cos, sin, kcache, vcache, kv_dtype, seq_stride):
+    """rope_append_kernel alone (woq_probe_rope_append): torch tensors on the device, the current stream."""
+    rc = lib().woq_probe_rope_append(_ptr(qkv), n_seq, T, start, heads, kv_heads, head_dim, _ptr(cos), _ptr(sin),
+                                     _ptr(kcache), _ptr(vcache), kv_dtype, seq_stride, stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def probe_attn_prefill(qkv, n_seq, T, start, heads, kv_heads, head_dim, kcache, vcache, kv_dtype, seq_stride, out,
+                       window):
+    """attn_prefill_kernel alone (woq_probe_attn_prefill)."""
+    rc = lib().woq_probe_attn_prefill(_ptr(qkv), n_seq, T, start, heads, kv_heads, head_dim, _ptr(kcache), _ptr(vcache),
+                                      kv_dtype, seq_stride, _ptr(out), window, stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def probe_attn_decode(qkv, kcache, vcache, kv_dtype, pos, cos, sin, heads, kv_heads, head_dim, max_ctx, window, splits,
+                      grouped, merge, chunk_fixed, out):
+    """the decode attention launches alone (woq_probe_attn_decode); `pos` is a device int32 tensor."""
+    rc = lib().woq_probe_attn_decode(_ptr(qkv), _ptr(kcache), _ptr(vcache), kv_dtype, _ptr(pos), _ptr(cos), _ptr(sin),
+                                     heads, kv_heads, head_dim, max_ctx, window, splits, grouped, merge, chunk_fixed,
+                                     _ptr(out), stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
 
 
 def check(rc):

@@ -8,6 +8,7 @@
 #include "woq_device.h"
 #include "woq_launch.h"
 #include "woq_xq.h"
+#include "../../include/woq_hip_experimental.h"
 
 namespace woq {
 
@@ -531,6 +532,40 @@ int woq_gelu(const void* x_dev, int dtype, size_t n, int approximate, void* out_
   hipLaunchKernelGGL(gelu_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x_dev, dtype, n, approximate,
                      out_dev);
   WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+// test entry point (include/woq_hip_experimental.h): the engine's separate decode-attention launches on their own
+WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos_dev,
+                                  const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
+                                  int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
+                                  float* out, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(heads > 0 && kv_heads > 0 && heads % kv_heads == 0 && max_ctx > 0 && window >= 0 && splits >= 1,
+            "QBits: bad attention shape");
+  WOQ_CHECK(merge == 0 || merge == 1, "QBits: merge must be 0 (combine launch) or 1 (last-arriver counters)");
+  const hipStream_t st = (hipStream_t)stream;
+  // the partial buffer of woq_attn_merge.h (o [heads][64][D], then ml [heads][64][2]) and one counter per head
+  const size_t part_bytes = (size_t)heads * ATTN_MAX_SLICES * (head_dim + 2) * sizeof(float);
+  float* part = nullptr;
+  unsigned int* counters = nullptr;
+  WOQ_HIP(hipMallocAsync((void**)&part, part_bytes, st));
+  if (merge) {
+    if (hipMallocAsync((void**)&counters, (size_t)heads * sizeof(unsigned int), st) != hipSuccess ||
+        hipMemsetAsync(counters, 0, (size_t)heads * sizeof(unsigned int), st) != hipSuccess) {
+      if (counters) hipFreeAsync(counters, st);
+      hipFreeAsync(part, st);
+      return woq::fail("QBits: could not allocate the attention merge counters");
+    }
+  }
+  const int rc = launch_attn_decode(qkv, kcache, vcache, kv_dtype, pos_dev, cos_dev, sin_dev, heads, kv_heads, head_dim,
+                                    max_ctx, window, out, splits, grouped, part, XqPtrs{nullptr, nullptr, nullptr}, st,
+                                    counters, chunk_fixed, nullptr, nullptr, 0);
+  const hipError_t le = hipGetLastError();
+  if (counters) hipFreeAsync(counters, st);
+  hipFreeAsync(part, st);
+  if (rc) return rc;
+  WOQ_HIP(le);
   WOQ_END
 }
 

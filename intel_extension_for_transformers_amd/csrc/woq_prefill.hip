@@ -25,6 +25,7 @@
 #include "woq_attn_merge.h"
 #include "woq_device.h"
 #include "woq_launch.h"
+#include "../../include/woq_hip_experimental.h"
 
 namespace woq {
 
@@ -864,3 +865,34 @@ void launch_gather_last(const float* h, int n_seq, int T, int hidden, float* dst
 }
 
 }  // namespace woq
+
+// ---- test entry points (include/woq_hip_experimental.h): the prompt pass's two launches on their own ----------------
+extern "C" {
+
+WOQ_API int woq_probe_rope_append(void* qkv, int n_seq, int T, int start, int heads, int kv_heads, int head_dim,
+                                  const float* cos_dev, const float* sin_dev, void* kcache, void* vcache, int kv_dtype,
+                                  size_t seq_stride_elems, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(n_seq > 0 && T > 0 && start >= 0 && heads > 0 && kv_heads > 0, "QBits: bad rope_append shape");
+  const int rc = woq::launch_rope_append((_Float16*)qkv, n_seq, T, start, heads, kv_heads, head_dim, cos_dev, sin_dev,
+                                         kcache, vcache, kv_dtype, seq_stride_elems, (hipStream_t)stream);
+  if (rc) return rc;
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_attn_prefill(const void* qkv, int n_seq, int T, int start, int heads, int kv_heads, int head_dim,
+                                   const void* kcache, const void* vcache, int kv_dtype, size_t seq_stride_elems,
+                                   void* out, int window, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(n_seq > 0 && T > 0 && start >= 0 && heads > 0 && kv_heads > 0 && heads % kv_heads == 0 && window >= 0,
+            "QBits: bad attention shape");
+  const int rc = woq::launch_attn_prefill((const _Float16*)qkv, n_seq, T, start, heads, kv_heads, head_dim, kcache,
+                                          vcache, kv_dtype, seq_stride_elems, (_Float16*)out, window,
+                                          (hipStream_t)stream);
+  if (rc) return rc;
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+}  // extern "C"
