@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "woq_device.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 
 #include "woq_comm_dev.h"
 #include "woq_xq.h"
@@ -204,8 +204,6 @@ int woq_comm_launch_allreduce(woq_comm* c, float* buf, size_t n, hipStream_t st)
   return 0;
 }
 
-// the engine's form: `pushed` = the producing GEMV already stored this rank's contribution into the peers' inboxes
-// (woq_comm_dev_ptr), `xo` (optional) = the summed vector also as an XQ vector (times norm_w, sums of squares in ssq_out)
 int woq_comm_launch_allreduce_ex(woq_comm* c, float* buf, size_t n, int pushed, const float* norm_w,
                                  const woq::XqPtrs& xo, float* ssq_out, hipStream_t st) {
   if (!c || !c->connected) return woq::fail("QBits: tensor-parallel communicator is not connected");
@@ -228,7 +226,6 @@ int woq_comm_launch_allreduce_ex(woq_comm* c, float* buf, size_t n, int pushed, 
   return 0;
 }
 
-// device-resident copy of the communicator record (peer inboxes, sequence word, rank / world), valid once connected
 const woq::CommDev* woq_comm_dev_ptr(woq_comm* c) { return c && c->connected ? c->dev_copy : nullptr; }
 
 int woq_comm_launch_greedy(woq_comm* c, const float* pmax, const int32_t* pidx, int n, int vocab_offset,

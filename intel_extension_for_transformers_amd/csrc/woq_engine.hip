@@ -15,84 +15,24 @@
 #include <algorithm>
 #include <vector>
 
-#include "woq_comm_dev.h"
 #include "woq_device.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 #include "../../include/woq_hip_experimental.h"
-#include "woq_xq.h"
 #include "woq_attn_merge.h"
-
-namespace woq {
-int launch_gemv_from_header(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
-                            const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w,
-                            float eps, const float* residual, int ld_res, int epi, int nt, hipStream_t st);
-void launch_embed(const void* embed, int dtype, const int32_t* token, int hidden, float* out, const float* norm_w,
-                  const XqPtrs& xo, float* ssq_out, unsigned int* step_seq, int32_t* pos, int max_ctx, int* status,
-                  hipStream_t st);
-int launch_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
-                       const float* cs, const float* sn, int heads, int kv_heads, int D, int max_ctx, int window,
-                       float* out, int splits, int grouped, float* part, const XqPtrs& xo, hipStream_t st,
-                       unsigned int* merge_counters, int chunk_fixed, const AttnA2A* a2a_grouped = nullptr,
-                       const unsigned int* seq = nullptr, int layer = 0);
-int attn_decode_mfma_slots(int kv_dtype, int rep);
-// batch-1 GEMV over an XQ activation vector (woq_gemv_xq.hip)
-bool gemv_xq_supported(const woq_blob_header& h, int epi);
-int launch_gemv_xq(const XqPtrs& xin, const void* blob, const woq_blob_header& h, const float* bias, float* out,
-                   const float* ssq_in, float eps, const float* residual, int epi, const XqPtrs& xo,
-                   const float* next_norm_w, float* ssq_out, hipStream_t st, const CommDev* tp);
-// [RMSNorm + qkv GEMV] + [RoPE + KV append + attention] in one launch (woq_gemv_attn.hip)
-bool gemv_xq_attn_supported(const woq_blob_header& h, int heads, int kv_heads, int head_dim, int kv_dtype, int max_ctx,
-                            int window, int splits);
-int launch_gemv_xq_attn(const XqPtrs& xin, const void* blob, const woq_blob_header& h, unsigned long long* qkv_g,
-                        const float* ssq_in, float eps, const unsigned int* seq, int layer, int* status, void* kcache,
-                        void* vcache, int kv_dtype, const int32_t* pos, const float* cs, const float* sn, int heads,
-                        int kv_heads, int max_ctx, int window, float* attn_out, const XqPtrs& xq_attn, hipStream_t st,
-                        int splits = 1, unsigned long long* part_g = nullptr);
-void launch_attn_combine(const float* part, int heads, int D, int splits, float* out, const XqPtrs& xo,
-                         hipStream_t st);
-int launch_gemv_fp8_engine(const float* act, int lda, const void* hi_blob, const woq_blob_header& hi, const void* lo_q,
-                           uint32_t fp8_type, float* out, int ldo, const float* norm_w, float eps, const float* residual,
-                           int ld_res, int epi, float* gu_tmp, hipStream_t st);
-int launch_gemv_twin(const void* blob, const woq_blob_header& h, int epi, int mode, unsigned int* sink, hipStream_t st);
-void launch_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype, int hidden,
-                    int vocab, float* logits, float* pmax, int32_t* pidx, hipStream_t st);
-void launch_argmax(const float* logits, int vocab, int32_t* token, int32_t* pos, hipStream_t st);
-void launch_argmax_pairs(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
-                         hipStream_t st);
-void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
-                         const void* embed, int dtype, int hidden, float* out, const float* norm_w, const XqPtrs& xo,
-                         float* ssq_out, unsigned int* step_seq, int max_ctx, int* status, hipStream_t st);
-// prompt pass (woq_gemm_f16.hip, woq_prefill.hip)
-size_t gemm_f16_workspace_bytes(int M, int Kpad, int Npad, int planes);
-int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
-                    const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w, float eps,
-                    const float* residual, int ld_res, int epi, void* ws, int fp32_class, hipStream_t st, const void* fp8_lo = nullptr, uint32_t fp8_type = 0,
-                    size_t ws_bytes = 0);
-size_t gemm_f16_workspace_bytes_blob(int M, const woq_blob_header& h, int planes);
-void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int M, int hidden, float* out,
-                       hipStream_t st);
-int launch_rope_append(_Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD, const float* cs,
-                       const float* sn, void* kcache, void* vcache, int kv_dtype, size_t seq_stride_elems,
-                       hipStream_t st);
-int launch_attn_prefill(const _Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD,
-                        const void* kcache, const void* vcache, int kv_dtype, size_t seq_stride_elems, _Float16* out,
-                        int window, hipStream_t st);
-void set_gemm_time_events(hipEvent_t before, hipEvent_t after);
-void launch_gather_last(const float* h, int n_seq, int T, int hidden, float* dst, hipStream_t st);
-}  // namespace woq
-// device-side tensor-parallel exchange (woq_comm.hip)
-int woq_comm_launch_allreduce(woq_comm* c, float* buf, size_t n, hipStream_t st);
-int woq_comm_launch_allreduce_ex(woq_comm* c, float* buf, size_t n, int pushed, const float* norm_w,
-                                 const woq::XqPtrs& xo, float* ssq_out, hipStream_t st);
-const woq::CommDev* woq_comm_dev_ptr(woq_comm* c);
-int woq_comm_launch_greedy(woq_comm* c, const float* pmax, const int32_t* pidx, int n, int vocab_offset,
-                           int32_t* token, int32_t* pos, int32_t* log, hipStream_t st);
 
 using woq::XqPtrs;
 
+// a layer's four projections in launch order, and the epilogue each runs with (1 = SiLU(gate) * up)
+enum Proj { P_QKV, P_O, P_GATE_UP, P_DOWN, P_COUNT };
+constexpr int kProjEpi[P_COUNT] = {0, 0, 1, 0};
+// the engine's own form of woq_layer_weights (woq_engine_set_layer converts). fp8-weight layers: blob / hdr are the HI
+// nibble plane's (include/woq_blob.h woq_fp8_headers) and fp8_lo the LO plane's tile data; null for integer / table layers
+struct EngineProj { const void* blob; woq_blob_header hdr; const void* fp8_lo; };
+struct EngineLayer { EngineProj p[P_COUNT]; const float* ln1; const float* ln2; };
+
 struct woq_engine {
   woq_engine_config cfg;
-  std::vector<woq_layer_weights> layers;
+  std::vector<EngineLayer> layers;
   const void* embed = nullptr;
   int embed_dtype = WOQ_F16;
   const float* final_norm = nullptr;
@@ -110,6 +50,8 @@ struct woq_engine {
   uint8_t* kcache = nullptr;
   uint8_t* vcache = nullptr;
   size_t kv_layer_bytes = 0;
+  uint8_t* k_of(int l) const { return kcache + (size_t)l * kv_layer_bytes; }  // layer l's K / V cache (sequence 0)
+  uint8_t* v_of(int l) const { return vcache + (size_t)l * kv_layer_bytes; }
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   // the same step captured `graph_unroll` times in a row (the token / position chain lives on the device, so k steps are
@@ -140,14 +82,9 @@ struct woq_engine {
   // context slices as attention workgroups of the fused launch (round 6; WOQ_FUSE_SLICED=0: sliced contexts keep the
   // three launches qkv | slices | combine — same-box A/B runs)
   bool fuse_sliced = true;
-  // fp8-weight layers (round 6; bestla_weightonly_dispatcher.hpp:62-72): `layers` then holds the HI nibble plane's blob
-  // and header of every projection (include/woq_blob.h woq_fp8_headers), fp8_lo the LO planes' tile data. Such engines
-  // run the fp32-activation step (no XQ vectors): fp8 matrix-core GEMVs with RMSNorm / residual fused, 6 launches a layer
+  // fp8-weight layers (round 6; bestla_weightonly_dispatcher.hpp:62-72; EngineProj). Such engines run the
+  // fp32-activation step (no XQ vectors): fp8 matrix-core GEMVs with RMSNorm / residual fused, 6 launches a layer
   uint32_t fp8_type = 0;  // 0 = integer / table layers; WOQ_W_FP8_E4M3 | WOQ_W_FP8_E5M2
-  struct Fp8Lo {
-    const void* p[4];  // qkv, o, gate_up, down
-  };
-  std::vector<Fp8Lo> fp8_lo;
   float* gu_tmp = nullptr;  // fp32 [2 * inter]: the fused gate/up projection's columns before SiLU * mul
   unsigned long long* attn_part_g = nullptr;  // their partials as {tag, fp32} granules [heads][64][head_dim + 2]
   bool fused_attn_applies(const woq_blob_header& qkv_hdr) const;
@@ -163,6 +100,9 @@ struct woq_engine {
            (cfg.tp_size <= 1 ? xq_enabled : (tp_xq && comm != nullptr && allreduce == nullptr));
   }
   const woq::CommDev* tp_push() const;  // where the row-parallel GEMVs push their partial sums (null = nowhere)
+  // residual input of a row-parallel projection (o_proj / down_proj) that adds onto `stream`: rank 0 carries the
+  // residual so that the sum over ranks adds it exactly once
+  const float* tp_residual(const float* stream) const { return cfg.tp_size <= 1 || cfg.tp_rank == 0 ? stream : nullptr; }
   woq_comm* comm = nullptr;  // device-side exchange: all-reduce kernels inside the (capturable) decode step
   int vocab_offset = 0;      // first vocabulary row of this rank's lm_head shard
   int nt = 1;
@@ -215,103 +155,94 @@ const woq::CommDev* woq_engine::tp_push() const {
 
 static const XqPtrs kNoXq = {nullptr, nullptr, nullptr};
 
-// one batch-1 projection over an XQ vector
-static int engine_gemv_xq(woq_engine* e, const XqPtrs& xin, const void* blob, const woq_blob_header& h, float* out,
-                          const float* ssq_in, const float* residual, int epi, const XqPtrs& xo,
-                          const float* next_norm_w, float* ssq_out, hipStream_t st, const CommDev* tp = nullptr) {
-  return launch_gemv_xq(xin, blob, h, nullptr, out, ssq_in, e->cfg.rms_eps, residual, epi, xo, next_norm_w, ssq_out, st,
-                        tp);
+// projection k of layer l as one batch-1 GEMV over an XQ vector
+static int engine_gemv_xq(woq_engine* e, int l, Proj k, const XqPtrs& xin, float* out, const float* ssq_in,
+                          const float* residual, const XqPtrs& xo, const float* next_norm_w, float* ssq_out,
+                          hipStream_t st, const CommDev* tp = nullptr) {
+  const EngineProj& p = e->layers[l].p[k];
+  return launch_gemv_xq(xin, p.blob, p.hdr, nullptr, out, ssq_in, e->cfg.rms_eps, residual, kProjEpi[k], xo, next_norm_w,
+                        ssq_out, st, tp);
 }
 
 // The row-parallel projection that ends a sub-block (o_proj / down_proj), XQ path. One GPU: hidden += x . W, and the new
-// hidden leaves as the next GEMV's XQ input. Tensor parallel: hidden = this rank's partial sum (rank 0 carries the
-// residual), pushed into the peers' inboxes from the epilogue; the all-reduce that follows emits the XQ vector.
-static int engine_row_parallel_xq(woq_engine* e, const XqPtrs& xin, const void* blob, const woq_blob_header& h,
-                                  const XqPtrs& xo, const float* next_norm_w, float* ssq_out, hipStream_t st) {
-  const woq_engine_config& c = e->cfg;
-  if (c.tp_size <= 1)
-    return engine_gemv_xq(e, xin, blob, h, e->hidden, nullptr, e->hidden, 0, xo, next_norm_w, ssq_out, st);
-  return engine_gemv_xq(e, xin, blob, h, e->hidden, nullptr, c.tp_rank == 0 ? e->hidden : nullptr, 0, kNoXq, nullptr,
-                        nullptr, st, e->tp_push());
+// hidden leaves as the next GEMV's XQ input. Tensor parallel: hidden = this rank's partial sum (tp_residual), pushed
+// into the peers' inboxes from the epilogue; the all-reduce that follows emits the XQ vector.
+static int engine_row_parallel_xq(woq_engine* e, int l, Proj k, const XqPtrs& xin, const XqPtrs& xo,
+                                  const float* next_norm_w, float* ssq_out, hipStream_t st) {
+  if (e->cfg.tp_size <= 1)
+    return engine_gemv_xq(e, l, k, xin, e->hidden, nullptr, e->hidden, xo, next_norm_w, ssq_out, st);
+  return engine_gemv_xq(e, l, k, xin, e->hidden, nullptr, e->tp_residual(e->hidden), kNoXq, nullptr, nullptr, st,
+                        e->tp_push());
 }
 
 // XQ form of the two sub-blocks: the same five launches, activations handed over as limb blocks
 static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
   const woq_engine_config& c = e->cfg;
-  const woq_layer_weights& w = e->layers[l];
+  const EngineLayer& w = e->layers[l];
   int rc = 0;
   const int ns = e->attn_splits > 1 ? e->attn_splits : 1;  // context slices (round 6: attention workgroups of the fused launch)
-  if (e->fused_attn_applies(w.qkv_hdr)) {
-    rc = launch_gemv_xq_attn(e->xq_hidden, w.qkv_blob, w.qkv_hdr, e->qkv_g, e->ssq_part, c.rms_eps, e->step_seq, l,
-                             e->fuse_status, e->kcache + (size_t)l * e->kv_layer_bytes,
-                             e->vcache + (size_t)l * e->kv_layer_bytes,
-                             c.kv_dtype, e->pos, e->cs, e->sn, c.heads, c.kv_heads, c.max_ctx, e->window, e->attn,
-                             e->xq_attn, st, ns, e->attn_part_g);  // (slices merge among themselves: no combine launch)
+  if (e->fused_attn_applies(w.p[P_QKV].hdr)) {
+    rc = launch_gemv_xq_attn(e->xq_hidden, w.p[P_QKV].blob, w.p[P_QKV].hdr, e->qkv_g, e->ssq_part, c.rms_eps,
+                             e->step_seq, l, e->fuse_status, e->k_of(l), e->v_of(l), c.kv_dtype, e->pos, e->cs, e->sn,
+                             c.heads, c.kv_heads, c.max_ctx, e->window, e->attn, e->xq_attn, st, ns,
+                             e->attn_part_g);  // (slices merge among themselves: no combine launch)
     if (rc) return rc;
   } else {
-    rc = engine_gemv_xq(e, e->xq_hidden, w.qkv_blob, w.qkv_hdr, e->qkv, e->ssq_part, nullptr, 0, kNoXq, nullptr,
-                        nullptr, st);
+    rc = engine_gemv_xq(e, l, P_QKV, e->xq_hidden, e->qkv, e->ssq_part, nullptr, kNoXq, nullptr, nullptr, st);
     if (rc) return rc;
     const AttnA2A a2a{e->attn_part_g, 0u, e->fuse_status};
-    rc = launch_attn_decode(e->qkv, e->kcache + (size_t)l * e->kv_layer_bytes,
-                            e->vcache + (size_t)l * e->kv_layer_bytes, c.kv_dtype, e->pos, e->cs, e->sn, c.heads,
-                            c.kv_heads, c.head_dim, c.max_ctx, e->window, e->attn, e->attn_splits, e->attn_grouped,
-                            e->attn_part, e->xq_attn, st, e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk,
+    rc = launch_attn_decode(e->qkv, e->k_of(l), e->v_of(l), c.kv_dtype, e->pos, e->cs, e->sn, c.heads, c.kv_heads,
+                            c.head_dim, c.max_ctx, e->window, e->attn, e->attn_splits, e->attn_grouped, e->attn_part,
+                            e->xq_attn, st, e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk,
                             e->grouped_a2a_ok() ? &a2a : nullptr, e->step_seq, l);
     if (rc) return rc;
   }
   // hidden += attn . W_o ; the new hidden leaves as the MLP's XQ input (times ln2) with its sums of squares
-  return engine_row_parallel_xq(e, e->xq_attn, w.o_blob, w.o_hdr, e->xq_hidden, w.ln2, e->ssq_part, st);
+  return engine_row_parallel_xq(e, l, P_O, e->xq_attn, e->xq_hidden, w.ln2, e->ssq_part, st);
 }
 
 static int engine_mlp_block_xq(woq_engine* e, int l, hipStream_t st) {
-  const woq_engine_config& c = e->cfg;
-  const woq_layer_weights& w = e->layers[l];
-  const int rc = engine_gemv_xq(e, e->xq_hidden, w.gate_up_blob, w.gate_up_hdr, nullptr, e->ssq_part, nullptr, 1,
-                                e->xq_act, nullptr, nullptr, st);
+  const int rc = engine_gemv_xq(e, l, P_GATE_UP, e->xq_hidden, nullptr, e->ssq_part, nullptr, e->xq_act, nullptr, nullptr,
+                                st);
   if (rc) return rc;
-  const bool last = l + 1 == c.layers;  // the last layer's output feeds the head, which reads fp32
-  return engine_row_parallel_xq(e, e->xq_act, w.down_blob, w.down_hdr, last ? kNoXq : e->xq_hidden,
+  const bool last = l + 1 == e->cfg.layers;  // the last layer's output feeds the head, which reads fp32
+  return engine_row_parallel_xq(e, l, P_DOWN, e->xq_act, last ? kNoXq : e->xq_hidden,
                                 last ? nullptr : e->layers[l + 1].ln1, last ? nullptr : e->ssq_part, st);
 }
 
-// one batch-1 projection of the fp32-activation step: integer / table blobs through the tile / generic GEMVs, fp8 layers
-// through the fp8 matrix-core GEMV (which: 0 qkv, 1 o, 2 gate_up, 3 down)
-static int engine_linear_f32(woq_engine* e, int l, int which, const float* act, int lda, const void* blob,
-                             const woq_blob_header& h, float* out, int ldo, const float* norm_w, const float* residual,
-                             int epi, hipStream_t st) {
+// projection k of layer l in the fp32-activation step: integer / table blobs through the tile / generic GEMVs, fp8 layers
+// through the fp8 matrix-core GEMV
+static int engine_linear_f32(woq_engine* e, int l, Proj k, const float* act, int lda, float* out, int ldo,
+                             const float* norm_w, const float* residual, hipStream_t st) {
   const woq_engine_config& c = e->cfg;
+  const EngineProj& p = e->layers[l].p[k];
   if (e->fp8_type != 0)
-    return launch_gemv_fp8_engine(act, lda, blob, h, e->fp8_lo[l].p[which], e->fp8_type, out, ldo, norm_w, c.rms_eps,
-                                  residual, c.hidden, epi, e->gu_tmp, st);
-  return launch_gemv_from_header(act, WOQ_F32, lda, blob, h, nullptr, out, WOQ_F32, ldo, 1, norm_w, c.rms_eps, residual,
-                                 c.hidden, epi, e->nt, st);
+    return launch_gemv_fp8_engine(act, lda, p.blob, p.hdr, p.fp8_lo, e->fp8_type, out, ldo, norm_w, c.rms_eps, residual,
+                                  c.hidden, kProjEpi[k], e->gu_tmp, st);
+  return launch_gemv_from_header(act, WOQ_F32, lda, p.blob, p.hdr, nullptr, out, WOQ_F32, ldo, 1, norm_w, c.rms_eps,
+                                 residual, c.hidden, kProjEpi[k], e->nt, st);
 }
 
 static int engine_attn_block(woq_engine* e, int l, hipStream_t st) {
   if (e->use_xq()) return engine_attn_block_xq(e, l, st);
   const woq_engine_config& c = e->cfg;
-  const woq_layer_weights& w = e->layers[l];
-  int rc = engine_linear_f32(e, l, 0, e->hidden, c.hidden, w.qkv_blob, w.qkv_hdr, e->qkv, w.qkv_hdr.N, w.ln1, nullptr, 0, st);
+  const EngineLayer& w = e->layers[l];
+  int rc = engine_linear_f32(e, l, P_QKV, e->hidden, c.hidden, e->qkv, w.p[P_QKV].hdr.N, w.ln1, nullptr, st);
   if (rc) return rc;
-  rc = launch_attn_decode(e->qkv, e->kcache + (size_t)l * e->kv_layer_bytes, e->vcache + (size_t)l * e->kv_layer_bytes,
-                          c.kv_dtype, e->pos, e->cs, e->sn, c.heads, c.kv_heads, c.head_dim, c.max_ctx, e->window,
-                          e->attn, e->attn_splits, e->attn_grouped, e->attn_part, kNoXq, st,
-                          e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk);
+  rc = launch_attn_decode(e->qkv, e->k_of(l), e->v_of(l), c.kv_dtype, e->pos, e->cs, e->sn, c.heads, c.kv_heads,
+                          c.head_dim, c.max_ctx, e->window, e->attn, e->attn_splits, e->attn_grouped, e->attn_part, kNoXq,
+                          st, e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk);
   if (rc) return rc;
-  // row-parallel o_proj: rank 0 carries the residual so that the sum over ranks adds it exactly once
-  const float* res = (c.tp_size <= 1 || c.tp_rank == 0) ? e->hidden : nullptr;
-  return engine_linear_f32(e, l, 1, e->attn, c.heads * c.head_dim, w.o_blob, w.o_hdr, e->hidden, c.hidden, nullptr, res, 0, st);
+  return engine_linear_f32(e, l, P_O, e->attn, c.heads * c.head_dim, e->hidden, c.hidden, nullptr,
+                           e->tp_residual(e->hidden), st);
 }
 
 static int engine_mlp_block(woq_engine* e, int l, hipStream_t st) {
   if (e->use_xq()) return engine_mlp_block_xq(e, l, st);
   const woq_engine_config& c = e->cfg;
-  const woq_layer_weights& w = e->layers[l];
-  int rc = engine_linear_f32(e, l, 2, e->hidden, c.hidden, w.gate_up_blob, w.gate_up_hdr, e->act, c.inter, w.ln2, nullptr, 1, st);
+  const int rc = engine_linear_f32(e, l, P_GATE_UP, e->hidden, c.hidden, e->act, c.inter, e->layers[l].ln2, nullptr, st);
   if (rc) return rc;
-  const float* res = (c.tp_size <= 1 || c.tp_rank == 0) ? e->hidden : nullptr;
-  return engine_linear_f32(e, l, 3, e->act, c.inter, w.down_blob, w.down_hdr, e->hidden, c.hidden, nullptr, res, 0, st);
+  return engine_linear_f32(e, l, P_DOWN, e->act, c.inter, e->hidden, c.hidden, nullptr, e->tp_residual(e->hidden), st);
 }
 
 // fuse_next: this step's greedy argmax and the NEXT step's embedding kernel as one launch (steps chained inside one
@@ -359,7 +290,6 @@ static int engine_allreduce_after(woq_engine* e, int l, int which, hipStream_t s
 
 // prompt pass: [rows, hidden] partials. Bandwidth-bound, so the bound callback (RCCL through torch.distributed) is the
 // transport when there is one; without it the device exchange carries the rows in inbox-sized pieces.
-size_t woq_comm_max_elems(woq_comm* c);
 static int engine_allreduce_rows(woq_engine* e, float* buf, size_t count, hipStream_t st) {
   if (e->cfg.tp_size <= 1) return 0;
   if (e->allreduce) {
@@ -410,10 +340,10 @@ static int engine_prefill_reserve(woq_engine* e, size_t rows) {
   // the largest call's workspace over EVERY layer's blobs: packed activation tiles + scales (+ the fragment image of a
   // table-type blob, so that such prompt passes allocate nothing per call either)
   size_t ws = 0;
-  for (const woq_layer_weights& w : e->layers)
-    for (const woq_blob_header* h : {&w.qkv_hdr, &w.o_hdr, &w.gate_up_hdr, &w.down_hdr})
-      ws = std::max(ws, gemm_f16_workspace_bytes_blob((int)rows, *h, 1) +
-                            (e->fp8_type ? (size_t)(h->Npad / WOQ_TILE_N) * (h->Kpad / WOQ_TILE_K) * 4 * 1024 : 0));
+  for (const EngineLayer& w : e->layers)
+    for (const EngineProj& p : w.p)
+      ws = std::max(ws, gemm_f16_workspace_bytes_blob((int)rows, p.hdr, 1) +
+                            (e->fp8_type ? (size_t)(p.hdr.Npad / WOQ_TILE_N) * (p.hdr.Kpad / WOQ_TILE_K) * 4 * 1024 : 0));
   if (rows <= e->pf_rows && ws <= e->pf_ws_bytes) return 0;
   WOQ_HIP(hipDeviceSynchronize());
   for (void* p : {(void*)e->pf_h, (void*)e->pf_qkv, (void*)e->pf_attn, (void*)e->pf_act, e->pf_ws})
@@ -440,31 +370,30 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
   int rc = engine_prefill_reserve(e, (size_t)M);
   if (rc) return rc;
   launch_embed_rows(e->embed, e->embed_dtype, tokens, M, c.hidden, e->pf_h, st);
-  const float* res = (c.tp_size <= 1 || c.tp_rank == 0) ? e->pf_h : nullptr;
-  auto lo_of = [&](int l, int which) -> const void* { return e->fp8_type ? e->fp8_lo[l].p[which] : nullptr; };
+  // projection k of layer l over all M rows: the column-parallel ones (qkv, gate/up) read the residual stream through
+  // RMSNorm `norm_w`, the row-parallel ones (o, down) add onto it
+  auto gemm = [&](int l, Proj k, const void* act, int act_dtype, int lda, void* out, int out_dtype, int ldo,
+                  const float* norm_w) {
+    const EngineProj& p = e->layers[l].p[k];
+    const bool rowp = k == P_O || k == P_DOWN;
+    return launch_gemm_f16(act, act_dtype, lda, p.blob, p.hdr, nullptr, out, out_dtype, ldo, M, norm_w,
+                           rowp ? 0.f : c.rms_eps, rowp ? e->tp_residual(e->pf_h) : nullptr, rowp ? c.hidden : 0,
+                           kProjEpi[k], e->pf_ws, 0, st, p.fp8_lo, e->fp8_type, e->pf_ws_bytes);
+  };
   for (int l = 0; l < c.layers; ++l) {
-    const woq_layer_weights& w = e->layers[l];
-    uint8_t* kc = e->kcache + (size_t)l * e->kv_layer_bytes;
-    uint8_t* vc = e->vcache + (size_t)l * e->kv_layer_bytes;
-    if ((rc = launch_gemm_f16(e->pf_h, WOQ_F32, c.hidden, w.qkv_blob, w.qkv_hdr, nullptr, e->pf_qkv, WOQ_F16, qkv_n, M,
-                              w.ln1, c.rms_eps, nullptr, 0, 0, e->pf_ws, 0, st, lo_of(l, 0), e->fp8_type, e->pf_ws_bytes)) != 0)
-      return rc;
+    const EngineLayer& w = e->layers[l];
+    uint8_t *kc = e->k_of(l), *vc = e->v_of(l);
+    if ((rc = gemm(l, P_QKV, e->pf_h, WOQ_F32, c.hidden, e->pf_qkv, WOQ_F16, qkv_n, w.ln1)) != 0) return rc;
     if ((rc = launch_rope_append(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, e->cs, e->sn, kc, vc,
                                  c.kv_dtype, seq_stride, st)) != 0)
       return rc;
     if ((rc = launch_attn_prefill(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, kc, vc, c.kv_dtype,
                                   seq_stride, e->pf_attn, e->window, st)) != 0)
       return rc;
-    if ((rc = launch_gemm_f16(e->pf_attn, WOQ_F16, c.heads * c.head_dim, w.o_blob, w.o_hdr, nullptr, e->pf_h, WOQ_F32,
-                              c.hidden, M, nullptr, 0.f, res, c.hidden, 0, e->pf_ws, 0, st, lo_of(l, 1), e->fp8_type, e->pf_ws_bytes)) != 0)
-      return rc;
+    if ((rc = gemm(l, P_O, e->pf_attn, WOQ_F16, c.heads * c.head_dim, e->pf_h, WOQ_F32, c.hidden, nullptr)) != 0) return rc;
     if ((rc = engine_allreduce_rows(e, e->pf_h, (size_t)M * c.hidden, st)) != 0) return rc;
-    if ((rc = launch_gemm_f16(e->pf_h, WOQ_F32, c.hidden, w.gate_up_blob, w.gate_up_hdr, nullptr, e->pf_act, WOQ_F16,
-                              c.inter, M, w.ln2, c.rms_eps, nullptr, 0, 1, e->pf_ws, 0, st, lo_of(l, 2), e->fp8_type, e->pf_ws_bytes)) != 0)
-      return rc;
-    if ((rc = launch_gemm_f16(e->pf_act, WOQ_F16, c.inter, w.down_blob, w.down_hdr, nullptr, e->pf_h, WOQ_F32,
-                              c.hidden, M, nullptr, 0.f, res, c.hidden, 0, e->pf_ws, 0, st, lo_of(l, 3), e->fp8_type, e->pf_ws_bytes)) != 0)
-      return rc;
+    if ((rc = gemm(l, P_GATE_UP, e->pf_h, WOQ_F32, c.hidden, e->pf_act, WOQ_F16, c.inter, w.ln2)) != 0) return rc;
+    if ((rc = gemm(l, P_DOWN, e->pf_act, WOQ_F16, c.inter, e->pf_h, WOQ_F32, c.hidden, nullptr)) != 0) return rc;
     if ((rc = engine_allreduce_rows(e, e->pf_h, (size_t)M * c.hidden, st)) != 0) return rc;
   }
   // logits of every sequence's last position; sequence 0 also lands in the decode step's buffers
@@ -619,7 +548,7 @@ int woq_engine_clear_status(woq_engine* e, void* stream) {
 }
 int woq_engine_fuse_attn(woq_engine* e) {
   if (!e || !e->use_xq() || e->layers.empty()) return 0;
-  return e->fused_attn_applies(e->layers[0].qkv_hdr) ? 1 : 0;
+  return e->fused_attn_applies(e->layers[0].p[P_QKV].hdr) ? 1 : 0;
 }
 void* woq_engine_kv_cache_ptr(woq_engine* e, int which) { return e ? (which ? e->vcache : e->kcache) : nullptr; }
 
@@ -716,12 +645,18 @@ int woq_engine_create(const woq_engine_config* cfg, woq_engine** out) {
   WOQ_END
 }
 
-void woq_engine_destroy(woq_engine* e) {
-  if (!e) return;
+static void engine_drop_graphs(woq_engine* e) {
   if (e->exec) hipGraphExecDestroy(e->exec);
   if (e->graph) hipGraphDestroy(e->graph);
   if (e->exec_k) hipGraphExecDestroy(e->exec_k);
   if (e->graph_k) hipGraphDestroy(e->graph_k);
+  e->exec = e->exec_k = nullptr;
+  e->graph = e->graph_k = nullptr;
+}
+
+void woq_engine_destroy(woq_engine* e) {
+  if (!e) return;
+  engine_drop_graphs(e);
   for (void* p : e->owned) hipFree(p);
   for (void* p : {(void*)e->pf_h, (void*)e->pf_qkv, (void*)e->pf_attn, (void*)e->pf_act, e->pf_ws})
     if (p) hipFree(p);
@@ -732,52 +667,50 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
   WOQ_TRY
   WOQ_CHECK(e && w && layer >= 0 && layer < e->cfg.layers, "QBits: bad layer index");
   const woq_engine_config& c = e->cfg;
-  // int4, or (round 4) a 4-bit table type: the same kernels with a digit-plane unpack (woq_gemv_common.h LutArgs); the
-  // fused qkv + attention launch stays int4-only (its support check says no)
-  auto takes = [](const woq_blob_header& h) {
-    return h.weight_type == WOQ_W_INT4_CLIP || (is_table_type(h.weight_type) && h.off_zp == 0);
-  };
+  const EngineLayer in = {{{w->qkv_blob, w->qkv_hdr, nullptr},
+                           {w->o_blob, w->o_hdr, nullptr},
+                           {w->gate_up_blob, w->gate_up_hdr, nullptr},
+                           {w->down_blob, w->down_hdr, nullptr}},
+                          w->ln1,
+                          w->ln2};
+  auto all = [&](auto pred) { return std::all_of(std::begin(in.p), std::end(in.p), pred); };
+  const woq_blob_header &qkv = in.p[P_QKV].hdr, &o = in.p[P_O].hdr, &gu = in.p[P_GATE_UP].hdr, &down = in.p[P_DOWN].hdr;
   // round 6: fp8_e4m3 / fp8_e5m2 layers (all four projections of every layer the same type; one GPU)
-  const bool fp8 = woq_weight_is_fp8(w->qkv_hdr.weight_type);
+  const bool fp8 = woq_weight_is_fp8(qkv.weight_type);
   if (fp8) {
-    WOQ_CHECK(w->o_hdr.weight_type == w->qkv_hdr.weight_type && w->gate_up_hdr.weight_type == w->qkv_hdr.weight_type &&
-                  w->down_hdr.weight_type == w->qkv_hdr.weight_type,
+    WOQ_CHECK(all([&](const EngineProj& p) { return p.hdr.weight_type == qkv.weight_type; }),
               "QBits: an fp8 layer needs all four projections in the same fp8 type");
     WOQ_CHECK(c.tp_size <= 1, "QBits: fp8-weight layers run on one GPU (no tensor-parallel decode path)");
   } else {
-    WOQ_CHECK(takes(w->qkv_hdr) && takes(w->o_hdr) && takes(w->gate_up_hdr) && takes(w->down_hdr),
+    // int4, or (round 4) a 4-bit table type: the same kernels with a digit-plane unpack (woq_gemv_common.h LutArgs); the
+    // fused qkv + attention launch stays int4-only (its support check says no)
+    WOQ_CHECK(all([](const EngineProj& p) {
+                return p.hdr.weight_type == WOQ_W_INT4_CLIP || (is_table_type(p.hdr.weight_type) && p.hdr.off_zp == 0);
+              }),
               "QBits: the fused engine takes int4_clip / nf4 / fp4 / fp8 layers");
   }
 
-  WOQ_CHECK(w->qkv_hdr.magic == WOQ_BLOB_MAGIC && w->o_hdr.magic == WOQ_BLOB_MAGIC &&
-                w->gate_up_hdr.magic == WOQ_BLOB_MAGIC && w->down_hdr.magic == WOQ_BLOB_MAGIC,
+  WOQ_CHECK(all([](const EngineProj& p) { return p.hdr.magic == WOQ_BLOB_MAGIC; }),
             "QBits: layer weights must be WQH1 blobs");
-  WOQ_CHECK(w->qkv_hdr.K == c.hidden && w->qkv_hdr.N == (c.heads + 2 * c.kv_heads) * c.head_dim,
-            "QBits: qkv blob shape mismatch");
-  WOQ_CHECK(w->o_hdr.K == c.heads * c.head_dim && w->o_hdr.N == c.hidden, "QBits: o_proj blob shape mismatch");
-  WOQ_CHECK(w->gate_up_hdr.K == c.hidden && w->gate_up_hdr.N == 2 * c.inter && (c.inter % 16) == 0,
+  WOQ_CHECK(qkv.K == c.hidden && qkv.N == (c.heads + 2 * c.kv_heads) * c.head_dim, "QBits: qkv blob shape mismatch");
+  WOQ_CHECK(o.K == c.heads * c.head_dim && o.N == c.hidden, "QBits: o_proj blob shape mismatch");
+  WOQ_CHECK(gu.K == c.hidden && gu.N == 2 * c.inter && (c.inter % 16) == 0,
             "QBits: gate_up blob shape mismatch (inter must be a multiple of 16)");
-  WOQ_CHECK(w->down_hdr.K == c.inter && w->down_hdr.N == c.hidden, "QBits: down_proj blob shape mismatch");
-  e->layers[layer] = *w;
+  WOQ_CHECK(down.K == c.inter && down.N == c.hidden, "QBits: down_proj blob shape mismatch");
+  e->layers[layer] = in;
   if (fp8) {
     // the composite container [outer header][HI blob][LO blob] (include/woq_blob.h): the engine keeps the HI plane as the
-    // layer's blob / header and the LO plane's tile data beside it; its headers follow from the outer one's parameters
-    if (e->fp8_lo.empty()) e->fp8_lo.resize(c.layers, woq_engine::Fp8Lo{{nullptr, nullptr, nullptr, nullptr}});
-    WOQ_CHECK(e->fp8_type == 0 || e->fp8_type == w->qkv_hdr.weight_type, "QBits: one fp8 type per engine");
-    e->fp8_type = w->qkv_hdr.weight_type;
-    woq_layer_weights& d = e->layers[layer];
-    const void** blobs[4] = {&d.qkv_blob, &d.o_blob, &d.gate_up_blob, &d.down_blob};
-    woq_blob_header* hdrs[4] = {&d.qkv_hdr, &d.o_hdr, &d.gate_up_hdr, &d.down_hdr};
-    for (int i = 0; i < 4; ++i) {
-      const woq_blob_header outer = *hdrs[i];
+    // projection's blob / header and the LO plane's tile data beside it; its headers follow from the outer one's parameters
+    WOQ_CHECK(e->fp8_type == 0 || e->fp8_type == qkv.weight_type, "QBits: one fp8 type per engine");
+    e->fp8_type = qkv.weight_type;
+    for (EngineProj& p : e->layers[layer].p) {
+      const woq_blob_header outer = p.hdr;
       woq_blob_header o2, hi, lo;
       WOQ_CHECK(outer.off_shuffle == 0, "QBits: fp8 layers with g_idx stay on the module path");
       WOQ_CHECK(woq_fp8_headers(&o2, &hi, &lo, outer.K, outer.N, outer.group, outer.weight_type, outer.scale_type,
                                 outer.compute_type, 0) == 0, "QBits: corrupt fp8 header");
-      const uint8_t* base = (const uint8_t*)*blobs[i];
-      *blobs[i] = base + outer.off_q;                                   // the HI plane's blob
-      *hdrs[i] = hi;
-      e->fp8_lo[layer].p[i] = base + outer.off_scale + lo.off_q;        // the LO plane's tile data
+      const uint8_t* base = (const uint8_t*)p.blob;
+      p = {base + outer.off_q, hi, base + outer.off_scale + lo.off_q};  // the HI plane's blob, the LO plane's tile data
     }
     if (e->gu_tmp == nullptr) {
       WOQ_HIP(hipMalloc((void**)&e->gu_tmp, (size_t)2 * c.inter * 4));
@@ -787,8 +720,7 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
     return 0;
   }
   WOQ_CHECK(e->fp8_type == 0, "QBits: fp8 and integer layers cannot be mixed in one engine");
-  e->xq_shapes_ok = e->xq_shapes_ok && gemv_xq_supported(w->qkv_hdr, 0) && gemv_xq_supported(w->o_hdr, 0) &&
-                    gemv_xq_supported(w->gate_up_hdr, 1) && gemv_xq_supported(w->down_hdr, 0);
+  for (int k = 0; k < P_COUNT; ++k) e->xq_shapes_ok = e->xq_shapes_ok && gemv_xq_supported(in.p[k].hdr, kProjEpi[k]);
   WOQ_END
 }
 
@@ -885,22 +817,7 @@ int woq_engine_capture(woq_engine* e, int greedy, void* stream) {
   int rc = engine_step_impl(e, 0, st);
   if (rc) return rc;
   WOQ_HIP(hipStreamSynchronize(st));
-  if (e->exec) {
-    hipGraphExecDestroy(e->exec);
-    e->exec = nullptr;
-  }
-  if (e->graph) {
-    hipGraphDestroy(e->graph);
-    e->graph = nullptr;
-  }
-  if (e->exec_k) {
-    hipGraphExecDestroy(e->exec_k);
-    e->exec_k = nullptr;
-  }
-  if (e->graph_k) {
-    hipGraphDestroy(e->graph_k);
-    e->graph_k = nullptr;
-  }
+  engine_drop_graphs(e);
   WOQ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
   rc = engine_step_impl(e, greedy, st);
   hipError_t ce = hipStreamEndCapture(st, &e->graph);
@@ -957,12 +874,10 @@ int woq_engine_time_gemv_mask(woq_engine* e, int mask, int reps, void* stream, f
   hipStream_t st = (hipStream_t)stream;
   const woq_engine_config& c = e->cfg;
   double bytes = 0;
-  for (int l = 0; l < c.layers; ++l) {
-    const woq_layer_weights& w = e->layers[l];
-    const woq_blob_header* hs[4] = {&w.qkv_hdr, &w.o_hdr, &w.gate_up_hdr, &w.down_hdr};
-    for (int j = 0; j < 4; ++j) {
-      if (!((mask >> j) & 1)) continue;
-      const woq_blob_header& h = *hs[j];
+  for (const EngineLayer& w : e->layers) {
+    for (int k = 0; k < P_COUNT; ++k) {
+      if (!((mask >> k) & 1)) continue;
+      const woq_blob_header& h = w.p[k].hdr;
       // algorithmic bytes: int4 payload + scales (+ zero points), unpadded
       bytes += (double)h.K * h.N * 0.5 + (double)h.n_groups * h.N * (h.scale_type == WOQ_F32 ? 4 : 2) +
                (h.off_zp ? (double)h.n_groups * h.N * 0.5 : 0.0);
@@ -970,38 +885,39 @@ int woq_engine_time_gemv_mask(woq_engine* e, int mask, int reps, void* stream, f
   }
   auto pass = [&](hipStream_t st) -> int {
     for (int l = 0; l < c.layers; ++l) {
-      const woq_layer_weights& w = e->layers[l];
+      const EngineLayer& w = e->layers[l];
+      const EngineProj &qkv = w.p[P_QKV], &o = w.p[P_O], &gu = w.p[P_GATE_UP], &down = w.p[P_DOWN];
       int rc;
       if (e->use_xq()) {  // the step's own four GEMV launches: same kernels, epilogues, XQ outputs, residual chaining
         const bool last = l + 1 == c.layers;
-        if ((mask & 1) && (rc = engine_gemv_xq(e, e->xq_hidden, w.qkv_blob, w.qkv_hdr, e->qkv, e->ssq_part, nullptr, 0,
-                                               kNoXq, nullptr, nullptr, st)) != 0)
+        if ((mask & 1) && (rc = engine_gemv_xq(e, l, P_QKV, e->xq_hidden, e->qkv, e->ssq_part, nullptr, kNoXq, nullptr,
+                                               nullptr, st)) != 0)
           return rc;
-        if ((mask & 2) && (rc = engine_gemv_xq(e, e->xq_attn, w.o_blob, w.o_hdr, e->hidden, nullptr, e->hidden, 0,
-                                               e->xq_hidden, w.ln2, e->ssq_part, st)) != 0)
+        if ((mask & 2) && (rc = engine_gemv_xq(e, l, P_O, e->xq_attn, e->hidden, nullptr, e->hidden, e->xq_hidden, w.ln2,
+                                               e->ssq_part, st)) != 0)
           return rc;
-        if ((mask & 4) && (rc = engine_gemv_xq(e, e->xq_hidden, w.gate_up_blob, w.gate_up_hdr, nullptr, e->ssq_part,
-                                               nullptr, 1, e->xq_act, nullptr, nullptr, st)) != 0)
+        if ((mask & 4) && (rc = engine_gemv_xq(e, l, P_GATE_UP, e->xq_hidden, nullptr, e->ssq_part, nullptr, e->xq_act,
+                                               nullptr, nullptr, st)) != 0)
           return rc;
-        if ((mask & 8) && (rc = engine_gemv_xq(e, e->xq_act, w.down_blob, w.down_hdr, e->hidden, nullptr, e->hidden, 0,
+        if ((mask & 8) && (rc = engine_gemv_xq(e, l, P_DOWN, e->xq_act, e->hidden, nullptr, e->hidden,
                                                last ? kNoXq : e->xq_hidden, last ? nullptr : e->layers[l + 1].ln1,
                                                last ? nullptr : e->ssq_part, st)) != 0)
           return rc;
         continue;
       }
-      rc = (mask & 1) ? launch_gemv_from_header(e->hidden, WOQ_F32, c.hidden, w.qkv_blob, w.qkv_hdr, nullptr, e->qkv,
-                                                WOQ_F32, w.qkv_hdr.N, 1, w.ln1, c.rms_eps, nullptr, 0, 0, e->nt, st)
+      rc = (mask & 1) ? launch_gemv_from_header(e->hidden, WOQ_F32, c.hidden, qkv.blob, qkv.hdr, nullptr, e->qkv,
+                                                WOQ_F32, qkv.hdr.N, 1, w.ln1, c.rms_eps, nullptr, 0, 0, e->nt, st)
                       : 0;
       if (rc) return rc;
-      rc = (mask & 2) ? launch_gemv_from_header(e->attn, WOQ_F32, c.heads * c.head_dim, w.o_blob, w.o_hdr, nullptr,
+      rc = (mask & 2) ? launch_gemv_from_header(e->attn, WOQ_F32, c.heads * c.head_dim, o.blob, o.hdr, nullptr,
                                                 e->qkv, WOQ_F32, c.hidden, 1, nullptr, 0.f, nullptr, 0, 0, e->nt, st)
                       : 0;
       if (rc) return rc;
-      rc = (mask & 4) ? launch_gemv_from_header(e->hidden, WOQ_F32, c.hidden, w.gate_up_blob, w.gate_up_hdr, nullptr,
+      rc = (mask & 4) ? launch_gemv_from_header(e->hidden, WOQ_F32, c.hidden, gu.blob, gu.hdr, nullptr,
                                                 e->act, WOQ_F32, c.inter, 1, w.ln2, c.rms_eps, nullptr, 0, 1, e->nt, st)
                       : 0;
       if (rc) return rc;
-      rc = (mask & 8) ? launch_gemv_from_header(e->act, WOQ_F32, c.inter, w.down_blob, w.down_hdr, nullptr, e->qkv,
+      rc = (mask & 8) ? launch_gemv_from_header(e->act, WOQ_F32, c.inter, down.blob, down.hdr, nullptr, e->qkv,
                                                 WOQ_F32, c.hidden, 1, nullptr, 0.f, nullptr, 0, 0, e->nt, st)
                       : 0;
       if (rc) return rc;
@@ -1028,14 +944,11 @@ int woq_engine_time_twin(woq_engine* e, int mode, int reps, void* stream, float*
   hipStream_t st = (hipStream_t)stream;
   unsigned int* sink = (unsigned int*)e->am_idx;  // any device word; never written (the twins' store is unreachable)
   auto pass = [&](hipStream_t st) -> int {
-    for (int l = 0; l < e->cfg.layers; ++l) {
-      const woq_layer_weights& w = e->layers[l];
-      int rc;
-      if ((rc = launch_gemv_twin(w.qkv_blob, w.qkv_hdr, 0, mode, sink, st)) != 0) return rc;
-      if ((rc = launch_gemv_twin(w.o_blob, w.o_hdr, 0, mode, sink, st)) != 0) return rc;
-      if ((rc = launch_gemv_twin(w.gate_up_blob, w.gate_up_hdr, 1, mode, sink, st)) != 0) return rc;
-      if ((rc = launch_gemv_twin(w.down_blob, w.down_hdr, 0, mode, sink, st)) != 0) return rc;
-    }
+    for (const EngineLayer& w : e->layers)
+      for (int k = 0; k < P_COUNT; ++k) {
+        const int rc = launch_gemv_twin(w.p[k].blob, w.p[k].hdr, kProjEpi[k], mode, sink, st);
+        if (rc) return rc;
+      }
     return 0;
   };
   // empty kernels are shorter than the host's launch call (~2.6 us): issued eagerly the pass would be host-bound and
@@ -1056,7 +969,8 @@ int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, int reps,
   WOQ_CHECK((size_t)n_rows <= e->pf_rows && n_rows > 8, "QBits: run a prompt pass of at least n_rows rows first");
   hipStream_t st = (hipStream_t)stream;
   const woq_engine_config& c = e->cfg;
-  const woq_layer_weights& w = e->layers[layer];
+  const EngineLayer& w = e->layers[layer];
+  const EngineProj& gu = w.p[P_GATE_UP];
   hipEvent_t k0, k1, c0, c1;
   WOQ_HIP(hipEventCreate(&k0));
   WOQ_HIP(hipEventCreate(&k1));
@@ -1066,7 +980,7 @@ int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, int reps,
   for (int r = 0; r <= reps; ++r) {  // pass 0 warms up
     WOQ_HIP(hipEventRecord(c0, st));
     set_gemm_time_events(k0, k1);
-    const int rc = launch_gemm_f16(e->pf_h, WOQ_F32, c.hidden, w.gate_up_blob, w.gate_up_hdr, nullptr, e->pf_act, WOQ_F16,
+    const int rc = launch_gemm_f16(e->pf_h, WOQ_F32, c.hidden, gu.blob, gu.hdr, nullptr, e->pf_act, WOQ_F16,
                                    c.inter, n_rows, w.ln2, c.rms_eps, nullptr, 0, 1, e->pf_ws, 0, st, nullptr, 0, e->pf_ws_bytes);
     set_gemm_time_events(nullptr, nullptr);
     if (rc) return rc;

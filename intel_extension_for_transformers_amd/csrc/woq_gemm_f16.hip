@@ -43,7 +43,7 @@
 
 #include "../../include/woq_hip_experimental.h"
 #include "woq_device.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 
 namespace woq {
 static hipEvent_t g_gemm_ev0 = nullptr, g_gemm_ev1 = nullptr;
@@ -1014,17 +1014,11 @@ size_t gemm_f16_workspace_bytes(int M, int Kpad, int Npad, int planes) {
   return ((base + 255) & ~(size_t)255) + SPLITK_WS;
 }
 
-// the same for one blob, fragment image of the float weight types included (4-8x the blob: what made table-type prompt
-// passes allocate per call while the engine's workspace sat unused — ADVICE r04)
 size_t gemm_f16_workspace_bytes_blob(int M, const woq_blob_header& h, int planes) {
   const size_t tiles = (size_t)(h.Npad / WOQ_TILE_N) * (h.Kpad / WOQ_TILE_K);
   return gemm_f16_workspace_bytes(M, h.Kpad, h.Npad, planes) + (is_table_type(h.weight_type) ? tiles * 4 * planes * 1024 : 0);
 }
 
-// out[M,N] = act[M,K] . W_deq (+ bias) with fp16 operands. `ws` = caller workspace of gemm_f16_workspace_bytes or
-// null (stream-ordered allocation per call, like the reference's per-call amalloc,
-// bestla_weightonly_dispatcher.cpp:108-118,179). norm_w/eps: RMSNorm fused into the pack pass (null = none);
-// residual / epi: see GemmF16Args; fp32_class: the three-product hi + lo form (compute_dtype fp32).
 int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
                     const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w, float eps,
                     const float* residual, int ld_res, int epi, void* ws, int fp32_class, hipStream_t st,
@@ -1178,8 +1172,6 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   return rc;
 }
 
-// events recorded on the launch stream right before / after the GEMM kernel of the next launch_gemm_f16 calls
-// (null = off): lets bench.py time the dominant prefill kernel without its pack pass
 void set_gemm_time_events(hipEvent_t before, hipEvent_t after) {
   g_gemm_ev0 = before;
   g_gemm_ev1 = after;

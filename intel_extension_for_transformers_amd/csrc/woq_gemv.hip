@@ -14,17 +14,11 @@
 // arithmetic on the same blob (activation rows staged in LDS as fp32, one workgroup per 16-column tile, waves
 // interleaved over the K tiles, wave-shuffle + LDS reduction). It is correct for every blob; it is not tuned.
 #include "woq_device.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 
 namespace woq {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_header& h, const float* norm_w,
-                       int epi, int out_dtype);
-int launch_gemv_tile(const void* act, int act_dtype, int lda, int M, const void* blob, const woq_blob_header& h,
-                     const float* bias, void* out, int out_dtype, int ldo, const float* norm_w, float eps,
-                     const float* residual, int ld_res, int epi, hipStream_t st);
 
 struct GenArgs {
   const u32x4* q;
@@ -225,8 +219,6 @@ static int launch_gemv_generic(const void* act, int act_dtype, int lda, int M, c
   return 0;
 }
 
-// Shared by woq_linear and the decode engine: rows in chunks through the i8 tile kernel when the call qualifies,
-// through the generic kernel otherwise. `nt` is reserved (weight loads are always non-temporal).
 int launch_gemv_from_header(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
                             const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w,
                             float eps, const float* residual, int ld_res, int epi, int nt, hipStream_t st) {
@@ -253,16 +245,6 @@ int launch_gemv_from_header(const void* act, int act_dtype, int lda, const void*
   return 0;
 }
 
-bool gemv_fp8_mfma_supported(const void* act, int act_dtype, int lda, const woq_blob_header& hi);
-int launch_gemv_fp8_mfma(const void* act, int act_dtype, int lda, int M, const void* hi_blob, const woq_blob_header& hi,
-                         const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo,
-                         hipStream_t st, const float* norm_w = nullptr, float eps = 0.f, const float* residual = nullptr,
-                         int ld_res = 0);
-
-// fp8 weights at decode row counts: the fp8-MFMA kernel (woq_gemv_fp8.hip: code bytes straight into the matrix cores,
-// activations as base-16 digits; round 4) where it takes the call, rows in chunks of 8; otherwise (per-32 / per-64 /
-// per-256 scales, g_idx, misaligned rows, K beyond 8192) the lookup kernel reading both nibble planes, rows in chunks of GEN_MAXM.
-// `hi` = the HI plane's header (scales, shuffle), `lo_q` = the LO plane's qdata.
 int launch_gemv_fp8(const void* act, int act_dtype, int lda, const void* hi_blob, const woq_blob_header& hi,
                     const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo, int M,
                     hipStream_t st) {
@@ -288,13 +270,6 @@ int launch_gemv_fp8(const void* act, int act_dtype, int lda, const void* hi_blob
   return 0;
 }
 
-void launch_silu_mul_tiles(const float* gu, int inter, float* act, hipStream_t st);
-
-// One batch-1 projection of an fp8-weight layer inside the decode engine (round 6): fp32 activation row in, fp32 out,
-// with the engine's fused prologue / epilogues — RMSNorm (norm_w, eps), residual add, and for the fused gate/up
-// projection (epi 1) SiLU(gate) * up. The fp8 matrix-core kernel (woq_gemv_fp8.hip) carries the norm and the residual
-// itself; its gate/up call writes the 2 * inter interleaved columns to `gu_tmp` and a small launch pairs them. Blobs it
-// does not take (g_idx, groups of 256, K beyond 12288) run the lookup kernel, which has all three built in.
 int launch_gemv_fp8_engine(const float* act, int lda, const void* hi_blob, const woq_blob_header& hi, const void* lo_q,
                            uint32_t fp8_type, float* out, int ldo, const float* norm_w, float eps, const float* residual,
                            int ld_res, int epi, float* gu_tmp, hipStream_t st) {

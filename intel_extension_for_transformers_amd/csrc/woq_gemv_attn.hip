@@ -24,7 +24,7 @@
 #include "woq_attn_decode.h"
 #include "woq_gemv_common.h"
 #include "woq_gemv_xqs.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 #include "woq_xq.h"
 
 namespace woq {
@@ -108,7 +108,6 @@ static int fused_attn_span(int max_ctx, int window, int splits) {
   return splits > 1 ? ((((reach + splits - 1) / splits) + 63) & ~63) + 64 : reach;
 }
 
-// does the fused launch take this (blob, attention) combination?
 bool gemv_xq_attn_supported(const woq_blob_header& h, int heads, int kv_heads, int head_dim, int kv_dtype, int max_ctx,
                             int window, int splits) {
   if (h.weight_type != WOQ_W_INT4_CLIP || h.off_shuffle != 0 || h.K != h.Kpad || h.N != h.Npad) return false;
@@ -181,10 +180,6 @@ static int launch_fused_kv(const FusedLaunch& a, int smode, bool asym, bool s32,
   return woq::fail("QBits: bad fused qkv + attention configuration");
 }
 
-// qkv_g ({tag, fp32} granules [(heads + 2 kv_heads) * 128]) = xin . W_qkv_deq * rsqrt(mean(x^2) + eps); per head, as its granules
-// arrive: RoPE, KV append at *pos, attention over the cache -> attn_out (+ its XQ form).
-// splits > 1: `splits` context slices per head; they merge among themselves through the tagged granules `part_g`
-// ([heads][64][130] x 8 B) and write attn_out / xq_attn — no combine launch.
 int launch_gemv_xq_attn(const XqPtrs& xin, const void* blob, const woq_blob_header& h, unsigned long long* qkv_g,
                         const float* ssq_in, float eps, const unsigned int* seq, int layer, int* status, void* kcache,
                         void* vcache, int kv_dtype, const int32_t* pos, const float* cs, const float* sn, int heads,

@@ -98,14 +98,6 @@ __device__ __forceinline__ void int4_b(uint32_t w0, uint32_t w1, i32x4& b) {
   b = i32x4{(int)((w0 << 4) & 0xf0f0f0f0u), (int)(w0 & 0xf0f0f0f0u), (int)((w1 << 4) & 0xf0f0f0f0u),
             (int)(w1 & 0xf0f0f0f0u)};
 }
-// host: the digit planes of a table weight type; returns NDIG (1 | 2 | 3), 0 = not a table. compute_type (woq_blob.h):
-// nf4 takes three planes for fp32 compute and two (table held to 2^-16 of its largest entry — finer than the bf16 / fp16
-// operands those modes ask for) otherwise
-int lut_args_for(uint32_t weight_type, uint32_t compute_type, LutArgs& L);
-
-// geometry pick of the tile GEMVs (woq_gemv_i8.hip): nw waves x tpw tiles cover tiles_k; false = not covered
-bool gemv_tile_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw);
-// K ranges one launch cannot hold run as chained launches; number of chunks, 0 = not covered
-int gemv_tile_k_chunks(int tiles_k, int cb, int smode, bool chainable);
+// (host side: lut_args_for in woq_host.h fills a LutArgs)
 
 }  // namespace woq

@@ -32,6 +32,7 @@
 #include <cstdlib>
 
 #include "woq_gemv_common.h"
+#include "woq_host.h"
 
 namespace woq {
 
@@ -374,7 +375,6 @@ static bool fp8_geometry(int tiles_k, int& nw, int& tpw) {
   return nw >= 1 && nw <= (tpw == 8 ? 12 : 16);
 }
 
-// Does the fp8-MFMA kernel take this call? `hi` = the HI plane's header (scales; the LO plane has the same geometry).
 bool gemv_fp8_mfma_supported(const void* act, int act_dtype, int lda, const woq_blob_header& hi) {
   if (hi.off_shuffle != 0 || hi.off_zp != 0 || hi.scale_mode > 1 || (hi.K & 3) != 0 || (lda & 3) != 0 ||
       (((uintptr_t)act) & (act_dtype == WOQ_F32 ? 15 : 7)) != 0)
@@ -385,7 +385,6 @@ bool gemv_fp8_mfma_supported(const void* act, int act_dtype, int lda, const woq_
   return fp8_geometry(hi.Kpad / WOQ_TILE_K, nw, tpw);
 }
 
-// rows 0..M-1 (M <= 8) of an fp8 weight: act [M, lda], out [M, ldo]
 int launch_gemv_fp8_mfma(const void* act, int act_dtype, int lda, int M, const void* hi_blob, const woq_blob_header& hi,
                          const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo,
                          hipStream_t st, const float* norm_w, float eps, const float* residual, int ld_res) {

@@ -48,6 +48,7 @@
 #include <algorithm>
 
 #include "woq_gemv_common.h"
+#include "woq_host.h"
 
 namespace woq {
 
@@ -692,8 +693,6 @@ int lut_args_for(uint32_t weight_type, uint32_t compute_type, LutArgs& L) {
   return ndig;
 }
 
-// K ranges one launch cannot hold are split into equal chunks run as chained launches (chunk i + 1 adds onto chunk
-// i's fp32 output through the residual input): linear epilogues only. Returns the number of chunks, 0 = not covered.
 int gemv_tile_k_chunks(int tiles_k, int cb, int smode, bool chainable) {
   int nw, tpw;
   if (gemv_tile_geometry(tiles_k, cb, smode, nw, tpw)) return 1;
@@ -703,18 +702,12 @@ int gemv_tile_k_chunks(int tiles_k, int cb, int smode, bool chainable) {
   return 0;
 }
 
-// geometry pick: nw waves x tpw tiles cover tiles_k (8 tiles = 8 KiB per wave per column tile; 4 for short K so
-// that a workgroup still has a few waves). Returns false when this kernel does not take the shape (K > 16384).
 bool gemv_tile_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw) {
   tpw = (tiles_k > 16 && !(cb == 2 && smode == 1)) ? 8 : 4;  // per-32 scales x 2 column tiles: register budget
   nw = (tiles_k + tpw - 1) / tpw;
   return nw <= (cb * tpw > 8 ? 8 : (smode == 1 ? 12 : 16));  // the kernel's __launch_bounds__
 }
 
-// largest M the tile kernel takes for this call (LDS budget), 0 if it is not covered: the kernel wants unshuffled
-// activation rows, fp32 and 16-B aligned (what the decode engine feeds it and what the reference's qbits boundary
-// always holds, modules.py:152-154) or fp16 / bf16 and 8-B aligned; anything else goes to the generic kernel in
-// woq_gemv.hip.
 int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_header& h, const float* norm_w,
                        int epi, int out_dtype) {
   const bool table = is_table_type(h.weight_type) && h.off_zp == 0;
@@ -739,7 +732,6 @@ int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_h
   return m;
 }
 
-// rows 0..M-1 (M <= gemv_tile_max_rows). x: [M, lda]; out: [M, ldo]; residual: [M, ld_res] or null.
 int launch_gemv_tile(const void* act, int act_dtype, int lda, int M, const void* blob, const woq_blob_header& h,
                      const float* bias, void* out, int out_dtype, int ldo, const float* norm_w, float eps,
                      const float* residual, int ld_res, int epi, hipStream_t st) {

@@ -9,6 +9,7 @@
 __device__ unsigned long long* g_xqs_probe = nullptr;
 #endif
 #include "woq_gemv_xqs.h"
+#include "woq_host.h"
 #include "woq_xq.h"
 
 #ifdef WOQ_XQS_STAMPS
@@ -119,7 +120,6 @@ static int xq_k_chunks(int tiles_k, int cb, int smode, bool chainable, int ndig 
   return 0;
 }
 
-// does the XQ kernel take this blob as a batch-1 projection? epi 1 = fused gate/up (SiLU * mul)
 bool gemv_xq_supported(const woq_blob_header& h, int epi) {
   const bool table = is_table_type(h.weight_type) && h.off_zp == 0;
   if ((h.weight_type != WOQ_W_INT4_CLIP && !table) || h.off_shuffle != 0 || (h.K % WOQ_TILE_K) != 0 || h.K != h.Kpad)
@@ -134,9 +134,6 @@ bool gemv_xq_supported(const woq_blob_header& h, int epi) {
   return xq_k_chunks(tiles_k, cb, (int)h.scale_mode, epi == 0, lut_args_for(h.weight_type, h.compute_type, lut)) > 0;
 }
 
-// out[N] (fp32, may be null when only the XQ output is wanted) = xin . W_deq (* rsqrt(mean(x^2) + eps) when ssq_in)
-// (+ bias) (+ residual), SiLU(gate) * up for epi 1; xo (optional): the result as the next kernel's XQ vector, after
-// multiplying by next_norm_w (optional), with its per-block sums of squares in ssq_out (optional).
 int launch_gemv_xq(const XqPtrs& xin, const void* blob, const woq_blob_header& h, const float* bias, float* out,
                    const float* ssq_in, float eps, const float* residual, int epi, const XqPtrs& xo,
                    const float* next_norm_w, float* ssq_out, hipStream_t st, const CommDev* tp) {
@@ -226,7 +223,6 @@ __global__ void gemv_empty_twin_kernel(unsigned int* __restrict__ sink) {
   if (threadIdx.x == 0x7fffffffu) sink[0] = 1;
 }
 
-// mode 0: load-only twin of the batch-1 GEMV of this blob; mode 1: an empty kernel on the same grid and block
 int launch_gemv_twin(const void* blob, const woq_blob_header& h, int epi, int mode, unsigned int* sink, hipStream_t st) {
   const int tiles_k = h.Kpad / WOQ_TILE_K, tiles_n = h.Npad / WOQ_TILE_N, cb = epi == 1 ? 2 : 1;
   LutArgs lut;

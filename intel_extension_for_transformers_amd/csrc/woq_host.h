@@ -1,0 +1,170 @@
+// woq_host.h — the host functions the library's translation units call across files, declared once, default arguments
+// included; every defining file includes it too. Declarations only: no device code (error / scratch plumbing: woq_launch.h).
+#pragma once
+#include "woq_comm_dev.h"
+#include "woq_launch.h"
+#include "woq_xq.h"
+
+namespace woq {
+struct AttnA2A;    // woq_attn_merge.h
+struct AttnMerge;  // woq_attn_merge.h
+struct LutArgs;    // woq_gemv_common.h
+
+// ---- woq_gemv.hip: small-M dispatch ------------------------------------------------------------------------------
+// Shared by woq_linear and the decode engine: rows in chunks through the i8 tile kernel when the call qualifies,
+// through the generic kernel otherwise. `nt` is reserved (weight loads are always non-temporal).
+int launch_gemv_from_header(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
+                            const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w,
+                            float eps, const float* residual, int ld_res, int epi, int nt, hipStream_t st);
+// fp8 weights at decode row counts: the fp8-MFMA kernel (woq_gemv_fp8.hip: code bytes straight into the matrix cores,
+// activations as base-16 digits; round 4) where it takes the call, rows in chunks of 8; otherwise (per-32 / per-64 /
+// per-256 scales, g_idx, misaligned rows, K beyond 8192) the lookup kernel reading both nibble planes, rows in chunks of GEN_MAXM.
+// `hi` = the HI plane's header (scales, shuffle), `lo_q` = the LO plane's qdata.
+int launch_gemv_fp8(const void* act, int act_dtype, int lda, const void* hi_blob, const woq_blob_header& hi,
+                    const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo, int M,
+                    hipStream_t st);
+// One batch-1 projection of an fp8-weight layer inside the decode engine (round 6): fp32 activation row in, fp32 out,
+// with the engine's fused prologue / epilogues — RMSNorm (norm_w, eps), residual add, and for the fused gate/up
+// projection (epi 1) SiLU(gate) * up. The fp8 matrix-core kernel (woq_gemv_fp8.hip) carries the norm and the residual
+// itself; its gate/up call writes the 2 * inter interleaved columns to `gu_tmp` and a small launch pairs them. Blobs it
+// does not take (g_idx, groups of 256, K beyond 12288) run the lookup kernel, which has all three built in.
+int launch_gemv_fp8_engine(const float* act, int lda, const void* hi_blob, const woq_blob_header& hi, const void* lo_q,
+                           uint32_t fp8_type, float* out, int ldo, const float* norm_w, float eps, const float* residual,
+                           int ld_res, int epi, float* gu_tmp, hipStream_t st);
+
+// ---- woq_gemv_i8.hip: the tile GEMV -------------------------------------------------------------------------------
+// the digit planes of a table weight type; returns NDIG (1 | 2 | 3), 0 = not a table. compute_type (woq_blob.h):
+// nf4 takes three planes for fp32 compute and two (table held to 2^-16 of its largest entry — finer than the bf16 / fp16
+// operands those modes ask for) otherwise
+int lut_args_for(uint32_t weight_type, uint32_t compute_type, LutArgs& L);
+// geometry pick: nw waves x tpw tiles cover tiles_k (8 tiles = 8 KiB per wave per column tile; 4 for short K so
+// that a workgroup still has a few waves). Returns false when this kernel does not take the shape (K > 16384).
+bool gemv_tile_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw);
+// K ranges one launch cannot hold are split into equal chunks run as chained launches (chunk i + 1 adds onto chunk
+// i's fp32 output through the residual input): linear epilogues only. Returns the number of chunks, 0 = not covered.
+int gemv_tile_k_chunks(int tiles_k, int cb, int smode, bool chainable);
+// largest M the tile kernel takes for this call (LDS budget), 0 if it is not covered: the kernel wants unshuffled
+// activation rows, fp32 and 16-B aligned (what the decode engine feeds it and what the reference's qbits boundary
+// always holds, modules.py:152-154) or fp16 / bf16 and 8-B aligned; anything else goes to the generic kernel in
+// woq_gemv.hip.
+int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_header& h, const float* norm_w,
+                       int epi, int out_dtype);
+// rows 0..M-1 (M <= gemv_tile_max_rows). x: [M, lda]; out: [M, ldo]; residual: [M, ld_res] or null.
+int launch_gemv_tile(const void* act, int act_dtype, int lda, int M, const void* blob, const woq_blob_header& h,
+                     const float* bias, void* out, int out_dtype, int ldo, const float* norm_w, float eps,
+                     const float* residual, int ld_res, int epi, hipStream_t st);
+
+// ---- woq_gemv_fp8.hip: the fp8 matrix-core GEMV -------------------------------------------------------------------
+// Does the fp8-MFMA kernel take this call? `hi` = the HI plane's header (scales; the LO plane has the same geometry).
+bool gemv_fp8_mfma_supported(const void* act, int act_dtype, int lda, const woq_blob_header& hi);
+// rows 0..M-1 (M <= 8) of an fp8 weight: act [M, lda], out [M, ldo]
+int launch_gemv_fp8_mfma(const void* act, int act_dtype, int lda, int M, const void* hi_blob, const woq_blob_header& hi,
+                         const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo,
+                         hipStream_t st, const float* norm_w = nullptr, float eps = 0.f, const float* residual = nullptr,
+                         int ld_res = 0);
+// act[p * 16 + i] = SiLU(gu[(2 p) * 16 + i]) * gu[(2 p + 1) * 16 + i] (silu_mul_tiles_kernel)
+void launch_silu_mul_tiles(const float* gu, int inter, float* act, hipStream_t st);
+
+// ---- woq_gemv_xq.hip: batch-1 GEMV over an XQ activation vector ---------------------------------------------------
+// does the XQ kernel take this blob as a batch-1 projection? epi 1 = fused gate/up (SiLU * mul)
+bool gemv_xq_supported(const woq_blob_header& h, int epi);
+// out[N] (fp32, may be null when only the XQ output is wanted) = xin . W_deq (* rsqrt(mean(x^2) + eps) when ssq_in)
+// (+ bias) (+ residual), SiLU(gate) * up for epi 1; xo (optional): the result as the next kernel's XQ vector, after
+// multiplying by next_norm_w (optional), with its per-block sums of squares in ssq_out (optional).
+int launch_gemv_xq(const XqPtrs& xin, const void* blob, const woq_blob_header& h, const float* bias, float* out,
+                   const float* ssq_in, float eps, const float* residual, int epi, const XqPtrs& xo,
+                   const float* next_norm_w, float* ssq_out, hipStream_t st, const CommDev* tp);
+// mode 0: load-only twin of the batch-1 GEMV of this blob; mode 1: an empty kernel on the same grid and block
+int launch_gemv_twin(const void* blob, const woq_blob_header& h, int epi, int mode, unsigned int* sink, hipStream_t st);
+
+// ---- woq_gemv_attn.hip: [RMSNorm + qkv GEMV] + [RoPE + KV append + attention] in one launch -----------------------
+// does the fused launch take this (blob, attention) combination?
+bool gemv_xq_attn_supported(const woq_blob_header& h, int heads, int kv_heads, int head_dim, int kv_dtype, int max_ctx,
+                            int window, int splits);
+// qkv_g ({tag, fp32} granules [(heads + 2 kv_heads) * 128]) = xin . W_qkv_deq * rsqrt(mean(x^2) + eps); per head, as its granules
+// arrive: RoPE, KV append at *pos, attention over the cache -> attn_out (+ its XQ form).
+// splits > 1: `splits` context slices per head; they merge among themselves through the tagged granules `part_g`
+// ([heads][64][130] x 8 B) and write attn_out / xq_attn — no combine launch.
+int launch_gemv_xq_attn(const XqPtrs& xin, const void* blob, const woq_blob_header& h, unsigned long long* qkv_g,
+                        const float* ssq_in, float eps, const unsigned int* seq, int layer, int* status, void* kcache,
+                        void* vcache, int kv_dtype, const int32_t* pos, const float* cs, const float* sn, int heads,
+                        int kv_heads, int max_ctx, int window, float* attn_out, const XqPtrs& xq_attn, hipStream_t st,
+                        int splits = 1, unsigned long long* part_g = nullptr);
+
+// ---- woq_ops.hip: the decode step's other launches ----------------------------------------------------------------
+void launch_embed(const void* embed, int dtype, const int32_t* token, int hidden, float* out, const float* norm_w,
+                  const XqPtrs& xo, float* ssq_out, unsigned int* step_seq, int32_t* pos, int max_ctx, int* status,
+                  hipStream_t st);
+// splits <= 1: one workgroup per head (short contexts); else `splits` slices per head + a combine launch, partials in
+// `part` (fp32 [heads][splits][D + 2]).
+// merge_counters (nullable): [heads] zero-initialised words — the slices' last workgroup merges (woq_attn_merge.h) and
+// no combine launch follows; chunk_fixed: position-independent slice geometry of the grouped form (0 = adaptive)
+int launch_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
+                       const float* cs, const float* sn, int heads, int kv_heads, int D, int max_ctx, int window,
+                       float* out, int splits, int grouped, float* part, const XqPtrs& xo, hipStream_t st,
+                       unsigned int* merge_counters, int chunk_fixed, const AttnA2A* a2a_grouped = nullptr,
+                       const unsigned int* seq = nullptr, int layer = 0);
+void launch_attn_combine(const float* part, int heads, int D, int splits, float* out, const XqPtrs& xo,
+                         hipStream_t st);
+// pmax / pidx (nullable): per-workgroup (max logit, its index), (vocab + 15) / 16 entries each
+void launch_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype, int hidden,
+                    int vocab, float* logits, float* pmax, int32_t* pidx, hipStream_t st);
+void launch_argmax(const float* logits, int vocab, int32_t* token, int32_t* pos, hipStream_t st);
+// greedy token from the (max, index) pairs of launch_lm_head
+void launch_argmax_pairs(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
+                         hipStream_t st);
+// greedy token of the step that just ran its lm_head + embedding row of the NEXT step, one launch (argmax_embed_kernel)
+void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
+                         const void* embed, int dtype, int hidden, float* out, const float* norm_w, const XqPtrs& xo,
+                         float* ssq_out, unsigned int* step_seq, int max_ctx, int* status, hipStream_t st);
+
+// ---- woq_prefill.hip: prompt-pass launches and the grouped decode attention ---------------------------------------
+void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int M, int hidden, float* out,
+                       hipStream_t st);
+int launch_rope_append(_Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD, const float* cs,
+                       const float* sn, void* kcache, void* vcache, int kv_dtype, size_t seq_stride_elems,
+                       hipStream_t st);
+int launch_attn_prefill(const _Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD,
+                        const void* kcache, const void* vcache, int kv_dtype, size_t seq_stride_elems, _Float16* out,
+                        int window, hipStream_t st);
+// last row of every sequence -> dst fp32 [n_seq][hidden]
+void launch_gather_last(const float* h, int n_seq, int T, int hidden, float* dst, hipStream_t st);
+// long-context decode attention of grouped-query models: true when this kernel took the call (head_dim 128, 2 / 4 / 8
+// query heads per kv head), false -> the caller uses the per-query-head sliced kernel
+// chunk_fixed: 0 = adaptive slices, else positions per slice (multiple of 32) of the position-independent geometry;
+// mg.counter != null: the last slice workgroup of a kv head merges (no combine launch needed)
+bool launch_attn_decode_mfma(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
+                             const float* cs, const float* sn, int heads, int kv_heads, int D, int window, int splits,
+                             float* part, int chunk_fixed, int max_ctx, const AttnMerge& mg, hipStream_t st);
+// workgroups of the grouped decode attention kernel the chip holds at once (0 = shape not covered): the all-to-all
+// merge needs the whole grid resident
+int attn_decode_mfma_slots(int kv_dtype, int rep);
+
+// ---- woq_gemm_f16.hip: the prompt pass's MFMA GEMM ----------------------------------------------------------------
+// workspace bytes of one blob's [M, K] x [K, N] call, fragment image of the float weight types included (4-8x the
+// blob: what made table-type prompt passes allocate per call while the engine's workspace sat unused — ADVICE r04)
+size_t gemm_f16_workspace_bytes_blob(int M, const woq_blob_header& h, int planes);
+// out[M,N] = act[M,K] . W_deq (+ bias) with fp16 operands. `ws` = caller workspace of gemm_f16_workspace_bytes or
+// null (stream-ordered allocation per call, like the reference's per-call amalloc,
+// bestla_weightonly_dispatcher.cpp:108-118,179). norm_w/eps: RMSNorm fused into the pack pass (null = none);
+// residual / epi: see GemmF16Args; fp32_class: the three-product hi + lo form (compute_dtype fp32).
+int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
+                    const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w, float eps,
+                    const float* residual, int ld_res, int epi, void* ws, int fp32_class, hipStream_t st,
+                    const void* fp8_lo = nullptr, uint32_t fp8_type = 0, size_t ws_bytes = 0);
+// events recorded on the launch stream right before / after the GEMM kernel of the next launch_gemm_f16 calls
+// (null = off): lets bench.py time the dominant prefill kernel without its pack pass
+void set_gemm_time_events(hipEvent_t before, hipEvent_t after);
+}  // namespace woq
+
+// ---- woq_comm.hip: device-side tensor-parallel exchange, the engine's internals -----------------------------------
+size_t woq_comm_max_elems(woq_comm* c);  // floats one all-reduce launch can carry (the inbox size)
+int woq_comm_launch_allreduce(woq_comm* c, float* buf, size_t n, hipStream_t st);
+// the engine's form: `pushed` = the producing GEMV already stored this rank's contribution into the peers' inboxes
+// (woq_comm_dev_ptr), `xo` (optional) = the summed vector also as an XQ vector (times norm_w, sums of squares in ssq_out)
+int woq_comm_launch_allreduce_ex(woq_comm* c, float* buf, size_t n, int pushed, const float* norm_w,
+                                 const woq::XqPtrs& xo, float* ssq_out, hipStream_t st);
+// device-resident copy of the communicator record (peer inboxes, sequence word, rank / world), valid once connected
+const woq::CommDev* woq_comm_dev_ptr(woq_comm* c);
+int woq_comm_launch_greedy(woq_comm* c, const float* pmax, const int32_t* pidx, int n, int vocab_offset,
+                           int32_t* token, int32_t* pos, int32_t* log, hipStream_t st);

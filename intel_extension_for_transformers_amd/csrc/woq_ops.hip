@@ -6,7 +6,7 @@
 // vector kernels: 16-byte loads, fp32 math, wave64 shuffles; no MFMA.
 #include "woq_attn_decode.h"
 #include "woq_device.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 #include "woq_xq.h"
 #include "../../include/woq_hip_experimental.h"
 
@@ -377,12 +377,6 @@ void launch_embed(const void* embed, int dtype, const int32_t* token, int hidden
                      norm_w, xo, ssq_out, step_seq, pos, max_ctx, status);
 }
 
-bool launch_attn_decode_mfma(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
-                             const float* cs, const float* sn, int heads, int kv_heads, int D, int window, int splits,
-                             float* part, int chunk_fixed, int max_ctx, const AttnMerge& mg, hipStream_t st);
-void launch_attn_combine(const float* part, int heads, int D, int splits, float* out, const XqPtrs& xo,
-                         hipStream_t st);
-
 template <typename KV, int HD>
 static int launch_attn_t(const float* qkv, void* kcache, void* vcache, const int32_t* pos, const float* cs,
                          const float* sn, int heads, int kv_heads, int max_ctx, int window, float* out, int splits,
@@ -418,10 +412,6 @@ static int launch_attn_t(const float* qkv, void* kcache, void* vcache, const int
   return 0;
 }
 
-// splits <= 1: one workgroup per head (short contexts); else `splits` slices per head + a combine launch, partials in
-// `part` (fp32 [heads][splits][D + 2]).
-// merge_counters (nullable): [heads] zero-initialised words — the slices' last workgroup merges (woq_attn_merge.h) and
-// no combine launch follows; chunk_fixed: position-independent slice geometry of the grouped form (0 = adaptive)
 int launch_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
                        const float* cs, const float* sn, int heads, int kv_heads, int D, int max_ctx, int window,
                        float* out, int splits, int grouped, float* part, const XqPtrs& xo, hipStream_t st,
@@ -460,7 +450,6 @@ void launch_attn_combine(const float* part, int heads, int D, int splits, float*
     hipLaunchKernelGGL(attn_combine_kernel<64>, dim3(heads), dim3(256), 0, st, part, splits, out, xo);
 }
 
-// pmax / pidx (nullable): per-workgroup (max logit, its index), (vocab + 15) / 16 entries each
 void launch_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype, int hidden,
                     int vocab, float* logits, float* pmax, int32_t* pidx, hipStream_t st) {
   hipLaunchKernelGGL(lm_head_kernel, dim3((vocab + 15) / 16), dim3(256), (size_t)hidden * 4, st, hidden_in, norm_w,
@@ -472,13 +461,11 @@ void launch_argmax(const float* logits, int vocab, int32_t* token, int32_t* pos,
                      (int32_t*)nullptr);
 }
 
-// greedy token from the (max, index) pairs of launch_lm_head
 void launch_argmax_pairs(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
                          hipStream_t st) {
   hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, pmax, pidx, n, token, pos, log);
 }
 
-// greedy token of the step that just ran its lm_head + embedding row of the NEXT step, one launch (argmax_embed_kernel)
 void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
                          const void* embed, int dtype, int hidden, float* out, const float* norm_w, const XqPtrs& xo,
                          float* ssq_out, unsigned int* step_seq, int max_ctx, int* status, hipStream_t st) {

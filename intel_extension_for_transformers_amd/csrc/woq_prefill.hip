@@ -24,7 +24,7 @@
 
 #include "woq_attn_merge.h"
 #include "woq_device.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 #include "../../include/woq_hip_experimental.h"
 
 namespace woq {
@@ -810,10 +810,6 @@ int launch_attn_prefill(const _Float16* qkv, int n_seq, int T, int start, int he
   return woq::fail("QBits: unsupported KV cache dtype");
 }
 
-// long-context decode attention of grouped-query models: true when this kernel took the call (head_dim 128, 2 / 4 / 8
-// query heads per kv head), false -> the caller uses the per-query-head sliced kernel
-// chunk_fixed: 0 = adaptive slices, else positions per slice (multiple of 32) of the position-independent geometry;
-// mg.counter != null: the last slice workgroup of a kv head merges (no combine launch needed)
 bool launch_attn_decode_mfma(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
                              const float* cs, const float* sn, int heads, int kv_heads, int D, int window, int splits,
                              float* part, int chunk_fixed, int max_ctx, const AttnMerge& mg, hipStream_t st) {
@@ -835,8 +831,6 @@ bool launch_attn_decode_mfma(const float* qkv, void* kcache, void* vcache, int k
   return false;
 }
 
-// workgroups of the grouped decode attention kernel the chip holds at once (0 = shape not covered): the all-to-all
-// merge needs the whole grid resident
 int attn_decode_mfma_slots(int kv_dtype, int rep) {
   static int cache[2][9] = {};  // [fp16 | fp8][rep], 0 = not asked yet, -1 = not covered
   const int ci = kv_dtype == WOQ_FP8_E4M3 ? 1 : 0;

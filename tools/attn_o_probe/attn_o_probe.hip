@@ -19,7 +19,7 @@
 // profiles/r02p_attn_o_fusion.txt).
 #include "woq_attn_body.h"
 #include "woq_gemv_xq_body.h"
-#include "woq_launch.h"
+#include "woq_host.h"
 
 namespace woq {
 
