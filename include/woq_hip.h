@@ -224,7 +224,10 @@ WOQ_API int woq_engine_fuse_attn(woq_engine* e);
  * waiting for its head's q / k / v after its bound (its outputs are then wrong); bit 1: a step started with its
  * position at or beyond max_ctx — it ran at max_ctx - 1 instead (outputs meaningless, nothing written out of bounds;
  * woq_engine_step / _replay cannot check a position that lives on the device); bit 2: a greedy step found no
- * winning logit (all NaN) and fed token 0; -1 = the read itself failed.
+ * winning logit (all NaN) and fed token 0; bit 3: a sampled step found more than 1024 scores at or above the k-th
+ * largest (ties) and kept the 1024 with the lowest ids among the tied — informational, the token stands; not set
+ * when the tie is at -inf below a finite best score (fewer than k finite scores: those candidates weigh 0);
+ * -1 = the read itself failed.
  * Synchronises `stream`. */
 WOQ_API int woq_engine_status(woq_engine* e, void* stream);
 /* resets the sticky status to 0 (stream-ordered): a caller that read a non-zero status, changed what caused it
@@ -246,6 +249,32 @@ WOQ_API int woq_engine_replay(woq_engine* e, int n, void* stream);
  * the host ~2.6 us per launch. (Round 4 note: graph replays looked ~1 us per kernel boundary slower until their launch
  * was moved off a stream that sat behind cross-stream event waits — profiles/r04ab_stream_mode_probe.txt.) */
 WOQ_API int woq_engine_steps(woq_engine* e, int n, int greedy, void* stream);
+/* ---- sampled token tail (added after the freeze of revision 4: new entry points only, nothing existing changed, so
+ * WOQ_ABI_VERSION stays 4 — a client that needs them looks the symbols up) -----------------------------------------
+ * With a sampler installed, every step that chains on the device (greedy != 0: woq_engine_step / _steps / _capture /
+ * _replay and the prompt pass's tail) picks its next token with Hugging Face's logits processing instead of the plain
+ * argmax, in one launch after the lm_head (csrc/woq_sample.hip), HF's order: RepetitionPenaltyLogitsProcessor over the
+ * ids of the `seen` bit set (fp32, `s < 0 ? s * penalty : s / penalty`), then argmax (do_sample == 0, lowest id on
+ * ties) or TemperatureLogitsWarper, TopKLogitsWarper (ties at the k-th value survive), TopPLogitsWarper
+ * (min_tokens_to_keep 1) and an inverse-CDF draw with u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 under counter
+ * (position fed, 0, 0, 0) and key (seed_lo, seed_hi): a token depends on (seed, position, logits) only, whatever the
+ * burst size or launch mode. Covered: do_sample == 0; 1 <= top_k <= 1024 with any top_p; top_k == 0 with top_p == 1. */
+typedef struct woq_sampler_config {
+  int32_t do_sample;        /* 0 = argmax of the penalised scores */
+  int32_t top_k;            /* 0 = whole vocabulary */
+  float temperature, top_p, repetition_penalty;
+  uint32_t seed_lo, seed_hi;
+  uint32_t reserved;        /* 0 */
+} woq_sampler_config;
+/* cfg (host memory) is copied into a device struct the kernel reads: changing parameters needs no new capture, only
+ * installing or removing (cfg == NULL) the sampler drops a captured graph. Synchronises the device. Fails with a
+ * "QBits:" message on a tensor-parallel engine (vocab-sharded head) or for a combination that is not covered. */
+WOQ_API int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg);
+/* history of the repetition penalty: uint32 [(vocab + 31) / 32] bit set owned by the engine. Marks tokens_dev[0..n)
+ * (device int32; may be NULL with n == 0), after zeroing the set when clear != 0; stream-ordered. The sampled tail
+ * marks every token it picks itself. */
+WOQ_API int woq_engine_sampler_seen(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream);
+WOQ_API void* woq_engine_sampler_seen_ptr(woq_engine* e);
 /* tensor-parallel seam: when set, the engine calls `fn(user, buf_dev, count_f32, stream)` after
  * o_proj and after down_proj (row-parallel partial sums -> sum over ranks). The Python host binds it
  * to RCCL via torch.distributed. NULL = single GPU. */

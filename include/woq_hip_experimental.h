@@ -73,6 +73,13 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
                                   const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
                                   int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
                                   float* out, void* stream);
+/* the sampled token tail alone (tests/test_gpu_sampler_kernel.py), forwarding to the engine's own launcher unchanged:
+ * logits fp32 [vocab], seen uint32 [(vocab + 31) / 32] (read for the penalty, the picked token's bit set), cfg in HOST
+ * memory, u_or_null = device fp32 uniform that overrides Philox, pos_dev = device int32 position (the Philox counter;
+ * not advanced), token_out device int32, philox_out4 (nullable) device uint32 [4], status (nullable) device int. */
+WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
+                             const float* u_or_null, const int32_t* pos_dev, int32_t* token_out, uint32_t* philox_out4,
+                             int* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,14 @@ class LayerWeights(ctypes.Structure):
                 ("qkv_hdr", BlobHeader), ("o_hdr", BlobHeader), ("gate_up_hdr", BlobHeader), ("down_hdr", BlobHeader)]
 
 
+class SamplerConfig(ctypes.Structure):
+    """struct woq_sampler_config (include/woq_hip.h)."""
+
+    _fields_ = [("do_sample", ctypes.c_int32), ("top_k", ctypes.c_int32), ("temperature", ctypes.c_float),
+                ("top_p", ctypes.c_float), ("repetition_penalty", ctypes.c_float), ("seed_lo", ctypes.c_uint32),
+                ("seed_hi", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
 
 # every symbol include/woq_hip.h declares (tests check the .so exports all of them): ABI version 4, the frozen boundary
@@ -76,12 +84,13 @@ EXPORTS = [
     "woq_engine_clear_status", "woq_comm_create", "woq_comm_handle", "woq_comm_connect", "woq_comm_allreduce_f32",
     "woq_comm_status", "woq_comm_set_timeout_ms", "woq_comm_destroy", "woq_engine_set_comm", "woq_set_workspace",
     "woq_engine_uses_xq", "woq_engine_token_log_ptr", "woq_table_digit_planes",
+    "woq_engine_set_sampler", "woq_engine_sampler_seen", "woq_engine_sampler_seen_ptr",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
     "woq_engine_set_attn_chunk", "woq_engine_attn_chunk", "woq_engine_time_gemv", "woq_engine_time_gemv_mask",
     "woq_engine_time_twin", "woq_engine_set_time_eager", "woq_engine_time_prefill_gemm", "woq_gemm_form_log",
-    "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode",
+    "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -171,6 +180,11 @@ def lib():
     L.woq_engine_uses_xq.argtypes = [vp]
     L.woq_engine_token_log_ptr.restype = vp
     L.woq_engine_token_log_ptr.argtypes = [vp]
+    L.woq_engine_set_sampler.argtypes = [vp, ctypes.POINTER(SamplerConfig)]
+    L.woq_engine_sampler_seen.argtypes = [vp, vp, ci, ci, vp]
+    L.woq_engine_sampler_seen_ptr.restype = vp
+    L.woq_engine_sampler_seen_ptr.argtypes = [vp]
+    L.woq_probe_sample.argtypes = [vp, ci, vp, ctypes.POINTER(SamplerConfig), vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -210,6 +224,25 @@ def probe_attn_decode(qkv, kcache, vcache, kv_dtype, pos, cos, sin, heads, kv_he
     rc = lib().woq_probe_attn_decode(_ptr(qkv), _ptr(kcache), _ptr(vcache), kv_dtype, _ptr(pos), _ptr(cos), _ptr(sin),
                                      heads, kv_heads, head_dim, max_ctx, window, splits, grouped, merge, chunk_fixed,
                                      _ptr(out), stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def sampler_config(do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):
+    """woq_sampler_config from Hugging Face's option names (None = HF's neutral value); `seed` is one 64-bit value."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return SamplerConfig(do_sample=int(bool(do_sample)), top_k=int(top_k or 0),
+                         temperature=float(1.0 if temperature is None else temperature),
+                         top_p=float(1.0 if top_p is None else top_p),
+                         repetition_penalty=float(1.0 if repetition_penalty is None else repetition_penalty),
+                         seed_lo=seed & 0xFFFFFFFF, seed_hi=seed >> 32, reserved=0)
+
+
+def probe_sample(logits, seen, cfg, pos, token_out, u=None, philox_out=None, status=None):
+    """the sampled token tail alone (woq_probe_sample): device tensors, `cfg` a SamplerConfig, the current stream."""
+    opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
+    rc = lib().woq_probe_sample(_ptr(logits), int(logits.numel()), _ptr(seen), ctypes.byref(cfg), opt(u), _ptr(pos),
+                                _ptr(token_out), opt(philox_out), opt(status), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
 

@@ -131,6 +131,12 @@ struct woq_engine {
   void* pf_ws = nullptr;        // GEMM pack workspace
   float* pf_last = nullptr;     // fp32 [max_batch][hidden]
   float* pf_logits = nullptr;   // fp32 [max_batch][vocab]
+  // sampled token tail (woq_sample.hip): with `sampler_on` a chaining step picks its token with launch_sample instead of
+  // the argmax launches. The parameters live in `samp_cfg` (device), the repetition penalty's history in `samp_seen`
+  bool sampler_on = false;
+  woq_sampler_config* samp_cfg = nullptr;
+  uint32_t* samp_seen = nullptr;  // [(vocab + 31) / 32]
+  int seen_words() const { return (cfg.vocab + 31) / 32; }
 };
 
 using namespace woq;
@@ -248,10 +254,21 @@ static int engine_mlp_block(woq_engine* e, int l, hipStream_t st) {
 // fuse_next: this step's greedy argmax and the NEXT step's embedding kernel as one launch (steps chained inside one
 // captured graph; one GPU, greedy) — woq_ops.hip argmax_embed_kernel
 static bool engine_can_fuse_next(const woq_engine* e, int greedy) {
-  return greedy && e->cfg.tp_size <= 1 && e->comm == nullptr;
+  return greedy && e->cfg.tp_size <= 1 && e->comm == nullptr && !e->sampler_on;  // sampled chains: sample -> embed
+}
+// the chaining tail with a sampler installed: token <- sample(logits), tok_log[pos] = token, pos += 1
+static void engine_sample(woq_engine* e, hipStream_t st) {
+  launch_sample(e->logits, e->cfg.vocab, e->samp_seen, e->samp_cfg, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr,
+                e->fuse_status, st);
 }
 static int engine_head(woq_engine* e, int greedy, hipStream_t st, bool fuse_next = false) {
   const woq_engine_config& c = e->cfg;
+  if (greedy && e->sampler_on) {  // the penalty changes values after the lm_head: its (max, index) pairs are of no use
+    launch_lm_head(e->hidden, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, e->logits, nullptr,
+                   nullptr, st);
+    engine_sample(e, st);
+    return 0;
+  }
   launch_lm_head(e->hidden, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, e->logits,
                  greedy ? e->am_val : nullptr, greedy ? e->am_idx : nullptr, st);
   if (fuse_next) {
@@ -404,7 +421,10 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
   WOQ_HIP(hipMemcpyAsync(e->hidden, e->pf_last, (size_t)c.hidden * 4, hipMemcpyDeviceToDevice, st));
   WOQ_HIP(hipMemcpyAsync(e->logits, e->pf_logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, st));
   WOQ_HIP(hipMemsetD32Async((hipDeviceptr_t)e->pos, start + T - 1, 1, st));
-  if (greedy) launch_argmax(e->logits, c.vocab, e->token, e->pos, st);  // token <- argmax, pos <- start + T
+  if (greedy && e->sampler_on)
+    engine_sample(e, st);  // token <- sample at counter start + T - 1, pos <- start + T
+  else if (greedy)
+    launch_argmax(e->logits, c.vocab, e->token, e->pos, st);  // token <- argmax, pos <- start + T
   return 0;
 }
 
@@ -604,8 +624,12 @@ int woq_engine_create(const woq_engine_config* cfg, woq_engine** out) {
   WOQ_HIP(hipMalloc((void**)&e->step_seq, 8));  // step counter (hand-off tags) + sticky status word
   WOQ_HIP(hipMemset(e->step_seq, 0, 8));
   e->fuse_status = (int*)(e->step_seq + 1);
+  WOQ_HIP(hipMalloc((void**)&e->samp_cfg, sizeof(woq_sampler_config)));
+  WOQ_HIP(hipMemset(e->samp_cfg, 0, sizeof(woq_sampler_config)));
+  WOQ_HIP(hipMalloc((void**)&e->samp_seen, (size_t)e->seen_words() * 4));
+  WOQ_HIP(hipMemset(e->samp_seen, 0, (size_t)e->seen_words() * 4));
   e->owned = {e->hidden, e->qkv, e->attn, e->act, e->logits, e->token, e->pos, e->kcache, e->vcache, e->pf_last,
-              e->pf_logits, e->attn_part, e->attn_cnt, e->am_val, e->am_idx, e->tok_log, e->step_seq};
+              e->pf_logits, e->attn_part, e->attn_cnt, e->am_val, e->am_idx, e->tok_log, e->step_seq, e->samp_cfg, e->samp_seen};
   {  // XQ vectors (woq_xq.h) for the three GEMV inputs of a layer
     // WOQ_ENGINE_XQ=0 turns the XQ hand-off off (the fp32-activation kernels). Round 2 picked by shape — at hidden 8192
     // the second recombination per tile cost more than the staging it removed (Llama-2-70B 119-120 vs 125-127 tokens/s);
@@ -775,6 +799,35 @@ int woq_engine_set_comm(woq_engine* e, woq_comm* comm, int vocab_offset) {
 }
 
 int woq_engine_uses_xq(woq_engine* e) { return e && e->use_xq() ? 1 : 0; }
+
+int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg) {
+  WOQ_TRY
+  WOQ_CHECK(e, "QBits: null engine");
+  if (cfg != nullptr) {
+    WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+              "QBits: the native sampler needs the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
+    const char* why = sampler_config_problem(*cfg);
+    if (why) return woq::fail(why);
+    // steps in flight on any stream still read the struct
+    WOQ_HIP(hipDeviceSynchronize());
+    WOQ_HIP(hipMemcpy(e->samp_cfg, cfg, sizeof(woq_sampler_config), hipMemcpyHostToDevice));
+  }
+  const bool on = cfg != nullptr;
+  if (on != e->sampler_on) engine_drop_graphs(e);  // a captured graph holds the other tail
+  e->sampler_on = on;
+  WOQ_END
+}
+
+int woq_engine_sampler_seen(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e && n >= 0 && (tokens_dev != nullptr || n == 0), "QBits: bad sampler history arguments");
+  if (clear) WOQ_HIP(hipMemsetAsync(e->samp_seen, 0, (size_t)e->seen_words() * 4, (hipStream_t)stream));
+  launch_sampler_seen(e->samp_seen, e->cfg.vocab, tokens_dev, n, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+void* woq_engine_sampler_seen_ptr(woq_engine* e) { return e ? e->samp_seen : nullptr; }
 
 int woq_engine_step(woq_engine* e, int greedy, void* stream) {
   WOQ_TRY

@@ -118,6 +118,22 @@ void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t*
                          const void* embed, int dtype, int hidden, float* out, const float* norm_w, const XqPtrs& xo,
                          float* ssq_out, unsigned int* step_seq, int max_ctx, int* status, hipStream_t st);
 
+// ---- woq_sample.hip: the sampled token tail -----------------------------------------------------------------------
+// next token from fp32 logits under the device-resident `cfg_dev` (repetition penalty over the `seen` bit set, then
+// argmax or temperature / top-k / top-p / draw), one launch of one workgroup. pos_advance (the engine's chain): the
+// uniform's Philox counter is *pos_advance, log[*pos_advance] = token, *pos_advance += 1; else pos_fixed is only read.
+// u_dev (nullable) overrides the Philox uniform; philox_out (nullable) receives the four Philox words; the picked
+// token's bit is set in `seen`; status |= 4 (every score NaN: token 0), 8 (more than 1024 candidates tied in).
+void launch_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg_dev, const float* u_dev,
+                   int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out,
+                   int* status, hipStream_t st);
+// seen |= bits of tokens[0..n) (ids outside [0, vocab) are ignored)
+void launch_sampler_seen(uint32_t* seen, int vocab, const int32_t* tokens, int n, hipStream_t st);
+// *dst = cfg, stream-ordered (the struct travels as a kernel argument)
+void launch_sampler_config_store(const woq_sampler_config& cfg, woq_sampler_config* dst, hipStream_t st);
+// null when the native sampler takes this combination, else the "QBits: ..." reason
+const char* sampler_config_problem(const woq_sampler_config& cfg);
+
 // ---- woq_prefill.hip: prompt-pass launches and the grouped decode attention ---------------------------------------
 void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int M, int hidden, float* out,
                        hipStream_t st);

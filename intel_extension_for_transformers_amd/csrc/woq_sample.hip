@@ -1,0 +1,394 @@
+// woq_sample.hip — the next-token choice of a decode step with a sampler installed: Hugging Face's repetition penalty,
+// temperature, top-k, top-p and the draw, in HF's order (runtime/engine.py DeviceSampler.processed is the torch
+// restatement), as ONE launch after the lm_head in place of the greedy argmax. One workgroup of 1024 threads; the launch
+// shape does not depend on data and every parameter is read from a device struct, so the step stays capturable and a
+// change of temperature / k / p / penalty / seed needs no new capture.
+//
+// Numerics. score = logit, for ids in the history bit set `s < 0 ? s * pen : s / pen`, then `/ T` when sampling: IEEE
+// fp32 operations (no fast-math), the same two torch applies — the kept set is pure comparisons of these values.
+//  - no sampling: argmax of the scores, lowest id on ties;
+//  - 1 <= top_k <= 1024: radix select (4 x 8 bits over an order-preserving uint32 key) of the k-th largest score, every
+//    score >= it is a candidate (ties at the k-th value survive, as in HF's `scores < kth` mask), candidates sorted by
+//    (score descending, id ascending), w_i = expf(s_i - s_0), inclusive sums c_i, nucleus cut on the tail mass
+//    Z - c_(i-1) <= (1 - top_p) * Z (never the first), draw = first kept i with c_i > u * Z';
+//  - top_k = 0 (top_p = 1): softmax over the whole vocabulary, the same inverse-CDF rule over ids in ascending order.
+// u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 with counter (position, 0, 0, 0) and key (seed_lo, seed_hi): a draw
+// depends on (seed, position, logits) only, so eager steps and graphs of any burst size give the same tokens.
+#include "woq_device.h"
+#include "woq_host.h"
+#include "../../include/woq_hip_experimental.h"
+
+namespace woq {
+namespace {
+
+constexpr int SAMPLE_THREADS = 1024;
+constexpr int SAMPLE_WAVES = SAMPLE_THREADS / 64;
+constexpr int SAMPLE_MAX_CAND = 1024;
+
+// order-preserving key of a score: larger score <-> larger key; NaN -> 0 (below -inf, never a candidate); -0 == +0
+__device__ __forceinline__ uint32_t score_key(float s) {
+  if (s != s) return 0u;
+  const uint32_t u = __float_as_uint(s + 0.0f);
+  return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_score(uint32_t k) {
+  return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k);
+}
+
+struct ScoreArgs {
+  const float* logits;
+  const uint32_t* seen;
+  float pen, temp;
+  bool use_pen, scale;
+};
+__device__ __forceinline__ float score_at(const ScoreArgs& a, int i) {
+  float s = a.logits[i];
+  if (a.use_pen && ((a.seen[i >> 5] >> (i & 31)) & 1u)) s = s < 0.f ? s * a.pen : s / a.pen;
+  if (a.scale) s = s / a.temp;
+  return s;
+}
+
+// Philox4x32-10 (Salmon et al., Random123): word 0..3 of counter (c0, 0, 0, 0) under key (k0, k1)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+  uint32_t c1 = 0u, c2 = 0u, c3 = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+__device__ __forceinline__ float wave_scan_f32(float v, int lane) {  // inclusive, lane order
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned int wave_scan_u32(unsigned int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// hist[bin] += 1 for every active lane, one LDS atomic per distinct bin of the wave: the top byte of a logit's key
+// takes a handful of values, and 64 lanes on one LDS address would serialise. Called by whole waves.
+__device__ __forceinline__ void wave_hist_add(unsigned int* hist, bool active, uint32_t bin, int lane) {
+  unsigned long long todo = __ballot(active);
+  while (todo != 0ull) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const uint32_t b = __shfl(bin, leader, 64);
+    const unsigned long long same = __ballot(active && bin == b);
+    if (lane == leader) atomicAdd(&hist[b], (unsigned int)__popcll(same));
+    todo &= ~same;
+  }
+}
+
+// max over the workgroup of (key << 32 | ~id): the largest score, lowest id on ties. Every thread gets the result.
+__device__ __forceinline__ unsigned long long block_best(const ScoreArgs& a, int vocab, unsigned long long* red, int tid) {
+  unsigned long long best = 0ull;
+  for (int i = tid; i < vocab; i += SAMPLE_THREADS) {
+    const unsigned long long v = ((unsigned long long)score_key(score_at(a, i)) << 32) | (uint32_t)(~i);
+    best = v > best ? v : best;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(best, o, 64);
+    best = t > best ? t : best;
+  }
+  if ((tid & 63) == 0) red[tid >> 6] = best;
+  __syncthreads();
+  best = red[0];
+#pragma unroll
+  for (int w = 1; w < SAMPLE_WAVES; ++w) best = red[w] > best ? red[w] : best;
+  __syncthreads();
+  return best;
+}
+
+// `advance` != 0: the engine's chain — log[pos] = token, pos += 1 (the next step's embedding kernel guards max_ctx)
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
+    const float* __restrict__ logits, int vocab, uint32_t* __restrict__ seen, const woq_sampler_config* __restrict__ cfgp,
+    const float* __restrict__ u_in, int32_t* __restrict__ token, int32_t* __restrict__ pos_io,
+    const int32_t* __restrict__ pos_ro, int32_t* __restrict__ log, uint32_t* __restrict__ philox_out,
+    int* __restrict__ status) {
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned long long cand[SAMPLE_MAX_CAND];
+  __shared__ float cdf[SAMPLE_MAX_CAND];
+  __shared__ unsigned long long red[SAMPLE_WAVES];
+  __shared__ float wsum[SAMPLE_WAVES];
+  __shared__ unsigned int wcnt[SAMPLE_WAVES];
+  __shared__ unsigned int sel[4];   // radix select: prefix, rank wanted inside it, keys above it, keys equal (last pass)
+  __shared__ unsigned int slot[4];  // compaction counters (front, ties), first dropped index, picked index
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const woq_sampler_config cfg = *cfgp;
+  const bool do_sample = cfg.do_sample != 0;
+  ScoreArgs sa;
+  sa.logits = logits, sa.seen = seen, sa.pen = cfg.repetition_penalty, sa.temp = cfg.temperature;
+  sa.use_pen = cfg.repetition_penalty != 1.0f, sa.scale = do_sample;
+
+  // what the finishing thread does with its pick (exactly one thread calls it; every read of `seen` lies before a
+  // barrier that this thread has passed)
+  auto finish = [&](int tok, int flags) {
+    const int p = pos_io != nullptr ? pos_io[0] : (pos_ro != nullptr ? pos_ro[0] : 0);
+    token[0] = tok;
+    atomicOr(&seen[tok >> 5], 1u << (tok & 31));
+    if (log != nullptr) log[p] = tok;
+    if (pos_io != nullptr) pos_io[0] = p + 1;
+    if (flags != 0 && status != nullptr) atomicOr(status, flags);
+  };
+
+  float u = 0.f;
+  if (do_sample) {  // every thread computes the same uniform (uniform control flow, scalar-friendly)
+    const int p = pos_io != nullptr ? pos_io[0] : (pos_ro != nullptr ? pos_ro[0] : 0);
+    uint32_t x[4];
+    philox4x32_10((uint32_t)p, cfg.seed_lo, cfg.seed_hi, x);
+    if (tid == 0 && philox_out != nullptr) philox_out[0] = x[0], philox_out[1] = x[1], philox_out[2] = x[2], philox_out[3] = x[3];
+    u = u_in != nullptr ? u_in[0] : (float)(x[0] >> 8) * 5.9604644775390625e-08f;
+  }
+  __syncthreads();  // the position was read by everyone before anyone advances it
+
+  const unsigned long long best = block_best(sa, vocab, red, tid);
+  const uint32_t best_key = (uint32_t)(best >> 32);
+  if (best_key == 0u) {  // every score NaN: token 0 and a status bit, as the argmax kernels do
+    if (tid == 0) finish(0, 4);
+    return;
+  }
+  if (!do_sample) {
+    if (tid == 0) finish((int)~(uint32_t)best, 0);
+    return;
+  }
+  const float s_max = key_score(best_key);
+
+  if (cfg.top_k <= 0) {
+    // ---- whole vocabulary: wave w owns the ids [w * seg, (w + 1) * seg), walked 64 at a time in ascending order; the
+    // running sum of a wave is built from the same scans in both passes, so the second pass ends on the first one's total
+    const int seg = (((vocab + SAMPLE_WAVES - 1) / SAMPLE_WAVES) + 63) & ~63;
+    const int w_lo = wid * seg < vocab ? wid * seg : vocab, w_hi = w_lo + seg < vocab ? w_lo + seg : vocab;
+    auto weight = [&](int i) -> float {
+      if (i >= w_hi) return 0.f;
+      const float s = score_at(sa, i);
+      return s != s ? 0.f : (s == s_max ? 1.f : expf(s - s_max));
+    };
+    float running = 0.f;
+    for (int b = w_lo; b < w_hi; b += 64) running += __shfl(wave_scan_f32(weight(b + lane), lane), 63, 64);
+    if (lane == 0) wsum[wid] = running;
+    __syncthreads();
+    float z = 0.f;
+    for (int w = 0; w < SAMPLE_WAVES; ++w) z += wsum[w];
+    const float target = u * z;
+    float base = 0.f, cum = 0.f;
+    int wsel = -1, wlast = 0;
+    for (int w = 0; w < SAMPLE_WAVES; ++w) {
+      const float nxt = cum + wsum[w];
+      if (wsum[w] > 0.f) wlast = w;
+      if (wsel < 0 && nxt > target) wsel = w, base = cum;
+      cum = nxt;
+    }
+    // rounding left no wave above the target: the last id with any mass (no lane of wave `wlast` then hits in the walk
+    // below, because base + its sum <= target, and the walk ends on its last lane with mass)
+    if (wsel < 0) {
+      wsel = wlast, base = 0.f;
+      for (int w = 0; w < wlast; ++w) base += wsum[w];
+    }
+    if (wid != wsel) return;
+    int found = -1, last_mass = w_lo;
+    running = 0.f;
+    for (int b = w_lo; b < w_hi && found < 0; b += 64) {
+      const float wv = weight(b + lane);
+      const float sc = wave_scan_f32(wv, lane);
+      const unsigned long long hit = __ballot(wv > 0.f && base + (running + sc) > target);
+      const unsigned long long mass = __ballot(wv > 0.f);
+      if (hit != 0ull) found = b + __ffsll((long long)hit) - 1;
+      if (mass != 0ull) last_mass = b + 63 - __clzll((long long)mass);
+      running += __shfl(sc, 63, 64);
+    }
+    if (lane == 0) finish(found >= 0 ? found : last_mass, 0);
+    return;
+  }
+
+  // ---- top-k: radix select of the k-th largest key, most significant byte first -----------------------------------
+  uint32_t prefix = 0u;
+  unsigned int want = (unsigned int)(cfg.top_k < vocab ? cfg.top_k : vocab);
+  want = want < (unsigned int)SAMPLE_MAX_CAND ? want : (unsigned int)SAMPLE_MAX_CAND;
+  unsigned int n_greater = 0u, n_equal = 0u;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0u;
+    __syncthreads();
+    for (int base = 0; base < vocab; base += SAMPLE_THREADS) {  // whole waves, whatever the tail
+      const int i = base + tid;
+      bool act = false;
+      uint32_t bin = 0u;
+      if (i < vocab) {
+        const uint32_t key = score_key(score_at(sa, i));
+        act = pass == 0 ? true : ((key >> (shift + 8)) == prefix);
+        bin = (key >> shift) & 255u;
+      }
+      wave_hist_add(hist, act, bin, lane);
+    }
+    __syncthreads();
+    if (wid == 0) {  // lane L looks at bins 255 - 4L .. 252 - 4L: counts from the top down
+      const unsigned int c0 = hist[255 - 4 * lane], c1 = hist[254 - 4 * lane], c2 = hist[253 - 4 * lane],
+                         c3 = hist[252 - 4 * lane];
+      const unsigned int mine = c0 + c1 + c2 + c3;
+      const unsigned int incl = wave_scan_u32(mine, lane), excl = incl - mine;
+      if (excl < want && want <= incl) {  // exactly one lane
+        unsigned int above = excl, b = 255u - 4u * lane, c = c0;
+        if (above + c < want) above += c, b -= 1u, c = c1;
+        if (above + c < want) above += c, b -= 1u, c = c2;
+        if (above + c < want) above += c, b -= 1u, c = c3;
+        sel[0] = (prefix << 8) | b, sel[1] = want - above, sel[2] = n_greater + above, sel[3] = c;
+      }
+    }
+    __syncthreads();
+    prefix = sel[0], want = sel[1], n_greater = sel[2], n_equal = sel[3];
+  }
+  const uint32_t kth = prefix;
+  if (kth == 0u) n_equal = 0u;  // fewer than k scores that are not NaN: those are the candidates, NaN never is
+  const unsigned int room = (unsigned int)SAMPLE_MAX_CAND - n_greater;  // n_greater < k <= 1024
+  const bool overflow = n_equal > room;  // more than 1024 survive the tie rule: the lowest ids among the tied, bit 8
+  // ... unless the tie is at -inf under a finite best score (fewer than k finite scores): those weigh exactly 0
+  const bool flag_overflow = overflow && !(kth == score_key(-INFINITY) && best_key != kth);
+  const unsigned int n = n_greater + (overflow ? room : n_equal);
+
+  // ---- candidates into LDS as (key << 32 | ~id), then a bitonic sort: score descending, id ascending ------------------
+  cand[tid] = 0ull;
+  if (tid < 4) slot[tid] = tid == 2 ? n : 0u;
+  __syncthreads();
+  for (int i = tid; i < vocab; i += SAMPLE_THREADS) {
+    const uint32_t key = score_key(score_at(sa, i));
+    const unsigned long long v = ((unsigned long long)key << 32) | (uint32_t)(~i);
+    if (key > kth)
+      cand[atomicAdd(&slot[0], 1u)] = v;
+    else if (key == kth && kth != 0u && !overflow)
+      cand[n_greater + atomicAdd(&slot[1], 1u)] = v;
+  }
+  if (overflow) {  // ties in id order, 1024 ids at a time, until the room is used up
+    unsigned int placed = 0u;
+    for (int base = 0; base < vocab && placed < room; base += SAMPLE_THREADS) {
+      const int i = base + tid;
+      const bool tie = i < vocab && score_key(score_at(sa, i)) == kth;
+      const unsigned long long m = __ballot(tie);
+      if (lane == 0) wcnt[wid] = (unsigned int)__popcll(m);
+      __syncthreads();
+      unsigned int before = 0u, total = 0u;
+      for (int w = 0; w < SAMPLE_WAVES; ++w) before += w < wid ? wcnt[w] : 0u, total += wcnt[w];
+      const unsigned int r = placed + before + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+      if (tie && r < room) cand[n_greater + r] = ((unsigned long long)kth << 32) | (uint32_t)(~i);
+      placed += total;
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  int P = 64;
+  while (P < (int)n) P <<= 1;
+  for (int k2 = 2; k2 <= P; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      if (tid < (P >> 1)) {
+        const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
+        const unsigned long long a = cand[i], b = cand[l];
+        if (((i & k2) == 0) ? (a < b) : (a > b)) cand[i] = b, cand[l] = a;
+      }
+      __syncthreads();
+    }
+
+  // ---- weights, inclusive sums, nucleus, draw ---------------------------------------------------------------------
+  const float s0 = key_score((uint32_t)(cand[0] >> 32));
+  float w = 0.f;
+  if (tid < (int)n) {
+    const float s = key_score((uint32_t)(cand[tid] >> 32));
+    w = s == s0 ? 1.f : expf(s - s0);
+  }
+  float c = wave_scan_f32(w, lane);
+  if (lane == 63) wsum[wid] = c;
+  __syncthreads();
+  float z = 0.f, off = 0.f;
+  for (int ww = 0; ww < SAMPLE_WAVES; ++ww) {
+    if (ww == wid) off = z;
+    z += wsum[ww];
+  }
+  c += off;
+  cdf[tid] = c;
+  __syncthreads();
+  if (cfg.top_p < 1.0f && tid >= 1 && tid < (int)n && z - cdf[tid - 1] <= (1.0f - cfg.top_p) * z) atomicMin(&slot[2], (unsigned int)tid);
+  __syncthreads();
+  const unsigned int m = slot[2];  // kept: the first m candidates (m >= 1)
+  if (tid == 0) slot[3] = m - 1u;
+  __syncthreads();
+  const float target = u * cdf[m - 1u];
+  if (tid < (int)m && w > 0.f && c > target) atomicMin(&slot[3], (unsigned int)tid);
+  __syncthreads();
+  if (tid == 0) finish((int)~(uint32_t)cand[slot[3]], flag_overflow ? 8 : 0);
+}
+
+__global__ void sampler_seen_kernel(uint32_t* __restrict__ seen, int vocab, const int32_t* __restrict__ tokens, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int t = tokens[i];
+  if (t >= 0 && t < vocab) atomicOr(&seen[t >> 5], 1u << (t & 31));
+}
+
+// a host struct into device memory as a kernel argument: stream-ordered and capturable, whatever the host memory is
+__global__ void sampler_config_store_kernel(woq_sampler_config v, woq_sampler_config* __restrict__ dst) { *dst = v; }
+
+}  // namespace
+
+void launch_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg_dev, const float* u_dev,
+                   int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out,
+                   int* status, hipStream_t st) {
+  hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(SAMPLE_THREADS), 0, st, logits, vocab, seen, cfg_dev, u_dev, token,
+                     pos_advance, pos_fixed, log, philox_out, status);
+}
+
+void launch_sampler_seen(uint32_t* seen, int vocab, const int32_t* tokens, int n, hipStream_t st) {
+  if (n > 0) hipLaunchKernelGGL(sampler_seen_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seen, vocab, tokens, n);
+}
+
+void launch_sampler_config_store(const woq_sampler_config& cfg, woq_sampler_config* dst, hipStream_t st) {
+  hipLaunchKernelGGL(sampler_config_store_kernel, dim3(1), dim3(1), 0, st, cfg, dst);
+}
+
+const char* sampler_config_problem(const woq_sampler_config& c) {
+  if (!(c.repetition_penalty > 0.f)) return "QBits: repetition_penalty must be a positive float";
+  if (c.do_sample == 0) return nullptr;
+  if (!(c.temperature > 0.f) || c.temperature * 0.f != 0.f) return "QBits: temperature must be a positive finite float when sampling";
+  if (!(c.top_p >= 0.f && c.top_p <= 1.f)) return "QBits: top_p must be in [0, 1]";
+  if (c.top_k < 0 || c.top_k > SAMPLE_MAX_CAND)
+    return "QBits: the native sampler takes top_k in [0, 1024] (larger values stay on the torch sampler)";
+  if (c.top_k == 0 && c.top_p < 1.f)
+    return "QBits: the native sampler takes top_k = 0 only with top_p = 1 (a nucleus over the whole vocabulary stays on "
+           "the torch sampler)";
+  return nullptr;
+}
+
+}  // namespace woq
+
+extern "C" {
+
+WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
+                             const float* u_or_null, const int32_t* pos_dev, int32_t* token_out, uint32_t* philox_out4,
+                             int* status, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(logits && seen && cfg && pos_dev && token_out && vocab >= 1, "QBits: bad sampler probe arguments");
+  const char* why = woq::sampler_config_problem(*cfg);
+  if (why) return woq::fail(why);
+  const hipStream_t st = (hipStream_t)stream;
+  woq_sampler_config* cfg_dev = nullptr;
+  WOQ_HIP(hipMallocAsync((void**)&cfg_dev, sizeof(woq_sampler_config), st));
+  woq::launch_sampler_config_store(*cfg, cfg_dev, st);
+  woq::launch_sample(logits, vocab, seen, cfg_dev, u_or_null, token_out, nullptr, pos_dev, nullptr, philox_out4, status,
+                     st);
+  WOQ_HIP(hipFreeAsync(cfg_dev, st));
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+}  // extern "C"

@@ -168,15 +168,16 @@ class BaseModel:
 
     def _engine_stream_sampled(self, ids, config, n_out):
         """The reference's default request (sampling + repetition penalty) on the fused engine: tokens are chosen on the
-        device (runtime.engine.DeviceSampler) and handed to the text stream one at a time."""
-        from ...runtime.engine import DeviceSampler, iter_sampled
+        device — by the engine's native sampler where it covers the request, else by runtime.engine.DeviceSampler — and
+        handed to the text stream one at a time."""
+        from ...runtime.engine import iter_sampled_auto
 
         eng, tok = self.engine, self.tokenizer
         eos = tok.eos_token_id
-        sampler = DeviceSampler(do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
-                                top_p=config.top_p, repetition_penalty=config.repetition_penalty)
         out, shown = [], ""
-        for new in iter_sampled(eng, ids, config.max_new_tokens, sampler, eos=() if eos is None else (eos,), burst=1):
+        for new in iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
+                                     do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
+                                     top_p=config.top_p, repetition_penalty=config.repetition_penalty):
             for t in new:
                 if eos is not None and t == eos:
                     continue

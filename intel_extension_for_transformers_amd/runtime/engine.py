@@ -7,6 +7,7 @@ decode path is an optional post-pass over the same WQH1 blobs. torch is plumbing
 streams); every kernel is in libwoq_hip.so.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -72,6 +73,8 @@ class WoqDecoderEngine:
         self._allreduce_cb = None
         self._comm = None
         self.captured = False
+        self.sampler_installed = False     # native sampler in the chaining tail (set_sampler / clear_sampler)
+        self.native_sampled_requests = 0   # requests that ran with it (iter_generate)
         # hipGraph capture is not allowed on the legacy null stream torch uses by default
         self._stream = torch.cuda.Stream(device=self.device)
 
@@ -410,9 +413,109 @@ class WoqDecoderEngine:
         L.check(L.lib().woq_engine_set_allreduce(self._h, ctypes.cast(None, L.ALLREDUCE_FN), None))
         self._allreduce_cb = None
 
-    def generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16):
+    # ---- native sampler: the next token of a chaining step chosen by csrc/woq_sample.hip ---------------------------
+    NATIVE_TOP_K_MAX = 1024
+
+    def native_sampler_supports(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0):
+        """True when `set_sampler` takes this request (the checks of csrc/woq_sample.hip `sampler_config_problem`): one
+        GPU (a tensor-parallel head is vocab-sharded); a positive penalty alone; sampling with a positive finite
+        temperature and 1 <= top_k <= 1024 with any top_p, or top_k = 0 with top_p = 1. Everything else keeps
+        `iter_sampled` + `DeviceSampler`, which answers or raises as it always did."""
+        if self.cfg.tp_size > 1 or self._comm is not None or self._allreduce_cb is not None:
+            return False
+        if not float(1.0 if repetition_penalty is None else repetition_penalty) > 0.0:
+            return False
+        if not do_sample:
+            return True
+        temperature = float(1.0 if temperature is None else temperature)
+        if not (temperature > 0.0 and math.isfinite(temperature)):
+            return False
+        top_k, top_p = int(top_k or 0), float(1.0 if top_p is None else top_p)
+        if top_k < 0 or top_k > self.NATIVE_TOP_K_MAX or not 0.0 <= top_p <= 1.0:
+            return False
+        return top_k > 0 or top_p >= 1.0
+
+    def set_sampler(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):
+        """Install (or re-parameterise) the native sampler: from now on every chaining step — the prompt pass's tail,
+        `step`, `run`, `replay` — picks its token with Hugging Face's repetition penalty / temperature / top-k / top-p in
+        HF's order and a Philox draw keyed by (`seed`, position). Installing drops a captured graph; changing the
+        parameters of an installed sampler does not (the kernel reads them from device memory)."""
+        if do_sample and float(1.0 if temperature is None else temperature) <= 0:
+            raise ValueError("`temperature` has to be a strictly positive float when sampling")
+        cfg = L.sampler_config(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
+        L.check(L.lib().woq_engine_set_sampler(self._h, ctypes.byref(cfg)))
+        if not self.sampler_installed:
+            self.captured = False
+        self.sampler_installed = True
+
+    def clear_sampler(self):
+        """Back to the plain greedy tail (drops a graph captured with the sampler)."""
+        L.check(L.lib().woq_engine_set_sampler(self._h, None))
+        if self.sampler_installed:
+            self.captured = False
+        self.sampler_installed = False
+
+    def mark_seen(self, token_ids, clear=True):
+        """The repetition penalty's history: set the bits of `token_ids` (after emptying the set when `clear`)."""
+        t = torch.as_tensor(token_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        L.check(L.lib().woq_engine_sampler_seen(self._h, t.data_ptr() if t.numel() else None, int(t.numel()),
+                                                int(bool(clear)), L.stream_ptr()))
+
+    def seen_bits(self):
+        """uint32-as-int32 view [(vocab + 31) / 32] of the history bit set (bit i & 31 of word i >> 5 = id i)."""
+        return _device_view(L.lib().woq_engine_sampler_seen_ptr(self._h), ((self.cfg.vocab + 31) // 32,), self.device,
+                            "<i4")
+
+    def iter_generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=()):
+        """Prompt pass + bursts of `burst` chained steps, yielding each burst's new tokens (the first one alone: it comes
+        from the prompt pass's tail). With a sampler installed the prompt is marked in the history first and every
+        token is the sampler's; without one this is the greedy chain. Stops after the first id in `eos` (kept)."""
+        ids = [int(t) for t in prompt_ids]
+        n = len(ids)
+        if n + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
+            raise RuntimeError("QBits: prompt (%d) + max_new_tokens (%d) exceeds the engine's max_ctx (%d)"
+                               % (n, max_new_tokens, self.cfg.max_ctx))
+        if self.sampler_installed:
+            self.mark_seen(ids, clear=True)
+            self.native_sampled_requests += 1
+        for s0 in range(0, n, chunk):
+            # the sampled tail marks its pick in the history, so with a sampler only the last chunk may end on it: an
+            # earlier chunk's throw-away token is neither prompt nor generated (the greedy argmax has no side effect)
+            self.prefill(ids[s0:s0 + chunk], start_pos=s0, greedy=not self.sampler_installed or s0 + chunk >= n)
+        self.tune_attn_for(n + max_new_tokens)
+        if max_new_tokens < 1:
+            return
+        eos = set(int(e) for e in eos)
+        first = int(self.token.item())  # the prompt pass's token
+        yield [first]
+        if first in eos:
+            return
+        made = 1
+        if made < max_new_tokens:
+            self.prepare_decode(greedy=True)
+        log = self.token_log()
+        while made < max_new_tokens:
+            k = min(int(burst), max_new_tokens - made)
+            p0 = n + made - 1  # position the next step feeds
+            self.replay(k)
+            new = log[p0:p0 + k].tolist()  # the burst's one host synchronisation
+            made += k
+            for j, t in enumerate(new):
+                if t in eos:
+                    yield new[:j + 1]
+                    return
+            yield new
+
+    def generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, sampler=None):
         """Greedy decode: the prompt goes through the prefill pass in chunks of `chunk` tokens, then bursts of `burst`
-        steps chained on the device (one host read of the token log per burst)."""
+        steps chained on the device (one host read of the token log per burst). `sampler` = a dict of `set_sampler`
+        arguments: the same loop with the native sampler installed for this call (removed afterwards)."""
+        if sampler is not None:
+            self.set_sampler(**sampler)
+            try:
+                return sum(self.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst), [])
+            finally:
+                self.clear_sampler()
         out = []
         ids = [int(t) for t in prompt_ids]
         if len(ids) + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
@@ -543,6 +646,35 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
                 new, done = new[:j + 1], True
                 break
         yield new
+
+
+def request_seed():
+    """One 63-bit value from torch's default CPU generator: `torch.manual_seed` makes sampled requests reproducible."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+
+
+def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chunk=2048, do_sample=False,
+                      temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0):
+    """A sampling / repetition-penalty request: on the native sampler (chained bursts, graph replays) when
+    `native_sampler_supports` says so, else `iter_sampled` with a `DeviceSampler`. The sampler is removed after the
+    request, so the next greedy request runs the untouched greedy path: in a `finally` of this generator, which runs when
+    the stream is exhausted, closed or collected — a consumer that stops early and keeps the generator alive should
+    `close()` it. Installing and removing each drop the captured graphs, so a sampled request and the greedy request
+    after it each pay one capture."""
+    opts = dict(do_sample=bool(do_sample), temperature=1.0 if temperature is None else temperature, top_k=top_k or 0,
+                top_p=1.0 if top_p is None else top_p,
+                repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty)
+    if opts["do_sample"] and float(opts["temperature"]) <= 0:
+        raise ValueError("`temperature` has to be a strictly positive float when sampling")
+    if not engine.native_sampler_supports(**opts):
+        yield from iter_sampled(engine, prompt_ids, max_new_tokens, DeviceSampler(**opts), eos=eos, burst=burst,
+                                chunk=chunk)
+        return
+    engine.set_sampler(seed=request_seed(), **opts)
+    try:
+        yield from engine.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, eos=eos)
+    finally:
+        engine.clear_sampler()
 
 
 def generate_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), on_tokens=None, burst=16, chunk=2048):

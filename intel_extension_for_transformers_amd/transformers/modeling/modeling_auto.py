@@ -367,11 +367,8 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
 
     def run_sampled():
         """prompt pass + steps whose next token the device sampler picks; returns (tokens, per-token latency)."""
-        from ...runtime.engine import DeviceSampler, generate_sampled
+        from ...runtime.engine import iter_sampled_auto
 
-        sampler = DeviceSampler(do_sample=opt("do_sample", False), temperature=opt("temperature", 1.0),
-                                top_k=opt("top_k", 0), top_p=opt("top_p", 1.0),
-                                repetition_penalty=opt("repetition_penalty", 1.0))
         latency, mark = [], [time.time()]
 
         def on_tokens(new):
@@ -382,8 +379,15 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
                 for t in new:
                     streamer.put(torch.tensor([t]))
 
-        out = generate_sampled(eng, prompt, max_new, sampler, eos=eos, on_tokens=on_tokens,
-                               burst=1 if streamer is not None else 16)
+        # the native sampler inside the engine's chained steps where it covers the request (runtime.engine.
+        # WoqDecoderEngine.native_sampler_supports), else a native step + the torch DeviceSampler per token
+        out = []
+        for new in iter_sampled_auto(eng, prompt, max_new, eos=eos, burst=1 if streamer is not None else 16,
+                                     do_sample=opt("do_sample", False), temperature=opt("temperature", 1.0),
+                                     top_k=opt("top_k", 0), top_p=opt("top_p", 1.0),
+                                     repetition_penalty=opt("repetition_penalty", 1.0)):
+            out += new
+            on_tokens(new)
         return out, latency
 
     def run_once():
@@ -430,7 +434,14 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     # qkv + attention launch gave up waiting for its head's q / k / v (GPU preempted / shared / under a debugger for
     # longer than the hand-off's 20 ms bound) and went on with stale values — the tokens since then and the KV rows of
     # those positions are wrong. bit 1: a step ran at or beyond max_ctx. Neither may come back as a normal result.
+    # bit 3 (native sampler): more than 1024 candidates tied at the k-th value and the 1024 lowest ids among them were
+    # kept — a handled truncation, the tokens stand.
     st = eng.status()
+    if st > 0 and (st & 8):
+        logger.warning("QBits: the native sampler kept the 1024 lowest ids of a larger tie at the k-th value")
+        st &= ~8
+        if st == 0:
+            eng.clear_status()
     if st != 0:
         eng.clear_status()
         if st & 1:

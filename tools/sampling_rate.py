@@ -1,0 +1,76 @@
+"""Rate of sampled requests on the decode engine: the native sampler (csrc/woq_sample.hip, chained bursts) against the
+torch sampler path (`iter_sampled` + `DeviceSampler`, one eager step + a dozen torch kernels per token) and the greedy
+chain, in one process. Llama-2-7B geometry over synthetic int4 weights (`synth_llama_weights`), a 32-token prompt + 256
+new tokens, prompt pass included (the harness of profiles/r04n_* / r04z_*). The paths alternate, every path is warmed
+up once, then `--rounds` timed rounds each; host clock around work that ends in a synchronise (the last burst's token
+read). Prints medians and min-max as tokens/s and writes them to `--out`.
+
+    python tools/sampling_rate.py --out profiles/r07_native_sampler.txt
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/sampling_rate.py --rounds 1 --paths native_default
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from intel_extension_for_transformers_amd.runtime.engine import (DeviceSampler, WoqDecoderEngine, generate_sampled,  # noqa: E402
+                                                                 synth_llama_weights)
+
+DEFAULT = dict(do_sample=True, temperature=0.1, top_k=40, top_p=0.75, repetition_penalty=1.1)  # neural_chat/config.py
+PENALTY = dict(do_sample=False, repetition_penalty=1.1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--prompt", type=int, default=32)
+    ap.add_argument("--new", type=int, default=256)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--paths", default="native_default,torch_default,native_penalty,torch_penalty,greedy")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    geom = dict(hidden=4096, inter=11008, heads=32, kv_heads=32, head_dim=128, layers=a.layers, vocab=32000)
+    eng = WoqDecoderEngine(max_ctx=512, **geom)
+    synth_llama_weights(eng, **geom)
+    prompt = torch.randint(3, geom["vocab"], (a.prompt,), generator=torch.Generator().manual_seed(1)).tolist()
+
+    def native(kw):
+        return lambda: eng.generate(prompt, a.new, sampler=dict(seed=1234, **kw))
+
+    def torch_path(kw):
+        return lambda: generate_sampled(eng, prompt, a.new, DeviceSampler(**kw))
+
+    paths = {"native_default": native(DEFAULT), "torch_default": torch_path(DEFAULT), "native_penalty": native(PENALTY),
+             "torch_penalty": torch_path(PENALTY), "greedy": lambda: eng.generate(prompt, a.new)}
+    names = [n for n in a.paths.split(",") if n]
+    times = {n: [] for n in names}
+    for r in range(a.rounds + 1):  # round 0 warms every path up (graph capture, torch's lazy kernels)
+        for n in names:
+            torch.cuda.synchronize()
+            tic = time.perf_counter()
+            out = paths[n]()  # ends on a host read of the last burst's tokens
+            torch.cuda.synchronize()
+            if r > 0:
+                times[n].append(time.perf_counter() - tic)
+            assert len(out) == a.new
+    assert eng.status() == 0
+    lines = ["# Llama-2-7B geometry (%d layers), int4 g128, %d-token prompt + %d new tokens, prompt pass included; "
+             "tokens/s over %d alternating rounds after one warm-up round of every path" % (a.layers, a.prompt, a.new, a.rounds),
+             "# path: median (min - max)"]
+    for n in names:
+        rate = sorted(a.new / t for t in times[n])
+        lines.append("%-15s %8.1f (%.1f - %.1f)" % (n, statistics.median(rate), rate[0], rate[-1]))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
