@@ -275,6 +275,25 @@ WOQ_API int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg)
  * marks every token it picks itself. */
 WOQ_API int woq_engine_sampler_seen(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream);
 WOQ_API void* woq_engine_sampler_seen_ptr(woq_engine* e);
+/* ---- per-token log-probabilities (new entry points only; WOQ_ABI_VERSION stays 4) ----------------------------------
+ * With recording on, every step that chains on the device (greedy != 0: the prompt pass's tail, woq_engine_step /
+ * _steps / _capture / _replay) writes, after its pick, one row of three device logs indexed like the token log (row p
+ * = the step that fed position p), csrc/woq_logprob.hip. A row describes the RAW model distribution, log_softmax over
+ * the fp32 lm_head logits of that step, before repetition penalty, temperature, top-k and top-p, whether the token came
+ * from the argmax or from the sampler:
+ *   chosen[p]          fp32   log-probability of the token the step picked
+ *   top_id[p][0..20)   int32  the 20 ids with the largest logits, ordered by (logit descending, id ascending)
+ *   top_lp[p][0..20)   fp32   their log-probabilities
+ * Always 20 (fewer alternatives are a host-side slice). NaN logits weigh 0 and are never listed; fewer than 20 other
+ * logits pad with id -1 / -inf; -inf logits are legal (log-probability -inf, listed last, ties by id); an all-NaN row
+ * gives chosen = NaN and every id -1 (status bit 2 comes from the pick). A logits-only step (greedy == 0) writes
+ * nothing. Two launches per step whose shape depends on the vocabulary alone; with recording off the step is unchanged.
+ * set_logprobs allocates the logs, max_ctx + 1 rows each, on first use; switching on or off drops a captured graph.
+ * Fails with a "QBits:" message on a tensor-parallel engine (vocab-sharded head). */
+WOQ_API int woq_engine_set_logprobs(woq_engine* e, int on);
+WOQ_API int woq_engine_logprobs(woq_engine* e); /* 1 when recording */
+/* which: 0 chosen, 1 top_id, 2 top_lp; NULL before the first woq_engine_set_logprobs(e, 1) */
+WOQ_API void* woq_engine_logprob_ptr(woq_engine* e, int which);
 /* tensor-parallel seam: when set, the engine calls `fn(user, buf_dev, count_f32, stream)` after
  * o_proj and after down_proj (row-parallel partial sums -> sum over ranks). The Python host binds it
  * to RCCL via torch.distributed. NULL = single GPU. */

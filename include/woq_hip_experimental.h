@@ -80,6 +80,11 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
 WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
                              const float* u_or_null, const int32_t* pos_dev, int32_t* token_out, uint32_t* philox_out4,
                              int* status, void* stream);
+/* the log-probability record alone (tests/test_gpu_logprob_kernel.py), forwarding to the engine's own launcher
+ * unchanged: logits fp32 [vocab], token_dev = device int32 id whose log-probability goes to chosen_out[0];
+ * top_id_out20 / top_lp_out20 = device int32 / fp32 [20]. Scratch is allocated and freed on `stream`. */
+WOQ_API int woq_probe_logprobs(const float* logits, int vocab, const int32_t* token_dev, float* chosen_out,
+                               int32_t* top_id_out20, float* top_lp_out20, void* stream);
 
 #ifdef __cplusplus
 }

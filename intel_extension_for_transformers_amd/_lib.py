@@ -85,12 +85,14 @@ EXPORTS = [
     "woq_comm_status", "woq_comm_set_timeout_ms", "woq_comm_destroy", "woq_engine_set_comm", "woq_set_workspace",
     "woq_engine_uses_xq", "woq_engine_token_log_ptr", "woq_table_digit_planes",
     "woq_engine_set_sampler", "woq_engine_sampler_seen", "woq_engine_sampler_seen_ptr",
+    "woq_engine_set_logprobs", "woq_engine_logprobs", "woq_engine_logprob_ptr",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
     "woq_engine_set_attn_chunk", "woq_engine_attn_chunk", "woq_engine_time_gemv", "woq_engine_time_gemv_mask",
     "woq_engine_time_twin", "woq_engine_set_time_eager", "woq_engine_time_prefill_gemm", "woq_gemm_form_log",
     "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
+    "woq_probe_logprobs",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -185,6 +187,11 @@ def lib():
     L.woq_engine_sampler_seen_ptr.restype = vp
     L.woq_engine_sampler_seen_ptr.argtypes = [vp]
     L.woq_probe_sample.argtypes = [vp, ci, vp, ctypes.POINTER(SamplerConfig), vp, vp, vp, vp, vp, vp]
+    L.woq_engine_set_logprobs.argtypes = [vp, ci]
+    L.woq_engine_logprobs.argtypes = [vp]
+    L.woq_engine_logprob_ptr.restype = vp
+    L.woq_engine_logprob_ptr.argtypes = [vp, ci]
+    L.woq_probe_logprobs.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -243,6 +250,17 @@ def probe_sample(logits, seen, cfg, pos, token_out, u=None, philox_out=None, sta
     opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
     rc = lib().woq_probe_sample(_ptr(logits), int(logits.numel()), _ptr(seen), ctypes.byref(cfg), opt(u), _ptr(pos),
                                 _ptr(token_out), opt(philox_out), opt(status), stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+LOGPROB_TOP = 20  # ids a log-probability record lists per position (csrc/woq_logprob.hip LP_TOP)
+
+
+def probe_logprobs(logits, token, chosen_out, top_id_out, top_lp_out):
+    """the log-probability record alone (woq_probe_logprobs): device tensors, the current stream."""
+    rc = lib().woq_probe_logprobs(_ptr(logits), int(logits.numel()), _ptr(token), _ptr(chosen_out), _ptr(top_id_out),
+                                  _ptr(top_lp_out), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
 

@@ -137,6 +137,13 @@ struct woq_engine {
   woq_sampler_config* samp_cfg = nullptr;
   uint32_t* samp_seen = nullptr;  // [(vocab + 31) / 32]
   int seen_words() const { return (cfg.vocab + 31) / 32; }
+  // log-probability record (woq_logprob.hip): with `logprobs_on` every chaining step writes row pos - 1 of three logs,
+  // [max_ctx + 1] rows each like tok_log, after its pick. Allocated by the first woq_engine_set_logprobs(e, 1)
+  bool logprobs_on = false;
+  float* lp_chosen = nullptr;   // [max_ctx + 1]
+  int32_t* lp_top_id = nullptr; // [max_ctx + 1][20]
+  float* lp_top_lp = nullptr;   // [max_ctx + 1][20]
+  void* lp_ws = nullptr;        // the slices' partial results
 };
 
 using namespace woq;
@@ -261,13 +268,20 @@ static void engine_sample(woq_engine* e, hipStream_t st) {
   launch_sample(e->logits, e->cfg.vocab, e->samp_seen, e->samp_cfg, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr,
                 e->fuse_status, st);
 }
+// the record of the pick that was just launched: reads token[0], pos[0] - 1 and the logits, which the stream orders
+// before the next lm_head (also behind a fused argmax + embed launch: that one writes the residual stream, not logits)
+static int engine_logprobs(woq_engine* e, hipStream_t st) {
+  if (!e->logprobs_on) return 0;
+  return launch_logprobs(e->logits, e->cfg.vocab, e->token, e->pos, e->cfg.max_ctx + 1, e->lp_ws, e->lp_chosen,
+                         e->lp_top_id, e->lp_top_lp, st);
+}
 static int engine_head(woq_engine* e, int greedy, hipStream_t st, bool fuse_next = false) {
   const woq_engine_config& c = e->cfg;
   if (greedy && e->sampler_on) {  // the penalty changes values after the lm_head: its (max, index) pairs are of no use
     launch_lm_head(e->hidden, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, e->logits, nullptr,
                    nullptr, st);
     engine_sample(e, st);
-    return 0;
+    return engine_logprobs(e, st);
   }
   launch_lm_head(e->hidden, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, e->logits,
                  greedy ? e->am_val : nullptr, greedy ? e->am_idx : nullptr, st);
@@ -276,13 +290,14 @@ static int engine_head(woq_engine* e, int greedy, hipStream_t st, bool fuse_next
     launch_argmax_embed(e->am_val, e->am_idx, (c.vocab + 15) / 16, e->token, e->pos, e->tok_log, e->embed, e->embed_dtype,
                         c.hidden, e->hidden, xq ? e->layers[0].ln1 : nullptr, xq ? e->xq_hidden : kNoXq,
                         xq ? e->ssq_part : nullptr, e->step_seq, c.max_ctx, e->fuse_status, st);
-    return 0;
+    return engine_logprobs(e, st);
   }
   if (greedy && e->comm && c.tp_size > 1)  // vocab-sharded head: one (max, global index) pair per rank
     return woq_comm_launch_greedy(e->comm, e->am_val, e->am_idx, (c.vocab + 15) / 16, e->vocab_offset, e->token,
                                   e->pos, e->tok_log, st);
-  if (greedy) launch_argmax_pairs(e->am_val, e->am_idx, (c.vocab + 15) / 16, e->token, e->pos, e->tok_log, st);
-  return 0;
+  if (!greedy) return 0;
+  launch_argmax_pairs(e->am_val, e->am_idx, (c.vocab + 15) / 16, e->token, e->pos, e->tok_log, st);
+  return engine_logprobs(e, st);
 }
 
 // sum of the row-parallel partials over the tensor-parallel ranks, in place on the residual stream, after sub-block
@@ -425,7 +440,7 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
     engine_sample(e, st);  // token <- sample at counter start + T - 1, pos <- start + T
   else if (greedy)
     launch_argmax(e->logits, c.vocab, e->token, e->pos, st);  // token <- argmax, pos <- start + T
-  return 0;
+  return greedy ? engine_logprobs(e, st) : 0;  // the first generated token's record, row start + T - 1
 }
 
 // `reps` passes of `body(stream)` between two events on `st` (after one untimed pass): what the launches cost inside the
@@ -828,6 +843,44 @@ int woq_engine_sampler_seen(woq_engine* e, const int32_t* tokens_dev, int n, int
 }
 
 void* woq_engine_sampler_seen_ptr(woq_engine* e) { return e ? e->samp_seen : nullptr; }
+
+int woq_engine_set_logprobs(woq_engine* e, int on) {
+  WOQ_TRY
+  WOQ_CHECK(e, "QBits: null engine");
+  const bool want = on != 0;
+  if (want) {
+    WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+              "QBits: log-probabilities need the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
+    WOQ_CHECK(logprob_vocab_ok(e->cfg.vocab), "QBits: the log-probability record covers vocabularies of up to 418816 ids");
+    if (e->lp_chosen == nullptr) {
+      const size_t rows = (size_t)e->cfg.max_ctx + 1;
+      void *a = nullptr, *b = nullptr, *c = nullptr, *w = nullptr;
+      WOQ_HIP(hipMalloc(&a, rows * 4));
+      e->owned.push_back(a);
+      WOQ_HIP(hipMalloc(&b, rows * 20 * 4));
+      e->owned.push_back(b);
+      WOQ_HIP(hipMalloc(&c, rows * 20 * 4));
+      e->owned.push_back(c);
+      WOQ_HIP(hipMalloc(&w, logprob_workspace_bytes(e->cfg.vocab)));
+      e->owned.push_back(w);
+      WOQ_HIP(hipMemset(a, 0, rows * 4));
+      WOQ_HIP(hipMemset(b, 0, rows * 20 * 4));
+      WOQ_HIP(hipMemset(c, 0, rows * 20 * 4));
+      e->lp_top_id = (int32_t*)b, e->lp_top_lp = (float*)c, e->lp_ws = w;
+      e->lp_chosen = (float*)a;  // last: what woq_engine_logprob_ptr and the steps test
+    }
+  }
+  if (want != e->logprobs_on) engine_drop_graphs(e);  // a captured graph holds the other tail
+  e->logprobs_on = want;
+  WOQ_END
+}
+
+int woq_engine_logprobs(woq_engine* e) { return e && e->logprobs_on ? 1 : 0; }
+
+void* woq_engine_logprob_ptr(woq_engine* e, int which) {
+  if (!e || e->lp_chosen == nullptr) return nullptr;
+  return which == 0 ? (void*)e->lp_chosen : which == 1 ? (void*)e->lp_top_id : which == 2 ? (void*)e->lp_top_lp : nullptr;
+}
 
 int woq_engine_step(woq_engine* e, int greedy, void* stream) {
   WOQ_TRY

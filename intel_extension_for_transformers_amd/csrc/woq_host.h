@@ -134,6 +134,17 @@ void launch_sampler_config_store(const woq_sampler_config& cfg, woq_sampler_conf
 // null when the native sampler takes this combination, else the "QBits: ..." reason
 const char* sampler_config_problem(const woq_sampler_config& cfg);
 
+// ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
+// After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at
+// token[0] (chosen [max_rows]) and at the 20 best ids by (logit descending, id ascending) (top_id / top_lp
+// [max_rows][20], padded with -1 / -inf), NaN logits weighing 0. Two launches shaped by `vocab` alone (slices of 1024
+// ids, then one merging workgroup); `ws` = logprob_workspace_bytes(vocab) bytes of device scratch, 8-byte aligned.
+// Returns non-zero (message set) for a vocabulary the merge cannot hold; p outside [0, max_rows) writes nothing.
+bool logprob_vocab_ok(int vocab);  // 1 .. 409 slices: what the merging workgroup holds in registers
+size_t logprob_workspace_bytes(int vocab);
+int launch_logprobs(const float* logits, int vocab, const int32_t* token, const int32_t* pos, int max_rows, void* ws,
+                    float* chosen, int32_t* top_id, float* top_lp, hipStream_t st);
+
 // ---- woq_prefill.hip: prompt-pass launches and the grouped decode attention ---------------------------------------
 void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int M, int hidden, float* out,
                        hipStream_t st);

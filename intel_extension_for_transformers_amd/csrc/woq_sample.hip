@@ -16,6 +16,7 @@
 // depends on (seed, position, logits) only, so eager steps and graphs of any burst size give the same tokens.
 #include "woq_device.h"
 #include "woq_host.h"
+#include "woq_score_key.h"
 #include "../../include/woq_hip_experimental.h"
 
 namespace woq {
@@ -24,16 +25,6 @@ namespace {
 constexpr int SAMPLE_THREADS = 1024;
 constexpr int SAMPLE_WAVES = SAMPLE_THREADS / 64;
 constexpr int SAMPLE_MAX_CAND = 1024;
-
-// order-preserving key of a score: larger score <-> larger key; NaN -> 0 (below -inf, never a candidate); -0 == +0
-__device__ __forceinline__ uint32_t score_key(float s) {
-  if (s != s) return 0u;
-  const uint32_t u = __float_as_uint(s + 0.0f);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(uint32_t k) {
-  return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k);
-}
 
 struct ScoreArgs {
   const float* logits;

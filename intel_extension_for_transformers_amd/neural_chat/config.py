@@ -21,6 +21,7 @@ class GenerationConfig:
     return_stats: bool = False
     format_version: str = "v2"
     task: str = ""
+    logprobs: int = None  # 0..20: fill BaseModel.last_logprobs with every emitted token's log-probability + alternatives
 
 
 @dataclass

@@ -108,6 +108,7 @@ class BaseModel:
         t_start = time.time()
         first = [None]
         n_out = [0]
+        self.last_logprobs = []  # one dict per emitted token when config.logprobs is set (_note_logprobs)
         # one sequence, one beam: the fused engine — greedy chains on the device; sampling (the reference's default:
         # do_sample, temperature, top_k, top_p) and the repetition penalty pick the next token with the device sampler
         engine_ok = config.num_beams == 1 and (config.num_return_sequences or 1) == 1 and not config.bad_words_ids \
@@ -116,6 +117,8 @@ class BaseModel:
         def pieces():
             if engine_ok and self.engine is not None and n_in + config.max_new_tokens <= self.engine.cfg.max_ctx:
                 yield from self._engine_stream(ids[0].tolist(), config, n_out)
+            elif getattr(config, "logprobs", None) is not None:
+                raise RuntimeError("QBits: logprobs need the fused engine")
             else:
                 yield from self._hf_stream(ids, config, n_out)
 
@@ -142,11 +145,44 @@ class BaseModel:
                 for k, v in stats.items():
                     yield "| {:<22} | {:<27} |\n".format(k, v)
 
+    def _note_logprobs(self, out, t, lp, top):
+        """One entry of `last_logprobs` for token `t` about to be appended to the emitted ids `out`: its id, decoded
+        string, log-probability under the raw model distribution, the `top` alternatives as (id, string, logprob) and
+        `text_offset`, where the token starts in the returned text."""
+        tok = self.tokenizer
+        self.last_logprobs.append({
+            "token_id": int(t), "token": tok.decode([int(t)]), "logprob": float(lp),
+            "top": [(int(i), tok.decode([int(i)]), float(v)) for i, v in top if i >= 0],
+            "text_offset": len(tok.decode(out, skip_special_tokens=True)) if out else 0})
+
+    def _engine_stream_logprobs(self, bursts, n_out):
+        """Text pieces of an engine stream that yields `(tokens, chosen_lps, top)` bursts; fills `last_logprobs` (EOS
+        excluded, as from the text)."""
+        tok = self.tokenizer
+        eos = tok.eos_token_id
+        out, shown = [], ""
+        for new, lps, tops in bursts:
+            for t, lp, top in zip(new, lps, tops):
+                if eos is not None and t == eos:
+                    continue
+                self._note_logprobs(out, t, lp, top)
+                out.append(t)
+                n_out[0] += 1
+            text = tok.decode(out, skip_special_tokens=True)
+            if not text.endswith("\ufffd"):  # hold back incomplete multi-byte pieces, like TextIteratorStreamer
+                yield text[len(shown):]
+                shown = text
+
     def _engine_stream(self, ids, config, n_out):
         eng, tok = self.engine, self.tokenizer
         eos = tok.eos_token_id
         if config.do_sample or (config.repetition_penalty or 1.0) != 1.0:
             yield from self._engine_stream_sampled(ids, config, n_out)
+            return
+        if getattr(config, "logprobs", None) is not None:  # the same greedy chain, with the step's records read back
+            yield from self._engine_stream_logprobs(
+                eng.iter_generate(ids, config.max_new_tokens, burst=1, eos=() if eos is None else (eos,),
+                                  logprobs=config.logprobs), n_out)
             return
         for s0 in range(0, len(ids), 2048):
             eng.prefill(ids[s0:s0 + 2048], start_pos=s0, greedy=True)
@@ -174,6 +210,13 @@ class BaseModel:
 
         eng, tok = self.engine, self.tokenizer
         eos = tok.eos_token_id
+        if getattr(config, "logprobs", None) is not None:
+            yield from self._engine_stream_logprobs(
+                iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
+                                  do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
+                                  top_p=config.top_p, repetition_penalty=config.repetition_penalty,
+                                  logprobs=config.logprobs), n_out)
+            return
         out, shown = [], ""
         for new in iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
                                      do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,

@@ -40,6 +40,8 @@ class ChatCompletionRequest(_Wire):
     presence_penalty: Optional[float] = 0.0
     frequency_penalty: Optional[float] = 0.0
     user: Optional[str] = None
+    logprobs: Optional[bool] = False
+    top_logprobs: Optional[int] = None
 
 
 class CompletionRequest(_Wire):
@@ -57,6 +59,7 @@ class CompletionRequest(_Wire):
     presence_penalty: Optional[float] = 0.0
     frequency_penalty: Optional[float] = 0.0
     user: Optional[str] = None
+    logprobs: Optional[int] = None
 
 
 def _error(status, message):
@@ -87,7 +90,46 @@ def _check_ranges(req):
         return "%s is outside [0, 1] - 'top_p'" % req.top_p
     if req.top_k is not None and -1 < req.top_k < 1:
         return "%s is out of Range. Either set top_k to -1 or >=1." % req.top_k
+    return _check_logprobs(req)
+
+
+def _wanted_logprobs(req):
+    """How many alternatives per token the request asks for (None = no log-probabilities): the chat route's
+    `logprobs: true` + `top_logprobs: 0..20`, the completions route's `logprobs: 0..5`."""
+    if isinstance(req, ChatCompletionRequest):
+        return int(req.top_logprobs or 0) if req.logprobs else None
+    return req.logprobs
+
+
+def _check_logprobs(req):
+    if isinstance(req, ChatCompletionRequest):
+        if req.top_logprobs is not None and not 0 <= req.top_logprobs <= 20:
+            return "%s is outside [0, 20] - 'top_logprobs'" % req.top_logprobs
+        if req.top_logprobs is not None and not req.logprobs:
+            return "'top_logprobs' needs 'logprobs' to be true"
+    elif req.logprobs is not None and not 0 <= req.logprobs <= 5:
+        return "%s is outside [0, 5] - 'logprobs'" % req.logprobs
+    if _wanted_logprobs(req) is not None and req.stream:
+        return "QBits: logprobs are not available on streamed responses"
     return None
+
+
+def _token_bytes(token):
+    return list(token.encode("utf-8"))
+
+
+def _chat_logprobs(entries, n_top):
+    """`choices[i].logprobs` of a chat completion from BaseModel.last_logprobs entries."""
+    return {"content": [{"token": e["token"], "logprob": e["logprob"], "bytes": _token_bytes(e["token"]),
+                         "top_logprobs": [{"token": s, "logprob": lp, "bytes": _token_bytes(s)}
+                                          for _i, s, lp in e["top"][:n_top]]} for e in entries]}
+
+
+def _completion_logprobs(entries, n_top, shift=0):
+    """`choices[i].logprobs` of a plain completion; `shift` = length of an echoed prompt in front of the text."""
+    return {"tokens": [e["token"] for e in entries], "token_logprobs": [e["logprob"] for e in entries],
+            "top_logprobs": [{s: lp for _i, s, lp in e["top"][:n_top]} for e in entries],
+            "text_offset": [e["text_offset"] + shift for e in entries]}
 
 
 class TextChatAPIRouter(APIRouter):
@@ -154,12 +196,22 @@ class TextChatAPIRouter(APIRouter):
     # ---- generation ------------------------------------------------------------------------------------------------
     def _generate(self, prompt, config, stops):
         """-> (text, finish_reason)."""
+        return self._generate_logprobs(prompt, config, stops)[:2]
+
+    def _generate_logprobs(self, prompt, config, stops):
+        """-> (text, finish_reason, the chatbot's last_logprobs entries of the kept text or None). The entries are read
+        under the lock the generation ran under; a stop string keeps the tokens that start before the cut."""
         with self._gpu:
             text = self.get_chatbot().predict(query=prompt, config=config)
+            entries = None
+            if getattr(config, "logprobs", None) is not None:
+                entries = list(getattr(self.get_chatbot(), "last_logprobs", None) or [])
         cut = min([text.find(s) for s in stops if s in text], default=-1)
         if cut >= 0:
-            return text[:cut], "stop"
-        return text, ("length" if self._count(text) >= config.max_new_tokens else "stop")
+            if entries is not None:
+                entries = [e for e in entries if e["text_offset"] < cut]
+            return text[:cut], "stop", entries
+        return text, ("length" if self._count(text) >= config.max_new_tokens else "stop"), entries
 
     def _stream(self, prompt, config, stops):
         """Text pieces until a stop string shows up (the piece is cut there). The generation itself runs in a worker
@@ -270,6 +322,7 @@ async def create_chat_completion(request: ChatCompletionRequest):
     except ValueError as e:
         return _error(400, str(e))
     config = router.generation_config(request, 512)
+    n_top = config.logprobs = _wanted_logprobs(request)
     stops = router._stops(request)
     rid, created = "chatcmpl-" + uuid.uuid4().hex[:22], int(time.time())
     if request.stream:
@@ -292,8 +345,10 @@ async def create_chat_completion(request: ChatCompletionRequest):
     choices, n_out = [], 0
     try:
         for i in range(request.n or 1):
-            text, why = await run_in_threadpool(router._generate, prompt, config, stops)
+            text, why, entries = await run_in_threadpool(router._generate_logprobs, prompt, config, stops)
             choices.append({"index": i, "message": {"role": "assistant", "content": text}, "finish_reason": why})
+            if entries is not None:
+                choices[-1]["logprobs"] = _chat_logprobs(entries, n_top)
             n_out += router._count(text)
     except Exception as e:
         return _error(500, str(e))
@@ -310,6 +365,7 @@ async def create_completion(request: CompletionRequest):
         return err
     prompts = [request.prompt] if isinstance(request.prompt, str) else list(request.prompt)
     config = router.generation_config(request, 16)
+    n_top = config.logprobs = _wanted_logprobs(request)
     stops = router._stops(request)
     rid, created = "cmpl-" + uuid.uuid4().hex[:22], int(time.time())
     if request.stream:
@@ -334,8 +390,9 @@ async def create_completion(request: CompletionRequest):
     try:
         for p in prompts:
             for _ in range(request.n or 1):
-                text, why = await run_in_threadpool(router._generate, p, config, stops)
-                choices.append({"index": len(choices), "text": (p + text) if request.echo else text, "logprobs": None,
+                text, why, entries = await run_in_threadpool(router._generate_logprobs, p, config, stops)
+                lps = None if entries is None else _completion_logprobs(entries, n_top, len(p) if request.echo else 0)
+                choices.append({"index": len(choices), "text": (p + text) if request.echo else text, "logprobs": lps,
                                 "finish_reason": why})
                 n_in += router._count(p)
                 n_out += router._count(text)

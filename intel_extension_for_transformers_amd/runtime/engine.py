@@ -75,6 +75,7 @@ class WoqDecoderEngine:
         self.captured = False
         self.sampler_installed = False     # native sampler in the chaining tail (set_sampler / clear_sampler)
         self.native_sampled_requests = 0   # requests that ran with it (iter_generate)
+        self.logprobs_on = False           # log-probability record after every chaining pick (set_logprobs)
         # hipGraph capture is not allowed on the legacy null stream torch uses by default
         self._stream = torch.cuda.Stream(device=self.device)
 
@@ -466,10 +467,65 @@ class WoqDecoderEngine:
         return _device_view(L.lib().woq_engine_sampler_seen_ptr(self._h), ((self.cfg.vocab + 31) // 32,), self.device,
                             "<i4")
 
-    def iter_generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=()):
+    # ---- log-probability record: csrc/woq_logprob.hip after every chaining pick -------------------------------------
+    LOGPROB_TOP = L.LOGPROB_TOP
+
+    def set_logprobs(self, on=True):
+        """Record, after every chaining pick (the prompt pass's tail, `step`, `run`, `replay`), the log-probability of
+        the picked token and the 20 most likely ids under the RAW model distribution (log_softmax of the fp32 logits,
+        before penalty / temperature / top-k / top-p) into `logprob_log()`. Switching on or off drops a captured graph.
+        Raises on a tensor-parallel engine (the head is vocab-sharded)."""
+        L.check(L.lib().woq_engine_set_logprobs(self._h, int(bool(on))))
+        if bool(on) != self.logprobs_on:
+            self.captured = False
+        self.logprobs_on = bool(on)
+
+    def clear_logprobs(self):
+        """Recording off: the step is the one it was before `set_logprobs` (the logs keep their contents)."""
+        self.set_logprobs(False)
+
+    def logprob_log(self):
+        """(chosen fp32 [max_ctx + 1], top_id int32 [max_ctx + 1, 20], top_lp fp32 [max_ctx + 1, 20]): views of the
+        engine's logs, row p = the record of the step that fed position p (the index of `token_log`). Top ids are
+        ordered by (logit descending, id ascending) and padded with -1 / -inf."""
+        rows, get = self.cfg.max_ctx + 1, L.lib().woq_engine_logprob_ptr
+        if not get(self._h, 0):
+            raise RuntimeError("QBits: no log-probability log before the first set_logprobs()")
+        return (_device_view(get(self._h, 0), (rows,), self.device),
+                _device_view(get(self._h, 1), (rows, self.LOGPROB_TOP), self.device, "<i4"),
+                _device_view(get(self._h, 2), (rows, self.LOGPROB_TOP), self.device))
+
+    def iter_generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=(), logprobs=None):
         """Prompt pass + bursts of `burst` chained steps, yielding each burst's new tokens (the first one alone: it comes
         from the prompt pass's tail). With a sampler installed the prompt is marked in the history first and every
-        token is the sampler's; without one this is the greedy chain. Stops after the first id in `eos` (kept)."""
+        token is the sampler's; without one this is the greedy chain. Stops after the first id in `eos` (kept).
+        `logprobs` = N in 0..20: recording is on for this call (the previous state returns afterwards) and every burst
+        is `(tokens, chosen_lps, top)` with `top` one list of N `(id, log-probability)` pairs per token, read back in
+        the burst's one synchronisation."""
+        if logprobs is None:
+            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, None)
+            return
+        n_top = int(logprobs)
+        if not 0 <= n_top <= self.LOGPROB_TOP:
+            raise ValueError("`logprobs` is a count of alternatives in [0, %d]" % self.LOGPROB_TOP)
+        before = self.logprobs_on
+        self.set_logprobs(True)
+        try:
+            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, n_top)
+        finally:
+            self.set_logprobs(before)
+
+    def _records(self, p0, k, n_top):
+        """rows p0 .. p0 + k - 1 of the token log and the three logs in ONE device-to-host copy"""
+        chosen, top_id, top_lp = self.logprob_log()
+        rows = slice(p0, p0 + k)
+        packed = torch.cat([self.token_log()[rows, None].double(), chosen[rows, None].double(),
+                            top_id[rows, :n_top].double(), top_lp[rows, :n_top].double()], dim=1).tolist()
+        toks = [int(r[0]) for r in packed]
+        top = [[(int(i), lp) for i, lp in zip(r[2:2 + n_top], r[2 + n_top:])] for r in packed]
+        return toks, [r[1] for r in packed], top
+
+    def _iter_generate(self, prompt_ids, max_new_tokens, chunk, burst, eos, n_top):
         ids = [int(t) for t in prompt_ids]
         n = len(ids)
         if n + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
@@ -481,13 +537,19 @@ class WoqDecoderEngine:
         for s0 in range(0, n, chunk):
             # the sampled tail marks its pick in the history, so with a sampler only the last chunk may end on it: an
             # earlier chunk's throw-away token is neither prompt nor generated (the greedy argmax has no side effect)
-            self.prefill(ids[s0:s0 + chunk], start_pos=s0, greedy=not self.sampler_installed or s0 + chunk >= n)
+            # (and with recording on only the last chunk's tail leaves a record)
+            self.prefill(ids[s0:s0 + chunk], start_pos=s0,
+                         greedy=not (self.sampler_installed or n_top is not None) or s0 + chunk >= n)
         self.tune_attn_for(n + max_new_tokens)
         if max_new_tokens < 1:
             return
         eos = set(int(e) for e in eos)
         first = int(self.token.item())  # the prompt pass's token
-        yield [first]
+        if n_top is None:
+            yield [first]
+        else:  # its record is row n - 1; the token log has no entry there (the prompt pass's pick does not log)
+            _, lps, top = self._records(n - 1, 1, n_top)
+            yield [first], lps, top
         if first in eos:
             return
         made = 1
@@ -498,24 +560,35 @@ class WoqDecoderEngine:
             k = min(int(burst), max_new_tokens - made)
             p0 = n + made - 1  # position the next step feeds
             self.replay(k)
-            new = log[p0:p0 + k].tolist()  # the burst's one host synchronisation
+            if n_top is None:
+                new = log[p0:p0 + k].tolist()  # the burst's one host synchronisation
+            else:
+                new, lps, top = self._records(p0, k, n_top)  # the same, with the records in the copy
             made += k
-            for j, t in enumerate(new):
-                if t in eos:
-                    yield new[:j + 1]
-                    return
-            yield new
+            stop = next((j + 1 for j, t in enumerate(new) if t in eos), None)
+            if n_top is None:
+                yield new[:stop]
+            else:
+                yield new[:stop], lps[:stop], top[:stop]
+            if stop is not None:
+                return
 
-    def generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, sampler=None):
+    def generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, sampler=None, logprobs=None):
         """Greedy decode: the prompt goes through the prefill pass in chunks of `chunk` tokens, then bursts of `burst`
         steps chained on the device (one host read of the token log per burst). `sampler` = a dict of `set_sampler`
-        arguments: the same loop with the native sampler installed for this call (removed afterwards)."""
-        if sampler is not None:
-            self.set_sampler(**sampler)
+        arguments: the same loop with the native sampler installed for this call (removed afterwards). `logprobs` = N
+        in 0..20: returns `(tokens, chosen_lps, top)` instead (see `iter_generate`)."""
+        if sampler is not None or logprobs is not None:
+            if sampler is not None:
+                self.set_sampler(**sampler)
             try:
-                return sum(self.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst), [])
+                bursts = list(self.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, logprobs=logprobs))
+                if logprobs is None:
+                    return sum(bursts, [])
+                return tuple(sum((b[i] for b in bursts), []) for i in range(3))
             finally:
-                self.clear_sampler()
+                if sampler is not None:
+                    self.clear_sampler()
         out = []
         ids = [int(t) for t in prompt_ids]
         if len(ids) + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
@@ -612,11 +685,13 @@ class DeviceSampler:
         return idx[pick]
 
 
-def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, chunk=2048):
+def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, chunk=2048, logprobs=None):
     """Prompt pass + decode steps with the next token chosen by `sampler` on the device (sampling and / or repetition
     penalty: the requests `generate`'s greedy chain does not cover). Every step is the engine's native step (logits
     only) followed by a dozen small torch kernels; nothing synchronises until `burst` tokens are read back (1 for a
-    text stream). Yields each burst's new tokens; stops after the first id in `eos` (kept in the output, like HF)."""
+    text stream). Yields each burst's new tokens; stops after the first id in `eos` (kept in the output, like HF).
+    `logprobs` = N in 0..20: yields `(tokens, chosen_lps, top)` like `WoqDecoderEngine.iter_generate`, the records
+    computed here with `torch.log_softmax` + `torch.topk` over the raw logits (ties in whatever order topk leaves)."""
     ids = [int(t) for t in prompt_ids]
     n = len(ids)
     if n + max_new_tokens > engine.cfg.max_ctx:
@@ -629,6 +704,12 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
         engine.prefill(ids[s0:s0 + chunk], start_pos=s0, greedy=False)
     engine.tune_attn_for(n + max_new_tokens)
     eos = set(int(e) for e in eos)
+    n_top = None
+    if logprobs is not None:
+        n_top = min(int(logprobs), engine.cfg.vocab)
+        if not 0 <= int(logprobs) <= L.LOGPROB_TOP:
+            raise ValueError("`logprobs` is a count of alternatives in [0, %d]" % L.LOGPROB_TOP)
+        rec = torch.empty(max(max_new_tokens, 1), 1 + 2 * n_top, dtype=torch.float64, device=dev)
     done, made = False, 0
     while not done and made < max_new_tokens:
         k = min(burst, max_new_tokens - made)
@@ -636,6 +717,13 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
             if made > 0:
                 engine.step(greedy=False)  # logits of the token just chosen, at position n + made - 1
             tok = sampler(engine.logits, hist[:n + made])
+            if n_top is not None:  # the raw distribution's view of the pick and of its best ids
+                lsm = torch.log_softmax(engine.logits, -1)
+                rec[made, 0] = lsm[tok[0]]
+                if n_top:
+                    best = torch.topk(engine.logits, n_top).indices
+                    rec[made, 1:1 + n_top] = best
+                    rec[made, 1 + n_top:] = lsm[best]
             hist[n + made] = tok[0]
             engine.token.copy_(tok.to(torch.int32))
             engine.pos.fill_(n + made)
@@ -645,7 +733,11 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
             if t in eos:
                 new, done = new[:j + 1], True
                 break
-        yield new
+        if n_top is None:
+            yield new
+            continue
+        rows = rec[made - k:made - k + len(new)].tolist()
+        yield new, [r[0] for r in rows], [[(int(i), lp) for i, lp in zip(r[1:1 + n_top], r[1 + n_top:])] for r in rows]
 
 
 def request_seed():
@@ -654,7 +746,7 @@ def request_seed():
 
 
 def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chunk=2048, do_sample=False,
-                      temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0):
+                      temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, logprobs=None):
     """A sampling / repetition-penalty request: on the native sampler (chained bursts, graph replays) when
     `native_sampler_supports` says so, else `iter_sampled` with a `DeviceSampler`. The sampler is removed after the
     request, so the next greedy request runs the untouched greedy path: in a `finally` of this generator, which runs when
@@ -668,11 +760,12 @@ def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chun
         raise ValueError("`temperature` has to be a strictly positive float when sampling")
     if not engine.native_sampler_supports(**opts):
         yield from iter_sampled(engine, prompt_ids, max_new_tokens, DeviceSampler(**opts), eos=eos, burst=burst,
-                                chunk=chunk)
+                                chunk=chunk, logprobs=logprobs)
         return
     engine.set_sampler(seed=request_seed(), **opts)
     try:
-        yield from engine.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, eos=eos)
+        yield from engine.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, eos=eos,
+                                        logprobs=logprobs)
     finally:
         engine.clear_sampler()
 

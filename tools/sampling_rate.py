@@ -7,6 +7,11 @@ read). Prints medians and min-max as tokens/s and writes them to `--out`.
 
     python tools/sampling_rate.py --out profiles/r07_native_sampler.txt
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/sampling_rate.py --rounds 1 --paths native_default
+
+Paths `greedy_logprobs` and `native_default_logprobs` are the greedy chain and the default chat request with the
+log-probability record on (csrc/woq_logprob.hip, 20 alternatives read back with every burst):
+
+    python tools/sampling_rate.py --paths greedy,greedy_logprobs,native_default,native_default_logprobs
 """
 import argparse
 import os
@@ -46,7 +51,10 @@ def main():
         return lambda: generate_sampled(eng, prompt, a.new, DeviceSampler(**kw))
 
     paths = {"native_default": native(DEFAULT), "torch_default": torch_path(DEFAULT), "native_penalty": native(PENALTY),
-             "torch_penalty": torch_path(PENALTY), "greedy": lambda: eng.generate(prompt, a.new)}
+             "torch_penalty": torch_path(PENALTY), "greedy": lambda: eng.generate(prompt, a.new),
+             "greedy_logprobs": lambda: eng.generate(prompt, a.new, logprobs=20)[0],
+             "native_default_logprobs": lambda: eng.generate(prompt, a.new, sampler=dict(seed=1234, **DEFAULT),
+                                                             logprobs=20)[0]}
     names = [n for n in a.paths.split(",") if n]
     times = {n: [] for n in names}
     for r in range(a.rounds + 1):  # round 0 warms every path up (graph capture, torch's lazy kernels)
