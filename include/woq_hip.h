@@ -202,6 +202,22 @@ WOQ_API int woq_engine_step(woq_engine* e, int greedy, void* stream);
 WOQ_API int woq_engine_prefill(woq_engine* e, const int32_t* tokens_dev, int n_seq, int T, int start_pos, int greedy,
                                void* stream);
 WOQ_API void* woq_engine_prefill_logits_ptr(woq_engine* e);
+/* like woq_engine_prefill with n_seq == 1, and it also writes rows of the three logs of
+ * woq_engine_logprob_ptr: row start_pos + t describes the raw distribution after position start_pos + t,
+ * chosen = log-probability of targets_dev[t] (device int32 [T]: the id at position start_pos + t + 1).
+ * greedy == 0: rows t = 0 .. T-1. greedy != 0: rows t = 0 .. T-2; row T-1 belongs to the chaining tail
+ * exactly as today (its target is the token the tail picks; targets_dev[T-1] is not read).
+ * Chunked scoring = calls with growing start_pos, a non-final chunk with greedy == 0 and the next chunk's first id as
+ * its last target. A row is the record documented at woq_engine_set_logprobs (20 ids, NaN logits weigh 0, -1 / -inf
+ * padding); a target outside [0, vocab) gives chosen = NaN, the row's 20 ids are written all the same. lm_head runs
+ * over all rows on the matrix cores, the final-norm row as a hi + lo pair in lm_head's type, fp32 accumulation
+ * (csrc/woq_score.hip), in blocks of 256 rows: the scratch (256 x vocab x 4 bytes of logits) is allocated on first use.
+ * KV cache, token_ptr, pos_ptr, logits_ptr and prefill_logits_ptr end as after woq_engine_prefill(e, tokens, 1, T,
+ * start_pos, greedy, stream). Fails with a "QBits:" message before the first woq_engine_set_logprobs(e, 1) (the logs
+ * do not exist; recording need not be on), on a tensor-parallel engine, for a vocabulary the record does not cover and
+ * for a hidden size that is no multiple of 8. */
+WOQ_API int woq_engine_prefill_scored(woq_engine* e, const int32_t* tokens_dev, int T, int start_pos,
+                                      const int32_t* targets_dev, int greedy, void* stream);
 /* decode attention regime: 1 = one workgroup per head (fastest up to a few hundred cached positions), n > 1 = n
  * context slices per head + a combine launch (long contexts). Takes effect at the next step / capture; a graph
  * captured earlier keeps the regime it was captured with. */

@@ -85,6 +85,16 @@ WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, con
  * top_id_out20 / top_lp_out20 = device int32 / fp32 [20]. Scratch is allocated and freed on `stream`. */
 WOQ_API int woq_probe_logprobs(const float* logits, int vocab, const int32_t* token_dev, float* chosen_out,
                                int32_t* top_id_out20, float* top_lp_out20, void* stream);
+/* the scored head alone (tests/test_gpu_score_kernel.py), forwarding to the engine's own launcher unchanged (csrc/
+ * woq_score.hip): hidden_rows fp32 [M][hidden], norm_w fp32 [hidden], W = dense lm_head [vocab][hidden] in w_dtype
+ * (WOQ_F16 | WOQ_BF16), targets = device int32 [M]; row r's record goes to chosen_out[r], top_id_out[r][0..20),
+ * top_lp_out[r][0..20). Scratch is allocated and freed on `stream`. */
+WOQ_API int woq_probe_score_rows(const float* hidden_rows, const float* norm_w, float eps, const void* W, int w_dtype,
+                                 int hidden, int vocab, const int32_t* targets, int M, float* chosen_out,
+                                 int32_t* top_id_out, float* top_lp_out, void* stream);
+/* fp32 [rows][hidden]: the residual stream the last prompt pass left (before the final norm), valid until the next
+ * prompt pass; NULL before the first one. For tests. */
+WOQ_API void* woq_engine_prefill_rows_ptr(woq_engine* e);
 
 #ifdef __cplusplus
 }

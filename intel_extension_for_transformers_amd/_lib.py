@@ -85,14 +85,14 @@ EXPORTS = [
     "woq_comm_status", "woq_comm_set_timeout_ms", "woq_comm_destroy", "woq_engine_set_comm", "woq_set_workspace",
     "woq_engine_uses_xq", "woq_engine_token_log_ptr", "woq_table_digit_planes",
     "woq_engine_set_sampler", "woq_engine_sampler_seen", "woq_engine_sampler_seen_ptr",
-    "woq_engine_set_logprobs", "woq_engine_logprobs", "woq_engine_logprob_ptr",
+    "woq_engine_set_logprobs", "woq_engine_logprobs", "woq_engine_logprob_ptr", "woq_engine_prefill_scored",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
     "woq_engine_set_attn_chunk", "woq_engine_attn_chunk", "woq_engine_time_gemv", "woq_engine_time_gemv_mask",
     "woq_engine_time_twin", "woq_engine_set_time_eager", "woq_engine_time_prefill_gemm", "woq_gemm_form_log",
     "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
-    "woq_probe_logprobs",
+    "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -192,6 +192,10 @@ def lib():
     L.woq_engine_logprob_ptr.restype = vp
     L.woq_engine_logprob_ptr.argtypes = [vp, ci]
     L.woq_probe_logprobs.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.woq_engine_prefill_scored.argtypes = [vp, vp, ci, ci, vp, ci, vp]
+    L.woq_probe_score_rows.argtypes = [vp, vp, cf, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp]
+    L.woq_engine_prefill_rows_ptr.restype = vp
+    L.woq_engine_prefill_rows_ptr.argtypes = [vp]
     _lib = L
     return L
 
@@ -261,6 +265,17 @@ def probe_logprobs(logits, token, chosen_out, top_id_out, top_lp_out):
     """the log-probability record alone (woq_probe_logprobs): device tensors, the current stream."""
     rc = lib().woq_probe_logprobs(_ptr(logits), int(logits.numel()), _ptr(token), _ptr(chosen_out), _ptr(top_id_out),
                                   _ptr(top_lp_out), stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def probe_score_rows(hidden_rows, norm_w, eps, W, targets, chosen_out, top_id_out, top_lp_out):
+    """the scored head alone (woq_probe_score_rows): hidden_rows fp32 [M, hidden], W fp16 / bf16 [vocab, hidden], targets
+    int32 [M]; device tensors, the current stream."""
+    M, hidden = hidden_rows.shape
+    rc = lib().woq_probe_score_rows(_ptr(hidden_rows), _ptr(norm_w), float(eps), _ptr(W), torch_dtype_code(W.dtype),
+                                    int(hidden), int(W.shape[0]), _ptr(targets), int(M), _ptr(chosen_out),
+                                    _ptr(top_id_out), _ptr(top_lp_out), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
 

@@ -144,6 +144,9 @@ struct woq_engine {
   int32_t* lp_top_id = nullptr; // [max_ctx + 1][20]
   float* lp_top_lp = nullptr;   // [max_ctx + 1][20]
   void* lp_ws = nullptr;        // the slices' partial results
+  // scored prompt pass (woq_score.hip): hi + lo rows, the logits of one block of 256 rows and their partials;
+  // allocated by the first woq_engine_prefill_scored and held, like pf_ws
+  void* score_ws = nullptr;
 };
 
 using namespace woq;
@@ -524,7 +527,33 @@ int woq_engine_prefill(woq_engine* e, const int32_t* tokens_dev, int n_seq, int 
   WOQ_END
 }
 
+int woq_engine_prefill_scored(woq_engine* e, const int32_t* tokens_dev, int T, int start_pos,
+                              const int32_t* targets_dev, int greedy, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e && e->embed && e->lm_head, "QBits: engine head not set");
+  WOQ_CHECK(tokens_dev && targets_dev && T >= 1 && start_pos >= 0, "QBits: bad prefill arguments");
+  WOQ_CHECK(start_pos + T <= e->cfg.max_ctx, "QBits: prefill runs past max_ctx");
+  WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+            "QBits: a tensor-parallel engine cannot score a prompt (its lm_head is vocab-sharded)");
+  WOQ_CHECK(e->lp_chosen != nullptr, "QBits: no log-probability log before the first woq_engine_set_logprobs(e, 1)");
+  const woq_engine_config& c = e->cfg;
+  if (const char* why = score_shape_problem(e->lm_head, e->lm_dtype, c.hidden, c.vocab)) return woq::fail(why);
+  const hipStream_t st = (hipStream_t)stream;
+  if (e->score_ws == nullptr) WOQ_HIP(hipMalloc(&e->score_ws, score_workspace_bytes(c.hidden, c.vocab)));
+  int rc = engine_prefill_impl(e, tokens_dev, 1, T, start_pos, greedy, st);
+  if (rc) return rc;
+  const int rows = greedy ? T - 1 : T;  // greedy: row start_pos + T - 1 is the chaining tail's
+  if (rows > 0) {
+    rc = launch_score_rows(e->pf_h, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, targets_dev,
+                           rows, start_pos, c.max_ctx + 1, e->score_ws, e->lp_chosen, e->lp_top_id, e->lp_top_lp, st);
+    if (rc) return rc;
+  }
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
 void* woq_engine_prefill_logits_ptr(woq_engine* e) { return e ? e->pf_logits : nullptr; }
+void* woq_engine_prefill_rows_ptr(woq_engine* e) { return e ? e->pf_h : nullptr; }
 int woq_engine_set_attn_splits(woq_engine* e, int splits) {
   WOQ_TRY
   WOQ_CHECK(e && splits >= 1 && splits <= 64, "QBits: attn_splits must be in [1, 64]");
@@ -699,6 +728,7 @@ void woq_engine_destroy(woq_engine* e) {
   for (void* p : e->owned) hipFree(p);
   for (void* p : {(void*)e->pf_h, (void*)e->pf_qkv, (void*)e->pf_attn, (void*)e->pf_act, e->pf_ws})
     if (p) hipFree(p);
+  if (e->score_ws) hipFree(e->score_ws);
   delete e;
 }
 

@@ -144,6 +144,25 @@ bool logprob_vocab_ok(int vocab);  // 1 .. 409 slices: what the merging workgrou
 size_t logprob_workspace_bytes(int vocab);
 int launch_logprobs(const float* logits, int vocab, const int32_t* token, const int32_t* pos, int max_rows, void* ws,
                     float* chosen, int32_t* top_id, float* top_lp, hipStream_t st);
+// The same two launches with a row dimension (the scored prompt pass): logits row r at logits + r * row_stride, its picked
+// id targets[r], its record in log row row0 + r (rows outside [0, max_rows) write nothing). A target outside [0, vocab)
+// gives chosen = NaN, the top 20 are written all the same. ws = rows * logprob_workspace_bytes(vocab); rows <= 65535.
+int launch_logprob_rows(const float* logits, size_t row_stride, int vocab, int rows, const int32_t* targets, int row0,
+                        int max_rows, void* ws, float* chosen, int32_t* top_id, float* top_lp, hipStream_t st);
+
+// ---- woq_score.hip: log-probabilities of a supplied token sequence over the prompt pass's rows ---------------------
+constexpr int SCORE_BLOCK_ROWS = 256;  // rows whose logits the scratch holds at once
+// null when the scored head takes this shape, else the "QBits: ..." reason
+const char* score_shape_problem(const void* W, int w_dtype, int hidden, int vocab);
+// scratch of launch_score_rows: the hi + lo activation rows, the logits of one block of 256 rows (256 x vocab x 4
+// bytes) and the record's partials for those rows
+size_t score_workspace_bytes(int hidden, int vocab);
+// rows r = 0 .. M-1 of fp32 `hidden_rows` [M][hidden]: final RMSNorm (norm_w, eps), logits over the dense fp16 / bf16
+// W [vocab][hidden] on the matrix cores (activation as hi + lo in W's type, fp32 accumulation), then the record of
+// launch_logprob_rows with targets[r] into log row row0 + r. In blocks of SCORE_BLOCK_ROWS rows: 4 launches a block.
+int launch_score_rows(const float* hidden_rows, const float* norm_w, float eps, const void* W, int w_dtype, int hidden,
+                      int vocab, const int32_t* targets, int M, int row0, int max_rows, void* ws, float* chosen,
+                      int32_t* top_id, float* top_lp, hipStream_t st);
 
 // ---- woq_prefill.hip: prompt-pass launches and the grouped decode attention ---------------------------------------
 void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int M, int hidden, float* out,

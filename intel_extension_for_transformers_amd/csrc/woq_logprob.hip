@@ -8,6 +8,8 @@
 //      Z = sum over slices of sum_i * expf(max_i - M), logZ = M + logf(Z), then the record of row p = pos[0] - 1:
 //      chosen[p] = logits[token[0]] - logZ, top_id[p][r], top_lp[p][r] = score_r - logZ.
 // The kernel boundary is the hand-off between the two: no flags, counters or fences, nothing to reset between launches.
+// Both kernels carry a row dimension (launch_logprob_rows: the scored prompt pass, woq_score.hip, records one row per
+// prompt position from a [rows][vocab] logits scratch); the decode step's form is the same code with one row.
 //
 // Order. Pairs compare as (score descending, id ascending) under one unsigned 64-bit maximum; they are distinct, so
 // round r of a selection is the largest pair below round r - 1's winner and nothing is ever removed. 0 stands for "no
@@ -73,8 +75,9 @@ __device__ __forceinline__ float block_sum_ordered(float v, float* wsum, int tid
   return z;
 }
 
-__global__ __launch_bounds__(LP_THREADS) void logprob_partial_kernel(const float* __restrict__ logits, int vocab,
-                                                                     uint32_t* __restrict__ part_key,
+// blockIdx.y = row: logits row `row` starts at logits + row * row_stride, its partials at index row * gridDim.x + slice
+__global__ __launch_bounds__(LP_THREADS) void logprob_partial_kernel(const float* __restrict__ logits, size_t row_stride,
+                                                                     int vocab, uint32_t* __restrict__ part_key,
                                                                      float* __restrict__ part_sum,
                                                                      unsigned long long* __restrict__ part_top) {
   constexpr int WAVES = LP_THREADS / 64;
@@ -83,6 +86,9 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_partial_kernel(const float
   __shared__ float wsum[WAVES];
   const int tid = threadIdx.x, slice = blockIdx.x;
   const int base = slice * LP_SLICE;
+  const size_t prow = (size_t)blockIdx.y * gridDim.x;
+  logits += (size_t)blockIdx.y * row_stride;
+  part_key += prow, part_sum += prow, part_top += prow * LP_TOP;
   float s[LP_PER];
   unsigned long long c[LP_PER];
 #pragma unroll
@@ -121,17 +127,20 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_partial_kernel(const float
   if (tid < LP_TOP) part_top[(size_t)slice * LP_TOP + tid] = tops[tid];
 }
 
-// max_rows: rows of the three logs; pos == nullptr: row 0 (the probe)
+// max_rows: rows of the three logs. blockIdx.x = row: its logits, partials and token[row]. pos != nullptr (the decode
+// step, one row): log row pos[0] - 1; pos == nullptr: log row row0 + row (the probe, the scored prompt pass)
 __global__ __launch_bounds__(LP_MERGE_THREADS) void logprob_merge_kernel(
-    const float* __restrict__ logits, int vocab, int n_slices, const uint32_t* __restrict__ part_key,
+    const float* __restrict__ logits, size_t row_stride, int vocab, int n_slices, const uint32_t* __restrict__ part_key,
     const float* __restrict__ part_sum, const unsigned long long* __restrict__ part_top,
-    const int32_t* __restrict__ token, const int32_t* __restrict__ pos, int max_rows, float* __restrict__ chosen,
-    int32_t* __restrict__ top_id, float* __restrict__ top_lp) {
+    const int32_t* __restrict__ token, const int32_t* __restrict__ pos, int row0, int max_rows,
+    float* __restrict__ chosen, int32_t* __restrict__ top_id, float* __restrict__ top_lp) {
   constexpr int WAVES = LP_MERGE_THREADS / 64;
   __shared__ unsigned long long red[2 * WAVES];
   __shared__ unsigned long long tops[LP_TOP];
   __shared__ float wsum[WAVES];
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x, row = blockIdx.x;
+  logits += (size_t)row * row_stride;
+  part_key += (size_t)row * n_slices, part_sum += (size_t)row * n_slices, part_top += (size_t)row * n_slices * LP_TOP;
   const int n_cand = n_slices * LP_TOP;
   unsigned long long c[LP_MERGE_PER];
 #pragma unroll
@@ -161,7 +170,7 @@ __global__ __launch_bounds__(LP_MERGE_THREADS) void logprob_merge_kernel(
   }
   const float Z = block_sum_ordered<WAVES>(acc, wsum, tid);  // (its barrier also publishes `tops`)
   if (tid >= LP_TOP) return;
-  const int p = pos != nullptr ? pos[0] - 1 : 0;
+  const int p = pos != nullptr ? pos[0] - 1 : row0 + row;
   if (p < 0 || p >= max_rows) return;  // a position the logs have no row for: nothing is written
   const float logZ = M + logf(Z);
   const bool none = m_key == 0u;  // every logit NaN
@@ -169,7 +178,7 @@ __global__ __launch_bounds__(LP_MERGE_THREADS) void logprob_merge_kernel(
   top_id[(size_t)p * LP_TOP + tid] = t != 0ull ? (int32_t)(~(uint32_t)t) : -1;
   top_lp[(size_t)p * LP_TOP + tid] = t != 0ull ? key_score((uint32_t)(t >> 32)) - logZ : -INFINITY;
   if (tid == 0) {
-    const int tok = token[0];
+    const int tok = token[row];
     chosen[p] = (none || tok < 0 || tok >= vocab) ? __uint_as_float(0x7FC00000u) : logits[tok] - logZ;
   }
 }
@@ -183,18 +192,33 @@ size_t logprob_workspace_bytes(int vocab) {
   return n * (LP_TOP * 8 + 4 + 4);
 }
 
-int launch_logprobs(const float* logits, int vocab, const int32_t* token, const int32_t* pos, int max_rows, void* ws,
-                    float* chosen, int32_t* top_id, float* top_lp, hipStream_t st) {
+// the two launches over `rows` logits rows; ws = rows * logprob_workspace_bytes(vocab)
+static int launch_logprobs_impl(const float* logits, size_t row_stride, int vocab, int rows, const int32_t* token,
+                                const int32_t* pos, int row0, int max_rows, void* ws, float* chosen, int32_t* top_id,
+                                float* top_lp, hipStream_t st) {
   const int n_slices = (vocab + LP_SLICE - 1) / LP_SLICE;
   if (!logprob_vocab_ok(vocab)) return woq::fail("QBits: the log-probability record covers vocabularies of up to 418816 ids");
-  unsigned long long* part_top = (unsigned long long*)ws;  // [n_slices][20], then the slice sums, then their max keys
-  float* part_sum = (float*)(part_top + (size_t)n_slices * LP_TOP);
-  uint32_t* part_key = (uint32_t*)(part_sum + n_slices);
-  hipLaunchKernelGGL(logprob_partial_kernel, dim3(n_slices), dim3(LP_THREADS), 0, st, logits, vocab, part_key, part_sum,
-                     part_top);
-  hipLaunchKernelGGL(logprob_merge_kernel, dim3(1), dim3(LP_MERGE_THREADS), 0, st, logits, vocab, n_slices, part_key,
-                     part_sum, part_top, token, pos, max_rows, chosen, top_id, top_lp);
+  const size_t n = (size_t)rows * n_slices;
+  unsigned long long* part_top = (unsigned long long*)ws;  // [rows][n_slices][20], then the slice sums, then their max keys
+  float* part_sum = (float*)(part_top + n * LP_TOP);
+  uint32_t* part_key = (uint32_t*)(part_sum + n);
+  hipLaunchKernelGGL(logprob_partial_kernel, dim3(n_slices, rows), dim3(LP_THREADS), 0, st, logits, row_stride, vocab,
+                     part_key, part_sum, part_top);
+  hipLaunchKernelGGL(logprob_merge_kernel, dim3(rows), dim3(LP_MERGE_THREADS), 0, st, logits, row_stride, vocab, n_slices,
+                     part_key, part_sum, part_top, token, pos, row0, max_rows, chosen, top_id, top_lp);
   return 0;
+}
+
+int launch_logprobs(const float* logits, int vocab, const int32_t* token, const int32_t* pos, int max_rows, void* ws,
+                    float* chosen, int32_t* top_id, float* top_lp, hipStream_t st) {
+  return launch_logprobs_impl(logits, 0, vocab, 1, token, pos, 0, max_rows, ws, chosen, top_id, top_lp, st);
+}
+
+int launch_logprob_rows(const float* logits, size_t row_stride, int vocab, int rows, const int32_t* targets, int row0,
+                        int max_rows, void* ws, float* chosen, int32_t* top_id, float* top_lp, hipStream_t st) {
+  if (rows < 1 || rows > 65535) return woq::fail("QBits: the row form of the log-probability record takes 1..65535 rows");
+  return launch_logprobs_impl(logits, row_stride, vocab, rows, targets, nullptr, row0, max_rows, ws, chosen, top_id, top_lp,
+                              st);
 }
 
 }  // namespace woq

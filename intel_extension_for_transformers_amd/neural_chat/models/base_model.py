@@ -101,6 +101,24 @@ class BaseModel:
         finally:
             config.return_stats = stats
 
+    def score_prompt(self, prompt, n_top=0):
+        """Log-probabilities the model assigns to the tokens of `prompt` itself (tokenised as `predict` tokenises a plain
+        completion): one entry per prompt token in the shape of `last_logprobs` entries (`token_id`, `token`, `logprob`,
+        `top` = `n_top` alternatives as (id, string, logprob), `text_offset`). The first token has nothing in front of
+        it: `logprob` None, `top` empty. One scored prompt pass on the fused engine (`WoqDecoderEngine.score`)."""
+        if self.engine is None:
+            raise RuntimeError("QBits: scoring a prompt needs the fused engine")
+        tok = self.tokenizer
+        ids = [int(t) for t in tok(prompt, return_tensors="pt").input_ids[0].tolist()]
+        lps, tops = self.engine.score(ids, logprobs=int(n_top)) if len(ids) > 1 else ([], [])
+        entries = []
+        for i, t in enumerate(ids):
+            top = [] if i == 0 else [(int(j), tok.decode([int(j)]), float(v)) for j, v in tops[i - 1] if j >= 0]
+            entries.append({"token_id": t, "token": tok.decode([t]), "logprob": None if i == 0 else float(lps[i - 1]),
+                            "top": top,
+                            "text_offset": len(tok.decode(ids[:i], skip_special_tokens=True)) if i else 0})
+        return entries
+
     # ---- generation ----------------------------------------------------------------------------------------------
     def _stream(self, prompt, config):
         ids = self.tokenizer(prompt, return_tensors="pt").input_ids

@@ -60,6 +60,7 @@ class CompletionRequest(_Wire):
     frequency_penalty: Optional[float] = 0.0
     user: Optional[str] = None
     logprobs: Optional[int] = None
+    prompt_logprobs: Optional[int] = None  # 0..20: score the PROMPT's tokens (choices[i].prompt_logprobs)
 
 
 def _error(status, message):
@@ -111,6 +112,14 @@ def _check_logprobs(req):
         return "%s is outside [0, 5] - 'logprobs'" % req.logprobs
     if _wanted_logprobs(req) is not None and req.stream:
         return "QBits: logprobs are not available on streamed responses"
+    n_prompt = getattr(req, "prompt_logprobs", None)  # the completions route only
+    if n_prompt is not None:
+        if not 0 <= n_prompt <= 20:
+            return "%s is outside [0, 20] - 'prompt_logprobs'" % n_prompt
+        if req.stream:
+            return "QBits: prompt_logprobs are not available on streamed responses"
+        if not hasattr(router.get_chatbot(), "score_prompt"):
+            return "QBits: this model cannot score a prompt - 'prompt_logprobs'"
     return None
 
 
@@ -130,6 +139,15 @@ def _completion_logprobs(entries, n_top, shift=0):
     return {"tokens": [e["token"] for e in entries], "token_logprobs": [e["logprob"] for e in entries],
             "top_logprobs": [{s: lp for _i, s, lp in e["top"][:n_top]} for e in entries],
             "text_offset": [e["text_offset"] + shift for e in entries]}
+
+
+def _prompt_logprobs(entries, n_top):
+    """`choices[i].prompt_logprobs`: the legacy completions object over the PROMPT's tokens (BaseModel.score_prompt
+    entries); the first token has nothing in front of it, so its `token_logprobs` / `top_logprobs` are null."""
+    return {"tokens": [e["token"] for e in entries], "token_logprobs": [e["logprob"] for e in entries],
+            "top_logprobs": [None if e["logprob"] is None else {s: lp for _i, s, lp in e["top"][:n_top]}
+                             for e in entries],
+            "text_offset": [e["text_offset"] for e in entries]}
 
 
 class TextChatAPIRouter(APIRouter):
@@ -212,6 +230,11 @@ class TextChatAPIRouter(APIRouter):
                 entries = [e for e in entries if e["text_offset"] < cut]
             return text[:cut], "stop", entries
         return text, ("length" if self._count(text) >= config.max_new_tokens else "stop"), entries
+
+    def _score_prompt(self, prompt, n_top):
+        """BaseModel.score_prompt under the engine lock."""
+        with self._gpu:
+            return self.get_chatbot().score_prompt(prompt, n_top)
 
     def _stream(self, prompt, config, stops):
         """Text pieces until a stop string shows up (the piece is cut there). The generation itself runs in a worker
@@ -389,11 +412,17 @@ async def create_completion(request: CompletionRequest):
     choices, n_in, n_out = [], 0, 0
     try:
         for p in prompts:
+            scored = None  # once per prompt, shared by its n choices
+            if request.prompt_logprobs is not None:
+                scored = _prompt_logprobs(await run_in_threadpool(router._score_prompt, p, request.prompt_logprobs),
+                                          request.prompt_logprobs)
             for _ in range(request.n or 1):
                 text, why, entries = await run_in_threadpool(router._generate_logprobs, p, config, stops)
                 lps = None if entries is None else _completion_logprobs(entries, n_top, len(p) if request.echo else 0)
                 choices.append({"index": len(choices), "text": (p + text) if request.echo else text, "logprobs": lps,
                                 "finish_reason": why})
+                if scored is not None:
+                    choices[-1]["prompt_logprobs"] = scored
                 n_in += router._count(p)
                 n_out += router._count(text)
     except Exception as e:

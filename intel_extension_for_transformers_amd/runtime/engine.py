@@ -495,6 +495,53 @@ class WoqDecoderEngine:
                 _device_view(get(self._h, 1), (rows, self.LOGPROB_TOP), self.device, "<i4"),
                 _device_view(get(self._h, 2), (rows, self.LOGPROB_TOP), self.device))
 
+    # ---- scoring a given text: csrc/woq_score.hip over the prompt pass's rows ----------------------------------------
+    def prefill_scored(self, tokens, targets, start_pos=0, greedy=False):
+        """`prefill` of one sequence that also writes rows start_pos .. of `logprob_log()`: row start_pos + t holds the
+        raw distribution after position start_pos + t, `chosen` = the log-probability of targets[t] (the id at position
+        start_pos + t + 1; an id outside the vocabulary gives NaN). greedy=True leaves the last row to the chaining tail.
+        Needs the logs (a `set_logprobs(True)` at some earlier point); recording need not be on."""
+        t = torch.as_tensor(tokens, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        g = torch.as_tensor(targets, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        if g.numel() != t.numel():
+            raise RuntimeError("QBits: prefill_scored takes one target per token")
+        L.check(L.lib().woq_engine_prefill_scored(self._h, t.data_ptr(), int(t.numel()), int(start_pos), g.data_ptr(),
+                                                  int(greedy), L.stream_ptr()))
+        ptr = L.lib().woq_engine_prefill_logits_ptr(self._h)
+        return _device_view(ptr, (1, self.cfg.vocab), self.device)
+
+    def prefill_rows(self, rows):
+        """fp32 view [rows, hidden] of the residual stream the last prompt pass left (before the final norm); for tests."""
+        return _device_view(L.lib().woq_engine_prefill_rows_ptr(self._h), (int(rows), self.cfg.hidden), self.device)
+
+    def score(self, ids, chunk=2048, logprobs=0):
+        """Log-probabilities the model assigns to a given text -> `(token_lps, top)`: token_lps[i] = log P(ids[i + 1] |
+        ids[:i + 1]) (len(ids) - 1 floats), top[i] = `logprobs` (0..20) pairs `(id, log-probability)` of the most likely
+        ids at that position. The text runs through `prefill_scored` in chunks of `chunk` tokens; one device-to-host
+        copy at the end. Leaves `logprobs_on` and an installed sampler as they were."""
+        ids = [int(t) for t in ids]
+        n, n_top = len(ids), int(logprobs)
+        if not 0 <= n_top <= self.LOGPROB_TOP:
+            raise ValueError("`logprobs` is a count of alternatives in [0, %d]" % self.LOGPROB_TOP)
+        if n < 2:
+            raise RuntimeError("QBits: scoring needs at least 2 tokens (got %d)" % n)
+        if n > self.cfg.max_ctx:
+            raise RuntimeError("QBits: text (%d tokens) exceeds the engine's max_ctx (%d)" % (n, self.cfg.max_ctx))
+        if not L.lib().woq_engine_logprob_ptr(self._h, 0):  # allocate the logs, leave recording as it was
+            before = self.logprobs_on
+            self.set_logprobs(True)
+            self.set_logprobs(before)
+        targets = ids[1:] + [-1]  # the last position has no next token: its row is dropped
+        for s0 in range(0, n, int(chunk)):
+            self.prefill_scored(ids[s0:s0 + chunk], targets[s0:s0 + chunk], start_pos=s0, greedy=False)
+        _, lps, top = self._records(0, n - 1, n_top)
+        return lps, top
+
+    def perplexity(self, ids, chunk=2048):
+        """exp(-mean(log P(ids[i + 1] | ids[:i + 1]))) of a text, the mean taken on the host in float64."""
+        lps, _ = self.score(ids, chunk=chunk)
+        return math.exp(-math.fsum(lps) / len(lps))
+
     def iter_generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=(), logprobs=None):
         """Prompt pass + bursts of `burst` chained steps, yielding each burst's new tokens (the first one alone: it comes
         from the prompt pass's tail). With a sampler installed the prompt is marked in the history first and every
