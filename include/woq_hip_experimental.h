@@ -92,6 +92,42 @@ WOQ_API int woq_probe_logprobs(const float* logits, int vocab, const int32_t* to
 WOQ_API int woq_probe_score_rows(const float* hidden_rows, const float* norm_w, float eps, const void* W, int w_dtype,
                                  int hidden, int vocab, const int32_t* targets, int M, float* chosen_out,
                                  int32_t* top_id_out, float* top_lp_out, void* stream);
+/* The XQ decode GEMV and the greedy token tail alone (tests/test_gpu_xq_gemv_kernel.py, tests/test_gpu_token_tail_kernel.py),
+ * each forwarding to the engine's own launcher unchanged. An XQ vector of K values (csrc/woq_xq.h) is three device
+ * buffers: limbs (((K / 16 * 48 + 1023) / 1024 + 1) * 1024 bytes, [K / 16][3][16] int8 used), u and sx fp32 [K / 16].
+ * xq_from_f32: x fp32 [K] (times norm_w when given), K % 16 == 0; ssq_out (nullable) fp32 [K / 16] = the blocks' sums
+ * of squares of x. */
+WOQ_API int woq_probe_xq_from_f32(const float* x, const float* norm_w, int K, void* limbs_out, float* u_out,
+                                  float* sx_out, float* ssq_out, void* stream);
+/* one batch-1 projection: x fp32 [K] is converted (times in_norm_w when given) to an XQ vector in scratch allocated and
+ * freed on `stream`, then the GEMV runs over `blob` (device memory; its header is read back, which synchronises the
+ * stream): out fp32 [N] (epi 1, a fuse_gate_up blob: SiLU(gate) * up, [N / 2]) = x . W (* rsqrt(mean(x^2) + eps) exactly
+ * when in_norm_w is given) (+ bias [N]) (+ residual); xo_* (nullable together) = the result times next_norm_w (nullable)
+ * as an XQ vector of Npad (epi 1: Npad / 2) values, ssq_out (nullable) its blocks' sums of squares. out may be null when
+ * xo is given. Returns the library's error when the GEMV refuses the call. */
+WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
+                              const float* bias, const float* residual, const float* next_norm_w, float* out,
+                              void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream);
+/* lm_head_kernel: hidden_in / norm_w fp32 [hidden] (hidden % 8 == 0), W dense [vocab][hidden] in w_dtype (WOQ_F16 |
+ * WOQ_BF16), logits fp32 [vocab]; pmax / pidx (nullable together) fp32 / int32 [(vocab + 15) / 16]: each 16-row
+ * workgroup's (max logit, lowest index of it). */
+WOQ_API int woq_probe_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype,
+                              int hidden, int vocab, float* logits, float* pmax, int32_t* pidx, void* stream);
+/* the greedy tails: mode 0 = argmax over logits [vocab] (the prompt pass's), mode 1 = argmax over the lm_head's
+ * (vocab + 15) / 16 pairs (the eager step's), mode 2 = the same fused with the next step's embedding (chained steps).
+ * All write token[0], pos[0] += 1; modes 1 and 2 also log[old pos] = token (log nullable) and status |= 4 when no pair
+ * won (token 0). Modes 0 and 1 read none of the arguments from `embed` on. Mode 2: embed [rows][hidden] in embed_dtype,
+ * out fp32 [hidden] = the token's row; with norm_w the row times norm_w also leaves as the XQ vector xo_* with ssq_out;
+ * step_seq (nullable) += 1; a position that reaches max_ctx is clamped to max_ctx - 1 and status |= 2. */
+WOQ_API int woq_probe_greedy_tail(int mode, const float* logits, int vocab, const float* pmax, const int32_t* pidx,
+                                  int32_t* token, int32_t* pos, int32_t* log, const void* embed, int embed_dtype,
+                                  int hidden, float* out, const float* norm_w, void* xo_limbs, float* xo_u, float* xo_sx,
+                                  float* ssq_out, unsigned int* step_seq, int max_ctx, int* status, void* stream);
+/* embed_kernel, the head of a decode step: the same outputs as mode 2 for the row of token[0]; pos (nullable) is only
+ * guarded (pos >= max_ctx: clamped, status |= 2), step_seq (nullable) += 1. */
+WOQ_API int woq_probe_embed(const void* embed, int embed_dtype, const int32_t* token, int hidden, float* out,
+                            const float* norm_w, void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out,
+                            unsigned int* step_seq, int32_t* pos, int max_ctx, int* status, void* stream);
 /* fp32 [rows][hidden]: the residual stream the last prompt pass left (before the final norm), valid until the next
  * prompt pass; NULL before the first one. For tests. */
 WOQ_API void* woq_engine_prefill_rows_ptr(woq_engine* e);

@@ -93,6 +93,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_engine_time_twin", "woq_engine_set_time_eager", "woq_engine_time_prefill_gemm", "woq_gemm_form_log",
     "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
+    "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -196,6 +197,11 @@ def lib():
     L.woq_probe_score_rows.argtypes = [vp, vp, cf, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp]
     L.woq_engine_prefill_rows_ptr.restype = vp
     L.woq_engine_prefill_rows_ptr.argtypes = [vp]
+    L.woq_probe_xq_from_f32.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
+    L.woq_probe_gemv_xq.argtypes = [vp, vp, cf, vp, ci] + [vp] * 9
+    L.woq_probe_lm_head.argtypes = [vp, vp, cf, vp, ci, ci, ci, vp, vp, vp, vp]
+    L.woq_probe_greedy_tail.argtypes = [ci, vp, ci] + [vp] * 6 + [ci, ci] + [vp] * 7 + [ci, vp, vp]
+    L.woq_probe_embed.argtypes = [vp, ci, vp, ci] + [vp] * 8 + [ci, vp, vp]
     _lib = L
     return L
 
@@ -278,6 +284,57 @@ def probe_score_rows(hidden_rows, norm_w, eps, W, targets, chosen_out, top_id_ou
                                     _ptr(top_id_out), _ptr(top_lp_out), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
+
+
+def xq_limb_bytes(K):
+    """bytes of the limb buffer of an XQ vector of K values (csrc/woq_xq.h xq_limb_bytes)"""
+    return ((K // 16 * 48 + 1023) // 1024) * 1024 + 1024
+
+
+def _opt(t):
+    return _ptr(t) if t is not None else None
+
+
+def _xq_ptrs(xo):
+    """xo = (limbs, u, sx) device tensors, or None"""
+    return (None, None, None) if xo is None else tuple(_ptr(t) for t in xo)
+
+
+def probe_xq_from_f32(x, norm_w, limbs_out, u_out, sx_out, ssq_out=None):
+    """the fp32 -> XQ conversion alone (woq_probe_xq_from_f32): device tensors, the current stream."""
+    check(lib().woq_probe_xq_from_f32(_ptr(x), _opt(norm_w), int(x.numel()), _ptr(limbs_out), _ptr(u_out), _ptr(sx_out),
+                                      _opt(ssq_out), stream_ptr()))
+
+
+def probe_gemv_xq(x, blob, epi=0, in_norm_w=None, eps=0.0, bias=None, residual=None, next_norm_w=None, out=None, xo=None,
+                  ssq_out=None):
+    """one batch-1 projection of the XQ GEMV (woq_probe_gemv_xq): x fp32 [K], blob a packed weight on the device,
+    xo = (limbs, u, sx) or None."""
+    check(lib().woq_probe_gemv_xq(_ptr(x), _opt(in_norm_w), float(eps), _ptr(blob), int(epi), _opt(bias), _opt(residual),
+                                  _opt(next_norm_w), _opt(out), *_xq_ptrs(xo), _opt(ssq_out), stream_ptr()))
+
+
+def probe_lm_head(hidden_in, norm_w, eps, W, logits, pmax=None, pidx=None):
+    """lm_head_kernel alone (woq_probe_lm_head): W fp16 / bf16 [vocab, hidden]."""
+    check(lib().woq_probe_lm_head(_ptr(hidden_in), _ptr(norm_w), float(eps), _ptr(W), torch_dtype_code(W.dtype),
+                                  int(W.shape[1]), int(W.shape[0]), _ptr(logits), _opt(pmax), _opt(pidx), stream_ptr()))
+
+
+def probe_greedy_tail(mode, vocab, token, pos, logits=None, pmax=None, pidx=None, log=None, embed=None, out=None,
+                      norm_w=None, xo=None, ssq_out=None, step_seq=None, max_ctx=0, status=None):
+    """one greedy tail (woq_probe_greedy_tail): mode 0 argmax over logits, 1 argmax over the lm_head's pairs, 2 the same
+    fused with the next step's embedding (embed [rows, hidden] fp16 / bf16 / fp32)."""
+    dt, hidden = (torch_dtype_code(embed.dtype), int(embed.shape[1])) if embed is not None else (0, 0)
+    check(lib().woq_probe_greedy_tail(int(mode), _opt(logits), int(vocab), _opt(pmax), _opt(pidx), _ptr(token), _ptr(pos),
+                                      _opt(log), _opt(embed), dt, hidden, _opt(out), _opt(norm_w), *_xq_ptrs(xo),
+                                      _opt(ssq_out), _opt(step_seq), int(max_ctx), _opt(status), stream_ptr()))
+
+
+def probe_embed(embed, token, out, norm_w=None, xo=None, ssq_out=None, step_seq=None, pos=None, max_ctx=0, status=None):
+    """embed_kernel alone (woq_probe_embed)."""
+    check(lib().woq_probe_embed(_ptr(embed), torch_dtype_code(embed.dtype), _ptr(token), int(embed.shape[1]), _ptr(out),
+                                _opt(norm_w), *_xq_ptrs(xo), _opt(ssq_out), _opt(step_seq), _opt(pos), int(max_ctx),
+                                _opt(status), stream_ptr()))
 
 
 def check(rc):

@@ -299,7 +299,7 @@ static int engine_head(woq_engine* e, int greedy, hipStream_t st, bool fuse_next
     return woq_comm_launch_greedy(e->comm, e->am_val, e->am_idx, (c.vocab + 15) / 16, e->vocab_offset, e->token,
                                   e->pos, e->tok_log, st);
   if (!greedy) return 0;
-  launch_argmax_pairs(e->am_val, e->am_idx, (c.vocab + 15) / 16, e->token, e->pos, e->tok_log, st);
+  launch_argmax_pairs(e->am_val, e->am_idx, (c.vocab + 15) / 16, e->token, e->pos, e->tok_log, e->fuse_status, st);
   return engine_logprobs(e, st);
 }
 

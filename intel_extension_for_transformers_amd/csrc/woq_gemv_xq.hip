@@ -11,6 +11,7 @@ __device__ unsigned long long* g_xqs_probe = nullptr;
 #include "woq_gemv_xqs.h"
 #include "woq_host.h"
 #include "woq_xq.h"
+#include "../../include/woq_hip_experimental.h"
 
 #ifdef WOQ_XQS_STAMPS
 extern "C" __attribute__((visibility("default"))) int woq_xqs_set_probe(void* buf_dev) {
@@ -275,3 +276,48 @@ void launch_xq_from_f32(const float* x, const float* norm_w, int K, const XqPtrs
 }
 
 }  // namespace woq
+
+extern "C" {
+
+// test entry points (include/woq_hip_experimental.h): the conversion and the XQ GEMV on caller-owned buffers
+WOQ_API int woq_probe_xq_from_f32(const float* x, const float* norm_w, int K, void* limbs_out, float* u_out,
+                                  float* sx_out, float* ssq_out, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(x && limbs_out && u_out && sx_out && K >= 16 && (K & 15) == 0, "QBits: bad XQ conversion probe arguments");
+  woq::launch_xq_from_f32(x, norm_w, K, woq::XqPtrs{(uint8_t*)limbs_out, u_out, sx_out}, ssq_out, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
+                              const float* bias, const float* residual, const float* next_norm_w, float* out,
+                              void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(x && blob && (epi == 0 || epi == 1), "QBits: bad XQ GEMV probe arguments");
+  WOQ_CHECK(out != nullptr || xo_limbs != nullptr, "QBits: the XQ GEMV probe needs an output");
+  WOQ_CHECK(xo_limbs == nullptr || (xo_u && xo_sx), "QBits: an XQ output needs all of its parts");
+  WOQ_CHECK(xo_limbs != nullptr || (next_norm_w == nullptr && ssq_out == nullptr),
+            "QBits: next_norm_w and ssq_out belong to the XQ output");
+  const hipStream_t st = (hipStream_t)stream;
+  woq_blob_header h;
+  WOQ_HIP(hipMemcpyAsync(&h, blob, sizeof(h), hipMemcpyDeviceToHost, st));
+  WOQ_HIP(hipStreamSynchronize(st));
+  WOQ_CHECK(h.magic == WOQ_BLOB_MAGIC, "QBits: not a WQH1 packed weight");
+  if (!woq::gemv_xq_supported(h, epi)) return woq::fail("QBits: shape not covered by the XQ GEMV");
+  // scratch: the input as an XQ vector, then its K / 16 RMSNorm partials
+  const size_t xq_sz = woq::xq_bytes(h.K), nblk = (size_t)h.K / 16;
+  uint8_t* ws = nullptr;
+  WOQ_HIP(hipMallocAsync((void**)&ws, xq_sz + nblk * sizeof(float), st));
+  const woq::XqPtrs xin = woq::xq_carve(ws, h.K);
+  float* ssq_in = in_norm_w != nullptr ? (float*)(ws + xq_sz) : nullptr;
+  woq::launch_xq_from_f32(x, in_norm_w, h.K, xin, ssq_in, st);
+  const int rc = woq::launch_gemv_xq(xin, blob, h, bias, out, ssq_in, eps, residual, epi,
+                                     woq::XqPtrs{(uint8_t*)xo_limbs, xo_u, xo_sx}, next_norm_w, ssq_out, st, nullptr);
+  const hipError_t le = hipGetLastError();
+  hipFreeAsync(ws, st);
+  if (rc) return rc;
+  WOQ_HIP(le);
+  WOQ_END
+}
+
+}  // extern "C"

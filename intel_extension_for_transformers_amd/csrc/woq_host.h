@@ -74,6 +74,8 @@ bool gemv_xq_supported(const woq_blob_header& h, int epi);
 int launch_gemv_xq(const XqPtrs& xin, const void* blob, const woq_blob_header& h, const float* bias, float* out,
                    const float* ssq_in, float eps, const float* residual, int epi, const XqPtrs& xo,
                    const float* next_norm_w, float* ssq_out, hipStream_t st, const CommDev* tp);
+// fp32 x[K] (times norm_w when given; K % 16 == 0) -> XQ vector xo, ssq_out (nullable) = per-block sums of squares of x
+void launch_xq_from_f32(const float* x, const float* norm_w, int K, const XqPtrs& xo, float* ssq_out, hipStream_t st);
 // mode 0: load-only twin of the batch-1 GEMV of this blob; mode 1: an empty kernel on the same grid and block
 int launch_gemv_twin(const void* blob, const woq_blob_header& h, int epi, int mode, unsigned int* sink, hipStream_t st);
 
@@ -110,9 +112,10 @@ void launch_attn_combine(const float* part, int heads, int D, int splits, float*
 void launch_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype, int hidden,
                     int vocab, float* logits, float* pmax, int32_t* pidx, hipStream_t st);
 void launch_argmax(const float* logits, int vocab, int32_t* token, int32_t* pos, hipStream_t st);
-// greedy token from the (max, index) pairs of launch_lm_head
+// greedy token from the (max, index) pairs of launch_lm_head; no pair won (every logit NaN or -inf): token 0 and
+// status (nullable) |= 4, the rule of launch_argmax_embed
 void launch_argmax_pairs(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
-                         hipStream_t st);
+                         int* status, hipStream_t st);
 // greedy token of the step that just ran its lm_head + embedding row of the NEXT step, one launch (argmax_embed_kernel)
 void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
                          const void* embed, int dtype, int hidden, float* out, const float* norm_w, const XqPtrs& xo,

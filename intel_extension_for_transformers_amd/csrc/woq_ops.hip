@@ -327,9 +327,12 @@ __global__ __launch_bounds__(256) void lm_head_kernel(const float* __restrict__ 
 // `cand` null: candidate i is logit i; else (logits[i], cand[i]) are the per-workgroup pairs lm_head_kernel left.
 // `log` (optional): log[position of the token that was just fed] = the new token, so a host that replays several steps
 // back to back can read them all afterwards instead of synchronising on every step.
+// No candidate won (every logit NaN or -inf): argmax_embed_kernel's rule — token 0 and status bit 2 — so that the
+// sentinel never reaches the next step's embedding lookup and the eager and the chained tail agree.
 __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ logits, const int32_t* __restrict__ cand,
                                                       int vocab, int32_t* __restrict__ token,
-                                                      int32_t* __restrict__ pos, int32_t* __restrict__ log) {
+                                                      int32_t* __restrict__ pos, int32_t* __restrict__ log,
+                                                      int* __restrict__ status) {
   __shared__ float bv[16];
   __shared__ int bi[16];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -363,6 +366,10 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
         best = bv[w];
         idx = bi[w];
       }
+    if (idx < 0 || (size_t)idx >= (cand ? (size_t)vocab * 16 : (size_t)vocab)) {
+      idx = 0;
+      if (status != nullptr) atomicOr(status, 4);
+    }
     token[0] = idx;
     if (log != nullptr) log[pos[0]] = idx;
     pos[0] = pos[0] + 1;
@@ -458,12 +465,12 @@ void launch_lm_head(const float* hidden_in, const float* norm_w, float eps, cons
 
 void launch_argmax(const float* logits, int vocab, int32_t* token, int32_t* pos, hipStream_t st) {
   hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, logits, (const int32_t*)nullptr, vocab, token, pos,
-                     (int32_t*)nullptr);
+                     (int32_t*)nullptr, (int*)nullptr);
 }
 
 void launch_argmax_pairs(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
-                         hipStream_t st) {
-  hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, pmax, pidx, n, token, pos, log);
+                         int* status, hipStream_t st) {
+  hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, pmax, pidx, n, token, pos, log, status);
 }
 
 void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t* token, int32_t* pos, int32_t* log,
@@ -553,6 +560,58 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
   hipFreeAsync(part, st);
   if (rc) return rc;
   WOQ_HIP(le);
+  WOQ_END
+}
+
+// test entry points (include/woq_hip_experimental.h): the token tail's launches on caller-owned buffers
+WOQ_API int woq_probe_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype,
+                              int hidden, int vocab, float* logits, float* pmax, int32_t* pidx, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(hidden_in && norm_w && W && logits && hidden >= 8 && (hidden & 7) == 0 && hidden <= 16384 && vocab >= 1,
+            "QBits: bad lm_head probe arguments");
+  WOQ_CHECK(w_dtype == WOQ_F16 || w_dtype == WOQ_BF16, "QBits: the lm_head is fp16 or bf16");
+  WOQ_CHECK((pmax == nullptr) == (pidx == nullptr), "QBits: pmax and pidx come together");
+  launch_lm_head(hidden_in, norm_w, eps, W, w_dtype, hidden, vocab, logits, pmax, pidx, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_greedy_tail(int mode, const float* logits, int vocab, const float* pmax, const int32_t* pidx,
+                                  int32_t* token, int32_t* pos, int32_t* log, const void* embed, int embed_dtype,
+                                  int hidden, float* out, const float* norm_w, void* xo_limbs, float* xo_u, float* xo_sx,
+                                  float* ssq_out, unsigned int* step_seq, int max_ctx, int* status, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(mode >= 0 && mode <= 2 && vocab >= 1 && token && pos, "QBits: bad greedy tail probe arguments");
+  const hipStream_t st = (hipStream_t)stream;
+  const int n_pairs = (vocab + 15) / 16;
+  if (mode == 0) {
+    WOQ_CHECK(logits != nullptr, "QBits: mode 0 reduces logits");
+    launch_argmax(logits, vocab, token, pos, st);
+  } else if (mode == 1) {
+    WOQ_CHECK(pmax && pidx, "QBits: modes 1 and 2 reduce the lm_head's pairs");
+    launch_argmax_pairs(pmax, pidx, n_pairs, token, pos, log, status, st);
+  } else {
+    WOQ_CHECK(pmax && pidx && embed && out && hidden >= 16 && (hidden & 15) == 0 && max_ctx >= 1,
+              "QBits: mode 2 needs the pairs and an embedding table");
+    WOQ_CHECK(embed_dtype == WOQ_F16 || embed_dtype == WOQ_BF16 || embed_dtype == WOQ_F32, "QBits: bad embedding type");
+    WOQ_CHECK(xo_limbs == nullptr || (norm_w && xo_u && xo_sx && ssq_out), "QBits: an XQ output needs all of its parts");
+    launch_argmax_embed(pmax, pidx, n_pairs, token, pos, log, embed, embed_dtype, hidden, out, norm_w,
+                        XqPtrs{(uint8_t*)xo_limbs, xo_u, xo_sx}, ssq_out, step_seq, max_ctx, status, st);
+  }
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_embed(const void* embed, int embed_dtype, const int32_t* token, int hidden, float* out,
+                            const float* norm_w, void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out,
+                            unsigned int* step_seq, int32_t* pos, int max_ctx, int* status, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(embed && token && out && hidden >= 16 && (hidden & 15) == 0, "QBits: bad embed probe arguments");
+  WOQ_CHECK(embed_dtype == WOQ_F16 || embed_dtype == WOQ_BF16 || embed_dtype == WOQ_F32, "QBits: bad embedding type");
+  WOQ_CHECK(xo_limbs == nullptr || (norm_w && xo_u && xo_sx && ssq_out), "QBits: an XQ output needs all of its parts");
+  launch_embed(embed, embed_dtype, token, hidden, out, norm_w, XqPtrs{(uint8_t*)xo_limbs, xo_u, xo_sx}, ssq_out,
+               step_seq, pos, max_ctx, status, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
   WOQ_END
 }
 

@@ -10,16 +10,17 @@
 // Format, for K = 16 * nb values: block b = values [16 b, 16 b + 16) — exactly what one producer workgroup (one
 // 16-column output tile of the previous GEMV, or 16 lanes of the attention / embedding kernels) owns, so no
 // cross-workgroup reduction is needed:
-//   limbs [nb][3][16] int8 : BALANCED signed digits of v = round(y * 2^(21 - e_b)) (|v| <= 2^22), e_b = exponent of
-//                            the block's max |y|: v = s0 + 2^8 s1 + 2^16 s2 with s0, s1 in [-128, 127], s2 in
-//                            [-64, 64] (round 3; round 2 stored offset-binary bytes and needed a ones row in the MFMA
+//   limbs [nb][3][16] int8 : BALANCED signed digits of v = round(y * 2^(21 - e_b)) (|v| <= 2^21), e_b = exponent of
+//                            the block's max |y| (max |y| in [2^(e_b - 1), 2^e_b)): v = s0 + 2^8 s1 + 2^16 s2 with
+//                            s0, s1 in [-128, 127], s2 in [-32, 32] (round 3; round 2 stored offset-binary bytes and needed a ones row in the MFMA
 //                            to take the offsets out again — 9 VALU per MFMA result instead of 4)
 //   u     [nb] fp32        : 2^(e_b - 25), undoes the block's fixed-point scale and the 16 * q weight bytes
 //   sx    [nb] fp32        : sum over the block of v, the fixed-point activations' sum (zero-point term)
 // A block is one (64-k half, lane quarter) of the consumer's v_mfma_i32_16x16x64_i8: MFMA rows 4 e .. 4 e + 2 carry
 // quarter e's three digits (row 4 e + 3 and the other quarters' k are zero), so ONE MFMA per half returns the four
 // blocks' digit sums separately, one per lane quarter, each scaled by its own u (and, for group 32, its own weight
-// scale). Element error <= max|x_block| * 2^-22. An all-zero buffer is a valid vector of zeros.
+// scale). Element error <= half a unit, 2^(e_b - 22) <= max|x_block| * 2^-21 (tests/xq_reference.py restates the format
+// bit for bit). An all-zero buffer is a valid vector of zeros.
 // RMSNorm stays separable: the producer multiplies by the NEXT norm's weight before converting and leaves one partial
 // sum of squares of the raw values per block; the consumer adds them up in a fixed order.
 #pragma once
