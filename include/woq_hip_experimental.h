@@ -128,6 +128,20 @@ WOQ_API int woq_probe_greedy_tail(int mode, const float* logits, int vocab, cons
 WOQ_API int woq_probe_embed(const void* embed, int embed_dtype, const int32_t* token, int hidden, float* out,
                             const float* norm_w, void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out,
                             unsigned int* step_seq, int32_t* pos, int max_ctx, int* status, void* stream);
+/* one projection of the fp32-activation decode step (tests/test_gpu_f32_gemv_kernel.py), run exactly as the engine runs
+ * it but on caller-owned device buffers and with the arguments the engine fixes left open: x [M][lda] in x_dtype, blob a
+ * packed weight on the device (its header is read back, which synchronises the stream), norm_w fp32 [K] (nullable) with
+ * eps = the fused RMSNorm, epi 1 = SiLU(gate) * up over a fuse_gate_up blob (out [M][N / 2]), bias fp32 [N] (nullable),
+ * residual fp32 [M][ld_res] (nullable, may alias out), out [M][ldo] in out_dtype. An fp8 composite blob is split like
+ * woq_linear splits it and goes to the engine's fp8 launcher, which takes M = 1, fp32 rows and no bias (anything else is
+ * an error); its epi 1 form needs gu_tmp = fp32 [N] of device scratch, without it the lookup kernel runs. Every other
+ * blob goes to the small-M dispatch. form_out (host, nullable) = {kernel, chained launches, waves, tiles per wave} of the
+ * launch, from the predicates the launchers themselves call: kernel 0 = generic / lookup (one launch, 4 waves, tiles per
+ * wave 0), 1 = the int8-MFMA tile kernel, 2 = the fp8 matrix-core kernel; waves and tiles per wave are those of the first
+ * chained launch. */
+WOQ_API int woq_probe_gemv_f32(const void* x, int x_dtype, int lda, int M, const void* blob, const float* norm_w,
+                               float eps, int epi, const float* bias, const float* residual, int ld_res, void* out,
+                               int out_dtype, int ldo, float* gu_tmp, int* form_out, void* stream);
 /* fp32 [rows][hidden]: the residual stream the last prompt pass left (before the final norm), valid until the next
  * prompt pass; NULL before the first one. For tests. */
 WOQ_API void* woq_engine_prefill_rows_ptr(woq_engine* e);

@@ -94,6 +94,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
+    "woq_probe_gemv_f32",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -202,6 +203,7 @@ def lib():
     L.woq_probe_lm_head.argtypes = [vp, vp, cf, vp, ci, ci, ci, vp, vp, vp, vp]
     L.woq_probe_greedy_tail.argtypes = [ci, vp, ci] + [vp] * 6 + [ci, ci] + [vp] * 7 + [ci, vp, vp]
     L.woq_probe_embed.argtypes = [vp, ci, vp, ci] + [vp] * 8 + [ci, vp, vp]
+    L.woq_probe_gemv_f32.argtypes = [vp, ci, ci, ci, vp, vp, cf, ci, vp, vp, ci, vp, ci, ci, vp, ctypes.POINTER(ci), vp]
     _lib = L
     return L
 
@@ -335,6 +337,20 @@ def probe_embed(embed, token, out, norm_w=None, xo=None, ssq_out=None, step_seq=
     check(lib().woq_probe_embed(_ptr(embed), torch_dtype_code(embed.dtype), _ptr(token), int(embed.shape[1]), _ptr(out),
                                 _opt(norm_w), *_xq_ptrs(xo), _opt(ssq_out), _opt(step_seq), _opt(pos), int(max_ctx),
                                 _opt(status), stream_ptr()))
+
+
+def probe_gemv_f32(x, blob, out, M=1, lda=None, ldo=None, norm_w=None, eps=0.0, epi=0, bias=None, residual=None,
+                   ld_res=None, gu_tmp=None):
+    """one projection of the fp32-activation decode step (woq_probe_gemv_f32): x / out / residual device tensors whose
+    data pointers are row 0 (views are fine), leading dimensions in elements; -> (kernel, chunks, waves, tiles per wave)
+    with kernel 0 = generic, 1 = tile, 2 = fp8 matrix-core."""
+    form = (ctypes.c_int * 4)()
+    lda = int(x.numel() // M if lda is None else lda)
+    ldo = int(out.numel() // M if ldo is None else ldo)
+    check(lib().woq_probe_gemv_f32(_ptr(x), torch_dtype_code(x.dtype), lda, int(M), _ptr(blob), _opt(norm_w), float(eps),
+                                   int(epi), _opt(bias), _opt(residual), int(ldo if ld_res is None else ld_res), _ptr(out),
+                                   torch_dtype_code(out.dtype), ldo, _opt(gu_tmp), form, stream_ptr()))
+    return tuple(form)
 
 
 def check(rc):

@@ -15,6 +15,7 @@
 // interleaved over the K tiles, wave-shuffle + LDS reduction). It is correct for every blob; it is not tuned.
 #include "woq_device.h"
 #include "woq_host.h"
+#include "../../include/woq_hip_experimental.h"
 
 namespace woq {
 
@@ -289,3 +290,56 @@ int launch_gemv_fp8_engine(const float* act, int lda, const void* hi_blob, const
 }
 
 }  // namespace woq
+
+extern "C" {
+
+WOQ_API int woq_probe_gemv_f32(const void* x, int x_dtype, int lda, int M, const void* blob, const float* norm_w,
+                               float eps, int epi, const float* bias, const float* residual, int ld_res, void* out,
+                               int out_dtype, int ldo, float* gu_tmp, int* form_out, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(x && blob && out && M >= 1 && (epi == 0 || epi == 1), "QBits: bad f32 GEMV probe arguments");
+  WOQ_CHECK(x_dtype >= WOQ_F32 && x_dtype <= WOQ_F16 && out_dtype >= WOQ_F32 && out_dtype <= WOQ_F16,
+            "QBits: unsupported qbits data type.");
+  const hipStream_t st = (hipStream_t)stream;
+  woq_blob_header h;
+  WOQ_HIP(hipMemcpyAsync(&h, blob, sizeof(h), hipMemcpyDeviceToHost, st));
+  WOQ_HIP(hipStreamSynchronize(st));
+  WOQ_CHECK(h.magic == WOQ_BLOB_MAGIC, "QBits: not a WQH1 packed weight");
+  WOQ_CHECK(lda >= h.K && ldo >= (epi == 1 ? h.N / 2 : h.N), "QBits: activation/output leading dimension smaller than K/N");
+  int form[4] = {0, 1, woq::GEN_NW, 0};  // the generic kernel: one launch of GEN_NW waves interleaved over the K tiles
+  int rc;
+  if (woq_weight_is_fp8(h.weight_type)) {
+    // the composite container, split as woq_linear and woq_engine_set_layer split it
+    WOQ_CHECK(M == 1 && x_dtype == WOQ_F32 && out_dtype == WOQ_F32 && bias == nullptr,
+              "QBits: the engine's fp8 GEMV takes one fp32 row and no bias");
+    woq_blob_header o, hi, lo;
+    WOQ_CHECK(woq_fp8_headers(&o, &hi, &lo, h.K, h.N, h.group, h.weight_type, h.scale_type, h.compute_type,
+                              h.off_shuffle != 0) == 0, "QBits: corrupt fp8 header");
+    const uint8_t* bhi = (const uint8_t*)blob + h.off_q;
+    const uint8_t* blo = (const uint8_t*)blob + h.off_scale;
+    if (woq::gemv_fp8_mfma_supported(x, WOQ_F32, lda, hi) && (epi != 1 || gu_tmp != nullptr)) {
+      form[0] = 2;
+      woq::fp8_geometry(hi.Kpad / WOQ_TILE_K, form[2], form[3]);
+    }
+    rc = woq::launch_gemv_fp8_engine((const float*)x, lda, bhi, hi, blo + lo.off_q, h.weight_type, (float*)out, ldo,
+                                     norm_w, eps, residual, ld_res, epi, gu_tmp, st);
+  } else {
+    const int rows = woq::gemv_tile_max_rows(x, x_dtype, lda, h, norm_w, epi, out_dtype);
+    if (rows > 0 && !(h.off_shuffle != 0 && M > 1)) {
+      const int tiles_k = h.Kpad / WOQ_TILE_K, cb = epi == 1 ? 2 : 1, smode = (int)h.scale_mode;
+      form[0] = 1;
+      form[1] = woq::gemv_tile_k_chunks(tiles_k, cb, smode, epi == 0 && !norm_w && out_dtype == WOQ_F32);
+      WOQ_CHECK(form[1] > 0 && woq::gemv_tile_geometry((tiles_k + form[1] - 1) / form[1], cb, smode, form[2], form[3]),
+                "QBits: shape not covered by the tile GEMV");
+    }
+    rc = woq::launch_gemv_from_header(x, x_dtype, lda, blob, h, bias, out, out_dtype, ldo, M, norm_w, eps, residual,
+                                      ld_res, epi, 1, st);
+  }
+  if (rc) return rc;
+  WOQ_HIP(hipGetLastError());
+  if (form_out != nullptr)
+    for (int i = 0; i < 4; ++i) form_out[i] = form[i];
+  WOQ_END
+}
+
+}  // extern "C"

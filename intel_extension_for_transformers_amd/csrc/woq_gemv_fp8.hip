@@ -369,7 +369,7 @@ static int launch_fp8_t(const F8Launch& a, hipStream_t st) {
 }
 
 // geometry: 4 tiles per wave and up to 16 waves (K <= 8192), else 8 tiles per wave and up to 12 waves (K <= 12288)
-static bool fp8_geometry(int tiles_k, int& nw, int& tpw) {
+bool fp8_geometry(int tiles_k, int& nw, int& tpw) {
   tpw = tiles_k > 64 ? 8 : 4;
   nw = (tiles_k + tpw - 1) / tpw;
   return nw >= 1 && nw <= (tpw == 8 ? 12 : 16);

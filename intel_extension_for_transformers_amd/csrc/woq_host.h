@@ -57,6 +57,8 @@ int launch_gemv_tile(const void* act, int act_dtype, int lda, int M, const void*
 // ---- woq_gemv_fp8.hip: the fp8 matrix-core GEMV -------------------------------------------------------------------
 // Does the fp8-MFMA kernel take this call? `hi` = the HI plane's header (scales; the LO plane has the same geometry).
 bool gemv_fp8_mfma_supported(const void* act, int act_dtype, int lda, const woq_blob_header& hi);
+// its geometry: nw waves x tpw tiles of both planes cover tiles_k; false when it does not take the K (beyond 12288)
+bool fp8_geometry(int tiles_k, int& nw, int& tpw);
 // rows 0..M-1 (M <= 8) of an fp8 weight: act [M, lda], out [M, ldo]
 int launch_gemv_fp8_mfma(const void* act, int act_dtype, int lda, int M, const void* hi_blob, const woq_blob_header& hi,
                          const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo,
