@@ -109,7 +109,7 @@ static int linear_int4(const void* act, int act_dtype, int lda, const void* blob
     return launch_gemm_f16(act, act_dtype, lda, blob, h, bias, out, out_dtype, ldo, M, nullptr, 0.f, residual, ld_res, 0,
                            nullptr, h.compute_type == WOQ_C_FP32 ? 1 : 0, st);
   return launch_gemv_from_header(act, act_dtype, lda, blob, h, bias, out, out_dtype, ldo, M, nullptr, 0.f, residual,
-                                 ld_res, 0, 1, st);
+                                 ld_res, 0, st);
 }
 
 int woq_table_digit_planes(int weight_type, int compute_type, uint32_t planes[3][4], float* wmul) {

@@ -105,7 +105,6 @@ struct woq_engine {
   const float* tp_residual(const float* stream) const { return cfg.tp_size <= 1 || cfg.tp_rank == 0 ? stream : nullptr; }
   woq_comm* comm = nullptr;  // device-side exchange: all-reduce kernels inside the (capturable) decode step
   int vocab_offset = 0;      // first vocabulary row of this rank's lm_head shard
-  int nt = 1;
   std::vector<void*> owned;  // everything hipMalloc'ed by create()
   // prompt pass: [n_seq * T] rows at a time; buffers grow on demand (never inside a captured graph)
   int32_t* tok_log = nullptr;   // [max_ctx + 1]: tok_log[p] = greedy token produced by the step that fed position p
@@ -236,7 +235,7 @@ static int engine_linear_f32(woq_engine* e, int l, Proj k, const float* act, int
     return launch_gemv_fp8_engine(act, lda, p.blob, p.hdr, p.fp8_lo, e->fp8_type, out, ldo, norm_w, c.rms_eps, residual,
                                   c.hidden, kProjEpi[k], e->gu_tmp, st);
   return launch_gemv_from_header(act, WOQ_F32, lda, p.blob, p.hdr, nullptr, out, WOQ_F32, ldo, 1, norm_w, c.rms_eps,
-                                 residual, c.hidden, kProjEpi[k], e->nt, st);
+                                 residual, c.hidden, kProjEpi[k], st);
 }
 
 static int engine_attn_block(woq_engine* e, int l, hipStream_t st) {
@@ -1042,19 +1041,19 @@ int woq_engine_time_gemv_mask(woq_engine* e, int mask, int reps, void* stream, f
         continue;
       }
       rc = (mask & 1) ? launch_gemv_from_header(e->hidden, WOQ_F32, c.hidden, qkv.blob, qkv.hdr, nullptr, e->qkv,
-                                                WOQ_F32, qkv.hdr.N, 1, w.ln1, c.rms_eps, nullptr, 0, 0, e->nt, st)
+                                                WOQ_F32, qkv.hdr.N, 1, w.ln1, c.rms_eps, nullptr, 0, 0, st)
                       : 0;
       if (rc) return rc;
       rc = (mask & 2) ? launch_gemv_from_header(e->attn, WOQ_F32, c.heads * c.head_dim, o.blob, o.hdr, nullptr,
-                                                e->qkv, WOQ_F32, c.hidden, 1, nullptr, 0.f, nullptr, 0, 0, e->nt, st)
+                                                e->qkv, WOQ_F32, c.hidden, 1, nullptr, 0.f, nullptr, 0, 0, st)
                       : 0;
       if (rc) return rc;
       rc = (mask & 4) ? launch_gemv_from_header(e->hidden, WOQ_F32, c.hidden, gu.blob, gu.hdr, nullptr,
-                                                e->act, WOQ_F32, c.inter, 1, w.ln2, c.rms_eps, nullptr, 0, 1, e->nt, st)
+                                                e->act, WOQ_F32, c.inter, 1, w.ln2, c.rms_eps, nullptr, 0, 1, st)
                       : 0;
       if (rc) return rc;
       rc = (mask & 8) ? launch_gemv_from_header(e->act, WOQ_F32, c.inter, down.blob, down.hdr, nullptr, e->qkv,
-                                                WOQ_F32, c.hidden, 1, nullptr, 0.f, nullptr, 0, 0, e->nt, st)
+                                                WOQ_F32, c.hidden, 1, nullptr, 0.f, nullptr, 0, 0, st)
                       : 0;
       if (rc) return rc;
     }

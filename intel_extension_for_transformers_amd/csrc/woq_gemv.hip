@@ -14,12 +14,11 @@
 // arithmetic on the same blob (activation rows staged in LDS as fp32, one workgroup per 16-column tile, waves
 // interleaved over the K tiles, wave-shuffle + LDS reduction). It is correct for every blob; it is not tuned.
 #include "woq_device.h"
+#include "woq_gemv_launch.h"
 #include "woq_host.h"
 #include "../../include/woq_hip_experimental.h"
 
 namespace woq {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct GenArgs {
   const u32x4* q;
@@ -176,21 +175,22 @@ static int launch_gemv_generic(const void* act, int act_dtype, int lda, int M, c
                                const woq_blob_header& h, const float* bias, void* out, int out_dtype, int ldo,
                                const float* norm_w, float eps, const float* residual, int ld_res, int epi,
                                hipStream_t st, const void* lo_plane = nullptr, uint32_t fp8_type = 0) {
+  BlobView v;
+  blob_view(blob, h, v);  // (this kernel divides by the group size: any number of tiles per group)
   GenArgs a;
-  const uint8_t* b = (const uint8_t*)blob;
-  a.q = (const u32x4*)(b + h.off_q);
+  a.q = v.q;
   a.q_lo = (const u32x4*)lo_plane;
-  a.scales = b + h.off_scale;
-  a.zp = h.off_zp ? b + h.off_zp : nullptr;
-  a.shuffle = h.off_shuffle ? (const int32_t*)(b + h.off_shuffle) : nullptr;
-  a.K = h.K;
-  a.N = h.N;
+  a.scales = v.scales;
+  a.zp = v.zp;
+  a.shuffle = v.shuffle;
+  a.K = v.K;
+  a.N = v.N;
   a.Kpad = h.Kpad;
-  a.tiles_k = h.Kpad / WOQ_TILE_K;
-  a.n_groups = h.n_groups;
+  a.tiles_k = v.tiles_k;
+  a.n_groups = v.n_groups;
   a.group = h.group;
   a.scale_type = (int)h.scale_type;
-  a.scale_mode = (int)h.scale_mode;
+  a.scale_mode = v.smode;
   a.x = act;
   a.x_dtype = act_dtype;
   a.lda = lda;
@@ -205,70 +205,62 @@ static int launch_gemv_generic(const void* act, int act_dtype, int lda, int M, c
   a.residual = residual;
   a.epi = epi;
   a.weight_type = lo_plane ? fp8_type : h.weight_type;
-  const int tiles_n = h.Npad / WOQ_TILE_N;
-  if (epi == 1 && (tiles_n & 1)) return woq::fail("QBits: fused gate/up weight needs an even number of column tiles");
+  if (epi == 1 && (v.tiles_n & 1)) return woq::fail("QBits: fused gate/up weight needs an even number of column tiles");
   const size_t lds = gen_lds_bytes(M, h.Kpad);
   if (lds > 158 * 1024) return woq::fail("QBits: K too large for the small-M GEMV (activation row does not fit LDS)");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemv_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       158 * 1024);  // the kernel also holds 1 KiB of static LDS (the value table)
-    if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
-    attr_set = true;
+  // the kernel also holds 1 KiB of static LDS (the value table)
+  if (const int rc = allow_dynamic_lds<gemv_generic_kernel>(158 * 1024)) return rc;
+  hipLaunchKernelGGL(gemv_generic_kernel, dim3(v.tiles_n / (epi == 1 ? 2 : 1)), dim3(GEN_NW * 64), lds, st, a);
+  return 0;
+}
+
+// rows per launch of the generic kernel at this K (LDS budget)
+static int gen_max_rows(int Kpad) {
+  int rows = GEN_MAXM;
+  while (rows > 1 && gen_lds_bytes(rows, Kpad) > 150 * 1024) --rows;
+  return rows;
+}
+
+// rows [0, M) of a call in chunks of at most `rows`: launch(act, out, residual, mc) of every chunk's first row, -> rc
+template <typename F>
+static int for_row_chunks(const void* act, int act_dtype, int lda, void* out, int out_dtype, int ldo,
+                          const float* residual, int ld_res, int M, int rows, F&& launch) {
+  const size_t esz_a = act_dtype == WOQ_F32 ? 4 : 2, esz_o = out_dtype == WOQ_F32 ? 4 : 2;
+  for (int m0 = 0; m0 < M; m0 += rows) {
+    const int rc = launch((const char*)act + (size_t)m0 * lda * esz_a, (char*)out + (size_t)m0 * ldo * esz_o,
+                          residual ? residual + (size_t)m0 * ld_res : nullptr, M - m0 < rows ? M - m0 : rows);
+    if (rc) return rc;
   }
-  hipLaunchKernelGGL(gemv_generic_kernel, dim3(tiles_n / (epi == 1 ? 2 : 1)), dim3(GEN_NW * 64), lds, st, a);
   return 0;
 }
 
 int launch_gemv_from_header(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
                             const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w,
-                            float eps, const float* residual, int ld_res, int epi, int nt, hipStream_t st) {
-  (void)nt;
-  const size_t esz_a = act_dtype == WOQ_F32 ? 4 : 2, esz_o = out_dtype == WOQ_F32 ? 4 : 2;
-  int rows = gemv_tile_max_rows(act, act_dtype, lda, h, norm_w, epi, out_dtype);
-  const bool tile = rows > 0 && !(h.off_shuffle != 0 && M > 1);  // act-order blobs: the tile kernel's gather form is batch-1
-  if (!tile) {
-    rows = GEN_MAXM;
-    while (rows > 1 && gen_lds_bytes(rows, h.Kpad) > 150 * 1024) --rows;
-  }
-  for (int m0 = 0; m0 < M; m0 += rows) {
-    const int mc = M - m0 < rows ? M - m0 : rows;
-    const void* a_p = (const char*)act + (size_t)m0 * lda * esz_a;
-    void* o_p = (char*)out + (size_t)m0 * ldo * esz_o;
-    const float* r_p = residual ? residual + (size_t)m0 * ld_res : nullptr;
-    // the tile kernel needs every row chunk 16-B aligned, which (lda & 3) == 0 and an aligned base guarantee
-    const int rc = tile ? launch_gemv_tile(a_p, act_dtype, lda, mc, blob, h, bias, o_p, out_dtype, ldo, norm_w, eps,
-                                           r_p, ld_res, epi, st)
-                        : launch_gemv_generic(a_p, act_dtype, lda, mc, blob, h, bias, o_p, out_dtype, ldo, norm_w,
-                                              eps, r_p, ld_res, epi, st);
-    if (rc) return rc;
-  }
-  return 0;
+                            float eps, const float* residual, int ld_res, int epi, hipStream_t st) {
+  const int tile_rows = gemv_tile_max_rows(act, act_dtype, lda, h, norm_w, epi, out_dtype);
+  const bool tile = tile_rows > 0 && !(h.off_shuffle != 0 && M > 1);  // act-order blobs: the tile kernel's gather form is batch-1
+  return for_row_chunks(act, act_dtype, lda, out, out_dtype, ldo, residual, ld_res, M,
+                        tile ? tile_rows : gen_max_rows(h.Kpad),
+                        [&](const void* a_p, void* o_p, const float* r_p, int mc) {
+                          // the tile kernel needs every row chunk 16-B aligned, which (lda & 3) == 0 and an aligned base guarantee
+                          return tile ? launch_gemv_tile(a_p, act_dtype, lda, mc, blob, h, bias, o_p, out_dtype, ldo,
+                                                         norm_w, eps, r_p, ld_res, epi, st)
+                                      : launch_gemv_generic(a_p, act_dtype, lda, mc, blob, h, bias, o_p, out_dtype, ldo,
+                                                            norm_w, eps, r_p, ld_res, epi, st);
+                        });
 }
 
 int launch_gemv_fp8(const void* act, int act_dtype, int lda, const void* hi_blob, const woq_blob_header& hi,
                     const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo, int M,
                     hipStream_t st) {
-  const size_t esz_a = act_dtype == WOQ_F32 ? 4 : 2, esz_o = out_dtype == WOQ_F32 ? 4 : 2;
-  if (gemv_fp8_mfma_supported(act, act_dtype, lda, hi)) {
-    for (int m0 = 0; m0 < M; m0 += 8) {
-      const int rc = launch_gemv_fp8_mfma((const char*)act + (size_t)m0 * lda * esz_a, act_dtype, lda,
-                                          M - m0 < 8 ? M - m0 : 8, hi_blob, hi, lo_q, fp8_type, bias,
-                                          (char*)out + (size_t)m0 * ldo * esz_o, out_dtype, ldo, st);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  int rows = GEN_MAXM;
-  while (rows > 1 && gen_lds_bytes(rows, hi.Kpad) > 150 * 1024) --rows;
-  for (int m0 = 0; m0 < M; m0 += rows) {
-    const int mc = M - m0 < rows ? M - m0 : rows;
-    const int rc = launch_gemv_generic((const char*)act + (size_t)m0 * lda * esz_a, act_dtype, lda, mc, hi_blob, hi,
-                                       bias, (char*)out + (size_t)m0 * ldo * esz_o, out_dtype, ldo, nullptr, 0.f,
-                                       nullptr, 0, 0, st, lo_q, fp8_type);
-    if (rc) return rc;
-  }
-  return 0;
+  const bool mfma = gemv_fp8_mfma_supported(act, act_dtype, lda, hi);
+  return for_row_chunks(act, act_dtype, lda, out, out_dtype, ldo, nullptr, 0, M, mfma ? 8 : gen_max_rows(hi.Kpad),
+                        [&](const void* a_p, void* o_p, const float*, int mc) {
+                          return mfma ? launch_gemv_fp8_mfma(a_p, act_dtype, lda, mc, hi_blob, hi, lo_q, fp8_type, bias,
+                                                             o_p, out_dtype, ldo, st)
+                                      : launch_gemv_generic(a_p, act_dtype, lda, mc, hi_blob, hi, bias, o_p, out_dtype,
+                                                            ldo, nullptr, 0.f, nullptr, 0, 0, st, lo_q, fp8_type);
+                        });
 }
 
 int launch_gemv_fp8_engine(const float* act, int lda, const void* hi_blob, const woq_blob_header& hi, const void* lo_q,
@@ -326,14 +318,12 @@ WOQ_API int woq_probe_gemv_f32(const void* x, int x_dtype, int lda, int M, const
   } else {
     const int rows = woq::gemv_tile_max_rows(x, x_dtype, lda, h, norm_w, epi, out_dtype);
     if (rows > 0 && !(h.off_shuffle != 0 && M > 1)) {
-      const int tiles_k = h.Kpad / WOQ_TILE_K, cb = epi == 1 ? 2 : 1, smode = (int)h.scale_mode;
-      form[0] = 1;
-      form[1] = woq::gemv_tile_k_chunks(tiles_k, cb, smode, epi == 0 && !norm_w && out_dtype == WOQ_F32);
-      WOQ_CHECK(form[1] > 0 && woq::gemv_tile_geometry((tiles_k + form[1] - 1) / form[1], cb, smode, form[2], form[3]),
-                "QBits: shape not covered by the tile GEMV");
+      const woq::KPlan plan = woq::gemv_tile_k_plan(h, norm_w, epi, out_dtype);
+      WOQ_CHECK(plan.chunks > 0, "QBits: shape not covered by the tile GEMV");
+      form[0] = 1, form[1] = plan.chunks, form[2] = plan.nw[0], form[3] = plan.tpw[0];
     }
     rc = woq::launch_gemv_from_header(x, x_dtype, lda, blob, h, bias, out, out_dtype, ldo, M, norm_w, eps, residual,
-                                      ld_res, epi, 1, st);
+                                      ld_res, epi, st);
   }
   if (rc) return rc;
   WOQ_HIP(hipGetLastError());

@@ -23,6 +23,7 @@
 
 #include "woq_attn_decode.h"
 #include "woq_gemv_common.h"
+#include "woq_gemv_launch.h"
 #include "woq_gemv_xqs.h"
 #include "woq_host.h"
 #include "woq_xq.h"
@@ -112,10 +113,8 @@ bool gemv_xq_attn_supported(const woq_blob_header& h, int heads, int kv_heads, i
                             int window, int splits) {
   if (h.weight_type != WOQ_W_INT4_CLIP || h.off_shuffle != 0 || h.K != h.Kpad || h.N != h.Npad) return false;
   if (h.Kpad / WOQ_TILE_K != 4 * FUSED_TPW) return false;  // four waves of eight tiles
-  if (h.scale_mode == 0 && h.n_groups > 1) {
-    const int tpg = h.group / WOQ_TILE_K;
-    if (tpg < 1 || (tpg & (tpg - 1)) != 0) return false;
-  }
+  BlobView v;
+  if (!blob_view(nullptr, h, v)) return false;
   // round 4: grouped-query shapes (Mistral-7B: 32 query / 8 kv heads) and a sliding window are taken as well — the
   // attention body always handled both (kh = h / rep, re-based cache pointers); round 3 simply had not tested them here
   if (kv_heads < 1 || heads % kv_heads != 0 || head_dim != 128 || splits > ATTN_A2A_MAX_SLICES) return false;
@@ -131,53 +130,39 @@ bool gemv_xq_attn_supported(const woq_blob_header& h, int heads, int kv_heads, i
   return attn_dec_lds_floats(128, fused_attn_span(max_ctx, window, splits)) * 4 <= 38 * 1024;
 }
 
+// what the fused launch carries beside the blob (BlobView)
 struct FusedLaunch {
-  const void* q;
-  const void* scales;
-  const void* zp;
   XqPtrs xin;
-  int tiles_k, K, N, n_groups, tpg_shift, flags, n_ssq;
+  int flags, n_ssq;
   unsigned long long* out;
   float eps;
   const float* ssq_in;
   FusedAttnArgs fa;
-  size_t lds;
+  size_t lds_attn;
 };
 
 template <int SMODE, bool ASYM, bool S32, typename KV>
-static int launch_fused_t(const FusedLaunch& a, hipStream_t st) {
-  auto kern = gemv_xqs_attn_kernel<SMODE, ASYM, S32, KV>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
-    attr_set = true;
-  }
+static int launch_fused_t(const BlobView& v, const FusedLaunch& a, hipStream_t st) {
+  // every workgroup gets max(attention LDS, GEMV LDS)
+  const size_t lds = std::max(a.lds_attn, XqsLds<FUSED_TPW, 1, SMODE, ASYM, S32>::total(4));
+  if (lds > 160 * 1024) return woq::fail("QBits: fused qkv + attention launch does not fit LDS");
+  constexpr auto kern = gemv_xqs_attn_kernel<SMODE, ASYM, S32, KV>;
+  if (const int rc = allow_dynamic_lds<kern>(160 * 1024)) return rc;
   XqsLate late;
-  late.zp = (const uint8_t*)a.zp, late.xsx = a.xin.sx, late.out = (float*)a.out, late.bias = nullptr, late.residual = nullptr;
+  late.zp = v.zp, late.xsx = a.xin.sx, late.out = (float*)a.out, late.bias = nullptr, late.residual = nullptr;
   late.ssq_in = a.ssq_in, late.next_norm_w = nullptr, late.ssq_out = nullptr, late.tp = nullptr;
   late.tag_seq = a.fa.seq, late.tag_layer = a.fa.layer, late.xo = XqPtrs{nullptr, nullptr, nullptr}, late.eps = a.eps;
-  late.N = a.N, late.K = a.K, late.n_ssq = a.n_ssq, late.lut = LutArgs{};
-  hipLaunchKernelGGL(kern, dim3(a.N / 16 + a.fa.heads * a.fa.ns), dim3(256), a.lds, st, (const u32x4*)a.q, a.scales,
-                     a.xin.limbs, a.xin.u, a.tiles_k, a.fa.heads * 8, FUSED_TPW, 0, a.n_groups,
-                     a.tpg_shift | (a.flags << 8) | ((a.N / 16) << 16), late, a.out, a.N, a.fa);
+  late.N = v.N, late.K = v.K, late.n_ssq = a.n_ssq, late.lut = LutArgs{};
+  hipLaunchKernelGGL(kern, dim3(v.N / 16 + a.fa.heads * a.fa.ns), dim3(256), lds, st, v.q, v.scales, a.xin.limbs,
+                     a.xin.u, v.tiles_k, a.fa.heads * 8, FUSED_TPW, 0, v.n_groups,
+                     v.tpg_shift | (a.flags << 8) | ((v.N / 16) << 16), late, a.out, v.N, a.fa);
   return 0;
 }
 
 template <typename KV>
-static int launch_fused_kv(const FusedLaunch& a, int smode, bool asym, bool s32, hipStream_t st) {
-#define WOQ_FA_CASE(SM, AS, S3) \
-  if (smode == SM && asym == AS && s32 == S3) return launch_fused_t<SM, AS, S3, KV>(a, st);
-  WOQ_FA_CASE(0, false, false)
-  WOQ_FA_CASE(0, false, true)
-  WOQ_FA_CASE(0, true, false)
-  WOQ_FA_CASE(0, true, true)
-  WOQ_FA_CASE(1, false, false)
-  WOQ_FA_CASE(1, false, true)
-  WOQ_FA_CASE(1, true, false)
-  WOQ_FA_CASE(1, true, true)
-#undef WOQ_FA_CASE
-  return woq::fail("QBits: bad fused qkv + attention configuration");
+static int launch_fused_kv(const BlobView& v, const FusedLaunch& a, hipStream_t st) {
+  return select_qform<true>(v.smode, v.asym, v.s32, v.ndig, "QBits: bad fused qkv + attention configuration",
+                            [&](auto SM, auto AS, auto S3, auto) { return launch_fused_t<SM(), AS(), S3(), KV>(v, a, st); });
 }
 
 int launch_gemv_xq_attn(const XqPtrs& xin, const void* blob, const woq_blob_header& h, unsigned long long* qkv_g,
@@ -185,51 +170,25 @@ int launch_gemv_xq_attn(const XqPtrs& xin, const void* blob, const woq_blob_head
                         void* vcache, int kv_dtype, const int32_t* pos, const float* cs, const float* sn, int heads,
                         int kv_heads, int max_ctx, int window, float* attn_out, const XqPtrs& xq_attn, hipStream_t st,
                         int splits, unsigned long long* part_g) {
+  BlobView v;
+  if (!blob_view(blob, h, v)) return woq::fail("QBits: bad fused qkv + attention configuration");
   FusedLaunch a;
   if (splits < 1) splits = 1;
-  const uint8_t* b = (const uint8_t*)blob;
-  a.q = b + h.off_q;
-  a.scales = b + h.off_scale;
-  a.zp = h.off_zp ? b + h.off_zp : nullptr;
   a.xin = xin;
-  a.K = h.K;
-  a.N = h.N;
-  a.tiles_k = h.Kpad / WOQ_TILE_K;
-  a.n_groups = h.n_groups;
-  a.tpg_shift = 0;
-  if (h.scale_mode == 0 && h.n_groups > 1) {
-    int tpg = h.group / WOQ_TILE_K;
-    while (tpg > 1) {
-      tpg >>= 1;
-      ++a.tpg_shift;
-    }
-  }
-  a.flags = h.scale_type == WOQ_BF16 ? 1 : 0;
+  a.flags = v.sbf16 ? 1 : 0;
   a.eps = eps;
   a.n_ssq = h.K / 16;
   a.ssq_in = ssq_in;
   a.out = qkv_g;
-  const int smode = (int)h.scale_mode;
-  const bool asym = a.zp != nullptr, s32 = h.scale_type == WOQ_F32;
   const int span = fused_attn_span(max_ctx, window, splits);
   const int spw = attn_dec_spw(span);
   if (splits > 1 && part_g == nullptr) return woq::fail("QBits: context slices in the fused launch need the partial granules");
   a.fa = FusedAttnArgs{seq, layer, status, kcache, vcache, pos, cs, sn, heads, kv_heads, window, spw, attn_out, xq_attn,
                        splits, part_g};
-  const size_t lds_attn = attn_dec_lds_floats(128, span) * 4;
-  size_t lds_gemv = 0;
-  if (smode == 0)
-    lds_gemv = asym ? (s32 ? XqsLds<FUSED_TPW, 1, 0, true, true>::total(4) : XqsLds<FUSED_TPW, 1, 0, true, false>::total(4))
-                    : (s32 ? XqsLds<FUSED_TPW, 1, 0, false, true>::total(4) : XqsLds<FUSED_TPW, 1, 0, false, false>::total(4));
-  else
-    lds_gemv = asym ? (s32 ? XqsLds<FUSED_TPW, 1, 1, true, true>::total(4) : XqsLds<FUSED_TPW, 1, 1, true, false>::total(4))
-                    : (s32 ? XqsLds<FUSED_TPW, 1, 1, false, true>::total(4) : XqsLds<FUSED_TPW, 1, 1, false, false>::total(4));
-  a.lds = std::max(lds_attn, lds_gemv);
-  if (a.lds > 160 * 1024) return woq::fail("QBits: fused qkv + attention launch does not fit LDS");
-  if (kv_dtype == WOQ_F16) return launch_fused_kv<_Float16>(a, smode, asym, s32, st);
-  if (kv_dtype == WOQ_FP8_E4M3) return launch_fused_kv<Fp8>(a, smode, asym, s32, st);
-  return launch_fused_kv<__bf16>(a, smode, asym, s32, st);
+  a.lds_attn = attn_dec_lds_floats(128, span) * 4;
+  if (kv_dtype == WOQ_F16) return launch_fused_kv<_Float16>(v, a, st);
+  if (kv_dtype == WOQ_FP8_E4M3) return launch_fused_kv<Fp8>(v, a, st);
+  return launch_fused_kv<__bf16>(v, a, st);
 }
-
 
 }  // namespace woq

@@ -32,6 +32,7 @@
 #include <cstdlib>
 
 #include "woq_gemv_common.h"
+#include "woq_gemv_launch.h"
 #include "woq_host.h"
 
 namespace woq {
@@ -342,29 +343,25 @@ __global__ __launch_bounds__(TPW == 8 ? 768 : 1024) void gemv_fp8_kernel(
   }
 }
 
+// what a launch carries beside the HI plane's view (BlobView: scales and geometry; the LO plane has the same geometry)
 struct F8Launch {
-  const void *qhi, *qlo, *scales, *x;
-  int tiles_k, K, N, n_groups, tpg_shift, M, ms, lda, ldo, out_dtype, flags, nw, grid;
+  const void *qlo, *x;
+  int M, ms, lda, ldo, out_dtype, flags, nw, grid;
   void* out;
   const float* bias;
   F8Fused fz;
 };
 
 template <int TPW, bool E5M2, bool S32, int SMODE>
-static int launch_fp8_t(const F8Launch& a, hipStream_t st) {
+static int launch_fp8_t(const BlobView& v, const F8Launch& a, hipStream_t st) {
   const size_t lds = f8_lds_bytes(a.M, a.ms, a.nw, TPW, SMODE);
-  auto kern = gemv_fp8_kernel<TPW, E5M2, S32, SMODE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       158 * 1024);  // the kernel also holds 512 B of static LDS (the RMSNorm partials)
-    if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
-    attr_set = true;
-  }
-  const int base = a.tiles_k / a.nw, rem = a.tiles_k % a.nw;
-  hipLaunchKernelGGL(kern, dim3(a.grid), dim3(a.nw * 64), lds, st, (const u32x4*)a.qhi, (const u32x4*)a.qlo, a.scales,
-                     a.x, a.tiles_k, a.K, base, rem, a.n_groups, a.tpg_shift, a.out, a.bias, a.N, a.M, a.ms, a.lda,
-                     a.ldo, a.out_dtype, a.flags, a.fz);
+  constexpr auto kern = gemv_fp8_kernel<TPW, E5M2, S32, SMODE>;
+  // the kernel also holds 512 B of static LDS (the RMSNorm partials)
+  if (const int rc = allow_dynamic_lds<kern>(158 * 1024)) return rc;
+  const int base = v.tiles_k / a.nw, rem = v.tiles_k % a.nw;
+  hipLaunchKernelGGL(kern, dim3(a.grid), dim3(a.nw * 64), lds, st, v.q, (const u32x4*)a.qlo, v.scales, a.x, v.tiles_k,
+                     v.K, base, rem, v.n_groups, v.tpg_shift, a.out, a.bias, v.N, a.M, a.ms, a.lda, a.ldo, a.out_dtype,
+                     a.flags, a.fz);
   return 0;
 }
 
@@ -388,49 +385,39 @@ bool gemv_fp8_mfma_supported(const void* act, int act_dtype, int lda, const woq_
 int launch_gemv_fp8_mfma(const void* act, int act_dtype, int lda, int M, const void* hi_blob, const woq_blob_header& hi,
                          const void* lo_q, uint32_t fp8_type, const float* bias, void* out, int out_dtype, int ldo,
                          hipStream_t st, const float* norm_w, float eps, const float* residual, int ld_res) {
+  BlobView v;  // tpg_shift 0: one tile per group (or one group), gemv_fp8_mfma_supported
+  if (!blob_view(hi_blob, hi, v)) return woq::fail("QBits: shape not covered by the fp8 decode GEMV");
   F8Launch a;
   if (norm_w != nullptr && act_dtype != WOQ_F32) return woq::fail("QBits: the fp8 GEMV's fused RMSNorm takes fp32 rows");
   a.fz = F8Fused{norm_w, eps, residual, ld_res};
-  const uint8_t* b = (const uint8_t*)hi_blob;
-  a.qhi = b + hi.off_q;
   a.qlo = lo_q;
-  a.scales = b + hi.off_scale;
   a.x = act;
-  a.tiles_k = hi.Kpad / WOQ_TILE_K;
-  a.K = hi.K;
-  a.N = hi.N;
-  a.n_groups = hi.n_groups;
-  a.tpg_shift = 0;  // one tile per group (or one group): gemv_fp8_mfma_supported
   a.M = M;
   a.lda = lda;
   a.ldo = ldo;
   a.out = out;
   a.out_dtype = out_dtype;
   a.bias = bias;
-  a.flags = (hi.scale_type == WOQ_BF16 ? 1 : 0) | (act_dtype == WOQ_F16 ? 4 : (act_dtype == WOQ_BF16 ? 8 : 0));
+  a.flags = (v.sbf16 ? 1 : 0) | (act_dtype == WOQ_F16 ? 4 : (act_dtype == WOQ_BF16 ? 8 : 0));
   int tpw;
-  if (M < 1 || M > F8_MAXM || !fp8_geometry(a.tiles_k, a.nw, tpw))
+  if (M < 1 || M > F8_MAXM || !fp8_geometry(v.tiles_k, a.nw, tpw))
     return woq::fail("QBits: shape not covered by the fp8 decode GEMV");
   a.ms = std::min(M, F8_SETM);
-  const int sm = (int)hi.scale_mode;
-  if (f8_lds_bytes(M, a.ms, a.nw, tpw, sm) > 150 * 1024) a.ms = 1;  // long K: one activation row per set
-  if (f8_lds_bytes(M, a.ms, a.nw, tpw, sm) > 150 * 1024) return woq::fail("QBits: activation rows do not fit LDS");
-  a.grid = hi.Npad / WOQ_TILE_N;
-  const bool e5m2 = fp8_type == WOQ_W_FP8_E5M2, s32 = hi.scale_type == WOQ_F32;
-const int smode = (int)hi.scale_mode;
-#define WOQ_F8_CASE(T, E, S)                                                     \
-  if (tpw == T && e5m2 == E && s32 == S)                                         \
-    return smode == 0 ? launch_fp8_t<T, E, S, 0>(a, st) : launch_fp8_t<T, E, S, 1>(a, st);
-  WOQ_F8_CASE(4, false, false)
-  WOQ_F8_CASE(4, false, true)
-  WOQ_F8_CASE(4, true, false)
-  WOQ_F8_CASE(4, true, true)
-  WOQ_F8_CASE(8, false, false)
-  WOQ_F8_CASE(8, false, true)
-  WOQ_F8_CASE(8, true, false)
-  WOQ_F8_CASE(8, true, true)
-#undef WOQ_F8_CASE
-  return woq::fail("QBits: bad fp8 GEMV configuration");
+  if (f8_lds_bytes(M, a.ms, a.nw, tpw, v.smode) > 150 * 1024) a.ms = 1;  // long K: one activation row per set
+  if (f8_lds_bytes(M, a.ms, a.nw, tpw, v.smode) > 150 * 1024) return woq::fail("QBits: activation rows do not fit LDS");
+  a.grid = v.tiles_n;
+  const bool e5m2 = fp8_type == WOQ_W_FP8_E5M2;
+  // the planes are symmetric int4-layout tiles; on top of the scale form: tiles per wave and the code type
+  const char* bad = "QBits: bad fp8 GEMV configuration";
+  return select_qform<true>(v.smode, v.asym, v.s32, v.ndig, bad, [&](auto SM, auto AS, auto S3, auto) {
+    if constexpr (AS()) {
+      return woq::fail(bad);
+    } else {
+      if (tpw == 4)
+        return e5m2 ? launch_fp8_t<4, true, S3(), SM()>(v, a, st) : launch_fp8_t<4, false, S3(), SM()>(v, a, st);
+      return e5m2 ? launch_fp8_t<8, true, S3(), SM()>(v, a, st) : launch_fp8_t<8, false, S3(), SM()>(v, a, st);
+    }
+  });
 }
 
 // act[p * 16 + i] = SiLU(gu[(2 p) * 16 + i]) * gu[(2 p + 1) * 16 + i]: the fused gate/up projection's 16-column tiles

@@ -48,6 +48,7 @@
 #include <algorithm>
 
 #include "woq_gemv_common.h"
+#include "woq_gemv_launch.h"
 #include "woq_host.h"
 
 namespace woq {
@@ -581,90 +582,49 @@ __global__ __launch_bounds__(CB * TPW > 8 ? 512 : (SMODE == 1 ? 768 : 1024)) voi
   }
 }
 
+// what a launch of this kernel carries beside the blob (BlobView)
 struct TileLaunch {
-  const void* q;
-  const void* scales;
-  const void* zp;
   const void* x;
   const float* norm_w;
-  int tiles_k, K, N, n_groups, tpg_shift, M, lda, ldo, ld_res, out_dtype, flags;
+  int M, lda, ldo, ld_res, out_dtype, flags;
   void* out;
   const float* bias;
   const float* residual;
   float eps;
   int nw, grid;
   int kt_begin, kt_count;  // K tiles [kt_begin, kt_begin + kt_count) of the blob covered by this launch
-  LutArgs lut;             // table weight types (ndig > 0)
-  int ndig;
-  const int32_t* shuffle;  // GPTQ act-order: activation index of every weight row (batch 1, int4), or null
 };
 
 template <int TPW, int CB, int SMODE, bool ASYM, bool S32, bool M1, int NDIG, bool SHUF = false>
-static int launch_tile_t(const TileLaunch& a, hipStream_t st) {
+static int launch_tile_t(const BlobView& v, const TileLaunch& a, hipStream_t st) {
   // act-order form: + the whole activation vector as fp32 behind the regular regions
-  const size_t lds = SHUF ? ((tile_lds_bytes(a.M, a.nw, TPW, CB) + 15) & ~(size_t)15) + (size_t)a.K * 4
+  const size_t lds = SHUF ? ((tile_lds_bytes(a.M, a.nw, TPW, CB) + 15) & ~(size_t)15) + (size_t)v.K * 4
                           : tile_lds_bytes(a.M, a.nw, TPW, CB);
   if (lds > 160 * 1024) return woq::fail("QBits: activation rows do not fit LDS");
-  auto kern = gemv_tile_kernel<TPW, CB, SMODE, ASYM, S32, M1, NDIG, SHUF>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
-    attr_set = true;
-  }
+  constexpr auto kern = gemv_tile_kernel<TPW, CB, SMODE, ASYM, S32, M1, NDIG, SHUF>;
+  if (const int rc = allow_dynamic_lds<kern>(160 * 1024)) return rc;
   const int base = a.kt_count / a.nw, rem = a.kt_count % a.nw;
-  hipLaunchKernelGGL(kern, dim3(a.grid), dim3(a.nw * 64), lds, st, (const u32x4*)a.q, a.scales, a.x, a.norm_w,
-                     a.tiles_k, a.K, base, rem, a.n_groups, a.tpg_shift, (const uint8_t*)a.zp, a.out, a.bias,
-                     a.residual, a.eps, a.N, a.M, a.lda, a.ldo, a.ld_res, a.out_dtype, a.flags, a.kt_begin, a.lut,
-                     a.shuffle);
+  hipLaunchKernelGGL(kern, dim3(a.grid), dim3(a.nw * 64), lds, st, v.q, v.scales, a.x, a.norm_w, v.tiles_k, v.K, base,
+                     rem, v.n_groups, v.tpg_shift, v.zp, a.out, a.bias, a.residual, a.eps, v.N, a.M, a.lda, a.ldo,
+                     a.ld_res, a.out_dtype, a.flags, a.kt_begin, v.lut, v.shuffle);
   return 0;
 }
 
 template <int TPW, int CB>
-static int launch_tile_sm(const TileLaunch& a, int smode, bool asym, bool s32, hipStream_t st) {
-  if (a.shuffle != nullptr) {  // act-order blobs: batch 1, int4 (gemv_tile_max_rows admits nothing else)
-    if (a.M != 1 || a.ndig != 0) return woq::fail("QBits: the act-order tile GEMV takes one int4 row");
-#define WOQ_TILE_SHUF(SM, AS, S3) \
-  if (smode == SM && asym == AS && s32 == S3) return launch_tile_t<TPW, CB, SM, AS, S3, true, 0, true>(a, st);
-    WOQ_TILE_SHUF(0, false, false)
-    WOQ_TILE_SHUF(0, false, true)
-    WOQ_TILE_SHUF(0, true, false)
-    WOQ_TILE_SHUF(0, true, true)
-    WOQ_TILE_SHUF(1, false, false)
-    WOQ_TILE_SHUF(1, false, true)
-    WOQ_TILE_SHUF(1, true, false)
-    WOQ_TILE_SHUF(1, true, true)
-#undef WOQ_TILE_SHUF
-    return woq::fail("QBits: bad tile GEMV configuration");
+static int launch_tile_sm(const BlobView& v, const TileLaunch& a, hipStream_t st) {
+  const char* bad = "QBits: bad tile GEMV configuration";
+  if (v.shuffle != nullptr) {  // act-order blobs: batch 1, int4 (gemv_tile_max_rows admits nothing else)
+    if (a.M != 1 || v.ndig != 0) return woq::fail("QBits: the act-order tile GEMV takes one int4 row");
+    return select_qform<true>(v.smode, v.asym, v.s32, 0, bad, [&](auto SM, auto AS, auto S3, auto) {
+      return launch_tile_t<TPW, CB, SM(), AS(), S3(), true, 0, true>(v, a, st);
+    });
   }
-#define WOQ_TILE_CASE(SM, AS, S3, ND)                                                   \
-  if (smode == SM && asym == AS && s32 == S3 && a.ndig == ND)                           \
-    return a.M == 1 ? launch_tile_t<TPW, CB, SM, AS, S3, true, ND>(a, st)               \
-                    : launch_tile_t<TPW, CB, SM, AS, S3, false, ND>(a, st);
-  WOQ_TILE_CASE(0, false, false, 0)
-  WOQ_TILE_CASE(0, false, true, 0)
-  WOQ_TILE_CASE(0, true, false, 0)
-  WOQ_TILE_CASE(0, true, true, 0)
-  WOQ_TILE_CASE(1, false, false, 0)
-  WOQ_TILE_CASE(1, false, true, 0)
-  WOQ_TILE_CASE(1, true, false, 0)
-  WOQ_TILE_CASE(1, true, true, 0)
-  // 4-bit table types: symmetric only; one digit plane (fp4_e2m1), two (bitsandbytes fp4; nf4 at reduced-precision
-  // compute) or three (nf4 at compute fp32)
-  WOQ_TILE_CASE(0, false, false, 1)
-  WOQ_TILE_CASE(0, false, true, 1)
-  WOQ_TILE_CASE(1, false, false, 1)
-  WOQ_TILE_CASE(1, false, true, 1)
-  WOQ_TILE_CASE(0, false, false, 2)
-  WOQ_TILE_CASE(0, false, true, 2)
-  WOQ_TILE_CASE(1, false, false, 2)
-  WOQ_TILE_CASE(1, false, true, 2)
-  WOQ_TILE_CASE(0, false, false, 3)
-  WOQ_TILE_CASE(0, false, true, 3)
-  WOQ_TILE_CASE(1, false, false, 3)
-  WOQ_TILE_CASE(1, false, true, 3)
-#undef WOQ_TILE_CASE
-  return woq::fail("QBits: bad tile GEMV configuration");
+  // 4-bit table types: one digit plane (fp4_e2m1), two (bitsandbytes fp4; nf4 at reduced-precision compute) or three
+  // (nf4 at compute fp32)
+  return select_qform(v.smode, v.asym, v.s32, v.ndig, bad, [&](auto SM, auto AS, auto S3, auto ND) {
+    return a.M == 1 ? launch_tile_t<TPW, CB, SM(), AS(), S3(), true, ND()>(v, a, st)
+                    : launch_tile_t<TPW, CB, SM(), AS(), S3(), false, ND()>(v, a, st);
+  });
 }
 
 // Digit planes of a table weight type (woq_gemv_common.h): v = round(table[c] * S) = d0 + 2^8 d1 + 2^16 d2, balanced
@@ -693,19 +653,16 @@ int lut_args_for(uint32_t weight_type, uint32_t compute_type, LutArgs& L) {
   return ndig;
 }
 
-int gemv_tile_k_chunks(int tiles_k, int cb, int smode, bool chainable) {
-  int nw, tpw;
-  if (gemv_tile_geometry(tiles_k, cb, smode, nw, tpw)) return 1;
-  if (!chainable) return 0;
-  for (int s = 2; s <= 8; ++s)
-    if (gemv_tile_geometry((tiles_k + s - 1) / s, cb, smode, nw, tpw)) return s;
-  return 0;
-}
-
 bool gemv_tile_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw) {
   tpw = (tiles_k > 16 && !(cb == 2 && smode == 1)) ? 8 : 4;  // per-32 scales x 2 column tiles: register budget
   nw = (tiles_k + tpw - 1) / tpw;
   return nw <= (cb * tpw > 8 ? 8 : (smode == 1 ? 12 : 16));  // the kernel's __launch_bounds__
+}
+
+KPlan gemv_tile_k_plan(const woq_blob_header& h, const float* norm_w, int epi, int out_dtype) {
+  const int cb = epi == 1 ? 2 : 1, smode = (int)h.scale_mode;
+  return plan_k_ranges(h.Kpad / WOQ_TILE_K, epi == 0 && !norm_w && out_dtype == WOQ_F32,
+                       [=](int tiles, int& nw, int& tpw) { return gemv_tile_geometry(tiles, cb, smode, nw, tpw); });
 }
 
 int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_header& h, const float* norm_w,
@@ -716,42 +673,24 @@ int gemv_tile_max_rows(const void* act, int act_dtype, int lda, const woq_blob_h
   if ((h.weight_type != WOQ_W_INT4_CLIP && !table) || (h.K & 3) != 0 || (lda & 3) != 0 ||
       (((uintptr_t)act) & (act_dtype == WOQ_F32 ? 15 : 7)) != 0 || (((uintptr_t)norm_w) & 15) != 0)
     return 0;
-  const int tiles_k = h.Kpad / WOQ_TILE_K;
+  const KPlan plan = gemv_tile_k_plan(h, norm_w, epi, out_dtype);
+  if (plan.chunks == 0) return 0;
+  if (h.off_shuffle != 0 && plan.chunks != 1) return 0;  // the act-order form copies the whole vector per launch: one K range
+  BlobView v;
+  if (!blob_view(nullptr, h, v)) return 0;
   const int cb = epi == 1 ? 2 : 1;
-  int nw, tpw;
-  const int chunks = gemv_tile_k_chunks(tiles_k, cb, (int)h.scale_mode, epi == 0 && !norm_w && out_dtype == WOQ_F32);
-  if (chunks == 0 || !gemv_tile_geometry((tiles_k + chunks - 1) / chunks, cb, (int)h.scale_mode, nw, tpw)) return 0;
-  if (h.off_shuffle != 0 && chunks != 1) return 0;  // the act-order form copies the whole vector per launch: one K range
-  if (h.scale_mode == 0 && h.n_groups > 1) {
-    const int tpg = h.group / WOQ_TILE_K;
-    if (tpg < 1 || (tpg & (tpg - 1)) != 0) return 0;  // tiles per group must be a power of two
-  }
   int m = h.off_shuffle != 0 ? 1 : TMAXM;
   const size_t extra = h.off_shuffle != 0 ? (size_t)h.K * 4 + 16 : 0;  // the act-order form's copy of the vector
-  while (m > 0 && tile_lds_bytes(m, nw, tpw, cb) + extra > 150 * 1024) --m;
+  while (m > 0 && tile_lds_bytes(m, plan.nw[0], plan.tpw[0], cb) + extra > 150 * 1024) --m;
   return m;
 }
 
 int launch_gemv_tile(const void* act, int act_dtype, int lda, int M, const void* blob, const woq_blob_header& h,
                      const float* bias, void* out, int out_dtype, int ldo, const float* norm_w, float eps,
                      const float* residual, int ld_res, int epi, hipStream_t st) {
+  BlobView v;
+  if (!blob_view(blob, h, v)) return woq::fail("QBits: shape not covered by the tile GEMV");
   TileLaunch a;
-  const uint8_t* b = (const uint8_t*)blob;
-  a.q = b + h.off_q;
-  a.scales = b + h.off_scale;
-  a.zp = h.off_zp ? b + h.off_zp : nullptr;
-  a.K = h.K;
-  a.N = h.N;
-  a.tiles_k = h.Kpad / WOQ_TILE_K;
-  a.n_groups = h.n_groups;
-  a.tpg_shift = 0;
-  if (h.scale_mode == 0 && h.n_groups > 1) {
-    int tpg = h.group / WOQ_TILE_K;
-    while (tpg > 1) {
-      tpg >>= 1;
-      ++a.tpg_shift;
-    }
-  }
   a.x = act;
   a.lda = lda;
   a.M = M;
@@ -763,39 +702,23 @@ int launch_gemv_tile(const void* act, int act_dtype, int lda, int M, const void*
   a.norm_w = norm_w;
   a.eps = eps;
   a.residual = residual;
-  a.flags = (h.scale_type == WOQ_BF16 ? 1 : 0) | (epi == 1 ? 2 : 0) |
-            (act_dtype == WOQ_F16 ? 4 : (act_dtype == WOQ_BF16 ? 8 : 0));
-  a.ndig = lut_args_for(h.weight_type, h.compute_type, a.lut);
-  a.shuffle = h.off_shuffle ? (const int32_t*)(b + h.off_shuffle) : nullptr;
-  const int tiles_n = h.Npad / WOQ_TILE_N;
+  a.flags = (v.sbf16 ? 1 : 0) | (epi == 1 ? 2 : 0) | (act_dtype == WOQ_F16 ? 4 : (act_dtype == WOQ_BF16 ? 8 : 0));
   const int cb = epi == 1 ? 2 : 1;
-  if (epi == 1 && (tiles_n & 1)) return woq::fail("QBits: fused gate/up weight needs an even number of column tiles");
-  const int smode = (int)h.scale_mode;
-  const bool asym = a.zp != nullptr, s32 = h.scale_type == WOQ_F32;
-  const int chunks = gemv_tile_k_chunks(a.tiles_k, cb, smode, epi == 0 && !norm_w && out_dtype == WOQ_F32);
-  if (M > TMAXM || chunks == 0)
-    return woq::fail("QBits: shape not covered by the tile GEMV");
-  a.grid = tiles_n / cb;
-  const int per = (a.tiles_k + chunks - 1) / chunks;
-  for (int c = 0; c < chunks; ++c) {
-    a.kt_begin = c * per;
-    a.kt_count = std::min(per, a.tiles_k - a.kt_begin);
-    if (a.kt_count <= 0) break;
-    int tpw;
-    if (!gemv_tile_geometry(a.kt_count, cb, smode, a.nw, tpw)) return woq::fail("QBits: shape not covered by the tile GEMV");
+  if (epi == 1 && (v.tiles_n & 1)) return woq::fail("QBits: fused gate/up weight needs an even number of column tiles");
+  const KPlan plan = gemv_tile_k_plan(h, norm_w, epi, out_dtype);
+  if (M > TMAXM || plan.chunks == 0) return woq::fail("QBits: shape not covered by the tile GEMV");
+  a.grid = v.tiles_n / cb;
+  return for_each_k_chunk(plan, [&](int c, int kt_begin, int kt_count, bool) {
+    a.kt_begin = kt_begin;
+    a.kt_count = kt_count;
+    a.nw = plan.nw[c];
     if (c > 0) {  // add onto the previous chunk's output
       a.bias = nullptr;
       a.residual = (const float*)out;
       a.ld_res = ldo;
     }
-    int rc;
-    if (cb == 2)
-      rc = tpw == 4 ? launch_tile_sm<4, 2>(a, smode, asym, s32, st) : launch_tile_sm<8, 2>(a, smode, asym, s32, st);
-    else
-      rc = tpw == 4 ? launch_tile_sm<4, 1>(a, smode, asym, s32, st) : launch_tile_sm<8, 1>(a, smode, asym, s32, st);
-    if (rc) return rc;
-  }
-  return 0;
+    return select_tpw_cb(plan.tpw[c], cb, [&](auto TPW, auto CB) { return launch_tile_sm<TPW(), CB()>(v, a, st); });
+  });
 }
 
 }  // namespace woq

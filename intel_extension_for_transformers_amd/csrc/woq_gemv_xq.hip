@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "woq_gemv_common.h"
+#include "woq_gemv_launch.h"
 #ifdef WOQ_XQS_STAMPS  // measurement build only (tools/xqs_stamps.py): per-(workgroup, wave) wall-clock stamps of the stages
 __device__ unsigned long long* g_xqs_probe = nullptr;
 #endif
@@ -22,12 +23,10 @@ extern "C" __attribute__((visibility("default"))) int woq_xqs_set_probe(void* bu
 
 namespace woq {
 
+// what a launch of the XQ kernel carries beside the blob (BlobView)
 struct XqLaunch {
-  const void* q;
-  const void* scales;
-  const void* zp;
   XqPtrs xin;
-  int tiles_k, K, N, n_groups, tpg_shift, flags;
+  int flags;
   float* out;
   const float* bias;
   const float* residual;
@@ -39,8 +38,6 @@ struct XqLaunch {
   float* ssq_out;
   const CommDev* tp;  // tensor parallel: push the outputs (partial sums) into the peers' inboxes from the epilogue
   int nw, grid, kt_begin, kt_count;
-  LutArgs lut;  // 4-bit table weight types (ndig > 0)
-  int ndig;
 };
 
 // window depth by tiles per wave (profiles/r03c_xq_probe.txt)
@@ -49,56 +46,21 @@ struct XqLaunch {
 constexpr int XQ_WINDOW_DEPTH = 6;
 
 template <int TPW, int CB, int SMODE, bool ASYM, bool S32, int NDIG>
-static int launch_xq_t(const XqLaunch& a, hipStream_t st) {
+static int launch_xq_t(const BlobView& v, const XqLaunch& a, hipStream_t st) {
   typedef XqsLds<TPW, CB, SMODE, ASYM, S32> L;
   const size_t lds = L::total(a.nw);
   if (lds > 160 * 1024) return woq::fail("QBits: XQ GEMV geometry does not fit LDS");
-  auto kern = gemv_xqs_kernel<TPW, CB, (TPW < XQ_WINDOW_DEPTH ? TPW : XQ_WINDOW_DEPTH), SMODE, ASYM, S32, NDIG>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
-    attr_set = true;
-  }
+  constexpr auto kern = gemv_xqs_kernel<TPW, CB, (TPW < XQ_WINDOW_DEPTH ? TPW : XQ_WINDOW_DEPTH), SMODE, ASYM, S32, NDIG>;
+  if (const int rc = allow_dynamic_lds<kern>(160 * 1024)) return rc;
   const int base = a.kt_count / a.nw, rem = a.kt_count % a.nw;
   XqsLate late;
-  late.zp = (const uint8_t*)a.zp, late.xsx = a.xin.sx, late.out = a.out, late.bias = a.bias, late.residual = a.residual;
+  late.zp = v.zp, late.xsx = a.xin.sx, late.out = a.out, late.bias = a.bias, late.residual = a.residual;
   late.ssq_in = a.ssq_in, late.next_norm_w = a.next_norm_w, late.ssq_out = a.ssq_out, late.tp = a.tp;
-  late.tag_seq = nullptr, late.tag_layer = 0, late.xo = a.xo, late.eps = a.eps, late.N = a.N, late.K = a.K;
-  late.n_ssq = a.n_ssq, late.lut = a.lut;
-  hipLaunchKernelGGL(kern, dim3(a.grid), dim3(a.nw * 64), lds, st, (const u32x4*)a.q, a.scales, a.xin.limbs, a.xin.u,
-                     a.tiles_k, a.kt_begin, base, rem, a.n_groups, a.tpg_shift | (a.flags << 8) | (a.nw << 16), late);
+  late.tag_seq = nullptr, late.tag_layer = 0, late.xo = a.xo, late.eps = a.eps, late.N = v.N, late.K = v.K;
+  late.n_ssq = a.n_ssq, late.lut = v.lut;
+  hipLaunchKernelGGL(kern, dim3(a.grid), dim3(a.nw * 64), lds, st, v.q, v.scales, a.xin.limbs, a.xin.u, v.tiles_k,
+                     a.kt_begin, base, rem, v.n_groups, v.tpg_shift | (a.flags << 8) | (a.nw << 16), late);
   return 0;
-}
-
-template <int TPW, int CB>
-static int launch_xq_sm(const XqLaunch& a, int smode, bool asym, bool s32, hipStream_t st) {
-#define WOQ_XQ_CASE(SM, AS, S3, ND) \
-  if (smode == SM && asym == AS && s32 == S3 && a.ndig == ND) return launch_xq_t<TPW, CB, SM, AS, S3, ND>(a, st);
-  WOQ_XQ_CASE(0, false, false, 0)
-  WOQ_XQ_CASE(0, false, true, 0)
-  WOQ_XQ_CASE(0, true, false, 0)
-  WOQ_XQ_CASE(0, true, true, 0)
-  WOQ_XQ_CASE(1, false, false, 0)
-  WOQ_XQ_CASE(1, false, true, 0)
-  WOQ_XQ_CASE(1, true, false, 0)
-  WOQ_XQ_CASE(1, true, true, 0)
-  // 4-bit table types (nf4 / fp4): symmetric; one digit plane (fp4_e2m1), two (bitsandbytes fp4, nf4 at reduced-
-  // precision compute) or three (nf4 at compute fp32)
-  WOQ_XQ_CASE(0, false, false, 1)
-  WOQ_XQ_CASE(0, false, true, 1)
-  WOQ_XQ_CASE(1, false, false, 1)
-  WOQ_XQ_CASE(1, false, true, 1)
-  WOQ_XQ_CASE(0, false, false, 2)
-  WOQ_XQ_CASE(0, false, true, 2)
-  WOQ_XQ_CASE(1, false, false, 2)
-  WOQ_XQ_CASE(1, false, true, 2)
-  WOQ_XQ_CASE(0, false, false, 3)
-  WOQ_XQ_CASE(0, false, true, 3)
-  WOQ_XQ_CASE(1, false, false, 3)
-  WOQ_XQ_CASE(1, false, true, 3)
-#undef WOQ_XQ_CASE
-  return woq::fail("QBits: bad XQ GEMV configuration");
 }
 
 // Geometry: nw waves x tpw tiles cover a K range of tiles_k tiles. Measured per projection of the Llama-2-7B layer
@@ -111,89 +73,67 @@ static bool xq_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw, int n
   nw = (tiles_k + tpw - 1) / tpw;
   return nw >= 1 && nw <= ((cb * tpw > 8 || wide) ? 8 : 16);  // the kernel's __launch_bounds__
 }
-// K ranges one launch cannot hold run as chained launches; number of chunks, 0 = not covered
-static int xq_k_chunks(int tiles_k, int cb, int smode, bool chainable, int ndig = 0) {
-  int nw, tpw;
-  if (xq_geometry(tiles_k, cb, smode, nw, tpw, ndig)) return 1;
-  if (!chainable) return 0;
-  for (int s = 2; s <= 8; ++s)
-    if (xq_geometry((tiles_k + s - 1) / s, cb, smode, nw, tpw, ndig)) return s;
-  return 0;
+// the chained launches of a batch-1 projection: walked by the GEMV and by its measurement twins alike
+static KPlan xq_k_plan(const BlobView& v, int epi) {
+  const int cb = epi == 1 ? 2 : 1;
+  return plan_k_ranges(v.tiles_k, epi == 0, [&](int tiles, int& nw, int& tpw) {
+    return xq_geometry(tiles, cb, v.smode, nw, tpw, v.ndig);
+  });
 }
 
-bool gemv_xq_supported(const woq_blob_header& h, int epi) {
+// view and K-range plan of a blob the XQ kernel takes as a batch-1 projection; false = it does not
+static bool xq_view(const void* blob, const woq_blob_header& h, int epi, BlobView& v, KPlan& plan) {
   const bool table = is_table_type(h.weight_type) && h.off_zp == 0;
   if ((h.weight_type != WOQ_W_INT4_CLIP && !table) || h.off_shuffle != 0 || (h.K % WOQ_TILE_K) != 0 || h.K != h.Kpad)
     return false;
-  const int tiles_k = h.Kpad / WOQ_TILE_K, cb = epi == 1 ? 2 : 1;
-  if (epi == 1 && ((h.Npad / WOQ_TILE_N) & 1)) return false;
-  if (h.scale_mode == 0 && h.n_groups > 1) {
-    const int tpg = h.group / WOQ_TILE_K;
-    if (tpg < 1 || (tpg & (tpg - 1)) != 0) return false;
-  }
-  LutArgs lut;
-  return xq_k_chunks(tiles_k, cb, (int)h.scale_mode, epi == 0, lut_args_for(h.weight_type, h.compute_type, lut)) > 0;
+  if (!blob_view(blob, h, v) || (epi == 1 && (v.tiles_n & 1))) return false;
+  plan = xq_k_plan(v, epi);
+  return plan.chunks > 0;
+}
+
+bool gemv_xq_supported(const woq_blob_header& h, int epi) {
+  BlobView v;
+  KPlan plan;
+  return xq_view(nullptr, h, epi, v, plan);
 }
 
 int launch_gemv_xq(const XqPtrs& xin, const void* blob, const woq_blob_header& h, const float* bias, float* out,
                    const float* ssq_in, float eps, const float* residual, int epi, const XqPtrs& xo,
                    const float* next_norm_w, float* ssq_out, hipStream_t st, const CommDev* tp) {
-  if (!gemv_xq_supported(h, epi)) return woq::fail("QBits: shape not covered by the XQ GEMV");
+  BlobView v;
+  KPlan plan;
+  if (!xq_view(blob, h, epi, v, plan)) return woq::fail("QBits: shape not covered by the XQ GEMV");
   XqLaunch a;
-  const uint8_t* b = (const uint8_t*)blob;
-  a.q = b + h.off_q;
-  a.scales = b + h.off_scale;
-  a.zp = h.off_zp ? b + h.off_zp : nullptr;
   a.xin = xin;
-  a.K = h.K;
-  a.N = h.N;
-  a.tiles_k = h.Kpad / WOQ_TILE_K;
-  a.n_groups = h.n_groups;
-  a.tpg_shift = 0;
-  if (h.scale_mode == 0 && h.n_groups > 1) {
-    int tpg = h.group / WOQ_TILE_K;
-    while (tpg > 1) {
-      tpg >>= 1;
-      ++a.tpg_shift;
-    }
-  }
-  a.flags = (h.scale_type == WOQ_BF16 ? 1 : 0) | (epi == 1 ? 2 : 0);
-  a.ndig = lut_args_for(h.weight_type, h.compute_type, a.lut);
+  a.flags = (v.sbf16 ? 1 : 0) | (epi == 1 ? 2 : 0);
   a.eps = eps;
   a.n_ssq = h.K / 16;
   if (ssq_in != nullptr && a.n_ssq > 1024) return woq::fail("QBits: RMSNorm partials beyond K = 16384");
   a.next_norm_w = next_norm_w;
   a.ssq_out = ssq_out;
-  const int tiles_n = h.Npad / WOQ_TILE_N, cb = epi == 1 ? 2 : 1;
-  const int smode = (int)h.scale_mode;
-  const bool asym = a.zp != nullptr, s32 = h.scale_type == WOQ_F32;
-  const int chunks = xq_k_chunks(a.tiles_k, cb, smode, epi == 0, a.ndig);
-  if (chunks > 1 && (ssq_in != nullptr || out == nullptr))
+  const int cb = epi == 1 ? 2 : 1;
+  if (plan.chunks > 1 && (ssq_in != nullptr || out == nullptr))
     return woq::fail("QBits: a K range split over chained launches takes no norm and needs an fp32 output");
-  a.grid = tiles_n / cb;
-  const int per = (a.tiles_k + chunks - 1) / chunks;
-  for (int c = 0; c < chunks; ++c) {
-    a.kt_begin = c * per;
-    a.kt_count = std::min(per, a.tiles_k - a.kt_begin);
-    if (a.kt_count <= 0) break;
-    const bool last = c == chunks - 1 || a.kt_begin + a.kt_count >= a.tiles_k;
-    int tpw;
-    if (!xq_geometry(a.kt_count, cb, smode, a.nw, tpw, a.ndig))
-      return woq::fail("QBits: shape not covered by the XQ GEMV");
-    a.out = out;
+  a.grid = v.tiles_n / cb;
+  a.out = out;
+  a.ssq_in = ssq_in;
+  return for_each_k_chunk(plan, [&](int c, int kt_begin, int kt_count, bool last) {
+    a.kt_begin = kt_begin;
+    a.kt_count = kt_count;
+    a.nw = plan.nw[c];
     a.bias = c == 0 ? bias : nullptr;
     a.residual = c == 0 ? residual : out;  // chunk c > 0 adds onto the previous chunk's output
-    a.ssq_in = ssq_in;
     a.xo = last ? xo : XqPtrs{nullptr, nullptr, nullptr};
     a.tp = last ? tp : nullptr;
-    int rc;
-    if (cb == 2)
-      rc = tpw == 4 ? launch_xq_sm<4, 2>(a, smode, asym, s32, st) : launch_xq_sm<8, 2>(a, smode, asym, s32, st);
-    else
-      rc = tpw == 4 ? launch_xq_sm<4, 1>(a, smode, asym, s32, st) : launch_xq_sm<8, 1>(a, smode, asym, s32, st);
-    if (rc) return rc;
-  }
-  return 0;
+    return select_tpw_cb(plan.tpw[c], cb, [&](auto TPW, auto CB) {
+      // 4-bit table types (nf4 / fp4): one digit plane (fp4_e2m1), two (bitsandbytes fp4, nf4 at reduced-precision
+      // compute) or three (nf4 at compute fp32)
+      return select_qform(v.smode, v.asym, v.s32, v.ndig, "QBits: bad XQ GEMV configuration",
+                          [&](auto SM, auto AS, auto S3, auto ND) {
+                            return launch_xq_t<TPW(), CB(), SM(), AS(), S3(), ND()>(v, a, st);
+                          });
+    });
+  });
 }
 
 // ---- measurement twins (bench.py roofline.ceiling): what THIS launch structure reaches with the arithmetic taken out --
@@ -225,36 +165,24 @@ __global__ void gemv_empty_twin_kernel(unsigned int* __restrict__ sink) {
 }
 
 int launch_gemv_twin(const void* blob, const woq_blob_header& h, int epi, int mode, unsigned int* sink, hipStream_t st) {
-  const int tiles_k = h.Kpad / WOQ_TILE_K, tiles_n = h.Npad / WOQ_TILE_N, cb = epi == 1 ? 2 : 1;
-  LutArgs lut;
-  const int ndig = lut_args_for(h.weight_type, h.compute_type, lut);
-  const int chunks = xq_k_chunks(tiles_k, cb, (int)h.scale_mode, epi == 0, ndig);
-  if (chunks == 0) return woq::fail("QBits: shape not covered by the XQ GEMV");
-  const int per = (tiles_k + chunks - 1) / chunks;
-  const u32x4* q = (const u32x4*)((const uint8_t*)blob + h.off_q);
-  for (int c = 0; c < chunks; ++c) {  // K ranges beyond one launch: the same chained launches as the GEMV
-    const int kt_begin = c * per, kt_count = std::min(per, tiles_k - kt_begin);
-    if (kt_count <= 0) break;
-    int nw, tpw;
-    if (!xq_geometry(kt_count, cb, (int)h.scale_mode, nw, tpw, ndig))
-      return woq::fail("QBits: shape not covered by the XQ GEMV");
-    const int base = kt_count / nw, rem = kt_count % nw;
-    const dim3 grid(tiles_n / cb), block(nw * 64);
+  BlobView v;
+  blob_view(blob, h, v);  // (the twins load tiles and touch no scale: any group size)
+  const int cb = epi == 1 ? 2 : 1;
+  const KPlan plan = xq_k_plan(v, epi);  // K ranges beyond one launch: the same chained launches as the GEMV
+  if (plan.chunks == 0) return woq::fail("QBits: shape not covered by the XQ GEMV");
+  return for_each_k_chunk(plan, [&](int c, int kt_begin, int kt_count, bool) {
+    const int nw = plan.nw[c], base = kt_count / nw, rem = kt_count % nw;
+    const dim3 grid(v.tiles_n / cb), block(nw * 64);
     if (mode == 1) {
       hipLaunchKernelGGL(gemv_empty_twin_kernel, grid, block, 0, st, sink);
-    } else if (cb == 2) {
-      if (tpw == 4)
-        hipLaunchKernelGGL((gemv_stream_twin_kernel<4, 2>), grid, block, 0, st, q, tiles_k, kt_begin, base, rem, sink);
-      else
-        hipLaunchKernelGGL((gemv_stream_twin_kernel<8, 2>), grid, block, 0, st, q, tiles_k, kt_begin, base, rem, sink);
-    } else {
-      if (tpw == 4)
-        hipLaunchKernelGGL((gemv_stream_twin_kernel<4, 1>), grid, block, 0, st, q, tiles_k, kt_begin, base, rem, sink);
-      else
-        hipLaunchKernelGGL((gemv_stream_twin_kernel<8, 1>), grid, block, 0, st, q, tiles_k, kt_begin, base, rem, sink);
+      return 0;
     }
-  }
-  return 0;
+    return select_tpw_cb(plan.tpw[c], cb, [&](auto TPW, auto CB) {
+      hipLaunchKernelGGL((gemv_stream_twin_kernel<TPW(), CB()>), grid, block, 0, st, v.q, v.tiles_k, kt_begin, base, rem,
+                         sink);
+      return 0;
+    });
+  });
 }
 
 // ---- standalone conversion: fp32 vector (optionally times a norm weight) -> XQ, one block per 16 threads ----------

@@ -9,13 +9,14 @@ namespace woq {
 struct AttnA2A;    // woq_attn_merge.h
 struct AttnMerge;  // woq_attn_merge.h
 struct LutArgs;    // woq_gemv_common.h
+struct KPlan;      // woq_gemv_launch.h
 
 // ---- woq_gemv.hip: small-M dispatch ------------------------------------------------------------------------------
 // Shared by woq_linear and the decode engine: rows in chunks through the i8 tile kernel when the call qualifies,
-// through the generic kernel otherwise. `nt` is reserved (weight loads are always non-temporal).
+// through the generic kernel otherwise.
 int launch_gemv_from_header(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
                             const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w,
-                            float eps, const float* residual, int ld_res, int epi, int nt, hipStream_t st);
+                            float eps, const float* residual, int ld_res, int epi, hipStream_t st);
 // fp8 weights at decode row counts: the fp8-MFMA kernel (woq_gemv_fp8.hip: code bytes straight into the matrix cores,
 // activations as base-16 digits; round 4) where it takes the call, rows in chunks of 8; otherwise (per-32 / per-64 /
 // per-256 scales, g_idx, misaligned rows, K beyond 8192) the lookup kernel reading both nibble planes, rows in chunks of GEN_MAXM.
@@ -40,9 +41,9 @@ int lut_args_for(uint32_t weight_type, uint32_t compute_type, LutArgs& L);
 // geometry pick: nw waves x tpw tiles cover tiles_k (8 tiles = 8 KiB per wave per column tile; 4 for short K so
 // that a workgroup still has a few waves). Returns false when this kernel does not take the shape (K > 16384).
 bool gemv_tile_geometry(int tiles_k, int cb, int smode, int& nw, int& tpw);
-// K ranges one launch cannot hold are split into equal chunks run as chained launches (chunk i + 1 adds onto chunk
-// i's fp32 output through the residual input): linear epilogues only. Returns the number of chunks, 0 = not covered.
-int gemv_tile_k_chunks(int tiles_k, int cb, int smode, bool chainable);
+// the chained launches of one call (woq_gemv_launch.h KPlan: chunks, tiles per chunk, nw x tpw of every chunk; K ranges
+// one launch cannot hold are split only for linear epilogues — epi 0, no norm, fp32 out); chunks == 0 = not covered
+KPlan gemv_tile_k_plan(const woq_blob_header& h, const float* norm_w, int epi, int out_dtype);
 // largest M the tile kernel takes for this call (LDS budget), 0 if it is not covered: the kernel wants unshuffled
 // activation rows, fp32 and 16-B aligned (what the decode engine feeds it and what the reference's qbits boundary
 // always holds, modules.py:152-154) or fp16 / bf16 and 8-B aligned; anything else goes to the generic kernel in

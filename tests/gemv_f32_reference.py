@@ -43,7 +43,7 @@ test_fp8_weight_types_decode_kernel (measured 2e-6 / 4.6e-6, profiles/r04ah_fp8_
 fp32 adder, so no chain count applies. Its epi 1 form (kernel + silu_mul_tiles_kernel) propagates that bound through
 SiLU * mul like A.
 
-Geometry: `geometry` restates gemv_tile_k_chunks / gemv_tile_geometry and launch_tile_t's balanced slices,
+Geometry: `geometry` restates gemv_tile_k_plan / gemv_tile_geometry and launch_tile_t's balanced slices,
 `fp8_geometry` restates fp8_geometry and launch_fp8_t's, `predict_form` restates the dispatch of launch_gemv_from_header /
 gemv_tile_max_rows and launch_gemv_fp8_engine / gemv_fp8_mfma_supported: (kernel, chained launches, waves, tiles per
 wave) with kernel 0 = generic (1, 4, 0), 1 = tile, 2 = fp8 matrix-core — what `woq_probe_gemv_f32` reports.
@@ -85,7 +85,7 @@ def _tile_one(tiles_k, cb, smode):
 
 def geometry(K, epi=0, smode=0, chainable=False):
     """the tile kernel's chained launches [(first tile, tiles, waves, tiles per wave, [tiles of each wave])]; [] = not
-    covered (gemv_tile_k_chunks returns 0)"""
+    covered (gemv_tile_k_plan: chunks == 0)"""
     tiles_k, cb = (K + 127) // 128, 2 if epi == 1 else 1
     chunks = 1 if _tile_one(tiles_k, cb, smode)[2] else 0
     if chunks == 0 and chainable:

@@ -585,7 +585,7 @@ def test_woq_linear_dispatch_seams(qbits, M, compute):
 @pytest.mark.parametrize("K", [16384, 16512])
 def test_decode_gemv_longest_k(qbits, K):
     """K = 16384 is the longest contraction one tile-kernel launch takes (16 waves x 8 tiles); one tile more runs as two
-    chained tile launches of 65 and 64 tiles (gemv_tile_k_chunks: a linear fp32 call is chainable), the second adding
+    chained tile launches of 65 and 64 tiles (gemv_tile_k_plan: a linear fp32 call is chainable), the second adding
     onto the first's output — the form `woq_probe_gemv_f32` reports for this call, asserted in
     test_gpu_f32_gemv_kernel.py. With a fused norm the same K goes to the generic kernel. Both against the oracle."""
     N, group = 32, 128

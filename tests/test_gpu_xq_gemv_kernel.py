@@ -3,7 +3,7 @@ through `woq_probe_gemv_xq` / `woq_probe_xq_from_f32`, against tests/xq_referenc
 
 Inputs, seed 0: weights RTN-quantised by the oracle from 0.05 * N(0, 1), x ~ N(0, 1) with one element times 30, norm
 weights 1 + 0.1 N(0, 1). N is 16 .. 64: K alone selects the launch geometry, and every case asserts first that its K
-still selects the form it names (`xq_reference.geometry` restates `xq_geometry` / `xq_k_chunks`). The device blob must
+still selects the form it names (`xq_reference.geometry` restates `xq_geometry` / `xq_k_plan`). The device blob must
 equal the oracle's repack byte for byte before anything is multiplied; W_deq is the oracle's dequantise of that repack.
 
 Per case (tolerance terms A, B from the reference alone, printed): |out - R0| <= 4 (A + B), |out - R1| <= 4 A; an XQ output

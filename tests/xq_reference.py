@@ -18,7 +18,7 @@ s2 in [-32, 32]; u = 2^(e - 25); sx = fl32(sum of the block's v); decode = v * u
 A test allows 4 x (A + B) against R0 and 4 x A against R1; the 4 is the margin the project gives its fp32 restatements
 (tests/score_reference.py).
 
-`geometry`: the launch shape `xq_geometry` / `xq_k_chunks` (csrc/woq_gemv_xq.hip) pick, restated so that a test can say
+`geometry`: the launch shape `xq_geometry` / `xq_k_plan` (csrc/woq_gemv_xq.hip) pick, restated so that a test can say
 which form its K selects.
 
 lm_head: `lm_head_f64` (tests/score_reference.py's norm and weights), tolerance 4 x A with A from `lm_head_f32`, an all-fp32
