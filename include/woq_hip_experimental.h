@@ -52,6 +52,17 @@ WOQ_API int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, i
  * (split-K), 4 three-product fp32-class form, 8 hand-scheduled K loop, 16 half-tile ring layout, 32 256-row tiles,
  * 64 raw-A rows. Lets a test assert which kernel its shape ran. */
 WOQ_API int woq_gemm_form_log(int* forms, int cap);
+/* What launch_gemm_f16 would decide for one call, without touching a device (tests/test_gemm_plan_cpu.py): the header
+ * is built with woq_header_init from (K, N, group, the woq_blob.h type codes, asym, act_shuffle); M rows of act_dtype
+ * with row stride lda, `aligned` = the activation pointer is 16-byte aligned, has_norm = an RMSNorm weight is passed,
+ * compute_type fp32 = the fp32-class form. fp8 != 0: the call of an fp8 weight (the header is then the HI plane's int4
+ * one, weight_type is ignored). tall / tall_raw: the WOQ_GEMM_TALL / WOQ_GEMM_TALL_RAW switches (defaults 1 / 0).
+ * out8 = {form bits, K slices, pack pass writes half-tile images, row blocks of the pack pass (0 = raw-A), workspace
+ * bytes of this call, workspace bytes the caller-side sizing function answers for it, bytes of split-K partials, the
+ * share the sizing reserves for them}. */
+WOQ_API int woq_probe_gemm_plan(int K, int N, int group, int weight_type, int scale_type, int compute_type, int asym,
+                                int act_shuffle, int M, int act_dtype, int lda, int aligned, int has_norm, int fp8,
+                                int tall, int tall_raw, long long* out8);
 /* Test entry points: the attention launches of the engine on caller-owned buffers, each forwarding to the engine's own
  * launcher unchanged (tests/test_gpu_attention_kernels.py). Caches [sequence][position][kv head][head_dim] in kv_dtype
  * (WOQ_F16 | WOQ_BF16 | WOQ_FP8_E4M3), `seq_stride_elems` elements between sequences; cos / sin fp32 [position][head_dim / 2].

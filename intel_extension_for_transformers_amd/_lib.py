@@ -94,7 +94,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
-    "woq_probe_gemv_f32",
+    "woq_probe_gemv_f32", "woq_probe_gemm_plan",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -168,6 +168,7 @@ def lib():
     L.woq_engine_set_tp_options.argtypes = [vp, ci, ci]
     L.woq_engine_time_prefill_gemm.argtypes = [vp, ci, ci, ci, vp, ctypes.POINTER(cf), ctypes.POINTER(cf)]
     L.woq_gemm_form_log.argtypes = [ctypes.POINTER(ci), ci]
+    L.woq_probe_gemm_plan.argtypes = [ci] * 16 + [ctypes.POINTER(ctypes.c_longlong)]
     L.woq_probe_rope_append.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, cs, vp]
     L.woq_probe_attn_prefill.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, cs, vp, ci, vp]
     L.woq_probe_attn_decode.argtypes = [vp, vp, vp, ci, vp, vp, vp] + [ci] * 9 + [vp, vp]
@@ -214,6 +215,18 @@ def gemm_form_log():
     buf = (ctypes.c_int * 64)()
     n = lib().woq_gemm_form_log(buf, 64)
     return list(buf[:min(n, 64)])
+
+
+def probe_gemm_plan(K, N, group, weight_type, scale_type, compute_type, asym, act_shuffle, M, act_dtype, lda,
+                    aligned=True, has_norm=False, fp8=False, tall=True, tall_raw=False):
+    """What the prefill GEMM's plan decides for one call (woq_probe_gemm_plan; host arithmetic, no device): a dict of
+    form (GEMM_FORM_* bits), nz, half_tiles, row_blocks, ws_total, ws_sized (what the sizing function answers for the
+    call), part_bytes and splitk_ws."""
+    out = (ctypes.c_longlong * 8)()
+    check(lib().woq_probe_gemm_plan(K, N, group, weight_type, scale_type, compute_type, int(asym), int(act_shuffle), M,
+                                    act_dtype, lda, int(aligned), int(has_norm), int(fp8), int(tall), int(tall_raw), out))
+    return dict(zip(("form", "nz", "half_tiles", "row_blocks", "ws_total", "ws_sized", "part_bytes", "splitk_ws"),
+                    (int(v) for v in out)))
 
 
 def _ptr(t):

@@ -376,8 +376,7 @@ static int engine_prefill_reserve(woq_engine* e, size_t rows) {
   size_t ws = 0;
   for (const EngineLayer& w : e->layers)
     for (const EngineProj& p : w.p)
-      ws = std::max(ws, gemm_f16_workspace_bytes_blob((int)rows, p.hdr, 1) +
-                            (e->fp8_type ? (size_t)(p.hdr.Npad / WOQ_TILE_N) * (p.hdr.Kpad / WOQ_TILE_K) * 4 * 1024 : 0));
+      ws = std::max(ws, gemm_f16_workspace_bytes_blob((int)rows, p.hdr, 1, e->fp8_type != 0));
   if (rows <= e->pf_rows && ws <= e->pf_ws_bytes) return 0;
   WOQ_HIP(hipDeviceSynchronize());
   for (void* p : {(void*)e->pf_h, (void*)e->pf_qkv, (void*)e->pf_attn, (void*)e->pf_act, e->pf_ws})
@@ -395,6 +394,18 @@ static int engine_prefill_reserve(woq_engine* e, size_t rows) {
   return 0;
 }
 
+// The prompt pass's GEMM call: projection k of layer l over M rows. The column-parallel ones (qkv, gate/up) read the
+// residual stream through RMSNorm `norm_w`, the row-parallel ones (o, down) add onto it.
+static int engine_prefill_gemm(woq_engine* e, int l, Proj k, int M, const void* act, int act_dtype, int lda, void* out,
+                               int out_dtype, int ldo, const float* norm_w, hipStream_t st) {
+  const woq_engine_config& c = e->cfg;
+  const EngineProj& p = e->layers[l].p[k];
+  const bool rowp = k == P_O || k == P_DOWN;
+  return launch_gemm_f16(act, act_dtype, lda, p.blob, p.hdr, nullptr, out, out_dtype, ldo, M, norm_w,
+                         rowp ? 0.f : c.rms_eps, rowp ? e->tp_residual(e->pf_h) : nullptr, rowp ? c.hidden : 0,
+                         kProjEpi[k], e->pf_ws, 0, st, p.fp8_lo, e->fp8_type, e->pf_ws_bytes);
+}
+
 static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, int T, int start, int greedy,
                                hipStream_t st) {
   const woq_engine_config& c = e->cfg;
@@ -404,30 +415,24 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
   int rc = engine_prefill_reserve(e, (size_t)M);
   if (rc) return rc;
   launch_embed_rows(e->embed, e->embed_dtype, tokens, M, c.hidden, e->pf_h, st);
-  // projection k of layer l over all M rows: the column-parallel ones (qkv, gate/up) read the residual stream through
-  // RMSNorm `norm_w`, the row-parallel ones (o, down) add onto it
-  auto gemm = [&](int l, Proj k, const void* act, int act_dtype, int lda, void* out, int out_dtype, int ldo,
-                  const float* norm_w) {
-    const EngineProj& p = e->layers[l].p[k];
-    const bool rowp = k == P_O || k == P_DOWN;
-    return launch_gemm_f16(act, act_dtype, lda, p.blob, p.hdr, nullptr, out, out_dtype, ldo, M, norm_w,
-                           rowp ? 0.f : c.rms_eps, rowp ? e->tp_residual(e->pf_h) : nullptr, rowp ? c.hidden : 0,
-                           kProjEpi[k], e->pf_ws, 0, st, p.fp8_lo, e->fp8_type, e->pf_ws_bytes);
-  };
   for (int l = 0; l < c.layers; ++l) {
     const EngineLayer& w = e->layers[l];
     uint8_t *kc = e->k_of(l), *vc = e->v_of(l);
-    if ((rc = gemm(l, P_QKV, e->pf_h, WOQ_F32, c.hidden, e->pf_qkv, WOQ_F16, qkv_n, w.ln1)) != 0) return rc;
+    rc = engine_prefill_gemm(e, l, P_QKV, M, e->pf_h, WOQ_F32, c.hidden, e->pf_qkv, WOQ_F16, qkv_n, w.ln1, st);
+    if (rc) return rc;
     if ((rc = launch_rope_append(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, e->cs, e->sn, kc, vc,
                                  c.kv_dtype, seq_stride, st)) != 0)
       return rc;
     if ((rc = launch_attn_prefill(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, kc, vc, c.kv_dtype,
                                   seq_stride, e->pf_attn, e->window, st)) != 0)
       return rc;
-    if ((rc = gemm(l, P_O, e->pf_attn, WOQ_F16, c.heads * c.head_dim, e->pf_h, WOQ_F32, c.hidden, nullptr)) != 0) return rc;
+    rc = engine_prefill_gemm(e, l, P_O, M, e->pf_attn, WOQ_F16, c.heads * c.head_dim, e->pf_h, WOQ_F32, c.hidden, nullptr, st);
+    if (rc) return rc;
     if ((rc = engine_allreduce_rows(e, e->pf_h, (size_t)M * c.hidden, st)) != 0) return rc;
-    if ((rc = gemm(l, P_GATE_UP, e->pf_h, WOQ_F32, c.hidden, e->pf_act, WOQ_F16, c.inter, w.ln2)) != 0) return rc;
-    if ((rc = gemm(l, P_DOWN, e->pf_act, WOQ_F16, c.inter, e->pf_h, WOQ_F32, c.hidden, nullptr)) != 0) return rc;
+    rc = engine_prefill_gemm(e, l, P_GATE_UP, M, e->pf_h, WOQ_F32, c.hidden, e->pf_act, WOQ_F16, c.inter, w.ln2, st);
+    if (rc) return rc;
+    rc = engine_prefill_gemm(e, l, P_DOWN, M, e->pf_act, WOQ_F16, c.inter, e->pf_h, WOQ_F32, c.hidden, nullptr, st);
+    if (rc) return rc;
     if ((rc = engine_allreduce_rows(e, e->pf_h, (size_t)M * c.hidden, st)) != 0) return rc;
   }
   // logits of every sequence's last position; sequence 0 also lands in the decode step's buffers
@@ -1104,8 +1109,6 @@ int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, int reps,
   WOQ_CHECK((size_t)n_rows <= e->pf_rows && n_rows > 8, "QBits: run a prompt pass of at least n_rows rows first");
   hipStream_t st = (hipStream_t)stream;
   const woq_engine_config& c = e->cfg;
-  const EngineLayer& w = e->layers[layer];
-  const EngineProj& gu = w.p[P_GATE_UP];
   hipEvent_t k0, k1, c0, c1;
   WOQ_HIP(hipEventCreate(&k0));
   WOQ_HIP(hipEventCreate(&k1));
@@ -1115,8 +1118,8 @@ int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, int reps,
   for (int r = 0; r <= reps; ++r) {  // pass 0 warms up
     WOQ_HIP(hipEventRecord(c0, st));
     set_gemm_time_events(k0, k1);
-    const int rc = launch_gemm_f16(e->pf_h, WOQ_F32, c.hidden, gu.blob, gu.hdr, nullptr, e->pf_act, WOQ_F16,
-                                   c.inter, n_rows, w.ln2, c.rms_eps, nullptr, 0, 1, e->pf_ws, 0, st, nullptr, 0, e->pf_ws_bytes);
+    const int rc = engine_prefill_gemm(e, layer, P_GATE_UP, n_rows, e->pf_h, WOQ_F32, c.hidden, e->pf_act, WOQ_F16,
+                                       c.inter, e->layers[layer].ln2, st);
     set_gemm_time_events(nullptr, nullptr);
     if (rc) return rc;
     WOQ_HIP(hipEventRecord(c1, st));

@@ -31,7 +31,9 @@
 // two LDS buffers of 32 KiB, two workgroups per CU — the kernel in THIS file (hipcc's instruction order; kept for the
 // fp32-class form and for odd K-tile counts). The one-product form normally runs the hand-scheduled K loop of
 // woq_gemm_f16p.h: same tiles and epilogue, 16-KiB half-tiles through a ring of three LDS slots, three workgroups
-// per CU, optionally fetching fp16 activation rows without a pack pass. Workgroup ids are laid out XCD-aware: the 64 workgroups that
+// per CU, optionally fetching fp16 activation rows without a pack pass; from 2048 rows and 1024 workgroups, 256-row
+// tiles over the same images (woq_gemm_f16t.h). plan_gemm_f16 (host side, below) decides once which of these a call runs,
+// its pack layout, grid and workspace. Workgroup ids are laid out XCD-aware: the 64 workgroups that
 // share an XCD's L2 at a time form an 8 x 8 super-tile (8 A row blocks x 8 B column blocks re-used 8x each).
 // Measured alternatives (MI355X, M = 8192, gate/up shape, 849 TFLOP/s as built): 8 waves per workgroup sharing one
 // A tile (128 x 256, one workgroup per CU) 799; 4 column tiles per wave (128 accumulator VGPRs, one workgroup per CU)
@@ -49,7 +51,7 @@ namespace woq {
 static hipEvent_t g_gemm_ev0 = nullptr, g_gemm_ev1 = nullptr;
 
 // forms of the recent launch_gemm_f16 calls (woq_gemm_form_log, include/woq_hip_experimental.h; bits mirrored in
-// _lib.py): what the selector picked, so that a test can tell which kernel its shape ran
+// _lib.py): what the plan picked, so that a test can tell which kernel its shape ran
 enum : int {
   GEMM_FORM_FRAG = 1,        // fragment-image kernel (table / fp8 weights)
   GEMM_FORM_SPLITK = 2,      // K slices
@@ -909,116 +911,147 @@ __global__ __launch_bounds__(256, NP == 1 ? 2 : 1) void gemm_f16frag_kernel(Gemm
   gemm_epilogue<CT>(a, acc, row0, ct0, i16, kq);
 }
 
-template <int NP>
-static int launch_f16frag_t(GemmF16Args& a, hipStream_t st) {
-  auto kern = gemm_f16frag_kernel<NP, 2>;
-  static bool attr_set = false;
-  static std::mutex attr_mu;
-  {
-    std::lock_guard<std::mutex> attr_lock(attr_mu);
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * FTILE_BYTES * 2);
-      if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
-      attr_set = true;
-    }
-  }
-  const int n_sup8 = (a.n_sup + 7) / 8;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(n_sup8 * 8 * 64)), dim3(256), 2 * FTILE_BYTES * (NP == 1 ? 1 : 2), st, a);
-  return 0;
-}
-
 #include "woq_gemm_f16p.h"
 #include "woq_gemm_f16t.h"
 
-// `form` (host side, not a kernel argument): ORs in GEMM_FORM_HANDSCHED / _RING / _TALL for the kernel it picks
-template <int SMODE, bool ASYM, bool S32, int NP>
-static int launch_f16_t(GemmF16Args& a, hipStream_t st, int& form) {
-  auto kern = gemm_f16s_kernel<SMODE, ASYM, S32, NP, 2>;
-  bool ring = false;
-  // the hand-scheduled K loop (woq_gemm_f16p.h) runs two K steps per trip: odd tile counts, and K slices (the kernel
-  // above takes a K range), keep the kernel above
-  if (NP == 1 && (a.tiles_k & 1) == 0 && a.kper == 0) {
-    form |= GEMM_FORM_HANDSCHED;
-    // (the ring form needs <= 168 VGPRs for its third workgroup per CU; group-32 asymmetric blobs with fp32 scales do
-    // not fit without spills and stay on the two-tile form)
-    constexpr bool ring_fits = !(SMODE == 1 && ASYM && S32);
-    ring = a.ring != 0 && ring_fits;
-#define WOQ_PICK(RAW_, RING_)                                                                       \
-  (S32 ? gemm_f16p_kernel<SMODE, ASYM, 2, RAW_, RING_>                                              \
-       : (a.scale_type == WOQ_BF16 ? gemm_f16p_kernel<SMODE, ASYM, 1, RAW_, RING_>                  \
-                                   : gemm_f16p_kernel<SMODE, ASYM, 0, RAW_, RING_>))
-    if constexpr (ring_fits) {
-      if (ring) kern = a.act_raw ? WOQ_PICK(true, true) : WOQ_PICK(false, true);
-    }
-    if (!ring)
-      kern = a.act_raw ? WOQ_PICK(true, false) : WOQ_PICK(false, false);
-#undef WOQ_PICK
-    if (ring) form |= GEMM_FORM_RING;
+// Host side. plan_gemm_f16 decides, before the first launch, which kernel form a call runs, how the pack pass lays the
+// activations out for it, the grid, and where everything sits in the workspace: pure arithmetic (no HIP calls, no
+// environment, no statics), which the CPU suite runs through woq_probe_gemm_plan.
+
+// The workspace share of a split-K call's partial sums: slices x rows x columns <= 512 / workgroups x 128 x 128 floats
+// per workgroup of the unsplit grid (the plan slices only grids of <= 256 workgroups and asks for <= 512 / workgroups
+// slices), i.e. <= 32 MiB whatever the shape; a fixed 40 MiB keeps the caller's sizing independent of the split.
+// tests/test_gemm_plan_cpu.py sweeps the bound.
+constexpr size_t SPLITK_WS = (size_t)40 << 20;
+
+// Byte offsets into one call's workspace: [activation tiles | row scales | column scales][fragment image][partials].
+struct GemmWorkspace {
+  size_t ap = 0, rs = 0, cs = 0, frag = 0, part = 0, total = 0;
+};
+// frag: with the fragment image, tiles x 4 fragments x planes x 64 lanes x 16 B; part_bytes: the split-K partials
+static GemmWorkspace gemm_workspace_layout(int M, const woq_blob_header& h, int planes, bool frag, size_t part_bytes) {
+  const size_t Mpad = ((size_t)M + FBM - 1) / FBM * FBM;
+  GemmWorkspace w;
+  w.rs = Mpad * h.Kpad * sizeof(uint16_t) * planes;
+  w.cs = w.rs + Mpad * sizeof(float);
+  w.frag = (w.cs + (size_t)h.Npad * sizeof(float) + 255) & ~(size_t)255;
+  w.part = w.frag + (frag ? (size_t)(h.Npad / WOQ_TILE_N) * (h.Kpad / WOQ_TILE_K) * 4 * planes * 1024 : 0);
+  w.total = w.part + part_bytes;
+  return w;
+}
+
+struct GemmPlan {
+  int form = 0;          // GEMM_FORM_* bits
+  int kper = 0, nz = 1;  // split-K: K tiles per slice (0 = no split), slices
+  bool frag = false, hand_scheduled = false, ring = false, raw = false, tall = false;
+  int half_tiles = 0, row_blocks = 0;  // pack pass: half-tile images (ring kernels); rows it converts (0 = raw-A)
+  // grid: row blocks of the kernel's own tile height (256 rows when tall), 128-row blocks of the packed layout,
+  // column blocks, 8 x 8 super-tiles along N and in all, workgroups launched per K slice, dynamic LDS of the launch
+  int nb_m = 0, nb_m128 = 0, nb_n = 0, sup_n = 0, n_sup = 0, grid_x = 0, lds_bytes = 0;
+  int ldp = 0;            // split-K partials: row stride, bytes (<= SPLITK_WS)
+  size_t part_bytes = 0;
+  GemmWorkspace ws;
+};
+
+// `h`: the blob's header (fp8: the HI plane's, with `fp8` set — that header does not say it). aligned: the activation
+// pointer is 16-byte aligned. tall_ok / tall_raw: the WOQ_GEMM_TALL / WOQ_GEMM_TALL_RAW switches.
+static GemmPlan plan_gemm_f16(const woq_blob_header& h, int M, int act_dtype, int lda, bool aligned, bool has_norm,
+                              bool fp32_class, bool fp8, bool tall_ok, bool tall_raw) {
+  GemmPlan p;
+  const int planes = fp32_class ? 2 : 1;
+  const int tiles_k = h.Kpad / WOQ_TILE_K, tiles_n = h.Npad / WOQ_TILE_N;
+  p.nb_m128 = (M + FBM - 1) / FBM;
+  p.nb_n = (tiles_n * 16 + 127) / 128;
+  // float weight types (4-bit tables; fp8 as two nibble planes): B pre-dequantised into MFMA fragments
+  p.frag = woq_weight_is_table(h.weight_type) || fp8;
+  // split-K: a call of one or two row blocks launches a few dozen workgroups on 256 CUs (M = 64: o / down 32, qkv 96,
+  // gate / up 172 — 43-93 us per call); K slices bring the grid to ~512 workgroups, one round at two per CU. Each
+  // slice keeps >= 4 K tiles, an even count.
+  // (measured on the Llama-2-7B prompt pass, 32 layers: 32 / 64 / 128 tokens 8.9 -> 5.6, 9.1 -> 6.0, 9.4 -> 6.6 ms;
+  // at 512 tokens slicing the 128-workgroup o / down calls LOSES 10 %: the slices run the compiler-scheduled kernel
+  // and pay the partials' round trip, so beyond one row block only really small grids are sliced)
+  const int wgs = p.nb_m128 * p.nb_n;
+  if (!p.frag && wgs <= (p.nb_m128 == 1 ? 256 : 64) && tiles_k >= 8) {
+    const int want = std::min(16, std::max(2, 512 / wgs));
+    p.kper = std::max(4, ((tiles_k + want - 1) / want + 1) & ~1);
+    p.nz = (tiles_k + p.kper - 1) / p.kper;
+    if (p.nz < 2) p.kper = 0, p.nz = 1;
   }
-  int LDS = ring ? 3 * (FTILE_BYTES / 2) : 2 * FTILE_BYTES * (NP == 1 ? 1 : 2);
+  p.ldp = (h.Npad + 31) & ~31;
+  p.part_bytes = p.kper ? (size_t)p.nz * M * p.ldp * sizeof(float) : 0;
+  // the hand-scheduled K loop (woq_gemm_f16p.h) runs two K steps per trip and one product: odd tile counts, K slices
+  // (gemm_f16s_kernel takes a K range) and the fp32-class form keep hipcc's schedule
+  p.hand_scheduled = !p.frag && !fp32_class && (tiles_k & 1) == 0 && p.kper == 0;
+  // the ring form needs <= 168 VGPRs for its third workgroup per CU; group-32 asymmetric blobs with fp32 scales do not
+  // fit without spills and stay on the two-tile form (no ring, so no 256-row tiles either)
+  p.ring = p.hand_scheduled && !(h.scale_mode == 1 && h.off_zp != 0 && h.scale_type == WOQ_F32);
+  // raw-A form: fp16 rows that need no gather, no RMSNorm and no rescale go to the hand-scheduled kernel as they are
+  // (the o_proj / down_proj calls of the prompt pass); only the column scales are computed by the pack pass
+  p.raw = p.hand_scheduled && act_dtype == WOQ_F16 && !has_norm && h.off_shuffle == 0 && (h.K & 127) == 0 &&
+          (lda & 7) == 0 && aligned && (size_t)M * lda * 2 < ((size_t)1 << 32);
   // round 6: 256-row workgroup tiles (woq_gemm_f16t.h) — the ring layout's half-tile images (or the raw rows), twice the
   // rows per wave, half the weight unpack per MFMA. From 2048 rows (below that the 128-row tiles fill the chip better);
   // WOQ_GEMM_TALL=0: off (A/B runs).
-  [[maybe_unused]] bool tall = false;
-  if constexpr (NP == 1 && !(SMODE == 1 && ASYM && S32)) {
-    static const bool tall_ok = !(getenv("WOQ_GEMM_TALL") && getenv("WOQ_GEMM_TALL")[0] == '0');
-    constexpr int tall_rows = 2048;
-    // raw-A calls (o / down of the prompt pass) keep the 128-row ring kernel: alone they gain 2-7 % on 256-row tiles, inside
-    // the engine's pass they lose (0.4915 vs 0.4975 with them on, profiles/r06i_*); WOQ_GEMM_TALL_RAW=1 turns them on
-    static const bool tall_raw = getenv("WOQ_GEMM_TALL_RAW") && getenv("WOQ_GEMM_TALL_RAW")[0] == '1';
-    // enough 256-row workgroups for two full rounds of the chip's 512 slots (M = 2048 x N = 4096 is 256 of them: 132 us
-    // against 82 us for the 128-row tiles, profiles/r06h_*)
-    constexpr int tall_wgs = 1024;
-    if (tall_ok && ring && a.M >= tall_rows && ((a.nb_m + 1) / 2) * a.nb_n >= tall_wgs && (tall_raw || !a.act_raw)) {
-      tall = true;
-      form |= GEMM_FORM_TALL;
-#define WOQ_PICK_T(RAW_)                                                                   \
-  (S32 ? gemm_f16t_kernel<SMODE, ASYM, 2, RAW_>                                            \
-       : (a.scale_type == WOQ_BF16 ? gemm_f16t_kernel<SMODE, ASYM, 1, RAW_> : gemm_f16t_kernel<SMODE, ASYM, 0, RAW_>))
-      kern = a.act_raw ? WOQ_PICK_T(true) : WOQ_PICK_T(false);
-#undef WOQ_PICK_T
-      a.nb_m128 = a.nb_m;
-      a.nb_m = (a.nb_m + 1) / 2;
-      a.n_sup = ((a.nb_m + 7) / 8) * a.sup_n;
-      LDS = 2 * FTILE_BYTES;
-    }
-  }
-  static const void* attr_set[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  static std::mutex attr_mu;  // (host threads launching concurrently)
-  std::lock_guard<std::mutex> attr_lock(attr_mu);
-  bool have = false;  // (attr_set: the kernels this instantiation can pick)
-  int free_slot = 11;
-  for (int i = 11; i >= 0; --i) {
-    have = have || attr_set[i] == (const void*)kern;
-    if (attr_set[i] == nullptr) free_slot = i;
-  }
-  if (!have) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * FTILE_BYTES * 2);
-    if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
-    attr_set[free_slot] = (const void*)kern;
-  }
-  const int n_sup8 = (a.n_sup + 7) / 8;
-  const unsigned nz = a.kper > 0 ? (unsigned)((a.tiles_k + a.kper - 1) / a.kper) : 1u;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(n_sup8 * 8 * 64), nz), dim3(256), LDS, st, a);
+  constexpr int tall_rows = 2048;
+  // enough 256-row workgroups for two full rounds of the chip's 512 slots (M = 2048 x N = 4096 is 256 of them: 132 us
+  // against 82 us for the 128-row tiles, profiles/r06h_*)
+  constexpr int tall_wgs = 1024;
+  // raw-A calls (o / down of the prompt pass) keep the 128-row ring kernel: alone they gain 2-7 % on 256-row tiles, inside
+  // the engine's pass they lose (0.4915 vs 0.4975 with them on, profiles/r06i_*); WOQ_GEMM_TALL_RAW=1 turns them on
+  p.tall = p.ring && tall_ok && M >= tall_rows && ((p.nb_m128 + 1) / 2) * p.nb_n >= tall_wgs && (tall_raw || !p.raw);
+  p.form = (p.frag ? GEMM_FORM_FRAG : 0) | (p.kper ? GEMM_FORM_SPLITK : 0) | (fp32_class ? GEMM_FORM_FP32 : 0) |
+           (p.hand_scheduled ? GEMM_FORM_HANDSCHED : 0) | (p.ring ? GEMM_FORM_RING : 0) |
+           (p.tall ? GEMM_FORM_TALL : 0) | (p.raw ? GEMM_FORM_RAW : 0);
+  p.half_tiles = p.ring ? 1 : 0, p.row_blocks = p.raw ? 0 : p.nb_m128 * FBM;
+  p.nb_m = p.tall ? (p.nb_m128 + 1) / 2 : p.nb_m128;
+  p.sup_n = (p.nb_n + 7) / 8;
+  p.n_sup = ((p.nb_m + 7) / 8) * p.sup_n;
+  p.grid_x = ((p.n_sup + 7) / 8) * 8 * 64;
+  // two 32-KiB tiles (x planes); the ring: three 16-KiB half-tile slots; 256-row tiles: two half-tile pairs
+  p.lds_bytes = p.tall ? 2 * FTILE_BYTES : p.ring ? 3 * (FTILE_BYTES / 2) : 2 * FTILE_BYTES * planes;
+  p.ws = gemm_workspace_layout(M, h, planes, p.frag, p.part_bytes);
+  return p;
+}
+
+// one launch of the planned grid; every GEMM kernel may use up to two two-plane tiles of dynamic LDS
+template <auto KERN>
+static int launch_gemm_kernel(const GemmF16Args& a, const GemmPlan& p, hipStream_t st) {
+  if (const int rc = allow_dynamic_lds<KERN>(2 * FTILE_BYTES * 2)) return rc;
+  hipLaunchKernelGGL(KERN, dim3((unsigned)p.grid_x, (unsigned)p.nz), dim3(256), p.lds_bytes, st, a);
   return 0;
 }
 
-// Workspace bytes for an [M, K] x [K, N] call (activation tiles + row scales + column scales).
-// (+ SPLITK_WS for the partial sums of a split-K call: slices x rows x columns <= 512 / workgroups x 128 x 128 floats
-// per workgroup of the unsplit grid, i.e. <= 34 MiB whatever the shape; a fixed 40 MiB keeps the caller's sizing simple)
-constexpr size_t SPLITK_WS = (size_t)40 << 20;
-size_t gemm_f16_workspace_bytes(int M, int Kpad, int Npad, int planes) {
-  const size_t Mpad = ((size_t)M + FBM - 1) / FBM * FBM;
-  const size_t base = Mpad * Kpad * sizeof(_Float16) * planes + Mpad * sizeof(float) + (size_t)Npad * sizeof(float);
-  return ((base + 255) & ~(size_t)255) + SPLITK_WS;
+// f(SMODE, ASYM, ST, NP, RAW, RING, TALL): the blob's form and the plan's as std::integral_constant arguments. ST: scale
+// storage 0 fp16 | 1 bf16 | 2 fp32; NP: 1 product, or 3 (fp32-class: no raw / ring / 256-row form); TALL implies RING.
+template <typename F>
+static int select_gemm_form(const woq_blob_header& h, bool fp32_class, const GemmPlan& p, F&& f) {
+  using std::false_type, std::true_type;
+  auto rows = [&](auto SM, auto AS, auto ST) {
+    const std::integral_constant<int, 1> np1;
+    auto raw = [&](auto RING, auto TALL) {
+      return p.raw ? f(SM, AS, ST, np1, true_type{}, RING, TALL) : f(SM, AS, ST, np1, false_type{}, RING, TALL);
+    };
+    if (fp32_class) return f(SM, AS, ST, std::integral_constant<int, 3>{}, false_type{}, false_type{}, false_type{});
+    if (p.tall) return raw(true_type{}, true_type{});
+    return p.ring ? raw(true_type{}, false_type{}) : raw(false_type{}, false_type{});
+  };
+  auto scales = [&](auto SM, auto AS) {
+    if (h.scale_type == WOQ_F32) return rows(SM, AS, std::integral_constant<int, 2>{});
+    return h.scale_type == WOQ_BF16 ? rows(SM, AS, std::integral_constant<int, 1>{})
+                                    : rows(SM, AS, std::integral_constant<int, 0>{});
+  };
+  if (h.scale_mode == 0) return h.off_zp ? scales(std::integral_constant<int, 0>{}, true_type{})
+                                         : scales(std::integral_constant<int, 0>{}, false_type{});
+  if (h.scale_mode == 1) return h.off_zp ? scales(std::integral_constant<int, 1>{}, true_type{})
+                                         : scales(std::integral_constant<int, 1>{}, false_type{});
+  return woq::fail("QBits: bad scale mode");
 }
 
-size_t gemm_f16_workspace_bytes_blob(int M, const woq_blob_header& h, int planes) {
-  const size_t tiles = (size_t)(h.Npad / WOQ_TILE_N) * (h.Kpad / WOQ_TILE_K);
-  return gemm_f16_workspace_bytes(M, h.Kpad, h.Npad, planes) + (is_table_type(h.weight_type) ? tiles * 4 * planes * 1024 : 0);
+size_t gemm_f16_workspace_bytes_blob(int M, const woq_blob_header& h, int planes, bool fp8) {
+  return gemm_workspace_layout(M, h, planes, woq_weight_is_table(h.weight_type) || fp8, SPLITK_WS).total;
 }
 
+// plan -> workspace -> arguments -> pack pass -> (fragment image) -> GEMM -> (split-K reduce); only the plan decides
 int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, const woq_blob_header& h,
                     const float* bias, void* out, int out_dtype, int ldo, int M, const float* norm_w, float eps,
                     const float* residual, int ld_res, int epi, void* ws, int fp32_class, hipStream_t st,
@@ -1026,8 +1059,25 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   const int planes = fp32_class ? 2 : 1;
   if (epi == 1 && (((h.Npad / WOQ_TILE_N) & 1) != 0 || (h.N & 31) != 0))
     return woq::fail("QBits: the SiLU*mul epilogue needs whole gate / up column-tile pairs");
-  GemmF16Args a;
+  // WOQ_GEMM_TALL=0: no 256-row tiles; WOQ_GEMM_TALL_RAW=1: for raw-A calls too. Read once per process.
+  static const bool tall_ok = !(getenv("WOQ_GEMM_TALL") && getenv("WOQ_GEMM_TALL")[0] == '0');
+  static const bool tall_raw = getenv("WOQ_GEMM_TALL_RAW") && getenv("WOQ_GEMM_TALL_RAW")[0] == '1';
+  const GemmPlan plan = plan_gemm_f16(h, M, act_dtype, lda, (((uintptr_t)act) & 15) == 0, norm_w != nullptr,
+                                      fp32_class != 0, fp8_lo != nullptr, tall_ok, tall_raw);
+  if (plan.frag && h.off_zp != 0) return woq::fail("QBits: float weight types are symmetric (no zero points)");
+  if (plan.part_bytes > SPLITK_WS) return woq::fail("QBits: split-K partials beyond their workspace share");
+  // the fragment image (4-8x the blob): a caller's workspace holds it only when it says it is large enough (`ws_bytes`:
+  // the engine sizes its prompt-pass workspace with gemm_f16_workspace_bytes_blob); otherwise per-call scratch
+  if (plan.frag && ws_bytes < plan.ws.total) ws = nullptr;
+  unsigned char* w = (unsigned char*)ws;
+  const bool mine = w == nullptr;  // no workspace passed in (the engine passes its own): take scratch
+  bool own = false;
+  if (mine) {
+    w = (unsigned char*)scratch_take(plan.ws.total, st, &own);
+    if (w == nullptr) return woq::fail("QBits: workspace allocation failed");
+  }
   const uint8_t* b = (const uint8_t*)blob;
+  GemmF16Args a;
   a.q = (const u32x4*)(b + h.off_q);
   a.scales = b + h.off_scale;
   a.zp = h.off_zp ? b + h.off_zp : nullptr;
@@ -1038,13 +1088,18 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   a.n_groups = h.n_groups;
   a.group = h.group;
   a.scale_type = (int)h.scale_type;
+  a.ap = (const _Float16*)(w + plan.ws.ap);
+  a.act_raw = plan.raw ? act : nullptr;
+  a.lda = lda;
+  a.ring = plan.ring ? 1 : 0;
+  a.rs = plan.raw ? nullptr : (const float*)(w + plan.ws.rs);
+  a.cs = (const float*)(w + plan.ws.cs);
   a.M = M;
-  a.nb_m = (M + FBM - 1) / FBM;
-  a.nb_m128 = a.nb_m;
-  a.nb_n = (a.tiles_n * 16 + 127) / 128;
-  const int sup_m = (a.nb_m + 7) / 8;
-  a.sup_n = (a.nb_n + 7) / 8;
-  a.n_sup = sup_m * a.sup_n;
+  a.nb_m = plan.nb_m;
+  a.nb_n = plan.nb_n;
+  a.sup_n = plan.sup_n;
+  a.n_sup = plan.n_sup;
+  a.nb_m128 = plan.nb_m128;
   a.out = out;
   a.out_dtype = out_dtype;
   a.ldo = ldo;
@@ -1052,70 +1107,19 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   a.residual = residual;
   a.ld_res = ld_res;
   a.epi = epi;
-  const size_t Mpad = (size_t)a.nb_m * FBM;
-  // float weight types (4-bit tables; fp8 as two nibble planes, `h` = the high plane's header): B pre-dequantised into
-  // MFMA fragments
-  const bool frag = is_table_type(h.weight_type) || fp8_lo != nullptr;
-  const size_t frag_bytes = frag ? (size_t)a.tiles_n * a.tiles_k * 4 * planes * 1024 : 0;
-  const size_t base_bytes = gemm_f16_workspace_bytes(M, h.Kpad, h.Npad, planes) - SPLITK_WS;  // (a multiple of 256)
-  // split-K: a call of one or two row blocks launches a few dozen workgroups on 256 CUs (M = 64: o / down 32, qkv 96,
-  // gate / up 172 — 43-93 us per call); K slices bring the grid to ~512 workgroups, one round at two per CU. Each
-  // slice keeps >= 4 K tiles, an even count.
-  int kper = 0, nz = 1;
-  {
-    const int wgs = a.nb_m * a.nb_n;
-    // (measured on the Llama-2-7B prompt pass, 32 layers: 32 / 64 / 128 tokens 8.9 -> 5.6, 9.1 -> 6.0, 9.4 -> 6.6 ms;
-    // at 512 tokens slicing the 128-workgroup o / down calls LOSES 10 %: the slices run the compiler-scheduled kernel
-    // and pay the partials' round trip, so beyond one row block only really small grids are sliced)
-    if (!frag && wgs <= (a.nb_m == 1 ? 256 : 64) && a.tiles_k >= 8) {
-      int want = std::min(16, std::max(2, 512 / wgs));
-      kper = std::max(4, ((a.tiles_k + want - 1) / want + 1) & ~1);
-      nz = (a.tiles_k + kper - 1) / kper;
-      if (nz < 2) kper = 0, nz = 1;
-    }
-  }
-  const int ldp = (h.Npad + 31) & ~31;
-  size_t part_bytes = kper ? (size_t)nz * M * ldp * sizeof(float) : 0;
-  if (part_bytes > SPLITK_WS) kper = 0, nz = 1, part_bytes = 0;  // (cannot happen: see SPLITK_WS)
-  const size_t total = base_bytes + frag_bytes + part_bytes;  // [tiles | row scales | column scales][fragments][partials]
-  if (frag && h.off_zp != 0) return woq::fail("QBits: float weight types are symmetric (no zero points)");
-  // the fragment image (4-8x the blob): a caller's workspace holds it only when it says it is large enough (`ws_bytes`:
-  // the engine sizes its prompt-pass workspace with gemm_f16_workspace_bytes_blob); otherwise per-call scratch
-  if (frag && ws_bytes < total) ws = nullptr;
-  unsigned char* w = (unsigned char*)ws;
-  const bool mine = w == nullptr;  // no workspace passed in (the engine passes its own): take scratch
-  bool own = false;
-  if (mine) {
-    w = (unsigned char*)scratch_take(total, st, &own);
-    if (w == nullptr) return woq::fail("QBits: workspace allocation failed");
-  }
-  a.ap = (const _Float16*)w;
-  a.rs = (const float*)(w + Mpad * h.Kpad * sizeof(_Float16) * planes);
-  a.cs = a.rs + Mpad;
-  a.bfrag = frag ? (const u32x4*)(w + base_bytes) : nullptr;
-  a.kper = kper;
-  a.part = kper ? (float*)(w + base_bytes + frag_bytes) : nullptr;
-  a.ldp = ldp;
-
-  // raw-A form: fp16 rows that need no gather, no RMSNorm and no rescale go to the hand-scheduled kernel as they are
-  // (the o_proj / down_proj calls of the prompt pass); only the column scales are computed here
-  const bool raw = !frag && !kper && !fp32_class && act_dtype == WOQ_F16 && norm_w == nullptr &&
-                   h.off_shuffle == 0 && (h.K & 127) == 0 && ((h.Kpad / WOQ_TILE_K) & 1) == 0 && (lda & 7) == 0 &&
-                   (((uintptr_t)act) & 15) == 0 && (size_t)M * lda * 2 < ((size_t)1 << 32);
-  a.act_raw = raw ? act : nullptr;
-  a.lda = lda;
-  if (raw) a.rs = nullptr;
-  const bool ring_fits = !(h.scale_mode == 1 && a.zp != nullptr && h.scale_type == WOQ_F32);  // (launch_f16_t: VGPRs)
-  a.ring = (ring_fits && !frag && !kper && !fp32_class && ((h.Kpad / WOQ_TILE_K) & 1) == 0) ? 1 : 0;
+  a.bfrag = plan.frag ? (const u32x4*)(w + plan.ws.frag) : nullptr;
+  a.kper = plan.kper;
+  a.part = plan.kper ? (float*)(w + plan.ws.part) : nullptr;
+  a.ldp = plan.ldp;
 
   PackF16Args p;
   p.planes = planes;
-  p.half_tiles = a.ring;
+  p.half_tiles = plan.half_tiles;
   p.x = act;
   p.x_dtype = act_dtype;
   p.lda = lda;
   p.M = M;
-  p.Mpad = (int)Mpad;
+  p.Mpad = plan.nb_m128 * FBM;
   p.K = h.K;
   p.Kpad = h.Kpad;
   p.shuffle = h.off_shuffle ? (const int32_t*)(b + h.off_shuffle) : nullptr;
@@ -1129,46 +1133,45 @@ int launch_gemm_f16(const void* act, int act_dtype, int lda, const void* blob, c
   p.n_groups = h.n_groups;
   p.tiles_k = a.tiles_k;
   p.Npad = h.Npad;
-  p.row_blocks = raw ? 0 : (int)Mpad;  // raw-A: only the column-scale blocks run
+  p.row_blocks = plan.row_blocks;
   p.cs = (float*)a.cs;
   hipLaunchKernelGGL(pack_f16_kernel, dim3((unsigned)(p.row_blocks + (h.Npad + 31) / 32)), dim3(256), 0, st, p);
 
   if (g_gemm_ev0) hipEventRecord(g_gemm_ev0, st);  // measurement hook (woq_engine_time_prefill_gemm): the GEMM alone
-  const bool asym = a.zp != nullptr;
-  const int sm = (int)h.scale_mode;
-  const bool s32 = h.scale_type == WOQ_F32;
-  int rc = 1;
-  int form = (frag ? GEMM_FORM_FRAG : 0) | (kper ? GEMM_FORM_SPLITK : 0) | (fp32_class ? GEMM_FORM_FP32 : 0) |
-             (raw ? GEMM_FORM_RAW : 0);
-  if (frag) {
+  int rc;
+  if (plan.frag) {
     DeqFragArgs d;
-    d.q = a.q, d.q_lo = (const u32x4*)fp8_lo, d.scales = a.scales, d.scale_type = a.scale_type, d.scale_mode = sm, d.n_groups = h.n_groups;
-    d.group = h.group, d.tiles_k = a.tiles_k, d.tiles_n = a.tiles_n, d.planes = planes, d.weight_type = fp8_lo ? fp8_type : h.weight_type;
-    d.cs = a.cs, d.out = (u32x4*)a.bfrag;
+    d.q = a.q, d.q_lo = (const u32x4*)fp8_lo, d.scales = a.scales, d.scale_type = a.scale_type, d.scale_mode = (int)h.scale_mode;
+    d.n_groups = h.n_groups, d.group = h.group, d.tiles_k = a.tiles_k, d.tiles_n = a.tiles_n, d.planes = planes;
+    d.weight_type = fp8_lo ? fp8_type : h.weight_type, d.cs = a.cs, d.out = (u32x4*)a.bfrag;
     const size_t tiles = (size_t)a.tiles_n * a.tiles_k;
     hipLaunchKernelGGL(deq_frag_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, d);
-    rc = fp32_class ? launch_f16frag_t<3>(a, st) : launch_f16frag_t<1>(a, st);
+    rc = fp32_class ? launch_gemm_kernel<gemm_f16frag_kernel<3, 2>>(a, plan, st)
+                    : launch_gemm_kernel<gemm_f16frag_kernel<1, 2>>(a, plan, st);
   } else {
-#define WOQ_F16_CASE(SM, AS)                                                                                  \
-  if (sm == SM && asym == AS)                                                                                 \
-    rc = fp32_class ? (s32 ? launch_f16_t<SM, AS, true, 3>(a, st, form) : launch_f16_t<SM, AS, false, 3>(a, st, form)) \
-                    : (s32 ? launch_f16_t<SM, AS, true, 1>(a, st, form) : launch_f16_t<SM, AS, false, 1>(a, st, form));
-  WOQ_F16_CASE(0, false)
-  WOQ_F16_CASE(0, true)
-  WOQ_F16_CASE(1, false)
-  WOQ_F16_CASE(1, true)
-#undef WOQ_F16_CASE
+    // (group-32 asymmetric blobs with fp32 scales: the plan never asks for their ring / 256-row kernels)
+    rc = select_gemm_form(h, fp32_class != 0, plan, [&](auto SM, auto AS, auto ST, auto NP, auto RAW, auto RING, auto TALL) {
+      if constexpr (TALL) {
+        return launch_gemm_kernel<gemm_f16t_kernel<SM, AS, ST, RAW>>(a, plan, st);
+      } else if constexpr (RING) {
+        return launch_gemm_kernel<gemm_f16p_kernel<SM, AS, ST, RAW, true>>(a, plan, st);
+      } else {
+        if constexpr (NP == 1)
+          if (plan.hand_scheduled) return launch_gemm_kernel<gemm_f16p_kernel<SM, AS, ST, RAW, false>>(a, plan, st);
+        return launch_gemm_kernel<gemm_f16s_kernel<SM, AS, ST == 2, NP, 2>>(a, plan, st);
+      }
+    });
   }
-  if (rc == 0 && kper) {
+  if (rc == 0 && plan.kper) {
     SplitKArgs r;
-    r.part = a.part, r.nz = nz, r.M = M, r.N = h.N, r.ldp = ldp, r.epi = epi, r.bias = bias, r.residual = residual;
+    r.part = a.part, r.nz = plan.nz, r.M = M, r.N = h.N, r.ldp = plan.ldp, r.epi = epi, r.bias = bias, r.residual = residual;
     r.ld_res = ld_res, r.out = out, r.out_dtype = out_dtype, r.ldo = ldo;
     const size_t elems = (size_t)M * (epi == 1 ? (h.N >> 1) : h.N);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, r);
   }
   if (g_gemm_ev1) hipEventRecord(g_gemm_ev1, st);
-  if (mine) scratch_release(w, total, own, st);
-  if (rc == 0) log_gemm_form(form);
+  if (mine) scratch_release(w, plan.ws.total, own, st);
+  if (rc == 0) log_gemm_form(plan.form);
   return rc;
 }
 
@@ -1185,4 +1188,22 @@ extern "C" WOQ_API int woq_gemm_form_log(int* forms, int cap) {
   if (forms != nullptr && cap > 0) std::copy(woq::g_form_log, woq::g_form_log + std::min(n, cap), forms);
   woq::g_form_n = 0;
   return n;
+}
+
+extern "C" WOQ_API int woq_probe_gemm_plan(int K, int N, int group, int weight_type, int scale_type, int compute_type,
+                                           int asym, int act_shuffle, int M, int act_dtype, int lda, int aligned,
+                                           int has_norm, int fp8, int tall, int tall_raw, long long* out8) {
+  woq_blob_header h;  // fp8: the HI plane's header, an int4 one (woq_fp8_headers)
+  if (out8 == nullptr || M <= 0 ||
+      woq_header_init(&h, K, N, group, fp8 ? 0u : (uint32_t)weight_type, (uint32_t)scale_type, (uint32_t)compute_type,
+                      asym, act_shuffle) != 0)
+    return woq::fail("QBits: bad argument");
+  const bool fp32_class = compute_type == WOQ_C_FP32;
+  const woq::GemmPlan p = woq::plan_gemm_f16(h, M, act_dtype, lda, aligned != 0, has_norm != 0, fp32_class, fp8 != 0,
+                                             tall != 0, tall_raw != 0);
+  out8[0] = p.form, out8[1] = p.nz, out8[2] = p.half_tiles, out8[3] = p.row_blocks;
+  out8[4] = (long long)p.ws.total;
+  out8[5] = (long long)woq::gemm_f16_workspace_bytes_blob(M, h, fp32_class ? 2 : 1, fp8 != 0);
+  out8[6] = (long long)p.part_bytes, out8[7] = (long long)woq::SPLITK_WS;
+  return 0;
 }

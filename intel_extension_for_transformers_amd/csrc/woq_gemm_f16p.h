@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256, RING ? 3 : 2) void gemm_f16p_kernel(GemmF16Arg
                                       a_src(min((KT) + 2, last)) + 4096, dma_dst + BUF * STAGE,       \
                                       dma_dst + BUF * STAGE + 4096, ro);
 
-  for (int kt = 0; kt < a.tiles_k; kt += 2) {  // tiles_k is even (launch_f16_t sends odd counts to gemm_f16s_kernel)
+  for (int kt = 0; kt < a.tiles_k; kt += 2) {  // tiles_k is even (plan_gemm_f16 sends odd counts to gemm_f16s_kernel)
     WOQ_KSTEP(0, B0, F0, B1, F1, kt)
     WOQ_KSTEP(1, B1, F1, B0, F0, kt + 1)
   }

@@ -1,6 +1,6 @@
 // woq_gemv_launch.h — host side shared by the decode-GEMV launchers (woq_gemv.hip, woq_gemv_i8.hip, woq_gemv_xq.hip,
 // woq_gemv_attn.hip, woq_gemv_fp8.hip): the decoded view of a blob, the selector that turns a blob's quantisation form
-// into template arguments, the K-range plan of chained launches, and the dynamic-LDS limit. Host code only.
+// into template arguments, and the K-range plan of chained launches. Host code only.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -125,16 +125,6 @@ int for_each_k_chunk(const KPlan& p, F&& body) {
     const int rc = body(c, kt_begin, kt_count, c == p.chunks - 1 || kt_begin + kt_count >= p.tiles_k);
     if (rc) return rc;
   }
-  return 0;
-}
-
-// ---- dynamic LDS --------------------------------------------------------------------------------------------------
-// Raises KERN's dynamic-LDS limit to `bytes` (beyond the 64 KiB default), once per process: the function-local static
-// is initialised by the first call, which the language makes thread-safe.
-template <auto KERN>
-int allow_dynamic_lds(int bytes) {
-  static const hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
   return 0;
 }
 

@@ -194,9 +194,11 @@ int attn_decode_mfma_slots(int kv_dtype, int rep);
 
 // ---- woq_gemm_f16.hip: the prompt pass's MFMA GEMM ----------------------------------------------------------------
 // workspace bytes of one blob's [M, K] x [K, N] call, fragment image of the float weight types included (4-8x the
-// blob: what made table-type prompt passes allocate per call while the engine's workspace sat unused — ADVICE r04)
-size_t gemm_f16_workspace_bytes_blob(int M, const woq_blob_header& h, int planes);
-// out[M,N] = act[M,K] . W_deq (+ bias) with fp16 operands. `ws` = caller workspace of gemm_f16_workspace_bytes or
+// blob: what made table-type prompt passes allocate per call while the engine's workspace sat unused — ADVICE r04);
+// fp8: the call passes an fp8 low plane (`h` = the HI plane's header, which does not say so)
+size_t gemm_f16_workspace_bytes_blob(int M, const woq_blob_header& h, int planes, bool fp8);
+// out[M,N] = act[M,K] . W_deq (+ bias) with fp16 operands. `ws` = caller workspace of gemm_f16_workspace_bytes_blob
+// (`ws_bytes`: its size, which the fragment image of the float weight types is checked against) or
 // null (stream-ordered allocation per call, like the reference's per-call amalloc,
 // bestla_weightonly_dispatcher.cpp:108-118,179). norm_w/eps: RMSNorm fused into the pack pass (null = none);
 // residual / epi: see GemmF16Args; fp32_class: the three-product hi + lo form (compute_dtype fp32).

@@ -15,6 +15,15 @@ inline int fail(const std::string& msg) {
   last_error_ref() = msg;
   return 1;
 }
+
+// Raises KERN's dynamic-LDS limit to `bytes` (beyond the 64 KiB default), once per process: the function-local static
+// is initialised by the first call, which the language makes thread-safe.
+template <auto KERN>
+int allow_dynamic_lds(int bytes) {
+  static const hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e));
+  return 0;
+}
 }  // namespace woq
 
 namespace woq {

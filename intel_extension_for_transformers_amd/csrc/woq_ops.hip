@@ -394,12 +394,8 @@ static int launch_attn_t(const float* qkv, void* kcache, void* vcache, const int
   const size_t lds = attn_dec_lds_floats(HD, span) * 4;
   if (lds > 160 * 1024) return woq::fail("QBits: max_ctx too large for the decode attention (raise attn_splits)");
   if (splits > 1) {
-    auto k = attn_decode_kernel<KV, HD, true>;
-    static bool once = false;
-    if (!once) {
-      hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      once = true;
-    }
+    constexpr auto k = attn_decode_kernel<KV, HD, true>;
+    if (const int rc = allow_dynamic_lds<k>(160 * 1024)) return rc;
     const AttnMerge mg{merge_counters, out, xo};
     hipLaunchKernelGGL(k, dim3(heads, splits), dim3(256), lds, st, qkv, (KV*)kcache, (KV*)vcache, pos, cs, sn,
                        heads | (kv_heads << 16), window, spw, part, XqPtrs{nullptr, nullptr, nullptr}, mg);
@@ -407,12 +403,8 @@ static int launch_attn_t(const float* qkv, void* kcache, void* vcache, const int
       hipLaunchKernelGGL(attn_combine_kernel<HD>, dim3(heads), dim3(256), 0, st, part, splits, out, xo);
     return 0;
   }
-  auto k = attn_decode_kernel<KV, HD, false>;
-  static bool once = false;
-  if (!once) {
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
+  constexpr auto k = attn_decode_kernel<KV, HD, false>;
+  if (const int rc = allow_dynamic_lds<k>(160 * 1024)) return rc;
   hipLaunchKernelGGL(k, dim3(heads), dim3(256), lds, st, qkv, (KV*)kcache, (KV*)vcache, pos, cs, sn,
                      heads | (kv_heads << 16), window, spw, out, xo,
                      AttnMerge{nullptr, nullptr, XqPtrs{nullptr, nullptr, nullptr}});

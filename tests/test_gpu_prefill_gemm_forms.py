@@ -1,5 +1,5 @@
-"""The prompt pass's MFMA GEMM in the form the selector picks for each shape (csrc/woq_gemm_f16.hip launch_gemm_f16 /
-launch_f16_t), every form asserted through `woq_gemm_form_log` so that a threshold change cannot quietly move a case
+"""The prompt pass's MFMA GEMM in the form the plan picks for each shape (csrc/woq_gemm_f16.hip plan_gemm_f16, carried
+out by launch_gemm_f16), every form asserted through `woq_gemm_form_log` so that a threshold change cannot quietly move a case
 off the kernel it covers. Centre: the 256-row workgroup tiles of csrc/woq_gemm_f16t.h (`gemm_f16t_kernel`, chosen from
 2048 rows when ceil(row blocks / 2) x column blocks >= 1024) at row counts that end anywhere in the last workgroup —
 no second 128-row image (odd row-block count), a partial one, one row in it — with a partly live last column tile,

@@ -78,13 +78,8 @@ template <typename KV, int HD, int TPW>
 static int launch_attn_o_sm(const AttnOArgs& a, int smode, bool asym, bool s32, int grid, size_t lds, hipStream_t st) {
 #define WOQ_AO_CASE(SM, AS, S3)                                                                                  \
   if (smode == SM && asym == AS && s32 == S3) {                                                                  \
-    auto kern = attn_o_kernel<KV, HD, TPW, SM, AS, S3>;                                                          \
-    static bool attr_set = false;                                                                                \
-    if (!attr_set) {                                                                                             \
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e)); \
-      attr_set = true;                                                                                           \
-    }                                                                                                            \
+    constexpr auto kern = attn_o_kernel<KV, HD, TPW, SM, AS, S3>;                                                \
+    if (const int rc = allow_dynamic_lds<kern>(160 * 1024)) return rc;                                           \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                                 \
     return 0;                                                                                                    \
   }

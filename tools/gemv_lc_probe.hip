@@ -438,13 +438,8 @@ template <int CB>
 static int launch_lc_sm(const LcArgs& a, int smode, bool asym, bool s32, int grid, size_t lds, hipStream_t st) {
 #define WOQ_LC_CASE(SM, AS, S3)                                                                                  \
   if (smode == SM && asym == AS && s32 == S3) {                                                                  \
-    auto kern = gemv_lc_kernel<CB, SM, AS, S3>;                                                                  \
-    static bool attr_set = false;                                                                                \
-    if (!attr_set) {                                                                                             \
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      if (e != hipSuccess) return woq::fail(std::string("QBits: hipFuncSetAttribute: ") + hipGetErrorString(e)); \
-      attr_set = true;                                                                                           \
-    }                                                                                                            \
+    constexpr auto kern = gemv_lc_kernel<CB, SM, AS, S3>;                                                        \
+    if (const int rc = allow_dynamic_lds<kern>(160 * 1024)) return rc;                                           \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(LC_THREADS), lds, st, a);                                          \
     return 0;                                                                                                    \
   }
