@@ -63,6 +63,18 @@ WOQ_API int woq_gemm_form_log(int* forms, int cap);
 WOQ_API int woq_probe_gemm_plan(int K, int N, int group, int weight_type, int scale_type, int compute_type, int asym,
                                 int act_shuffle, int M, int act_dtype, int lda, int aligned, int has_norm, int fp8,
                                 int tall, int tall_raw, long long* out8);
+/* one prompt-pass projection (tests/test_gpu_prefill_gemm_epilogues.py): forwards to launch_gemm_f16 unchanged, on
+ * caller-owned device buffers and with the arguments the engine fixes left open. act [M][lda] in act_dtype, blob a packed
+ * weight on the device (its header is read back, which synchronises the stream), norm_w fp32 [K] (nullable) with eps =
+ * RMSNorm fused into the pack pass, epi 1 = SiLU(gate) * up over a fuse_gate_up blob (out [M][N / 2]; N % 32 != 0 is the
+ * launcher's error), bias fp32 [N] (nullable), residual fp32 [M][ld_res] (nullable, may alias out), out [M][ldo] in
+ * out_dtype, fp32_class != 0 = the three-product form. ws (nullable) / ws_bytes = a caller workspace: a fragment-image
+ * call (nf4 / fp4 / fp8 weights) uses it only when ws_bytes covers the plan's bytes, else per-call scratch; any other
+ * call must bring at least what the engine's sizing function asks for. An fp8 composite blob is split like woq_linear
+ * splits it; an int8 composite (two chained calls) is refused. woq_gemm_form_log reports the form that ran. */
+WOQ_API int woq_probe_gemm_f16(const void* act, int act_dtype, int lda, int M, const void* blob, const float* norm_w,
+                               float eps, int epi, const float* bias, const float* residual, int ld_res, void* out,
+                               int out_dtype, int ldo, int fp32_class, void* ws, size_t ws_bytes, void* stream);
 /* Test entry points: the attention launches of the engine on caller-owned buffers, each forwarding to the engine's own
  * launcher unchanged (tests/test_gpu_attention_kernels.py). Caches [sequence][position][kv head][head_dim] in kv_dtype
  * (WOQ_F16 | WOQ_BF16 | WOQ_FP8_E4M3), `seq_stride_elems` elements between sequences; cos / sin fp32 [position][head_dim / 2].

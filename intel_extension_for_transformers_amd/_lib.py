@@ -94,7 +94,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
-    "woq_probe_gemv_f32", "woq_probe_gemm_plan",
+    "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -205,6 +205,7 @@ def lib():
     L.woq_probe_greedy_tail.argtypes = [ci, vp, ci] + [vp] * 6 + [ci, ci] + [vp] * 7 + [ci, vp, vp]
     L.woq_probe_embed.argtypes = [vp, ci, vp, ci] + [vp] * 8 + [ci, vp, vp]
     L.woq_probe_gemv_f32.argtypes = [vp, ci, ci, ci, vp, vp, cf, ci, vp, vp, ci, vp, ci, ci, vp, ctypes.POINTER(ci), vp]
+    L.woq_probe_gemm_f16.argtypes = [vp, ci, ci, ci, vp, vp, cf, ci, vp, vp, ci, vp, ci, ci, ci, vp, cs, vp]
     _lib = L
     return L
 
@@ -364,6 +365,19 @@ def probe_gemv_f32(x, blob, out, M=1, lda=None, ldo=None, norm_w=None, eps=0.0, 
                                    int(epi), _opt(bias), _opt(residual), int(ldo if ld_res is None else ld_res), _ptr(out),
                                    torch_dtype_code(out.dtype), ldo, _opt(gu_tmp), form, stream_ptr()))
     return tuple(form)
+
+
+def probe_gemm_f16(x, blob, out, M, lda=None, ldo=None, norm_w=None, eps=0.0, epi=0, bias=None, residual=None,
+                   ld_res=None, fp32_class=False, ws=None, ws_bytes=0):
+    """one prompt-pass projection through launch_gemm_f16 (woq_probe_gemm_f16): x / out / residual device tensors whose
+    data pointers are row 0 (views are fine), leading dimensions in elements; ws = a device workspace of ws_bytes (or
+    None: per-call scratch). woq_gemm_form_log reports the form."""
+    lda = int(x.numel() // M if lda is None else lda)
+    ldo = int(out.numel() // M if ldo is None else ldo)
+    check(lib().woq_probe_gemm_f16(_ptr(x), torch_dtype_code(x.dtype), lda, int(M), _ptr(blob), _opt(norm_w), float(eps),
+                                   int(epi), _opt(bias), _opt(residual), int(ldo if ld_res is None else ld_res), _ptr(out),
+                                   torch_dtype_code(out.dtype), ldo, int(bool(fp32_class)), _opt(ws), int(ws_bytes),
+                                   stream_ptr()))
 
 
 def check(rc):

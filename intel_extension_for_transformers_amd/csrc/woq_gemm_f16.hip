@@ -1207,3 +1207,44 @@ extern "C" WOQ_API int woq_probe_gemm_plan(int K, int N, int group, int weight_t
   out8[6] = (long long)p.part_bytes, out8[7] = (long long)woq::SPLITK_WS;
   return 0;
 }
+
+extern "C" WOQ_API int woq_probe_gemm_f16(const void* act, int act_dtype, int lda, int M, const void* blob,
+                                          const float* norm_w, float eps, int epi, const float* bias,
+                                          const float* residual, int ld_res, void* out, int out_dtype, int ldo,
+                                          int fp32_class, void* ws, size_t ws_bytes, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(act && blob && out && M >= 1 && (epi == 0 || epi == 1), "QBits: bad prefill GEMM probe arguments");
+  WOQ_CHECK(act_dtype >= WOQ_F32 && act_dtype <= WOQ_F16 && out_dtype >= WOQ_F32 && out_dtype <= WOQ_F16,
+            "QBits: unsupported qbits data type.");
+  const hipStream_t st = (hipStream_t)stream;
+  woq_blob_header h;
+  WOQ_HIP(hipMemcpyAsync(&h, blob, sizeof(h), hipMemcpyDeviceToHost, st));
+  WOQ_HIP(hipStreamSynchronize(st));
+  WOQ_CHECK(h.magic == WOQ_BLOB_MAGIC, "QBits: not a WQH1 packed weight");
+  WOQ_CHECK(h.weight_type != WOQ_W_INT8, "QBits: the prefill GEMM probe takes no int8 composite (two calls: woq_linear)");
+  const int n_out = epi == 1 ? h.N / 2 : h.N;
+  WOQ_CHECK(lda >= h.K && ldo >= n_out && (residual == nullptr || ld_res >= n_out),
+            "QBits: activation/output leading dimension smaller than K/N");
+  // the launcher itself falls back to scratch only for a fragment-image call whose workspace is too small; any other
+  // call trusts its caller's workspace (the engine sizes it with gemm_f16_workspace_bytes_blob), so the probe asks for that
+  const bool frag = woq_weight_is_table(h.weight_type) || woq_weight_is_fp8(h.weight_type);
+  WOQ_CHECK(ws == nullptr || frag ||
+                ws_bytes >= woq::gemm_f16_workspace_bytes_blob(M, h, fp32_class ? 2 : 1, false),
+            "QBits: workspace smaller than the prefill GEMM's sizing function asks for");
+  int rc;
+  if (woq_weight_is_fp8(h.weight_type)) {  // the composite container, split as woq_linear splits it
+    woq_blob_header o, hi, lo;
+    WOQ_CHECK(woq_fp8_headers(&o, &hi, &lo, h.K, h.N, h.group, h.weight_type, h.scale_type, h.compute_type,
+                              h.off_shuffle != 0) == 0, "QBits: corrupt fp8 header");
+    const uint8_t* bhi = (const uint8_t*)blob + h.off_q;
+    const uint8_t* blo = (const uint8_t*)blob + h.off_scale;
+    rc = woq::launch_gemm_f16(act, act_dtype, lda, bhi, hi, bias, out, out_dtype, ldo, M, norm_w, eps, residual, ld_res,
+                              epi, ws, fp32_class, st, blo + lo.off_q, h.weight_type, ws_bytes);
+  } else {
+    rc = woq::launch_gemm_f16(act, act_dtype, lda, blob, h, bias, out, out_dtype, ldo, M, norm_w, eps, residual, ld_res,
+                              epi, ws, fp32_class, st, nullptr, 0, ws_bytes);
+  }
+  if (rc) return rc;
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
