@@ -291,6 +291,36 @@ WOQ_API int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg)
  * marks every token it picks itself. */
 WOQ_API int woq_engine_sampler_seen(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream);
 WOQ_API void* woq_engine_sampler_seen_ptr(woq_engine* e);
+/* ---- sampler controls: logit bias, presence / frequency penalty, min_p (new entry points only; WOQ_ABI_VERSION stays
+ * 4 and woq_sampler_config stays 32 bytes) -----------------------------------------------------------------------------
+ * With controls installed beside a sampler, the score of id i is built from the fp32 logit l by these fp32 operations,
+ * each rounded on its own, in this order: s = l + bias[i] for ids with a bias entry (finite, or -inf = a ban; ahead of
+ * the penalties like HF's SequenceBiasLogitsProcessor and vLLM's logit_bias); the repetition penalty over `seen` as
+ * above; for ids GENERATED c[i] > 0 times in this request s = s - (frequency_penalty * (float)c[i]), then
+ * s = s - presence_penalty (prompt tokens do not count — the vLLM convention; a host that wants otherwise preloads the
+ * counts); then / temperature, top-k and top-p as above, and min_p (HF's MinPLogitsWarper, min_tokens_to_keep 1, after
+ * top-p): a candidate stays iff expf(s_i - s_max) >= min_p. With do_sample == 0 the pick is the argmax of the
+ * penalised scores. top_k == 0 with top_p == 1 and 0 < min_p <= 1 is covered. A pre-pass over the whole chip writes the
+ * scores into an engine-owned scratch and the sampling launch reads that (csrc/woq_sample.hip): one more launch per
+ * step, shapes by the vocabulary alone; the log-probability record keeps describing the raw logits. The tail also
+ * counts every token it picks. */
+typedef struct woq_sampler_controls {
+  float presence_penalty, frequency_penalty; /* finite; 0 = off */
+  float min_p;                               /* [0, 1]; 0 = off; > 0 needs do_sample */
+  int32_t n_bias;                            /* entries of the two host arrays, 0..1024 */
+  uint32_t reserved[4];                      /* 0 */
+} woq_sampler_controls;
+/* ctl (host memory) and the n_bias (token id, value) pairs are copied into device memory the kernels read: changing them
+ * needs no new capture, installing or removing (ctl == NULL; also woq_engine_set_sampler(e, NULL)) the controls drops a
+ * captured graph. Needs a sampler installed. Synchronises the device. Fails with a "QBits:" message for ids outside
+ * [0, vocab), duplicate ids, n_bias > 1024, min_p outside [0, 1] or > 0 without do_sample, non-finite penalties and a
+ * bias of +inf or NaN. */
+WOQ_API int woq_engine_set_sampler_controls(woq_engine* e, const woq_sampler_controls* ctl, const int32_t* bias_ids_host,
+                                            const float* bias_vals_host);
+/* the generated-token counts: uint32 [vocab] owned by the engine. counts[tokens_dev[j]] += 1 for j in [0, n) (device
+ * int32; may be NULL with n == 0) after zeroing the table when clear != 0; stream-ordered. */
+WOQ_API int woq_engine_sampler_counts(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream);
+WOQ_API void* woq_engine_sampler_count_ptr(woq_engine* e);
 /* ---- per-token log-probabilities (new entry points only; WOQ_ABI_VERSION stays 4) ----------------------------------
  * With recording on, every step that chains on the device (greedy != 0: the prompt pass's tail, woq_engine_step /
  * _steps / _capture / _replay) writes, after its pick, one row of three device logs indexed like the token log (row p

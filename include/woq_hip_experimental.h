@@ -103,6 +103,17 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
 WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
                              const float* u_or_null, const int32_t* pos_dev, int32_t* token_out, uint32_t* philox_out4,
                              int* status, void* stream);
+/* the token tail with sampler controls alone (tests/test_gpu_sampler_controls_kernel.py), forwarding to the engine's own
+ * launcher: as woq_probe_sample, plus counts uint32 [vocab] (read by the pre-pass, the picked token's entry + 1), ctl
+ * and its n_bias (id, value) pairs in HOST memory, adjusted_out = device fp32 [vocab] that receives the pre-pass's
+ * scores (bias, repetition / frequency / presence penalty; before the temperature), kept_out (nullable) = device uint32
+ * that a sampled draw sets to the number of ids it was over (after top-k, top-p and min_p). A refused configuration
+ * returns non-zero before anything is launched. */
+WOQ_API int woq_probe_sample_controls(const float* logits, int vocab, uint32_t* seen, uint32_t* counts,
+                                      const woq_sampler_config* cfg, const woq_sampler_controls* ctl,
+                                      const int32_t* bias_ids_host, const float* bias_vals_host, const float* u_or_null,
+                                      const int32_t* pos_dev, int32_t* token_out, float* adjusted_out,
+                                      uint32_t* kept_out, int* status, void* stream);
 /* the log-probability record alone (tests/test_gpu_logprob_kernel.py), forwarding to the engine's own launcher
  * unchanged: logits fp32 [vocab], token_dev = device int32 id whose log-probability goes to chosen_out[0];
  * top_id_out20 / top_lp_out20 = device int32 / fp32 [20]. Scratch is allocated and freed on `stream`. */

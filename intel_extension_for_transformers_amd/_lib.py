@@ -68,6 +68,15 @@ class SamplerConfig(ctypes.Structure):
                 ("seed_hi", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class SamplerControls(ctypes.Structure):
+    """struct woq_sampler_controls (include/woq_hip.h)."""
+
+    _fields_ = [("presence_penalty", ctypes.c_float), ("frequency_penalty", ctypes.c_float), ("min_p", ctypes.c_float),
+                ("n_bias", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+SAMPLER_MAX_BIAS = 1024  # logit_bias entries the native sampler takes (csrc/woq_sample.hip SAMPLER_MAX_BIAS)
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
 
 # every symbol include/woq_hip.h declares (tests check the .so exports all of them): ABI version 4, the frozen boundary
@@ -86,6 +95,7 @@ EXPORTS = [
     "woq_engine_uses_xq", "woq_engine_token_log_ptr", "woq_table_digit_planes",
     "woq_engine_set_sampler", "woq_engine_sampler_seen", "woq_engine_sampler_seen_ptr",
     "woq_engine_set_logprobs", "woq_engine_logprobs", "woq_engine_logprob_ptr", "woq_engine_prefill_scored",
+    "woq_engine_set_sampler_controls", "woq_engine_sampler_counts", "woq_engine_sampler_count_ptr",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -94,7 +104,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_rope_append", "woq_probe_attn_prefill", "woq_probe_attn_decode", "woq_probe_sample",
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
-    "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16",
+    "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16", "woq_probe_sample_controls",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -190,6 +200,12 @@ def lib():
     L.woq_engine_sampler_seen_ptr.restype = vp
     L.woq_engine_sampler_seen_ptr.argtypes = [vp]
     L.woq_probe_sample.argtypes = [vp, ci, vp, ctypes.POINTER(SamplerConfig), vp, vp, vp, vp, vp, vp]
+    L.woq_engine_set_sampler_controls.argtypes = [vp, ctypes.POINTER(SamplerControls), vp, vp]
+    L.woq_engine_sampler_counts.argtypes = [vp, vp, ci, ci, vp]
+    L.woq_engine_sampler_count_ptr.restype = vp
+    L.woq_engine_sampler_count_ptr.argtypes = [vp]
+    L.woq_probe_sample_controls.argtypes = [vp, ci, vp, vp, ctypes.POINTER(SamplerConfig),
+                                            ctypes.POINTER(SamplerControls)] + [vp] * 9
     L.woq_engine_set_logprobs.argtypes = [vp, ci]
     L.woq_engine_logprobs.argtypes = [vp]
     L.woq_engine_logprob_ptr.restype = vp
@@ -276,6 +292,31 @@ def probe_sample(logits, seen, cfg, pos, token_out, u=None, philox_out=None, sta
     opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
     rc = lib().woq_probe_sample(_ptr(logits), int(logits.numel()), _ptr(seen), ctypes.byref(cfg), opt(u), _ptr(pos),
                                 _ptr(token_out), opt(philox_out), opt(status), stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def sampler_controls(presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None):
+    """(woq_sampler_controls, int32 id array, float value array) from the OpenAI / HF option names (None = neutral);
+    `logit_bias` maps token ids to fp32 values (-inf = a ban). The arrays are ctypes arrays (None when empty)."""
+    items = sorted((int(k), float(v)) for k, v in dict(logit_bias or {}).items())
+    n = len(items)
+    ids = (ctypes.c_int32 * n)(*[k for k, _ in items]) if n else None
+    vals = (ctypes.c_float * n)(*[v for _, v in items]) if n else None
+    ctl = SamplerControls(presence_penalty=float(presence_penalty or 0.0), frequency_penalty=float(frequency_penalty or 0.0),
+                          min_p=float(min_p or 0.0), n_bias=n)
+    return ctl, ids, vals
+
+
+def probe_sample_controls(logits, seen, counts, cfg, controls, pos, token_out, adjusted_out, u=None, status=None,
+                          kept_out=None):
+    """the token tail with sampler controls alone (woq_probe_sample_controls): device tensors, `cfg` a SamplerConfig,
+    `controls` what `sampler_controls` returns, `kept_out` a device int32 [1] for the size of the drawn-from set, the
+    current stream."""
+    ctl, ids, vals = controls
+    rc = lib().woq_probe_sample_controls(_ptr(logits), int(logits.numel()), _ptr(seen), _ptr(counts), ctypes.byref(cfg),
+                                         ctypes.byref(ctl), ids, vals, _opt(u), _ptr(pos), _ptr(token_out),
+                                         _ptr(adjusted_out), _opt(kept_out), _opt(status), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
 

@@ -136,6 +136,17 @@ struct woq_engine {
   woq_sampler_config* samp_cfg = nullptr;
   uint32_t* samp_seen = nullptr;  // [(vocab + 31) / 32]
   int seen_words() const { return (cfg.vocab + 31) / 32; }
+  // sampler controls (logit bias, presence / frequency penalty, min_p): with `controls_on` the tail is the pre-pass +
+  // the sampling launch over its scratch (launch_sample_controls). Allocated by the first use, [vocab] each
+  bool controls_on = false;
+  woq_sampler_config samp_cfg_host = {};  // what samp_cfg holds (the controls' checks read do_sample)
+  woq_sampler_controls samp_ctl_host = {};  // what samp_ctl holds (set_sampler re-checks min_p against do_sample)
+  woq_sampler_controls* samp_ctl = nullptr;
+  float* samp_bias = nullptr;      // dense, NaN = no entry
+  uint32_t* samp_count = nullptr;  // times each id was generated in this request
+  float* samp_adj = nullptr;       // the pre-pass's scores
+  int32_t* samp_bias_ids = nullptr;  // [1024] + [1024] staging of the (id, value) pairs
+  float* samp_bias_vals = nullptr;
   // log-probability record (woq_logprob.hip): with `logprobs_on` every chaining step writes row pos - 1 of three logs,
   // [max_ctx + 1] rows each like tok_log, after its pick. Allocated by the first woq_engine_set_logprobs(e, 1)
   bool logprobs_on = false;
@@ -267,6 +278,11 @@ static bool engine_can_fuse_next(const woq_engine* e, int greedy) {
 }
 // the chaining tail with a sampler installed: token <- sample(logits), tok_log[pos] = token, pos += 1
 static void engine_sample(woq_engine* e, hipStream_t st) {
+  if (e->controls_on) {
+    launch_sample_controls(e->logits, e->cfg.vocab, e->samp_seen, e->samp_count, e->samp_bias, e->samp_cfg, e->samp_ctl,
+                           e->samp_adj, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr, e->fuse_status, st);
+    return;
+  }
   launch_sample(e->logits, e->cfg.vocab, e->samp_seen, e->samp_cfg, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr,
                 e->fuse_status, st);
 }
@@ -857,14 +873,80 @@ int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg) {
               "QBits: the native sampler needs the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
     const char* why = sampler_config_problem(*cfg);
     if (why) return woq::fail(why);
+    // the controls' own rule, whichever of the two entry points comes second
+    WOQ_CHECK(!(e->controls_on && e->samp_ctl_host.min_p > 0.f && cfg->do_sample == 0),
+              "QBits: min_p needs do_sample (greedy decoding keeps one token anyway)");
     // steps in flight on any stream still read the struct
     WOQ_HIP(hipDeviceSynchronize());
     WOQ_HIP(hipMemcpy(e->samp_cfg, cfg, sizeof(woq_sampler_config), hipMemcpyHostToDevice));
+    e->samp_cfg_host = *cfg;
   }
   const bool on = cfg != nullptr;
-  if (on != e->sampler_on) engine_drop_graphs(e);  // a captured graph holds the other tail
+  if (on != e->sampler_on || (!on && e->controls_on)) engine_drop_graphs(e);  // a captured graph holds the other tail
   e->sampler_on = on;
+  if (!on) e->controls_on = false;  // the controls live beside a sampler
   WOQ_END
+}
+
+// the controls' device memory, on first use (never inside a capture: both callers are host-synchronous set-up calls)
+static int engine_controls_alloc(woq_engine* e) {
+  WOQ_TRY
+  if (e->samp_count != nullptr) return 0;
+  const size_t v = (size_t)e->cfg.vocab;
+  char* buf = nullptr;  // [counts v][bias v][adj v][ids 1024][vals 1024][controls]
+  WOQ_HIP(hipMalloc((void**)&buf, (3 * v + 2048) * 4 + sizeof(woq_sampler_controls)));
+  WOQ_HIP(hipMemset(buf, 0, (3 * v + 2048) * 4 + sizeof(woq_sampler_controls)));
+  WOQ_HIP(hipMemset(buf + v * 4, 0xFF, v * 4));  // no bias entries
+  e->owned.push_back(buf);
+  e->samp_count = (uint32_t*)buf;
+  e->samp_bias = (float*)(buf + v * 4);
+  e->samp_adj = (float*)(buf + 2 * v * 4);
+  e->samp_bias_ids = (int32_t*)(buf + 3 * v * 4);
+  e->samp_bias_vals = (float*)(buf + (3 * v + 1024) * 4);
+  e->samp_ctl = (woq_sampler_controls*)(buf + (3 * v + 2048) * 4);
+  WOQ_END
+}
+
+int woq_engine_set_sampler_controls(woq_engine* e, const woq_sampler_controls* ctl, const int32_t* bias_ids_host,
+                                    const float* bias_vals_host) {
+  WOQ_TRY
+  WOQ_CHECK(e, "QBits: null engine");
+  if (ctl != nullptr) {
+    WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+              "QBits: the native sampler needs the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
+    WOQ_CHECK(e->sampler_on, "QBits: sampler controls need a sampler installed (woq_engine_set_sampler first)");
+    const char* why = sampler_controls_problem(*ctl, e->samp_cfg_host, e->cfg.vocab, bias_ids_host, bias_vals_host);
+    if (why) return woq::fail(why);
+    if (engine_controls_alloc(e) != 0) return 1;
+    WOQ_HIP(hipDeviceSynchronize());  // steps in flight on any stream still read the struct and the table
+    if (ctl->n_bias > 0) {
+      WOQ_HIP(hipMemcpy(e->samp_bias_ids, bias_ids_host, (size_t)ctl->n_bias * 4, hipMemcpyHostToDevice));
+      WOQ_HIP(hipMemcpy(e->samp_bias_vals, bias_vals_host, (size_t)ctl->n_bias * 4, hipMemcpyHostToDevice));
+    }
+    if (launch_sampler_bias_store(e->samp_bias, e->cfg.vocab, e->samp_bias_ids, e->samp_bias_vals, ctl->n_bias, nullptr) != 0)
+      return 1;
+    WOQ_HIP(hipMemcpy(e->samp_ctl, ctl, sizeof(woq_sampler_controls), hipMemcpyHostToDevice));
+    e->samp_ctl_host = *ctl;
+    WOQ_HIP(hipDeviceSynchronize());
+  }
+  const bool on = ctl != nullptr;
+  if (on != e->controls_on) engine_drop_graphs(e);  // a captured graph holds the other tail
+  e->controls_on = on;
+  WOQ_END
+}
+
+int woq_engine_sampler_counts(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e && n >= 0 && (tokens_dev != nullptr || n == 0), "QBits: bad sampler count arguments");
+  if (engine_controls_alloc(e) != 0) return 1;
+  if (clear) WOQ_HIP(hipMemsetAsync(e->samp_count, 0, (size_t)e->cfg.vocab * 4, (hipStream_t)stream));
+  launch_sampler_counts(e->samp_count, e->cfg.vocab, tokens_dev, n, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+void* woq_engine_sampler_count_ptr(woq_engine* e) {
+  return e && engine_controls_alloc(e) == 0 ? e->samp_count : nullptr;
 }
 
 int woq_engine_sampler_seen(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream) {

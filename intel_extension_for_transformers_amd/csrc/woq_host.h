@@ -139,6 +139,23 @@ void launch_sampler_seen(uint32_t* seen, int vocab, const int32_t* tokens, int n
 void launch_sampler_config_store(const woq_sampler_config& cfg, woq_sampler_config* dst, hipStream_t st);
 // null when the native sampler takes this combination, else the "QBits: ..." reason
 const char* sampler_config_problem(const woq_sampler_config& cfg);
+// The same choice with sampler controls: a pre-pass over the whole chip writes adj[i] = the score of id i after the logit
+// bias (dense table `bias`, NaN = no entry), the repetition penalty and the frequency / presence penalties over
+// `counts` (uint32 [vocab], times generated), then the sampling workgroup runs over `adj` (min_p from ctl_dev) and also
+// does counts[token] += 1. Two launches whose shapes depend on the vocabulary alone; `logits` is only read.
+void launch_sample_controls(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
+                            const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev, float* adj,
+                            const float* u_dev, int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed,
+                            int32_t* log, uint32_t* philox_out, int* status, hipStream_t st,
+                            uint32_t* kept_out = nullptr);  // (nullable) ids a sampled draw was over
+// counts[tokens[j]] += 1 for j in [0, n) (ids outside [0, vocab) are ignored)
+void launch_sampler_counts(uint32_t* counts, int vocab, const int32_t* tokens, int n, hipStream_t st);
+// bias[0..vocab) = NaN ("no entry"), then bias[ids_dev[j]] = vals_dev[j] for j in [0, n); stream-ordered
+int launch_sampler_bias_store(float* bias, int vocab, const int32_t* ids_dev, const float* vals_dev, int n, hipStream_t st);
+void launch_sampler_controls_store(const woq_sampler_controls& ctl, woq_sampler_controls* dst, hipStream_t st);
+// null when the controls are acceptable beside `cfg` (ids / vals: ctl.n_bias host entries), else the "QBits: ..." reason
+const char* sampler_controls_problem(const woq_sampler_controls& ctl, const woq_sampler_config& cfg, int vocab,
+                                     const int32_t* ids, const float* vals);
 
 // ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
 // After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at

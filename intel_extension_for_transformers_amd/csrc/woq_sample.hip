@@ -14,6 +14,20 @@
 //  - top_k = 0 (top_p = 1): softmax over the whole vocabulary, the same inverse-CDF rule over ids in ascending order.
 // u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 with counter (position, 0, 0, 0) and key (seed_lo, seed_hi): a draw
 // depends on (seed, position, logits) only, so eager steps and graphs of any burst size give the same tokens.
+//
+// Sampler controls (woq_sampler_controls: logit bias, presence / frequency penalty, min_p). With them installed a pre-pass
+// over the whole chip (score_adjust_kernel, one id per thread) writes, for every id, the fp32 score
+//   s = l; s = s + b[i] (ids with a bias entry); repetition penalty as above; for ids generated c[i] > 0 times
+//   s = s - (freq * (float)c[i]); s = s - pres
+// — every operation rounded on its own (compiled with fp contraction off: no fma) — into an engine-owned
+// scratch, and the sampling workgroup runs over that scratch with its own penalty step off (sample_kernel<true>): its six
+// walks over the vocabulary stay one load per visit. A dense bias table holds NaN where an id has no entry (a bias is
+// never NaN), so `-0.0` stays `-0.0` there. min_p (HF MinPLogitsWarper after top-k / top-p): a candidate stays iff
+// w_i = expf(s_i - s_0) >= min_p; in the whole-vocabulary walk a weight below min_p counts as 0. The finishing thread
+// also counts its pick in c. The logits themselves are never modified (the log-probability record reads them).
+#include <algorithm>
+#include <vector>
+
 #include "woq_device.h"
 #include "woq_host.h"
 #include "woq_score_key.h"
@@ -25,6 +39,7 @@ namespace {
 constexpr int SAMPLE_THREADS = 1024;
 constexpr int SAMPLE_WAVES = SAMPLE_THREADS / 64;
 constexpr int SAMPLE_MAX_CAND = 1024;
+constexpr int SAMPLER_MAX_BIAS = 1024;
 
 struct ScoreArgs {
   const float* logits;
@@ -104,11 +119,16 @@ __device__ __forceinline__ unsigned long long block_best(const ScoreArgs& a, int
 }
 
 // `advance` != 0: the engine's chain — log[pos] = token, pos += 1 (the next step's embedding kernel guards max_ctx)
+// CTL (sampler controls): `logits` is the pre-pass's adjusted-score scratch (no penalty step here), min_p comes from
+// `ctlp`, the pick is counted in `counts` and kept_out (nullable; the probe's) receives how many ids a sampled draw
+// was over; without CTL all three are unused and the kernel is the one it always was
+template <bool CTL>
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     const float* __restrict__ logits, int vocab, uint32_t* __restrict__ seen, const woq_sampler_config* __restrict__ cfgp,
     const float* __restrict__ u_in, int32_t* __restrict__ token, int32_t* __restrict__ pos_io,
     const int32_t* __restrict__ pos_ro, int32_t* __restrict__ log, uint32_t* __restrict__ philox_out,
-    int* __restrict__ status) {
+    int* __restrict__ status, const woq_sampler_controls* __restrict__ ctlp, uint32_t* __restrict__ counts,
+    uint32_t* __restrict__ kept_out) {
   __shared__ unsigned int hist[256];
   __shared__ unsigned long long cand[SAMPLE_MAX_CAND];
   __shared__ float cdf[SAMPLE_MAX_CAND];
@@ -123,7 +143,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   const bool do_sample = cfg.do_sample != 0;
   ScoreArgs sa;
   sa.logits = logits, sa.seen = seen, sa.pen = cfg.repetition_penalty, sa.temp = cfg.temperature;
-  sa.use_pen = cfg.repetition_penalty != 1.0f, sa.scale = do_sample;
+  sa.use_pen = !CTL && cfg.repetition_penalty != 1.0f, sa.scale = do_sample;
+  float min_p = 0.f;
+  if constexpr (CTL) min_p = ctlp->min_p;
 
   // what the finishing thread does with its pick (exactly one thread calls it; every read of `seen` lies before a
   // barrier that this thread has passed)
@@ -131,6 +153,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     const int p = pos_io != nullptr ? pos_io[0] : (pos_ro != nullptr ? pos_ro[0] : 0);
     token[0] = tok;
     atomicOr(&seen[tok >> 5], 1u << (tok & 31));
+    if constexpr (CTL) counts[tok] += 1u;
     if (log != nullptr) log[p] = tok;
     if (pos_io != nullptr) pos_io[0] = p + 1;
     if (flags != 0 && status != nullptr) atomicOr(status, flags);
@@ -166,12 +189,27 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     auto weight = [&](int i) -> float {
       if (i >= w_hi) return 0.f;
       const float s = score_at(sa, i);
-      return s != s ? 0.f : (s == s_max ? 1.f : expf(s - s_max));
+      const float wv = s != s ? 0.f : (s == s_max ? 1.f : expf(s - s_max));
+      if constexpr (CTL) return wv >= min_p ? wv : 0.f;
+      return wv;
     };
     float running = 0.f;
-    for (int b = w_lo; b < w_hi; b += 64) running += __shfl(wave_scan_f32(weight(b + lane), lane), 63, 64);
+    unsigned int n_mass = 0u;
+    for (int b = w_lo; b < w_hi; b += 64) {
+      const float wv = weight(b + lane);
+      if constexpr (CTL) n_mass += (unsigned int)__popcll(__ballot(wv > 0.f));
+      running += __shfl(wave_scan_f32(wv, lane), 63, 64);
+    }
     if (lane == 0) wsum[wid] = running;
+    if constexpr (CTL)
+      if (lane == 0) wcnt[wid] = n_mass;
     __syncthreads();
+    if constexpr (CTL)
+      if (tid == 0 && kept_out != nullptr) {
+        unsigned int total = 0u;
+        for (int w = 0; w < SAMPLE_WAVES; ++w) total += wcnt[w];
+        kept_out[0] = total;
+      }
     float z = 0.f;
     for (int w = 0; w < SAMPLE_WAVES; ++w) z += wsum[w];
     const float target = u * z;
@@ -310,9 +348,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   cdf[tid] = c;
   __syncthreads();
   if (cfg.top_p < 1.0f && tid >= 1 && tid < (int)n && z - cdf[tid - 1] <= (1.0f - cfg.top_p) * z) atomicMin(&slot[2], (unsigned int)tid);
+  if constexpr (CTL)  // min_p: sorted candidates, so the kept ones are a prefix too (the first weighs exactly 1)
+    if (tid >= 1 && tid < (int)n && !(w >= min_p)) atomicMin(&slot[2], (unsigned int)tid);
   __syncthreads();
   const unsigned int m = slot[2];  // kept: the first m candidates (m >= 1)
   if (tid == 0) slot[3] = m - 1u;
+  if constexpr (CTL)
+    if (tid == 0 && kept_out != nullptr) kept_out[0] = m;
   __syncthreads();
   const float target = u * cdf[m - 1u];
   if (tid < (int)m && w > 0.f && c > target) atomicMin(&slot[3], (unsigned int)tid);
@@ -329,14 +371,84 @@ __global__ void sampler_seen_kernel(uint32_t* __restrict__ seen, int vocab, cons
 
 // a host struct into device memory as a kernel argument: stream-ordered and capturable, whatever the host memory is
 __global__ void sampler_config_store_kernel(woq_sampler_config v, woq_sampler_config* __restrict__ dst) { *dst = v; }
+__global__ void sampler_controls_store_kernel(woq_sampler_controls v, woq_sampler_controls* __restrict__ dst) { *dst = v; }
+
+constexpr int ADJUST_THREADS = 256;  // one id per thread: 125 .. 501 workgroups for 32000 .. 128256 ids, four loads each
+
+// steps 1-4 of the controls' contract for every id (the header comment); `adj` is what sample_kernel<true> reads
+__global__ __launch_bounds__(ADJUST_THREADS) void score_adjust_kernel(
+    const float* __restrict__ logits, int vocab, const uint32_t* __restrict__ seen, const uint32_t* __restrict__ counts,
+    const float* __restrict__ bias, const woq_sampler_config* __restrict__ cfgp,
+    const woq_sampler_controls* __restrict__ ctlp, float* __restrict__ adj) {
+// No contraction: `s - freq * c` must round twice. Plain operators under this pragma — HIP's __fmul_rn / __fsub_rn are
+// inline functions over plain operators that carry their header's contract flag, and fuse into one fma once inlined.
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * ADJUST_THREADS + threadIdx.x;
+  if (i >= vocab) return;
+  const float pen = cfgp->repetition_penalty, pres = ctlp->presence_penalty, freq = ctlp->frequency_penalty;
+  float s = logits[i];
+  const float b = bias[i];
+  if (b == b) s = s + b;  // NaN = no entry
+  if (pen != 1.0f && ((seen[i >> 5] >> (i & 31)) & 1u)) s = s < 0.f ? s * pen : s / pen;
+  const uint32_t c = counts[i];
+  if (c > 0u) {
+    const float step = freq * (float)c;
+    s = s - step;
+    s = s - pres;
+  }
+  adj[i] = s;
+}
+
+__global__ void sampler_counts_kernel(uint32_t* __restrict__ counts, int vocab, const int32_t* __restrict__ tokens, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int t = tokens[i];
+  if (t >= 0 && t < vocab) atomicAdd(&counts[t], 1u);
+}
+
+// bias[ids[j]] = vals[j] over a table that launch_sampler_bias_store has just filled with NaN (ids checked by the host)
+__global__ void sampler_bias_scatter_kernel(float* __restrict__ bias, int vocab, const int32_t* __restrict__ ids,
+                                            const float* __restrict__ vals, int n) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int t = ids[j];
+  if (t >= 0 && t < vocab) bias[t] = vals[j];
+}
 
 }  // namespace
 
 void launch_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg_dev, const float* u_dev,
                    int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out,
                    int* status, hipStream_t st) {
-  hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(SAMPLE_THREADS), 0, st, logits, vocab, seen, cfg_dev, u_dev, token,
-                     pos_advance, pos_fixed, log, philox_out, status);
+  hipLaunchKernelGGL(sample_kernel<false>, dim3(1), dim3(SAMPLE_THREADS), 0, st, logits, vocab, seen, cfg_dev, u_dev,
+                     token, pos_advance, pos_fixed, log, philox_out, status, (const woq_sampler_controls*)nullptr,
+                     (uint32_t*)nullptr, (uint32_t*)nullptr);
+}
+
+void launch_sample_controls(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
+                            const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev, float* adj,
+                            const float* u_dev, int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed,
+                            int32_t* log, uint32_t* philox_out, int* status, hipStream_t st, uint32_t* kept_out) {
+  hipLaunchKernelGGL(score_adjust_kernel, dim3((vocab + ADJUST_THREADS - 1) / ADJUST_THREADS), dim3(ADJUST_THREADS), 0, st,
+                     logits, vocab, (const uint32_t*)seen, (const uint32_t*)counts, bias, cfg_dev, ctl_dev, adj);
+  hipLaunchKernelGGL(sample_kernel<true>, dim3(1), dim3(SAMPLE_THREADS), 0, st, (const float*)adj, vocab, seen, cfg_dev,
+                     u_dev, token, pos_advance, pos_fixed, log, philox_out, status, ctl_dev, counts, kept_out);
+}
+
+void launch_sampler_counts(uint32_t* counts, int vocab, const int32_t* tokens, int n, hipStream_t st) {
+  if (n > 0) hipLaunchKernelGGL(sampler_counts_kernel, dim3((n + 255) / 256), dim3(256), 0, st, counts, vocab, tokens, n);
+}
+
+int launch_sampler_bias_store(float* bias, int vocab, const int32_t* ids_dev, const float* vals_dev, int n, hipStream_t st) {
+  WOQ_TRY
+  WOQ_HIP(hipMemsetAsync(bias, 0xFF, (size_t)vocab * 4, st));  // 0xFFFFFFFF: a NaN, "no entry"
+  if (n > 0)
+    hipLaunchKernelGGL(sampler_bias_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, st, bias, vocab, ids_dev, vals_dev, n);
+  WOQ_END
+}
+
+void launch_sampler_controls_store(const woq_sampler_controls& ctl, woq_sampler_controls* dst, hipStream_t st) {
+  hipLaunchKernelGGL(sampler_controls_store_kernel, dim3(1), dim3(1), 0, st, ctl, dst);
 }
 
 void launch_sampler_seen(uint32_t* seen, int vocab, const int32_t* tokens, int n, hipStream_t st) {
@@ -360,6 +472,24 @@ const char* sampler_config_problem(const woq_sampler_config& c) {
   return nullptr;
 }
 
+const char* sampler_controls_problem(const woq_sampler_controls& c, const woq_sampler_config& cfg, int vocab,
+                                     const int32_t* ids, const float* vals) {
+  if (c.presence_penalty * 0.f != 0.f || c.frequency_penalty * 0.f != 0.f)
+    return "QBits: presence_penalty and frequency_penalty must be finite floats";
+  if (!(c.min_p >= 0.f && c.min_p <= 1.f)) return "QBits: min_p must be in [0, 1]";
+  if (c.min_p > 0.f && cfg.do_sample == 0) return "QBits: min_p needs do_sample (greedy decoding keeps one token anyway)";
+  if (c.n_bias < 0 || c.n_bias > SAMPLER_MAX_BIAS) return "QBits: the native sampler takes at most 1024 logit_bias entries";
+  if (c.n_bias > 0 && (ids == nullptr || vals == nullptr)) return "QBits: logit_bias entries without their arrays";
+  std::vector<int32_t> sorted(ids, ids + c.n_bias);
+  std::sort(sorted.begin(), sorted.end());
+  for (int j = 0; j < c.n_bias; ++j) {
+    if (sorted[j] < 0 || sorted[j] >= vocab) return "QBits: logit_bias token id outside the vocabulary";
+    if (j > 0 && sorted[j] == sorted[j - 1]) return "QBits: duplicate logit_bias token id";
+    if (vals[j] != vals[j] || vals[j] == INFINITY) return "QBits: a logit_bias value must be finite or -inf (a ban)";
+  }
+  return nullptr;
+}
+
 }  // namespace woq
 
 extern "C" {
@@ -378,6 +508,46 @@ WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, con
   woq::launch_sample(logits, vocab, seen, cfg_dev, u_or_null, token_out, nullptr, pos_dev, nullptr, philox_out4, status,
                      st);
   WOQ_HIP(hipFreeAsync(cfg_dev, st));
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_sample_controls(const float* logits, int vocab, uint32_t* seen, uint32_t* counts,
+                                      const woq_sampler_config* cfg, const woq_sampler_controls* ctl,
+                                      const int32_t* bias_ids_host, const float* bias_vals_host, const float* u_or_null,
+                                      const int32_t* pos_dev, int32_t* token_out, float* adjusted_out,
+                                      uint32_t* kept_out, int* status, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(logits && seen && counts && cfg && ctl && pos_dev && token_out && adjusted_out && vocab >= 1,
+            "QBits: bad sampler probe arguments");
+  const char* why = woq::sampler_config_problem(*cfg);
+  if (why == nullptr) why = woq::sampler_controls_problem(*ctl, *cfg, vocab, bias_ids_host, bias_vals_host);
+  if (why) return woq::fail(why);
+  const hipStream_t st = (hipStream_t)stream;
+  const int n = ctl->n_bias;
+  char* buf = nullptr;  // [config 32][controls 32][bias table vocab * 4][ids n * 4][values n * 4]
+  const size_t table = 64, ids_at = table + (size_t)vocab * 4, vals_at = ids_at + (size_t)n * 4;
+  WOQ_HIP(hipMallocAsync((void**)&buf, vals_at + (size_t)n * 4 + 4, st));
+  if (n > 0) {  // the host arrays may go away when this returns: copies that have completed by then
+    hipError_t err = hipMemcpyAsync(buf + ids_at, bias_ids_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipMemcpyAsync(buf + vals_at, bias_vals_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) {
+      hipFreeAsync(buf, st);
+      return woq::fail(std::string("QBits: HIP error '") + hipGetErrorString(err) + "' copying the logit_bias entries");
+    }
+  }
+  woq_sampler_config* cfg_dev = (woq_sampler_config*)buf;
+  woq_sampler_controls* ctl_dev = (woq_sampler_controls*)(buf + 32);
+  woq::launch_sampler_config_store(*cfg, cfg_dev, st);
+  woq::launch_sampler_controls_store(*ctl, ctl_dev, st);
+  int rc = woq::launch_sampler_bias_store((float*)(buf + table), vocab, (const int32_t*)(buf + ids_at),
+                                          (const float*)(buf + vals_at), n, st);
+  if (rc == 0)
+    woq::launch_sample_controls(logits, vocab, seen, counts, (const float*)(buf + table), cfg_dev, ctl_dev, adjusted_out,
+                                u_or_null, token_out, nullptr, pos_dev, nullptr, nullptr, status, st, kept_out);
+  WOQ_HIP(hipFreeAsync(buf, st));
+  if (rc) return rc;
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }

@@ -1,7 +1,7 @@
 """Configuration objects of the chat pipeline — field names and defaults of the reference's neural_chat/config.py
 (GenerationConfig :400-423, LoadingModelConfig :426-436, PipelineConfig :466-517) for the fields this path reads."""
 from dataclasses import dataclass
-from typing import List
+from typing import Dict, List
 
 
 @dataclass
@@ -21,6 +21,12 @@ class GenerationConfig:
     return_stats: bool = False
     format_version: str = "v2"
     task: str = ""
+    # OpenAI / vLLM sampling controls, applied on the device by the engine's sampler (runtime.engine set_sampler):
+    presence_penalty: float = 0.0   # subtracted once from the score of every token generated so far
+    frequency_penalty: float = 0.0  # subtracted once per time a token was generated so far
+    min_p: float = 0.0              # sampling keeps tokens at least min_p times as likely as the likeliest
+    logit_bias: Dict[int, float] = None  # token id -> value added to its logit ahead of the penalties (-inf = a ban)
+    seed: int = None                # a sampled request with a seed is reproducible (None: torch's CPU generator)
     logprobs: int = None  # 0..20: fill BaseModel.last_logprobs with every emitted token's log-probability + alternatives
 
 

@@ -191,10 +191,21 @@ class BaseModel:
                 yield text[len(shown):]
                 shown = text
 
+    @staticmethod
+    def _sampler_controls(config):
+        """the request's sampling controls as `iter_sampled_auto` keywords (neutral values where the config has none)"""
+        return dict(presence_penalty=getattr(config, "presence_penalty", 0.0) or 0.0,
+                    frequency_penalty=getattr(config, "frequency_penalty", 0.0) or 0.0,
+                    min_p=(getattr(config, "min_p", 0.0) or 0.0) if config.do_sample else 0.0,  # a warper: sampling only
+                    logit_bias=dict(getattr(config, "logit_bias", None) or {}), seed=getattr(config, "seed", None))
+
     def _engine_stream(self, ids, config, n_out):
         eng, tok = self.engine, self.tokenizer
         eos = tok.eos_token_id
-        if config.do_sample or (config.repetition_penalty or 1.0) != 1.0:
+        ctl = self._sampler_controls(config)
+        # a penalty or a bias with temperature 0 is a greedy request over the penalised scores: the sampler's argmax
+        if config.do_sample or (config.repetition_penalty or 1.0) != 1.0 or ctl["presence_penalty"] \
+                or ctl["frequency_penalty"] or ctl["logit_bias"]:
             yield from self._engine_stream_sampled(ids, config, n_out)
             return
         if getattr(config, "logprobs", None) is not None:  # the same greedy chain, with the step's records read back
@@ -233,12 +244,13 @@ class BaseModel:
                 iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
                                   do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
                                   top_p=config.top_p, repetition_penalty=config.repetition_penalty,
-                                  logprobs=config.logprobs), n_out)
+                                  logprobs=config.logprobs, **self._sampler_controls(config)), n_out)
             return
         out, shown = [], ""
         for new in iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
                                      do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
-                                     top_p=config.top_p, repetition_penalty=config.repetition_penalty):
+                                     top_p=config.top_p, repetition_penalty=config.repetition_penalty,
+                                     **self._sampler_controls(config)):
             for t in new:
                 if eos is not None and t == eos:
                     continue
@@ -253,17 +265,27 @@ class BaseModel:
         import torch
         from transformers import TextIteratorStreamer
 
+        ctl = self._sampler_controls(config)
+        if ctl["presence_penalty"] or ctl["frequency_penalty"] or ctl["logit_bias"]:
+            # HF's generate has no presence / frequency penalty and no OpenAI logit_bias: refuse, never ignore
+            raise RuntimeError("QBits: presence_penalty, frequency_penalty and logit_bias need the fused engine (one "
+                               "sequence, one beam, prompt + max_new_tokens within its context)")
         streamer = TextIteratorStreamer(self.tokenizer, skip_prompt=True, skip_special_tokens=True)
         gen = dict(max_new_tokens=config.max_new_tokens, do_sample=config.do_sample, num_beams=config.num_beams,
                    use_cache=config.use_cache, repetition_penalty=config.repetition_penalty,
                    num_return_sequences=config.num_return_sequences, pad_token_id=self.tokenizer.eos_token_id)
         if config.do_sample:
             gen.update(temperature=config.temperature, top_k=config.top_k, top_p=config.top_p)
+            if ctl["min_p"]:
+                gen.update(min_p=ctl["min_p"])
         err = []
         result = []
+        seed = ctl["seed"]
 
         def work():
             try:
+                if seed is not None and config.do_sample:  # HF's loop draws from torch's default generator
+                    torch.manual_seed(int(seed) & (2 ** 63 - 1))
                 with torch.no_grad():
                     result.append(self.model.generate(ids.to("cuda"), streamer=streamer, **gen))
             except Exception as e:  # surfaced on the consumer side, like the reference's errors_queue

@@ -39,6 +39,9 @@ class ChatCompletionRequest(_Wire):
     repetition_penalty: Optional[float] = 1.0
     presence_penalty: Optional[float] = 0.0
     frequency_penalty: Optional[float] = 0.0
+    logit_bias: Optional[Dict[str, float]] = None  # token-id strings -> [-100, 100], as OpenAI sends them
+    seed: Optional[int] = None
+    min_p: Optional[float] = None
     user: Optional[str] = None
     logprobs: Optional[bool] = False
     top_logprobs: Optional[int] = None
@@ -58,6 +61,9 @@ class CompletionRequest(_Wire):
     repetition_penalty: Optional[float] = 1.0
     presence_penalty: Optional[float] = 0.0
     frequency_penalty: Optional[float] = 0.0
+    logit_bias: Optional[Dict[str, float]] = None  # token-id strings -> [-100, 100], as OpenAI sends them
+    seed: Optional[int] = None
+    min_p: Optional[float] = None
     user: Optional[str] = None
     logprobs: Optional[int] = None
     prompt_logprobs: Optional[int] = None  # 0..20: score the PROMPT's tokens (choices[i].prompt_logprobs)
@@ -70,6 +76,42 @@ def _error(status, message):
 
 MAX_N = 8           # completions per request
 MAX_TOKENS = 8192   # new tokens per completion
+MAX_LOGIT_BIAS = 300  # logit_bias entries per request (OpenAI's bound)
+
+
+def _vocab_size(bot):
+    """ids the model scores: the engine's vocabulary, else the tokenizer's length, else unknown (None)"""
+    cfg = getattr(getattr(bot, "engine", None), "cfg", None)
+    if cfg is not None:
+        return int(cfg.vocab)
+    tok = getattr(bot, "tokenizer", None)
+    return len(tok) if hasattr(tok, "__len__") else None
+
+
+def _check_sampler_controls(req):
+    """presence / frequency penalty, logit_bias and min_p: OpenAI's ranges, the file's message style."""
+    for name in ("presence_penalty", "frequency_penalty"):
+        v = getattr(req, name)
+        if v is not None and not v >= -2:  # (a NaN fails the first test)
+            return "%s is less than the minimum of -2 - '%s'" % (v, name)
+        if v is not None and v > 2:
+            return "%s is greater than the maximum of 2 - '%s'" % (v, name)
+    if req.min_p is not None and not 0 <= req.min_p <= 1:
+        return "%s is outside [0, 1] - 'min_p'" % req.min_p
+    bias = req.logit_bias or {}
+    if len(bias) > MAX_LOGIT_BIAS:
+        return "%s is greater than the maximum of %d - 'logit_bias' entries" % (len(bias), MAX_LOGIT_BIAS)
+    vocab = _vocab_size(router.get_chatbot()) if bias else None
+    for key, v in bias.items():
+        try:
+            tid = int(key)
+        except (TypeError, ValueError):
+            return "%r is not a token id - 'logit_bias'" % (key,)
+        if str(tid) != str(key).strip() or tid < 0 or (vocab is not None and tid >= vocab):
+            return "%r is not a token id of this model - 'logit_bias'" % (key,)
+        if not -100 <= v <= 100:
+            return "%s is outside [-100, 100] - 'logit_bias'" % v
+    return None
 
 
 def _check_ranges(req):
@@ -91,7 +133,7 @@ def _check_ranges(req):
         return "%s is outside [0, 1] - 'top_p'" % req.top_p
     if req.top_k is not None and -1 < req.top_k < 1:
         return "%s is out of Range. Either set top_k to -1 or >=1." % req.top_k
-    return _check_logprobs(req)
+    return _check_sampler_controls(req) or _check_logprobs(req)
 
 
 def _wanted_logprobs(req):
@@ -196,11 +238,14 @@ class TextChatAPIRouter(APIRouter):
     @staticmethod
     def generation_config(req, default_max_tokens):
         greedy = not req.temperature or req.top_k == 1
+        bias = {int(k): float(v) for k, v in (req.logit_bias or {}).items()}
         return GenerationConfig(temperature=req.temperature if req.temperature else 1.0, top_p=req.top_p,
                                 top_k=req.top_k if req.top_k and req.top_k > 0 else 0,
                                 repetition_penalty=req.repetition_penalty or 1.0,
                                 max_new_tokens=req.max_tokens or default_max_tokens, do_sample=not greedy,
-                                task="chat")
+                                task="chat", presence_penalty=req.presence_penalty or 0.0,
+                                frequency_penalty=req.frequency_penalty or 0.0, min_p=req.min_p or 0.0,
+                                logit_bias=bias or None, seed=req.seed)
 
     @staticmethod
     def _stops(req, conv=None):

@@ -74,6 +74,7 @@ class WoqDecoderEngine:
         self._comm = None
         self.captured = False
         self.sampler_installed = False     # native sampler in the chaining tail (set_sampler / clear_sampler)
+        self.controls_installed = False    # ... with logit bias / presence / frequency penalty / min_p beside it
         self.native_sampled_requests = 0   # requests that ran with it (iter_generate)
         self.logprobs_on = False           # log-probability record after every chaining pick (set_logprobs)
         # hipGraph capture is not allowed on the legacy null stream torch uses by default
@@ -417,17 +418,26 @@ class WoqDecoderEngine:
     # ---- native sampler: the next token of a chaining step chosen by csrc/woq_sample.hip ---------------------------
     NATIVE_TOP_K_MAX = 1024
 
-    def native_sampler_supports(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0):
-        """True when `set_sampler` takes this request (the checks of csrc/woq_sample.hip `sampler_config_problem`): one
-        GPU (a tensor-parallel head is vocab-sharded); a positive penalty alone; sampling with a positive finite
-        temperature and 1 <= top_k <= 1024 with any top_p, or top_k = 0 with top_p = 1. Everything else keeps
-        `iter_sampled` + `DeviceSampler`, which answers or raises as it always did."""
+    def native_sampler_supports(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
+                                presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None):
+        """True when `set_sampler` takes this request (the checks of csrc/woq_sample.hip `sampler_config_problem` and
+        `sampler_controls_problem`): one GPU (a tensor-parallel head is vocab-sharded); a positive penalty alone;
+        sampling with a positive finite temperature and 1 <= top_k <= 1024 with any top_p, or top_k = 0 with top_p = 1;
+        finite presence / frequency penalties, min_p in [0, 1] (> 0 only when sampling), at most 1024 bias entries
+        inside the vocabulary, each finite or -inf. Everything else keeps `iter_sampled` + `DeviceSampler`, which
+        answers or raises as it always did."""
         if self.cfg.tp_size > 1 or self._comm is not None or self._allreduce_cb is not None:
             return False
         if not float(1.0 if repetition_penalty is None else repetition_penalty) > 0.0:
             return False
+        pres, freq, min_p, bias = _controls(presence_penalty, frequency_penalty, min_p, logit_bias)
+        if not (math.isfinite(pres) and math.isfinite(freq) and 0.0 <= min_p <= 1.0):
+            return False
+        if len(bias) > L.SAMPLER_MAX_BIAS or any(not 0 <= k < self.cfg.vocab or v != v or v == float("inf")
+                                                 for k, v in bias.items()):
+            return False
         if not do_sample:
-            return True
+            return min_p == 0.0
         temperature = float(1.0 if temperature is None else temperature)
         if not (temperature > 0.0 and math.isfinite(temperature)):
             return False
@@ -436,25 +446,57 @@ class WoqDecoderEngine:
             return False
         return top_k > 0 or top_p >= 1.0
 
-    def set_sampler(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):
+    def set_sampler(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0,
+                    presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None):
         """Install (or re-parameterise) the native sampler: from now on every chaining step — the prompt pass's tail,
         `step`, `run`, `replay` — picks its token with Hugging Face's repetition penalty / temperature / top-k / top-p in
         HF's order and a Philox draw keyed by (`seed`, position). Installing drops a captured graph; changing the
-        parameters of an installed sampler does not (the kernel reads them from device memory)."""
+        parameters of an installed sampler does not (the kernel reads them from device memory).
+        `presence_penalty` / `frequency_penalty` (OpenAI's, over the tokens generated in this request), `min_p` (HF's
+        MinPLogitsWarper) and `logit_bias` ({token id: value}, -inf = a ban, added ahead of the penalties): the sampler
+        controls, installed only when one of them is not neutral — one more launch per step (a pre-pass over the
+        vocabulary). Installing or removing them drops a captured graph; changing their values does not."""
         if do_sample and float(1.0 if temperature is None else temperature) <= 0:
             raise ValueError("`temperature` has to be a strictly positive float when sampling")
         cfg = L.sampler_config(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
         L.check(L.lib().woq_engine_set_sampler(self._h, ctypes.byref(cfg)))
+        was_installed = self.sampler_installed
         if not self.sampler_installed:
             self.captured = False
         self.sampler_installed = True
+        pres, freq, min_p, bias = _controls(presence_penalty, frequency_penalty, min_p, logit_bias)
+        if pres != 0.0 or freq != 0.0 or min_p != 0.0 or bias:
+            ctl, ids, vals = L.sampler_controls(pres, freq, min_p, bias)
+            if L.lib().woq_engine_set_sampler_controls(self._h, ctypes.byref(ctl), ids, vals) != 0:
+                why = L.lib().woq_last_error().decode()
+                if not was_installed:  # refused controls leave no half-installed sampler behind
+                    self.clear_sampler()
+                raise RuntimeError(why)
+            if not self.controls_installed:
+                self.captured = False
+            self.controls_installed = True
+        elif self.controls_installed:
+            L.check(L.lib().woq_engine_set_sampler_controls(self._h, None, None, None))
+            self.captured = False
+            self.controls_installed = False
 
     def clear_sampler(self):
-        """Back to the plain greedy tail (drops a graph captured with the sampler)."""
+        """Back to the plain greedy tail (drops a graph captured with the sampler; removes the controls too)."""
         L.check(L.lib().woq_engine_set_sampler(self._h, None))
         if self.sampler_installed:
             self.captured = False
-        self.sampler_installed = False
+        self.sampler_installed = self.controls_installed = False
+
+    def mark_counts(self, token_ids, clear=True):
+        """The frequency / presence penalties' history: count `token_ids` (after zeroing the table when `clear`). The
+        sampled tail counts every token it picks itself; `iter_generate` starts a request from zero."""
+        t = torch.as_tensor(token_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        L.check(L.lib().woq_engine_sampler_counts(self._h, t.data_ptr() if t.numel() else None, int(t.numel()),
+                                                  int(bool(clear)), L.stream_ptr()))
+
+    def token_counts(self):
+        """uint32-as-int32 view [vocab] of how often each id was generated in this request."""
+        return _device_view(L.lib().woq_engine_sampler_count_ptr(self._h), (self.cfg.vocab,), self.device, "<i4")
 
     def mark_seen(self, token_ids, clear=True):
         """The repetition penalty's history: set the bits of `token_ids` (after emptying the set when `clear`)."""
@@ -580,6 +622,8 @@ class WoqDecoderEngine:
                                % (n, max_new_tokens, self.cfg.max_ctx))
         if self.sampler_installed:
             self.mark_seen(ids, clear=True)
+            if self.controls_installed:
+                self.mark_counts([], clear=True)  # prompt tokens do not count: the penalties are over generated ids
             self.native_sampled_requests += 1
         for s0 in range(0, n, chunk):
             # the sampled tail marks its pick in the history, so with a sampler only the last chunk may end on it: an
@@ -665,7 +709,17 @@ class DeviceSampler:
     `torch.multinomial` on the softmax; argmax otherwise. Plain torch ops in HF's order (checked against the HF classes in
     tests/test_api_cpu.py); no host synchronisation — the caller reads tokens back in bursts."""
 
-    def __init__(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, generator=None):
+    def __init__(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, generator=None,
+                 presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None):
+        """`logit_bias` ({token id: value}, HF's single-token `sequence_bias`, -inf = a suppressed token) is added ahead
+        of the repetition penalty (where HF's SequenceBiasLogitsProcessor sits); `frequency_penalty` / `presence_penalty`
+        (OpenAI's: `s - frequency * count`, then `s - presence`, over the ids GENERATED so far) follow it; `min_p` is HF's
+        MinPLogitsWarper after top-p. The order of csrc/woq_sample.hip, every step one fp32 torch op."""
+        self.presence, self.frequency, self.min_p, self.bias = _controls(presence_penalty, frequency_penalty, min_p,
+                                                                         logit_bias)
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError("`min_p` has to be a float in the range [0, 1]")
+        self._bias_dev = None
         self.do_sample = bool(do_sample)
         self.temperature = float(temperature if temperature is not None else 1.0)
         self.top_k = int(top_k or 0)
@@ -675,12 +729,31 @@ class DeviceSampler:
         if self.do_sample and self.temperature <= 0:
             raise ValueError("`temperature` has to be a strictly positive float when sampling")
 
-    def processed(self, logits, history):
-        """logits fp32 [vocab]; history int64 [n] (prompt + generated so far) -> the scores sampling draws from."""
-        scores = logits.clone()
+    def _adjusted(self, logits, history, generated):
+        """bias, repetition penalty, frequency and presence penalty: a new tensor, or `logits` itself when all are off"""
+        scores = logits
+        if self.bias:
+            if self._bias_dev is None or self._bias_dev[0].device != logits.device:
+                self._bias_dev = (torch.tensor(list(self.bias), dtype=torch.int64, device=logits.device),
+                                  torch.tensor(list(self.bias.values()), dtype=torch.float32, device=logits.device))
+            scores = logits.clone()
+            scores[self._bias_dev[0]] += self._bias_dev[1]
         if self.penalty != 1.0 and history.numel():
+            scores = scores.clone() if scores is logits else scores
             picked = scores[history]
             scores[history] = torch.where(picked < 0, picked * self.penalty, picked / self.penalty)
+        if (self.frequency != 0.0 or self.presence != 0.0) and generated is not None and generated.numel():
+            counts = torch.bincount(generated, minlength=scores.numel())
+            hit = counts > 0
+            scores = torch.where(hit, scores - counts.to(torch.float32) * self.frequency, scores)
+            scores = torch.where(hit, scores - self.presence, scores)
+        return scores
+
+    def processed(self, logits, history, generated=None):
+        """logits fp32 [vocab]; history int64 [n] (prompt + generated so far); generated int64 [m] (the generated part
+        alone: what the frequency / presence penalties count) -> the scores sampling draws from."""
+        scores = self._adjusted(logits, history, generated)
+        scores = scores.clone() if scores is logits else scores
         if not self.do_sample:
             return scores
         if self.temperature != 1.0:
@@ -695,29 +768,34 @@ class DeviceSampler:
             drop = cum <= (1.0 - self.top_p)
             drop[-1] = False  # min_tokens_to_keep = 1
             scores = scores.masked_fill(torch.zeros_like(drop).scatter(0, order, drop), float("-inf"))
+        if self.min_p > 0.0:
+            scores = self._min_p_cut(scores)
         return scores
+
+    def _min_p_cut(self, scores):
+        """HF MinPLogitsWarper, min_tokens_to_keep 1: drop what is less likely than min_p x the likeliest token"""
+        probs = scores.softmax(-1)
+        drop = probs < self.min_p * probs.amax()
+        drop[probs.argmax()] = False
+        return scores.masked_fill(drop, float("-inf"))
 
     TIE_SLACK = 8  # candidates kept beyond top_k so that values tied with the k-th one survive like in HF's mask
 
-    def __call__(self, logits, history):
+    def __call__(self, logits, history, generated=None):
         if self.do_sample and 0 < self.top_k < logits.numel():
-            return self._draw_top_k(logits, history)
-        scores = self.processed(logits, history)
+            return self._draw_top_k(logits, history, generated)
+        scores = self.processed(logits, history, generated)
         if not self.do_sample:
             return scores.argmax().reshape(1)
         return torch.multinomial(scores.softmax(-1), 1, generator=self.generator)
 
-    def _draw_top_k(self, logits, history):
+    def _draw_top_k(self, logits, history, generated=None):
         """The same distribution as `processed` + softmax + multinomial when top_k is set, without sorting the whole
         vocabulary: after the top-k mask only the candidates matter (everything else has probability 0), so the
         temperature, the nucleus cut and the draw run on top_k (+ TIE_SLACK) values — a 32000-entry sort per token is
         most of what sampling costs otherwise (profiles/r04n_*). Ties beyond TIE_SLACK entries at the k-th value would
         be cut where HF keeps them all; fp32 logits do not tie in practice."""
-        scores = logits
-        if self.penalty != 1.0 and history.numel():
-            scores = logits.clone()
-            picked = scores[history]
-            scores[history] = torch.where(picked < 0, picked * self.penalty, picked / self.penalty)
+        scores = self._adjusted(logits, history, generated)
         k2 = min(self.top_k + self.TIE_SLACK, scores.numel())
         vals, idx = torch.topk(scores, k2)  # descending
         if self.temperature != 1.0:
@@ -728,6 +806,8 @@ class DeviceSampler:
             drop = asc.softmax(-1).cumsum(-1) <= (1.0 - self.top_p)
             drop[-1] = False
             vals = vals.masked_fill(drop.flip(0), float("-inf"))
+        if self.min_p > 0.0:
+            vals = self._min_p_cut(vals)
         pick = torch.multinomial(vals.softmax(-1), 1, generator=self.generator)
         return idx[pick]
 
@@ -763,7 +843,7 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
         for _ in range(k):
             if made > 0:
                 engine.step(greedy=False)  # logits of the token just chosen, at position n + made - 1
-            tok = sampler(engine.logits, hist[:n + made])
+            tok = sampler(engine.logits, hist[:n + made], hist[n:n + made])
             if n_top is not None:  # the raw distribution's view of the pick and of its best ids
                 lsm = torch.log_softmax(engine.logits, -1)
                 rec[made, 0] = lsm[tok[0]]
@@ -787,30 +867,44 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
         yield new, [r[0] for r in rows], [[(int(i), lp) for i, lp in zip(r[1:1 + n_top], r[1 + n_top:])] for r in rows]
 
 
+def _controls(presence_penalty, frequency_penalty, min_p, logit_bias):
+    """(presence, frequency, min_p, {int id: float value}) with None = neutral"""
+    return (float(presence_penalty or 0.0), float(frequency_penalty or 0.0), float(min_p or 0.0),
+            {int(k): float(v) for k, v in dict(logit_bias or {}).items()})
+
+
 def request_seed():
     """One 63-bit value from torch's default CPU generator: `torch.manual_seed` makes sampled requests reproducible."""
     return int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
 
 
 def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chunk=2048, do_sample=False,
-                      temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, logprobs=None):
+                      temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, logprobs=None, presence_penalty=0.0,
+                      frequency_penalty=0.0, min_p=0.0, logit_bias=None, seed=None):
     """A sampling / repetition-penalty request: on the native sampler (chained bursts, graph replays) when
     `native_sampler_supports` says so, else `iter_sampled` with a `DeviceSampler`. The sampler is removed after the
     request, so the next greedy request runs the untouched greedy path: in a `finally` of this generator, which runs when
     the stream is exhausted, closed or collected — a consumer that stops early and keeps the generator alive should
     `close()` it. Installing and removing each drop the captured graphs, so a sampled request and the greedy request
-    after it each pay one capture."""
+    after it each pay one capture. `seed` = None: `request_seed()`; a given seed makes the request reproducible (on the
+    torch sampler it seeds a device generator of the request's own)."""
+    pres, freq, min_p, bias = _controls(presence_penalty, frequency_penalty, min_p, logit_bias)
     opts = dict(do_sample=bool(do_sample), temperature=1.0 if temperature is None else temperature, top_k=top_k or 0,
                 top_p=1.0 if top_p is None else top_p,
-                repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty)
+                repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
+                presence_penalty=pres, frequency_penalty=freq, min_p=min_p, logit_bias=bias)
     if opts["do_sample"] and float(opts["temperature"]) <= 0:
         raise ValueError("`temperature` has to be a strictly positive float when sampling")
     if not engine.native_sampler_supports(**opts):
-        yield from iter_sampled(engine, prompt_ids, max_new_tokens, DeviceSampler(**opts), eos=eos, burst=burst,
-                                chunk=chunk, logprobs=logprobs)
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=engine.device)
+            gen.manual_seed(int(seed) & (2 ** 63 - 1))
+        yield from iter_sampled(engine, prompt_ids, max_new_tokens, DeviceSampler(generator=gen, **opts), eos=eos,
+                                burst=burst, chunk=chunk, logprobs=logprobs)
         return
-    engine.set_sampler(seed=request_seed(), **opts)
-    try:
+    try:  # (inside: the sampler may be installed already when the controls are refused)
+        engine.set_sampler(seed=request_seed() if seed is None else int(seed), **opts)
         yield from engine.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, eos=eos,
                                         logprobs=logprobs)
     finally:

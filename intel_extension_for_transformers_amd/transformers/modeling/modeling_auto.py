@@ -284,6 +284,27 @@ def _materialise_buffers(model, device):
             (model.get_submodule(parent_name) if parent_name else model)._modules[leaf] = fresh.to(device)
 
 
+def _single_token_bias(sequence_bias, suppress_tokens, vocab):
+    """HF's `sequence_bias` ({(id,): value} or [[[id], value], ...]) and `suppress_tokens` as one {id: value} table for
+    the engine's logit bias (a suppressed token is a bias of -inf), or None when an entry spans several tokens, lies
+    outside the vocabulary or is not a number: those keep HF's loop, which handles or refuses them."""
+    bias = {}
+    try:
+        items = sequence_bias.items() if isinstance(sequence_bias, dict) else (sequence_bias or [])
+        for seq, value in items:
+            seq = [seq] if isinstance(seq, int) else list(seq)
+            if len(seq) != 1 or isinstance(value, bool) or not isinstance(value, (int, float)):
+                return None
+            bias[int(seq[0])] = bias.get(int(seq[0]), 0.0) + float(value)
+        for t in suppress_tokens or []:
+            bias[int(t)] = float("-inf")
+    except (TypeError, ValueError):
+        return None
+    if any(not 0 <= t < vocab or v != v or v == float("inf") for t, v in bias.items()):
+        return None
+    return bias
+
+
 def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     """`model.generate` with the fused native engine underneath when the request is one it covers — a single
     sequence, greedy, one beam, no logits processing beyond the default — and HF's own generate (over the
@@ -316,13 +337,18 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     # sampling (temperature / top-k / top-p) and the repetition penalty — the reference's NeuralChat defaults
     # (neural_chat/config.py:400-409) — ride the engine too, the next token chosen on the device (runtime.engine.
     # DeviceSampler: HF's processors / warpers in HF's order); any other logits processing keeps HF's loop
-    sampled = bool(opt("do_sample", False)) or (opt("repetition_penalty", 1.0) or 1.0) != 1.0
+    # min_p, single-token sequence_bias and suppress_tokens map onto the engine's sampler controls (same order as HF's
+    # processors); a multi-token sequence_bias keeps HF's loop
+    bias = _single_token_bias(opt("sequence_bias"), opt("suppress_tokens"), int(getattr(self.config, "vocab_size", 0) or 0))
+    min_p = (opt("min_p") or 0.0) if opt("do_sample", False) else 0.0  # a warper: HF applies it only when sampling
+    # (bias None: an entry the engine cannot take — `sampled` then makes `plain_sampling` decide, and it says HF's loop)
+    sampled = bool(opt("do_sample", False)) or (opt("repetition_penalty", 1.0) or 1.0) != 1.0 or bias is None or bool(bias)
     plain_sampling = ((opt("typical_p", 1.0) or 1.0) == 1.0 and not opt("epsilon_cutoff", 0.0) and not opt("eta_cutoff", 0.0)
-                      and opt("min_p") is None and opt("penalty_alpha") is None
+                      and bias is not None and opt("penalty_alpha") is None
                       and (opt("encoder_repetition_penalty", 1.0) or 1.0) == 1.0 and not opt("renormalize_logits", False)
-                      and all(opt(k) is None for k in ("exponential_decay_length_penalty", "suppress_tokens",
+                      and all(opt(k) is None for k in ("exponential_decay_length_penalty",
                                                        "begin_suppress_tokens", "forced_bos_token_id", "forced_eos_token_id",
-                                                       "sequence_bias", "guidance_scale")))
+                                                       "guidance_scale")))
     simple = (torch.is_tensor(ids) and ids.dim() == 2 and ids.shape[0] == 1 and ids.shape[1] >= 1
               and (not sampled or plain_sampling) and (opt("num_beams", 1) or 1) == 1
               and (opt("num_return_sequences", 1) or 1) == 1
@@ -385,7 +411,8 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
         for new in iter_sampled_auto(eng, prompt, max_new, eos=eos, burst=1 if streamer is not None else 16,
                                      do_sample=opt("do_sample", False), temperature=opt("temperature", 1.0),
                                      top_k=opt("top_k", 0), top_p=opt("top_p", 1.0),
-                                     repetition_penalty=opt("repetition_penalty", 1.0)):
+                                     repetition_penalty=opt("repetition_penalty", 1.0), min_p=min_p,
+                                     logit_bias=bias):
             out += new
             on_tokens(new)
         return out, latency

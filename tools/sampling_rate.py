@@ -12,6 +12,11 @@ Paths `greedy_logprobs` and `native_default_logprobs` are the greedy chain and t
 log-probability record on (csrc/woq_logprob.hip, 20 alternatives read back with every burst):
 
     python tools/sampling_rate.py --paths greedy,greedy_logprobs,native_default,native_default_logprobs
+
+Path `native_default_controls` is the default chat request plus `frequency_penalty = 0.5, min_p = 0.05` (the sampler
+controls: one pre-pass launch more per token):
+
+    python tools/sampling_rate.py --paths native_default,native_default_controls
 """
 import argparse
 import os
@@ -28,6 +33,7 @@ from intel_extension_for_transformers_amd.runtime.engine import (DeviceSampler, 
 
 DEFAULT = dict(do_sample=True, temperature=0.1, top_k=40, top_p=0.75, repetition_penalty=1.1)  # neural_chat/config.py
 PENALTY = dict(do_sample=False, repetition_penalty=1.1)
+CONTROLS = dict(DEFAULT, frequency_penalty=0.5, min_p=0.05)
 
 
 def main():
@@ -51,6 +57,7 @@ def main():
         return lambda: generate_sampled(eng, prompt, a.new, DeviceSampler(**kw))
 
     paths = {"native_default": native(DEFAULT), "torch_default": torch_path(DEFAULT), "native_penalty": native(PENALTY),
+             "native_default_controls": native(CONTROLS),
              "torch_penalty": torch_path(PENALTY), "greedy": lambda: eng.generate(prompt, a.new),
              "greedy_logprobs": lambda: eng.generate(prompt, a.new, logprobs=20)[0],
              "native_default_logprobs": lambda: eng.generate(prompt, a.new, sampler=dict(seed=1234, **DEFAULT),
@@ -72,7 +79,7 @@ def main():
              "# path: median (min - max)"]
     for n in names:
         rate = sorted(a.new / t for t in times[n])
-        lines.append("%-15s %8.1f (%.1f - %.1f)" % (n, statistics.median(rate), rate[0], rate[-1]))
+        lines.append("%-24s %8.1f (%.1f - %.1f)" % (n, statistics.median(rate), rate[0], rate[-1]))
     text = "\n".join(lines)
     print(text)
     if a.out:
