@@ -96,6 +96,20 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
                                   const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
                                   int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
                                   float* out, void* stream);
+/* What plan_attn_decode (csrc/woq_attn_decode.hip) decides for one decode step's attention, without touching a device
+ * (tests/test_attn_plan_cpu.py). in23 = {heads, kv_heads, head_dim, kv_dtype, max_ctx, window | splits, grouped, fold,
+ * chunk_fixed, fuse_attn, fuse_sliced, grouped_a2a | xq step, granule buffers present, layers, slots (resident
+ * workgroups of the grouped kernel, 0 = not covered) | the qkv blob as woq_header_init builds its header: K (0 = no
+ * blob), group, weight_type, scale_type, asym, act_shuffle}; N is (heads + 2 kv_heads) * head_dim.
+ * out11 = {form (0 fused into the qkv launch, 1 per query head, 2 grouped), merge (0 none, 1 combine launch, 2 arrival
+ * counters, 3 among the slices), slices, effective chunk_fixed, span, positions per wave, LDS bytes, grid x, grid y,
+ * launches of qkv projection + attention, refused}. Where the launch would fail: refused = 1, form and slices still say
+ * what was tried, and the call returns non-zero with the launcher's error text. */
+WOQ_API int woq_probe_attn_decode_plan(const int* in23, long long* out11);
+/* the plan the engine's next step would follow for layer 0, as out11 above; splits > 0 / grouped >= 0 evaluate it at
+ * that slice count / grouped request instead of the engine's own. The engine is not changed. A plan the launch would
+ * refuse is an answer, not a failure of this call: it returns 0 with refused = 1 and the reason in woq_last_error. */
+WOQ_API int woq_engine_attn_plan(woq_engine* e, int splits, int grouped, long long* out11);
 /* the sampled token tail alone (tests/test_gpu_sampler_kernel.py), forwarding to the engine's own launcher unchanged:
  * logits fp32 [vocab], seen uint32 [(vocab + 31) / 32] (read for the penalty, the picked token's bit set), cfg in HOST
  * memory, u_or_null = device fp32 uniform that overrides Philox, pos_dev = device int32 position (the Philox counter;

@@ -105,10 +105,16 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
     "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16", "woq_probe_sample_controls",
+    "woq_probe_attn_decode_plan", "woq_engine_attn_plan",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
 GEMM_FORM_RING, GEMM_FORM_TALL, GEMM_FORM_RAW = 16, 32, 64
+# the decode attention plan (csrc/woq_host.h AttnForm / AttnMergeMode): how a step's attention runs, how its slices merge
+ATTN_FUSED, ATTN_PER_HEAD, ATTN_GROUPED = 0, 1, 2
+ATTN_MERGE_NONE, ATTN_MERGE_COMBINE, ATTN_MERGE_COUNTER, ATTN_MERGE_A2A = 0, 1, 2, 3
+_ATTN_PLAN_FIELDS = ("form", "merge", "slices", "chunk_fixed", "span", "spw", "lds", "grid_x", "grid_y", "launches",
+                     "refused")
 
 _lib = None
 
@@ -182,6 +188,8 @@ def lib():
     L.woq_probe_rope_append.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, cs, vp]
     L.woq_probe_attn_prefill.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, cs, vp, ci, vp]
     L.woq_probe_attn_decode.argtypes = [vp, vp, vp, ci, vp, vp, vp] + [ci] * 9 + [vp, vp]
+    L.woq_probe_attn_decode_plan.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_longlong)]
+    L.woq_engine_attn_plan.argtypes = [vp, ci, ci, ctypes.POINTER(ctypes.c_longlong)]
     L.woq_comm_create.argtypes = [ci, ci, cs, ctypes.POINTER(vp)]
     L.woq_comm_handle.argtypes = [vp, vp, cs]
     L.woq_comm_connect.argtypes = [vp, vp, ctypes.POINTER(ci)]
@@ -275,6 +283,31 @@ def probe_attn_decode(qkv, kcache, vcache, kv_dtype, pos, cos, sin, heads, kv_he
                                      _ptr(out), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
+
+
+def probe_attn_decode_plan(heads, kv_heads, head_dim, kv_dtype, max_ctx, window=0, splits=1, grouped=False, fold=False,
+                           chunk_fixed=0, fuse_attn=True, fuse_sliced=True, grouped_a2a=True, xq=True, granules=True,
+                           layers=32, slots=0, qkv_k=0, group=128, weight_type=W_INT4_CLIP, scale_type=F16, asym=False,
+                           act_shuffle=False):
+    """What the decode attention's plan decides for one step (woq_probe_attn_decode_plan; host arithmetic, no device): a
+    dict of form (ATTN_*), merge (ATTN_MERGE_*), slices, chunk_fixed, span, spw, lds, grid_x, grid_y, launches, refused.
+    qkv_k > 0: the qkv blob is [(heads + 2 kv_heads) * head_dim, qkv_k] packed with the options that follow; 0 = none.
+    Raises RuntimeError with the launcher's message where the launch would fail."""
+    args = (ctypes.c_int * 23)(heads, kv_heads, head_dim, kv_dtype, max_ctx, window, splits, int(grouped), int(fold),
+                               chunk_fixed, int(fuse_attn), int(fuse_sliced), int(grouped_a2a), int(xq), int(granules),
+                               layers, slots, qkv_k, group, weight_type, scale_type, int(asym), int(act_shuffle))
+    out = (ctypes.c_longlong * 11)()
+    check(lib().woq_probe_attn_decode_plan(args, out))
+    return dict(zip(_ATTN_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def engine_attn_plan(handle, splits=0, grouped=-1):
+    """The plan the engine's next step would follow for layer 0 (woq_engine_attn_plan), as probe_attn_decode_plan's dict;
+    splits > 0 / grouped >= 0 evaluate it at that slice count / grouped request. The engine is not changed. A plan the
+    launch would refuse (a per-head workgroup beyond its LDS, ...) does not raise here: refused = 1, form as tried."""
+    out = (ctypes.c_longlong * 11)()
+    check(lib().woq_engine_attn_plan(handle, int(splits), int(grouped), out))
+    return dict(zip(_ATTN_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def sampler_config(do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):

@@ -1,5 +1,5 @@
 // woq_attn_decode.h — single-query (decode) attention of one head as a device function, shared by the standalone
-// launch (woq_ops.hip: attn_decode_kernel) and the fused qkv-GEMV + attention launch (woq_gemv_attn.hip).
+// launch (woq_attn_decode.hip: attn_decode_kernel) and the fused qkv-GEMV + attention launch (woq_gemv_attn.hip).
 // Reference: stock HF eager attention over the KV cache run by PyTorch CPU ops.
 #pragma once
 #include "woq_attn_merge.h"
@@ -56,6 +56,7 @@ struct AttnGranule {
 // SPLIT on a granule source (round 6): no combine launch — the slices of a head publish tagged partial granules
 // (part_g) and finalise the head's XQ blocks themselves (woq_attn_merge.h, all-to-all merge; at most 16 slices here).
 constexpr int ATTN_A2A_MAX_SLICES = 16;
+constexpr int FUSED_TPW = 8;  // K tiles per wave of the fused launch's strips (four waves: the qkv blob has 32 K tiles)
 
 // One 256-thread workgroup runs the body (the standalone and the fused launches): the two meeting points are workgroup
 // barriers, the result leaves as fp32 in `out` (+ its XQ block in `xo`, published through `pub` when an o_proj

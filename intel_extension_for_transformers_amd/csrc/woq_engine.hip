@@ -18,7 +18,6 @@
 #include "woq_device.h"
 #include "woq_host.h"
 #include "../../include/woq_hip_experimental.h"
-#include "woq_attn_merge.h"
 
 using woq::XqPtrs;
 
@@ -74,24 +73,11 @@ struct woq_engine {
   unsigned long long* qkv_g = nullptr;
   unsigned int* step_seq = nullptr;
   int* fuse_status = nullptr;
-  bool fuse_attn = true;             // qkv GEMV + attention in one launch where the shape allows (woq_gemv_attn.hip)
-  // in-launch hand-off tags are (step counter << 6) | layer (woq_gemv_attn.hip):
-  // beyond 64 layers the layer bits would run into the counter and a stale granule could pass for a fresh one, so
-  // deeper models keep the separate launches
-  bool tags_ok() const { return cfg.layers <= 64; }
-  // context slices as attention workgroups of the fused launch (round 6; WOQ_FUSE_SLICED=0: sliced contexts keep the
-  // three launches qkv | slices | combine — same-box A/B runs)
-  bool fuse_sliced = true;
   // fp8-weight layers (round 6; bestla_weightonly_dispatcher.hpp:62-72; EngineProj). Such engines run the
   // fp32-activation step (no XQ vectors): fp8 matrix-core GEMVs with RMSNorm / residual fused, 6 launches a layer
   uint32_t fp8_type = 0;  // 0 = integer / table layers; WOQ_W_FP8_E4M3 | WOQ_W_FP8_E5M2
   float* gu_tmp = nullptr;  // fp32 [2 * inter]: the fused gate/up projection's columns before SiLU * mul
-  unsigned long long* attn_part_g = nullptr;  // their partials as {tag, fp32} granules [heads][64][head_dim + 2]
-  bool fused_attn_applies(const woq_blob_header& qkv_hdr) const;
-  // grouped matrix-core slices (a launch of their own) merging among themselves instead of a combine launch: every slice
-  // workgroup of the launch must be resident at once (they wait for each other) — WOQ_GROUPED_A2A=0: combine launch
-  bool grouped_a2a = true;
-  bool grouped_a2a_ok() const;
+  unsigned long long* attn_part_g = nullptr;  // the slices' partials as {tag, fp32} granules [heads][64][head_dim + 2]
   // tensor parallel ranks take the XQ path when the exchange runs on the device (its all-reduce kernel then emits the
   // next XQ vector itself); with a host-side transport they keep the fp32-activation kernels
   bool tp_xq = true, tp_fused_push = true;
@@ -111,14 +97,16 @@ struct woq_engine {
   float* am_val = nullptr;      // per-workgroup (max logit, index) pairs of the lm_head launch, for the greedy argmax
   int32_t* am_idx = nullptr;
   int window = 0;               // sliding-window attention (HF Mistral sliding_window), 0 = full causal
-  int attn_splits = 1;          // decode attention: context slices per head (long contexts)
-  int attn_grouped = 0;         // sliced regime: one workgroup per kv head x slice on the matrix cores (GQA shapes)
+  // decode attention: what is asked for (slices, grouped form, merge and fusion switches; woq_host.h AttnOptions). fold =
+  // WOQ_ATTN_FOLD=1: built, parity-tested and measured SLOWER than the combine launch (+3..5 us per layer: three
+  // dependent device-scope round trips on the launch's tail, profiles/r04d_*); opt-in, default off. fuse_sliced /
+  // grouped_a2a = WOQ_FUSE_SLICED / WOQ_GROUPED_A2A (0: sliced contexts keep the separate launches / the combine launch)
+  woq::AttnOptions attn_opt;
+  // how layer l's attention runs under `o` (plan_attn_decode): decided per call, host arithmetic only
+  woq::AttnDecodePlan attn_plan(int l, const woq::AttnOptions& o) const;
+  woq::AttnDecodeIO attn_io(int l, const XqPtrs& xo) const;
   float* attn_part = nullptr;   // fp32 partials of the sliced decode attention (layout: woq_attn_merge.h)
   unsigned int* attn_cnt = nullptr;  // [heads] arrival counters of the slices' last-workgroup merge, zero between launches
-  bool attn_fold = false;       // WOQ_ATTN_FOLD=1: the last slice workgroup merges instead of a combine launch — built,
-                                // parity-tested and measured SLOWER (+3..5 us per layer: three dependent device-scope
-                                // round trips on the launch's tail, profiles/r04d_*); opt-in, default off
-  int attn_chunk = 0;           // grouped form: positions per slice of the position-independent geometry, 0 = adaptive
   bool time_eager = true;       // woq_engine_time_gemv / _twin: passes issued eagerly (how bursts run by default) or as a
                                 // replayed graph (round 3's measure; woq_engine_set_time_eager(e, 0))
   int max_batch = 1;
@@ -161,18 +149,16 @@ struct woq_engine {
 
 using namespace woq;
 
-bool woq_engine::fused_attn_applies(const woq_blob_header& qkv_hdr) const {
-  if (!fuse_attn || qkv_g == nullptr || attn_grouped || !tags_ok()) return false;
-  if (attn_splits > 1 && (!fuse_sliced || attn_part_g == nullptr || attn_fold)) return false;
-  return gemv_xq_attn_supported(qkv_hdr, cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.kv_dtype, cfg.max_ctx, window,
-                                attn_splits);
+AttnDecodePlan woq_engine::attn_plan(int l, const AttnOptions& o) const {
+  const bool xq = use_xq();
+  // the one device-derived number (asked once per shape, then remembered): only the grouped form's all-to-all merge reads it
+  const int slots = xq && o.grouped && o.grouped_a2a ? attn_decode_mfma_slots(cfg.kv_dtype, cfg.heads / cfg.kv_heads) : 0;
+  return plan_attn_decode(AttnShape{cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.kv_dtype, cfg.max_ctx, window}, o,
+                          AttnFacts{xq, qkv_g != nullptr && attn_part_g != nullptr, cfg.layers, &layers[l].p[P_QKV].hdr, slots});
 }
 
-bool woq_engine::grouped_a2a_ok() const {
-  if (!grouped_a2a || !attn_grouped || attn_fold || attn_part_g == nullptr || !tags_ok() || attn_splits < 2 || attn_splits > 32)
-    return false;
-  const int rep = cfg.kv_heads > 0 ? cfg.heads / cfg.kv_heads : 0;
-  return cfg.kv_heads * attn_splits <= attn_decode_mfma_slots(cfg.kv_dtype, rep);
+AttnDecodeIO woq_engine::attn_io(int l, const XqPtrs& xo) const {
+  return AttnDecodeIO{qkv, k_of(l), v_of(l), pos, cs, sn, attn, xo, attn_part, attn_cnt, attn_part_g, step_seq, l, fuse_status};
 }
 
 const woq::CommDev* woq_engine::tp_push() const {
@@ -206,21 +192,15 @@ static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
   const woq_engine_config& c = e->cfg;
   const EngineLayer& w = e->layers[l];
   int rc = 0;
-  const int ns = e->attn_splits > 1 ? e->attn_splits : 1;  // context slices (round 6: attention workgroups of the fused launch)
-  if (e->fused_attn_applies(w.p[P_QKV].hdr)) {
-    rc = launch_gemv_xq_attn(e->xq_hidden, w.p[P_QKV].blob, w.p[P_QKV].hdr, e->qkv_g, e->ssq_part, c.rms_eps,
-                             e->step_seq, l, e->fuse_status, e->k_of(l), e->v_of(l), c.kv_dtype, e->pos, e->cs, e->sn,
-                             c.heads, c.kv_heads, c.max_ctx, e->window, e->attn, e->xq_attn, st, ns,
-                             e->attn_part_g);  // (slices merge among themselves: no combine launch)
+  const AttnDecodePlan plan = e->attn_plan(l, e->attn_opt);
+  const AttnDecodeIO io = e->attn_io(l, e->xq_attn);
+  if (plan.form == ATTN_FUSED) {
+    rc = launch_gemv_xq_attn(plan, io, e->xq_hidden, w.p[P_QKV].blob, w.p[P_QKV].hdr, e->qkv_g, e->ssq_part, c.rms_eps, st);
     if (rc) return rc;
   } else {
     rc = engine_gemv_xq(e, l, P_QKV, e->xq_hidden, e->qkv, e->ssq_part, nullptr, kNoXq, nullptr, nullptr, st);
     if (rc) return rc;
-    const AttnA2A a2a{e->attn_part_g, 0u, e->fuse_status};
-    rc = launch_attn_decode(e->qkv, e->k_of(l), e->v_of(l), c.kv_dtype, e->pos, e->cs, e->sn, c.heads, c.kv_heads,
-                            c.head_dim, c.max_ctx, e->window, e->attn, e->attn_splits, e->attn_grouped, e->attn_part,
-                            e->xq_attn, st, e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk,
-                            e->grouped_a2a_ok() ? &a2a : nullptr, e->step_seq, l);
+    rc = launch_attn_decode(plan, io, st);
     if (rc) return rc;
   }
   // hidden += attn . W_o ; the new hidden leaves as the MLP's XQ input (times ln2) with its sums of squares
@@ -255,9 +235,7 @@ static int engine_attn_block(woq_engine* e, int l, hipStream_t st) {
   const EngineLayer& w = e->layers[l];
   int rc = engine_linear_f32(e, l, P_QKV, e->hidden, c.hidden, e->qkv, w.p[P_QKV].hdr.N, w.ln1, nullptr, st);
   if (rc) return rc;
-  rc = launch_attn_decode(e->qkv, e->k_of(l), e->v_of(l), c.kv_dtype, e->pos, e->cs, e->sn, c.heads, c.kv_heads,
-                          c.head_dim, c.max_ctx, e->window, e->attn, e->attn_splits, e->attn_grouped, e->attn_part, kNoXq,
-                          st, e->attn_fold ? e->attn_cnt : nullptr, e->attn_chunk);
+  rc = launch_attn_decode(e->attn_plan(l, e->attn_opt), e->attn_io(l, kNoXq), st);
   if (rc) return rc;
   return engine_linear_f32(e, l, P_O, e->attn, c.heads * c.head_dim, e->hidden, c.hidden, nullptr,
                            e->tp_residual(e->hidden), st);
@@ -577,24 +555,24 @@ void* woq_engine_prefill_rows_ptr(woq_engine* e) { return e ? e->pf_h : nullptr;
 int woq_engine_set_attn_splits(woq_engine* e, int splits) {
   WOQ_TRY
   WOQ_CHECK(e && splits >= 1 && splits <= 64, "QBits: attn_splits must be in [1, 64]");
-  e->attn_splits = splits;  // takes effect at the next step / capture (a captured graph keeps its own)
+  e->attn_opt.splits = splits;  // takes effect at the next step / capture (a captured graph keeps its own)
   WOQ_END
 }
-int woq_engine_attn_splits(woq_engine* e) { return e ? e->attn_splits : 0; }
+int woq_engine_attn_splits(woq_engine* e) { return e ? e->attn_opt.splits : 0; }
 int woq_engine_set_attn_grouped(woq_engine* e, int on) {
   WOQ_TRY
   WOQ_CHECK(e != nullptr, "QBits: null engine");
-  e->attn_grouped = on != 0;
+  e->attn_opt.grouped = on != 0;
   WOQ_END
 }
-int woq_engine_attn_grouped(woq_engine* e) { return e ? e->attn_grouped : 0; }
+int woq_engine_attn_grouped(woq_engine* e) { return e ? (int)e->attn_opt.grouped : 0; }
 int woq_engine_set_attn_chunk(woq_engine* e, int chunk) {
   WOQ_TRY
   WOQ_CHECK(e != nullptr && chunk >= 0 && chunk % 32 == 0, "QBits: attn_chunk must be a non-negative multiple of 32");
-  e->attn_chunk = chunk;  // takes effect at the next step / capture
+  e->attn_opt.chunk_fixed = chunk;  // takes effect at the next step / capture
   WOQ_END
 }
-int woq_engine_attn_chunk(woq_engine* e) { return e ? e->attn_chunk : 0; }
+int woq_engine_attn_chunk(woq_engine* e) { return e ? e->attn_opt.chunk_fixed : 0; }
 int woq_engine_set_time_eager(woq_engine* e, int on) {
   WOQ_TRY
   WOQ_CHECK(e != nullptr, "QBits: null engine");
@@ -611,7 +589,7 @@ int woq_engine_set_tp_options(woq_engine* e, int xq, int fused_push) {
 int woq_engine_set_fuse_attn(woq_engine* e, int on) {
   WOQ_TRY
   WOQ_CHECK(e != nullptr, "QBits: null engine");
-  e->fuse_attn = on != 0;
+  e->attn_opt.fuse_attn = on != 0;
   WOQ_END
 }
 int woq_engine_status(woq_engine* e, void* stream) {  // bit 0 hand-off give-up, bit 1 position clamp
@@ -632,7 +610,16 @@ int woq_engine_clear_status(woq_engine* e, void* stream) {
 }
 int woq_engine_fuse_attn(woq_engine* e) {
   if (!e || !e->use_xq() || e->layers.empty()) return 0;
-  return e->fused_attn_applies(e->layers[0].p[P_QKV].hdr) ? 1 : 0;
+  return e->attn_plan(0, e->attn_opt).form == ATTN_FUSED ? 1 : 0;
+}
+int woq_engine_attn_plan(woq_engine* e, int splits, int grouped, long long* out11) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr && out11 != nullptr && !e->layers.empty() && splits <= 64, "QBits: bad argument");
+  AttnOptions o = e->attn_opt;  // a copy: the engine keeps its own
+  if (splits > 0) o.splits = splits;
+  if (grouped >= 0) o.grouped = grouped != 0;
+  attn_plan_report(e->attn_plan(0, o), out11);  // a refused plan is an answer too: its form, and refused = 1
+  WOQ_END
 }
 void* woq_engine_kv_cache_ptr(woq_engine* e, int which) { return e ? (which ? e->vcache : e->kcache) : nullptr; }
 
@@ -664,20 +651,20 @@ int woq_engine_create(const woq_engine_config* cfg, woq_engine** out) {
   WOQ_HIP(hipMemset(e->kcache, 0, kv_total));
   WOQ_HIP(hipMemset(e->vcache, 0, kv_total));
   // decode attention slices: reserved[1] if given, else enough to fill the chip once the context is long
-  e->attn_splits = cfg->reserved[1] > 0 ? cfg->reserved[1]
-                   : (cfg->max_ctx > 4096 ? std::max(2, std::min(32, 1024 / std::max(1, (int)cfg->heads))) : 1);
-  WOQ_CHECK(e->attn_splits <= 64, "QBits: attn_splits must be <= 64");
+  e->attn_opt.splits = cfg->reserved[1] > 0 ? cfg->reserved[1]
+                       : (cfg->max_ctx > 4096 ? std::max(2, std::min(32, 1024 / std::max(1, (int)cfg->heads))) : 1);
+  WOQ_CHECK(e->attn_opt.splits <= 64, "QBits: attn_splits must be <= 64");
   e->window = cfg->reserved[2] > 0 ? cfg->reserved[2] : 0;
   WOQ_HIP(hipMalloc((void**)&e->attn_part, (size_t)cfg->heads * 64 * (cfg->head_dim + 2) * 4));  // room for 64 slices
   WOQ_HIP(hipMalloc((void**)&e->attn_cnt, (size_t)cfg->heads * 4));
   WOQ_HIP(hipMemset(e->attn_cnt, 0, (size_t)cfg->heads * 4));
   {
     const char* af = getenv("WOQ_ATTN_FOLD");
-    e->attn_fold = af ? af[0] != '0' : false;
+    e->attn_opt.fold = af ? af[0] != '0' : false;
     const char* ga = getenv("WOQ_GROUPED_A2A");
-    e->grouped_a2a = ga ? ga[0] != '0' : true;
+    e->attn_opt.grouped_a2a = ga ? ga[0] != '0' : true;
     const char* fs = getenv("WOQ_FUSE_SLICED");
-    e->fuse_sliced = fs ? fs[0] != '0' : true;
+    e->attn_opt.fuse_sliced = fs ? fs[0] != '0' : true;
   }
   WOQ_HIP(hipMalloc((void**)&e->tok_log, (size_t)(cfg->max_ctx + 1) * 4));
   WOQ_HIP(hipMemset(e->tok_log, 0, (size_t)(cfg->max_ctx + 1) * 4));
@@ -702,7 +689,7 @@ int woq_engine_create(const woq_engine_config* cfg, woq_engine** out) {
     const char* sw = getenv("WOQ_ENGINE_XQ");
     e->xq_enabled = sw ? sw[0] != '0' : true;
     const char* fa = getenv("WOQ_ENGINE_FUSE_ATTN");
-    e->fuse_attn = fa ? fa[0] != '0' : true;
+    e->attn_opt.fuse_attn = fa ? fa[0] != '0' : true;
     const char* tx = getenv("WOQ_TP_XQ");
     e->tp_xq = tx ? tx[0] != '0' : true;
     const char* tf = getenv("WOQ_TP_FUSED_PUSH");

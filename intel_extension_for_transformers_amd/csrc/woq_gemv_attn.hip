@@ -16,8 +16,9 @@
 // 32 waiting workgroups cannot keep 768 strips off a chip that holds all of them at once.
 // A first form without resident attention workgroups — the strip that completes a head runs its attention — was
 // correct but slower than two launches (profiles/r03j_fused_attn_last_arriver_negative.txt).
-// Scope: multi-head attention shapes (heads == kv_heads), head_dim 128, K = 32 tiles at 8 per wave (4 waves),
-// one context slice, no sliding window; everything else keeps the two launches.
+// Scope: head_dim 128, K = 32 tiles at 8 per wave (4 waves), up to 16 context slices that merge among themselves; the
+// rule is the plan's (woq_attn_decode.hip plan_attn_decode, fused_attn_covers), and this launcher takes the plan's
+// slices, span and LDS. Everything else keeps the separate launches.
 #include <algorithm>
 #include <cstdlib>
 
@@ -46,7 +47,6 @@ struct FusedAttnArgs {
   unsigned long long* part_g;  // ns > 1: the slices' partials as tagged granules (woq_attn_decode.h attn_part_granule)
 };
 
-constexpr int FUSED_TPW = 8;
 // Round 6: the q strips of the fused launch are given the WHOLE slice as their window (8 tiles per wave up front) and the
 // k / v strips a shallower one, so that q lands while k / v are still streaming: the attention workgroups then run
 // everything over the cache on q alone (woq_attn_decode.h) and only the new position's score and value stand behind
@@ -103,33 +103,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void g
                                                                       (tpg_flags >> 8) & 0xff, 4, xqs_late_ptr());
 }
 
-// positions one attention workgroup of the fused launch may have to hold scores for (launch_attn_t's sizing)
-static int fused_attn_span(int max_ctx, int window, int splits) {
-  const int reach = window > 0 ? std::min(window, max_ctx) : max_ctx;
-  return splits > 1 ? ((((reach + splits - 1) / splits) + 63) & ~63) + 64 : reach;
-}
-
-bool gemv_xq_attn_supported(const woq_blob_header& h, int heads, int kv_heads, int head_dim, int kv_dtype, int max_ctx,
-                            int window, int splits) {
-  if (h.weight_type != WOQ_W_INT4_CLIP || h.off_shuffle != 0 || h.K != h.Kpad || h.N != h.Npad) return false;
-  if (h.Kpad / WOQ_TILE_K != 4 * FUSED_TPW) return false;  // four waves of eight tiles
-  BlobView v;
-  if (!blob_view(nullptr, h, v)) return false;
-  // round 4: grouped-query shapes (Mistral-7B: 32 query / 8 kv heads) and a sliding window are taken as well — the
-  // attention body always handled both (kh = h / rep, re-based cache pointers); round 3 simply had not tested them here
-  if (kv_heads < 1 || heads % kv_heads != 0 || head_dim != 128 || splits > ATTN_A2A_MAX_SLICES) return false;
-  if (splits > 1 && heads * splits > 512) return false;  // the slices of a head wait for each other: resident together
-  if (splits > 1 && (heads + 2 * kv_heads) * 8 + heads * splits > 65535) return false;  // the packed strip count
-  if (h.N != (heads + 2 * kv_heads) * head_dim) return false;
-  (void)window;
-  if (kv_dtype != WOQ_F16 && kv_dtype != WOQ_BF16 && kv_dtype != WOQ_FP8_E4M3) return false;
-  // every workgroup of the launch gets max(attention LDS, GEMV LDS): the 768 strip workgroups (three per CU, four on
-  // the CUs that also hold an attention workgroup) inherit the attention's score buffer, which grows with max_ctx.
-  // Up to 38 KiB (max_ctx 8192) four workgroups still share a CU's 160 KiB; beyond that the strips would lose
-  // occupancy to a buffer they never touch, so such engines keep the two launches.
-  return attn_dec_lds_floats(128, fused_attn_span(max_ctx, window, splits)) * 4 <= 38 * 1024;
-}
-
 // what the fused launch carries beside the blob (BlobView)
 struct FusedLaunch {
   XqPtrs xin;
@@ -165,29 +138,26 @@ static int launch_fused_kv(const BlobView& v, const FusedLaunch& a, hipStream_t 
                             [&](auto SM, auto AS, auto S3, auto) { return launch_fused_t<SM(), AS(), S3(), KV>(v, a, st); });
 }
 
-int launch_gemv_xq_attn(const XqPtrs& xin, const void* blob, const woq_blob_header& h, unsigned long long* qkv_g,
-                        const float* ssq_in, float eps, const unsigned int* seq, int layer, int* status, void* kcache,
-                        void* vcache, int kv_dtype, const int32_t* pos, const float* cs, const float* sn, int heads,
-                        int kv_heads, int max_ctx, int window, float* attn_out, const XqPtrs& xq_attn, hipStream_t st,
-                        int splits, unsigned long long* part_g) {
+int launch_gemv_xq_attn(const AttnDecodePlan& plan, const AttnDecodeIO& io, const XqPtrs& xin, const void* blob,
+                        const woq_blob_header& h, unsigned long long* qkv_g, const float* ssq_in, float eps,
+                        hipStream_t st) {
   BlobView v;
-  if (!blob_view(blob, h, v)) return woq::fail("QBits: bad fused qkv + attention configuration");
+  if (plan.form != ATTN_FUSED || !blob_view(blob, h, v)) return woq::fail("QBits: bad fused qkv + attention configuration");
+  if (plan.slices > 1 && io.part_g == nullptr)
+    return woq::fail("QBits: context slices in the fused launch need the partial granules");
   FusedLaunch a;
-  if (splits < 1) splits = 1;
   a.xin = xin;
   a.flags = v.sbf16 ? 1 : 0;
   a.eps = eps;
   a.n_ssq = h.K / 16;
   a.ssq_in = ssq_in;
   a.out = qkv_g;
-  const int span = fused_attn_span(max_ctx, window, splits);
-  const int spw = attn_dec_spw(span);
-  if (splits > 1 && part_g == nullptr) return woq::fail("QBits: context slices in the fused launch need the partial granules");
-  a.fa = FusedAttnArgs{seq, layer, status, kcache, vcache, pos, cs, sn, heads, kv_heads, window, spw, attn_out, xq_attn,
-                       splits, part_g};
-  a.lds_attn = attn_dec_lds_floats(128, span) * 4;
-  if (kv_dtype == WOQ_F16) return launch_fused_kv<_Float16>(v, a, st);
-  if (kv_dtype == WOQ_FP8_E4M3) return launch_fused_kv<Fp8>(v, a, st);
+  const AttnShape& s = plan.shape;
+  a.fa = FusedAttnArgs{io.seq, io.layer, io.status, io.kcache, io.vcache, io.pos, io.cs, io.sn, s.heads, s.kv_heads,
+                       s.window, plan.spw, io.out, io.xo, plan.slices, io.part_g};
+  a.lds_attn = plan.lds;
+  if (s.kv_dtype == WOQ_F16) return launch_fused_kv<_Float16>(v, a, st);
+  if (s.kv_dtype == WOQ_FP8_E4M3) return launch_fused_kv<Fp8>(v, a, st);
   return launch_fused_kv<__bf16>(v, a, st);
 }
 

@@ -6,8 +6,6 @@
 #include "woq_xq.h"
 
 namespace woq {
-struct AttnA2A;    // woq_attn_merge.h
-struct AttnMerge;  // woq_attn_merge.h
 struct LutArgs;    // woq_gemv_common.h
 struct KPlan;      // woq_gemv_launch.h
 
@@ -82,35 +80,78 @@ void launch_xq_from_f32(const float* x, const float* norm_w, int K, const XqPtrs
 // mode 0: load-only twin of the batch-1 GEMV of this blob; mode 1: an empty kernel on the same grid and block
 int launch_gemv_twin(const void* blob, const woq_blob_header& h, int epi, int mode, unsigned int* sink, hipStream_t st);
 
+// ---- woq_attn_decode.hip: a decode step's attention — the plan and the separate launches --------------------------
+// A step's attention runs in one of three forms — FUSED: attention workgroups behind the qkv GEMV's strips, one launch
+// (woq_gemv_attn.hip); PER_HEAD / GROUPED: qkv GEMV, then one workgroup per (query head, slice) / one matrix-core
+// workgroup per (kv head, slice) — and its context slices merge in one of three ways: a COMBINE launch, the last slice
+// workgroup to arrive (COUNTER) or the slices among themselves through tagged granules (A2A; both woq_attn_merge.h).
+enum AttnForm { ATTN_FUSED = 0, ATTN_PER_HEAD = 1, ATTN_GROUPED = 2 };
+enum AttnMergeMode { ATTN_MERGE_NONE = 0, ATTN_MERGE_COMBINE = 1, ATTN_MERGE_COUNTER = 2, ATTN_MERGE_A2A = 3 };
+struct AttnShape { int heads, kv_heads, head_dim, kv_dtype, max_ctx, window; };
+struct AttnOptions {  // what is asked for; the plan says what runs
+  int splits = 1;        // context slices per head (<= 1: none)
+  bool grouped = false;  // the grouped form, where it applies
+  bool fold = false;     // merge by arrival counters (WOQ_ATTN_FOLD=1; measured slower than the combine launch)
+  int chunk_fixed = 0;   // grouped form: positions per slice of the position-independent geometry, 0 = adaptive
+  bool fuse_attn = true, fuse_sliced = true;  // the fused launch where the shape allows; context slices in it as well
+  bool grouped_a2a = true;  // grouped slices merge among themselves where the whole grid is resident
+};
+struct AttnFacts {  // what the engine is
+  bool xq, granules;  // the XQ step (the fp32-activation one never fuses, never merges A2A); the granule buffers exist
+  int layers;         // hand-off tags are (step << 6) | layer: at most 64 layers
+  const woq_blob_header* qkv_hdr;  // the layer's qkv blob (nullable = no fused launch)
+  int slots;          // attn_decode_mfma_slots for this shape, 0 = not covered
+};
+struct AttnDecodePlan {
+  AttnShape shape;
+  AttnForm form;
+  AttnMergeMode merge;
+  int slices, chunk_fixed;  // >= 1; GROUPED: the geometry that runs (no multiple of 32 -> 0, adaptive)
+  int span, spw;            // FUSED / PER_HEAD: positions a workgroup / a wave may hold scores for (woq_attn_decode.h)
+  size_t lds;               // dynamic LDS bytes of an attention workgroup
+  unsigned grid_x, grid_y;  // of the launch that holds the attention workgroups
+  int launches;             // qkv projection and attention together
+  const char* error;        // null, or why launch_attn_decode will refuse (the other fields then mean nothing)
+};
+// Decides once how the attention of a step runs. Pure host arithmetic: no HIP call, no environment, no statics.
+AttnDecodePlan plan_attn_decode(const AttnShape& s, const AttnOptions& o, const AttnFacts& f);
+// a plan as the probes report it: {form, merge, slices, chunk_fixed, span, spw, LDS bytes, grid x, grid y, launches,
+// refused}; refused = 1: launch_attn_decode would fail, and the error text (woq_last_error) is set to the reason
+void attn_plan_report(const AttnDecodePlan& p, long long* out11);
+// the device buffers of one layer's attention; which of them a launch touches follows from the plan
+struct AttnDecodeIO {
+  const float* qkv;       // fp32 [(heads + 2 kv_heads) * D] un-rotated projections (the separate launches' input)
+  void *kcache, *vcache;  // [max_ctx][kv_heads][D]; the new k / v are appended at *pos
+  const int32_t* pos;
+  const float *cs, *sn;
+  float* out;             // fp32 [heads * D], and `xo` its XQ form for the o_proj GEMV (or all null)
+  XqPtrs xo;
+  float* part;            // fp32 partials of the slices (layout: woq_attn_merge.h)
+  unsigned int* counters; // COUNTER: [heads] words, zero between launches
+  unsigned long long* part_g;  // A2A: {tag, fp32} partial granules [heads][64][D + 2]
+  const unsigned int* seq;     // FUSED / A2A: device-side step counter, tag = seq << 6 | layer
+  int layer;
+  int* status;            // sticky give-up flag
+};
+// the attention launch(es) of a PER_HEAD or GROUPED plan; a plan with an error text fails with it
+int launch_attn_decode(const AttnDecodePlan& plan, const AttnDecodeIO& io, hipStream_t st);
+// workgroups of the grouped decode attention kernel the chip holds at once (0 = shape not covered): the all-to-all
+// merge needs the whole grid resident. Asks the device once per (cache type, group size) and remembers.
+int attn_decode_mfma_slots(int kv_dtype, int rep);
+
 // ---- woq_gemv_attn.hip: [RMSNorm + qkv GEMV] + [RoPE + KV append + attention] in one launch -----------------------
-// does the fused launch take this (blob, attention) combination?
-bool gemv_xq_attn_supported(const woq_blob_header& h, int heads, int kv_heads, int head_dim, int kv_dtype, int max_ctx,
-                            int window, int splits);
-// qkv_g ({tag, fp32} granules [(heads + 2 kv_heads) * 128]) = xin . W_qkv_deq * rsqrt(mean(x^2) + eps); per head, as its granules
-// arrive: RoPE, KV append at *pos, attention over the cache -> attn_out (+ its XQ form).
-// splits > 1: `splits` context slices per head; they merge among themselves through the tagged granules `part_g`
-// ([heads][64][130] x 8 B) and write attn_out / xq_attn — no combine launch.
-int launch_gemv_xq_attn(const XqPtrs& xin, const void* blob, const woq_blob_header& h, unsigned long long* qkv_g,
-                        const float* ssq_in, float eps, const unsigned int* seq, int layer, int* status, void* kcache,
-                        void* vcache, int kv_dtype, const int32_t* pos, const float* cs, const float* sn, int heads,
-                        int kv_heads, int max_ctx, int window, float* attn_out, const XqPtrs& xq_attn, hipStream_t st,
-                        int splits = 1, unsigned long long* part_g = nullptr);
+// A FUSED plan's launch. qkv_g ({tag, fp32} granules [(heads + 2 kv_heads) * 128]) = xin . W_qkv_deq *
+// rsqrt(mean(x^2) + eps); per head, as its granules arrive: RoPE, KV append at *io.pos, attention over the cache ->
+// io.out (+ io.xo). plan.slices > 1: context slices per head; they merge among themselves through io.part_g and write
+// io.out / io.xo — no combine launch.
+int launch_gemv_xq_attn(const AttnDecodePlan& plan, const AttnDecodeIO& io, const XqPtrs& xin, const void* blob,
+                        const woq_blob_header& h, unsigned long long* qkv_g, const float* ssq_in, float eps,
+                        hipStream_t st);
 
 // ---- woq_ops.hip: the decode step's other launches ----------------------------------------------------------------
 void launch_embed(const void* embed, int dtype, const int32_t* token, int hidden, float* out, const float* norm_w,
                   const XqPtrs& xo, float* ssq_out, unsigned int* step_seq, int32_t* pos, int max_ctx, int* status,
                   hipStream_t st);
-// splits <= 1: one workgroup per head (short contexts); else `splits` slices per head + a combine launch, partials in
-// `part` (fp32 [heads][splits][D + 2]).
-// merge_counters (nullable): [heads] zero-initialised words — the slices' last workgroup merges (woq_attn_merge.h) and
-// no combine launch follows; chunk_fixed: position-independent slice geometry of the grouped form (0 = adaptive)
-int launch_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
-                       const float* cs, const float* sn, int heads, int kv_heads, int D, int max_ctx, int window,
-                       float* out, int splits, int grouped, float* part, const XqPtrs& xo, hipStream_t st,
-                       unsigned int* merge_counters, int chunk_fixed, const AttnA2A* a2a_grouped = nullptr,
-                       const unsigned int* seq = nullptr, int layer = 0);
-void launch_attn_combine(const float* part, int heads, int D, int splits, float* out, const XqPtrs& xo,
-                         hipStream_t st);
 // pmax / pidx (nullable): per-workgroup (max logit, its index), (vocab + 15) / 16 entries each
 void launch_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype, int hidden,
                     int vocab, float* logits, float* pmax, int32_t* pidx, hipStream_t st);
@@ -187,7 +228,7 @@ int launch_score_rows(const float* hidden_rows, const float* norm_w, float eps, 
                       int vocab, const int32_t* targets, int M, int row0, int max_rows, void* ws, float* chosen,
                       int32_t* top_id, float* top_lp, hipStream_t st);
 
-// ---- woq_prefill.hip: prompt-pass launches and the grouped decode attention ---------------------------------------
+// ---- woq_prefill.hip: the prompt pass's launches outside its GEMMs -------------------------------------------------
 void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int M, int hidden, float* out,
                        hipStream_t st);
 int launch_rope_append(_Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD, const float* cs,
@@ -198,16 +239,6 @@ int launch_attn_prefill(const _Float16* qkv, int n_seq, int T, int start, int he
                         int window, hipStream_t st);
 // last row of every sequence -> dst fp32 [n_seq][hidden]
 void launch_gather_last(const float* h, int n_seq, int T, int hidden, float* dst, hipStream_t st);
-// long-context decode attention of grouped-query models: true when this kernel took the call (head_dim 128, 2 / 4 / 8
-// query heads per kv head), false -> the caller uses the per-query-head sliced kernel
-// chunk_fixed: 0 = adaptive slices, else positions per slice (multiple of 32) of the position-independent geometry;
-// mg.counter != null: the last slice workgroup of a kv head merges (no combine launch needed)
-bool launch_attn_decode_mfma(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
-                             const float* cs, const float* sn, int heads, int kv_heads, int D, int window, int splits,
-                             float* part, int chunk_fixed, int max_ctx, const AttnMerge& mg, hipStream_t st);
-// workgroups of the grouped decode attention kernel the chip holds at once (0 = shape not covered): the all-to-all
-// merge needs the whole grid resident
-int attn_decode_mfma_slots(int kv_dtype, int rep);
 
 // ---- woq_gemm_f16.hip: the prompt pass's MFMA GEMM ----------------------------------------------------------------
 // workspace bytes of one blob's [M, K] x [K, N] call, fragment image of the float weight types included (4-8x the

@@ -1,10 +1,12 @@
 // woq_ops.hip — the ops between the quantised linears, as gfx950 kernels.
 //
 // In the reference these are stock HF transformers module forwards run by PyTorch CPU ops
-// (LlamaRMSNorm, apply_rotary_pos_emb, SiLU*mul in LlamaMLP, GPT-2 gelu_new,
-// eager attention over the KV cache); ITREX contributes no code there. All are HBM/latency-bound
-// vector kernels: 16-byte loads, fp32 math, wave64 shuffles; no MFMA.
-#include "woq_attn_decode.h"
+// (LlamaRMSNorm, apply_rotary_pos_emb, SiLU*mul in LlamaMLP, GPT-2 gelu_new);
+// ITREX contributes no code there. All are HBM/latency-bound vector kernels: 16-byte loads, fp32 math,
+// wave64 shuffles; no MFMA. Also here: the head (embedding row) and the token tail (lm_head, argmax) of the
+// engine's decode step; its attention is woq_attn_decode.hip.
+#include <algorithm>
+
 #include "woq_device.h"
 #include "woq_host.h"
 #include "woq_xq.h"
@@ -171,76 +173,6 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
   }
 }
 
-template <typename KV, int HD, bool SPLIT>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restrict__ qkv, KV* __restrict__ kcache,
-                                                          KV* __restrict__ vcache, const int32_t* __restrict__ pos_p,
-                                                          const float* __restrict__ cs, const float* __restrict__ sn,
-                                                          int hk, int window, int spw,
-                                                          float* __restrict__ out, XqPtrs xo, AttnMerge mg) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  // hk = heads | kv_heads << 16: with `window` the 13th and 14th argument dwords — everything in front of the first
-  // K / V request is preloaded (the argument segment's first read costs ~1 us, profiles/r06c_xqs_stage_stamps.txt)
-  const int heads = hk & 0xffff, kv_heads = hk >> 16;
-  // workgroup ids go round-robin over the 8 XCDs: give every XCD a run of consecutive heads, so that the query heads
-  // sharing a kv head (GQA) share an L2 instead of pulling the same cache rows into several
-  const int bx = (int)blockIdx.x;
-  const int h = (heads & 7) == 0 ? (bx & 7) * (heads >> 3) + (bx >> 3) : bx;
-  attn_decode_body<KV, HD, SPLIT>(sm, h, (int)blockIdx.y, (int)gridDim.y, AttnPlain{qkv}, kcache, vcache, pos_p, cs,
-                                  sn, heads, kv_heads, window, spw, out, xo);
-  if constexpr (SPLIT) {  // `out` = the partial buffer; the head's last slice workgroup merges (woq_attn_merge.h)
-    if (mg.counter != nullptr) attn_slices_merge<HD, 1>(out, heads, h, 1, (int)gridDim.y, mg.counter + h, mg, sm);
-  }
-}
-
-// merge the slices of attn_decode_kernel<SPLIT>: out[h][d] = sum_s o_s[d] e^(m_s - m) / sum_s l_s e^(m_s - m).
-// 256 threads per head; two thread groups of HD walk alternate slices. Round 4: ONE round trip — a thread's partial
-// rows (clamped, branch-free; rows past ns weigh 0) are requested together with the slice maxima / sums, before anything
-// is waited for; the weights are then worked out in LDS while the rows are in flight (round 3 read the maxima, then
-// the rows: two dependent trips in a launch that is nothing but latency, 5.1 us per layer at 32 slices).
-template <int HD>
-__global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restrict__ part, int ns,
-                                                          float* __restrict__ out, XqPtrs xo) {
-  __shared__ float ms[64], wl[64], wsc[64], red[256];
-  constexpr int GROUPS = 256 / HD;                // 2 for head_dim 128, 4 for 64
-  constexpr int PER = ATTN_MAX_SLICES / GROUPS;   // partial rows a thread may have to fetch
-  const int h = blockIdx.x, tid = threadIdx.x;
-  const int d = tid % HD, grp = tid / HD;
-  const float* p = part + (size_t)h * ATTN_MAX_SLICES * HD;  // woq_attn_merge.h: o [head][64][HD], then ml [head][64][2]
-  const float* pml = part + (size_t)gridDim.x * ATTN_MAX_SLICES * HD + (size_t)h * ATTN_MAX_SLICES * 2;
-  const int si = min(tid, ns - 1);
-  const float m_r = pml[si * 2], l_r = pml[si * 2 + 1];
-  float v[PER];
-#pragma unroll
-  for (int u = 0; u < PER; ++u) v[u] = p[(size_t)min(grp + u * GROUPS, ns - 1) * HD + d];
-  if (tid < ns) ms[tid] = m_r, wl[tid] = l_r;
-  __syncthreads();
-  float m = -INFINITY;
-  for (int s = 0; s < ns; ++s) m = fmaxf(m, ms[s]);
-  if (tid < ns) {
-    const float w = ms[tid] == -INFINITY ? 0.f : __expf(ms[tid] - m);
-    wsc[tid] = w;
-    wl[tid] *= w;
-  }
-  __syncthreads();
-  float l = 0.f;
-  for (int s = 0; s < ns; ++s) l += wl[s];
-  float o = 0.f;
-#pragma unroll
-  for (int u = 0; u < PER; ++u) {
-    const int s = grp + u * GROUPS;
-    if (s < ns) o = fmaf(v[u], wsc[s], o);  // ascending s
-  }
-  red[tid] = o;
-  __syncthreads();
-  if (grp == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int g2 = 0; g2 < GROUPS; ++g2) t += red[g2 * HD + d];
-    out[(size_t)h * HD + d] = t / l;
-    if (xo.limbs != nullptr) xq_emit16(t / l, xo, (h * HD + d) >> 4, d & 15);
-  }
-}
-
 // logits[v] = sum_h xn[h] * W[v][h], W dense fp16/bf16 [vocab, hidden] (lm_head is NOT quantised:
 // utils/config.py:836-837). Final RMSNorm fused in the prologue. One wave per vocab row, 4 rows per WG.
 __global__ __launch_bounds__(256) void lm_head_kernel(const float* __restrict__ hidden_in,
@@ -384,71 +316,6 @@ void launch_embed(const void* embed, int dtype, const int32_t* token, int hidden
                      norm_w, xo, ssq_out, step_seq, pos, max_ctx, status);
 }
 
-template <typename KV, int HD>
-static int launch_attn_t(const float* qkv, void* kcache, void* vcache, const int32_t* pos, const float* cs,
-                         const float* sn, int heads, int kv_heads, int max_ctx, int window, float* out, int splits,
-                         float* part, const XqPtrs& xo, unsigned int* merge_counters, hipStream_t st) {
-  const int reach = window > 0 ? min(window, max_ctx) : max_ctx;  // positions a query can see
-  const int span = splits > 1 ? ((((reach + splits - 1) / splits) + 63) & ~63) + 64 : reach;
-  const int spw = attn_dec_spw(span);
-  const size_t lds = attn_dec_lds_floats(HD, span) * 4;
-  if (lds > 160 * 1024) return woq::fail("QBits: max_ctx too large for the decode attention (raise attn_splits)");
-  if (splits > 1) {
-    constexpr auto k = attn_decode_kernel<KV, HD, true>;
-    if (const int rc = allow_dynamic_lds<k>(160 * 1024)) return rc;
-    const AttnMerge mg{merge_counters, out, xo};
-    hipLaunchKernelGGL(k, dim3(heads, splits), dim3(256), lds, st, qkv, (KV*)kcache, (KV*)vcache, pos, cs, sn,
-                       heads | (kv_heads << 16), window, spw, part, XqPtrs{nullptr, nullptr, nullptr}, mg);
-    if (merge_counters == nullptr)
-      hipLaunchKernelGGL(attn_combine_kernel<HD>, dim3(heads), dim3(256), 0, st, part, splits, out, xo);
-    return 0;
-  }
-  constexpr auto k = attn_decode_kernel<KV, HD, false>;
-  if (const int rc = allow_dynamic_lds<k>(160 * 1024)) return rc;
-  hipLaunchKernelGGL(k, dim3(heads), dim3(256), lds, st, qkv, (KV*)kcache, (KV*)vcache, pos, cs, sn,
-                     heads | (kv_heads << 16), window, spw, out, xo,
-                     AttnMerge{nullptr, nullptr, XqPtrs{nullptr, nullptr, nullptr}});
-  return 0;
-}
-
-int launch_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos,
-                       const float* cs, const float* sn, int heads, int kv_heads, int D, int max_ctx, int window,
-                       float* out, int splits, int grouped, float* part, const XqPtrs& xo, hipStream_t st,
-                       unsigned int* merge_counters, int chunk_fixed, const AttnA2A* a2a_grouped, const unsigned int* seq,
-                       int layer) {
-  if (D != 64 && D != 128) return woq::fail("QBits: attention head_dim must be 64 or 128");
-  if (splits > ATTN_MAX_SLICES) return woq::fail("QBits: at most 64 context slices");
-  // grouped-query form (woq_prefill.hip): only where it applies — head_dim 128, 2 / 4 / 8 query heads per kv head,
-  // an fp16 or fp8 cache — anything else keeps the per-query-head slices
-  // a2a_grouped (round 6, nullable; grouped form only): the slices merge among themselves through tagged granules
-  // (woq_attn_merge.h) — no combine launch; the caller has checked that the grid can be resident at once
-  AttnMerge mg{merge_counters, out, xo};
-  const bool a2a = grouped && a2a_grouped != nullptr && merge_counters == nullptr && splits <= 32;
-  if (a2a) mg.part_g = a2a_grouped->part_g, mg.seq = seq, mg.layer = layer, mg.status = a2a_grouped->status;
-  if (grouped && launch_attn_decode_mfma(qkv, kcache, vcache, kv_dtype, pos, cs, sn, heads, kv_heads, D, window, splits,
-                                          part, chunk_fixed, max_ctx, mg, st)) {
-    if (merge_counters == nullptr && !a2a) launch_attn_combine(part, heads, D, splits, out, xo, st);
-    return 0;
-  }
-#define WOQ_ATTN_DEC(T)                                                                                              \
-  return D == 128 ? launch_attn_t<T, 128>(qkv, kcache, vcache, pos, cs, sn, heads, kv_heads, max_ctx, window, out,   \
-                                          splits, part, xo, merge_counters, st)                                     \
-                  : launch_attn_t<T, 64>(qkv, kcache, vcache, pos, cs, sn, heads, kv_heads, max_ctx, window, out,    \
-                                         splits, part, xo, merge_counters, st);
-  if (kv_dtype == WOQ_F16) { WOQ_ATTN_DEC(_Float16) }
-  if (kv_dtype == WOQ_FP8_E4M3) { WOQ_ATTN_DEC(Fp8) }
-  WOQ_ATTN_DEC(__bf16)
-#undef WOQ_ATTN_DEC
-}
-
-void launch_attn_combine(const float* part, int heads, int D, int splits, float* out, const XqPtrs& xo,
-                         hipStream_t st) {
-  if (D == 128)
-    hipLaunchKernelGGL(attn_combine_kernel<128>, dim3(heads), dim3(256), 0, st, part, splits, out, xo);
-  else
-    hipLaunchKernelGGL(attn_combine_kernel<64>, dim3(heads), dim3(256), 0, st, part, splits, out, xo);
-}
-
 void launch_lm_head(const float* hidden_in, const float* norm_w, float eps, const void* W, int w_dtype, int hidden,
                     int vocab, float* logits, float* pmax, int32_t* pidx, hipStream_t st) {
   hipLaunchKernelGGL(lm_head_kernel, dim3((vocab + 15) / 16), dim3(256), (size_t)hidden * 4, st, hidden_in, norm_w,
@@ -518,40 +385,6 @@ int woq_gelu(const void* x_dev, int dtype, size_t n, int approximate, void* out_
   hipLaunchKernelGGL(gelu_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x_dev, dtype, n, approximate,
                      out_dev);
   WOQ_HIP(hipGetLastError());
-  WOQ_END
-}
-
-// test entry point (include/woq_hip_experimental.h): the engine's separate decode-attention launches on their own
-WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos_dev,
-                                  const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
-                                  int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
-                                  float* out, void* stream) {
-  WOQ_TRY
-  WOQ_CHECK(heads > 0 && kv_heads > 0 && heads % kv_heads == 0 && max_ctx > 0 && window >= 0 && splits >= 1,
-            "QBits: bad attention shape");
-  WOQ_CHECK(merge == 0 || merge == 1, "QBits: merge must be 0 (combine launch) or 1 (last-arriver counters)");
-  const hipStream_t st = (hipStream_t)stream;
-  // the partial buffer of woq_attn_merge.h (o [heads][64][D], then ml [heads][64][2]) and one counter per head
-  const size_t part_bytes = (size_t)heads * ATTN_MAX_SLICES * (head_dim + 2) * sizeof(float);
-  float* part = nullptr;
-  unsigned int* counters = nullptr;
-  WOQ_HIP(hipMallocAsync((void**)&part, part_bytes, st));
-  if (merge) {
-    if (hipMallocAsync((void**)&counters, (size_t)heads * sizeof(unsigned int), st) != hipSuccess ||
-        hipMemsetAsync(counters, 0, (size_t)heads * sizeof(unsigned int), st) != hipSuccess) {
-      if (counters) hipFreeAsync(counters, st);
-      hipFreeAsync(part, st);
-      return woq::fail("QBits: could not allocate the attention merge counters");
-    }
-  }
-  const int rc = launch_attn_decode(qkv, kcache, vcache, kv_dtype, pos_dev, cos_dev, sin_dev, heads, kv_heads, head_dim,
-                                    max_ctx, window, out, splits, grouped, part, XqPtrs{nullptr, nullptr, nullptr}, st,
-                                    counters, chunk_fixed, nullptr, nullptr, 0);
-  const hipError_t le = hipGetLastError();
-  if (counters) hipFreeAsync(counters, st);
-  hipFreeAsync(part, st);
-  if (rc) return rc;
-  WOQ_HIP(le);
   WOQ_END
 }
 

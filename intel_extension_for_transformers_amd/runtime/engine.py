@@ -328,10 +328,15 @@ class WoqDecoderEngine:
         """Reset the sticky status (after the caller dealt with what it reported)."""
         L.check(L.lib().woq_engine_clear_status(self._h, L.stream_ptr()))
 
+    def attn_plan(self, splits=0, grouped=-1):
+        """How the next step / capture runs its attention (layer 0): a dict of form (L.ATTN_*), merge (L.ATTN_MERGE_*),
+        slices, chunk_fixed, ... (L.engine_attn_plan); `splits` > 0 / `grouped` >= 0 ask about another slice count /
+        grouped request without changing the engine."""
+        return L.engine_attn_plan(self._h, splits, grouped)
+
     def _grouped_applies(self):
-        c = self.cfg
-        return (c.head_dim == 128 and c.kv_heads > 0 and c.heads // c.kv_heads in (2, 4, 8)
-                and c.kv_dtype in (L.F16, L.FP8_E4M3))
+        """True when a sliced context asked to run grouped would run the grouped-query matrix-core form."""
+        return self.attn_plan(splits=2, grouped=1)["form"] == L.ATTN_GROUPED
 
     def tune_attn_for(self, positions):
         """Pick the regime for a context of `positions` cached tokens (host-side hint: the position lives on the
@@ -364,12 +369,8 @@ class WoqDecoderEngine:
             self.set_attn_splits(max(2, min(32, 1024 // max(1, self.cfg.heads), positions // 64)))
 
     def uses_fused_attn_sliced(self):
-        """True when a sliced context would ride in the fused qkv launch (probe: the engine's own predicate at two slices)."""
-        keep = L.lib().woq_engine_attn_splits(self._h)
-        L.check(L.lib().woq_engine_set_attn_splits(self._h, 2))
-        ok = bool(L.lib().woq_engine_fuse_attn(self._h))
-        L.check(L.lib().woq_engine_set_attn_splits(self._h, keep))
-        return ok
+        """True when a sliced context would ride in the fused qkv launch (the engine's plan at two slices)."""
+        return self.attn_plan(splits=2)["form"] == L.ATTN_FUSED
 
     def kv_cache(self, which="k"):
         """The engine's K or V cache as a torch view [max_batch, layers, max_ctx, kv_heads, head_dim] (no copy)."""

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+from intel_extension_for_transformers_amd import _lib as L
 from oracle import woq_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -148,8 +149,6 @@ def test_decode_step_sliced_regime_7b_attention_geometry_vs_oracle(ctx, sliced, 
 
 
 def L_splits(eng):
-    from intel_extension_for_transformers_amd import _lib as L
-
     return int(L.lib().woq_engine_attn_splits(eng._h))
 
 
@@ -245,6 +244,8 @@ def test_fused_launch_takes_grouped_query_and_window_shapes(kv_dtype, window):
     for mode in ("separate", "fused"):
         eng.set_fuse_attn(mode == "fused")
         assert eng.uses_fused_attn() == (mode == "fused")
+        plan = eng.attn_plan()  # the two runs compare two forms: one launch against qkv GEMV + one workgroup per head
+        assert (plan["form"], plan["merge"]) == ((L.ATTN_FUSED if mode == "fused" else L.ATTN_PER_HEAD), L.ATTN_MERGE_NONE)
         eng.prefill(prompt, greedy=True)
         logs = []
         for _ in range(5):
@@ -287,6 +288,9 @@ def test_fused_launch_with_context_slices_equals_separate_launches(kv_heads, kv_
     for mode in ("separate", "fused"):
         eng.set_fuse_attn(mode == "fused")
         assert eng.uses_fused_attn() == (mode == "fused") and L_splits(eng) == splits
+        plan = eng.attn_plan()  # slices merging among themselves in the fused launch against slices + combine launch
+        assert (plan["form"], plan["merge"], plan["slices"]) == (
+            (L.ATTN_FUSED, L.ATTN_MERGE_A2A, splits) if mode == "fused" else (L.ATTN_PER_HEAD, L.ATTN_MERGE_COMBINE, splits))
         eng.prefill(prompt, greedy=True)
         logs = []
         for _ in range(5):
@@ -325,6 +329,9 @@ def test_grouped_slices_self_merge_at_the_mistral_geometry(kv_dtype, splits, ctx
         eng.set_attn_splits(splits)
         eng.set_attn_grouped(True)
         assert eng.uses_xq() and not eng.uses_fused_attn()
+        plan = eng.attn_plan()
+        assert (plan["form"], plan["merge"], plan["slices"]) == (
+            L.ATTN_GROUPED, L.ATTN_MERGE_A2A if a2a == "1" else L.ATTN_MERGE_COMBINE, splits)
         eng.prefill(prompt, greedy=True)
         logs = []
         for _ in range(4):

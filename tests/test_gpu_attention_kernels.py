@@ -1,7 +1,8 @@
 """The engine's attention kernels on their own, element by element against a float64 reference (tests/attn_reference.py),
 through the test entry points of include/woq_hip_experimental.h: `rope_append_kernel` and `attn_prefill_kernel`
-(csrc/woq_prefill.hip), and the decode launches — `attn_decode_kernel` with one workgroup per head or context slices,
-`attn_combine_kernel`, the last-arriver slice merge and the grouped-query `attn_decode_mfma_kernel`.
+(csrc/woq_prefill.hip), and the decode launches (csrc/woq_attn_decode.hip) — `attn_decode_kernel` with one workgroup
+per head or context slices, `attn_combine_kernel`, the last-arriver slice merge and the grouped-query
+`attn_decode_mfma_kernel`.
 
 Inputs (every family at every shape where it applies): random; needles (query p of head h is beta times the stored K
 row of one target — p + 1, the first future position; p, the diagonal; p + 1 - window, the oldest visible one;

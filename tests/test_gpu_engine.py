@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from intel_extension_for_transformers_amd import _lib as L
 from oracle import woq_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +94,15 @@ def _tiny(group, asym, scale_dtype, seed=0, max_ctx=64, max_batch=1, head_dim=64
     eng.set_head(embed, torch.from_numpy(norm), lm)
     oracle = orc.LlamaOracle(cfg, embed.float().numpy(), layers, norm, lm.float().numpy())
     return eng, oracle, cfg
+
+
+def _assert_attn_plan(eng, form, merge=None, chunk=None):
+    """the form (and slice merge, and grouped chunk) the engine's next step runs its attention in: an A/B test whose two
+    engines ran the same form would pass without comparing anything"""
+    p = eng.attn_plan()
+    assert p["form"] == form, p
+    assert merge is None or p["merge"] == merge, p
+    assert chunk is None or p["chunk_fixed"] == chunk, p
 
 
 @pytest.mark.parametrize("group,asym,scale_dtype", [(128, False, "fp16"), (32, True, "fp32"), (-1, False, "bf16")])
@@ -329,6 +339,8 @@ def test_decode_attention_context_slices_vs_oracle(head_dim, splits, grouped, hi
     eng, oracle, cfg = _tiny(128, False, "fp16", seed=2, max_ctx=256, head_dim=head_dim, attn_splits=splits,
                              hidden=hidden, attn_grouped=grouped)
     assert cfg["kv_heads"] == 128 // head_dim and cfg["heads"] == hidden // head_dim
+    _assert_attn_plan(eng, L.ATTN_GROUPED if grouped else L.ATTN_PER_HEAD)
+    assert eng.attn_plan()["slices"] == splits
     rng = np.random.default_rng(3)
     toks = rng.integers(0, cfg["vocab"], 200).tolist()
     for i, t in enumerate(toks):
@@ -364,6 +376,7 @@ def test_grouped_attention_fixed_chunk_slices_vs_oracle(hidden, chunk, splits, m
                              attn_grouped=True)
     monkeypatch.delenv("WOQ_ATTN_FOLD")
     eng.set_attn_chunk(chunk)
+    _assert_attn_plan(eng, L.ATTN_GROUPED, L.ATTN_MERGE_COUNTER, chunk)
     rng = np.random.default_rng(8)
     toks = rng.integers(0, cfg["vocab"], 200).tolist()
     check = {0, 1, chunk - 1, chunk, chunk + 1, 2 * chunk - 1, 2 * chunk, splits * chunk - 1, splits * chunk,
@@ -401,6 +414,8 @@ def test_grouped_slices_merging_among_themselves_equal_the_combine_launch(hidden
         monkeypatch.setenv("WOQ_GROUPED_A2A", a2a)
         engs.append(_tiny(128, False, "fp16", seed=6, max_ctx=256, head_dim=128, attn_splits=splits, hidden=hidden,
                           attn_grouped=True, kv_dtype=kv_dtype)[0])
+    _assert_attn_plan(engs[0], L.ATTN_GROUPED, L.ATTN_MERGE_COMBINE)
+    _assert_attn_plan(engs[1], L.ATTN_GROUPED, L.ATTN_MERGE_A2A)
     cfg_vocab = 384
     rng = np.random.default_rng(9)
     for i, t in enumerate(rng.integers(0, cfg_vocab, 150).tolist()):
@@ -423,17 +438,46 @@ def test_grouped_slices_merging_among_themselves_equal_the_combine_launch(hidden
     assert torch.equal(toks[0][0], toks[1][0]) and torch.equal(toks[0][1], toks[1][1])
 
 
+@pytest.mark.parametrize("kv_dtype,grouped_from", [(torch.float16, True), (torch.bfloat16, False)])
+def test_tuner_on_a_context_two_slices_cannot_hold(kv_dtype, grouped_from):
+    """max_ctx 79233 at head_dim 128: a per-head workgroup over half the context is beyond its 160 KiB of LDS, so the
+    plan at two slices — what `tune_attn_for` asks about before it picks a slice count — is a refusal. That is an answer
+    (not fused, not grouped), not an error: the tuner goes on to a slice count that fits, as it always did, for short
+    and long contexts, grouped-query (fp16 cache) or not (bf16 cache); the engine itself is left as it was set."""
+    eng, _, cfg = _tiny(128, False, "fp16", seed=1, max_ctx=79233, head_dim=128, hidden=256, kv_dtype=kv_dtype)
+    p = eng.attn_plan(splits=2)
+    assert (p["form"], p["slices"], p["refused"]) == (L.ATTN_PER_HEAD, 2, 1)
+    assert "max_ctx too large" in L.lib().woq_last_error().decode()
+    assert not eng.uses_fused_attn_sliced() and eng._grouped_applies() == grouped_from
+    for positions, grouped in ((5000, False), (70000, grouped_from)):
+        eng.tune_attn_for(positions)
+        p = eng.attn_plan()
+        assert p["refused"] == 0 and p["slices"] == 32 and p["lds"] <= 160 * 1024, p
+        assert p["form"] == (L.ATTN_GROUPED if grouped else L.ATTN_PER_HEAD), p
+    eng.set_attn_grouped(False)
+    eng.token.fill_(5)
+    eng.pos.fill_(0)
+    eng.step(greedy=False)
+    torch.cuda.synchronize()
+    assert eng.status() == 0 and bool(torch.isfinite(eng.logits).all())
+
+
 @pytest.mark.parametrize("grouped,hidden,head_dim", [(False, 256, 64), (False, 256, 128), (True, 512, 128)])
 def test_slice_merge_by_last_workgroup_equals_the_combine_launch(grouped, hidden, head_dim, monkeypatch):
-    """The two ways of merging context-slice partials — the last slice workgroup of a head (default) and the separate
-    combine launch (WOQ_ATTN_FOLD=0, the A/B twin) — run the same sums in the same order: logits equal to 1e-6 of the
-    largest over 150 decode steps, greedy tokens identical."""
+    """The two ways of merging context-slice partials — the separate combine launch (the default) and the last slice
+    workgroup of a head (WOQ_ATTN_FOLD=1, opt-in) — run the same sums in the same order: logits equal to 1e-6 of the
+    largest over 150 decode steps, greedy tokens identical. (WOQ_GROUPED_A2A=0: by default the grouped slices of the
+    twin without counters would merge among themselves and no combine launch would run.)"""
+    monkeypatch.setenv("WOQ_GROUPED_A2A", "0")
     monkeypatch.setenv("WOQ_ATTN_FOLD", "0")
     e0, _, cfg = _tiny(128, False, "fp16", seed=6, max_ctx=256, head_dim=head_dim, attn_splits=4, hidden=hidden,
                        attn_grouped=grouped)
     monkeypatch.setenv("WOQ_ATTN_FOLD", "1")
     e1, _, _ = _tiny(128, False, "fp16", seed=6, max_ctx=256, head_dim=head_dim, attn_splits=4, hidden=hidden,
                      attn_grouped=grouped)
+    form = L.ATTN_GROUPED if grouped else L.ATTN_PER_HEAD
+    _assert_attn_plan(e0, form, L.ATTN_MERGE_COMBINE)
+    _assert_attn_plan(e1, form, L.ATTN_MERGE_COUNTER)
     rng = np.random.default_rng(9)
     for i, t in enumerate(rng.integers(0, cfg["vocab"], 150).tolist()):
         outs = []

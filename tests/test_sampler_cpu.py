@@ -87,6 +87,8 @@ def test_abi_and_binding_carry_the_sampler_entry_points():
     assert re.search(r"WOQ_API int woq_probe_gemv_f32\(", exp) and "woq_probe_gemv_f32" in _lib.EXPERIMENTAL_EXPORTS
     assert re.search(r"WOQ_API int woq_probe_gemm_plan\(", exp) and "woq_probe_gemm_plan" in _lib.EXPERIMENTAL_EXPORTS
     assert re.search(r"WOQ_API int woq_probe_gemm_f16\(", exp) and "woq_probe_gemm_f16" in _lib.EXPERIMENTAL_EXPORTS
+    for n in ("woq_probe_attn_decode_plan", "woq_engine_attn_plan"):
+        assert re.search(r"WOQ_API int %s\(" % n, exp) and n in _lib.EXPERIMENTAL_EXPORTS
     assert "#define WOQ_ABI_VERSION 4" in header and "struct woq_sampler_config" in header
     assert ctypes.sizeof(_lib.SamplerConfig) == 32
     cfg = _lib.sampler_config(True, 0.1, 40, 0.75, 1.1, seed=(7 << 32) | 9)
@@ -96,5 +98,6 @@ def test_abi_and_binding_carry_the_sampler_entry_points():
     assert all(n in integration for n in new)
     if os.path.exists(_lib.LIB_PATH):
         lib = ctypes.CDLL(_lib.LIB_PATH)
-        for n in new | {"woq_probe_sample", "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16"}:
+        for n in new | {"woq_probe_sample", "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16",
+                        "woq_probe_attn_decode_plan", "woq_engine_attn_plan"}:
             getattr(lib, n)
