@@ -243,6 +243,8 @@ WOQ_API int woq_engine_fuse_attn(woq_engine* e);
  * winning logit (all NaN) and fed token 0; bit 3: a sampled step found more than 1024 scores at or above the k-th
  * largest (ties) and kept the 1024 with the lowest ids among the tied — informational, the token stands; not set
  * when the tie is at -inf below a finite best score (fewer than k finite scores: those candidates weigh 0);
+ * bit 4: a step with a token guide picked an id that the guide's state bans (a state with every id banned, which a
+ * well-formed guide does not have) or whose entry names no state of the table — the state stayed where it was;
  * -1 = the read itself failed.
  * Synchronises `stream`. */
 WOQ_API int woq_engine_status(woq_engine* e, void* stream);
@@ -321,6 +323,27 @@ WOQ_API int woq_engine_set_sampler_controls(woq_engine* e, const woq_sampler_con
  * int32; may be NULL with n == 0) after zeroing the table when clear != 0; stream-ordered. */
 WOQ_API int woq_engine_sampler_counts(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream);
 WOQ_API void* woq_engine_sampler_count_ptr(woq_engine* e);
+/* ---- token guide: constrained decoding (new entry points only; WOQ_ABI_VERSION stays 4, no struct changes) -----------
+ * A guide is a deterministic automaton over token ids as a dense table next[n_states][vocab] of uint16_t: 0xFFFF = the
+ * id is banned in that state, any other value = the state after that id; 1 <= n_states <= 65535. With one installed
+ * beside a sampler, every chaining step builds its scores by the four steps of the sampler controls above (neutral
+ * controls when none are installed) and then, as step 5, s = -inf where next[state][i] == 0xFFFF; the pick follows as
+ * above, and a one-thread launch after it sets state = next[state][token]. Two more launches per step than the plain
+ * sampled tail (the pre-pass and the advance), shapes by the vocabulary alone. The state lives on the device, so bursts
+ * of steps and replayed graphs follow the guide with no host round trip. A well-formed guide has no state with every
+ * id banned; the device does not check: such a state picks what the sampler picks among all -inf scores, stays, and
+ * raises status bit 4. The log-probability record keeps describing the raw logits.
+ * set_guide copies the table (DEVICE memory, n_states * vocab uint16_t) into memory the engine owns, grown when needed
+ * and kept; the kernels read the table pointer and the state from a device struct, so installing another guide over
+ * an installed one, or resetting the state, keeps a captured graph valid. Installing the first guide or removing it
+ * (table_dev == NULL; also woq_engine_set_sampler(e, NULL)) drops a captured graph. Needs a sampler installed.
+ * Synchronises the device. Fails with a "QBits:" message on a tensor-parallel engine, for n_states outside 1..65535
+ * and for start_state outside [0, n_states). */
+WOQ_API int woq_engine_set_guide(woq_engine* e, const void* table_dev, int n_states, int start_state);
+/* state = `state`, stream-ordered (a request starts from its guide's start state, or from the state after its prompt) */
+WOQ_API int woq_engine_guide_reset(woq_engine* e, int state, void* stream);
+/* int32[1] on the device: the guide's current state; NULL before the first woq_engine_set_guide */
+WOQ_API void* woq_engine_guide_state_ptr(woq_engine* e);
 /* ---- per-token log-probabilities (new entry points only; WOQ_ABI_VERSION stays 4) ----------------------------------
  * With recording on, every step that chains on the device (greedy != 0: the prompt pass's tail, woq_engine_step /
  * _steps / _capture / _replay) writes, after its pick, one row of three device logs indexed like the token log (row p

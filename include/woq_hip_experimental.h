@@ -128,6 +128,16 @@ WOQ_API int woq_probe_sample_controls(const float* logits, int vocab, uint32_t* 
                                       const int32_t* bias_ids_host, const float* bias_vals_host, const float* u_or_null,
                                       const int32_t* pos_dev, int32_t* token_out, float* adjusted_out,
                                       uint32_t* kept_out, int* status, void* stream);
+/* the token tail with a token guide alone (tests/test_gpu_guide_kernel.py), forwarding to the engine's own launchers:
+ * as woq_probe_sample_controls, plus table_dev = device uint16_t [n_states][vocab], `state` = the state whose row masks
+ * the scores, `advance_state` = the state the advance starts from (< 0: `state`; another one lets a test hand the
+ * advance a pick that its row bans), state_out = device int32 that receives the state after the advance. status bit 4:
+ * the pick was banned in the advance's row (the state stayed). */
+WOQ_API int woq_probe_guide(const float* logits, int vocab, uint32_t* seen, uint32_t* counts,
+                            const woq_sampler_config* cfg, const woq_sampler_controls* ctl,
+                            const int32_t* bias_ids_host, const float* bias_vals_host, const uint16_t* table_dev,
+                            int n_states, int state, int advance_state, const float* u_or_null, const int32_t* pos_dev,
+                            int32_t* token_out, float* adjusted_out, int32_t* state_out, int* status, void* stream);
 /* the log-probability record alone (tests/test_gpu_logprob_kernel.py), forwarding to the engine's own launcher
  * unchanged: logits fp32 [vocab], token_dev = device int32 id whose log-probability goes to chosen_out[0];
  * top_id_out20 / top_lp_out20 = device int32 / fp32 [20]. Scratch is allocated and freed on `stream`. */

@@ -96,6 +96,7 @@ EXPORTS = [
     "woq_engine_set_sampler", "woq_engine_sampler_seen", "woq_engine_sampler_seen_ptr",
     "woq_engine_set_logprobs", "woq_engine_logprobs", "woq_engine_logprob_ptr", "woq_engine_prefill_scored",
     "woq_engine_set_sampler_controls", "woq_engine_sampler_counts", "woq_engine_sampler_count_ptr",
+    "woq_engine_set_guide", "woq_engine_guide_reset", "woq_engine_guide_state_ptr",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -105,7 +106,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
     "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16", "woq_probe_sample_controls",
-    "woq_probe_attn_decode_plan", "woq_engine_attn_plan",
+    "woq_probe_attn_decode_plan", "woq_engine_attn_plan", "woq_probe_guide",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -214,6 +215,12 @@ def lib():
     L.woq_engine_sampler_count_ptr.argtypes = [vp]
     L.woq_probe_sample_controls.argtypes = [vp, ci, vp, vp, ctypes.POINTER(SamplerConfig),
                                             ctypes.POINTER(SamplerControls)] + [vp] * 9
+    L.woq_engine_set_guide.argtypes = [vp, vp, ci, ci]
+    L.woq_engine_guide_reset.argtypes = [vp, ci, vp]
+    L.woq_engine_guide_state_ptr.restype = vp
+    L.woq_engine_guide_state_ptr.argtypes = [vp]
+    L.woq_probe_guide.argtypes = [vp, ci, vp, vp, ctypes.POINTER(SamplerConfig), ctypes.POINTER(SamplerControls), vp, vp,
+                                  vp, ci, ci, ci] + [vp] * 7
     L.woq_engine_set_logprobs.argtypes = [vp, ci]
     L.woq_engine_logprobs.argtypes = [vp]
     L.woq_engine_logprob_ptr.restype = vp
@@ -352,6 +359,22 @@ def probe_sample_controls(logits, seen, counts, cfg, controls, pos, token_out, a
                                          _ptr(adjusted_out), _opt(kept_out), _opt(status), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
+
+
+GUIDE_BANNED = 0xFFFF  # a token guide's table entry for a banned id (csrc/woq_host.h GUIDE_BANNED)
+STATUS_GUIDE_BANNED_PICK = 16  # woq_engine_status bit 4
+
+
+def probe_guide(logits, seen, counts, cfg, controls, table, state, pos, token_out, adjusted_out, state_out,
+                advance_state=-1, u=None, status=None):
+    """the token tail with a token guide alone (woq_probe_guide): as `probe_sample_controls`, `table` a device int16 /
+    uint16 tensor [n_states, vocab], `state` the row that masks, `advance_state` the row the advance reads (< 0: the
+    same), `state_out` a device int32 [1]."""
+    ctl, ids, vals = controls
+    check(lib().woq_probe_guide(_ptr(logits), int(logits.numel()), _ptr(seen), _ptr(counts), ctypes.byref(cfg),
+                                ctypes.byref(ctl), ids, vals, _ptr(table), int(table.shape[0]), int(state),
+                                int(advance_state), _opt(u), _ptr(pos), _ptr(token_out), _ptr(adjusted_out),
+                                _ptr(state_out), _opt(status), stream_ptr()))
 
 
 LOGPROB_TOP = 20  # ids a log-probability record lists per position (csrc/woq_logprob.hip LP_TOP)

@@ -135,6 +135,14 @@ struct woq_engine {
   float* samp_adj = nullptr;       // the pre-pass's scores
   int32_t* samp_bias_ids = nullptr;  // [1024] + [1024] staging of the (id, value) pairs
   float* samp_bias_vals = nullptr;
+  // token guide (woq_sample.hip): with `guide_on` the tail is the guided pre-pass + the sampling launch + the state's
+  // advance. It runs over the controls' memory whether or not controls are installed (neutral values then). The table
+  // is the engine's own copy, grown on demand and kept; `guide` (device) names it and holds the state
+  bool guide_on = false;
+  woq::GuideState* guide = nullptr;
+  woq::GuideState guide_host = {};  // what `guide` holds, bar the state the steps move
+  uint16_t* guide_table = nullptr;
+  size_t guide_cap = 0;  // bytes
   // log-probability record (woq_logprob.hip): with `logprobs_on` every chaining step writes row pos - 1 of three logs,
   // [max_ctx + 1] rows each like tok_log, after its pick. Allocated by the first woq_engine_set_logprobs(e, 1)
   bool logprobs_on = false;
@@ -256,6 +264,12 @@ static bool engine_can_fuse_next(const woq_engine* e, int greedy) {
 }
 // the chaining tail with a sampler installed: token <- sample(logits), tok_log[pos] = token, pos += 1
 static void engine_sample(woq_engine* e, hipStream_t st) {
+  if (e->guide_on) {  // the row of the guide's state bans ids before the pick, the state follows the pick
+    launch_sample_guided(e->logits, e->cfg.vocab, e->samp_seen, e->samp_count, e->samp_bias, e->samp_cfg, e->samp_ctl,
+                         e->guide, e->samp_adj, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr, e->fuse_status, st);
+    launch_guide_advance(e->guide, e->cfg.vocab, e->token, e->fuse_status, st);
+    return;
+  }
   if (e->controls_on) {
     launch_sample_controls(e->logits, e->cfg.vocab, e->samp_seen, e->samp_count, e->samp_bias, e->samp_cfg, e->samp_ctl,
                            e->samp_adj, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr, e->fuse_status, st);
@@ -736,6 +750,7 @@ void woq_engine_destroy(woq_engine* e) {
   for (void* p : {(void*)e->pf_h, (void*)e->pf_qkv, (void*)e->pf_attn, (void*)e->pf_act, e->pf_ws})
     if (p) hipFree(p);
   if (e->score_ws) hipFree(e->score_ws);
+  if (e->guide_table) hipFree(e->guide_table);
   delete e;
 }
 
@@ -869,9 +884,9 @@ int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg) {
     e->samp_cfg_host = *cfg;
   }
   const bool on = cfg != nullptr;
-  if (on != e->sampler_on || (!on && e->controls_on)) engine_drop_graphs(e);  // a captured graph holds the other tail
+  if (on != e->sampler_on || (!on && (e->controls_on || e->guide_on))) engine_drop_graphs(e);  // a graph holds the other tail
   e->sampler_on = on;
-  if (!on) e->controls_on = false;  // the controls live beside a sampler
+  if (!on) e->controls_on = e->guide_on = false;  // the controls and the guide live beside a sampler
   WOQ_END
 }
 
@@ -891,6 +906,17 @@ static int engine_controls_alloc(woq_engine* e) {
   e->samp_bias_ids = (int32_t*)(buf + 3 * v * 4);
   e->samp_bias_vals = (float*)(buf + (3 * v + 1024) * 4);
   e->samp_ctl = (woq_sampler_controls*)(buf + (3 * v + 2048) * 4);
+  WOQ_END
+}
+
+// neutral controls into the (allocated) controls' memory: what the guided tail reads when only a guide is installed
+static int engine_controls_neutral(woq_engine* e) {
+  WOQ_TRY
+  WOQ_HIP(hipDeviceSynchronize());
+  WOQ_HIP(hipMemset(e->samp_bias, 0xFF, (size_t)e->cfg.vocab * 4));  // no bias entries
+  WOQ_HIP(hipMemset(e->samp_ctl, 0, sizeof(woq_sampler_controls)));
+  e->samp_ctl_host = woq_sampler_controls{};
+  WOQ_HIP(hipDeviceSynchronize());
   WOQ_END
 }
 
@@ -915,12 +941,63 @@ int woq_engine_set_sampler_controls(woq_engine* e, const woq_sampler_controls* c
     WOQ_HIP(hipMemcpy(e->samp_ctl, ctl, sizeof(woq_sampler_controls), hipMemcpyHostToDevice));
     e->samp_ctl_host = *ctl;
     WOQ_HIP(hipDeviceSynchronize());
+  } else if (e->guide_on && e->controls_on) {
+    if (engine_controls_neutral(e) != 0) return 1;  // the guided tail goes on reading them
   }
   const bool on = ctl != nullptr;
   if (on != e->controls_on) engine_drop_graphs(e);  // a captured graph holds the other tail
   e->controls_on = on;
   WOQ_END
 }
+
+int woq_engine_set_guide(woq_engine* e, const void* table_dev, int n_states, int start_state) {
+  WOQ_TRY
+  WOQ_CHECK(e, "QBits: null engine");
+  if (table_dev == nullptr) {  // the table stays allocated for the next guide
+    if (e->guide_on) engine_drop_graphs(e);
+    e->guide_on = false;
+    return 0;
+  }
+  WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+            "QBits: a token guide needs the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
+  WOQ_CHECK(e->sampler_on, "QBits: a token guide needs a sampler installed (woq_engine_set_sampler first)");
+  const char* why = guide_problem(n_states, start_state);
+  if (why) return woq::fail(why);
+  if (engine_controls_alloc(e) != 0) return 1;
+  WOQ_HIP(hipDeviceSynchronize());  // steps in flight on any stream still read the struct and the table
+  if (!e->controls_on && engine_controls_neutral(e) != 0) return 1;
+  if (e->guide == nullptr) {
+    WOQ_HIP(hipMalloc((void**)&e->guide, sizeof(GuideState)));
+    e->owned.push_back(e->guide);
+  }
+  const size_t bytes = (size_t)n_states * (size_t)e->cfg.vocab * sizeof(uint16_t);
+  uint16_t* retired = nullptr;
+  if (bytes > e->guide_cap) {  // a failed allocation leaves the installed guide as it is
+    uint16_t* grown = nullptr;
+    WOQ_HIP(hipMalloc((void**)&grown, bytes));
+    retired = e->guide_table;
+    e->guide_table = grown, e->guide_cap = bytes;
+  }
+  WOQ_HIP(hipMemcpy(e->guide_table, table_dev, bytes, hipMemcpyDeviceToDevice));
+  e->guide_host = GuideState{e->guide_table, n_states, start_state};
+  WOQ_HIP(hipMemcpy(e->guide, &e->guide_host, sizeof(GuideState), hipMemcpyHostToDevice));
+  WOQ_HIP(hipDeviceSynchronize());
+  if (retired) hipFree(retired);  // the device struct names the new table by now
+  if (!e->guide_on) engine_drop_graphs(e);  // a captured graph holds the other tail
+  e->guide_on = true;
+  WOQ_END
+}
+
+int woq_engine_guide_reset(woq_engine* e, int state, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e && e->guide_on, "QBits: no token guide installed");
+  WOQ_CHECK(state >= 0 && state < e->guide_host.n_states, "QBits: the token guide's state is outside its table");
+  launch_guide_state_store(e->guide, state, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+void* woq_engine_guide_state_ptr(woq_engine* e) { return e && e->guide ? &e->guide->state : nullptr; }
 
 int woq_engine_sampler_counts(woq_engine* e, const int32_t* tokens_dev, int n, int clear, void* stream) {
   WOQ_TRY

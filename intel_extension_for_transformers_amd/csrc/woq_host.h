@@ -197,6 +197,28 @@ void launch_sampler_controls_store(const woq_sampler_controls& ctl, woq_sampler_
 // null when the controls are acceptable beside `cfg` (ids / vals: ctl.n_bias host entries), else the "QBits: ..." reason
 const char* sampler_controls_problem(const woq_sampler_controls& ctl, const woq_sampler_config& cfg, int vocab,
                                      const int32_t* ids, const float* vals);
+// A token guide (include/woq_hip.h woq_engine_set_guide): a dense table next[n_states][vocab] of uint16, GUIDE_BANNED =
+// the id is banned in that state, anything else = the state after that id. The kernels read the table pointer and the
+// state from this device struct, so another table or another state needs no new capture.
+constexpr uint16_t GUIDE_BANNED = 0xFFFFu;
+struct GuideState {
+  const uint16_t* table;
+  int32_t n_states;
+  int32_t state;
+};
+// launch_sample_controls with the guide's ban as the pre-pass's last step: adj[i] = -inf where
+// table[state * vocab + i] == GUIDE_BANNED (the row offset in 64 bits). The state is only read.
+void launch_sample_guided(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
+                          const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev,
+                          const GuideState* guide_dev, float* adj, const float* u_dev, int32_t* token,
+                          int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out, int* status,
+                          hipStream_t st, uint32_t* kept_out = nullptr);
+// after the pick, one thread: state <- table[state * vocab + token[0]], or, where that is GUIDE_BANNED (or no state of
+// the table), the state stays and status |= 16
+void launch_guide_advance(GuideState* guide_dev, int vocab, const int32_t* token, int* status, hipStream_t st);
+void launch_guide_state_store(GuideState* guide_dev, int32_t state, hipStream_t st);  // stream-ordered, capturable
+// null when (n_states, start_state) describe a table the guide takes, else the "QBits: ..." reason
+const char* guide_problem(int n_states, int start_state);
 
 // ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
 // After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at

@@ -25,6 +25,11 @@
 // never NaN), so `-0.0` stays `-0.0` there. min_p (HF MinPLogitsWarper after top-k / top-p): a candidate stays iff
 // w_i = expf(s_i - s_0) >= min_p; in the whole-vocabulary walk a weight below min_p counts as 0. The finishing thread
 // also counts its pick in c. The logits themselves are never modified (the log-probability record reads them).
+//
+// Token guide (woq_host.h GuideState: a dense uint16 table next[n_states][vocab] and a state, both on the device). With
+// one installed the pre-pass is score_adjust_guided_kernel: the four steps above, then step 5, `s = -inf` where the
+// state's row holds 0xFFFF. After the sampling launch a one-thread launch (guide_advance_kernel) moves the state to
+// row[token]. Pointer and state are read from the struct: another guide, or a reset, needs no new capture.
 #include <algorithm>
 #include <vector>
 
@@ -399,6 +404,47 @@ __global__ __launch_bounds__(ADJUST_THREADS) void score_adjust_kernel(
   adj[i] = s;
 }
 
+// The twin of score_adjust_kernel with a token guide installed: steps 1-4 word for word (kept as a twin so that the
+// kernel above stays the one it is), then step 5, the ban of the guide's current row. The table pointer and the state
+// come from the device struct, never from the launch: another guide or a reset keeps a captured graph valid.
+__global__ __launch_bounds__(ADJUST_THREADS) void score_adjust_guided_kernel(
+    const float* __restrict__ logits, int vocab, const uint32_t* __restrict__ seen, const uint32_t* __restrict__ counts,
+    const float* __restrict__ bias, const woq_sampler_config* __restrict__ cfgp,
+    const woq_sampler_controls* __restrict__ ctlp, const GuideState* __restrict__ guide, float* __restrict__ adj) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * ADJUST_THREADS + threadIdx.x;
+  if (i >= vocab) return;
+  const float pen = cfgp->repetition_penalty, pres = ctlp->presence_penalty, freq = ctlp->frequency_penalty;
+  const uint16_t* row = guide->table + (size_t)guide->state * (size_t)vocab;  // 64-bit: 65535 states x 128256 ids
+  float s = logits[i];
+  const float b = bias[i];
+  if (b == b) s = s + b;  // NaN = no entry
+  if (pen != 1.0f && ((seen[i >> 5] >> (i & 31)) & 1u)) s = s < 0.f ? s * pen : s / pen;
+  const uint32_t c = counts[i];
+  if (c > 0u) {
+    const float step = freq * (float)c;
+    s = s - step;
+    s = s - pres;
+  }
+  if (row[i] == GUIDE_BANNED) s = -INFINITY;  // last: a positive penalty cannot lift -inf, so the order does not matter
+  adj[i] = s;
+}
+
+// after the pick: the guide's state follows the picked id. One thread; the sampler's token is always inside [0, vocab).
+// A banned pick (only a state with every id banned, or a table that names a state it does not have, gets here) leaves
+// the state where it is and raises status bit 4.
+__global__ void guide_advance_kernel(GuideState* __restrict__ guide, int vocab, const int32_t* __restrict__ token,
+                                     int* __restrict__ status) {
+  const int32_t st = guide->state;
+  const uint16_t nxt = guide->table[(size_t)st * (size_t)vocab + (size_t)token[0]];
+  if (nxt != GUIDE_BANNED && (int32_t)nxt < guide->n_states)
+    guide->state = (int32_t)nxt;
+  else if (status != nullptr)
+    atomicOr(status, 16);
+}
+
+__global__ void guide_state_store_kernel(GuideState* __restrict__ guide, int32_t state) { guide->state = state; }
+
 __global__ void sampler_counts_kernel(uint32_t* __restrict__ counts, int vocab, const int32_t* __restrict__ tokens, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -433,6 +479,32 @@ void launch_sample_controls(const float* logits, int vocab, uint32_t* seen, uint
                      logits, vocab, (const uint32_t*)seen, (const uint32_t*)counts, bias, cfg_dev, ctl_dev, adj);
   hipLaunchKernelGGL(sample_kernel<true>, dim3(1), dim3(SAMPLE_THREADS), 0, st, (const float*)adj, vocab, seen, cfg_dev,
                      u_dev, token, pos_advance, pos_fixed, log, philox_out, status, ctl_dev, counts, kept_out);
+}
+
+void launch_sample_guided(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
+                          const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev,
+                          const GuideState* guide_dev, float* adj, const float* u_dev, int32_t* token,
+                          int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out, int* status,
+                          hipStream_t st, uint32_t* kept_out) {
+  hipLaunchKernelGGL(score_adjust_guided_kernel, dim3((vocab + ADJUST_THREADS - 1) / ADJUST_THREADS), dim3(ADJUST_THREADS),
+                     0, st, logits, vocab, (const uint32_t*)seen, (const uint32_t*)counts, bias, cfg_dev, ctl_dev, guide_dev,
+                     adj);
+  hipLaunchKernelGGL(sample_kernel<true>, dim3(1), dim3(SAMPLE_THREADS), 0, st, (const float*)adj, vocab, seen, cfg_dev,
+                     u_dev, token, pos_advance, pos_fixed, log, philox_out, status, ctl_dev, counts, kept_out);
+}
+
+void launch_guide_advance(GuideState* guide_dev, int vocab, const int32_t* token, int* status, hipStream_t st) {
+  hipLaunchKernelGGL(guide_advance_kernel, dim3(1), dim3(1), 0, st, guide_dev, vocab, token, status);
+}
+
+void launch_guide_state_store(GuideState* guide_dev, int32_t state, hipStream_t st) {
+  hipLaunchKernelGGL(guide_state_store_kernel, dim3(1), dim3(1), 0, st, guide_dev, state);
+}
+
+const char* guide_problem(int n_states, int start_state) {
+  if (n_states < 1 || n_states > 65535) return "QBits: a token guide has 1 to 65535 states";
+  if (start_state < 0 || start_state >= n_states) return "QBits: the token guide's start state is outside its table";
+  return nullptr;
 }
 
 void launch_sampler_counts(uint32_t* counts, int vocab, const int32_t* tokens, int n, hipStream_t st) {
@@ -490,6 +562,42 @@ const char* sampler_controls_problem(const woq_sampler_controls& c, const woq_sa
   return nullptr;
 }
 
+// what a probe of the controls' tail needs on the device, one allocation on `st` (the caller frees `buf` on `st`):
+// [config 32][controls 32][guide state 32][bias table vocab * 4][ids n * 4][values n * 4]
+struct ProbeControls {
+  char* buf;
+  woq_sampler_config* cfg;
+  woq_sampler_controls* ctl;
+  GuideState* guide;  // not written here
+  float* bias;
+};
+static int probe_controls_setup(const woq_sampler_config& cfg, const woq_sampler_controls& ctl, int vocab,
+                                const int32_t* bias_ids_host, const float* bias_vals_host, hipStream_t st,
+                                ProbeControls* out) {
+  WOQ_TRY
+  const int n = ctl.n_bias;
+  char* buf = nullptr;
+  const size_t table = 96, ids_at = table + (size_t)vocab * 4, vals_at = ids_at + (size_t)n * 4;
+  WOQ_HIP(hipMallocAsync((void**)&buf, vals_at + (size_t)n * 4 + 4, st));
+  if (n > 0) {  // the host arrays may go away when the probe returns: copies that have completed by then
+    hipError_t err = hipMemcpyAsync(buf + ids_at, bias_ids_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipMemcpyAsync(buf + vals_at, bias_vals_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) {
+      hipFreeAsync(buf, st);
+      return fail(std::string("QBits: HIP error '") + hipGetErrorString(err) + "' copying the logit_bias entries");
+    }
+  }
+  *out = {buf, (woq_sampler_config*)buf, (woq_sampler_controls*)(buf + 32), (GuideState*)(buf + 64), (float*)(buf + table)};
+  launch_sampler_config_store(cfg, out->cfg, st);
+  launch_sampler_controls_store(ctl, out->ctl, st);
+  if (launch_sampler_bias_store(out->bias, vocab, (const int32_t*)(buf + ids_at), (const float*)(buf + vals_at), n, st) != 0) {
+    hipFreeAsync(buf, st);
+    return 1;
+  }
+  WOQ_END
+}
+
 }  // namespace woq
 
 extern "C" {
@@ -524,30 +632,46 @@ WOQ_API int woq_probe_sample_controls(const float* logits, int vocab, uint32_t* 
   if (why == nullptr) why = woq::sampler_controls_problem(*ctl, *cfg, vocab, bias_ids_host, bias_vals_host);
   if (why) return woq::fail(why);
   const hipStream_t st = (hipStream_t)stream;
-  const int n = ctl->n_bias;
-  char* buf = nullptr;  // [config 32][controls 32][bias table vocab * 4][ids n * 4][values n * 4]
-  const size_t table = 64, ids_at = table + (size_t)vocab * 4, vals_at = ids_at + (size_t)n * 4;
-  WOQ_HIP(hipMallocAsync((void**)&buf, vals_at + (size_t)n * 4 + 4, st));
-  if (n > 0) {  // the host arrays may go away when this returns: copies that have completed by then
-    hipError_t err = hipMemcpyAsync(buf + ids_at, bias_ids_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(buf + vals_at, bias_vals_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) {
-      hipFreeAsync(buf, st);
-      return woq::fail(std::string("QBits: HIP error '") + hipGetErrorString(err) + "' copying the logit_bias entries");
-    }
-  }
-  woq_sampler_config* cfg_dev = (woq_sampler_config*)buf;
-  woq_sampler_controls* ctl_dev = (woq_sampler_controls*)(buf + 32);
-  woq::launch_sampler_config_store(*cfg, cfg_dev, st);
-  woq::launch_sampler_controls_store(*ctl, ctl_dev, st);
-  int rc = woq::launch_sampler_bias_store((float*)(buf + table), vocab, (const int32_t*)(buf + ids_at),
-                                          (const float*)(buf + vals_at), n, st);
-  if (rc == 0)
-    woq::launch_sample_controls(logits, vocab, seen, counts, (const float*)(buf + table), cfg_dev, ctl_dev, adjusted_out,
-                                u_or_null, token_out, nullptr, pos_dev, nullptr, nullptr, status, st, kept_out);
-  WOQ_HIP(hipFreeAsync(buf, st));
+  woq::ProbeControls pc;
+  int rc = woq::probe_controls_setup(*cfg, *ctl, vocab, bias_ids_host, bias_vals_host, st, &pc);
   if (rc) return rc;
+  woq::launch_sample_controls(logits, vocab, seen, counts, pc.bias, pc.cfg, pc.ctl, adjusted_out, u_or_null, token_out,
+                              nullptr, pos_dev, nullptr, nullptr, status, st, kept_out);
+  WOQ_HIP(hipFreeAsync(pc.buf, st));
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_guide(const float* logits, int vocab, uint32_t* seen, uint32_t* counts,
+                            const woq_sampler_config* cfg, const woq_sampler_controls* ctl,
+                            const int32_t* bias_ids_host, const float* bias_vals_host, const uint16_t* table_dev,
+                            int n_states, int state, int advance_state, const float* u_or_null, const int32_t* pos_dev,
+                            int32_t* token_out, float* adjusted_out, int32_t* state_out, int* status, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(logits && seen && counts && cfg && ctl && table_dev && pos_dev && token_out && adjusted_out && state_out &&
+                vocab >= 1,
+            "QBits: bad guide probe arguments");
+  const char* why = woq::sampler_config_problem(*cfg);
+  if (why == nullptr) why = woq::sampler_controls_problem(*ctl, *cfg, vocab, bias_ids_host, bias_vals_host);
+  if (why == nullptr) why = woq::guide_problem(n_states, state);
+  if (why == nullptr && advance_state >= 0) why = woq::guide_problem(n_states, advance_state);
+  if (why) return woq::fail(why);
+  const hipStream_t st = (hipStream_t)stream;
+  woq::ProbeControls pc;
+  int rc = woq::probe_controls_setup(*cfg, *ctl, vocab, bias_ids_host, bias_vals_host, st, &pc);
+  if (rc) return rc;
+  const woq::GuideState g = {table_dev, n_states, state};
+  hipError_t err = hipMemcpyAsync(pc.guide, &g, sizeof(g), hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);  // `g` goes away when this returns
+  if (err == hipSuccess) {
+    woq::launch_sample_guided(logits, vocab, seen, counts, pc.bias, pc.cfg, pc.ctl, pc.guide, adjusted_out, u_or_null,
+                              token_out, nullptr, pos_dev, nullptr, nullptr, status, st);
+    if (advance_state >= 0) woq::launch_guide_state_store(pc.guide, advance_state, st);
+    woq::launch_guide_advance(pc.guide, vocab, token_out, status, st);
+    err = hipMemcpyAsync(state_out, &pc.guide->state, 4, hipMemcpyDeviceToDevice, st);
+  }
+  hipFreeAsync(pc.buf, st);
+  WOQ_HIP(err);
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }

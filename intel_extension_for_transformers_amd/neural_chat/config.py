@@ -27,6 +27,10 @@ class GenerationConfig:
     min_p: float = 0.0              # sampling keeps tokens at least min_p times as likely as the likeliest
     logit_bias: Dict[int, float] = None  # token id -> value added to its logit ahead of the penalties (-inf = a ban)
     seed: int = None                # a sampled request with a seed is reproducible (None: torch's CPU generator)
+    # structured output (vLLM's names): the generated text is one of the strings / fully matches the pattern. A token
+    # automaton the engine follows on the device (runtime.guide.TokenGuide); one of the two at most
+    guided_choice: List[str] = None
+    guided_regex: str = None
     logprobs: int = None  # 0..20: fill BaseModel.last_logprobs with every emitted token's log-probability + alternatives
 
 

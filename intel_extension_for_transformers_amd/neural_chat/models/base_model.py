@@ -129,14 +129,21 @@ class BaseModel:
         self.last_logprobs = []  # one dict per emitted token when config.logprobs is set (_note_logprobs)
         # one sequence, one beam: the fused engine — greedy chains on the device; sampling (the reference's default:
         # do_sample, temperature, top_k, top_p) and the repetition penalty pick the next token with the device sampler
-        engine_ok = config.num_beams == 1 and (config.num_return_sequences or 1) == 1 and not config.bad_words_ids \
-            and not config.force_words_ids
+        # (bad_words_ids, guided_choice and guided_regex ride the engine too: a token guide its sampler follows)
+        engine_ok = config.num_beams == 1 and (config.num_return_sequences or 1) == 1 and not config.force_words_ids
+        guide = self.request_guide(config)
+        if guide is not None and self.engine is not None and not self.engine.native_sampler_supports(guide=guide):
+            engine_ok = False
+        if guide is None and config.bad_words_ids:  # words the guide's builder does not take: Hugging Face's loop
+            engine_ok = False
 
         def pieces():
             if engine_ok and self.engine is not None and n_in + config.max_new_tokens <= self.engine.cfg.max_ctx:
                 yield from self._engine_stream(ids[0].tolist(), config, n_out)
             elif getattr(config, "logprobs", None) is not None:
                 raise RuntimeError("QBits: logprobs need the fused engine")
+            elif getattr(config, "guided_choice", None) or getattr(config, "guided_regex", None):
+                raise RuntimeError("QBits: guided_choice / guided_regex need the fused engine")
             else:
                 yield from self._hf_stream(ids, config, n_out)
 
@@ -191,10 +198,50 @@ class BaseModel:
                 yield text[len(shown):]
                 shown = text
 
-    @staticmethod
-    def _sampler_controls(config):
+    def request_guide(self, config):
+        """The TokenGuide of a request, or None: `guided_choice` / `guided_regex` over this tokenizer's bytes
+        (ValueError with the builder's message for a pattern it does not take, for both at once and for a model without
+        an EOS token), else `bad_words_ids` as Hugging Face's NoBadWordsLogitsProcessor. Built once per tokenizer and
+        pattern."""
+        from ...runtime.guide import TokenGuide, token_bytes
+
+        choice, regex = getattr(config, "guided_choice", None), getattr(config, "guided_regex", None)
+        bad = getattr(config, "bad_words_ids", None)
+        if choice is not None and regex is not None:
+            raise ValueError("guided_choice and guided_regex cannot be used together")
+        if choice is None and regex is None and not bad:
+            return None
+        if self.engine is None:
+            return None  # (_stream says what needs the engine; bad_words_ids stay with Hugging Face's loop)
+        vocab = int(self.engine.cfg.vocab)
+        cache = self.__dict__.setdefault("_guide_cache", {})
+        if choice is None and regex is None:
+            key = ("bad_words", tuple(tuple(int(t) for t in w) for w in bad))
+            if key not in cache:
+                try:
+                    cache[key] = TokenGuide.from_bad_words(bad, vocab)
+                except ValueError:
+                    cache[key] = None  # what the builder does not take keeps Hugging Face's loop
+            return cache[key]
+        key = ("choice", tuple(choice)) if choice is not None else ("regex", regex)
+        if key not in cache:
+            tok = self.tokenizer
+            if tok.eos_token_id is None:
+                raise ValueError("guided decoding needs a tokenizer with an EOS token (the guide ends the text with it)")
+            if "bytes" not in cache:
+                pieces = token_bytes(tok)
+                cache["bytes"] = (pieces + [b""] * vocab)[:vocab]  # the model's head may be padded past the tokenizer
+            if choice is not None and (not choice or not all(isinstance(c, str) and c for c in choice)):
+                raise ValueError("guided_choice is a non-empty list of non-empty strings")
+            while len(cache) > 64:  # a bound on what a server keeps
+                cache.pop(next(k for k in cache if k != "bytes"))
+            cache[key] = (TokenGuide.from_choices(choice, cache["bytes"], [tok.eos_token_id]) if choice is not None
+                          else TokenGuide.from_regex(regex, cache["bytes"], [tok.eos_token_id]))
+        return cache[key]
+
+    def _sampler_controls(self, config):
         """the request's sampling controls as `iter_sampled_auto` keywords (neutral values where the config has none)"""
-        return dict(presence_penalty=getattr(config, "presence_penalty", 0.0) or 0.0,
+        return dict(guide=self.request_guide(config), presence_penalty=getattr(config, "presence_penalty", 0.0) or 0.0,
                     frequency_penalty=getattr(config, "frequency_penalty", 0.0) or 0.0,
                     min_p=(getattr(config, "min_p", 0.0) or 0.0) if config.do_sample else 0.0,  # a warper: sampling only
                     logit_bias=dict(getattr(config, "logit_bias", None) or {}), seed=getattr(config, "seed", None))
@@ -205,7 +252,7 @@ class BaseModel:
         ctl = self._sampler_controls(config)
         # a penalty or a bias with temperature 0 is a greedy request over the penalised scores: the sampler's argmax
         if config.do_sample or (config.repetition_penalty or 1.0) != 1.0 or ctl["presence_penalty"] \
-                or ctl["frequency_penalty"] or ctl["logit_bias"]:
+                or ctl["frequency_penalty"] or ctl["logit_bias"] or ctl["guide"] is not None:
             yield from self._engine_stream_sampled(ids, config, n_out)
             return
         if getattr(config, "logprobs", None) is not None:  # the same greedy chain, with the step's records read back

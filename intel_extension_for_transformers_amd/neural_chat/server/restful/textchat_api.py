@@ -42,6 +42,8 @@ class ChatCompletionRequest(_Wire):
     logit_bias: Optional[Dict[str, float]] = None  # token-id strings -> [-100, 100], as OpenAI sends them
     seed: Optional[int] = None
     min_p: Optional[float] = None
+    guided_choice: Optional[List[str]] = None  # vLLM's structured output: the text is one of these strings
+    guided_regex: Optional[str] = None         # ... or fully matches this pattern (runtime/guide.py from_regex)
     user: Optional[str] = None
     logprobs: Optional[bool] = False
     top_logprobs: Optional[int] = None
@@ -64,6 +66,8 @@ class CompletionRequest(_Wire):
     logit_bias: Optional[Dict[str, float]] = None  # token-id strings -> [-100, 100], as OpenAI sends them
     seed: Optional[int] = None
     min_p: Optional[float] = None
+    guided_choice: Optional[List[str]] = None  # vLLM's structured output: the text is one of these strings
+    guided_regex: Optional[str] = None         # ... or fully matches this pattern (runtime/guide.py from_regex)
     user: Optional[str] = None
     logprobs: Optional[int] = None
     prompt_logprobs: Optional[int] = None  # 0..20: score the PROMPT's tokens (choices[i].prompt_logprobs)
@@ -114,6 +118,27 @@ def _check_sampler_controls(req):
     return None
 
 
+def _check_guided(req):
+    """guided_choice / guided_regex: one of the two, and a pattern the guide's builder takes (its message otherwise)."""
+    if req.guided_choice is None and req.guided_regex is None:
+        return None
+    if req.guided_choice is not None and req.guided_regex is not None:
+        return "guided_choice and guided_regex cannot be used together"
+    if req.guided_choice is not None and (not req.guided_choice or not all(req.guided_choice)):
+        return "guided_choice is a non-empty list of non-empty strings"
+    try:
+        if req.guided_regex is not None:
+            from ....runtime.guide import check_regex
+
+            check_regex(req.guided_regex)
+        build = getattr(router.get_chatbot(), "request_guide", None)
+        if build is not None:  # over the model's own vocabulary (kept per pattern: the request reuses it)
+            build(GenerationConfig(guided_choice=req.guided_choice, guided_regex=req.guided_regex))
+    except ValueError as e:
+        return "%s - '%s'" % (e, "guided_regex" if req.guided_regex is not None else "guided_choice")
+    return None
+
+
 def _check_ranges(req):
     """Parameter ranges of textchat_api.py:56-102, same messages."""
     if req.max_tokens is not None and req.max_tokens <= 0:
@@ -133,7 +158,7 @@ def _check_ranges(req):
         return "%s is outside [0, 1] - 'top_p'" % req.top_p
     if req.top_k is not None and -1 < req.top_k < 1:
         return "%s is out of Range. Either set top_k to -1 or >=1." % req.top_k
-    return _check_sampler_controls(req) or _check_logprobs(req)
+    return _check_sampler_controls(req) or _check_guided(req) or _check_logprobs(req)
 
 
 def _wanted_logprobs(req):
@@ -245,7 +270,8 @@ class TextChatAPIRouter(APIRouter):
                                 max_new_tokens=req.max_tokens or default_max_tokens, do_sample=not greedy,
                                 task="chat", presence_penalty=req.presence_penalty or 0.0,
                                 frequency_penalty=req.frequency_penalty or 0.0, min_p=req.min_p or 0.0,
-                                logit_bias=bias or None, seed=req.seed)
+                                logit_bias=bias or None, seed=req.seed, guided_choice=req.guided_choice or None,
+                                guided_regex=req.guided_regex)
 
     @staticmethod
     def _stops(req, conv=None):

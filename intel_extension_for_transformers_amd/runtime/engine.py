@@ -10,6 +10,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from .. import _lib as L
@@ -77,6 +78,10 @@ class WoqDecoderEngine:
         self.controls_installed = False    # ... with logit bias / presence / frequency penalty / min_p beside it
         self.native_sampled_requests = 0   # requests that ran with it (iter_generate)
         self.logprobs_on = False           # log-probability record after every chaining pick (set_logprobs)
+        self.guide_installed = False       # token guide in the chaining tail (set_guide / clear_guide)
+        self._guide = None                 # ... the TokenGuide, its prefix and whether set_guide installed the sampler
+        self._guide_prefix = ()
+        self._guide_owns_sampler = False
         # hipGraph capture is not allowed on the legacy null stream torch uses by default
         self._stream = torch.cuda.Stream(device=self.device)
 
@@ -420,14 +425,17 @@ class WoqDecoderEngine:
     NATIVE_TOP_K_MAX = 1024
 
     def native_sampler_supports(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0,
-                                presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None):
+                                presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None, guide=None):
         """True when `set_sampler` takes this request (the checks of csrc/woq_sample.hip `sampler_config_problem` and
         `sampler_controls_problem`): one GPU (a tensor-parallel head is vocab-sharded); a positive penalty alone;
         sampling with a positive finite temperature and 1 <= top_k <= 1024 with any top_p, or top_k = 0 with top_p = 1;
         finite presence / frequency penalties, min_p in [0, 1] (> 0 only when sampling), at most 1024 bias entries
-        inside the vocabulary, each finite or -inf. Everything else keeps `iter_sampled` + `DeviceSampler`, which
-        answers or raises as it always did."""
+        inside the vocabulary, each finite or -inf; `guide` (a TokenGuide, `set_guide`) with a table over this
+        vocabulary. Everything else keeps `iter_sampled` + `DeviceSampler`, which answers or raises as it always did
+        (it has no guide)."""
         if self.cfg.tp_size > 1 or self._comm is not None or self._allreduce_cb is not None:
+            return False
+        if guide is not None and guide.table.shape[1] != self.cfg.vocab:
             return False
         if not float(1.0 if repetition_penalty is None else repetition_penalty) > 0.0:
             return False
@@ -461,6 +469,7 @@ class WoqDecoderEngine:
             raise ValueError("`temperature` has to be a strictly positive float when sampling")
         cfg = L.sampler_config(do_sample, temperature, top_k, top_p, repetition_penalty, seed)
         L.check(L.lib().woq_engine_set_sampler(self._h, ctypes.byref(cfg)))
+        self._guide_owns_sampler = False  # the caller's sampler from here on: clear_guide leaves it
         was_installed = self.sampler_installed
         if not self.sampler_installed:
             self.captured = False
@@ -482,11 +491,65 @@ class WoqDecoderEngine:
             self.controls_installed = False
 
     def clear_sampler(self):
-        """Back to the plain greedy tail (drops a graph captured with the sampler; removes the controls too)."""
+        """Back to the plain greedy tail (drops a graph captured with the sampler; removes the controls and the guide
+        too)."""
         L.check(L.lib().woq_engine_set_sampler(self._h, None))
         if self.sampler_installed:
             self.captured = False
-        self.sampler_installed = self.controls_installed = False
+        self.sampler_installed = self.controls_installed = self.guide_installed = False
+        self._guide, self._guide_prefix, self._guide_owns_sampler = None, (), False
+
+    # ---- token guide: constrained decoding (runtime/guide.py builds the tables) --------------------------------------
+    def set_guide(self, guide, prefix_ids=()):
+        """Install a `TokenGuide` (or replace the installed one): from now on every chaining step bans the ids its
+        state's row bans before the pick and moves the state on the pick, on the device. Installs a greedy sampler when
+        none is installed (`clear_guide` removes that one again). Installing drops a captured graph; replacing a guide
+        by another, and `guide_reset`, do not (the kernels read table and state from device memory). The state starts
+        at `guide.walk(prefix_ids)`; `iter_generate` starts every request at the guide's state after its prompt
+        (`guide.prompt_state`) followed by `prefix_ids`."""
+        if guide.table.shape[1] != self.cfg.vocab:
+            raise RuntimeError("QBits: the guide's table is over %d ids, the engine's vocabulary has %d"
+                               % (guide.table.shape[1], self.cfg.vocab))
+        prefix = tuple(int(t) for t in prefix_ids)
+        state = guide.walk(prefix)
+        owns = not self.sampler_installed
+        if owns:
+            self.set_sampler()
+        table = torch.from_numpy(guide.table.view(np.int16)).to(self.device)
+        if L.lib().woq_engine_set_guide(self._h, table.data_ptr(), guide.n_states, state) != 0:  # (synchronises)
+            why = L.lib().woq_last_error().decode()
+            if owns:
+                self.clear_sampler()
+            raise RuntimeError(why)
+        if not self.guide_installed:
+            self.captured = False
+        self.guide_installed = True
+        self._guide, self._guide_prefix = guide, prefix
+        self._guide_owns_sampler = owns or self._guide_owns_sampler
+
+    def clear_guide(self):
+        """Remove the guide (drops a graph captured with it), and the greedy sampler `set_guide` installed for it."""
+        if self._guide_owns_sampler:
+            self.clear_sampler()
+            return
+        L.check(L.lib().woq_engine_set_guide(self._h, None, 0, 0))
+        if self.guide_installed:
+            self.captured = False
+        self.guide_installed = False
+        self._guide, self._guide_prefix = None, ()
+
+    def guide_reset(self, state=None):
+        """The guide's state <- `state` (default: after `prefix_ids`), stream-ordered; a captured graph stays valid."""
+        if state is None:
+            state = self._guide.walk(self._guide_prefix)
+        L.check(L.lib().woq_engine_guide_reset(self._h, int(state), L.stream_ptr()))
+
+    def guide_state(self):
+        """The guide's current state (one host synchronisation)."""
+        ptr = L.lib().woq_engine_guide_state_ptr(self._h)
+        if not ptr or not self.guide_installed:
+            raise RuntimeError("QBits: no token guide installed")
+        return int(_device_view(ptr, (1,), self.device, "<i4").item())
 
     def mark_counts(self, token_ids, clear=True):
         """The frequency / presence penalties' history: count `token_ids` (after zeroing the table when `clear`). The
@@ -625,6 +688,8 @@ class WoqDecoderEngine:
             self.mark_seen(ids, clear=True)
             if self.controls_installed:
                 self.mark_counts([], clear=True)  # prompt tokens do not count: the penalties are over generated ids
+            if self.guide_installed:  # where the request's text starts: after the prompt for a bad-words guide
+                self.guide_reset(self._guide.walk(self._guide_prefix, self._guide.prompt_state(ids)))
             self.native_sampled_requests += 1
         for s0 in range(0, n, chunk):
             # the sampled tail marks its pick in the history, so with a sampler only the last chunk may end on it: an
@@ -881,14 +946,15 @@ def request_seed():
 
 def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chunk=2048, do_sample=False,
                       temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, logprobs=None, presence_penalty=0.0,
-                      frequency_penalty=0.0, min_p=0.0, logit_bias=None, seed=None):
+                      frequency_penalty=0.0, min_p=0.0, logit_bias=None, seed=None, guide=None):
     """A sampling / repetition-penalty request: on the native sampler (chained bursts, graph replays) when
     `native_sampler_supports` says so, else `iter_sampled` with a `DeviceSampler`. The sampler is removed after the
     request, so the next greedy request runs the untouched greedy path: in a `finally` of this generator, which runs when
     the stream is exhausted, closed or collected — a consumer that stops early and keeps the generator alive should
     `close()` it. Installing and removing each drop the captured graphs, so a sampled request and the greedy request
     after it each pay one capture. `seed` = None: `request_seed()`; a given seed makes the request reproducible (on the
-    torch sampler it seeds a device generator of the request's own)."""
+    torch sampler it seeds a device generator of the request's own). `guide` = a TokenGuide the request follows
+    (`set_guide`); it runs on the native sampler only, so a request it cannot take raises."""
     pres, freq, min_p, bias = _controls(presence_penalty, frequency_penalty, min_p, logit_bias)
     opts = dict(do_sample=bool(do_sample), temperature=1.0 if temperature is None else temperature, top_k=top_k or 0,
                 top_p=1.0 if top_p is None else top_p,
@@ -896,6 +962,9 @@ def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chun
                 presence_penalty=pres, frequency_penalty=freq, min_p=min_p, logit_bias=bias)
     if opts["do_sample"] and float(opts["temperature"]) <= 0:
         raise ValueError("`temperature` has to be a strictly positive float when sampling")
+    if guide is not None and not engine.native_sampler_supports(guide=guide, **opts):
+        raise RuntimeError("QBits: a token guide runs on the native sampler, which does not take this request "
+                           "(tensor parallel, another vocabulary, or sampling options it does not cover)")
     if not engine.native_sampler_supports(**opts):
         gen = None
         if seed is not None:
@@ -906,6 +975,8 @@ def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chun
         return
     try:  # (inside: the sampler may be installed already when the controls are refused)
         engine.set_sampler(seed=request_seed() if seed is None else int(seed), **opts)
+        if guide is not None:
+            engine.set_guide(guide)
         yield from engine.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, eos=eos,
                                         logprobs=logprobs)
     finally:

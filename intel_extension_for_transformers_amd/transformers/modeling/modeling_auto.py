@@ -334,6 +334,13 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     ids = inputs if inputs is not None else kwargs.get("input_ids")
     gc = generation_config if generation_config is not None else self.generation_config
     opt = lambda k, d=None: kwargs[k] if k in kwargs else getattr(gc, k, d)  # noqa: E731
+    # constrained decoding: `guide=` (a runtime.guide.TokenGuide; this keyword is the engine's, HF has none) and
+    # `bad_words_ids` (built into a guide below) make the engine's sampler follow a token automaton on the device
+    guide = kwargs.pop("guide", None)
+    bad_words = opt("bad_words_ids")
+    if guide is not None and bad_words:
+        raise ValueError("`guide` together with `bad_words_ids` is not supported (it would need the product of the two "
+                         "automata)")
     # sampling (temperature / top-k / top-p) and the repetition penalty — the reference's NeuralChat defaults
     # (neural_chat/config.py:400-409) — ride the engine too, the next token chosen on the device (runtime.engine.
     # DeviceSampler: HF's processors / warpers in HF's order); any other logits processing keeps HF's loop
@@ -342,7 +349,8 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     bias = _single_token_bias(opt("sequence_bias"), opt("suppress_tokens"), int(getattr(self.config, "vocab_size", 0) or 0))
     min_p = (opt("min_p") or 0.0) if opt("do_sample", False) else 0.0  # a warper: HF applies it only when sampling
     # (bias None: an entry the engine cannot take — `sampled` then makes `plain_sampling` decide, and it says HF's loop)
-    sampled = bool(opt("do_sample", False)) or (opt("repetition_penalty", 1.0) or 1.0) != 1.0 or bias is None or bool(bias)
+    sampled = (bool(opt("do_sample", False)) or (opt("repetition_penalty", 1.0) or 1.0) != 1.0 or bias is None or bool(bias)
+               or guide is not None or bool(bad_words))
     plain_sampling = ((opt("typical_p", 1.0) or 1.0) == 1.0 and not opt("epsilon_cutoff", 0.0) and not opt("eta_cutoff", 0.0)
                       and bias is not None and opt("penalty_alpha") is None
                       and (opt("encoder_repetition_penalty", 1.0) or 1.0) == 1.0 and not opt("renormalize_logits", False)
@@ -352,7 +360,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     simple = (torch.is_tensor(ids) and ids.dim() == 2 and ids.shape[0] == 1 and ids.shape[1] >= 1
               and (not sampled or plain_sampling) and (opt("num_beams", 1) or 1) == 1
               and (opt("num_return_sequences", 1) or 1) == 1
-              and not opt("no_repeat_ngram_size", 0) and not opt("bad_words_ids") and not opt("force_words_ids")
+              and not opt("no_repeat_ngram_size", 0) and not opt("force_words_ids")
               and not opt("min_new_tokens", 0) and not opt("min_length", 0)
               and not any(kwargs.get(k) is not None for k in ("logits_processor", "stopping_criteria",
                                                               "prefix_allowed_tokens_fn", "assistant_model",
@@ -362,6 +370,9 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     if simple and mask is not None and not bool(torch.all(mask == 1)):
         simple = False
     if not simple or getattr(self, "_woq_engine_off", False):
+        if guide is not None:
+            raise RuntimeError("QBits: `guide=` needs a request the native engine covers (one sequence, one beam, no "
+                               "other logits processing); Hugging Face's loop has no token guide")
         return hf_generate(inputs, generation_config=generation_config, **kwargs) if inputs is not None else \
             hf_generate(generation_config=generation_config, **kwargs)
     n_in = int(ids.shape[1])
@@ -374,15 +385,32 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
 
         want = n_in + max_new
         ctx = int(min(max(want, 512), getattr(self.config, "max_position_embeddings", want) or want))
+        no_guide = "QBits: `guide=` needs the native engine, which cannot serve this request (%s)"
         if ctx < want:
+            if guide is not None:
+                raise RuntimeError(no_guide % "longer than the model's positions")
             return hf_generate(inputs, generation_config=generation_config, **kwargs)
         try:
             eng = optimize_transformers(self, max_ctx=1 << (ctx - 1).bit_length())
         except RuntimeError:  # not a Llama-class int4 model: the module path serves it
             self._woq_engine_off = True
+            if guide is not None:
+                raise RuntimeError(no_guide % "not a model the engine takes")
             return hf_generate(inputs, generation_config=generation_config, **kwargs)
     if max_new < 1:
         return (ids, []) if want_latency else ids
+    if bad_words:  # HF's NoBadWordsLogitsProcessor as a guide; what the engine cannot take keeps HF's loop
+        from ...runtime.guide import TokenGuide
+
+        try:
+            guide = TokenGuide.from_bad_words(bad_words, eng.cfg.vocab)
+        except (TypeError, ValueError):
+            guide = None
+        if guide is None or not eng.native_sampler_supports(
+                do_sample=opt("do_sample", False), temperature=opt("temperature", 1.0), top_k=opt("top_k", 0),
+                top_p=opt("top_p", 1.0), repetition_penalty=opt("repetition_penalty", 1.0), min_p=min_p, logit_bias=bias,
+                guide=guide):
+            return hf_generate(inputs, generation_config=generation_config, **kwargs)
     eos = opt("eos_token_id")
     eos = set() if eos is None else set(eos if isinstance(eos, (list, tuple)) else [eos])
     streamer = kwargs.get("streamer")
@@ -412,7 +440,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
                                      do_sample=opt("do_sample", False), temperature=opt("temperature", 1.0),
                                      top_k=opt("top_k", 0), top_p=opt("top_p", 1.0),
                                      repetition_penalty=opt("repetition_penalty", 1.0), min_p=min_p,
-                                     logit_bias=bias):
+                                     logit_bias=bias, guide=guide):
             out += new
             on_tokens(new)
         return out, latency

@@ -17,6 +17,13 @@ Path `native_default_controls` is the default chat request plus `frequency_penal
 controls: one pre-pass launch more per token):
 
     python tools/sampling_rate.py --paths native_default,native_default_controls
+
+Path `native_default_guided` is the default chat request under a permissive regex guide (the guided pre-pass and the
+state's advance: two launches more per token than `native_default`); `--guide-build` times the regex builder on the
+host for the largest pattern of tests/test_guide_cpu.py at two vocabulary sizes (no GPU work):
+
+    python tools/sampling_rate.py --paths native_default,native_default_guided
+    python tools/sampling_rate.py --guide-build
 """
 import argparse
 import os
@@ -34,6 +41,28 @@ from intel_extension_for_transformers_amd.runtime.engine import (DeviceSampler, 
 DEFAULT = dict(do_sample=True, temperature=0.1, top_k=40, top_p=0.75, repetition_penalty=1.1)  # neural_chat/config.py
 PENALTY = dict(do_sample=False, repetition_penalty=1.1)
 CONTROLS = dict(DEFAULT, frequency_penalty=0.5, min_p=0.05)
+BUILD_REGEX = r'\{\"\w{1,4}\":(true|false|null)\}'  # the largest pattern of tests/test_guide_cpu.py
+
+
+def synthetic_pieces(vocab, seed=1):
+    """a vocabulary of `vocab` byte strings: the 256 single bytes, then random printable ASCII pieces of 2..8 bytes"""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    pieces = [bytes([b]) for b in range(256)]
+    pieces += [bytes(rng.integers(32, 127, rng.integers(2, 9)).tolist()) for _ in range(vocab - 256)]
+    return pieces
+
+
+def guide_build_times():
+    from intel_extension_for_transformers_amd.runtime.guide import TokenGuide
+
+    for vocab in (32000, 128256):
+        pieces = synthetic_pieces(vocab)
+        tic = time.perf_counter()
+        g = TokenGuide.from_regex(BUILD_REGEX, pieces, [2])
+        print("from_regex(%s) at vocab %d: %d states, %.2f s on the host" % (BUILD_REGEX, vocab, g.n_states,
+                                                                           time.perf_counter() - tic))
 
 
 def main():
@@ -44,7 +73,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--paths", default="native_default,torch_default,native_penalty,torch_penalty,greedy")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--guide-build", action="store_true", help="time the regex builder on the host and exit")
     a = ap.parse_args()
+    if a.guide_build:
+        guide_build_times()
+        return
     geom = dict(hidden=4096, inter=11008, heads=32, kv_heads=32, head_dim=128, layers=a.layers, vocab=32000)
     eng = WoqDecoderEngine(max_ctx=512, **geom)
     synth_llama_weights(eng, **geom)
@@ -56,7 +89,21 @@ def main():
     def torch_path(kw):
         return lambda: generate_sampled(eng, prompt, a.new, DeviceSampler(**kw))
 
-    paths = {"native_default": native(DEFAULT), "torch_default": torch_path(DEFAULT), "native_penalty": native(PENALTY),
+    def guided():
+        """the default request under a guide that permits every printable text (and EOS anywhere)"""
+        from intel_extension_for_transformers_amd.runtime.guide import TokenGuide
+
+        if "guide" not in cache:
+            cache["guide"] = TokenGuide.from_regex(r"[ -~]*", synthetic_pieces(geom["vocab"]), [2])
+        eng.set_sampler(seed=1234, **DEFAULT)
+        eng.set_guide(cache["guide"])
+        try:
+            return sum(eng.iter_generate(prompt, a.new), [])
+        finally:
+            eng.clear_sampler()
+
+    cache = {}
+    paths = {"native_default_guided": guided, "native_default": native(DEFAULT), "torch_default": torch_path(DEFAULT), "native_penalty": native(PENALTY),
              "native_default_controls": native(CONTROLS),
              "torch_penalty": torch_path(PENALTY), "greedy": lambda: eng.generate(prompt, a.new),
              "greedy_logprobs": lambda: eng.generate(prompt, a.new, logprobs=20)[0],
