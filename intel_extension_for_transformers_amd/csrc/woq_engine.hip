@@ -13,6 +13,7 @@
 // Residual stream and the GEMV I/O stay fp32 (the reference up-casts every activation to fp32 at the
 // qbits boundary, modules.py:152-154); the KV cache is fp16/bf16.
 #include <algorithm>
+#include <tuple>
 #include <vector>
 
 #include "woq_device.h"
@@ -28,6 +29,11 @@ constexpr int kProjEpi[P_COUNT] = {0, 0, 1, 0};
 // nibble plane's (include/woq_blob.h woq_fp8_headers) and fp8_lo the LO plane's tile data; null for integer / table layers
 struct EngineProj { const void* blob; woq_blob_header hdr; const void* fp8_lo; };
 struct EngineLayer { EngineProj p[P_COUNT]; const float* ln1; const float* ln2; };
+// the pick after an lm_head (woq_engine::tail decides, engine_tail issues); pairs: that lm_head emits (max, index) pairs
+enum TailPick { PICK_NONE, PICK_SAMPLED, PICK_ARGMAX_FULL, PICK_ARGMAX_PAIRS, PICK_ARGMAX_EMBED, PICK_TP_GREEDY };
+struct Tail { TailPick pick; bool pairs; };
+// (sampler, controls, guide, logprobs): what a captured graph holds of the tail; a setter that changes it drops the graphs
+using TailKey = std::tuple<bool, bool, bool, bool>;
 
 struct woq_engine {
   woq_engine_config cfg;
@@ -118,14 +124,14 @@ struct woq_engine {
   void* pf_ws = nullptr;        // GEMM pack workspace
   float* pf_last = nullptr;     // fp32 [max_batch][hidden]
   float* pf_logits = nullptr;   // fp32 [max_batch][vocab]
-  // sampled token tail (woq_sample.hip): with `sampler_on` a chaining step picks its token with launch_sample instead of
-  // the argmax launches. The parameters live in `samp_cfg` (device), the repetition penalty's history in `samp_seen`
+  // sampled token tail (woq_sample.hip): with `sampler_on` a chaining step picks its token with launch_sample_tail instead
+  // of the argmax launches. The parameters live in `samp_cfg` (device), the repetition penalty's history in `samp_seen`
   bool sampler_on = false;
   woq_sampler_config* samp_cfg = nullptr;
   uint32_t* samp_seen = nullptr;  // [(vocab + 31) / 32]
   int seen_words() const { return (cfg.vocab + 31) / 32; }
   // sampler controls (logit bias, presence / frequency penalty, min_p): with `controls_on` the tail is the pre-pass +
-  // the sampling launch over its scratch (launch_sample_controls). Allocated by the first use, [vocab] each
+  // the sampling launch over its scratch. Allocated by the first use, [vocab] each
   bool controls_on = false;
   woq_sampler_config samp_cfg_host = {};  // what samp_cfg holds (the controls' checks read do_sample)
   woq_sampler_controls samp_ctl_host = {};  // what samp_ctl holds (set_sampler re-checks min_p against do_sample)
@@ -153,6 +159,12 @@ struct woq_engine {
   // scored prompt pass (woq_score.hip): hi + lo rows, the logits of one block of 256 rows and their partials;
   // allocated by the first woq_engine_prefill_scored and held, like pf_ws
   void* score_ws = nullptr;
+  // the token tail, decided here alone: the pick after the lm_head of a step (after_prompt: of a prompt pass)
+  Tail tail(bool greedy, bool fuse_next, bool after_prompt) const;
+  woq::SampleTail sample_tail() const;  // the buffers of a sampled pick
+  TailKey tail_key() const { return TailKey{sampler_on, controls_on, guide_on, logprobs_on}; }
+  // the sampler, the guide, the record and a scored prompt read every logit: a tensor-parallel head is vocab-sharded
+  bool whole_vocab() const { return cfg.tp_size <= 1 && comm == nullptr && allreduce == nullptr; }
 };
 
 using namespace woq;
@@ -257,26 +269,27 @@ static int engine_mlp_block(woq_engine* e, int l, hipStream_t st) {
   return engine_linear_f32(e, l, P_DOWN, e->act, c.inter, e->hidden, c.hidden, nullptr, e->tp_residual(e->hidden), st);
 }
 
+// A sampler's penalty changes values after the lm_head, so its pairs are of no use; the prompt pass's lm_head emits none.
 // fuse_next: this step's greedy argmax and the NEXT step's embedding kernel as one launch (steps chained inside one
-// captured graph; one GPU, greedy) — woq_ops.hip argmax_embed_kernel
-static bool engine_can_fuse_next(const woq_engine* e, int greedy) {
-  return greedy && e->cfg.tp_size <= 1 && e->comm == nullptr && !e->sampler_on;  // sampled chains: sample -> embed
+// captured graph; one GPU) — woq_ops.hip argmax_embed_kernel. A vocab-sharded head: one (max, global index) pair per rank
+Tail woq_engine::tail(bool greedy, bool fuse_next, bool after_prompt) const {
+  if (!greedy) return {PICK_NONE, false};
+  if (sampler_on) return {PICK_SAMPLED, false};
+  if (after_prompt) return {PICK_ARGMAX_FULL, false};
+  if (fuse_next && cfg.tp_size <= 1 && comm == nullptr) return {PICK_ARGMAX_EMBED, true};
+  return {comm != nullptr && cfg.tp_size > 1 ? PICK_TP_GREEDY : PICK_ARGMAX_PAIRS, true};
 }
-// the chaining tail with a sampler installed: token <- sample(logits), tok_log[pos] = token, pos += 1
-static void engine_sample(woq_engine* e, hipStream_t st) {
-  if (e->guide_on) {  // the row of the guide's state bans ids before the pick, the state follows the pick
-    launch_sample_guided(e->logits, e->cfg.vocab, e->samp_seen, e->samp_count, e->samp_bias, e->samp_cfg, e->samp_ctl,
-                         e->guide, e->samp_adj, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr, e->fuse_status, st);
-    launch_guide_advance(e->guide, e->cfg.vocab, e->token, e->fuse_status, st);
-    return;
-  }
-  if (e->controls_on) {
-    launch_sample_controls(e->logits, e->cfg.vocab, e->samp_seen, e->samp_count, e->samp_bias, e->samp_cfg, e->samp_ctl,
-                           e->samp_adj, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr, e->fuse_status, st);
-    return;
-  }
-  launch_sample(e->logits, e->cfg.vocab, e->samp_seen, e->samp_cfg, nullptr, e->token, e->pos, nullptr, e->tok_log, nullptr,
-                e->fuse_status, st);
+static bool engine_can_fuse_next(const woq_engine* e, int greedy) {
+  return e->tail(greedy != 0, true, false).pick == PICK_ARGMAX_EMBED;  // sampled chains: sample -> embed
+}
+// the controls' memory travels with controls or a guide (which reads neutral controls when none are installed)
+SampleTail woq_engine::sample_tail() const {
+  SampleTail t;
+  t.logits = logits, t.vocab = cfg.vocab, t.seen = samp_seen, t.cfg = samp_cfg;
+  if (controls_on || guide_on) t.counts = samp_count, t.bias = samp_bias, t.ctl = samp_ctl, t.adj = samp_adj;
+  if (guide_on) t.guide = guide;
+  t.token = token, t.pos_advance = pos, t.log = tok_log, t.status = fuse_status;
+  return t;
 }
 // the record of the pick that was just launched: reads token[0], pos[0] - 1 and the logits, which the stream orders
 // before the next lm_head (also behind a fused argmax + embed launch: that one writes the residual stream, not logits)
@@ -285,29 +298,39 @@ static int engine_logprobs(woq_engine* e, hipStream_t st) {
   return launch_logprobs(e->logits, e->cfg.vocab, e->token, e->pos, e->cfg.max_ctx + 1, e->lp_ws, e->lp_chosen,
                          e->lp_top_id, e->lp_top_lp, st);
 }
+// the pick, then its record (the tensor-parallel greedy pick has none: the record needs the whole vocabulary)
+static int engine_tail(woq_engine* e, TailPick pick, hipStream_t st) {
+  const woq_engine_config& c = e->cfg;
+  const int n_pairs = (c.vocab + 15) / 16;  // of the lm_head's (max, index) pairs
+  switch (pick) {
+    case PICK_NONE: return 0;
+    case PICK_TP_GREEDY:
+      return woq_comm_launch_greedy(e->comm, e->am_val, e->am_idx, n_pairs, e->vocab_offset, e->token, e->pos, e->tok_log, st);
+    case PICK_SAMPLED: {  // token <- sample(logits), tok_log[pos] = token, pos += 1; a guide's state follows the pick
+      const SampleTail t = e->sample_tail();
+      if (const int rc = launch_sample_tail(t, st)) return rc;
+      if (t.guide != nullptr) launch_guide_advance(e->guide, t.vocab, t.token, t.status, st);
+      break;
+    }
+    case PICK_ARGMAX_FULL: launch_argmax(e->logits, c.vocab, e->token, e->pos, st); break;  // token <- argmax, pos += 1
+    case PICK_ARGMAX_PAIRS:
+      launch_argmax_pairs(e->am_val, e->am_idx, n_pairs, e->token, e->pos, e->tok_log, e->fuse_status, st);
+      break;
+    case PICK_ARGMAX_EMBED: {
+      const bool xq = e->use_xq();
+      launch_argmax_embed(e->am_val, e->am_idx, n_pairs, e->token, e->pos, e->tok_log, e->embed, e->embed_dtype, c.hidden,
+                          e->hidden, xq ? e->layers[0].ln1 : nullptr, xq ? e->xq_hidden : kNoXq,
+                          xq ? e->ssq_part : nullptr, e->step_seq, c.max_ctx, e->fuse_status, st);
+    }
+  }
+  return engine_logprobs(e, st);
+}
 static int engine_head(woq_engine* e, int greedy, hipStream_t st, bool fuse_next = false) {
   const woq_engine_config& c = e->cfg;
-  if (greedy && e->sampler_on) {  // the penalty changes values after the lm_head: its (max, index) pairs are of no use
-    launch_lm_head(e->hidden, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, e->logits, nullptr,
-                   nullptr, st);
-    engine_sample(e, st);
-    return engine_logprobs(e, st);
-  }
+  const Tail t = e->tail(greedy != 0, fuse_next, false);
   launch_lm_head(e->hidden, e->final_norm, c.rms_eps, e->lm_head, e->lm_dtype, c.hidden, c.vocab, e->logits,
-                 greedy ? e->am_val : nullptr, greedy ? e->am_idx : nullptr, st);
-  if (fuse_next) {
-    const bool xq = e->use_xq();
-    launch_argmax_embed(e->am_val, e->am_idx, (c.vocab + 15) / 16, e->token, e->pos, e->tok_log, e->embed, e->embed_dtype,
-                        c.hidden, e->hidden, xq ? e->layers[0].ln1 : nullptr, xq ? e->xq_hidden : kNoXq,
-                        xq ? e->ssq_part : nullptr, e->step_seq, c.max_ctx, e->fuse_status, st);
-    return engine_logprobs(e, st);
-  }
-  if (greedy && e->comm && c.tp_size > 1)  // vocab-sharded head: one (max, global index) pair per rank
-    return woq_comm_launch_greedy(e->comm, e->am_val, e->am_idx, (c.vocab + 15) / 16, e->vocab_offset, e->token,
-                                  e->pos, e->tok_log, st);
-  if (!greedy) return 0;
-  launch_argmax_pairs(e->am_val, e->am_idx, (c.vocab + 15) / 16, e->token, e->pos, e->tok_log, e->fuse_status, st);
-  return engine_logprobs(e, st);
+                 t.pairs ? e->am_val : nullptr, t.pairs ? e->am_idx : nullptr, st);
+  return engine_tail(e, t.pick, st);
 }
 
 // sum of the row-parallel partials over the tensor-parallel ranks, in place on the residual stream, after sub-block
@@ -451,11 +474,9 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
   WOQ_HIP(hipMemcpyAsync(e->hidden, e->pf_last, (size_t)c.hidden * 4, hipMemcpyDeviceToDevice, st));
   WOQ_HIP(hipMemcpyAsync(e->logits, e->pf_logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, st));
   WOQ_HIP(hipMemsetD32Async((hipDeviceptr_t)e->pos, start + T - 1, 1, st));
-  if (greedy && e->sampler_on)
-    engine_sample(e, st);  // token <- sample at counter start + T - 1, pos <- start + T
-  else if (greedy)
-    launch_argmax(e->logits, c.vocab, e->token, e->pos, st);  // token <- argmax, pos <- start + T
-  return greedy ? engine_logprobs(e, st) : 0;  // the first generated token's record, row start + T - 1
+  // greedy: token <- sample at counter start + T - 1 or argmax, pos <- start + T, and the first generated token's
+  // record, row start + T - 1
+  return engine_tail(e, e->tail(greedy != 0, false, true).pick, st);
 }
 
 // `reps` passes of `body(stream)` between two events on `st` (after one untimed pass): what the launches cost inside the
@@ -545,8 +566,7 @@ int woq_engine_prefill_scored(woq_engine* e, const int32_t* tokens_dev, int T, i
   WOQ_CHECK(e && e->embed && e->lm_head, "QBits: engine head not set");
   WOQ_CHECK(tokens_dev && targets_dev && T >= 1 && start_pos >= 0, "QBits: bad prefill arguments");
   WOQ_CHECK(start_pos + T <= e->cfg.max_ctx, "QBits: prefill runs past max_ctx");
-  WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
-            "QBits: a tensor-parallel engine cannot score a prompt (its lm_head is vocab-sharded)");
+  WOQ_CHECK(e->whole_vocab(), "QBits: a tensor-parallel engine cannot score a prompt (its lm_head is vocab-sharded)");
   WOQ_CHECK(e->lp_chosen != nullptr, "QBits: no log-probability log before the first woq_engine_set_logprobs(e, 1)");
   const woq_engine_config& c = e->cfg;
   if (const char* why = score_shape_problem(e->lm_head, e->lm_dtype, c.hidden, c.vocab)) return woq::fail(why);
@@ -742,6 +762,9 @@ static void engine_drop_graphs(woq_engine* e) {
   e->exec = e->exec_k = nullptr;
   e->graph = e->graph_k = nullptr;
 }
+static void engine_tail_changed(woq_engine* e, const TailKey& before) {
+  if (!(e->tail_key() == before)) engine_drop_graphs(e);
+}
 
 void woq_engine_destroy(woq_engine* e) {
   if (!e) return;
@@ -870,8 +893,9 @@ int woq_engine_uses_xq(woq_engine* e) { return e && e->use_xq() ? 1 : 0; }
 int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg) {
   WOQ_TRY
   WOQ_CHECK(e, "QBits: null engine");
+  const TailKey before = e->tail_key();
   if (cfg != nullptr) {
-    WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+    WOQ_CHECK(e->whole_vocab(),
               "QBits: the native sampler needs the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
     const char* why = sampler_config_problem(*cfg);
     if (why) return woq::fail(why);
@@ -883,10 +907,9 @@ int woq_engine_set_sampler(woq_engine* e, const woq_sampler_config* cfg) {
     WOQ_HIP(hipMemcpy(e->samp_cfg, cfg, sizeof(woq_sampler_config), hipMemcpyHostToDevice));
     e->samp_cfg_host = *cfg;
   }
-  const bool on = cfg != nullptr;
-  if (on != e->sampler_on || (!on && (e->controls_on || e->guide_on))) engine_drop_graphs(e);  // a graph holds the other tail
-  e->sampler_on = on;
-  if (!on) e->controls_on = e->guide_on = false;  // the controls and the guide live beside a sampler
+  e->sampler_on = cfg != nullptr;
+  if (!e->sampler_on) e->controls_on = e->guide_on = false;  // the controls and the guide live beside a sampler
+  engine_tail_changed(e, before);
   WOQ_END
 }
 
@@ -924,8 +947,9 @@ int woq_engine_set_sampler_controls(woq_engine* e, const woq_sampler_controls* c
                                     const float* bias_vals_host) {
   WOQ_TRY
   WOQ_CHECK(e, "QBits: null engine");
+  const TailKey before = e->tail_key();
   if (ctl != nullptr) {
-    WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+    WOQ_CHECK(e->whole_vocab(),
               "QBits: the native sampler needs the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
     WOQ_CHECK(e->sampler_on, "QBits: sampler controls need a sampler installed (woq_engine_set_sampler first)");
     const char* why = sampler_controls_problem(*ctl, e->samp_cfg_host, e->cfg.vocab, bias_ids_host, bias_vals_host);
@@ -944,21 +968,21 @@ int woq_engine_set_sampler_controls(woq_engine* e, const woq_sampler_controls* c
   } else if (e->guide_on && e->controls_on) {
     if (engine_controls_neutral(e) != 0) return 1;  // the guided tail goes on reading them
   }
-  const bool on = ctl != nullptr;
-  if (on != e->controls_on) engine_drop_graphs(e);  // a captured graph holds the other tail
-  e->controls_on = on;
+  e->controls_on = ctl != nullptr;
+  engine_tail_changed(e, before);
   WOQ_END
 }
 
 int woq_engine_set_guide(woq_engine* e, const void* table_dev, int n_states, int start_state) {
   WOQ_TRY
   WOQ_CHECK(e, "QBits: null engine");
+  const TailKey before = e->tail_key();
   if (table_dev == nullptr) {  // the table stays allocated for the next guide
-    if (e->guide_on) engine_drop_graphs(e);
     e->guide_on = false;
+    engine_tail_changed(e, before);
     return 0;
   }
-  WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+  WOQ_CHECK(e->whole_vocab(),
             "QBits: a token guide needs the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
   WOQ_CHECK(e->sampler_on, "QBits: a token guide needs a sampler installed (woq_engine_set_sampler first)");
   const char* why = guide_problem(n_states, start_state);
@@ -983,8 +1007,8 @@ int woq_engine_set_guide(woq_engine* e, const void* table_dev, int n_states, int
   WOQ_HIP(hipMemcpy(e->guide, &e->guide_host, sizeof(GuideState), hipMemcpyHostToDevice));
   WOQ_HIP(hipDeviceSynchronize());
   if (retired) hipFree(retired);  // the device struct names the new table by now
-  if (!e->guide_on) engine_drop_graphs(e);  // a captured graph holds the other tail
   e->guide_on = true;
+  engine_tail_changed(e, before);
   WOQ_END
 }
 
@@ -1027,9 +1051,9 @@ void* woq_engine_sampler_seen_ptr(woq_engine* e) { return e ? e->samp_seen : nul
 int woq_engine_set_logprobs(woq_engine* e, int on) {
   WOQ_TRY
   WOQ_CHECK(e, "QBits: null engine");
-  const bool want = on != 0;
-  if (want) {
-    WOQ_CHECK(e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+  const TailKey before = e->tail_key();
+  if (on != 0) {
+    WOQ_CHECK(e->whole_vocab(),
               "QBits: log-probabilities need the whole vocabulary on one GPU (a tensor-parallel head is vocab-sharded)");
     WOQ_CHECK(logprob_vocab_ok(e->cfg.vocab), "QBits: the log-probability record covers vocabularies of up to 418816 ids");
     if (e->lp_chosen == nullptr) {
@@ -1050,8 +1074,8 @@ int woq_engine_set_logprobs(woq_engine* e, int on) {
       e->lp_chosen = (float*)a;  // last: what woq_engine_logprob_ptr and the steps test
     }
   }
-  if (want != e->logprobs_on) engine_drop_graphs(e);  // a captured graph holds the other tail
-  e->logprobs_on = want;
+  e->logprobs_on = on != 0;
+  engine_tail_changed(e, before);
   WOQ_END
 }
 

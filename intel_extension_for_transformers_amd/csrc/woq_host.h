@@ -166,37 +166,6 @@ void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t*
                          float* ssq_out, unsigned int* step_seq, int max_ctx, int* status, hipStream_t st);
 
 // ---- woq_sample.hip: the sampled token tail -----------------------------------------------------------------------
-// next token from fp32 logits under the device-resident `cfg_dev` (repetition penalty over the `seen` bit set, then
-// argmax or temperature / top-k / top-p / draw), one launch of one workgroup. pos_advance (the engine's chain): the
-// uniform's Philox counter is *pos_advance, log[*pos_advance] = token, *pos_advance += 1; else pos_fixed is only read.
-// u_dev (nullable) overrides the Philox uniform; philox_out (nullable) receives the four Philox words; the picked
-// token's bit is set in `seen`; status |= 4 (every score NaN: token 0), 8 (more than 1024 candidates tied in).
-void launch_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg_dev, const float* u_dev,
-                   int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out,
-                   int* status, hipStream_t st);
-// seen |= bits of tokens[0..n) (ids outside [0, vocab) are ignored)
-void launch_sampler_seen(uint32_t* seen, int vocab, const int32_t* tokens, int n, hipStream_t st);
-// *dst = cfg, stream-ordered (the struct travels as a kernel argument)
-void launch_sampler_config_store(const woq_sampler_config& cfg, woq_sampler_config* dst, hipStream_t st);
-// null when the native sampler takes this combination, else the "QBits: ..." reason
-const char* sampler_config_problem(const woq_sampler_config& cfg);
-// The same choice with sampler controls: a pre-pass over the whole chip writes adj[i] = the score of id i after the logit
-// bias (dense table `bias`, NaN = no entry), the repetition penalty and the frequency / presence penalties over
-// `counts` (uint32 [vocab], times generated), then the sampling workgroup runs over `adj` (min_p from ctl_dev) and also
-// does counts[token] += 1. Two launches whose shapes depend on the vocabulary alone; `logits` is only read.
-void launch_sample_controls(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
-                            const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev, float* adj,
-                            const float* u_dev, int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed,
-                            int32_t* log, uint32_t* philox_out, int* status, hipStream_t st,
-                            uint32_t* kept_out = nullptr);  // (nullable) ids a sampled draw was over
-// counts[tokens[j]] += 1 for j in [0, n) (ids outside [0, vocab) are ignored)
-void launch_sampler_counts(uint32_t* counts, int vocab, const int32_t* tokens, int n, hipStream_t st);
-// bias[0..vocab) = NaN ("no entry"), then bias[ids_dev[j]] = vals_dev[j] for j in [0, n); stream-ordered
-int launch_sampler_bias_store(float* bias, int vocab, const int32_t* ids_dev, const float* vals_dev, int n, hipStream_t st);
-void launch_sampler_controls_store(const woq_sampler_controls& ctl, woq_sampler_controls* dst, hipStream_t st);
-// null when the controls are acceptable beside `cfg` (ids / vals: ctl.n_bias host entries), else the "QBits: ..." reason
-const char* sampler_controls_problem(const woq_sampler_controls& ctl, const woq_sampler_config& cfg, int vocab,
-                                     const int32_t* ids, const float* vals);
 // A token guide (include/woq_hip.h woq_engine_set_guide): a dense table next[n_states][vocab] of uint16, GUIDE_BANNED =
 // the id is banned in that state, anything else = the state after that id. The kernels read the table pointer and the
 // state from this device struct, so another table or another state needs no new capture.
@@ -206,14 +175,45 @@ struct GuideState {
   int32_t n_states;
   int32_t state;
 };
-// launch_sample_controls with the guide's ban as the pre-pass's last step: adj[i] = -inf where
-// table[state * vocab + i] == GUIDE_BANNED (the row offset in 64 bits). The state is only read.
-void launch_sample_guided(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
-                          const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev,
-                          const GuideState* guide_dev, float* adj, const float* u_dev, int32_t* token,
-                          int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out, int* status,
-                          hipStream_t st, uint32_t* kept_out = nullptr);
-// after the pick, one thread: state <- table[state * vocab + token[0]], or, where that is GUIDE_BANNED (or no state of
+// The device buffers of one sampled pick; which of them are set decides what launch_sample_tail runs.
+//  - `adj` null: next token from the fp32 `logits` under the device-resident `cfg` (repetition penalty over the `seen`
+//    bit set, then argmax or temperature / top-k / top-p / draw), one launch of one workgroup (sample_kernel<false>).
+//  - `adj` set (sampler controls): a pre-pass over the whole chip (score_adjust_kernel<false>) writes adj[i] = the score
+//    of id i after the logit bias (dense table `bias`, NaN = no entry), the repetition penalty and the frequency /
+//    presence penalties over `counts` (uint32 [vocab], times generated), then the sampling workgroup runs over `adj`
+//    (sample_kernel<true>: min_p from `ctl`) and also does counts[token] += 1. Two launches whose shapes depend on the
+//    vocabulary alone; `logits` is only read.
+//  - `guide` set as well: the pre-pass (score_adjust_kernel<true>) ends on adj[i] = -inf where
+//    table[state * vocab + i] == GUIDE_BANNED (the row offset in 64 bits). The state is only read.
+// pos_advance (the engine's chain): the Philox counter is *pos_advance, log[*pos_advance] = token (`log` nullable), then
+// *pos_advance += 1; else pos_fixed is only read. Sets the token's bit in `seen`; status |= 4 (every score NaN: token 0), 8
+// (more than 1024 candidates tied in).
+struct SampleTail {
+  const float* logits = nullptr; int vocab = 0; uint32_t* seen = nullptr; const woq_sampler_config* cfg = nullptr;
+  // the controls' memory, all four or none; a guide needs it
+  uint32_t* counts = nullptr; const float* bias = nullptr; const woq_sampler_controls* ctl = nullptr; float* adj = nullptr;
+  const GuideState* guide = nullptr;
+  int32_t *token = nullptr, *pos_advance = nullptr, *log = nullptr; const int32_t* pos_fixed = nullptr; int* status = nullptr;
+  // the probes' (null in the engine): u overrides the Philox uniform, philox_out receives the four Philox words,
+  // kept_out (controls) the number of ids a sampled draw was over
+  const float* u = nullptr; uint32_t *philox_out = nullptr, *kept_out = nullptr;
+};
+int launch_sample_tail(const SampleTail& t, hipStream_t st);  // non-zero (message set): the slots contradict each other
+// seen |= bits of tokens[0..n) (ids outside [0, vocab) are ignored)
+void launch_sampler_seen(uint32_t* seen, int vocab, const int32_t* tokens, int n, hipStream_t st);
+// *dst = cfg, stream-ordered (the struct travels as a kernel argument)
+void launch_sampler_config_store(const woq_sampler_config& cfg, woq_sampler_config* dst, hipStream_t st);
+// null when the native sampler takes this combination, else the "QBits: ..." reason
+const char* sampler_config_problem(const woq_sampler_config& cfg);
+// counts[tokens[j]] += 1 for j in [0, n) (ids outside [0, vocab) are ignored)
+void launch_sampler_counts(uint32_t* counts, int vocab, const int32_t* tokens, int n, hipStream_t st);
+// bias[0..vocab) = NaN ("no entry"), then bias[ids_dev[j]] = vals_dev[j] for j in [0, n); stream-ordered
+int launch_sampler_bias_store(float* bias, int vocab, const int32_t* ids_dev, const float* vals_dev, int n, hipStream_t st);
+void launch_sampler_controls_store(const woq_sampler_controls& ctl, woq_sampler_controls* dst, hipStream_t st);
+// null when the controls are acceptable beside `cfg` (ids / vals: ctl.n_bias host entries), else the "QBits: ..." reason
+const char* sampler_controls_problem(const woq_sampler_controls& ctl, const woq_sampler_config& cfg, int vocab,
+                                     const int32_t* ids, const float* vals);
+// after a guided pick, one thread: state <- table[state * vocab + token[0]], or, where that is GUIDE_BANNED (or no state of
 // the table), the state stays and status |= 16
 void launch_guide_advance(GuideState* guide_dev, int vocab, const int32_t* token, int* status, hipStream_t st);
 void launch_guide_state_store(GuideState* guide_dev, int32_t state, hipStream_t st);  // stream-ordered, capturable

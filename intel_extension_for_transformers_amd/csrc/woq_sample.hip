@@ -16,7 +16,7 @@
 // depends on (seed, position, logits) only, so eager steps and graphs of any burst size give the same tokens.
 //
 // Sampler controls (woq_sampler_controls: logit bias, presence / frequency penalty, min_p). With them installed a pre-pass
-// over the whole chip (score_adjust_kernel, one id per thread) writes, for every id, the fp32 score
+// over the whole chip (score_adjust_kernel<false>, one id per thread) writes, for every id, the fp32 score
 //   s = l; s = s + b[i] (ids with a bias entry); repetition penalty as above; for ids generated c[i] > 0 times
 //   s = s - (freq * (float)c[i]); s = s - pres
 // — every operation rounded on its own (compiled with fp contraction off: no fma) — into an engine-owned
@@ -27,9 +27,10 @@
 // also counts its pick in c. The logits themselves are never modified (the log-probability record reads them).
 //
 // Token guide (woq_host.h GuideState: a dense uint16 table next[n_states][vocab] and a state, both on the device). With
-// one installed the pre-pass is score_adjust_guided_kernel: the four steps above, then step 5, `s = -inf` where the
+// one installed the pre-pass is score_adjust_kernel<true>: the four steps above, then step 5, `s = -inf` where the
 // state's row holds 0xFFFF. After the sampling launch a one-thread launch (guide_advance_kernel) moves the state to
 // row[token]. Pointer and state are read from the struct: another guide, or a reset, needs no new capture.
+// One launcher, launch_sample_tail, issues all three forms: the buffers set in its SampleTail (woq_host.h) decide.
 #include <algorithm>
 #include <vector>
 
@@ -380,17 +381,22 @@ __global__ void sampler_controls_store_kernel(woq_sampler_controls v, woq_sample
 
 constexpr int ADJUST_THREADS = 256;  // one id per thread: 125 .. 501 workgroups for 32000 .. 128256 ids, four loads each
 
-// steps 1-4 of the controls' contract for every id (the header comment); `adj` is what sample_kernel<true> reads
+// steps 1-4 of the controls' contract for every id (the header comment); `adj` is what sample_kernel<true> reads.
+// GUIDED: then step 5, the ban of the guide's current row (`guide` is not read otherwise). The table pointer and the
+// state come from the device struct, never from the launch: another guide or a reset keeps a captured graph valid.
+template <bool GUIDED>
 __global__ __launch_bounds__(ADJUST_THREADS) void score_adjust_kernel(
     const float* __restrict__ logits, int vocab, const uint32_t* __restrict__ seen, const uint32_t* __restrict__ counts,
     const float* __restrict__ bias, const woq_sampler_config* __restrict__ cfgp,
-    const woq_sampler_controls* __restrict__ ctlp, float* __restrict__ adj) {
+    const woq_sampler_controls* __restrict__ ctlp, const GuideState* __restrict__ guide, float* __restrict__ adj) {
 // No contraction: `s - freq * c` must round twice. Plain operators under this pragma — HIP's __fmul_rn / __fsub_rn are
 // inline functions over plain operators that carry their header's contract flag, and fuse into one fma once inlined.
 #pragma clang fp contract(off)
   const int i = blockIdx.x * ADJUST_THREADS + threadIdx.x;
   if (i >= vocab) return;
   const float pen = cfgp->repetition_penalty, pres = ctlp->presence_penalty, freq = ctlp->frequency_penalty;
+  const uint16_t* row = nullptr;
+  if constexpr (GUIDED) row = guide->table + (size_t)guide->state * (size_t)vocab;  // 64-bit: 65535 states x 128256 ids
   float s = logits[i];
   const float b = bias[i];
   if (b == b) s = s + b;  // NaN = no entry
@@ -401,32 +407,8 @@ __global__ __launch_bounds__(ADJUST_THREADS) void score_adjust_kernel(
     s = s - step;
     s = s - pres;
   }
-  adj[i] = s;
-}
-
-// The twin of score_adjust_kernel with a token guide installed: steps 1-4 word for word (kept as a twin so that the
-// kernel above stays the one it is), then step 5, the ban of the guide's current row. The table pointer and the state
-// come from the device struct, never from the launch: another guide or a reset keeps a captured graph valid.
-__global__ __launch_bounds__(ADJUST_THREADS) void score_adjust_guided_kernel(
-    const float* __restrict__ logits, int vocab, const uint32_t* __restrict__ seen, const uint32_t* __restrict__ counts,
-    const float* __restrict__ bias, const woq_sampler_config* __restrict__ cfgp,
-    const woq_sampler_controls* __restrict__ ctlp, const GuideState* __restrict__ guide, float* __restrict__ adj) {
-#pragma clang fp contract(off)
-  const int i = blockIdx.x * ADJUST_THREADS + threadIdx.x;
-  if (i >= vocab) return;
-  const float pen = cfgp->repetition_penalty, pres = ctlp->presence_penalty, freq = ctlp->frequency_penalty;
-  const uint16_t* row = guide->table + (size_t)guide->state * (size_t)vocab;  // 64-bit: 65535 states x 128256 ids
-  float s = logits[i];
-  const float b = bias[i];
-  if (b == b) s = s + b;  // NaN = no entry
-  if (pen != 1.0f && ((seen[i >> 5] >> (i & 31)) & 1u)) s = s < 0.f ? s * pen : s / pen;
-  const uint32_t c = counts[i];
-  if (c > 0u) {
-    const float step = freq * (float)c;
-    s = s - step;
-    s = s - pres;
-  }
-  if (row[i] == GUIDE_BANNED) s = -INFINITY;  // last: a positive penalty cannot lift -inf, so the order does not matter
+  if constexpr (GUIDED)  // last: a positive penalty cannot lift -inf, so the order does not matter
+    if (row[i] == GUIDE_BANNED) s = -INFINITY;
   adj[i] = s;
 }
 
@@ -463,34 +445,19 @@ __global__ void sampler_bias_scatter_kernel(float* __restrict__ bias, int vocab,
 
 }  // namespace
 
-void launch_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg_dev, const float* u_dev,
-                   int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out,
-                   int* status, hipStream_t st) {
-  hipLaunchKernelGGL(sample_kernel<false>, dim3(1), dim3(SAMPLE_THREADS), 0, st, logits, vocab, seen, cfg_dev, u_dev,
-                     token, pos_advance, pos_fixed, log, philox_out, status, (const woq_sampler_controls*)nullptr,
-                     (uint32_t*)nullptr, (uint32_t*)nullptr);
-}
-
-void launch_sample_controls(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
-                            const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev, float* adj,
-                            const float* u_dev, int32_t* token, int32_t* pos_advance, const int32_t* pos_fixed,
-                            int32_t* log, uint32_t* philox_out, int* status, hipStream_t st, uint32_t* kept_out) {
-  hipLaunchKernelGGL(score_adjust_kernel, dim3((vocab + ADJUST_THREADS - 1) / ADJUST_THREADS), dim3(ADJUST_THREADS), 0, st,
-                     logits, vocab, (const uint32_t*)seen, (const uint32_t*)counts, bias, cfg_dev, ctl_dev, adj);
-  hipLaunchKernelGGL(sample_kernel<true>, dim3(1), dim3(SAMPLE_THREADS), 0, st, (const float*)adj, vocab, seen, cfg_dev,
-                     u_dev, token, pos_advance, pos_fixed, log, philox_out, status, ctl_dev, counts, kept_out);
-}
-
-void launch_sample_guided(const float* logits, int vocab, uint32_t* seen, uint32_t* counts, const float* bias,
-                          const woq_sampler_config* cfg_dev, const woq_sampler_controls* ctl_dev,
-                          const GuideState* guide_dev, float* adj, const float* u_dev, int32_t* token,
-                          int32_t* pos_advance, const int32_t* pos_fixed, int32_t* log, uint32_t* philox_out, int* status,
-                          hipStream_t st, uint32_t* kept_out) {
-  hipLaunchKernelGGL(score_adjust_guided_kernel, dim3((vocab + ADJUST_THREADS - 1) / ADJUST_THREADS), dim3(ADJUST_THREADS),
-                     0, st, logits, vocab, (const uint32_t*)seen, (const uint32_t*)counts, bias, cfg_dev, ctl_dev, guide_dev,
-                     adj);
-  hipLaunchKernelGGL(sample_kernel<true>, dim3(1), dim3(SAMPLE_THREADS), 0, st, (const float*)adj, vocab, seen, cfg_dev,
-                     u_dev, token, pos_advance, pos_fixed, log, philox_out, status, ctl_dev, counts, kept_out);
+int launch_sample_tail(const SampleTail& t, hipStream_t st) {
+  const bool ctl = t.adj != nullptr;
+  // a missing or misplaced slot fails here, not on the device (without `adj` the kernel then gets nulls for the rest)
+  if ((t.counts != nullptr) != ctl || (t.bias != nullptr) != ctl || (t.ctl != nullptr) != ctl || (t.guide != nullptr && !ctl))
+    return fail("QBits: a sampled pick takes the controls' four buffers or none of them, and a guide only with them");
+  if (ctl)  // the pre-pass: logits -> adj
+    hipLaunchKernelGGL(t.guide != nullptr ? score_adjust_kernel<true> : score_adjust_kernel<false>,
+                       dim3((t.vocab + ADJUST_THREADS - 1) / ADJUST_THREADS), dim3(ADJUST_THREADS), 0, st, t.logits, t.vocab,
+                       (const uint32_t*)t.seen, (const uint32_t*)t.counts, t.bias, t.cfg, t.ctl, t.guide, t.adj);
+  hipLaunchKernelGGL(ctl ? sample_kernel<true> : sample_kernel<false>, dim3(1), dim3(SAMPLE_THREADS), 0, st,
+                     ctl ? (const float*)t.adj : t.logits, t.vocab, t.seen, t.cfg, t.u, t.token, t.pos_advance, t.pos_fixed,
+                     t.log, t.philox_out, t.status, t.ctl, t.counts, ctl ? t.kept_out : nullptr);
+  return 0;
 }
 
 void launch_guide_advance(GuideState* guide_dev, int vocab, const int32_t* token, int* status, hipStream_t st) {
@@ -562,23 +529,17 @@ const char* sampler_controls_problem(const woq_sampler_controls& c, const woq_sa
   return nullptr;
 }
 
-// what a probe of the controls' tail needs on the device, one allocation on `st` (the caller frees `buf` on `st`):
-// [config 32][controls 32][guide state 32][bias table vocab * 4][ids n * 4][values n * 4]
-struct ProbeControls {
-  char* buf;
-  woq_sampler_config* cfg;
-  woq_sampler_controls* ctl;
-  GuideState* guide;  // not written here
-  float* bias;
-};
-static int probe_controls_setup(const woq_sampler_config& cfg, const woq_sampler_controls& ctl, int vocab,
-                                const int32_t* bias_ids_host, const float* bias_vals_host, hipStream_t st,
-                                ProbeControls* out) {
+// What a probe's pick `t` needs on the device, one allocation on `st` (the caller frees `*out` on `st`): [config 32] and,
+// with controls (`ctl` not null), [controls 32][guide state 32, not written here][bias table vocab * 4][ids n * 4]
+// [values n * 4]. `t` (its vocab is read) leaves with the config and, with controls, their struct and table.
+constexpr size_t PROBE_GUIDE_AT = 64;
+static int probe_tail_setup(const woq_sampler_config& cfg, const woq_sampler_controls* ctl, const int32_t* bias_ids_host,
+                            const float* bias_vals_host, hipStream_t st, SampleTail* t, char** out) {
   WOQ_TRY
-  const int n = ctl.n_bias;
+  const int n = ctl != nullptr ? ctl->n_bias : 0;
   char* buf = nullptr;
-  const size_t table = 96, ids_at = table + (size_t)vocab * 4, vals_at = ids_at + (size_t)n * 4;
-  WOQ_HIP(hipMallocAsync((void**)&buf, vals_at + (size_t)n * 4 + 4, st));
+  const size_t table = 96, ids_at = table + (size_t)t->vocab * 4, vals_at = ids_at + (size_t)n * 4;
+  WOQ_HIP(hipMallocAsync((void**)&buf, ctl != nullptr ? vals_at + (size_t)n * 4 + 4 : sizeof(woq_sampler_config), st));
   if (n > 0) {  // the host arrays may go away when the probe returns: copies that have completed by then
     hipError_t err = hipMemcpyAsync(buf + ids_at, bias_ids_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
     if (err == hipSuccess) err = hipMemcpyAsync(buf + vals_at, bias_vals_host, (size_t)n * 4, hipMemcpyHostToDevice, st);
@@ -588,10 +549,14 @@ static int probe_controls_setup(const woq_sampler_config& cfg, const woq_sampler
       return fail(std::string("QBits: HIP error '") + hipGetErrorString(err) + "' copying the logit_bias entries");
     }
   }
-  *out = {buf, (woq_sampler_config*)buf, (woq_sampler_controls*)(buf + 32), (GuideState*)(buf + 64), (float*)(buf + table)};
-  launch_sampler_config_store(cfg, out->cfg, st);
-  launch_sampler_controls_store(ctl, out->ctl, st);
-  if (launch_sampler_bias_store(out->bias, vocab, (const int32_t*)(buf + ids_at), (const float*)(buf + vals_at), n, st) != 0) {
+  *out = buf;
+  launch_sampler_config_store(cfg, (woq_sampler_config*)buf, st);
+  t->cfg = (const woq_sampler_config*)buf;
+  if (ctl == nullptr) return 0;
+  launch_sampler_controls_store(*ctl, (woq_sampler_controls*)(buf + 32), st);
+  t->ctl = (const woq_sampler_controls*)(buf + 32), t->bias = (const float*)(buf + table);
+  if (launch_sampler_bias_store((float*)(buf + table), t->vocab, (const int32_t*)(buf + ids_at),
+                                (const float*)(buf + vals_at), n, st) != 0) {
     hipFreeAsync(buf, st);
     return 1;
   }
@@ -610,12 +575,15 @@ WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, con
   const char* why = woq::sampler_config_problem(*cfg);
   if (why) return woq::fail(why);
   const hipStream_t st = (hipStream_t)stream;
-  woq_sampler_config* cfg_dev = nullptr;
-  WOQ_HIP(hipMallocAsync((void**)&cfg_dev, sizeof(woq_sampler_config), st));
-  woq::launch_sampler_config_store(*cfg, cfg_dev, st);
-  woq::launch_sample(logits, vocab, seen, cfg_dev, u_or_null, token_out, nullptr, pos_dev, nullptr, philox_out4, status,
-                     st);
-  WOQ_HIP(hipFreeAsync(cfg_dev, st));
+  woq::SampleTail t;
+  t.logits = logits, t.vocab = vocab, t.seen = seen, t.token = token_out, t.pos_fixed = pos_dev, t.status = status;
+  t.u = u_or_null, t.philox_out = philox_out4;
+  char* buf = nullptr;
+  int rc = woq::probe_tail_setup(*cfg, nullptr, nullptr, nullptr, st, &t, &buf);
+  if (rc) return rc;
+  rc = woq::launch_sample_tail(t, st);
+  WOQ_HIP(hipFreeAsync(buf, st));
+  if (rc) return rc;
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }
@@ -632,12 +600,15 @@ WOQ_API int woq_probe_sample_controls(const float* logits, int vocab, uint32_t* 
   if (why == nullptr) why = woq::sampler_controls_problem(*ctl, *cfg, vocab, bias_ids_host, bias_vals_host);
   if (why) return woq::fail(why);
   const hipStream_t st = (hipStream_t)stream;
-  woq::ProbeControls pc;
-  int rc = woq::probe_controls_setup(*cfg, *ctl, vocab, bias_ids_host, bias_vals_host, st, &pc);
+  woq::SampleTail t;
+  t.logits = logits, t.vocab = vocab, t.seen = seen, t.token = token_out, t.pos_fixed = pos_dev, t.status = status;
+  t.u = u_or_null, t.counts = counts, t.adj = adjusted_out, t.kept_out = kept_out;
+  char* buf = nullptr;
+  int rc = woq::probe_tail_setup(*cfg, ctl, bias_ids_host, bias_vals_host, st, &t, &buf);
   if (rc) return rc;
-  woq::launch_sample_controls(logits, vocab, seen, counts, pc.bias, pc.cfg, pc.ctl, adjusted_out, u_or_null, token_out,
-                              nullptr, pos_dev, nullptr, nullptr, status, st, kept_out);
-  WOQ_HIP(hipFreeAsync(pc.buf, st));
+  rc = woq::launch_sample_tail(t, st);
+  WOQ_HIP(hipFreeAsync(buf, st));
+  if (rc) return rc;
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }
@@ -657,20 +628,24 @@ WOQ_API int woq_probe_guide(const float* logits, int vocab, uint32_t* seen, uint
   if (why == nullptr && advance_state >= 0) why = woq::guide_problem(n_states, advance_state);
   if (why) return woq::fail(why);
   const hipStream_t st = (hipStream_t)stream;
-  woq::ProbeControls pc;
-  int rc = woq::probe_controls_setup(*cfg, *ctl, vocab, bias_ids_host, bias_vals_host, st, &pc);
+  woq::SampleTail t;
+  t.logits = logits, t.vocab = vocab, t.seen = seen, t.token = token_out, t.pos_fixed = pos_dev, t.status = status;
+  t.u = u_or_null, t.counts = counts, t.adj = adjusted_out;
+  char* buf = nullptr;
+  int rc = woq::probe_tail_setup(*cfg, ctl, bias_ids_host, bias_vals_host, st, &t, &buf);
   if (rc) return rc;
+  woq::GuideState* guide = (woq::GuideState*)(buf + woq::PROBE_GUIDE_AT);
+  t.guide = guide;
   const woq::GuideState g = {table_dev, n_states, state};
-  hipError_t err = hipMemcpyAsync(pc.guide, &g, sizeof(g), hipMemcpyHostToDevice, st);
+  hipError_t err = hipMemcpyAsync(guide, &g, sizeof(g), hipMemcpyHostToDevice, st);
   if (err == hipSuccess) err = hipStreamSynchronize(st);  // `g` goes away when this returns
-  if (err == hipSuccess) {
-    woq::launch_sample_guided(logits, vocab, seen, counts, pc.bias, pc.cfg, pc.ctl, pc.guide, adjusted_out, u_or_null,
-                              token_out, nullptr, pos_dev, nullptr, nullptr, status, st);
-    if (advance_state >= 0) woq::launch_guide_state_store(pc.guide, advance_state, st);
-    woq::launch_guide_advance(pc.guide, vocab, token_out, status, st);
-    err = hipMemcpyAsync(state_out, &pc.guide->state, 4, hipMemcpyDeviceToDevice, st);
+  if (err == hipSuccess && (rc = woq::launch_sample_tail(t, st)) == 0) {
+    if (advance_state >= 0) woq::launch_guide_state_store(guide, advance_state, st);
+    woq::launch_guide_advance(guide, vocab, token_out, status, st);
+    err = hipMemcpyAsync(state_out, &guide->state, 4, hipMemcpyDeviceToDevice, st);
   }
-  hipFreeAsync(pc.buf, st);
+  hipFreeAsync(buf, st);
+  if (rc) return rc;
   WOQ_HIP(err);
   WOQ_HIP(hipGetLastError());
   WOQ_END

@@ -1,4 +1,4 @@
-"""Reference pieces for the token guide (runtime/guide.py, csrc/woq_sample.hip `score_adjust_guided_kernel` and
+"""Reference pieces for the token guide (runtime/guide.py, csrc/woq_sample.hip `score_adjust_kernel<true>` and
 `guide_advance_kernel`), shared by tests/test_guide_cpu.py and the GPU guide tests.
 
 * `masked_f32`: step 5 of the score contract on top of tests/sampler_controls_reference.py: -inf where the state's row

@@ -1,4 +1,4 @@
-"""The token tail with a token guide (csrc/woq_sample.hip: `score_adjust_guided_kernel` + `sample_kernel<true>` +
+"""The token tail with a token guide (csrc/woq_sample.hip: `score_adjust_kernel<true>` + `sample_kernel<true>` +
 `guide_advance_kernel`) alone, through `woq_probe_guide`, against tests/guide_reference.py on top of
 tests/sampler_controls_reference.py.
 

@@ -3,7 +3,8 @@ prompt pass, eager steps, the one-step graph and the graph of 8 chained steps pi
 Deterministic settings are held token for token to the torch path (`iter_sampled` + `DeviceSampler`: same logits kernels,
 same IEEE penalty); a seeded sampled run is checked step by step against tests/sampler_reference.py with the numpy Philox
 uniform of each position (acceptance rule and tolerance of tests/test_gpu_sampler_kernel.py), and must not depend on the
-launch mode, the burst size or a parameter change without recapture."""
+launch mode, the burst size or a parameter change without recapture. One table test pins which setter calls drop a
+captured graph: those that change (sampler, controls, guide, logprobs), and no others."""
 import copy
 
 import numpy as np
@@ -162,6 +163,83 @@ def test_seeded_sampled_run_step_by_step_and_across_launch_modes(qmodel):
     finally:
         eng.clear_sampler()
     assert out[:25] == tokens[:25] and out != tokens
+    assert eng.status() == 0 and not eng.captured
+
+
+# the reachable tails as (sampler, controls, guide, logprobs): what a captured graph holds of the tail
+TAILS = [(s, c, g, lp) for s, c, g in ((0, 0, 0), (1, 0, 0), (1, 1, 0), (1, 0, 1), (1, 1, 1)) for lp in (0, 1)]
+
+
+def _permissive_guide(vocab, flip):
+    """two states, nothing banned: every id moves to the other state (`flip`) or stays"""
+    from intel_extension_for_transformers_amd.runtime.guide import TokenGuide
+
+    table = np.empty((2, vocab), np.uint16)
+    table[0], table[1] = (1, 0) if flip else (0, 1)
+    return TokenGuide(table)
+
+
+def _set_tail(eng, tail, variant=0):
+    """the engine into `tail` through the public setters alone; `variant` changes every installed value, no flag"""
+    s, c, g, lp = tail
+    if s:
+        eng.set_sampler(do_sample=True, temperature=0.9 + variant, top_k=8, seed=3 + variant,
+                        **(dict(presence_penalty=0.5 + variant, logit_bias={7: -1.0 - variant}) if c else {}))
+        if g:
+            eng.set_guide(_permissive_guide(eng.cfg.vocab, flip=bool(variant)))
+        elif eng.guide_installed:
+            eng.clear_guide()
+    else:
+        eng.clear_sampler()
+    eng.set_logprobs(bool(lp))
+    assert (eng.sampler_installed, eng.controls_installed, eng.guide_installed, eng.logprobs_on) == tuple(map(bool, tail))
+
+
+def _replay_one(eng):
+    """woq_engine_replay(h, 1, stream) itself: (return code, message)"""
+    from intel_extension_for_transformers_amd import _lib as L
+
+    rc = L.lib().woq_engine_replay(eng._h, 1, L.stream_ptr())
+    return rc, (L.lib().woq_last_error().decode() if rc else "")
+
+
+def test_a_captured_graph_survives_a_setter_iff_the_tail_stays(qmodel):
+    """Every ordered pair (A, B) of the ten tails: capture under A, move to B through the setters (other values where
+    both have the same thing installed), replay. The graph is still there iff A == B; otherwise the replay is refused
+    with a message (no fault). `eng.captured` says the same throughout. All 100 pairs are walked: on the two-layer model
+    a capture is well under a millisecond and the whole table takes about 0.1 s on an MI355X."""
+    eng = qmodel.woq_engine
+    eng.launch = "graph"
+    eng.prefill(PROMPT, greedy=True)
+    try:
+        for a in TAILS:
+            for b in TAILS:
+                _set_tail(eng, a)
+                eng.pos.fill_(len(PROMPT))
+                eng.capture()
+                _set_tail(eng, b, variant=1)
+                rc, why = _replay_one(eng)
+                assert eng.captured == (a == b), (a, b)
+                if a == b:
+                    assert rc == 0, (a, b, why)
+                else:
+                    assert rc != 0 and "engine graph not captured" in why, (a, b, rc, why)
+        # what the setters document to keep the graph, one by one
+        _set_tail(eng, (1, 1, 1, 0))
+        eng.capture()
+        for keep in (lambda: eng.set_sampler(do_sample=True, temperature=5.0, top_k=200, presence_penalty=0.5),  # sampler
+                     lambda: eng.set_sampler(do_sample=True, temperature=5.0, top_k=200, min_p=0.1),  # the controls' values
+                     lambda: eng.set_guide(_permissive_guide(eng.cfg.vocab, flip=True)),  # another guide
+                     lambda: eng.guide_reset(1)):
+            keep()
+            assert eng.captured and _replay_one(eng) == (0, "")
+        # removing the controls under an installed guide runs the same kernels and still drops the graph
+        eng.set_sampler(do_sample=True, temperature=5.0, top_k=200)
+        assert not eng.captured and eng.guide_installed and _replay_one(eng)[0] != 0
+        torch.cuda.synchronize()
+    finally:
+        eng.clear_sampler()
+        eng.set_logprobs(False)
     assert eng.status() == 0 and not eng.captured
 
 
