@@ -187,7 +187,9 @@ __global__ void extract_kernel(const uint8_t* __restrict__ blob, woq_blob_header
 }
 
 // RTN: one thread per (group, column). int4 "clip" range (bits = 4) or int8 (bits = 8). Rounding rule documented in DESIGN.md
-// (parity unpinned: BesTLA's quantiser is not in /root/reference). rintf = round-half-even.
+// (parity unpinned: BesTLA's quantiser is not in /root/reference). rintf = round-half-even. sym: s = max|w| / qmax;
+// asym: s = (max(mx, 0) - min(mn, 0)) / levels, z = clip(rne(-min(mn, 0) / s), 0, levels) — the range always holds
+// zero, so a group on one side of zero is within half a step like any other (tests/quant_reference.py).
 __global__ void rtn_kernel(const float* __restrict__ w, int transpose, int K, int N, int group, int n_groups,
                            int asym, int bits, int8_t* __restrict__ q, float* __restrict__ scales,
                            int8_t* __restrict__ zp) {
@@ -210,9 +212,10 @@ __global__ void rtn_kernel(const float* __restrict__ w, int transpose, int K, in
     s = amax / (float)qmax;
     if (s == 0.f) s = 1.f;
   } else {
-    s = (mx - mn) / (float)levels;
+    const float hi = fmaxf(mx, 0.f), lo = fminf(mn, 0.f);  // zero inside the range: a one-sided group keeps its codes
+    s = (hi - lo) / (float)levels;
     if (s == 0.f) s = 1.f;
-    z = (int)rintf(-mn / s);
+    z = (int)rintf(-lo / s);
     z = max(0, min(levels, z));
   }
   scales[idx] = s;
@@ -265,7 +268,8 @@ __global__ void rtn_lut_kernel(const float* __restrict__ w, int transpose, int K
 // beats -0 and a midpoint takes the smaller code). Parity unpinned like the other rules (BesTLA's quantiser is not
 // in the reference tree). Load-time kernel: a plain search over the 256 codes.
 __global__ void rtn_fp8_kernel(const float* __restrict__ w, int transpose, int K, int N, int group, int n_groups,
-                               uint32_t weight_type, int e8m0, int8_t* __restrict__ q, float* __restrict__ scales) {
+                               uint32_t weight_type, int e8m0, int scale_type, int8_t* __restrict__ q,
+                               float* __restrict__ scales) {
   __shared__ float val[256];
   val[threadIdx.x & 255] = fp8_code_value(weight_type, threadIdx.x & 255);
   __syncthreads();
@@ -283,6 +287,10 @@ __global__ void rtn_fp8_kernel(const float* __restrict__ w, int transpose, int K
     s = ldexpf(1.0f, f == 0.5f ? e - 1 : e);
   }
   scales[idx] = s;
+  // the codes are chosen against the scale as the blob keeps it (repack rounds `scales` the same way), so that each
+  // is the nearest to what dequantisation multiplies by
+  if (scale_type == WOQ_BF16) s = bf16_bits_to_f32(f32_to_bf16_bits(s));
+  if (scale_type == WOQ_F16) s = f16_bits_to_f32(f32_to_f16_bits(s));
   for (int k = k0; k < k1; ++k) {
     const float v = (transpose ? w[(size_t)n * K + k] : w[(size_t)k * N + n]) / s;
     int best = 0;
@@ -480,7 +488,8 @@ int woq_quantize_to_packed_weight(const float* weight_dev, int transpose, int K,
   size_t nt = (size_t)n_groups * N;
   if (fp8)
     hipLaunchKernelGGL(rtn_fp8_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, weight_dev, transpose, K,
-                       N, group, n_groups, (uint32_t)weight_type, scale_type == WOQ_SCALE_FP8_E8M0 ? 1 : 0, q, sc);
+                       N, group, n_groups, (uint32_t)weight_type, scale_type == WOQ_SCALE_FP8_E8M0 ? 1 : 0,
+                       scale_type == WOQ_SCALE_FP8_E8M0 ? (int)WOQ_BF16 : scale_type, q, sc);
   else if (is_table_type((uint32_t)weight_type))
     hipLaunchKernelGGL(rtn_lut_kernel, dim3((unsigned)((nt + 127) / 128)), dim3(128), 0, st, weight_dev, transpose, K,
                        N, group, n_groups, (uint32_t)weight_type, q, sc);

@@ -181,8 +181,10 @@ ORC_API void orc_convert_idx(const int32_t* g_idx, int K, int blocksize, int32_t
 /* ---------------------------------------------------------------------------------------
  * RTN quantiser — PARITY UNPINNED (see header). Formula implied by the reference's own
  * re-quantisation helper quant_weight_w_scale (modules.py:264-295): q = round(w/scale + zp),
- * with the int4 "clip" range: sym scale = max|w| / 7, q in [-8,7]; asym scale = (max-min)/15,
- * zp = round(-min/scale), q in [0,15] then shifted to the signed domain (q-8, zp-8).
+ * with the int4 "clip" range: sym scale = max|w| / 7, q in [-8,7]; asym over the range widened to
+ * hold zero, lo = min(min w, 0), hi = max(max w, 0): scale = (hi - lo) / 15, zp = round(-lo / scale),
+ * q in [0,15] then shifted to the signed domain (q-8, zp-8). (Without the widening a group on one
+ * side of zero clips its zero point and saturates every code; tests/quant_reference.py.)
  * weight is [K,N] (transpose=0) or [N,K] (transpose=1, nn.Linear layout, qbits.cpp:90-92).
  * outputs: q int8 [K,N] signed domain, scales fp32 [G,N], zp int8 [G,N] signed domain.
  * rounding: nearbyintf (round-half-even, what torch.round does).
@@ -208,9 +210,10 @@ ORC_API void orc_rtn_quantize(const float* w, int transpose, int K, int N, int g
         s = amax / 7.f;
         if (s == 0.f) s = 1.f;
       } else {
-        s = (mx - mn) / 15.f;
+        const float hi = mx > 0.f ? mx : 0.f, lo = mn < 0.f ? mn : 0.f; /* zero inside the range */
+        s = (hi - lo) / 15.f;
         if (s == 0.f) s = 1.f;
-        z = (int)nearbyintf(-mn / s);
+        z = (int)nearbyintf(-lo / s);
         z = z < 0 ? 0 : (z > 15 ? 15 : z);
       }
       scales[(size_t)g * N + n] = s;

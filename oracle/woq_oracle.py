@@ -267,8 +267,8 @@ def _int8_parts(blob):
 
 def rtn_quantize_int8(w, transpose, group, asym):
     """8-bit form of the (parity-unpinned) RTN rule of woq_oracle.c, in fp32 arithmetic like the device kernel:
-    sym s = max|w| / 127, q = clip(rne(w / s), -128, 127); asym s = (max - min) / 255, z = clip(rne(-min / s), 0, 255),
-    q = clip(rne(w / s) + z, 0, 255) - 128, zp = z - 128."""
+    sym s = max|w| / 127, q = clip(rne(w / s), -128, 127); asym, lo = min(min w, 0), hi = max(max w, 0):
+    s = (hi - lo) / 255, z = clip(rne(-lo / s), 0, 255), q = clip(rne(w / s) + z, 0, 255) - 128, zp = z - 128."""
     return rtn_quantize_bits(w, transpose, group, asym, 8)
 
 
@@ -289,8 +289,9 @@ def repack_narrow(q, scales, zp=None, shuffle=None, group=-1, scale_type=F32, co
 def rtn_quantize_bits(w, transpose, group, asym, bits):
     """The (parity-unpinned) RTN rule of woq_oracle.c for any width, in fp32 arithmetic like the device kernel:
     qmax = 2^(bits-1) - 1, levels = 2^bits - 1, off = 2^(bits-1);
-    sym s = max|w| / qmax, q = clip(rne(w / s), -off, qmax); asym s = (max - min) / levels,
-    z = clip(rne(-min / s), 0, levels), q = clip(rne(w / s) + z, 0, levels) - off, zp = z - off."""
+    sym s = max|w| / qmax, q = clip(rne(w / s), -off, qmax); asym over the range widened to hold zero,
+    lo = min(min w, 0), hi = max(max w, 0): s = (hi - lo) / levels, z = clip(rne(-lo / s), 0, levels),
+    q = clip(rne(w / s) + z, 0, levels) - off, zp = z - off."""
     qmax, levels, off = (1 << (bits - 1)) - 1, (1 << bits) - 1, 1 << (bits - 1)
     w = np.asarray(w, np.float32)
     w = w.T if transpose else w
@@ -307,10 +308,10 @@ def rtn_quantize_bits(w, transpose, group, asym, bits):
             sc[sc == 0] = 1
             q[gi * g:gi * g + blk.shape[0]] = np.clip(np.rint(blk / sc), -off, qmax).astype(np.int8)
         else:
-            mx, mn = blk.max(0), blk.min(0)
-            sc = ((mx - mn) / np.float32(levels)).astype(np.float32)
+            hi, lo = np.maximum(blk.max(0), np.float32(0)), np.minimum(blk.min(0), np.float32(0))
+            sc = ((hi - lo) / np.float32(levels)).astype(np.float32)
             sc[sc == 0] = 1
-            zz = np.clip(np.rint(-mn / sc), 0, levels).astype(np.int32)
+            zz = np.clip(np.rint(-lo / sc), 0, levels).astype(np.int32)
             q[gi * g:gi * g + blk.shape[0]] = (np.clip(np.rint(blk / sc).astype(np.int32) + zz, 0, levels) - off).astype(np.int8)
             z[gi] = (zz - off).astype(np.int8)
         s[gi] = sc
@@ -342,10 +343,12 @@ FP8_TABLES = {W_FP8_E4M3: _fp8_table(W_FP8_E4M3), W_FP8_E5M2: _fp8_table(W_FP8_E
 FP8_MAX = {W_FP8_E4M3: 448.0, W_FP8_E5M2: 57344.0}
 
 
-def rtn_quantize_fp8(w, transpose, group, wtype, e8m0=False):
+def rtn_quantize_fp8(w, transpose, group, wtype, e8m0=False, scale_type=F32):
     """scale = max|w| / fp8_max per group (e8m0: the next power of two at or above it), code = the finite code whose
     value is nearest to w / scale in fp32, lowest code on ties — the device kernel's rule (parity unpinned: BesTLA's
-    quantiser is not in the reference tree). Returns codes uint8 [K, N], scales fp32 [G, N]."""
+    quantiser is not in the reference tree). With 16-bit scale storage (`scale_type`) the codes are chosen against the
+    scale as the blob will keep it, so that each is the nearest to what dequantisation multiplies by. Returns codes
+    uint8 [K, N], scales fp32 [G, N] (before the storage rounding, which repack applies)."""
     w = np.asarray(w, np.float32)
     w = w.T if transpose else w
     K, N = w.shape
@@ -362,7 +365,9 @@ def rtn_quantize_fp8(w, transpose, group, wtype, e8m0=False):
         if e8m0:
             f, e = np.frexp(sc)
             sc = np.ldexp(np.float32(1), np.where(f == 0.5, e - 1, e)).astype(np.float32)
-        d = np.abs((blk / sc)[..., None].astype(np.float32) - tab[None, None, :])
+        sq = bf16_round(sc) if scale_type == BF16 else (sc.astype(np.float16).astype(np.float32)
+                                                        if scale_type == F16 else sc)
+        d = np.abs((blk / sq)[..., None].astype(np.float32) - tab[None, None, :])
         d[..., ~finite] = np.inf
         q[gi * g:gi * g + blk.shape[0]] = d.argmin(-1).astype(np.uint8)  # first (lowest) code on ties
         s[gi] = sc
