@@ -275,8 +275,10 @@ WOQ_API int woq_engine_steps(woq_engine* e, int n, int greedy, void* stream);
  * ids of the `seen` bit set (fp32, `s < 0 ? s * penalty : s / penalty`), then argmax (do_sample == 0, lowest id on
  * ties) or TemperatureLogitsWarper, TopKLogitsWarper (ties at the k-th value survive), TopPLogitsWarper
  * (min_tokens_to_keep 1) and an inverse-CDF draw with u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 under counter
- * (position fed, 0, 0, 0) and key (seed_lo, seed_hi): a token depends on (seed, position, logits) only, whatever the
- * burst size or launch mode. Covered: do_sample == 0; 1 <= top_k <= 1024 with any top_p; top_k == 0 with top_p == 1. */
+ * (position fed + discarded, 0, 0, 0) and key (seed_lo, seed_hi), `discarded` = the positions a rolling KV cache has
+ * dropped (woq_engine_kv_shift; 0 for a request that never shifts, uint32 wrap): a token depends on (seed, absolute
+ * position in the stream, logits) only, whatever the burst size or launch mode, and no draw repeats after a shift.
+ * Covered: do_sample == 0; 1 <= top_k <= 1024 with any top_p; top_k == 0 with top_p == 1. */
 typedef struct woq_sampler_config {
   int32_t do_sample;        /* 0 = argmax of the penalised scores */
   int32_t top_k;            /* 0 = whole vocabulary */
@@ -363,6 +365,27 @@ WOQ_API int woq_engine_set_logprobs(woq_engine* e, int on);
 WOQ_API int woq_engine_logprobs(woq_engine* e); /* 1 when recording */
 /* which: 0 chosen, 1 top_id, 2 top_lp; NULL before the first woq_engine_set_logprobs(e, 1) */
 WOQ_API void* woq_engine_logprob_ptr(woq_engine* e, int which);
+/* ---- rolling KV cache (StreamingLLM, reference docs/streamingllm.md: n_keep sinks, n_discard dropped after them; new
+ * entry points only, WOQ_ABI_VERSION stays 4, no struct changes) -------------------------------------------------------
+ * Sequence `seq`'s cache holds positions [0, n_cached). The call drops positions [n_keep, n_keep + n_discard) and moves
+ * every later row n_discard positions down, in place, in every layer (csrc/woq_kv_shift.hip): V rows are copied bit for
+ * bit; K rows, which are stored rotated, are rotated back by the angle of n_discard with row n_discard of the tables
+ * given to woq_engine_set_head (pairing d, d + D/2: a = K[p][d], b = K[p][d + D/2] -> a * cos + b * sin, b * cos -
+ * a * sin, products and sum in fp64, the sum rounded to fp32) and stored with the cache type's rounding and saturation —
+ * what the append kernels would have written at position p - n_discard, up to that rounding. Afterwards rows [0, n_keep) are bit-unchanged, rows
+ * [n_keep, n_cached - n_discard) hold the shifted rows, rows [n_cached - n_discard, n_cached) are unspecified, rows at
+ * or beyond n_cached and every other sequence are untouched. Every shift re-rounds the moved K rows to the cache type:
+ * for fp16 / bf16 one more rounding of the size the row already carries, for e4m3 a 3-bit mantissa each time.
+ * All geometry comes from the host, which counts its tokens: nothing is read back, nothing synchronises, nothing
+ * allocates; the work is stream-ordered and capturable. move_pos != 0 (seq == 0 only) also does pos -= n_discard and
+ * discarded += n_discard on the device in the same stream order, so a replayed graph or an eager burst issued next
+ * feeds position n_cached - n_discard. n_keep + n_discard == n_cached is legal: no row moves, only the two words change.
+ * Fails with a "QBits:" message, launching nothing: on a tensor-parallel engine, with a sliding window (reserved[2]),
+ * for seq outside [0, max_batch), n_keep < 0, n_discard < 1, n_keep + n_discard > n_cached, n_cached > max_ctx, and
+ * move_pos with seq != 0. */
+WOQ_API int   woq_engine_kv_shift(woq_engine* e, int seq, int n_keep, int n_discard, int n_cached, int move_pos, void* stream);
+WOQ_API void* woq_engine_discarded_ptr(woq_engine* e);                    /* int32[1] on the device */
+WOQ_API int   woq_engine_discarded_set(woq_engine* e, int value, void* stream);
 /* tensor-parallel seam: when set, the engine calls `fn(user, buf_dev, count_f32, stream)` after
  * o_proj and after down_proj (row-parallel partial sums -> sum over ranks). The Python host binds it
  * to RCCL via torch.distributed. NULL = single GPU. */

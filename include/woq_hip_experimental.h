@@ -117,6 +117,11 @@ WOQ_API int woq_engine_attn_plan(woq_engine* e, int splits, int grouped, long lo
 WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
                              const float* u_or_null, const int32_t* pos_dev, int32_t* token_out, uint32_t* philox_out4,
                              int* status, void* stream);
+/* woq_probe_sample with the word a rolling KV cache keeps (woq_engine_discarded_ptr, or any device int32; NULL = 0): the
+ * Philox counter is *pos_dev + *discarded_dev with uint32 wrap (tests/test_gpu_streaming_engine.py). */
+WOQ_API int woq_probe_sample_stream(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
+                                    const float* u_or_null, const int32_t* pos_dev, const int32_t* discarded_dev,
+                                    int32_t* token_out, uint32_t* philox_out4, int* status, void* stream);
 /* the token tail with sampler controls alone (tests/test_gpu_sampler_controls_kernel.py), forwarding to the engine's own
  * launcher: as woq_probe_sample, plus counts uint32 [vocab] (read by the pre-pass, the picked token's entry + 1), ctl
  * and its n_bias (id, value) pairs in HOST memory, adjusted_out = device fp32 [vocab] that receives the pre-pass's

@@ -97,6 +97,7 @@ EXPORTS = [
     "woq_engine_set_logprobs", "woq_engine_logprobs", "woq_engine_logprob_ptr", "woq_engine_prefill_scored",
     "woq_engine_set_sampler_controls", "woq_engine_sampler_counts", "woq_engine_sampler_count_ptr",
     "woq_engine_set_guide", "woq_engine_guide_reset", "woq_engine_guide_state_ptr",
+    "woq_engine_kv_shift", "woq_engine_discarded_ptr", "woq_engine_discarded_set",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -106,7 +107,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_logprobs", "woq_probe_score_rows", "woq_engine_prefill_rows_ptr",
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
     "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16", "woq_probe_sample_controls",
-    "woq_probe_attn_decode_plan", "woq_engine_attn_plan", "woq_probe_guide",
+    "woq_probe_attn_decode_plan", "woq_engine_attn_plan", "woq_probe_guide", "woq_probe_sample_stream",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -209,6 +210,11 @@ def lib():
     L.woq_engine_sampler_seen_ptr.restype = vp
     L.woq_engine_sampler_seen_ptr.argtypes = [vp]
     L.woq_probe_sample.argtypes = [vp, ci, vp, ctypes.POINTER(SamplerConfig), vp, vp, vp, vp, vp, vp]
+    L.woq_probe_sample_stream.argtypes = [vp, ci, vp, ctypes.POINTER(SamplerConfig), vp, vp, vp, vp, vp, vp, vp]
+    L.woq_engine_kv_shift.argtypes = [vp, ci, ci, ci, ci, ci, vp]
+    L.woq_engine_discarded_ptr.restype = vp
+    L.woq_engine_discarded_ptr.argtypes = [vp]
+    L.woq_engine_discarded_set.argtypes = [vp, ci, vp]
     L.woq_engine_set_sampler_controls.argtypes = [vp, ctypes.POINTER(SamplerControls), vp, vp]
     L.woq_engine_sampler_counts.argtypes = [vp, vp, ci, ci, vp]
     L.woq_engine_sampler_count_ptr.restype = vp
@@ -332,6 +338,17 @@ def probe_sample(logits, seen, cfg, pos, token_out, u=None, philox_out=None, sta
     opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
     rc = lib().woq_probe_sample(_ptr(logits), int(logits.numel()), _ptr(seen), ctypes.byref(cfg), opt(u), _ptr(pos),
                                 _ptr(token_out), opt(philox_out), opt(status), stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def probe_sample_stream(logits, seen, cfg, pos, discarded, token_out, u=None, philox_out=None, status=None):
+    """`probe_sample` with the rolling cache's word (woq_probe_sample_stream): `discarded` = an int32 device tensor or a
+    raw device pointer (`woq_engine_discarded_ptr`), None = 0; the Philox counter is position + discarded."""
+    opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
+    disc = discarded if discarded is None or isinstance(discarded, int) else _ptr(discarded)
+    rc = lib().woq_probe_sample_stream(_ptr(logits), int(logits.numel()), _ptr(seen), ctypes.byref(cfg), opt(u), _ptr(pos),
+                                       disc, _ptr(token_out), opt(philox_out), opt(status), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
 

@@ -52,6 +52,9 @@ struct woq_engine {
   float* logits = nullptr;
   int32_t* token = nullptr;
   int32_t* pos = nullptr;
+  // positions a rolling KV cache has dropped in the running request (woq_engine_kv_shift; 0 otherwise): the sampled
+  // tail's Philox counter is pos + discarded
+  int32_t* discarded = nullptr;
   uint8_t* kcache = nullptr;
   uint8_t* vcache = nullptr;
   size_t kv_layer_bytes = 0;
@@ -288,7 +291,7 @@ SampleTail woq_engine::sample_tail() const {
   t.logits = logits, t.vocab = cfg.vocab, t.seen = samp_seen, t.cfg = samp_cfg;
   if (controls_on || guide_on) t.counts = samp_count, t.bias = samp_bias, t.ctl = samp_ctl, t.adj = samp_adj;
   if (guide_on) t.guide = guide;
-  t.token = token, t.pos_advance = pos, t.log = tok_log, t.status = fuse_status;
+  t.token = token, t.pos_advance = pos, t.log = tok_log, t.status = fuse_status, t.discarded = discarded;
   return t;
 }
 // the record of the pick that was just launched: reads token[0], pos[0] - 1 and the logits, which the stream orders
@@ -657,6 +660,38 @@ int woq_engine_attn_plan(woq_engine* e, int splits, int grouped, long long* out1
 }
 void* woq_engine_kv_cache_ptr(woq_engine* e, int which) { return e ? (which ? e->vcache : e->kcache) : nullptr; }
 
+// rolling KV cache: every argument is checked before the first launch, so a refused call leaves the cache as it was
+int woq_engine_kv_shift(woq_engine* e, int seq, int n_keep, int n_discard, int n_cached, int move_pos, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr, "QBits: null engine");
+  const woq_engine_config& c = e->cfg;
+  WOQ_CHECK(c.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+            "QBits: the rolling KV cache runs on one GPU (no tensor-parallel shift)");
+  WOQ_CHECK(e->window == 0, "QBits: the rolling KV cache does not combine with a sliding window");
+  WOQ_CHECK(seq >= 0 && seq < e->max_batch, "QBits: KV shift: sequence outside [0, max_batch)");
+  WOQ_CHECK(n_keep >= 0 && n_discard >= 1, "QBits: KV shift needs n_keep >= 0 and n_discard >= 1");
+  WOQ_CHECK((long long)n_keep + n_discard <= n_cached, "QBits: KV shift: n_keep + n_discard exceeds the cached positions");
+  WOQ_CHECK(n_cached <= c.max_ctx, "QBits: KV shift: n_cached exceeds the engine's max_ctx");
+  WOQ_CHECK(move_pos == 0 || seq == 0, "QBits: KV shift: only sequence 0 has a position to move");
+  WOQ_CHECK(e->cs != nullptr && e->sn != nullptr, "QBits: KV shift before woq_engine_set_head (no rotation tables)");
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t seq_bytes = e->kv_layer_bytes * c.layers;
+  if (const int rc = launch_kv_shift(e->kcache + seq_bytes * seq, e->vcache + seq_bytes * seq, c.kv_dtype, c.layers,
+                                     c.kv_heads, c.head_dim, c.max_ctx, e->cs, e->sn, n_keep, n_discard, n_cached, st))
+    return rc;
+  if (move_pos != 0) launch_kv_shift_words(e->pos, e->discarded, n_discard, st);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+void* woq_engine_discarded_ptr(woq_engine* e) { return e ? e->discarded : nullptr; }
+int woq_engine_discarded_set(woq_engine* e, int value, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr, "QBits: null engine");
+  launch_i32_store(e->discarded, value, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
 int woq_engine_create(const woq_engine_config* cfg, woq_engine** out) {
   WOQ_TRY
   WOQ_CHECK(cfg && out, "QBits: null engine config");
@@ -676,6 +711,8 @@ int woq_engine_create(const woq_engine_config* cfg, woq_engine** out) {
   WOQ_HIP(hipMalloc((void**)&e->pos, 4));
   WOQ_HIP(hipMemset(e->token, 0, 4));
   WOQ_HIP(hipMemset(e->pos, 0, 4));
+  WOQ_HIP(hipMalloc((void**)&e->discarded, 4));
+  WOQ_HIP(hipMemset(e->discarded, 0, 4));
   e->kv_layer_bytes = (size_t)cfg->max_ctx * cfg->kv_heads * cfg->head_dim * woq_dtype_size((uint32_t)cfg->kv_dtype);
   // KV cache [sequence][layer][position][kv head][d]; sequence 0 is the one the decode step continues
   e->max_batch = cfg->reserved[0] > 1 ? cfg->reserved[0] : 1;
@@ -714,7 +751,8 @@ int woq_engine_create(const woq_engine_config* cfg, woq_engine** out) {
   WOQ_HIP(hipMalloc((void**)&e->samp_seen, (size_t)e->seen_words() * 4));
   WOQ_HIP(hipMemset(e->samp_seen, 0, (size_t)e->seen_words() * 4));
   e->owned = {e->hidden, e->qkv, e->attn, e->act, e->logits, e->token, e->pos, e->kcache, e->vcache, e->pf_last,
-              e->pf_logits, e->attn_part, e->attn_cnt, e->am_val, e->am_idx, e->tok_log, e->step_seq, e->samp_cfg, e->samp_seen};
+              e->pf_logits, e->attn_part, e->attn_cnt, e->am_val, e->am_idx, e->tok_log, e->step_seq, e->samp_cfg, e->samp_seen,
+              e->discarded};
   {  // XQ vectors (woq_xq.h) for the three GEMV inputs of a layer
     // WOQ_ENGINE_XQ=0 turns the XQ hand-off off (the fp32-activation kernels). Round 2 picked by shape — at hidden 8192
     // the second recombination per tile cost more than the staging it removed (Llama-2-70B 119-120 vs 125-127 tokens/s);

@@ -185,15 +185,18 @@ struct GuideState {
 //    vocabulary alone; `logits` is only read.
 //  - `guide` set as well: the pre-pass (score_adjust_kernel<true>) ends on adj[i] = -inf where
 //    table[state * vocab + i] == GUIDE_BANNED (the row offset in 64 bits). The state is only read.
-// pos_advance (the engine's chain): the Philox counter is *pos_advance, log[*pos_advance] = token (`log` nullable), then
-// *pos_advance += 1; else pos_fixed is only read. Sets the token's bit in `seen`; status |= 4 (every score NaN: token 0), 8
-// (more than 1024 candidates tied in).
+// pos_advance (the engine's chain): the Philox counter is *pos_advance + *discarded, log[*pos_advance] = token (`log`
+// nullable), then *pos_advance += 1; else pos_fixed is only read. `discarded` (nullable = 0): the positions a rolling KV
+// cache has dropped so far (woq_engine_kv_shift), which makes the counter the token's absolute index in the stream, with
+// uint32 wrap. Sets the token's bit in `seen`; status |= 4 (every score NaN: token 0), 8 (more than 1024 candidates
+// tied in).
 struct SampleTail {
   const float* logits = nullptr; int vocab = 0; uint32_t* seen = nullptr; const woq_sampler_config* cfg = nullptr;
   // the controls' memory, all four or none; a guide needs it
   uint32_t* counts = nullptr; const float* bias = nullptr; const woq_sampler_controls* ctl = nullptr; float* adj = nullptr;
   const GuideState* guide = nullptr;
   int32_t *token = nullptr, *pos_advance = nullptr, *log = nullptr; const int32_t* pos_fixed = nullptr; int* status = nullptr;
+  const int32_t* discarded = nullptr;
   // the probes' (null in the engine): u overrides the Philox uniform, philox_out receives the four Philox words,
   // kept_out (controls) the number of ids a sampled draw was over
   const float* u = nullptr; uint32_t *philox_out = nullptr, *kept_out = nullptr;
@@ -219,6 +222,18 @@ void launch_guide_advance(GuideState* guide_dev, int vocab, const int32_t* token
 void launch_guide_state_store(GuideState* guide_dev, int32_t state, hipStream_t st);  // stream-ordered, capturable
 // null when (n_states, start_state) describe a table the guide takes, else the "QBits: ..." reason
 const char* guide_problem(int n_states, int start_state);
+
+// ---- woq_kv_shift.hip: the rolling KV cache's shift ---------------------------------------------------------------
+// One sequence's caches kseq / vseq ([layers][max_ctx][kv_heads * D] in kv_dtype), in place: for p in
+// [n_keep + n_discard, n_cached) V[p - n_discard] = V[p] and K[p - n_discard] = K[p] rotated back by row n_discard of the
+// fp32 tables cs / sn ([max_ctx][D / 2]; the row is read only when rows move). Each thread owns columns and walks the
+// positions in ascending order, so the overlapping ranges need no order between workgroups. One launch, capturable.
+// Non-zero (message set) for a geometry outside 0 <= n_keep, 1 <= n_discard, n_keep + n_discard <= n_cached <= max_ctx.
+int launch_kv_shift(void* kseq, void* vseq, int kv_dtype, int layers, int kv_heads, int D, int max_ctx, const float* cs,
+                    const float* sn, int n_keep, int n_discard, int n_cached, hipStream_t st);
+// pos -= n_discard, discarded += n_discard (uint32 wrap), one thread, stream-ordered
+void launch_kv_shift_words(int32_t* pos, int32_t* discarded, int n_discard, hipStream_t st);
+void launch_i32_store(int32_t* dst, int32_t v, hipStream_t st);  // *dst = v, stream-ordered, capturable
 
 // ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
 // After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at

@@ -38,6 +38,20 @@ __device__ __forceinline__ h8 kv_load8(const void* base, size_t elem) {
     return r;
   }
 }
+// 8 consecutive cache elements -> 8 fp32, exact for every cache type (bf16 does not pass through fp16, whose range is
+// narrower): what a kernel that re-stores the values with kv_store8 reads (woq_kv_shift.hip)
+template <int KVD>
+__device__ __forceinline__ void kv_load8_f32(const void* base, size_t elem, float (&v)[8]) {
+  if constexpr (KVD == WOQ_BF16) {
+    const u32x4 raw = *(const u32x4*)((const uint16_t*)base + elem);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = bf16_bits_to_f32((uint16_t)(raw[j >> 1] >> (16 * (j & 1))));
+  } else {
+    const h8 r = kv_load8<KVD>(base, elem);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (float)r[j];
+  }
+}
 // 8 fp32 -> 8 consecutive cache elements (fp16 saturates at the format's largest finite value)
 template <int KVD>
 __device__ __forceinline__ void kv_store8(void* base, size_t elem, const float (&v)[8]) {

@@ -12,8 +12,10 @@
 //    (score descending, id ascending), w_i = expf(s_i - s_0), inclusive sums c_i, nucleus cut on the tail mass
 //    Z - c_(i-1) <= (1 - top_p) * Z (never the first), draw = first kept i with c_i > u * Z';
 //  - top_k = 0 (top_p = 1): softmax over the whole vocabulary, the same inverse-CDF rule over ids in ascending order.
-// u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 with counter (position, 0, 0, 0) and key (seed_lo, seed_hi): a draw
-// depends on (seed, position, logits) only, so eager steps and graphs of any burst size give the same tokens.
+// u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 with counter (position + discarded, 0, 0, 0) and key (seed_lo,
+// seed_hi); `discarded` = the positions a rolling KV cache has dropped (woq_engine_kv_shift; 0 otherwise), so the counter
+// is the token's absolute index in the stream and a draw depends on (seed, absolute position, logits) only: eager steps
+// and graphs of any burst size give the same tokens, and no u comes round again after a shift.
 //
 // Sampler controls (woq_sampler_controls: logit bias, presence / frequency penalty, min_p). With them installed a pre-pass
 // over the whole chip (score_adjust_kernel<false>, one id per thread) writes, for every id, the fp32 score
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     const float* __restrict__ u_in, int32_t* __restrict__ token, int32_t* __restrict__ pos_io,
     const int32_t* __restrict__ pos_ro, int32_t* __restrict__ log, uint32_t* __restrict__ philox_out,
     int* __restrict__ status, const woq_sampler_controls* __restrict__ ctlp, uint32_t* __restrict__ counts,
-    uint32_t* __restrict__ kept_out) {
+    uint32_t* __restrict__ kept_out, const int32_t* __restrict__ discarded) {
   __shared__ unsigned int hist[256];
   __shared__ unsigned long long cand[SAMPLE_MAX_CAND];
   __shared__ float cdf[SAMPLE_MAX_CAND];
@@ -169,7 +171,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   if (do_sample) {  // every thread computes the same uniform (uniform control flow, scalar-friendly)
     const int p = pos_io != nullptr ? pos_io[0] : (pos_ro != nullptr ? pos_ro[0] : 0);
     uint32_t x[4];
-    philox4x32_10((uint32_t)p, cfg.seed_lo, cfg.seed_hi, x);
+    // the counter is the token's absolute index in the stream: the position fed plus what a rolling cache has dropped
+    const uint32_t c0 = (uint32_t)p + (discarded != nullptr ? (uint32_t)discarded[0] : 0u);
+    philox4x32_10(c0, cfg.seed_lo, cfg.seed_hi, x);
     if (tid == 0 && philox_out != nullptr) philox_out[0] = x[0], philox_out[1] = x[1], philox_out[2] = x[2], philox_out[3] = x[3];
     u = u_in != nullptr ? u_in[0] : (float)(x[0] >> 8) * 5.9604644775390625e-08f;
   }
@@ -456,7 +460,7 @@ int launch_sample_tail(const SampleTail& t, hipStream_t st) {
                        (const uint32_t*)t.seen, (const uint32_t*)t.counts, t.bias, t.cfg, t.ctl, t.guide, t.adj);
   hipLaunchKernelGGL(ctl ? sample_kernel<true> : sample_kernel<false>, dim3(1), dim3(SAMPLE_THREADS), 0, st,
                      ctl ? (const float*)t.adj : t.logits, t.vocab, t.seen, t.cfg, t.u, t.token, t.pos_advance, t.pos_fixed,
-                     t.log, t.philox_out, t.status, t.ctl, t.counts, ctl ? t.kept_out : nullptr);
+                     t.log, t.philox_out, t.status, t.ctl, t.counts, ctl ? t.kept_out : nullptr, t.discarded);
   return 0;
 }
 
@@ -567,9 +571,9 @@ static int probe_tail_setup(const woq_sampler_config& cfg, const woq_sampler_con
 
 extern "C" {
 
-WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
-                             const float* u_or_null, const int32_t* pos_dev, int32_t* token_out, uint32_t* philox_out4,
-                             int* status, void* stream) {
+static int probe_sample_impl(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
+                             const float* u_or_null, const int32_t* pos_dev, const int32_t* discarded_dev,
+                             int32_t* token_out, uint32_t* philox_out4, int* status, void* stream) {
   WOQ_TRY
   WOQ_CHECK(logits && seen && cfg && pos_dev && token_out && vocab >= 1, "QBits: bad sampler probe arguments");
   const char* why = woq::sampler_config_problem(*cfg);
@@ -577,7 +581,7 @@ WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, con
   const hipStream_t st = (hipStream_t)stream;
   woq::SampleTail t;
   t.logits = logits, t.vocab = vocab, t.seen = seen, t.token = token_out, t.pos_fixed = pos_dev, t.status = status;
-  t.u = u_or_null, t.philox_out = philox_out4;
+  t.u = u_or_null, t.philox_out = philox_out4, t.discarded = discarded_dev;
   char* buf = nullptr;
   int rc = woq::probe_tail_setup(*cfg, nullptr, nullptr, nullptr, st, &t, &buf);
   if (rc) return rc;
@@ -586,6 +590,19 @@ WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, con
   if (rc) return rc;
   WOQ_HIP(hipGetLastError());
   WOQ_END
+}
+
+WOQ_API int woq_probe_sample(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
+                             const float* u_or_null, const int32_t* pos_dev, int32_t* token_out, uint32_t* philox_out4,
+                             int* status, void* stream) {
+  return probe_sample_impl(logits, vocab, seen, cfg, u_or_null, pos_dev, nullptr, token_out, philox_out4, status, stream);
+}
+
+WOQ_API int woq_probe_sample_stream(const float* logits, int vocab, uint32_t* seen, const woq_sampler_config* cfg,
+                                    const float* u_or_null, const int32_t* pos_dev, const int32_t* discarded_dev,
+                                    int32_t* token_out, uint32_t* philox_out4, int* status, void* stream) {
+  return probe_sample_impl(logits, vocab, seen, cfg, u_or_null, pos_dev, discarded_dev, token_out, philox_out4, status,
+                           stream);
 }
 
 WOQ_API int woq_probe_sample_controls(const float* logits, int vocab, uint32_t* seen, uint32_t* counts,

@@ -31,6 +31,13 @@ class GenerationConfig:
     # automaton the engine follows on the device (runtime.guide.TokenGuide); one of the two at most
     guided_choice: List[str] = None
     guided_regex: str = None
+    # rolling KV cache (StreamingLLM; Neural Speed's names, reference docs/streamingllm.md): with any of the three set a
+    # request may be longer than the engine's cache — the first n_keep positions stay as attention sinks, n_discard
+    # positions after them are dropped whenever ctx_size positions are cached (runtime.streaming.StreamingConfig:
+    # ctx_size None = the engine's max_ctx, n_keep None = 4, n_discard None / -1 = half of what is not kept)
+    ctx_size: int = None
+    n_keep: int = None
+    n_discard: int = None
     logprobs: int = None  # 0..20: fill BaseModel.last_logprobs with every emitted token's log-probability + alternatives
 
 

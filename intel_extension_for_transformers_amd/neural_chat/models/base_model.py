@@ -137,8 +137,13 @@ class BaseModel:
         if guide is None and config.bad_words_ids:  # words the guide's builder does not take: Hugging Face's loop
             engine_ok = False
 
+        # rolling KV cache (config.ctx_size / n_keep / n_discard): a request longer than the engine's cache stays on
+        # the engine, which drops old positions behind its attention sinks (runtime.streaming)
+        streaming = self._streaming(config)
+
         def pieces():
-            if engine_ok and self.engine is not None and n_in + config.max_new_tokens <= self.engine.cfg.max_ctx:
+            if engine_ok and self.engine is not None and (n_in + config.max_new_tokens <= self.engine.cfg.max_ctx
+                                                          or streaming is not None):
                 yield from self._engine_stream(ids[0].tolist(), config, n_out)
             elif getattr(config, "logprobs", None) is not None:
                 raise RuntimeError("QBits: logprobs need the fused engine")
@@ -239,6 +244,14 @@ class BaseModel:
                           else TokenGuide.from_regex(regex, cache["bytes"], [tok.eos_token_id]))
         return cache[key]
 
+    @staticmethod
+    def _streaming(config):
+        """the request's StreamingConfig (GenerationConfig.ctx_size / n_keep / n_discard), None when none is set"""
+        from ...runtime.streaming import streaming_from_keywords
+
+        return streaming_from_keywords(getattr(config, "ctx_size", None), getattr(config, "n_keep", None),
+                                       getattr(config, "n_discard", None))
+
     def _sampler_controls(self, config):
         """the request's sampling controls as `iter_sampled_auto` keywords (neutral values where the config has none)"""
         return dict(guide=self.request_guide(config), presence_penalty=getattr(config, "presence_penalty", 0.0) or 0.0,
@@ -258,7 +271,21 @@ class BaseModel:
         if getattr(config, "logprobs", None) is not None:  # the same greedy chain, with the step's records read back
             yield from self._engine_stream_logprobs(
                 eng.iter_generate(ids, config.max_new_tokens, burst=1, eos=() if eos is None else (eos,),
-                                  logprobs=config.logprobs), n_out)
+                                  logprobs=config.logprobs, streaming=self._streaming(config)), n_out)
+            return
+        if self._streaming(config) is not None:  # the greedy chain over a rolling cache: the engine's planned loop
+            out, shown = [], ""
+            for new in eng.iter_generate(ids, config.max_new_tokens, burst=1, eos=() if eos is None else (eos,),
+                                         streaming=self._streaming(config)):
+                for t in new:
+                    if eos is not None and t == eos:
+                        continue
+                    out.append(t)
+                    n_out[0] += 1
+                text = tok.decode(out, skip_special_tokens=True)
+                if not text.endswith("\ufffd"):  # hold back incomplete multi-byte pieces, like TextIteratorStreamer
+                    yield text[len(shown):]
+                    shown = text
             return
         for s0 in range(0, len(ids), 2048):
             eng.prefill(ids[s0:s0 + 2048], start_pos=s0, greedy=True)
@@ -291,13 +318,14 @@ class BaseModel:
                 iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
                                   do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
                                   top_p=config.top_p, repetition_penalty=config.repetition_penalty,
-                                  logprobs=config.logprobs, **self._sampler_controls(config)), n_out)
+                                  logprobs=config.logprobs, streaming=self._streaming(config),
+                                  **self._sampler_controls(config)), n_out)
             return
         out, shown = [], ""
         for new in iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
                                      do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
                                      top_p=config.top_p, repetition_penalty=config.repetition_penalty,
-                                     **self._sampler_controls(config)):
+                                     streaming=self._streaming(config), **self._sampler_controls(config)):
             for t in new:
                 if eos is not None and t == eos:
                     continue

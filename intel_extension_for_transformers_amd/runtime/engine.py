@@ -15,6 +15,7 @@ import torch
 
 from .. import _lib as L
 from .. import qbits
+from .streaming import StreamingConfig, plan_steps, plan_stream  # noqa: F401  (StreamingConfig: part of this module's API)
 
 
 def build_rope_tables(max_pos, head_dim, theta=10000.0, device="cuda"):
@@ -188,6 +189,34 @@ class WoqDecoderEngine:
         """int32 view [max_ctx + 1] of the engine's token log: slot p = the greedy token of the step that fed position
         p. After `replay(k)` from position p0 the k new tokens are token_log()[p0 : p0 + k] — one host read."""
         return _device_view(L.lib().woq_engine_token_log_ptr(self._h), (self.cfg.max_ctx + 1,), self.device, "<i4")
+
+    def kv_shift(self, n_keep, n_discard, n_cached, seq=0, move_pos=True):
+        """Rolling KV cache (woq_engine_kv_shift): drop positions [n_keep, n_keep + n_discard) of sequence `seq`, whose
+        cache holds `n_cached` rows, and move the later rows down in place, K rows rotated back by the angle of
+        `n_discard`. `move_pos` (sequence 0): the device position and the `discarded` word follow, so the burst issued
+        next feeds position n_cached - n_discard. Issued on the current stream, the one bursts run on: no
+        synchronisation, no read-back. Every shift re-rounds the moved K rows to the cache type."""
+        L.check(L.lib().woq_engine_kv_shift(self._h, int(seq), int(n_keep), int(n_discard), int(n_cached),
+                                            int(bool(move_pos)), L.stream_ptr()))
+
+    def discarded(self):
+        """Positions the rolling cache has dropped in the running request (one host synchronisation): the sampled
+        tail's Philox counter is position + discarded."""
+        return int(_device_view(L.lib().woq_engine_discarded_ptr(self._h), (1,), self.device, "<i4").item())
+
+    def set_discarded(self, value=0):
+        """discarded = value, stream-ordered (a request starts from 0)."""
+        L.check(L.lib().woq_engine_discarded_set(self._h, int(value), L.stream_ptr()))
+
+    def _request_geometry(self, n_prompt, max_new_tokens, streaming):
+        """(ctx_size, n_keep, n_discard) of a request with a rolling cache, (None, 0, 0) of one without, which has to
+        fit the cache as a whole."""
+        if streaming is not None:
+            return streaming.resolve(self.cfg.max_ctx, n_prompt)
+        if n_prompt + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
+            raise RuntimeError("QBits: prompt (%d) + max_new_tokens (%d) exceeds the engine's max_ctx (%d)"
+                               % (n_prompt, max_new_tokens, self.cfg.max_ctx))
+        return None, 0, 0
 
     def uses_xq(self):
         """True when the decode step's kernels hand activations over as XQ limb blocks (csrc/woq_xq.h)."""
@@ -648,15 +677,17 @@ class WoqDecoderEngine:
         lps, _ = self.score(ids, chunk=chunk)
         return math.exp(-math.fsum(lps) / len(lps))
 
-    def iter_generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=(), logprobs=None):
+    def iter_generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=(), logprobs=None, streaming=None):
         """Prompt pass + bursts of `burst` chained steps, yielding each burst's new tokens (the first one alone: it comes
         from the prompt pass's tail). With a sampler installed the prompt is marked in the history first and every
         token is the sampler's; without one this is the greedy chain. Stops after the first id in `eos` (kept).
         `logprobs` = N in 0..20: recording is on for this call (the previous state returns afterwards) and every burst
         is `(tokens, chosen_lps, top)` with `top` one list of N `(id, log-probability)` pairs per token, read back in
-        the burst's one synchronisation."""
+        the burst's one synchronisation. `streaming` = a StreamingConfig: the request runs over a rolling KV cache
+        (`plan_stream`: bursts clipped at ctx_size, a `kv_shift` whenever the cache is full) and may be longer than
+        the cache; tokens and records are read at cache positions."""
         if logprobs is None:
-            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, None)
+            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, None, streaming)
             return
         n_top = int(logprobs)
         if not 0 <= n_top <= self.LOGPROB_TOP:
@@ -664,7 +695,7 @@ class WoqDecoderEngine:
         before = self.logprobs_on
         self.set_logprobs(True)
         try:
-            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, n_top)
+            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, n_top, streaming)
         finally:
             self.set_logprobs(before)
 
@@ -678,12 +709,21 @@ class WoqDecoderEngine:
         top = [[(int(i), lp) for i, lp in zip(r[2:2 + n_top], r[2 + n_top:])] for r in packed]
         return toks, [r[1] for r in packed], top
 
-    def _iter_generate(self, prompt_ids, max_new_tokens, chunk, burst, eos, n_top):
+    def _iter_generate(self, prompt_ids, max_new_tokens, chunk, burst, eos, n_top, streaming=None):
         ids = [int(t) for t in prompt_ids]
+        geometry = self._request_geometry(len(ids), max_new_tokens, streaming)
+        if streaming is None:
+            yield from self._iter_planned(ids, max_new_tokens, chunk, burst, eos, n_top, geometry)
+            return
+        self.set_discarded(0)  # a request counts its dropped positions from 0; one without streaming always runs with 0
+        try:
+            yield from self._iter_planned(ids, max_new_tokens, chunk, burst, eos, n_top, geometry)
+        finally:
+            self.set_discarded(0)
+
+    def _iter_planned(self, ids, max_new_tokens, chunk, burst, eos, n_top, geometry):
         n = len(ids)
-        if n + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
-            raise RuntimeError("QBits: prompt (%d) + max_new_tokens (%d) exceeds the engine's max_ctx (%d)"
-                               % (n, max_new_tokens, self.cfg.max_ctx))
+        ctx, n_keep, n_discard = geometry
         if self.sampler_installed:
             self.mark_seen(ids, clear=True)
             if self.controls_installed:
@@ -697,7 +737,7 @@ class WoqDecoderEngine:
             # (and with recording on only the last chunk's tail leaves a record)
             self.prefill(ids[s0:s0 + chunk], start_pos=s0,
                          greedy=not (self.sampler_installed or n_top is not None) or s0 + chunk >= n)
-        self.tune_attn_for(n + max_new_tokens)
+        self.tune_attn_for(n + max_new_tokens if ctx is None else min(ctx, n + max_new_tokens))
         if max_new_tokens < 1:
             return
         eos = set(int(e) for e in eos)
@@ -709,19 +749,19 @@ class WoqDecoderEngine:
             yield [first], lps, top
         if first in eos:
             return
-        made = 1
-        if made < max_new_tokens:
+        if max_new_tokens > 1:
             self.prepare_decode(greedy=True)
         log = self.token_log()
-        while made < max_new_tokens:
-            k = min(int(burst), max_new_tokens - made)
-            p0 = n + made - 1  # position the next step feeds
+        for ev in plan_stream(n, max_new_tokens, ctx, n_keep, n_discard, burst):
+            if ev[0] == "shift":  # the cache is full: drop n_discard positions, the device position follows
+                self.kv_shift(n_keep, n_discard, ev[1])
+                continue
+            _, p0, k = ev  # p0 = cache position the next step feeds
             self.replay(k)
             if n_top is None:
                 new = log[p0:p0 + k].tolist()  # the burst's one host synchronisation
             else:
                 new, lps, top = self._records(p0, k, n_top)  # the same, with the records in the copy
-            made += k
             stop = next((j + 1 for j, t in enumerate(new) if t in eos), None)
             if n_top is None:
                 yield new[:stop]
@@ -730,38 +770,50 @@ class WoqDecoderEngine:
             if stop is not None:
                 return
 
-    def generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, sampler=None, logprobs=None):
+    def generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, sampler=None, logprobs=None, streaming=None):
         """Greedy decode: the prompt goes through the prefill pass in chunks of `chunk` tokens, then bursts of `burst`
         steps chained on the device (one host read of the token log per burst). `sampler` = a dict of `set_sampler`
         arguments: the same loop with the native sampler installed for this call (removed afterwards). `logprobs` = N
-        in 0..20: returns `(tokens, chosen_lps, top)` instead (see `iter_generate`)."""
+        in 0..20: returns `(tokens, chosen_lps, top)` instead (see `iter_generate`). `streaming` = a StreamingConfig: a
+        rolling KV cache, so prompt + max_new_tokens may exceed the cache (see `iter_generate`)."""
         if sampler is not None or logprobs is not None:
             if sampler is not None:
                 self.set_sampler(**sampler)
             try:
-                bursts = list(self.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, logprobs=logprobs))
+                bursts = list(self.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, logprobs=logprobs,
+                                                 streaming=streaming))
                 if logprobs is None:
                     return sum(bursts, [])
                 return tuple(sum((b[i] for b in bursts), []) for i in range(3))
             finally:
                 if sampler is not None:
                     self.clear_sampler()
-        out = []
         ids = [int(t) for t in prompt_ids]
-        if len(ids) + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
-            raise RuntimeError("QBits: prompt (%d) + max_new_tokens (%d) exceeds the engine's max_ctx (%d)"
-                               % (len(ids), max_new_tokens, self.cfg.max_ctx))
+        geometry = self._request_geometry(len(ids), max_new_tokens, streaming)
+        if streaming is None:
+            return self._generate_planned(ids, max_new_tokens, chunk, burst, geometry)
+        self.set_discarded(0)
+        try:
+            return self._generate_planned(ids, max_new_tokens, chunk, burst, geometry)
+        finally:
+            self.set_discarded(0)
+
+    def _generate_planned(self, ids, max_new_tokens, chunk, burst, geometry):
+        out = []
+        ctx, n_keep, n_discard = geometry
         for s0 in range(0, len(ids), chunk):
             self.prefill(ids[s0:s0 + chunk], start_pos=s0, greedy=True)
-        self.tune_attn_for(len(ids) + max_new_tokens)
+        self.tune_attn_for(len(ids) + max_new_tokens if ctx is None else min(ctx, len(ids) + max_new_tokens))
         if max_new_tokens < 1:
             return out
         out.append(int(self.token.item()))  # the prompt pass's token
         self.prepare_decode(greedy=True)
         log = self.token_log()
-        while len(out) < max_new_tokens:
-            k = min(int(burst), max_new_tokens - len(out))
-            p0 = len(ids) + len(out) - 1  # position the next step feeds
+        for ev in plan_stream(len(ids), max_new_tokens, ctx, n_keep, n_discard, burst):
+            if ev[0] == "shift":
+                self.kv_shift(n_keep, n_discard, ev[1])
+                continue
+            _, p0, k = ev  # p0 = cache position the next step feeds
             self.replay(k)
             out += log[p0:p0 + k].tolist()
         return out
@@ -878,24 +930,41 @@ class DeviceSampler:
         return idx[pick]
 
 
-def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, chunk=2048, logprobs=None):
+def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, chunk=2048, logprobs=None,
+                 streaming=None):
     """Prompt pass + decode steps with the next token chosen by `sampler` on the device (sampling and / or repetition
     penalty: the requests `generate`'s greedy chain does not cover). Every step is the engine's native step (logits
     only) followed by a dozen small torch kernels; nothing synchronises until `burst` tokens are read back (1 for a
     text stream). Yields each burst's new tokens; stops after the first id in `eos` (kept in the output, like HF).
     `logprobs` = N in 0..20: yields `(tokens, chosen_lps, top)` like `WoqDecoderEngine.iter_generate`, the records
-    computed here with `torch.log_softmax` + `torch.topk` over the raw logits (ties in whatever order topk leaves)."""
+    computed here with `torch.log_softmax` + `torch.topk` over the raw logits (ties in whatever order topk leaves).
+    `streaming` = a StreamingConfig: a rolling KV cache (`plan_stream`); the host sets the position of every step here,
+    so the shifts leave the device position alone."""
     ids = [int(t) for t in prompt_ids]
     n = len(ids)
-    if n + max_new_tokens > engine.cfg.max_ctx:
-        raise RuntimeError("QBits: prompt (%d) + max_new_tokens (%d) exceeds the engine's max_ctx (%d)"
-                           % (n, max_new_tokens, engine.cfg.max_ctx))
+    ctx, n_keep, n_discard = engine._request_geometry(n, max_new_tokens, streaming)
+    if streaming is None:
+        yield from _iter_sampled_planned(engine, ids, max_new_tokens, sampler, eos, burst, chunk, logprobs, (ctx, 0, 0))
+        return
+    engine.set_discarded(0)
+    try:
+        yield from _iter_sampled_planned(engine, ids, max_new_tokens, sampler, eos, burst, chunk, logprobs,
+                                         (ctx, n_keep, n_discard))
+    finally:
+        engine.set_discarded(0)
+
+
+def _iter_sampled_planned(engine, ids, max_new_tokens, sampler, eos, burst, chunk, logprobs, geometry):
+    n = len(ids)
+    ctx, n_keep, n_discard = geometry
+    # the cache position every step after the first token feeds, with the shifts between them
+    steps = plan_steps(plan_stream(n, max_new_tokens, ctx, n_keep, n_discard, burst))
     dev = engine.device
     hist = torch.empty(n + max_new_tokens, dtype=torch.int64, device=dev)
     hist[:n] = torch.tensor(ids, dtype=torch.int64, device=dev)
     for s0 in range(0, n, chunk):
         engine.prefill(ids[s0:s0 + chunk], start_pos=s0, greedy=False)
-    engine.tune_attn_for(n + max_new_tokens)
+    engine.tune_attn_for(n + max_new_tokens if ctx is None else min(ctx, n + max_new_tokens))
     eos = set(int(e) for e in eos)
     n_top = None
     if logprobs is not None:
@@ -903,12 +972,18 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
         if not 0 <= int(logprobs) <= L.LOGPROB_TOP:
             raise ValueError("`logprobs` is a count of alternatives in [0, %d]" % L.LOGPROB_TOP)
         rec = torch.empty(max(max_new_tokens, 1), 1 + 2 * n_top, dtype=torch.float64, device=dev)
-    done, made = False, 0
+    done, made, feed = False, 0, n  # feed = cache position of the next step (n + made until a shift)
     while not done and made < max_new_tokens:
         k = min(burst, max_new_tokens - made)
         for _ in range(k):
             if made > 0:
-                engine.step(greedy=False)  # logits of the token just chosen, at position n + made - 1
+                ev = next(steps)
+                if ev[0] == "shift":  # the cache is full: drop n_discard positions, then feed n_cached - n_discard
+                    engine.kv_shift(n_keep, n_discard, ev[1], move_pos=False)
+                    ev = next(steps)
+                    engine.pos.fill_(ev[1])
+                engine.step(greedy=False)  # logits of the token just chosen, at cache position ev[1]
+                feed = ev[1] + 1
             tok = sampler(engine.logits, hist[:n + made], hist[n:n + made])
             if n_top is not None:  # the raw distribution's view of the pick and of its best ids
                 lsm = torch.log_softmax(engine.logits, -1)
@@ -919,7 +994,7 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
                     rec[made, 1 + n_top:] = lsm[best]
             hist[n + made] = tok[0]
             engine.token.copy_(tok.to(torch.int32))
-            engine.pos.fill_(n + made)
+            engine.pos.fill_(feed)
             made += 1
         new = hist[n + made - k:n + made].tolist()  # the burst's one host synchronisation
         for j, t in enumerate(new):
@@ -946,7 +1021,7 @@ def request_seed():
 
 def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chunk=2048, do_sample=False,
                       temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, logprobs=None, presence_penalty=0.0,
-                      frequency_penalty=0.0, min_p=0.0, logit_bias=None, seed=None, guide=None):
+                      frequency_penalty=0.0, min_p=0.0, logit_bias=None, seed=None, guide=None, streaming=None):
     """A sampling / repetition-penalty request: on the native sampler (chained bursts, graph replays) when
     `native_sampler_supports` says so, else `iter_sampled` with a `DeviceSampler`. The sampler is removed after the
     request, so the next greedy request runs the untouched greedy path: in a `finally` of this generator, which runs when
@@ -954,7 +1029,8 @@ def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chun
     `close()` it. Installing and removing each drop the captured graphs, so a sampled request and the greedy request
     after it each pay one capture. `seed` = None: `request_seed()`; a given seed makes the request reproducible (on the
     torch sampler it seeds a device generator of the request's own). `guide` = a TokenGuide the request follows
-    (`set_guide`); it runs on the native sampler only, so a request it cannot take raises."""
+    (`set_guide`); it runs on the native sampler only, so a request it cannot take raises. `streaming` = a
+    StreamingConfig: the request runs over a rolling KV cache on either path."""
     pres, freq, min_p, bias = _controls(presence_penalty, frequency_penalty, min_p, logit_bias)
     opts = dict(do_sample=bool(do_sample), temperature=1.0 if temperature is None else temperature, top_k=top_k or 0,
                 top_p=1.0 if top_p is None else top_p,
@@ -971,14 +1047,14 @@ def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chun
             gen = torch.Generator(device=engine.device)
             gen.manual_seed(int(seed) & (2 ** 63 - 1))
         yield from iter_sampled(engine, prompt_ids, max_new_tokens, DeviceSampler(generator=gen, **opts), eos=eos,
-                                burst=burst, chunk=chunk, logprobs=logprobs)
+                                burst=burst, chunk=chunk, logprobs=logprobs, streaming=streaming)
         return
     try:  # (inside: the sampler may be installed already when the controls are refused)
         engine.set_sampler(seed=request_seed() if seed is None else int(seed), **opts)
         if guide is not None:
             engine.set_guide(guide)
         yield from engine.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, eos=eos,
-                                        logprobs=logprobs)
+                                        logprobs=logprobs, streaming=streaming)
     finally:
         engine.clear_sampler()
 

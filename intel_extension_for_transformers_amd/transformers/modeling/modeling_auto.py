@@ -337,6 +337,13 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     # constrained decoding: `guide=` (a runtime.guide.TokenGuide; this keyword is the engine's, HF has none) and
     # `bad_words_ids` (built into a guide below) make the engine's sampler follow a token automaton on the device
     guide = kwargs.pop("guide", None)
+    # rolling KV cache: Neural Speed's generate keywords (reference docs/streamingllm.md). With any of them given the
+    # request may outgrow the cache: no larger engine is built, the engine drops n_discard positions after its n_keep
+    # sinks whenever ctx_size positions are cached (runtime.streaming). HF's loop has no counterpart.
+    from ...runtime.streaming import plan_stream, streaming_from_keywords
+
+    streaming = streaming_from_keywords(kwargs.pop("ctx_size", None), kwargs.pop("n_keep", None),
+                                        kwargs.pop("n_discard", None))
     bad_words = opt("bad_words_ids")
     if guide is not None and bad_words:
         raise ValueError("`guide` together with `bad_words_ids` is not supported (it would need the product of the two "
@@ -373,6 +380,9 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
         if guide is not None:
             raise RuntimeError("QBits: `guide=` needs a request the native engine covers (one sequence, one beam, no "
                                "other logits processing); Hugging Face's loop has no token guide")
+        if streaming is not None:
+            raise RuntimeError("QBits: ctx_size / n_keep / n_discard need a request the native engine covers (one "
+                               "sequence, one beam, no other logits processing); Hugging Face's loop has no rolling cache")
         return hf_generate(inputs, generation_config=generation_config, **kwargs) if inputs is not None else \
             hf_generate(generation_config=generation_config, **kwargs)
     n_in = int(ids.shape[1])
@@ -380,15 +390,23 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     if max_new is None:
         max_new = max(int(opt("max_length", 20)) - n_in, 0)
     eng = getattr(self, "woq_engine", None)
-    if eng is None or eng.cfg.max_ctx < n_in + max_new:
+    # positions the engine has to hold: the whole request, or with a rolling cache its ctx_size (None: what the engine
+    # at hand holds, else the model's positions)
+    want = n_in + max_new
+    if streaming is not None:
+        model_ctx = getattr(self.config, "max_position_embeddings", None) or want
+        want = min(want, streaming.ctx_size or (eng.cfg.max_ctx if eng is not None else model_ctx))
+    if eng is None or eng.cfg.max_ctx < want:
         from ...runtime.engine import optimize_transformers
 
-        want = n_in + max_new
         ctx = int(min(max(want, 512), getattr(self.config, "max_position_embeddings", want) or want))
         no_guide = "QBits: `guide=` needs the native engine, which cannot serve this request (%s)"
+        no_stream = "QBits: ctx_size / n_keep / n_discard need the native engine, which cannot serve this request (%s)"
         if ctx < want:
             if guide is not None:
                 raise RuntimeError(no_guide % "longer than the model's positions")
+            if streaming is not None:
+                raise RuntimeError(no_stream % "ctx_size is longer than the model's positions")
             return hf_generate(inputs, generation_config=generation_config, **kwargs)
         try:
             eng = optimize_transformers(self, max_ctx=1 << (ctx - 1).bit_length())
@@ -396,7 +414,11 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
             self._woq_engine_off = True
             if guide is not None:
                 raise RuntimeError(no_guide % "not a model the engine takes")
+            if streaming is not None:
+                raise RuntimeError(no_stream % "not a model the engine takes")
             return hf_generate(inputs, generation_config=generation_config, **kwargs)
+    # (ctx_size, n_keep, n_discard), checked against this engine and prompt; (None, 0, 0) without a rolling cache
+    geometry = eng._request_geometry(n_in, max_new, streaming)
     if max_new < 1:
         return (ids, []) if want_latency else ids
     if bad_words:  # HF's NoBadWordsLogitsProcessor as a guide; what the engine cannot take keeps HF's loop
@@ -440,7 +462,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
                                      do_sample=opt("do_sample", False), temperature=opt("temperature", 1.0),
                                      top_k=opt("top_k", 0), top_p=opt("top_p", 1.0),
                                      repetition_penalty=opt("repetition_penalty", 1.0), min_p=min_p,
-                                     logit_bias=bias, guide=guide):
+                                     logit_bias=bias, guide=guide, streaming=streaming):
             out += new
             on_tokens(new)
         return out, latency
@@ -453,7 +475,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
         tic = time.time()
         for s0 in range(0, n_in, 2048):
             eng.prefill(prompt[s0:s0 + 2048], start_pos=s0, greedy=True)
-        eng.tune_attn_for(n_in + max_new)
+        eng.tune_attn_for(n_in + max_new if geometry[0] is None else min(geometry[0], n_in + max_new))
         if max_new > 1:
             eng.prepare_decode(greedy=True)  # a captured graph only in "graph" launch mode (engine.py LAUNCH)
         # Tokens are read back in bursts: the steps chain on the device and log their tokens (engine.token_log), so the
@@ -466,9 +488,13 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
         burst = 1 if streamer is not None else 16
         log = eng.token_log()
         done = out[0] in eos
-        while not done and len(out) < max_new:
-            k = min(burst, max_new - len(out))
-            p0 = n_in + len(out) - 1  # position the next step feeds
+        for ev in plan_stream(n_in, max_new, *geometry, burst=burst):
+            if done:
+                break
+            if ev[0] == "shift":  # rolling cache: it is full, drop n_discard positions (the device position follows)
+                eng.kv_shift(geometry[1], geometry[2], ev[1])
+                continue
+            _, p0, k = ev  # p0 = cache position the next step feeds
             tic = time.time()
             eng.replay(k)
             new = log[p0:p0 + k].tolist()  # one host synchronisation per burst
@@ -483,7 +509,18 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
                     break
         return out, latency
 
-    out, latency = run_once()
+    if streaming is None:
+        run_once_checked = run_once
+    else:
+        def run_once_checked():
+            """the request with the dropped-position count starting from 0, and back at 0 for whatever runs next"""
+            eng.set_discarded(0)
+            try:
+                return run_once()
+            finally:
+                eng.set_discarded(0)
+
+    out, latency = run_once_checked()
     # The decode step reports what it cannot raise from the device through a sticky status word; the host has just
     # synchronised on the last burst, so one more 4-byte read is free. bit 0: an attention workgroup of the fused
     # qkv + attention launch gave up waiting for its head's q / k / v (GPU preempted / shared / under a debugger for
@@ -509,7 +546,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
             raise RuntimeError("QBits: the decode engine reported status %d (bit 0: in-launch hand-off timed out, "
                                "bit 1: position beyond max_ctx)%s" % (st, "; tokens already streamed are not reliable"
                                                                      if streamer is not None else ""))
-        out, latency = run_once()  # same request, separate launches
+        out, latency = run_once_checked()  # same request, separate launches
         st = eng.status()
         if st != 0:
             eng.clear_status()
