@@ -88,6 +88,21 @@ WOQ_API int woq_quantize_to_packed_weight(const float* weight_dev, int transpose
                                           int weight_type, int scale_type, int compute_type, int asym,
                                           void* blob_dev, size_t blob_bytes, void* stream);
 
+/* the sequential sweep of GPTQ calibration over one block of B <= 128 consecutive input features, c0 <= j < c0 + B
+ * (no reference counterpart: the reference hands GPTQ to neural_compressor; algorithm and layout: csrc/woq_gptq.hip,
+ * DESIGN.md "GPTQ"). w fp32 [K,N] in working order (Linear.weight.T), modified in place; u fp32 [K,K] upper triangular
+ * with H^-1 = U^T U. Per column, j ascending: at a group start the RTN parameters (woq_quantize_to_packed_weight's rule;
+ * bits 2 | 3 | 4 | 8, sym or asym) of the current rows of the group go to scale fp32 [G,N] / zp int8 [G,N]; q int8 [K,N]
+ * row j = the code (scale, zp and q in the domain woq_repack_quantized_weight takes); err fp32 [B,N] row j - c0 =
+ * (w[j] - dequantised) / u[j][j]; the block's later rows take -err * u[j][k]; w[j] = the dequantised value. The rows
+ * after the block are the caller's: w[c0+B:] -= u[c0:c0+B, c0+B:]^T err. group <= 0 or > K = one group per column.
+ * params_given != 0 (static groups): scale / zp are read, not computed. col_group int32 [K] or NULL: the group of every
+ * working row (after an act-order permutation), NULL = j / group. Computing parameters needs c0 and group to be
+ * multiples of 32 (or one group per column). Asynchronous on `stream`; allocates nothing. */
+WOQ_API int woq_gptq_sweep(float* w_dev, const float* u_dev, int K, int N, int c0, int B, int group, int bits, int asym,
+                           int params_given, const int32_t* col_group_dev, int8_t* q_dev, float* scale_dev,
+                           int8_t* zp_dev, float* err_dev, void* stream);
+
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device
  * memory from the host. */

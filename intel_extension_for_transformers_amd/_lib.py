@@ -97,7 +97,7 @@ EXPORTS = [
     "woq_engine_set_logprobs", "woq_engine_logprobs", "woq_engine_logprob_ptr", "woq_engine_prefill_scored",
     "woq_engine_set_sampler_controls", "woq_engine_sampler_counts", "woq_engine_sampler_count_ptr",
     "woq_engine_set_guide", "woq_engine_guide_reset", "woq_engine_guide_state_ptr",
-    "woq_engine_kv_shift", "woq_engine_discarded_ptr", "woq_engine_discarded_set",
+    "woq_engine_kv_shift", "woq_engine_discarded_ptr", "woq_engine_discarded_set", "woq_gptq_sweep",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -140,6 +140,7 @@ def lib():
     L.woq_repack_quantized_weight.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, cs, vp]
     L.woq_quantize_to_packed_weight.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, cs, vp]
     L.woq_dequantize_packed_weight.argtypes = [vp, ctypes.POINTER(BlobHeader), vp, ci, vp]
+    L.woq_gptq_sweep.argtypes = [vp, vp] + [ci] * 8 + [vp] * 6
     L.woq_read_header.argtypes = [vp, ctypes.POINTER(BlobHeader), vp]
     L.woq_blob_extract.argtypes = [vp, ctypes.POINTER(BlobHeader), ci, vp, vp]
     L.woq_linear.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, vp, ci, ci, ci, vp]

@@ -15,7 +15,7 @@ from .. import _lib as L
 __all__ = [
     "woq_linear", "repack_quantized_weight", "quantize_to_packed_weight", "dequantize_packed_weight",
     "acquire_packed_weight_info", "get_packed_weight_size", "set_woq_workspace", "set_qbits_threads",
-    "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu",
+    "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
 ]
 
 
@@ -120,6 +120,31 @@ def quantize_to_packed_weight(fp32_weight, transpose, blocksize, compute_type, w
                                                   size, L.stream_ptr()))
     header_of(out)
     return out
+
+
+def gptq_sweep(w, u, c0, rows, group, bits, asym, q, scale, zp, err, params_given=False, col_group=None):
+    """The sequential sweep of GPTQ over one block of `rows` <= 128 input features starting at c0 (woq_gptq_sweep,
+    csrc/woq_gptq.hip; no reference counterpart). In place on the caller's device tensors: w fp32 [K, N] (working order,
+    Linear.weight.T), u fp32 [K, K] upper with H^-1 = U^T U, q int8 [K, N], scale fp32 [G, N], zp int8 [G, N] or None
+    (sym), err fp32 [>= rows, N]; q / scale / zp in the domain `repack_quantized_weight` takes. params_given: scale / zp
+    are read (static groups); col_group int32 [K]: the group of every working row, None = row // group."""
+    k, n = w.shape
+    g = k if group <= 0 or group > k else group
+    n_groups = (k + g - 1) // g
+
+    def ok(t, dtype, shape):
+        return t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape
+
+    if not (ok(w, torch.float32, (k, n)) and ok(u, torch.float32, (k, k)) and ok(q, torch.int8, (k, n))
+            and ok(scale, torch.float32, (n_groups, n)) and (zp is None or ok(zp, torch.int8, (n_groups, n)))
+            and err.is_cuda and err.dtype == torch.float32 and err.is_contiguous() and err.dim() == 2
+            and err.shape[0] >= rows and err.shape[1] == n
+            and (col_group is None or ok(col_group, torch.int32, (k,)))):
+        raise RuntimeError("QBits: gptq_sweep takes contiguous device tensors w fp32 [K,N], u fp32 [K,K], q int8 [K,N], "
+                           "scale fp32 [G,N], zp int8 [G,N], err fp32 [rows,N], col_group int32 [K]")
+    L.check(L.lib().woq_gptq_sweep(_ptr(w), _ptr(u), k, n, int(c0), int(rows), int(group), int(bits), int(bool(asym)),
+                                   int(bool(params_given)), _ptr(col_group), _ptr(q), _ptr(scale), _ptr(zp), _ptr(err),
+                                   L.stream_ptr()))
 
 
 def dequantize_packed_weight(compressed_weight, dequantize_weight, transpose, compute_type, weight_type, scale_type):

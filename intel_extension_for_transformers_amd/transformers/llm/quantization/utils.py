@@ -218,11 +218,24 @@ def _replace_linear(model, modules_to_not_convert, current_key_name, quantizatio
 
 def convert_to_quantized_model(model, config, device="cuda"):
     """reference utils.py:531-702 for the weight-only configs. RTN: quantise every eligible linear on the device.
-    AWQ / TEQ / GPTQ / AutoRound need calibration passes that the reference runs inside neural_compressor (external);
-    here those configs are accepted for PRE-QUANTISED checkpoints (optimum-format tensors already on the modules),
-    and raise for an fp model instead of silently falling back to RTN."""
+    GPTQ on an fp model: calibrate on the device (gptq.py gptq_quantize_model: Hessians from `config.calib_dataloader`
+    or `config.dataset=[texts]` + tokenizer, the sweep in csrc/woq_gptq.hip); the decoder blocks' linears are
+    quantised, lm_head and anything outside the blocks stays as it is. AWQ / TEQ / AutoRound need calibration passes
+    that the reference runs inside neural_compressor (external); those configs (and GPTQ) are accepted for
+    PRE-QUANTISED checkpoints (optimum-format tensors already on the modules), and raise for an fp model instead of
+    silently falling back to RTN."""
     method = getattr(config.quant_method, "value", config.quant_method)
     has_packed = any(_packed_checkpoint_linear(m) for m in model.modules())
+    if method == "gptq" and not has_packed:
+        from .gptq import gptq_quantize_model, validate_gptq_request
+
+        validate_gptq_request(model, config)  # NotImplementedError for what is not built, before a device is needed
+        if str(device) == "cpu":
+            raise RuntimeError("QBits: the MI355X backend has no CPU path (device must be 'cuda')")
+        orig_dtype = next((p.dtype for p in model.parameters()), torch.float32)
+        model = gptq_quantize_model(model, config, device=device)
+        model._woq_orig_dtype = orig_dtype
+        return model
     if method != "rtn" and not has_packed:
         raise NotImplementedError(
             "%s calibration is not part of the MI355X hot path (the reference delegates it to neural_compressor); "

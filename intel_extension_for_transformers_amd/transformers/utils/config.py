@@ -316,6 +316,14 @@ class GPTQConfig(ITREXQuantizationConfigMixin):
                ("static_groups", False), ("use_mse_search", False), ("true_sequential", False),
                ("layer_wise", False)) + _TAIL
 
+    def __init__(self, *args, **kwargs):
+        # calibration data for an fp model (transformers/llm/quantization/gptq.py): an iterable of input_ids tensors, or
+        # of dicts / tuples holding them; kept by reference (never copied or serialised). Without it, `dataset` may be
+        # a list of strings, tokenised with `tokenizer`.
+        loader = kwargs.pop("calib_dataloader", None)
+        super().__init__(*args, **kwargs)
+        self.calib_dataloader = loader
+
 
 class AwqConfig(ITREXQuantizationConfigMixin):
     """config.py:979-1049. `zero_point=True` means asym."""
