@@ -401,6 +401,23 @@ WOQ_API void* woq_engine_logprob_ptr(woq_engine* e, int which);
 WOQ_API int   woq_engine_kv_shift(woq_engine* e, int seq, int n_keep, int n_discard, int n_cached, int move_pos, void* stream);
 WOQ_API void* woq_engine_discarded_ptr(woq_engine* e);                    /* int32[1] on the device */
 WOQ_API int   woq_engine_discarded_set(woq_engine* e, int value, void* stream);
+/* ---- per-layer extras of Llama-class variants: Qwen2's q / k / v biases, Qwen3's q / k norm (new entry point only,
+ * WOQ_ABI_VERSION stays 4, no struct changes) ----------------------------------------------------------------------------
+ * optional per-layer extras of Llama-class variants; every pointer may be NULL (= absent); fp32 on the device;
+ * the engine keeps the pointers (the caller owns the memory), like woq_engine_set_layer:
+ *   qkv_bias [(heads + 2 kv_heads) * head_dim]  added to the fused q|k|v projection (Qwen2)
+ *   q_norm, k_norm [head_dim]                   RMSNorm over head_dim of every q / k head BEFORE RoPE,
+ *                                               eps = cfg.rms_eps (Qwen3); both or neither
+ * The bias is added in the projection's epilogue, after the input RMSNorm's factor, in the decode step (all three
+ * forms: fused qkv + attention launch, XQ GEMV, fp32-activation GEMV) and in the prompt pass's GEMM. The norm is
+ * x * rsqrt(mean(x^2) + eps) * w in fp32 (HF Qwen3RMSNorm), inside the decode attention (per-query-head and fused forms;
+ * a layer with a norm never takes the grouped form) and the prompt pass's RoPE / append kernel, where q and k are
+ * rounded once, after norm and rotation. The call comes after woq_engine_set_layer for that layer (which clears the
+ * layer's extras); a call that changes which extras are present, or their pointers, drops captured graphs. Fails with a
+ * "QBits:" message on a tensor-parallel engine (tp_size > 1, a communicator or an all-reduce callback), for a bias on
+ * fp8-weight layers, for only one of q_norm / k_norm, and for a norm with head_dim not a multiple of 16. */
+WOQ_API int woq_engine_set_layer_extras(woq_engine* e, int layer, const float* qkv_bias_dev,
+                                        const float* q_norm_dev, const float* k_norm_dev);
 /* tensor-parallel seam: when set, the engine calls `fn(user, buf_dev, count_f32, stream)` after
  * o_proj and after down_proj (row-parallel partial sums -> sum over ranks). The Python host binds it
  * to RCCL via torch.distributed. NULL = single GPU. */

@@ -96,6 +96,18 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
                                   const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
                                   int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
                                   float* out, void* stream);
+/* woq_probe_rope_append / woq_probe_attn_decode with the per-head q / k RMSNorm of woq_engine_set_layer_extras in front
+ * of the rotation (tests/test_gpu_qknorm_kernels.py): q_norm_dev / k_norm_dev fp32 [head_dim], both required; the decode
+ * probe runs the per-query-head form (the grouped form does not carry the norm). */
+WOQ_API int woq_probe_rope_append_qknorm(void* qkv, int n_seq, int T, int start, int heads, int kv_heads, int head_dim,
+                                         const float* cos_dev, const float* sin_dev, void* kcache, void* vcache,
+                                         int kv_dtype, size_t seq_stride_elems, const float* q_norm_dev,
+                                         const float* k_norm_dev, float eps, void* stream);
+WOQ_API int woq_probe_attn_decode_qknorm(const float* qkv, void* kcache, void* vcache, int kv_dtype,
+                                         const int32_t* pos_dev, const float* cos_dev, const float* sin_dev, int heads,
+                                         int kv_heads, int head_dim, int max_ctx, int window, int splits, int merge,
+                                         const float* q_norm_dev, const float* k_norm_dev, float eps, float* out,
+                                         void* stream);
 /* What plan_attn_decode (csrc/woq_attn_decode.hip) decides for one decode step's attention, without touching a device
  * (tests/test_attn_plan_cpu.py). in23 = {heads, kv_heads, head_dim, kv_dtype, max_ctx, window | splits, grouped, fold,
  * chunk_fixed, fuse_attn, fuse_sliced, grouped_a2a | xq step, granule buffers present, layers, slots (resident

@@ -98,6 +98,7 @@ EXPORTS = [
     "woq_engine_set_sampler_controls", "woq_engine_sampler_counts", "woq_engine_sampler_count_ptr",
     "woq_engine_set_guide", "woq_engine_guide_reset", "woq_engine_guide_state_ptr",
     "woq_engine_kv_shift", "woq_engine_discarded_ptr", "woq_engine_discarded_set", "woq_gptq_sweep",
+    "woq_engine_set_layer_extras",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -108,6 +109,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_xq_from_f32", "woq_probe_gemv_xq", "woq_probe_lm_head", "woq_probe_greedy_tail", "woq_probe_embed",
     "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16", "woq_probe_sample_controls",
     "woq_probe_attn_decode_plan", "woq_engine_attn_plan", "woq_probe_guide", "woq_probe_sample_stream",
+    "woq_probe_rope_append_qknorm", "woq_probe_attn_decode_qknorm",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -153,6 +155,7 @@ def lib():
     L.woq_engine_destroy.restype = None
     L.woq_engine_set_layer.argtypes = [vp, ci, ctypes.POINTER(LayerWeights)]
     L.woq_engine_set_head.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp]
+    L.woq_engine_set_layer_extras.argtypes = [vp, ci, vp, vp, vp]
     for f in ("woq_engine_token_ptr", "woq_engine_pos_ptr", "woq_engine_logits_ptr", "woq_engine_hidden_ptr"):
         getattr(L, f).restype = vp
         getattr(L, f).argtypes = [vp]
@@ -191,6 +194,8 @@ def lib():
     L.woq_probe_rope_append.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, cs, vp]
     L.woq_probe_attn_prefill.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, cs, vp, ci, vp]
     L.woq_probe_attn_decode.argtypes = [vp, vp, vp, ci, vp, vp, vp] + [ci] * 9 + [vp, vp]
+    L.woq_probe_rope_append_qknorm.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, cs, vp, vp, cf, vp]
+    L.woq_probe_attn_decode_qknorm.argtypes = [vp, vp, vp, ci, vp, vp, vp] + [ci] * 7 + [vp, vp, cf, vp, vp]
     L.woq_probe_attn_decode_plan.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_longlong)]
     L.woq_engine_attn_plan.argtypes = [vp, ci, ci, ctypes.POINTER(ctypes.c_longlong)]
     L.woq_comm_create.argtypes = [ci, ci, cs, ctypes.POINTER(vp)]
@@ -295,6 +300,27 @@ def probe_attn_decode(qkv, kcache, vcache, kv_dtype, pos, cos, sin, heads, kv_he
     rc = lib().woq_probe_attn_decode(_ptr(qkv), _ptr(kcache), _ptr(vcache), kv_dtype, _ptr(pos), _ptr(cos), _ptr(sin),
                                      heads, kv_heads, head_dim, max_ctx, window, splits, grouped, merge, chunk_fixed,
                                      _ptr(out), stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def probe_rope_append_qknorm(qkv, n_seq, T, start, heads, kv_heads, head_dim, cos, sin, kcache, vcache, kv_dtype,
+                             seq_stride, q_norm, k_norm, eps):
+    """rope_append with the per-head q / k RMSNorm in front of the rotation (woq_probe_rope_append_qknorm); q_norm /
+    k_norm: fp32 [head_dim] on the device."""
+    rc = lib().woq_probe_rope_append_qknorm(_ptr(qkv), n_seq, T, start, heads, kv_heads, head_dim, _ptr(cos), _ptr(sin),
+                                            _ptr(kcache), _ptr(vcache), kv_dtype, seq_stride, _ptr(q_norm),
+                                            _ptr(k_norm), eps, stream_ptr())
+    if rc != 0:
+        raise RuntimeError(lib().woq_last_error().decode())
+
+
+def probe_attn_decode_qknorm(qkv, kcache, vcache, kv_dtype, pos, cos, sin, heads, kv_heads, head_dim, max_ctx, window,
+                             splits, merge, q_norm, k_norm, eps, out):
+    """the per-query-head decode attention with the q / k RMSNorm (woq_probe_attn_decode_qknorm)."""
+    rc = lib().woq_probe_attn_decode_qknorm(_ptr(qkv), _ptr(kcache), _ptr(vcache), kv_dtype, _ptr(pos), _ptr(cos),
+                                            _ptr(sin), heads, kv_heads, head_dim, max_ctx, window, splits, merge,
+                                            _ptr(q_norm), _ptr(k_norm), eps, _ptr(out), stream_ptr())
     if rc != 0:
         raise RuntimeError(lib().woq_last_error().decode())
 

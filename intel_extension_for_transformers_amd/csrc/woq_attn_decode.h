@@ -58,17 +58,33 @@ struct AttnGranule {
 constexpr int ATTN_A2A_MAX_SLICES = 16;
 constexpr int FUSED_TPW = 8;  // K tiles per wave of the fused launch's strips (four waves: the qkv blob has 32 K tiles)
 
+// QKN (Qwen3): every q head and the new k head go through an RMSNorm over HD BEFORE the rotation, in fp32 like HF's
+// Qwen3RMSNorm — x * rsqrt(mean(x^2) + eps) * w. The lanes < half hold elements d and d + half: they form a^2 + b^2, the
+// wave sums it (other lanes add 0) and every lane scales its pair by r * w. One order for both sources (granules and
+// plain), so the fused and the separate launches stay bit-identical. The instantiations without QKN compile as before.
+struct AttnQkNorm {
+  const float* q;  // fp32 [HD] weights of the q heads' norm
+  const float* k;  // fp32 [HD] weights of the k heads' norm
+  float eps;
+};
+template <int HD>
+__device__ __forceinline__ float attn_qk_rnorm(float a, float b, float eps) {
+  const float ss = wave_sum_dpp(fmaf(a, a, b * b));
+  return 1.0f / sqrtf(fmaf(ss, 1.0f / (float)HD, eps));
+}
+
 // One 256-thread workgroup runs the body (the standalone and the fused launches): the two meeting points are workgroup
 // barriers, the result leaves as fp32 in `out` (+ its XQ block in `xo`, published through `pub` when an o_proj
 // workgroup of the same launch may be waiting for it).
 // `h`: query head of this workgroup, `slice` / `n_slices`: its part of the cached positions (SPLIT), `sm`: LDS base
-template <typename KV, int HD, bool SPLIT, typename SRC>
+template <typename KV, int HD, bool SPLIT, typename SRC, bool QKN = false>
 __device__ __forceinline__ void attn_decode_body(float* sm, int h, int slice, int n_slices, const SRC& src,
                                                  KV* __restrict__ kcache, KV* __restrict__ vcache,
                                                  const int32_t* __restrict__ pos_p, const float* __restrict__ cs,
                                                  const float* __restrict__ sn, int heads, int kv_heads, int window,
                                                  int spw, float* __restrict__ out, const XqPtrs& xo,
-                                                 const XqPub& pub = XqPub{nullptr, 0u}) {
+                                                 const XqPub& pub = XqPub{nullptr, 0u},
+                                                 const AttnQkNorm& qn = AttnQkNorm{nullptr, nullptr, 0.f}) {
   // value `idx` of the attention output; called by whole 16-lane rows (idx & 15 == lane & 15)
   auto put = [=](float v, int idx) {
     out[idx] = v;
@@ -162,7 +178,16 @@ __device__ __forceinline__ void attn_decode_body(float* sm, int h, int slice, in
   float s_new = 0.f;
   float ra = 0.f, rb = 0.f, rc = 0.f, rs = 0.f;  // rotated, pre-scaled q halves and the cos / sin of this lane (lanes < half)
   const bool q_lane = lane < half && (!SRC::granules || wid == 0);
+  float qn_a = 0.f, qn_b = 0.f, qw_a = 0.f, qw_b = 0.f;  // QKN: this lane's un-normalised q pair and its norm weights
+  // (explicit fused multiply-adds: hipcc contracts a * b + c * d by context, and the granule and plain sources of this
+  // body are different contexts — the fused launch and the separate launches must stay bit-identical)
+  auto rotate_q = [&](float qa, float qb) {
+    ra = fmaf(qa, rc, -(qb * rs)) * scale, rb = fmaf(qb, rc, qa * rs) * scale;
+    qw[lane] = ra;
+    qw[lane + half] = rb;
+  };
   if (q_lane) {
+    if constexpr (QKN) qw_a = qn.q[lane], qw_b = qn.q[lane + half];
     rc = cs[(size_t)apos * half + lane], rs = sn[(size_t)apos * half + lane];
     const size_t oq = (size_t)h * HD + lane;
     float qa, qb;
@@ -183,18 +208,41 @@ __device__ __forceinline__ void attn_decode_body(float* sm, int h, int slice, in
     } else {
       qa = src.qkv[oq], qb = src.qkv[oq + half];
     }
-    // (explicit fused multiply-adds: hipcc contracts a * b + c * d by context, and the granule and plain sources of this
-    // body are different contexts — the fused launch and the separate launches must stay bit-identical)
-    ra = fmaf(qa, rc, -(qb * rs)) * scale, rb = fmaf(qb, rc, qa * rs) * scale;
-    qw[lane] = ra;
-    qw[lane + half] = rb;
+    if constexpr (QKN)
+      qn_a = qa, qn_b = qb;  // normalised behind the branch: the sum of squares is the whole wave's
+    else
+      rotate_q(qa, qb);
+  }
+  if constexpr (QKN) {
+    if (!SRC::granules || wid == 0) {  // (wave-uniform; lanes that hold no q add 0)
+      const float r = attn_qk_rnorm<HD>(qn_a, qn_b, qn.eps);
+      if (q_lane) rotate_q(qn_a * (r * qw_a), qn_b * (r * qw_b));
+    }
   }
   // k / v of the new token (wave 0 of the workgroup that holds the new position): rotate k, round both through the cache
   // dtype, append (the first query head of each kv group), score against the rotated q still in this lane's registers
   auto new_position = [&]() {
+    // rotate, round, score and append this lane's k / v pair
+    auto finish = [&](float ka, float kb, float va, float vb) {
+      const KV ka_r = (KV)fmaf(ka, rc, -(kb * rs)), kb_r = (KV)fmaf(kb, rc, ka * rs);
+      const KV va_r = (KV)va, vb_r = (KV)vb;
+      s_new = fmaf(ra, (float)ka_r, rb * (float)kb_r);
+      vn[lane] = (float)va_r;
+      vn[lane + half] = (float)vb_r;
+      if (h % rep == 0) {
+        KV* kd = kcache + ((size_t)npos_abs * kv_heads + kh) * HD;
+        KV* vd = vcache + ((size_t)npos_abs * kv_heads + kh) * HD;
+        kd[lane] = ka_r;
+        kd[lane + half] = kb_r;
+        vd[lane] = va_r;
+        vd[lane + half] = vb_r;
+      }
+    };
+    float kn_a = 0.f, kn_b = 0.f, vn_a = 0.f, vn_b = 0.f, kw_a = 0.f, kw_b = 0.f;  // QKN: the pair, held over the wave's sum
     if (lane < half) {
       const size_t ok = (size_t)(heads + kh) * HD + lane, ov = (size_t)(heads + kv_heads + kh) * HD + lane;
       float ka, kb, va, vb;
+      if constexpr (QKN) kw_a = qn.k[lane], kw_b = qn.k[lane + half];
       if constexpr (SRC::granules) {
         const unsigned long long t0 = wall_clock64();
         for (;;) {
@@ -217,19 +265,14 @@ __device__ __forceinline__ void attn_decode_body(float* sm, int h, int slice, in
         ka = src.qkv[ok], kb = src.qkv[ok + half];
         va = src.qkv[ov], vb = src.qkv[ov + half];
       }
-      const KV ka_r = (KV)fmaf(ka, rc, -(kb * rs)), kb_r = (KV)fmaf(kb, rc, ka * rs);
-      const KV va_r = (KV)va, vb_r = (KV)vb;
-      s_new = fmaf(ra, (float)ka_r, rb * (float)kb_r);
-      vn[lane] = (float)va_r;
-      vn[lane + half] = (float)vb_r;
-      if (h % rep == 0) {
-        KV* kd = kcache + ((size_t)npos_abs * kv_heads + kh) * HD;
-        KV* vd = vcache + ((size_t)npos_abs * kv_heads + kh) * HD;
-        kd[lane] = ka_r;
-        kd[lane + half] = kb_r;
-        vd[lane] = va_r;
-        vd[lane + half] = vb_r;
-      }
+      if constexpr (QKN)
+        kn_a = ka, kn_b = kb, vn_a = va, vn_b = vb;
+      else
+        finish(ka, kb, va, vb);
+    }
+    if constexpr (QKN) {  // (wave 0, all of it: new_position is called wave-uniformly)
+      const float r = attn_qk_rnorm<HD>(kn_a, kn_b, qn.eps);
+      if (lane < half) finish(kn_a * (r * kw_a), kn_b * (r * kw_b), vn_a, vn_b);
     }
     s_new = wave_sum_dpp(s_new);
     if (lane == 0) ml[8] = s_new;

@@ -3,7 +3,7 @@
 //
 // Reference path replaced: stock HF eager attention over the KV cache run by PyTorch CPU ops.
 // Kernels: attn_decode_kernel (one workgroup per query head and context slice: the body of woq_attn_decode.h on plain
-// fp32 inputs), attn_combine_kernel (the slices' merge as a launch of its own) and attn_decode_mfma_kernel (grouped-query
+// fp32 inputs; attn_decode_qkn_kernel: the same with a per-head q / k RMSNorm), attn_combine_kernel (the slices' merge as a launch of its own) and attn_decode_mfma_kernel (grouped-query
 // models at long contexts: one matrix-core workgroup per kv head and slice). The fused form — the same body behind the
 // qkv GEMV's strips — is woq_gemv_attn.hip; the in-launch merges are woq_attn_merge.h.
 // plan_attn_decode (host side, below) decides once per call which form runs, how its slices merge and their geometry;
@@ -39,6 +39,26 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restric
   attn_decode_body<KV, HD, SPLIT>(sm, h, (int)blockIdx.y, (int)gridDim.y, AttnPlain{qkv}, kcache, vcache, pos_p, cs,
                                   sn, heads, kv_heads, window, spw, out, xo);
   if constexpr (SPLIT) {  // `out` = the partial buffer; the head's last slice workgroup merges (woq_attn_merge.h)
+    if (mg.counter != nullptr) attn_slices_merge<HD, 1>(out, heads, h, 1, (int)gridDim.y, mg.counter + h, mg, sm);
+  }
+}
+
+// the same launch with the per-head q / k RMSNorm in front of the rotation (woq_attn_decode.h QKN): a kernel of its own,
+// so that the one above keeps its arguments and its code
+template <typename KV, int HD, bool SPLIT>
+__global__ __launch_bounds__(256) void attn_decode_qkn_kernel(const float* __restrict__ qkv, KV* __restrict__ kcache,
+                                                              KV* __restrict__ vcache, const int32_t* __restrict__ pos_p,
+                                                              const float* __restrict__ cs, const float* __restrict__ sn,
+                                                              int hk, int window, int spw, float* __restrict__ out,
+                                                              XqPtrs xo, AttnMerge mg, AttnQkNorm qn) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int heads = hk & 0xffff, kv_heads = hk >> 16;
+  const int bx = (int)blockIdx.x;
+  const int h = (heads & 7) == 0 ? (bx & 7) * (heads >> 3) + (bx >> 3) : bx;
+  attn_decode_body<KV, HD, SPLIT, AttnPlain, true>(sm, h, (int)blockIdx.y, (int)gridDim.y, AttnPlain{qkv}, kcache, vcache,
+                                                   pos_p, cs, sn, heads, kv_heads, window, spw, out, xo,
+                                                   XqPub{nullptr, 0u}, qn);
+  if constexpr (SPLIT) {
     if (mg.counter != nullptr) attn_slices_merge<HD, 1>(out, heads, h, 1, (int)gridDim.y, mg.counter + h, mg, sm);
   }
 }
@@ -534,7 +554,8 @@ AttnDecodePlan plan_attn_decode(const AttnShape& s, const AttnOptions& o, const 
   // GROUPED: only where it applies — sliced, head_dim 128, 2 / 4 / 8 query heads per kv head, an fp16 or fp8 cache,
   // counts that fit the packed argument dword — anything else keeps the per-query-head kernels
   const int rep = s.kv_heads > 0 ? s.heads / s.kv_heads : 0;
-  if (o.grouped && s.head_dim == 128 && p.slices > 1 && s.heads <= 255 && s.kv_heads <= 255 &&
+  // (a layer with a q / k norm: the grouped kernel does not carry it — such layers keep the per-query-head kernels)
+  if (o.grouped && !f.qk_norm && s.head_dim == 128 && p.slices > 1 && s.heads <= 255 && s.kv_heads <= 255 &&
       o.chunk_fixed / 32 <= 65535 && attn_mfma_kernel_for(s.kv_dtype, rep) != nullptr) {
     p.form = ATTN_GROUPED;
     p.chunk_fixed = o.chunk_fixed % DST != 0 ? 0 : o.chunk_fixed;
@@ -564,6 +585,14 @@ static int launch_attn_per_head(const AttnDecodePlan& p, const AttnDecodeIO& io,
   // sliced: the kernel writes partials, and the merge (its last workgroups, or the combine launch) the output and its XQ form
   const AttnMerge mg = SPLIT ? AttnMerge{p.merge == ATTN_MERGE_COUNTER ? io.counters : nullptr, io.out, io.xo}
                              : AttnMerge{nullptr, nullptr, no_xq};
+  if (io.q_norm != nullptr) {
+    constexpr auto kn = attn_decode_qkn_kernel<KV, HD, SPLIT>;
+    if (const int rc = allow_dynamic_lds<kn>(160 * 1024)) return rc;
+    hipLaunchKernelGGL(kn, dim3(p.grid_x, p.grid_y), dim3(256), p.lds, st, io.qkv, (KV*)io.kcache, (KV*)io.vcache, io.pos,
+                       io.cs, io.sn, p.shape.heads | (p.shape.kv_heads << 16), p.shape.window, p.spw,
+                       SPLIT ? io.part : io.out, SPLIT ? no_xq : io.xo, mg, AttnQkNorm{io.q_norm, io.k_norm, io.qk_eps});
+    return 0;
+  }
   hipLaunchKernelGGL(k, dim3(p.grid_x, p.grid_y), dim3(256), p.lds, st, io.qkv, (KV*)io.kcache, (KV*)io.vcache, io.pos,
                      io.cs, io.sn, p.shape.heads | (p.shape.kv_heads << 16), p.shape.window, p.spw,
                      SPLIT ? io.part : io.out, SPLIT ? no_xq : io.xo, mg);
@@ -580,6 +609,9 @@ int launch_attn_decode(const AttnDecodePlan& p, const AttnDecodeIO& io, hipStrea
   if (p.error != nullptr) return woq::fail(p.error);
   if (p.form == ATTN_FUSED) return woq::fail("QBits: a fused attention plan runs inside the qkv launch");
   const AttnShape& s = p.shape;
+  if ((io.q_norm != nullptr) != (io.k_norm != nullptr)) return woq::fail("QBits: q_norm and k_norm come together");
+  if (io.q_norm != nullptr && p.form == ATTN_GROUPED)
+    return woq::fail("QBits: the grouped decode attention does not carry a q / k norm");
   if (p.form == ATTN_GROUPED) {
     AttnMerge mg{p.merge == ATTN_MERGE_COUNTER ? io.counters : nullptr, io.out, io.xo};
     if (p.merge == ATTN_MERGE_A2A) mg.part_g = io.part_g, mg.seq = io.seq, mg.layer = io.layer, mg.status = io.status;
@@ -654,11 +686,11 @@ WOQ_API int woq_probe_attn_decode_plan(const int* in23, long long* out11) {
   WOQ_END
 }
 
-// test entry point (include/woq_hip_experimental.h): the engine's separate decode-attention launches on their own
-WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos_dev,
-                                  const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
-                                  int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
-                                  float* out, void* stream) {
+// the engine's separate decode-attention launches on their own (both probes below)
+static int probe_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos_dev,
+                             const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
+                             int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed, float* out,
+                             void* stream, const float* q_norm, const float* k_norm, float qk_eps) {
   WOQ_TRY
   WOQ_CHECK(heads > 0 && kv_heads > 0 && heads % kv_heads == 0 && max_ctx > 0 && window >= 0 && splits >= 1,
             "QBits: bad attention shape");
@@ -667,7 +699,7 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
   AttnOptions o;
   o.splits = splits, o.grouped = grouped != 0, o.fold = merge != 0, o.chunk_fixed = chunk_fixed;
   const AttnDecodePlan plan = plan_attn_decode(AttnShape{heads, kv_heads, head_dim, kv_dtype, max_ctx, window}, o,
-                                               AttnFacts{false, false, 0, nullptr, 0});
+                                               AttnFacts{false, false, 0, nullptr, 0, q_norm != nullptr});
   if (plan.error != nullptr) return woq::fail(plan.error);
   // the partial buffer of woq_attn_merge.h (o [heads][64][D], then ml [heads][64][2]) and one counter per head
   const size_t part_bytes = (size_t)heads * ATTN_MAX_SLICES * (head_dim + 2) * sizeof(float);
@@ -683,7 +715,7 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
     }
   }
   const AttnDecodeIO io{qkv, kcache, vcache, pos_dev, cos_dev, sin_dev, out, XqPtrs{nullptr, nullptr, nullptr},
-                        part, counters, nullptr, nullptr, 0, nullptr};
+                        part, counters, nullptr, nullptr, 0, nullptr, q_norm, k_norm, qk_eps};
   const int rc = launch_attn_decode(plan, io, st);
   const hipError_t le = hipGetLastError();
   if (counters) hipFreeAsync(counters, st);
@@ -691,6 +723,24 @@ WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, 
   if (rc) return rc;
   WOQ_HIP(le);
   WOQ_END
+}
+
+// test entry points (include/woq_hip_experimental.h)
+WOQ_API int woq_probe_attn_decode(const float* qkv, void* kcache, void* vcache, int kv_dtype, const int32_t* pos_dev,
+                                  const float* cos_dev, const float* sin_dev, int heads, int kv_heads, int head_dim,
+                                  int max_ctx, int window, int splits, int grouped, int merge, int chunk_fixed,
+                                  float* out, void* stream) {
+  return probe_attn_decode(qkv, kcache, vcache, kv_dtype, pos_dev, cos_dev, sin_dev, heads, kv_heads, head_dim, max_ctx,
+                           window, splits, grouped, merge, chunk_fixed, out, stream, nullptr, nullptr, 0.f);
+}
+WOQ_API int woq_probe_attn_decode_qknorm(const float* qkv, void* kcache, void* vcache, int kv_dtype,
+                                         const int32_t* pos_dev, const float* cos_dev, const float* sin_dev, int heads,
+                                         int kv_heads, int head_dim, int max_ctx, int window, int splits, int merge,
+                                         const float* q_norm_dev, const float* k_norm_dev, float eps, float* out,
+                                         void* stream) {
+  if (q_norm_dev == nullptr || k_norm_dev == nullptr) return woq::fail("QBits: q_norm and k_norm come together");
+  return probe_attn_decode(qkv, kcache, vcache, kv_dtype, pos_dev, cos_dev, sin_dev, heads, kv_heads, head_dim, max_ctx,
+                           window, splits, 0, merge, 0, out, stream, q_norm_dev, k_norm_dev, eps);
 }
 
 }  // extern "C"

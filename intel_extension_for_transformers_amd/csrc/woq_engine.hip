@@ -28,7 +28,15 @@ constexpr int kProjEpi[P_COUNT] = {0, 0, 1, 0};
 // the engine's own form of woq_layer_weights (woq_engine_set_layer converts). fp8-weight layers: blob / hdr are the HI
 // nibble plane's (include/woq_blob.h woq_fp8_headers) and fp8_lo the LO plane's tile data; null for integer / table layers
 struct EngineProj { const void* blob; woq_blob_header hdr; const void* fp8_lo; };
-struct EngineLayer { EngineProj p[P_COUNT]; const float* ln1; const float* ln2; };
+// qkv_bias / q_norm / k_norm: the optional extras of woq_engine_set_layer_extras (null = absent)
+struct EngineLayer {
+  EngineProj p[P_COUNT];
+  const float* ln1;
+  const float* ln2;
+  const float* qkv_bias = nullptr;
+  const float* q_norm = nullptr;
+  const float* k_norm = nullptr;
+};
 // the pick after an lm_head (woq_engine::tail decides, engine_tail issues); pairs: that lm_head emits (max, index) pairs
 enum TailPick { PICK_NONE, PICK_SAMPLED, PICK_ARGMAX_FULL, PICK_ARGMAX_PAIRS, PICK_ARGMAX_EMBED, PICK_TP_GREEDY };
 struct Tail { TailPick pick; bool pairs; };
@@ -177,11 +185,13 @@ AttnDecodePlan woq_engine::attn_plan(int l, const AttnOptions& o) const {
   // the one device-derived number (asked once per shape, then remembered): only the grouped form's all-to-all merge reads it
   const int slots = xq && o.grouped && o.grouped_a2a ? attn_decode_mfma_slots(cfg.kv_dtype, cfg.heads / cfg.kv_heads) : 0;
   return plan_attn_decode(AttnShape{cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.kv_dtype, cfg.max_ctx, window}, o,
-                          AttnFacts{xq, qkv_g != nullptr && attn_part_g != nullptr, cfg.layers, &layers[l].p[P_QKV].hdr, slots});
+                          AttnFacts{xq, qkv_g != nullptr && attn_part_g != nullptr, cfg.layers, &layers[l].p[P_QKV].hdr, slots,
+                                    layers[l].q_norm != nullptr});
 }
 
 AttnDecodeIO woq_engine::attn_io(int l, const XqPtrs& xo) const {
-  return AttnDecodeIO{qkv, k_of(l), v_of(l), pos, cs, sn, attn, xo, attn_part, attn_cnt, attn_part_g, step_seq, l, fuse_status};
+  return AttnDecodeIO{qkv, k_of(l), v_of(l), pos, cs, sn, attn, xo, attn_part, attn_cnt, attn_part_g, step_seq, l, fuse_status,
+                      layers[l].q_norm, layers[l].k_norm, cfg.rms_eps};
 }
 
 const woq::CommDev* woq_engine::tp_push() const {
@@ -195,8 +205,8 @@ static int engine_gemv_xq(woq_engine* e, int l, Proj k, const XqPtrs& xin, float
                           const float* residual, const XqPtrs& xo, const float* next_norm_w, float* ssq_out,
                           hipStream_t st, const CommDev* tp = nullptr) {
   const EngineProj& p = e->layers[l].p[k];
-  return launch_gemv_xq(xin, p.blob, p.hdr, nullptr, out, ssq_in, e->cfg.rms_eps, residual, kProjEpi[k], xo, next_norm_w,
-                        ssq_out, st, tp);
+  return launch_gemv_xq(xin, p.blob, p.hdr, k == P_QKV ? e->layers[l].qkv_bias : nullptr, out, ssq_in, e->cfg.rms_eps,
+                        residual, kProjEpi[k], xo, next_norm_w, ssq_out, st, tp);
 }
 
 // The row-parallel projection that ends a sub-block (o_proj / down_proj), XQ path. One GPU: hidden += x . W, and the new
@@ -218,7 +228,8 @@ static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
   const AttnDecodePlan plan = e->attn_plan(l, e->attn_opt);
   const AttnDecodeIO io = e->attn_io(l, e->xq_attn);
   if (plan.form == ATTN_FUSED) {
-    rc = launch_gemv_xq_attn(plan, io, e->xq_hidden, w.p[P_QKV].blob, w.p[P_QKV].hdr, e->qkv_g, e->ssq_part, c.rms_eps, st);
+    rc = launch_gemv_xq_attn(plan, io, e->xq_hidden, w.p[P_QKV].blob, w.p[P_QKV].hdr, e->qkv_g, e->ssq_part, c.rms_eps, st,
+                             w.qkv_bias);
     if (rc) return rc;
   } else {
     rc = engine_gemv_xq(e, l, P_QKV, e->xq_hidden, e->qkv, e->ssq_part, nullptr, kNoXq, nullptr, nullptr, st);
@@ -248,8 +259,8 @@ static int engine_linear_f32(woq_engine* e, int l, Proj k, const float* act, int
   if (e->fp8_type != 0)
     return launch_gemv_fp8_engine(act, lda, p.blob, p.hdr, p.fp8_lo, e->fp8_type, out, ldo, norm_w, c.rms_eps, residual,
                                   c.hidden, kProjEpi[k], e->gu_tmp, st);
-  return launch_gemv_from_header(act, WOQ_F32, lda, p.blob, p.hdr, nullptr, out, WOQ_F32, ldo, 1, norm_w, c.rms_eps,
-                                 residual, c.hidden, kProjEpi[k], st);
+  return launch_gemv_from_header(act, WOQ_F32, lda, p.blob, p.hdr, k == P_QKV ? e->layers[l].qkv_bias : nullptr, out,
+                                 WOQ_F32, ldo, 1, norm_w, c.rms_eps, residual, c.hidden, kProjEpi[k], st);
 }
 
 static int engine_attn_block(woq_engine* e, int l, hipStream_t st) {
@@ -435,7 +446,8 @@ static int engine_prefill_gemm(woq_engine* e, int l, Proj k, int M, const void* 
   const woq_engine_config& c = e->cfg;
   const EngineProj& p = e->layers[l].p[k];
   const bool rowp = k == P_O || k == P_DOWN;
-  return launch_gemm_f16(act, act_dtype, lda, p.blob, p.hdr, nullptr, out, out_dtype, ldo, M, norm_w,
+  return launch_gemm_f16(act, act_dtype, lda, p.blob, p.hdr, k == P_QKV ? e->layers[l].qkv_bias : nullptr, out, out_dtype,
+                         ldo, M, norm_w,
                          rowp ? 0.f : c.rms_eps, rowp ? e->tp_residual(e->pf_h) : nullptr, rowp ? c.hidden : 0,
                          kProjEpi[k], e->pf_ws, 0, st, p.fp8_lo, e->fp8_type, e->pf_ws_bytes);
 }
@@ -455,7 +467,7 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
     rc = engine_prefill_gemm(e, l, P_QKV, M, e->pf_h, WOQ_F32, c.hidden, e->pf_qkv, WOQ_F16, qkv_n, w.ln1, st);
     if (rc) return rc;
     if ((rc = launch_rope_append(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, e->cs, e->sn, kc, vc,
-                                 c.kv_dtype, seq_stride, st)) != 0)
+                                 c.kv_dtype, seq_stride, st, w.q_norm, w.k_norm, c.rms_eps)) != 0)
       return rc;
     if ((rc = launch_attn_prefill(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, kc, vc, c.kv_dtype,
                                   seq_stride, e->pf_attn, e->window, st)) != 0)
@@ -849,7 +861,7 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
   WOQ_CHECK(gu.K == c.hidden && gu.N == 2 * c.inter && (c.inter % 16) == 0,
             "QBits: gate_up blob shape mismatch (inter must be a multiple of 16)");
   WOQ_CHECK(down.K == c.inter && down.N == c.hidden, "QBits: down_proj blob shape mismatch");
-  e->layers[layer] = in;
+  e->layers[layer] = in;  // (a layer set again starts without extras: woq_engine_set_layer_extras comes after)
   if (fp8) {
     // the composite container [outer header][HI blob][LO blob] (include/woq_blob.h): the engine keeps the HI plane as the
     // projection's blob / header and the LO plane's tile data beside it; its headers follow from the outer one's parameters
@@ -873,6 +885,24 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
   }
   WOQ_CHECK(e->fp8_type == 0, "QBits: fp8 and integer layers cannot be mixed in one engine");
   for (int k = 0; k < P_COUNT; ++k) e->xq_shapes_ok = e->xq_shapes_ok && gemv_xq_supported(in.p[k].hdr, kProjEpi[k]);
+  WOQ_END
+}
+
+int woq_engine_set_layer_extras(woq_engine* e, int layer, const float* qkv_bias_dev, const float* q_norm_dev,
+                                const float* k_norm_dev) {
+  WOQ_TRY
+  WOQ_CHECK(e && layer >= 0 && layer < e->cfg.layers, "QBits: bad layer index");
+  EngineLayer& w = e->layers[layer];
+  const bool any = qkv_bias_dev != nullptr || q_norm_dev != nullptr || k_norm_dev != nullptr;
+  WOQ_CHECK(!any || (e->cfg.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr),
+            "QBits: layer extras (qkv bias, q/k norm) run on one GPU (no tensor-parallel path)");
+  WOQ_CHECK(w.p[P_QKV].blob != nullptr, "QBits: woq_engine_set_layer_extras comes after woq_engine_set_layer");
+  WOQ_CHECK((q_norm_dev != nullptr) == (k_norm_dev != nullptr), "QBits: q_norm and k_norm come together (both or neither)");
+  WOQ_CHECK(qkv_bias_dev == nullptr || e->fp8_type == 0, "QBits: fp8-weight layers do not take a qkv bias");
+  WOQ_CHECK(q_norm_dev == nullptr || (e->cfg.head_dim % 16) == 0, "QBits: a q/k norm needs head_dim to be a multiple of 16");
+  // which extras are present decides which kernels a captured step holds (and their pointers are baked into it)
+  if (w.qkv_bias != qkv_bias_dev || w.q_norm != q_norm_dev || w.k_norm != k_norm_dev) engine_drop_graphs(e);
+  w.qkv_bias = qkv_bias_dev, w.q_norm = q_norm_dev, w.k_norm = k_norm_dev;
   WOQ_END
 }
 

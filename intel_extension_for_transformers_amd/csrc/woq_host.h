@@ -101,6 +101,7 @@ struct AttnFacts {  // what the engine is
   int layers;         // hand-off tags are (step << 6) | layer: at most 64 layers
   const woq_blob_header* qkv_hdr;  // the layer's qkv blob (nullable = no fused launch)
   int slots;          // attn_decode_mfma_slots for this shape, 0 = not covered
+  bool qk_norm = false;  // the layer has a per-head q / k RMSNorm: the grouped form does not carry it (falls to per-head)
 };
 struct AttnDecodePlan {
   AttnShape shape;
@@ -132,6 +133,9 @@ struct AttnDecodeIO {
   const unsigned int* seq;     // FUSED / A2A: device-side step counter, tag = seq << 6 | layer
   int layer;
   int* status;            // sticky give-up flag
+  // per-head RMSNorm of q and of the new k over D BEFORE the rotation (Qwen3): fp32 [D] weights, both or neither
+  const float *q_norm = nullptr, *k_norm = nullptr;
+  float qk_eps = 0.f;
 };
 // the attention launch(es) of a PER_HEAD or GROUPED plan; a plan with an error text fails with it
 int launch_attn_decode(const AttnDecodePlan& plan, const AttnDecodeIO& io, hipStream_t st);
@@ -144,9 +148,10 @@ int attn_decode_mfma_slots(int kv_dtype, int rep);
 // rsqrt(mean(x^2) + eps); per head, as its granules arrive: RoPE, KV append at *io.pos, attention over the cache ->
 // io.out (+ io.xo). plan.slices > 1: context slices per head; they merge among themselves through io.part_g and write
 // io.out / io.xo — no combine launch.
+// bias (nullable): fp32 [N], added in the strips' epilogue after the RMSNorm factor (Qwen2's q / k / v biases)
 int launch_gemv_xq_attn(const AttnDecodePlan& plan, const AttnDecodeIO& io, const XqPtrs& xin, const void* blob,
                         const woq_blob_header& h, unsigned long long* qkv_g, const float* ssq_in, float eps,
-                        hipStream_t st);
+                        hipStream_t st, const float* bias = nullptr);
 
 // ---- woq_ops.hip: the decode step's other launches ----------------------------------------------------------------
 void launch_embed(const void* embed, int dtype, const int32_t* token, int hidden, float* out, const float* norm_w,
@@ -268,9 +273,10 @@ int launch_score_rows(const float* hidden_rows, const float* norm_w, float eps, 
 // ---- woq_prefill.hip: the prompt pass's launches outside its GEMMs -------------------------------------------------
 void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int M, int hidden, float* out,
                        hipStream_t st);
+// q_norm / k_norm (fp32 [HD], both or neither; eps): RMSNorm of every q / k head over HD before the rotation
 int launch_rope_append(_Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD, const float* cs,
                        const float* sn, void* kcache, void* vcache, int kv_dtype, size_t seq_stride_elems,
-                       hipStream_t st);
+                       hipStream_t st, const float* q_norm = nullptr, const float* k_norm = nullptr, float qk_eps = 0.f);
 int launch_attn_prefill(const _Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD,
                         const void* kcache, const void* vcache, int kv_dtype, size_t seq_stride_elems, _Float16* out,
                         int window, hipStream_t st);

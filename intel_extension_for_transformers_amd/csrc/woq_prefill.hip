@@ -87,6 +87,74 @@ __global__ __launch_bounds__(256) void rope_append_kernel(_Float16* __restrict__
   }
 }
 
+// The same pass with a per-head RMSNorm on q and k in front of the rotation (Qwen3's q_norm / k_norm, HF Qwen3RMSNorm in
+// fp32: x * rsqrt(mean(x^2) + eps) * w). A head slot is spread over cph = HD / 16 neighbouring lanes (cph a power of
+// two: a group never straddles a wave), so its sum of squares is a butterfly over those lanes — no LDS, no barrier.
+// Normalised and rotated in fp32 from the fp16 projections, rounded ONCE (q to fp16, k to the cache type); v untouched.
+// The grid is padded to whole waves and no thread leaves early: threads past the end (whole groups: the thread count
+// is a multiple of cph) recompute the last chunk and store nothing, so every lane a butterfly reads is there.
+template <int KVD>
+__global__ __launch_bounds__(256) void rope_append_qkn_kernel(_Float16* __restrict__ qkv, int M, int T, int start,
+                                                              int heads, int kv_heads, int HD,
+                                                              const float* __restrict__ cs, const float* __restrict__ sn,
+                                                              void* __restrict__ kcache, void* __restrict__ vcache,
+                                                              size_t seq_stride_elems, const float* __restrict__ q_norm,
+                                                              const float* __restrict__ k_norm, float eps) {
+  const int half = HD >> 1, cph = half >> 3;
+  const int nslots = heads + 2 * kv_heads;
+  const size_t per_row = (size_t)nslots * cph, total = (size_t)M * per_row;
+  const size_t gid0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = gid0 < total;
+  const size_t gid = live ? gid0 : total - 1;
+  const int m = (int)(gid / per_row);
+  const int rem = (int)(gid % per_row);
+  const int slot = rem / cph, c8 = (rem % cph) * 8;
+  const int seq = m / T, pos = start + m % T;
+  _Float16* x = qkv + (size_t)m * nslots * HD + (size_t)slot * HD;
+  const h8 xa = *(const h8*)(x + c8), xb = *(const h8*)(x + c8 + half);
+  float a[8], b[8], ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    a[j] = (float)xa[j], b[j] = (float)xb[j];
+    ss = fmaf(a[j], a[j], ss);
+    ss = fmaf(b[j], b[j], ss);
+  }
+  for (int o = 1; o < cph; o <<= 1) ss += __shfl_xor(ss, o, 64);  // every lane of the wave takes part
+  float ra[8], rb[8];
+  if (slot < heads + kv_heads) {
+    const float r = 1.0f / sqrtf(ss / (float)HD + eps);
+    const float* w = slot < heads ? q_norm : k_norm;
+    const float4_t wa0 = *(const float4_t*)(w + c8), wa1 = *(const float4_t*)(w + c8 + 4);
+    const float4_t wb0 = *(const float4_t*)(w + c8 + half), wb1 = *(const float4_t*)(w + c8 + half + 4);
+    const float wa[8] = {wa0.x, wa0.y, wa0.z, wa0.w, wa1.x, wa1.y, wa1.z, wa1.w};
+    const float wb[8] = {wb0.x, wb0.y, wb0.z, wb0.w, wb1.x, wb1.y, wb1.z, wb1.w};
+    const float4_t c0 = *(const float4_t*)(cs + (size_t)pos * half + c8), c1 = *(const float4_t*)(cs + (size_t)pos * half + c8 + 4);
+    const float4_t s0 = *(const float4_t*)(sn + (size_t)pos * half + c8), s1 = *(const float4_t*)(sn + (size_t)pos * half + c8 + 4);
+    const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float sv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float na = a[j] * (r * wa[j]), nb = b[j] * (r * wb[j]);
+      ra[j] = na * cc[j] - nb * sv[j];
+      rb[j] = nb * cc[j] + na * sv[j];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ra[j] = a[j], rb[j] = b[j];
+  }
+  if (!live) return;
+  if (slot < heads) {
+    kv_store8<WOQ_F16>(x, c8, ra);
+    kv_store8<WOQ_F16>(x, c8 + half, rb);
+  } else {
+    const int kh = slot < heads + kv_heads ? slot - heads : slot - heads - kv_heads;
+    void* cache = slot < heads + kv_heads ? kcache : vcache;
+    const size_t e = (size_t)seq * seq_stride_elems + ((size_t)pos * kv_heads + kh) * HD;
+    kv_store8<KVD>(cache, e + c8, ra);
+    kv_store8<KVD>(cache, e + c8 + half, rb);
+  }
+}
+
 // ---- causal attention over the cache -----------------------------------------------------------------------------
 constexpr int AQB = 128;  // query rows per workgroup
 constexpr int AKT = 64;   // cache positions per tile
@@ -321,11 +389,28 @@ void launch_embed_rows(const void* embed, int dtype, const int32_t* tokens, int 
 
 int launch_rope_append(_Float16* qkv, int n_seq, int T, int start, int heads, int kv_heads, int HD, const float* cs,
                        const float* sn, void* kcache, void* vcache, int kv_dtype, size_t seq_stride_elems,
-                       hipStream_t st) {
+                       hipStream_t st, const float* q_norm, const float* k_norm, float qk_eps) {
   if ((HD & 15) != 0) return woq::fail("QBits: head_dim must be a multiple of 16");
   const int M = n_seq * T;
   const size_t threads = (size_t)M * (heads + 2 * kv_heads) * (HD / 16);
   const dim3 grid((unsigned)((threads + 255) / 256));
+  if ((q_norm != nullptr) != (k_norm != nullptr)) return woq::fail("QBits: q_norm and k_norm come together");
+  if (q_norm != nullptr) {
+    const int cph = HD / 16;  // lanes per head slot: the butterfly wants a power of two inside one wave
+    if ((cph & (cph - 1)) != 0 || cph > 64)
+      return woq::fail("QBits: a q/k norm needs head_dim = 16 * a power of two (at most 1024)");
+#define WOQ_ROPE_QKN_CASE(KVD)                                                                                      \
+  if (kv_dtype == KVD) {                                                                                            \
+    hipLaunchKernelGGL(rope_append_qkn_kernel<KVD>, grid, dim3(256), 0, st, qkv, M, T, start, heads, kv_heads, HD,  \
+                       cs, sn, kcache, vcache, seq_stride_elems, q_norm, k_norm, qk_eps);                           \
+    return 0;                                                                                                       \
+  }
+    WOQ_ROPE_QKN_CASE(WOQ_F16)
+    WOQ_ROPE_QKN_CASE(WOQ_BF16)
+    WOQ_ROPE_QKN_CASE(WOQ_FP8_E4M3)
+#undef WOQ_ROPE_QKN_CASE
+    return woq::fail("QBits: unsupported KV cache dtype");
+  }
   if (kv_dtype == WOQ_F16)
     hipLaunchKernelGGL(rope_append_kernel<WOQ_F16>, grid, dim3(256), 0, st, qkv, M, T, start, heads, kv_heads, HD, cs,
                        sn, kcache, vcache, seq_stride_elems);
@@ -390,6 +475,21 @@ WOQ_API int woq_probe_rope_append(void* qkv, int n_seq, int T, int start, int he
   WOQ_CHECK(n_seq > 0 && T > 0 && start >= 0 && heads > 0 && kv_heads > 0, "QBits: bad rope_append shape");
   const int rc = woq::launch_rope_append((_Float16*)qkv, n_seq, T, start, heads, kv_heads, head_dim, cos_dev, sin_dev,
                                          kcache, vcache, kv_dtype, seq_stride_elems, (hipStream_t)stream);
+  if (rc) return rc;
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_rope_append_qknorm(void* qkv, int n_seq, int T, int start, int heads, int kv_heads, int head_dim,
+                                         const float* cos_dev, const float* sin_dev, void* kcache, void* vcache,
+                                         int kv_dtype, size_t seq_stride_elems, const float* q_norm_dev,
+                                         const float* k_norm_dev, float eps, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(n_seq > 0 && T > 0 && start >= 0 && heads > 0 && kv_heads > 0, "QBits: bad rope_append shape");
+  WOQ_CHECK(q_norm_dev != nullptr && k_norm_dev != nullptr, "QBits: q_norm and k_norm come together");
+  const int rc = woq::launch_rope_append((_Float16*)qkv, n_seq, T, start, heads, kv_heads, head_dim, cos_dev, sin_dev,
+                                         kcache, vcache, kv_dtype, seq_stride_elems, (hipStream_t)stream, q_norm_dev,
+                                         k_norm_dev, eps);
   if (rc) return rc;
   WOQ_HIP(hipGetLastError());
   WOQ_END

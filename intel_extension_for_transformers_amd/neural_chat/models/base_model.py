@@ -67,8 +67,10 @@ class BaseModel:
         if not hasattr(self.model, "quantization_config"):
             return
         try:
-            from ...runtime.engine import optimize_transformers
+            from ...runtime.engine import engine_supports, optimize_transformers
 
+            if not engine_supports(self.model.config)[0]:  # the acceptance rule shared with `generate` and the TP host
+                return
             ctx = int(min(getattr(self.model.config, "max_position_embeddings", 2048) or 2048, 8192))
             self.engine = optimize_transformers(self.model, max_ctx=ctx)
         except RuntimeError:

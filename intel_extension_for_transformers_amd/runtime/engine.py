@@ -18,11 +18,133 @@ from .. import qbits
 from .streaming import StreamingConfig, plan_steps, plan_stream  # noqa: F401  (StreamingConfig: part of this module's API)
 
 
-def build_rope_tables(max_pos, head_dim, theta=10000.0, device="cuda"):
-    """cos/sin [max_pos, head_dim/2] fp32, HF LlamaRotaryEmbedding's default parameterisation."""
-    inv_freq = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).float() / head_dim))
+ENGINE_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")  # the one list: engine_supports reads it, nothing else does
+ROPE_TYPES = ("default", "linear", "llama3", "yarn")  # build_rope_tables' parameterisations
+
+
+def rope_scaling_of(config):
+    """(rope type, parameter dict) of an HF config: `rope_scaling` or `rope_parameters`, whichever it has."""
+    rs = getattr(config, "rope_scaling", None) or getattr(config, "rope_parameters", None) or {}
+    if not isinstance(rs, dict):
+        return "default", {}
+    return (rs.get("rope_type") or rs.get("type") or "default"), rs
+
+
+def rope_inv_freq(head_dim, theta=10000.0, rope_scaling=None, max_position_embeddings=None):
+    """(inv_freq fp32 [head_dim / 2], attention factor): HF's `default`, `linear`, `llama3` and `yarn` RoPE
+    parameterisations restated in HF's operation order (transformers/modeling_rope_utils.py: the fp32 tensor ops, the
+    Python-float scalars). Anything else raises."""
+    rtype, rs = ("default", {}) if not rope_scaling else \
+        ((rope_scaling.get("rope_type") or rope_scaling.get("type") or "default"), rope_scaling)
+    if rtype not in ROPE_TYPES:
+        raise RuntimeError("QBits: the fused decode engine implements plain RoPE only (rope scaling %r)" % rtype)
+    dim = head_dim
+    inv_freq = 1.0 / (theta ** (torch.arange(0, dim, 2, dtype=torch.int64).float() / dim))
+    if rtype == "default":
+        return inv_freq, 1.0
+    factor = rs.get("factor")
+    if rtype == "linear":
+        return inv_freq / factor, 1.0
+    orig = rs.get("original_max_position_embeddings") or max_position_embeddings
+    if orig is None:
+        raise RuntimeError("QBits: rope scaling %r needs original_max_position_embeddings" % rtype)
+    if rtype == "llama3":
+        low_f, high_f = rs["low_freq_factor"], rs["high_freq_factor"]
+        low_wavelen, high_wavelen = orig / low_f, orig / high_f
+        wavelen = 2 * math.pi / inv_freq
+        scaled = torch.where(wavelen > low_wavelen, inv_freq / factor, inv_freq)
+        smooth = (orig / wavelen - low_f) / (high_f - low_f)
+        smoothed = (1 - smooth) * scaled / factor + smooth * scaled
+        medium = ~(wavelen < high_wavelen) * ~(wavelen > low_wavelen)
+        return torch.where(medium, smoothed, scaled), 1.0
+    # yarn
+    if factor is None:
+        factor = max_position_embeddings / orig
+
+    def mscale_of(scale, mscale=1):
+        return 1.0 if scale <= 1 else 0.1 * mscale * math.log(scale) + 1.0
+
+    att = rs.get("attention_factor")
+    if att is None:
+        ms, ms_all = rs.get("mscale"), rs.get("mscale_all_dim")
+        att = float(mscale_of(factor, ms) / mscale_of(factor, ms_all)) if ms and ms_all else mscale_of(factor)
+    beta_fast, beta_slow = rs.get("beta_fast") or 32, rs.get("beta_slow") or 1
+
+    def correction_dim(rot):
+        return (dim * math.log(orig / (rot * 2 * math.pi))) / (2 * math.log(theta))
+
+    low, high = correction_dim(beta_fast), correction_dim(beta_slow)
+    if rs.get("truncate", True):
+        low, high = math.floor(low), math.ceil(high)
+    low, high = max(low, 0), min(high, dim - 1)
+    if low == high:
+        high += 0.001
+    pos_freqs = theta ** (torch.arange(0, dim, 2).float() / dim)
+    extrapolation, interpolation = 1.0 / pos_freqs, 1.0 / (factor * pos_freqs)
+    ramp = torch.clamp((torch.arange(dim // 2, dtype=torch.float32) - low) / (high - low), 0, 1)
+    ext = 1 - ramp
+    return interpolation * (1 - ext) + extrapolation * ext, float(att)
+
+
+def build_rope_tables(max_pos, head_dim, theta=10000.0, device="cuda", rope_scaling=None,
+                      max_position_embeddings=None):
+    """cos/sin [max_pos, head_dim/2] fp32: HF's rotary module for the `default` parameterisation and, with
+    `rope_scaling` (an HF rope_scaling / rope_parameters dict), for `linear`, `llama3` and `yarn`: the angles are
+    position * inv_freq in fp32, and cos / sin are multiplied by HF's attention factor (yarn; 1 elsewhere —
+    rope_inv_freq returns it, and a rolling KV cache refuses tables where it is not 1). `dynamic`, `longrope` and
+    anything unknown raise."""
+    inv_freq, att = rope_inv_freq(head_dim, theta, rope_scaling, max_position_embeddings)
     ang = torch.arange(max_pos, dtype=torch.float32)[:, None] * inv_freq[None, :]
-    return ang.cos().contiguous().to(device), ang.sin().contiguous().to(device)
+    cos, sin = ang.cos(), ang.sin()
+    if att != 1.0:
+        cos, sin = cos * att, sin * att
+    return cos.contiguous().to(device), sin.contiguous().to(device)
+
+
+def engine_window(config):
+    """The sliding window (0 = full causal attention) the engine runs an HF config with. llama / mistral:
+    `sliding_window` as it stands. qwen2 / qwen3: from `layer_types` when present (all full: 0, all sliding:
+    `sliding_window`, mixed: refused), else `sliding_window` only under `use_sliding_window`."""
+    window = int(getattr(config, "sliding_window", None) or 0)
+    if getattr(config, "model_type", "") not in ("qwen2", "qwen3"):
+        return window  # Mistral v0.1: 4096; null / absent = full causal attention
+    kinds = set(getattr(config, "layer_types", None) or ())
+    if kinds:
+        if kinds == {"full_attention"}:
+            return 0
+        if kinds == {"sliding_attention"}:
+            return window
+        raise RuntimeError("QBits: the fused decode engine runs one attention form in every layer (layer_types mixes %s)"
+                           % " and ".join(sorted(kinds)))
+    return window if getattr(config, "use_sliding_window", False) else 0
+
+
+def engine_supports(config):
+    """(ok, reason): does the fused decode engine take a model of this HF config? The one acceptance rule —
+    optimize_transformers, the engine-backed `generate`, NeuralChat's engine gate and the tensor-parallel host all ask
+    here. A refusal's reason names the config field that caused it. (What only the modules can tell — the weight types,
+    a bias that the config does not announce — optimize_transformers checks on the model itself.)"""
+    mt = getattr(config, "model_type", "")
+    if mt not in ENGINE_MODEL_TYPES:
+        return False, "QBits: the fused decode engine covers Llama-class decoders (model_type %s), got %r" % (
+            " / ".join(ENGINE_MODEL_TYPES), mt)
+    rtype, rs = rope_scaling_of(config)
+    if rtype not in ROPE_TYPES:
+        return False, "QBits: the fused decode engine implements plain RoPE only (rope scaling %r)" % rtype
+    if (rs.get("partial_rotary_factor") or getattr(config, "partial_rotary_factor", None) or 1.0) != 1.0:
+        return False, "QBits: the fused decode engine rotates whole heads only (partial_rotary_factor)"
+    if getattr(config, "hidden_act", "silu") not in ("silu", "swish"):
+        return False, "QBits: the fused decode engine implements the SiLU-gated MLP only (hidden_act %r)" % config.hidden_act
+    # llama / mistral / qwen3: attention_bias puts a bias on o_proj as well; qwen2's q / k / v biases are not a config field
+    if mt != "qwen2" and getattr(config, "attention_bias", False):
+        return False, "QBits: the fused decode engine does not take biased projections (attention_bias: o_proj)"
+    if getattr(config, "mlp_bias", False):
+        return False, "QBits: the fused decode engine does not take biased projections (mlp_bias)"
+    try:
+        engine_window(config)
+    except RuntimeError as e:
+        return False, str(e)
+    return True, ""
 
 
 def fuse_gate_up(gate, up):
@@ -106,7 +228,28 @@ class WoqDecoderEngine:
         self._keep += [qkv_blob, o_blob, gate_up_blob, down_blob, ln1, ln2]
         self.layer_tensors[idx] = dict(qkv=qkv_blob, o=o_blob, gate_up=gate_up_blob, down=down_blob, ln1=ln1, ln2=ln2)
 
-    def set_head(self, embed, final_norm, lm_head, cos=None, sin=None):
+    def set_layer_extras(self, idx, qkv_bias=None, q_norm=None, k_norm=None):
+        """Optional extras of layer `idx` (woq_engine_set_layer_extras; after set_layer): `qkv_bias`
+        [(heads + 2 kv_heads) * head_dim] added to the fused q|k|v projection (Qwen2), `q_norm` / `k_norm` [head_dim]
+        = the weights of the per-head RMSNorm on q and k in front of RoPE (Qwen3; both or neither). One GPU only."""
+        def dev(t):
+            return None if t is None else t.detach().to(self.device, torch.float32).contiguous()
+
+        qkv_bias, q_norm, k_norm = dev(qkv_bias), dev(q_norm), dev(k_norm)
+        n_qkv = (self.cfg.heads + 2 * self.cfg.kv_heads) * self.cfg.head_dim
+        for t, n, what in ((qkv_bias, n_qkv, "qkv_bias"), (q_norm, self.cfg.head_dim, "q_norm"),
+                           (k_norm, self.cfg.head_dim, "k_norm")):
+            if t is not None and t.numel() != n:
+                raise RuntimeError("QBits: %s has %d elements, the engine's shape needs %d" % (what, t.numel(), n))
+        L.check(L.lib().woq_engine_set_layer_extras(self._h, int(idx), *(None if t is None else t.data_ptr()
+                                                                         for t in (qkv_bias, q_norm, k_norm))))
+        self.captured = False  # (the native side dropped its graphs if the extras changed)
+        self._keep += [t for t in (qkv_bias, q_norm, k_norm) if t is not None]
+        self.layer_tensors.setdefault(idx, {}).update(qkv_bias=qkv_bias, q_norm=q_norm, k_norm=k_norm)
+
+    def set_head(self, embed, final_norm, lm_head, cos=None, sin=None, attention_factor=1.0):
+        """`cos` / `sin`: caller-built tables (build_rope_tables) and the attention factor they were multiplied by."""
+        self.rope_attention_factor = float(attention_factor)
         embed = embed.to(self.device).contiguous()
         lm_head = lm_head.to(self.device).contiguous()
         final_norm = final_norm.to(self.device, torch.float32).contiguous()
@@ -196,6 +339,7 @@ class WoqDecoderEngine:
         `n_discard`. `move_pos` (sequence 0): the device position and the `discarded` word follow, so the burst issued
         next feeds position n_cached - n_discard. Issued on the current stream, the one bursts run on: no
         synchronisation, no read-back. Every shift re-rounds the moved K rows to the cache type."""
+        self._check_shiftable()
         L.check(L.lib().woq_engine_kv_shift(self._h, int(seq), int(n_keep), int(n_discard), int(n_cached),
                                             int(bool(move_pos)), L.stream_ptr()))
 
@@ -208,10 +352,18 @@ class WoqDecoderEngine:
         """discarded = value, stream-ordered (a request starts from 0)."""
         L.check(L.lib().woq_engine_discarded_set(self._h, int(value), L.stream_ptr()))
 
+    def _check_shiftable(self):
+        """The K re-rotation multiplies by a table row: right for any per-dimension frequency, wrong for tables scaled
+        by an attention factor (yarn), whose rows are not rotations."""
+        if getattr(self, "rope_attention_factor", 1.0) != 1.0:
+            raise RuntimeError("QBits: the rolling KV cache does not combine with RoPE tables scaled by an attention "
+                               "factor (%g: yarn rope scaling)" % self.rope_attention_factor)
+
     def _request_geometry(self, n_prompt, max_new_tokens, streaming):
         """(ctx_size, n_keep, n_discard) of a request with a rolling cache, (None, 0, 0) of one without, which has to
         fit the cache as a whole."""
         if streaming is not None:
+            self._check_shiftable()
             return streaming.resolve(self.cfg.max_ctx, n_prompt)
         if n_prompt + max_new_tokens > self.cfg.max_ctx:  # the kernels index the KV cache by position, unchecked
             raise RuntimeError("QBits: prompt (%d) + max_new_tokens (%d) exceeds the engine's max_ctx (%d)"
@@ -1236,17 +1388,14 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16):
     builds the native batch-1 decode engine over the SAME quantised weights (q/k/v fused along N, gate/up
     interleaved per 16-column tile for the fused SiLU*mul epilogue). Mirrors the two-step shape of the reference's
     Intel-GPU flow, `ipex.optimize_transformers(qmodel, ...)` after `from_pretrained`
-    (docs/weightonlyquant.md:199-202). Llama-class decoders (Llama-2, Mistral: RMSNorm, RoPE, gated SiLU MLP)."""
+    (docs/weightonlyquant.md:199-202). Llama-class decoders (RMSNorm, RoPE, gated SiLU MLP): Llama-2 / 3.x, Mistral,
+    Qwen2 (q / k / v biases) and Qwen3 (per-head q / k norm), with HF's default, linear, llama3 or yarn RoPE."""
     cfg = model.config
-    if getattr(cfg, "model_type", "") not in ("llama", "mistral"):
-        raise RuntimeError("QBits: the fused decode engine covers Llama-class decoders, got %r" % cfg.model_type)
     # anything the engine's kernels do not implement keeps the model on the module path instead of changing its maths
-    rs = getattr(cfg, "rope_scaling", None) or (getattr(cfg, "rope_parameters", None) or {})
-    rtype = (rs.get("rope_type") or rs.get("type") or "default") if isinstance(rs, dict) else "default"
-    if rtype not in ("default", None):
-        raise RuntimeError("QBits: the fused decode engine implements plain RoPE only (rope scaling %r)" % rtype)
-    if getattr(cfg, "hidden_act", "silu") not in ("silu", "swish"):
-        raise RuntimeError("QBits: the fused decode engine implements the SiLU-gated MLP only (%r)" % cfg.hidden_act)
+    ok, reason = engine_supports(cfg)
+    if not ok:
+        raise RuntimeError(reason)
+    rtype, rs = rope_scaling_of(cfg)
     layers = model.model.layers
     first = layers[0].self_attn.q_proj
     wdt = getattr(first, "weight_dtype", "int4_clip")
@@ -1262,7 +1411,7 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16):
     if theta is None:
         theta = (getattr(cfg, "rope_parameters", None) or {}).get("rope_theta", 10000.0)
     dev = first.weight.device
-    window = getattr(cfg, "sliding_window", None) or 0  # Mistral v0.1: 4096; null / absent = full causal attention
+    window = engine_window(cfg)
     eng = WoqDecoderEngine(hidden, inter, heads, kv_heads, head_dim, len(layers), cfg.vocab_size, max_ctx=max_ctx,
                            rms_eps=cfg.rms_norm_eps, rope_theta=float(theta), kv_dtype=kv_dtype, device=dev,
                            sliding_window=int(window))
@@ -1300,9 +1449,19 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16):
 
     for l, layer in enumerate(layers):
         at, mlp = layer.self_attn, layer.mlp
-        for m in (at.q_proj, at.k_proj, at.v_proj, at.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
+        for m in (at.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
             if m.bias is not None:
                 raise RuntimeError("QBits: the fused decode engine does not take biased projections")
+        # q / k / v biases (Qwen2) ride in the fused projection's epilogue: all three, or the model keeps the module path
+        biases = [m.bias for m in (at.q_proj, at.k_proj, at.v_proj)]
+        if any(b is not None for b in biases) and any(b is None for b in biases):
+            state = ", ".join("%s_proj.bias %s" % (n, "missing" if b is None else "set") for n, b in zip("qkv", biases))
+            raise RuntimeError("QBits: the fused decode engine takes q_proj / k_proj / v_proj biases only together "
+                               "(layers.%d has %s)" % (l, state))
+        qkv_bias = torch.cat([b.detach().float().reshape(-1) for b in biases]) if biases[0] is not None else None
+        q_norm, k_norm = getattr(at, "q_norm", None), getattr(at, "k_norm", None)
+        if (q_norm is None) != (k_norm is None):
+            raise RuntimeError("QBits: the fused decode engine takes q_norm and k_norm only together (layers.%d)" % l)
         qkv = pack(*cat([_signed_parts(at.q_proj), _signed_parts(at.k_proj), _signed_parts(at.v_proj)],
                         "layers.%d q_proj / k_proj / v_proj" % l))
         g, u = _signed_parts(mlp.gate_proj), _signed_parts(mlp.up_proj)
@@ -1310,8 +1469,17 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16):
                   _same_order([g, u], "layers.%d gate_proj / up_proj" % l))
         eng.set_layer(l, qkv, at.o_proj.weight.data, gu, mlp.down_proj.weight.data, layer.input_layernorm.weight,
                       layer.post_attention_layernorm.weight)
+        if qkv_bias is not None or q_norm is not None:
+            eng.set_layer_extras(l, qkv_bias=qkv_bias, q_norm=None if q_norm is None else q_norm.weight,
+                                 k_norm=None if k_norm is None else k_norm.weight)
     head_dtype = kv_dtype if kv_dtype in (torch.float16, torch.bfloat16) else torch.float16  # fp8 is cache-only
+    cos = sin = None
+    att = 1.0
+    if rtype != "default":  # (the default tables are set_head's own)
+        mpe = getattr(cfg, "max_position_embeddings", None)
+        att = rope_inv_freq(head_dim, float(theta), rs, mpe)[1]
+        cos, sin = build_rope_tables(max_ctx, head_dim, float(theta), dev, rope_scaling=rs, max_position_embeddings=mpe)
     eng.set_head(model.model.embed_tokens.weight.detach().to(head_dtype), model.model.norm.weight,
-                 model.lm_head.weight.detach().to(head_dtype))
+                 model.lm_head.weight.detach().to(head_dtype), cos, sin, attention_factor=att)
     model.woq_engine = eng
     return eng

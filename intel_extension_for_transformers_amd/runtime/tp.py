@@ -70,6 +70,23 @@ def shard_llama_layer(parts, rank, world, heads, kv_heads, head_dim, group):
     return out
 
 
+def tp_supports(config):
+    """(ok, reason) for sharding a model of this HF config: the engine's own acceptance rule (engine_supports), minus
+    what the tensor-parallel step does not carry — the per-layer extras. Qwen2's q / k / v biases and Qwen3's q / k
+    norm are refused by name here rather than dropped by the sharding."""
+    from .engine import engine_supports
+
+    ok, reason = engine_supports(config)
+    if not ok:
+        return ok, reason
+    mt = getattr(config, "model_type", "")
+    if mt == "qwen2" or getattr(config, "attention_bias", False):
+        return False, "QBits: the tensor-parallel engine does not take q_proj / k_proj / v_proj biases (model_type %r)" % mt
+    if mt == "qwen3":
+        return False, "QBits: the tensor-parallel engine does not take a q_norm / k_norm (model_type %r)" % mt
+    return True, ""
+
+
 def shard_vocab(lm_head, rank, world):
     """lm_head [vocab, hidden] -> the rank's vocab rows (padded split: the last rank may hold fewer)."""
     v = lm_head.shape[0]

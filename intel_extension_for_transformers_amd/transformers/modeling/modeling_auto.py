@@ -563,7 +563,9 @@ def _finish(model, qcfg):
     model.quantization_config = qcfg
     model.config.quantization_config = qcfg.to_dict()
     model.save_pretrained = types.MethodType(save_low_bit, model)
-    if getattr(model.config, "model_type", "") in ("llama", "mistral") and getattr(qcfg, "bits", 4) == 4 \
+    from ...runtime.engine import engine_supports  # the one acceptance rule (model families, RoPE forms, biases)
+
+    if engine_supports(model.config)[0] and getattr(qcfg, "bits", 4) == 4 \
             and hasattr(model, "generate") and not hasattr(model, "_woq_hf_generate"):
         model._woq_hf_generate = model.generate
         model.generate = types.MethodType(_engine_generate, model)
