@@ -187,17 +187,19 @@ class BaseModel:
             "top": [(int(i), tok.decode([int(i)]), float(v)) for i, v in top if i >= 0],
             "text_offset": len(tok.decode(out, skip_special_tokens=True)) if out else 0})
 
-    def _engine_stream_logprobs(self, bursts, n_out):
-        """Text pieces of an engine stream that yields `(tokens, chosen_lps, top)` bursts; fills `last_logprobs` (EOS
-        excluded, as from the text)."""
+    def _text_pieces(self, bursts, n_out):
+        """Text pieces of an engine stream whose bursts are token lists or `(tokens, chosen_lps, top)`; the latter fill
+        `last_logprobs`. EOS is left out of the text, the count `n_out` and the records."""
         tok = self.tokenizer
         eos = tok.eos_token_id
         out, shown = [], ""
-        for new, lps, tops in bursts:
-            for t, lp, top in zip(new, lps, tops):
+        for burst in bursts:
+            new, lps, tops = burst if isinstance(burst, tuple) else (burst, None, None)
+            for j, t in enumerate(new):
                 if eos is not None and t == eos:
                     continue
-                self._note_logprobs(out, t, lp, top)
+                if lps is not None:
+                    self._note_logprobs(out, t, lps[j], tops[j])
                 out.append(t)
                 n_out[0] += 1
             text = tok.decode(out, skip_special_tokens=True)
@@ -262,81 +264,25 @@ class BaseModel:
                     logit_bias=dict(getattr(config, "logit_bias", None) or {}), seed=getattr(config, "seed", None))
 
     def _engine_stream(self, ids, config, n_out):
-        eng, tok = self.engine, self.tokenizer
-        eos = tok.eos_token_id
-        ctl = self._sampler_controls(config)
-        # a penalty or a bias with temperature 0 is a greedy request over the penalised scores: the sampler's argmax
-        if config.do_sample or (config.repetition_penalty or 1.0) != 1.0 or ctl["presence_penalty"] \
-                or ctl["frequency_penalty"] or ctl["logit_bias"] or ctl["guide"] is not None:
-            yield from self._engine_stream_sampled(ids, config, n_out)
-            return
-        if getattr(config, "logprobs", None) is not None:  # the same greedy chain, with the step's records read back
-            yield from self._engine_stream_logprobs(
-                eng.iter_generate(ids, config.max_new_tokens, burst=1, eos=() if eos is None else (eos,),
-                                  logprobs=config.logprobs, streaming=self._streaming(config)), n_out)
-            return
-        if self._streaming(config) is not None:  # the greedy chain over a rolling cache: the engine's planned loop
-            out, shown = [], ""
-            for new in eng.iter_generate(ids, config.max_new_tokens, burst=1, eos=() if eos is None else (eos,),
-                                         streaming=self._streaming(config)):
-                for t in new:
-                    if eos is not None and t == eos:
-                        continue
-                    out.append(t)
-                    n_out[0] += 1
-                text = tok.decode(out, skip_special_tokens=True)
-                if not text.endswith("\ufffd"):  # hold back incomplete multi-byte pieces, like TextIteratorStreamer
-                    yield text[len(shown):]
-                    shown = text
-            return
-        for s0 in range(0, len(ids), 2048):
-            eng.prefill(ids[s0:s0 + 2048], start_pos=s0, greedy=True)
-        eng.tune_attn_for(len(ids) + config.max_new_tokens)
-        eng.prepare_decode(greedy=True)  # a captured graph only in "graph" launch mode (engine.py LAUNCH)
-        out, shown = [], ""
-        for i in range(config.max_new_tokens):
-            t = int(eng.token.item())
-            if eos is not None and t == eos:
-                break
-            out.append(t)
-            n_out[0] += 1
-            text = tok.decode(out, skip_special_tokens=True)
-            if not text.endswith("�"):  # hold back incomplete multi-byte pieces, like TextIteratorStreamer
-                yield text[len(shown):]
-                shown = text
-            if i + 1 < config.max_new_tokens:
-                eng.replay(1)
-
-    def _engine_stream_sampled(self, ids, config, n_out):
-        """The reference's default request (sampling + repetition penalty) on the fused engine: tokens are chosen on the
-        device — by the engine's native sampler where it covers the request, else by runtime.engine.DeviceSampler — and
-        handed to the text stream one at a time."""
+        """The request on the fused engine, handed to the text stream one token at a time. The reference's default
+        request (sampling + repetition penalty), the other penalties, a bias and a guide need a sampler: tokens are chosen
+        on the device, by the engine's native sampler where it covers the request, else by runtime.request.DeviceSampler
+        (a penalty or a bias with temperature 0 is a greedy request over the penalised scores: the sampler's argmax).
+        Everything else is the greedy chain."""
         from ...runtime.engine import iter_sampled_auto
 
-        eng, tok = self.engine, self.tokenizer
-        eos = tok.eos_token_id
-        if getattr(config, "logprobs", None) is not None:
-            yield from self._engine_stream_logprobs(
-                iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
-                                  do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
-                                  top_p=config.top_p, repetition_penalty=config.repetition_penalty,
-                                  logprobs=config.logprobs, streaming=self._streaming(config),
-                                  **self._sampler_controls(config)), n_out)
-            return
-        out, shown = [], ""
-        for new in iter_sampled_auto(eng, ids, config.max_new_tokens, eos=() if eos is None else (eos,), burst=1,
-                                     do_sample=config.do_sample, temperature=config.temperature, top_k=config.top_k,
-                                     top_p=config.top_p, repetition_penalty=config.repetition_penalty,
-                                     streaming=self._streaming(config), **self._sampler_controls(config)):
-            for t in new:
-                if eos is not None and t == eos:
-                    continue
-                out.append(t)
-                n_out[0] += 1
-            text = tok.decode(out, skip_special_tokens=True)
-            if not text.endswith("\ufffd"):  # hold back incomplete multi-byte pieces, like TextIteratorStreamer
-                yield text[len(shown):]
-                shown = text
+        eos = self.tokenizer.eos_token_id
+        ctl = self._sampler_controls(config)
+        common = dict(burst=1, eos=() if eos is None else (eos,), logprobs=getattr(config, "logprobs", None),
+                      streaming=self._streaming(config))
+        if config.do_sample or (config.repetition_penalty or 1.0) != 1.0 or ctl["presence_penalty"] \
+                or ctl["frequency_penalty"] or ctl["logit_bias"] or ctl["guide"] is not None:
+            bursts = iter_sampled_auto(self.engine, ids, config.max_new_tokens, do_sample=config.do_sample,
+                                       temperature=config.temperature, top_k=config.top_k, top_p=config.top_p,
+                                       repetition_penalty=config.repetition_penalty, **common, **ctl)
+        else:
+            bursts = self.engine.iter_generate(ids, config.max_new_tokens, **common)
+        yield from self._text_pieces(bursts, n_out)
 
     def _hf_stream(self, ids, config, n_out):
         import torch

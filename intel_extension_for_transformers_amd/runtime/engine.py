@@ -15,7 +15,10 @@ import torch
 
 from .. import _lib as L
 from .. import qbits
-from .streaming import StreamingConfig, plan_steps, plan_stream  # noqa: F401  (StreamingConfig: part of this module's API)
+from . import request
+# the request loops live in runtime/request.py; their public names stay part of this module's API, like StreamingConfig
+from .request import DeviceSampler, _controls, generate_sampled, iter_sampled, iter_sampled_auto, request_seed  # noqa: F401
+from .streaming import StreamingConfig, plan_steps, plan_stream  # noqa: F401
 
 
 ENGINE_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")  # the one list: engine_supports reads it, nothing else does
@@ -807,9 +810,7 @@ class WoqDecoderEngine:
         ids at that position. The text runs through `prefill_scored` in chunks of `chunk` tokens; one device-to-host
         copy at the end. Leaves `logprobs_on` and an installed sampler as they were."""
         ids = [int(t) for t in ids]
-        n, n_top = len(ids), int(logprobs)
-        if not 0 <= n_top <= self.LOGPROB_TOP:
-            raise ValueError("`logprobs` is a count of alternatives in [0, %d]" % self.LOGPROB_TOP)
+        n, n_top = len(ids), request._top_count(logprobs)
         if n < 2:
             raise RuntimeError("QBits: scoring needs at least 2 tokens (got %d)" % n)
         if n > self.cfg.max_ctx:
@@ -821,7 +822,7 @@ class WoqDecoderEngine:
         targets = ids[1:] + [-1]  # the last position has no next token: its row is dropped
         for s0 in range(0, n, int(chunk)):
             self.prefill_scored(ids[s0:s0 + chunk], targets[s0:s0 + chunk], start_pos=s0, greedy=False)
-        _, lps, top = self._records(0, n - 1, n_top)
+        _, lps, top = request._records(self, 0, n - 1, n_top)
         return lps, top
 
     def perplexity(self, ids, chunk=2048):
@@ -829,396 +830,14 @@ class WoqDecoderEngine:
         lps, _ = self.score(ids, chunk=chunk)
         return math.exp(-math.fsum(lps) / len(lps))
 
+    # ---- a whole request: runtime/request.py drives the engine --------------------------------------------------------
     def iter_generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=(), logprobs=None, streaming=None):
-        """Prompt pass + bursts of `burst` chained steps, yielding each burst's new tokens (the first one alone: it comes
-        from the prompt pass's tail). With a sampler installed the prompt is marked in the history first and every
-        token is the sampler's; without one this is the greedy chain. Stops after the first id in `eos` (kept).
-        `logprobs` = N in 0..20: recording is on for this call (the previous state returns afterwards) and every burst
-        is `(tokens, chosen_lps, top)` with `top` one list of N `(id, log-probability)` pairs per token, read back in
-        the burst's one synchronisation. `streaming` = a StreamingConfig: the request runs over a rolling KV cache
-        (`plan_stream`: bursts clipped at ctx_size, a `kv_shift` whenever the cache is full) and may be longer than
-        the cache; tokens and records are read at cache positions."""
-        if logprobs is None:
-            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, None, streaming)
-            return
-        n_top = int(logprobs)
-        if not 0 <= n_top <= self.LOGPROB_TOP:
-            raise ValueError("`logprobs` is a count of alternatives in [0, %d]" % self.LOGPROB_TOP)
-        before = self.logprobs_on
-        self.set_logprobs(True)
-        try:
-            yield from self._iter_generate(prompt_ids, max_new_tokens, chunk, burst, eos, n_top, streaming)
-        finally:
-            self.set_logprobs(before)
-
-    def _records(self, p0, k, n_top):
-        """rows p0 .. p0 + k - 1 of the token log and the three logs in ONE device-to-host copy"""
-        chosen, top_id, top_lp = self.logprob_log()
-        rows = slice(p0, p0 + k)
-        packed = torch.cat([self.token_log()[rows, None].double(), chosen[rows, None].double(),
-                            top_id[rows, :n_top].double(), top_lp[rows, :n_top].double()], dim=1).tolist()
-        toks = [int(r[0]) for r in packed]
-        top = [[(int(i), lp) for i, lp in zip(r[2:2 + n_top], r[2 + n_top:])] for r in packed]
-        return toks, [r[1] for r in packed], top
-
-    def _iter_generate(self, prompt_ids, max_new_tokens, chunk, burst, eos, n_top, streaming=None):
-        ids = [int(t) for t in prompt_ids]
-        geometry = self._request_geometry(len(ids), max_new_tokens, streaming)
-        if streaming is None:
-            yield from self._iter_planned(ids, max_new_tokens, chunk, burst, eos, n_top, geometry)
-            return
-        self.set_discarded(0)  # a request counts its dropped positions from 0; one without streaming always runs with 0
-        try:
-            yield from self._iter_planned(ids, max_new_tokens, chunk, burst, eos, n_top, geometry)
-        finally:
-            self.set_discarded(0)
-
-    def _iter_planned(self, ids, max_new_tokens, chunk, burst, eos, n_top, geometry):
-        n = len(ids)
-        ctx, n_keep, n_discard = geometry
-        if self.sampler_installed:
-            self.mark_seen(ids, clear=True)
-            if self.controls_installed:
-                self.mark_counts([], clear=True)  # prompt tokens do not count: the penalties are over generated ids
-            if self.guide_installed:  # where the request's text starts: after the prompt for a bad-words guide
-                self.guide_reset(self._guide.walk(self._guide_prefix, self._guide.prompt_state(ids)))
-            self.native_sampled_requests += 1
-        for s0 in range(0, n, chunk):
-            # the sampled tail marks its pick in the history, so with a sampler only the last chunk may end on it: an
-            # earlier chunk's throw-away token is neither prompt nor generated (the greedy argmax has no side effect)
-            # (and with recording on only the last chunk's tail leaves a record)
-            self.prefill(ids[s0:s0 + chunk], start_pos=s0,
-                         greedy=not (self.sampler_installed or n_top is not None) or s0 + chunk >= n)
-        self.tune_attn_for(n + max_new_tokens if ctx is None else min(ctx, n + max_new_tokens))
-        if max_new_tokens < 1:
-            return
-        eos = set(int(e) for e in eos)
-        first = int(self.token.item())  # the prompt pass's token
-        if n_top is None:
-            yield [first]
-        else:  # its record is row n - 1; the token log has no entry there (the prompt pass's pick does not log)
-            _, lps, top = self._records(n - 1, 1, n_top)
-            yield [first], lps, top
-        if first in eos:
-            return
-        if max_new_tokens > 1:
-            self.prepare_decode(greedy=True)
-        log = self.token_log()
-        for ev in plan_stream(n, max_new_tokens, ctx, n_keep, n_discard, burst):
-            if ev[0] == "shift":  # the cache is full: drop n_discard positions, the device position follows
-                self.kv_shift(n_keep, n_discard, ev[1])
-                continue
-            _, p0, k = ev  # p0 = cache position the next step feeds
-            self.replay(k)
-            if n_top is None:
-                new = log[p0:p0 + k].tolist()  # the burst's one host synchronisation
-            else:
-                new, lps, top = self._records(p0, k, n_top)  # the same, with the records in the copy
-            stop = next((j + 1 for j, t in enumerate(new) if t in eos), None)
-            if n_top is None:
-                yield new[:stop]
-            else:
-                yield new[:stop], lps[:stop], top[:stop]
-            if stop is not None:
-                return
+        """`request.iter_generate` over this engine: prompt pass + bursts of chained steps, yielding each burst's tokens."""
+        return request.iter_generate(self, prompt_ids, max_new_tokens, chunk, burst, eos, logprobs, streaming)
 
     def generate(self, prompt_ids, max_new_tokens, chunk=2048, burst=16, sampler=None, logprobs=None, streaming=None):
-        """Greedy decode: the prompt goes through the prefill pass in chunks of `chunk` tokens, then bursts of `burst`
-        steps chained on the device (one host read of the token log per burst). `sampler` = a dict of `set_sampler`
-        arguments: the same loop with the native sampler installed for this call (removed afterwards). `logprobs` = N
-        in 0..20: returns `(tokens, chosen_lps, top)` instead (see `iter_generate`). `streaming` = a StreamingConfig: a
-        rolling KV cache, so prompt + max_new_tokens may exceed the cache (see `iter_generate`)."""
-        if sampler is not None or logprobs is not None:
-            if sampler is not None:
-                self.set_sampler(**sampler)
-            try:
-                bursts = list(self.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, logprobs=logprobs,
-                                                 streaming=streaming))
-                if logprobs is None:
-                    return sum(bursts, [])
-                return tuple(sum((b[i] for b in bursts), []) for i in range(3))
-            finally:
-                if sampler is not None:
-                    self.clear_sampler()
-        ids = [int(t) for t in prompt_ids]
-        geometry = self._request_geometry(len(ids), max_new_tokens, streaming)
-        if streaming is None:
-            return self._generate_planned(ids, max_new_tokens, chunk, burst, geometry)
-        self.set_discarded(0)
-        try:
-            return self._generate_planned(ids, max_new_tokens, chunk, burst, geometry)
-        finally:
-            self.set_discarded(0)
-
-    def _generate_planned(self, ids, max_new_tokens, chunk, burst, geometry):
-        out = []
-        ctx, n_keep, n_discard = geometry
-        for s0 in range(0, len(ids), chunk):
-            self.prefill(ids[s0:s0 + chunk], start_pos=s0, greedy=True)
-        self.tune_attn_for(len(ids) + max_new_tokens if ctx is None else min(ctx, len(ids) + max_new_tokens))
-        if max_new_tokens < 1:
-            return out
-        out.append(int(self.token.item()))  # the prompt pass's token
-        self.prepare_decode(greedy=True)
-        log = self.token_log()
-        for ev in plan_stream(len(ids), max_new_tokens, ctx, n_keep, n_discard, burst):
-            if ev[0] == "shift":
-                self.kv_shift(n_keep, n_discard, ev[1])
-                continue
-            _, p0, k = ev  # p0 = cache position the next step feeds
-            self.replay(k)
-            out += log[p0:p0 + k].tolist()
-        return out
-
-
-class DeviceSampler:
-    """Next-token choice on the device from the engine's fp32 logits, with Hugging Face's semantics for the options the
-    reference's NeuralChat passes by default (`neural_chat/config.py:400-409`: do_sample=True, temperature 0.1, top_k 40,
-    top_p 0.75, repetition_penalty 1.1): RepetitionPenaltyLogitsProcessor over prompt + generated ids, then — when
-    sampling — TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper (min_tokens_to_keep 1) and
-    `torch.multinomial` on the softmax; argmax otherwise. Plain torch ops in HF's order (checked against the HF classes in
-    tests/test_api_cpu.py); no host synchronisation — the caller reads tokens back in bursts."""
-
-    def __init__(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, generator=None,
-                 presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None):
-        """`logit_bias` ({token id: value}, HF's single-token `sequence_bias`, -inf = a suppressed token) is added ahead
-        of the repetition penalty (where HF's SequenceBiasLogitsProcessor sits); `frequency_penalty` / `presence_penalty`
-        (OpenAI's: `s - frequency * count`, then `s - presence`, over the ids GENERATED so far) follow it; `min_p` is HF's
-        MinPLogitsWarper after top-p. The order of csrc/woq_sample.hip, every step one fp32 torch op."""
-        self.presence, self.frequency, self.min_p, self.bias = _controls(presence_penalty, frequency_penalty, min_p,
-                                                                         logit_bias)
-        if not 0.0 <= self.min_p <= 1.0:
-            raise ValueError("`min_p` has to be a float in the range [0, 1]")
-        self._bias_dev = None
-        self.do_sample = bool(do_sample)
-        self.temperature = float(temperature if temperature is not None else 1.0)
-        self.top_k = int(top_k or 0)
-        self.top_p = float(top_p if top_p is not None else 1.0)
-        self.penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        self.generator = generator
-        if self.do_sample and self.temperature <= 0:
-            raise ValueError("`temperature` has to be a strictly positive float when sampling")
-
-    def _adjusted(self, logits, history, generated):
-        """bias, repetition penalty, frequency and presence penalty: a new tensor, or `logits` itself when all are off"""
-        scores = logits
-        if self.bias:
-            if self._bias_dev is None or self._bias_dev[0].device != logits.device:
-                self._bias_dev = (torch.tensor(list(self.bias), dtype=torch.int64, device=logits.device),
-                                  torch.tensor(list(self.bias.values()), dtype=torch.float32, device=logits.device))
-            scores = logits.clone()
-            scores[self._bias_dev[0]] += self._bias_dev[1]
-        if self.penalty != 1.0 and history.numel():
-            scores = scores.clone() if scores is logits else scores
-            picked = scores[history]
-            scores[history] = torch.where(picked < 0, picked * self.penalty, picked / self.penalty)
-        if (self.frequency != 0.0 or self.presence != 0.0) and generated is not None and generated.numel():
-            counts = torch.bincount(generated, minlength=scores.numel())
-            hit = counts > 0
-            scores = torch.where(hit, scores - counts.to(torch.float32) * self.frequency, scores)
-            scores = torch.where(hit, scores - self.presence, scores)
-        return scores
-
-    def processed(self, logits, history, generated=None):
-        """logits fp32 [vocab]; history int64 [n] (prompt + generated so far); generated int64 [m] (the generated part
-        alone: what the frequency / presence penalties count) -> the scores sampling draws from."""
-        scores = self._adjusted(logits, history, generated)
-        scores = scores.clone() if scores is logits else scores
-        if not self.do_sample:
-            return scores
-        if self.temperature != 1.0:
-            scores = scores / self.temperature
-        if self.top_k > 0:
-            k = min(self.top_k, scores.numel())
-            kth = torch.topk(scores, k).values[-1]
-            scores = scores.masked_fill(scores < kth, float("-inf"))
-        if self.top_p < 1.0:
-            sorted_scores, order = torch.sort(scores, descending=False)
-            cum = sorted_scores.softmax(-1).cumsum(-1)
-            drop = cum <= (1.0 - self.top_p)
-            drop[-1] = False  # min_tokens_to_keep = 1
-            scores = scores.masked_fill(torch.zeros_like(drop).scatter(0, order, drop), float("-inf"))
-        if self.min_p > 0.0:
-            scores = self._min_p_cut(scores)
-        return scores
-
-    def _min_p_cut(self, scores):
-        """HF MinPLogitsWarper, min_tokens_to_keep 1: drop what is less likely than min_p x the likeliest token"""
-        probs = scores.softmax(-1)
-        drop = probs < self.min_p * probs.amax()
-        drop[probs.argmax()] = False
-        return scores.masked_fill(drop, float("-inf"))
-
-    TIE_SLACK = 8  # candidates kept beyond top_k so that values tied with the k-th one survive like in HF's mask
-
-    def __call__(self, logits, history, generated=None):
-        if self.do_sample and 0 < self.top_k < logits.numel():
-            return self._draw_top_k(logits, history, generated)
-        scores = self.processed(logits, history, generated)
-        if not self.do_sample:
-            return scores.argmax().reshape(1)
-        return torch.multinomial(scores.softmax(-1), 1, generator=self.generator)
-
-    def _draw_top_k(self, logits, history, generated=None):
-        """The same distribution as `processed` + softmax + multinomial when top_k is set, without sorting the whole
-        vocabulary: after the top-k mask only the candidates matter (everything else has probability 0), so the
-        temperature, the nucleus cut and the draw run on top_k (+ TIE_SLACK) values — a 32000-entry sort per token is
-        most of what sampling costs otherwise (profiles/r04n_*). Ties beyond TIE_SLACK entries at the k-th value would
-        be cut where HF keeps them all; fp32 logits do not tie in practice."""
-        scores = self._adjusted(logits, history, generated)
-        k2 = min(self.top_k + self.TIE_SLACK, scores.numel())
-        vals, idx = torch.topk(scores, k2)  # descending
-        if self.temperature != 1.0:
-            vals = vals / self.temperature
-        vals = vals.masked_fill(vals < vals[self.top_k - 1], float("-inf"))
-        if self.top_p < 1.0:  # HF: ascending order, drop while the cumulative probability <= 1 - top_p, keep the last
-            asc = vals.flip(0)
-            drop = asc.softmax(-1).cumsum(-1) <= (1.0 - self.top_p)
-            drop[-1] = False
-            vals = vals.masked_fill(drop.flip(0), float("-inf"))
-        if self.min_p > 0.0:
-            vals = self._min_p_cut(vals)
-        pick = torch.multinomial(vals.softmax(-1), 1, generator=self.generator)
-        return idx[pick]
-
-
-def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, chunk=2048, logprobs=None,
-                 streaming=None):
-    """Prompt pass + decode steps with the next token chosen by `sampler` on the device (sampling and / or repetition
-    penalty: the requests `generate`'s greedy chain does not cover). Every step is the engine's native step (logits
-    only) followed by a dozen small torch kernels; nothing synchronises until `burst` tokens are read back (1 for a
-    text stream). Yields each burst's new tokens; stops after the first id in `eos` (kept in the output, like HF).
-    `logprobs` = N in 0..20: yields `(tokens, chosen_lps, top)` like `WoqDecoderEngine.iter_generate`, the records
-    computed here with `torch.log_softmax` + `torch.topk` over the raw logits (ties in whatever order topk leaves).
-    `streaming` = a StreamingConfig: a rolling KV cache (`plan_stream`); the host sets the position of every step here,
-    so the shifts leave the device position alone."""
-    ids = [int(t) for t in prompt_ids]
-    n = len(ids)
-    ctx, n_keep, n_discard = engine._request_geometry(n, max_new_tokens, streaming)
-    if streaming is None:
-        yield from _iter_sampled_planned(engine, ids, max_new_tokens, sampler, eos, burst, chunk, logprobs, (ctx, 0, 0))
-        return
-    engine.set_discarded(0)
-    try:
-        yield from _iter_sampled_planned(engine, ids, max_new_tokens, sampler, eos, burst, chunk, logprobs,
-                                         (ctx, n_keep, n_discard))
-    finally:
-        engine.set_discarded(0)
-
-
-def _iter_sampled_planned(engine, ids, max_new_tokens, sampler, eos, burst, chunk, logprobs, geometry):
-    n = len(ids)
-    ctx, n_keep, n_discard = geometry
-    # the cache position every step after the first token feeds, with the shifts between them
-    steps = plan_steps(plan_stream(n, max_new_tokens, ctx, n_keep, n_discard, burst))
-    dev = engine.device
-    hist = torch.empty(n + max_new_tokens, dtype=torch.int64, device=dev)
-    hist[:n] = torch.tensor(ids, dtype=torch.int64, device=dev)
-    for s0 in range(0, n, chunk):
-        engine.prefill(ids[s0:s0 + chunk], start_pos=s0, greedy=False)
-    engine.tune_attn_for(n + max_new_tokens if ctx is None else min(ctx, n + max_new_tokens))
-    eos = set(int(e) for e in eos)
-    n_top = None
-    if logprobs is not None:
-        n_top = min(int(logprobs), engine.cfg.vocab)
-        if not 0 <= int(logprobs) <= L.LOGPROB_TOP:
-            raise ValueError("`logprobs` is a count of alternatives in [0, %d]" % L.LOGPROB_TOP)
-        rec = torch.empty(max(max_new_tokens, 1), 1 + 2 * n_top, dtype=torch.float64, device=dev)
-    done, made, feed = False, 0, n  # feed = cache position of the next step (n + made until a shift)
-    while not done and made < max_new_tokens:
-        k = min(burst, max_new_tokens - made)
-        for _ in range(k):
-            if made > 0:
-                ev = next(steps)
-                if ev[0] == "shift":  # the cache is full: drop n_discard positions, then feed n_cached - n_discard
-                    engine.kv_shift(n_keep, n_discard, ev[1], move_pos=False)
-                    ev = next(steps)
-                    engine.pos.fill_(ev[1])
-                engine.step(greedy=False)  # logits of the token just chosen, at cache position ev[1]
-                feed = ev[1] + 1
-            tok = sampler(engine.logits, hist[:n + made], hist[n:n + made])
-            if n_top is not None:  # the raw distribution's view of the pick and of its best ids
-                lsm = torch.log_softmax(engine.logits, -1)
-                rec[made, 0] = lsm[tok[0]]
-                if n_top:
-                    best = torch.topk(engine.logits, n_top).indices
-                    rec[made, 1:1 + n_top] = best
-                    rec[made, 1 + n_top:] = lsm[best]
-            hist[n + made] = tok[0]
-            engine.token.copy_(tok.to(torch.int32))
-            engine.pos.fill_(feed)
-            made += 1
-        new = hist[n + made - k:n + made].tolist()  # the burst's one host synchronisation
-        for j, t in enumerate(new):
-            if t in eos:
-                new, done = new[:j + 1], True
-                break
-        if n_top is None:
-            yield new
-            continue
-        rows = rec[made - k:made - k + len(new)].tolist()
-        yield new, [r[0] for r in rows], [[(int(i), lp) for i, lp in zip(r[1:1 + n_top], r[1 + n_top:])] for r in rows]
-
-
-def _controls(presence_penalty, frequency_penalty, min_p, logit_bias):
-    """(presence, frequency, min_p, {int id: float value}) with None = neutral"""
-    return (float(presence_penalty or 0.0), float(frequency_penalty or 0.0), float(min_p or 0.0),
-            {int(k): float(v) for k, v in dict(logit_bias or {}).items()})
-
-
-def request_seed():
-    """One 63-bit value from torch's default CPU generator: `torch.manual_seed` makes sampled requests reproducible."""
-    return int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
-
-
-def iter_sampled_auto(engine, prompt_ids, max_new_tokens, eos=(), burst=16, chunk=2048, do_sample=False,
-                      temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, logprobs=None, presence_penalty=0.0,
-                      frequency_penalty=0.0, min_p=0.0, logit_bias=None, seed=None, guide=None, streaming=None):
-    """A sampling / repetition-penalty request: on the native sampler (chained bursts, graph replays) when
-    `native_sampler_supports` says so, else `iter_sampled` with a `DeviceSampler`. The sampler is removed after the
-    request, so the next greedy request runs the untouched greedy path: in a `finally` of this generator, which runs when
-    the stream is exhausted, closed or collected — a consumer that stops early and keeps the generator alive should
-    `close()` it. Installing and removing each drop the captured graphs, so a sampled request and the greedy request
-    after it each pay one capture. `seed` = None: `request_seed()`; a given seed makes the request reproducible (on the
-    torch sampler it seeds a device generator of the request's own). `guide` = a TokenGuide the request follows
-    (`set_guide`); it runs on the native sampler only, so a request it cannot take raises. `streaming` = a
-    StreamingConfig: the request runs over a rolling KV cache on either path."""
-    pres, freq, min_p, bias = _controls(presence_penalty, frequency_penalty, min_p, logit_bias)
-    opts = dict(do_sample=bool(do_sample), temperature=1.0 if temperature is None else temperature, top_k=top_k or 0,
-                top_p=1.0 if top_p is None else top_p,
-                repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
-                presence_penalty=pres, frequency_penalty=freq, min_p=min_p, logit_bias=bias)
-    if opts["do_sample"] and float(opts["temperature"]) <= 0:
-        raise ValueError("`temperature` has to be a strictly positive float when sampling")
-    if guide is not None and not engine.native_sampler_supports(guide=guide, **opts):
-        raise RuntimeError("QBits: a token guide runs on the native sampler, which does not take this request "
-                           "(tensor parallel, another vocabulary, or sampling options it does not cover)")
-    if not engine.native_sampler_supports(**opts):
-        gen = None
-        if seed is not None:
-            gen = torch.Generator(device=engine.device)
-            gen.manual_seed(int(seed) & (2 ** 63 - 1))
-        yield from iter_sampled(engine, prompt_ids, max_new_tokens, DeviceSampler(generator=gen, **opts), eos=eos,
-                                burst=burst, chunk=chunk, logprobs=logprobs, streaming=streaming)
-        return
-    try:  # (inside: the sampler may be installed already when the controls are refused)
-        engine.set_sampler(seed=request_seed() if seed is None else int(seed), **opts)
-        if guide is not None:
-            engine.set_guide(guide)
-        yield from engine.iter_generate(prompt_ids, max_new_tokens, chunk=chunk, burst=burst, eos=eos,
-                                        logprobs=logprobs, streaming=streaming)
-    finally:
-        engine.clear_sampler()
-
-
-def generate_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), on_tokens=None, burst=16, chunk=2048):
-    """`iter_sampled` to the end; `on_tokens(list)` receives each burst. Returns the new tokens."""
-    out = []
-    for new in iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=eos, burst=burst, chunk=chunk):
-        out += new
-        if on_tokens is not None:
-            on_tokens(new)
-    return out
+        """`request.generate` over this engine: `iter_generate` to the end -> the new tokens."""
+        return request.generate(self, prompt_ids, max_new_tokens, chunk, burst, sampler, logprobs, streaming)
 
 
 def _device_view(ptr, shape, device, typestr="<f4"):

@@ -340,7 +340,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     # rolling KV cache: Neural Speed's generate keywords (reference docs/streamingllm.md). With any of them given the
     # request may outgrow the cache: no larger engine is built, the engine drops n_discard positions after its n_keep
     # sinks whenever ctx_size positions are cached (runtime.streaming). HF's loop has no counterpart.
-    from ...runtime.streaming import plan_stream, streaming_from_keywords
+    from ...runtime.streaming import streaming_from_keywords
 
     streaming = streaming_from_keywords(kwargs.pop("ctx_size", None), kwargs.pop("n_keep", None),
                                         kwargs.pop("n_discard", None))
@@ -417,8 +417,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
             if streaming is not None:
                 raise RuntimeError(no_stream % "not a model the engine takes")
             return hf_generate(inputs, generation_config=generation_config, **kwargs)
-    # (ctx_size, n_keep, n_discard), checked against this engine and prompt; (None, 0, 0) without a rolling cache
-    geometry = eng._request_geometry(n_in, max_new, streaming)
+    eng._request_geometry(n_in, max_new, streaming)  # raises what this engine and prompt cannot serve, before anything is streamed
     if max_new < 1:
         return (ids, []) if want_latency else ids
     if bad_words:  # HF's NoBadWordsLogitsProcessor as a guide; what the engine cannot take keeps HF's loop
@@ -441,86 +440,34 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
         streamer.put(ids.cpu())
     import time
 
-    def run_sampled():
-        """prompt pass + steps whose next token the device sampler picks; returns (tokens, per-token latency)."""
-        from ...runtime.engine import iter_sampled_auto
+    from ...runtime.engine import iter_sampled_auto
 
-        latency, mark = [], [time.time()]
-
-        def on_tokens(new):
+    def run_once():
+        """The request over the engine's burst iterator -> (tokens, per-token latency). Sampling / penalties / a guide: the
+        native sampler inside the chained steps where it covers the request (WoqDecoderEngine.native_sampler_supports),
+        else a native step + the torch DeviceSampler per token; everything else: the greedy chain. Tokens are read back
+        in bursts (one host synchronisation each; a stop token is noticed at the end of its burst), one token per burst
+        with a streamer (latency first). The first burst is the prompt pass's token; a burst's tokens share its average."""
+        burst = 1 if streamer is not None else 16
+        if sampled:
+            bursts = iter_sampled_auto(eng, prompt, max_new, eos=eos, burst=burst, do_sample=opt("do_sample", False),
+                                       temperature=opt("temperature", 1.0), top_k=opt("top_k", 0), top_p=opt("top_p", 1.0),
+                                       repetition_penalty=opt("repetition_penalty", 1.0), min_p=min_p, logit_bias=bias,
+                                       guide=guide, streaming=streaming)
+        else:
+            bursts = eng.iter_generate(prompt, max_new, burst=burst, eos=eos, streaming=streaming)
+        out, latency, mark = [], [], time.time()
+        for new in bursts:  # the one place a burst's tokens are stamped and handed to the streamer
             now = time.time()
-            latency.extend([(now - mark[0]) / len(new)] * len(new))
-            mark[0] = now
+            latency += [(now - mark) / len(new)] * len(new)
+            mark = now
+            out += new
             if streamer is not None:
                 for t in new:
                     streamer.put(torch.tensor([t]))
-
-        # the native sampler inside the engine's chained steps where it covers the request (runtime.engine.
-        # WoqDecoderEngine.native_sampler_supports), else a native step + the torch DeviceSampler per token
-        out = []
-        for new in iter_sampled_auto(eng, prompt, max_new, eos=eos, burst=1 if streamer is not None else 16,
-                                     do_sample=opt("do_sample", False), temperature=opt("temperature", 1.0),
-                                     top_k=opt("top_k", 0), top_p=opt("top_p", 1.0),
-                                     repetition_penalty=opt("repetition_penalty", 1.0), min_p=min_p,
-                                     logit_bias=bias, guide=guide, streaming=streaming):
-            out += new
-            on_tokens(new)
         return out, latency
 
-    def run_once():
-        """prompt pass + chained decode steps; returns (tokens, per-token latency)."""
-        if sampled:
-            return run_sampled()
-        latency = []
-        tic = time.time()
-        for s0 in range(0, n_in, 2048):
-            eng.prefill(prompt[s0:s0 + 2048], start_pos=s0, greedy=True)
-        eng.tune_attn_for(n_in + max_new if geometry[0] is None else min(geometry[0], n_in + max_new))
-        if max_new > 1:
-            eng.prepare_decode(greedy=True)  # a captured graph only in "graph" launch mode (engine.py LAUNCH)
-        # Tokens are read back in bursts: the steps chain on the device and log their tokens (engine.token_log), so the
-        # host synchronises once per burst instead of once per token. A stop token is noticed at the end of its burst —
-        # the few steps run past it are discarded. With a streamer the burst is one token (latency first).
-        out = [int(eng.token.item())]  # the prompt pass's token (the .item() synchronises)
-        latency.append(time.time() - tic)
-        if streamer is not None:
-            streamer.put(torch.tensor(out))
-        burst = 1 if streamer is not None else 16
-        log = eng.token_log()
-        done = out[0] in eos
-        for ev in plan_stream(n_in, max_new, *geometry, burst=burst):
-            if done:
-                break
-            if ev[0] == "shift":  # rolling cache: it is full, drop n_discard positions (the device position follows)
-                eng.kv_shift(geometry[1], geometry[2], ev[1])
-                continue
-            _, p0, k = ev  # p0 = cache position the next step feeds
-            tic = time.time()
-            eng.replay(k)
-            new = log[p0:p0 + k].tolist()  # one host synchronisation per burst
-            per_token = (time.time() - tic) / k  # the burst's steps chain on the device: its tokens share the average
-            for t in new:
-                latency.append(per_token)
-                out.append(t)
-                if streamer is not None:
-                    streamer.put(torch.tensor([t]))
-                if t in eos:
-                    done = True
-                    break
-        return out, latency
-
-    if streaming is None:
-        run_once_checked = run_once
-    else:
-        def run_once_checked():
-            """the request with the dropped-position count starting from 0, and back at 0 for whatever runs next"""
-            eng.set_discarded(0)
-            try:
-                return run_once()
-            finally:
-                eng.set_discarded(0)
-
-    out, latency = run_once_checked()
+    out, latency = run_once()
     # The decode step reports what it cannot raise from the device through a sticky status word; the host has just
     # synchronised on the last burst, so one more 4-byte read is free. bit 0: an attention workgroup of the fused
     # qkv + attention launch gave up waiting for its head's q / k / v (GPU preempted / shared / under a debugger for
@@ -546,7 +493,7 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
             raise RuntimeError("QBits: the decode engine reported status %d (bit 0: in-launch hand-off timed out, "
                                "bit 1: position beyond max_ctx)%s" % (st, "; tokens already streamed are not reliable"
                                                                      if streamer is not None else ""))
-        out, latency = run_once_checked()  # same request, separate launches
+        out, latency = run_once()  # same request, separate launches
         st = eng.status()
         if st != 0:
             eng.clear_status()

@@ -125,6 +125,18 @@ def test_generate_streams_past_the_cache_and_equals_the_chain(tiny, chain, launc
     assert eng.generate(PROMPT, 20, burst=burst, streaming=_streaming()) == eng.generate(PROMPT, 20, burst=burst)
 
 
+@pytest.mark.parametrize("launch", ["graph", "eager"])
+def test_one_and_two_token_requests_return_the_chains_first_tokens(tiny, chain, launch):
+    """`generate` shares the iterator's rule: decode is prepared (a graph captured) only when more than one token is
+    asked for."""
+    eng = tiny[0]
+    eng.launch = launch
+    eng.captured = False
+    eng.clear_status()
+    assert eng.generate(PROMPT, 1) == chain[0][:1] and eng.status() == 0
+    assert eng.generate(PROMPT, 2) == chain[0][:2] and eng.status() == 0
+
+
 def test_without_streaming_the_request_is_refused_as_before(tiny):
     eng = tiny[0]
     for call in (lambda: eng.generate(PROMPT, N_NEW), lambda: list(eng.iter_generate(PROMPT, N_NEW)),
