@@ -103,6 +103,25 @@ WOQ_API int woq_gptq_sweep(float* w_dev, const float* u_dev, int K, int N, int c
                            int params_given, const int32_t* col_group_dev, int8_t* q_dev, float* scale_dev,
                            int8_t* zp_dev, float* err_dev, void* stream);
 
+/* the two searches of AWQ calibration (no reference counterpart: the reference hands AWQ to neural_compressor; algorithm
+ * and layout: csrc/woq_awq.hip, DESIGN.md "AWQ"). w fp32 [K,N] in working order (Linear.weight.T); Q = the RTN rule of
+ * woq_quantize_to_packed_weight at bits 2 | 3 | 4 | 8, sym or asym, groups of `group` rows (the last may be short).
+ * Both are asynchronous on `stream`, allocate nothing and modify no input.
+ *
+ * woq_awq_scale_delta: d_out fp32 [K,N] = diag(1/s) Q(diag(s) W) - W for one candidate s fp32 [K] (every s[k] nonzero)
+ * of the scale search; each product, quotient and difference is rounded on its own. group <= 0 or > K = one group per
+ * column. The loss tr(D^T H D) is the caller's GEMM. */
+WOQ_API int woq_awq_scale_delta(const float* w_dev, const float* s_dev, int K, int N, int group, int bits, int asym,
+                                float* d_out_dev, void* stream);
+
+/* woq_awq_clip_search: per column n and group g, candidates c_j = 1 - j / n_grid, j < n_cand <= n_grid: the group is
+ * clamped to +-c_j max|w| (sym) or [c_j min(min w, 0), c_j max(max w, 0)] (asym), d = Q(clamped) - w,
+ * losses fp32 [n_cand,G,N][j][g][n] = d^T G d with G the group's diagonal block of h fp32 [K,K] (symmetric; row stride
+ * ldh >= K, in elements); best int32 [G,N] = the first minimum; w_out fp32 [K,N] = w clamped by it. group: 32, 64 or 128. */
+WOQ_API int woq_awq_clip_search(const float* w_dev, const float* h_dev, int ldh, int K, int N, int group, int bits,
+                                int asym, int n_grid, int n_cand, int32_t* best_dev, float* losses_dev,
+                                float* w_out_dev, void* stream);
+
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device
  * memory from the host. */

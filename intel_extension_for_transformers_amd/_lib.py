@@ -98,7 +98,7 @@ EXPORTS = [
     "woq_engine_set_sampler_controls", "woq_engine_sampler_counts", "woq_engine_sampler_count_ptr",
     "woq_engine_set_guide", "woq_engine_guide_reset", "woq_engine_guide_state_ptr",
     "woq_engine_kv_shift", "woq_engine_discarded_ptr", "woq_engine_discarded_set", "woq_gptq_sweep",
-    "woq_engine_set_layer_extras",
+    "woq_engine_set_layer_extras", "woq_awq_scale_delta", "woq_awq_clip_search",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -143,6 +143,8 @@ def lib():
     L.woq_quantize_to_packed_weight.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, cs, vp]
     L.woq_dequantize_packed_weight.argtypes = [vp, ctypes.POINTER(BlobHeader), vp, ci, vp]
     L.woq_gptq_sweep.argtypes = [vp, vp] + [ci] * 8 + [vp] * 6
+    L.woq_awq_scale_delta.argtypes = [vp, vp] + [ci] * 5 + [vp, vp]
+    L.woq_awq_clip_search.argtypes = [vp, vp] + [ci] * 8 + [vp] * 4
     L.woq_read_header.argtypes = [vp, ctypes.POINTER(BlobHeader), vp]
     L.woq_blob_extract.argtypes = [vp, ctypes.POINTER(BlobHeader), ci, vp, vp]
     L.woq_linear.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, vp, ci, ci, ci, vp]

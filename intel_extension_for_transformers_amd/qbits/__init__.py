@@ -16,6 +16,7 @@ __all__ = [
     "woq_linear", "repack_quantized_weight", "quantize_to_packed_weight", "dequantize_packed_weight",
     "acquire_packed_weight_info", "get_packed_weight_size", "set_woq_workspace", "set_qbits_threads",
     "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
+    "awq_scale_delta", "awq_clip_search",
 ]
 
 
@@ -145,6 +146,48 @@ def gptq_sweep(w, u, c0, rows, group, bits, asym, q, scale, zp, err, params_give
     L.check(L.lib().woq_gptq_sweep(_ptr(w), _ptr(u), k, n, int(c0), int(rows), int(group), int(bits), int(bool(asym)),
                                    int(bool(params_given)), _ptr(col_group), _ptr(q), _ptr(scale), _ptr(zp), _ptr(err),
                                    L.stream_ptr()))
+
+
+def _f32_dev(t, shape):
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+
+
+def awq_scale_delta(w, s, group, bits, asym, out=None):
+    """D = diag(1 / s) Q(diag(s) W) - W for one candidate of AWQ's scale search (woq_awq_scale_delta, csrc/woq_awq.hip;
+    no reference counterpart): w fp32 [K, N] (working order, Linear.weight.T), s fp32 [K] (nonzero), Q the RTN rule of
+    `quantize_to_packed_weight` at (bits, group, asym). Returns `out` fp32 [K, N] (allocated when None)."""
+    k, n = w.shape
+    if out is None:
+        out = torch.empty_like(w)
+    if not (_f32_dev(w, (k, n)) and _f32_dev(s, (k,)) and _f32_dev(out, (k, n))):
+        raise RuntimeError("QBits: awq_scale_delta takes contiguous fp32 device tensors w [K,N], s [K], out [K,N]")
+    L.check(L.lib().woq_awq_scale_delta(_ptr(w), _ptr(s), k, n, int(group), int(bits), int(bool(asym)), _ptr(out),
+                                        L.stream_ptr()))
+    return out
+
+
+def awq_clip_search(w, h, group, bits, asym, n_grid=20, n_cand=10, w_out=None, losses=None):
+    """AWQ's clip search over every (group, column) cell of w fp32 [K, N] (woq_awq_clip_search, csrc/woq_awq.hip; no
+    reference counterpart): candidates c_j = 1 - j / n_grid, j < n_cand; the loss of a cell is d^T G d with
+    d = Q(clamped) - w and G the group's diagonal block of h fp32 [K, K] (symmetric; a view with unit column stride is fine).
+    group: 32, 64 or 128. -> (best int32 [G, N], losses fp32 [n_cand, G, N], w_out fp32 [K, N] = w clamped by best)."""
+    k, n = w.shape
+    g = (k + group - 1) // group if group > 0 else 0
+    if w_out is None:
+        w_out = torch.empty_like(w)
+    if not (_f32_dev(w, (k, n)) and _f32_dev(w_out, (k, n)) and h.is_cuda and h.dtype == torch.float32
+            and tuple(h.shape) == (k, k) and h.stride(1) == 1 and h.stride(0) >= k):
+        raise RuntimeError("QBits: awq_clip_search takes fp32 device tensors w [K,N] and w_out [K,N] (contiguous) and "
+                           "h [K,K] (unit column stride)")
+    best = torch.empty(g, n, dtype=torch.int32, device=w.device)
+    if losses is None:
+        losses = torch.empty(int(n_cand), g, n, dtype=torch.float32, device=w.device)
+    elif not _f32_dev(losses, (int(n_cand), g, n)):
+        raise RuntimeError("QBits: awq_clip_search: losses must be a contiguous fp32 device tensor [n_cand,G,N]")
+    L.check(L.lib().woq_awq_clip_search(_ptr(w), _ptr(h), int(h.stride(0)), k, n, int(group), int(bits),
+                                        int(bool(asym)), int(n_grid), int(n_cand), _ptr(best), _ptr(losses),
+                                        _ptr(w_out), L.stream_ptr()))
+    return best, losses, w_out
 
 
 def dequantize_packed_weight(compressed_weight, dequantize_weight, transpose, compute_type, weight_type, scale_type):

@@ -1,0 +1,273 @@
+"""AWQ calibration on the device: `from_pretrained(fp_model, quantization_config=AwqConfig(...))`.
+
+The reference hands this step to neural_compressor (external, CPU; reference utils.py:531-702); here the algorithm
+(Lin et al. 2023, as in llm-awq / AutoAWQ, with the linear-output objective) is restated — tests/awq_reference.py is its
+float64 statement. The loss is the squared output error of the linears, so a block's activations enter only through
+H = X^T X / T and a = mean |x| per distinct input tensor (q / k / v share one, gate / up share one); none are kept.
+
+  auto_scale   per absorb group (the linears that share an input, and the op that produces it): 20 candidates
+               s = a^(i / 20), normalised; loss = sum over the linears of tr(D^T H D), D = diag(1 / s) Q(diag(s) W) - W
+               from qbits.awq_scale_delta (csrc/woq_awq.hip), the trace one GEMM; every group of a block is searched
+               against the fp weights, then the scales are folded in: the linears' input columns * s, the producing op
+               / s (Llama-class layouts only)
+  auto_clip    per linear (q_proj / k_proj leaves skipped, AutoAWQ's rule) under H' = diag(1 / s) H diag(1 / s):
+               qbits.awq_clip_search picks each (group, column) cell's clamp out of 10 candidates and clamps the weight
+  quantise     the scaled, clamped weight goes through QuantizedLinearQBits.set_fp_weights_bias, the device RTN: the
+               result is a plain RTN blob plus changed norm / projection weights, nothing new for save / load or the
+               engine
+
+torch does the GEMM-shaped parts (H += X^T X, H @ D) through rocBLAS on purpose, as in gptq.py.
+"""
+import logging
+
+import torch
+
+from .... import qbits
+from .gptq import _BITS, _Stop, _block_linears, _data_source, _decoder_blocks, _is_conv1d, _run_block
+from .gptq import calibration_batches
+from .nn.modules import QuantizedLinearQBits
+
+logger = logging.getLogger(__name__)
+
+N_GRID = 20  # candidates of the scale search, r_i = i / N_GRID; the clip search's c_j = 1 - j / N_GRID
+N_CLIP = 10  # candidates of the clip search
+CLIP_GROUPS = (32, 64, 128)  # the group sizes whose Gram block the clip kernel keeps in LDS
+SCALE_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")  # the attribute layout the scale folding knows
+_NO_CLIP = ("q_proj", "k_proj")
+
+# absorb groups of a Llama-class block: (the scaled linears, the op that absorbs 1 / s)
+_GROUPS = (
+    (("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "input_layernorm"),
+    (("self_attn.o_proj",), "self_attn.v_proj"),
+    (("mlp.gate_proj", "mlp.up_proj"), "post_attention_layernorm"),
+    (("mlp.down_proj",), "mlp.up_proj"),
+)
+# linears of such a block that see the same input tensor as another: the statistics are taken once
+_SAME_INPUT = {"self_attn.k_proj": "self_attn.q_proj", "self_attn.v_proj": "self_attn.q_proj",
+               "mlp.up_proj": "mlp.gate_proj"}
+
+
+def _model_type(model):
+    return getattr(getattr(model, "config", None), "model_type", None) or type(model).__name__
+
+
+def _check_options(model, config):
+    for opt in ("use_double_quant", "layer_wise"):
+        if getattr(config, opt, False):
+            raise NotImplementedError("AWQ on the MI355X path does not implement %s" % opt)
+    if config.weight_dtype not in _BITS:
+        raise NotImplementedError("AWQ quantises to the integer weight types (int4_clip, int8), not weight_dtype=%s"
+                                  % config.weight_dtype)
+    try:
+        _data_source(config)
+    except NotImplementedError:
+        raise NotImplementedError(
+            "AwqConfig calibration is not part of the MI355X hot path without calibration data (dataset=%r is not "
+            "downloaded): pass calib_dataloader= (an iterable of input_ids tensors) or dataset=[texts] with tokenizer="
+            % (getattr(config, "dataset", None),)) from None
+    _decoder_blocks(model)
+    if config.auto_scale and _model_type(model) not in SCALE_MODEL_TYPES:
+        raise NotImplementedError("AWQ auto_scale folds scales into Llama-class blocks (model_type %s), not model type "
+                                  "%s: use auto_scale=False" % (" / ".join(SCALE_MODEL_TYPES), _model_type(model)))
+    if config.auto_clip and config.group_size not in CLIP_GROUPS:
+        raise NotImplementedError("AWQ auto_clip keeps a group's Gram block on chip and takes group_size 32, 64 or 128, "
+                                  "not group_size=%s: use auto_clip=False" % config.group_size)
+
+
+def validate_awq_request(model, config):
+    """Everything about a request that can be refused without touching a device."""
+    _check_options(model, config)
+
+
+def normalised_scale(a, i, n_grid=N_GRID):
+    """candidate i of the scale search from a = mean |x| [K]: clamp(a^(i / n_grid), 1e-4) / sqrt(max min)"""
+    s = a.pow(i / n_grid).clamp_(min=1e-4)
+    return s / (s.max() * s.min()).sqrt()
+
+
+def _kn(m):
+    """the linear's weight as fp32 [K, N], a fresh contiguous tensor"""
+    w = m.weight.data if _is_conv1d(m) else m.weight.data.t()
+    return w.to(torch.float32).clone(memory_format=torch.contiguous_format)
+
+
+def search_scale(weights_kn, h, a, group, bits, asym):
+    """the scale search of one absorb group: weights_kn = the fp32 [K, N] weights of its linears, h [K, K], a [K] ->
+    (best index, s [K], losses list)"""
+    losses = []
+    d = [torch.empty_like(w) for w in weights_kn]
+    for i in range(N_GRID):
+        s = normalised_scale(a, i).contiguous()
+        loss = 0.0
+        for w, di in zip(weights_kn, d):
+            qbits.awq_scale_delta(w, s, group, bits, asym, out=di)
+            loss += float((di * (h @ di)).sum(dtype=torch.float64))
+        losses.append(loss)
+    best = min(range(N_GRID), key=lambda i: (losses[i], i))  # the first minimum
+    return best, normalised_scale(a, best), losses
+
+
+def fold_scale(block, names, prev, s):
+    """Fold s [K] into the block, function-preserving: the input columns of the linears `names` * s, the op `prev` that
+    produces their input / s (a norm's weight; a linear's output rows and bias)."""
+    for name in names:
+        m = block.get_submodule(name)
+        m.weight.data.mul_(s.to(m.weight.dtype)[None, :])
+    p = block.get_submodule(prev)
+    sp = s.to(p.weight.dtype)
+    if isinstance(p, torch.nn.Linear):
+        p.weight.data.div_(sp[:, None])
+        if p.bias is not None:
+            p.bias.data.div_(s.to(p.bias.dtype))
+    else:
+        p.weight.data.div_(sp)
+
+
+def apply_scales(block, scales):
+    """`scales` {group index: s}: fold every searched scale of a block in (see _GROUPS)"""
+    for gi, s in scales.items():
+        names, prev = _GROUPS[gi]
+        fold_scale(block, names, prev, s)
+
+
+def _scale_groups(block, linears, where):
+    """the absorb groups of this block that can be searched: every member among `linears`; a group whose producing op
+    is a linear only where that linear's outputs are the group's inputs one to one (o_proj after v_proj: not under
+    grouped-query attention, AutoAWQ's rule)"""
+    have = {name for name, _ in linears}
+    out = []
+    for gi, (names, prev) in enumerate(_GROUPS):
+        if not all(n in have for n in names):
+            logger.info("AWQ %s: absorb group %s skipped (not every linear is quantised)", where, "/".join(names))
+            continue
+        p = block.get_submodule(prev)
+        if isinstance(p, torch.nn.Linear):
+            if prev not in have:
+                logger.info("AWQ %s: absorb group %s skipped (%s is not quantised)", where, names[0], prev)
+                continue
+            if p.out_features != block.get_submodule(names[0]).in_features:
+                # AutoAWQ compares the two weights' shapes, the same test wherever heads * head_dim = hidden
+                logger.info("AWQ %s: %s scale skipped (grouped-query attention: %s has %d outputs for %d inputs)",
+                            where, names[0], prev, p.out_features, block.get_submodule(names[0]).in_features)
+                continue
+        out.append(gi)
+    return out
+
+
+@torch.no_grad()
+def awq_quantize_model(model, config, device="cuda"):
+    """Quantise every eligible linear of every decoder block of an fp model with AWQ, in place. Block by block: forward
+    hooks accumulate X^T X and sum |x| per distinct input (fp32, on the device) while the block runs over the calibration
+    samples; scales are searched and folded in, clamps searched and applied, every linear replaced by its RTN blob; the
+    block runs again, quantised, to produce the next block's inputs. lm_head and whatever else `llm_int8_skip_modules`
+    names stay."""
+    _check_options(model, config)
+    batches = calibration_batches(config)
+    path, blocks = _decoder_blocks(model)
+    skip = list(getattr(config, "llm_int8_skip_modules", None) or [])
+    bits = _BITS[config.weight_dtype]
+    asym = not bool(config.sym)
+    group = config.group_size
+    llama = _model_type(model) in SCALE_MODEL_TYPES
+    model.to(device)
+    model.eval()
+
+    inputs = []
+
+    def grab(_module, args, kwargs):
+        inputs.append((args, kwargs))
+        raise _Stop()
+
+    handle = blocks[0].register_forward_pre_hook(grab, with_kwargs=True)
+    use_cache = getattr(model.config, "use_cache", None) if hasattr(model, "config") else None
+    try:
+        if use_cache is not None:
+            model.config.use_cache = False
+        for ids in batches:
+            try:
+                model(input_ids=ids.to(device))
+            except _Stop:
+                pass
+    finally:
+        handle.remove()
+        if use_cache is not None:
+            model.config.use_cache = use_cache
+
+    tf32 = torch.backends.cuda.matmul.allow_tf32
+    torch.backends.cuda.matmul.allow_tf32 = False  # H += X^T X and the loss H @ D are fp32 GEMMs
+    try:
+        for li, block in enumerate(blocks):
+            where = "%s.%d" % (path, li)
+            linears = _block_linears(block, where, skip)
+            source = {name: (_SAME_INPUT.get(name, name) if llama else name) for name, _ in linears}
+            have = {name for name, _ in linears}
+            source = {name: (src if src in have else name) for name, src in source.items()}
+            gram, asum, count, hooks = {}, {}, {}, []
+            for name, m in linears:
+                if source[name] != name:
+                    continue
+                kdim = m.weight.shape[0] if _is_conv1d(m) else m.in_features
+                gram[name] = torch.zeros(kdim, kdim, dtype=torch.float32, device=device)
+                asum[name] = torch.zeros(kdim, dtype=torch.float32, device=device)
+                count[name] = 0
+
+                def accumulate(_m, args, _out, name=name):
+                    x = args[0].reshape(-1, args[0].shape[-1]).float()
+                    gram[name].addmm_(x.t(), x)
+                    asum[name].add_(x.abs().sum(0))
+                    count[name] += x.shape[0]
+
+                hooks.append(m.register_forward_hook(accumulate))
+            _run_block(block, inputs)
+            for hk in hooks:
+                hk.remove()
+            for name in gram:
+                gram[name].div_(max(1, count[name]))
+                asum[name].div_(max(1, count[name]))
+
+            # auto_scale: every group against the fp weights, then all of them folded in
+            in_scale = {}
+            if config.auto_scale:
+                scales = {}
+                for gi in _scale_groups(block, linears, where):
+                    names = _GROUPS[gi][0]
+                    src = source[names[0]]
+                    best, s, losses = search_scale([_kn(block.get_submodule(n)) for n in names], gram[src], asum[src],
+                                                   group, bits, asym)
+                    logger.info("AWQ %s %s: scale exponent %.2f, loss %.6g (RTN %.6g)", where, "/".join(names),
+                                best / N_GRID, losses[best], losses[0])
+                    scales[gi] = s
+                    for n in names:
+                        in_scale[n] = s
+                apply_scales(block, scales)
+
+            for name, m in linears:
+                w_kn = _kn(m)
+                if config.auto_clip and name.rpartition(".")[2] not in _NO_CLIP:
+                    h = gram[source[name]]
+                    if name in in_scale:
+                        s = in_scale[name]
+                        h = h / torch.outer(s, s)
+                    best, losses, w_kn = qbits.awq_clip_search(w_kn, h, group, bits, asym, N_GRID, N_CLIP)
+                    picked = losses.gather(0, best.long()[None]).sum(dtype=torch.float64)
+                    logger.info("AWQ %s.%s: clip loss %.6g (RTN %.6g), %.0f%% of the cells clipped", where, name,
+                                float(picked), float(losses[0].sum(dtype=torch.float64)),
+                                100.0 * float((best > 0).float().mean()))
+                k, n = w_kn.shape
+                new = QuantizedLinearQBits(k, n, m.bias is not None, compute_dtype=config.compute_dtype,
+                                           compress_statistics=False, weight_dtype=config.weight_dtype,
+                                           bits=config.bits, scale_dtype=config.scale_dtype, blocksize=config.group_size,
+                                           scheme=config.scheme, device=device)
+                new.set_fp_weights_bias(w_kn.t(), m.bias.data if m.bias is not None else None)
+                new.source_cls = type(m)
+                new.requires_grad_(False)
+                parent_name, _, leaf = name.rpartition(".")
+                parent = block.get_submodule(parent_name) if parent_name else block
+                parent._modules[leaf] = new
+            del gram, asum
+            outs = _run_block(block, inputs)
+            inputs = [((y,) + tuple(args[1:]), kwargs) if args else ((), dict(kwargs, hidden_states=y))
+                      for (args, kwargs), y in zip(inputs, outs)]
+    finally:
+        torch.backends.cuda.matmul.allow_tf32 = tf32
+    return model

@@ -220,20 +220,25 @@ def convert_to_quantized_model(model, config, device="cuda"):
     """reference utils.py:531-702 for the weight-only configs. RTN: quantise every eligible linear on the device.
     GPTQ on an fp model: calibrate on the device (gptq.py gptq_quantize_model: Hessians from `config.calib_dataloader`
     or `config.dataset=[texts]` + tokenizer, the sweep in csrc/woq_gptq.hip); the decoder blocks' linears are
-    quantised, lm_head and anything outside the blocks stays as it is. AWQ / TEQ / AutoRound need calibration passes
-    that the reference runs inside neural_compressor (external); those configs (and GPTQ) are accepted for
-    PRE-QUANTISED checkpoints (optimum-format tensors already on the modules), and raise for an fp model instead of
+    quantised, lm_head and anything outside the blocks stays as it is. AWQ on an fp model: calibrate on the device the
+    same way (awq.py awq_quantize_model: the scale and clip searches of csrc/woq_awq.hip; scales are folded into the
+    norms / preceding projections of Llama-class blocks, the result is a plain RTN blob). TEQ / AutoRound are trained
+    searches that the reference runs inside neural_compressor (external); those configs (and GPTQ / AWQ) are accepted
+    for PRE-QUANTISED checkpoints (optimum-format tensors already on the modules), and raise for an fp model instead of
     silently falling back to RTN."""
     method = getattr(config.quant_method, "value", config.quant_method)
     has_packed = any(_packed_checkpoint_linear(m) for m in model.modules())
-    if method == "gptq" and not has_packed:
-        from .gptq import gptq_quantize_model, validate_gptq_request
+    if method in ("gptq", "awq") and not has_packed:
+        if method == "gptq":
+            from .gptq import gptq_quantize_model as calibrate, validate_gptq_request as validate
+        else:
+            from .awq import awq_quantize_model as calibrate, validate_awq_request as validate
 
-        validate_gptq_request(model, config)  # NotImplementedError for what is not built, before a device is needed
+        validate(model, config)  # NotImplementedError for what is not built, before a device is needed
         if str(device) == "cpu":
             raise RuntimeError("QBits: the MI355X backend has no CPU path (device must be 'cuda')")
         orig_dtype = next((p.dtype for p in model.parameters()), torch.float32)
-        model = gptq_quantize_model(model, config, device=device)
+        model = calibrate(model, config, device=device)
         model._woq_orig_dtype = orig_dtype
         return model
     if method != "rtn" and not has_packed:

@@ -335,7 +335,11 @@ class AwqConfig(ITREXQuantizationConfigMixin):
                ("use_double_quant", False), ("double_quant_scale_dtype", None), ("zero_point", True)) + _TAIL
 
     def __init__(self, *args, **kwargs):
+        # calibration data for an fp model (transformers/llm/quantization/awq.py), as GPTQConfig takes it: kept by
+        # reference, never copied or serialised
+        loader = kwargs.pop("calib_dataloader", None)
         super().__init__(*args, **kwargs)
+        self.calib_dataloader = loader
         self.sym = not self.zero_point
         self.scheme = "sym" if self.sym else "asym"
 
