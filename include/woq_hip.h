@@ -204,6 +204,9 @@ typedef struct woq_layer_weights {
 
 WOQ_API int woq_engine_create(const woq_engine_config* cfg, woq_engine** out);
 WOQ_API void woq_engine_destroy(woq_engine* e);
+/* Every check runs before the layer is stored: a refused call leaves the engine as it was. All layers of an engine are
+ * of one kind (integer / 4-bit table blobs, or fp8 blobs of one type), in whichever order they are set; a step, capture,
+ * phase or prompt pass is refused until every layer has been set. */
 WOQ_API int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w);
 /* embed: fp16/bf16 [vocab, hidden]; final norm fp32 [hidden]; lm_head fp16/bf16 [vocab_shard, hidden]
  * (NOT quantised, like the reference: utils/config.py:836-837 llm_int8_skip_modules). */

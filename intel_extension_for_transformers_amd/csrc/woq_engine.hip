@@ -28,11 +28,15 @@ constexpr int kProjEpi[P_COUNT] = {0, 0, 1, 0};
 // the engine's own form of woq_layer_weights (woq_engine_set_layer converts). fp8-weight layers: blob / hdr are the HI
 // nibble plane's (include/woq_blob.h woq_fp8_headers) and fp8_lo the LO plane's tile data; null for integer / table layers
 struct EngineProj { const void* blob; woq_blob_header hdr; const void* fp8_lo; };
+// what woq_engine_set_layer last committed for a layer: nothing yet, integer / 4-bit table blobs, fp8-weight blobs. A step
+// needs every layer set and all of one kind (engine_layers_problem)
+enum LayerKind { LAYER_UNSET, LAYER_INT, LAYER_FP8 };
 // qkv_bias / q_norm / k_norm: the optional extras of woq_engine_set_layer_extras (null = absent)
 struct EngineLayer {
   EngineProj p[P_COUNT];
   const float* ln1;
   const float* ln2;
+  LayerKind kind = LAYER_UNSET;
   const float* qkv_bias = nullptr;
   const float* q_norm = nullptr;
   const float* k_norm = nullptr;
@@ -199,6 +203,22 @@ const woq::CommDev* woq_engine::tp_push() const {
 }
 
 static const XqPtrs kNoXq = {nullptr, nullptr, nullptr};
+
+// Why the engine's layers cannot be launched over (null = they can): every entry point that launches a layer's kernels
+// asks before its first launch. An unset layer holds null blobs; fp8 and integer layers take different kernels off one
+// engine-wide switch (fp8_type), so a mix would hand one kind's blob to the other's kernel.
+static const char* engine_layers_problem(const woq_engine* e) {
+  for (const EngineLayer& w : e->layers) {
+    if (w.kind == LAYER_UNSET) return "QBits: engine layer not set (woq_engine_set_layer comes first, for every layer)";
+    // (woq_engine_set_layer never commits a mix: this line guards the kernels' precondition where they are launched)
+    if (w.kind != e->layers[0].kind) return "QBits: fp8 and integer layers cannot be mixed in one engine";
+  }
+  return nullptr;
+}
+#define WOQ_CHECK_LAYERS(e)                                                \
+  do {                                                                     \
+    if (const char* why = engine_layers_problem(e)) return woq::fail(why); \
+  } while (0)
 
 // projection k of layer l as one batch-1 GEMV over an XQ vector
 static int engine_gemv_xq(woq_engine* e, int l, Proj k, const XqPtrs& xin, float* out, const float* ssq_in,
@@ -568,6 +588,7 @@ int woq_engine_prefill(woq_engine* e, const int32_t* tokens_dev, int n_seq, int 
   WOQ_CHECK(tokens_dev && n_seq >= 1 && T >= 1 && start_pos >= 0, "QBits: bad prefill arguments");
   WOQ_CHECK(n_seq <= e->max_batch, "QBits: prefill batch exceeds the engine's max_batch");
   WOQ_CHECK(start_pos + T <= e->cfg.max_ctx, "QBits: prefill runs past max_ctx");
+  WOQ_CHECK_LAYERS(e);
   WOQ_CHECK((long long)n_seq * T < (1ll << 31), "QBits: prefill row count overflows");
   int rc = engine_prefill_impl(e, tokens_dev, n_seq, T, start_pos, greedy, (hipStream_t)stream);
   if (rc) return rc;
@@ -585,6 +606,7 @@ int woq_engine_prefill_scored(woq_engine* e, const int32_t* tokens_dev, int T, i
   WOQ_CHECK(e->lp_chosen != nullptr, "QBits: no log-probability log before the first woq_engine_set_logprobs(e, 1)");
   const woq_engine_config& c = e->cfg;
   if (const char* why = score_shape_problem(e->lm_head, e->lm_dtype, c.hidden, c.vocab)) return woq::fail(why);
+  WOQ_CHECK_LAYERS(e);  // (after the argument checks, before the first allocation and launch)
   const hipStream_t st = (hipStream_t)stream;
   if (e->score_ws == nullptr) WOQ_HIP(hipMalloc(&e->score_ws, score_workspace_bytes(c.hidden, c.vocab)));
   int rc = engine_prefill_impl(e, tokens_dev, 1, T, start_pos, greedy, st);
@@ -831,14 +853,16 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
   WOQ_TRY
   WOQ_CHECK(e && w && layer >= 0 && layer < e->cfg.layers, "QBits: bad layer index");
   const woq_engine_config& c = e->cfg;
-  const EngineLayer in = {{{w->qkv_blob, w->qkv_hdr, nullptr},
-                           {w->o_blob, w->o_hdr, nullptr},
-                           {w->gate_up_blob, w->gate_up_hdr, nullptr},
-                           {w->down_blob, w->down_hdr, nullptr}},
-                          w->ln1,
-                          w->ln2};
+  // built and checked as a local: a refused call leaves the engine as it was (a layer set again starts without extras:
+  // woq_engine_set_layer_extras comes after)
+  EngineLayer in = {{{w->qkv_blob, w->qkv_hdr, nullptr},
+                     {w->o_blob, w->o_hdr, nullptr},
+                     {w->gate_up_blob, w->gate_up_hdr, nullptr},
+                     {w->down_blob, w->down_hdr, nullptr}},
+                    w->ln1,
+                    w->ln2};
   auto all = [&](auto pred) { return std::all_of(std::begin(in.p), std::end(in.p), pred); };
-  const woq_blob_header &qkv = in.p[P_QKV].hdr, &o = in.p[P_O].hdr, &gu = in.p[P_GATE_UP].hdr, &down = in.p[P_DOWN].hdr;
+  const woq_blob_header qkv = in.p[P_QKV].hdr, o = in.p[P_O].hdr, gu = in.p[P_GATE_UP].hdr, down = in.p[P_DOWN].hdr;
   // round 6: fp8_e4m3 / fp8_e5m2 layers (all four projections of every layer the same type; one GPU)
   const bool fp8 = woq_weight_is_fp8(qkv.weight_type);
   if (fp8) {
@@ -861,13 +885,18 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
   WOQ_CHECK(gu.K == c.hidden && gu.N == 2 * c.inter && (c.inter % 16) == 0,
             "QBits: gate_up blob shape mismatch (inter must be a multiple of 16)");
   WOQ_CHECK(down.K == c.inter && down.N == c.hidden, "QBits: down_proj blob shape mismatch");
-  e->layers[layer] = in;  // (a layer set again starts without extras: woq_engine_set_layer_extras comes after)
+  // one kind per engine, whichever order the layers arrive in (the layer being replaced does not count)
+  in.kind = fp8 ? LAYER_FP8 : LAYER_INT;
+  for (int l = 0; l < c.layers; ++l) {
+    const EngineLayer& other = e->layers[l];
+    if (l == layer || other.kind == LAYER_UNSET) continue;
+    WOQ_CHECK(other.kind == in.kind, "QBits: fp8 and integer layers cannot be mixed in one engine");
+    WOQ_CHECK(!fp8 || e->fp8_type == qkv.weight_type, "QBits: one fp8 type per engine");
+  }
   if (fp8) {
     // the composite container [outer header][HI blob][LO blob] (include/woq_blob.h): the engine keeps the HI plane as the
     // projection's blob / header and the LO plane's tile data beside it; its headers follow from the outer one's parameters
-    WOQ_CHECK(e->fp8_type == 0 || e->fp8_type == qkv.weight_type, "QBits: one fp8 type per engine");
-    e->fp8_type = qkv.weight_type;
-    for (EngineProj& p : e->layers[layer].p) {
+    for (EngineProj& p : in.p) {
       const woq_blob_header outer = p.hdr;
       woq_blob_header o2, hi, lo;
       WOQ_CHECK(outer.off_shuffle == 0, "QBits: fp8 layers with g_idx stay on the module path");
@@ -876,15 +905,21 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
       const uint8_t* base = (const uint8_t*)p.blob;
       p = {base + outer.off_q, hi, base + outer.off_scale + lo.off_q};  // the HI plane's blob, the LO plane's tile data
     }
+    // (the one effect ahead of the commit: engine-owned scratch that nothing reads unless an fp8 layer is committed)
     if (e->gu_tmp == nullptr) {
       WOQ_HIP(hipMalloc((void**)&e->gu_tmp, (size_t)2 * c.inter * 4));
       e->owned.push_back(e->gu_tmp);
     }
-    e->xq_shapes_ok = false;  // fp8 layers run the fp32-activation step
-    return 0;
   }
-  WOQ_CHECK(e->fp8_type == 0, "QBits: fp8 and integer layers cannot be mixed in one engine");
-  for (int k = 0; k < P_COUNT; ++k) e->xq_shapes_ok = e->xq_shapes_ok && gemv_xq_supported(in.p[k].hdr, kProjEpi[k]);
+  // every check has passed: commit
+  e->layers[layer] = in;
+  e->fp8_type = fp8 ? qkv.weight_type : 0;  // (all set layers are of this kind)
+  // xq_shapes_ok only ever goes from true to false: an engine whose fp8 (or XQ-refused) layer is later replaced by one
+  // the XQ GEMV covers stays on the fp32-activation step — correct, only slower
+  if (fp8)
+    e->xq_shapes_ok = false;  // fp8 layers run the fp32-activation step
+  else
+    for (int k = 0; k < P_COUNT; ++k) e->xq_shapes_ok = e->xq_shapes_ok && gemv_xq_supported(in.p[k].hdr, kProjEpi[k]);
   WOQ_END
 }
 
@@ -1157,6 +1192,7 @@ void* woq_engine_logprob_ptr(woq_engine* e, int which) {
 int woq_engine_step(woq_engine* e, int greedy, void* stream) {
   WOQ_TRY
   WOQ_CHECK(e && e->embed && e->lm_head, "QBits: engine head not set");
+  WOQ_CHECK_LAYERS(e);
   int rc = engine_step_impl(e, greedy, (hipStream_t)stream);
   if (rc) return rc;
   WOQ_HIP(hipGetLastError());
@@ -1166,6 +1202,7 @@ int woq_engine_step(woq_engine* e, int greedy, void* stream) {
 int woq_engine_phase(woq_engine* e, int layer, int phase, int greedy, void* stream) {
   WOQ_TRY
   WOQ_CHECK(e && e->embed && e->lm_head, "QBits: engine head not set");
+  WOQ_CHECK_LAYERS(e);
   hipStream_t st = (hipStream_t)stream;
   int rc = 0;
   if (phase == 0) {
@@ -1186,6 +1223,7 @@ int woq_engine_phase(woq_engine* e, int layer, int phase, int greedy, void* stre
 int woq_engine_capture(woq_engine* e, int greedy, void* stream) {
   WOQ_TRY
   WOQ_CHECK(e && e->embed && e->lm_head, "QBits: engine head not set");
+  WOQ_CHECK_LAYERS(e);
   WOQ_CHECK(!e->allreduce || (e->comm && e->cfg.tp_size > 1),
             "QBits: graph capture with a host all-reduce callback is not supported (bind a device communicator)");
   hipStream_t st = (hipStream_t)stream;
@@ -1226,6 +1264,7 @@ int woq_engine_capture(woq_engine* e, int greedy, void* stream) {
 int woq_engine_steps(woq_engine* e, int n, int greedy, void* stream) {
   WOQ_TRY
   WOQ_CHECK(e && e->embed && e->lm_head, "QBits: engine head not set");
+  WOQ_CHECK_LAYERS(e);
   for (int i = 0; i < n; ++i) {
     const int rc = engine_step_impl(e, greedy, (hipStream_t)stream);
     if (rc) return rc;
@@ -1249,6 +1288,7 @@ int woq_engine_time_gemv_mask(woq_engine* e, int mask, int reps, void* stream, f
                               int* launches_per_pass) {
   WOQ_TRY
   WOQ_CHECK(e && total_ms && bytes_per_pass && launches_per_pass && (mask & 15) != 0, "QBits: bad argument");
+  WOQ_CHECK_LAYERS(e);
   hipStream_t st = (hipStream_t)stream;
   const woq_engine_config& c = e->cfg;
   double bytes = 0;
@@ -1319,6 +1359,7 @@ int woq_engine_time_gemv(woq_engine* e, int reps, void* stream, float* total_ms,
 int woq_engine_time_twin(woq_engine* e, int mode, int reps, void* stream, float* total_ms) {
   WOQ_TRY
   WOQ_CHECK(e && total_ms && (mode == 0 || mode == 1), "QBits: bad argument");
+  WOQ_CHECK_LAYERS(e);
   hipStream_t st = (hipStream_t)stream;
   unsigned int* sink = (unsigned int*)e->am_idx;  // any device word; never written (the twins' store is unreachable)
   auto pass = [&](hipStream_t st) -> int {
@@ -1345,6 +1386,7 @@ int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, int reps,
   WOQ_TRY
   WOQ_CHECK(e && gemm_ms && call_ms && layer >= 0 && layer < e->cfg.layers && reps >= 1, "QBits: bad argument");
   WOQ_CHECK((size_t)n_rows <= e->pf_rows && n_rows > 8, "QBits: run a prompt pass of at least n_rows rows first");
+  WOQ_CHECK_LAYERS(e);
   hipStream_t st = (hipStream_t)stream;
   const woq_engine_config& c = e->cfg;
   hipEvent_t k0, k1, c0, c1;

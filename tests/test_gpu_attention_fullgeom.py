@@ -30,8 +30,9 @@ KV_TOL = 1e-2
 
 
 def build_attention_geometry(kv_heads=32, window=0, kv_dtype=torch.float16, max_ctx=2304, max_batch=1, layers=2, seed=21,
-                             group=128, asym=False, inter=512, vocab=512):
-    """hidden 4096 = 32 heads x 128 with a narrow MLP / vocabulary; engine + oracle over the same host-made tensors."""
+                             group=128, asym=False, inter=512, vocab=512, parts_out=None):
+    """hidden 4096 = 32 heads x 128 with a narrow MLP / vocabulary; engine + oracle over the same host-made tensors.
+    parts_out: a list that receives, per layer, the (q, scale, zp) behind each device blob (see below)."""
     from intel_extension_for_transformers_amd import qbits
     from intel_extension_for_transformers_amd.runtime import WoqDecoderEngine, fuse_gate_up
     from tests.test_gpu_fullsize_oracle import _gpu_pack, _host_qsz
@@ -59,6 +60,16 @@ def build_attention_geometry(kv_heads=32, window=0, kv_dtype=torch.float16, max_
         ly["ln1"] = (1 + 0.05 * rng.standard_normal(H)).astype(np.float32)
         ly["ln2"] = (1 + 0.05 * rng.standard_normal(H)).astype(np.float32)
         eng.set_layer(l, qkv, o, gu, down, tt(ly["ln1"]), tt(ly["ln2"]))
+        if parts_out is not None:
+            # the (q, scale, zp) behind each device blob in the blob's own column order, as tests/test_gpu_engine.py
+            # `_tiny` records them (tests/test_gpu_engine_stages.py); the device blobs and norm weights are
+            # eng.layer_tensors[l]
+            fuse = lambda i: fuse_gate_up(tt(parts["gate"][i]), tt(parts["up"][i])).numpy()  # noqa: E731
+            raw = dict(qkv=(cat(0), cat(1), cat(2) if asym else None, None), o=parts["o"] + (None,),
+                       gate_up=(fuse(0), fuse(1), fuse(2) if asym else None, None), down=parts["down"] + (None,))
+            parts_out.append(dict(raw=raw, group=group, asym=asym, scale_dtype="fp16", weight_dtype="int4_clip",
+                                  compute_dtype="fp32",
+                                  cpu_pack=lambda q, s, z, gi: orc.repack(q, s, z, None, group, scale_type=orc.F16)))
         lys.append(ly)
     embed = tt((rng.standard_normal((vocab, H)) * 0.5).astype(np.float32)).half()
     lm = tt((rng.standard_normal((vocab, H)) * 0.02).astype(np.float32)).half()

@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 def _tiny(group, asym, scale_dtype, seed=0, max_ctx=64, max_batch=1, head_dim=64, kv_dtype=torch.float16,
           attn_splits=0, window=0, hidden=256, attn_grouped=False, weight_dtype="int4_clip", compute_dtype="fp32",
-          act_order=False):
+          act_order=False, parts_out=None):
+    """parts_out: a list that receives, per layer, the (q, scale, zp) behind each device blob (see below)"""
     from intel_extension_for_transformers_amd import qbits
     from intel_extension_for_transformers_amd.runtime import WoqDecoderEngine, fuse_gate_up
 
@@ -87,6 +88,15 @@ def _tiny(group, asym, scale_dtype, seed=0, max_ctx=64, max_batch=1, head_dim=64
         ly["ln1"] = (1 + 0.1 * rng.standard_normal(H)).astype(np.float32)
         ly["ln2"] = (1 + 0.1 * rng.standard_normal(H)).astype(np.float32)
         eng.set_layer(l, qkv, o, gu, down, torch.from_numpy(ly["ln1"]), torch.from_numpy(ly["ln2"]))
+        if parts_out is not None:
+            # the (q, scale, zp) behind each device blob, in the blob's own column order, and the oracle's byte-identical
+            # repack of them where it has one (tests/test_gpu_engine_stages.py restates the kernels from these); the
+            # device blobs and norm weights themselves are eng.layer_tensors[l]
+            fz = lambda i: fuse_gate_up(tt(parts["gate"][i]), tt(parts["up"][i])).numpy()  # noqa: E731
+            raw = dict(qkv=(cat(0), cat(1), cat(2) if asym else None, gi["q"]), o=parts["o"] + (gi["o"],),
+                       gate_up=(fz(0), fz(1), fz(2) if asym else None, gi["gate"]), down=parts["down"] + (gi["down"],))
+            parts_out.append(dict(raw=raw, cpu_pack=cpu_pack, group=group, asym=asym, scale_dtype=scale_dtype,
+                                  weight_dtype=weight_dtype, compute_dtype=compute_dtype))
         layers.append(ly)
     embed = torch.from_numpy(rng.standard_normal((cfg["vocab"], H)).astype(np.float32)).half()
     lm = torch.from_numpy((rng.standard_normal((cfg["vocab"], H)) * 0.1).astype(np.float32)).half()
