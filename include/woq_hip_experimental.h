@@ -183,6 +183,29 @@ WOQ_API int woq_probe_xq_from_f32(const float* x, const float* norm_w, int K, vo
 WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
                               const float* bias, const float* residual, const float* next_norm_w, float* out,
                               void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream);
+/* The tensor-parallel exchange alone (tests/test_gpu_tp_kernels.py), each forwarding to the engine's own launcher
+ * unchanged. Every rank of a connected communicator issues the same chain of collectives.
+ * gemv_xq_tp: woq_probe_gemv_xq whose last chained launch also pushes its live output columns, this rank's partial sums,
+ * into the peers' inboxes under the sequence number of the all-reduce that must follow with pushed != 0. */
+WOQ_API int woq_probe_gemv_xq_tp(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
+                                 const float* bias, const float* residual, const float* next_norm_w, float* out,
+                                 void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream,
+                                 woq_comm* comm);
+/* in-place sum over ranks of buf[0..n) in rank order from 0.f (woq_comm_launch_allreduce_ex): pushed != 0 = the
+ * contribution is already in the peers' inboxes (woq_probe_gemv_xq_tp); xo_* (nullable together; n % 16 == 0) = the sum
+ * times norm_w (nullable) as an XQ vector, ssq_out (nullable) fp32 [n / 16] = the blocks' sums of squares of the sum. */
+WOQ_API int woq_probe_comm_allreduce(woq_comm* comm, float* buf, size_t n, int pushed, const float* norm_w,
+                                     void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream);
+/* the greedy pick over a vocab-sharded lm_head's (max, local index) pairs (woq_comm_launch_greedy): token[0] = the
+ * global index of the highest value over all ranks, lowest index on ties, log[pos[0]] = token (log nullable), pos[0] += 1;
+ * no pair won on any rank: token 0 and status (nullable, device int) |= 4. */
+WOQ_API int woq_probe_comm_greedy(woq_comm* comm, const float* pmax, const int32_t* pidx, int n_pairs, int vocab_offset,
+                                  int32_t* token, int32_t* pos, int32_t* log, int* status, void* stream);
+/* sets the sequence number of the next collective (never 0), stream-ordered. Test only: every rank calls it with the
+ * same value while no collective of any rank is in flight (synchronise and meet first — a peer still pulling from the
+ * buffer the new parity selects would lose its data), and on an inbox that holds none of the tags the sequence will
+ * reach (the same tag on a stale granule reads as arrived). */
+WOQ_API int woq_probe_comm_set_seq(woq_comm* comm, unsigned int seq, void* stream);
 /* lm_head_kernel: hidden_in / norm_w fp32 [hidden] (hidden % 8 == 0), W dense [vocab][hidden] in w_dtype (WOQ_F16 |
  * WOQ_BF16), logits fp32 [vocab]; pmax / pidx (nullable together) fp32 / int32 [(vocab + 15) / 16]: each 16-row
  * workgroup's (max logit, lowest index of it). */

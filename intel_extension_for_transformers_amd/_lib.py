@@ -110,6 +110,7 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_gemv_f32", "woq_probe_gemm_plan", "woq_probe_gemm_f16", "woq_probe_sample_controls",
     "woq_probe_attn_decode_plan", "woq_engine_attn_plan", "woq_probe_guide", "woq_probe_sample_stream",
     "woq_probe_rope_append_qknorm", "woq_probe_attn_decode_qknorm",
+    "woq_probe_gemv_xq_tp", "woq_probe_comm_allreduce", "woq_probe_comm_greedy", "woq_probe_comm_set_seq",
 ]
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
@@ -246,6 +247,10 @@ def lib():
     L.woq_engine_prefill_rows_ptr.argtypes = [vp]
     L.woq_probe_xq_from_f32.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
     L.woq_probe_gemv_xq.argtypes = [vp, vp, cf, vp, ci] + [vp] * 9
+    L.woq_probe_gemv_xq_tp.argtypes = [vp, vp, cf, vp, ci] + [vp] * 10
+    L.woq_probe_comm_allreduce.argtypes = [vp, vp, cs, ci] + [vp] * 6
+    L.woq_probe_comm_greedy.argtypes = [vp, vp, vp, ci, ci] + [vp] * 5
+    L.woq_probe_comm_set_seq.argtypes = [vp, ctypes.c_uint, vp]
     L.woq_probe_lm_head.argtypes = [vp, vp, cf, vp, ci, ci, ci, vp, vp, vp, vp]
     L.woq_probe_greedy_tail.argtypes = [ci, vp, ci] + [vp] * 6 + [ci, ci] + [vp] * 7 + [ci, vp, vp]
     L.woq_probe_embed.argtypes = [vp, ci, vp, ci] + [vp] * 8 + [ci, vp, vp]
@@ -471,6 +476,36 @@ def probe_gemv_xq(x, blob, epi=0, in_norm_w=None, eps=0.0, bias=None, residual=N
     xo = (limbs, u, sx) or None."""
     check(lib().woq_probe_gemv_xq(_ptr(x), _opt(in_norm_w), float(eps), _ptr(blob), int(epi), _opt(bias), _opt(residual),
                                   _opt(next_norm_w), _opt(out), *_xq_ptrs(xo), _opt(ssq_out), stream_ptr()))
+
+
+def probe_gemv_xq_tp(comm, x, blob, epi=0, in_norm_w=None, eps=0.0, bias=None, residual=None, next_norm_w=None, out=None,
+                     xo=None, ssq_out=None):
+    """`probe_gemv_xq` whose epilogue also pushes the outputs into the peers' inboxes (woq_probe_gemv_xq_tp): `comm` a
+    connected runtime.comm.DeviceComm; the all-reduce that follows runs with pushed=True."""
+    check(lib().woq_probe_gemv_xq_tp(_ptr(x), _opt(in_norm_w), float(eps), _ptr(blob), int(epi), _opt(bias),
+                                     _opt(residual), _opt(next_norm_w), _opt(out), *_xq_ptrs(xo), _opt(ssq_out),
+                                     stream_ptr(), comm.handle))
+
+
+def probe_comm_allreduce(comm, buf, n=None, pushed=False, norm_w=None, xo=None, ssq_out=None):
+    """the engine's all-reduce launch alone (woq_probe_comm_allreduce): in-place sum over ranks of buf[:n] (fp32 device
+    tensor; n defaults to its size), xo = (limbs, u, sx) or None, the current stream."""
+    check(lib().woq_probe_comm_allreduce(comm.handle, _ptr(buf), int(buf.numel() if n is None else n), int(bool(pushed)),
+                                         _opt(norm_w), *_xq_ptrs(xo), _opt(ssq_out), stream_ptr()))
+
+
+def probe_comm_greedy(comm, pmax, pidx, vocab_offset, token, pos, log=None, status=None, n_pairs=None):
+    """the tensor-parallel greedy pick alone (woq_probe_comm_greedy): pmax fp32 / pidx int32 device tensors of this rank's
+    pairs, token / pos / status device int32 [1], log device int32."""
+    n = int(pmax.numel() if n_pairs is None else n_pairs)
+    check(lib().woq_probe_comm_greedy(comm.handle, _ptr(pmax), _ptr(pidx), n, int(vocab_offset), _ptr(token), _ptr(pos),
+                                      _opt(log), _opt(status), stream_ptr()))
+
+
+def probe_comm_set_seq(comm, seq):
+    """test only (woq_probe_comm_set_seq): the sequence number of the communicator's next collective; every rank, the
+    same value, with no collective in flight."""
+    check(lib().woq_probe_comm_set_seq(comm.handle, int(seq), stream_ptr()))
 
 
 def probe_lm_head(hidden_in, norm_w, eps, W, logits, pmax=None, pidx=None):

@@ -31,6 +31,7 @@
 
 #include "woq_comm_dev.h"
 #include "woq_xq.h"
+#include "../../include/woq_hip_experimental.h"
 
 namespace woq {
 
@@ -113,10 +114,13 @@ __global__ __launch_bounds__(256) void allreduce_ll_kernel(CommDev c, float* __r
 // greedy token of a vocab-sharded lm_head: local argmax over the lm_head launch's per-workgroup (max, index) pairs,
 // one (max, global index) pair per rank exchanged through the inboxes, winner = highest value, lowest global index
 // on ties (a single-device argmax over the gathered row). Writes token and advances pos. One workgroup.
+// No candidate won on any rank (every pair NaN, or -inf under the sentinel index): argmax_kernel's rule — token 0 and
+// status bit 2 of the engine's status word — so that the sentinel never reaches the next step's embedding lookup. The
+// rule reads the merged pair, which is the same on every rank, so the ranks still agree.
 __global__ __launch_bounds__(1024) void tp_greedy_kernel(CommDev c, const float* __restrict__ pmax,
                                                          const int32_t* __restrict__ pidx, int n, int vocab_offset,
                                                          int32_t* __restrict__ token, int32_t* __restrict__ pos,
-                                                         int32_t* __restrict__ log) {
+                                                         int32_t* __restrict__ log, int* __restrict__ status) {
   __shared__ float bv[16];
   __shared__ int bi[16];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -172,6 +176,10 @@ __global__ __launch_bounds__(1024) void tp_greedy_kernel(CommDev c, const float*
       top = v;
       top_i = (int)ib;
     }
+  }
+  if (top_i < 0 || top_i == 0x7fffffff) {
+    top_i = 0;
+    if (status != nullptr) atomicOr(status, 4);
   }
   token[0] = top_i;
   if (log != nullptr) log[pos[0]] = top_i;
@@ -229,12 +237,17 @@ int woq_comm_launch_allreduce_ex(woq_comm* c, float* buf, size_t n, int pushed, 
 const woq::CommDev* woq_comm_dev_ptr(woq_comm* c) { return c && c->connected ? c->dev_copy : nullptr; }
 
 int woq_comm_launch_greedy(woq_comm* c, const float* pmax, const int32_t* pidx, int n, int vocab_offset,
-                           int32_t* token, int32_t* pos, int32_t* log, hipStream_t st) {
+                           int32_t* token, int32_t* pos, int32_t* log, int* status, hipStream_t st) {
   if (!c || !c->connected) return woq::fail("QBits: tensor-parallel communicator is not connected");
   hipLaunchKernelGGL(woq::tp_greedy_kernel, dim3(1), dim3(1024), 0, st, c->dev, pmax, pidx, n, vocab_offset, token,
-                     pos, log);
+                     pos, log, status);
   return 0;
 }
+
+namespace woq {
+// test only (woq_probe_comm_set_seq): the sequence number of the next collective
+__global__ void comm_set_seq_kernel(uint32_t* ctl, uint32_t seq) { atomicExch(&ctl[0], seq); }
+}  // namespace woq
 
 extern "C" {
 
@@ -337,6 +350,41 @@ int woq_comm_set_timeout_ms(woq_comm* c, int ms) {
   c->dev.timeout_ticks = (uint32_t)ms * 100000u;
   if (c->dev_copy != nullptr)
     WOQ_HIP(hipMemcpy(c->dev_copy, &c->dev, sizeof(woq::CommDev), hipMemcpyHostToDevice));
+  WOQ_END
+}
+
+// test entry points (include/woq_hip_experimental.h): the collective launches on caller-owned buffers
+WOQ_API int woq_probe_comm_allreduce(woq_comm* c, float* buf, size_t n, int pushed, const float* norm_w, void* xo_limbs,
+                                     float* xo_u, float* xo_sx, float* ssq_out, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(c && buf, "QBits: bad all-reduce probe arguments");
+  WOQ_CHECK(xo_limbs == nullptr || (xo_u && xo_sx), "QBits: an XQ output needs all of its parts");
+  WOQ_CHECK(xo_limbs != nullptr || (norm_w == nullptr && ssq_out == nullptr),
+            "QBits: norm_w and ssq_out belong to the XQ output");
+  const int rc = woq_comm_launch_allreduce_ex(c, buf, n, pushed, norm_w, woq::XqPtrs{(uint8_t*)xo_limbs, xo_u, xo_sx},
+                                              ssq_out, (hipStream_t)stream);
+  if (rc) return rc;
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_comm_greedy(woq_comm* c, const float* pmax, const int32_t* pidx, int n_pairs, int vocab_offset,
+                                  int32_t* token, int32_t* pos, int32_t* log, int* status, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(c && pmax && pidx && n_pairs >= 1 && token && pos, "QBits: bad greedy exchange probe arguments");
+  const int rc = woq_comm_launch_greedy(c, pmax, pidx, n_pairs, vocab_offset, token, pos, log, status,
+                                        (hipStream_t)stream);
+  if (rc) return rc;
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+WOQ_API int woq_probe_comm_set_seq(woq_comm* c, unsigned int seq, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(c && c->connected, "QBits: tensor-parallel communicator is not connected");
+  WOQ_CHECK(seq != 0, "QBits: 0 is never a live sequence number");
+  hipLaunchKernelGGL(woq::comm_set_seq_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, c->dev.ctl, (uint32_t)seq);
+  WOQ_HIP(hipGetLastError());
   WOQ_END
 }
 

@@ -339,7 +339,8 @@ static int engine_tail(woq_engine* e, TailPick pick, hipStream_t st) {
   switch (pick) {
     case PICK_NONE: return 0;
     case PICK_TP_GREEDY:
-      return woq_comm_launch_greedy(e->comm, e->am_val, e->am_idx, n_pairs, e->vocab_offset, e->token, e->pos, e->tok_log, st);
+      return woq_comm_launch_greedy(e->comm, e->am_val, e->am_idx, n_pairs, e->vocab_offset, e->token, e->pos, e->tok_log,
+                                    e->fuse_status, st);
     case PICK_SAMPLED: {  // token <- sample(logits), tok_log[pos] = token, pos += 1; a guide's state follows the pick
       const SampleTail t = e->sample_tail();
       if (const int rc = launch_sample_tail(t, st)) return rc;

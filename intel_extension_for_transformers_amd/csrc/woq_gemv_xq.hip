@@ -217,10 +217,14 @@ WOQ_API int woq_probe_xq_from_f32(const float* x, const float* norm_w, int K, vo
   WOQ_END
 }
 
-WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
-                              const float* bias, const float* residual, const float* next_norm_w, float* out,
-                              void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream) {
+// `comm` (woq_probe_gemv_xq_tp; null = none): the last chained launch pushes its outputs, this rank's partial sums, into
+// the peers' inboxes
+static int probe_gemv_xq(const float* x, const float* in_norm_w, float eps, const void* blob, int epi, const float* bias,
+                         const float* residual, const float* next_norm_w, float* out, void* xo_limbs, float* xo_u,
+                         float* xo_sx, float* ssq_out, void* stream, woq_comm* comm) {
   WOQ_TRY
+  const woq::CommDev* tp = comm != nullptr ? woq_comm_dev_ptr(comm) : nullptr;
+  WOQ_CHECK(comm == nullptr || tp != nullptr, "QBits: tensor-parallel communicator is not connected");
   WOQ_CHECK(x && blob && (epi == 0 || epi == 1), "QBits: bad XQ GEMV probe arguments");
   WOQ_CHECK(out != nullptr || xo_limbs != nullptr, "QBits: the XQ GEMV probe needs an output");
   WOQ_CHECK(xo_limbs == nullptr || (xo_u && xo_sx), "QBits: an XQ output needs all of its parts");
@@ -232,6 +236,8 @@ WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps,
   WOQ_HIP(hipStreamSynchronize(st));
   WOQ_CHECK(h.magic == WOQ_BLOB_MAGIC, "QBits: not a WQH1 packed weight");
   if (!woq::gemv_xq_supported(h, epi)) return woq::fail("QBits: shape not covered by the XQ GEMV");
+  WOQ_CHECK(tp == nullptr || (size_t)(epi == 1 ? h.N / 2 : h.N) <= woq_comm_max_elems(comm),
+            "QBits: more output columns than the communicator's inbox holds");
   // scratch: the input as an XQ vector, then its K / 16 RMSNorm partials
   const size_t xq_sz = woq::xq_bytes(h.K), nblk = (size_t)h.K / 16;
   uint8_t* ws = nullptr;
@@ -240,12 +246,28 @@ WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps,
   float* ssq_in = in_norm_w != nullptr ? (float*)(ws + xq_sz) : nullptr;
   woq::launch_xq_from_f32(x, in_norm_w, h.K, xin, ssq_in, st);
   const int rc = woq::launch_gemv_xq(xin, blob, h, bias, out, ssq_in, eps, residual, epi,
-                                     woq::XqPtrs{(uint8_t*)xo_limbs, xo_u, xo_sx}, next_norm_w, ssq_out, st, nullptr);
+                                     woq::XqPtrs{(uint8_t*)xo_limbs, xo_u, xo_sx}, next_norm_w, ssq_out, st, tp);
   const hipError_t le = hipGetLastError();
   hipFreeAsync(ws, st);
   if (rc) return rc;
   WOQ_HIP(le);
   WOQ_END
+}
+
+WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
+                              const float* bias, const float* residual, const float* next_norm_w, float* out,
+                              void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream) {
+  return probe_gemv_xq(x, in_norm_w, eps, blob, epi, bias, residual, next_norm_w, out, xo_limbs, xo_u, xo_sx, ssq_out,
+                       stream, nullptr);
+}
+
+WOQ_API int woq_probe_gemv_xq_tp(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
+                                 const float* bias, const float* residual, const float* next_norm_w, float* out,
+                                 void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream,
+                                 woq_comm* comm) {
+  if (comm == nullptr) return woq::fail("QBits: the tensor-parallel XQ GEMV probe needs a communicator");
+  return probe_gemv_xq(x, in_norm_w, eps, blob, epi, bias, residual, next_norm_w, out, xo_limbs, xo_u, xo_sx, ssq_out,
+                       stream, comm);
 }
 
 }  // extern "C"

@@ -311,5 +311,6 @@ int woq_comm_launch_allreduce_ex(woq_comm* c, float* buf, size_t n, int pushed, 
                                  const woq::XqPtrs& xo, float* ssq_out, hipStream_t st);
 // device-resident copy of the communicator record (peer inboxes, sequence word, rank / world), valid once connected
 const woq::CommDev* woq_comm_dev_ptr(woq_comm* c);
+// `status` (nullable) = the engine's status word: |= 4 when no pair won on any rank (token 0), like launch_argmax_pairs
 int woq_comm_launch_greedy(woq_comm* c, const float* pmax, const int32_t* pidx, int n, int vocab_offset,
-                           int32_t* token, int32_t* pos, int32_t* log, hipStream_t st);
+                           int32_t* token, int32_t* pos, int32_t* log, int* status, hipStream_t st);
