@@ -122,6 +122,32 @@ WOQ_API int woq_awq_clip_search(const float* w_dev, const float* h_dev, int ldh,
                                 int asym, int n_grid, int n_cand, int32_t* best_dev, float* losses_dev,
                                 float* w_out_dev, void* stream);
 
+/* the quantiser of AutoRound calibration (no reference counterpart: the reference hands AutoRound to neural_compressor /
+ * auto-round; rule, gradients and layout: csrc/woq_autoround.hip, DESIGN.md "AutoRound"). w fp32 [K,N] in working order
+ * (Linear.weight.T); v fp32 [K,N] the rounding offset in [-0.5, 0.5]; alpha, beta fp32 [G,N] the range factors in
+ * [0, 1]; groups of `group` rows (the last may be short; group <= 0 or > K = one group per column); bits 2 | 3 | 4 | 8,
+ * sym or asym. v = 0, alpha = beta = 1 is woq_quantize_to_packed_weight's RTN rule, bit for bit. Dtypes are
+ * woq_dtype codes (fp32, bf16, fp16). All three are asynchronous on `stream` and allocate nothing.
+ *
+ * woq_autoround_forward: out [K,N] of out_dtype = the fake-quantised weight W~, the fp32 value rounded once. */
+WOQ_API int woq_autoround_forward(const float* w_dev, const float* v_dev, const float* alpha_dev,
+                                  const float* beta_dev, int K, int N, int group, int bits, int asym, void* out_dev,
+                                  int out_dtype, void* stream);
+
+/* woq_autoround_step: recomputes the forward, forms dL/dv, dL/dalpha, dL/dbeta from g = dL/dW~ [K,N] of g_dtype
+ * (rounding straight-through, clips passing inside their range) and applies p <- clamp(p - lr sign(grad)) to v (lr_v)
+ * and to alpha, beta (lr_minmax) in place; dL/dv is never stored. dalpha_out / dbeta_out: fp32 [G,N] or NULL, the raw
+ * gradients. No floating-point atomics: the same inputs give the same bits. */
+WOQ_API int woq_autoround_step(const float* w_dev, float* v_dev, float* alpha_dev, float* beta_dev, const void* g_dev,
+                               int g_dtype, int K, int N, int group, int bits, int asym, float lr_v, float lr_minmax,
+                               float* dalpha_out_dev, float* dbeta_out_dev, void* stream);
+
+/* woq_autoround_codes: q int8 [K,N], scale fp32 [G,N], zp int8 [G,N] (NULL when sym) in the domain
+ * woq_repack_quantized_weight takes. */
+WOQ_API int woq_autoround_codes(const float* w_dev, const float* v_dev, const float* alpha_dev, const float* beta_dev,
+                                int K, int N, int group, int bits, int asym, int8_t* q_dev, float* scale_dev,
+                                int8_t* zp_dev, void* stream);
+
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device
  * memory from the host. */

@@ -1,0 +1,299 @@
+// woq_autoround.hip — the quantiser of AutoRound calibration (Cheng et al. 2023, "Optimize Weight Rounding via Signed
+// Gradient Descent"): its forward, its backward fused with the SignSGD update, and the final codes.
+// tests/autoround_reference.py is the float64 statement, transformers/llm/quantization/autoround.py the driver.
+//
+//   w      fp32 [K, N] row-major, row k = input feature k (Linear.weight.T)
+//   V      fp32 [K, N] in [-0.5, 0.5], the rounding offset         alpha, beta  fp32 [G, N] in [0, 1], the range factors
+//   group  `group` consecutive k of one column (the last may be short); mn = min(min v, 0), mx = max(max v, 0)
+//
+//   asym   lo = alpha mn, hi = beta mx, s = (hi - lo) / L (0 -> 1), z = clip(rne(-lo / s), 0, L)
+//          t = w / s + V, c = clip(rne(t) + z, 0, L), W~ = (c - z) s
+//   sym    amax = beta mx >= alpha (-mn) ? beta mx : alpha (-mn), s = amax / qmax (0 -> 1)
+//          t = w / s + V, c = clip(rne(t), -off, qmax), W~ = c s
+//
+// the package's RTN rule (rtn_kernel in woq_pack.hip, rtn_params / rtn_deq in woq_awq.hip) with V, alpha and beta put in,
+// in that rule's fp32 expression order, every step rounded on its own (no contraction): V = 0, alpha = beta = 1 gives
+// RTN's bits. The codes are clamped as floats before the conversion to int (the same values wherever RTN's int
+// arithmetic does not overflow; a tiny alpha makes w / s large).
+//
+// Gradients, rne straight-through, clip passing inside its range (bounds included), g = dL/dW~, q = c - z (asym) | c:
+//   an element whose code was not clipped   dV = g s (only its sign is used: sign(g), s > 0), ds += g (q - w / s)
+//   a clipped element                       dV = 0, asym: ds += g (q - lo / s), dlo += g; sym: ds += g c
+//   asym   dhi = ds / L, dlo -= ds / L, dalpha = dlo mn, dbeta = dhi mx
+//   sym    damax = ds / qmax, to beta (times mx) where beta mx >= alpha (-mn), else to alpha (times -mn)
+//   a group whose s was replaced by 1 gives alpha and beta no gradient
+// Step: p <- clamp(p - lr sign(grad)), sign(0) = 0; V in [-0.5, 0.5], alpha / beta in [0, 1]. dV is never stored.
+//
+// Layout, as awq_scale_delta_kernel: a thread owns one column of one group, a range pass then a main pass over the
+// group's rows; lanes side by side along N, every row access coalesced. The group sums ds and dlo stay in the thread's
+// registers in row order: no floating-point atomics, two runs give the same bits. One thread per column and group is
+// only N G / 64 waves (2048 for a 4096 x 4096 linear at group 128, two per SIMD, each with 128 dependent-free but
+// serially issued rows): groups of 64 rows and more are split over 4 threads of a workgroup (64 columns x 4 slices),
+// groups longer than 256 rows (group -1 on a wide layer) over 16 (1024 threads), contiguous rows each; the slices'
+// ranges (exact: min and max) and partial sums meet in LDS and slice 0 adds the partial sums in slice order, so the
+// combination order is fixed. Both row loops are unrolled by four for loads in flight. Measured against the
+// one-slice form in one session (profiles/r17_autoround.txt): forward 1.4 - 2.5 x, step 1.3 - 2.1 x at group 128.
+// fp32 VALU throughout. Memory bound: the forward reads w twice (the second time from L2: a workgroup's group is
+// 32 KiB at group 128) and V once and writes W~, 10 B per weight from HBM with a 16-bit output; the step reads w,
+// V and g and writes V, 14 - 16 B per weight. Measured at the Llama-2-7B shapes: forward 3.7 - 4.0 TB/s, step
+// 4.1 - 4.5 TB/s, about half of the 8 TB/s peak.
+// Registers (tools/kres.py), 1 / 4 / 16 slices: forward 25 / 32 / 32 VGPRs, step 48 / 52 / 52, codes 33 / 39 / 39;
+// 0 / 2 / 8 KiB LDS; eight waves per SIMD, no AGPRs, no scratch, no spills. The only fmas in the code are those of the
+// divisions.
+#include "woq_device.h"
+#include "woq_launch.h"
+
+namespace woq {
+namespace {
+
+constexpr int AR_THREADS = 256;      // one slice: 256 columns of one group per workgroup
+constexpr int AR_SPLIT_COLS = 64;    // a split group: 64 columns per workgroup, times the slices
+constexpr int AR_MID_ROWS = 64;      // groups of at least this many rows are split over AR_MID_SLICES threads per column,
+constexpr int AR_MID_SLICES = 4;
+constexpr int AR_SPLIT_ROWS = 256;   // groups longer than this over AR_SLICES (1024 threads)
+constexpr int AR_SLICES = 16;
+
+enum { AR_FORWARD = 0, AR_STEP = 1, AR_CODES = 2 };
+
+struct ArArgs {
+  const float* w;
+  float* v;      // read; written by the step
+  float* alpha;  // read; written by the step
+  float* beta;
+  int K, N, group, bits, asym;
+  // forward
+  void* out;
+  int out_dt;
+  // step
+  const void* g;
+  int g_dt;
+  float lr_v, lr_mm;
+  float* dalpha;  // nullable: the raw gradients
+  float* dbeta;
+  // codes
+  int8_t* q;
+  float* scale;
+  int8_t* zp;  // nullable (sym)
+};
+
+__device__ __forceinline__ float ar_sign(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+
+template <int MODE, int SLICES>
+__global__ __launch_bounds__(SLICES == 1 ? AR_THREADS : SLICES * AR_SPLIT_COLS) void autoround_kernel(const ArArgs a) {
+#pragma clang fp contract(off)
+  constexpr int COLS = SLICES == 1 ? AR_THREADS : AR_SPLIT_COLS;
+  __shared__ float red[SLICES == 1 ? 1 : 2 * SLICES * COLS];
+  const int n = blockIdx.x * COLS + threadIdx.x;
+  const int slice = SLICES == 1 ? 0 : (int)threadIdx.y;
+  const bool valid = n < a.N;
+  if (SLICES == 1 && !valid) return;  // no barrier on this path
+  const size_t N = (size_t)a.N;
+  const int k0 = blockIdx.y * a.group, k1 = min(a.K, k0 + a.group);
+  const int per = (k1 - k0 + SLICES - 1) / SLICES;
+  const int r0 = min(k1, k0 + slice * per), r1 = min(k1, r0 + per);
+  const size_t cell = (size_t)blockIdx.y * N + (size_t)n;
+
+  // the range: 0 belongs to it, so an empty slice is neutral
+  float mn = 0.f, mx = 0.f;
+  if (valid)
+#pragma unroll 4
+    for (int k = r0; k < r1; ++k) {
+      const float v = a.w[(size_t)k * N + n];
+      mx = fmaxf(mx, v);
+      mn = fminf(mn, v);
+    }
+  if constexpr (SLICES > 1) {
+    red[slice * COLS + threadIdx.x] = mn;
+    red[(SLICES + slice) * COLS + threadIdx.x] = mx;
+    __syncthreads();
+    for (int i = 0; i < SLICES; ++i) {
+      mn = fminf(mn, red[i * COLS + threadIdx.x]);
+      mx = fmaxf(mx, red[(SLICES + i) * COLS + threadIdx.x]);
+    }
+    __syncthreads();  // red is reused for the partial sums
+  }
+
+  const int qmax = (1 << (a.bits - 1)) - 1, levels = (1 << a.bits) - 1, off = 1 << (a.bits - 1);
+  const float al = valid ? a.alpha[cell] : 1.f, be = valid ? a.beta[cell] : 1.f;
+  float s, lo = 0.f, cmin, cmax;
+  int zi = 0;
+  bool beta_side = false;
+  if (a.asym) {
+    lo = al * mn;
+    const float hi = be * mx;
+    s = (hi - lo) / (float)levels;
+    cmin = 0.f;
+    cmax = (float)levels;
+  } else {
+    const float pa = be * mx, pb = al * (-mn);
+    beta_side = pa >= pb;
+    s = (beta_side ? pa : pb) / (float)qmax;
+    cmin = (float)-off;
+    cmax = (float)qmax;
+  }
+  const bool replaced = s == 0.f;
+  if (replaced) s = 1.f;
+  float los = 0.f;  // lo / s: where a clipped element's code sits, in steps
+  if (a.asym) {
+    zi = (int)fminf(fmaxf(rintf(-lo / s), 0.f), (float)levels);
+    los = lo / s;
+  }
+  const float zf = (float)zi;
+
+  float ds = 0.f, dlo = 0.f;
+  if (valid)
+#pragma unroll 4
+    for (int k = r0; k < r1; ++k) {
+      const size_t i = (size_t)k * N + n;
+      const float wk = a.w[i], vk = a.v[i];
+      const float wd = wk / s;
+      const float t = wd + vk;
+      const float rz = rintf(t) + zf;  // exact below 2^24, and clipped either way beyond
+      const int qi = (int)fminf(fmaxf(rz, cmin), cmax) - zi;
+      if constexpr (MODE == AR_FORWARD) {
+        store_f32(a.out, i, a.out_dt, (float)qi * s);
+      } else if constexpr (MODE == AR_CODES) {
+        a.q[i] = (int8_t)(a.asym ? qi + zi - off : qi);
+      } else {
+        const float gk = load_f32(a.g, i, a.g_dt);
+        const bool clipped = rz < cmin || rz > cmax;
+        const float qf = (float)qi;
+        if (!clipped) {
+          ds = ds + gk * (qf - wd);
+          a.v[i] = fminf(fmaxf(vk - a.lr_v * ar_sign(gk), -0.5f), 0.5f);
+        } else if (a.asym) {
+          ds = ds + gk * (qf - los);
+          dlo = dlo + gk;
+        } else {
+          ds = ds + gk * qf;
+        }
+      }
+    }
+
+  if constexpr (MODE == AR_CODES) {
+    if (valid && slice == 0) {
+      a.scale[cell] = s;
+      if (a.asym && a.zp) a.zp[cell] = (int8_t)(zi - off);
+    }
+  }
+  if constexpr (MODE == AR_STEP) {
+    if constexpr (SLICES > 1) {
+      red[slice * COLS + threadIdx.x] = ds;
+      red[(SLICES + slice) * COLS + threadIdx.x] = dlo;
+      __syncthreads();
+      if (slice != 0) return;
+      ds = 0.f, dlo = 0.f;
+      for (int i = 0; i < SLICES; ++i) {  // slice order, fixed
+        ds = ds + red[i * COLS + threadIdx.x];
+        dlo = dlo + red[(SLICES + i) * COLS + threadIdx.x];
+      }
+    }
+    if (!valid) return;
+    float da = 0.f, db = 0.f;
+    if (!replaced) {
+      if (a.asym) {
+        const float dhi = ds / (float)levels;
+        da = (dlo - dhi) * mn;
+        db = dhi * mx;
+      } else {
+        const float dm = ds / (float)qmax;
+        if (beta_side)
+          db = dm * mx;
+        else
+          da = dm * (-mn);
+      }
+    }
+    if (a.dalpha) a.dalpha[cell] = da;
+    if (a.dbeta) a.dbeta[cell] = db;
+    a.alpha[cell] = fminf(fmaxf(al - a.lr_mm * ar_sign(da), 0.f), 1.f);
+    a.beta[cell] = fminf(fmaxf(be - a.lr_mm * ar_sign(db), 0.f), 1.f);
+  }
+}
+
+bool ar_bits_ok(int bits) { return bits == 2 || bits == 3 || bits == 4 || bits == 8; }
+bool ar_dtype_ok(int dt) { return dt == WOQ_F32 || dt == WOQ_BF16 || dt == WOQ_F16; }
+
+// the shape checks every entry point shares; fills K, N, group (as the kernel takes it) and the grid
+const char* ar_shape(ArArgs& a, dim3& grid, dim3& block, int& slices) {
+  if (a.K < 1 || a.N < 1) return "bad shape";
+  if (!ar_bits_ok(a.bits)) return "bits must be 2, 3, 4 or 8";
+  if (a.group <= 0 || a.group > a.K) a.group = a.K;  // one group per column
+  const int n_groups = (a.K + a.group - 1) / a.group;
+  if (n_groups > 65535) return "more than 65535 groups";
+  slices = a.group > AR_SPLIT_ROWS ? AR_SLICES : (a.group >= AR_MID_ROWS ? AR_MID_SLICES : 1);
+  const int cols = slices > 1 ? AR_SPLIT_COLS : AR_THREADS;
+  grid = dim3((unsigned)((a.N + cols - 1) / cols), (unsigned)n_groups);
+  block = slices > 1 ? dim3(AR_SPLIT_COLS, slices) : dim3(AR_THREADS);
+  return nullptr;
+}
+
+template <int MODE>
+void ar_launch(const ArArgs& a, dim3 grid, dim3 block, int slices, hipStream_t st) {
+  if (slices == AR_SLICES)
+    hipLaunchKernelGGL((autoround_kernel<MODE, AR_SLICES>), grid, block, 0, st, a);
+  else if (slices == AR_MID_SLICES)
+    hipLaunchKernelGGL((autoround_kernel<MODE, AR_MID_SLICES>), grid, block, 0, st, a);
+  else
+    hipLaunchKernelGGL((autoround_kernel<MODE, 1>), grid, block, 0, st, a);
+}
+
+}  // namespace
+}  // namespace woq
+
+extern "C" int woq_autoround_forward(const float* w_dev, const float* v_dev, const float* alpha_dev,
+                                     const float* beta_dev, int K, int N, int group, int bits, int asym, void* out_dev,
+                                     int out_dtype, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(w_dev && v_dev && alpha_dev && beta_dev && out_dev, "QBits: autoround_forward: null tensor");
+  WOQ_CHECK(woq::ar_dtype_ok(out_dtype), "QBits: autoround_forward: the output is fp32, fp16 or bf16");
+  woq::ArArgs a = {};
+  a.w = w_dev, a.v = const_cast<float*>(v_dev), a.alpha = const_cast<float*>(alpha_dev);
+  a.beta = const_cast<float*>(beta_dev);
+  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.out = out_dev, a.out_dt = out_dtype;
+  dim3 grid, block;
+  int slices;
+  if (const char* why = woq::ar_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: autoround_forward: ") + why);
+  woq::ar_launch<woq::AR_FORWARD>(a, grid, block, slices, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+extern "C" int woq_autoround_step(const float* w_dev, float* v_dev, float* alpha_dev, float* beta_dev, const void* g_dev,
+                                  int g_dtype, int K, int N, int group, int bits, int asym, float lr_v, float lr_minmax,
+                                  float* dalpha_out_dev, float* dbeta_out_dev, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(w_dev && v_dev && alpha_dev && beta_dev && g_dev, "QBits: autoround_step: null tensor");
+  WOQ_CHECK(woq::ar_dtype_ok(g_dtype), "QBits: autoround_step: the gradient is fp32, fp16 or bf16");
+  WOQ_CHECK(lr_v >= 0.f && lr_minmax >= 0.f, "QBits: autoround_step: a learning rate is negative or not a number");
+  woq::ArArgs a = {};
+  a.w = w_dev, a.v = v_dev, a.alpha = alpha_dev, a.beta = beta_dev;
+  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.g = g_dev, a.g_dt = g_dtype, a.lr_v = lr_v, a.lr_mm = lr_minmax;
+  a.dalpha = dalpha_out_dev, a.dbeta = dbeta_out_dev;
+  dim3 grid, block;
+  int slices;
+  if (const char* why = woq::ar_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: autoround_step: ") + why);
+  woq::ar_launch<woq::AR_STEP>(a, grid, block, slices, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+extern "C" int woq_autoround_codes(const float* w_dev, const float* v_dev, const float* alpha_dev, const float* beta_dev,
+                                   int K, int N, int group, int bits, int asym, int8_t* q_dev, float* scale_dev,
+                                   int8_t* zp_dev, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(w_dev && v_dev && alpha_dev && beta_dev && q_dev && scale_dev, "QBits: autoround_codes: null tensor");
+  WOQ_CHECK(!asym || zp_dev, "QBits: autoround_codes: asym needs a zero-point tensor");
+  woq::ArArgs a = {};
+  a.w = w_dev, a.v = const_cast<float*>(v_dev), a.alpha = const_cast<float*>(alpha_dev);
+  a.beta = const_cast<float*>(beta_dev);
+  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.q = q_dev, a.scale = scale_dev, a.zp = zp_dev;
+  dim3 grid, block;
+  int slices;
+  if (const char* why = woq::ar_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: autoround_codes: ") + why);
+  woq::ar_launch<woq::AR_CODES>(a, grid, block, slices, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}

@@ -16,7 +16,7 @@ __all__ = [
     "woq_linear", "repack_quantized_weight", "quantize_to_packed_weight", "dequantize_packed_weight",
     "acquire_packed_weight_info", "get_packed_weight_size", "set_woq_workspace", "set_qbits_threads",
     "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
-    "awq_scale_delta", "awq_clip_search",
+    "awq_scale_delta", "awq_clip_search", "autoround_forward", "autoround_step", "autoround_codes",
 ]
 
 
@@ -188,6 +188,67 @@ def awq_clip_search(w, h, group, bits, asym, n_grid=20, n_cand=10, w_out=None, l
                                         int(bool(asym)), int(n_grid), int(n_cand), _ptr(best), _ptr(losses),
                                         _ptr(w_out), L.stream_ptr()))
     return best, losses, w_out
+
+
+def _autoround_args(name, w, v, alpha, beta, group):
+    """the argument checks the three AutoRound calls share -> (K, N, G)"""
+    if w.dim() != 2:
+        raise RuntimeError("QBits: %s: w must be [K,N]" % name)
+    k, n = w.shape
+    g = k if group <= 0 or group > k else group
+    n_groups = (k + g - 1) // g
+    if not (_f32_dev(w, (k, n)) and _f32_dev(v, (k, n)) and _f32_dev(alpha, (n_groups, n))
+            and _f32_dev(beta, (n_groups, n))):
+        raise RuntimeError("QBits: %s takes contiguous fp32 device tensors w [K,N], v [K,N], alpha [G,N], beta [G,N]"
+                           % name)
+    return k, n, n_groups
+
+
+_AUTOROUND_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def autoround_forward(w, v, alpha, beta, group, bits, asym, out=None, dtype=None):
+    """AutoRound's fake-quantised weight W~ [K, N] (woq_autoround_forward, csrc/woq_autoround.hip; no reference
+    counterpart): w fp32 [K, N] (working order, Linear.weight.T), v fp32 [K, N] the rounding offset, alpha / beta fp32
+    [G, N] the range factors; v = 0, alpha = beta = 1 is the RTN rule of `quantize_to_packed_weight` at (bits, group,
+    asym). Returns `out` (fp32, fp16 or bf16; allocated as `dtype`, default fp32, when None)."""
+    k, n, _ = _autoround_args("autoround_forward", w, v, alpha, beta, group)
+    if out is None:
+        out = torch.empty(k, n, dtype=dtype or torch.float32, device=w.device)
+    if not (out.is_cuda and out.dtype in _AUTOROUND_DTYPES and out.is_contiguous() and tuple(out.shape) == (k, n)):
+        raise RuntimeError("QBits: autoround_forward: out must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
+    L.check(L.lib().woq_autoround_forward(_ptr(w), _ptr(v), _ptr(alpha), _ptr(beta), k, n, int(group), int(bits),
+                                          int(bool(asym)), _ptr(out), L.torch_dtype_code(out.dtype), L.stream_ptr()))
+    return out
+
+
+def autoround_step(w, v, alpha, beta, g, group, bits, asym, lr_v, lr_minmax, dalpha=None, dbeta=None):
+    """One SignSGD step of AutoRound on one linear (woq_autoround_step, csrc/woq_autoround.hip): from g = dL/dW~ [K, N]
+    (fp32, fp16 or bf16) the forward is recomputed, the gradients of v, alpha and beta formed (rounding straight-through)
+    and p <- clamp(p - lr sign(grad)) applied in place to v (lr_v, kept in [-0.5, 0.5]) and alpha / beta (lr_minmax, kept
+    in [0, 1]). dalpha / dbeta: optional fp32 [G, N] outputs for the raw gradients."""
+    k, n, n_groups = _autoround_args("autoround_step", w, v, alpha, beta, group)
+    if not (g.is_cuda and g.dtype in _AUTOROUND_DTYPES and g.is_contiguous() and tuple(g.shape) == (k, n)):
+        raise RuntimeError("QBits: autoround_step: g must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
+    for t in (dalpha, dbeta):
+        if t is not None and not _f32_dev(t, (n_groups, n)):
+            raise RuntimeError("QBits: autoround_step: dalpha / dbeta must be contiguous fp32 device tensors [G,N]")
+    L.check(L.lib().woq_autoround_step(_ptr(w), _ptr(v), _ptr(alpha), _ptr(beta), _ptr(g), L.torch_dtype_code(g.dtype),
+                                       k, n, int(group), int(bits), int(bool(asym)), float(lr_v), float(lr_minmax),
+                                       _ptr(dalpha), _ptr(dbeta), L.stream_ptr()))
+
+
+def autoround_codes(w, v, alpha, beta, group, bits, asym):
+    """The codes of AutoRound's quantiser at (v, alpha, beta) (woq_autoround_codes, csrc/woq_autoround.hip) ->
+    (q int8 [K, N], scale fp32 [G, N], zp int8 [G, N] or None (sym)) in the signed domain `repack_quantized_weight`
+    takes, as `gptq_quantize_weight` returns them."""
+    k, n, n_groups = _autoround_args("autoround_codes", w, v, alpha, beta, group)
+    q = torch.empty(k, n, dtype=torch.int8, device=w.device)
+    scale = torch.empty(n_groups, n, dtype=torch.float32, device=w.device)
+    zp = torch.empty(n_groups, n, dtype=torch.int8, device=w.device) if asym else None
+    L.check(L.lib().woq_autoround_codes(_ptr(w), _ptr(v), _ptr(alpha), _ptr(beta), k, n, int(group), int(bits),
+                                        int(bool(asym)), _ptr(q), _ptr(scale), _ptr(zp), L.stream_ptr()))
+    return q, scale, zp
 
 
 def dequantize_packed_weight(compressed_weight, dequantize_weight, transpose, compute_type, weight_type, scale_type):

@@ -1,0 +1,275 @@
+"""AutoRound calibration on the device: `from_pretrained(fp_model, quantization_config=AutoRoundConfig(...))`.
+
+The reference hands this step to neural_compressor / auto-round (external; reference utils.py:531-702); here the method
+(Cheng et al. 2023, "Optimize Weight Rounding via Signed Gradient Descent") is restated — tests/autoround_reference.py
+is the float64 statement of its quantiser. Per linear the trainables are a rounding offset V [K, N] in [-0.5, 0.5]
+(initially 0) and two range factors alpha, beta [G, N] in [0, 1] (initially 1); V = 0, alpha = beta = 1 is the
+package's RTN. They are trained decoder block by decoder block with SignSGD against the fp block's outputs:
+
+  forward    every eligible linear computes x.matmul(W~) + bias with W~ = qbits.autoround_forward(w, V, alpha, beta)
+             (csrc/woq_autoround.hip), one launch per linear per iteration
+  backward   autograd gives dL/dW~ (the block's own ops, torch); qbits.autoround_step turns it into the three gradients
+             and applies p <- clamp(p - lr_t sign(grad)) in place, one launch per linear; lr_t = lr (1 - t / iters)
+  keep       the parameters at the lowest loss seen (iteration 0 is RTN), then qbits.autoround_codes ->
+             QuantizedLinearQBits.set_weights_bias, as gptq.py finishes: a plain blob, nothing new for save / load or
+             the engine
+
+A minibatch is drawn from the calibration batches (`calibration_batches`: rows of equal length, `batch_size` of them,
+default 8): whole batches in a random order until `batch_size` samples are reached, from a torch.Generator seeded
+with 42. torch does the GEMM-shaped parts and the block's backward on purpose, as in gptq.py.
+"""
+import logging
+
+import torch
+
+from .... import qbits
+from .gptq import _BITS, _Stop, _block_linears, _data_source, _decoder_blocks, _is_conv1d, _run_block
+from .gptq import calibration_batches
+from .nn.modules import QuantizedLinearQBits
+
+logger = logging.getLogger(__name__)
+
+SEED = 42  # of the minibatch draw
+DEFAULT_BATCH = 8
+
+
+def _check_options(model, config):
+    for opt in ("use_double_quant", "layer_wise", "quant_lm_head"):
+        if getattr(config, opt, False):
+            raise NotImplementedError("AutoRound on the MI355X path does not implement %s" % opt)
+    if config.weight_dtype not in _BITS:
+        raise NotImplementedError("AutoRound quantises to the integer weight types (int4_clip, int8), not "
+                                  "weight_dtype=%s" % config.weight_dtype)
+    _decoder_blocks(model)
+    try:
+        _data_source(config)
+    except NotImplementedError:
+        raise NotImplementedError(
+            "AutoRoundConfig calibration is not part of the MI355X hot path without calibration data (dataset=%r is "
+            "not downloaded): pass calib_dataloader= (an iterable of input_ids tensors) or dataset=[texts] with "
+            "tokenizer=" % (getattr(config, "dataset", None),)) from None
+
+
+def validate_autoround_request(model, config):
+    """Everything about a request that can be refused without touching a device."""
+    _check_options(model, config)
+
+
+def learning_rates(config):
+    """(iters, lr, minmax_lr): lr defaults to 1 / iters, minmax_lr to lr"""
+    iters = max(0, int(config.iters))
+    lr = getattr(config, "lr", None)
+    lr = (1.0 / iters if iters else 0.0) if lr is None else float(lr)
+    mm = getattr(config, "minmax_lr", None)
+    return iters, lr, (lr if mm is None else float(mm))
+
+
+def schedule(lr, t, iters):
+    """the learning rate of iteration t: linear decay to zero at `iters`"""
+    return lr * (1.0 - t / iters)
+
+
+class _Batched:
+    """the config as `calibration_batches` reads it, with AutoRound's batch size"""
+
+    def __init__(self, config):
+        self._config = config
+        self.batch_size = int(getattr(config, "batch_size", DEFAULT_BATCH) or DEFAULT_BATCH)
+
+    def __getattr__(self, name):
+        return getattr(self._config, name)
+
+
+class _Quantiser:
+    """the trainables of one linear and what the two launches need"""
+
+    def __init__(self, module, group, bits, asym, dtype):
+        w = module.weight.data if _is_conv1d(module) else module.weight.data.t()
+        self.w = w.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        k, n = self.w.shape
+        g = k if group <= 0 or group > k else group
+        self.group, self.bits, self.asym, self.dtype = group, bits, asym, dtype
+        # V is the tensor autograd sees (FakeQuant needs an input that requires grad); it never receives one
+        self.v = torch.zeros(k, n, dtype=torch.float32, device=w.device).requires_grad_(True)
+        self.alpha = torch.ones((k + g - 1) // g, n, dtype=torch.float32, device=w.device)
+        self.beta = torch.ones_like(self.alpha)
+        self.bias = module.bias.data if module.bias is not None else None
+        self.lr_v = self.lr_mm = 0.0
+        self.wq = None
+
+    def params(self):
+        return self.v.detach().clone(), self.alpha.clone(), self.beta.clone()
+
+
+class FakeQuant(torch.autograd.Function):
+    """W~ of one linear: the forward is qbits.autoround_forward, the backward the fused gradient + SignSGD step
+    (qbits.autoround_step) on the quantiser's own tensors; no gradient is returned."""
+
+    @staticmethod
+    def forward(ctx, v, q):
+        ctx.q = q
+        return qbits.autoround_forward(q.w, v.detach(), q.alpha, q.beta, q.group, q.bits, q.asym, dtype=q.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        q = ctx.q
+        qbits.autoround_step(q.w, q.v.detach(), q.alpha, q.beta, g.contiguous(), q.group, q.bits, q.asym, q.lr_v,
+                             q.lr_mm)
+        return None, None
+
+
+def _wrap(module, q):
+    def forward(x):
+        y = x.matmul(q.wq)
+        return y + q.bias if q.bias is not None else y
+
+    module.forward = forward
+
+
+def _next_inputs(inputs, outs):
+    return [((y,) + tuple(args[1:]), kwargs) if args else ((), dict(kwargs, hidden_states=y))
+            for (args, kwargs), y in zip(inputs, outs)]
+
+
+def _samples(unit):
+    args, kwargs = unit
+    x = args[0] if args else kwargs["hidden_states"]
+    return int(x.shape[0])
+
+
+def _train_block(block, quantisers, inputs, targets, iters, lr, minmax_lr, batch_size, gen):
+    """`iters` SignSGD iterations on one block -> (rtn_loss, best_loss, best_iter, best parameters per linear)"""
+    best, best_loss, best_iter, rtn_loss = None, None, -1, None
+    flags = [(p, p.requires_grad) for p in block.parameters()]
+    for p, _ in flags:
+        p.requires_grad_(False)
+    try:
+        with torch.enable_grad():
+            for t in range(iters):
+                order = torch.randperm(len(inputs), generator=gen).tolist()
+                picked, count = [], 0
+                for i in order:
+                    picked.append(i)
+                    count += _samples(inputs[i])
+                    if count >= batch_size:
+                        break
+                for q in quantisers:
+                    q.lr_v, q.lr_mm = schedule(lr, t, iters), schedule(minmax_lr, t, iters)
+                    q.wq = FakeQuant.apply(q.v, q)
+                total = sum(targets[i].numel() for i in picked)
+                loss = 0.0
+                for i in picked:
+                    y = _run_block(block, [inputs[i]])[0]
+                    loss = loss + (y.float() - targets[i].float()).square().sum()
+                loss = loss / total
+                value = float(loss.detach())
+                if t == 0:
+                    rtn_loss = value
+                if best_loss is None or value < best_loss:  # before the update: these parameters gave this loss
+                    best_loss, best_iter = value, t
+                    best = [q.params() for q in quantisers]
+                loss.backward()
+                for q in quantisers:
+                    q.wq = None
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
+    return rtn_loss, best_loss, best_iter, best
+
+
+@torch.no_grad()
+def autoround_quantize_model(model, config, device="cuda"):
+    """Quantise every eligible linear of every decoder block of an fp model with AutoRound, in place. Block by block:
+    the fp block's outputs on the fp inputs are the targets; the block's linears run with the fake quantiser while V,
+    alpha and beta take `config.iters` SignSGD steps; the best parameters become the blob. With
+    `disable_quanted_input=True` (the default) the next block trains on the fp outputs, otherwise on the outputs of the
+    blocks quantised so far (two input lists), the targets still from the fp stream. `iters=0` is RTN through this path.
+    lm_head and whatever else `llm_int8_skip_modules` names stay. model._autoround_log: (rtn_loss, best_loss, best_iter)
+    per block."""
+    _check_options(model, config)
+    batched = _Batched(config)
+    batches = calibration_batches(batched)
+    path, blocks = _decoder_blocks(model)
+    skip = list(getattr(config, "llm_int8_skip_modules", None) or [])
+    bits = _BITS[config.weight_dtype]
+    asym = not bool(config.sym)
+    iters, lr, minmax_lr = learning_rates(config)
+    fp_stream_only = bool(getattr(config, "disable_quanted_input", True))
+    model.to(device)
+    model.eval()
+
+    inputs = []
+
+    def grab(_module, args, kwargs):
+        inputs.append((args, kwargs))
+        raise _Stop()
+
+    handle = blocks[0].register_forward_pre_hook(grab, with_kwargs=True)
+    use_cache = getattr(model.config, "use_cache", None) if hasattr(model, "config") else None
+    try:
+        if use_cache is not None:
+            model.config.use_cache = False
+        for ids in batches:
+            try:
+                model(input_ids=ids.to(device))
+            except _Stop:
+                pass
+    finally:
+        handle.remove()
+        if use_cache is not None:
+            model.config.use_cache = use_cache
+
+    gen = torch.Generator().manual_seed(SEED)
+    q_inputs = inputs  # what the block trains on; the fp stream itself unless disable_quanted_input=False
+    model._autoround_log = []
+    tf32 = torch.backends.cuda.matmul.allow_tf32
+    torch.backends.cuda.matmul.allow_tf32 = False
+    try:
+        for li, block in enumerate(blocks):
+            where = "%s.%d" % (path, li)
+            linears = _block_linears(block, where, skip)
+            targets = _run_block(block, inputs)
+            dtype = targets[0].dtype if targets[0].dtype in (torch.float16, torch.bfloat16) else torch.float32
+            quantisers = [_Quantiser(m, config.group_size, bits, asym, dtype) for _, m in linears]
+            entry = (None, None, -1)
+            if iters > 0 and quantisers:
+                for (_, m), q in zip(linears, quantisers):
+                    _wrap(m, q)
+                try:
+                    rtn_loss, best_loss, best_iter, best = _train_block(block, quantisers, q_inputs, targets, iters, lr,
+                                                                        minmax_lr, batched.batch_size, gen)
+                finally:
+                    for _, m in linears:
+                        del m.forward
+                entry = (rtn_loss, best_loss, best_iter)
+                logger.info("AutoRound %s: loss %.6g at iteration %d (RTN %.6g)", where, best_loss, best_iter, rtn_loss)
+            else:
+                best = [q.params() for q in quantisers]
+            model._autoround_log.append(entry)
+
+            for (name, m), q, (v, alpha, beta) in zip(linears, quantisers, best):
+                codes, scales, zeros = qbits.autoround_codes(q.w, v, alpha, beta, config.group_size, bits, asym)
+                k, n = codes.shape
+                new = QuantizedLinearQBits(k, n, m.bias is not None, compute_dtype=config.compute_dtype,
+                                           compress_statistics=False, weight_dtype=config.weight_dtype, bits=config.bits,
+                                           scale_dtype=config.scale_dtype, blocksize=config.group_size,
+                                           scheme=config.scheme, device=device)
+                if bits == 4:  # set_weights_bias takes 4-bit values unsigned, as the checkpoint formats store them
+                    codes = codes + 8
+                    zeros = zeros + 8 if zeros is not None else None
+                new.set_weights_bias(codes, scales, zeros, torch.empty(0, dtype=torch.int32), config,
+                                     m.bias.data if m.bias is not None else None)
+                new.source_cls = type(m)
+                new.requires_grad_(False)
+                parent_name, _, leaf = name.rpartition(".")
+                parent = block.get_submodule(parent_name) if parent_name else block
+                parent._modules[leaf] = new
+            del quantisers, best
+            if not fp_stream_only:
+                q_inputs = _next_inputs(q_inputs, _run_block(block, q_inputs))
+            inputs = _next_inputs(inputs, targets)
+            if fp_stream_only:
+                q_inputs = inputs
+    finally:
+        torch.backends.cuda.matmul.allow_tf32 = tf32
+    return model

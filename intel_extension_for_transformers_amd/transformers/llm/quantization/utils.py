@@ -222,17 +222,21 @@ def convert_to_quantized_model(model, config, device="cuda"):
     or `config.dataset=[texts]` + tokenizer, the sweep in csrc/woq_gptq.hip); the decoder blocks' linears are
     quantised, lm_head and anything outside the blocks stays as it is. AWQ on an fp model: calibrate on the device the
     same way (awq.py awq_quantize_model: the scale and clip searches of csrc/woq_awq.hip; scales are folded into the
-    norms / preceding projections of Llama-class blocks, the result is a plain RTN blob). TEQ / AutoRound are trained
-    searches that the reference runs inside neural_compressor (external); those configs (and GPTQ / AWQ) are accepted
-    for PRE-QUANTISED checkpoints (optimum-format tensors already on the modules), and raise for an fp model instead of
-    silently falling back to RTN."""
+    norms / preceding projections of Llama-class blocks, the result is a plain RTN blob). AutoRound on an fp model:
+    trained on the device, block by block (autoround.py autoround_quantize_model: SignSGD on a rounding offset and two
+    range factors per group, the quantiser's forward and its backward + update in csrc/woq_autoround.hip; the result is
+    a plain blob). TEQ is a trained search that the reference runs inside neural_compressor (external); that config
+    (like GPTQ / AWQ / AutoRound) is accepted for PRE-QUANTISED checkpoints (optimum-format tensors already on the
+    modules), and raises for an fp model instead of silently falling back to RTN."""
     method = getattr(config.quant_method, "value", config.quant_method)
     has_packed = any(_packed_checkpoint_linear(m) for m in model.modules())
-    if method in ("gptq", "awq") and not has_packed:
+    if method in ("gptq", "awq", "autoround") and not has_packed:
         if method == "gptq":
             from .gptq import gptq_quantize_model as calibrate, validate_gptq_request as validate
-        else:
+        elif method == "awq":
             from .awq import awq_quantize_model as calibrate, validate_awq_request as validate
+        else:
+            from .autoround import autoround_quantize_model as calibrate, validate_autoround_request as validate
 
         validate(model, config)  # NotImplementedError for what is not built, before a device is needed
         if str(device) == "cpu":

@@ -364,6 +364,13 @@ class AutoRoundConfig(ITREXQuantizationConfigMixin):
                ("disable_quanted_input", True), ("n_samples", 128), ("seq_len", 2048), ("iters", 200),
                ("quant_lm_head", False), ("layer_wise", False)) + _TAIL
 
+    def __init__(self, *args, **kwargs):
+        # calibration data for an fp model (transformers/llm/quantization/autoround.py), as GPTQConfig takes it: kept by
+        # reference, never copied or serialised
+        loader = kwargs.pop("calib_dataloader", None)
+        super().__init__(*args, **kwargs)
+        self.calib_dataloader = loader
+
 
 # the pre-split name used by BASELINE.json's north star (not present in the reference snapshot)
 WeightOnlyQuantConfig = RtnConfig
