@@ -188,16 +188,24 @@ WOQ_API int woq_linear(const void* act_dev, int act_dtype, int lda, const void* 
 
 /* ---- ops between the linears (replace stock-HF module forwards) -------------- */
 
-/* HF LlamaRMSNorm: out = x * rsqrt(mean(x^2) + eps) * weight ; x/out dtype [rows, d], weight fp32 [d]. */
+/* The four calls below refuse, before any launch, a dtype code other than WOQ_F32, WOQ_F16 or WOQ_BF16, a null pointer
+ * with a non-zero size and a negative size; rows / tokens / heads / n == 0 is a no-op. Results are computed in fp32 and
+ * rounded once on store (nearest even; fp16 overflow goes to +-inf, nothing saturates). */
+
+/* HF LlamaRMSNorm: out = x * rsqrt(mean(x^2) + eps) * weight ; x/out dtype [rows, d], weight fp32 [d].
+ * dtype, out_dtype: WOQ_F32, WOQ_F16 or WOQ_BF16, each on its own; rows >= 0, d > 0; x, out contiguous [rows, d]. */
 WOQ_API int woq_rmsnorm(const void* x_dev, int dtype, const float* weight_dev, float eps, int rows, int d,
                         void* out_dev, int out_dtype, void* stream);
 /* HF apply_rotary_pos_emb (rotate_half) in place on x [tokens, heads, D]; cos/sin fp32 tables
- * [max_pos, D/2]; pos int32 [tokens] (device). */
+ * [max_pos, D/2]; pos int32 [tokens] (device).
+ * dtype: WOQ_F32, WOQ_F16 or WOQ_BF16; tokens, heads >= 0, D even; every pos[t] in [0, max_pos) (not checked). */
 WOQ_API int woq_rope(void* x_dev, int dtype, const int32_t* pos_dev, const float* cos_dev, const float* sin_dev,
                      int tokens, int heads, int D, void* stream);
-/* HF LlamaMLP elementwise part: out = silu(gate) * up, n elements. */
+/* HF LlamaMLP elementwise part: out = silu(gate) * up, n elements.
+ * dtype: WOQ_F32, WOQ_F16 or WOQ_BF16, shared by gate, up and out [n]; out may be gate or up. */
 WOQ_API int woq_silu_mul(const void* gate_dev, const void* up_dev, int dtype, size_t n, void* out_dev, void* stream);
-/* GeLU: approximate != 0 -> tanh form ("gelu_new", GPT-2), else erf form. */
+/* GeLU: approximate != 0 -> tanh form ("gelu_new", GPT-2), else erf form.
+ * dtype: WOQ_F32, WOQ_F16 or WOQ_BF16, shared by x and out [n]; out may be x. */
 WOQ_API int woq_gelu(const void* x_dev, int dtype, size_t n, int approximate, void* out_dev, void* stream);
 
 /* ---- fused batch-1 decode engine (Llama-class decoder; the measured path of bench.py) ----------

@@ -343,13 +343,18 @@ void launch_argmax_embed(const float* pmax, const int32_t* pidx, int n, int32_t*
 
 using namespace woq;
 
+// the element ops' load_f32 / store_f32 read every code that is not fp32 or bf16 as two-byte fp16
+static bool elem_dtype_ok(int dt) { return dt == WOQ_F32 || dt == WOQ_F16 || dt == WOQ_BF16; }
+
 extern "C" {
 
 int woq_rmsnorm(const void* x_dev, int dtype, const float* weight_dev, float eps, int rows, int d, void* out_dev,
                 int out_dtype, void* stream) {
   WOQ_TRY
   WOQ_CHECK(rows >= 0 && d > 0, "QBits: bad rmsnorm shape");
+  WOQ_CHECK(elem_dtype_ok(dtype) && elem_dtype_ok(out_dtype), "QBits: rmsnorm takes fp32, fp16 or bf16 in and out");
   if (rows == 0) return 0;
+  WOQ_CHECK(x_dev && weight_dev && out_dev, "QBits: rmsnorm: null x, weight or out");
   hipLaunchKernelGGL(rmsnorm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x_dev, dtype, weight_dev, eps, d,
                      out_dev, out_dtype);
   WOQ_HIP(hipGetLastError());
@@ -360,8 +365,11 @@ int woq_rope(void* x_dev, int dtype, const int32_t* pos_dev, const float* cos_de
              int heads, int D, void* stream) {
   WOQ_TRY
   WOQ_CHECK((D & 1) == 0, "QBits: rope head_dim must be even");
+  WOQ_CHECK(tokens >= 0 && heads >= 0 && D >= 0, "QBits: bad rope shape");
+  WOQ_CHECK(elem_dtype_ok(dtype), "QBits: rope takes fp32, fp16 or bf16");
   size_t total = (size_t)tokens * heads * (D / 2);
   if (total == 0) return 0;
+  WOQ_CHECK(x_dev && pos_dev && cos_dev && sin_dev, "QBits: rope: null x, pos, cos or sin");
   hipLaunchKernelGGL(rope_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev,
                      dtype, pos_dev, cos_dev, sin_dev, heads, D, total);
   WOQ_HIP(hipGetLastError());
@@ -370,7 +378,9 @@ int woq_rope(void* x_dev, int dtype, const int32_t* pos_dev, const float* cos_de
 
 int woq_silu_mul(const void* gate_dev, const void* up_dev, int dtype, size_t n, void* out_dev, void* stream) {
   WOQ_TRY
+  WOQ_CHECK(elem_dtype_ok(dtype), "QBits: silu_mul takes fp32, fp16 or bf16");
   if (n == 0) return 0;
+  WOQ_CHECK(gate_dev && up_dev && out_dev, "QBits: silu_mul: null gate, up or out");
   unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(silu_mul_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, gate_dev, up_dev, dtype, n,
                      out_dev);
@@ -380,7 +390,9 @@ int woq_silu_mul(const void* gate_dev, const void* up_dev, int dtype, size_t n, 
 
 int woq_gelu(const void* x_dev, int dtype, size_t n, int approximate, void* out_dev, void* stream) {
   WOQ_TRY
+  WOQ_CHECK(elem_dtype_ok(dtype), "QBits: gelu takes fp32, fp16 or bf16");
   if (n == 0) return 0;
+  WOQ_CHECK(x_dev && out_dev, "QBits: gelu: null x or out");
   unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(gelu_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x_dev, dtype, n, approximate,
                      out_dev);

@@ -379,36 +379,77 @@ def check_torch_compatibility(version):
 
 
 # ---- ops between the linears (no reference boundary exists for these: they replace HF module forwards) ----
+# The kernels index by the sizes handed down and nothing else, so every tensor is checked here: a wrong dtype, length or
+# device would be an out-of-bounds access, not an error. Inputs may be strided (they are copied); outputs may not.
+def _elem_dev(t, like, numel=None, shape=None):
+    """t: a contiguous fp32 / fp16 / bf16 tensor on `like`'s device, of this numel / shape when given"""
+    return (t.is_cuda and t.device == like.device and t.is_contiguous() and L.torch_dtype_code(t.dtype) is not None
+            and (numel is None or t.numel() == numel) and (shape is None or tuple(t.shape) == tuple(shape)))
+
+
 def rmsnorm(x, weight, eps, out=None):
-    x = x.contiguous()
+    """out = x / sqrt(mean(x^2) + eps) * weight over the last dimension of x [..., d] (fp32 / fp16 / bf16, device);
+    weight [d] on the device (a 16-bit weight is widened to fp32); out (allocated when None): x's shape, any of the
+    three types, contiguous."""
+    code = L.torch_dtype_code(x.dtype)
+    if not (x.is_cuda and x.dim() >= 1 and x.shape[-1] > 0):
+        raise RuntimeError("QBits: rmsnorm takes a device tensor x [..., d] with d > 0")
     d = x.shape[-1]
+    if not (_elem_dev(weight.contiguous(), x, shape=(d,))):
+        raise RuntimeError("QBits: rmsnorm takes a device weight [d] (fp32, fp16 or bf16)")
+    x = x.contiguous()
     out = torch.empty_like(x) if out is None else out
-    L.check(L.lib().woq_rmsnorm(_ptr(x), L.torch_dtype_code(x.dtype), _ptr(weight.float().contiguous()), float(eps),
-                                x.numel() // d, d, _ptr(out), L.torch_dtype_code(out.dtype), L.stream_ptr()))
+    if not _elem_dev(out, x, shape=x.shape):
+        raise RuntimeError("QBits: rmsnorm: out must be a contiguous device tensor of x's shape (fp32, fp16 or bf16)")
+    L.check(L.lib().woq_rmsnorm(_ptr(x), code, _ptr(weight.float().contiguous()), float(eps), x.numel() // d, d,
+                                _ptr(out), L.torch_dtype_code(out.dtype), L.stream_ptr()))
     return out
 
 
 def rope(x, pos, cos, sin):
-    """In place on x [tokens, heads, D]; cos/sin fp32 [max_pos, D/2]; pos int32 [tokens] (device)."""
-    if not x.is_contiguous():
-        raise RuntimeError("QBits: rope needs a contiguous [tokens, heads, D] tensor")
+    """In place on x [tokens, heads, D] (fp32 / fp16 / bf16, contiguous, D even); cos/sin fp32 [max_pos, D/2]; pos int32
+    [tokens] (device). Every pos[t] must lie in [0, max_pos): the values live on the device and are not read here."""
+    code = L.torch_dtype_code(x.dtype)
+    if not (x.dim() == 3 and _elem_dev(x, x)):
+        raise RuntimeError("QBits: rope needs a contiguous [tokens, heads, D] device tensor")
     t, h, d = x.shape
-    L.check(L.lib().woq_rope(_ptr(x), L.torch_dtype_code(x.dtype), _ptr(pos), _ptr(cos), _ptr(sin), t, h, d,
-                             L.stream_ptr()))
+    if d % 2 != 0:
+        raise RuntimeError("QBits: rope head_dim must be even")
+    if not (pos.is_cuda and pos.device == x.device and pos.dtype == torch.int32 and pos.is_contiguous()
+            and tuple(pos.shape) == (t,)):
+        raise RuntimeError("QBits: rope takes a contiguous int32 device tensor pos [tokens]")
+    if not (cos.dim() == 2 and cos.device == x.device and _f32_dev(cos, (cos.shape[0], d // 2))
+            and sin.device == x.device and _f32_dev(sin, tuple(cos.shape)) and (cos.shape[0] > 0 or x.numel() == 0)):
+        raise RuntimeError("QBits: rope takes contiguous fp32 device tables cos, sin [max_pos, D/2]")
+    L.check(L.lib().woq_rope(_ptr(x), code, _ptr(pos), _ptr(cos), _ptr(sin), t, h, d, L.stream_ptr()))
     return x
 
 
 def silu_mul(gate, up, out=None):
+    """out = gate / (1 + exp(-gate)) * up, element by element; gate, up, out of one type (fp32 / fp16 / bf16) and numel
+    on the device. out may be gate or up."""
+    code = L.torch_dtype_code(gate.dtype)
     gate, up = gate.contiguous(), up.contiguous()
+    if not (_elem_dev(gate, gate) and up.dtype == gate.dtype and _elem_dev(up, gate, numel=gate.numel())):
+        raise RuntimeError("QBits: silu_mul takes device tensors gate, up of one dtype and numel")
     out = torch.empty_like(gate) if out is None else out
-    L.check(L.lib().woq_silu_mul(_ptr(gate), _ptr(up), L.torch_dtype_code(gate.dtype), gate.numel(), _ptr(out),
-                                 L.stream_ptr()))
+    if not (out.dtype == gate.dtype and _elem_dev(out, gate, numel=gate.numel())):
+        raise RuntimeError("QBits: silu_mul: out must be a contiguous device tensor of gate's dtype and numel")
+    L.check(L.lib().woq_silu_mul(_ptr(gate), _ptr(up), code, gate.numel(), _ptr(out), L.stream_ptr()))
     return out
 
 
 def gelu(x, approximate="tanh", out=None):
+    """GeLU element by element: approximate "tanh" (gelu_new) or "erf" / "none" (the exact form); x, out of one type
+    (fp32 / fp16 / bf16) and numel on the device."""
+    code = L.torch_dtype_code(x.dtype)
+    if approximate not in ("tanh", "erf", "none"):
+        raise RuntimeError("QBits: gelu: approximate is \"tanh\" or \"erf\" / \"none\", not %r" % (approximate,))
     x = x.contiguous()
+    if not _elem_dev(x, x):
+        raise RuntimeError("QBits: gelu takes a device tensor x")
     out = torch.empty_like(x) if out is None else out
-    L.check(L.lib().woq_gelu(_ptr(x), L.torch_dtype_code(x.dtype), x.numel(), 1 if approximate == "tanh" else 0,
-                             _ptr(out), L.stream_ptr()))
+    if not (out.dtype == x.dtype and _elem_dev(out, x, numel=x.numel())):
+        raise RuntimeError("QBits: gelu: out must be a contiguous device tensor of x's dtype and numel")
+    L.check(L.lib().woq_gelu(_ptr(x), code, x.numel(), 1 if approximate == "tanh" else 0, _ptr(out), L.stream_ptr()))
     return out
