@@ -11,10 +11,10 @@
 //   sym    amax = beta mx >= alpha (-mn) ? beta mx : alpha (-mn), s = amax / qmax (0 -> 1)
 //          t = w / s + V, c = clip(rne(t), -off, qmax), W~ = c s
 //
-// the package's RTN rule (rtn_kernel in woq_pack.hip, rtn_params / rtn_deq in woq_awq.hip) with V, alpha and beta put in,
-// in that rule's fp32 expression order, every step rounded on its own (no contraction): V = 0, alpha = beta = 1 gives
-// RTN's bits. The codes are clamped as floats before the conversion to int (the same values wherever RTN's int
-// arithmetic does not overflow; a tiny alpha makes w / s large).
+// the package's RTN rule (woq_rtn.h, whose rtn_range this file takes) with V, alpha and beta put in, in that rule's fp32
+// expression order, every step rounded on its own (no contraction): V = 0, alpha = beta = 1 gives RTN's bits. The
+// codes are clamped as floats before the conversion to int (the same values wherever RTN's int arithmetic does not
+// overflow; a tiny alpha makes w / s large).
 //
 // Gradients, rne straight-through, clip passing inside its range (bounds included), g = dL/dW~, q = c - z (asym) | c:
 //   an element whose code was not clipped   dV = g s (only its sign is used: sign(g), s > 0), ds += g (q - w / s)
@@ -42,6 +42,7 @@
 // divisions.
 #include "woq_device.h"
 #include "woq_launch.h"
+#include "woq_rtn.h"
 
 namespace woq {
 namespace {
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(SLICES == 1 ? AR_THREADS : SLICES * AR_SPLIT_COLS) 
     __syncthreads();  // red is reused for the partial sums
   }
 
-  const int qmax = (1 << (a.bits - 1)) - 1, levels = (1 << a.bits) - 1, off = 1 << (a.bits - 1);
+  const auto [qmax, levels, off] = rtn_range(a.bits);
   const float al = valid ? a.alpha[cell] : 1.f, be = valid ? a.beta[cell] : 1.f;
   float s, lo = 0.f, cmin, cmax;
   int zi = 0;
@@ -210,16 +211,15 @@ __global__ __launch_bounds__(SLICES == 1 ? AR_THREADS : SLICES * AR_SPLIT_COLS) 
   }
 }
 
-bool ar_bits_ok(int bits) { return bits == 2 || bits == 3 || bits == 4 || bits == 8; }
 bool ar_dtype_ok(int dt) { return dt == WOQ_F32 || dt == WOQ_BF16 || dt == WOQ_F16; }
 
 // the shape checks every entry point shares; fills K, N, group (as the kernel takes it) and the grid
 const char* ar_shape(ArArgs& a, dim3& grid, dim3& block, int& slices) {
   if (a.K < 1 || a.N < 1) return "bad shape";
-  if (!ar_bits_ok(a.bits)) return "bits must be 2, 3, 4 or 8";
-  if (a.group <= 0 || a.group > a.K) a.group = a.K;  // one group per column
-  const int n_groups = (a.K + a.group - 1) / a.group;
-  if (n_groups > 65535) return "more than 65535 groups";
+  if (!rtn_bits_ok(a.bits)) return "bits must be 2, 3, 4 or 8";
+  a.group = rtn_group(a.K, a.group);
+  const int n_groups = rtn_group_count(a.K, a.group);
+  if (!n_groups) return "more than 65535 groups";
   slices = a.group > AR_SPLIT_ROWS ? AR_SLICES : (a.group >= AR_MID_ROWS ? AR_MID_SLICES : 1);
   const int cols = slices > 1 ? AR_SPLIT_COLS : AR_THREADS;
   grid = dim3((unsigned)((a.N + cols - 1) / cols), (unsigned)n_groups);

@@ -2,9 +2,7 @@
 // objective): tests/awq_reference.py is their float64 statement, transformers/llm/quantization/awq.py the driver.
 //
 //   w  fp32 [K, N] row-major, row k = input feature k (Linear.weight.T)
-//   Q  the package's RTN at (bits, group, sym | asym): rtn_kernel's rule (woq_pack.hip), restated here as
-//      gptq_sweep_kernel restates it — parameters from the group's range, rintf, a zero scale becomes 1, the asym zero
-//      point clamped to 0 .. levels
+//   Q  the package's RTN at (bits, group, sym | asym): woq_rtn.h, the rule rtn_kernel (woq_pack.hip) writes blobs with
 //
 // 1. awq_scale_delta_kernel: D = diag(1 / s) Q(diag(s) W) - W for one candidate s [K] of the scale search. One thread per
 //    column and group, two passes over the group's rows (range, then codes); the loss tr(D^T H D) is the caller's, a GEMM.
@@ -38,39 +36,12 @@
 //    LDS; no AGPRs, no scratch, no spills; the delta kernel 24 VGPRs.
 #include "woq_device.h"
 #include "woq_launch.h"
+#include "woq_rtn.h"
 
 namespace woq {
 namespace {
 
 constexpr int AWQ_THREADS = 256;
-
-struct RtnRange {
-  int qmax, levels, off;
-};
-__device__ __forceinline__ RtnRange rtn_range(int bits) {
-  return {(1 << (bits - 1)) - 1, (1 << bits) - 1, 1 << (bits - 1)};
-}
-
-// the rule's parameters of a group whose values span [mn, mx] with largest magnitude amax
-__device__ __forceinline__ void rtn_params(const RtnRange& r, int asym, float mx, float mn, float amax, float& s, int& z) {
-  z = 0;
-  if (!asym) {
-    s = amax / (float)r.qmax;
-    if (s == 0.f) s = 1.f;
-  } else {
-    const float hi = fmaxf(mx, 0.f), lo = fminf(mn, 0.f);
-    s = (hi - lo) / (float)r.levels;
-    if (s == 0.f) s = 1.f;
-    z = max(0, min(r.levels, (int)rintf(-lo / s)));
-  }
-}
-
-// the rule's dequantised value of v under (s, z)
-__device__ __forceinline__ float rtn_deq(const RtnRange& r, int asym, float v, float s, int z) {
-  if (!asym) return (float)max(-r.off, min(r.qmax, (int)rintf(v / s))) * s;
-  const int c = max(0, min(r.levels, (int)rintf(v / s) + z));
-  return (float)(c - z) * s;
-}
 
 // ---- 1. the scale search's delta ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(AWQ_THREADS) void awq_scale_delta_kernel(const float* __restrict__ w,
@@ -275,8 +246,6 @@ void launch_clip(const ClipArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((awq_clip_kernel<GROUP, 0>), grid, dim3(AWQ_THREADS), 0, st, a);
 }
 
-bool awq_bits_ok(int bits) { return bits == 2 || bits == 3 || bits == 4 || bits == 8; }
-
 }  // namespace
 }  // namespace woq
 
@@ -285,10 +254,10 @@ extern "C" int woq_awq_scale_delta(const float* w_dev, const float* s_dev, int K
   WOQ_TRY
   WOQ_CHECK(w_dev && s_dev && d_out_dev, "QBits: awq_scale_delta: null tensor");
   WOQ_CHECK(K >= 1 && N >= 1, "QBits: awq_scale_delta: bad shape");
-  WOQ_CHECK(woq::awq_bits_ok(bits), "QBits: awq_scale_delta: bits must be 2, 3, 4 or 8");
-  if (group <= 0 || group > K) group = K;  // one group per column
-  const int n_groups = (K + group - 1) / group;
-  WOQ_CHECK(n_groups <= 65535, "QBits: awq_scale_delta: more than 65535 groups");
+  WOQ_CHECK(woq::rtn_bits_ok(bits), "QBits: awq_scale_delta: bits must be 2, 3, 4 or 8");
+  group = woq::rtn_group(K, group);
+  const int n_groups = woq::rtn_group_count(K, group);
+  WOQ_CHECK(n_groups, "QBits: awq_scale_delta: more than 65535 groups");
   const dim3 grid((unsigned)((N + woq::AWQ_THREADS - 1) / woq::AWQ_THREADS), (unsigned)n_groups);
   hipLaunchKernelGGL(woq::awq_scale_delta_kernel, grid, dim3(woq::AWQ_THREADS), 0, (hipStream_t)stream, w_dev, s_dev, K,
                      N, group, bits, asym ? 1 : 0, d_out_dev);
@@ -302,12 +271,13 @@ extern "C" int woq_awq_clip_search(const float* w_dev, const float* h_dev, int l
   WOQ_TRY
   WOQ_CHECK(w_dev && h_dev && best_dev && losses_dev && w_out_dev, "QBits: awq_clip_search: null tensor");
   WOQ_CHECK(K >= 1 && N >= 1 && ldh >= K, "QBits: awq_clip_search: bad shape (h is [K, K] with a row stride >= K)");
-  WOQ_CHECK(woq::awq_bits_ok(bits), "QBits: awq_clip_search: bits must be 2, 3, 4 or 8");
+  WOQ_CHECK(woq::rtn_bits_ok(bits), "QBits: awq_clip_search: bits must be 2, 3, 4 or 8");
   WOQ_CHECK(group == 32 || group == 64 || group == 128,
             "QBits: awq_clip_search: group must be 32, 64 or 128 (the Gram block of a group lives in LDS)");
   WOQ_CHECK(n_grid >= 1 && n_cand >= 1 && n_cand <= n_grid,
             "QBits: awq_clip_search: needs 1 <= n_cand <= n_grid (every candidate keeps a positive range)");
-  WOQ_CHECK((K + group - 1) / group <= 65535, "QBits: awq_clip_search: more than 65535 groups");
+  // group stays as given: with K < group the one short group still runs in its own kernel form
+  WOQ_CHECK(woq::rtn_group_count(K, group), "QBits: awq_clip_search: more than 65535 groups");
   const woq::ClipArgs a = {w_dev, h_dev, K, N, ldh, bits, asym ? 1 : 0, n_grid, n_cand, best_dev, losses_dev, w_out_dev};
   if (group == 128)
     woq::launch_clip<128>(a, (hipStream_t)stream);

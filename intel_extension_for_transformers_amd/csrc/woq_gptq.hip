@@ -6,8 +6,8 @@
 //
 // For every column n on its own, j ascending over c0 <= j < c0 + B:
 //   gid = col_group ? col_group[j] : j / group
-//   at a group start (j % group == 0, parameters not given): (s, z) = the RTN parameters (rtn_kernel's rule,
-//     woq_pack.hip; tests/quant_reference.py) of the CURRENT w[j .. min(j + group, K) - 1][n] — rows of this block as
+//   at a group start (j % group == 0, parameters not given): (s, z) = the RTN parameters (woq_rtn.h, rtn_kernel's rule;
+//     tests/quant_reference.py) of the CURRENT w[j .. min(j + group, K) - 1][n] — rows of this block as
 //     updated so far, rows beyond it as they stand in memory — stored to scale[gid][n], zp[gid][n]
 //   code = that rule's code of w[j][n], q[j][n] = code (the signed domain woq_repack_quantized_weight takes)
 //   d = its dequantised value (one fp32 product), e = (w[j][n] - d) / u[j][j] (an fp32 subtraction and a correctly
@@ -32,6 +32,7 @@
 // multiples of 32 (or one group per column) when it has to compute parameters, which is what the package's blob takes.
 #include "woq_device.h"
 #include "woq_launch.h"
+#include "woq_rtn.h"
 
 namespace woq {
 namespace {
@@ -123,7 +124,7 @@ __device__ __forceinline__ void gptq_steps(float (&wr)[GPTQ_BLOCK], const float 
                                            GptqState& st, bool valid, int n) {
   if constexpr (J < GPTQ_BLOCK) {
     if (J >= g.B) return;  // uniform: a short last block ends here
-    const int qmax = (1 << (g.bits - 1)) - 1, levels = (1 << g.bits) - 1, off = 1 << (g.bits - 1);
+    const RtnRange r = rtn_range(g.bits);
     const size_t N = (size_t)g.N;
     const int ja = g.c0 + J;
     const int gid = g.col_group ? g.col_group[ja] : ja / g.group;
@@ -141,25 +142,16 @@ __device__ __forceinline__ void gptq_steps(float (&wr)[GPTQ_BLOCK], const float 
           mn = fminf(mn, v);
           amax = fmaxf(amax, fabsf(v));
         }
-        st.z = 0;
-        if (!g.asym) {
-          st.s = amax / (float)qmax;
-          if (st.s == 0.f) st.s = 1.f;
-        } else {
-          const float hi = fmaxf(mx, 0.f), lo = fminf(mn, 0.f);
-          st.s = (hi - lo) / (float)levels;
-          if (st.s == 0.f) st.s = 1.f;
-          st.z = max(0, min(levels, (int)rintf(-lo / st.s)));
-        }
+        rtn_params(r, g.asym, mx, mn, amax, st.s, st.z);
         if (valid) {
           g.scale[(size_t)gid * N + n] = st.s;
-          if (g.asym) g.zp[(size_t)gid * N + n] = (int8_t)(st.z - off);
+          if (g.asym) g.zp[(size_t)gid * N + n] = (int8_t)(st.z - r.off);
         }
       }
     }
     if (!computed && (J == 0 || (g.params_given && gid != st.gid_prev))) {
       st.s = valid ? g.scale[(size_t)gid * N + n] : 1.f;
-      st.z = (g.asym && valid) ? (int)g.zp[(size_t)gid * N + n] + off : 0;
+      st.z = (g.asym && valid) ? (int)g.zp[(size_t)gid * N + n] + r.off : 0;
     }
     st.gid_prev = gid;
 
@@ -174,14 +166,7 @@ __device__ __forceinline__ void gptq_steps(float (&wr)[GPTQ_BLOCK], const float 
       // no contraction here: e is taken against the value that is stored, the product rounded first, then the
       // subtraction (contracted, v - qi * s would become one fma against the unrounded product)
 #pragma clang fp contract(off)
-      if (!g.asym) {
-        qi = max(-off, min(qmax, (int)rintf(v / s)));
-        d = (float)qi * s;
-      } else {
-        const int c = max(0, min(levels, (int)rintf(v / s) + st.z));
-        d = (float)(c - st.z) * s;
-        qi = c - off;
-      }
+      rtn_quant(r, g.asym, v, s, st.z, qi, d);
       e = (v - d) / us[J][J];
     }
     gptq_update<C0>(wr, us[J], e, ua, ub);
@@ -223,9 +208,9 @@ extern "C" int woq_gptq_sweep(float* w_dev, const float* u_dev, int K, int N, in
   WOQ_CHECK(K >= 1 && N >= 1, "QBits: gptq_sweep: bad shape");
   WOQ_CHECK(B >= 1 && B <= woq::GPTQ_BLOCK && c0 >= 0 && c0 <= K - B,
             "QBits: gptq_sweep: the block must be 1 .. 128 rows inside the weight");
-  WOQ_CHECK(bits == 2 || bits == 3 || bits == 4 || bits == 8, "QBits: gptq_sweep: bits must be 2, 3, 4 or 8");
+  WOQ_CHECK(woq::rtn_bits_ok(bits), "QBits: gptq_sweep: bits must be 2, 3, 4 or 8");
   WOQ_CHECK(!asym || zp_dev, "QBits: gptq_sweep: asym needs a zero-point tensor");
-  if (group <= 0 || group > K) group = K;  // one group per column
+  group = woq::rtn_group(K, group);
   WOQ_CHECK(params_given || ((c0 % 32) == 0 && ((group % 32) == 0 || group == K)),
             "QBits: gptq_sweep: computing parameters needs c0 and the group size to be multiples of 32 (or group -1)");
   const woq::GptqArgs g = {w_dev, u_dev, K, N, c0, B, group, bits, asym ? 1 : 0, params_given ? 1 : 0, col_group_dev,

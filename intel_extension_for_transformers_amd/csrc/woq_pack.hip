@@ -8,6 +8,7 @@
 // All HBM-bound byte shuffles; none of them is on the per-token path.
 #include "woq_device.h"
 #include "woq_launch.h"
+#include "woq_rtn.h"
 
 namespace woq {
 
@@ -186,15 +187,12 @@ __global__ void extract_kernel(const uint8_t* __restrict__ blob, woq_blob_header
     ((int8_t*)out)[idx] = (int8_t)(uz - 8);
 }
 
-// RTN: one thread per (group, column). int4 "clip" range (bits = 4) or int8 (bits = 8). Rounding rule documented in DESIGN.md
-// (parity unpinned: BesTLA's quantiser is not in /root/reference). rintf = round-half-even. sym: s = max|w| / qmax;
-// asym: s = (max(mx, 0) - min(mn, 0)) / levels, z = clip(rne(-min(mn, 0) / s), 0, levels) — the range always holds
-// zero, so a group on one side of zero is within half a step like any other (tests/quant_reference.py).
+// RTN: one thread per (group, column), the rule of woq_rtn.h at bits = 2, 3, 4 ("clip" ranges) or 8 (parity unpinned:
+// BesTLA's quantiser is not in the reference tree).
 __global__ void rtn_kernel(const float* __restrict__ w, int transpose, int K, int N, int group, int n_groups,
                            int asym, int bits, int8_t* __restrict__ q, float* __restrict__ scales,
                            int8_t* __restrict__ zp) {
-  // bits = 4: 7 / 15 / 8; 8: 127 / 255 / 128; 3: 3 / 7 / 4; 2: 1 / 3 / 2
-  const int qmax = (1 << (bits - 1)) - 1, levels = (1 << bits) - 1, off = 1 << (bits - 1);
+  const RtnRange r = rtn_range(bits);
   size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)n_groups * N) return;
   int g = (int)(idx / (size_t)N), n = (int)(idx % (size_t)N);
@@ -207,30 +205,13 @@ __global__ void rtn_kernel(const float* __restrict__ w, int transpose, int K, in
     amax = fmaxf(amax, fabsf(v));
   }
   float s;
-  int z = 0;
-  if (!asym) {
-    s = amax / (float)qmax;
-    if (s == 0.f) s = 1.f;
-  } else {
-    const float hi = fmaxf(mx, 0.f), lo = fminf(mn, 0.f);  // zero inside the range: a one-sided group keeps its codes
-    s = (hi - lo) / (float)levels;
-    if (s == 0.f) s = 1.f;
-    z = (int)rintf(-lo / s);
-    z = max(0, min(levels, z));
-  }
+  int z;
+  rtn_params(r, asym, mx, mn, amax, s, z);
   scales[idx] = s;
-  if (asym) zp[idx] = (int8_t)(z - off);
+  if (asym) zp[idx] = (int8_t)(z - r.off);
   for (int k = k0; k < k1; ++k) {
     float v = transpose ? w[(size_t)n * K + k] : w[(size_t)k * N + n];
-    int qi;
-    if (!asym) {
-      qi = (int)rintf(v / s);
-      qi = max(-off, min(qmax, qi));
-    } else {
-      qi = (int)rintf(v / s) + z;
-      qi = max(0, min(levels, qi)) - off;
-    }
-    q[(size_t)k * N + n] = (int8_t)qi;
+    q[(size_t)k * N + n] = (int8_t)rtn_code(r, asym, v, s, z);
   }
 }
 

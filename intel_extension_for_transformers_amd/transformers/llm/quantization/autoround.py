@@ -23,9 +23,8 @@ import logging
 import torch
 
 from .... import qbits
-from .gptq import _BITS, _Stop, _block_linears, _data_source, _decoder_blocks, _is_conv1d, _run_block
-from .gptq import calibration_batches
-from .nn.modules import QuantizedLinearQBits
+from .calibration import (BITS, block_linears, calibration_batches, capture_block_inputs, check_request,
+                          decoder_blocks, fp32_matmul, install_quantized, next_inputs, run_block, weight_kn)
 
 logger = logging.getLogger(__name__)
 
@@ -33,26 +32,9 @@ SEED = 42  # of the minibatch draw
 DEFAULT_BATCH = 8
 
 
-def _check_options(model, config):
-    for opt in ("use_double_quant", "layer_wise", "quant_lm_head"):
-        if getattr(config, opt, False):
-            raise NotImplementedError("AutoRound on the MI355X path does not implement %s" % opt)
-    if config.weight_dtype not in _BITS:
-        raise NotImplementedError("AutoRound quantises to the integer weight types (int4_clip, int8), not "
-                                  "weight_dtype=%s" % config.weight_dtype)
-    _decoder_blocks(model)
-    try:
-        _data_source(config)
-    except NotImplementedError:
-        raise NotImplementedError(
-            "AutoRoundConfig calibration is not part of the MI355X hot path without calibration data (dataset=%r is "
-            "not downloaded): pass calib_dataloader= (an iterable of input_ids tensors) or dataset=[texts] with "
-            "tokenizer=" % (getattr(config, "dataset", None),)) from None
-
-
 def validate_autoround_request(model, config):
     """Everything about a request that can be refused without touching a device."""
-    _check_options(model, config)
+    check_request(model, config, "AutoRound", ("use_double_quant", "layer_wise", "quant_lm_head"), blocks_first=True)
 
 
 def learning_rates(config):
@@ -69,24 +51,12 @@ def schedule(lr, t, iters):
     return lr * (1.0 - t / iters)
 
 
-class _Batched:
-    """the config as `calibration_batches` reads it, with AutoRound's batch size"""
-
-    def __init__(self, config):
-        self._config = config
-        self.batch_size = int(getattr(config, "batch_size", DEFAULT_BATCH) or DEFAULT_BATCH)
-
-    def __getattr__(self, name):
-        return getattr(self._config, name)
-
-
 class _Quantiser:
     """the trainables of one linear and what the two launches need"""
 
     def __init__(self, module, group, bits, asym, dtype):
-        w = module.weight.data if _is_conv1d(module) else module.weight.data.t()
-        self.w = w.to(torch.float32).clone(memory_format=torch.contiguous_format)
-        k, n = self.w.shape
+        self.w = w = weight_kn(module)
+        k, n = w.shape
         g = k if group <= 0 or group > k else group
         self.group, self.bits, self.asym, self.dtype = group, bits, asym, dtype
         # V is the tensor autograd sees (FakeQuant needs an input that requires grad); it never receives one
@@ -126,11 +96,6 @@ def _wrap(module, q):
     module.forward = forward
 
 
-def _next_inputs(inputs, outs):
-    return [((y,) + tuple(args[1:]), kwargs) if args else ((), dict(kwargs, hidden_states=y))
-            for (args, kwargs), y in zip(inputs, outs)]
-
-
 def _samples(unit):
     args, kwargs = unit
     x = args[0] if args else kwargs["hidden_states"]
@@ -159,7 +124,7 @@ def _train_block(block, quantisers, inputs, targets, iters, lr, minmax_lr, batch
                 total = sum(targets[i].numel() for i in picked)
                 loss = 0.0
                 for i in picked:
-                    y = _run_block(block, [inputs[i]])[0]
+                    y = run_block(block, [inputs[i]])[0]
                     loss = loss + (y.float() - targets[i].float()).square().sum()
                 loss = loss / total
                 value = float(loss.detach())
@@ -186,49 +151,26 @@ def autoround_quantize_model(model, config, device="cuda"):
     blocks quantised so far (two input lists), the targets still from the fp stream. `iters=0` is RTN through this path.
     lm_head and whatever else `llm_int8_skip_modules` names stay. model._autoround_log: (rtn_loss, best_loss, best_iter)
     per block."""
-    _check_options(model, config)
-    batched = _Batched(config)
-    batches = calibration_batches(batched)
-    path, blocks = _decoder_blocks(model)
+    validate_autoround_request(model, config)
+    batch_size = int(getattr(config, "batch_size", DEFAULT_BATCH) or DEFAULT_BATCH)
+    batches = calibration_batches(config, batch_size)
+    path, blocks = decoder_blocks(model)
     skip = list(getattr(config, "llm_int8_skip_modules", None) or [])
-    bits = _BITS[config.weight_dtype]
+    bits = BITS[config.weight_dtype]
     asym = not bool(config.sym)
     iters, lr, minmax_lr = learning_rates(config)
     fp_stream_only = bool(getattr(config, "disable_quanted_input", True))
     model.to(device)
     model.eval()
-
-    inputs = []
-
-    def grab(_module, args, kwargs):
-        inputs.append((args, kwargs))
-        raise _Stop()
-
-    handle = blocks[0].register_forward_pre_hook(grab, with_kwargs=True)
-    use_cache = getattr(model.config, "use_cache", None) if hasattr(model, "config") else None
-    try:
-        if use_cache is not None:
-            model.config.use_cache = False
-        for ids in batches:
-            try:
-                model(input_ids=ids.to(device))
-            except _Stop:
-                pass
-    finally:
-        handle.remove()
-        if use_cache is not None:
-            model.config.use_cache = use_cache
-
+    inputs = capture_block_inputs(model, blocks, batches, device)
     gen = torch.Generator().manual_seed(SEED)
     q_inputs = inputs  # what the block trains on; the fp stream itself unless disable_quanted_input=False
     model._autoround_log = []
-    tf32 = torch.backends.cuda.matmul.allow_tf32
-    torch.backends.cuda.matmul.allow_tf32 = False
-    try:
+    with fp32_matmul():
         for li, block in enumerate(blocks):
             where = "%s.%d" % (path, li)
-            linears = _block_linears(block, where, skip)
-            targets = _run_block(block, inputs)
+            linears = block_linears(block, where, skip)
+            targets = run_block(block, inputs)
             dtype = targets[0].dtype if targets[0].dtype in (torch.float16, torch.bfloat16) else torch.float32
             quantisers = [_Quantiser(m, config.group_size, bits, asym, dtype) for _, m in linears]
             entry = (None, None, -1)
@@ -237,7 +179,7 @@ def autoround_quantize_model(model, config, device="cuda"):
                     _wrap(m, q)
                 try:
                     rtn_loss, best_loss, best_iter, best = _train_block(block, quantisers, q_inputs, targets, iters, lr,
-                                                                        minmax_lr, batched.batch_size, gen)
+                                                                        minmax_lr, batch_size, gen)
                 finally:
                     for _, m in linears:
                         del m.forward
@@ -249,27 +191,11 @@ def autoround_quantize_model(model, config, device="cuda"):
 
             for (name, m), q, (v, alpha, beta) in zip(linears, quantisers, best):
                 codes, scales, zeros = qbits.autoround_codes(q.w, v, alpha, beta, config.group_size, bits, asym)
-                k, n = codes.shape
-                new = QuantizedLinearQBits(k, n, m.bias is not None, compute_dtype=config.compute_dtype,
-                                           compress_statistics=False, weight_dtype=config.weight_dtype, bits=config.bits,
-                                           scale_dtype=config.scale_dtype, blocksize=config.group_size,
-                                           scheme=config.scheme, device=device)
-                if bits == 4:  # set_weights_bias takes 4-bit values unsigned, as the checkpoint formats store them
-                    codes = codes + 8
-                    zeros = zeros + 8 if zeros is not None else None
-                new.set_weights_bias(codes, scales, zeros, torch.empty(0, dtype=torch.int32), config,
-                                     m.bias.data if m.bias is not None else None)
-                new.source_cls = type(m)
-                new.requires_grad_(False)
-                parent_name, _, leaf = name.rpartition(".")
-                parent = block.get_submodule(parent_name) if parent_name else block
-                parent._modules[leaf] = new
+                install_quantized(block, name, m, config, device, codes=codes, scales=scales, zeros=zeros)
             del quantisers, best
             if not fp_stream_only:
-                q_inputs = _next_inputs(q_inputs, _run_block(block, q_inputs))
-            inputs = _next_inputs(inputs, targets)
+                q_inputs = next_inputs(q_inputs, run_block(block, q_inputs))
+            inputs = next_inputs(inputs, targets)
             if fp_stream_only:
                 q_inputs = inputs
-    finally:
-        torch.backends.cuda.matmul.allow_tf32 = tf32
     return model

@@ -23,9 +23,9 @@ import logging
 import torch
 
 from .... import qbits
-from .gptq import _BITS, _Stop, _block_linears, _data_source, _decoder_blocks, _is_conv1d, _run_block
-from .gptq import calibration_batches
-from .nn.modules import QuantizedLinearQBits
+from .calibration import (BITS, block_linears, calibration_batches, capture_block_inputs, check_request,
+                          collect_input_stats, decoder_blocks, fp32_matmul, install_quantized, next_inputs, run_block,
+                          weight_kn)
 
 logger = logging.getLogger(__name__)
 
@@ -51,21 +51,9 @@ def _model_type(model):
     return getattr(getattr(model, "config", None), "model_type", None) or type(model).__name__
 
 
-def _check_options(model, config):
-    for opt in ("use_double_quant", "layer_wise"):
-        if getattr(config, opt, False):
-            raise NotImplementedError("AWQ on the MI355X path does not implement %s" % opt)
-    if config.weight_dtype not in _BITS:
-        raise NotImplementedError("AWQ quantises to the integer weight types (int4_clip, int8), not weight_dtype=%s"
-                                  % config.weight_dtype)
-    try:
-        _data_source(config)
-    except NotImplementedError:
-        raise NotImplementedError(
-            "AwqConfig calibration is not part of the MI355X hot path without calibration data (dataset=%r is not "
-            "downloaded): pass calib_dataloader= (an iterable of input_ids tensors) or dataset=[texts] with tokenizer="
-            % (getattr(config, "dataset", None),)) from None
-    _decoder_blocks(model)
+def validate_awq_request(model, config):
+    """Everything about a request that can be refused without touching a device."""
+    check_request(model, config, "AWQ", ("use_double_quant", "layer_wise"))
     if config.auto_scale and _model_type(model) not in SCALE_MODEL_TYPES:
         raise NotImplementedError("AWQ auto_scale folds scales into Llama-class blocks (model_type %s), not model type "
                                   "%s: use auto_scale=False" % (" / ".join(SCALE_MODEL_TYPES), _model_type(model)))
@@ -74,21 +62,10 @@ def _check_options(model, config):
                                   "not group_size=%s: use auto_clip=False" % config.group_size)
 
 
-def validate_awq_request(model, config):
-    """Everything about a request that can be refused without touching a device."""
-    _check_options(model, config)
-
-
 def normalised_scale(a, i, n_grid=N_GRID):
     """candidate i of the scale search from a = mean |x| [K]: clamp(a^(i / n_grid), 1e-4) / sqrt(max min)"""
     s = a.pow(i / n_grid).clamp_(min=1e-4)
     return s / (s.max() * s.min()).sqrt()
-
-
-def _kn(m):
-    """the linear's weight as fp32 [K, N], a fresh contiguous tensor"""
-    w = m.weight.data if _is_conv1d(m) else m.weight.data.t()
-    return w.to(torch.float32).clone(memory_format=torch.contiguous_format)
 
 
 def search_scale(weights_kn, h, a, group, bits, asym):
@@ -161,66 +138,25 @@ def awq_quantize_model(model, config, device="cuda"):
     samples; scales are searched and folded in, clamps searched and applied, every linear replaced by its RTN blob; the
     block runs again, quantised, to produce the next block's inputs. lm_head and whatever else `llm_int8_skip_modules`
     names stay."""
-    _check_options(model, config)
+    validate_awq_request(model, config)
     batches = calibration_batches(config)
-    path, blocks = _decoder_blocks(model)
+    path, blocks = decoder_blocks(model)
     skip = list(getattr(config, "llm_int8_skip_modules", None) or [])
-    bits = _BITS[config.weight_dtype]
+    bits = BITS[config.weight_dtype]
     asym = not bool(config.sym)
     group = config.group_size
     llama = _model_type(model) in SCALE_MODEL_TYPES
     model.to(device)
     model.eval()
-
-    inputs = []
-
-    def grab(_module, args, kwargs):
-        inputs.append((args, kwargs))
-        raise _Stop()
-
-    handle = blocks[0].register_forward_pre_hook(grab, with_kwargs=True)
-    use_cache = getattr(model.config, "use_cache", None) if hasattr(model, "config") else None
-    try:
-        if use_cache is not None:
-            model.config.use_cache = False
-        for ids in batches:
-            try:
-                model(input_ids=ids.to(device))
-            except _Stop:
-                pass
-    finally:
-        handle.remove()
-        if use_cache is not None:
-            model.config.use_cache = use_cache
-
-    tf32 = torch.backends.cuda.matmul.allow_tf32
-    torch.backends.cuda.matmul.allow_tf32 = False  # H += X^T X and the loss H @ D are fp32 GEMMs
-    try:
+    inputs = capture_block_inputs(model, blocks, batches, device)
+    with fp32_matmul():  # H += X^T X and the loss H @ D are fp32 GEMMs
         for li, block in enumerate(blocks):
             where = "%s.%d" % (path, li)
-            linears = _block_linears(block, where, skip)
-            source = {name: (_SAME_INPUT.get(name, name) if llama else name) for name, _ in linears}
+            linears = block_linears(block, where, skip)
             have = {name for name, _ in linears}
+            source = {name: (_SAME_INPUT.get(name, name) if llama else name) for name in have}
             source = {name: (src if src in have else name) for name, src in source.items()}
-            gram, asum, count, hooks = {}, {}, {}, []
-            for name, m in linears:
-                if source[name] != name:
-                    continue
-                kdim = m.weight.shape[0] if _is_conv1d(m) else m.in_features
-                gram[name] = torch.zeros(kdim, kdim, dtype=torch.float32, device=device)
-                asum[name] = torch.zeros(kdim, dtype=torch.float32, device=device)
-                count[name] = 0
-
-                def accumulate(_m, args, _out, name=name):
-                    x = args[0].reshape(-1, args[0].shape[-1]).float()
-                    gram[name].addmm_(x.t(), x)
-                    asum[name].add_(x.abs().sum(0))
-                    count[name] += x.shape[0]
-
-                hooks.append(m.register_forward_hook(accumulate))
-            _run_block(block, inputs)
-            for hk in hooks:
-                hk.remove()
+            gram, asum, count = collect_input_stats(block, linears, inputs, source, abs_sum=True)
             for name in gram:
                 gram[name].div_(max(1, count[name]))
                 asum[name].div_(max(1, count[name]))
@@ -232,8 +168,8 @@ def awq_quantize_model(model, config, device="cuda"):
                 for gi in _scale_groups(block, linears, where):
                     names = _GROUPS[gi][0]
                     src = source[names[0]]
-                    best, s, losses = search_scale([_kn(block.get_submodule(n)) for n in names], gram[src], asum[src],
-                                                   group, bits, asym)
+                    best, s, losses = search_scale([weight_kn(block.get_submodule(n)) for n in names], gram[src],
+                                                   asum[src], group, bits, asym)
                     logger.info("AWQ %s %s: scale exponent %.2f, loss %.6g (RTN %.6g)", where, "/".join(names),
                                 best / N_GRID, losses[best], losses[0])
                     scales[gi] = s
@@ -242,7 +178,7 @@ def awq_quantize_model(model, config, device="cuda"):
                 apply_scales(block, scales)
 
             for name, m in linears:
-                w_kn = _kn(m)
+                w_kn = weight_kn(m)
                 if config.auto_clip and name.rpartition(".")[2] not in _NO_CLIP:
                     h = gram[source[name]]
                     if name in in_scale:
@@ -253,21 +189,7 @@ def awq_quantize_model(model, config, device="cuda"):
                     logger.info("AWQ %s.%s: clip loss %.6g (RTN %.6g), %.0f%% of the cells clipped", where, name,
                                 float(picked), float(losses[0].sum(dtype=torch.float64)),
                                 100.0 * float((best > 0).float().mean()))
-                k, n = w_kn.shape
-                new = QuantizedLinearQBits(k, n, m.bias is not None, compute_dtype=config.compute_dtype,
-                                           compress_statistics=False, weight_dtype=config.weight_dtype,
-                                           bits=config.bits, scale_dtype=config.scale_dtype, blocksize=config.group_size,
-                                           scheme=config.scheme, device=device)
-                new.set_fp_weights_bias(w_kn.t(), m.bias.data if m.bias is not None else None)
-                new.source_cls = type(m)
-                new.requires_grad_(False)
-                parent_name, _, leaf = name.rpartition(".")
-                parent = block.get_submodule(parent_name) if parent_name else block
-                parent._modules[leaf] = new
+                install_quantized(block, name, m, config, device, fp_weight_kn=w_kn)
             del gram, asum
-            outs = _run_block(block, inputs)
-            inputs = [((y,) + tuple(args[1:]), kwargs) if args else ((), dict(kwargs, hidden_states=y))
-                      for (args, kwargs), y in zip(inputs, outs)]
-    finally:
-        torch.backends.cuda.matmul.allow_tf32 = tf32
+            inputs = next_inputs(inputs, run_block(block, inputs))
     return model

@@ -14,6 +14,7 @@ import logging
 
 import torch
 
+from .calibration import is_conv1d
 from .nn.modules import QuantizedLinearQBits
 
 logger = logging.getLogger(__name__)
@@ -142,10 +143,6 @@ def _to_i32(t64):
 
 
 # ---- a15: module surgery --------------------------------------------------------------------------------------------
-def _is_conv1d(m):
-    return type(m).__name__ == "Conv1D" and hasattr(m, "nf")  # HF GPT-2 projection: weight already [K, N] (F10)
-
-
 def _packed_checkpoint_linear(m):
     """A linear that already carries optimum-format tensors (INC WeightOnlyLinear / AutoGPTQ QuantLinear shells)."""
     return all(hasattr(m, a) for a in ("qweight", "scales")) and not isinstance(m, QuantizedLinearQBits)
@@ -176,9 +173,9 @@ def _replace_linear(model, modules_to_not_convert, current_key_name, quantizatio
         key = (current_key_name or []) + [name]
         dotted = ".".join(key)
         eligible = (isinstance(module, torch.nn.Linear) and not isinstance(module, QuantizedLinearQBits)) \
-            or _is_conv1d(module) or _packed_checkpoint_linear(module)
+            or is_conv1d(module) or _packed_checkpoint_linear(module)
         if eligible and not any(s in dotted for s in modules_to_not_convert):
-            if _is_conv1d(module):
+            if is_conv1d(module):
                 in_features, out_features = module.weight.shape[0], module.nf
             elif hasattr(module, "in_features"):
                 in_features, out_features = module.in_features, module.out_features
@@ -204,7 +201,7 @@ def _replace_linear(model, modules_to_not_convert, current_key_name, quantizatio
                                          g_idx if g_idx is not None else torch.empty(0, dtype=torch.int32), cfg, bias)
                 else:
                     w = module.weight.data
-                    w = w.t() if _is_conv1d(module) else w  # -> nn.Linear layout [N, K]
+                    w = w.t() if is_conv1d(module) else w  # -> nn.Linear layout [N, K]
                     new.set_fp_weights_bias(w.to(device), bias)
             new.source_cls = type(module)
             new.requires_grad_(False)
@@ -218,16 +215,17 @@ def _replace_linear(model, modules_to_not_convert, current_key_name, quantizatio
 
 def convert_to_quantized_model(model, config, device="cuda"):
     """reference utils.py:531-702 for the weight-only configs. RTN: quantise every eligible linear on the device.
-    GPTQ on an fp model: calibrate on the device (gptq.py gptq_quantize_model: Hessians from `config.calib_dataloader`
-    or `config.dataset=[texts]` + tokenizer, the sweep in csrc/woq_gptq.hip); the decoder blocks' linears are
-    quantised, lm_head and anything outside the blocks stays as it is. AWQ on an fp model: calibrate on the device the
-    same way (awq.py awq_quantize_model: the scale and clip searches of csrc/woq_awq.hip; scales are folded into the
-    norms / preceding projections of Llama-class blocks, the result is a plain RTN blob). AutoRound on an fp model:
-    trained on the device, block by block (autoround.py autoround_quantize_model: SignSGD on a rounding offset and two
-    range factors per group, the quantiser's forward and its backward + update in csrc/woq_autoround.hip; the result is
-    a plain blob). TEQ is a trained search that the reference runs inside neural_compressor (external); that config
-    (like GPTQ / AWQ / AutoRound) is accepted for PRE-QUANTISED checkpoints (optimum-format tensors already on the
-    modules), and raises for an fp model instead of silently falling back to RTN."""
+    GPTQ on an fp model: calibrate on the device (gptq.py gptq_quantize_model, on calibration.py's walk down the
+    decoder blocks like the two methods after it: Hessians from `config.calib_dataloader` or `config.dataset=[texts]`
+    + tokenizer, the sweep in csrc/woq_gptq.hip); the decoder blocks' linears are quantised, lm_head and anything
+    outside the blocks stays as it is. AWQ on an fp model: calibrate on the device the same way (awq.py
+    awq_quantize_model: the scale and clip searches of csrc/woq_awq.hip; scales are folded into the norms / preceding
+    projections of Llama-class blocks, the result is a plain RTN blob). AutoRound on an fp model: trained on the device,
+    block by block (autoround.py autoround_quantize_model: SignSGD on a rounding offset and two range factors per
+    group, the quantiser's forward and its backward + update in csrc/woq_autoround.hip; the result is a plain blob).
+    TEQ is a trained search that the reference runs inside neural_compressor (external); that config (like GPTQ / AWQ /
+    AutoRound) is accepted for PRE-QUANTISED checkpoints (optimum-format tensors already on the modules), and raises
+    for an fp model instead of silently falling back to RTN."""
     method = getattr(config.quant_method, "value", config.quant_method)
     has_packed = any(_packed_checkpoint_linear(m) for m in model.modules())
     if method in ("gptq", "awq", "autoround") and not has_packed:

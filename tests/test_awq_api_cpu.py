@@ -92,7 +92,7 @@ def test_calibration_data_is_kept_by_reference_and_not_serialised():
     assert "calib_dataloader" not in c.to_json_string(use_diff=False)
     assert AwqConfig().calib_dataloader is None and AwqConfig.from_dict(c.to_dict()).calib_dataloader is None
     assert c.sym is False and _cfg(zero_point=False).scheme == "sym"
-    from intel_extension_for_transformers_amd.transformers.llm.quantization.gptq import calibration_batches
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.calibration import calibration_batches
 
     got = calibration_batches(_cfg(calib_dataloader=[torch.arange(16).reshape(2, 8)], n_samples=3, seq_len=5))
     assert [tuple(b.shape) for b in got] == [(1, 5), (1, 5)]  # AwqConfig has no batch_size: one row a batch

@@ -109,7 +109,8 @@ def _tiny(kind):
 @pytest.mark.parametrize("kind", ["mha", "gqa", "qwen2"])
 def test_scale_folding_preserves_the_function(kind):
     from intel_extension_for_transformers_amd.transformers.llm.quantization import awq
-    from intel_extension_for_transformers_amd.transformers.llm.quantization.gptq import _block_linears
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.calibration import (
+        block_linears as _block_linears)
 
     model = _tiny(kind)
     ids = torch.randint(0, 256, (2, 24), generator=torch.Generator().manual_seed(2))

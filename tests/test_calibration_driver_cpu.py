@@ -1,0 +1,164 @@
+"""What GPTQ, AWQ and AutoRound calibration share (transformers/llm/quantization/calibration.py), on the CPU: the stream
+of block inputs against the model's own hidden states, the hooked input statistics against float64, the batch-size
+override, and that the three method files no longer import from one another. Tiny random-init models as in
+tests/test_gpu_gptq_model.py, with three layers so that there is a middle block."""
+import ast
+import functools
+import os
+import types
+
+import pytest
+import torch
+
+from intel_extension_for_transformers_amd.transformers.llm.quantization import calibration as C
+
+TOKENS, K = 256, 128  # 2 batches x 4 rows x 32 ids; the hidden size
+# linears of a Llama block that see the same tensor as another (awq.py's _SAME_INPUT)
+SAME_INPUT = {"self_attn.k_proj": "self_attn.q_proj", "self_attn.v_proj": "self_attn.q_proj",
+              "mlp.up_proj": "mlp.gate_proj"}
+
+
+def _llama():
+    from transformers import LlamaConfig, LlamaForCausalLM
+
+    torch.manual_seed(0)
+    cfg = LlamaConfig(hidden_size=K, intermediate_size=256, num_hidden_layers=3, num_attention_heads=4,
+                      num_key_value_heads=4, head_dim=64, vocab_size=256, max_position_embeddings=128,
+                      rms_norm_eps=1e-5, tie_word_embeddings=False)
+    return LlamaForCausalLM(cfg).float().eval()
+
+
+def _gpt2():
+    from transformers import GPT2Config, GPT2LMHeadModel
+
+    torch.manual_seed(0)
+    return GPT2LMHeadModel(GPT2Config(n_embd=K, n_layer=3, n_head=4, vocab_size=256, n_positions=64)).float().eval()
+
+
+def _calib():
+    g = torch.Generator().manual_seed(1)
+    return [torch.randint(0, 256, (4, 32), generator=g) for _ in range(2)]
+
+
+@functools.lru_cache(maxsize=None)
+def _walked(kind):
+    """(model, blocks, the captured inputs of block 0, the model's own hidden states per batch): computed once per
+    model, shared by the tests and left unchanged by them"""
+    model = _llama() if kind == "llama" else _gpt2()
+    model.config.use_cache = True
+    blocks = C.decoder_blocks(model)[1]
+    batches = _calib()
+    with torch.no_grad():
+        inputs = C.capture_block_inputs(model, blocks, batches, "cpu")
+        hidden = [model(ids, output_hidden_states=True).hidden_states for ids in batches]
+    return model, blocks, inputs, hidden
+
+
+def _hidden(unit):
+    args, kwargs = unit
+    return args[0] if args else kwargs["hidden_states"]
+
+
+@pytest.mark.parametrize("kind", ["llama", "gpt2"])
+def test_the_stream_is_the_models_own_hidden_states(kind):
+    model, blocks, inputs, hidden = _walked(kind)
+    assert len(blocks) == 3 and len(inputs) == 2
+    assert model.config.use_cache is True and not blocks[0]._forward_pre_hooks
+    with torch.no_grad():
+        for li, block in enumerate(blocks):  # the entry after the last block is past the final norm: not compared
+            for b, unit in enumerate(inputs):
+                assert torch.equal(_hidden(unit), hidden[b][li]), (li, b)
+            inputs = C.next_inputs(inputs, C.run_block(block, inputs))
+
+
+@pytest.mark.parametrize("kind", ["llama", "gpt2"])
+def test_use_cache_and_the_hook_are_restored_when_the_forward_raises(kind):
+    model, blocks, _, _ = _walked(kind)
+
+    def refuse(_module, _args):
+        raise RuntimeError("no embedding today")
+
+    handle = model.get_input_embeddings().register_forward_pre_hook(refuse)
+    try:
+        with pytest.raises(RuntimeError, match="no embedding today"):
+            C.capture_block_inputs(model, blocks, _calib(), "cpu")
+    finally:
+        handle.remove()
+    assert model.config.use_cache is True and not blocks[0]._forward_pre_hooks
+
+
+def _hooks(block):
+    """every hook on the block's modules (transformers keeps output-recording hooks of its own on some)"""
+    return [(name, list(m._forward_hooks.values()), list(m._forward_pre_hooks.values()))
+            for name, m in block.named_modules()]
+
+
+@pytest.mark.parametrize("shared", [False, True])
+@pytest.mark.parametrize("abs_sum", [False, True])
+def test_input_statistics_against_float64(abs_sum, shared):
+    _, blocks, inputs, _ = _walked("llama")
+    block = blocks[0]
+    linears = C.block_linears(block, "model.layers.0", [])
+    assert len(linears) == 7
+    source = {name: SAME_INPUT.get(name, name) for name, _ in linears} if shared else None
+    before = _hooks(block)
+    with torch.no_grad():
+        xtx, asum, count = C.collect_input_stats(block, linears, inputs, source, abs_sum)
+        x = torch.cat([block.input_layernorm(_hidden(u)).reshape(-1, K) for u in inputs]).double()
+    assert _hooks(block) == before and not any(m._forward_hooks for _, m in linears)
+    expect = {name for name, _ in linears if not shared or name not in SAME_INPUT}
+    assert set(xtx) == set(count) == expect and set(asum) == (expect if abs_sum else set())
+    assert all(c == TOKENS for c in count.values()) and x.shape == (TOKENS, K)
+    # the fp32 summation bound: T roundings of at most 2^-23 of the running sum of magnitudes each
+    bound = TOKENS * 2.0 ** -23 * (x.abs().t() @ x.abs())
+    ref = x.t() @ x
+    for name in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
+        if name not in expect:
+            continue
+        assert xtx[name].dtype == torch.float32
+        err = (xtx[name].double() - ref).abs()
+        print("%s X^T X: worst err / bound %.3g" % (name, float((err / bound).max())))
+        assert bool((err <= bound).all())
+        if abs_sum:
+            aerr = (asum[name].double() - x.abs().sum(0)).abs()
+            abound = TOKENS * 2.0 ** -23 * x.abs().sum(0)
+            print("%s sum |x|: worst err / bound %.3g" % (name, float((aerr / abound).max())))
+            assert bool((aerr <= abound).all())
+
+
+def test_hooks_are_removed_when_the_block_raises_half_way():
+    _, blocks, inputs, _ = _walked("llama")
+    block = blocks[0]
+    linears = C.block_linears(block, "blocks.0", [])
+    before = _hooks(block)
+    with torch.no_grad(), pytest.raises(TypeError):
+        C.collect_input_stats(block, linears, [inputs[0], ((), {})], abs_sum=True)  # the second unit has no hidden states
+    assert _hooks(block) == before and not any(m._forward_hooks for _, m in linears)
+
+
+def test_batch_size_override():
+    rows = [torch.arange(6) + i for i in range(10)] + [torch.arange(4) + i for i in range(9)]
+    cfg = types.SimpleNamespace(calib_dataloader=rows, dataset=None, n_samples=19, seq_len=6)  # no batch_size
+    got = C.calibration_batches(cfg, batch_size=8)
+    assert [tuple(b.shape) for b in got] == [(8, 6), (2, 6), (8, 4), (1, 4)]  # rows of equal length, 8 per batch
+    assert torch.equal(torch.cat([b.reshape(-1) for b in got]), torch.cat(rows))
+    assert [tuple(b.shape) for b in C.calibration_batches(cfg)] == [(1, 6)] * 10 + [(1, 4)] * 9
+    cfg.batch_size = 4  # the config's own value holds without an override, and gives way to one
+    assert [tuple(b.shape) for b in C.calibration_batches(cfg)][:3] == [(4, 6), (4, 6), (2, 6)]
+    assert tuple(C.calibration_batches(cfg, batch_size=8)[0].shape) == (8, 6)
+
+
+def test_the_method_files_do_not_import_from_one_another():
+    methods = ("gptq", "awq", "autoround")
+    here = os.path.dirname(os.path.abspath(C.__file__))
+    for name in methods:
+        tree = ast.parse(open(os.path.join(here, name + ".py")).read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom):
+                imported = [node.module or ""] + [a.name for a in node.names]
+            elif isinstance(node, ast.Import):
+                imported = [a.name for a in node.names]
+            else:
+                continue
+            for other in methods:
+                assert not any(part == other for i in imported for part in i.split(".")), (name, ast.dump(node))

@@ -57,7 +57,7 @@ def test_model_without_decoder_blocks_is_named():
 def test_calibration_data_is_kept_by_reference_and_not_serialised():
     c = _cfg(calib_dataloader=IDS, n_samples=3, seq_len=5, batch_size=2)
     assert c.calib_dataloader is IDS and "calib_dataloader" not in c.to_dict()
-    from intel_extension_for_transformers_amd.transformers.llm.quantization.gptq import calibration_batches
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.calibration import calibration_batches
 
     loader = [{"input_ids": torch.arange(16).reshape(2, 8)}, (torch.arange(8),), torch.arange(8)]
     got = calibration_batches(_cfg(calib_dataloader=loader, n_samples=3, seq_len=5, batch_size=2))

@@ -14,11 +14,12 @@ from tests import quant_reference as Q
 pytestmark = pytest.mark.gpu
 
 DELTA_SHAPES = [(256, 96, 64), (384, 200, 128), (200, 70, 32)]  # the last: a short final group and a ragged N
-CLIP_SHAPES = [(256, 96, 32), (384, 200, 128), (200, 70, 64)]
+# the last two: K < group, one short group that still runs in its group's own kernel form
+CLIP_SHAPES = [(256, 96, 32), (384, 200, 128), (200, 70, 64), (100, 200, 128), (48, 96, 64)]
 EPS = 2.0 ** -24
 
-# sum over the cells of losses[best], device over reference, on the six clip cases below, measured on the MI355X
-# (profiles/r16_awq.txt): the largest |ratio - 1| was 6.02e-8; the bound is 16 x that. A wrong Gram element or clamp
+# sum over the cells of losses[best], device over reference, on the six clip cases with K > group, measured on the
+# MI355X (profiles/r16_awq.txt): the largest |ratio - 1| was 6.02e-8; the bound is 16 x that. A wrong Gram element or clamp
 # moves the sum by tens of percent (RTN's is 1.45 to 2.2 times the best).
 CLIP_SUM_MARGIN = 16 * 6.02e-8
 

@@ -25,7 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from intel_extension_for_transformers_amd import qbits  # noqa: E402
-from intel_extension_for_transformers_amd.transformers.llm.quantization import autoround  # noqa: E402
+from intel_extension_for_transformers_amd.transformers.llm.quantization import autoround, calibration  # noqa: E402
 
 SHAPES = "4096x12288,4096x4096,4096x22016,11008x4096"
 PEAK = 8.0e12  # bytes / s
@@ -109,22 +109,11 @@ def rate_block(group, bits, reps, batch, seq):
                       num_key_value_heads=32, vocab_size=1024, max_position_embeddings=seq, tie_word_embeddings=False)
     model = LlamaForCausalLM(cfg).to(torch.bfloat16).to(dev).eval()
     block = model.model.layers[0]
-    inputs = []
-
-    def grab(_m, args, kwargs):
-        inputs.append((args, kwargs))
-        raise autoround._Stop()
-
-    handle = block.register_forward_pre_hook(grab, with_kwargs=True)
-    model.config.use_cache = False
     with torch.no_grad():
-        try:
-            model(input_ids=torch.randint(0, 1024, (batch, seq), device=dev))
-        except autoround._Stop:
-            pass
-        handle.remove()
-        targets = autoround._run_block(block, inputs)
-    linears = autoround._block_linears(block, "model.layers.0", [])
+        ids = torch.randint(0, 1024, (batch, seq), device=dev)
+        inputs = calibration.capture_block_inputs(model, [block], [ids], dev)
+        targets = calibration.run_block(block, inputs)
+    linears = calibration.block_linears(block, "model.layers.0", [])
     quantisers = [autoround._Quantiser(m, group, bits, True, torch.bfloat16) for _, m in linears]
     for (_, m), q in zip(linears, quantisers):
         autoround._wrap(m, q)
