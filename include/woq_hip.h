@@ -148,6 +148,24 @@ WOQ_API int woq_autoround_codes(const float* w_dev, const float* v_dev, const fl
                                 int K, int N, int group, int bits, int asym, int8_t* q_dev, float* scale_dev,
                                 int8_t* zp_dev, void* stream);
 
+/* the quantiser of TEQ calibration (no reference counterpart: the reference hands TEQ to neural_compressor; rule,
+ * gradient and layout: csrc/woq_teq.hip, DESIGN.md "TEQ"). w fp32 [K,N] in working order (Linear.weight.T); a fp32 [K]
+ * the trainable per-input-channel scale, positive; groups of `group` rows (the last may be short; group <= 0 or > K =
+ * one group per column); bits 2 | 3 | 4 | 8, sym or asym. u = w[k,n] a[k] goes through woq_quantize_to_packed_weight's
+ * RTN rule and W~ = dequantised / a[k], each step rounded on its own: a = 1 is that rule bit for bit. Dtypes are
+ * woq_dtype codes (fp32, bf16, fp16). Both are asynchronous on `stream` and modify no input.
+ *
+ * woq_teq_forward: out [K,N] of out_dtype = W~, the fp32 value rounded once. Allocates nothing. */
+WOQ_API int woq_teq_forward(const float* w_dev, const float* a_dev, int K, int N, int group, int bits, int asym,
+                            void* out_dev, int out_dtype, void* stream);
+
+/* woq_teq_grad: da fp32 [K] (overwritten) = dL/da from g = dL/dW~ [K,N] of g_dtype: the forward is recomputed, rounding
+ * is straight-through, clips pass inside their range, a group's max / min pass to the row that attains them. No
+ * floating-point atomics and a summation order the layout fixes: the same inputs give the same bytes. Takes
+ * K * ceil(N / 64) floats of scratch (woq_set_workspace, else a stream-ordered allocation). */
+WOQ_API int woq_teq_grad(const float* w_dev, const float* a_dev, const void* g_dev, int g_dtype, int K, int N,
+                         int group, int bits, int asym, float* da_dev, void* stream);
+
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device
  * memory from the host. */

@@ -17,6 +17,7 @@ __all__ = [
     "acquire_packed_weight_info", "get_packed_weight_size", "set_woq_workspace", "set_qbits_threads",
     "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
     "awq_scale_delta", "awq_clip_search", "autoround_forward", "autoround_step", "autoround_codes",
+    "teq_forward", "teq_grad",
 ]
 
 
@@ -249,6 +250,47 @@ def autoround_codes(w, v, alpha, beta, group, bits, asym):
     L.check(L.lib().woq_autoround_codes(_ptr(w), _ptr(v), _ptr(alpha), _ptr(beta), k, n, int(group), int(bits),
                                         int(bool(asym)), _ptr(q), _ptr(scale), _ptr(zp), L.stream_ptr()))
     return q, scale, zp
+
+
+def _teq_args(name, w, a):
+    """the argument checks the two TEQ calls share -> (K, N)"""
+    if w.dim() != 2:
+        raise RuntimeError("QBits: %s: w must be [K,N]" % name)
+    k, n = w.shape
+    if not (_f32_dev(w, (k, n)) and _f32_dev(a, (k,))):
+        raise RuntimeError("QBits: %s takes contiguous fp32 device tensors w [K,N], a [K]" % name)
+    return k, n
+
+
+def teq_forward(w, a, group, bits, asym, out=None, dtype=None):
+    """TEQ's fake-quantised weight W~ = Q(diag(a) w) / a [K, N] (woq_teq_forward, csrc/woq_teq.hip; no reference
+    counterpart): w fp32 [K, N] (working order, Linear.weight.T), a fp32 [K] the per-input-channel scale (positive); Q
+    the RTN rule of `quantize_to_packed_weight` at (bits, group, asym), so a = 1 is that rule. Returns `out` (fp32, fp16
+    or bf16; allocated as `dtype`, default fp32, when None)."""
+    k, n = _teq_args("teq_forward", w, a)
+    if out is None:
+        out = torch.empty(k, n, dtype=dtype or torch.float32, device=w.device)
+    if not (out.is_cuda and out.dtype in _AUTOROUND_DTYPES and out.is_contiguous() and tuple(out.shape) == (k, n)):
+        raise RuntimeError("QBits: teq_forward: out must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
+    L.check(L.lib().woq_teq_forward(_ptr(w), _ptr(a), k, n, int(group), int(bits), int(bool(asym)), _ptr(out),
+                                    L.torch_dtype_code(out.dtype), L.stream_ptr()))
+    return out
+
+
+def teq_grad(w, a, g, group, bits, asym, out=None):
+    """dL/da fp32 [K] of TEQ's quantiser from g = dL/dW~ [K, N] (fp32, fp16 or bf16) (woq_teq_grad, csrc/woq_teq.hip):
+    the forward is recomputed, rounding is straight-through, a group's max / min pass to the row that attains them.
+    Deterministic: the same inputs give the same bytes. Returns `out` (overwritten; allocated when None)."""
+    k, n = _teq_args("teq_grad", w, a)
+    if not (g.is_cuda and g.dtype in _AUTOROUND_DTYPES and g.is_contiguous() and tuple(g.shape) == (k, n)):
+        raise RuntimeError("QBits: teq_grad: g must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
+    if out is None:
+        out = torch.empty(k, dtype=torch.float32, device=w.device)
+    if not _f32_dev(out, (k,)):
+        raise RuntimeError("QBits: teq_grad: out must be a contiguous fp32 device tensor [K]")
+    L.check(L.lib().woq_teq_grad(_ptr(w), _ptr(a), _ptr(g), L.torch_dtype_code(g.dtype), k, n, int(group), int(bits),
+                                 int(bool(asym)), _ptr(out), L.stream_ptr()))
+    return out
 
 
 def dequantize_packed_weight(compressed_weight, dequantize_weight, transpose, compute_type, weight_type, scale_type):

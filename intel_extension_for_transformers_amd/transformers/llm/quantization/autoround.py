@@ -102,6 +102,17 @@ def _samples(unit):
     return int(x.shape[0])
 
 
+def draw_minibatch(inputs, batch_size, gen):
+    """the indices of one minibatch: whole batches in a random order until `batch_size` samples are reached"""
+    picked, count = [], 0
+    for i in torch.randperm(len(inputs), generator=gen).tolist():
+        picked.append(i)
+        count += _samples(inputs[i])
+        if count >= batch_size:
+            break
+    return picked
+
+
 def _train_block(block, quantisers, inputs, targets, iters, lr, minmax_lr, batch_size, gen):
     """`iters` SignSGD iterations on one block -> (rtn_loss, best_loss, best_iter, best parameters per linear)"""
     best, best_loss, best_iter, rtn_loss = None, None, -1, None
@@ -111,13 +122,7 @@ def _train_block(block, quantisers, inputs, targets, iters, lr, minmax_lr, batch
     try:
         with torch.enable_grad():
             for t in range(iters):
-                order = torch.randperm(len(inputs), generator=gen).tolist()
-                picked, count = [], 0
-                for i in order:
-                    picked.append(i)
-                    count += _samples(inputs[i])
-                    if count >= batch_size:
-                        break
+                picked = draw_minibatch(inputs, batch_size, gen)
                 for q in quantisers:
                     q.lr_v, q.lr_mm = schedule(lr, t, iters), schedule(minmax_lr, t, iters)
                     q.wq = FakeQuant.apply(q.v, q)

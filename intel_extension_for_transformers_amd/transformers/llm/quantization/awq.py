@@ -107,25 +107,26 @@ def apply_scales(block, scales):
         fold_scale(block, names, prev, s)
 
 
-def _scale_groups(block, linears, where):
+def _scale_groups(block, linears, where, method="AWQ"):
     """the absorb groups of this block that can be searched: every member among `linears`; a group whose producing op
     is a linear only where that linear's outputs are the group's inputs one to one (o_proj after v_proj: not under
-    grouped-query attention, AutoAWQ's rule)"""
+    grouped-query attention, AutoAWQ's rule). `method` names the caller in the log lines (teq.py shares the rule)."""
     have = {name for name, _ in linears}
     out = []
     for gi, (names, prev) in enumerate(_GROUPS):
         if not all(n in have for n in names):
-            logger.info("AWQ %s: absorb group %s skipped (not every linear is quantised)", where, "/".join(names))
+            logger.info("%s %s: absorb group %s skipped (not every linear is quantised)", method, where,
+                        "/".join(names))
             continue
         p = block.get_submodule(prev)
         if isinstance(p, torch.nn.Linear):
             if prev not in have:
-                logger.info("AWQ %s: absorb group %s skipped (%s is not quantised)", where, names[0], prev)
+                logger.info("%s %s: absorb group %s skipped (%s is not quantised)", method, where, names[0], prev)
                 continue
             if p.out_features != block.get_submodule(names[0]).in_features:
                 # AutoAWQ compares the two weights' shapes, the same test wherever heads * head_dim = hidden
-                logger.info("AWQ %s: %s scale skipped (grouped-query attention: %s has %d outputs for %d inputs)",
-                            where, names[0], prev, p.out_features, block.get_submodule(names[0]).in_features)
+                logger.info("%s %s: %s scale skipped (grouped-query attention: %s has %d outputs for %d inputs)",
+                            method, where, names[0], prev, p.out_features, block.get_submodule(names[0]).in_features)
                 continue
         out.append(gi)
     return out

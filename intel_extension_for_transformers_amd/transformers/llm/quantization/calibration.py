@@ -1,5 +1,5 @@
-"""What the calibrated methods (gptq.py, awq.py, autoround.py) share: the request checks, the calibration batches, the
-walk down the decoder blocks (the first block's inputs as the model itself calls it, a block run over them, the next
+"""What the calibrated methods (gptq.py, awq.py, autoround.py, teq.py) share: the request checks, the calibration
+batches, the walk down the decoder blocks (the first block's inputs as the model itself calls it, a block run over them, the next
 block's inputs), the per-linear input statistics from forward hooks, and the swap of a linear for its
 QuantizedLinearQBits. Plain functions; every method keeps its own loop over the blocks.
 """
@@ -14,7 +14,7 @@ BITS = {name: bits for bits, name in WNAME.items()}
 
 _NOT_PART = " calibration is not part of the MI355X hot path without calibration data (dataset=%r is not downloaded)"
 _NO_DATA = {"GPTQ": "GPTQ calibration does not download datasets (dataset=%r)", "AWQ": "AwqConfig" + _NOT_PART,
-            "AutoRound": "AutoRoundConfig" + _NOT_PART}
+            "AutoRound": "AutoRoundConfig" + _NOT_PART, "TEQ": "TeqConfig" + _NOT_PART}
 
 
 # ---- the request ---------------------------------------------------------------------------------------------------
@@ -30,7 +30,7 @@ def data_source(config, method="GPTQ"):
 
 
 def check_request(model, config, method, unsupported_options, blocks_first=False):
-    """Everything about a request that can be refused without touching a device; `method` is GPTQ, AWQ or AutoRound.
+    """Everything about a request that can be refused without touching a device; `method` is GPTQ, AWQ, AutoRound or TEQ.
     `blocks_first`: a model without decoder blocks is named before missing data (AutoRound's order)."""
     for opt in unsupported_options:
         if getattr(config, opt, False):

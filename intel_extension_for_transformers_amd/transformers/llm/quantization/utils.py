@@ -223,18 +223,22 @@ def convert_to_quantized_model(model, config, device="cuda"):
     projections of Llama-class blocks, the result is a plain RTN blob). AutoRound on an fp model: trained on the device,
     block by block (autoround.py autoround_quantize_model: SignSGD on a rounding offset and two range factors per
     group, the quantiser's forward and its backward + update in csrc/woq_autoround.hip; the result is a plain blob).
-    TEQ is a trained search that the reference runs inside neural_compressor (external); that config (like GPTQ / AWQ /
-    AutoRound) is accepted for PRE-QUANTISED checkpoints (optimum-format tensors already on the modules), and raises
-    for an fp model instead of silently falling back to RTN."""
+    TEQ on an fp model: trained on the device, block by block (teq.py teq_quantize_model: Adam on one per-channel scale
+    per absorb group of a Llama-class block, the fake-quantised weight and the scale's gradient in csrc/woq_teq.hip; the
+    scales are folded in as AWQ's are, the result is a plain RTN blob). Every one of these configs is also accepted
+    for PRE-QUANTISED checkpoints (optimum-format tensors already on the modules); a request a method does not build
+    raises instead of silently falling back to RTN."""
     method = getattr(config.quant_method, "value", config.quant_method)
     has_packed = any(_packed_checkpoint_linear(m) for m in model.modules())
-    if method in ("gptq", "awq", "autoround") and not has_packed:
+    if method in ("gptq", "awq", "autoround", "teq") and not has_packed:
         if method == "gptq":
             from .gptq import gptq_quantize_model as calibrate, validate_gptq_request as validate
         elif method == "awq":
             from .awq import awq_quantize_model as calibrate, validate_awq_request as validate
-        else:
+        elif method == "autoround":
             from .autoround import autoround_quantize_model as calibrate, validate_autoround_request as validate
+        else:
+            from .teq import teq_quantize_model as calibrate, validate_teq_request as validate
 
         validate(model, config)  # NotImplementedError for what is not built, before a device is needed
         if str(device) == "cpu":

@@ -353,6 +353,23 @@ class TeqConfig(ITREXQuantizationConfigMixin):
                ("absorb_to_layer", {}), ("n_samples", 128), ("seq_len", 2048), ("use_double_quant", False),
                ("double_quant_scale_dtype", None), ("sym", True)) + _TAIL
 
+    def __init__(self, *args, **kwargs):
+        # calibration data for an fp model (transformers/llm/quantization/teq.py), as GPTQConfig takes it: kept by
+        # reference, never copied or serialised. The training knobs of that path are plain attributes outside _fields,
+        # so the serialised schema stays the reference's.
+        loader = kwargs.pop("calib_dataloader", None)
+        train_steps = kwargs.pop("train_steps", 1000)
+        lr = kwargs.pop("lr", 1e-3)
+        batch_size = kwargs.pop("batch_size", 8)
+        super().__init__(*args, **kwargs)
+        self.calib_dataloader = loader
+        self.train_steps, self.lr, self.batch_size = train_steps, lr, batch_size
+
+    _TRAIN_KNOBS = ("train_steps", "lr", "batch_size")
+
+    def to_dict(self):
+        return {k: v for k, v in super().to_dict().items() if k not in self._TRAIN_KNOBS}
+
 
 class AutoRoundConfig(ITREXQuantizationConfigMixin):
     """config.py:1118-1200."""

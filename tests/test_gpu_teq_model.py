@@ -1,0 +1,275 @@
+"""TEQ calibration end to end on the GPU: `from_pretrained(fp_model, quantization_config=TeqConfig(...))` on tiny
+random-init 2-layer Llama-class models (no checkpoints, no network): one with as many kv heads as query heads (all four
+absorb groups train) and one with grouped-query attention (the o_proj group is skipped)."""
+import copy
+import functools
+import logging
+import math
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+STEPS, LR = 20, 1e-2
+NO_PRODUCER_ROLE = ("self_attn.q_proj", "self_attn.k_proj", "mlp.gate_proj", "mlp.down_proj")
+
+
+def _tiny_llama(kv_heads):
+    from transformers import LlamaConfig, LlamaForCausalLM
+
+    torch.manual_seed(0)
+    # head_dim 64 (the decode engine's smallest), 4 query heads: hidden 128 -> 256, so o_proj has 256 inputs and v_proj
+    # 256 outputs with 4 kv heads, 128 with 2
+    cfg = LlamaConfig(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=4,
+                      num_key_value_heads=kv_heads, head_dim=64, vocab_size=256, max_position_embeddings=128,
+                      rms_norm_eps=1e-5, tie_word_embeddings=False)
+    model = LlamaForCausalLM(cfg).float().eval()
+    g = torch.Generator().manual_seed(7)
+    with torch.no_grad():
+        for layer in model.model.layers:
+            for norm in (layer.input_layernorm, layer.post_attention_layernorm):
+                norm.weight.copy_(torch.exp(torch.empty(128).uniform_(math.log(0.25), math.log(8.0), generator=g)))
+    return model
+
+
+def _calib():
+    g = torch.Generator().manual_seed(1)
+    return [torch.randint(0, 256, (8, 32), generator=g)]  # 8 samples of 32 ids
+
+
+def _config(**kw):
+    from intel_extension_for_transformers_amd.transformers import TeqConfig
+
+    kw.setdefault("calib_dataloader", _calib())
+    kw.setdefault("batch_size", 8)  # every step sees all samples
+    return TeqConfig(bits=4, group_size=32, n_samples=8, seq_len=32, **kw)
+
+
+def _convert(fp, cfg):
+    from intel_extension_for_transformers_amd.transformers import AutoModelForCausalLM
+
+    return AutoModelForCausalLM.from_pretrained(copy.deepcopy(fp), quantization_config=cfg)
+
+
+def _quantised(model):
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.nn.modules import QuantizedLinearQBits
+
+    return [(n, m) for n, m in model.named_modules() if isinstance(m, QuantizedLinearQBits)]
+
+
+def _deq(module):
+    from intel_extension_for_transformers_amd import qbits
+
+    w = module.weight.data
+    k, n = (int(qbits.acquire_packed_weight_info(w, t)[0]) for t in (2, 3))
+    out = torch.empty(k, n, dtype=torch.float32, device=w.device)
+    qbits.dequantize_packed_weight(w, out, False, module.compute_dtype, module.weight_dtype, module.scale_dtype)
+    return out
+
+
+@pytest.mark.parametrize("sym", [True, False])
+@pytest.mark.parametrize("kv_heads", [4, 2])
+def test_zero_steps_are_rtn(kv_heads, sym):
+    """train_steps=0: every quantised linear's blob is RtnConfig's, byte for byte, and the norms are untouched"""
+    from intel_extension_for_transformers_amd.transformers import RtnConfig
+
+    fp = _tiny_llama(kv_heads)
+    teq = _convert(fp, _config(train_steps=0, sym=sym))
+    rtn = _convert(fp, RtnConfig(bits=4, group_size=32, sym=sym))
+    names = [n for n, _ in _quantised(teq)]
+    assert len(names) == 14 and "lm_head" not in names
+    assert teq._teq_log == [(None, None, -1)] * 2
+    for n in names:
+        assert torch.equal(teq.get_submodule(n).weight.data, rtn.get_submodule(n).weight.data), n
+    for a, b in zip(teq.model.layers, fp.model.layers):
+        assert torch.equal(a.input_layernorm.weight.cpu(), b.input_layernorm.weight)
+
+
+class _Capture(logging.Handler):
+    def __init__(self):
+        super().__init__(level=logging.INFO)
+        self.lines = []
+
+    def emit(self, record):
+        self.lines.append(record.getMessage())
+
+
+@functools.lru_cache(maxsize=None)
+def _trained(kv_heads, sym=True):
+    """one conversion at train_steps=20, lr=1e-2, with the driver's log lines"""
+    fp = _tiny_llama(kv_heads)
+    handler = _Capture()
+    loggers = [logging.getLogger("intel_extension_for_transformers_amd.transformers.llm.quantization." + m)
+               for m in ("awq", "teq")]
+    levels = [lg.level for lg in loggers]
+    for lg in loggers:
+        lg.addHandler(handler)
+        lg.setLevel(logging.INFO)
+    try:
+        model = _convert(fp, _config(train_steps=STEPS, lr=LR, sym=sym))
+    finally:
+        for lg, level in zip(loggers, levels):
+            lg.removeHandler(handler)
+            lg.setLevel(level)
+    return fp, model, handler.lines
+
+
+@pytest.mark.parametrize("kv_heads,sym", [(4, True), (2, True), (2, False)])
+def test_training_lowers_the_block_loss(kv_heads, sym):
+    fp, model, lines = _trained(kv_heads, sym)
+    log = model._teq_log
+    print("kv_heads=%d sym=%d: (rtn loss, best loss, best step) per block: %s" % (kv_heads, sym, log))
+    assert len(log) == 2
+    for rtn_loss, best_loss, best_step in log:
+        assert math.isfinite(rtn_loss) and math.isfinite(best_loss) and 0 <= best_step < STEPS
+        assert best_loss <= rtn_loss  # the same data every step, and step 0 is kept as the best so far
+    assert any(best < rtn for rtn, best, _ in log)
+    assert len(_quantised(model)) == 14 and type(model.lm_head).__name__ == "Linear"
+    for li, (q, f) in enumerate(zip(model.model.layers, fp.model.layers)):
+        scales = model._teq_scales[li]
+        assert sorted(scales) == ([0, 1, 2, 3] if kv_heads == 4 else [0, 2, 3])
+        for a in scales.values():
+            assert float(a.min()) >= 1e-4 and torch.isfinite(a).all()
+        if log[li][2] > 0:  # something other than RTN was kept: the norms took 1 / a
+            assert not torch.equal(q.input_layernorm.weight.cpu(), f.input_layernorm.weight)
+            assert torch.equal(q.input_layernorm.weight, f.input_layernorm.weight.cuda() / scales[0])
+            assert torch.equal(q.post_attention_layernorm.weight, f.post_attention_layernorm.weight.cuda() / scales[2])
+    assert any(step > 0 for _, _, step in log)
+    skipped = [ln for ln in lines if "TEQ" in ln and "o_proj scale skipped (grouped-query attention" in ln]
+    assert len(skipped) == (0 if kv_heads == 4 else 2), lines
+
+
+@pytest.mark.parametrize("kv_heads,sym", [(4, True), (2, True), (2, False)])
+def test_blobs_are_the_quantiser_at_the_kept_scales(kv_heads, sym):
+    """a linear that produces for no trained group (q, k, gate, down; v as well under grouped-query attention, where the
+    o_proj group is skipped and v_proj's columns are untouched): dequantize(blob)[k, n] / a[k] equals teq_forward of the
+    original fp32 weight at the kept a, bit for bit (4 bits)"""
+    from intel_extension_for_transformers_amd import qbits
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.awq import _GROUPS
+
+    fp, model, _ = _trained(kv_heads, sym)
+    names = NO_PRODUCER_ROLE + (("self_attn.v_proj",) if kv_heads == 2 else ())
+    for li, (q, f) in enumerate(zip(model.model.layers, fp.model.layers)):
+        scales = model._teq_scales[li]
+        for name in names:
+            gi = [i for i, (members, _) in enumerate(_GROUPS) if name in members][0]
+            a = scales[gi]
+            w = f.get_submodule(name).weight.data.t().float().contiguous().cuda()
+            want = qbits.teq_forward(w, a, 32, 4, not sym)
+            got = _deq(q.get_submodule(name)) / a[:, None]
+            assert torch.equal(got, want), (li, name)
+
+
+@pytest.mark.parametrize("kv_heads,sym", [(4, True), (2, False)])
+def test_installed_block_reaches_the_logged_loss(kv_heads, sym):
+    """the installed block on the calibration inputs of the fp stream: its loss is within 2 % of the logged best loss
+    (fp32 rounding of the fold against the division inside W~, and the ties a producer's column factor may flip)"""
+    from intel_extension_for_transformers_amd.transformers.llm.quantization import calibration as C
+
+    fp, model, _ = _trained(kv_heads, sym)
+    ref = copy.deepcopy(fp).cuda()
+    blocks = ref.model.layers
+    with torch.no_grad():
+        inputs = C.capture_block_inputs(ref, blocks, _calib(), "cuda")
+        for li, block in enumerate(blocks):
+            targets = C.run_block(block, inputs)
+            outs = C.run_block(model.model.layers[li], inputs)
+            total = sum(t.numel() for t in targets)
+            loss = sum(float((y.float() - t.float()).square().sum()) for y, t in zip(outs, targets)) / total
+            best = model._teq_log[li][1]
+            print("kv_heads=%d sym=%d block %d: installed loss %.6g, logged best %.6g"
+                  % (kv_heads, sym, li, loss, best))
+            assert abs(loss - best) <= 0.02 * best
+            inputs = C.next_inputs(inputs, targets)
+
+
+def test_a_second_conversion_gives_the_same_bytes():
+    fp, model, _ = _trained(4)
+    again = _convert(fp, _config(train_steps=STEPS, lr=LR))
+    assert again._teq_log == model._teq_log
+    for (n, a), (_, b) in zip(_quantised(model), _quantised(again)):
+        assert torch.equal(a.weight.data, b.weight.data), n
+    for a, b in zip(model.model.layers, again.model.layers):
+        assert torch.equal(a.input_layernorm.weight, b.input_layernorm.weight)
+
+
+@pytest.mark.parametrize("kv_heads", [4, 2])
+def test_round_trip_and_the_decode_engine(tmp_path, kv_heads):
+    from intel_extension_for_transformers_amd.runtime.engine import optimize_transformers
+    from intel_extension_for_transformers_amd.transformers import AutoModelForCausalLM
+
+    _, qmodel, _ = _trained(kv_heads)
+    probe = torch.tensor([[5, 17, 200, 3, 77, 9]], device="cuda")
+    with torch.no_grad():
+        logits = qmodel(probe).logits.float()
+    qmodel.save_pretrained(str(tmp_path / "q"))
+    back = AutoModelForCausalLM.from_pretrained(str(tmp_path / "q"))
+    with torch.no_grad():
+        assert torch.equal(back(probe).logits.float(), logits)
+
+    # the decode engine builds on the result and agrees with the module path (the bound
+    # tests/test_gpu_autoround_model.py::test_round_trip_and_the_decode_engine uses)
+    eng = optimize_transformers(qmodel, max_ctx=64, kv_dtype=torch.float16)
+    prompt = [5, 17, 200, 3, 77]
+    pids = torch.tensor([prompt], device="cuda")
+    with torch.no_grad():
+        ref_logits = qmodel(pids).logits[0, -1].float()
+        ref_out = qmodel._woq_hf_generate(pids, max_new_tokens=6, do_sample=False)[0, len(prompt):].tolist()
+    for i, t in enumerate(prompt):
+        eng.token.fill_(t)
+        eng.pos.fill_(i)
+        eng.step(greedy=False)
+    got = eng.logits.float()
+    assert (got - ref_logits).abs().max().item() <= 2e-3 * ref_logits.abs().max().item() + 1e-4
+    assert eng.generate(prompt, 6) == ref_out
+
+
+def test_texts_with_a_tokenizer_calibrate_too():
+    class Tok:
+        def __call__(self, text):
+            return {"input_ids": [ord(c) % 256 for c in text]}
+
+    texts = ["the quick brown fox jumps over the lazy dog " * 2, "pack my box with five dozen liquor jugs " * 2]
+    from intel_extension_for_transformers_amd.transformers import TeqConfig
+
+    cfg = TeqConfig(bits=4, group_size=32, dataset=texts, tokenizer=Tok(), n_samples=2, seq_len=48, train_steps=4)
+    qmodel = _convert(_tiny_llama(2), cfg)
+    assert len(_quantised(qmodel)) == 14 and len(qmodel._teq_log) == 2
+    with torch.no_grad():
+        assert torch.isfinite(qmodel(torch.tensor([[5, 17, 200]], device="cuda")).logits).all()
+
+
+def test_neural_chat_pipeline_with_a_teq_config(tmp_path):
+    """PipelineConfig(optimization_config=TeqConfig(...)) -> build_chatbot: the model is calibrated at load time, the
+    decode engine builds on it and a greedy request answers the same through the engine and the module path."""
+    from tokenizers import Tokenizer, models, pre_tokenizers
+    from transformers import PreTrainedTokenizerFast
+
+    from intel_extension_for_transformers_amd.neural_chat import GenerationConfig, PipelineConfig, build_chatbot
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.nn.modules import QuantizedLinearQBits
+
+    d = tmp_path / "tiny-llama-chat"
+    fp = _tiny_llama(2)
+    fp.generation_config.eos_token_id = None  # random-init model: never stop early
+    fp.save_pretrained(str(d))
+    vocab = {"<unk>": 0, "<s>": 1, "</s>": 2}
+    vocab.update({"w%d" % i: i for i in range(3, fp.config.vocab_size)})
+    tk = Tokenizer(models.WordLevel(vocab, unk_token="<unk>"))
+    tk.pre_tokenizer = pre_tokenizers.WhitespaceSplit()
+    PreTrainedTokenizerFast(tokenizer_object=tk, unk_token="<unk>", bos_token="<s>",
+                            eos_token="</s>").save_pretrained(str(d))
+    opt = _config(train_steps=4, lr=LR, scale_dtype="fp16")
+    bot = build_chatbot(PipelineConfig(model_name_or_path=str(d), device="cuda", optimization_config=opt))
+    assert bot.engine is not None
+    assert isinstance(bot.model.model.layers[0].mlp.down_proj, QuantizedLinearQBits)
+    cfg = GenerationConfig(max_new_tokens=8, do_sample=False, repetition_penalty=1.0)
+    text = bot.predict("w5 w17 w200 w3 w77", config=cfg)
+    assert len(text.split()) == 8
+    bot_engine, bot.engine = bot.engine, None
+    bot.model._woq_engine_off = True
+    try:
+        assert bot.predict("w5 w17 w200 w3 w77", config=cfg) == text
+    finally:
+        bot.engine = bot_engine
+        bot.model._woq_engine_off = False
