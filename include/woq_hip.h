@@ -166,6 +166,27 @@ WOQ_API int woq_teq_forward(const float* w_dev, const float* a_dev, int K, int N
 WOQ_API int woq_teq_grad(const float* w_dev, const float* a_dev, const void* g_dev, int g_dtype, int K, int N,
                          int group, int bits, int asym, float* da_dev, void* stream);
 
+/* ---- backward of the linear with respect to its activations (reference: autograd/functions.py:163-179, which
+ * dequantises the whole weight and calls a matmul; new entry points only, WOQ_ABI_VERSION stays 4) -------------------
+ * dX[m][k] = sum_n dY[m][n] w[k][n], w as woq_dequantize_packed_weight defines it; for an act-order blob w is indexed
+ * by blob row j and the result is written to column shuffle[j]. grad_out [M, ldg >= N] and grad_in [M, ldo >= K]
+ * (overwritten; columns at or beyond K are not touched) are fp32 | bf16 | fp16. One fp16 product per operand pair on
+ * the matrix cores (dY with an exact power-of-two scale per row, w relative to the blob's largest scale), fp32
+ * accumulation over all of N in a fixed order, no floating-point atomics: the same inputs give the same bytes; a 16-bit
+ * output is the fp32 result rounded once (csrc/woq_linear_bwd.hip, DESIGN.md "QLoRA backward"). Weight types: int4 /
+ * int3 / int2 sym and asym, int8, nf4, fp4_e2m1, fp4_e2m1_bnb, every group size and both scale modes; fp8 weights fail
+ * with a "QBits:" message. Stream-ordered, allocates nothing and synchronises nothing: its scratch is
+ * woq_linear_backward_workspace(M, hdr) bytes of the workspace (woq_set_workspace), and a workspace without that much
+ * room fails with a message that names the size, launching nothing.
+ *
+ * woq_linear_backward_workspace: 2 * Mpad * Npad64 (the fp16 image of dY) + 4 * Mpad rounded up to 256 (row scales)
+ * + 256 (one word: the blob's largest scale), Mpad = M rounded up to 128, Npad64 = N rounded up to 64. It holds no
+ * image of W and does not grow with K * N. 0 for a bad header or M <= 0. */
+WOQ_API int woq_linear_backward(const void* grad_out_dev, int grad_dtype, int ldg, const void* blob_dev,
+                                const woq_blob_header* hdr, void* grad_in_dev, int out_dtype, int ldo, int M,
+                                void* stream);
+WOQ_API size_t woq_linear_backward_workspace(int M, const woq_blob_header* hdr);
+
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device
  * memory from the host. */

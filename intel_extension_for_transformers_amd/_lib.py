@@ -100,6 +100,7 @@ EXPORTS = [
     "woq_engine_kv_shift", "woq_engine_discarded_ptr", "woq_engine_discarded_set", "woq_gptq_sweep",
     "woq_engine_set_layer_extras", "woq_awq_scale_delta", "woq_awq_clip_search",
     "woq_autoround_forward", "woq_autoround_step", "woq_autoround_codes", "woq_teq_forward", "woq_teq_grad",
+    "woq_linear_backward", "woq_linear_backward_workspace",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -152,6 +153,9 @@ def lib():
     L.woq_autoround_codes.argtypes = [vp] * 4 + [ci] * 5 + [vp] * 4
     L.woq_teq_forward.argtypes = [vp, vp] + [ci] * 5 + [vp, ci, vp]
     L.woq_teq_grad.argtypes = [vp, vp, vp] + [ci] * 6 + [vp, vp]
+    L.woq_linear_backward.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, ci, ci, ci, vp]
+    L.woq_linear_backward_workspace.restype = cs
+    L.woq_linear_backward_workspace.argtypes = [ci, ctypes.POINTER(BlobHeader)]
     L.woq_read_header.argtypes = [vp, ctypes.POINTER(BlobHeader), vp]
     L.woq_blob_extract.argtypes = [vp, ctypes.POINTER(BlobHeader), ci, vp, vp]
     L.woq_linear.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, vp, ci, ci, ci, vp]

@@ -57,10 +57,11 @@ void* scratch_take(size_t bytes, hipStream_t st, bool* own) {
     g_ws.has_last = true;
     void* p = g_ws.base + g_ws.used;
     g_ws.used += need;
-    *own = false;
+    if (own != nullptr) *own = false;
     return p;
   }
 private_alloc:
+  if (own == nullptr) return nullptr;  // the caller takes the workspace or nothing (woq_linear_backward)
   void* p = nullptr;
   *own = true;
   if (hipMallocAsync(&p, bytes, st) != hipSuccess) {

@@ -32,6 +32,7 @@ namespace woq {
 // every call) when it has room, which keeps the call allocation-free and capturable into a hipGraph; otherwise
 // stream-ordered allocation, like the reference's per-call amalloc (:108-118,179). Nested takes release in LIFO order.
 // Like the reference's global workspace pointer, not safe for concurrent calls from several host threads / streams.
+// own == nullptr: the workspace or nothing — null when it has no room, never an allocation.
 void* scratch_take(size_t bytes, hipStream_t st, bool* own);
 void scratch_release(void* p, size_t bytes, bool own, hipStream_t st);
 }  // namespace woq

@@ -56,6 +56,13 @@ class BaseModel:
         else:  # weight-only quantisation at load time, reference model_utils.py:796-822
             self.model = AutoModelForCausalLM.from_pretrained(self.model_name, quantization_config=opt,
                                                               device_map="cuda")
+        if kwargs.get("peft_path"):
+            # reference model_utils.py load_model: PeftModel.from_pretrained(model, peft_path), kept unmerged. Here the
+            # adapter goes over the blobs (llm/quantization/lora.py) and the model stays on the module path: the fused
+            # engine refuses unmerged adapters
+            from ...transformers.llm.quantization.lora import load_peft_adapter
+
+            load_peft_adapter(self.model, kwargs["peft_path"])
         self.model.eval()
         self.conv_template = self.get_default_conv_template()
         self._try_engine()

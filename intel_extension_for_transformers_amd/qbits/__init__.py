@@ -17,7 +17,7 @@ __all__ = [
     "acquire_packed_weight_info", "get_packed_weight_size", "set_woq_workspace", "set_qbits_threads",
     "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
     "awq_scale_delta", "awq_clip_search", "autoround_forward", "autoround_step", "autoround_codes",
-    "teq_forward", "teq_grad",
+    "teq_forward", "teq_grad", "woq_linear_backward", "woq_linear_backward_workspace",
 ]
 
 
@@ -334,6 +334,66 @@ def woq_linear(activation, weight, bias, output, compute_type, weight_type, scal
               "execute time:%.4fms" % (m, hdr.N, hdr.K, weight_type, compute_type, hdr.group,
                                        str(activation.dtype).replace("torch.", ""),
                                        str(output.dtype).replace("torch.", ""), t0.elapsed_time(t1)), flush=True)
+
+
+_own_workspace = None  # the workspace woq_linear_backward keeps when the caller has set none (grown on demand)
+
+
+def woq_linear_backward_workspace(m, weight):
+    """Bytes of workspace `woq_linear_backward` takes for `m` rows of gradient against this blob
+    (woq_linear_backward_workspace, include/woq_hip.h): the fp16 image of dY and its row scales, never an image of W."""
+    hdr = header_of(weight)
+    return int(L.lib().woq_linear_backward_workspace(int(m), ctypes.byref(hdr)))
+
+
+def _rows_ok(t, cols):
+    return t.dim() == 2 and t.shape[1] == cols and t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= cols)
+
+
+def woq_linear_backward(grad_output, weight, grad_input=None, dtype=None):
+    """grad_input[M,K] = grad_output[M,N] @ W_deq^T straight from the blob (woq_linear_backward, csrc/woq_linear_bwd.hip;
+    the reference's statement is autograd/functions.py:163-179, which dequantises the whole weight first). For an
+    act-order blob the result is in the caller's (un-shuffled) column order. grad_output / grad_input: fp32, bf16 or
+    fp16 device tensors with unit column stride (row-strided views go down as they are); grad_input is allocated as
+    `dtype` (default: grad_output's) when None. Deterministic: the same inputs give the same bytes. fp8 weights raise.
+
+    Scratch comes from the workspace (`set_woq_workspace`) and nowhere else: with one set, a call it has no room for
+    raises with the size it needs; with none set, this module keeps one of its own, grown when a call needs more, so
+    that a steady training loop allocates nothing."""
+    global _own_workspace
+    hdr = header_of(weight)
+    if not (grad_output.is_cuda and grad_output.device == weight.device):
+        raise RuntimeError("QBits: woq_linear_backward: grad_output must be on the packed weight's HIP device")
+    if not _rows_ok(grad_output, hdr.N):
+        raise RuntimeError("QBits: woq_linear_backward takes grad_output [M, N=%d] with unit column stride, got shape %s "
+                           "stride %s" % (hdr.N, tuple(grad_output.shape), tuple(grad_output.stride())))
+    gcode = L.torch_dtype_code(grad_output.dtype)
+    m = grad_output.shape[0]
+    if grad_input is None:
+        grad_input = torch.empty(m, hdr.K, dtype=dtype or grad_output.dtype, device=grad_output.device)
+    elif dtype is not None and grad_input.dtype != dtype:
+        raise RuntimeError("QBits: woq_linear_backward: grad_input is %s, dtype asks for %s" % (grad_input.dtype, dtype))
+    if not (grad_input.is_cuda and grad_input.device == weight.device):
+        raise RuntimeError("QBits: woq_linear_backward: grad_input must be on the packed weight's HIP device")
+    if not (_rows_ok(grad_input, hdr.K) and grad_input.shape[0] == m):
+        raise RuntimeError("QBits: woq_linear_backward takes grad_input [M=%d, K=%d] with unit column stride, got shape "
+                           "%s stride %s" % (m, hdr.K, tuple(grad_input.shape), tuple(grad_input.stride())))
+    ocode = L.torch_dtype_code(grad_input.dtype)
+    if m == 0:
+        return grad_input
+    if _workspace is None or _workspace is _own_workspace:
+        need = int(L.lib().woq_linear_backward_workspace(m, ctypes.byref(hdr)))
+        fits = (_own_workspace is not None and _own_workspace.numel() >= need
+                and _own_workspace.device == weight.device)
+        if not fits:
+            _own_workspace = torch.empty(need, dtype=torch.uint8, device=weight.device)
+        if not fits or _workspace is None:
+            set_woq_workspace(_own_workspace)
+    ldg = grad_output.stride(0) if m > 1 else max(grad_output.stride(0), hdr.N)
+    ldo = grad_input.stride(0) if m > 1 else max(grad_input.stride(0), hdr.K)
+    L.check(L.lib().woq_linear_backward(_ptr(grad_output), gcode, ldg, _ptr(weight), ctypes.byref(hdr), _ptr(grad_input),
+                                        ocode, ldo, m, L.stream_ptr()))
+    return grad_input
 
 
 def _ascii(s):

@@ -1014,6 +1014,9 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16):
     ok, reason = engine_supports(cfg)
     if not ok:
         raise RuntimeError(reason)
+    if any(hasattr(m, "lora_A") for m in model.modules()):
+        raise RuntimeError("QBits: the fused decode engine does not run unmerged LoRA adapters (the model keeps the "
+                           "module path); fold them into the blobs with model.merge_and_unload() first")
     rtype, rs = rope_scaling_of(cfg)
     layers = model.model.layers
     first = layers[0].self_attn.q_proj

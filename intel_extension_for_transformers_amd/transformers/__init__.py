@@ -9,8 +9,16 @@ def __getattr__(name):  # the model classes import torch + HF transformers: load
         from .modeling import modeling_auto
 
         return getattr(modeling_auto, name)
+    if name in _LORA:  # LoRA over blobs (llm/quantization/lora.py): torch only
+        from .llm.quantization import lora
+
+        return getattr(lora, name)
     raise AttributeError(name)
 
 
+_LORA = ("LoraConfig", "QuantizedLoraLinearQBits", "prepare_model_for_kbit_training", "get_peft_model")
+
+
 __all__ = ["AutoModelForCausalLM", "AutoModel", "AutoModelForSeq2SeqLM", "RtnConfig", "AwqConfig", "TeqConfig",
-           "GPTQConfig", "AutoRoundConfig", "WeightOnlyQuantConfig", "MixedPrecisionConfig"]
+           "GPTQConfig", "AutoRoundConfig", "WeightOnlyQuantConfig", "MixedPrecisionConfig", "LoraConfig",
+           "QuantizedLoraLinearQBits", "prepare_model_for_kbit_training", "get_peft_model"]

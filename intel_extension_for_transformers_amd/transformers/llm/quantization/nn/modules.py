@@ -92,9 +92,10 @@ class QuantizedLinearQBits(torch.nn.Linear):
         if bias is None and self.bias is not None:
             bias = self._bias32 = self.bias.detach().to(x.device, torch.float32).contiguous()
         # reference modules.py:155-164: matmul_kbit -> qbits.woq_linear, or the dequantise -> matmul reference arm
-        # under QBITS_DEBUG (autograd/functions.py:184-217)
+        # under QBITS_DEBUG (autograd/functions.py:184-217). An input that asks for a gradient takes the training form
+        # (MatMulKBit: same forward, and a backward that carries dY to the layers in front); nothing else does.
         out = matmul_kbit(x2, self.weight, bias, out, self.compute_dtype, self.weight_dtype, self.scale_dtype,
-                          self.scheme, do_dequant=False)
+                          self.scheme, do_dequant=torch.is_grad_enabled() and x2.requires_grad)
         out = out.view(*shape, self.out_features)
         if os.environ.get("backend", None) == "use_vllm":  # vLLM's linear layers return (output, output_bias):
             return out, None                               # the reference's seam, modules.py:166-167
