@@ -24,35 +24,19 @@
 //   a group whose s was replaced by 1 gives alpha and beta no gradient
 // Step: p <- clamp(p - lr sign(grad)), sign(0) = 0; V in [-0.5, 0.5], alpha / beta in [0, 1]. dV is never stored.
 //
-// Layout, as awq_scale_delta_kernel: a thread owns one column of one group, a range pass then a main pass over the
-// group's rows; lanes side by side along N, every row access coalesced. The group sums ds and dlo stay in the thread's
-// registers in row order: no floating-point atomics, two runs give the same bits. One thread per column and group is
-// only N G / 64 waves (2048 for a 4096 x 4096 linear at group 128, two per SIMD, each with 128 dependent-free but
-// serially issued rows): groups of 64 rows and more are split over 4 threads of a workgroup (64 columns x 4 slices),
-// groups longer than 256 rows (group -1 on a wide layer) over 16 (1024 threads), contiguous rows each; the slices'
-// ranges (exact: min and max) and partial sums meet in LDS and slice 0 adds the partial sums in slice order, so the
-// combination order is fixed. Both row loops are unrolled by four for loads in flight. Measured against the
-// one-slice form in one session (profiles/r17_autoround.txt): forward 1.4 - 2.5 x, step 1.3 - 2.1 x at group 128.
-// fp32 VALU throughout. Memory bound: the forward reads w twice (the second time from L2: a workgroup's group is
-// 32 KiB at group 128) and V once and writes W~, 10 B per weight from HBM with a 16-bit output; the step reads w,
-// V and g and writes V, 14 - 16 B per weight. Measured at the Llama-2-7B shapes: forward 3.7 - 4.0 TB/s, step
-// 4.1 - 4.5 TB/s, about half of the 8 TB/s peak.
+// Layout: woq_group_cols.h. The slices' ranges are exact (min and max); ds and dlo are the two sums that meet in slice
+// order. Both row loops are unrolled by four for loads in flight. fp32 VALU throughout. Memory bound: the forward reads
+// w twice (the second time from L2: a workgroup's group is 32 KiB at group 128) and V once and writes W~, 10 B per
+// weight from HBM with a 16-bit output; the step reads w, V and g and writes V, 14 - 16 B per weight. Measured at the
+// Llama-2-7B shapes (profiles/r17_autoround.txt): forward 3.7 - 4.0 TB/s, step 4.1 - 4.5 TB/s, half of the 8 TB/s peak.
 // Registers (tools/kres.py), 1 / 4 / 16 slices: forward 25 / 32 / 32 VGPRs, step 48 / 52 / 52, codes 33 / 39 / 39;
 // 0 / 2 / 8 KiB LDS; eight waves per SIMD, no AGPRs, no scratch, no spills. The only fmas in the code are those of the
 // divisions.
 #include "woq_device.h"
-#include "woq_launch.h"
-#include "woq_rtn.h"
+#include "woq_group_cols.h"
 
 namespace woq {
 namespace {
-
-constexpr int AR_THREADS = 256;      // one slice: 256 columns of one group per workgroup
-constexpr int AR_SPLIT_COLS = 64;    // a split group: 64 columns per workgroup, times the slices
-constexpr int AR_MID_ROWS = 64;      // groups of at least this many rows are split over AR_MID_SLICES threads per column,
-constexpr int AR_MID_SLICES = 4;
-constexpr int AR_SPLIT_ROWS = 256;   // groups longer than this over AR_SLICES (1024 threads)
-constexpr int AR_SLICES = 16;
 
 enum { AR_FORWARD = 0, AR_STEP = 1, AR_CODES = 2 };
 
@@ -80,18 +64,18 @@ struct ArArgs {
 __device__ __forceinline__ float ar_sign(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
 template <int MODE, int SLICES>
-__global__ __launch_bounds__(SLICES == 1 ? AR_THREADS : SLICES * AR_SPLIT_COLS) void autoround_kernel(const ArArgs a) {
+__global__ __launch_bounds__(GroupCols<SLICES>::THREADS) void autoround_kernel(const ArArgs a) {
 #pragma clang fp contract(off)
-  constexpr int COLS = SLICES == 1 ? AR_THREADS : AR_SPLIT_COLS;
+  using GC = GroupCols<SLICES>;
+  constexpr int COLS = GC::COLS;
   __shared__ float red[SLICES == 1 ? 1 : 2 * SLICES * COLS];
-  const int n = blockIdx.x * COLS + threadIdx.x;
-  const int slice = SLICES == 1 ? 0 : (int)threadIdx.y;
+  const int n = GC::column();
+  const int slice = GC::slice();
   const bool valid = n < a.N;
   if (SLICES == 1 && !valid) return;  // no barrier on this path
   const size_t N = (size_t)a.N;
-  const int k0 = blockIdx.y * a.group, k1 = min(a.K, k0 + a.group);
-  const int per = (k1 - k0 + SLICES - 1) / SLICES;
-  const int r0 = min(k1, k0 + slice * per), r1 = min(k1, r0 + per);
+  const GC gc(a.K, a.group, slice);
+  const int r0 = gc.r0, r1 = gc.r1;
   const size_t cell = (size_t)blockIdx.y * N + (size_t)n;
 
   // the range: 0 belongs to it, so an empty slice is neutral
@@ -178,17 +162,10 @@ __global__ __launch_bounds__(SLICES == 1 ? AR_THREADS : SLICES * AR_SPLIT_COLS) 
     }
   }
   if constexpr (MODE == AR_STEP) {
-    if constexpr (SLICES > 1) {
-      red[slice * COLS + threadIdx.x] = ds;
-      red[(SLICES + slice) * COLS + threadIdx.x] = dlo;
-      __syncthreads();
-      if (slice != 0) return;
-      ds = 0.f, dlo = 0.f;
-      for (int i = 0; i < SLICES; ++i) {  // slice order, fixed
-        ds = ds + red[i * COLS + threadIdx.x];
-        dlo = dlo + red[(SLICES + i) * COLS + threadIdx.x];
-      }
-    }
+    GC::leave_sums(red, slice, ds, dlo);
+    if (slice != 0) return;
+    const float2 sums = GC::take_sums(red, ds, dlo);
+    ds = sums.x, dlo = sums.y;
     if (!valid) return;
     float da = 0.f, db = 0.f;
     if (!replaced) {
@@ -211,30 +188,11 @@ __global__ __launch_bounds__(SLICES == 1 ? AR_THREADS : SLICES * AR_SPLIT_COLS) 
   }
 }
 
-bool ar_dtype_ok(int dt) { return dt == WOQ_F32 || dt == WOQ_BF16 || dt == WOQ_F16; }
-
-// the shape checks every entry point shares; fills K, N, group (as the kernel takes it) and the grid
-const char* ar_shape(ArArgs& a, dim3& grid, dim3& block, int& slices) {
-  if (a.K < 1 || a.N < 1) return "bad shape";
-  if (!rtn_bits_ok(a.bits)) return "bits must be 2, 3, 4 or 8";
-  a.group = rtn_group(a.K, a.group);
-  const int n_groups = rtn_group_count(a.K, a.group);
-  if (!n_groups) return "more than 65535 groups";
-  slices = a.group > AR_SPLIT_ROWS ? AR_SLICES : (a.group >= AR_MID_ROWS ? AR_MID_SLICES : 1);
-  const int cols = slices > 1 ? AR_SPLIT_COLS : AR_THREADS;
-  grid = dim3((unsigned)((a.N + cols - 1) / cols), (unsigned)n_groups);
-  block = slices > 1 ? dim3(AR_SPLIT_COLS, slices) : dim3(AR_THREADS);
-  return nullptr;
-}
-
 template <int MODE>
-void ar_launch(const ArArgs& a, dim3 grid, dim3 block, int slices, hipStream_t st) {
-  if (slices == AR_SLICES)
-    hipLaunchKernelGGL((autoround_kernel<MODE, AR_SLICES>), grid, block, 0, st, a);
-  else if (slices == AR_MID_SLICES)
-    hipLaunchKernelGGL((autoround_kernel<MODE, AR_MID_SLICES>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((autoround_kernel<MODE, 1>), grid, block, 0, st, a);
+void ar_run(const ArArgs& a, const GroupColsPlan& p, hipStream_t st) {
+  group_cols_dispatch(p.slices, [&](auto slices) {
+    hipLaunchKernelGGL((autoround_kernel<MODE, decltype(slices)::value>), p.grid, p.block, 0, st, a);
+  });
 }
 
 }  // namespace
@@ -245,16 +203,16 @@ extern "C" int woq_autoround_forward(const float* w_dev, const float* v_dev, con
                                      int out_dtype, void* stream) {
   WOQ_TRY
   WOQ_CHECK(w_dev && v_dev && alpha_dev && beta_dev && out_dev, "QBits: autoround_forward: null tensor");
-  WOQ_CHECK(woq::ar_dtype_ok(out_dtype), "QBits: autoround_forward: the output is fp32, fp16 or bf16");
+  WOQ_CHECK(woq::fake_quant_dtype_ok(out_dtype), "QBits: autoround_forward: the output is fp32, fp16 or bf16");
+  woq::GroupColsPlan p;
+  if (const char* why = woq::group_cols_plan(K, N, group, bits, p))
+    WOQ_FAIL(std::string("QBits: autoround_forward: ") + why);
   woq::ArArgs a = {};
   a.w = w_dev, a.v = const_cast<float*>(v_dev), a.alpha = const_cast<float*>(alpha_dev);
   a.beta = const_cast<float*>(beta_dev);
-  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.K = K, a.N = N, a.group = p.group, a.bits = bits, a.asym = asym ? 1 : 0;
   a.out = out_dev, a.out_dt = out_dtype;
-  dim3 grid, block;
-  int slices;
-  if (const char* why = woq::ar_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: autoround_forward: ") + why);
-  woq::ar_launch<woq::AR_FORWARD>(a, grid, block, slices, (hipStream_t)stream);
+  woq::ar_run<woq::AR_FORWARD>(a, p, (hipStream_t)stream);
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }
@@ -264,17 +222,17 @@ extern "C" int woq_autoround_step(const float* w_dev, float* v_dev, float* alpha
                                   float* dalpha_out_dev, float* dbeta_out_dev, void* stream) {
   WOQ_TRY
   WOQ_CHECK(w_dev && v_dev && alpha_dev && beta_dev && g_dev, "QBits: autoround_step: null tensor");
-  WOQ_CHECK(woq::ar_dtype_ok(g_dtype), "QBits: autoround_step: the gradient is fp32, fp16 or bf16");
+  WOQ_CHECK(woq::fake_quant_dtype_ok(g_dtype), "QBits: autoround_step: the gradient is fp32, fp16 or bf16");
   WOQ_CHECK(lr_v >= 0.f && lr_minmax >= 0.f, "QBits: autoround_step: a learning rate is negative or not a number");
+  woq::GroupColsPlan p;
+  if (const char* why = woq::group_cols_plan(K, N, group, bits, p))
+    WOQ_FAIL(std::string("QBits: autoround_step: ") + why);
   woq::ArArgs a = {};
   a.w = w_dev, a.v = v_dev, a.alpha = alpha_dev, a.beta = beta_dev;
-  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.K = K, a.N = N, a.group = p.group, a.bits = bits, a.asym = asym ? 1 : 0;
   a.g = g_dev, a.g_dt = g_dtype, a.lr_v = lr_v, a.lr_mm = lr_minmax;
   a.dalpha = dalpha_out_dev, a.dbeta = dbeta_out_dev;
-  dim3 grid, block;
-  int slices;
-  if (const char* why = woq::ar_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: autoround_step: ") + why);
-  woq::ar_launch<woq::AR_STEP>(a, grid, block, slices, (hipStream_t)stream);
+  woq::ar_run<woq::AR_STEP>(a, p, (hipStream_t)stream);
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }
@@ -285,15 +243,15 @@ extern "C" int woq_autoround_codes(const float* w_dev, const float* v_dev, const
   WOQ_TRY
   WOQ_CHECK(w_dev && v_dev && alpha_dev && beta_dev && q_dev && scale_dev, "QBits: autoround_codes: null tensor");
   WOQ_CHECK(!asym || zp_dev, "QBits: autoround_codes: asym needs a zero-point tensor");
+  woq::GroupColsPlan p;
+  if (const char* why = woq::group_cols_plan(K, N, group, bits, p))
+    WOQ_FAIL(std::string("QBits: autoround_codes: ") + why);
   woq::ArArgs a = {};
   a.w = w_dev, a.v = const_cast<float*>(v_dev), a.alpha = const_cast<float*>(alpha_dev);
   a.beta = const_cast<float*>(beta_dev);
-  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.K = K, a.N = N, a.group = p.group, a.bits = bits, a.asym = asym ? 1 : 0;
   a.q = q_dev, a.scale = scale_dev, a.zp = zp_dev;
-  dim3 grid, block;
-  int slices;
-  if (const char* why = woq::ar_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: autoround_codes: ") + why);
-  woq::ar_launch<woq::AR_CODES>(a, grid, block, slices, (hipStream_t)stream);
+  woq::ar_run<woq::AR_CODES>(a, p, (hipStream_t)stream);
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }

@@ -5,7 +5,8 @@
 //   Q  the package's RTN at (bits, group, sym | asym): woq_rtn.h, the rule rtn_kernel (woq_pack.hip) writes blobs with
 //
 // 1. awq_scale_delta_kernel: D = diag(1 / s) Q(diag(s) W) - W for one candidate s [K] of the scale search. One thread per
-//    column and group, two passes over the group's rows (range, then codes); the loss tr(D^T H D) is the caller's, a GEMM.
+//    column and group (woq_group_cols.h, the one-slice form), two passes over the group's rows (range, then codes); the
+//    loss tr(D^T H D) is the caller's, a GEMM.
 //    Every step is rounded on its own (no contraction): the product w * s, the dequantised code * scale, the correctly
 //    rounded division by s, the subtraction. Memory bound, nothing to tune.
 //
@@ -35,13 +36,12 @@
 //    Registers (tools/kres.py), sym / asym: GROUP 128 = 217 / 221 VGPRs, 64 = 162 / 166, 32 = 97 / 93; 64 / 16 / 4 KiB
 //    LDS; no AGPRs, no scratch, no spills; the delta kernel 24 VGPRs.
 #include "woq_device.h"
-#include "woq_launch.h"
-#include "woq_rtn.h"
+#include "woq_group_cols.h"
 
 namespace woq {
 namespace {
 
-constexpr int AWQ_THREADS = 256;
+constexpr int AWQ_THREADS = GC_THREADS;  // both kernels: 256 columns of one group per workgroup
 
 // ---- 1. the scale search's delta ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(AWQ_THREADS) void awq_scale_delta_kernel(const float* __restrict__ w,
@@ -253,14 +253,11 @@ extern "C" int woq_awq_scale_delta(const float* w_dev, const float* s_dev, int K
                                    float* d_out_dev, void* stream) {
   WOQ_TRY
   WOQ_CHECK(w_dev && s_dev && d_out_dev, "QBits: awq_scale_delta: null tensor");
-  WOQ_CHECK(K >= 1 && N >= 1, "QBits: awq_scale_delta: bad shape");
-  WOQ_CHECK(woq::rtn_bits_ok(bits), "QBits: awq_scale_delta: bits must be 2, 3, 4 or 8");
-  group = woq::rtn_group(K, group);
-  const int n_groups = woq::rtn_group_count(K, group);
-  WOQ_CHECK(n_groups, "QBits: awq_scale_delta: more than 65535 groups");
-  const dim3 grid((unsigned)((N + woq::AWQ_THREADS - 1) / woq::AWQ_THREADS), (unsigned)n_groups);
-  hipLaunchKernelGGL(woq::awq_scale_delta_kernel, grid, dim3(woq::AWQ_THREADS), 0, (hipStream_t)stream, w_dev, s_dev, K,
-                     N, group, bits, asym ? 1 : 0, d_out_dev);
+  woq::GroupColsPlan p;  // the one-slice form: 256 columns of one group per workgroup
+  if (const char* why = woq::group_cols_plan(K, N, group, bits, p, false))
+    WOQ_FAIL(std::string("QBits: awq_scale_delta: ") + why);
+  hipLaunchKernelGGL(woq::awq_scale_delta_kernel, p.grid, p.block, 0, (hipStream_t)stream, w_dev, s_dev, K, N, p.group,
+                     bits, asym ? 1 : 0, d_out_dev);
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }

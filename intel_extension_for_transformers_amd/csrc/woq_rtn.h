@@ -10,6 +10,7 @@
 // gptq_sweep_kernel (woq_gptq.hip), awq_scale_delta_kernel and awq_clip_kernel (woq_awq.hip). They are correct only
 // if it is the same rule bit for bit, which is why it lives here. AutoRound's quantiser (woq_autoround.hip) is this
 // rule with V, alpha and beta put in and float clamps; it takes rtn_range from here and keeps its own expressions.
+// TEQ's quantiser (woq_teq.hip) is this rule on w a[k]; its gradient also takes from rtn_params whether s was replaced.
 // Every function turns contraction off for itself: each step is rounded on its own whatever the caller's setting.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,19 +24,24 @@ __device__ __forceinline__ RtnRange rtn_range(int bits) {
   return {(1 << (bits - 1)) - 1, (1 << bits) - 1, 1 << (bits - 1)};
 }
 
-// the rule's parameters of a group whose values span [mn, mx] with largest magnitude amax
-__device__ __forceinline__ void rtn_params(const RtnRange& r, int asym, float mx, float mn, float amax, float& s, int& z) {
+// the rule's parameters of a group whose values span [mn, mx] with largest magnitude amax -> whether the step came out
+// zero and was replaced by 1: a gradient through s (woq_teq.hip) has to know, everyone else ignores it
+__device__ __forceinline__ bool rtn_params(const RtnRange& r, int asym, float mx, float mn, float amax, float& s, int& z) {
 #pragma clang fp contract(off)
   z = 0;
+  bool replaced;
   if (!asym) {
     s = amax / (float)r.qmax;
-    if (s == 0.f) s = 1.f;
+    replaced = s == 0.f;
+    if (replaced) s = 1.f;
   } else {
     const float hi = fmaxf(mx, 0.f), lo = fminf(mn, 0.f);
     s = (hi - lo) / (float)r.levels;
-    if (s == 0.f) s = 1.f;
+    replaced = s == 0.f;
+    if (replaced) s = 1.f;
     z = max(0, min(r.levels, (int)rintf(-lo / s)));
   }
+  return replaced;
 }
 
 // v under (s, z): the rule's code, in the signed domain woq_repack_quantized_weight takes, and that code's dequantised

@@ -20,11 +20,8 @@
 //          Elo = (DLO - DS / L) w[kmin,n] on row kmin where min u < 0
 //   da[k]  = sum_n direct[k,n] + the E terms that land on row k;   a group whose s was replaced by 1 has no E
 //
-// Layout, as awq_scale_delta_kernel and autoround_kernel: a thread owns one column of one group, a range pass then a
-// main pass over the group's rows; lanes side by side along N, every row access coalesced. Groups of 64 rows and more
-// are split over 4 threads of a workgroup (64 columns x 4 slices), groups longer than 256 rows over 16, contiguous rows
-// each; the slices' ranges (exact: min, max and the first row that attains them) and the partial sums DS / DLO meet in
-// LDS and are combined in slice order.
+// Layout: woq_group_cols.h. The slices' ranges are exact (min, max and, for the gradient, the first row that attains
+// them: slice order is row order and the comparison is strict); DS and DLO are the two sums that meet in slice order.
 //
 // The reduction over the columns has no floating-point atomics and an order the layout fixes: a wave is 64 columns
 // ("column block") of some rows of one group. Per row it sums direct over its lanes with a fixed xor butterfly; lane j
@@ -42,21 +39,16 @@
 // butterfly steps, each a cross-lane read and an add, beside some forty VALU instructions per element row). Requesting
 // four rows' loads ahead of the arithmetic was measured 15 - 25 % slower (65 VGPRs, seven waves) and is not kept; a
 // reduce-scatter butterfly over several rows at once would cut the cross-lane steps about fivefold and is open.
-// Registers (tools/kres.py), 1 / 4 / 16 slices: forward 20 / 34 / 55 VGPRs, gradient 47 / 51 / 51, the final sum 15;
+// Registers (tools/kres.py), 1 / 4 / 16 slices: forward 20 / 34 / 55 VGPRs, gradient 44 / 49 / 49, the final sum 15;
 // 0 / 3 / 12 KiB LDS forward, 4 / 7 / 25 KiB gradient; eight waves per SIMD, no AGPRs, no scratch, no spills.
 #include "woq_device.h"
-#include "woq_launch.h"
-#include "woq_rtn.h"
+#include "woq_group_cols.h"
 
 namespace woq {
 namespace {
 
-constexpr int TEQ_THREADS = 256;      // one slice: 256 columns of one group per workgroup (four column blocks)
-constexpr int TEQ_WAVE = 64;          // a column block
-constexpr int TEQ_MID_ROWS = 64;      // groups of at least this many rows: TEQ_MID_SLICES threads per column,
-constexpr int TEQ_MID_SLICES = 4;
-constexpr int TEQ_SPLIT_ROWS = 256;   // groups longer than this over TEQ_SLICES (1024 threads)
-constexpr int TEQ_SLICES = 16;
+constexpr int TEQ_WAVE = 64;  // a column block: the width of the row sum's butterfly
+static_assert(GC_SPLIT_COLS == TEQ_WAVE && GC_THREADS % TEQ_WAVE == 0, "a wave is one column block of one slice");
 
 enum { TEQ_FORWARD = 0, TEQ_GRAD = 1 };
 
@@ -80,24 +72,24 @@ __device__ __forceinline__ float teq_wave_sum(float x) {
 }
 
 template <int MODE, int SLICES>
-__global__ __launch_bounds__(SLICES == 1 ? TEQ_THREADS : SLICES * TEQ_WAVE) void teq_kernel(const TeqArgs a) {
+__global__ __launch_bounds__(GroupCols<SLICES>::THREADS) void teq_kernel(const TeqArgs a) {
 #pragma clang fp contract(off)
-  constexpr int COLS = SLICES == 1 ? TEQ_THREADS : TEQ_WAVE;
+  using GC = GroupCols<SLICES>;
+  constexpr int COLS = GC::COLS;
   constexpr bool GRAD = MODE == TEQ_GRAD;
   __shared__ float red[SLICES == 1 ? 1 : 3 * SLICES * COLS];
   __shared__ int redk[(SLICES == 1 || !GRAD) ? 1 : 3 * SLICES * COLS];
   __shared__ float ent_e[GRAD ? 2 * COLS : 1];
   __shared__ int ent_k[GRAD ? 2 * COLS : 1];
-  const int n = blockIdx.x * COLS + threadIdx.x;
+  const int n = GC::column();
   const int lane = threadIdx.x & (TEQ_WAVE - 1);
-  const int slice = SLICES == 1 ? 0 : (int)threadIdx.y;
+  const int slice = GC::slice();
   const bool valid = n < a.N;
   const bool wave_live = n - lane < a.N;  // the wave's column block exists
   if (!GRAD && SLICES == 1 && !valid) return;  // no barrier and no cross-lane sum on this path
   const size_t N = (size_t)a.N;
-  const int k0 = blockIdx.y * a.group, k1 = min(a.K, k0 + a.group);
-  const int per = (k1 - k0 + SLICES - 1) / SLICES;
-  const int r0 = min(k1, k0 + slice * per), r1 = min(k1, r0 + per);
+  const GC gc(a.K, a.group, slice);
+  const int r0 = gc.r0, r1 = gc.r1;
 
   // the range of u: 0 belongs to it, so an empty slice is neutral; a row index stays -1 where nothing exceeds 0
   float mn = 0.f, mx = 0.f, amax = 0.f;
@@ -145,7 +137,7 @@ __global__ __launch_bounds__(SLICES == 1 ? TEQ_THREADS : SLICES * TEQ_WAVE) void
   const RtnRange r = rtn_range(a.bits);
   float s;
   int z;
-  rtn_params(r, a.asym, mx, mn, amax, s, z);
+  const bool dead = rtn_params(r, a.asym, mx, mn, amax, s, z);  // no gradient through a step that is not s
 
   if constexpr (!GRAD) {
     if (valid)
@@ -157,8 +149,6 @@ __global__ __launch_bounds__(SLICES == 1 ? TEQ_THREADS : SLICES * TEQ_WAVE) void
         store_f32(a.out, i, a.out_dt, rtn_deq(r, a.asym, u, s, z) / ak);
       }
   } else {
-    // rtn_params' own expressions: whether it replaced a zero step by 1
-    const bool dead = a.asym ? (fmaxf(mx, 0.f) - fminf(mn, 0.f)) / (float)r.levels == 0.f : amax / (float)r.qmax == 0.f;
     const float zf = a.asym ? -fminf(mn, 0.f) / s : 0.f;
     const float cmin = a.asym ? 0.f : (float)-r.off, cmax = a.asym ? (float)r.levels : (float)r.qmax;
     const int cb = (n - lane) / TEQ_WAVE;
@@ -195,19 +185,10 @@ __global__ __launch_bounds__(SLICES == 1 ? TEQ_THREADS : SLICES * TEQ_WAVE) void
       if ((j == TEQ_WAVE - 1 || k == r1 - 1) && wave_live && lane <= j) part[k - j + lane] = keep;
     }
 
-    if constexpr (SLICES > 1) {
-      red[slice * COLS + threadIdx.x] = ds;
-      red[(SLICES + slice) * COLS + threadIdx.x] = dlo;
-      __syncthreads();
-    }
+    GC::leave_sums(red, slice, ds, dlo);
     if (slice == 0) {
-      if constexpr (SLICES > 1) {
-        ds = 0.f, dlo = 0.f;
-        for (int i = 0; i < SLICES; ++i) {  // slice order, fixed
-          ds = ds + red[i * COLS + threadIdx.x];
-          dlo = dlo + red[(SLICES + i) * COLS + threadIdx.x];
-        }
-      }
+      const float2 sums = GC::take_sums(red, ds, dlo);
+      ds = sums.x, dlo = sums.y;
       float e0 = 0.f, e1 = 0.f;
       int ka = -1, kb = -1;
       if (valid && !dead) {
@@ -242,10 +223,10 @@ __global__ __launch_bounds__(SLICES == 1 ? TEQ_THREADS : SLICES * TEQ_WAVE) void
 }
 
 // da[k] = sum of partial[cb][k] in column-block order
-__global__ __launch_bounds__(TEQ_THREADS) void teq_sum_kernel(const float* __restrict__ partial, int n_blocks, int K,
+__global__ __launch_bounds__(GC_THREADS) void teq_sum_kernel(const float* __restrict__ partial, int n_blocks, int K,
                                                              float* __restrict__ da) {
 #pragma clang fp contract(off)
-  const int k = blockIdx.x * TEQ_THREADS + threadIdx.x;
+  const int k = blockIdx.x * GC_THREADS + threadIdx.x;
   if (k >= K) return;
   float acc = 0.f;
 #pragma unroll 4
@@ -253,30 +234,11 @@ __global__ __launch_bounds__(TEQ_THREADS) void teq_sum_kernel(const float* __res
   da[k] = acc;
 }
 
-bool teq_dtype_ok(int dt) { return dt == WOQ_F32 || dt == WOQ_BF16 || dt == WOQ_F16; }
-
-// the shape checks both entry points share; fills group (as the kernel takes it) and the grid
-const char* teq_shape(TeqArgs& a, dim3& grid, dim3& block, int& slices) {
-  if (a.K < 1 || a.N < 1) return "bad shape";
-  if (!rtn_bits_ok(a.bits)) return "bits must be 2, 3, 4 or 8";
-  a.group = rtn_group(a.K, a.group);
-  const int n_groups = rtn_group_count(a.K, a.group);
-  if (!n_groups) return "more than 65535 groups";
-  slices = a.group > TEQ_SPLIT_ROWS ? TEQ_SLICES : (a.group >= TEQ_MID_ROWS ? TEQ_MID_SLICES : 1);
-  const int cols = slices > 1 ? TEQ_WAVE : TEQ_THREADS;
-  grid = dim3((unsigned)((a.N + cols - 1) / cols), (unsigned)n_groups);
-  block = slices > 1 ? dim3(TEQ_WAVE, slices) : dim3(TEQ_THREADS);
-  return nullptr;
-}
-
 template <int MODE>
-void teq_launch(const TeqArgs& a, dim3 grid, dim3 block, int slices, hipStream_t st) {
-  if (slices == TEQ_SLICES)
-    hipLaunchKernelGGL((teq_kernel<MODE, TEQ_SLICES>), grid, block, 0, st, a);
-  else if (slices == TEQ_MID_SLICES)
-    hipLaunchKernelGGL((teq_kernel<MODE, TEQ_MID_SLICES>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((teq_kernel<MODE, 1>), grid, block, 0, st, a);
+void teq_run(const TeqArgs& a, const GroupColsPlan& p, hipStream_t st) {
+  group_cols_dispatch(p.slices, [&](auto slices) {
+    hipLaunchKernelGGL((teq_kernel<MODE, decltype(slices)::value>), p.grid, p.block, 0, st, a);
+  });
 }
 
 }  // namespace
@@ -286,15 +248,14 @@ extern "C" int woq_teq_forward(const float* w_dev, const float* a_dev, int K, in
                                void* out_dev, int out_dtype, void* stream) {
   WOQ_TRY
   WOQ_CHECK(w_dev && a_dev && out_dev, "QBits: teq_forward: null tensor");
-  WOQ_CHECK(woq::teq_dtype_ok(out_dtype), "QBits: teq_forward: the output is fp32, fp16 or bf16");
+  WOQ_CHECK(woq::fake_quant_dtype_ok(out_dtype), "QBits: teq_forward: the output is fp32, fp16 or bf16");
+  woq::GroupColsPlan p;
+  if (const char* why = woq::group_cols_plan(K, N, group, bits, p)) WOQ_FAIL(std::string("QBits: teq_forward: ") + why);
   woq::TeqArgs a = {};
   a.w = w_dev, a.a = a_dev;
-  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.K = K, a.N = N, a.group = p.group, a.bits = bits, a.asym = asym ? 1 : 0;
   a.out = out_dev, a.out_dt = out_dtype;
-  dim3 grid, block;
-  int slices;
-  if (const char* why = woq::teq_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: teq_forward: ") + why);
-  woq::teq_launch<woq::TEQ_FORWARD>(a, grid, block, slices, (hipStream_t)stream);
+  woq::teq_run<woq::TEQ_FORWARD>(a, p, (hipStream_t)stream);
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }
@@ -303,23 +264,22 @@ extern "C" int woq_teq_grad(const float* w_dev, const float* a_dev, const void* 
                             int group, int bits, int asym, float* da_dev, void* stream) {
   WOQ_TRY
   WOQ_CHECK(w_dev && a_dev && g_dev && da_dev, "QBits: teq_grad: null tensor");
-  WOQ_CHECK(woq::teq_dtype_ok(g_dtype), "QBits: teq_grad: the gradient is fp32, fp16 or bf16");
+  WOQ_CHECK(woq::fake_quant_dtype_ok(g_dtype), "QBits: teq_grad: the gradient is fp32, fp16 or bf16");
+  woq::GroupColsPlan p;
+  if (const char* why = woq::group_cols_plan(K, N, group, bits, p)) WOQ_FAIL(std::string("QBits: teq_grad: ") + why);
   woq::TeqArgs a = {};
   a.w = w_dev, a.a = a_dev;
-  a.K = K, a.N = N, a.group = group, a.bits = bits, a.asym = asym ? 1 : 0;
+  a.K = K, a.N = N, a.group = p.group, a.bits = bits, a.asym = asym ? 1 : 0;
   a.g = g_dev, a.g_dt = g_dtype;
-  dim3 grid, block;
-  int slices;
-  if (const char* why = woq::teq_shape(a, grid, block, slices)) WOQ_FAIL(std::string("QBits: teq_grad: ") + why);
   hipStream_t st = (hipStream_t)stream;
   const int n_blocks = (N + woq::TEQ_WAVE - 1) / woq::TEQ_WAVE;
   const size_t bytes = (size_t)n_blocks * (size_t)K * sizeof(float);
   bool own = false;
   a.partial = (float*)woq::scratch_take(bytes, st, &own);
   WOQ_CHECK(a.partial != nullptr, "QBits: teq_grad: scratch allocation failed");
-  woq::teq_launch<woq::TEQ_GRAD>(a, grid, block, slices, st);
-  hipLaunchKernelGGL(woq::teq_sum_kernel, dim3((unsigned)((K + woq::TEQ_THREADS - 1) / woq::TEQ_THREADS)),
-                     dim3(woq::TEQ_THREADS), 0, st, a.partial, n_blocks, K, da_dev);
+  woq::teq_run<woq::TEQ_GRAD>(a, p, st);
+  hipLaunchKernelGGL(woq::teq_sum_kernel, dim3((unsigned)((K + woq::GC_THREADS - 1) / woq::GC_THREADS)),
+                     dim3(woq::GC_THREADS), 0, st, a.partial, n_blocks, K, da_dev);
   const hipError_t e = hipGetLastError();
   woq::scratch_release(a.partial, bytes, own, st);
   WOQ_HIP(e);

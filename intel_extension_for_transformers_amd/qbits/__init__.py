@@ -124,6 +124,13 @@ def quantize_to_packed_weight(fp32_weight, transpose, blocksize, compute_type, w
     return out
 
 
+def rtn_groups(k, group):
+    """csrc/woq_rtn.h's rtn_group / rtn_group_count for K = k: (the group size as the kernels take it: <= 0 or > K means
+    one group per column; the number of groups, the last may be short)"""
+    g = k if group <= 0 or group > k else group
+    return g, (k + g - 1) // g
+
+
 def gptq_sweep(w, u, c0, rows, group, bits, asym, q, scale, zp, err, params_given=False, col_group=None):
     """The sequential sweep of GPTQ over one block of `rows` <= 128 input features starting at c0 (woq_gptq_sweep,
     csrc/woq_gptq.hip; no reference counterpart). In place on the caller's device tensors: w fp32 [K, N] (working order,
@@ -131,8 +138,7 @@ def gptq_sweep(w, u, c0, rows, group, bits, asym, q, scale, zp, err, params_give
     (sym), err fp32 [>= rows, N]; q / scale / zp in the domain `repack_quantized_weight` takes. params_given: scale / zp
     are read (static groups); col_group int32 [K]: the group of every working row, None = row // group."""
     k, n = w.shape
-    g = k if group <= 0 or group > k else group
-    n_groups = (k + g - 1) // g
+    n_groups = rtn_groups(k, group)[1]
 
     def ok(t, dtype, shape):
         return t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape
@@ -173,7 +179,7 @@ def awq_clip_search(w, h, group, bits, asym, n_grid=20, n_cand=10, w_out=None, l
     d = Q(clamped) - w and G the group's diagonal block of h fp32 [K, K] (symmetric; a view with unit column stride is fine).
     group: 32, 64 or 128. -> (best int32 [G, N], losses fp32 [n_cand, G, N], w_out fp32 [K, N] = w clamped by best)."""
     k, n = w.shape
-    g = (k + group - 1) // group if group > 0 else 0
+    g = rtn_groups(k, group)[1]
     if w_out is None:
         w_out = torch.empty_like(w)
     if not (_f32_dev(w, (k, n)) and _f32_dev(w_out, (k, n)) and h.is_cuda and h.dtype == torch.float32
@@ -196,8 +202,7 @@ def _autoround_args(name, w, v, alpha, beta, group):
     if w.dim() != 2:
         raise RuntimeError("QBits: %s: w must be [K,N]" % name)
     k, n = w.shape
-    g = k if group <= 0 or group > k else group
-    n_groups = (k + g - 1) // g
+    n_groups = rtn_groups(k, group)[1]
     if not (_f32_dev(w, (k, n)) and _f32_dev(v, (k, n)) and _f32_dev(alpha, (n_groups, n))
             and _f32_dev(beta, (n_groups, n))):
         raise RuntimeError("QBits: %s takes contiguous fp32 device tensors w [K,N], v [K,N], alpha [G,N], beta [G,N]"
@@ -205,7 +210,7 @@ def _autoround_args(name, w, v, alpha, beta, group):
     return k, n, n_groups
 
 
-_AUTOROUND_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+_FAKE_QUANT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)  # of a W~ and of its gradient
 
 
 def autoround_forward(w, v, alpha, beta, group, bits, asym, out=None, dtype=None):
@@ -216,7 +221,7 @@ def autoround_forward(w, v, alpha, beta, group, bits, asym, out=None, dtype=None
     k, n, _ = _autoround_args("autoround_forward", w, v, alpha, beta, group)
     if out is None:
         out = torch.empty(k, n, dtype=dtype or torch.float32, device=w.device)
-    if not (out.is_cuda and out.dtype in _AUTOROUND_DTYPES and out.is_contiguous() and tuple(out.shape) == (k, n)):
+    if not (out.is_cuda and out.dtype in _FAKE_QUANT_DTYPES and out.is_contiguous() and tuple(out.shape) == (k, n)):
         raise RuntimeError("QBits: autoround_forward: out must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
     L.check(L.lib().woq_autoround_forward(_ptr(w), _ptr(v), _ptr(alpha), _ptr(beta), k, n, int(group), int(bits),
                                           int(bool(asym)), _ptr(out), L.torch_dtype_code(out.dtype), L.stream_ptr()))
@@ -229,7 +234,7 @@ def autoround_step(w, v, alpha, beta, g, group, bits, asym, lr_v, lr_minmax, dal
     and p <- clamp(p - lr sign(grad)) applied in place to v (lr_v, kept in [-0.5, 0.5]) and alpha / beta (lr_minmax, kept
     in [0, 1]). dalpha / dbeta: optional fp32 [G, N] outputs for the raw gradients."""
     k, n, n_groups = _autoround_args("autoround_step", w, v, alpha, beta, group)
-    if not (g.is_cuda and g.dtype in _AUTOROUND_DTYPES and g.is_contiguous() and tuple(g.shape) == (k, n)):
+    if not (g.is_cuda and g.dtype in _FAKE_QUANT_DTYPES and g.is_contiguous() and tuple(g.shape) == (k, n)):
         raise RuntimeError("QBits: autoround_step: g must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
     for t in (dalpha, dbeta):
         if t is not None and not _f32_dev(t, (n_groups, n)):
@@ -270,7 +275,7 @@ def teq_forward(w, a, group, bits, asym, out=None, dtype=None):
     k, n = _teq_args("teq_forward", w, a)
     if out is None:
         out = torch.empty(k, n, dtype=dtype or torch.float32, device=w.device)
-    if not (out.is_cuda and out.dtype in _AUTOROUND_DTYPES and out.is_contiguous() and tuple(out.shape) == (k, n)):
+    if not (out.is_cuda and out.dtype in _FAKE_QUANT_DTYPES and out.is_contiguous() and tuple(out.shape) == (k, n)):
         raise RuntimeError("QBits: teq_forward: out must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
     L.check(L.lib().woq_teq_forward(_ptr(w), _ptr(a), k, n, int(group), int(bits), int(bool(asym)), _ptr(out),
                                     L.torch_dtype_code(out.dtype), L.stream_ptr()))
@@ -282,7 +287,7 @@ def teq_grad(w, a, g, group, bits, asym, out=None):
     the forward is recomputed, rounding is straight-through, a group's max / min pass to the row that attains them.
     Deterministic: the same inputs give the same bytes. Returns `out` (overwritten; allocated when None)."""
     k, n = _teq_args("teq_grad", w, a)
-    if not (g.is_cuda and g.dtype in _AUTOROUND_DTYPES and g.is_contiguous() and tuple(g.shape) == (k, n)):
+    if not (g.is_cuda and g.dtype in _FAKE_QUANT_DTYPES and g.is_contiguous() and tuple(g.shape) == (k, n)):
         raise RuntimeError("QBits: teq_grad: g must be a contiguous fp32 / fp16 / bf16 device tensor [K,N]")
     if out is None:
         out = torch.empty(k, dtype=torch.float32, device=w.device)

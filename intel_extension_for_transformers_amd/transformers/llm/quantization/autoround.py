@@ -23,13 +23,11 @@ import logging
 import torch
 
 from .... import qbits
-from .calibration import (BITS, block_linears, calibration_batches, capture_block_inputs, check_request,
-                          decoder_blocks, fp32_matmul, install_quantized, next_inputs, run_block, weight_kn)
+from .calibration import (BITS, DEFAULT_BATCH, SEED, block_linears, calibration_batches, capture_block_inputs,
+                          check_request, decoder_blocks, fake_quant_dtype, fake_quant_forward, fp32_matmul,
+                          install_quantized, next_inputs, run_block, train_block, weight_kn)
 
 logger = logging.getLogger(__name__)
-
-SEED = 42  # of the minibatch draw
-DEFAULT_BATCH = 8
 
 
 def validate_autoround_request(model, config):
@@ -57,11 +55,10 @@ class _Quantiser:
     def __init__(self, module, group, bits, asym, dtype):
         self.w = w = weight_kn(module)
         k, n = w.shape
-        g = k if group <= 0 or group > k else group
         self.group, self.bits, self.asym, self.dtype = group, bits, asym, dtype
         # V is the tensor autograd sees (FakeQuant needs an input that requires grad); it never receives one
         self.v = torch.zeros(k, n, dtype=torch.float32, device=w.device).requires_grad_(True)
-        self.alpha = torch.ones((k + g - 1) // g, n, dtype=torch.float32, device=w.device)
+        self.alpha = torch.ones(qbits.rtn_groups(k, group)[1], n, dtype=torch.float32, device=w.device)
         self.beta = torch.ones_like(self.alpha)
         self.bias = module.bias.data if module.bias is not None else None
         self.lr_v = self.lr_mm = 0.0
@@ -88,63 +85,16 @@ class FakeQuant(torch.autograd.Function):
         return None, None
 
 
-def _wrap(module, q):
-    def forward(x):
-        y = x.matmul(q.wq)
-        return y + q.bias if q.bias is not None else y
+def block_trainer(quantisers, iters, lr, minmax_lr):
+    """what calibration.train_block runs around its loss -> (begin_step, after_backward, snapshot). begin_step sets the
+    iteration's rates and builds every W~; the SignSGD step itself is FakeQuant's backward, nothing is left for after."""
+    def begin_step(t):
+        for q in quantisers:
+            q.lr_v, q.lr_mm = schedule(lr, t, iters), schedule(minmax_lr, t, iters)
+            q.wq = FakeQuant.apply(q.v, q)
+        return quantisers
 
-    module.forward = forward
-
-
-def _samples(unit):
-    args, kwargs = unit
-    x = args[0] if args else kwargs["hidden_states"]
-    return int(x.shape[0])
-
-
-def draw_minibatch(inputs, batch_size, gen):
-    """the indices of one minibatch: whole batches in a random order until `batch_size` samples are reached"""
-    picked, count = [], 0
-    for i in torch.randperm(len(inputs), generator=gen).tolist():
-        picked.append(i)
-        count += _samples(inputs[i])
-        if count >= batch_size:
-            break
-    return picked
-
-
-def _train_block(block, quantisers, inputs, targets, iters, lr, minmax_lr, batch_size, gen):
-    """`iters` SignSGD iterations on one block -> (rtn_loss, best_loss, best_iter, best parameters per linear)"""
-    best, best_loss, best_iter, rtn_loss = None, None, -1, None
-    flags = [(p, p.requires_grad) for p in block.parameters()]
-    for p, _ in flags:
-        p.requires_grad_(False)
-    try:
-        with torch.enable_grad():
-            for t in range(iters):
-                picked = draw_minibatch(inputs, batch_size, gen)
-                for q in quantisers:
-                    q.lr_v, q.lr_mm = schedule(lr, t, iters), schedule(minmax_lr, t, iters)
-                    q.wq = FakeQuant.apply(q.v, q)
-                total = sum(targets[i].numel() for i in picked)
-                loss = 0.0
-                for i in picked:
-                    y = run_block(block, [inputs[i]])[0]
-                    loss = loss + (y.float() - targets[i].float()).square().sum()
-                loss = loss / total
-                value = float(loss.detach())
-                if t == 0:
-                    rtn_loss = value
-                if best_loss is None or value < best_loss:  # before the update: these parameters gave this loss
-                    best_loss, best_iter = value, t
-                    best = [q.params() for q in quantisers]
-                loss.backward()
-                for q in quantisers:
-                    q.wq = None
-    finally:
-        for p, flag in flags:
-            p.requires_grad_(flag)
-    return rtn_loss, best_loss, best_iter, best
+    return begin_step, lambda t: None, lambda: [q.params() for q in quantisers]
 
 
 @torch.no_grad()
@@ -176,18 +126,14 @@ def autoround_quantize_model(model, config, device="cuda"):
             where = "%s.%d" % (path, li)
             linears = block_linears(block, where, skip)
             targets = run_block(block, inputs)
-            dtype = targets[0].dtype if targets[0].dtype in (torch.float16, torch.bfloat16) else torch.float32
+            dtype = fake_quant_dtype(targets)
             quantisers = [_Quantiser(m, config.group_size, bits, asym, dtype) for _, m in linears]
             entry = (None, None, -1)
             if iters > 0 and quantisers:
-                for (_, m), q in zip(linears, quantisers):
-                    _wrap(m, q)
-                try:
-                    rtn_loss, best_loss, best_iter, best = _train_block(block, quantisers, q_inputs, targets, iters, lr,
-                                                                        minmax_lr, batch_size, gen)
-                finally:
-                    for _, m in linears:
-                        del m.forward
+                with fake_quant_forward(linears, quantisers):
+                    rtn_loss, best_loss, best_iter, best = train_block(
+                        block, q_inputs, targets, iters, batch_size, gen,
+                        *block_trainer(quantisers, iters, lr, minmax_lr))
                 entry = (rtn_loss, best_loss, best_iter)
                 logger.info("AutoRound %s: loss %.6g at iteration %d (RTN %.6g)", where, best_loss, best_iter, rtn_loss)
             else:

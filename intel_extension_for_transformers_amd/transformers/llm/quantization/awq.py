@@ -23,40 +23,28 @@ import logging
 import torch
 
 from .... import qbits
-from .calibration import (BITS, block_linears, calibration_batches, capture_block_inputs, check_request,
-                          collect_input_stats, decoder_blocks, fp32_matmul, install_quantized, next_inputs, run_block,
-                          weight_kn)
+from .calibration import (ABSORB_GROUPS, BITS, SCALE_MODEL_TYPES, absorb_groups, block_linears, calibration_batches,
+                          capture_block_inputs, check_request, collect_input_stats, decoder_blocks, fp32_matmul,
+                          install_quantized, model_type, next_inputs, run_block, weight_kn)
 
 logger = logging.getLogger(__name__)
 
 N_GRID = 20  # candidates of the scale search, r_i = i / N_GRID; the clip search's c_j = 1 - j / N_GRID
 N_CLIP = 10  # candidates of the clip search
 CLIP_GROUPS = (32, 64, 128)  # the group sizes whose Gram block the clip kernel keeps in LDS
-SCALE_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")  # the attribute layout the scale folding knows
 _NO_CLIP = ("q_proj", "k_proj")
 
-# absorb groups of a Llama-class block: (the scaled linears, the op that absorbs 1 / s)
-_GROUPS = (
-    (("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "input_layernorm"),
-    (("self_attn.o_proj",), "self_attn.v_proj"),
-    (("mlp.gate_proj", "mlp.up_proj"), "post_attention_layernorm"),
-    (("mlp.down_proj",), "mlp.up_proj"),
-)
 # linears of such a block that see the same input tensor as another: the statistics are taken once
 _SAME_INPUT = {"self_attn.k_proj": "self_attn.q_proj", "self_attn.v_proj": "self_attn.q_proj",
                "mlp.up_proj": "mlp.gate_proj"}
 
 
-def _model_type(model):
-    return getattr(getattr(model, "config", None), "model_type", None) or type(model).__name__
-
-
 def validate_awq_request(model, config):
     """Everything about a request that can be refused without touching a device."""
     check_request(model, config, "AWQ", ("use_double_quant", "layer_wise"))
-    if config.auto_scale and _model_type(model) not in SCALE_MODEL_TYPES:
+    if config.auto_scale and model_type(model) not in SCALE_MODEL_TYPES:
         raise NotImplementedError("AWQ auto_scale folds scales into Llama-class blocks (model_type %s), not model type "
-                                  "%s: use auto_scale=False" % (" / ".join(SCALE_MODEL_TYPES), _model_type(model)))
+                                  "%s: use auto_scale=False" % (" / ".join(SCALE_MODEL_TYPES), model_type(model)))
     if config.auto_clip and config.group_size not in CLIP_GROUPS:
         raise NotImplementedError("AWQ auto_clip keeps a group's Gram block on chip and takes group_size 32, 64 or 128, "
                                   "not group_size=%s: use auto_clip=False" % config.group_size)
@@ -101,35 +89,10 @@ def fold_scale(block, names, prev, s):
 
 
 def apply_scales(block, scales):
-    """`scales` {group index: s}: fold every searched scale of a block in (see _GROUPS)"""
+    """`scales` {group index: s}: fold every searched scale of a block in (see ABSORB_GROUPS)"""
     for gi, s in scales.items():
-        names, prev = _GROUPS[gi]
+        names, prev = ABSORB_GROUPS[gi]
         fold_scale(block, names, prev, s)
-
-
-def _scale_groups(block, linears, where, method="AWQ"):
-    """the absorb groups of this block that can be searched: every member among `linears`; a group whose producing op
-    is a linear only where that linear's outputs are the group's inputs one to one (o_proj after v_proj: not under
-    grouped-query attention, AutoAWQ's rule). `method` names the caller in the log lines (teq.py shares the rule)."""
-    have = {name for name, _ in linears}
-    out = []
-    for gi, (names, prev) in enumerate(_GROUPS):
-        if not all(n in have for n in names):
-            logger.info("%s %s: absorb group %s skipped (not every linear is quantised)", method, where,
-                        "/".join(names))
-            continue
-        p = block.get_submodule(prev)
-        if isinstance(p, torch.nn.Linear):
-            if prev not in have:
-                logger.info("%s %s: absorb group %s skipped (%s is not quantised)", method, where, names[0], prev)
-                continue
-            if p.out_features != block.get_submodule(names[0]).in_features:
-                # AutoAWQ compares the two weights' shapes, the same test wherever heads * head_dim = hidden
-                logger.info("%s %s: %s scale skipped (grouped-query attention: %s has %d outputs for %d inputs)",
-                            method, where, names[0], prev, p.out_features, block.get_submodule(names[0]).in_features)
-                continue
-        out.append(gi)
-    return out
 
 
 @torch.no_grad()
@@ -146,7 +109,7 @@ def awq_quantize_model(model, config, device="cuda"):
     bits = BITS[config.weight_dtype]
     asym = not bool(config.sym)
     group = config.group_size
-    llama = _model_type(model) in SCALE_MODEL_TYPES
+    llama = model_type(model) in SCALE_MODEL_TYPES
     model.to(device)
     model.eval()
     inputs = capture_block_inputs(model, blocks, batches, device)
@@ -166,8 +129,8 @@ def awq_quantize_model(model, config, device="cuda"):
             in_scale = {}
             if config.auto_scale:
                 scales = {}
-                for gi in _scale_groups(block, linears, where):
-                    names = _GROUPS[gi][0]
+                for gi in absorb_groups(block, linears, where, "AWQ"):
+                    names = ABSORB_GROUPS[gi][0]
                     src = source[names[0]]
                     best, s, losses = search_scale([weight_kn(block.get_submodule(n)) for n in names], gram[src],
                                                    asum[src], group, bits, asym)

@@ -1,9 +1,12 @@
 """What the calibrated methods (gptq.py, awq.py, autoround.py, teq.py) share: the request checks, the calibration
 batches, the walk down the decoder blocks (the first block's inputs as the model itself calls it, a block run over them, the next
-block's inputs), the per-linear input statistics from forward hooks, and the swap of a linear for its
-QuantizedLinearQBits. Plain functions; every method keeps its own loop over the blocks.
+block's inputs), the per-linear input statistics from forward hooks, the absorb groups of a Llama-class block (AWQ, TEQ),
+the block-by-block training of a fake quantiser (AutoRound, TEQ: the minibatch draw, the wrap of the linears, the loop)
+and the swap of a linear for its QuantizedLinearQBits. Plain functions; every method keeps its own loop over the blocks,
+and no method file imports from another.
 """
 import contextlib
+import logging
 
 import torch
 
@@ -11,6 +14,8 @@ from .nn.modules import QuantizedLinearQBits
 
 WNAME = {4: "int4_clip", 8: "int8", 3: "int3_clip", 2: "int2_clip"}
 BITS = {name: bits for bits, name in WNAME.items()}
+
+_log = logging.getLogger(__name__)
 
 _NOT_PART = " calibration is not part of the MI355X hot path without calibration data (dataset=%r is not downloaded)"
 _NO_DATA = {"GPTQ": "GPTQ calibration does not download datasets (dataset=%r)", "AWQ": "AwqConfig" + _NOT_PART,
@@ -200,6 +205,128 @@ def collect_input_stats(block, linears, inputs, source=None, abs_sum=False):
         for hk in hooks:
             hk.remove()
     return xtx, asum, count
+
+
+# ---- the absorb groups of a Llama-class block (AWQ's scales, TEQ's trainable scales) ----------------------------------
+SCALE_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")  # the attribute layout the scale folding knows
+
+# (the scaled linears: they share an input; the op that produces it and absorbs 1 / s)
+ABSORB_GROUPS = (
+    (("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "input_layernorm"),
+    (("self_attn.o_proj",), "self_attn.v_proj"),
+    (("mlp.gate_proj", "mlp.up_proj"), "post_attention_layernorm"),
+    (("mlp.down_proj",), "mlp.up_proj"),
+)
+
+
+def model_type(model):
+    return getattr(getattr(model, "config", None), "model_type", None) or type(model).__name__
+
+
+def absorb_groups(block, linears, where, method):
+    """the absorb groups of this block that can take a scale (indices into ABSORB_GROUPS): every member among `linears`;
+    a group whose producing op is a linear only where that linear's outputs are the group's inputs one to one (o_proj
+    after v_proj: not under grouped-query attention, AutoAWQ's rule). `method` (AWQ, TEQ) names the caller in the log
+    lines, which go to its file's logger."""
+    logger = logging.getLogger("%s.%s" % (__package__, method.lower()))
+    have = {name for name, _ in linears}
+    out = []
+    for gi, (names, prev) in enumerate(ABSORB_GROUPS):
+        if not all(n in have for n in names):
+            logger.info("%s %s: absorb group %s skipped (not every linear is quantised)", method, where,
+                        "/".join(names))
+            continue
+        p = block.get_submodule(prev)
+        if isinstance(p, torch.nn.Linear):
+            if prev not in have:
+                logger.info("%s %s: absorb group %s skipped (%s is not quantised)", method, where, names[0], prev)
+                continue
+            if p.out_features != block.get_submodule(names[0]).in_features:
+                # AutoAWQ compares the two weights' shapes, the same test wherever heads * head_dim = hidden
+                logger.info("%s %s: %s scale skipped (grouped-query attention: %s has %d outputs for %d inputs)",
+                            method, where, names[0], prev, p.out_features, block.get_submodule(names[0]).in_features)
+                continue
+        out.append(gi)
+    return out
+
+
+# ---- training a fake quantiser block by block (AutoRound, TEQ) --------------------------------------------------------
+SEED = 42  # of the minibatch draw
+DEFAULT_BATCH = 8
+
+
+def _samples(unit):
+    args, kwargs = unit
+    x = args[0] if args else kwargs["hidden_states"]
+    return int(x.shape[0])
+
+
+def draw_minibatch(inputs, batch_size, gen):
+    """the indices of one minibatch: whole batches in a random order until `batch_size` samples are reached"""
+    picked, count = [], 0
+    for i in torch.randperm(len(inputs), generator=gen).tolist():
+        picked.append(i)
+        count += _samples(inputs[i])
+        if count >= batch_size:
+            break
+    return picked
+
+
+def fake_quant_dtype(outs):
+    """the dtype of a W~: the block output's where that is fp16 or bf16, else fp32"""
+    return outs[0].dtype if outs[0].dtype in (torch.float16, torch.bfloat16) else torch.float32
+
+
+@contextlib.contextmanager
+def fake_quant_forward(linears, quantisers):
+    """Inside, every linear of `linears` [(name, module)] computes x.matmul(q.wq) + q.bias with its quantiser q (same
+    order): an instance `forward`, removed on any exit."""
+    for (_, m), q in zip(linears, quantisers):
+        m.forward = lambda x, q=q: x.matmul(q.wq) if q.bias is None else x.matmul(q.wq) + q.bias
+    try:
+        yield
+    finally:
+        for _, m in linears:
+            del m.forward
+
+
+def train_block(block, inputs, targets, steps, batch_size, gen, begin_step, after_backward, snapshot):
+    """`steps` training steps of one block's fake quantisers (its linears inside fake_quant_forward) against `targets`,
+    the fp block's outputs -> (first_loss, best_loss, best_step, best_snapshot). Per step t: one draw_minibatch;
+    begin_step(t) sets the rates, builds the W~ (q.wq) of the trained quantisers and returns them; the mean squared error
+    over the picked batches; snapshot() is kept at the lowest loss so far (before the update: these parameters gave this
+    loss; a tie keeps the earlier step); backward(); after_backward(t) does what the quantisers' own backward left of the
+    update; the W~ built this step are dropped. The block's parameters are frozen inside and restored on any exit."""
+    best, best_loss, best_step, first_loss = None, None, -1, None
+    flags = [(p, p.requires_grad) for p in block.parameters()]
+    for p, _ in flags:
+        p.requires_grad_(False)
+    try:
+        with torch.enable_grad():
+            for t in range(steps):
+                picked = draw_minibatch(inputs, batch_size, gen)
+                rebuilt = begin_step(t)
+                total = sum(targets[i].numel() for i in picked)
+                loss = 0.0
+                for i in picked:
+                    y = run_block(block, [inputs[i]])[0]
+                    loss = loss + (y.float() - targets[i].float()).square().sum()
+                loss = loss / total
+                value = float(loss.detach())
+                _log.debug("step %d: batches %s, loss %.9g", t, picked, value)
+                if t == 0:
+                    first_loss = value
+                if best_loss is None or value < best_loss:
+                    best_loss, best_step = value, t
+                    best = snapshot()
+                loss.backward()
+                after_backward(t)
+                for q in rebuilt:
+                    q.wq = None
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
+    return first_loss, best_loss, best_step, best
 
 
 # ---- the result -------------------------------------------------------------------------------------------------------

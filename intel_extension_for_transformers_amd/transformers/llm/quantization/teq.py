@@ -2,15 +2,15 @@
 
 The reference hands this step to neural_compressor's TEQuantizer (external); here the method (Cheng et al. 2023, "TEQ:
 Trainable Equivalent Transformation for Quantization of LLMs") is restated — tests/teq_reference.py is the float64
-statement of its quantiser and of the quantiser's gradient. Every absorb group of a Llama-class decoder block (awq.py
-_GROUPS: the linears that share an input, and the op that produces it) has one trainable scale a [K], positive,
+statement of its quantiser and of the quantiser's gradient. Every absorb group of a Llama-class decoder block
+(calibration.py ABSORB_GROUPS: the linears that share an input, and the op that produces it) has one trainable scale a [K], positive,
 initially 1. The group's linears see diag(a) W, the producing op is divided by a: in real arithmetic the block computes
 the same function, and a is trained so that RTN of the scaled weights loses less.
 
   forward    every eligible linear computes x.matmul(W~) + bias with W~ = Q(diag(a) W) / a = qbits.teq_forward(w, a)
              (csrc/woq_teq.hip), one launch per linear per step; a linear in no trained group has a = 1 and no gradient
   backward   autograd gives dL/dW~ (the block's own ops, torch); qbits.teq_grad turns it into dL/da, one launch per
-             linear; a group's gradient is the sum over its linears in _GROUPS order
+             linear; a group's gradient is the sum over its linears in ABSORB_GROUPS order
   update     torch's Adam on the [K] vectors, betas (0.9, 0.9), eps 1e-8, no weight decay (neural_compressor's values);
              the learning rate warms up linearly over the first 5 % of the steps and decays linearly to 0; a >= 1e-4
   keep       the scales at the lowest loss seen (step 0 is RTN), folded in on fp32 working copies: a group's linears
@@ -28,7 +28,7 @@ Two decisions differ from neural_compressor's training against the whole model's
      column commutes with the RTN rule in real arithmetic (the group scale takes the factor, the codes stay), so it
      changes nothing in that linear's quantisation error and gets no gradient from it; it enters only at the fold.
 
-A minibatch is drawn as in autoround.py (a torch.Generator seeded with 42). torch does the GEMM-shaped parts, the
+The loop and its minibatch draw are calibration.py's train_block, shared with autoround.py. torch does the GEMM-shaped parts, the
 block's backward and Adam on purpose.
 """
 import logging
@@ -36,10 +36,10 @@ import logging
 import torch
 
 from .... import qbits
-from .autoround import DEFAULT_BATCH, SEED, _wrap, draw_minibatch
-from .awq import _GROUPS, SCALE_MODEL_TYPES, _model_type, _scale_groups
-from .calibration import (BITS, block_linears, calibration_batches, capture_block_inputs, check_request,
-                          decoder_blocks, fp32_matmul, install_quantized, next_inputs, run_block, weight_kn)
+from .calibration import (ABSORB_GROUPS, BITS, DEFAULT_BATCH, SCALE_MODEL_TYPES, SEED, absorb_groups, block_linears,
+                          calibration_batches, capture_block_inputs, check_request, decoder_blocks, fake_quant_dtype,
+                          fake_quant_forward, fp32_matmul, install_quantized, model_type, next_inputs, run_block,
+                          train_block, weight_kn)
 
 logger = logging.getLogger(__name__)
 
@@ -51,9 +51,9 @@ FLOOR = 1e-4                   # of a, AWQ's floor
 def validate_teq_request(model, config):
     """Everything about a request that can be refused without touching a device."""
     check_request(model, config, "TEQ", ("use_double_quant", "layer_wise", "absorb_to_layer"))
-    if _model_type(model) not in SCALE_MODEL_TYPES:
+    if model_type(model) not in SCALE_MODEL_TYPES:
         raise NotImplementedError("TEQ folds its scales into Llama-class blocks (model_type %s), not model type %s"
-                                  % (" / ".join(SCALE_MODEL_TYPES), _model_type(model)))
+                                  % (" / ".join(SCALE_MODEL_TYPES), model_type(model)))
 
 
 def schedule(lr, t, steps):
@@ -70,10 +70,10 @@ def fold_scales(block, weights, scales):
     is changed in place (a group's linears w * a[k], then a producing linear's columns / a[n]); a producing linear's
     bias and a producing norm's weight are divided in the module, in their own dtype."""
     for gi, a in scales.items():
-        for name in _GROUPS[gi][0]:
+        for name in ABSORB_GROUPS[gi][0]:
             weights[name].mul_(a.to(weights[name].dtype)[:, None])
     for gi, a in scales.items():
-        prev = _GROUPS[gi][1]
+        prev = ABSORB_GROUPS[gi][1]
         p = block.get_submodule(prev)
         if prev in weights:
             weights[prev].div_(a.to(weights[prev].dtype)[None, :])
@@ -97,7 +97,7 @@ class _Quantiser:
 
 class FakeQuant(torch.autograd.Function):
     """W~ of one linear: the forward is qbits.teq_forward, the backward qbits.teq_grad. The gradient is left on the
-    quantiser, not returned: the group's sum is taken in _GROUPS order by the training loop."""
+    quantiser, not returned: the group's sum is taken in ABSORB_GROUPS order by the training loop."""
 
     @staticmethod
     def forward(ctx, a, q):
@@ -111,66 +111,47 @@ class FakeQuant(torch.autograd.Function):
         return None, None
 
 
-def train_block(block, quantisers, groups, inputs, targets, steps, lr, batch_size, gen):
-    """`steps` Adam steps on one block -> (rtn_loss, best_loss, best_step, best scales {group index: a}).
-    `groups` {group index: (a, the group's quantisers in _GROUPS order)}"""
+def block_trainer(quantisers, groups, steps, lr):
+    """what calibration.train_block runs around its loss -> (begin_step, after_backward, snapshot). A quantiser in no
+    trained group keeps one W~ for the whole loop, built here; begin_step builds the others'. after_backward sums every
+    group's gradient in ABSORB_GROUPS order, takes the Adam step at the step's rate and keeps a at FLOOR or above."""
     params = [a for a, _ in groups.values()]
     opt = torch.optim.Adam(params, lr=lr, betas=BETAS, eps=EPS, weight_decay=0.0)
-    best, best_loss, best_step, rtn_loss = None, None, -1, None
-    flags = [(p, p.requires_grad) for p in block.parameters()]
-    for p, _ in flags:
-        p.requires_grad_(False)
-    try:
-        with torch.enable_grad():
-            for q in quantisers:
-                if not q.a.requires_grad:  # in no trained group: the same W~ at every step
-                    q.wq = FakeQuant.apply(q.a, q)
-            for t in range(steps):
-                picked = draw_minibatch(inputs, batch_size, gen)
-                for q in quantisers:
-                    if q.a.requires_grad:
-                        q.wq = FakeQuant.apply(q.a, q)
-                total = sum(targets[i].numel() for i in picked)
-                loss = 0.0
-                for i in picked:
-                    y = run_block(block, [inputs[i]])[0]
-                    loss = loss + (y.float() - targets[i].float()).square().sum()
-                loss = loss / total
-                value = float(loss.detach())
-                if t == 0:
-                    rtn_loss = value
-                if best_loss is None or value < best_loss:  # before the update: these scales gave this loss
-                    best_loss, best_step = value, t
-                    best = {gi: a.detach().clone() for gi, (a, _) in groups.items()}
-                loss.backward()
-                for a, members in groups.values():
-                    grad = members[0].da
-                    for q in members[1:]:
-                        grad = grad + q.da
-                    a.grad = grad
-                for pg in opt.param_groups:
-                    pg["lr"] = schedule(lr, t, steps)
-                opt.step()
-                with torch.no_grad():
-                    for a in params:
-                        a.clamp_(min=FLOOR)
-                for q in quantisers:
-                    q.da = None
-                    if q.a.requires_grad:
-                        q.wq = None
-    finally:
-        for p, flag in flags:
-            p.requires_grad_(flag)
-    return rtn_loss, best_loss, best_step, best
+    trained = [q for q in quantisers if q.a.requires_grad]
+    for q in quantisers:
+        if not q.a.requires_grad:
+            q.wq = FakeQuant.apply(q.a, q)
+
+    def begin_step(t):
+        for q in trained:
+            q.wq = FakeQuant.apply(q.a, q)
+        return trained
+
+    def after_backward(t):
+        for a, members in groups.values():
+            grad = members[0].da
+            for q in members[1:]:
+                grad = grad + q.da
+            a.grad = grad
+        for pg in opt.param_groups:
+            pg["lr"] = schedule(lr, t, steps)
+        opt.step()
+        with torch.no_grad():
+            for a in params:
+                a.clamp_(min=FLOOR)
+        for q in quantisers:
+            q.da = None
+
+    return begin_step, after_backward, lambda: {gi: a.detach().clone() for gi, (a, _) in groups.items()}
 
 
 def block_quantisers(linears, trained, group, bits, asym, dtype, device):
-    """One trainable a [K] per group of `trained` (indices into _GROUPS), one quantiser per linear, every linear's
-    forward wrapped -> (quantisers in `linears` order, {group index: (a, the group's quantisers in _GROUPS order)}).
+    """One trainable a [K] per group of `trained` (indices into ABSORB_GROUPS), one quantiser per linear -> (quantisers
+    in `linears` order, {group index: (a, the group's quantisers in ABSORB_GROUPS order)}).
     A linear in no trained group sees a = 1 without grad."""
     modules, by_name, groups = dict(linears), {}, {}
     for gi in trained:
-        names = _GROUPS[gi][0]
+        names = ABSORB_GROUPS[gi][0]
         a = torch.ones(modules[names[0]].in_features, dtype=torch.float32, device=device).requires_grad_(True)
         for name in names:
             by_name[name] = _Quantiser(modules[name], a, group, bits, asym, dtype)
@@ -179,7 +160,6 @@ def block_quantisers(linears, trained, group, bits, asym, dtype, device):
         if name not in by_name:
             ones = torch.ones(m.in_features, dtype=torch.float32, device=device)
             by_name[name] = _Quantiser(m, ones, group, bits, asym, dtype)
-        _wrap(m, by_name[name])
     return [by_name[name] for name, _ in linears], groups
 
 
@@ -211,16 +191,13 @@ def teq_quantize_model(model, config, device="cuda"):
             linears = block_linears(block, where, skip)
             targets = run_block(block, inputs)
             entry, best = (None, None, -1), {}
-            trained = _scale_groups(block, linears, where, "TEQ") if steps > 0 else []
+            trained = absorb_groups(block, linears, where, "TEQ") if steps > 0 else []
             if trained:
-                dtype = targets[0].dtype if targets[0].dtype in (torch.float16, torch.bfloat16) else torch.float32
-                quantisers, groups = block_quantisers(linears, trained, config.group_size, bits, asym, dtype, device)
-                try:
-                    rtn_loss, best_loss, best_step, best = train_block(block, quantisers, groups, inputs, targets,
-                                                                       steps, lr, batch_size, gen)
-                finally:
-                    for _, m in linears:
-                        del m.forward
+                quantisers, groups = block_quantisers(linears, trained, config.group_size, bits, asym,
+                                                      fake_quant_dtype(targets), device)
+                with fake_quant_forward(linears, quantisers):
+                    rtn_loss, best_loss, best_step, best = train_block(
+                        block, inputs, targets, steps, batch_size, gen, *block_trainer(quantisers, groups, steps, lr))
                 entry = (rtn_loss, best_loss, best_step)
                 logger.info("TEQ %s: loss %.6g at step %d (RTN %.6g)", where, best_loss, best_step, rtn_loss)
                 del quantisers, groups

@@ -110,7 +110,7 @@ def _tiny(kind):
 def test_scale_folding_preserves_the_function(kind):
     from intel_extension_for_transformers_amd.transformers.llm.quantization import awq
     from intel_extension_for_transformers_amd.transformers.llm.quantization.calibration import (
-        block_linears as _block_linears)
+        ABSORB_GROUPS, absorb_groups, block_linears as _block_linears)
 
     model = _tiny(kind)
     ids = torch.randint(0, 256, (2, 24), generator=torch.Generator().manual_seed(2))
@@ -119,11 +119,11 @@ def test_scale_folding_preserves_the_function(kind):
     folded = copy.deepcopy(model)
     gen = torch.Generator().manual_seed(3)
     for block in folded.model.layers:
-        groups = awq._scale_groups(block, _block_linears(block, "model.layers", []), "test")
+        groups = absorb_groups(block, _block_linears(block, "model.layers", []), "test", "AWQ")
         assert groups == ([0, 2, 3] if kind == "gqa" else [0, 1, 2, 3])  # grouped-query attention: no o_proj scale
         scales = {}
         for gi in groups:
-            k = block.get_submodule(awq._GROUPS[gi][0][0]).in_features
+            k = block.get_submodule(ABSORB_GROUPS[gi][0][0]).in_features
             scales[gi] = torch.exp(torch.empty(k).uniform_(-1.5, 1.5, generator=gen))  # 0.22 .. 4.5
         before = {n: p.detach().clone() for n, p in block.named_parameters()}
         awq.apply_scales(block, scales)

@@ -1,9 +1,11 @@
-"""What GPTQ, AWQ and AutoRound calibration share (transformers/llm/quantization/calibration.py), on the CPU: the stream
-of block inputs against the model's own hidden states, the hooked input statistics against float64, the batch-size
-override, and that the three method files no longer import from one another. Tiny random-init models as in
-tests/test_gpu_gptq_model.py, with three layers so that there is a middle block."""
+"""What GPTQ, AWQ, AutoRound and TEQ calibration share (transformers/llm/quantization/calibration.py), on the CPU: the
+stream of block inputs against the model's own hidden states, the hooked input statistics against float64, the
+batch-size override, the block-training loop and the fake-quant wrap on a toy block in plain torch, and that the method
+files do not import from one another. Tiny random-init models as in tests/test_gpu_gptq_model.py, with three layers so
+that there is a middle block."""
 import ast
 import functools
+import logging
 import os
 import types
 
@@ -149,7 +151,7 @@ def test_batch_size_override():
 
 
 def test_the_method_files_do_not_import_from_one_another():
-    methods = ("gptq", "awq", "autoround")
+    methods = ("gptq", "awq", "autoround", "teq")
     here = os.path.dirname(os.path.abspath(C.__file__))
     for name in methods:
         tree = ast.parse(open(os.path.join(here, name + ".py")).read())
@@ -162,3 +164,133 @@ def test_the_method_files_do_not_import_from_one_another():
                 continue
             for other in methods:
                 assert not any(part == other for i in imported for part in i.split(".")), (name, ast.dump(node))
+
+
+# ---- train_block and the wrap, on a toy block ---------------------------------------------------------------------------
+class _Toy:
+    """one nn.Linear(8, 8) as the block, 5 batches of 3 rows, and a quantiser W~ = w + p with p trained by plain SGD"""
+
+    def __init__(self, lr=0.05, same_batches=False):
+        g = torch.Generator().manual_seed(5)
+        self.block = torch.nn.Linear(8, 8)
+        with torch.no_grad():
+            self.block.weight.copy_(torch.randn(8, 8, generator=g))
+            self.block.bias.copy_(torch.randn(8, generator=g))
+        self.block.bias.requires_grad_(False)  # one flag of each kind to restore
+        xs = [torch.randn(3, 8, generator=g) for _ in range(5)]
+        ys = [torch.randn(3, 8, generator=g) for _ in range(5)]
+        if same_batches:
+            xs, ys = [xs[0]] * 5, [ys[0]] * 5
+        self.inputs = [((x,), {}) for x in xs]  # run_block's units
+        self.targets = ys
+        self.linears = [("", self.block)]
+        self.w = self.block.weight.data.t().clone()
+        self.bias = self.block.bias.data
+        self.p = torch.zeros(8, 8, requires_grad=True)
+        self.wq, self.lr = None, lr
+        self.seen, self.frozen, self.p_at, self.snapshots = [], [], [], 0
+        self.block.register_forward_pre_hook(self._saw)
+
+    def _saw(self, _module, args):
+        if self.seen:  # inside a step: the first unit that holds this very tensor
+            self.seen[-1].append([i for i, u in enumerate(self.inputs) if _hidden(u) is args[0]][0])
+
+    def begin_step(self, t):
+        self.seen.append([])
+        self.frozen.append([p.requires_grad for p in self.block.parameters()])
+        self.p_at.append(self.p.detach().clone())
+        self.wq = self.w + self.p
+        return [self]
+
+    def after_backward(self, t):
+        with torch.no_grad():
+            self.p.sub_(self.lr * self.p.grad)
+        self.p.grad = None
+
+    def snapshot(self):
+        self.snapshots += 1
+        return self.p.detach().clone()
+
+    def loss(self, p, picked):
+        """the loop's loss expression, outside the loop"""
+        wq = self.w + p
+        total = sum(self.targets[i].numel() for i in picked)
+        loss = 0.0
+        for i in picked:
+            y = _hidden(self.inputs[i]).matmul(wq) + self.bias
+            loss = loss + (y.float() - self.targets[i].float()).square().sum()
+        return float(loss / total)
+
+    def train(self, steps, begin_step=None):
+        gen = torch.Generator().manual_seed(C.SEED)
+        with C.fake_quant_forward(self.linears, [self]):
+            return C.train_block(self.block, self.inputs, self.targets, steps, 4, gen,
+                                 begin_step or self.begin_step, self.after_backward, self.snapshot)
+
+
+def _logged(caplog):
+    return [r.args for r in caplog.records if r.name == C.__name__ and r.msg.startswith("step %d")]
+
+
+def test_train_block_draws_once_per_step_and_logs_the_loss_of_the_expression(caplog):
+    toy, steps = _Toy(), 6
+    flags = [p.requires_grad for p in toy.block.parameters()]
+    assert flags == [True, False]
+    with caplog.at_level(logging.DEBUG, logger=C.__name__):
+        first, best, best_step, kept = toy.train(steps)
+    gen = torch.Generator().manual_seed(C.SEED)
+    want = [C.draw_minibatch(toy.inputs, 4, gen) for _ in range(steps)]
+    assert all(len(w) == 2 for w in want)  # 3 rows a batch, 4 asked for
+    assert toy.seen == want  # what the block really ran on, in order
+    logged = _logged(caplog)
+    assert [(t, picked) for t, picked, _ in logged] == list(enumerate(want))
+    losses = [toy.loss(toy.p_at[t], want[t]) for t in range(steps)]
+    assert [value for _, _, value in logged] == losses  # exactly
+    assert first == losses[0] and best == min(losses) and best_step == losses.index(min(losses))
+    assert torch.equal(kept, toy.p_at[best_step])  # best before the update
+    assert len(set(losses)) == steps and best_step > 0  # SGD moved, so the checks above could tell steps apart
+    assert all(f == [False, False] for f in toy.frozen)
+    assert [p.requires_grad for p in toy.block.parameters()] == flags
+    assert toy.block.weight.grad is None and toy.wq is None and "forward" not in toy.block.__dict__
+
+
+def test_train_block_with_one_step_keeps_the_initial_parameters():
+    toy = _Toy()
+    first, best, best_step, kept = toy.train(1)
+    assert first == best and best_step == 0 and toy.snapshots == 1
+    assert torch.equal(kept, torch.zeros(8, 8)) and not torch.equal(toy.p.detach(), kept)  # kept before the update
+
+
+def test_train_block_keeps_the_earlier_step_on_a_tie():
+    toy = _Toy(lr=0.0, same_batches=True)  # every draw is two copies of one batch and nothing moves: every loss ties
+    first, best, best_step, kept = toy.train(4)
+    assert first == best and best_step == 0 and toy.snapshots == 1
+
+
+def test_train_block_restores_requires_grad_when_step_two_raises():
+    toy = _Toy()
+    flags = [p.requires_grad for p in toy.block.parameters()]
+
+    def begin_step(t):
+        if t == 1:
+            raise RuntimeError("no W~ today")
+        return toy.begin_step(t)
+
+    with pytest.raises(RuntimeError, match="no W~ today"):
+        toy.train(3, begin_step)
+    assert toy.frozen == [[False, False]]
+    assert [p.requires_grad for p in toy.block.parameters()] == flags == [True, False]
+    assert "forward" not in toy.block.__dict__
+
+
+def test_the_wrap_computes_with_the_quantiser_and_is_gone_after_a_raising_body():
+    toy = _Toy()
+    x = _hidden(toy.inputs[0])
+    plain = toy.block(x)
+    toy.wq = 2.0 * toy.w
+    with pytest.raises(KeyError):
+        with C.fake_quant_forward(toy.linears, [toy]):
+            assert "forward" in toy.block.__dict__
+            assert torch.equal(toy.block(x), x.matmul(toy.wq) + toy.bias)
+            raise KeyError("body")
+    assert "forward" not in toy.block.__dict__ and torch.equal(toy.block(x), plain)

@@ -146,14 +146,14 @@ def test_blobs_are_the_quantiser_at_the_kept_scales(kv_heads, sym):
     o_proj group is skipped and v_proj's columns are untouched): dequantize(blob)[k, n] / a[k] equals teq_forward of the
     original fp32 weight at the kept a, bit for bit (4 bits)"""
     from intel_extension_for_transformers_amd import qbits
-    from intel_extension_for_transformers_amd.transformers.llm.quantization.awq import _GROUPS
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.calibration import ABSORB_GROUPS
 
     fp, model, _ = _trained(kv_heads, sym)
     names = NO_PRODUCER_ROLE + (("self_attn.v_proj",) if kv_heads == 2 else ())
     for li, (q, f) in enumerate(zip(model.model.layers, fp.model.layers)):
         scales = model._teq_scales[li]
         for name in names:
-            gi = [i for i, (members, _) in enumerate(_GROUPS) if name in members][0]
+            gi = [i for i, (members, _) in enumerate(ABSORB_GROUPS) if name in members][0]
             a = scales[gi]
             w = f.get_submodule(name).weight.data.t().float().contiguous().cuda()
             want = qbits.teq_forward(w, a, 32, 4, not sym)

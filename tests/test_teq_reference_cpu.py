@@ -98,14 +98,14 @@ def test_fold_preserves_the_block():
     """all four groups at once, on a float64 block with biases: the linears' working copies * a[k], the producing
     linears' columns and biases / a, the norms / a; outputs within 1e-10"""
     from intel_extension_for_transformers_amd.transformers.llm.quantization import teq
-    from intel_extension_for_transformers_amd.transformers.llm.quantization.awq import _GROUPS
+    from intel_extension_for_transformers_amd.transformers.llm.quantization.calibration import ABSORB_GROUPS
 
     block, run = _tiny_block()
     want = run(block)
     folded = copy.deepcopy(block)
     gen = torch.Generator().manual_seed(3)
     scales = {gi: torch.exp(0.5 * torch.randn(folded.get_submodule(names[0]).in_features, generator=gen,
-                                              dtype=torch.float64)) for gi, (names, _) in enumerate(_GROUPS)}
+                                              dtype=torch.float64)) for gi, (names, _) in enumerate(ABSORB_GROUPS)}
     linears = [(n, m) for n, m in folded.named_modules() if isinstance(m, torch.nn.Linear)]
     assert len(linears) == 7
     weights = {n: m.weight.data.t().clone() for n, m in linears}

@@ -115,15 +115,15 @@ def rate_block(group, bits, reps, batch, seq):
         targets = calibration.run_block(block, inputs)
     linears = calibration.block_linears(block, "model.layers.0", [])
     quantisers = [autoround._Quantiser(m, group, bits, True, torch.bfloat16) for _, m in linears]
-    for (_, m), q in zip(linears, quantisers):
-        autoround._wrap(m, q)
-    gen = torch.Generator().manual_seed(autoround.SEED)
+    gen = torch.Generator().manual_seed(calibration.SEED)
     n = 4
 
     def run():
-        autoround._train_block(block, quantisers, inputs, targets, n, 1e-3, 1e-3, batch, gen)
+        calibration.train_block(block, inputs, targets, n, batch, gen,
+                                *autoround.block_trainer(quantisers, n, 1e-3, 1e-3))
 
-    ms = timed(run, reps, warm=1) / n
+    with calibration.fake_quant_forward(linears, quantisers):
+        ms = timed(run, reps, warm=1) / n
     gs = [torch.randn_like(q.w).to(torch.bfloat16) for q in quantisers]
 
     def launches():

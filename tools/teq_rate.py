@@ -27,7 +27,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from intel_extension_for_transformers_amd import qbits  # noqa: E402
 from intel_extension_for_transformers_amd.transformers.llm.quantization import calibration, teq  # noqa: E402
-from intel_extension_for_transformers_amd.transformers.llm.quantization.autoround import SEED  # noqa: E402
 
 SHAPES = "4096x12288,4096x4096,4096x22016,11008x4096"
 PEAK = 8.0e12  # bytes / s
@@ -123,13 +122,14 @@ def rate_block(group, bits, asym, reps, batch, seq):
         targets = calibration.run_block(block, inputs)
     linears = calibration.block_linears(block, "model.layers.0", [])
     quantisers, groups = teq.block_quantisers(linears, [0, 1, 2, 3], group, bits, asym, torch.bfloat16, dev)
-    gen = torch.Generator().manual_seed(SEED)
+    gen = torch.Generator().manual_seed(calibration.SEED)
     n = 4
 
     def run():
-        teq.train_block(block, quantisers, groups, inputs, targets, n, 1e-3, batch, gen)
+        calibration.train_block(block, inputs, targets, n, batch, gen, *teq.block_trainer(quantisers, groups, n, 1e-3))
 
-    ms = timed(run, reps, warm=1) / n
+    with calibration.fake_quant_forward(linears, quantisers):
+        ms = timed(run, reps, warm=1) / n
     gs = [torch.randn_like(q.w).to(torch.bfloat16) for q in quantisers]
 
     def launches():
