@@ -513,6 +513,33 @@ WOQ_API int   woq_engine_discarded_set(woq_engine* e, int value, void* stream);
  * fp8-weight layers, for only one of q_norm / k_norm, and for a norm with head_dim not a multiple of 16. */
 WOQ_API int woq_engine_set_layer_extras(woq_engine* e, int layer, const float* qkv_bias_dev,
                                         const float* q_norm_dev, const float* k_norm_dev);
+/* ---- unmerged LoRA adapters on the engine (new entry points only, WOQ_ABI_VERSION stays 4, no struct changes) ---------
+ * A targeted projection computes y = x . W_deq (+ bias) + scaling * (x . A^T) . B^T with A [r][K], B [N][r] in fp32 and
+ * fp32 accumulation (the reference's QuantizedLoraLinearQBits.forward at inference: dropout is the identity); x is the
+ * projection's own input (the RMSNorm output for q / k / v and gate / up, the attention output for o_proj,
+ * SiLU(gate) * up for down_proj). Targets: 0 q_proj, 1 k_proj, 2 v_proj, 3 o_proj, 4 gate_proj, 5 up_proj, 6 down_proj;
+ * any subset, ranks may differ per target, 1 <= r <= 64. One adapter per target at a time.
+ *   lora_reserve  once per engine: the per-layer A / B tables of all seven targets at rank r_max, the device descriptors
+ *                 the kernels read ranks and scalings from, and the decode step's four delta buffers. Changes no step.
+ *   set_lora      copies one target's tables in (a_dev: fp32 [r][K], b_dev: fp32 [N][r], dense, device memory; the
+ *                 caller's tensors are free afterwards); r == 0 removes the target. Synchronises the device.
+ *   clear_lora    removes every target.   lora_on: the number of (layer, fused projection) pairs that carry an adapter.
+ * Decode step: in front of every fused projection (q|k|v, o, gate/up, down) with at least one installed part ONE launch
+ * (csrc/woq_lora.hip) writes static bias + scaling * B . (A . x) per output column, which the projection's GEMV takes
+ * through its bias slot: after the RMSNorm factor, before SiLU * mul, the residual add and the XQ output; all forms
+ * (XQ GEMV, fused qkv + attention, fp32-activation GEMV). Prompt pass: two launches per such projection on the f32-input
+ * matrix cores; q / k / v and gate / up are rounded to fp16 once more than without an adapter. A projection
+ * without an installed part keeps exactly the calls it has without adapters, and an engine without adapters issues no
+ * new launch. Captured graphs: a call that changes WHICH (layer, fused projection) pairs carry an adapter drops them;
+ * other values, or another adapter of the same targets and ranks up to r_max, keep them (tables, descriptors and launch
+ * geometry do not move; ranks are device data). Every refusal is checked before any state changes: a tensor-parallel
+ * engine (tp_size > 1, a communicator or an all-reduce callback), fp8-weight layers, r > r_max, set before reserve, a
+ * layer that is not set, a second reserve, shapes whose rows / columns are no multiples of 16. */
+WOQ_API int woq_engine_lora_reserve(woq_engine* e, int r_max);
+WOQ_API int woq_engine_set_lora(woq_engine* e, int layer, int target, const float* a_dev, const float* b_dev, int r,
+                                float scaling);
+WOQ_API int woq_engine_clear_lora(woq_engine* e);
+WOQ_API int woq_engine_lora_on(woq_engine* e);
 /* tensor-parallel seam: when set, the engine calls `fn(user, buf_dev, count_f32, stream)` after
  * o_proj and after down_proj (row-parallel partial sums -> sum over ranks). The Python host binds it
  * to RCCL via torch.distributed. NULL = single GPU. */

@@ -183,6 +183,29 @@ WOQ_API int woq_probe_xq_from_f32(const float* x, const float* norm_w, int K, vo
 WOQ_API int woq_probe_gemv_xq(const float* x, const float* in_norm_w, float eps, const void* blob, int epi,
                               const float* bias, const float* residual, const float* next_norm_w, float* out,
                               void* xo_limbs, float* xo_u, float* xo_sx, float* ssq_out, void* stream);
+/* The LoRA adapter kernels alone (csrc/woq_lora.hip; tests/test_gpu_lora_kernel.py), each forwarding to the engine's own
+ * launcher unchanged. A projection's adapter is given as host arrays of n_parts (1..3) entries: a_dev[p] = device fp32
+ * A_p [ranks[p]][K], b_dev[p] = device fp32 B_p [cols[p]][ranks[p]], scalings[p] = lora_alpha / r; ranks[p] == 0 = the
+ * part has no adapter (its pointers are not read); cols[p] % 16 == 0 and their sum is N. interleave != 0 (two parts,
+ * gate and up): the N blob columns alternate gate / up in 16-column tiles (runtime.fuse_gate_up).
+ * delta, the decode step's launch: out fp32 [N] = base_bias (nullable = 0) + s_p * B_p . (inv * A_p . x).
+ *   form 0: x / xq_u / xq_sx = an XQ vector of K values (woq_probe_xq_from_f32), aux = its K / 16 sums of squares
+ *           (nullable; given: inv = 1 / sqrt(sum(aux) / K + eps), else 1)
+ *   form 1: x fp32 [K], aux = a norm weight fp32 [K] (nullable; given: x * aux and inv = 1 / sqrt(mean(x^2) + eps))
+ * shrink, the prompt pass's first launch: T fp32 [M][ldt], columns 0 .. sum(ranks) = inv_m * A_p . (X[m] * norm_w) over the
+ *   stacked rows of the parts; X fp32 [M][ldx] (norm_w nullable) or fp16 (x_dtype WOQ_F16, norm_w NULL).
+ * expand, its second: mode 0 out fp32 [M][ldo] += s_p * T[m] . B_p^T, mode 1 the same on fp16, mode 2 (interleave, gu =
+ *   fp16 [M][ld_gu] gate/up rows in blob column order) out fp16 [M][ldo], N / 2 columns, = SiLU(gate + D) * (up + D). */
+WOQ_API int woq_probe_lora_delta(int form, const void* x, const float* xq_u, const float* xq_sx, const float* aux,
+                                 float eps, int K, int N, int n_parts, int interleave, const void* const* a_dev,
+                                 const void* const* b_dev, const int* ranks, const int* cols, const float* scalings,
+                                 const float* base_bias, float* out, void* stream);
+WOQ_API int woq_probe_lora_shrink(const void* X, int x_dtype, int ldx, int M, int K, const float* norm_w, float eps,
+                                  int n_parts, const void* const* a_dev, const int* ranks, float* T, int ldt,
+                                  void* stream);
+WOQ_API int woq_probe_lora_expand(int mode, const float* T, int ldt, int M, int N, int n_parts,
+                                  const void* const* b_dev, const int* ranks, const int* cols, const float* scalings,
+                                  void* out, int ldo, const void* gu, int ld_gu, void* stream);
 /* The tensor-parallel exchange alone (tests/test_gpu_tp_kernels.py), each forwarding to the engine's own launcher
  * unchanged. Every rank of a connected communicator issues the same chain of collectives.
  * gemv_xq_tp: woq_probe_gemv_xq whose last chained launch also pushes its live output columns, this rank's partial sums,

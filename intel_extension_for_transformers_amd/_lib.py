@@ -101,6 +101,7 @@ EXPORTS = [
     "woq_engine_set_layer_extras", "woq_awq_scale_delta", "woq_awq_clip_search",
     "woq_autoround_forward", "woq_autoround_step", "woq_autoround_codes", "woq_teq_forward", "woq_teq_grad",
     "woq_linear_backward", "woq_linear_backward_workspace",
+    "woq_engine_lora_reserve", "woq_engine_set_lora", "woq_engine_clear_lora", "woq_engine_lora_on",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -113,7 +114,12 @@ EXPERIMENTAL_EXPORTS = [
     "woq_probe_attn_decode_plan", "woq_engine_attn_plan", "woq_probe_guide", "woq_probe_sample_stream",
     "woq_probe_rope_append_qknorm", "woq_probe_attn_decode_qknorm",
     "woq_probe_gemv_xq_tp", "woq_probe_comm_allreduce", "woq_probe_comm_greedy", "woq_probe_comm_set_seq",
+    "woq_probe_lora_delta", "woq_probe_lora_shrink", "woq_probe_lora_expand",
 ]
+# the engine's LoRA targets (include/woq_hip.h woq_engine_set_lora), by HF module name
+LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+LORA_MAX_RANK = 64
+LORA_EXPAND_ADD_F32, LORA_EXPAND_ADD_F16, LORA_EXPAND_SILU = 0, 1, 2  # csrc/woq_host.h LoraExpandMode
 # woq_gemm_form_log bits: which prefill-GEMM form a launch ran (csrc/woq_gemm_f16.hip GEMM_FORM_*)
 GEMM_FORM_FRAG, GEMM_FORM_SPLITK, GEMM_FORM_FP32, GEMM_FORM_HANDSCHED = 1, 2, 4, 8
 GEMM_FORM_RING, GEMM_FORM_TALL, GEMM_FORM_RAW = 16, 32, 64
@@ -169,6 +175,13 @@ def lib():
     L.woq_engine_set_layer.argtypes = [vp, ci, ctypes.POINTER(LayerWeights)]
     L.woq_engine_set_head.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp]
     L.woq_engine_set_layer_extras.argtypes = [vp, ci, vp, vp, vp]
+    L.woq_engine_lora_reserve.argtypes = [vp, ci]
+    L.woq_engine_set_lora.argtypes = [vp, ci, ci, vp, vp, ci, cf]
+    L.woq_engine_clear_lora.argtypes = [vp]
+    L.woq_engine_lora_on.argtypes = [vp]
+    L.woq_probe_lora_delta.argtypes = [ci, vp, vp, vp, vp, cf, ci, ci, ci, ci] + [vp] * 8
+    L.woq_probe_lora_shrink.argtypes = [vp, ci, ci, ci, ci, vp, cf, ci, vp, vp, vp, ci, vp]
+    L.woq_probe_lora_expand.argtypes = [ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, ci, vp]
     for f in ("woq_engine_token_ptr", "woq_engine_pos_ptr", "woq_engine_logits_ptr", "woq_engine_hidden_ptr"):
         getattr(L, f).restype = vp
         getattr(L, f).argtypes = [vp]
@@ -566,6 +579,59 @@ def probe_gemm_f16(x, blob, out, M, lda=None, ldo=None, norm_w=None, eps=0.0, ep
                                    int(epi), _opt(bias), _opt(residual), int(ldo if ld_res is None else ld_res), _ptr(out),
                                    torch_dtype_code(out.dtype), ldo, int(bool(fp32_class)), _opt(ws), int(ws_bytes),
                                    stream_ptr()))
+
+
+def _lora_parts(parts, want_a, want_b):
+    """parts = [(A or None, B or None, scaling), ...] device fp32 tensors A [r, K] / B [n, r] (None = the part has no
+    adapter: give (None, n_cols, 0.0) there) -> the host arrays the LoRA probes take. Keeps nothing alive: the caller's
+    tensors must outlive the call."""
+    n = len(parts)
+    a, b = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
+    r, cols, s = (ctypes.c_int * n)(), (ctypes.c_int * n)(), (ctypes.c_float * n)()
+    for i, (A, B, sc) in enumerate(parts):
+        if A is None and not hasattr(B, "data_ptr"):  # (None, n_cols, _): an absent part
+            r[i], cols[i], s[i] = 0, int(B or 16), 0.0
+            continue
+        r[i] = int(A.shape[0] if A is not None else B.shape[1])
+        cols[i] = int(B.shape[0]) if B is not None else 16
+        s[i] = float(sc)
+        a[i] = A.data_ptr() if A is not None else None
+        b[i] = B.data_ptr() if B is not None else None
+        if (want_a and A is None) or (want_b and B is None):
+            raise ValueError("this probe reads the part's %s table" % ("A" if want_a and A is None else "B"))
+    return n, a, b, r, cols, s
+
+
+def probe_lora_delta(parts, out, x=None, xq=None, ssq=None, norm_w=None, eps=0.0, base_bias=None, interleave=False):
+    """the decode step's LoRA delta launch alone (woq_probe_lora_delta). Input: `xq` = (limbs, u, sx) of K values with
+    `ssq` (its K / 16 sums of squares, or None = no norm), or `x` fp32 [K] with `norm_w` (or None). out fp32 [N]."""
+    n, a, b, r, cols, s = _lora_parts(parts, True, True)
+    if xq is not None:
+        K = int(xq[1].numel()) * 16
+        check(lib().woq_probe_lora_delta(0, _ptr(xq[0]), _ptr(xq[1]), _ptr(xq[2]), _opt(ssq), float(eps), K,
+                                         int(out.numel()), n, int(bool(interleave)), a, b, r, cols, s, _opt(base_bias),
+                                         _ptr(out), stream_ptr()))
+    else:
+        check(lib().woq_probe_lora_delta(1, _ptr(x), None, None, _opt(norm_w), float(eps), int(x.numel()),
+                                         int(out.numel()), n, int(bool(interleave)), a, b, r, cols, s, _opt(base_bias),
+                                         _ptr(out), stream_ptr()))
+
+
+def probe_lora_shrink(X, M, K, a_parts, T, ldx=None, ldt=None, norm_w=None, eps=0.0):
+    """the prompt pass's LoRA shrink alone (woq_probe_lora_shrink): X fp32 / fp16 rows (data pointer = row 0), a_parts =
+    the parts' A tables fp32 [r, K], T fp32 [>= M, ldt]."""
+    n, a, _, r, _, _ = _lora_parts([(A, None, 1.0) for A in a_parts], True, False)
+    check(lib().woq_probe_lora_shrink(_ptr(X), torch_dtype_code(X.dtype), int(K if ldx is None else ldx), int(M), int(K),
+                                      _opt(norm_w), float(eps), n, a, r, _ptr(T), int(T.shape[-1] if ldt is None else ldt),
+                                      stream_ptr()))
+
+
+def probe_lora_expand(mode, T, M, N, parts, out, ldo, ldt=None, gu=None, ld_gu=0):
+    """the prompt pass's LoRA expand alone (woq_probe_lora_expand): parts = [(None, B, scaling) | (None, n_cols, 0.0)],
+    mode LORA_EXPAND_*; out is updated in place (modes 0, 1) or written (mode 2, from the fp16 gate/up rows `gu`)."""
+    n, _, b, r, cols, s = _lora_parts(parts, False, True)
+    check(lib().woq_probe_lora_expand(int(mode), _ptr(T), int(T.shape[-1] if ldt is None else ldt), int(M), int(N), n, b, r,
+                                      cols, s, _ptr(out), int(ldo), _opt(gu), int(ld_gu), stream_ptr()))
 
 
 def check(rc):

@@ -174,6 +174,35 @@ struct woq_engine {
   // scored prompt pass (woq_score.hip): hi + lo rows, the logits of one block of 256 rows and their partials;
   // allocated by the first woq_engine_prefill_scored and held, like pf_ws
   void* score_ws = nullptr;
+  // unmerged LoRA adapters (woq_lora.hip; woq_engine_lora_reserve / woq_engine_set_lora). Per layer and projection kind
+  // one device descriptor (parts, ranks, scalings: what the kernels read) with its host mirror; per (layer, target) an A
+  // and a B table at rank lora_rmax, which installed values are copied into; one delta buffer per projection kind, which
+  // the decode step's GEMV takes as its bias. A (layer, kind) is active while one of its parts has a rank above 0: only
+  // then does a step hold its delta launch, so a change of that set drops captured graphs, other values do not
+  int lora_rmax = 0;  // 0 = not reserved
+  struct LoraTable { float* A; float* B; };
+  std::vector<LoraTable> lora_tab;         // [layers][LORA_TARGETS]
+  std::vector<woq::LoraDesc> lora_host;    // [layers][P_COUNT], what lora_desc holds
+  woq::LoraDesc* lora_desc = nullptr;      // device, [layers][P_COUNT]
+  float* lora_delta[P_COUNT] = {nullptr, nullptr, nullptr, nullptr};  // fp32 [qkv_n], [hidden], [2 * inter], [hidden]
+  float* pf_t = nullptr;                   // prompt pass: fp32 [rows][LORA_MAX_PARTS * lora_rmax], the shrink's output
+  _Float16* pf_gu = nullptr;               // fp16 [rows][2 * inter]: gate/up before SiLU * mul, when gate or up is targeted
+  size_t pf_t_rows = 0, pf_gu_rows = 0;
+  int lora_ldt() const { return woq::LORA_MAX_PARTS * lora_rmax; }
+  int lora_rows(int l, int k) const {  // stacked rows of (layer, kind); 0 = no adapter there
+    if (lora_rmax == 0) return 0;
+    const woq::LoraDesc& d = lora_host[(size_t)l * P_COUNT + k];
+    int r = 0;
+    for (int p = 0; p < d.n_parts; ++p) r += d.part[p].r;
+    return r;
+  }
+  const woq::LoraDesc* lora_dev(int l, int k) const { return lora_desc + (size_t)l * P_COUNT + k; }
+  int lora_active_count() const {
+    int n = 0;
+    for (int l = 0; lora_rmax > 0 && l < cfg.layers; ++l)
+      for (int k = 0; k < P_COUNT; ++k) n += lora_rows(l, k) > 0 ? 1 : 0;
+    return n;
+  }
   // the token tail, decided here alone: the pick after the lm_head of a step (after_prompt: of a prompt pass)
   Tail tail(bool greedy, bool fuse_next, bool after_prompt) const;
   woq::SampleTail sample_tail() const;  // the buffers of a sampled pick
@@ -220,13 +249,47 @@ static const char* engine_layers_problem(const woq_engine* e) {
     if (const char* why = engine_layers_problem(e)) return woq::fail(why); \
   } while (0)
 
-// projection k of layer l as one batch-1 GEMV over an XQ vector
+// the static per-column bias of projection k (Qwen2's q | k | v biases), null = none
+static const float* engine_static_bias(const woq_engine* e, int l, Proj k) {
+  return k == P_QKV ? e->layers[l].qkv_bias : nullptr;
+}
+
+// projection k of layer l as one batch-1 GEMV over an XQ vector, adapter-less (what the timing hooks launch)
+static int engine_gemv_xq_base(woq_engine* e, int l, Proj k, const XqPtrs& xin, float* out, const float* ssq_in,
+                               const float* residual, const XqPtrs& xo, const float* next_norm_w, float* ssq_out,
+                               hipStream_t st, const CommDev* tp = nullptr) {
+  const EngineProj& p = e->layers[l].p[k];
+  return launch_gemv_xq(xin, p.blob, p.hdr, engine_static_bias(e, l, k), out, ssq_in, e->cfg.rms_eps, residual,
+                        kProjEpi[k], xo, next_norm_w, ssq_out, st, tp);
+}
+
+// The `bias` the decode GEMV of (l, k) takes. No adapter there: the static bias, and nothing is launched. With one: the
+// delta launch over the projection's own input (woq_lora.hip) writes static bias + s * B . (inv * A . x) into the kind's
+// buffer, which every GEMV form adds after the RMSNorm factor. Exactly one of xin.limbs / x32 is given.
+static int engine_lora_bias(woq_engine* e, int l, Proj k, const XqPtrs& xin, const float* ssq_in, const float* x32,
+                            const float* norm_w, hipStream_t st, const float** bias) {
+  *bias = engine_static_bias(e, l, k);
+  if (e->lora_rows(l, k) == 0) return 0;
+  const woq_blob_header& h = e->layers[l].p[k].hdr;
+  const int rc = x32 == nullptr ? launch_lora_delta_xq(e->lora_dev(l, k), xin, ssq_in, e->cfg.rms_eps, h.K, h.N, *bias,
+                                                       e->lora_delta[k], st)
+                                : launch_lora_delta_f32(e->lora_dev(l, k), x32, norm_w, e->cfg.rms_eps, h.K, h.N, *bias,
+                                                        e->lora_delta[k], st);
+  *bias = e->lora_delta[k];
+  return rc;
+}
+
+// projection k of layer l as one batch-1 GEMV over an XQ vector (behind its adapter's delta launch, if it has one)
 static int engine_gemv_xq(woq_engine* e, int l, Proj k, const XqPtrs& xin, float* out, const float* ssq_in,
                           const float* residual, const XqPtrs& xo, const float* next_norm_w, float* ssq_out,
                           hipStream_t st, const CommDev* tp = nullptr) {
+  if (e->lora_rows(l, k) == 0)
+    return engine_gemv_xq_base(e, l, k, xin, out, ssq_in, residual, xo, next_norm_w, ssq_out, st, tp);
+  const float* bias = nullptr;
+  if (const int rc = engine_lora_bias(e, l, k, xin, ssq_in, nullptr, nullptr, st, &bias)) return rc;
   const EngineProj& p = e->layers[l].p[k];
-  return launch_gemv_xq(xin, p.blob, p.hdr, k == P_QKV ? e->layers[l].qkv_bias : nullptr, out, ssq_in, e->cfg.rms_eps,
-                        residual, kProjEpi[k], xo, next_norm_w, ssq_out, st, tp);
+  return launch_gemv_xq(xin, p.blob, p.hdr, bias, out, ssq_in, e->cfg.rms_eps, residual, kProjEpi[k], xo, next_norm_w,
+                        ssq_out, st, tp);
 }
 
 // The row-parallel projection that ends a sub-block (o_proj / down_proj), XQ path. One GPU: hidden += x . W, and the new
@@ -248,8 +311,10 @@ static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
   const AttnDecodePlan plan = e->attn_plan(l, e->attn_opt);
   const AttnDecodeIO io = e->attn_io(l, e->xq_attn);
   if (plan.form == ATTN_FUSED) {
+    const float* bias = nullptr;
+    if ((rc = engine_lora_bias(e, l, P_QKV, e->xq_hidden, e->ssq_part, nullptr, nullptr, st, &bias)) != 0) return rc;
     rc = launch_gemv_xq_attn(plan, io, e->xq_hidden, w.p[P_QKV].blob, w.p[P_QKV].hdr, e->qkv_g, e->ssq_part, c.rms_eps, st,
-                             w.qkv_bias);
+                             bias);
     if (rc) return rc;
   } else {
     rc = engine_gemv_xq(e, l, P_QKV, e->xq_hidden, e->qkv, e->ssq_part, nullptr, kNoXq, nullptr, nullptr, st);
@@ -279,8 +344,10 @@ static int engine_linear_f32(woq_engine* e, int l, Proj k, const float* act, int
   if (e->fp8_type != 0)
     return launch_gemv_fp8_engine(act, lda, p.blob, p.hdr, p.fp8_lo, e->fp8_type, out, ldo, norm_w, c.rms_eps, residual,
                                   c.hidden, kProjEpi[k], e->gu_tmp, st);
-  return launch_gemv_from_header(act, WOQ_F32, lda, p.blob, p.hdr, k == P_QKV ? e->layers[l].qkv_bias : nullptr, out,
-                                 WOQ_F32, ldo, 1, norm_w, c.rms_eps, residual, c.hidden, kProjEpi[k], st);
+  const float* bias = nullptr;
+  if (const int rc = engine_lora_bias(e, l, k, kNoXq, nullptr, act, norm_w, st, &bias)) return rc;
+  return launch_gemv_from_header(act, WOQ_F32, lda, p.blob, p.hdr, bias, out, WOQ_F32, ldo, 1, norm_w, c.rms_eps, residual,
+                                 c.hidden, kProjEpi[k], st);
 }
 
 static int engine_attn_block(woq_engine* e, int l, hipStream_t st) {
@@ -435,8 +502,36 @@ static int engine_step_impl(woq_engine* e, int greedy, hipStream_t st, int chain
 // M = batch * T rows (nn/modules.py:140-169). Same here: every linear is one MFMA GEMM over all rows
 // (woq_gemm_f16.hip: RMSNorm fused into the activation pack pass, residual add / SiLU*mul fused into the epilogue),
 // attention is one launch per layer over the KV cache (woq_prefill.hip). 6 launches + 4 pack passes per layer.
+
+// the adapters' share of the prompt pass's buffers: the shrink's output for `rows` rows and, while gate or up is
+// targeted somewhere, the un-activated gate/up rows
+static int engine_prefill_reserve_lora(woq_engine* e, size_t rows) {
+  const woq_engine_config& c = e->cfg;
+  bool any = false, gu = false;
+  for (int l = 0; l < c.layers; ++l)
+    for (int k = 0; k < P_COUNT; ++k)
+      if (e->lora_rows(l, k) > 0) any = true, gu = gu || k == P_GATE_UP;
+  if (any && rows > e->pf_t_rows) {
+    WOQ_HIP(hipDeviceSynchronize());
+    if (e->pf_t) WOQ_HIP(hipFree(e->pf_t));
+    e->pf_t = nullptr, e->pf_t_rows = 0;
+    WOQ_HIP(hipMalloc((void**)&e->pf_t, rows * (size_t)e->lora_ldt() * 4));
+    e->pf_t_rows = rows;
+  }
+  if (gu && rows > e->pf_gu_rows) {
+    WOQ_HIP(hipDeviceSynchronize());
+    if (e->pf_gu) WOQ_HIP(hipFree(e->pf_gu));
+    e->pf_gu = nullptr, e->pf_gu_rows = 0;
+    WOQ_HIP(hipMalloc((void**)&e->pf_gu, rows * (size_t)c.inter * 2 * 2));
+    e->pf_gu_rows = rows;
+  }
+  return 0;
+}
+
 static int engine_prefill_reserve(woq_engine* e, size_t rows) {
   const woq_engine_config& c = e->cfg;
+  if (e->lora_rmax > 0)
+    if (const int rc = engine_prefill_reserve_lora(e, rows)) return rc;
   // the largest call's workspace over EVERY layer's blobs: packed activation tiles + scales (+ the fragment image of a
   // table-type blob, so that such prompt passes allocate nothing per call either)
   size_t ws = 0;
@@ -463,14 +558,38 @@ static int engine_prefill_reserve(woq_engine* e, size_t rows) {
 // The prompt pass's GEMM call: projection k of layer l over M rows. The column-parallel ones (qkv, gate/up) read the
 // residual stream through RMSNorm `norm_w`, the row-parallel ones (o, down) add onto it.
 static int engine_prefill_gemm(woq_engine* e, int l, Proj k, int M, const void* act, int act_dtype, int lda, void* out,
-                               int out_dtype, int ldo, const float* norm_w, hipStream_t st) {
+                               int out_dtype, int ldo, const float* norm_w, hipStream_t st, int epi = -1) {
   const woq_engine_config& c = e->cfg;
   const EngineProj& p = e->layers[l].p[k];
   const bool rowp = k == P_O || k == P_DOWN;
   return launch_gemm_f16(act, act_dtype, lda, p.blob, p.hdr, k == P_QKV ? e->layers[l].qkv_bias : nullptr, out, out_dtype,
                          ldo, M, norm_w,
                          rowp ? 0.f : c.rms_eps, rowp ? e->tp_residual(e->pf_h) : nullptr, rowp ? c.hidden : 0,
-                         kProjEpi[k], e->pf_ws, 0, st, p.fp8_lo, e->fp8_type, e->pf_ws_bytes);
+                         epi < 0 ? kProjEpi[k] : epi, e->pf_ws, 0, st, p.fp8_lo, e->fp8_type, e->pf_ws_bytes);
+}
+
+// The adapter of (l, k) over the prompt pass's M rows (woq_lora.hip): T = inv * A . (X * norm_w), then the expand in the
+// kind's store mode. qkv: onto the fp16 q | k | v rows after the base GEMM (one more fp16 rounding of q, k, v than the
+// adapter-less pass has); o_proj / down_proj: onto the fp32 residual stream BEFORE the base GEMM, which adds onto it through
+// its residual slot; gate/up: the base GEMM left plain gate / up rows in pf_gu, the expand adds, applies SiLU * mul and
+// writes pf_act. Only called for a (layer, kind) with an adapter.
+static int engine_prefill_lora(woq_engine* e, int l, Proj k, int M, hipStream_t st) {
+  const woq_engine_config& c = e->cfg;
+  const woq_blob_header& h = e->layers[l].p[k].hdr;
+  const LoraDesc* d = e->lora_dev(l, k);
+  const EngineLayer& w = e->layers[l];
+  const void* x = k == P_O ? (const void*)e->pf_attn : k == P_DOWN ? (const void*)e->pf_act : (const void*)e->pf_h;
+  const bool f32 = k == P_QKV || k == P_GATE_UP;
+  const float* norm_w = k == P_QKV ? w.ln1 : k == P_GATE_UP ? w.ln2 : nullptr;
+  int rc = launch_lora_shrink(d, e->lora_rows(l, k), x, f32 ? WOQ_F32 : WOQ_F16, h.K, M, h.K, norm_w, c.rms_eps, e->pf_t,
+                              e->lora_ldt(), st);
+  if (rc) return rc;
+  switch (k) {
+    case P_QKV: return launch_lora_expand(d, e->pf_t, e->lora_ldt(), M, h.N, LORA_EXPAND_ADD_F16, e->pf_qkv, h.N, nullptr, 0, st);
+    case P_GATE_UP:
+      return launch_lora_expand(d, e->pf_t, e->lora_ldt(), M, h.N, LORA_EXPAND_SILU, e->pf_act, c.inter, e->pf_gu, h.N, st);
+    default: return launch_lora_expand(d, e->pf_t, e->lora_ldt(), M, h.N, LORA_EXPAND_ADD_F32, e->pf_h, c.hidden, nullptr, 0, st);
+  }
 }
 
 static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, int T, int start, int greedy,
@@ -487,17 +606,25 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
     uint8_t *kc = e->k_of(l), *vc = e->v_of(l);
     rc = engine_prefill_gemm(e, l, P_QKV, M, e->pf_h, WOQ_F32, c.hidden, e->pf_qkv, WOQ_F16, qkv_n, w.ln1, st);
     if (rc) return rc;
+    if (e->lora_rows(l, P_QKV) > 0 && (rc = engine_prefill_lora(e, l, P_QKV, M, st)) != 0) return rc;
     if ((rc = launch_rope_append(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, e->cs, e->sn, kc, vc,
                                  c.kv_dtype, seq_stride, st, w.q_norm, w.k_norm, c.rms_eps)) != 0)
       return rc;
     if ((rc = launch_attn_prefill(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, kc, vc, c.kv_dtype,
                                   seq_stride, e->pf_attn, e->window, st)) != 0)
       return rc;
+    if (e->lora_rows(l, P_O) > 0 && (rc = engine_prefill_lora(e, l, P_O, M, st)) != 0) return rc;
     rc = engine_prefill_gemm(e, l, P_O, M, e->pf_attn, WOQ_F16, c.heads * c.head_dim, e->pf_h, WOQ_F32, c.hidden, nullptr, st);
     if (rc) return rc;
     if ((rc = engine_allreduce_rows(e, e->pf_h, (size_t)M * c.hidden, st)) != 0) return rc;
-    rc = engine_prefill_gemm(e, l, P_GATE_UP, M, e->pf_h, WOQ_F32, c.hidden, e->pf_act, WOQ_F16, c.inter, w.ln2, st);
+    if (e->lora_rows(l, P_GATE_UP) > 0) {  // plain gate / up rows, then the adapter's expand applies SiLU * mul
+      rc = engine_prefill_gemm(e, l, P_GATE_UP, M, e->pf_h, WOQ_F32, c.hidden, e->pf_gu, WOQ_F16, 2 * c.inter, w.ln2, st, 0);
+      if (rc == 0) rc = engine_prefill_lora(e, l, P_GATE_UP, M, st);
+    } else {
+      rc = engine_prefill_gemm(e, l, P_GATE_UP, M, e->pf_h, WOQ_F32, c.hidden, e->pf_act, WOQ_F16, c.inter, w.ln2, st);
+    }
     if (rc) return rc;
+    if (e->lora_rows(l, P_DOWN) > 0 && (rc = engine_prefill_lora(e, l, P_DOWN, M, st)) != 0) return rc;
     rc = engine_prefill_gemm(e, l, P_DOWN, M, e->pf_act, WOQ_F16, c.inter, e->pf_h, WOQ_F32, c.hidden, nullptr, st);
     if (rc) return rc;
     if ((rc = engine_allreduce_rows(e, e->pf_h, (size_t)M * c.hidden, st)) != 0) return rc;
@@ -846,6 +973,8 @@ void woq_engine_destroy(woq_engine* e) {
   for (void* p : {(void*)e->pf_h, (void*)e->pf_qkv, (void*)e->pf_attn, (void*)e->pf_act, e->pf_ws})
     if (p) hipFree(p);
   if (e->score_ws) hipFree(e->score_ws);
+  if (e->pf_t) hipFree(e->pf_t);
+  if (e->pf_gu) hipFree(e->pf_gu);
   if (e->guide_table) hipFree(e->guide_table);
   delete e;
 }
@@ -870,6 +999,7 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
     WOQ_CHECK(all([&](const EngineProj& p) { return p.hdr.weight_type == qkv.weight_type; }),
               "QBits: an fp8 layer needs all four projections in the same fp8 type");
     WOQ_CHECK(c.tp_size <= 1, "QBits: fp8-weight layers run on one GPU (no tensor-parallel decode path)");
+    WOQ_CHECK(e->lora_rmax == 0, "QBits: fp8-weight layers do not take LoRA adapters (woq_engine_lora_reserve has run)");
   } else {
     // int4, or (round 4) a 4-bit table type: the same kernels with a digit-plane unpack (woq_gemv_common.h LutArgs); the
     // fused qkv + attention launch stays int4-only (its support check says no)
@@ -942,6 +1072,134 @@ int woq_engine_set_layer_extras(woq_engine* e, int layer, const float* qkv_bias_
   WOQ_END
 }
 
+// ---- unmerged LoRA adapters ------------------------------------------------------------------------------------------
+// target -> (projection kind, part of it, K, columns): q | k | v, o, gate / up, down
+enum { LORA_TARGETS = 7 };
+struct LoraTargetShape { Proj kind; int part, K, n; };
+static LoraTargetShape lora_target_shape(const woq_engine_config& c, int target) {
+  const int attn_k = c.heads * c.head_dim, kv_n = c.kv_heads * c.head_dim;
+  switch (target) {
+    case 0: return {P_QKV, 0, c.hidden, attn_k};
+    case 1: return {P_QKV, 1, c.hidden, kv_n};
+    case 2: return {P_QKV, 2, c.hidden, kv_n};
+    case 3: return {P_O, 0, attn_k, c.hidden};
+    case 4: return {P_GATE_UP, 0, c.hidden, c.inter};
+    case 5: return {P_GATE_UP, 1, c.hidden, c.inter};
+    default: return {P_DOWN, 0, c.inter, c.hidden};
+  }
+}
+// why this engine cannot carry adapters (null = it can)
+static const char* engine_lora_problem(const woq_engine* e) {
+  if (e->cfg.tp_size > 1 || e->comm != nullptr || e->allreduce != nullptr)
+    return "QBits: LoRA adapters run on one GPU (no tensor-parallel path)";
+  if (e->fp8_type != 0) return "QBits: fp8-weight layers do not take LoRA adapters (their engine GEMV takes no bias)";
+  return nullptr;
+}
+// the host mirror -> the device descriptors, between steps (steps in flight on any stream still read them)
+static int engine_lora_upload(woq_engine* e) {
+  WOQ_HIP(hipMemcpy(e->lora_desc, e->lora_host.data(), e->lora_host.size() * sizeof(LoraDesc), hipMemcpyHostToDevice));
+  WOQ_HIP(hipDeviceSynchronize());
+  return 0;
+}
+
+int woq_engine_lora_reserve(woq_engine* e, int r_max) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr, "QBits: null engine");
+  WOQ_CHECK(r_max >= 1 && r_max <= LORA_MAX_RANK, "QBits: LoRA ranks run from 1 to 64");
+  WOQ_CHECK(e->lora_rmax == 0, "QBits: woq_engine_lora_reserve runs once per engine");
+  if (const char* why = engine_lora_problem(e)) return woq::fail(why);
+  const woq_engine_config& c = e->cfg;
+  size_t a_floats = 0, b_floats = 0;  // of one layer, at rank 1
+  for (int t = 0; t < LORA_TARGETS; ++t) {
+    const LoraTargetShape s = lora_target_shape(c, t);
+    WOQ_CHECK(s.K >= 16 && (s.K & 15) == 0 && s.n >= 16 && (s.n & 15) == 0,
+              "QBits: LoRA adapters need every projection's rows and columns to be multiples of 16");
+    WOQ_CHECK(((size_t)s.K + LORA_MAX_ROWS + 4) * 4 <= (size_t)LORA_DELTA_MAX_LDS,
+              "QBits: the LoRA delta launch holds K up to 40000 input values");
+    a_floats += (size_t)s.K, b_floats += (size_t)s.n;
+  }
+  const size_t per_layer = (a_floats + b_floats) * r_max;  // every table's size is a multiple of 16 floats
+  const int qkv_n = (c.heads + 2 * c.kv_heads) * c.head_dim;
+  const size_t delta_floats = (size_t)qkv_n + c.hidden + 2 * (size_t)c.inter + c.hidden;
+  float* tab = nullptr;
+  LoraDesc* desc = nullptr;
+  WOQ_HIP(hipMalloc((void**)&tab, (per_layer * c.layers + delta_floats) * 4));
+  if (hipMalloc((void**)&desc, (size_t)c.layers * P_COUNT * sizeof(LoraDesc)) != hipSuccess) {
+    hipFree(tab);
+    return woq::fail("QBits: out of device memory for the LoRA descriptors");
+  }
+  WOQ_HIP(hipMemset(tab, 0, (per_layer * c.layers + delta_floats) * 4));
+  e->owned.push_back(tab);
+  e->owned.push_back(desc);
+  e->lora_tab.assign((size_t)c.layers * LORA_TARGETS, woq_engine::LoraTable{nullptr, nullptr});
+  e->lora_host.assign((size_t)c.layers * P_COUNT, LoraDesc{});
+  float* cur = tab;
+  for (int l = 0; l < c.layers; ++l) {
+    for (int k = 0; k < P_COUNT; ++k) {
+      LoraDesc& d = e->lora_host[(size_t)l * P_COUNT + k];
+      d.n_parts = k == P_QKV ? 3 : k == P_GATE_UP ? 2 : 1;
+      d.interleave = k == P_GATE_UP ? 1 : 0;
+    }
+    for (int t = 0; t < LORA_TARGETS; ++t) {
+      const LoraTargetShape s = lora_target_shape(c, t);
+      woq_engine::LoraTable& tb = e->lora_tab[(size_t)l * LORA_TARGETS + t];
+      tb.A = cur, cur += (size_t)s.K * r_max;
+      tb.B = cur, cur += (size_t)s.n * r_max;
+      e->lora_host[(size_t)l * P_COUNT + s.kind].part[s.part] = LoraPart{tb.A, tb.B, 0, s.n, 0.f, 0};
+    }
+  }
+  e->lora_delta[P_QKV] = cur, cur += qkv_n;
+  e->lora_delta[P_O] = cur, cur += c.hidden;
+  e->lora_delta[P_GATE_UP] = cur, cur += 2 * (size_t)c.inter;
+  e->lora_delta[P_DOWN] = cur;
+  e->lora_desc = desc;
+  e->lora_rmax = r_max;  // (no part has a rank yet: no step changes, the captured graphs stay)
+  return engine_lora_upload(e);
+  WOQ_END
+}
+
+int woq_engine_set_lora(woq_engine* e, int layer, int target, const float* a_dev, const float* b_dev, int r,
+                        float scaling) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr, "QBits: null engine");
+  WOQ_CHECK(e->lora_rmax > 0, "QBits: woq_engine_set_lora comes after woq_engine_lora_reserve");
+  if (const char* why = engine_lora_problem(e)) return woq::fail(why);
+  WOQ_CHECK(layer >= 0 && layer < e->cfg.layers, "QBits: bad layer index");
+  WOQ_CHECK(target >= 0 && target < LORA_TARGETS, "QBits: LoRA targets run from 0 (q_proj) to 6 (down_proj)");
+  WOQ_CHECK(e->layers[layer].kind != LAYER_UNSET, "QBits: woq_engine_set_lora comes after woq_engine_set_layer");
+  WOQ_CHECK(r >= 0 && r <= e->lora_rmax, "QBits: the adapter's rank exceeds the r_max of woq_engine_lora_reserve");
+  WOQ_CHECK(r == 0 || (a_dev != nullptr && b_dev != nullptr), "QBits: a LoRA target needs its A and B tables");
+  const LoraTargetShape s = lora_target_shape(e->cfg, target);
+  const size_t di = (size_t)layer * P_COUNT + s.kind;
+  const woq_engine::LoraTable& tb = e->lora_tab[(size_t)layer * LORA_TARGETS + target];
+  const bool was = e->lora_rows(layer, s.kind) > 0;
+  WOQ_HIP(hipDeviceSynchronize());  // steps in flight on any stream still read the tables
+  if (r > 0) {
+    WOQ_HIP(hipMemcpy(tb.A, a_dev, (size_t)r * s.K * 4, hipMemcpyDeviceToDevice));
+    WOQ_HIP(hipMemcpy(tb.B, b_dev, (size_t)s.n * r * 4, hipMemcpyDeviceToDevice));
+  }
+  LoraPart& P = e->lora_host[di].part[s.part];
+  P.r = r, P.s = r > 0 ? scaling : 0.f;
+  if (const int rc = engine_lora_upload(e)) return rc;
+  // which projections have an adapter decides which launches a captured step holds; ranks and values are device data
+  if ((e->lora_rows(layer, s.kind) > 0) != was) engine_drop_graphs(e);
+  WOQ_END
+}
+
+int woq_engine_clear_lora(woq_engine* e) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr, "QBits: null engine");
+  if (e->lora_rmax == 0 || e->lora_active_count() == 0) return 0;
+  WOQ_HIP(hipDeviceSynchronize());
+  for (LoraDesc& d : e->lora_host)
+    for (LoraPart& P : d.part) P.r = 0, P.s = 0.f;
+  if (const int rc = engine_lora_upload(e)) return rc;
+  engine_drop_graphs(e);
+  WOQ_END
+}
+
+int woq_engine_lora_on(woq_engine* e) { return e ? e->lora_active_count() : 0; }
+
 int woq_engine_set_head(woq_engine* e, const void* embed_dev, int embed_dtype, const float* final_norm_dev,
                         const void* lm_head_dev, int lm_head_dtype, const float* cos_dev, const float* sin_dev) {
   WOQ_TRY
@@ -978,6 +1236,7 @@ void* woq_engine_hidden_ptr(woq_engine* e) { return e->hidden; }
 int woq_engine_set_allreduce(woq_engine* e, woq_allreduce_fn fn, void* user) {
   WOQ_TRY
   WOQ_CHECK(e, "QBits: null engine");
+  WOQ_CHECK(fn == nullptr || e->lora_active_count() == 0, "QBits: LoRA adapters run on one GPU (no tensor-parallel path)");
   e->allreduce = fn;
   e->allreduce_user = user;
   WOQ_END
@@ -987,6 +1246,7 @@ int woq_engine_set_comm(woq_engine* e, woq_comm* comm, int vocab_offset) {
   WOQ_TRY
   WOQ_CHECK(e, "QBits: null engine");
   WOQ_CHECK(vocab_offset >= 0, "QBits: bad vocabulary offset");
+  WOQ_CHECK(comm == nullptr || e->lora_active_count() == 0, "QBits: LoRA adapters run on one GPU (no tensor-parallel path)");
   e->comm = comm;
   e->vocab_offset = vocab_offset;
   WOQ_END
@@ -1309,16 +1569,16 @@ int woq_engine_time_gemv_mask(woq_engine* e, int mask, int reps, void* stream, f
       int rc;
       if (e->use_xq()) {  // the step's own four GEMV launches: same kernels, epilogues, XQ outputs, residual chaining
         const bool last = l + 1 == c.layers;
-        if ((mask & 1) && (rc = engine_gemv_xq(e, l, P_QKV, e->xq_hidden, e->qkv, e->ssq_part, nullptr, kNoXq, nullptr,
+        if ((mask & 1) && (rc = engine_gemv_xq_base(e, l, P_QKV, e->xq_hidden, e->qkv, e->ssq_part, nullptr, kNoXq, nullptr,
                                                nullptr, st)) != 0)
           return rc;
-        if ((mask & 2) && (rc = engine_gemv_xq(e, l, P_O, e->xq_attn, e->hidden, nullptr, e->hidden, e->xq_hidden, w.ln2,
+        if ((mask & 2) && (rc = engine_gemv_xq_base(e, l, P_O, e->xq_attn, e->hidden, nullptr, e->hidden, e->xq_hidden, w.ln2,
                                                e->ssq_part, st)) != 0)
           return rc;
-        if ((mask & 4) && (rc = engine_gemv_xq(e, l, P_GATE_UP, e->xq_hidden, nullptr, e->ssq_part, nullptr, e->xq_act,
+        if ((mask & 4) && (rc = engine_gemv_xq_base(e, l, P_GATE_UP, e->xq_hidden, nullptr, e->ssq_part, nullptr, e->xq_act,
                                                nullptr, nullptr, st)) != 0)
           return rc;
-        if ((mask & 8) && (rc = engine_gemv_xq(e, l, P_DOWN, e->xq_act, e->hidden, nullptr, e->hidden,
+        if ((mask & 8) && (rc = engine_gemv_xq_base(e, l, P_DOWN, e->xq_act, e->hidden, nullptr, e->hidden,
                                                last ? kNoXq : e->xq_hidden, last ? nullptr : e->layers[l + 1].ln1,
                                                last ? nullptr : e->ssq_part, st)) != 0)
           return rc;

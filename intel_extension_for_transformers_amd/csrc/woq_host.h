@@ -283,6 +283,38 @@ int launch_attn_prefill(const _Float16* qkv, int n_seq, int T, int start, int he
 // last row of every sequence -> dst fp32 [n_seq][hidden]
 void launch_gather_last(const float* h, int n_seq, int T, int hidden, float* dst, hipStream_t st);
 
+// ---- woq_lora.hip: unmerged LoRA adapters beside the packed projections -------------------------------------------
+// One fused projection's adapter as the kernels read it from device memory: its parts in blob column order (q | k | v
+// concatenated; gate / up with `interleave`: 16-column tiles alternate gate, up as runtime.fuse_gate_up lays them out;
+// one part for o_proj and down_proj). Part p: A [r][K] and B [n][r] fp32, both dense, s = lora_alpha / r; r == 0 = the
+// part carries no adapter. The stacked rows of all parts' A (at most LORA_MAX_ROWS) index the shrink's output columns.
+constexpr int LORA_MAX_PARTS = 3, LORA_MAX_RANK = 64, LORA_MAX_ROWS = LORA_MAX_PARTS * LORA_MAX_RANK;
+constexpr int LORA_DELTA_MAX_LDS = 160 * 1024;  // the delta launch stages its K input values in LDS
+struct LoraPart { const float* A; const float* B; int32_t r, n; float s; int32_t reserved; };
+struct LoraDesc { LoraPart part[LORA_MAX_PARTS]; int32_t n_parts, interleave; };
+const char* lora_desc_problem(const LoraDesc& host_copy, int N);  // null, or the "QBits: ..." reason
+// decode: out[n] (fp32 [N], blob column order) = base_bias[n] (nullable = 0) + s_p * sum_j B_p[n'][j] * t_p[j],
+// t_p[j] = inv * sum_k A_p[j][k] * x[k]. XQ form: x = the decoded XQ vector, inv = 1 / sqrt(sum(ssq_in) / K + eps) when
+// ssq_in (K / 16 partial sums of squares) is given, else 1. fp32 form: x = x[k] * norm_w[k] and inv from the kernel's own
+// sum of squares of x when norm_w is given, else x as it stands and inv = 1. One launch whose geometry depends on K and N
+// alone; columns of a part with r == 0 receive base_bias bit for bit. K % 16 == 0, K <= 40000.
+int launch_lora_delta_xq(const LoraDesc* desc_dev, const XqPtrs& xin, const float* ssq_in, float eps, int K, int N,
+                         const float* base_bias, float* out, hipStream_t st);
+int launch_lora_delta_f32(const LoraDesc* desc_dev, const float* x, const float* norm_w, float eps, int K, int N,
+                          const float* base_bias, float* out, hipStream_t st);
+// prompt pass, shrink: T[m][j] (fp32 [M][ldt], j over the r_tot stacked rows) = inv_m * sum_k A[j][k] * g_k * X[m][k]; X
+// fp32 [M][ldx] with norm_w (g = norm_w, inv_m = the row's RMSNorm factor) or without, or fp16 without. r_tot = the sum
+// of the parts' ranks (the host's copy: it shapes the grid). K % 16 == 0, ldx % 4 == 0.
+int launch_lora_shrink(const LoraDesc* desc_dev, int r_tot, const void* X, int x_dtype, int ldx, int M, int K,
+                       const float* norm_w, float eps, float* T, int ldt, hipStream_t st);
+// prompt pass, expand: D[m][n] = s_p * sum_j T[m][roff_p + j] * B_p[n'][j] over the N blob columns, stored as
+//   ADD_F32  out fp32 [M][ldo] += D          ADD_F16  out fp16 [M][ldo] = fp16(out + D)
+//   SILU     (gate / up, interleave) out fp16 [M][ldo] (N / 2 columns) = SiLU(gu_gate + D_gate) * (gu_up + D_up) in fp32,
+//            gu = the base GEMM's fp16 [M][ld_gu] gate/up rows in blob column order
+enum LoraExpandMode { LORA_EXPAND_ADD_F32 = 0, LORA_EXPAND_ADD_F16 = 1, LORA_EXPAND_SILU = 2 };
+int launch_lora_expand(const LoraDesc* desc_dev, const float* T, int ldt, int M, int N, int mode, void* out, int ldo,
+                       const _Float16* gu, int ld_gu, hipStream_t st);
+
 // ---- woq_gemm_f16.hip: the prompt pass's MFMA GEMM ----------------------------------------------------------------
 // workspace bytes of one blob's [M, K] x [K, N] call, fragment image of the float weight types included (4-8x the
 // blob: what made table-type prompt passes allocate per call while the engine's workspace sat unused — ADVICE r04);

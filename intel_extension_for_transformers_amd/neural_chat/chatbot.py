@@ -24,6 +24,7 @@ def build_chatbot(config: PipelineConfig = None):
         "device": config.device,
         "use_cache": config.loading_config.use_cache,
         "peft_path": config.loading_config.peft_path,
+        "peft_on_engine": getattr(config.loading_config, "peft_on_engine", False),
         "use_neural_speed": config.loading_config.use_neural_speed,
         "gguf_model_path": config.loading_config.gguf_model_path,
         "optimization_config": config.optimization_config,

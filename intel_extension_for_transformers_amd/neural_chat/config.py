@@ -44,6 +44,9 @@ class GenerationConfig:
 @dataclass
 class LoadingModelConfig:
     peft_path: str = None
+    # peft_path's adapter on the fused decode engine, unmerged (optimize_transformers(model, adapters="unmerged")); the
+    # default keeps such a chatbot on the module path
+    peft_on_engine: bool = False
     use_cache: bool = True
     world_size: int = 1
     use_neural_speed: bool = False  # accepted for signature parity; must stay False here

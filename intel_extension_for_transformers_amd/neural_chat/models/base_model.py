@@ -58,18 +58,18 @@ class BaseModel:
                                                               device_map="cuda")
         if kwargs.get("peft_path"):
             # reference model_utils.py load_model: PeftModel.from_pretrained(model, peft_path), kept unmerged. Here the
-            # adapter goes over the blobs (llm/quantization/lora.py) and the model stays on the module path: the fused
-            # engine refuses unmerged adapters
+            # adapter goes over the blobs (llm/quantization/lora.py) and the model stays on the module path, unless
+            # LoadingModelConfig(peft_on_engine=True) asks for the engine to carry the adapter unmerged
             from ...transformers.llm.quantization.lora import load_peft_adapter
 
             load_peft_adapter(self.model, kwargs["peft_path"])
         self.model.eval()
         self.conv_template = self.get_default_conv_template()
-        self._try_engine()
+        self._try_engine("unmerged" if kwargs.get("peft_path") and kwargs.get("peft_on_engine") else None)
 
-    def _try_engine(self):
+    def _try_engine(self, adapters=None):
         """Build the fused decode engine when the model is a quantised Llama-class decoder; otherwise stay on the
-        module path (not an error)."""
+        module path (not an error). `adapters`: optimize_transformers' keyword."""
         self.engine = None
         if not hasattr(self.model, "quantization_config"):
             return
@@ -79,7 +79,7 @@ class BaseModel:
             if not engine_supports(self.model.config)[0]:  # the acceptance rule shared with `generate` and the TP host
                 return
             ctx = int(min(getattr(self.model.config, "max_position_embeddings", 2048) or 2048, 8192))
-            self.engine = optimize_transformers(self.model, max_ctx=ctx)
+            self.engine = optimize_transformers(self.model, max_ctx=ctx, adapters=adapters)
         except RuntimeError:
             self.engine = None
 

@@ -250,6 +250,117 @@ class WoqDecoderEngine:
         self._keep += [t for t in (qkv_bias, q_norm, k_norm) if t is not None]
         self.layer_tensors.setdefault(idx, {}).update(qkv_bias=qkv_bias, q_norm=q_norm, k_norm=k_norm)
 
+    # ---- unmerged LoRA adapters (include/woq_hip.h woq_engine_set_lora; csrc/woq_lora.hip) ----------------------------
+    def _lora_shape(self, target):
+        """(K, N) of a target's projection: A is [r, K], B is [N, r]"""
+        c = self.cfg
+        attn, kv = c.heads * c.head_dim, c.kv_heads * c.head_dim
+        return {"q_proj": (c.hidden, attn), "k_proj": (c.hidden, kv), "v_proj": (c.hidden, kv), "o_proj": (attn, c.hidden),
+                "gate_proj": (c.hidden, c.inter), "up_proj": (c.hidden, c.inter), "down_proj": (c.inter, c.hidden)}[target]
+
+    @staticmethod
+    def _lora_entries(source):
+        """{(layer, target name): (A, B, scaling)} of a model wrapped by `get_peft_model` / `load_peft_adapter`, of a
+        PEFT adapter directory (adapter_config.json + adapter_model.safetensors), or of such a dict itself."""
+        from ..transformers.llm.quantization import lora
+
+        def place(path):
+            parts = path.split(".")
+            if "layers" not in parts or parts[-1] not in L.LORA_TARGETS:
+                raise RuntimeError("QBits: the engine carries adapters on %s of the decoder layers; %r is not one"
+                                   % (" / ".join(L.LORA_TARGETS), path))
+            return int(parts[parts.index("layers") + 1]), parts[-1]
+
+        out = {}
+        if isinstance(source, dict):  # {(layer, target name): (A [r, K], B [N, r], scaling)} as it stands
+            for layer, target in source:
+                place("layers.%d.%s" % (int(layer), target))
+            return {(int(l), t): v for (l, t), v in source.items()}
+        if isinstance(source, (str, os.PathLike)):
+            from safetensors.torch import load_file
+
+            cfg = lora.LoraConfig.from_pretrained(source)
+            tensors = load_file(os.path.join(source, lora.WEIGHTS_NAME))
+            halves = {}
+            for key, t in tensors.items():
+                prefix, _, rest = key.partition("base_model.model.")
+                path, _, which = rest.rpartition(".lora_")
+                if prefix or which.split(".")[0] not in ("A", "B"):
+                    raise RuntimeError("QBits: adapter key %r is no LoRA weight" % key)
+                halves.setdefault(place(path), {})[which.split(".")[0]] = t
+            for where, ab in halves.items():
+                if set(ab) != {"A", "B"}:
+                    raise RuntimeError("QBits: the adapter holds only lora_%s for layer %d %s" % (next(iter(ab)), *where))
+                out[where] = (ab["A"], ab["B"], float(cfg.lora_alpha) / int(ab["A"].shape[0]))
+            return out
+        for name, m in lora._lora_modules(source):
+            if m.merged:
+                raise RuntimeError("QBits: %s is merged into its blob; unmerge() it or serve the merged model" % name)
+            out[place(name)] = (m.lora_A[m.active_adapter].weight, m.lora_B[m.active_adapter].weight, float(m.scaling))
+        return out
+
+    def _lora_kinds(self, placed):
+        kind = {"q_proj": 0, "k_proj": 0, "v_proj": 0, "o_proj": 1, "gate_proj": 2, "up_proj": 2, "down_proj": 3}
+        return {(l, kind[t]) for l, t in placed}
+
+    def set_lora(self, source, r_max=None):
+        """Installs the adapter of `source` (a model wrapped by `get_peft_model` / `load_peft_adapter`, a PEFT adapter
+        directory, or a dict {(layer, "q_proj" | ... | "down_proj"): (A [r, K], B [N, r], scaling)}) on the engine, unmerged: every targeted projection computes x W + scaling * (x A^T) B^T in
+        the decode step and the prompt pass. The values are COPIED (fp32): the engine sees those of the last `set_lora`,
+        whatever happens to the modules afterwards. Targets the previous adapter had and this one has not are removed.
+        `r_max` (default: this adapter's largest rank) sizes the engine's tables on the first call; a later adapter of
+        the same targets and ranks up to it keeps a captured graph."""
+        entries = self._lora_entries(source)
+        if not entries:
+            raise RuntimeError("QBits: no LoRA adapter found to install")
+        staged = {}
+        for (layer, target), (a, b, s) in entries.items():
+            K, N = self._lora_shape(target)
+            r = int(a.shape[0])
+            if not 0 <= layer < self.cfg.layers:
+                raise RuntimeError("QBits: the adapter names layer %d; the engine has %d" % (layer, self.cfg.layers))
+            if tuple(a.shape) != (r, K) or tuple(b.shape) != (N, r):
+                raise RuntimeError("QBits: layer %d %s: lora_A is %s and lora_B is %s; the engine's projection needs "
+                                   "[r, %d] and [%d, r]" % (layer, target, tuple(a.shape), tuple(b.shape), K, N))
+            if not 1 <= r <= L.LORA_MAX_RANK:
+                raise RuntimeError("QBits: LoRA ranks run from 1 to %d (layer %d %s has %d)" % (L.LORA_MAX_RANK, layer, target, r))
+            staged[(layer, target)] = (a.detach().to(self.device, torch.float32).contiguous(),
+                                       b.detach().to(self.device, torch.float32).contiguous(), r, float(s))
+        lib = L.lib()
+        biggest = max(v[2] for v in staged.values())
+        have = getattr(self, "lora_r_max", 0)
+        want = have or (int(r_max) if r_max is not None else biggest)
+        if biggest > want:  # (before anything changes)
+            raise RuntimeError("QBits: the adapter's rank (%d) exceeds the r_max of woq_engine_lora_reserve (%d)" % (biggest, want))
+        if have == 0:
+            L.check(lib.woq_engine_lora_reserve(self._h, want))
+            self.lora_r_max, self._lora_placed = want, set()
+        before = self._lora_kinds(self._lora_placed)
+        try:
+            for (layer, target), (a, b, r, s) in staged.items():
+                L.check(lib.woq_engine_set_lora(self._h, layer, L.LORA_TARGETS.index(target), a.data_ptr(), b.data_ptr(), r, s))
+                self._lora_placed.add((layer, target))
+            for layer, target in sorted(self._lora_placed - set(staged)):
+                L.check(lib.woq_engine_set_lora(self._h, layer, L.LORA_TARGETS.index(target), None, None, 0, 0.0))
+                self._lora_placed.discard((layer, target))
+        finally:
+            if self._lora_kinds(self._lora_placed) != before:
+                self.captured = False  # (the native side dropped its graphs: other launches in the step)
+
+    def clear_lora(self):
+        """Removes every installed adapter target: the step and the prompt pass are the adapter-less ones again."""
+        if getattr(self, "lora_r_max", 0) == 0:
+            return
+        L.check(L.lib().woq_engine_clear_lora(self._h))
+        if self._lora_placed:
+            self.captured = False
+        self._lora_placed = set()
+
+    @property
+    def lora_on(self):
+        """True while at least one projection of the engine carries an adapter."""
+        return L.lib().woq_engine_lora_on(self._h) > 0
+
     def set_head(self, embed, final_norm, lm_head, cos=None, sin=None, attention_factor=1.0):
         """`cos` / `sin`: caller-built tables (build_rope_tables) and the attention factor they were multiplied by."""
         self.rope_attention_factor = float(attention_factor)
@@ -1002,21 +1113,30 @@ def _same_order(parts, what):
     return idx[0]
 
 
-def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16):
+def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16, adapters=None):
     """Post-pass over a model returned by `AutoModelForCausalLM.from_pretrained(..., quantization_config=...)`:
     builds the native batch-1 decode engine over the SAME quantised weights (q/k/v fused along N, gate/up
     interleaved per 16-column tile for the fused SiLU*mul epilogue). Mirrors the two-step shape of the reference's
     Intel-GPU flow, `ipex.optimize_transformers(qmodel, ...)` after `from_pretrained`
     (docs/weightonlyquant.md:199-202). Llama-class decoders (RMSNorm, RoPE, gated SiLU MLP): Llama-2 / 3.x, Mistral,
-    Qwen2 (q / k / v biases) and Qwen3 (per-head q / k norm), with HF's default, linear, llama3 or yarn RoPE."""
+    Qwen2 (q / k / v biases) and Qwen3 (per-head q / k norm), with HF's default, linear, llama3 or yarn RoPE.
+
+    A model that holds unmerged LoRA adapters (`get_peft_model`, `load_peft_adapter`) is refused unless
+    `adapters="unmerged"`: the engine is then built over the adopted blobs and the model's adapter installed on it
+    (`WoqDecoderEngine.set_lora`: a copy — after training the adapter further, call `model.woq_engine.set_lora(model)`
+    again), and `model.generate` runs on the engine from then on."""
+    if adapters not in (None, "unmerged"):
+        raise ValueError("QBits: optimize_transformers(adapters=%r): None or \"unmerged\"" % (adapters,))
     cfg = model.config
     # anything the engine's kernels do not implement keeps the model on the module path instead of changing its maths
     ok, reason = engine_supports(cfg)
     if not ok:
         raise RuntimeError(reason)
-    if any(hasattr(m, "lora_A") for m in model.modules()):
-        raise RuntimeError("QBits: the fused decode engine does not run unmerged LoRA adapters (the model keeps the "
-                           "module path); fold them into the blobs with model.merge_and_unload() first")
+    has_adapters = any(hasattr(m, "lora_A") for m in model.modules())
+    if has_adapters and adapters is None:
+        raise RuntimeError("QBits: the fused decode engine does not run unmerged LoRA adapters by default (the model keeps "
+                           "the module path); fold them into the blobs with model.merge_and_unload() first (lossy: RTN), "
+                           "or pass optimize_transformers(model, adapters=\"unmerged\") to serve them as they are")
     rtype, rs = rope_scaling_of(cfg)
     layers = model.model.layers
     first = layers[0].self_attn.q_proj
@@ -1103,5 +1223,9 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16):
         cos, sin = build_rope_tables(max_ctx, head_dim, float(theta), dev, rope_scaling=rs, max_position_embeddings=mpe)
     eng.set_head(model.model.embed_tokens.weight.detach().to(head_dtype), model.model.norm.weight,
                  model.lm_head.weight.detach().to(head_dtype), cos, sin, attention_factor=att)
+    if has_adapters:
+        eng.set_lora(model)  # raises what the engine cannot carry (fp8 layers, ranks beyond 64): no engine then
+        model._woq_adapters = "unmerged"  # `generate` rebuilds a longer engine the same way
+        model._woq_engine_off = False
     model.woq_engine = eng
     return eng

@@ -9,8 +9,16 @@ their blobs, under PEFT's names and PEFT's on-disk format — without PEFT, whic
   * adapters are saved as `adapter_config.json` + `adapter_model.safetensors` with keys
     `base_model.model.<module path>.lora_A.weight`, so they move to and from PEFT.
 
-One adapter ("default") at a time; no DoRA, no rsLoRA, `bias="none"` only. The fused decode engine does not run
-unmerged adapters: such a model keeps the module path until `merge_and_unload()`.
+One adapter ("default") at a time; no DoRA, no rsLoRA, `bias="none"` only.
+
+Serving. A wrapped model keeps the module path by default (`get_peft_model` switches the engine-backed `generate` off),
+and `merge_and_unload()` is the lossy way onto the fused decode engine: it re-quantises W + scaling B A with RTN, and an
+act-order blob refuses it. `optimize_transformers(model, adapters="unmerged")` is the other way: the engine is built over
+the adopted blobs and carries the adapters as they are, x W_deq + scaling (x A^T) B^T in fp32 on q / k / v / o / gate /
+up / down of the decoder layers, ranks 1..64 (runtime/engine.py `WoqDecoderEngine.set_lora`, csrc/woq_lora.hip). The
+engine holds a COPY of lora_A / lora_B: it sees the values of the last `set_lora`, so after training further call
+`model.woq_engine.set_lora(model)` again. Not on the engine: tensor-parallel engines, fp8-weight layers, adapters on
+lm_head or the embeddings, several adapters in one step.
 """
 import json
 import math
@@ -170,10 +178,12 @@ def _lora_modules(model):
 
 
 def _engine_off(model, off):
-    """a decode engine built over the blobs knows nothing of the adapters: drop it, and keep `generate` on the modules"""
+    """a decode engine built over the blobs knows nothing of the adapters now on (or off) the model: drop it, and keep
+    `generate` on the modules until `optimize_transformers(model, adapters="unmerged")` opts in again"""
     if getattr(model, "woq_engine", None) is not None:
         model.woq_engine = None
     model._woq_engine_off = bool(off)
+    model._woq_adapters = None
 
 
 def print_trainable_parameters(model):

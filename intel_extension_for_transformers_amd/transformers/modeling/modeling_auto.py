@@ -409,7 +409,9 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
                 raise RuntimeError(no_stream % "ctx_size is longer than the model's positions")
             return hf_generate(inputs, generation_config=generation_config, **kwargs)
         try:
-            eng = optimize_transformers(self, max_ctx=1 << (ctx - 1).bit_length())
+            # (a model that opted in with optimize_transformers(adapters="unmerged") keeps its adapters on the longer engine)
+            eng = optimize_transformers(self, max_ctx=1 << (ctx - 1).bit_length(),
+                                        adapters=getattr(self, "_woq_adapters", None))
         except RuntimeError:  # not a Llama-class int4 model: the module path serves it
             self._woq_engine_off = True
             if guide is not None:
