@@ -496,6 +496,42 @@ WOQ_API void* woq_engine_logprob_ptr(woq_engine* e, int which);
 WOQ_API int   woq_engine_kv_shift(woq_engine* e, int seq, int n_keep, int n_discard, int n_cached, int move_pos, void* stream);
 WOQ_API void* woq_engine_discarded_ptr(woq_engine* e);                    /* int32[1] on the device */
 WOQ_API int   woq_engine_discarded_set(woq_engine* e, int value, void* stream);
+/* ---- H2O heavy-hitter KV eviction (reference kv_cache_compression/prune/h2o.py; csrc/woq_h2o.hip; new entry points
+ * only, WOQ_ABI_VERSION stays 4, no struct changes) ---------------------------------------------------------------------
+ * score[layer][kv head][p] (fp32) = the softmax probability row p received, summed over every query so far (the prompt
+ * rows under the causal mask, then one per decode step) and over the query heads of the kv group. With H2O installed a
+ * decode step runs the separate qkv | attention launches and one score launch per layer behind them, and a prompt pass of
+ * one sequence two score launches per layer behind its append; an engine without it launches what it launched before.
+ * woq_engine_set_h2o allocates the score ([layers][kv_heads][max_ctx], zeroed) and its scratch and drops captured graphs
+ * when it changes. Fails with a "QBits:" message on a tensor-parallel engine, with a sliding window, with max_batch > 1,
+ * for more than 16 query heads per kv head and for a head_dim other than 64 / 128.
+ * woq_engine_h2o_evict (sequence 0, a cache of n_cached rows): every (layer, kv head) drops the n_discard rows with the
+ * lowest score among rows [n_keep, n_cached - recent), ties to the lower row; kept rows keep their order and move down: V
+ * and score rows bit for bit, K rotated back by the angle of its own distance with woq_engine_kv_shift's arithmetic; the
+ * n_discard freed score rows are zeroed; move_pos as in woq_engine_kv_shift. recent == n_cached - n_keep - n_discard is
+ * woq_engine_kv_shift, byte for byte. Two launches (+ the words'), stream-ordered, capturable, nothing read back. */
+WOQ_API int   woq_engine_set_h2o(woq_engine* e, int on);
+WOQ_API int   woq_engine_h2o_reset(woq_engine* e, void* stream);          /* score = 0, stream-ordered */
+WOQ_API void* woq_engine_h2o_score_ptr(woq_engine* e);                    /* NULL before woq_engine_set_h2o(e, 1) */
+WOQ_API int   woq_engine_h2o_evict(woq_engine* e, int seq, int n_keep, int n_discard, int recent, int n_cached,
+                                   int move_pos, void* stream);
+/* The four kernels on caller buffers (device pointers; caches [layers][max_ctx][kv_heads * head_dim] in kv_dtype).
+ * score_decode: one layer; qkv = the step's fp32 un-rotated q | k | v, row *pos of kcache already appended; score
+ *   [kv_heads][max_ctx] += ; scratch = woq_h2o_decode_scratch_bytes bytes, zero before the first call (the kernel leaves
+ *   its counters zero). score_prompt: one layer; qkv = the chunk's fp16 rows with q rotated, cache rows [0, start + T)
+ *   written; lse = fp32 [heads][T] scratch. select: dst int32 [layers][kv_heads][max_ctx], rows [0, n_cached) written.
+ *   compact: score may be NULL. */
+WOQ_API size_t woq_h2o_decode_scratch_bytes(int kv_heads, int max_ctx);
+WOQ_API int   woq_h2o_score_decode(const void* qkv_f32, const void* kcache, int kv_dtype, int heads, int kv_heads,
+                                   int head_dim, int max_ctx, const void* pos_dev, const void* cos_dev, const void* sin_dev,
+                                   const void* q_norm, float eps, void* score, void* scratch, void* stream);
+WOQ_API int   woq_h2o_score_prompt(const void* qkv_f16, int T, int start, int heads, int kv_heads, int head_dim,
+                                   const void* kcache, int kv_dtype, int max_ctx, void* lse, void* score, void* stream);
+WOQ_API int   woq_h2o_select(const void* score, void* dst, int layers, int kv_heads, int max_ctx, int n_keep, int n_discard,
+                             int recent, int n_cached, void* stream);
+WOQ_API int   woq_h2o_compact(void* kcache, void* vcache, void* score, const void* dst, int kv_dtype, int layers,
+                              int kv_heads, int head_dim, int max_ctx, const void* cos_dev, const void* sin_dev, int n_keep,
+                              int n_discard, int n_cached, void* stream);
 /* ---- per-layer extras of Llama-class variants: Qwen2's q / k / v biases, Qwen3's q / k norm (new entry point only,
  * WOQ_ABI_VERSION stays 4, no struct changes) ----------------------------------------------------------------------------
  * optional per-layer extras of Llama-class variants; every pointer may be NULL (= absent); fp32 on the device;

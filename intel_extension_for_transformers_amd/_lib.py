@@ -102,6 +102,8 @@ EXPORTS = [
     "woq_autoround_forward", "woq_autoround_step", "woq_autoround_codes", "woq_teq_forward", "woq_teq_grad",
     "woq_linear_backward", "woq_linear_backward_workspace",
     "woq_engine_lora_reserve", "woq_engine_set_lora", "woq_engine_clear_lora", "woq_engine_lora_on",
+    "woq_engine_set_h2o", "woq_engine_h2o_reset", "woq_engine_h2o_score_ptr", "woq_engine_h2o_evict",
+    "woq_h2o_decode_scratch_bytes", "woq_h2o_score_decode", "woq_h2o_score_prompt", "woq_h2o_select", "woq_h2o_compact",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -247,6 +249,17 @@ def lib():
     L.woq_engine_discarded_ptr.restype = vp
     L.woq_engine_discarded_ptr.argtypes = [vp]
     L.woq_engine_discarded_set.argtypes = [vp, ci, vp]
+    L.woq_engine_set_h2o.argtypes = [vp, ci]
+    L.woq_engine_h2o_reset.argtypes = [vp, vp]
+    L.woq_engine_h2o_score_ptr.restype = vp
+    L.woq_engine_h2o_score_ptr.argtypes = [vp]
+    L.woq_engine_h2o_evict.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp]
+    L.woq_h2o_decode_scratch_bytes.restype = cs
+    L.woq_h2o_decode_scratch_bytes.argtypes = [ci, ci]
+    L.woq_h2o_score_decode.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp]
+    L.woq_h2o_score_prompt.argtypes = [vp, ci, ci, ci, ci, ci, vp, ci, ci, vp, vp, vp]
+    L.woq_h2o_select.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+    L.woq_h2o_compact.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp]
     L.woq_engine_set_sampler_controls.argtypes = [vp, ctypes.POINTER(SamplerControls), vp, vp]
     L.woq_engine_sampler_counts.argtypes = [vp, vp, ci, ci, vp]
     L.woq_engine_sampler_count_ptr.restype = vp
@@ -632,6 +645,39 @@ def probe_lora_expand(mode, T, M, N, parts, out, ldo, ldt=None, gu=None, ld_gu=0
     n, _, b, r, cols, s = _lora_parts(parts, False, True)
     check(lib().woq_probe_lora_expand(int(mode), _ptr(T), int(T.shape[-1] if ldt is None else ldt), int(M), int(N), n, b, r,
                                       cols, s, _ptr(out), int(ldo), _opt(gu), int(ld_gu), stream_ptr()))
+
+
+# ---- H2O eviction's kernels on caller tensors (include/woq_hip.h woq_h2o_*; csrc/woq_h2o.hip), the current stream ----
+def h2o_score_decode(qkv, kcache, kv_dtype, heads, kv_heads, head_dim, pos, cos, sin, score, scratch, q_norm=None,
+                     eps=0.0):
+    """One layer's decode score: `score` fp32 [kv_heads, max_ctx] += ; `kcache` [max_ctx, kv_heads, head_dim] with row
+    `pos[0]` appended; `scratch` = a zeroed byte tensor of `h2o_decode_scratch_bytes` (left with zero counters)."""
+    check(lib().woq_h2o_score_decode(_ptr(qkv), _ptr(kcache), kv_dtype, heads, kv_heads, head_dim, score.shape[-1],
+                                     _ptr(pos), _ptr(cos), _ptr(sin), None if q_norm is None else _ptr(q_norm), eps,
+                                     _ptr(score), _ptr(scratch), stream_ptr()))
+
+
+def h2o_decode_scratch_bytes(kv_heads, max_ctx):
+    return int(lib().woq_h2o_decode_scratch_bytes(kv_heads, max_ctx))
+
+
+def h2o_score_prompt(qkv, start, heads, kv_heads, head_dim, kcache, kv_dtype, lse, score):
+    """One layer's prompt score over the chunk `qkv` (fp16 [T, (heads + 2 kv_heads) * head_dim], q rotated) at `start`."""
+    check(lib().woq_h2o_score_prompt(_ptr(qkv), qkv.shape[0], start, heads, kv_heads, head_dim, _ptr(kcache), kv_dtype,
+                                     score.shape[-1], _ptr(lse), _ptr(score), stream_ptr()))
+
+
+def h2o_select(score, dst, n_keep, n_discard, recent, n_cached):
+    """`score` fp32 / `dst` int32 [layers, kv_heads, max_ctx]: dst[..., p] = the row p moves to, -1 = dropped."""
+    check(lib().woq_h2o_select(_ptr(score), _ptr(dst), score.shape[0], score.shape[1], score.shape[2], n_keep, n_discard,
+                               recent, n_cached, stream_ptr()))
+
+
+def h2o_compact(kcache, vcache, score, dst, kv_dtype, head_dim, cos, sin, n_keep, n_discard, n_cached):
+    """The gather along `dst`, in place; caches [layers, max_ctx, kv_heads, head_dim], `score` may be None."""
+    check(lib().woq_h2o_compact(_ptr(kcache), _ptr(vcache), None if score is None else _ptr(score), _ptr(dst), kv_dtype,
+                                dst.shape[0], dst.shape[1], head_dim, dst.shape[2], _ptr(cos), _ptr(sin), n_keep, n_discard,
+                                n_cached, stream_ptr()))
 
 
 def check(rc):

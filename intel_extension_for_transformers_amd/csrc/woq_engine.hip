@@ -203,6 +203,21 @@ struct woq_engine {
       for (int k = 0; k < P_COUNT; ++k) n += lora_rows(l, k) > 0 ? 1 : 0;
     return n;
   }
+  // H2O heavy-hitter eviction (woq_h2o.hip; woq_engine_set_h2o). With `h2o_on` a step's attention runs in the separate
+  // qkv | attention form (the fused launch keeps q in granules only) with one score launch per layer behind it, and the
+  // prompt pass of one sequence two score launches per layer behind its append. Allocated by the first set_h2o(e, 1)
+  bool h2o_on = false;
+  float* h2o_score = nullptr;    // fp32 [layers][kv_heads][max_ctx]
+  void* h2o_scratch = nullptr;   // the decode score's counters, slice partials and logits (one layer's: stream order)
+  int32_t* h2o_dst = nullptr;    // int32 [layers][kv_heads][max_ctx]: the selection's destination per source row
+  float* h2o_lse = nullptr;      // prompt pass: fp32 [heads][rows], grown on demand like pf_ws
+  size_t h2o_lse_rows = 0;
+  size_t h2o_layer_floats() const { return (size_t)cfg.kv_heads * cfg.max_ctx; }
+  woq::AttnOptions step_attn_opt() const {  // what a step asks of its attention
+    woq::AttnOptions o = attn_opt;
+    if (h2o_on) o.fuse_attn = false;
+    return o;
+  }
   // the token tail, decided here alone: the pick after the lm_head of a step (after_prompt: of a prompt pass)
   Tail tail(bool greedy, bool fuse_next, bool after_prompt) const;
   woq::SampleTail sample_tail() const;  // the buffers of a sampled pick
@@ -303,14 +318,24 @@ static int engine_row_parallel_xq(woq_engine* e, int l, Proj k, const XqPtrs& xi
                         e->tp_push());
 }
 
+// H2O: layer l's score launch of a step, behind the attention launch that appended the layer's K row (nothing without H2O)
+static int engine_h2o_score_step(woq_engine* e, int l, hipStream_t st) {
+  if (!e->h2o_on) return 0;
+  const woq_engine_config& c = e->cfg;
+  return launch_h2o_score_decode(e->qkv, e->k_of(l), c.kv_dtype, c.heads, c.kv_heads, c.head_dim, c.max_ctx, e->pos, e->cs,
+                                 e->sn, e->layers[l].q_norm, c.rms_eps, e->h2o_score + (size_t)l * e->h2o_layer_floats(),
+                                 e->h2o_scratch, st);
+}
+
 // XQ form of the two sub-blocks: the same five launches, activations handed over as limb blocks
 static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
   const woq_engine_config& c = e->cfg;
   const EngineLayer& w = e->layers[l];
   int rc = 0;
-  const AttnDecodePlan plan = e->attn_plan(l, e->attn_opt);
+  const AttnDecodePlan plan = e->attn_plan(l, e->step_attn_opt());
   const AttnDecodeIO io = e->attn_io(l, e->xq_attn);
   if (plan.form == ATTN_FUSED) {
+    if (e->h2o_on) return woq::fail("QBits: H2O needs the separate qkv | attention launches, the plan came out fused");
     const float* bias = nullptr;
     if ((rc = engine_lora_bias(e, l, P_QKV, e->xq_hidden, e->ssq_part, nullptr, nullptr, st, &bias)) != 0) return rc;
     rc = launch_gemv_xq_attn(plan, io, e->xq_hidden, w.p[P_QKV].blob, w.p[P_QKV].hdr, e->qkv_g, e->ssq_part, c.rms_eps, st,
@@ -321,6 +346,7 @@ static int engine_attn_block_xq(woq_engine* e, int l, hipStream_t st) {
     if (rc) return rc;
     rc = launch_attn_decode(plan, io, st);
     if (rc) return rc;
+    if ((rc = engine_h2o_score_step(e, l, st)) != 0) return rc;
   }
   // hidden += attn . W_o ; the new hidden leaves as the MLP's XQ input (times ln2) with its sums of squares
   return engine_row_parallel_xq(e, l, P_O, e->xq_attn, e->xq_hidden, w.ln2, e->ssq_part, st);
@@ -356,8 +382,9 @@ static int engine_attn_block(woq_engine* e, int l, hipStream_t st) {
   const EngineLayer& w = e->layers[l];
   int rc = engine_linear_f32(e, l, P_QKV, e->hidden, c.hidden, e->qkv, w.p[P_QKV].hdr.N, w.ln1, nullptr, st);
   if (rc) return rc;
-  rc = launch_attn_decode(e->attn_plan(l, e->attn_opt), e->attn_io(l, kNoXq), st);
+  rc = launch_attn_decode(e->attn_plan(l, e->step_attn_opt()), e->attn_io(l, kNoXq), st);
   if (rc) return rc;
+  if ((rc = engine_h2o_score_step(e, l, st)) != 0) return rc;
   return engine_linear_f32(e, l, P_O, e->attn, c.heads * c.head_dim, e->hidden, c.hidden, nullptr,
                            e->tp_residual(e->hidden), st);
 }
@@ -600,6 +627,16 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
   const size_t seq_stride = e->kv_layer_bytes / woq_dtype_size((uint32_t)c.kv_dtype) * c.layers;  // elements between sequences
   int rc = engine_prefill_reserve(e, (size_t)M);
   if (rc) return rc;
+  if (e->h2o_on) {
+    if (n_seq != 1) return woq::fail("QBits: H2O scores one sequence (prefill with n_seq 1)");
+    if ((size_t)T > e->h2o_lse_rows) {
+      WOQ_HIP(hipDeviceSynchronize());
+      if (e->h2o_lse) WOQ_HIP(hipFree(e->h2o_lse));
+      e->h2o_lse = nullptr, e->h2o_lse_rows = 0;
+      WOQ_HIP(hipMalloc((void**)&e->h2o_lse, (size_t)c.heads * T * 4));
+      e->h2o_lse_rows = (size_t)T;
+    }
+  }
   launch_embed_rows(e->embed, e->embed_dtype, tokens, M, c.hidden, e->pf_h, st);
   for (int l = 0; l < c.layers; ++l) {
     const EngineLayer& w = e->layers[l];
@@ -609,6 +646,10 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
     if (e->lora_rows(l, P_QKV) > 0 && (rc = engine_prefill_lora(e, l, P_QKV, M, st)) != 0) return rc;
     if ((rc = launch_rope_append(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, e->cs, e->sn, kc, vc,
                                  c.kv_dtype, seq_stride, st, w.q_norm, w.k_norm, c.rms_eps)) != 0)
+      return rc;
+    if (e->h2o_on && (rc = launch_h2o_score_prompt(e->pf_qkv, T, start, c.heads, c.kv_heads, c.head_dim, kc, c.kv_dtype,
+                                                   c.max_ctx, e->h2o_lse,
+                                                   e->h2o_score + (size_t)l * e->h2o_layer_floats(), st)) != 0)
       return rc;
     if ((rc = launch_attn_prefill(e->pf_qkv, n_seq, T, start, c.heads, c.kv_heads, c.head_dim, kc, vc, c.kv_dtype,
                                   seq_stride, e->pf_attn, e->window, st)) != 0)
@@ -809,7 +850,7 @@ int woq_engine_clear_status(woq_engine* e, void* stream) {
 }
 int woq_engine_fuse_attn(woq_engine* e) {
   if (!e || !e->use_xq() || e->layers.empty()) return 0;
-  return e->attn_plan(0, e->attn_opt).form == ATTN_FUSED ? 1 : 0;
+  return e->attn_plan(0, e->step_attn_opt()).form == ATTN_FUSED ? 1 : 0;
 }
 int woq_engine_attn_plan(woq_engine* e, int splits, int grouped, long long* out11) {
   WOQ_TRY
@@ -850,6 +891,71 @@ int woq_engine_discarded_set(woq_engine* e, int value, void* stream) {
   WOQ_TRY
   WOQ_CHECK(e != nullptr, "QBits: null engine");
   launch_i32_store(e->discarded, value, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+
+static void engine_drop_graphs(woq_engine* e);
+// H2O: the engine-level entry points (include/woq_hip.h)
+int woq_engine_set_h2o(woq_engine* e, int on) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr, "QBits: null engine");
+  const woq_engine_config& c = e->cfg;
+  if (on != 0) {
+    WOQ_CHECK(c.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+              "QBits: H2O eviction runs on one GPU (no tensor-parallel engine)");
+    WOQ_CHECK(e->window == 0, "QBits: H2O eviction does not combine with a sliding window");
+    WOQ_CHECK(e->max_batch == 1, "QBits: H2O eviction takes an engine of one sequence (max_batch 1)");
+    WOQ_CHECK(c.heads / c.kv_heads <= 16, "QBits: H2O takes at most 16 query heads per kv head");
+    WOQ_CHECK(c.head_dim == 64 || c.head_dim == 128, "QBits: H2O takes head_dim 64 or 128");
+    if (e->h2o_score == nullptr) {
+      const size_t score_bytes = (size_t)c.layers * e->h2o_layer_floats() * 4;
+      const size_t scratch_bytes = h2o_decode_scratch_bytes(c.kv_heads, c.max_ctx);
+      void *sc = nullptr, *ws = nullptr, *ds = nullptr;
+      WOQ_HIP(hipMalloc(&sc, score_bytes));
+      e->owned.push_back(sc);
+      WOQ_HIP(hipMalloc(&ws, scratch_bytes));
+      e->owned.push_back(ws);
+      WOQ_HIP(hipMalloc(&ds, score_bytes));
+      e->owned.push_back(ds);
+      WOQ_HIP(hipMemset(sc, 0, score_bytes));
+      WOQ_HIP(hipMemset(ws, 0, scratch_bytes));
+      WOQ_HIP(hipMemset(ds, 0xff, score_bytes));
+      e->h2o_score = (float*)sc, e->h2o_scratch = ws, e->h2o_dst = (int32_t*)ds;
+    }
+  }
+  if (e->h2o_on != (on != 0)) engine_drop_graphs(e);  // a captured step holds (or lacks) the score launches
+  e->h2o_on = on != 0;
+  WOQ_END
+}
+int woq_engine_h2o_reset(woq_engine* e, void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr && e->h2o_score != nullptr, "QBits: no H2O score before the first woq_engine_set_h2o(e, 1)");
+  launch_h2o_zero(e->h2o_score, (size_t)e->cfg.layers * e->h2o_layer_floats() * 4, (hipStream_t)stream);
+  WOQ_HIP(hipGetLastError());
+  WOQ_END
+}
+void* woq_engine_h2o_score_ptr(woq_engine* e) { return e ? e->h2o_score : nullptr; }
+// every argument is checked before the first launch, so a refused call leaves the cache as it was
+int woq_engine_h2o_evict(woq_engine* e, int seq, int n_keep, int n_discard, int recent, int n_cached, int move_pos,
+                         void* stream) {
+  WOQ_TRY
+  WOQ_CHECK(e != nullptr && e->h2o_on, "QBits: H2O eviction before woq_engine_set_h2o(e, 1)");
+  const woq_engine_config& c = e->cfg;
+  WOQ_CHECK(seq == 0, "QBits: H2O eviction: the engine scores sequence 0 only");
+  WOQ_CHECK(n_keep >= 0 && n_discard >= 1 && recent >= 0, "QBits: H2O needs n_keep >= 0, n_discard >= 1 and recent >= 0");
+  WOQ_CHECK((long long)n_keep + n_discard + recent <= n_cached,
+            "QBits: H2O: n_keep + n_discard + recent exceeds the cached positions");
+  WOQ_CHECK(n_cached <= c.max_ctx, "QBits: H2O: n_cached exceeds the engine's max_ctx");
+  WOQ_CHECK(e->cs != nullptr && e->sn != nullptr, "QBits: H2O eviction before woq_engine_set_head (no rotation tables)");
+  const hipStream_t st = (hipStream_t)stream;
+  if (const int rc = launch_h2o_select(e->h2o_score, e->h2o_dst, c.layers, c.kv_heads, c.max_ctx, n_keep, n_discard, recent,
+                                       n_cached, st))
+    return rc;
+  if (const int rc = launch_h2o_compact(e->kcache, e->vcache, e->h2o_score, e->h2o_dst, c.kv_dtype, c.layers, c.kv_heads,
+                                        c.head_dim, c.max_ctx, e->cs, e->sn, n_keep, n_discard, n_cached, st))
+    return rc;
+  if (move_pos != 0) launch_kv_shift_words(e->pos, e->discarded, n_discard, st);
   WOQ_HIP(hipGetLastError());
   WOQ_END
 }
@@ -976,6 +1082,7 @@ void woq_engine_destroy(woq_engine* e) {
   if (e->pf_t) hipFree(e->pf_t);
   if (e->pf_gu) hipFree(e->pf_gu);
   if (e->guide_table) hipFree(e->guide_table);
+  if (e->h2o_lse) hipFree(e->h2o_lse);
   delete e;
 }
 

@@ -240,6 +240,31 @@ int launch_kv_shift(void* kseq, void* vseq, int kv_dtype, int layers, int kv_hea
 void launch_kv_shift_words(int32_t* pos, int32_t* discarded, int n_discard, hipStream_t st);
 void launch_i32_store(int32_t* dst, int32_t v, hipStream_t st);  // *dst = v, stream-ordered, capturable
 
+// ---- woq_h2o.hip: H2O heavy-hitter eviction — score, select, compact ------------------------------------------------
+// Device scratch of launch_h2o_score_decode: arrival counters (zero before the first launch; every launch leaves them
+// zero), the slices' per-head (max, sum) and the logits of one layer.
+size_t h2o_decode_scratch_bytes(int kv_heads, int max_ctx);
+void launch_h2o_zero(void* p, size_t bytes, hipStream_t st);  // bytes (a multiple of 4) of zeros, a kernel: capturable
+// One layer of a decode step, after its K row was appended at *pos: score[kvh][p] (fp32 [kv_heads][max_ctx]) += the
+// probability row p <= *pos received from the kv group's query heads. q from the step's fp32 un-rotated qkv: q-norm
+// (nullable weights) and RoPE at *pos as the decode attention does them. One launch whose grid depends on max_ctx alone.
+int launch_h2o_score_decode(const float* qkv, const void* kcache, int kv_dtype, int heads, int kv_heads, int D, int max_ctx,
+                            const int32_t* pos, const float* cs, const float* sn, const float* q_norm, float eps,
+                            float* score, void* scratch, hipStream_t st);
+// One layer of a prompt chunk of one sequence, after launch_rope_append: score += the column sums of the chunk's causal
+// attention over cache rows [0, start + T). lse: fp32 [heads][T] scratch. Two launches.
+int launch_h2o_score_prompt(const _Float16* qkv, int T, int start, int heads, int kv_heads, int D, const void* kcache,
+                            int kv_dtype, int max_ctx, float* lse, float* score, hipStream_t st);
+// dst[l][kvh][p] (int32 [layers][kv_heads][max_ctx], p < n_cached) = the row p moves to, -1 for the n_discard rows with the
+// lowest score among [n_keep, n_cached - recent) (ties: the lower row goes)
+int launch_h2o_select(const float* score, int32_t* dst, int layers, int kv_heads, int max_ctx, int n_keep, int n_discard,
+                      int recent, int n_cached, hipStream_t st);
+// the gather along dst, in place: V and score rows (nullable) copied, K rows rotated back by table row p - dst[p]; score
+// rows [n_cached - n_discard, n_cached) are zeroed. One launch.
+int launch_h2o_compact(void* kseq, void* vseq, float* score, const int32_t* dst, int kv_dtype, int layers, int kv_heads,
+                       int D, int max_ctx, const float* cs, const float* sn, int n_keep, int n_discard, int n_cached,
+                       hipStream_t st);
+
 // ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
 // After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at
 // token[0] (chosen [max_rows]) and at the 20 best ids by (logit descending, id ascending) (top_id / top_lp

@@ -38,6 +38,12 @@ class GenerationConfig:
     ctx_size: int = None
     n_keep: int = None
     n_discard: int = None
+    # H2O heavy-hitter eviction over the same three (runtime.streaming.H2OConfig): with `recent` (newest rows never
+    # dropped: a count, or a ratio of ctx_size below 1) or the two ratios set, a full cache drops its least-attended rows
+    # instead of the oldest. heavy_ratio / recent_ratio: the reference's spelling as remembered, unverified
+    recent: float = None
+    heavy_ratio: float = None
+    recent_ratio: float = None
     logprobs: int = None  # 0..20: fill BaseModel.last_logprobs with every emitted token's log-probability + alternatives
 
 

@@ -257,11 +257,14 @@ class BaseModel:
 
     @staticmethod
     def _streaming(config):
-        """the request's StreamingConfig (GenerationConfig.ctx_size / n_keep / n_discard), None when none is set"""
+        """the request's StreamingConfig (GenerationConfig.ctx_size / n_keep / n_discard), an H2OConfig when `recent` or
+        the two ratios are set as well, None when none is set"""
         from ...runtime.streaming import streaming_from_keywords
 
         return streaming_from_keywords(getattr(config, "ctx_size", None), getattr(config, "n_keep", None),
-                                       getattr(config, "n_discard", None))
+                                       getattr(config, "n_discard", None), recent=getattr(config, "recent", None),
+                                       heavy_ratio=getattr(config, "heavy_ratio", None),
+                                       recent_ratio=getattr(config, "recent_ratio", None))
 
     def _sampler_controls(self, config):
         """the request's sampling controls as `iter_sampled_auto` keywords (neutral values where the config has none)"""

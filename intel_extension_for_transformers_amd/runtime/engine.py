@@ -18,7 +18,7 @@ from .. import qbits
 from . import request
 # the request loops live in runtime/request.py; their public names stay part of this module's API, like StreamingConfig
 from .request import DeviceSampler, _controls, generate_sampled, iter_sampled, iter_sampled_auto, request_seed  # noqa: F401
-from .streaming import StreamingConfig, plan_steps, plan_stream  # noqa: F401
+from .streaming import H2OConfig, StreamingConfig, plan_steps, plan_stream  # noqa: F401
 
 
 ENGINE_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")  # the one list: engine_supports reads it, nothing else does
@@ -205,6 +205,7 @@ class WoqDecoderEngine:
         self.native_sampled_requests = 0   # requests that ran with it (iter_generate)
         self.logprobs_on = False           # log-probability record after every chaining pick (set_logprobs)
         self.guide_installed = False       # token guide in the chaining tail (set_guide / clear_guide)
+        self.h2o_installed = False         # H2O attention scores kept by steps and prompt passes (set_h2o)
         self._guide = None                 # ... the TokenGuide, its prefix and whether set_guide installed the sampler
         self._guide_prefix = ()
         self._guide_owns_sampler = False
@@ -465,6 +466,39 @@ class WoqDecoderEngine:
     def set_discarded(self, value=0):
         """discarded = value, stream-ordered (a request starts from 0)."""
         L.check(L.lib().woq_engine_discarded_set(self._h, int(value), L.stream_ptr()))
+
+    def set_h2o(self, on=True):
+        """H2O heavy-hitter eviction (woq_engine_set_h2o; csrc/woq_h2o.hip): while on, every decode step and every prompt
+        chunk adds the attention each cached row received to a per-(layer, kv head) score, and `h2o_evict` may drop the
+        least-attended rows. Steps then run the separate qkv | attention launches plus one score launch per layer; a
+        change drops captured graphs. Off: the engine launches what it launched before."""
+        if on:
+            self._check_shiftable()
+        L.check(L.lib().woq_engine_set_h2o(self._h, int(bool(on))))
+        if self.h2o_installed != bool(on):
+            self.captured = False  # the engine dropped its graphs: a captured step holds (or lacks) the score launches
+        self.h2o_installed = bool(on)
+
+    def h2o_reset(self):
+        """scores = 0, stream-ordered (a request starts from 0)."""
+        L.check(L.lib().woq_engine_h2o_reset(self._h, L.stream_ptr()))
+
+    def h2o_scores(self):
+        """fp32 view [layers, kv_heads, max_ctx] of the scores: entry [l, h, p] = the softmax probability cache row p of
+        kv head h received in layer l, summed over the queries so far and the kv group's query heads."""
+        ptr = L.lib().woq_engine_h2o_score_ptr(self._h)
+        if not ptr:
+            raise RuntimeError("QBits: no H2O scores before set_h2o(True)")
+        return _device_view(ptr, (self.cfg.layers, self.cfg.kv_heads, self.cfg.max_ctx), self.device, "<f4")
+
+    def h2o_evict(self, n_keep, n_discard, recent, n_cached, move_pos=True):
+        """H2O's answer to a full cache of `n_cached` rows (woq_engine_h2o_evict): every (layer, kv head) drops the
+        `n_discard` lowest-scoring rows among [n_keep, n_cached - recent), ties to the lower row; the kept rows move down
+        in order, V and score bit for bit, K rotated back by its own distance. `move_pos` as in `kv_shift`. Issued on the
+        current stream: no synchronisation, no read-back."""
+        self._check_shiftable()
+        L.check(L.lib().woq_engine_h2o_evict(self._h, 0, int(n_keep), int(n_discard), int(recent), int(n_cached),
+                                             int(bool(move_pos)), L.stream_ptr()))
 
     def _check_shiftable(self):
         """The K re-rotation multiplies by a table row: right for any per-dimension frequency, wrong for tables scaled

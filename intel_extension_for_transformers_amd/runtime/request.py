@@ -11,7 +11,7 @@ built on the two iterators; so are `model.generate` (transformers/modeling/model
 import torch
 
 from .. import _lib as L
-from .streaming import plan_steps, plan_stream
+from .streaming import H2OConfig, plan_steps, plan_stream
 
 
 # ---- the shared pieces ------------------------------------------------------------------------------------------------
@@ -19,17 +19,34 @@ def _request(engine, driver, prompt_ids, max_new_tokens, logprobs, streaming, *a
     """The scope of one request around `driver(engine, ids, max_new_tokens, geometry, n_top, *args)`: everything that can
     refuse the request is checked before anything is launched, and with a rolling cache the request counts its dropped
     positions from 0 and leaves 0 behind however it ends (exhausted, closed, an exception) — one without `streaming`
-    always runs with 0."""
+    always runs with 0. `streaming` = an H2OConfig: the geometry carries `recent` as a fourth entry, the engine keeps
+    attention scores for the length of the request (`set_h2o`, scores from zero) and a full cache is answered with
+    `h2o_evict` (`_drop`)."""
     n_top = None if logprobs is None else _top_count(logprobs)
     ids = [int(t) for t in prompt_ids]
     geometry = engine._request_geometry(len(ids), max_new_tokens, streaming)
+    h2o = isinstance(streaming, H2OConfig)
     if streaming is not None:
         engine.set_discarded(0)
     try:
+        if h2o:
+            engine.set_h2o(True)
+            engine.h2o_reset()
         yield from driver(engine, ids, max_new_tokens, geometry, n_top, *args)
     finally:
         if streaming is not None:
             engine.set_discarded(0)
+        if h2o:
+            engine.set_h2o(False)
+
+
+def _drop(engine, geometry, n_cached, move_pos=True):
+    """The answer to a `("shift", n_cached)` event: the rolling cache's shift, or H2O's eviction when the request's
+    geometry carries `recent`."""
+    if len(geometry) > 3:
+        engine.h2o_evict(geometry[1], geometry[2], geometry[3], n_cached, move_pos=move_pos)
+    else:
+        engine.kv_shift(geometry[1], geometry[2], n_cached, move_pos=move_pos)
 
 
 def _top_count(logprobs):
@@ -92,7 +109,8 @@ def iter_generate(engine, prompt_ids, max_new_tokens, chunk=2048, burst=16, eos=
     is `(tokens, chosen_lps, top)` with `top` one list of N `(id, log-probability)` pairs per token, read back in
     the burst's one synchronisation. `streaming` = a StreamingConfig: the request runs over a rolling KV cache
     (`plan_stream`: bursts clipped at ctx_size, a `kv_shift` whenever the cache is full) and may be longer than
-    the cache; tokens and records are read at cache positions."""
+    the cache; tokens and records are read at cache positions. An H2OConfig in its place: the same schedule, but a full
+    cache drops its least-attended rows (`h2o_evict`) instead of the oldest."""
     return _request(engine, _chained, prompt_ids, max_new_tokens, logprobs, streaming, chunk, burst, eos)
 
 
@@ -109,7 +127,7 @@ def _chained(engine, ids, max_new_tokens, geometry, n_top, chunk, burst, eos):
 
 def _chained_bursts(engine, ids, max_new_tokens, geometry, n_top, chunk, burst, eos):
     n = len(ids)
-    ctx, n_keep, n_discard = geometry
+    ctx, n_keep, n_discard = geometry[:3]
     if engine.sampler_installed:
         engine.mark_seen(ids, clear=True)
         if engine.controls_installed:
@@ -135,7 +153,7 @@ def _chained_bursts(engine, ids, max_new_tokens, geometry, n_top, chunk, burst, 
     log = engine.token_log()
     for ev in plan_stream(n, max_new_tokens, ctx, n_keep, n_discard, burst):
         if ev[0] == "shift":  # the cache is full: drop n_discard positions, the device position follows
-            engine.kv_shift(n_keep, n_discard, ev[1])
+            _drop(engine, geometry, ev[1])  # (an H2OConfig: the least-attended rows instead of the oldest)
             continue
         _, p0, k = ev  # p0 = cache position the next step feeds
         engine.replay(k)
@@ -293,7 +311,7 @@ def iter_sampled(engine, prompt_ids, max_new_tokens, sampler, eos=(), burst=16, 
 
 def _host_fed(engine, ids, max_new_tokens, geometry, n_top, sampler, chunk, burst, eos):
     n = len(ids)
-    ctx, n_keep, n_discard = geometry
+    ctx, n_keep, n_discard = geometry[:3]
     # the cache position every step after the first token feeds, with the shifts between them
     steps = plan_steps(plan_stream(n, max_new_tokens, ctx, n_keep, n_discard, burst))
     dev = engine.device
@@ -311,7 +329,7 @@ def _host_fed(engine, ids, max_new_tokens, geometry, n_top, sampler, chunk, burs
             if made > 0:
                 ev = next(steps)
                 if ev[0] == "shift":  # the cache is full: drop n_discard positions, then feed n_cached - n_discard
-                    engine.kv_shift(n_keep, n_discard, ev[1], move_pos=False)
+                    _drop(engine, geometry, ev[1], move_pos=False)
                     ev = next(steps)
                     engine.pos.fill_(ev[1])
                 engine.step(greedy=False)  # logits of the token just chosen, at cache position ev[1]

@@ -39,8 +39,73 @@ class StreamingConfig:
         return "StreamingConfig(ctx_size=%r, n_keep=%r, n_discard=%r)" % (self.ctx_size, self.n_keep, self.n_discard)
 
 
-def streaming_from_keywords(ctx_size=None, n_keep=None, n_discard=None):
-    """Neural Speed's three generate keywords -> a StreamingConfig, or None when none of them is given."""
+class H2OConfig(StreamingConfig):
+    """H2O heavy-hitter eviction (reference kv_cache_compression/prune/h2o.py, docs/h2o.md) as a request option beside the
+    rolling cache: the same `ctx_size`, `n_keep`, `n_discard` and schedule (`plan_stream`), but when the cache is full
+    every (layer, kv head) drops the `n_discard` rows that received the least attention so far among rows
+    `[n_keep, ctx_size - recent)`, ties to the older row (`WoqDecoderEngine.h2o_evict`). `recent` = the newest rows that
+    are never dropped: a count, a ratio of `ctx_size` (a float below 1), or -1 = half of what `n_keep` and `n_discard`
+    leave. `recent == ctx_size - n_keep - n_discard` is the rolling cache itself.
+
+    `heavy_ratio` / `recent_ratio`: the reference's ratio spelling as remembered — UNVERIFIED against the reference tree,
+    which this project has no copy of. Given (both), they set `recent = recent_ratio * ctx_size` and
+    `n_discard = ctx_size - n_keep - recent - heavy_ratio * ctx_size`."""
+
+    def __init__(self, ctx_size=None, n_keep=4, n_discard=-1, recent=-1, heavy_ratio=None, recent_ratio=None):
+        StreamingConfig.__init__(self, ctx_size, n_keep, n_discard)
+        if (heavy_ratio is None) != (recent_ratio is None):
+            raise ValueError("QBits: H2O heavy_ratio and recent_ratio come together")
+        self.recent = recent
+        self.heavy_ratio = None if heavy_ratio is None else float(heavy_ratio)
+        self.recent_ratio = None if recent_ratio is None else float(recent_ratio)
+
+    def resolve(self, max_ctx, n_prompt=0):
+        """(ctx_size, n_keep, n_discard, recent), or ValueError: StreamingConfig's rule, plus recent >= 0 and
+        n_keep + n_discard + recent <= ctx_size."""
+        ctx = int(max_ctx) if self.ctx_size is None else self.ctx_size
+        disc, recent = self.n_discard, self.recent
+        if self.heavy_ratio is not None:
+            recent = int(self.recent_ratio * ctx)
+            disc = ctx - self.n_keep - recent - int(self.heavy_ratio * ctx)
+            if disc == -1:  # (-1 means "half" to the base rule; here it is a budget that does not fit)
+                disc = -2
+        ctx, keep, disc = StreamingConfig(ctx, self.n_keep, disc).resolve(max_ctx, n_prompt)
+        if isinstance(recent, float) and recent < 1.0:
+            recent = int(recent * ctx)
+        recent = (ctx - keep - disc) // 2 if recent == -1 else int(recent)
+        if recent < 0:
+            raise ValueError("QBits: H2O recent (%d) must be >= 0" % recent)
+        if keep + disc + recent > ctx:
+            raise ValueError("QBits: H2O n_keep (%d) + n_discard (%d) + recent (%d) exceeds ctx_size (%d)"
+                             % (keep, disc, recent, ctx))
+        return ctx, keep, disc, recent
+
+    def __repr__(self):
+        return "H2OConfig(ctx_size=%r, n_keep=%r, n_discard=%r, recent=%r, heavy_ratio=%r, recent_ratio=%r)" % (
+            self.ctx_size, self.n_keep, self.n_discard, self.recent, self.heavy_ratio, self.recent_ratio)
+
+
+def h2o_from_keywords(h2o_config=None, ctx_size=None, n_keep=None, n_discard=None, recent=None, heavy_ratio=None,
+                      recent_ratio=None):
+    """An H2OConfig from `h2o_config` (an H2OConfig, or a dict of its arguments) or from the keywords; None when neither
+    `h2o_config`, `recent` nor the ratios are given."""
+    if isinstance(h2o_config, H2OConfig):
+        return h2o_config
+    if h2o_config is not None:
+        return H2OConfig(**dict(h2o_config))
+    if recent is None and heavy_ratio is None and recent_ratio is None:
+        return None
+    return H2OConfig(ctx_size, 4 if n_keep is None else n_keep, -1 if n_discard is None else n_discard,
+                     -1 if recent is None else recent, heavy_ratio, recent_ratio)
+
+
+def streaming_from_keywords(ctx_size=None, n_keep=None, n_discard=None, h2o_config=None, recent=None, heavy_ratio=None,
+                            recent_ratio=None):
+    """Neural Speed's three generate keywords -> a StreamingConfig, or None when none of them is given. With `h2o_config`
+    (an H2OConfig or a dict of its arguments), `recent` or the two ratios: an H2OConfig (`h2o_from_keywords`)."""
+    h2o = h2o_from_keywords(h2o_config, ctx_size, n_keep, n_discard, recent, heavy_ratio, recent_ratio)
+    if h2o is not None:
+        return h2o
     if ctx_size is None and n_keep is None and n_discard is None:
         return None
     return StreamingConfig(ctx_size, 4 if n_keep is None else n_keep, -1 if n_discard is None else n_discard)

@@ -342,8 +342,10 @@ def _engine_generate(self, inputs=None, generation_config=None, **kwargs):
     # sinks whenever ctx_size positions are cached (runtime.streaming). HF's loop has no counterpart.
     from ...runtime.streaming import streaming_from_keywords
 
+    # `h2o_config=` (an H2OConfig or a dict of its arguments): the same schedule, but a full cache drops its least-attended
+    # rows (H2O, reference kv_cache_compression/prune/h2o.py) instead of the oldest; engine-backed path only
     streaming = streaming_from_keywords(kwargs.pop("ctx_size", None), kwargs.pop("n_keep", None),
-                                        kwargs.pop("n_discard", None))
+                                        kwargs.pop("n_discard", None), h2o_config=kwargs.pop("h2o_config", None))
     bad_words = opt("bad_words_ids")
     if guide is not None and bad_words:
         raise ValueError("`guide` together with `bad_words_ids` is not supported (it would need the product of the two "
