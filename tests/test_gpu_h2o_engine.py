@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 from intel_extension_for_transformers_amd.runtime.engine import H2OConfig, StreamingConfig
-from oracle import woq_oracle as orc
+from tests import h2o_reference as H
 from tests import kv_shift_reference as KR
 from tests.test_gpu_engine import _tiny
 
@@ -53,52 +53,39 @@ def test_scores_do_not_change_the_step_and_sum_to_the_queries_seen(eng):
     assert np.abs(total - G * n).max() <= G * n * n * 2.0 ** -23
 
 
-def test_scores_are_the_oracles_attention_summed_over_queries_and_group(tiny, monkeypatch):
+def test_scores_are_the_oracles_attention_summed_over_queries_and_group(tiny):
     """The wiring (q un-rotated with its bias, the layer's score rows, the K row appended before the launch, every prompt
     chunk counted): the prompt in two chunks and 8 steps against the fp32 CPU oracle, whose attention calls are wrapped to
-    add up their float64 probabilities. Bound: the engine's q and K lie within the prompt pass's 1e-2 of the oracle's
-    (the smoke bound; steps are tighter), so a logit is off by at most d = 2e-2 * max|logit| and a probability by the
-    factor exp(2 d)."""
+    add up their float64 probabilities (tests/h2o_reference.py). Bound: the engine's q and K lie within the prompt pass's
+    1e-2 of the oracle's (the smoke bound; steps are tighter), so a logit is off by at most d = 2e-2 * max|logit| and a
+    probability by the factor exp(2 d)."""
     eng, oracle, cfg = tiny
-    layers, KV, D = cfg["layers"], cfg["kv_heads"], cfg["head_dim"]
-    G = cfg["heads"] // KV
-    want, seen = np.zeros((layers, KV, CTX)), {"calls": 0, "logit": 0.0}
-
-    def add(q, k, start):
-        li, T, n = seen["calls"] % layers, q.shape[0], k.shape[0]
-        seen["calls"] += 1
-        s = np.einsum("tkgd,pkd->kgtp", q.reshape(T, KV, G, D).astype(np.float64), k.astype(np.float64)) / np.sqrt(D)
-        vis = np.arange(n)[None, :] <= start + np.arange(T)[:, None]
-        seen["logit"] = max(seen["logit"], float(np.abs(s[..., vis]).max()))
-        p = np.exp(np.where(vis, s, -np.inf))
-        want[li, :, :n] += (p / p.sum(-1, keepdims=True)).sum((1, 2))
-
-    dec, pro = orc.attn_decode, orc.attn_prompt
-    monkeypatch.setattr(orc, "attn_decode", lambda q, k, v: (add(q[None], k, k.shape[0] - 1), dec(q, k, v))[1])
-    monkeypatch.setattr(orc, "attn_prompt", lambda q, k, v, start, window=0: (add(q, k, start), pro(q, k, v, start, window))[1])
+    layers = cfg["layers"]
     eng.clear_status()
     eng.set_h2o(True)
     eng.h2o_reset()
     oracle.reset()
-    eng.prefill(PROMPT[:4], start_pos=0, greedy=False)
-    tok = int(eng.prefill(PROMPT[4:], start_pos=4, greedy=False)[0].argmax())
-    oracle.forward_prompt(PROMPT[:4], 0)
-    oracle.forward_prompt(PROMPT[4:], 4)
-    for p in range(len(PROMPT), len(PROMPT) + 8):
-        eng.token.fill_(tok)
-        eng.pos.fill_(p)
-        eng.step(greedy=False)
-        oracle.forward_token(tok, p)
-        tok = int(eng.logits.argmax())
+    with H.ScoreBook(layers, cfg["heads"], cfg["kv_heads"], cfg["head_dim"], CTX) as book:
+        eng.prefill(PROMPT[:4], start_pos=0, greedy=False)
+        tok = int(eng.prefill(PROMPT[4:], start_pos=4, greedy=False)[0].argmax())
+        oracle.forward_prompt(PROMPT[:4], 0)
+        oracle.forward_prompt(PROMPT[4:], 4)
+        for p in range(len(PROMPT), len(PROMPT) + 8):
+            eng.token.fill_(tok)
+            eng.pos.fill_(p)
+            eng.step(greedy=False)
+            oracle.forward_token(tok, p)
+            tok = int(eng.logits.argmax())
+    want = book.score
     got = eng.h2o_scores().cpu().numpy().astype(np.float64)
     eng.set_h2o(False)
     oracle.reset()
     n = len(PROMPT) + 8
-    d = 2e-2 * seen["logit"]
+    d = 2e-2 * book.logit
     rel = np.abs(got[..., :n] - want[..., :n]) / want[..., :n]
     print("largest logit %.3f, bound %.3e, worst relative score error %.3e, score spread %.2f .. %.2f"
-          % (seen["logit"], np.expm1(2 * d), rel.max(), want[..., :n].min(), want[..., :n].max()))
-    assert seen["calls"] == layers * 10 and eng.status() == 0
+          % (book.logit, np.expm1(2 * d), rel.max(), want[..., :n].min(), want[..., :n].max()))
+    assert book.calls == layers * 10 and eng.status() == 0
     assert (rel <= np.expm1(2 * d)).all() and not got[..., n:].any()
 
 
