@@ -187,6 +187,31 @@ WOQ_API int woq_linear_backward(const void* grad_out_dev, int grad_dtype, int ld
                                 void* stream);
 WOQ_API size_t woq_linear_backward_workspace(int M, const woq_blob_header* hdr);
 
+/* ---- the routed expert block of a sparse mixture-of-experts layer (no reference counterpart: the reference quantises
+ * linears only; the definition is HF's MixtralExperts / Qwen3MoeExperts forward; new entry points only, WOQ_ABI_VERSION
+ * stays 4) ---------------------------------------------------------------------------------------------------------------
+ * out[t] = sum_j topk_w[t][j] * down_e( SiLU(gate_e x_t) * up_e x_t ), e = topk_idx[t][j], summed in the order
+ * j = 0 .. top_k - 1. x [T, ldx >= hidden] and out [T, ldo >= hidden] are fp32 | bf16 | fp16; topk_idx [T, top_k] is
+ * int32, or int64 when idx_is_int64 (what torch.topk yields); topk_w [T, top_k] fp32. An id outside [0, E) drops its slot:
+ * it contributes zero. The E gate/up blobs (K = hidden, N = 2 * inter, columns [0, inter) gate and [inter, 2 * inter)
+ * up) lie gate_up_stride bytes apart from gate_up_blobs_dev and share the host header gate_up_hdr; the E down blobs
+ * (K = inter, N = hidden) likewise. Weight types: int4 / int3 / int2, sym and asym, every group size and both scale
+ * modes, no act-order; inter % 16 == 0 and hidden % 4 == 0; at most 1024 experts and 8192 routed slots (T * top_k) a
+ * call. Anything else fails with a "QBits:" message, launching nothing. Four launches (plan, gate/up, down, combine:
+ * csrc/woq_moe.hip, DESIGN.md "Mixture-of-experts") whose shapes do not depend on the routing; stream-ordered, no host
+ * synchronisation, no allocation, no floating-point atomics: the same inputs give the same bytes. Activations go
+ * through the decode GEMV's exact fixed point (|x - x~| <= max|x_chunk| 2^-22 per 1024-k chunk of a row), everything
+ * after it is fp32.
+ *
+ * woq_moe_workspace: bytes of device scratch one call takes (16-byte aligned): the plan's tables and the fp32 rows
+ * [T * top_k][inter] and [T * top_k][hidden]. 0 for a shape outside the limits above. */
+WOQ_API size_t woq_moe_workspace(int T, int top_k, int E, int hidden, int inter);
+WOQ_API int woq_moe_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,
+                            const float* topk_w_dev, int T, int top_k, int E, const void* gate_up_blobs_dev,
+                            const woq_blob_header* gate_up_hdr, size_t gate_up_stride, const void* down_blobs_dev,
+                            const woq_blob_header* down_hdr, size_t down_stride, void* out_dev, int out_dtype, int ldo,
+                            void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device
  * memory from the host. */

@@ -104,6 +104,7 @@ EXPORTS = [
     "woq_engine_lora_reserve", "woq_engine_set_lora", "woq_engine_clear_lora", "woq_engine_lora_on",
     "woq_engine_set_h2o", "woq_engine_h2o_reset", "woq_engine_h2o_score_ptr", "woq_engine_h2o_evict",
     "woq_h2o_decode_scratch_bytes", "woq_h2o_score_decode", "woq_h2o_score_prompt", "woq_h2o_select", "woq_h2o_compact",
+    "woq_moe_workspace", "woq_moe_forward",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -164,6 +165,10 @@ def lib():
     L.woq_linear_backward.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, ci, ci, ci, vp]
     L.woq_linear_backward_workspace.restype = cs
     L.woq_linear_backward_workspace.argtypes = [ci, ctypes.POINTER(BlobHeader)]
+    L.woq_moe_workspace.restype = cs
+    L.woq_moe_workspace.argtypes = [ci] * 5
+    L.woq_moe_forward.argtypes = [vp, ci, ci, vp, ci, vp, ci, ci, ci, vp, ctypes.POINTER(BlobHeader), cs, vp,
+                                  ctypes.POINTER(BlobHeader), cs, vp, ci, ci, vp, cs, vp]
     L.woq_read_header.argtypes = [vp, ctypes.POINTER(BlobHeader), vp]
     L.woq_blob_extract.argtypes = [vp, ctypes.POINTER(BlobHeader), ci, vp, vp]
     L.woq_linear.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, vp, ci, ci, ci, vp]

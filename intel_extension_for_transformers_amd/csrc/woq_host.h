@@ -265,6 +265,26 @@ int launch_h2o_compact(void* kseq, void* vseq, float* score, const int32_t* dst,
                        int D, int max_ctx, const float* cs, const float* sn, int n_keep, int n_discard, int n_cached,
                        hipStream_t st);
 
+// ---- woq_moe.hip: the routed expert block of a sparse mixture-of-experts layer --------------------------------------
+constexpr int MOE_BLOCK_ROWS = 16;      // rows of one block of the plan's table: four MFMA row sets of four tokens
+constexpr int MOE_MAX_EXPERTS = 1024;   // the plan's histogram lives in LDS
+constexpr int MOE_MAX_SLOTS = 8192;     // routed slots T * top_k of one call: the plan keeps their ids in LDS
+// One call (include/woq_hip.h woq_moe_forward, which checks all of it): E blobs of each kind at a uniform stride under
+// one header, the routing on the device, `workspace` of woq_moe_workspace bytes.
+struct MoeCall {
+  const void* x; int x_dtype, ldx;
+  const void* topk_idx; bool idx_is_int64; const float* topk_w;
+  int T, top_k, E;
+  const void* gate_up_blobs; const woq_blob_header* gate_up_hdr; size_t gate_up_stride;
+  const void* down_blobs; const woq_blob_header* down_hdr; size_t down_stride;
+  void* out; int out_dtype, ldo;
+  void* workspace;
+};
+// null when the grouped launches take expert blobs under this header at this stride, else the "QBits: ..." reason
+const char* moe_header_problem(const woq_blob_header& h, size_t stride);
+// plan, gate/up, down, combine: four launches shaped by (T, top_k, E, hidden, inter) alone, no host synchronisation
+int launch_moe_forward(const MoeCall& m, hipStream_t st);
+
 // ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
 // After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at
 // token[0] (chosen [max_rows]) and at the 20 best ids by (logit descending, id ascending) (top_id / top_lp

@@ -1,0 +1,524 @@
+// woq_moe.hip — the routed expert block of a sparse mixture-of-experts layer over int4 blobs:
+//   out[t] = sum_j topk_w[t][j] * down_e( SiLU(gate_e x_t) * up_e x_t ),  e = topk_idx[t][j],  j = 0 .. k-1 in that order
+// with E gate/up blobs (K = H, N = 2 I, columns [0, I) gate and [I, 2 I) up) and E down blobs (K = I, N = H), each kind
+// at one uniform byte stride and under one header. The definition is HF's MixtralExperts / Qwen3MoeExperts forward (a
+// one-hot mask, nonzero() on the host, two F.linear and an index_add_ per hit expert); an id outside [0, E) drops its
+// slot there and here.
+//
+// Four launches whose shapes depend on (T, k, E, H, I) alone — the routing never reaches the host:
+//  1. plan (one workgroup): histogram of the ids over experts in LDS, exclusive scan, a STABLE scatter of the slot ids
+//     s = t k + j into expert order (sorted[], and its inverse pos_of[], -1 for a dropped slot), and a table of blocks
+//     {expert, first sorted slot, rows <= 16} with its count. The count is not known to the host, so launches 2 and 3
+//     size their grids for the bound ceil(T k / 16) + min(E, T k) and a workgroup past the count returns.
+//  2. gate/up: a workgroup = one block of <= 16 rows x one pair of 16-column tiles (gate tile tn, up tile tn + I / 16).
+//  3. down: the same inner loop with K = I, one 16-column tile per workgroup, fp32 rows y[sorted slot][H].
+//  4. combine: out[t][n] = sum_j w[t][j] y[pos_of[t k + j]][n], j ascending, rounded once to the output type.
+// No floating-point atomics and a fixed summation order everywhere: the same inputs give the same bytes.
+//
+// The inner loop (2 and 3). The blob tile is the B fragment of v_mfma_i32_16x16x64_i8 (include/woq_blob.h) and int4_b
+// makes the operand in three VALU instructions. The A operand is woq_gemv_i8.hip's: an activation row becomes the exact
+// 22-bit + sign fixed point relative to its maximum, carried as three int8 limb rows plus a ones row — four activation
+// rows per MFMA row set, four row sets per block. K is walked in chunks of 1024 (8 tiles): the workgroup stages the
+// chunk of its <= 16 rows as limbs in LDS (wave w: rows w, w + 4, ...; a row's fixed-point scale is per chunk, so an
+// I of 14336 never has to fit at once), then its four waves interleave over the chunk's tiles (wave w: tiles w, w + 4).
+// A wave requests its two tiles' weight words before the staging, so they fly under it; each tile's words are loaded once
+// and meet all row sets. Per-group scales (and zero points: sum_k (q - zp) x = sum_k q x - zp sum_k x, the second sum
+// from an MFMA against ones) are applied in fp32 after limb_combine, per tile (scale_mode 0) or per 32-k block
+// (scale_mode 1: each 64-k MFMA is issued twice, the other 32-k half's A operand read from a block of zeros). The
+// waves' partial sums meet in LDS and are added in wave order.
+#include <math.h>
+
+#include <algorithm>
+#include <string>
+
+#include "woq_gemv_common.h"
+#include "woq_host.h"
+
+namespace woq {
+namespace {
+
+constexpr int MOE_KC = 1024;              // k per staged chunk
+constexpr int MOE_TPC = MOE_KC / 128;     // weight tiles per chunk
+constexpr int MOE_RB = MOE_KC + 16;       // bytes of a limb row in LDS (+16: rows on distinct banks)
+constexpr int MOE_WAVES = 4;
+constexpr int MOE_TPW = MOE_TPC / MOE_WAVES;  // tiles of a chunk per wave
+constexpr int MOE_PLAN_THREADS = 1024;
+
+struct MoeBlock {
+  int32_t expert, first, rows, pad;
+};
+
+// ---- 1. plan ---------------------------------------------------------------------------------------------------------
+template <bool IDX64>
+__global__ __launch_bounds__(MOE_PLAN_THREADS) void moe_plan_kernel(const void* __restrict__ topk_idx, int S, int E,
+                                                                    int32_t* __restrict__ sorted,
+                                                                    int32_t* __restrict__ pos_of,
+                                                                    MoeBlock* __restrict__ blocks,
+                                                                    int32_t* __restrict__ nblocks) {
+  __shared__ int32_t ids[MOE_MAX_SLOTS];
+  __shared__ int32_t cnt[MOE_MAX_EXPERTS], off[MOE_MAX_EXPERTS];
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  for (int e = tid; e < E; e += nthr) cnt[e] = 0;
+  __syncthreads();
+  for (int s = tid; s < S; s += nthr) {
+    const long long v = IDX64 ? (long long)((const int64_t*)topk_idx)[s] : (long long)((const int32_t*)topk_idx)[s];
+    const int e = (v >= 0 && v < (long long)E) ? (int)v : -1;
+    ids[s] = e;
+    if (e >= 0)
+      atomicAdd(&cnt[e], 1);  // an integer count: the result does not depend on the order
+    else
+      pos_of[s] = -1;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0, nb = 0;
+    for (int e = 0; e < E; ++e) {
+      const int c = cnt[e];
+      off[e] = run;
+      for (int r = 0; r < c; r += MOE_BLOCK_ROWS) blocks[nb++] = MoeBlock{e, run + r, min(MOE_BLOCK_ROWS, c - r), 0};
+      run += c;
+    }
+    *nblocks = nb;
+  }
+  __syncthreads();
+  // stable: expert e's thread walks the slots in ascending order (every thread reads the same LDS word: a broadcast)
+  for (int e = tid; e < E; e += nthr) {
+    if (cnt[e] == 0) continue;
+    int p = off[e];
+    for (int s = 0; s < S; ++s) {
+      if (ids[s] == e) {
+        sorted[p] = s;
+        pos_of[s] = p;
+        ++p;
+      }
+    }
+  }
+}
+
+// ---- 2 / 3. the grouped product --------------------------------------------------------------------------------------
+struct MoeGemmArgs {
+  const uint8_t* blobs;  // expert e's blob at blobs + e * stride
+  size_t stride, off_q, off_scale, off_zp;
+  int K, N, tiles_k, n_groups, group, scale_type;
+  const void* x;  // gate/up: activations [T, ldx] of x_dtype; down: fp32 rows [sorted slot][ldx]
+  int x_dtype, ldx, top_k;
+  const int32_t* sorted;
+  const MoeBlock* blocks;
+  const int32_t* nblocks;
+  float* out;  // gate/up: SiLU(g) * u [sorted slot][ldo]; down: y [sorted slot][ldo]
+  int ldo, half_tiles;
+};
+
+__device__ __forceinline__ float moe_scale(const void* s, size_t i, int st) {
+  if (st == WOQ_F32) return ((const float*)s)[i];
+  const uint16_t b = ((const uint16_t*)s)[i];
+  return st == WOQ_BF16 ? bf16_bits_to_f32(b) : f16_bits_to_f32(b);
+}
+
+// GU: the gate/up launch (two column tiles, SiLU * mul epilogue, rows gathered by token) | the down launch
+template <bool GU, int SMODE, bool ASYM>
+__global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmArgs a) {
+  constexpr int CB = GU ? 2 : 1;
+  constexpr int NS = SMODE == 1 ? 4 : 1;  // scales of a tile and column
+  __shared__ __attribute__((aligned(16))) unsigned char strip[MOE_BLOCK_ROWS * 3 * MOE_RB];  // [row][limb][MOE_RB]
+  __shared__ __attribute__((aligned(16))) unsigned char zero_blk[64], ones_blk[64];
+  __shared__ float unsc_s[MOE_BLOCK_ROWS];  // per row: 2^(e - 25) of the staged chunk
+  __shared__ float slab[MOE_WAVES][4][CB][64];
+
+  const int b = (int)blockIdx.y;
+  if (b >= *a.nblocks) return;
+  const MoeBlock blk = a.blocks[b];
+  const int expert = __builtin_amdgcn_readfirstlane(blk.expert), first = __builtin_amdgcn_readfirstlane(blk.first);
+  const int R = __builtin_amdgcn_readfirstlane(blk.rows);
+  const int nrs = (R + 3) >> 2;  // live row sets
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int i16 = lane & 15, kq = lane >> 4;
+  if (tid < 16) {
+    ((uint32_t*)zero_blk)[tid] = 0u;
+    ((uint32_t*)ones_blk)[tid] = 0x01010101u;
+    unsc_s[tid] = 0.f;
+  }
+
+  const uint8_t* blob = a.blobs + (size_t)expert * a.stride;
+  const u32x4* q = (const u32x4*)(blob + a.off_q);
+  const void* scales = blob + a.off_scale;
+  const uint8_t* zps = blob + a.off_zp;
+  int tn[CB];
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) tn[cb] = (int)blockIdx.x + cb * a.half_tiles;
+
+  float acc[4][CB];
+#pragma unroll
+  for (int rs = 0; rs < 4; ++rs)
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) acc[rs][cb] = 0.f;
+  const i32x4 izero = {0, 0, 0, 0};
+  const i32x4 b_ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+  const int a_m = i16 >> 2, a_part = i16 & 3;
+
+  const int nchunks = (a.tiles_k + MOE_TPC - 1) / MOE_TPC;
+#pragma unroll 1
+  for (int c = 0; c < nchunks; ++c) {
+    // ---- this wave's tiles of the chunk: weight words, scales, zero points — requested before the staging ----
+    u32x4 w[MOE_TPW][CB];
+    float sc[MOE_TPW][CB][NS];
+    int uz[MOE_TPW][CB][NS];
+#pragma unroll
+    for (int ti = 0; ti < MOE_TPW; ++ti) {
+      const int kt = c * MOE_TPC + wid + ti * MOE_WAVES;
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) {
+        w[ti][cb] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) sc[ti][cb][s] = 0.f, uz[ti][cb][s] = 8;
+        if (kt >= a.tiles_k) continue;
+        w[ti][cb] = __builtin_nontemporal_load(q + ((size_t)tn[cb] * a.tiles_k + kt) * 64 + lane);
+        if constexpr (SMODE == 0) {
+          const int grp = a.n_groups == 1 ? 0 : min(kt * 128 / a.group, a.n_groups - 1);
+          const size_t si = ((size_t)tn[cb] * a.n_groups + grp) * 16 + i16;
+          sc[ti][cb][0] = moe_scale(scales, si, a.scale_type);
+          if constexpr (ASYM) uz[ti][cb][0] = (int)zps[si];
+        } else {
+          const size_t si = (((size_t)tn[cb] * a.tiles_k + kt) * 16 + i16) * 4;
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            sc[ti][cb][s] = moe_scale(scales, si + s, a.scale_type);
+            if constexpr (ASYM) uz[ti][cb][s] = (int)zps[si + s];
+          }
+        }
+      }
+    }
+
+    // ---- stage the chunk of the block's rows as limbs (stage_row of woq_gemv_i8.hip, XJ = 4) ----
+    __syncthreads();  // the previous chunk's operand reads (first chunk: the constant blocks' stores) are done
+    const int k0 = c * MOE_KC;
+    const int xlen = max(0, min(MOE_KC, a.K - k0));
+    for (int m = wid; m < R; m += MOE_WAVES) {
+      float4_t xv[4];
+      if constexpr (GU) {
+        const int slot = __builtin_amdgcn_readfirstlane(a.sorted[first + m]);
+        const size_t row_off = (size_t)(slot / a.top_k) * a.ldx + k0;
+        if (a.x_dtype == WOQ_F32) {
+          const rsrc_t rx = make_rsrc((const float*)a.x + row_off, xlen * 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + j * 1024, 0, 0));
+        } else {
+          const rsrc_t rx = make_rsrc((const uint16_t*)a.x + row_off, xlen * 2);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint2 r = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rx, lane * 8 + j * 512, 0, 0));
+            const uint16_t hb[4] = {(uint16_t)r.x, (uint16_t)(r.x >> 16), (uint16_t)r.y, (uint16_t)(r.y >> 16)};
+            float f[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const float fb = bf16_bits_to_f32(hb[i]), fh = f16_bits_to_f32(hb[i]);
+              f[i] = a.x_dtype == WOQ_BF16 ? fb : fh;
+            }
+            xv[j] = (float4_t){f[0], f[1], f[2], f[3]};
+          }
+        }
+      } else {
+        const rsrc_t rx = make_rsrc((const float*)a.x + (size_t)(first + m) * a.ldx + k0, xlen * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + j * 1024, 0, 0));
+      }
+      float amax = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        amax = fmaxf(fmaxf(amax, fabsf(xv[j].x)), fmaxf(fabsf(xv[j].y), fmaxf(fabsf(xv[j].z), fabsf(xv[j].w))));
+      amax = wave_max_dpp(amax);
+      // amax < 2^e  =>  |x| * 2^(21 - e) < 2^21: the sum with 1.5 * 2^23 stays inside [2^23, 2^24), where ulp = 1, so its
+      // mantissa IS round(x * 2^(21 - e)) + 2^22 (offset binary, 22 bits + sign)
+      int e = 0;
+      if (amax > 0.f && amax < INFINITY) e = max(-100, min(100, __builtin_amdgcn_frexp_expf(amax)));
+      const float sfix = ldexpf(1.f, 21 - e);
+      if (lane == 0) unsc_s[m] = ldexpf(1.f, e - 25);  // undoes the fixed-point scale and the 16 * q weight bytes
+      unsigned char* r0 = strip + (size_t)(3 * m) * MOE_RB + lane * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t va = __float_as_uint(fmaf(xv[j].x, sfix, 12582912.f));
+        const uint32_t vb = __float_as_uint(fmaf(xv[j].y, sfix, 12582912.f));
+        const uint32_t vc = __float_as_uint(fmaf(xv[j].z, sfix, 12582912.f));
+        const uint32_t vd = __float_as_uint(fmaf(xv[j].w, sfix, 12582912.f));
+        // byte n of (va, vb, vc, vd) into one word: v_perm_b32(hi, lo, sel) picks bytes of {hi:lo}, 0x0c = zero
+        const uint32_t ab0 = __builtin_amdgcn_perm(vb, va, 0x0c0c0400u), cd0 = __builtin_amdgcn_perm(vd, vc, 0x04000c0cu);
+        const uint32_t ab1 = __builtin_amdgcn_perm(vb, va, 0x0c0c0501u), cd1 = __builtin_amdgcn_perm(vd, vc, 0x05010c0cu);
+        const uint32_t ab2 = __builtin_amdgcn_perm(vb, va, 0x0c0c0602u), cd2 = __builtin_amdgcn_perm(vd, vc, 0x06020c0cu);
+        *(uint32_t*)(r0 + j * 256) = (ab0 | cd0) ^ 0x80808080u;               // limb 0: b0 - 128
+        *(uint32_t*)(r0 + MOE_RB + j * 256) = (ab1 | cd1) ^ 0x80808080u;      // limb 1: b1 - 128
+        *(uint32_t*)(r0 + 2 * MOE_RB + j * 256) = ab2 | cd2;                  // limb 2: b2 in [0, 127]
+      }
+    }
+    __syncthreads();
+
+    // ---- inner products: MFMA row r = lane & 15 -> activation row (r >> 2) of the set, part r & 3 (limb 0..2 | ones);
+    // D: lane quarter kq holds activation row kq of the set for column lane & 15 ----
+#pragma unroll
+    for (int rs = 0; rs < 4; ++rs) {  // unrolled: acc[rs] stays in registers
+      if (rs >= nrs) break;
+      const int row_a = 4 * rs + a_m;
+      const bool a_live = row_a < R;
+      const bool a_data = a_live && a_part != 3;
+      const unsigned char* a_base =
+          !a_live ? zero_blk + kq * 16
+                  : (a_part == 3 ? ones_blk + kq * 16 : strip + (size_t)(3 * row_a + a_part) * MOE_RB + kq * 16);
+      const int st_t = a_data ? 128 : 0, st_h = a_data ? 64 : 0;
+      const float un = unsc_s[4 * rs + kq];
+#pragma unroll
+      for (int ti = 0; ti < MOE_TPW; ++ti) {
+        const int tt = wid + ti * MOE_WAVES;  // tile of the chunk
+        if (c * MOE_TPC + tt >= a.tiles_k) continue;
+        if constexpr (SMODE == 0) {
+          const i32x4 a0 = *(const i32x4*)(a_base + tt * st_t);
+          const i32x4 a1 = *(const i32x4*)(a_base + tt * st_t + st_h);
+          float sx = 0.f;  // sum_k x~_k of this tile (asym only), in fixed-point units
+          if constexpr (ASYM) {
+            i32x4 ds = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b_ones, izero, 0, 0, 0);
+            ds = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b_ones, ds, 0, 0, 0);
+            sx = limb_combine(ds);
+          }
+#pragma unroll
+          for (int cb = 0; cb < CB; ++cb) {
+            const u32x4 wv = w[ti][cb];
+            i32x4 b0, b1;
+            int4_b(wv.x, wv.y, b0);
+            int4_b(wv.z, wv.w, b1);
+            i32x4 d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0, izero, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1, d, 0, 0, 0);
+            float f = limb_combine(d);
+            // b_ones carries 1 where the weights carry 16 * q: the zero point enters as 16 * zp
+            if constexpr (ASYM) f = fmaf(-16.f * (float)(uz[ti][cb][0] - 8), sx, f);
+            acc[rs][cb] = fmaf(sc[ti][cb][0] * un, f, acc[rs][cb]);
+          }
+        } else {
+          // the two 32-k halves of a 64-k MFMA belong to different groups: lanes kq < 2 feed the first, kq >= 2 the second
+          const unsigned char* a_lo = kq < 2 ? a_base : zero_blk;
+          const unsigned char* a_hi = kq < 2 ? zero_blk : a_base;
+          const int lo_t = kq < 2 ? st_t : 0, lo_h = kq < 2 ? st_h : 0;
+          const int hi_t = kq < 2 ? 0 : st_t, hi_h = kq < 2 ? 0 : st_h;
+          i32x4 al[2], ah[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            al[h] = *(const i32x4*)(a_lo + tt * lo_t + h * lo_h);
+            ah[h] = *(const i32x4*)(a_hi + tt * hi_t + h * hi_h);
+          }
+          float sx[4] = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (ASYM) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              sx[2 * h] = limb_combine(__builtin_amdgcn_mfma_i32_16x16x64_i8(al[h], b_ones, izero, 0, 0, 0));
+              sx[2 * h + 1] = limb_combine(__builtin_amdgcn_mfma_i32_16x16x64_i8(ah[h], b_ones, izero, 0, 0, 0));
+            }
+          }
+#pragma unroll
+          for (int cb = 0; cb < CB; ++cb) {
+            const u32x4 wv = w[ti][cb];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              i32x4 bq;
+              int4_b(h == 0 ? wv.x : wv.z, h == 0 ? wv.y : wv.w, bq);
+#pragma unroll
+              for (int g2 = 0; g2 < 2; ++g2) {
+                const int s = 2 * h + g2;  // 32-k block of the tile
+                float f = limb_combine(
+                    __builtin_amdgcn_mfma_i32_16x16x64_i8(g2 == 0 ? al[h] : ah[h], bq, izero, 0, 0, 0));
+                if constexpr (ASYM) f = fmaf(-16.f * (float)(uz[ti][cb][s] - 8), sx[s], f);
+                acc[rs][cb] = fmaf(sc[ti][cb][s] * un, f, acc[rs][cb]);
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+
+  // ---- the waves' partial sums, added in wave order; epilogue ----
+#pragma unroll
+  for (int rs = 0; rs < 4; ++rs)
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) slab[wid][rs][cb][lane] = acc[rs][cb];
+  __syncthreads();
+  const int row = tid >> 4, col = tid & 15;
+  if (row >= R) return;
+  const int e_rs = row >> 2, e_l = (row & 3) * 16 + col;
+  float v[CB];
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    v[cb] = 0.f;
+#pragma unroll
+    for (int w2 = 0; w2 < MOE_WAVES; ++w2) v[cb] += slab[w2][e_rs][cb][e_l];
+  }
+  const int n = (int)blockIdx.x * 16 + col;
+  if constexpr (GU) {
+    a.out[(size_t)(first + row) * a.ldo + n] = v[0] / (1.0f + expf(-v[0])) * v[CB - 1];  // n < I: I % 16 == 0
+  } else {
+    if (n < a.N) a.out[(size_t)(first + row) * a.ldo + n] = v[0];
+  }
+}
+
+// ---- 4. combine ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restrict__ y, const int32_t* __restrict__ pos_of,
+                                                          const float* __restrict__ topk_w, int top_k, int H,
+                                                          void* __restrict__ out, int out_dtype, int ldo) {
+  const int t = (int)blockIdx.y, n = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (n >= H) return;
+  float acc = 0.f;
+  for (int j = 0; j < top_k; ++j) {
+    const int p = pos_of[t * top_k + j];
+    if (p >= 0) acc = fmaf(topk_w[t * top_k + j], y[(size_t)p * H + n], acc);  // a dropped slot contributes zero
+  }
+  store_f32(out, (size_t)t * ldo + n, out_dtype, acc);
+}
+
+struct MoeWorkspace {
+  size_t sorted, pos_of, blocks, nblocks, h, y, total;
+  int max_blocks;
+};
+MoeWorkspace moe_workspace(int T, int top_k, int E, int hidden, int inter) {
+  MoeWorkspace w;
+  const size_t S = (size_t)T * top_k;
+  w.max_blocks = (int)((S + MOE_BLOCK_ROWS - 1) / MOE_BLOCK_ROWS + std::min<size_t>((size_t)E, S));
+  w.sorted = 0;
+  w.pos_of = w.sorted + woq_round_up(S * 4, 256);
+  w.blocks = w.pos_of + woq_round_up(S * 4, 256);
+  w.nblocks = w.blocks + woq_round_up((size_t)w.max_blocks * sizeof(MoeBlock), 256);
+  w.h = w.nblocks + 256;
+  w.y = w.h + woq_round_up(S * (size_t)inter * 4, 256);
+  w.total = w.y + woq_round_up(S * (size_t)hidden * 4, 256);
+  return w;
+}
+
+bool moe_shape_ok(int T, int top_k, int E, int hidden, int inter) {
+  return T > 0 && top_k > 0 && E > 0 && hidden > 0 && inter > 0 && E <= MOE_MAX_EXPERTS &&
+         (long long)T * top_k <= MOE_MAX_SLOTS;
+}
+
+template <bool GU>
+int moe_launch_gemm(const MoeGemmArgs& a, bool smode1, bool asym, dim3 grid, hipStream_t st) {
+  const dim3 block(MOE_WAVES * 64);
+  if (!smode1 && !asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 0, false>), grid, block, 0, st, a);
+  if (!smode1 && asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 0, true>), grid, block, 0, st, a);
+  if (smode1 && !asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 1, false>), grid, block, 0, st, a);
+  if (smode1 && asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 1, true>), grid, block, 0, st, a);
+  return 0;
+}
+
+MoeGemmArgs moe_gemm_args(const void* blobs, const woq_blob_header& h, size_t stride) {
+  MoeGemmArgs a = {};
+  a.blobs = (const uint8_t*)blobs, a.stride = stride;
+  a.off_q = h.off_q, a.off_scale = h.off_scale, a.off_zp = h.off_zp;
+  a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.n_groups = h.n_groups, a.group = h.group;
+  a.scale_type = (int)h.scale_type;
+  return a;
+}
+
+}  // namespace
+
+const char* moe_header_problem(const woq_blob_header& h, size_t stride) {
+  if (h.magic != WOQ_BLOB_MAGIC) return "QBits: woq_moe_forward: not a WQH1 packed weight";
+  if (h.weight_type != WOQ_W_INT4_CLIP)
+    return "QBits: woq_moe_forward takes int4 / int3 / int2 expert blobs; other weight types run the per-expert loop";
+  if (h.off_shuffle != 0) return "QBits: woq_moe_forward: act-order expert blobs are not built";
+  if (h.K <= 0 || h.N <= 0 || h.Kpad % WOQ_TILE_K != 0 || h.Npad % WOQ_TILE_N != 0 || h.n_groups <= 0 || h.group <= 0 ||
+      h.scale_mode > 1u || h.scale_type > (uint32_t)WOQ_F16)
+    return "QBits: woq_moe_forward: corrupt blob header";
+  if (h.scale_mode == 0 && h.n_groups > 1 && h.group % WOQ_TILE_K != 0) return "QBits: woq_moe_forward: corrupt blob header";
+  if (stride < h.total_bytes || stride % 16 != 0)
+    return "QBits: woq_moe_forward: the expert stride is smaller than a blob or no multiple of 16";
+  return nullptr;
+}
+
+int launch_moe_forward(const MoeCall& m, hipStream_t st) {
+  const woq_blob_header& gh = *m.gate_up_hdr;
+  const woq_blob_header& dh = *m.down_hdr;
+  const int H = dh.N, I = dh.K;
+  const MoeWorkspace w = moe_workspace(m.T, m.top_k, m.E, H, I);
+  uint8_t* ws = (uint8_t*)m.workspace;
+  int32_t* sorted = (int32_t*)(ws + w.sorted);
+  int32_t* pos_of = (int32_t*)(ws + w.pos_of);
+  MoeBlock* blocks = (MoeBlock*)(ws + w.blocks);
+  int32_t* nblocks = (int32_t*)(ws + w.nblocks);
+  float* hbuf = (float*)(ws + w.h);
+  float* ybuf = (float*)(ws + w.y);
+  const int S = m.T * m.top_k;
+
+  if (m.idx_is_int64)
+    hipLaunchKernelGGL(moe_plan_kernel<true>, dim3(1), dim3(MOE_PLAN_THREADS), 0, st, m.topk_idx, S, m.E, sorted, pos_of,
+                       blocks, nblocks);
+  else
+    hipLaunchKernelGGL(moe_plan_kernel<false>, dim3(1), dim3(MOE_PLAN_THREADS), 0, st, m.topk_idx, S, m.E, sorted,
+                       pos_of, blocks, nblocks);
+
+  MoeGemmArgs g = moe_gemm_args(m.gate_up_blobs, gh, m.gate_up_stride);
+  g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
+  g.sorted = sorted, g.blocks = blocks, g.nblocks = nblocks;
+  g.out = hbuf, g.ldo = I, g.half_tiles = I / 16;
+  moe_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, dim3((unsigned)(I / 16), (unsigned)w.max_blocks), st);
+
+  MoeGemmArgs d = moe_gemm_args(m.down_blobs, dh, m.down_stride);
+  d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
+  d.sorted = sorted, d.blocks = blocks, d.nblocks = nblocks;
+  d.out = ybuf, d.ldo = H, d.half_tiles = 0;
+  moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks),
+                         st);
+
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((H + 255) / 256), (unsigned)m.T), dim3(256), 0, st, ybuf, pos_of,
+                     m.topk_w, m.top_k, H, m.out, m.out_dtype, m.ldo);
+  WOQ_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace woq
+
+extern "C" size_t woq_moe_workspace(int T, int top_k, int E, int hidden, int inter) {
+  if (!woq::moe_shape_ok(T, top_k, E, hidden, inter)) return 0;
+  return woq::moe_workspace(T, top_k, E, hidden, inter).total;
+}
+
+extern "C" int woq_moe_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,
+                               const float* topk_w_dev, int T, int top_k, int E, const void* gate_up_blobs_dev,
+                               const woq_blob_header* gate_up_hdr, size_t gate_up_stride, const void* down_blobs_dev,
+                               const woq_blob_header* down_hdr, size_t down_stride, void* out_dev, int out_dtype, int ldo,
+                               void* workspace_dev, size_t workspace_bytes, void* stream) {
+  WOQ_TRY
+  using namespace woq;
+  WOQ_CHECK(gate_up_hdr && down_hdr, "QBits: woq_moe_forward: null header");
+  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(*down_hdr, down_stride)) WOQ_FAIL(p);
+  const int H = down_hdr->N, I = down_hdr->K;
+  WOQ_CHECK(gate_up_hdr->K == H && gate_up_hdr->N == 2 * I,
+            "QBits: woq_moe_forward: gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");
+  WOQ_CHECK(I % 16 == 0, "QBits: woq_moe_forward: the intermediate size must be a multiple of 16 (gate tile tn pairs with up "
+                         "tile tn + inter / 16)");
+  WOQ_CHECK(H % 4 == 0, "QBits: woq_moe_forward: the hidden size must be a multiple of 4");
+  auto dtype_ok = [](int d) { return d == WOQ_F32 || d == WOQ_BF16 || d == WOQ_F16; };
+  WOQ_CHECK(dtype_ok(x_dtype) && dtype_ok(out_dtype), "QBits: unsupported qbits data type.");
+  if (T <= 0) return 0;
+  WOQ_CHECK(moe_shape_ok(T, top_k, E, H, I),
+            "QBits: woq_moe_forward takes at most " + std::to_string(MOE_MAX_EXPERTS) + " experts and " +
+                std::to_string(MOE_MAX_SLOTS) + " routed slots (T * top_k) per call");
+  WOQ_CHECK(x_dev && topk_idx_dev && topk_w_dev && gate_up_blobs_dev && down_blobs_dev && out_dev && workspace_dev,
+            "QBits: woq_moe_forward: null tensor");
+  WOQ_CHECK(ldx >= H && ldo >= H, "QBits: woq_moe_forward: leading dimension smaller than hidden");
+  const size_t xsz = woq_dtype_size((uint32_t)x_dtype);
+  WOQ_CHECK((uintptr_t)x_dev % (4 * xsz) == 0 && ((size_t)ldx * xsz) % (4 * xsz) == 0,
+            "QBits: woq_moe_forward: activation rows must be aligned to four elements");
+  WOQ_CHECK((uintptr_t)gate_up_blobs_dev % 16 == 0 && (uintptr_t)down_blobs_dev % 16 == 0 &&
+                (uintptr_t)workspace_dev % 16 == 0,
+            "QBits: woq_moe_forward: blobs and workspace must be 16-byte aligned");
+  const size_t need = moe_workspace(T, top_k, E, H, I).total;
+  WOQ_CHECK(workspace_bytes >= need, "QBits: woq_moe_forward: the workspace holds " + std::to_string(workspace_bytes) +
+                                         " bytes, this call needs " + std::to_string(need) + " (woq_moe_workspace)");
+  MoeCall m;
+  m.x = x_dev, m.x_dtype = x_dtype, m.ldx = ldx;
+  m.topk_idx = topk_idx_dev, m.idx_is_int64 = idx_is_int64 != 0, m.topk_w = topk_w_dev;
+  m.T = T, m.top_k = top_k, m.E = E;
+  m.gate_up_blobs = gate_up_blobs_dev, m.gate_up_hdr = gate_up_hdr, m.gate_up_stride = gate_up_stride;
+  m.down_blobs = down_blobs_dev, m.down_hdr = down_hdr, m.down_stride = down_stride;
+  m.out = out_dev, m.out_dtype = out_dtype, m.ldo = ldo, m.workspace = workspace_dev;
+  if (const int rc = launch_moe_forward(m, (hipStream_t)stream)) return rc;
+  WOQ_END
+}

@@ -17,7 +17,7 @@ __all__ = [
     "acquire_packed_weight_info", "get_packed_weight_size", "set_woq_workspace", "set_qbits_threads",
     "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
     "awq_scale_delta", "awq_clip_search", "autoround_forward", "autoround_step", "autoround_codes",
-    "teq_forward", "teq_grad", "woq_linear_backward", "woq_linear_backward_workspace",
+    "teq_forward", "teq_grad", "woq_linear_backward", "woq_linear_backward_workspace", "moe_forward", "moe_workspace",
 ]
 
 
@@ -399,6 +399,71 @@ def woq_linear_backward(grad_output, weight, grad_input=None, dtype=None):
     L.check(L.lib().woq_linear_backward(_ptr(grad_output), gcode, ldg, _ptr(weight), ctypes.byref(hdr), _ptr(grad_input),
                                         ocode, ldo, m, L.stream_ptr()))
     return grad_input
+
+
+MOE_MAX_EXPERTS, MOE_MAX_SLOTS = 1024, 8192  # csrc/woq_host.h: what one moe_forward call takes (slots = T * top_k)
+_moe_scratch = None  # moe_forward's own scratch, grown on demand: a steady decode loop allocates nothing
+
+
+def moe_workspace(t, top_k, e, hidden, inter):
+    """Bytes of scratch one `moe_forward` call takes (woq_moe_workspace, include/woq_hip.h); 0 = a shape it refuses."""
+    return int(L.lib().woq_moe_workspace(int(t), int(top_k), int(e), int(hidden), int(inter)))
+
+
+def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_blobs, out=None, workspace=None):
+    """out[t] = sum_j top_k_weights[t, j] * down_e(SiLU(gate_e x_t) * up_e x_t), e = top_k_index[t, j], j ascending
+    (woq_moe_forward, csrc/woq_moe.hip; the definition is HF's MixtralExperts.forward, no reference counterpart).
+    hidden_states [T, H] fp32 / bf16 / fp16 with unit column stride; top_k_index [T, k] int64 or int32 (an id outside
+    [0, E) drops its slot); top_k_weights [T, k]; gate_up_blobs / down_blobs uint8 [E, stride]: E WQH1 blobs each
+    (K = H, N = 2I, gate columns first | K = I, N = H) as `quantize_to_packed_weight` writes them. Four launches and no
+    host synchronisation, whatever the routing; deterministic. `out` [T, H] (allocated in hidden_states' type when None);
+    `workspace`: a uint8 device tensor of `moe_workspace` bytes (this module keeps one of its own when None)."""
+    global _moe_scratch
+    gh, dh = header_of(gate_up_blobs), header_of(down_blobs)
+    x = hidden_states
+    if not (x.is_cuda and x.dim() == 2 and x.device == gate_up_blobs.device == down_blobs.device):
+        raise RuntimeError("QBits: moe_forward takes hidden_states [T, H] on the expert blobs' HIP device")
+    if x.dtype not in _FAKE_QUANT_DTYPES:  # fp32 / fp16 / bf16 go down as they are
+        x = x.float()
+    if not _rows_ok(x, dh.N):
+        x = x.contiguous()
+    t, hidden = x.shape
+    for b in (gate_up_blobs, down_blobs):
+        if not (b.dim() == 2 and b.is_contiguous() and b.element_size() == 1 and b.shape[0] == gate_up_blobs.shape[0]):
+            raise RuntimeError("QBits: moe_forward takes contiguous one-byte expert blob tensors [E, stride]")
+    idx = top_k_index
+    if idx.dim() != 2 or idx.shape[0] != t or idx.dtype not in (torch.int64, torch.int32) or idx.device != x.device:
+        raise RuntimeError("QBits: moe_forward takes top_k_index [T, k] int64 / int32 on the device")
+    idx = idx.contiguous()
+    k = idx.shape[1]
+    w = top_k_weights
+    if tuple(w.shape) != (t, k) or w.device != x.device:
+        raise RuntimeError("QBits: moe_forward takes top_k_weights [T, k] on the device")
+    w = w.float().contiguous()
+    if out is None:
+        out = torch.empty(t, hidden, dtype=x.dtype, device=x.device)
+    if not (out.is_cuda and out.device == x.device and out.dtype in _FAKE_QUANT_DTYPES and _rows_ok(out, hidden)
+            and out.shape[0] == t):
+        raise RuntimeError("QBits: moe_forward: out must be a device tensor [T, H] with unit column stride")
+    if t == 0:
+        return out
+    e_n = gate_up_blobs.shape[0]
+    need = moe_workspace(t, k, e_n, dh.N, dh.K)
+    ws = workspace
+    if ws is None:
+        if need and (_moe_scratch is None or _moe_scratch.numel() < need or _moe_scratch.device != x.device):
+            _moe_scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = _moe_scratch
+    elif not (ws.is_cuda and ws.device == x.device and ws.is_contiguous()):
+        raise RuntimeError("QBits: moe_forward: the workspace must be a contiguous tensor on the device")
+    ldx = x.stride(0) if t > 1 else max(x.stride(0), hidden)
+    ldo = out.stride(0) if t > 1 else max(out.stride(0), hidden)
+    L.check(L.lib().woq_moe_forward(_ptr(x), L.torch_dtype_code(x.dtype), ldx, _ptr(idx), int(idx.dtype == torch.int64),
+                                    _ptr(w), t, k, e_n, _ptr(gate_up_blobs), ctypes.byref(gh), gate_up_blobs.stride(0),
+                                    _ptr(down_blobs), ctypes.byref(dh), down_blobs.stride(0), _ptr(out),
+                                    L.torch_dtype_code(out.dtype), ldo, _ptr(ws),
+                                    0 if ws is None else ws.numel() * ws.element_size(), L.stream_ptr()))
+    return out
 
 
 def _ascii(s):

@@ -34,9 +34,20 @@ def data_source(config, method="GPTQ"):
                               "tensors) or dataset=[texts] with tokenizer=")
 
 
+def is_moe_experts(module):
+    """An expert collection of a sparse mixture-of-experts block as HF holds it (MixtralExperts, Qwen3MoeExperts): 3-D
+    `gate_up_proj [E, 2I, H]` and `down_proj [E, H, I]` and an `act_fn`."""
+    gu, dn = getattr(module, "gate_up_proj", None), getattr(module, "down_proj", None)
+    return (torch.is_tensor(gu) and torch.is_tensor(dn) and gu.dim() == 3 and dn.dim() == 3 and hasattr(module, "act_fn")
+            and gu.shape[0] == dn.shape[0] and gu.shape[1] == 2 * dn.shape[2] and gu.shape[2] == dn.shape[1])
+
+
 def check_request(model, config, method, unsupported_options, blocks_first=False):
     """Everything about a request that can be refused without touching a device; `method` is GPTQ, AWQ, AutoRound or TEQ.
     `blocks_first`: a model without decoder blocks is named before missing data (AutoRound's order)."""
+    if any(is_moe_experts(m) for m in model.modules()):
+        raise NotImplementedError("%s on the MI355X path does not calibrate mixture-of-experts expert weights (3-D "
+                                  "gate_up_proj / down_proj); use RtnConfig" % method)
     for opt in unsupported_options:
         if getattr(config, opt, False):
             raise NotImplementedError("%s on the MI355X path does not implement %s" % (method, opt))

@@ -14,7 +14,8 @@ import logging
 
 import torch
 
-from .calibration import is_conv1d
+from .calibration import is_conv1d, is_moe_experts
+from .nn.moe import PackedExpertsShell, QuantizedMoEExpertsQBits, silu_act, warn_other_activation
 from .nn.modules import QuantizedLinearQBits
 
 logger = logging.getLogger(__name__)
@@ -166,8 +167,9 @@ def replace_linear(model, modules_to_not_convert=None, current_key_name=None, qu
 
 def _replace_linear(model, modules_to_not_convert, current_key_name, quantization_config, is_replaced=False,
                     device="cuda", empty_weights=False):
-    """Recursive walk (reference utils.py:164-434). Eligible: nn.Linear, HF Conv1D, packed-checkpoint linears; a module
-    is skipped when any entry of `modules_to_not_convert` is a substring of its dotted name (:189-201)."""
+    """Recursive walk (reference utils.py:164-434). Eligible: nn.Linear, HF Conv1D, packed-checkpoint linears, and the
+    expert collections of sparse MoE blocks (nn/moe.py; no reference counterpart); a module is skipped when any entry of
+    `modules_to_not_convert` is a substring of its dotted name (:189-201)."""
     cfg = quantization_config
     for name, module in list(model.named_children()):
         key = (current_key_name or []) + [name]
@@ -205,6 +207,26 @@ def _replace_linear(model, modules_to_not_convert, current_key_name, quantizatio
                     new.set_fp_weights_bias(w.to(device), bias)
             new.source_cls = type(module)
             new.requires_grad_(False)
+            model._modules[name] = new
+            is_replaced = True
+        elif (isinstance(module, PackedExpertsShell) or is_moe_experts(module)) \
+                and not any(s in dotted for s in modules_to_not_convert):
+            # the expert collection of a sparse MoE block: 3-D parameters, which the linear test above never sees
+            if not isinstance(module, PackedExpertsShell) and not silu_act(module.act_fn):
+                warn_other_activation(dotted, module.act_fn)
+                continue
+            if isinstance(module, PackedExpertsShell):
+                e_n, hidden, inter = module.num_experts, module.hidden_dim, module.intermediate_dim
+            else:
+                e_n, hidden, inter = module.down_proj.shape
+            new = QuantizedMoEExpertsQBits(e_n, hidden, inter, compute_dtype=cfg.compute_dtype,
+                                           weight_dtype=cfg.weight_dtype, bits=cfg.bits, scale_dtype=cfg.scale_dtype,
+                                           blocksize=cfg.group_size, scheme=cfg.scheme, device=device)
+            if isinstance(module, PackedExpertsShell):
+                new.set_packed_weights(module.tensors, cfg)
+            elif not empty_weights:
+                new.set_fp_weights(module.gate_up_proj.data, module.down_proj.data)
+            new.source_cls = type(module)
             model._modules[name] = new
             is_replaced = True
         elif len(list(module.children())) > 0:

@@ -19,6 +19,7 @@ import torch
 import transformers
 
 from ..llm.quantization.nn.modules import QuantizedLinearQBits
+from ..llm.quantization.nn.moe import PackedExpertsShell, QuantizedMoEExpertsQBits, is_moe_experts
 from ..llm.quantization.utils import convert_to_quantized_model, pack_weight, replace_linear, unpack_weight
 from ..utils.config import (AutoRoundConfig, AwqConfig, GPTQConfig, ITREXQuantizationConfigMixin, RtnConfig,
                             TeqConfig)
@@ -79,6 +80,10 @@ def save_low_bit(self, save_directory, push_to_hub=False, safe_serialization=Tru
                 tensors[name + ".g_idx"] = g_idx.cpu().contiguous()
             if mod.bias is not None:
                 tensors[name + ".bias"] = mod.bias.detach().cpu().contiguous()
+            quantized.add(name)
+        elif isinstance(mod, QuantizedMoEExpertsQBits):  # <name>.gate_up_proj.qweight ...: a leading expert dimension
+            for suffix, t in mod.export_tensors().items():
+                tensors[name + "." + suffix] = t
             quantized.add(name)
     seen_ptr = {}
     for key, t in self.state_dict().items():
@@ -168,6 +173,11 @@ def _load_packed(d, qcfg, tensors, quantized, aliases, device, awq_gemm=False):
         parent_name, _, leaf = name.rpartition(".")
         parent = model.get_submodule(parent_name) if parent_name else model
         old = getattr(parent, leaf)
+        if name + ".gate_up_proj.qweight" in tensors:  # an expert collection (save_low_bit): stacked over the experts
+            parts = {k[len(name) + 1:]: v.to(device) for k, v in tensors.items() if k.startswith(name + ".")}
+            e_n, hidden, inter = old.down_proj.shape
+            parent._modules[leaf] = PackedExpertsShell(e_n, hidden, inter, parts)
+            continue
         if hasattr(old, "nf"):
             k, n = old.weight.shape[0], old.nf
         else:
@@ -176,7 +186,7 @@ def _load_packed(d, qcfg, tensors, quantized, aliases, device, awq_gemm=False):
                  if name + "." + s in tensors}
         parent._modules[leaf] = _ShellLinear(k, n, parts, awq_gemm=awq_gemm)
     skip = [n for n, m in model.named_modules()
-            if isinstance(m, torch.nn.Linear) or type(m).__name__ == "Conv1D"]  # whatever was left unquantised
+            if isinstance(m, torch.nn.Linear) or type(m).__name__ == "Conv1D" or is_moe_experts(m)]  # left unquantised
     replace_linear(model, skip, None, qcfg, device=device)
     state = {k: v for k, v in tensors.items() if not any(k.startswith(q + ".") for q in quantized)}
     for first, rest in aliases.items():
