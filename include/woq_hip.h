@@ -211,6 +211,20 @@ WOQ_API int woq_moe_forward(const void* x_dev, int x_dtype, int ldx, const void*
                             const woq_blob_header* gate_up_hdr, size_t gate_up_stride, const void* down_blobs_dev,
                             const woq_blob_header* down_hdr, size_t down_stride, void* out_dev, int out_dtype, int ldo,
                             void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The prompt form of the same block (csrc/woq_moe_prompt.hip): same arguments, same definition (dropped slots included),
+ * same weight types and header messages, for many rows per expert: up to 65536 routed slots a call, refused above with a
+ * message that names the limit. Six launches (a three-launch plan over 1024-slot segments, gate/up, down, combine) whose
+ * shapes do not depend on the routing. Numerics: one fp16 product per operand pair on v_mfma_f32_16x16x32_f16 with fp32
+ * accumulation (the dense prompt GEMM's contract in its bf16 / fp16 / int8 compute modes); activation rows are scaled by
+ * an exact power of two per row and 128-k tile, scale_mode-1 scales by one per column and tile, scale_mode-0 scales are
+ * applied in fp32. Deterministic. woq_moe_prompt_workspace: the plan's tables, one count per (segment, expert) and the
+ * fp32 rows [T * top_k][inter] and [T * top_k][hidden]; 0 for a shape outside the limits. */
+WOQ_API size_t woq_moe_prompt_workspace(int T, int top_k, int E, int hidden, int inter);
+WOQ_API int woq_moe_prompt_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,
+                                   const float* topk_w_dev, int T, int top_k, int E, const void* gate_up_blobs_dev,
+                                   const woq_blob_header* gate_up_hdr, size_t gate_up_stride, const void* down_blobs_dev,
+                                   const woq_blob_header* down_hdr, size_t down_stride, void* out_dev, int out_dtype,
+                                   int ldo, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device

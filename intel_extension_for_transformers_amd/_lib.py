@@ -104,7 +104,7 @@ EXPORTS = [
     "woq_engine_lora_reserve", "woq_engine_set_lora", "woq_engine_clear_lora", "woq_engine_lora_on",
     "woq_engine_set_h2o", "woq_engine_h2o_reset", "woq_engine_h2o_score_ptr", "woq_engine_h2o_evict",
     "woq_h2o_decode_scratch_bytes", "woq_h2o_score_decode", "woq_h2o_score_prompt", "woq_h2o_select", "woq_h2o_compact",
-    "woq_moe_workspace", "woq_moe_forward",
+    "woq_moe_workspace", "woq_moe_forward", "woq_moe_prompt_workspace", "woq_moe_prompt_forward",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -169,6 +169,9 @@ def lib():
     L.woq_moe_workspace.argtypes = [ci] * 5
     L.woq_moe_forward.argtypes = [vp, ci, ci, vp, ci, vp, ci, ci, ci, vp, ctypes.POINTER(BlobHeader), cs, vp,
                                   ctypes.POINTER(BlobHeader), cs, vp, ci, ci, vp, cs, vp]
+    L.woq_moe_prompt_workspace.restype = cs
+    L.woq_moe_prompt_workspace.argtypes = L.woq_moe_workspace.argtypes
+    L.woq_moe_prompt_forward.argtypes = L.woq_moe_forward.argtypes
     L.woq_read_header.argtypes = [vp, ctypes.POINTER(BlobHeader), vp]
     L.woq_blob_extract.argtypes = [vp, ctypes.POINTER(BlobHeader), ci, vp, vp]
     L.woq_linear.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, vp, ci, ci, ci, vp]

@@ -284,6 +284,19 @@ struct MoeCall {
 const char* moe_header_problem(const woq_blob_header& h, size_t stride);
 // plan, gate/up, down, combine: four launches shaped by (T, top_k, E, hidden, inter) alone, no host synchronisation
 int launch_moe_forward(const MoeCall& m, hipStream_t st);
+// a row of the plan's block table: `rows` sorted slots of one expert from sorted position `first`
+struct MoeBlock { int32_t expert, first, rows, pad; };
+// out[t][n] = sum_j topk_w[t][j] * y[pos_of[t k + j]][n] (fp32 y [sorted slot][H]), j ascending, a dropped slot (-1)
+// contributing zero, rounded once to out_dtype: the last launch of both forms
+void launch_moe_combine(const float* y, const int32_t* pos_of, const float* topk_w, int T, int top_k, int H, void* out,
+                        int out_dtype, int ldo, hipStream_t st);
+
+// ---- woq_moe_prompt.hip: the same block for many rows per expert, on the fp16 MFMA ---------------------------------
+constexpr int MOE_PROMPT_ROWS = 128;          // rows of one block of its table: the row tile of the product
+constexpr int MOE_PROMPT_MAX_SLOTS = 65536;   // routed slots of one call: 64 plan segments of 1024
+// plan (count, scan, scatter), gate/up, down, combine: six launches shaped by (T, top_k, E, hidden, inter) alone;
+// `workspace` of woq_moe_prompt_workspace bytes
+int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st);
 
 // ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
 // After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at

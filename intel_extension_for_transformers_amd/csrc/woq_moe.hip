@@ -44,10 +44,6 @@ constexpr int MOE_WAVES = 4;
 constexpr int MOE_TPW = MOE_TPC / MOE_WAVES;  // tiles of a chunk per wave
 constexpr int MOE_PLAN_THREADS = 1024;
 
-struct MoeBlock {
-  int32_t expert, first, rows, pad;
-};
-
 // ---- 1. plan ---------------------------------------------------------------------------------------------------------
 template <bool IDX64>
 __global__ __launch_bounds__(MOE_PLAN_THREADS) void moe_plan_kernel(const void* __restrict__ topk_idx, int S, int E,
@@ -431,6 +427,12 @@ const char* moe_header_problem(const woq_blob_header& h, size_t stride) {
   return nullptr;
 }
 
+void launch_moe_combine(const float* y, const int32_t* pos_of, const float* topk_w, int T, int top_k, int H, void* out,
+                        int out_dtype, int ldo, hipStream_t st) {
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((H + 255) / 256), (unsigned)T), dim3(256), 0, st, y, pos_of, topk_w,
+                     top_k, H, out, out_dtype, ldo);
+}
+
 int launch_moe_forward(const MoeCall& m, hipStream_t st) {
   const woq_blob_header& gh = *m.gate_up_hdr;
   const woq_blob_header& dh = *m.down_hdr;
@@ -465,8 +467,7 @@ int launch_moe_forward(const MoeCall& m, hipStream_t st) {
   moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks),
                          st);
 
-  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((H + 255) / 256), (unsigned)m.T), dim3(256), 0, st, ybuf, pos_of,
-                     m.topk_w, m.top_k, H, m.out, m.out_dtype, m.ldo);
+  launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
   WOQ_HIP(hipGetLastError());
   return 0;
 }

@@ -1,0 +1,567 @@
+// woq_moe_prompt.hip — the prompt form of the routed expert block (woq_moe.hip states the definition): the same four
+// stages for MANY rows per expert, on the fp16 matrix instruction v_mfma_f32_16x16x32_f16.
+//
+//  1. plan, three launches, for up to MOE_PROMPT_MAX_SLOTS slots s = t k + j in segments of 1024:
+//       count    one workgroup per segment: histogram of the segment's ids over the experts in LDS (integer atomics: the
+//                counts do not depend on the order) -> counts[segment][E]; pos_of[s] = -1 for an id outside [0, E)
+//       scan     one workgroup: expert totals, their exclusive scan, counts[segment][e] <- first sorted position of
+//                expert e's slots of that segment, and the block table {expert, first, rows <= MOE_PROMPT_ROWS} + count
+//       scatter  one workgroup per segment: expert e's thread walks the segment's ids (LDS, a broadcast read) in
+//                ascending order from counts[segment][e] -> sorted[], pos_of[]. Stable, so deterministic.
+//     The host never learns the routing: the product grids are sized for ceil(S / 128) + min(E, S) blocks and a
+//     workgroup past the count returns.
+//  2. gate/up and 3. down: one kernel, moe_prompt_gemm_kernel<GU, SMODE, ASYM>. A workgroup of four waves takes one table
+//     block (<= 128 rows of one expert) by 128 weight columns; a wave owns ALL the rows by two 16-column blob tiles — a
+//     gate tile and the matching up tile (the workgroup then yields 64 columns of SiLU(g) * u), or two adjacent down
+//     tiles — so every weight word is fetched and unpacked once per workgroup and meets all eight row tiles.
+//       K is walked one blob tile (128 k) at a time. The block's rows are gathered through sorted[] (gate/up: the token
+//     slot / top_k of x; down: the slot's own fp32 h row), multiplied by an exact power of two chosen PER ROW AND TILE
+//     from the tile's largest magnitude (|x| 2^(15 - e) < 2^15), rounded once to fp16 and written to LDS in the A-fragment
+//     image of the dense prompt GEMM (woq_gemm_f16.hip): 256-byte rows, 16-byte chunk c (8 k, in the nibble-extraction
+//     order {0,2,4,6,1,3,5,7}) of row r in slot c ^ (r & 15), so every ds_read_b128 group covers the 64 banks once. Two
+//     images: the next tile's weight words and activation rows are requested before this tile's MFMAs and converted
+//     behind them; one barrier per tile.
+//       Weights go from blob words to fp16 B fragments in registers, as dq8s of woq_gemm_f16.hip does it: a three-input
+//     bit op per nibble pair gives fp16 (1024 + u | 64 + u), one packed add of -(base + zp) gives q - zp exactly.
+//     scale_mode 0 has ONE scale per tile and column, so the operand stays the exact integer and the scale is applied in
+//     fp32; scale_mode 1 (four 32-k scales a tile) multiplies by the scale relative to 2^E > the tile's largest scale of
+//     that column (an exact power of two, so a scale of 5e-6 or a bf16 scale outside fp16's range stays normal).
+//       A tile's products are accumulated in fresh fp32 fragments and folded into the running fp32 accumulators with
+//     2^(e - 15)[row] * (scale | 2^E)[column]. One fp16 product per operand pair, fp32 accumulation: the contract of the
+//     dense prompt GEMM's bf16 / fp16 / int8 compute modes. Row tiles past the block's rows are skipped wave-uniformly.
+//  4. combine: woq_moe.hip's launch_moe_combine.
+// No split-K, no floating-point atomics, a fixed summation order: the same inputs give the same bytes.
+#include <math.h>
+
+#include <algorithm>
+#include <string>
+
+#include "woq_gemv_common.h"
+#include "woq_host.h"
+
+namespace woq {
+namespace {
+
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+
+constexpr int MP_SEG = 1024;                          // slots of one plan segment = threads of a plan workgroup
+constexpr int MP_ROWS = MOE_PROMPT_ROWS;              // rows of a table block
+constexpr int MP_WAVES = 4, MP_CT = 2;                // waves of a workgroup, column tiles of a wave
+constexpr int MP_IMAGE = MP_ROWS * WOQ_TILE_K * 2;    // bytes of one A image: 128 rows x 128 k fp16
+constexpr int MP_LDS = 2 * MP_IMAGE + 2 * MP_ROWS * 4;  // two images + two sets of row factors
+static_assert(MP_ROWS == 128, "the staging map and the eight row tiles of a wave assume 128-row blocks");
+
+// ---- 1. plan ---------------------------------------------------------------------------------------------------------
+template <bool IDX64>
+__device__ __forceinline__ int moe_prompt_id(const void* topk_idx, int s, int E) {
+  const long long v = IDX64 ? (long long)((const int64_t*)topk_idx)[s] : (long long)((const int32_t*)topk_idx)[s];
+  return (v >= 0 && v < (long long)E) ? (int)v : -1;
+}
+
+template <bool IDX64>
+__global__ __launch_bounds__(MP_SEG) void moe_prompt_count_kernel(const void* __restrict__ topk_idx, int S, int E,
+                                                                  int32_t* __restrict__ counts,
+                                                                  int32_t* __restrict__ pos_of) {
+  __shared__ int32_t cnt[MOE_MAX_EXPERTS];
+  const int tid = threadIdx.x, seg = blockIdx.x, s = seg * MP_SEG + tid;
+  if (tid < E) cnt[tid] = 0;
+  __syncthreads();
+  if (s < S) {
+    const int e = moe_prompt_id<IDX64>(topk_idx, s, E);
+    if (e >= 0)
+      atomicAdd(&cnt[e], 1);  // an integer count: the result does not depend on the order
+    else
+      pos_of[s] = -1;
+  }
+  __syncthreads();
+  if (tid < E) counts[(size_t)seg * E + tid] = cnt[tid];
+}
+
+__global__ __launch_bounds__(MP_SEG) void moe_prompt_scan_kernel(int nseg, int E, int32_t* __restrict__ counts,
+                                                                 MoeBlock* __restrict__ blocks,
+                                                                 int32_t* __restrict__ nblocks) {
+  __shared__ int32_t tot[MOE_MAX_EXPERTS], off[MOE_MAX_EXPERTS], bb[MOE_MAX_EXPERTS];
+  const int e = threadIdx.x;
+  if (e < E) {
+    int c = 0;
+    for (int g = 0; g < nseg; ++g) c += counts[(size_t)g * E + e];
+    tot[e] = c;
+  }
+  __syncthreads();
+  if (e == 0) {
+    int run = 0, nb = 0;
+    for (int i = 0; i < E; ++i) {
+      off[i] = run, bb[i] = nb;
+      run += tot[i], nb += (tot[i] + MP_ROWS - 1) / MP_ROWS;
+    }
+    *nblocks = nb;
+  }
+  __syncthreads();
+  if (e >= E) return;
+  int run = off[e];
+  for (int g = 0; g < nseg; ++g) {
+    const int c = counts[(size_t)g * E + e];
+    counts[(size_t)g * E + e] = run;
+    run += c;
+  }
+  for (int r = 0, nb = bb[e]; r < tot[e]; r += MP_ROWS, ++nb)
+    blocks[nb] = MoeBlock{e, off[e] + r, min(MP_ROWS, tot[e] - r), 0};
+}
+
+template <bool IDX64>
+__global__ __launch_bounds__(MP_SEG) void moe_prompt_scatter_kernel(const void* __restrict__ topk_idx, int S, int E,
+                                                                    const int32_t* __restrict__ counts,
+                                                                    int32_t* __restrict__ sorted,
+                                                                    int32_t* __restrict__ pos_of) {
+  __shared__ int32_t ids[MP_SEG];
+  const int tid = threadIdx.x, seg = blockIdx.x, s0 = seg * MP_SEG;
+  const int n = min(MP_SEG, S - s0);
+  ids[tid] = tid < n ? moe_prompt_id<IDX64>(topk_idx, s0 + tid, E) : -1;
+  __syncthreads();
+  if (tid >= E) return;
+  int p = counts[(size_t)seg * E + tid];
+  for (int i = 0; i < n; ++i) {  // every thread reads the same LDS word: a broadcast
+    if (ids[i] == tid) {
+      sorted[p] = s0 + i;
+      pos_of[s0 + i] = p;
+      ++p;
+    }
+  }
+}
+
+// ---- 2 / 3. the grouped product --------------------------------------------------------------------------------------
+struct MoePromptArgs {
+  const uint8_t* blobs;  // expert e's blob at blobs + e * stride
+  size_t stride, off_q, off_scale, off_zp;
+  int K, N, tiles_k, tiles_n, n_groups, group, scale_type;
+  const void* x;  // gate/up: activations [T, ldx] of x_dtype; down: fp32 rows [sorted slot][ldx]
+  int x_dtype, ldx, top_k;
+  const int32_t* sorted;
+  const MoeBlock* blocks;
+  const int32_t* nblocks;
+  float* out;  // gate/up: SiLU(g) * u [sorted slot][ldo]; down: y [sorted slot][ldo]
+  int ldo, half_tiles;
+};
+
+template <int SMODE>
+struct MoePromptB {  // one K tile of one wave's weight operand, as loaded
+  u32x4 w[MP_CT];
+  float sc[MP_CT][SMODE == 1 ? 4 : 1];
+  uint32_t uz[MP_CT][SMODE == 1 ? 2 : 1];
+};
+
+// 8 signed nibbles of one blob word -> 8 fp16 (q - zp) [* r], k order {0,2,4,6,1,3,5,7}: dq8s of woq_gemm_f16.hip
+template <bool MUL>
+__device__ __forceinline__ h8 moe_prompt_dq8(uint32_t w, h2 nlo, h2 nhi, h2 r) {
+  const uint32_t y = w >> 8;
+  h2 f0 = __builtin_bit_cast(h2, (w & 0x000f000fu) ^ 0x64086408u) + nlo;
+  h2 f1 = __builtin_bit_cast(h2, (w & 0x00f000f0u) ^ 0x54805480u) + nhi;
+  h2 f2 = __builtin_bit_cast(h2, (y & 0x000f000fu) ^ 0x64086408u) + nlo;
+  h2 f3 = __builtin_bit_cast(h2, (y & 0x00f000f0u) ^ 0x54805480u) + nhi;
+  if constexpr (MUL) f0 *= r, f1 *= r, f2 *= r, f3 *= r;
+  return __builtin_bit_cast(h8, (u32x4){__builtin_bit_cast(uint32_t, f0), __builtin_bit_cast(uint32_t, f1),
+                                        __builtin_bit_cast(uint32_t, f2), __builtin_bit_cast(uint32_t, f3)});
+}
+
+// GU: the gate/up launch (gate tile + up tile per wave, SiLU * mul epilogue, rows gathered by token) | the down launch
+template <bool GU, int SMODE, bool ASYM>
+__global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const MoePromptArgs a) {
+  constexpr int NS = SMODE == 1 ? 2 : 1;  // scales of a tile, column and lane: its 32-k block of either 64-k half
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];  // [2][MP_IMAGE] images, [2][MP_ROWS] factors
+  float* unsc = (float*)(smem + 2 * MP_IMAGE);
+
+  const int b = (int)blockIdx.y;
+  if (b >= *a.nblocks) return;
+  const MoeBlock blk = a.blocks[b];
+  const int expert = __builtin_amdgcn_readfirstlane(blk.expert), first = __builtin_amdgcn_readfirstlane(blk.first);
+  const int R = __builtin_amdgcn_readfirstlane(blk.rows);
+  const int nrt = (R + 15) >> 4;       // live row tiles
+  const int nst = (nrt + 1) & ~1;      // staged row tiles: the MFMA loop takes them in pairs
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int i16 = lane & 15, kq = lane >> 4;
+
+  const uint8_t* blob = a.blobs + (size_t)expert * a.stride;
+  const u32x4* q = (const u32x4*)(blob + a.off_q);
+  const void* scales = blob + a.off_scale;
+  const uint8_t* zps = blob + a.off_zp;
+  // this wave's column tiles (clamped for the loads; `live` decides the stores)
+  int tn[MP_CT];
+  bool live[MP_CT];
+  const int wt = (int)blockIdx.x * MP_WAVES + wid;
+  if constexpr (GU) {
+    live[0] = live[1] = wt < a.half_tiles;
+    tn[0] = min(wt, a.half_tiles - 1), tn[1] = tn[0] + a.half_tiles;
+  } else {
+#pragma unroll
+    for (int c = 0; c < MP_CT; ++c) live[c] = wt * MP_CT + c < a.tiles_n, tn[c] = min(wt * MP_CT + c, a.tiles_n - 1);
+  }
+
+  // staging map: thread = (row group rg, chunk c16); item i = row 16 i + rg, i.e. one row tile per item
+  const int c16 = tid & 15, rg = tid >> 4;
+  int src[8];  // the item's source row (gate/up: the token; down: the sorted slot), -1 = no row
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = 16 * i + rg;
+    src[i] = -1;
+    if (row < R) src[i] = GU ? a.sorted[first + row] / a.top_k : first + row;
+  }
+  const bool x32 = !GU || a.x_dtype == WOQ_F32, xbf = a.x_dtype == WOQ_BF16;
+
+  // Staging runs in two halves of four row tiles (half g: items 4 g .. 4 g + 3), each requested before one half of the
+  // tile's MFMAs and converted behind it: 32 registers in flight instead of 64.
+  u32x4 raw[4][2];
+  auto stage_load = [&](int kt, int g) {  // K % 4 == 0: a group of four elements lies inside K or outside it
+    const int k = kt * WOQ_TILE_K + c16 * 8;
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+      const int i = 4 * g + ii;
+      raw[ii][0] = raw[ii][1] = u32x4{0u, 0u, 0u, 0u};
+      if (i >= nst || src[i] < 0) continue;
+      const size_t so = (size_t)src[i] * a.ldx + k;
+      if (x32) {
+        const float* p = (const float*)a.x + so;
+        if (k + 4 <= a.K) raw[ii][0] = *(const u32x4*)p;
+        if (k + 8 <= a.K) raw[ii][1] = *(const u32x4*)(p + 4);
+      } else {
+        const uint16_t* p = (const uint16_t*)a.x + so;
+        if (k + 4 <= a.K) {
+          const uint2 v = *(const uint2*)p;
+          raw[ii][0].x = v.x, raw[ii][0].y = v.y;
+        }
+        if (k + 8 <= a.K) {
+          const uint2 v = *(const uint2*)(p + 4);
+          raw[ii][0].z = v.x, raw[ii][0].w = v.y;
+        }
+      }
+    }
+  };
+  auto stage_write = [&](int buf, int g) {
+    unsigned char* img = smem + buf * MP_IMAGE;
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+      const int i = 4 * g + ii;
+      if (i >= nst) break;  // wave-uniform
+      float f[8];
+      if (x32) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = __uint_as_float(raw[ii][j >> 2][j & 3]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint16_t bits = (uint16_t)(raw[ii][0][j >> 1] >> (16 * (j & 1)));
+          const float fb = bf16_bits_to_f32(bits), fh = f16_bits_to_f32(bits);
+          f[j] = xbf ? fb : fh;
+        }
+      }
+      float amax = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
+      // the 16 lanes of a DPP row hold the 16 chunks of one activation row: four butterfly steps leave the row's maximum
+      amax = fmaxf(amax, WOQ_DPP_F32(amax, 0xB1));
+      amax = fmaxf(amax, WOQ_DPP_F32(amax, 0x4E));
+      amax = fmaxf(amax, WOQ_DPP_F32(amax, 0x141));
+      amax = fmaxf(amax, WOQ_DPP_F32(amax, 0x140));
+      int e = 0;  // amax < 2^e  =>  |x| 2^(15 - e) < 2^15
+      if (amax > 0.f && amax < INFINITY) e = max(-100, min(100, __builtin_amdgcn_frexp_expf(amax)));
+      const float sfix = ldexpf(1.f, 15 - e);
+      const int row = 16 * i + rg;
+      h8 hh;
+#pragma unroll
+      for (int e8 = 0; e8 < 8; ++e8) hh[e8] = (_Float16)(f[e8 < 4 ? 2 * e8 : 2 * (e8 - 4) + 1] * sfix);
+      *(h8*)(img + row * 256 + ((c16 ^ (row & 15)) << 4)) = hh;
+      if (c16 == 0) unsc[buf * MP_ROWS + row] = row < R ? ldexpf(1.f, e - 15) : 0.f;
+    }
+  };
+
+  auto load_b = [&](int kt, MoePromptB<SMODE>& bw) {
+#pragma unroll
+    for (int c = 0; c < MP_CT; ++c) {
+      bw.w[c] = __builtin_nontemporal_load(q + ((size_t)tn[c] * a.tiles_k + kt) * 64 + lane);
+      if constexpr (SMODE == 0) {
+        const int grp = a.n_groups == 1 ? 0 : min(kt * WOQ_TILE_K / a.group, a.n_groups - 1);
+        const size_t si = ((size_t)tn[c] * a.n_groups + grp) * 16 + i16;
+        bw.sc[c][0] = load_f32(scales, si, a.scale_type);
+        bw.uz[c][0] = ASYM ? (uint32_t)zps[si] : 8u;
+      } else {
+        const size_t si = (((size_t)tn[c] * a.tiles_k + kt) * 16 + i16) * 4;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) bw.sc[c][s] = load_f32(scales, si + s, a.scale_type);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) bw.uz[c][h] = ASYM ? (uint32_t)zps[si + 2 * h + (kq >> 1)] : 8u;
+      }
+    }
+  };
+
+  float4_t acc[8][MP_CT];
+#pragma unroll
+  for (int rt = 0; rt < 8; ++rt)
+#pragma unroll
+    for (int c = 0; c < MP_CT; ++c) acc[rt][c] = (float4_t){0.f, 0.f, 0.f, 0.f};
+  // A fragment of (64-k half h, part p) = blob word hp = 2 h + p: chunk 8 h + 2 kq + p of row 16 rt + i16
+  int a_off[4];
+#pragma unroll
+  for (int hp = 0; hp < 4; ++hp) a_off[hp] = i16 * 256 + ((((hp >> 1) * 8 + kq * 2 + (hp & 1)) ^ i16) << 4);
+
+  float cs[MP_CT];   // fp32 column factor of the tile in hand
+  h8 bf[4][MP_CT];   // its B fragments
+  auto unpack = [&](const MoePromptB<SMODE>& bw) {
+#pragma unroll
+    for (int c = 0; c < MP_CT; ++c) {
+      h2 r2[NS], nlo[NS], nhi[NS];
+      if constexpr (SMODE == 0) {
+        cs[c] = bw.sc[c][0];
+        r2[0] = (h2){(_Float16)1.f, (_Float16)1.f};
+      } else {
+        const float mx = fmaxf(fmaxf(fabsf(bw.sc[c][0]), fabsf(bw.sc[c][1])), fmaxf(fabsf(bw.sc[c][2]), fabsf(bw.sc[c][3])));
+        int E2 = 0;  // mx < 2^E2: the relative scales lie in (-1, 1), the largest of them in [1/2, 1)
+        if (mx > 0.f && mx < INFINITY) E2 = max(-120, min(120, __builtin_amdgcn_frexp_expf(mx)));
+        cs[c] = ldexpf(1.f, E2);
+        const float inv = ldexpf(1.f, -E2);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const _Float16 rr = (_Float16)((kq < 2 ? bw.sc[c][2 * h] : bw.sc[c][2 * h + 1]) * inv);
+          r2[h] = (h2){rr, rr};
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const float uz = (float)(bw.uz[c][s] & 0xffu);
+        const _Float16 l = (_Float16)(-(1024.f + uz)), hg = (_Float16)(-(64.f + uz));
+        nlo[s] = (h2){l, l}, nhi[s] = (h2){hg, hg};
+      }
+#pragma unroll
+      for (int hp = 0; hp < 4; ++hp) {
+        const int s = SMODE == 0 ? 0 : (hp >> 1);
+        bf[hp][c] = moe_prompt_dq8<SMODE == 1>(bw.w[c][hp], nlo[s], nhi[s], r2[s]);
+      }
+    }
+  };
+  auto compute = [&](int buf, int g) {  // row tiles 4 g .. 4 g + 3, in pairs
+    const unsigned char* img = smem + buf * MP_IMAGE;
+    const float* un = unsc + buf * MP_ROWS;
+#pragma unroll
+    for (int rp = 2 * g; rp < 2 * g + 2; ++rp) {  // unrolled: acc stays in registers
+      if (2 * rp >= nrt) break;                   // wave-uniform
+      float4_t t[2][MP_CT];
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int c = 0; c < MP_CT; ++c) t[u][c] = (float4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int hp = 0; hp < 4; ++hp)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const h8 af = *(const h8*)(img + (2 * rp + u) * 4096 + a_off[hp]);
+#pragma unroll
+          for (int c = 0; c < MP_CT; ++c) t[u][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[hp][c], t[u][c], 0, 0, 0);
+        }
+      // D: lane (column i16, rows 4 kq + j) of the 16 x 16 fragment
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const float4_t rs = *(const float4_t*)(un + (2 * rp + u) * 16 + kq * 4);
+#pragma unroll
+        for (int c = 0; c < MP_CT; ++c)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[2 * rp + u][c][j] = fmaf(t[u][c][j], rs[j] * cs[c], acc[2 * rp + u][c][j]);
+      }
+    }
+  };
+
+  // ---- K loop: one blob tile a trip, the next tile's operands requested before this tile's MFMAs ----
+  MoePromptB<SMODE> b0, b1;
+  load_b(0, b0);
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    stage_load(0, g);
+    stage_write(0, g);
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int kt = 0; kt < a.tiles_k; ++kt) {
+    const int buf = kt & 1;
+    const bool more = kt + 1 < a.tiles_k;
+    if (more) load_b(kt + 1, b1);
+    unpack(b0);
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      if (more) stage_load(kt + 1, g);
+      compute(buf, g);
+      if (more) stage_write(buf ^ 1, g);
+    }
+    __syncthreads();  // image buf ^ 1 is complete; every read of image buf is done
+    if (more) b0 = b1;
+  }
+
+  // ---- epilogue ----
+#pragma unroll
+  for (int rt = 0; rt < 8; ++rt) {
+    if (rt >= nrt) break;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = rt * 16 + kq * 4 + j;
+      if (row >= R) continue;
+      float* orow = a.out + (size_t)(first + row) * a.ldo;
+      if constexpr (GU) {
+        const float g = acc[rt][0][j], u = acc[rt][1][j];
+        if (live[0]) orow[wt * 16 + i16] = g / (1.0f + expf(-g)) * u;  // wt < half_tiles: a column inside I
+      } else {
+#pragma unroll
+        for (int c = 0; c < MP_CT; ++c) {
+          const int n = (wt * MP_CT + c) * 16 + i16;
+          if (live[c] && n < a.N) orow[n] = acc[rt][c][j];
+        }
+      }
+    }
+  }
+}
+
+struct MoePromptWorkspace {
+  size_t sorted, pos_of, blocks, nblocks, counts, h, y, total;
+  int max_blocks, nseg;
+};
+MoePromptWorkspace moe_prompt_ws(int T, int top_k, int E, int hidden, int inter) {
+  MoePromptWorkspace w;
+  const size_t S = (size_t)T * top_k;
+  w.max_blocks = (int)((S + MP_ROWS - 1) / MP_ROWS + std::min<size_t>((size_t)E, S));
+  w.nseg = (int)((S + MP_SEG - 1) / MP_SEG);
+  w.sorted = 0;
+  w.pos_of = w.sorted + woq_round_up(S * 4, 256);
+  w.blocks = w.pos_of + woq_round_up(S * 4, 256);
+  w.nblocks = w.blocks + woq_round_up((size_t)w.max_blocks * sizeof(MoeBlock), 256);
+  w.counts = w.nblocks + 256;
+  w.h = w.counts + woq_round_up((size_t)w.nseg * E * 4, 256);
+  w.y = w.h + woq_round_up(S * (size_t)inter * 4, 256);
+  w.total = w.y + woq_round_up(S * (size_t)hidden * 4, 256);
+  return w;
+}
+
+bool moe_prompt_shape_ok(int T, int top_k, int E, int hidden, int inter) {
+  return T > 0 && top_k > 0 && E > 0 && hidden > 0 && inter > 0 && E <= MOE_MAX_EXPERTS &&
+         (long long)T * top_k <= MOE_PROMPT_MAX_SLOTS;
+}
+
+template <bool GU, int SMODE, bool ASYM>
+int moe_prompt_launch_one(const MoePromptArgs& a, dim3 grid, hipStream_t st) {
+  if (const int rc = allow_dynamic_lds<moe_prompt_gemm_kernel<GU, SMODE, ASYM>>(MP_LDS)) return rc;
+  hipLaunchKernelGGL((moe_prompt_gemm_kernel<GU, SMODE, ASYM>), grid, dim3(MP_WAVES * 64), MP_LDS, st, a);
+  return 0;
+}
+template <bool GU>
+int moe_prompt_launch_gemm(const MoePromptArgs& a, bool smode1, bool asym, dim3 grid, hipStream_t st) {
+  if (!smode1) return asym ? moe_prompt_launch_one<GU, 0, true>(a, grid, st) : moe_prompt_launch_one<GU, 0, false>(a, grid, st);
+  return asym ? moe_prompt_launch_one<GU, 1, true>(a, grid, st) : moe_prompt_launch_one<GU, 1, false>(a, grid, st);
+}
+
+MoePromptArgs moe_prompt_args(const void* blobs, const woq_blob_header& h, size_t stride) {
+  MoePromptArgs a = {};
+  a.blobs = (const uint8_t*)blobs, a.stride = stride;
+  a.off_q = h.off_q, a.off_scale = h.off_scale, a.off_zp = h.off_zp;
+  a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.tiles_n = h.Npad / WOQ_TILE_N;
+  a.n_groups = h.n_groups, a.group = h.group, a.scale_type = (int)h.scale_type;
+  return a;
+}
+
+}  // namespace
+
+int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st) {
+  const woq_blob_header& gh = *m.gate_up_hdr;
+  const woq_blob_header& dh = *m.down_hdr;
+  const int H = dh.N, I = dh.K;
+  const MoePromptWorkspace w = moe_prompt_ws(m.T, m.top_k, m.E, H, I);
+  uint8_t* ws = (uint8_t*)m.workspace;
+  int32_t* sorted = (int32_t*)(ws + w.sorted);
+  int32_t* pos_of = (int32_t*)(ws + w.pos_of);
+  MoeBlock* blocks = (MoeBlock*)(ws + w.blocks);
+  int32_t* nblocks = (int32_t*)(ws + w.nblocks);
+  int32_t* counts = (int32_t*)(ws + w.counts);
+  float* hbuf = (float*)(ws + w.h);
+  float* ybuf = (float*)(ws + w.y);
+  const int S = m.T * m.top_k;
+
+  const dim3 pgrid((unsigned)w.nseg), pblock(MP_SEG);
+  if (m.idx_is_int64)
+    hipLaunchKernelGGL(moe_prompt_count_kernel<true>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, pos_of);
+  else
+    hipLaunchKernelGGL(moe_prompt_count_kernel<false>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, pos_of);
+  hipLaunchKernelGGL(moe_prompt_scan_kernel, dim3(1), pblock, 0, st, w.nseg, m.E, counts, blocks, nblocks);
+  if (m.idx_is_int64)
+    hipLaunchKernelGGL(moe_prompt_scatter_kernel<true>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, sorted, pos_of);
+  else
+    hipLaunchKernelGGL(moe_prompt_scatter_kernel<false>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, sorted, pos_of);
+
+  MoePromptArgs g = moe_prompt_args(m.gate_up_blobs, gh, m.gate_up_stride);
+  g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
+  g.sorted = sorted, g.blocks = blocks, g.nblocks = nblocks;
+  g.out = hbuf, g.ldo = I, g.half_tiles = I / 16;
+  const unsigned gx = (unsigned)((I / 16 + MP_WAVES - 1) / MP_WAVES);
+  if (const int rc = moe_prompt_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, dim3(gx, (unsigned)w.max_blocks), st))
+    return rc;
+
+  MoePromptArgs d = moe_prompt_args(m.down_blobs, dh, m.down_stride);
+  d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
+  d.sorted = sorted, d.blocks = blocks, d.nblocks = nblocks;
+  d.out = ybuf, d.ldo = H, d.half_tiles = 0;
+  const unsigned dx = (unsigned)((d.tiles_n + MP_WAVES * MP_CT - 1) / (MP_WAVES * MP_CT));
+  if (const int rc = moe_prompt_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, dim3(dx, (unsigned)w.max_blocks), st))
+    return rc;
+
+  launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
+  WOQ_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace woq
+
+extern "C" size_t woq_moe_prompt_workspace(int T, int top_k, int E, int hidden, int inter) {
+  if (!woq::moe_prompt_shape_ok(T, top_k, E, hidden, inter)) return 0;
+  return woq::moe_prompt_ws(T, top_k, E, hidden, inter).total;
+}
+
+extern "C" int woq_moe_prompt_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,
+                                      const float* topk_w_dev, int T, int top_k, int E, const void* gate_up_blobs_dev,
+                                      const woq_blob_header* gate_up_hdr, size_t gate_up_stride,
+                                      const void* down_blobs_dev, const woq_blob_header* down_hdr, size_t down_stride,
+                                      void* out_dev, int out_dtype, int ldo, void* workspace_dev, size_t workspace_bytes,
+                                      void* stream) {
+  WOQ_TRY
+  using namespace woq;
+  WOQ_CHECK(gate_up_hdr && down_hdr, "QBits: woq_moe_prompt_forward: null header");
+  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(*down_hdr, down_stride)) WOQ_FAIL(p);
+  const int H = down_hdr->N, I = down_hdr->K;
+  WOQ_CHECK(gate_up_hdr->K == H && gate_up_hdr->N == 2 * I,
+            "QBits: woq_moe_prompt_forward: gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");
+  WOQ_CHECK(I % 16 == 0, "QBits: woq_moe_prompt_forward: the intermediate size must be a multiple of 16 (gate tile tn pairs "
+                         "with up tile tn + inter / 16)");
+  WOQ_CHECK(H % 4 == 0, "QBits: woq_moe_prompt_forward: the hidden size must be a multiple of 4");
+  auto dtype_ok = [](int d) { return d == WOQ_F32 || d == WOQ_BF16 || d == WOQ_F16; };
+  WOQ_CHECK(dtype_ok(x_dtype) && dtype_ok(out_dtype), "QBits: unsupported qbits data type.");
+  if (T <= 0) return 0;
+  WOQ_CHECK(moe_prompt_shape_ok(T, top_k, E, H, I),
+            "QBits: woq_moe_prompt_forward takes at most " + std::to_string(MOE_MAX_EXPERTS) + " experts and " +
+                std::to_string(MOE_PROMPT_MAX_SLOTS) + " routed slots (T * top_k) per call");
+  WOQ_CHECK(x_dev && topk_idx_dev && topk_w_dev && gate_up_blobs_dev && down_blobs_dev && out_dev && workspace_dev,
+            "QBits: woq_moe_prompt_forward: null tensor");
+  WOQ_CHECK(ldx >= H && ldo >= H, "QBits: woq_moe_prompt_forward: leading dimension smaller than hidden");
+  const size_t xsz = woq_dtype_size((uint32_t)x_dtype);
+  WOQ_CHECK((uintptr_t)x_dev % (4 * xsz) == 0 && ldx % 4 == 0,
+            "QBits: woq_moe_prompt_forward: activation rows must be aligned to four elements");
+  WOQ_CHECK((uintptr_t)gate_up_blobs_dev % 16 == 0 && (uintptr_t)down_blobs_dev % 16 == 0 &&
+                (uintptr_t)workspace_dev % 16 == 0,
+            "QBits: woq_moe_prompt_forward: blobs and workspace must be 16-byte aligned");
+  const size_t need = moe_prompt_ws(T, top_k, E, H, I).total;
+  WOQ_CHECK(workspace_bytes >= need, "QBits: woq_moe_prompt_forward: the workspace holds " +
+                                         std::to_string(workspace_bytes) + " bytes, this call needs " +
+                                         std::to_string(need) + " (woq_moe_prompt_workspace)");
+  MoeCall m;
+  m.x = x_dev, m.x_dtype = x_dtype, m.ldx = ldx;
+  m.topk_idx = topk_idx_dev, m.idx_is_int64 = idx_is_int64 != 0, m.topk_w = topk_w_dev;
+  m.T = T, m.top_k = top_k, m.E = E;
+  m.gate_up_blobs = gate_up_blobs_dev, m.gate_up_hdr = gate_up_hdr, m.gate_up_stride = gate_up_stride;
+  m.down_blobs = down_blobs_dev, m.down_hdr = down_hdr, m.down_stride = down_stride;
+  m.out = out_dev, m.out_dtype = out_dtype, m.ldo = ldo, m.workspace = workspace_dev;
+  if (const int rc = launch_moe_prompt_forward(m, (hipStream_t)stream)) return rc;
+  WOQ_END
+}

@@ -17,7 +17,7 @@ __all__ = [
     "acquire_packed_weight_info", "get_packed_weight_size", "set_woq_workspace", "set_qbits_threads",
     "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
     "awq_scale_delta", "awq_clip_search", "autoround_forward", "autoround_step", "autoround_codes",
-    "teq_forward", "teq_grad", "woq_linear_backward", "woq_linear_backward_workspace", "moe_forward", "moe_workspace",
+    "teq_forward", "teq_grad", "woq_linear_backward", "woq_linear_backward_workspace", "moe_forward", "moe_workspace", "MOE_PROMPT_MAX_SLOTS",
 ]
 
 
@@ -402,23 +402,32 @@ def woq_linear_backward(grad_output, weight, grad_input=None, dtype=None):
 
 
 MOE_MAX_EXPERTS, MOE_MAX_SLOTS = 1024, 8192  # csrc/woq_host.h: what one moe_forward call takes (slots = T * top_k)
+MOE_PROMPT_MAX_SLOTS = 65536  # csrc/woq_host.h: the slots of one form="prompt" call
 _moe_scratch = None  # moe_forward's own scratch, grown on demand: a steady decode loop allocates nothing
 
 
-def moe_workspace(t, top_k, e, hidden, inter):
-    """Bytes of scratch one `moe_forward` call takes (woq_moe_workspace, include/woq_hip.h); 0 = a shape it refuses."""
-    return int(L.lib().woq_moe_workspace(int(t), int(top_k), int(e), int(hidden), int(inter)))
+def moe_workspace(t, top_k, e, hidden, inter, form="grouped"):
+    """Bytes of scratch one `moe_forward` call takes (woq_moe_workspace | woq_moe_prompt_workspace, include/woq_hip.h);
+    0 = a shape it refuses."""
+    fn = L.lib().woq_moe_prompt_workspace if form == "prompt" else L.lib().woq_moe_workspace
+    return int(fn(int(t), int(top_k), int(e), int(hidden), int(inter)))
 
 
-def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_blobs, out=None, workspace=None):
+def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_blobs, out=None, workspace=None,
+                form="grouped"):
     """out[t] = sum_j top_k_weights[t, j] * down_e(SiLU(gate_e x_t) * up_e x_t), e = top_k_index[t, j], j ascending
     (woq_moe_forward, csrc/woq_moe.hip; the definition is HF's MixtralExperts.forward, no reference counterpart).
     hidden_states [T, H] fp32 / bf16 / fp16 with unit column stride; top_k_index [T, k] int64 or int32 (an id outside
     [0, E) drops its slot); top_k_weights [T, k]; gate_up_blobs / down_blobs uint8 [E, stride]: E WQH1 blobs each
     (K = H, N = 2I, gate columns first | K = I, N = H) as `quantize_to_packed_weight` writes them. Four launches and no
     host synchronisation, whatever the routing; deterministic. `out` [T, H] (allocated in hidden_states' type when None);
-    `workspace`: a uint8 device tensor of `moe_workspace` bytes (this module keeps one of its own when None)."""
+    `workspace`: a uint8 device tensor of `moe_workspace` bytes (this module keeps one of its own when None).
+    `form`: "grouped" (at most 16 rows a workgroup on the exact int8 fixed point, up to MOE_MAX_SLOTS slots: decode and
+    short prompts) or "prompt" (woq_moe_prompt_forward, csrc/woq_moe_prompt.hip: 128-row blocks on the fp16 MFMA, one
+    fp16 product per operand pair with fp32 accumulation, up to MOE_PROMPT_MAX_SLOTS slots, six launches)."""
     global _moe_scratch
+    if form not in ("grouped", "prompt"):
+        raise RuntimeError("QBits: moe_forward: form must be 'grouped' or 'prompt'")
     gh, dh = header_of(gate_up_blobs), header_of(down_blobs)
     x = hidden_states
     if not (x.is_cuda and x.dim() == 2 and x.device == gate_up_blobs.device == down_blobs.device):
@@ -448,7 +457,7 @@ def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_b
     if t == 0:
         return out
     e_n = gate_up_blobs.shape[0]
-    need = moe_workspace(t, k, e_n, dh.N, dh.K)
+    need = moe_workspace(t, k, e_n, dh.N, dh.K, form)
     ws = workspace
     if ws is None:
         if need and (_moe_scratch is None or _moe_scratch.numel() < need or _moe_scratch.device != x.device):
@@ -458,11 +467,12 @@ def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_b
         raise RuntimeError("QBits: moe_forward: the workspace must be a contiguous tensor on the device")
     ldx = x.stride(0) if t > 1 else max(x.stride(0), hidden)
     ldo = out.stride(0) if t > 1 else max(out.stride(0), hidden)
-    L.check(L.lib().woq_moe_forward(_ptr(x), L.torch_dtype_code(x.dtype), ldx, _ptr(idx), int(idx.dtype == torch.int64),
-                                    _ptr(w), t, k, e_n, _ptr(gate_up_blobs), ctypes.byref(gh), gate_up_blobs.stride(0),
-                                    _ptr(down_blobs), ctypes.byref(dh), down_blobs.stride(0), _ptr(out),
-                                    L.torch_dtype_code(out.dtype), ldo, _ptr(ws),
-                                    0 if ws is None else ws.numel() * ws.element_size(), L.stream_ptr()))
+    fn = L.lib().woq_moe_prompt_forward if form == "prompt" else L.lib().woq_moe_forward
+    L.check(fn(_ptr(x), L.torch_dtype_code(x.dtype), ldx, _ptr(idx), int(idx.dtype == torch.int64),
+               _ptr(w), t, k, e_n, _ptr(gate_up_blobs), ctypes.byref(gh), gate_up_blobs.stride(0),
+               _ptr(down_blobs), ctypes.byref(dh), down_blobs.stride(0), _ptr(out),
+               L.torch_dtype_code(out.dtype), ldo, _ptr(ws),
+               0 if ws is None else ws.numel() * ws.element_size(), L.stream_ptr()))
     return out
 
 

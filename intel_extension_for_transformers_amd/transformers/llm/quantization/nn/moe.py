@@ -7,7 +7,10 @@ so HF's `*SparseMoeBlock` and its router stay as they are. Every expert's two ma
 `qbits.quantize_to_packed_weight` into WQH1 blobs, stacked at a uniform stride: `gate_up_blobs`, `down_blobs` uint8
 [E, stride]. Two forms compute the same block:
   grouped  one `qbits.moe_forward` call (csrc/woq_moe.hip: plan, gate/up, down, combine — four launches, the routing never
-           reaches the host), for T <= `grouped_max_tokens` and the integer 4-bit-storage weight types;
+           reaches the host), for T <= `grouped_max_tokens` (below `prompt_min_tokens`) and the integer 4-bit-storage
+           weight types;
+  prompt   the same call with form="prompt" (csrc/woq_moe_prompt.hip: 128-row blocks of one expert on the fp16 MFMA, six
+           launches) from `prompt_min_tokens` rows up, in row chunks of at most `qbits.MOE_PROMPT_MAX_SLOTS` slots;
   loop     HF's per-expert loop with each `F.linear` a `qbits.woq_linear` on the expert's slice of the blob tensor: above
            that limit, and for the weight types the grouped kernels do not take (nf4, fp4, fp8, int8).
 """
@@ -55,6 +58,10 @@ class QuantizedMoEExpertsQBits(torch.nn.Module):
     # The largest T of tools/moe_rate.py's {1, 4, 16, 64, 256} at which the grouped form is not slower than the loop form
     # at both measured shapes (Mixtral-8x7B and Qwen3-30B-A3B, int4 g128): profiles/r22_moe_rate.txt.
     grouped_max_tokens = 256
+    # From this many rows the prompt form serves the call: the smallest T of tools/moe_rate.py's {64, 128, ..., 4096} from
+    # which its median is below that of the form that served the T before (grouped up to 256, loop above), at both
+    # measured shapes and by more than either's min-to-median spread (profiles/r23_moe_prompt_rate.txt). Not measured below.
+    prompt_min_tokens = 64
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, compute_dtype="fp32", weight_dtype="int4_clip", bits=4,
                  scale_dtype="fp32", blocksize=32, scheme="sym", device=None):
@@ -74,11 +81,27 @@ class QuantizedMoEExpertsQBits(torch.nn.Module):
     def forward(self, hidden_states, top_k_index, top_k_weights):
         if self.gate_up_blobs.numel() == 0:
             raise RuntimeError("QBits: QuantizedMoEExpertsQBits has no packed weights (call set_fp_weights first)")
-        t = hidden_states.shape[0]
+        t, k = hidden_states.shape[0], top_k_index.shape[-1]
+        if self.grouped_supported() and t >= self.prompt_min_tokens:
+            return self.prompt_forward(hidden_states, top_k_index, top_k_weights, max(1, qbits.MOE_PROMPT_MAX_SLOTS // k))
         if (self.grouped_supported() and t <= self.grouped_max_tokens
                 and t * top_k_index.shape[-1] <= qbits.MOE_MAX_SLOTS):
             return qbits.moe_forward(hidden_states, top_k_index, top_k_weights, self.gate_up_blobs, self.down_blobs)
         return self.loop_forward(hidden_states, top_k_index, top_k_weights)
+
+    def prompt_forward(self, hidden_states, top_k_index, top_k_weights, chunk_tokens):
+        """form="prompt" over row chunks of whole tokens (rows are independent, so chunking is exact)"""
+        t = hidden_states.shape[0]
+        if t <= chunk_tokens:
+            return qbits.moe_forward(hidden_states, top_k_index, top_k_weights, self.gate_up_blobs, self.down_blobs,
+                                     form="prompt")
+        x = hidden_states if hidden_states.dtype in (torch.float32, torch.bfloat16, torch.float16) else hidden_states.float()
+        out = torch.empty(t, self.hidden_dim, dtype=x.dtype, device=x.device)
+        for r in range(0, t, chunk_tokens):
+            s = slice(r, min(r + chunk_tokens, t))
+            qbits.moe_forward(x[s], top_k_index[s], top_k_weights[s], self.gate_up_blobs, self.down_blobs, out=out[s],
+                              form="prompt")
+        return out
 
     def _expert_views(self, kind):
         """the E blobs of a kind as 1-D views that carry their header (qbits.header_of then never reads the device)"""

@@ -1,8 +1,11 @@
 """What one routed expert block costs at the Mixtral-8x7B shape (H 4096, I 14336, E 8, k 2) and the Qwen3-30B-A3B shape
-(H 2048, I 768, E 128, k 8), int4 g128 symmetric, fp16 activations, T in {1, 4, 16, 64, 256}, uniform random routing
-(k distinct experts per token, softmax weights):
+(H 2048, I 768, E 128, k 8), int4 g128 symmetric, fp16 activations, T in {1, 4, 16, 64, 128, 256, 512, 1024, 2048, 4096}
+(a shape whose k admits no more than 8192 tokens in one prompt-form call also runs that T and one chunked T beyond it),
+uniform random routing (k distinct experts per token, softmax weights):
 
   grouped  QuantizedMoEExpertsQBits' one `qbits.moe_forward` call (csrc/woq_moe.hip: four launches, no host round trip)
+  prompt   the same call with form="prompt" (csrc/woq_moe_prompt.hip: six launches, 128-row blocks on the fp16 MFMA), from
+           T = 64 up; beyond `qbits.MOE_PROMPT_MAX_SLOTS` slots through the module's row chunks
   loop     its per-expert loop form (`qbits.woq_linear` on the expert's blobs, a host round trip for the experts hit)
   hf_fp16  the fp16 `MixtralExperts.forward` it replaces (HF's own loop, `_experts_implementation = "eager"`)
 
@@ -26,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = {"mixtral-8x7b": (4096, 14336, 8, 2), "qwen3-30b-a3b": (2048, 768, 128, 8)}
-TOKENS = (1, 4, 16, 64, 256)
+TOKENS = (1, 4, 16, 64, 128, 256, 512, 1024, 2048, 4096)
+PROMPT_FROM = 64
 
 
 def main():
@@ -75,7 +79,8 @@ def main():
         mod.set_fp_weights(hf.gate_up_proj.data, hf.down_proj.data)
         blob_bytes = mod.gate_up_blobs.shape[1] + mod.down_blobs.shape[1]
         rows = {}
-        for T in TOKENS:
+        one_call = qbits.MOE_PROMPT_MAX_SLOTS // k
+        for T in TOKENS + ((one_call, one_call + one_call // 2) if one_call <= 8192 else ()):
             x = torch.randn(T, H, generator=gen, device="cuda", dtype=torch.float16)
             sets = []
             for _ in range(args.routings):
@@ -83,11 +88,15 @@ def main():
                 w, idx = torch.topk(score, k, dim=-1)
                 sets.append((idx, torch.softmax(w, dim=-1)))
             hit = statistics.mean(len(torch.unique(idx)) for idx, _ in sets)
+            g = p = (float("nan"), float("nan"))
             with torch.no_grad():
-                g = timed(lambda i: qbits.moe_forward(x, *sets[i % len(sets)], mod.gate_up_blobs, mod.down_blobs))
+                if T * k <= qbits.MOE_MAX_SLOTS:
+                    g = timed(lambda i: qbits.moe_forward(x, *sets[i % len(sets)], mod.gate_up_blobs, mod.down_blobs))
+                if T >= PROMPT_FROM:
+                    p = timed(lambda i: mod.prompt_forward(x, *sets[i % len(sets)], one_call))
                 lp = timed(lambda i: mod.loop_forward(x, *sets[i % len(sets)]))
                 h = timed(lambda i: hf(x, sets[i % len(sets)][0], sets[i % len(sets)][1].half()))
-            rows[T] = {"grouped_us": g, "loop_us": lp, "hf_fp16_us": h, "experts_hit": round(hit, 2),
+            rows[T] = {"grouped_us": g, "prompt_us": p, "loop_us": lp, "hf_fp16_us": h, "experts_hit": round(hit, 2),
                        "grouped_GBps": round(hit * blob_bytes / g[1] / 1e3, 1)}
         res["shapes"][name] = {"H": H, "I": I, "E": E, "k": k, "blob_bytes_per_expert": blob_bytes, "T": rows}
         del hf, mod
@@ -97,10 +106,12 @@ def main():
     for name, s in res["shapes"].items():
         print("%s (H %d, I %d, E %d, k %d; %d blob bytes an expert)" % (name, s["H"], s["I"], s["E"], s["k"],
                                                                        s["blob_bytes_per_expert"]))
-        print("  %5s %19s %19s %19s %12s %13s" % ("T", "grouped", "loop", "hf fp16", "experts hit", "grouped GB/s"))
+        print("  %5s %21s %21s %21s %21s %12s %13s" % ("T", "grouped", "prompt", "loop", "hf fp16", "experts hit",
+                                                        "grouped GB/s"))
         for T, r in s["T"].items():
-            print("  %5d %9.1f /%8.1f %9.1f /%8.1f %9.1f /%8.1f %12.2f %13.1f" % (
-                T, *r["grouped_us"], *r["loop_us"], *r["hf_fp16_us"], r["experts_hit"], r["grouped_GBps"]))
+            print("  %5d %10.1f /%9.1f %10.1f /%9.1f %10.1f /%9.1f %10.1f /%9.1f %12.2f %13.1f" % (
+                T, *r["grouped_us"], *r["prompt_us"], *r["loop_us"], *r["hf_fp16_us"], r["experts_hit"],
+                r["grouped_GBps"]))
     print(json.dumps(res, separators=(",", ":")))
 
 
