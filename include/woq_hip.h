@@ -656,6 +656,52 @@ WOQ_API int woq_engine_set_tp_options(woq_engine* e, int xq, int fused_push);
  * down partial, 2 = head. layer ignored for phase 2. */
 WOQ_API int woq_engine_phase(woq_engine* e, int layer, int phase, int greedy, void* stream);
 
+/* The router of a sparse mixture-of-experts layer, in front of woq_moe_forward's block (csrc/woq_moe_route.hip; HF MixtralTopKRouter / Qwen3MoeTopKRouter), all in fp32 and
+ * in a fixed order: xn = x * rsqrt(mean(x^2) + eps) * norm_w (norm_w NULL: xn = x), logit[e] = xn . router_w[e],
+ * p = softmax(logit), the top_k largest p in descending order (equal p: the lower expert id first), w = p[idx], divided by
+ * its own sum when renorm != 0. x fp32 [T, ldx]; norm_w fp32 [H]; router_w [E, H] dense in router_dtype (fp32 / bf16 /
+ * fp16); xn_out fp32 [T, H] or NULL; idx_out int32 [T, top_k]; w_out fp32 [T, top_k]. H % 4 == 0, 1 <= E <= 256,
+ * 1 <= top_k <= min(E, 16), pointers 16-byte aligned, ldx % 4 == 0; anything else fails with a "QBits:" message before
+ * any launch. One launch, stream-ordered, no allocation, no floating-point atomics: the same inputs give the same bytes.
+ * T == 1 runs the decode form (several workgroups, the last to arrive selects) and needs scratch_dev:
+ * woq_moe_route_scratch_bytes() bytes, zero before the first call, left ready for the next one by every call; calls that
+ * share a scratch must be ordered by their stream. T > 1 runs on v_mfma_f32_16x16x4_f32 and ignores scratch_dev.
+ * A NaN probability (a NaN or infinite input) ranks below every number: the ids stay in [0, E), the weights are NaN.
+ * T == 1 only, all four or none: sorted_out / pos_of_out int32 [top_k], blocks_out {expert, first, rows, pad} int32
+ * [top_k][4] and nblocks_out int32 [1] receive the row's plan as woq_moe_forward's plan launch would write it from
+ * idx_out. */
+WOQ_API size_t woq_moe_route_scratch_bytes(void);
+WOQ_API int woq_moe_route(const float* x_dev, int ldx, const float* norm_w_dev, float eps, const void* router_w_dev,
+                          int router_dtype, int T, int H, int E, int top_k, int renorm, float* xn_out,
+                                int32_t* idx_out, float* w_out, void* scratch_dev, int32_t* sorted_out,
+                                int32_t* pos_of_out, void* blocks_out, int32_t* nblocks_out, void* stream);
+
+
+/* ---- sparse mixture-of-experts layers on the engine (new entry points only, WOQ_ABI_VERSION stays 4) -------------------
+ * A layer whose MLP is a routed expert block (HF Mixtral / Qwen3-MoE). woq_engine_set_layer comes first for that layer,
+ * with gate_up_blob and down_blob NULL (their headers are not read); the layer then counts as unset until this call.
+ * Layers are dense or sparse one by one. router_w: [E, hidden] dense in router_dtype (fp32 / bf16 / fp16); the stacked
+ * expert blobs exactly as woq_moe_forward takes them (gate columns [0, I), up [I, 2 I), one header and stride a kind).
+ * Decode step, sparse layer: the attention block as ever, then four launches — route (woq_moe_route's decode form over
+ * the fp32 residual row through post_attention_layernorm, which also writes the grouped products' plan), grouped gate/up,
+ * grouped down, and the combine onto the residual stream, which emits the next layer's XQ vector. Prompt pass: route
+ * over all rows, woq_moe_forward's launches below 64 rows and woq_moe_prompt_forward's from 64 (in row chunks of whole
+ * tokens within its slot limit), combined onto the residual rows; workspace grows with the other prompt buffers, never
+ * inside a capture. Fails with a "QBits:" message, before anything is stored, on a tensor-parallel engine, on fp8-weight
+ * layers, for expert blobs woq_moe_forward refuses (nf4 / fp4 / fp8 / int8, act-order), for E > 256 or top_k > 16, and
+ * while a LoRA adapter sits on the layer's gate / up / down targets (woq_engine_set_lora refuses those on a sparse
+ * layer; q / k / v / o stay allowed). woq_engine_phase and the timing hooks refuse an engine with a sparse layer. */
+typedef struct woq_moe_layer_weights {
+  const void* router_w;
+  int32_t router_dtype, experts, top_k, renorm; /* renorm: divide the top_k weights by their sum */
+  int32_t moe_inter, reserved[3];
+  const void* gate_up_blobs; /* [E] blobs [hidden -> 2 * moe_inter] */
+  const void* down_blobs;    /* [E] blobs [moe_inter -> hidden] */
+  uint64_t gate_up_stride, down_stride;
+  woq_blob_header gate_up_hdr, down_hdr;
+} woq_moe_layer_weights;
+WOQ_API int woq_engine_set_layer_moe(woq_engine* e, int layer, const woq_moe_layer_weights* w);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,16 @@ class LayerWeights(ctypes.Structure):
                 ("qkv_hdr", BlobHeader), ("o_hdr", BlobHeader), ("gate_up_hdr", BlobHeader), ("down_hdr", BlobHeader)]
 
 
+class MoeLayerWeights(ctypes.Structure):
+    """struct woq_moe_layer_weights (include/woq_hip.h)."""
+
+    _fields_ = [("router_w", ctypes.c_void_p), ("router_dtype", ctypes.c_int32), ("experts", ctypes.c_int32),
+                ("top_k", ctypes.c_int32), ("renorm", ctypes.c_int32), ("moe_inter", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3), ("gate_up_blobs", ctypes.c_void_p), ("down_blobs", ctypes.c_void_p),
+                ("gate_up_stride", ctypes.c_uint64), ("down_stride", ctypes.c_uint64),
+                ("gate_up_hdr", BlobHeader), ("down_hdr", BlobHeader)]
+
+
 class SamplerConfig(ctypes.Structure):
     """struct woq_sampler_config (include/woq_hip.h)."""
 
@@ -105,6 +115,7 @@ EXPORTS = [
     "woq_engine_set_h2o", "woq_engine_h2o_reset", "woq_engine_h2o_score_ptr", "woq_engine_h2o_evict",
     "woq_h2o_decode_scratch_bytes", "woq_h2o_score_decode", "woq_h2o_score_prompt", "woq_h2o_select", "woq_h2o_compact",
     "woq_moe_workspace", "woq_moe_forward", "woq_moe_prompt_workspace", "woq_moe_prompt_forward",
+    "woq_moe_route_scratch_bytes", "woq_moe_route", "woq_engine_set_layer_moe",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -172,6 +183,9 @@ def lib():
     L.woq_moe_prompt_workspace.restype = cs
     L.woq_moe_prompt_workspace.argtypes = L.woq_moe_workspace.argtypes
     L.woq_moe_prompt_forward.argtypes = L.woq_moe_forward.argtypes
+    L.woq_moe_route_scratch_bytes.restype = cs
+    L.woq_moe_route_scratch_bytes.argtypes = []
+    L.woq_moe_route.argtypes = [vp, ci, vp, cf, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.woq_read_header.argtypes = [vp, ctypes.POINTER(BlobHeader), vp]
     L.woq_blob_extract.argtypes = [vp, ctypes.POINTER(BlobHeader), ci, vp, vp]
     L.woq_linear.argtypes = [vp, ci, ci, vp, ctypes.POINTER(BlobHeader), vp, vp, ci, ci, ci, vp]
@@ -185,6 +199,7 @@ def lib():
     L.woq_engine_set_layer.argtypes = [vp, ci, ctypes.POINTER(LayerWeights)]
     L.woq_engine_set_head.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp]
     L.woq_engine_set_layer_extras.argtypes = [vp, ci, vp, vp, vp]
+    L.woq_engine_set_layer_moe.argtypes = [vp, ci, ctypes.POINTER(MoeLayerWeights)]
     L.woq_engine_lora_reserve.argtypes = [vp, ci]
     L.woq_engine_set_lora.argtypes = [vp, ci, ci, vp, vp, ci, cf]
     L.woq_engine_clear_lora.argtypes = [vp]

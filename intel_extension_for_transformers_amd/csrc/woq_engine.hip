@@ -31,6 +31,17 @@ struct EngineProj { const void* blob; woq_blob_header hdr; const void* fp8_lo; }
 // what woq_engine_set_layer last committed for a layer: nothing yet, integer / 4-bit table blobs, fp8-weight blobs. A step
 // needs every layer set and all of one kind (engine_layers_problem)
 enum LayerKind { LAYER_UNSET, LAYER_INT, LAYER_FP8 };
+// a sparse layer's MLP (woq_engine_set_layer_moe): the router and the stacked expert blobs as woq_moe.hip takes them.
+// pending: woq_engine_set_layer came with no gate/up and down blobs, the layer waits for its experts
+struct EngineMoe {
+  bool on = false, pending = false;
+  const void* router = nullptr;
+  int router_dtype = WOQ_F32, E = 0, top_k = 0, renorm = 0, inter = 0;
+  const void* gu_blobs = nullptr;
+  const void* down_blobs = nullptr;
+  size_t gu_stride = 0, down_stride = 0;
+  woq_blob_header gu_hdr = {}, down_hdr = {};
+};
 // qkv_bias / q_norm / k_norm: the optional extras of woq_engine_set_layer_extras (null = absent)
 struct EngineLayer {
   EngineProj p[P_COUNT];
@@ -40,6 +51,7 @@ struct EngineLayer {
   const float* qkv_bias = nullptr;
   const float* q_norm = nullptr;
   const float* k_norm = nullptr;
+  EngineMoe moe;
 };
 // the pick after an lm_head (woq_engine::tail decides, engine_tail issues); pairs: that lm_head emits (max, index) pairs
 enum TailPick { PICK_NONE, PICK_SAMPLED, PICK_ARGMAX_FULL, PICK_ARGMAX_PAIRS, PICK_ARGMAX_EMBED, PICK_TP_GREEDY };
@@ -218,6 +230,23 @@ struct woq_engine {
     if (h2o_on) o.fuse_attn = false;
     return o;
   }
+  // sparse layers (woq_moe_route.hip, woq_moe.hip, woq_moe_prompt.hip). Decode: one row's xn, ids, weights, the router's
+  // scratch (ticket word zero between launches) and the grouped form's workspace for T = 1, sized for the largest sparse
+  // layer by woq_engine_set_layer_moe. Prompt pass: the same per row, grown on demand with the other prompt buffers
+  float* moe_xn = nullptr;
+  int32_t* moe_idx = nullptr;
+  float* moe_w = nullptr;
+  void* moe_scratch = nullptr;
+  void* moe_ws = nullptr;
+  size_t moe_ws_bytes = 0;
+  float* pf_moe_xn = nullptr;
+  int32_t* pf_moe_idx = nullptr;
+  float* pf_moe_w = nullptr;
+  void* pf_moe_ws = nullptr;
+  size_t pf_moe_rows = 0, pf_moe_ws_bytes = 0;
+  bool any_moe() const {
+    return std::any_of(layers.begin(), layers.end(), [](const EngineLayer& w) { return w.moe.on; });
+  }
   // the token tail, decided here alone: the pick after the lm_head of a step (after_prompt: of a prompt pass)
   Tail tail(bool greedy, bool fuse_next, bool after_prompt) const;
   woq::SampleTail sample_tail() const;  // the buffers of a sampled pick
@@ -254,6 +283,7 @@ static const XqPtrs kNoXq = {nullptr, nullptr, nullptr};
 static const char* engine_layers_problem(const woq_engine* e) {
   for (const EngineLayer& w : e->layers) {
     if (w.kind == LAYER_UNSET) return "QBits: engine layer not set (woq_engine_set_layer comes first, for every layer)";
+    if (w.moe.pending) return "QBits: engine layer set without an MLP (woq_engine_set_layer_moe brings its experts)";
     // (woq_engine_set_layer never commits a mix: this line guards the kernels' precondition where they are launched)
     if (w.kind != e->layers[0].kind) return "QBits: fp8 and integer layers cannot be mixed in one engine";
   }
@@ -389,7 +419,41 @@ static int engine_attn_block(woq_engine* e, int l, hipStream_t st) {
                            e->tp_residual(e->hidden), st);
 }
 
+// the expert blobs of layer l over T rows of xn, combined onto `res`: the call both forms take
+static MoeCall engine_moe_call(const woq_engine* e, int l, int T, const float* xn, const int32_t* idx, const float* w,
+                               void* ws, const MoeResidual* res) {
+  const EngineMoe& m = e->layers[l].moe;
+  MoeCall c;
+  c.x = xn, c.x_dtype = WOQ_F32, c.ldx = e->cfg.hidden;
+  c.topk_idx = idx, c.idx_is_int64 = false, c.topk_w = w;
+  c.T = T, c.top_k = m.top_k, c.E = m.E;
+  c.gate_up_blobs = m.gu_blobs, c.gate_up_hdr = &m.gu_hdr, c.gate_up_stride = m.gu_stride;
+  c.down_blobs = m.down_blobs, c.down_hdr = &m.down_hdr, c.down_stride = m.down_stride;
+  c.out = nullptr, c.out_dtype = WOQ_F32, c.ldo = e->cfg.hidden, c.workspace = ws;
+  c.residual = res;
+  return c;
+}
+
+// A sparse layer's MLP in the step, four launches: route (RMSNorm, logits, soft-max, top-k, and the plan of the one row),
+// grouped gate/up, grouped down, combine onto the residual stream — which leaves the new row as the next layer's XQ
+// input, as down_proj's epilogue does in a dense layer (nothing after the last layer: the head reads fp32)
+static int engine_moe_block(woq_engine* e, int l, hipStream_t st) {
+  const woq_engine_config& c = e->cfg;
+  const EngineMoe& m = e->layers[l].moe;
+  const MoeRoutePlan plan = moe_plan_tables(e->moe_ws, 1, m.top_k, m.E);
+  int rc = launch_moe_route(e->hidden, c.hidden, e->layers[l].ln2, c.rms_eps, m.router, m.router_dtype, 1, c.hidden, m.E,
+                            m.top_k, m.renorm, e->moe_xn, e->moe_idx, e->moe_w, e->moe_scratch, plan, st);
+  if (rc) return rc;
+  const bool emit = e->use_xq() && l + 1 < c.layers;
+  const MoeResidual res = {e->hidden, c.hidden, emit ? e->xq_hidden : kNoXq, emit ? e->layers[l + 1].ln1 : nullptr,
+                           emit ? e->ssq_part : nullptr};
+  MoeCall call = engine_moe_call(e, l, 1, e->moe_xn, e->moe_idx, e->moe_w, e->moe_ws, &res);
+  call.plan_ready = true;
+  return launch_moe_forward(call, st);
+}
+
 static int engine_mlp_block(woq_engine* e, int l, hipStream_t st) {
+  if (e->layers[l].moe.on) return engine_moe_block(e, l, st);
   if (e->use_xq()) return engine_mlp_block_xq(e, l, st);
   const woq_engine_config& c = e->cfg;
   const int rc = engine_linear_f32(e, l, P_GATE_UP, e->hidden, c.hidden, e->act, c.inter, e->layers[l].ln2, nullptr, st);
@@ -555,16 +619,72 @@ static int engine_prefill_reserve_lora(woq_engine* e, size_t rows) {
   return 0;
 }
 
+// rows of one expert call of a sparse layer's prompt pass: all of them in the grouped form (below MOE_PROMPT_MIN_ROWS
+// rows its slot limit is never reached), whole tokens within the prompt form's slot limit otherwise
+static int engine_moe_chunk_rows(int M, int top_k) {
+  return M < MOE_PROMPT_MIN_ROWS ? M : std::min(M, std::max(1, MOE_PROMPT_MAX_SLOTS / top_k));
+}
+
+// the sparse layers' share of the prompt pass's buffers: xn, ids and weights of `rows` rows and the largest call's workspace
+static int engine_prefill_reserve_moe(woq_engine* e, size_t rows) {
+  const woq_engine_config& c = e->cfg;
+  size_t ws = 0;
+  for (const EngineLayer& w : e->layers) {
+    if (!w.moe.on) continue;
+    const int chunk = engine_moe_chunk_rows((int)rows, w.moe.top_k);
+    ws = std::max(ws, (int)rows < MOE_PROMPT_MIN_ROWS ? woq_moe_workspace(chunk, w.moe.top_k, w.moe.E, c.hidden, w.moe.inter)
+                                                      : woq_moe_prompt_workspace(chunk, w.moe.top_k, w.moe.E, c.hidden, w.moe.inter));
+  }
+  if (rows <= e->pf_moe_rows && ws <= e->pf_moe_ws_bytes) return 0;
+  WOQ_HIP(hipDeviceSynchronize());
+  for (void* p : {(void*)e->pf_moe_xn, (void*)e->pf_moe_idx, (void*)e->pf_moe_w, e->pf_moe_ws})
+    if (p) WOQ_HIP(hipFree(p));
+  e->pf_moe_xn = nullptr, e->pf_moe_idx = nullptr, e->pf_moe_w = nullptr, e->pf_moe_ws = nullptr;
+  rows = std::max(rows, e->pf_moe_rows), ws = std::max(ws, e->pf_moe_ws_bytes);
+  e->pf_moe_rows = 0, e->pf_moe_ws_bytes = 0;
+  WOQ_HIP(hipMalloc((void**)&e->pf_moe_xn, rows * c.hidden * 4));
+  WOQ_HIP(hipMalloc((void**)&e->pf_moe_idx, rows * 16 * 4));
+  WOQ_HIP(hipMalloc((void**)&e->pf_moe_w, rows * 16 * 4));
+  WOQ_HIP(hipMalloc(&e->pf_moe_ws, ws));
+  e->pf_moe_rows = rows, e->pf_moe_ws_bytes = ws;
+  return 0;
+}
+
+// A sparse layer's MLP over the prompt pass's M rows: route into the xn rows, then per row chunk the grouped form's
+// launches (below MOE_PROMPT_MIN_ROWS rows) or the prompt form's, combined onto the residual rows
+static int engine_prefill_moe(woq_engine* e, int l, int M, hipStream_t st) {
+  const woq_engine_config& c = e->cfg;
+  const EngineMoe& m = e->layers[l].moe;
+  const MoeRoutePlan none = {nullptr, nullptr, nullptr, nullptr};
+  int rc = launch_moe_route(e->pf_h, c.hidden, e->layers[l].ln2, c.rms_eps, m.router, m.router_dtype, M, c.hidden, m.E,
+                            m.top_k, m.renorm, e->pf_moe_xn, e->pf_moe_idx, e->pf_moe_w, e->moe_scratch, none, st);
+  if (rc) return rc;
+  const int chunk = engine_moe_chunk_rows(M, m.top_k);
+  for (int r0 = 0; r0 < M; r0 += chunk) {
+    const int rows = std::min(chunk, M - r0);
+    const MoeResidual res = {e->pf_h + (size_t)r0 * c.hidden, c.hidden, kNoXq, nullptr, nullptr};
+    const MoeCall call = engine_moe_call(e, l, rows, e->pf_moe_xn + (size_t)r0 * c.hidden,
+                                         e->pf_moe_idx + (size_t)r0 * m.top_k, e->pf_moe_w + (size_t)r0 * m.top_k,
+                                         e->pf_moe_ws, &res);
+    rc = M < MOE_PROMPT_MIN_ROWS ? launch_moe_forward(call, st) : launch_moe_prompt_forward(call, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 static int engine_prefill_reserve(woq_engine* e, size_t rows) {
   const woq_engine_config& c = e->cfg;
   if (e->lora_rmax > 0)
     if (const int rc = engine_prefill_reserve_lora(e, rows)) return rc;
+  if (e->any_moe())
+    if (const int rc = engine_prefill_reserve_moe(e, rows)) return rc;
   // the largest call's workspace over EVERY layer's blobs: packed activation tiles + scales (+ the fragment image of a
   // table-type blob, so that such prompt passes allocate nothing per call either)
   size_t ws = 0;
   for (const EngineLayer& w : e->layers)
-    for (const EngineProj& p : w.p)
-      ws = std::max(ws, gemm_f16_workspace_bytes_blob((int)rows, p.hdr, 1, e->fp8_type != 0));
+    for (int k = 0; k < P_COUNT; ++k)
+      if (!(w.moe.on && (k == P_GATE_UP || k == P_DOWN)))  // (a sparse layer holds no dense MLP blobs)
+        ws = std::max(ws, gemm_f16_workspace_bytes_blob((int)rows, w.p[k].hdr, 1, e->fp8_type != 0));
   if (rows <= e->pf_rows && ws <= e->pf_ws_bytes) return 0;
   WOQ_HIP(hipDeviceSynchronize());
   for (void* p : {(void*)e->pf_h, (void*)e->pf_qkv, (void*)e->pf_attn, (void*)e->pf_act, e->pf_ws})
@@ -658,6 +778,10 @@ static int engine_prefill_impl(woq_engine* e, const int32_t* tokens, int n_seq, 
     rc = engine_prefill_gemm(e, l, P_O, M, e->pf_attn, WOQ_F16, c.heads * c.head_dim, e->pf_h, WOQ_F32, c.hidden, nullptr, st);
     if (rc) return rc;
     if ((rc = engine_allreduce_rows(e, e->pf_h, (size_t)M * c.hidden, st)) != 0) return rc;
+    if (w.moe.on) {
+      if ((rc = engine_prefill_moe(e, l, M, st)) != 0) return rc;
+      continue;
+    }
     if (e->lora_rows(l, P_GATE_UP) > 0) {  // plain gate / up rows, then the adapter's expand applies SiLU * mul
       rc = engine_prefill_gemm(e, l, P_GATE_UP, M, e->pf_h, WOQ_F32, c.hidden, e->pf_gu, WOQ_F16, 2 * c.inter, w.ln2, st, 0);
       if (rc == 0) rc = engine_prefill_lora(e, l, P_GATE_UP, M, st);
@@ -1083,6 +1207,8 @@ void woq_engine_destroy(woq_engine* e) {
   if (e->pf_gu) hipFree(e->pf_gu);
   if (e->guide_table) hipFree(e->guide_table);
   if (e->h2o_lse) hipFree(e->h2o_lse);
+  for (void* p : {(void*)e->pf_moe_xn, (void*)e->pf_moe_idx, (void*)e->pf_moe_w, e->pf_moe_ws, e->moe_ws})
+    if (p) hipFree(p);
   delete e;
 }
 
@@ -1098,13 +1224,18 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
                      {w->down_blob, w->down_hdr, nullptr}},
                     w->ln1,
                     w->ln2};
-  auto all = [&](auto pred) { return std::all_of(std::begin(in.p), std::end(in.p), pred); };
+  // no gate/up and down blobs: a sparse layer, whose experts woq_engine_set_layer_moe brings (their headers are not read)
+  const bool no_mlp = w->gate_up_blob == nullptr && w->down_blob == nullptr;
+  if (no_mlp) in.p[P_GATE_UP] = in.p[P_DOWN] = EngineProj{nullptr, {}, nullptr};
+  in.moe.pending = no_mlp;
+  auto all = [&](auto pred) { return std::all_of(std::begin(in.p), std::begin(in.p) + (no_mlp ? 2 : P_COUNT), pred); };
   const woq_blob_header qkv = in.p[P_QKV].hdr, o = in.p[P_O].hdr, gu = in.p[P_GATE_UP].hdr, down = in.p[P_DOWN].hdr;
   // round 6: fp8_e4m3 / fp8_e5m2 layers (all four projections of every layer the same type; one GPU)
   const bool fp8 = woq_weight_is_fp8(qkv.weight_type);
   if (fp8) {
     WOQ_CHECK(all([&](const EngineProj& p) { return p.hdr.weight_type == qkv.weight_type; }),
               "QBits: an fp8 layer needs all four projections in the same fp8 type");
+    WOQ_CHECK(!no_mlp, "QBits: fp8-weight engines do not take sparse mixture-of-experts layers");
     WOQ_CHECK(c.tp_size <= 1, "QBits: fp8-weight layers run on one GPU (no tensor-parallel decode path)");
     WOQ_CHECK(e->lora_rmax == 0, "QBits: fp8-weight layers do not take LoRA adapters (woq_engine_lora_reserve has run)");
   } else {
@@ -1120,9 +1251,11 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
             "QBits: layer weights must be WQH1 blobs");
   WOQ_CHECK(qkv.K == c.hidden && qkv.N == (c.heads + 2 * c.kv_heads) * c.head_dim, "QBits: qkv blob shape mismatch");
   WOQ_CHECK(o.K == c.heads * c.head_dim && o.N == c.hidden, "QBits: o_proj blob shape mismatch");
-  WOQ_CHECK(gu.K == c.hidden && gu.N == 2 * c.inter && (c.inter % 16) == 0,
+  WOQ_CHECK(no_mlp || (gu.K == c.hidden && gu.N == 2 * c.inter && (c.inter % 16) == 0),
             "QBits: gate_up blob shape mismatch (inter must be a multiple of 16)");
-  WOQ_CHECK(down.K == c.inter && down.N == c.hidden, "QBits: down_proj blob shape mismatch");
+  WOQ_CHECK(no_mlp || (down.K == c.inter && down.N == c.hidden), "QBits: down_proj blob shape mismatch");
+  WOQ_CHECK(!no_mlp || (c.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr),
+            "QBits: sparse mixture-of-experts layers run on one GPU (no tensor-parallel path)");
   // one kind per engine, whichever order the layers arrive in (the layer being replaced does not count)
   in.kind = fp8 ? LAYER_FP8 : LAYER_INT;
   for (int l = 0; l < c.layers; ++l) {
@@ -1150,6 +1283,7 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
     }
   }
   // every check has passed: commit
+  if (e->layers[layer].moe.on || no_mlp) engine_drop_graphs(e);  // (the step's launches change with the layer's kind)
   e->layers[layer] = in;
   e->fp8_type = fp8 ? qkv.weight_type : 0;  // (all set layers are of this kind)
   // xq_shapes_ok only ever goes from true to false: an engine whose fp8 (or XQ-refused) layer is later replaced by one
@@ -1157,7 +1291,67 @@ int woq_engine_set_layer(woq_engine* e, int layer, const woq_layer_weights* w) {
   if (fp8)
     e->xq_shapes_ok = false;  // fp8 layers run the fp32-activation step
   else
-    for (int k = 0; k < P_COUNT; ++k) e->xq_shapes_ok = e->xq_shapes_ok && gemv_xq_supported(in.p[k].hdr, kProjEpi[k]);
+    for (int k = 0; k < (no_mlp ? 2 : (int)P_COUNT); ++k)
+      e->xq_shapes_ok = e->xq_shapes_ok && gemv_xq_supported(in.p[k].hdr, kProjEpi[k]);
+  WOQ_END
+}
+
+int woq_engine_set_layer_moe(woq_engine* e, int layer, const woq_moe_layer_weights* w) {
+  WOQ_TRY
+  WOQ_CHECK(e && w && layer >= 0 && layer < e->cfg.layers, "QBits: bad layer index");
+  const woq_engine_config& c = e->cfg;
+  EngineLayer& L = e->layers[layer];
+  WOQ_CHECK(L.kind != LAYER_UNSET && (L.moe.pending || L.moe.on),
+            "QBits: woq_engine_set_layer_moe comes after woq_engine_set_layer for that layer, called without gate/up and "
+            "down blobs");
+  WOQ_CHECK(c.tp_size <= 1 && e->comm == nullptr && e->allreduce == nullptr,
+            "QBits: sparse mixture-of-experts layers run on one GPU (no tensor-parallel path)");
+  WOQ_CHECK(e->fp8_type == 0 && L.kind == LAYER_INT, "QBits: fp8-weight engines do not take sparse mixture-of-experts layers");
+  WOQ_CHECK(w->router_w && w->gate_up_blobs && w->down_blobs, "QBits: woq_engine_set_layer_moe: null tensor");
+  WOQ_CHECK(w->router_dtype == WOQ_F32 || w->router_dtype == WOQ_BF16 || w->router_dtype == WOQ_F16,
+            "QBits: woq_engine_set_layer_moe takes a router weight in fp32, bf16 or fp16");
+  WOQ_CHECK(w->experts >= 1 && w->experts <= 256, "QBits: woq_engine_set_layer_moe takes 1 to 256 experts");
+  WOQ_CHECK(w->top_k >= 1 && w->top_k <= std::min(w->experts, 16),
+            "QBits: woq_engine_set_layer_moe takes 1 <= top_k <= min(experts, 16)");
+  if (const char* p = moe_header_problem(w->gate_up_hdr, (size_t)w->gate_up_stride)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(w->down_hdr, (size_t)w->down_stride)) WOQ_FAIL(p);
+  const int I = w->moe_inter;
+  WOQ_CHECK(I > 0 && I % 16 == 0 && c.hidden % 16 == 0 && w->gate_up_hdr.K == c.hidden && w->gate_up_hdr.N == 2 * I &&
+                w->down_hdr.K == I && w->down_hdr.N == c.hidden,
+            "QBits: woq_engine_set_layer_moe: expert blobs must be [hidden -> 2 * moe_inter] and [moe_inter -> hidden], "
+            "moe_inter and hidden multiples of 16");
+  WOQ_CHECK((uintptr_t)w->router_w % 16 == 0 && (uintptr_t)w->gate_up_blobs % 16 == 0 && (uintptr_t)w->down_blobs % 16 == 0,
+            "QBits: woq_engine_set_layer_moe: router and blobs must be 16-byte aligned");
+  for (int k : {(int)P_GATE_UP, (int)P_DOWN})
+    WOQ_CHECK(e->lora_rows(layer, k) == 0,
+              "QBits: a sparse layer takes no LoRA adapter on gate_proj / up_proj / down_proj (q / k / v / o stay allowed)");
+  // the decode step's buffers, for the largest sparse layer (never inside a capture: the graphs are dropped below)
+  const size_t need = woq_moe_workspace(1, w->top_k, w->experts, c.hidden, I);
+  WOQ_CHECK(need > 0, "QBits: woq_engine_set_layer_moe: shape outside woq_moe_forward's limits");
+  if (e->moe_scratch == nullptr) {
+    WOQ_HIP(hipMalloc((void**)&e->moe_xn, (size_t)c.hidden * 4));
+    WOQ_HIP(hipMalloc((void**)&e->moe_idx, 16 * 4));
+    WOQ_HIP(hipMalloc((void**)&e->moe_w, 16 * 4));
+    WOQ_HIP(hipMalloc(&e->moe_scratch, woq_moe_route_scratch_bytes()));
+    WOQ_HIP(hipMemset(e->moe_scratch, 0, woq_moe_route_scratch_bytes()));
+    for (void* p : {(void*)e->moe_xn, (void*)e->moe_idx, (void*)e->moe_w, e->moe_scratch}) e->owned.push_back(p);
+  }
+  engine_drop_graphs(e);
+  if (need > e->moe_ws_bytes) {
+    WOQ_HIP(hipDeviceSynchronize());
+    if (e->moe_ws) WOQ_HIP(hipFree(e->moe_ws));
+    e->moe_ws = nullptr, e->moe_ws_bytes = 0;
+    WOQ_HIP(hipMalloc(&e->moe_ws, need));
+    e->moe_ws_bytes = need;
+  }
+  // every check has passed: commit
+  EngineMoe& m = L.moe;
+  m.on = true, m.pending = false;
+  m.router = w->router_w, m.router_dtype = w->router_dtype, m.E = w->experts, m.top_k = w->top_k, m.renorm = w->renorm;
+  m.inter = I;
+  m.gu_blobs = w->gate_up_blobs, m.down_blobs = w->down_blobs;
+  m.gu_stride = (size_t)w->gate_up_stride, m.down_stride = (size_t)w->down_stride;
+  m.gu_hdr = w->gate_up_hdr, m.down_hdr = w->down_hdr;
   WOQ_END
 }
 
@@ -1277,6 +1471,8 @@ int woq_engine_set_lora(woq_engine* e, int layer, int target, const float* a_dev
   WOQ_CHECK(r >= 0 && r <= e->lora_rmax, "QBits: the adapter's rank exceeds the r_max of woq_engine_lora_reserve");
   WOQ_CHECK(r == 0 || (a_dev != nullptr && b_dev != nullptr), "QBits: a LoRA target needs its A and B tables");
   const LoraTargetShape s = lora_target_shape(e->cfg, target);
+  WOQ_CHECK(r == 0 || !(e->layers[layer].moe.on || e->layers[layer].moe.pending) || (s.kind != P_GATE_UP && s.kind != P_DOWN),
+            "QBits: a sparse layer takes no LoRA adapter on gate_proj / up_proj / down_proj (q / k / v / o stay allowed)");
   const size_t di = (size_t)layer * P_COUNT + s.kind;
   const woq_engine::LoraTable& tb = e->lora_tab[(size_t)layer * LORA_TARGETS + target];
   const bool was = e->lora_rows(layer, s.kind) > 0;
@@ -1657,6 +1853,7 @@ int woq_engine_time_gemv_mask(woq_engine* e, int mask, int reps, void* stream, f
   WOQ_TRY
   WOQ_CHECK(e && total_ms && bytes_per_pass && launches_per_pass && (mask & 15) != 0, "QBits: bad argument");
   WOQ_CHECK_LAYERS(e);
+  WOQ_CHECK(!e->any_moe(), "QBits: the timing hooks walk dense layers only (this engine has a sparse layer)");
   hipStream_t st = (hipStream_t)stream;
   const woq_engine_config& c = e->cfg;
   double bytes = 0;
@@ -1728,6 +1925,7 @@ int woq_engine_time_twin(woq_engine* e, int mode, int reps, void* stream, float*
   WOQ_TRY
   WOQ_CHECK(e && total_ms && (mode == 0 || mode == 1), "QBits: bad argument");
   WOQ_CHECK_LAYERS(e);
+  WOQ_CHECK(!e->any_moe(), "QBits: the timing hooks walk dense layers only (this engine has a sparse layer)");
   hipStream_t st = (hipStream_t)stream;
   unsigned int* sink = (unsigned int*)e->am_idx;  // any device word; never written (the twins' store is unreachable)
   auto pass = [&](hipStream_t st) -> int {
@@ -1755,6 +1953,7 @@ int woq_engine_time_prefill_gemm(woq_engine* e, int layer, int n_rows, int reps,
   WOQ_CHECK(e && gemm_ms && call_ms && layer >= 0 && layer < e->cfg.layers && reps >= 1, "QBits: bad argument");
   WOQ_CHECK((size_t)n_rows <= e->pf_rows && n_rows > 8, "QBits: run a prompt pass of at least n_rows rows first");
   WOQ_CHECK_LAYERS(e);
+  WOQ_CHECK(!e->any_moe(), "QBits: the timing hooks walk dense layers only (this engine has a sparse layer)");
   hipStream_t st = (hipStream_t)stream;
   const woq_engine_config& c = e->cfg;
   hipEvent_t k0, k1, c0, c1;

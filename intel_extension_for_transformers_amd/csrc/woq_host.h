@@ -279,6 +279,11 @@ struct MoeCall {
   const void* down_blobs; const woq_blob_header* down_hdr; size_t down_stride;
   void* out; int out_dtype, ldo;
   void* workspace;
+  // the engine's two variations (both off in the public entry points, whose launches and bytes stay as they were):
+  // plan_ready: the plan tables already stand in `workspace` (woq_moe_route.hip's decode form wrote them), no plan launch;
+  // residual: the last launch is launch_moe_combine_residual onto these rows instead of launch_moe_combine into `out`
+  bool plan_ready = false;
+  const struct MoeResidual* residual = nullptr;
 };
 // null when the grouped launches take expert blobs under this header at this stride, else the "QBits: ..." reason
 const char* moe_header_problem(const woq_blob_header& h, size_t stride);
@@ -290,6 +295,11 @@ struct MoeBlock { int32_t expert, first, rows, pad; };
 // contributing zero, rounded once to out_dtype: the last launch of both forms
 void launch_moe_combine(const float* y, const int32_t* pos_of, const float* topk_w, int T, int top_k, int H, void* out,
                         int out_dtype, int ldo, hipStream_t st);
+// where the grouped form's plan tables lie in a workspace of woq_moe_workspace(T, top_k, E, ..) bytes
+struct MoeRoutePlan { int32_t* sorted; int32_t* pos_of; MoeBlock* blocks; int32_t* nblocks; };
+MoeRoutePlan moe_plan_tables(void* workspace, int T, int top_k, int E);
+// rows of the module's `prompt_min_tokens`: from this many rows the engine's prompt pass takes the prompt form
+constexpr int MOE_PROMPT_MIN_ROWS = 64;
 
 // ---- woq_moe_prompt.hip: the same block for many rows per expert, on the fp16 MFMA ---------------------------------
 constexpr int MOE_PROMPT_ROWS = 128;          // rows of one block of its table: the row tile of the product
@@ -297,6 +307,23 @@ constexpr int MOE_PROMPT_MAX_SLOTS = 65536;   // routed slots of one call: 64 pl
 // plan (count, scan, scatter), gate/up, down, combine: six launches shaped by (T, top_k, E, hidden, inter) alone;
 // `workspace` of woq_moe_prompt_workspace bytes
 int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st);
+
+// ---- woq_moe_route.hip: the router of a sparse layer -----------------------------------------------------------------
+// include/woq_hip_experimental.h woq_moe_route, which this is: checks (a "QBits:" message, nothing launched), then
+// one launch — the decode form for T == 1 (scratch: woq_moe_route_scratch_bytes, its ticket word zero), the MFMA
+// form otherwise. plan (T == 1, all four tables or none): the row's routing as woq_moe.hip's plan kernel would write it
+// from idx — sorted[top_k], pos_of[top_k], blocks[top_k] and their count — so that the grouped products can follow
+// without a plan launch
+int launch_moe_route(const float* x, int ldx, const float* norm_w, float eps, const void* router_w, int router_dtype,
+                     int T, int H, int E, int top_k, int renorm, float* xn, int32_t* idx, float* w, void* scratch,
+                     const MoeRoutePlan& plan, hipStream_t st);
+// The combine of a sparse layer inside the engine, onto the fp32 residual stream:
+//   hidden[t][n] += sum_j w[t][j] * y[pos_of[t k + j]][n], j ascending, a dropped slot contributing zero.
+// xo (one row only, H % 16 == 0): the new row also leaves as the next layer's XQ input, times next_norm_w, with the
+// per-block sums of squares of the raw values in ssq_out — what the dense layer's down_proj epilogue emits
+struct MoeResidual { float* hidden; int ldh; XqPtrs xo; const float* next_norm_w; float* ssq_out; };
+int launch_moe_combine_residual(const float* y, const int32_t* pos_of, const float* topk_w, int T, int top_k, int H,
+                                const MoeResidual& r, hipStream_t st);
 
 // ---- woq_logprob.hip: the log-probability record of a chaining step ----------------------------------------------
 // After the pick: row p = *pos - 1 of the three logs (pos null: row 0) <- log_softmax over the raw fp32 logits at

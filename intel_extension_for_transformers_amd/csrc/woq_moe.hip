@@ -447,7 +447,9 @@ int launch_moe_forward(const MoeCall& m, hipStream_t st) {
   float* ybuf = (float*)(ws + w.y);
   const int S = m.T * m.top_k;
 
-  if (m.idx_is_int64)
+  if (m.plan_ready)
+    ;  // (the router wrote the tables)
+  else if (m.idx_is_int64)
     hipLaunchKernelGGL(moe_plan_kernel<true>, dim3(1), dim3(MOE_PLAN_THREADS), 0, st, m.topk_idx, S, m.E, sorted, pos_of,
                        blocks, nblocks);
   else
@@ -467,9 +469,20 @@ int launch_moe_forward(const MoeCall& m, hipStream_t st) {
   moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks),
                          st);
 
-  launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
+  if (m.residual != nullptr) {
+    if (const int rc = launch_moe_combine_residual(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, *m.residual, st)) return rc;
+  } else {
+    launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
+  }
   WOQ_HIP(hipGetLastError());
   return 0;
+}
+
+MoeRoutePlan moe_plan_tables(void* workspace, int T, int top_k, int E) {
+  const MoeWorkspace w = moe_workspace(T, top_k, E, 0, 0);
+  uint8_t* ws = (uint8_t*)workspace;
+  return MoeRoutePlan{(int32_t*)(ws + w.sorted), (int32_t*)(ws + w.pos_of), (MoeBlock*)(ws + w.blocks),
+                      (int32_t*)(ws + w.nblocks)};
 }
 
 }  // namespace woq

@@ -507,7 +507,11 @@ int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st) {
   if (const int rc = moe_prompt_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, dim3(dx, (unsigned)w.max_blocks), st))
     return rc;
 
-  launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
+  if (m.residual != nullptr) {
+    if (const int rc = launch_moe_combine_residual(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, *m.residual, st)) return rc;
+  } else {
+    launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
+  }
   WOQ_HIP(hipGetLastError());
   return 0;
 }

@@ -476,6 +476,43 @@ def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_b
     return out
 
 
+def moe_route(x, router_w, top_k, renorm, norm_w=None, eps=0.0, plan=False):
+    """-> (xn [T, H] fp32, idx [T, top_k] int32, w [T, top_k] fp32): the router of a sparse layer in fp32
+    (woq_moe_route, csrc/woq_moe_route.hip). xn = x * rsqrt(mean(x^2) + eps) * norm_w (xn = x without norm_w), p =
+    softmax(xn @ router_w.T), the top_k largest p descending (equal p: the lower expert id first), w = p[idx], divided
+    by its own sum when `renorm`. x fp32 [T, H] with unit column stride; router_w [E, H] fp32 / bf16 / fp16. One launch:
+    T == 1 the decode form, more rows on the f32 MFMA; deterministic. A NaN probability ranks below every number.
+    `plan` (T == 1): also returns (sorted [k], pos_of [k], blocks [k, 4], nblocks [1]) int32, the row's plan tables in
+    csrc/woq_moe.hip's format."""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and router_w.dim() == 2
+            and router_w.device == x.device and router_w.dtype in _FAKE_QUANT_DTYPES):
+        raise RuntimeError("QBits: moe_route takes x fp32 [T, H] and router_w [E, H] fp32 / bf16 / fp16 on one HIP device")
+    t, h = x.shape
+    e_n = router_w.shape[0]
+    if router_w.shape[1] != h or (norm_w is not None and tuple(norm_w.shape) != (h,)):
+        raise RuntimeError("QBits: moe_route: router_w must be [E, H] and norm_w [H]")
+    if not _rows_ok(x, h):
+        x = x.contiguous()
+    router_w = router_w.contiguous()
+    if norm_w is not None:
+        norm_w = norm_w.to(device=x.device, dtype=torch.float32).contiguous()
+    xn = torch.empty(t, h, dtype=torch.float32, device=x.device)
+    idx = torch.empty(t, int(top_k), dtype=torch.int32, device=x.device)
+    w = torch.empty(t, int(top_k), dtype=torch.float32, device=x.device)
+    # the decode form's logits and ticket word: a scratch per call (the engine owns one for its steps)
+    scratch = torch.zeros(int(L.lib().woq_moe_route_scratch_bytes()), dtype=torch.uint8, device=x.device) if t == 1 else None
+    tables = [torch.empty(n, dtype=torch.int32, device=x.device) for n in (top_k, top_k, 4 * top_k, 1)] if plan else []
+    ldx = x.stride(0) if t > 1 else max(x.stride(0), h)
+    L.check(L.lib().woq_moe_route(_ptr(x), ldx, None if norm_w is None else _ptr(norm_w), float(eps),
+                                  _ptr(router_w), L.torch_dtype_code(router_w.dtype), t, h, e_n, int(top_k),
+                                  int(bool(renorm)), _ptr(xn), _ptr(idx), _ptr(w),
+                                  None if scratch is None else _ptr(scratch),
+                                  *([_ptr(v) for v in tables] or [None] * 4), L.stream_ptr()))
+    if plan:
+        return xn, idx, w, (tables[0], tables[1], tables[2].view(-1, 4), tables[3])
+    return xn, idx, w
+
+
 def _ascii(s):
     return torch.tensor([ord(c) for c in s], dtype=torch.int32)
 

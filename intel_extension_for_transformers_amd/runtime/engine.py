@@ -22,6 +22,8 @@ from .streaming import H2OConfig, StreamingConfig, plan_steps, plan_stream  # no
 
 
 ENGINE_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")  # the one list: engine_supports reads it, nothing else does
+# sparse mixture-of-experts decoders: engine_supports accepts them too; their sparse layers go through set_layer_moe
+ENGINE_MOE_MODEL_TYPES = ("mixtral", "qwen3_moe")
 ROPE_TYPES = ("default", "linear", "llama3", "yarn")  # build_rope_tables' parameterisations
 
 
@@ -128,9 +130,9 @@ def engine_supports(config):
     here. A refusal's reason names the config field that caused it. (What only the modules can tell — the weight types,
     a bias that the config does not announce — optimize_transformers checks on the model itself.)"""
     mt = getattr(config, "model_type", "")
-    if mt not in ENGINE_MODEL_TYPES:
+    if mt not in ENGINE_MODEL_TYPES + ENGINE_MOE_MODEL_TYPES:
         return False, "QBits: the fused decode engine covers Llama-class decoders (model_type %s), got %r" % (
-            " / ".join(ENGINE_MODEL_TYPES), mt)
+            " / ".join(ENGINE_MODEL_TYPES + ENGINE_MOE_MODEL_TYPES), mt)
     rtype, rs = rope_scaling_of(config)
     if rtype not in ROPE_TYPES:
         return False, "QBits: the fused decode engine implements plain RoPE only (rope scaling %r)" % rtype
@@ -221,8 +223,17 @@ class WoqDecoderEngine:
             pass
 
     def set_layer(self, idx, qkv_blob, o_blob, gate_up_blob, down_blob, ln1, ln2):
+        """`gate_up_blob` and `down_blob` both None: a sparse layer, whose MLP `set_layer_moe` brings next."""
         ln1 = ln1.to(self.device, torch.float32).contiguous()
         ln2 = ln2.to(self.device, torch.float32).contiguous()
+        if gate_up_blob is None and down_blob is None:
+            w = L.LayerWeights(qkv_blob=qkv_blob.data_ptr(), o_blob=o_blob.data_ptr(), ln1=ln1.data_ptr(),
+                               ln2=ln2.data_ptr(), qkv_hdr=qbits.header_of(qkv_blob), o_hdr=qbits.header_of(o_blob))
+            L.check(L.lib().woq_engine_set_layer(self._h, idx, ctypes.byref(w)))
+            self.captured = False
+            self._keep += [qkv_blob, o_blob, ln1, ln2]
+            self.layer_tensors[idx] = dict(qkv=qkv_blob, o=o_blob, ln1=ln1, ln2=ln2)
+            return
         w = L.LayerWeights(qkv_blob=qkv_blob.data_ptr(), o_blob=o_blob.data_ptr(),
                            gate_up_blob=gate_up_blob.data_ptr(), down_blob=down_blob.data_ptr(),
                            ln1=ln1.data_ptr(), ln2=ln2.data_ptr(), qkv_hdr=qbits.header_of(qkv_blob),
@@ -231,6 +242,30 @@ class WoqDecoderEngine:
         L.check(L.lib().woq_engine_set_layer(self._h, idx, ctypes.byref(w)))
         self._keep += [qkv_blob, o_blob, gate_up_blob, down_blob, ln1, ln2]
         self.layer_tensors[idx] = dict(qkv=qkv_blob, o=o_blob, gate_up=gate_up_blob, down=down_blob, ln1=ln1, ln2=ln2)
+
+    def set_layer_moe(self, idx, router_w, top_k, renorm, gate_up_blobs, down_blobs):
+        """The MLP of sparse layer `idx` (woq_engine_set_layer_moe; after `set_layer(idx, ..., None, None, ...)`):
+        `router_w` [E, hidden] in fp32 / bf16 / fp16 and the stacked expert blobs [E, stride] exactly as
+        `QuantizedMoEExpertsQBits` holds them. One GPU, int4 experts only; refusals carry a "QBits:" message."""
+        router_w = router_w.detach().to(self.device).contiguous()
+        if router_w.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            router_w = router_w.float()
+        gate_up_blobs, down_blobs = gate_up_blobs.to(self.device), down_blobs.to(self.device)
+        if gate_up_blobs.dim() != 2 or down_blobs.dim() != 2 or gate_up_blobs.shape[0] != router_w.shape[0] \
+                or down_blobs.shape[0] != router_w.shape[0] or not gate_up_blobs.is_contiguous() \
+                or not down_blobs.is_contiguous():
+            raise RuntimeError("QBits: set_layer_moe takes contiguous [E, stride] expert blobs, E = the router's rows")
+        gh, dh = qbits.header_of(gate_up_blobs[0]), qbits.header_of(down_blobs[0])
+        w = L.MoeLayerWeights(router_w=router_w.data_ptr(), router_dtype=L.torch_dtype_code(router_w.dtype),
+                              experts=int(router_w.shape[0]), top_k=int(top_k), renorm=int(bool(renorm)),
+                              moe_inter=int(dh.K), gate_up_blobs=gate_up_blobs.data_ptr(),
+                              down_blobs=down_blobs.data_ptr(), gate_up_stride=int(gate_up_blobs.shape[1]),
+                              down_stride=int(down_blobs.shape[1]), gate_up_hdr=gh, down_hdr=dh)
+        L.check(L.lib().woq_engine_set_layer_moe(self._h, int(idx), ctypes.byref(w)))
+        self.captured = False  # (the native side dropped its graphs)
+        self._keep += [router_w, gate_up_blobs, down_blobs]
+        self.layer_tensors.setdefault(idx, {}).update(router=router_w, expert_gate_up=gate_up_blobs,
+                                                      expert_down=down_blobs)
 
     def set_layer_extras(self, idx, qkv_bias=None, q_norm=None, k_norm=None):
         """Optional extras of layer `idx` (woq_engine_set_layer_extras; after set_layer): `qkv_bias`
@@ -1147,6 +1182,29 @@ def _same_order(parts, what):
     return idx[0]
 
 
+def _sparse_mlp(l, mlp):
+    """Is layers.l's `mlp` a sparse block the engine takes — a `QuantizedMoEExpertsQBits` under `.experts` and a Mixtral /
+    Qwen3-MoE top-k router with an [E, H] weight under `.gate`? False for a dense MLP; anything in between is refused."""
+    from ..transformers.llm.quantization.nn.moe import QuantizedMoEExpertsQBits
+
+    experts, gate = getattr(mlp, "experts", None), getattr(mlp, "gate", None)
+    if experts is None and gate is None and hasattr(mlp, "gate_proj"):
+        return False
+    where = "QBits: the fused decode engine: layers.%d.mlp " % l
+    if getattr(mlp, "shared_expert", None) is not None or getattr(mlp, "shared_experts", None) is not None:
+        raise RuntimeError(where + "has shared experts, which the sparse layer kind does not run")
+    if not isinstance(experts, QuantizedMoEExpertsQBits):
+        raise RuntimeError(where + "holds %s under .experts, not quantised expert blobs" % type(experts).__name__)
+    if not experts.grouped_supported():
+        raise RuntimeError(where + "has %s experts, which the grouped expert kernels do not take (int4 / int3 / int2 "
+                           "only; the model keeps the module path)" % experts.weight_dtype)
+    if type(gate).__name__ not in ("MixtralTopKRouter", "Qwen3MoeTopKRouter") or getattr(gate, "weight", None) is None \
+            or tuple(gate.weight.shape) != (experts.num_experts, experts.hidden_dim):
+        raise RuntimeError(where + "routes through %s, not a Mixtral / Qwen3-MoE top-k router with an [E, H] weight"
+                           % type(gate).__name__)
+    return True
+
+
 def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16, adapters=None):
     """Post-pass over a model returned by `AutoModelForCausalLM.from_pretrained(..., quantization_config=...)`:
     builds the native batch-1 decode engine over the SAME quantised weights (q/k/v fused along N, gate/up
@@ -1198,10 +1256,11 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16, adapters=
         return (getattr(m, "weight_dtype", "int4_clip"), getattr(m, "bits", 4), m.blocksize, m.scale_dtype, m.scheme,
                 getattr(m, "compute_dtype", "fp32"))
 
+    sparse = [_sparse_mlp(l, layer.mlp) for l, layer in enumerate(layers)]
     for l, layer in enumerate(layers):
         at, mlp = layer.self_attn, layer.mlp
-        for name, m in (("q_proj", at.q_proj), ("k_proj", at.k_proj), ("v_proj", at.v_proj), ("o_proj", at.o_proj),
-                        ("gate_proj", mlp.gate_proj), ("up_proj", mlp.up_proj), ("down_proj", mlp.down_proj)):
+        dense = () if sparse[l] else (("gate_proj", mlp.gate_proj), ("up_proj", mlp.up_proj), ("down_proj", mlp.down_proj))
+        for name, m in (("q_proj", at.q_proj), ("k_proj", at.k_proj), ("v_proj", at.v_proj), ("o_proj", at.o_proj)) + dense:
             if not hasattr(m, "blocksize") or _sig(m) != _sig(first):
                 raise RuntimeError("QBits: the fused decode engine needs one quantisation recipe for every projection; "
                                    "layers.%d.%s is %r, layers.0.q_proj is %r" %
@@ -1225,7 +1284,7 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16, adapters=
 
     for l, layer in enumerate(layers):
         at, mlp = layer.self_attn, layer.mlp
-        for m in (at.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
+        for m in (at.o_proj,) if sparse[l] else (at.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
             if m.bias is not None:
                 raise RuntimeError("QBits: the fused decode engine does not take biased projections")
         # q / k / v biases (Qwen2) ride in the fused projection's epilogue: all three, or the model keeps the module path
@@ -1240,11 +1299,17 @@ def optimize_transformers(model, max_ctx=2048, kv_dtype=torch.float16, adapters=
             raise RuntimeError("QBits: the fused decode engine takes q_norm and k_norm only together (layers.%d)" % l)
         qkv = pack(*cat([_signed_parts(at.q_proj), _signed_parts(at.k_proj), _signed_parts(at.v_proj)],
                         "layers.%d q_proj / k_proj / v_proj" % l))
-        g, u = _signed_parts(mlp.gate_proj), _signed_parts(mlp.up_proj)
-        gu = pack(fuse_gate_up(g[0], u[0]), fuse_gate_up(g[1], u[1]), fuse_gate_up(g[2], u[2]) if asym else None,
-                  _same_order([g, u], "layers.%d gate_proj / up_proj" % l))
-        eng.set_layer(l, qkv, at.o_proj.weight.data, gu, mlp.down_proj.weight.data, layer.input_layernorm.weight,
-                      layer.post_attention_layernorm.weight)
+        if sparse[l]:
+            eng.set_layer(l, qkv, at.o_proj.weight.data, None, None, layer.input_layernorm.weight,
+                          layer.post_attention_layernorm.weight)
+            eng.set_layer_moe(l, mlp.gate.weight.data, mlp.gate.top_k, getattr(mlp.gate, "norm_topk_prob", True),
+                              mlp.experts.gate_up_blobs, mlp.experts.down_blobs)
+        else:
+            g, u = _signed_parts(mlp.gate_proj), _signed_parts(mlp.up_proj)
+            gu = pack(fuse_gate_up(g[0], u[0]), fuse_gate_up(g[1], u[1]), fuse_gate_up(g[2], u[2]) if asym else None,
+                      _same_order([g, u], "layers.%d gate_proj / up_proj" % l))
+            eng.set_layer(l, qkv, at.o_proj.weight.data, gu, mlp.down_proj.weight.data, layer.input_layernorm.weight,
+                          layer.post_attention_layernorm.weight)
         if qkv_bias is not None or q_norm is not None:
             eng.set_layer_extras(l, qkv_bias=qkv_bias, q_norm=None if q_norm is None else q_norm.weight,
                                  k_norm=None if k_norm is None else k_norm.weight)

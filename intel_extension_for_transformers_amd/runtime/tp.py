@@ -82,6 +82,10 @@ def tp_supports(config):
     mt = getattr(config, "model_type", "")
     if mt == "qwen2" or getattr(config, "attention_bias", False):
         return False, "QBits: the tensor-parallel engine does not take q_proj / k_proj / v_proj biases (model_type %r)" % mt
+    from .engine import ENGINE_MOE_MODEL_TYPES
+
+    if mt in ENGINE_MOE_MODEL_TYPES:
+        return False, "QBits: the tensor-parallel engine does not take sparse mixture-of-experts layers (model_type %r)" % mt
     if mt == "qwen3":
         return False, "QBits: the tensor-parallel engine does not take a q_norm / k_norm (model_type %r)" % mt
     return True, ""
