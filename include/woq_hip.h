@@ -195,8 +195,10 @@ WOQ_API size_t woq_linear_backward_workspace(int M, const woq_blob_header* hdr);
  * int32, or int64 when idx_is_int64 (what torch.topk yields); topk_w [T, top_k] fp32. An id outside [0, E) drops its slot:
  * it contributes zero. The E gate/up blobs (K = hidden, N = 2 * inter, columns [0, inter) gate and [inter, 2 * inter)
  * up) lie gate_up_stride bytes apart from gate_up_blobs_dev and share the host header gate_up_hdr; the E down blobs
- * (K = inter, N = hidden) likewise. Weight types: int4 / int3 / int2, sym and asym, every group size and both scale
- * modes, no act-order; inter % 16 == 0 and hidden % 4 == 0; at most 1024 experts and 8192 routed slots (T * top_k) a
+ * (K = inter, N = hidden) likewise. Weight types, read from the header: int4 / int3 / int2 and int8 (the composite's two
+ * nibble planes in one launch, combined as 16 hi + lo in int32), sym and asym; nf4 / fp4_e2m1 / fp4_e2m1_bnb (sym; the
+ * decode GEMV's digit planes, whose count follows the header's compute type); every group size and both scale modes, no
+ * act-order, no fp8; inter % 16 == 0 and hidden % 4 == 0; at most 1024 experts and 8192 routed slots (T * top_k) a
  * call. Anything else fails with a "QBits:" message, launching nothing. Four launches (plan, gate/up, down, combine:
  * csrc/woq_moe.hip, DESIGN.md "Mixture-of-experts") whose shapes do not depend on the routing; stream-ordered, no host
  * synchronisation, no allocation, no floating-point atomics: the same inputs give the same bytes. Activations go
@@ -217,7 +219,8 @@ WOQ_API int woq_moe_forward(const void* x_dev, int x_dtype, int ldx, const void*
  * shapes do not depend on the routing. Numerics: one fp16 product per operand pair on v_mfma_f32_16x16x32_f16 with fp32
  * accumulation (the dense prompt GEMM's contract in its bf16 / fp16 / int8 compute modes); activation rows are scaled by
  * an exact power of two per row and 128-k tile, scale_mode-1 scales by one per column and tile, scale_mode-0 scales are
- * applied in fp32. Deterministic. woq_moe_prompt_workspace: the plan's tables, one count per (segment, expert) and the
+ * applied in fp32. The weight operand is the exact integer q - zp (int4; int8: 16 hi + lo - zp) or fp16(table[code]) for
+ * nf4 / fp4. Deterministic. woq_moe_prompt_workspace: the plan's tables, one count per (segment, expert) and the
  * fp32 rows [T * top_k][inter] and [T * top_k][hidden]; 0 for a shape outside the limits. */
 WOQ_API size_t woq_moe_prompt_workspace(int T, int top_k, int E, int hidden, int inter);
 WOQ_API int woq_moe_prompt_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,

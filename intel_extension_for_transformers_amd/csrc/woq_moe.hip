@@ -1,4 +1,4 @@
-// woq_moe.hip — the routed expert block of a sparse mixture-of-experts layer over int4 blobs:
+// woq_moe.hip — the routed expert block of a sparse mixture-of-experts layer over int4, nf4 / fp4 and int8 blobs:
 //   out[t] = sum_j topk_w[t][j] * down_e( SiLU(gate_e x_t) * up_e x_t ),  e = topk_idx[t][j],  j = 0 .. k-1 in that order
 // with E gate/up blobs (K = H, N = 2 I, columns [0, I) gate and [I, 2 I) up) and E down blobs (K = I, N = H), each kind
 // at one uniform byte stride and under one header. The definition is HF's MixtralExperts / Qwen3MoeExperts forward (a
@@ -94,8 +94,9 @@ __global__ __launch_bounds__(MOE_PLAN_THREADS) void moe_plan_kernel(const void* 
 // ---- 2 / 3. the grouped product --------------------------------------------------------------------------------------
 struct MoeGemmArgs {
   const uint8_t* blobs;  // expert e's blob at blobs + e * stride
-  size_t stride, off_q, off_scale, off_zp;
+  size_t stride, off_q[2], off_scale, off_zp[2];  // [plane]: woq_host.h MoePlanes
   int K, N, tiles_k, n_groups, group, scale_type;
+  LutArgs lut;  // table kinds: the digit planes and wmul of lut_args_for, as the decode GEMV takes them
   const void* x;  // gate/up: activations [T, ldx] of x_dtype; down: fp32 rows [sorted slot][ldx]
   int x_dtype, ldx, top_k;
   const int32_t* sorted;
@@ -111,11 +112,28 @@ __device__ __forceinline__ float moe_scale(const void* s, size_t i, int st) {
   return st == WOQ_BF16 ? bf16_bits_to_f32(b) : f16_bits_to_f32(b);
 }
 
+constexpr int MOE_WK_INT8 = 4;
+
 // GU: the gate/up launch (two column tiles, SiLU * mul epilogue, rows gathered by token) | the down launch
-template <bool GU, int SMODE, bool ASYM>
+// WK, the weight kind: 0 = int4 | 1, 2, 3 = a table type (nf4 / fp4) as that many digit planes | MOE_WK_INT8 = the int8
+// composite. Only the B operand differs:
+//   table  the nibbles are codes: lut_b turns a 64-k half into NDIG int8 digit operands, one MFMA per plane against the
+//          same A operand, f = f0 + 2^8 f1 + 2^16 f2 after limb_combine, LutArgs::wmul folded into the scale. The digit
+//          operands do not depend on the row set, so here the tile loop is the OUTER one: they are built once per tile,
+//          column tile and half, just before the MFMAs of all live row sets, and only the weight words stay resident.
+//   int8   both planes' words of a tile are requested together; both meet the same A registers and the two int32
+//          fragments are added as 16 hi + lo BEFORE limb_combine (exact: a limb sum is below 2^21, 17 of them below
+//          2^26), so a tile costs the fp32 roundings of an int4 tile. The zero points 16 zhi + zlo enter through the ones
+//          row as one integer: the LO plane always carries one, the HI plane only under ASYM.
+template <bool GU, int SMODE, bool ASYM, int WK>
 __global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmArgs a) {
   constexpr int CB = GU ? 2 : 1;
   constexpr int NS = SMODE == 1 ? 4 : 1;  // scales of a tile and column
+  constexpr int NDIG = WK >= 1 && WK <= 3 ? WK : 0;
+  constexpr bool I8 = WK == MOE_WK_INT8;
+  constexpr int NP = I8 ? 2 : 1;         // nibble planes
+  constexpr bool ZP = ASYM || I8;        // a zero-point term through the ones row
+  static_assert(!(NDIG > 0 && ASYM), "the table types are symmetric");
   __shared__ __attribute__((aligned(16))) unsigned char strip[MOE_BLOCK_ROWS * 3 * MOE_RB];  // [row][limb][MOE_RB]
   __shared__ __attribute__((aligned(16))) unsigned char zero_blk[64], ones_blk[64];
   __shared__ float unsc_s[MOE_BLOCK_ROWS];  // per row: 2^(e - 25) of the staged chunk
@@ -137,9 +155,11 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmA
   }
 
   const uint8_t* blob = a.blobs + (size_t)expert * a.stride;
-  const u32x4* q = (const u32x4*)(blob + a.off_q);
+  const u32x4* q[NP];
+  const uint8_t* zps[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) q[p] = (const u32x4*)(blob + a.off_q[p]), zps[p] = blob + a.off_zp[p];
   const void* scales = blob + a.off_scale;
-  const uint8_t* zps = blob + a.off_zp;
   int tn[CB];
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb) tn[cb] = (int)blockIdx.x + cb * a.half_tiles;
@@ -157,31 +177,37 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmA
 #pragma unroll 1
   for (int c = 0; c < nchunks; ++c) {
     // ---- this wave's tiles of the chunk: weight words, scales, zero points — requested before the staging ----
-    u32x4 w[MOE_TPW][CB];
+    u32x4 w[MOE_TPW][CB][NP];
     float sc[MOE_TPW][CB][NS];
-    int uz[MOE_TPW][CB][NS];
+    int uz[MOE_TPW][CB][NS];  // zero point + 8; int8: 16 zhi + zlo + 8, the composite's zero point in LO-plane units
+    auto load_qparams = [&](int ti, int cb, int s, size_t si) {
+      sc[ti][cb][s] = moe_scale(scales, si, a.scale_type);
+      if constexpr (NDIG > 0) sc[ti][cb][s] *= a.lut.wmul;
+      if constexpr (I8)
+        uz[ti][cb][s] = 16 * ((ASYM ? (int)zps[0][si] : 8) - 8) + (int)zps[1][si];
+      else if constexpr (ASYM)
+        uz[ti][cb][s] = (int)zps[0][si];
+    };
 #pragma unroll
     for (int ti = 0; ti < MOE_TPW; ++ti) {
       const int kt = c * MOE_TPC + wid + ti * MOE_WAVES;
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
-        w[ti][cb] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int p = 0; p < NP; ++p) w[ti][cb][p] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
         for (int s = 0; s < NS; ++s) sc[ti][cb][s] = 0.f, uz[ti][cb][s] = 8;
         if (kt >= a.tiles_k) continue;
-        w[ti][cb] = __builtin_nontemporal_load(q + ((size_t)tn[cb] * a.tiles_k + kt) * 64 + lane);
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+          w[ti][cb][p] = __builtin_nontemporal_load(q[p] + ((size_t)tn[cb] * a.tiles_k + kt) * 64 + lane);
         if constexpr (SMODE == 0) {
           const int grp = a.n_groups == 1 ? 0 : min(kt * 128 / a.group, a.n_groups - 1);
-          const size_t si = ((size_t)tn[cb] * a.n_groups + grp) * 16 + i16;
-          sc[ti][cb][0] = moe_scale(scales, si, a.scale_type);
-          if constexpr (ASYM) uz[ti][cb][0] = (int)zps[si];
+          load_qparams(ti, cb, 0, ((size_t)tn[cb] * a.n_groups + grp) * 16 + i16);
         } else {
           const size_t si = (((size_t)tn[cb] * a.tiles_k + kt) * 16 + i16) * 4;
 #pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            sc[ti][cb][s] = moe_scale(scales, si + s, a.scale_type);
-            if constexpr (ASYM) uz[ti][cb][s] = (int)zps[si + s];
-          }
+          for (int s = 0; s < 4; ++s) load_qparams(ti, cb, s, si + s);
         }
       }
     }
@@ -252,77 +278,154 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmA
 
     // ---- inner products: MFMA row r = lane & 15 -> activation row (r >> 2) of the set, part r & 3 (limb 0..2 | ones);
     // D: lane quarter kq holds activation row kq of the set for column lane & 15 ----
-#pragma unroll
-    for (int rs = 0; rs < 4; ++rs) {  // unrolled: acc[rs] stays in registers
-      if (rs >= nrs) break;
+    // this lane's A operand of row set rs: tile tt's first half at a_base + tt * st_t, its second st_h further
+    auto a_operand = [&](int rs, const unsigned char*& a_base, int& st_t, int& st_h) {
       const int row_a = 4 * rs + a_m;
       const bool a_live = row_a < R;
       const bool a_data = a_live && a_part != 3;
-      const unsigned char* a_base =
-          !a_live ? zero_blk + kq * 16
-                  : (a_part == 3 ? ones_blk + kq * 16 : strip + (size_t)(3 * row_a + a_part) * MOE_RB + kq * 16);
-      const int st_t = a_data ? 128 : 0, st_h = a_data ? 64 : 0;
-      const float un = unsc_s[4 * rs + kq];
+      a_base = !a_live ? zero_blk + kq * 16
+                       : (a_part == 3 ? ones_blk + kq * 16 : strip + (size_t)(3 * row_a + a_part) * MOE_RB + kq * 16);
+      st_t = a_data ? 128 : 0, st_h = a_data ? 64 : 0;
+    };
+    // f0 + 2^8 f1 + 2^16 f2 of one A operand against the digit operands, most significant plane first
+    auto digit_dot = [&](const i32x4& av, const i32x4 (&bd)[NDIG > 0 ? NDIG : 1], i32x4 (&d)[NDIG > 0 ? NDIG : 1],
+                         bool add) {
+#pragma unroll
+      for (int j = 0; j < NDIG; ++j) d[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bd[j], add ? d[j] : izero, 0, 0, 0);
+    };
+    auto digit_sum = [&](const i32x4 (&d)[NDIG > 0 ? NDIG : 1]) {
+      float f = limb_combine(d[NDIG > 0 ? NDIG - 1 : 0]);
+#pragma unroll
+      for (int j = NDIG - 2; j >= 0; --j) f = fmaf(f, 256.f, limb_combine(d[j]));
+      return f;
+    };
+    if constexpr (NDIG > 0) {
 #pragma unroll
       for (int ti = 0; ti < MOE_TPW; ++ti) {
         const int tt = wid + ti * MOE_WAVES;  // tile of the chunk
         if (c * MOE_TPC + tt >= a.tiles_k) continue;
-        if constexpr (SMODE == 0) {
-          const i32x4 a0 = *(const i32x4*)(a_base + tt * st_t);
-          const i32x4 a1 = *(const i32x4*)(a_base + tt * st_t + st_h);
-          float sx = 0.f;  // sum_k x~_k of this tile (asym only), in fixed-point units
-          if constexpr (ASYM) {
-            i32x4 ds = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b_ones, izero, 0, 0, 0);
-            ds = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b_ones, ds, 0, 0, 0);
-            sx = limb_combine(ds);
-          }
 #pragma unroll
-          for (int cb = 0; cb < CB; ++cb) {
-            const u32x4 wv = w[ti][cb];
-            i32x4 b0, b1;
-            int4_b(wv.x, wv.y, b0);
-            int4_b(wv.z, wv.w, b1);
-            i32x4 d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0, izero, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1, d, 0, 0, 0);
-            float f = limb_combine(d);
-            // b_ones carries 1 where the weights carry 16 * q: the zero point enters as 16 * zp
-            if constexpr (ASYM) f = fmaf(-16.f * (float)(uz[ti][cb][0] - 8), sx, f);
-            acc[rs][cb] = fmaf(sc[ti][cb][0] * un, f, acc[rs][cb]);
-          }
-        } else {
-          // the two 32-k halves of a 64-k MFMA belong to different groups: lanes kq < 2 feed the first, kq >= 2 the second
-          const unsigned char* a_lo = kq < 2 ? a_base : zero_blk;
-          const unsigned char* a_hi = kq < 2 ? zero_blk : a_base;
-          const int lo_t = kq < 2 ? st_t : 0, lo_h = kq < 2 ? st_h : 0;
-          const int hi_t = kq < 2 ? 0 : st_t, hi_h = kq < 2 ? 0 : st_h;
-          i32x4 al[2], ah[2];
+        for (int cb = 0; cb < CB; ++cb) {
+          const u32x4 wv = w[ti][cb][0];
+          if constexpr (SMODE == 0) {
+            i32x4 b0[NDIG], b1[NDIG];
+            lut_b<NDIG>(a.lut, wv.x, wv.y, b0);
+            lut_b<NDIG>(a.lut, wv.z, wv.w, b1);
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            al[h] = *(const i32x4*)(a_lo + tt * lo_t + h * lo_h);
-            ah[h] = *(const i32x4*)(a_hi + tt * hi_t + h * hi_h);
-          }
-          float sx[4] = {0.f, 0.f, 0.f, 0.f};
-          if constexpr (ASYM) {
+            for (int rs = 0; rs < 4; ++rs) {
+              if (rs >= nrs) break;
+              const unsigned char* a_base;
+              int st_t, st_h;
+              a_operand(rs, a_base, st_t, st_h);
+              i32x4 d[NDIG];
+              digit_dot(*(const i32x4*)(a_base + tt * st_t), b0, d, false);
+              digit_dot(*(const i32x4*)(a_base + tt * st_t + st_h), b1, d, true);
+              acc[rs][cb] = fmaf(sc[ti][cb][0] * unsc_s[4 * rs + kq], digit_sum(d), acc[rs][cb]);
+            }
+          } else {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-              sx[2 * h] = limb_combine(__builtin_amdgcn_mfma_i32_16x16x64_i8(al[h], b_ones, izero, 0, 0, 0));
-              sx[2 * h + 1] = limb_combine(__builtin_amdgcn_mfma_i32_16x16x64_i8(ah[h], b_ones, izero, 0, 0, 0));
+              i32x4 bq[NDIG];
+              lut_b<NDIG>(a.lut, h == 0 ? wv.x : wv.z, h == 0 ? wv.y : wv.w, bq);
+#pragma unroll
+              for (int rs = 0; rs < 4; ++rs) {
+                if (rs >= nrs) break;
+                const unsigned char* a_base;
+                int st_t, st_h;
+                a_operand(rs, a_base, st_t, st_h);
+                const float un = unsc_s[4 * rs + kq];
+#pragma unroll
+                for (int g2 = 0; g2 < 2; ++g2) {  // lanes kq < 2 feed the half's first 32-k block, kq >= 2 its second
+                  const bool mine = (kq < 2) == (g2 == 0);
+                  const unsigned char* ap = mine ? a_base + tt * st_t + h * st_h : zero_blk;
+                  i32x4 d[NDIG];
+                  digit_dot(*(const i32x4*)ap, bq, d, false);
+                  acc[rs][cb] = fmaf(sc[ti][cb][2 * h + g2] * un, digit_sum(d), acc[rs][cb]);
+                }
+              }
             }
           }
+        }
+      }
+    } else {
 #pragma unroll
-          for (int cb = 0; cb < CB; ++cb) {
-            const u32x4 wv = w[ti][cb];
+      for (int rs = 0; rs < 4; ++rs) {  // unrolled: acc[rs] stays in registers
+        if (rs >= nrs) break;
+        const unsigned char* a_base;
+        int st_t, st_h;
+        a_operand(rs, a_base, st_t, st_h);
+        const float un = unsc_s[4 * rs + kq];
+#pragma unroll
+        for (int ti = 0; ti < MOE_TPW; ++ti) {
+          const int tt = wid + ti * MOE_WAVES;  // tile of the chunk
+          if (c * MOE_TPC + tt >= a.tiles_k) continue;
+          if constexpr (SMODE == 0) {
+            const i32x4 a0 = *(const i32x4*)(a_base + tt * st_t);
+            const i32x4 a1 = *(const i32x4*)(a_base + tt * st_t + st_h);
+            float sx = 0.f;  // sum_k x~_k of this tile (zero points only), in fixed-point units
+            if constexpr (ZP) {
+              i32x4 ds = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b_ones, izero, 0, 0, 0);
+              ds = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b_ones, ds, 0, 0, 0);
+              sx = limb_combine(ds);
+            }
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+              i32x4 d[NP];
+#pragma unroll
+              for (int p = 0; p < NP; ++p) {
+                const u32x4 wv = w[ti][cb][p];
+                i32x4 b0, b1;
+                int4_b(wv.x, wv.y, b0);
+                int4_b(wv.z, wv.w, b1);
+                d[p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0, izero, 0, 0, 0);
+                d[p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1, d[p], 0, 0, 0);
+              }
+              if constexpr (I8) d[0] = d[0] * 16 + d[1];  // 16 hi + lo
+              float f = limb_combine(d[0]);
+              // b_ones carries 1 where the weights carry 16 * q: the zero point enters as 16 * zp
+              if constexpr (ZP) f = fmaf(-16.f * (float)(uz[ti][cb][0] - 8), sx, f);
+              acc[rs][cb] = fmaf(sc[ti][cb][0] * un, f, acc[rs][cb]);
+            }
+          } else {
+            // the two 32-k halves of a 64-k MFMA belong to different groups: lanes kq < 2 feed the first, kq >= 2 the second
+            const unsigned char* a_lo = kq < 2 ? a_base : zero_blk;
+            const unsigned char* a_hi = kq < 2 ? zero_blk : a_base;
+            const int lo_t = kq < 2 ? st_t : 0, lo_h = kq < 2 ? st_h : 0;
+            const int hi_t = kq < 2 ? 0 : st_t, hi_h = kq < 2 ? 0 : st_h;
+            i32x4 al[2], ah[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-              i32x4 bq;
-              int4_b(h == 0 ? wv.x : wv.z, h == 0 ? wv.y : wv.w, bq);
+              al[h] = *(const i32x4*)(a_lo + tt * lo_t + h * lo_h);
+              ah[h] = *(const i32x4*)(a_hi + tt * hi_t + h * hi_h);
+            }
+            float sx[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (ZP) {
 #pragma unroll
-              for (int g2 = 0; g2 < 2; ++g2) {
-                const int s = 2 * h + g2;  // 32-k block of the tile
-                float f = limb_combine(
-                    __builtin_amdgcn_mfma_i32_16x16x64_i8(g2 == 0 ? al[h] : ah[h], bq, izero, 0, 0, 0));
-                if constexpr (ASYM) f = fmaf(-16.f * (float)(uz[ti][cb][s] - 8), sx[s], f);
-                acc[rs][cb] = fmaf(sc[ti][cb][s] * un, f, acc[rs][cb]);
+              for (int h = 0; h < 2; ++h) {
+                sx[2 * h] = limb_combine(__builtin_amdgcn_mfma_i32_16x16x64_i8(al[h], b_ones, izero, 0, 0, 0));
+                sx[2 * h + 1] = limb_combine(__builtin_amdgcn_mfma_i32_16x16x64_i8(ah[h], b_ones, izero, 0, 0, 0));
+              }
+            }
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                i32x4 bq[NP];
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                  const u32x4 wv = w[ti][cb][p];
+                  int4_b(h == 0 ? wv.x : wv.z, h == 0 ? wv.y : wv.w, bq[p]);
+                }
+#pragma unroll
+                for (int g2 = 0; g2 < 2; ++g2) {
+                  const int s = 2 * h + g2;  // 32-k block of the tile
+                  i32x4 d = __builtin_amdgcn_mfma_i32_16x16x64_i8(g2 == 0 ? al[h] : ah[h], bq[0], izero, 0, 0, 0);
+                  if constexpr (I8)  // 16 hi + lo
+                    d = d * 16 + __builtin_amdgcn_mfma_i32_16x16x64_i8(g2 == 0 ? al[h] : ah[h], bq[1], izero, 0, 0, 0);
+                  float f = limb_combine(d);
+                  if constexpr (ZP) f = fmaf(-16.f * (float)(uz[ti][cb][s] - 8), sx[s], f);
+                  acc[rs][cb] = fmaf(sc[ti][cb][s] * un, f, acc[rs][cb]);
+                }
               }
             }
           }
@@ -392,39 +495,80 @@ bool moe_shape_ok(int T, int top_k, int E, int hidden, int inter) {
          (long long)T * top_k <= MOE_MAX_SLOTS;
 }
 
-template <bool GU>
-int moe_launch_gemm(const MoeGemmArgs& a, bool smode1, bool asym, dim3 grid, hipStream_t st) {
+template <bool GU, int SMODE, bool ASYM>
+void moe_launch_kind(const MoeGemmArgs& a, int wk, dim3 grid, hipStream_t st) {
   const dim3 block(MOE_WAVES * 64);
-  if (!smode1 && !asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 0, false>), grid, block, 0, st, a);
-  if (!smode1 && asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 0, true>), grid, block, 0, st, a);
-  if (smode1 && !asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 1, false>), grid, block, 0, st, a);
-  if (smode1 && asym) hipLaunchKernelGGL((moe_gemm_kernel<GU, 1, true>), grid, block, 0, st, a);
+  if (wk == 0) hipLaunchKernelGGL((moe_gemm_kernel<GU, SMODE, ASYM, 0>), grid, block, 0, st, a);
+  if (wk == MOE_WK_INT8) hipLaunchKernelGGL((moe_gemm_kernel<GU, SMODE, ASYM, MOE_WK_INT8>), grid, block, 0, st, a);
+  if constexpr (!ASYM) {  // moe_header_problem admits no table blob with zero points
+    if (wk == 1) hipLaunchKernelGGL((moe_gemm_kernel<GU, SMODE, false, 1>), grid, block, 0, st, a);
+    if (wk == 2) hipLaunchKernelGGL((moe_gemm_kernel<GU, SMODE, false, 2>), grid, block, 0, st, a);
+    if (wk == 3) hipLaunchKernelGGL((moe_gemm_kernel<GU, SMODE, false, 3>), grid, block, 0, st, a);
+  }
+}
+
+// `wk`: the kernel's weight kind, from moe_gemm_args
+template <bool GU>
+int moe_launch_gemm(const MoeGemmArgs& a, bool smode1, bool asym, int wk, dim3 grid, hipStream_t st) {
+  if (!smode1 && !asym) moe_launch_kind<GU, 0, false>(a, wk, grid, st);
+  if (!smode1 && asym) moe_launch_kind<GU, 0, true>(a, wk, grid, st);
+  if (smode1 && !asym) moe_launch_kind<GU, 1, false>(a, wk, grid, st);
+  if (smode1 && asym) moe_launch_kind<GU, 1, true>(a, wk, grid, st);
   return 0;
 }
 
-MoeGemmArgs moe_gemm_args(const void* blobs, const woq_blob_header& h, size_t stride) {
+MoeGemmArgs moe_gemm_args(const void* blobs, const woq_blob_header& h, size_t stride, int& wk) {
   MoeGemmArgs a = {};
   a.blobs = (const uint8_t*)blobs, a.stride = stride;
-  a.off_q = h.off_q, a.off_scale = h.off_scale, a.off_zp = h.off_zp;
+  const MoePlanes p = moe_blob_planes(h);
+  for (int i = 0; i < 2; ++i) a.off_q[i] = p.off_q[i], a.off_zp[i] = p.off_zp[i];
+  a.off_scale = p.off_scale;
   a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.n_groups = h.n_groups, a.group = h.group;
   a.scale_type = (int)h.scale_type;
+  const int ndig = lut_args_for(h.weight_type, h.compute_type, a.lut);  // 0, and an empty table, for the integer kinds
+  wk = p.kind == MOE_W_TABLE ? ndig : (p.kind == MOE_W_INT8 ? MOE_WK_INT8 : 0);
   return a;
 }
 
 }  // namespace
 
-const char* moe_header_problem(const woq_blob_header& h, size_t stride) {
+const char* moe_header_problem(const woq_blob_header& h, size_t stride, bool int4_only) {
   if (h.magic != WOQ_BLOB_MAGIC) return "QBits: woq_moe_forward: not a WQH1 packed weight";
-  if (h.weight_type != WOQ_W_INT4_CLIP)
+  const bool table = woq_weight_is_table(h.weight_type);
+  // fp8 blobs are code bytes for the fp8 MFMA, another kernel
+  if (h.weight_type != WOQ_W_INT4_CLIP && (int4_only || (h.weight_type != WOQ_W_INT8 && !table)))
     return "QBits: woq_moe_forward takes int4 / int3 / int2 expert blobs; other weight types run the per-expert loop";
   if (h.off_shuffle != 0) return "QBits: woq_moe_forward: act-order expert blobs are not built";
   if (h.K <= 0 || h.N <= 0 || h.Kpad % WOQ_TILE_K != 0 || h.Npad % WOQ_TILE_N != 0 || h.n_groups <= 0 || h.group <= 0 ||
       h.scale_mode > 1u || h.scale_type > (uint32_t)WOQ_F16)
     return "QBits: woq_moe_forward: corrupt blob header";
   if (h.scale_mode == 0 && h.n_groups > 1 && h.group % WOQ_TILE_K != 0) return "QBits: woq_moe_forward: corrupt blob header";
+  if (table && h.off_zp != 0) return "QBits: woq_moe_forward: corrupt blob header";  // the table types are symmetric
+  if (h.weight_type == WOQ_W_INT8) {  // the composite's sections must lie where woq_int8_headers puts them
+    woq_blob_header o, hi, lo;
+    if (woq_int8_headers(&o, &hi, &lo, h.K, h.N, h.group, h.scale_type, h.compute_type, h.off_zp != 0, 0) != 0 ||
+        o.off_q != h.off_q || o.off_scale != h.off_scale || o.off_zp != h.off_zp || o.total_bytes != h.total_bytes)
+      return "QBits: woq_moe_forward: corrupt blob header";
+  }
   if (stride < h.total_bytes || stride % 16 != 0)
     return "QBits: woq_moe_forward: the expert stride is smaller than a blob or no multiple of 16";
   return nullptr;
+}
+
+MoePlanes moe_blob_planes(const woq_blob_header& h) {
+  MoePlanes p = {};
+  if (h.weight_type == WOQ_W_INT8) {
+    woq_blob_header o, hi, lo;
+    woq_int8_headers(&o, &hi, &lo, h.K, h.N, h.group, h.scale_type, h.compute_type, h.off_zp != 0, 0);
+    p.kind = MOE_W_INT8;
+    p.off_q[0] = h.off_q + hi.off_q, p.off_q[1] = h.off_scale + lo.off_q;
+    p.off_scale = h.off_scale + lo.off_scale;
+    p.off_zp[0] = hi.off_zp ? h.off_q + hi.off_zp : 0, p.off_zp[1] = h.off_scale + lo.off_zp;
+    return p;
+  }
+  p.kind = woq_weight_is_table(h.weight_type) ? MOE_W_TABLE : MOE_W_INT4;
+  p.off_q[0] = h.off_q, p.off_scale = h.off_scale, p.off_zp[0] = h.off_zp;
+  return p;
 }
 
 void launch_moe_combine(const float* y, const int32_t* pos_of, const float* topk_w, int T, int top_k, int H, void* out,
@@ -456,18 +600,19 @@ int launch_moe_forward(const MoeCall& m, hipStream_t st) {
     hipLaunchKernelGGL(moe_plan_kernel<false>, dim3(1), dim3(MOE_PLAN_THREADS), 0, st, m.topk_idx, S, m.E, sorted,
                        pos_of, blocks, nblocks);
 
-  MoeGemmArgs g = moe_gemm_args(m.gate_up_blobs, gh, m.gate_up_stride);
+  int g_wk, d_wk;
+  MoeGemmArgs g = moe_gemm_args(m.gate_up_blobs, gh, m.gate_up_stride, g_wk);
   g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
   g.sorted = sorted, g.blocks = blocks, g.nblocks = nblocks;
   g.out = hbuf, g.ldo = I, g.half_tiles = I / 16;
-  moe_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, dim3((unsigned)(I / 16), (unsigned)w.max_blocks), st);
+  moe_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, g_wk, dim3((unsigned)(I / 16), (unsigned)w.max_blocks), st);
 
-  MoeGemmArgs d = moe_gemm_args(m.down_blobs, dh, m.down_stride);
+  MoeGemmArgs d = moe_gemm_args(m.down_blobs, dh, m.down_stride, d_wk);
   d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
   d.sorted = sorted, d.blocks = blocks, d.nblocks = nblocks;
   d.out = ybuf, d.ldo = H, d.half_tiles = 0;
-  moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks),
-                         st);
+  moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, d_wk,
+                         dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks), st);
 
   if (m.residual != nullptr) {
     if (const int rc = launch_moe_combine_residual(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, *m.residual, st)) return rc;
@@ -500,8 +645,8 @@ extern "C" int woq_moe_forward(const void* x_dev, int x_dtype, int ldx, const vo
   WOQ_TRY
   using namespace woq;
   WOQ_CHECK(gate_up_hdr && down_hdr, "QBits: woq_moe_forward: null header");
-  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride)) WOQ_FAIL(p);
-  if (const char* p = moe_header_problem(*down_hdr, down_stride)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride, false)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(*down_hdr, down_stride, false)) WOQ_FAIL(p);
   const int H = down_hdr->N, I = down_hdr->K;
   WOQ_CHECK(gate_up_hdr->K == H && gate_up_hdr->N == 2 * I,
             "QBits: woq_moe_forward: gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");

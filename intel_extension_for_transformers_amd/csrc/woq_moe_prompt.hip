@@ -27,11 +27,14 @@
 //     fp32; scale_mode 1 (four 32-k scales a tile) multiplies by the scale relative to 2^E > the tile's largest scale of
 //     that column (an exact power of two, so a scale of 5e-6 or a bf16 scale outside fp16's range stays normal).
 //       A tile's products are accumulated in fresh fp32 fragments and folded into the running fp32 accumulators with
-//     2^(e - 15)[row] * (scale | 2^E)[column]. One fp16 product per operand pair, fp32 accumulation: the contract of the
+//     2^(e - 15)[row] * (scale | 2^E)[column]. The table types (nf4 / fp4) and the int8 composite differ in this step
+//     alone: moe_prompt_lut8 selects fp16(table[code]) per nibble, the int8 operand is 16 (hi - zhi) + (lo - zlo) of the
+//     two planes' words (exact in fp16); scales as for int4. One fp16 product per operand pair, fp32 accumulation: the contract of the
 //     dense prompt GEMM's bf16 / fp16 / int8 compute modes. Row tiles past the block's rows are skipped wave-uniformly.
 //  4. combine: woq_moe.hip's launch_moe_combine.
 // No split-K, no floating-point atomics, a fixed summation order: the same inputs give the same bytes.
 #include <math.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -133,8 +136,9 @@ __global__ __launch_bounds__(MP_SEG) void moe_prompt_scatter_kernel(const void* 
 // ---- 2 / 3. the grouped product --------------------------------------------------------------------------------------
 struct MoePromptArgs {
   const uint8_t* blobs;  // expert e's blob at blobs + e * stride
-  size_t stride, off_q, off_scale, off_zp;
+  size_t stride, off_q[2], off_scale, off_zp[2];  // [plane]: woq_host.h MoePlanes
   int K, N, tiles_k, tiles_n, n_groups, group, scale_type;
+  LutArgs lut;  // table kinds: the 16 table values as fp16, d[0] their low bytes and d[1] their high bytes (moe_prompt_lut)
   const void* x;  // gate/up: activations [T, ldx] of x_dtype; down: fp32 rows [sorted slot][ldx]
   int x_dtype, ldx, top_k;
   const int32_t* sorted;
@@ -144,11 +148,11 @@ struct MoePromptArgs {
   int ldo, half_tiles;
 };
 
-template <int SMODE>
-struct MoePromptB {  // one K tile of one wave's weight operand, as loaded
-  u32x4 w[MP_CT];
+template <int SMODE, int NP>
+struct MoePromptB {  // one K tile of one wave's weight operand, as loaded; NP nibble planes
+  u32x4 w[MP_CT][NP];
   float sc[MP_CT][SMODE == 1 ? 4 : 1];
-  uint32_t uz[MP_CT][SMODE == 1 ? 2 : 1];
+  uint32_t uz[MP_CT][NP][SMODE == 1 ? 2 : 1];
 };
 
 // 8 signed nibbles of one blob word -> 8 fp16 (q - zp) [* r], k order {0,2,4,6,1,3,5,7}: dq8s of woq_gemm_f16.hip
@@ -164,10 +168,29 @@ __device__ __forceinline__ h8 moe_prompt_dq8(uint32_t w, h2 nlo, h2 nhi, h2 r) {
                                         __builtin_bit_cast(uint32_t, f2), __builtin_bit_cast(uint32_t, f3)});
 }
 
+// 8 table codes of one blob word -> the 8 fp16 table values in moe_prompt_dq8's element order. lut_quad looks up a byte
+// per code in either byte plane of the fp16 table; v_perm_b32 pairs the low and high bytes of k-offsets (0, 2) | (1, 3)
+// of the low nibbles and (4, 6) | (5, 7) of the high ones.
+__device__ __forceinline__ h8 moe_prompt_lut8(const LutArgs& L, uint32_t w) {
+  uint32_t lo[2], hi[2];
+  lut_quad<2>(L, w & 0x0f0f0f0fu, lo);
+  lut_quad<2>(L, (w >> 4) & 0x0f0f0f0fu, hi);
+  return __builtin_bit_cast(h8, (u32x4){__builtin_amdgcn_perm(lo[1], lo[0], 0x06020400u),
+                                        __builtin_amdgcn_perm(hi[1], hi[0], 0x06020400u),
+                                        __builtin_amdgcn_perm(lo[1], lo[0], 0x07030501u),
+                                        __builtin_amdgcn_perm(hi[1], hi[0], 0x07030501u)});
+}
+
 // GU: the gate/up launch (gate tile + up tile per wave, SiLU * mul epilogue, rows gathered by token) | the down launch
-template <bool GU, int SMODE, bool ASYM>
+// WK (woq_host.h MoeWeightKind) picks the blob words -> fp16 B fragment step and nothing else:
+//   MOE_W_TABLE  fp16(table[code]) per nibble (moe_prompt_lut8): exact for fp4_e2m1, one rounding of the value otherwise
+//   MOE_W_INT8   16 (hi - zhi) + (lo - zlo) from the two planes' words, an integer of magnitude <= 255: exact in fp16
+// either times the relative scale under scale_mode 1, as the int4 operand is.
+template <bool GU, int SMODE, bool ASYM, int WK>
 __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const MoePromptArgs a) {
   constexpr int NS = SMODE == 1 ? 2 : 1;  // scales of a tile, column and lane: its 32-k block of either 64-k half
+  constexpr int NP = WK == MOE_W_INT8 ? 2 : 1;
+  static_assert(!(WK == MOE_W_TABLE && ASYM), "the table types are symmetric");
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];  // [2][MP_IMAGE] images, [2][MP_ROWS] factors
   float* unsc = (float*)(smem + 2 * MP_IMAGE);
 
@@ -183,9 +206,11 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
   const int i16 = lane & 15, kq = lane >> 4;
 
   const uint8_t* blob = a.blobs + (size_t)expert * a.stride;
-  const u32x4* q = (const u32x4*)(blob + a.off_q);
+  const u32x4* q[NP];
+  const uint8_t* zps[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) q[p] = (const u32x4*)(blob + a.off_q[p]), zps[p] = blob + a.off_zp[p];
   const void* scales = blob + a.off_scale;
-  const uint8_t* zps = blob + a.off_zp;
   // this wave's column tiles (clamped for the loads; `live` decides the stores)
   int tn[MP_CT];
   bool live[MP_CT];
@@ -275,21 +300,28 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
     }
   };
 
-  auto load_b = [&](int kt, MoePromptB<SMODE>& bw) {
+  // plane p carries zero points under ASYM; the int8 composite's LO plane (p == 1) always does
+  auto load_uz = [&](int p, size_t si) { return (ASYM || p == 1) ? (uint32_t)zps[p][si] : 8u; };
+  auto load_b = [&](int kt, MoePromptB<SMODE, NP>& bw) {
 #pragma unroll
     for (int c = 0; c < MP_CT; ++c) {
-      bw.w[c] = __builtin_nontemporal_load(q + ((size_t)tn[c] * a.tiles_k + kt) * 64 + lane);
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+        bw.w[c][p] = __builtin_nontemporal_load(q[p] + ((size_t)tn[c] * a.tiles_k + kt) * 64 + lane);
       if constexpr (SMODE == 0) {
         const int grp = a.n_groups == 1 ? 0 : min(kt * WOQ_TILE_K / a.group, a.n_groups - 1);
         const size_t si = ((size_t)tn[c] * a.n_groups + grp) * 16 + i16;
         bw.sc[c][0] = load_f32(scales, si, a.scale_type);
-        bw.uz[c][0] = ASYM ? (uint32_t)zps[si] : 8u;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) bw.uz[c][p][0] = load_uz(p, si);
       } else {
         const size_t si = (((size_t)tn[c] * a.tiles_k + kt) * 16 + i16) * 4;
 #pragma unroll
         for (int s = 0; s < 4; ++s) bw.sc[c][s] = load_f32(scales, si + s, a.scale_type);
 #pragma unroll
-        for (int h = 0; h < 2; ++h) bw.uz[c][h] = ASYM ? (uint32_t)zps[si + 2 * h + (kq >> 1)] : 8u;
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) bw.uz[c][p][h] = load_uz(p, si + 2 * h + (kq >> 1));
       }
     }
   };
@@ -306,10 +338,10 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
 
   float cs[MP_CT];   // fp32 column factor of the tile in hand
   h8 bf[4][MP_CT];   // its B fragments
-  auto unpack = [&](const MoePromptB<SMODE>& bw) {
+  auto unpack = [&](const MoePromptB<SMODE, NP>& bw) {
 #pragma unroll
     for (int c = 0; c < MP_CT; ++c) {
-      h2 r2[NS], nlo[NS], nhi[NS];
+      h2 r2[NS], nlo[NP][NS], nhi[NP][NS];
       if constexpr (SMODE == 0) {
         cs[c] = bw.sc[c][0];
         r2[0] = (h2){(_Float16)1.f, (_Float16)1.f};
@@ -326,15 +358,28 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
         }
       }
 #pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const float uz = (float)(bw.uz[c][s] & 0xffu);
-        const _Float16 l = (_Float16)(-(1024.f + uz)), hg = (_Float16)(-(64.f + uz));
-        nlo[s] = (h2){l, l}, nhi[s] = (h2){hg, hg};
-      }
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const float uz = (float)(bw.uz[c][p][s] & 0xffu);
+          const _Float16 l = (_Float16)(-(1024.f + uz)), hg = (_Float16)(-(64.f + uz));
+          nlo[p][s] = (h2){l, l}, nhi[p][s] = (h2){hg, hg};
+        }
 #pragma unroll
       for (int hp = 0; hp < 4; ++hp) {
         const int s = SMODE == 0 ? 0 : (hp >> 1);
-        bf[hp][c] = moe_prompt_dq8<SMODE == 1>(bw.w[c][hp], nlo[s], nhi[s], r2[s]);
+        if constexpr (WK == MOE_W_INT4) {
+          bf[hp][c] = moe_prompt_dq8<SMODE == 1>(bw.w[c][0][hp], nlo[0][s], nhi[0][s], r2[s]);
+        } else {
+          h8 v;
+          if constexpr (WK == MOE_W_TABLE)
+            v = moe_prompt_lut8(a.lut, bw.w[c][0][hp]);
+          else
+            v = moe_prompt_dq8<false>(bw.w[c][0][hp], nlo[0][s], nhi[0][s], r2[s]) * (_Float16)16.f +
+                moe_prompt_dq8<false>(bw.w[c][NP - 1][hp], nlo[NP - 1][s], nhi[NP - 1][s], r2[s]);
+          if constexpr (SMODE == 1) v *= (h8){r2[s].x, r2[s].x, r2[s].x, r2[s].x, r2[s].x, r2[s].x, r2[s].x, r2[s].x};
+          bf[hp][c] = v;
+        }
       }
     }
   };
@@ -370,7 +415,7 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
   };
 
   // ---- K loop: one blob tile a trip, the next tile's operands requested before this tile's MFMAs ----
-  MoePromptB<SMODE> b0, b1;
+  MoePromptB<SMODE, NP> b0, b1;
   load_b(0, b0);
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
@@ -442,22 +487,51 @@ bool moe_prompt_shape_ok(int T, int top_k, int E, int hidden, int inter) {
          (long long)T * top_k <= MOE_PROMPT_MAX_SLOTS;
 }
 
-template <bool GU, int SMODE, bool ASYM>
+template <bool GU, int SMODE, bool ASYM, int WK>
 int moe_prompt_launch_one(const MoePromptArgs& a, dim3 grid, hipStream_t st) {
-  if (const int rc = allow_dynamic_lds<moe_prompt_gemm_kernel<GU, SMODE, ASYM>>(MP_LDS)) return rc;
-  hipLaunchKernelGGL((moe_prompt_gemm_kernel<GU, SMODE, ASYM>), grid, dim3(MP_WAVES * 64), MP_LDS, st, a);
+  if (const int rc = allow_dynamic_lds<moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK>>(MP_LDS)) return rc;
+  hipLaunchKernelGGL((moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK>), grid, dim3(MP_WAVES * 64), MP_LDS, st, a);
   return 0;
 }
+template <bool GU, int SMODE, bool ASYM>
+int moe_prompt_launch_kind(const MoePromptArgs& a, MoeWeightKind kind, dim3 grid, hipStream_t st) {
+  if (kind == MOE_W_INT8) return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT8>(a, grid, st);
+  if constexpr (!ASYM) {  // moe_header_problem admits no table blob with zero points
+    if (kind == MOE_W_TABLE) return moe_prompt_launch_one<GU, SMODE, false, MOE_W_TABLE>(a, grid, st);
+  }
+  return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT4>(a, grid, st);
+}
 template <bool GU>
-int moe_prompt_launch_gemm(const MoePromptArgs& a, bool smode1, bool asym, dim3 grid, hipStream_t st) {
-  if (!smode1) return asym ? moe_prompt_launch_one<GU, 0, true>(a, grid, st) : moe_prompt_launch_one<GU, 0, false>(a, grid, st);
-  return asym ? moe_prompt_launch_one<GU, 1, true>(a, grid, st) : moe_prompt_launch_one<GU, 1, false>(a, grid, st);
+int moe_prompt_launch_gemm(const MoePromptArgs& a, bool smode1, bool asym, MoeWeightKind kind, dim3 grid, hipStream_t st) {
+  if (!smode1)
+    return asym ? moe_prompt_launch_kind<GU, 0, true>(a, kind, grid, st) : moe_prompt_launch_kind<GU, 0, false>(a, kind, grid, st);
+  return asym ? moe_prompt_launch_kind<GU, 1, true>(a, kind, grid, st) : moe_prompt_launch_kind<GU, 1, false>(a, kind, grid, st);
 }
 
-MoePromptArgs moe_prompt_args(const void* blobs, const woq_blob_header& h, size_t stride) {
+// the fp16 table of a table weight type as two byte planes (what lut_quad looks up): d[0][c / 4] byte c % 4 = the low
+// byte of fp16(table[c]), d[1] the high byte
+LutArgs moe_prompt_lut(uint32_t weight_type) {
+  static const float nf4[16] = WOQ_LUT_NF4, e2m1[16] = WOQ_LUT_FP4_E2M1, bnb[16] = WOQ_LUT_FP4_BNB;
+  const float* tab = weight_type == WOQ_W_NF4 ? nf4 : (weight_type == WOQ_W_FP4_E2M1 ? e2m1 : bnb);
+  LutArgs L = {};
+  L.wmul = 1.f;
+  for (int c = 0; c < 16; ++c) {
+    const _Float16 v = (_Float16)tab[c];
+    uint16_t bits;
+    memcpy(&bits, &v, 2);
+    L.d[0][c >> 2] |= (uint32_t)(bits & 0xffu) << (8 * (c & 3));
+    L.d[1][c >> 2] |= (uint32_t)(bits >> 8) << (8 * (c & 3));
+  }
+  return L;
+}
+
+MoePromptArgs moe_prompt_args(const void* blobs, const woq_blob_header& h, size_t stride, MoeWeightKind& kind) {
   MoePromptArgs a = {};
   a.blobs = (const uint8_t*)blobs, a.stride = stride;
-  a.off_q = h.off_q, a.off_scale = h.off_scale, a.off_zp = h.off_zp;
+  const MoePlanes p = moe_blob_planes(h);
+  for (int i = 0; i < 2; ++i) a.off_q[i] = p.off_q[i], a.off_zp[i] = p.off_zp[i];
+  a.off_scale = p.off_scale, kind = p.kind;
+  if (kind == MOE_W_TABLE) a.lut = moe_prompt_lut(h.weight_type);
   a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.tiles_n = h.Npad / WOQ_TILE_N;
   a.n_groups = h.n_groups, a.group = h.group, a.scale_type = (int)h.scale_type;
   return a;
@@ -491,20 +565,23 @@ int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st) {
   else
     hipLaunchKernelGGL(moe_prompt_scatter_kernel<false>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, sorted, pos_of);
 
-  MoePromptArgs g = moe_prompt_args(m.gate_up_blobs, gh, m.gate_up_stride);
+  MoeWeightKind g_kind, d_kind;
+  MoePromptArgs g = moe_prompt_args(m.gate_up_blobs, gh, m.gate_up_stride, g_kind);
   g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
   g.sorted = sorted, g.blocks = blocks, g.nblocks = nblocks;
   g.out = hbuf, g.ldo = I, g.half_tiles = I / 16;
   const unsigned gx = (unsigned)((I / 16 + MP_WAVES - 1) / MP_WAVES);
-  if (const int rc = moe_prompt_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, dim3(gx, (unsigned)w.max_blocks), st))
+  if (const int rc = moe_prompt_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, g_kind,
+                                                  dim3(gx, (unsigned)w.max_blocks), st))
     return rc;
 
-  MoePromptArgs d = moe_prompt_args(m.down_blobs, dh, m.down_stride);
+  MoePromptArgs d = moe_prompt_args(m.down_blobs, dh, m.down_stride, d_kind);
   d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
   d.sorted = sorted, d.blocks = blocks, d.nblocks = nblocks;
   d.out = ybuf, d.ldo = H, d.half_tiles = 0;
   const unsigned dx = (unsigned)((d.tiles_n + MP_WAVES * MP_CT - 1) / (MP_WAVES * MP_CT));
-  if (const int rc = moe_prompt_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, dim3(dx, (unsigned)w.max_blocks), st))
+  if (const int rc = moe_prompt_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, d_kind,
+                                                   dim3(dx, (unsigned)w.max_blocks), st))
     return rc;
 
   if (m.residual != nullptr) {
@@ -532,8 +609,8 @@ extern "C" int woq_moe_prompt_forward(const void* x_dev, int x_dtype, int ldx, c
   WOQ_TRY
   using namespace woq;
   WOQ_CHECK(gate_up_hdr && down_hdr, "QBits: woq_moe_prompt_forward: null header");
-  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride)) WOQ_FAIL(p);
-  if (const char* p = moe_header_problem(*down_hdr, down_stride)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride, false)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(*down_hdr, down_stride, false)) WOQ_FAIL(p);
   const int H = down_hdr->N, I = down_hdr->K;
   WOQ_CHECK(gate_up_hdr->K == H && gate_up_hdr->N == 2 * I,
             "QBits: woq_moe_prompt_forward: gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");

@@ -1185,7 +1185,7 @@ def _same_order(parts, what):
 def _sparse_mlp(l, mlp):
     """Is layers.l's `mlp` a sparse block the engine takes — a `QuantizedMoEExpertsQBits` under `.experts` and a Mixtral /
     Qwen3-MoE top-k router with an [E, H] weight under `.gate`? False for a dense MLP; anything in between is refused."""
-    from ..transformers.llm.quantization.nn.moe import QuantizedMoEExpertsQBits
+    from ..transformers.llm.quantization.nn.moe import _ENGINE_WEIGHT_TYPES, QuantizedMoEExpertsQBits
 
     experts, gate = getattr(mlp, "experts", None), getattr(mlp, "gate", None)
     if experts is None and gate is None and hasattr(mlp, "gate_proj"):
@@ -1195,8 +1195,8 @@ def _sparse_mlp(l, mlp):
         raise RuntimeError(where + "has shared experts, which the sparse layer kind does not run")
     if not isinstance(experts, QuantizedMoEExpertsQBits):
         raise RuntimeError(where + "holds %s under .experts, not quantised expert blobs" % type(experts).__name__)
-    if not experts.grouped_supported():
-        raise RuntimeError(where + "has %s experts, which the grouped expert kernels do not take (int4 / int3 / int2 "
+    if not experts.grouped_supported() or experts.weight_dtype not in _ENGINE_WEIGHT_TYPES:
+        raise RuntimeError(where + "has %s experts, which the engine's sparse layer does not take (int4 / int3 / int2 "
                            "only; the model keeps the module path)" % experts.weight_dtype)
     if type(gate).__name__ not in ("MixtralTopKRouter", "Qwen3MoeTopKRouter") or getattr(gate, "weight", None) is None \
             or tuple(gate.weight.shape) != (experts.num_experts, experts.hidden_dim):
