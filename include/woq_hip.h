@@ -197,8 +197,9 @@ WOQ_API size_t woq_linear_backward_workspace(int M, const woq_blob_header* hdr);
  * up) lie gate_up_stride bytes apart from gate_up_blobs_dev and share the host header gate_up_hdr; the E down blobs
  * (K = inter, N = hidden) likewise. Weight types, read from the header: int4 / int3 / int2 and int8 (the composite's two
  * nibble planes in one launch, combined as 16 hi + lo in int32), sym and asym; nf4 / fp4_e2m1 / fp4_e2m1_bnb (sym; the
- * decode GEMV's digit planes, whose count follows the header's compute type); every group size and both scale modes, no
- * act-order, no fp8; inter % 16 == 0 and hidden % 4 == 0; at most 1024 experts and 8192 routed slots (T * top_k) a
+ * decode GEMV's digit planes, whose count follows the header's compute type); fp8_e4m3 / fp8_e5m2 (sym; the code bytes of
+ * the composite's two planes as the B operand of the fp8 MFMA, the activation as six base-16 digits); every group size
+ * and both scale modes, no act-order; inter % 16 == 0 and hidden % 4 == 0; at most 1024 experts and 8192 routed slots (T * top_k) a
  * call. Anything else fails with a "QBits:" message, launching nothing. Four launches (plan, gate/up, down, combine:
  * csrc/woq_moe.hip, DESIGN.md "Mixture-of-experts") whose shapes do not depend on the routing; stream-ordered, no host
  * synchronisation, no allocation, no floating-point atomics: the same inputs give the same bytes. Activations go

@@ -286,14 +286,16 @@ struct MoeCall {
   const struct MoeResidual* residual = nullptr;
 };
 // null when the grouped launches take expert blobs under this header at this stride, else the "QBits: ..." reason.
-// `int4_only` (the decode engine's sparse layer) also refuses the table types and the int8 composite, which
-// woq_moe_forward / woq_moe_prompt_forward take.
+// `int4_only` (the decode engine's sparse layer) also refuses the table types, the int8 composite and the fp8 types,
+// which woq_moe_forward / woq_moe_prompt_forward take.
 const char* moe_header_problem(const woq_blob_header& h, size_t stride, bool int4_only = true);
 // What both forms' products read of an expert blob, resolved on the host. MOE_W_INT4 and MOE_W_TABLE (nf4 / fp4: the
 // nibble is a table code, symmetric) have one nibble plane, [0]. MOE_W_INT8 is the composite of woq_int8_headers: the HI
 // plane [0] and the LO plane [1], q8 - zp8 = 16 (hi - zhi) + (lo - zlo); off_scale = the LO plane's scales s, which both
 // share; off_zp[1] always stands, off_zp[0] only under an asymmetric blob. An absent zero-point section is offset 0.
-enum MoeWeightKind { MOE_W_INT4 = 0, MOE_W_TABLE = 1, MOE_W_INT8 = 2 };
+// MOE_W_FP8 (fp8_e4m3 / fp8_e5m2) is the composite of woq_fp8_headers: the same two planes holding the nibbles of the code
+// byte (hi << 4) | (lo ^ 8), off_scale = the LO plane's scales, symmetric: no zero point is read.
+enum MoeWeightKind { MOE_W_INT4 = 0, MOE_W_TABLE = 1, MOE_W_INT8 = 2, MOE_W_FP8 = 3 };
 struct MoePlanes {
   MoeWeightKind kind;
   size_t off_q[2], off_scale, off_zp[2];

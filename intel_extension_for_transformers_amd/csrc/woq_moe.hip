@@ -1,4 +1,4 @@
-// woq_moe.hip — the routed expert block of a sparse mixture-of-experts layer over int4, nf4 / fp4 and int8 blobs:
+// woq_moe.hip — the routed expert block of a sparse mixture-of-experts layer over int4, nf4 / fp4, int8 and fp8 blobs:
 //   out[t] = sum_j topk_w[t][j] * down_e( SiLU(gate_e x_t) * up_e x_t ),  e = topk_idx[t][j],  j = 0 .. k-1 in that order
 // with E gate/up blobs (K = H, N = 2 I, columns [0, I) gate and [I, 2 I) up) and E down blobs (K = I, N = H), each kind
 // at one uniform byte stride and under one header. The definition is HF's MixtralExperts / Qwen3MoeExperts forward (a
@@ -25,7 +25,8 @@
 // and meet all row sets. Per-group scales (and zero points: sum_k (q - zp) x = sum_k q x - zp sum_k x, the second sum
 // from an MFMA against ones) are applied in fp32 after limb_combine, per tile (scale_mode 0) or per 32-k block
 // (scale_mode 1: each 64-k MFMA is issued twice, the other 32-k half's A operand read from a block of zeros). The
-// waves' partial sums meet in LDS and are added in wave order.
+// waves' partial sums meet in LDS and are added in wave order. fp8 blobs take launches 2 and 3 through a kernel of their
+// own on the fp8 MFMA, moe_fp8_gemm_kernel below.
 #include <math.h>
 
 #include <algorithm>
@@ -104,6 +105,7 @@ struct MoeGemmArgs {
   const int32_t* nblocks;
   float* out;  // gate/up: SiLU(g) * u [sorted slot][ldo]; down: y [sorted slot][ldo]
   int ldo, half_tiles;
+  int e5m2, lds_rows;  // fp8 blobs: the codes are e5m2 | the digit rows the launch's LDS holds: min(16, T k)
 };
 
 __device__ __forceinline__ float moe_scale(const void* s, size_t i, int st) {
@@ -112,7 +114,7 @@ __device__ __forceinline__ float moe_scale(const void* s, size_t i, int st) {
   return st == WOQ_BF16 ? bf16_bits_to_f32(b) : f16_bits_to_f32(b);
 }
 
-constexpr int MOE_WK_INT8 = 4;
+constexpr int MOE_WK_INT8 = 4, MOE_WK_FP8 = 5;  // (fp8: moe_fp8_gemm_kernel below)
 
 // GU: the gate/up launch (two column tiles, SiLU * mul epilogue, rows gathered by token) | the down launch
 // WK, the weight kind: 0 = int4 | 1, 2, 3 = a table type (nf4 / fp4) as that many digit planes | MOE_WK_INT8 = the int8
@@ -458,6 +460,360 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmA
   }
 }
 
+// ---- 2 / 3 for fp8 expert blobs: the grouped product on the fp8 matrix cores -------------------------------------------
+// w = value(code) * scale with an 8-bit float code (e4m3 / e5m2): the int8 route above does not apply, the code byte is
+// no integer. v_mfma_f32_16x16x32_fp8_fp8 / _fp8_bf8 reads it as it is (woq_gemv_fp8.hip states the arithmetic): the
+// B operand is code = (hi << 4) | (lo ^ 8) of the composite's two nibble planes, about one VALU per weight; the A operand
+// is the activation as SIX balanced base-16 digits d_j in [-8, 7] of v = round(x 2^(21 - e)), e per row and 1024-k
+// chunk, each an exact e4m3 value; every product is exact, the sums run in the MFMA's fp32 accumulator and
+// sum_j 16^j S_j is taken in fp32. The work split is moe_gemm_kernel's: a workgroup = one table block x one 16-column
+// tile (gate/up: the pair tn, tn + I / 16), four waves interleaved over the tiles of a chunk, weight words requested
+// before the staging and fetched once per workgroup, partial sums added in wave order.
+//   Staging. u = v + 0x888888 has the nibbles d_j + 8 (a balanced digit is a plain digit of the number shifted by
+// eight in every place), and u is one integer add away from the bits of fl32(x 2^(21 - e) + 1.5 2^23). Byte n of four
+// neighbouring u's is gathered into one word by v_perm_b32, and its low / high nibbles go through a 16-entry byte table
+// (lut_quad: nibble -> the e4m3 byte of nibble - 8): about 11 VALU per activation for all six digits, against about 30
+// for the convert-and-pack form of the dense GEMV. Digit rows lie in LDS as [row][digit][MOE_RB].
+//   Row-set packing, chosen wave-uniformly from the block's row count R:
+//     R <= 2  (decode) the GEMV's: MFMA row r = 6 m + j holds digit j of row m, ONE MFMA pair per 32 k and column tile;
+//             the six digit sums of a row sit in two lane quarters and are weighted by 16^j 2^(e - 21) and summed over
+//             the quarters once, after the last chunk.
+//     R > 2   row set j holds digit j of all 16 rows: six MFMA pairs per 32 k, no idle MFMA row at R = 16, and the
+//             recombination is lane-local over six accumulator fragments. With [row][digit] rows of 1040 B the sixteen
+//             lanes of a quarter read 16 B at a stride of 6240 B: 4 (6 i + kq) mod 64 covers every bank four times, the
+//             minimum for a 1 KB request.
+//     One row under the second packing would issue six MFMA pairs where one does: the launch would be bound by the
+//     matrix pipe, not by the weight stream, which is why decode blocks keep the first (not measured: the second
+//     packing was never run at R <= 2).
+//   LDS is dynamic: one zero row + 6 min(16, T k) digit rows of 1040 B, the attribute set once for the 16-row maximum
+//   (100880 B + 8.3 KB static: one workgroup of four waves per CU). A decode call asks for what its rows need — T k = 2:
+//   13.5 KB; T k = 8: 51 KB — and keeps the two workgroups per CU that the kernel's registers allow (138 - 190 VGPRs +
+//   up to 48 accumulation registers: two waves per SIMD).
+//   Scales: scale_mode 0 per tile in fp32 after the recombination; scale_mode 1 as woq_gemv_fp8.hip: each 64-k half is
+//   issued once per 32-k block with the other block's two lane quarters reading the zero row, at the same offsets.
+//   Dead MFMA rows read the zero row too (digit byte 0 = +0.0), buffer loads return zero past K, tiles past tiles_k are
+//   skipped: nothing but the block's own rows and the slice's own k reaches an accumulator.
+typedef long i64_t;
+constexpr int MOE_F8_DIG = 6;
+constexpr int moe_fp8_lds_bytes(int rows) { return (1 + MOE_F8_DIG * rows) * MOE_RB; }
+
+template <bool E5M2>
+__device__ __forceinline__ float4_t moe_mfma_f8(i64_t a, i64_t b, float4_t c) {
+  if constexpr (E5M2)
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_bf8(a, b, c, 0, 0, 0);  // A: e4m3 digits, B: e5m2 codes
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
+}
+// the 16 code bytes of one lane and 64-k half; k order of a dword pair: low nibbles, high nibbles (woq_blob.h)
+__device__ __forceinline__ void moe_fp8_codes(uint32_t h0, uint32_t h1, uint32_t l0, uint32_t l1, i64_t& bq0, i64_t& bq1) {
+  const uint32_t b0 = ((h0 & 0x0f0f0f0fu) << 4) | ((l0 & 0x0f0f0f0fu) ^ 0x08080808u);
+  const uint32_t b1 = (h0 & 0xf0f0f0f0u) | (((l0 >> 4) & 0x0f0f0f0fu) ^ 0x08080808u);
+  const uint32_t b2 = ((h1 & 0x0f0f0f0fu) << 4) | ((l1 & 0x0f0f0f0fu) ^ 0x08080808u);
+  const uint32_t b3 = (h1 & 0xf0f0f0f0u) | (((l1 >> 4) & 0x0f0f0f0fu) ^ 0x08080808u);
+  bq0 = (i64_t)(((unsigned long)b1 << 32) | b0), bq1 = (i64_t)(((unsigned long)b3 << 32) | b2);
+}
+
+template <bool GU, int SMODE, bool E5M2>
+__global__ __launch_bounds__(MOE_WAVES * 64) void moe_fp8_gemm_kernel(const MoeGemmArgs a) {
+  constexpr int CB = GU ? 2 : 1;
+  constexpr int NS = SMODE == 1 ? 4 : 1;
+  constexpr int ND = MOE_F8_DIG;
+  extern __shared__ __attribute__((aligned(16))) unsigned char f8_lds[];  // [zero row][row][digit][MOE_RB]
+  __shared__ __attribute__((aligned(16))) float unsc_s[MOE_BLOCK_ROWS];  // per row: 2^(e - 21) of the staged chunk
+  __shared__ float slab[MOE_WAVES][CB][MOE_BLOCK_ROWS][16];
+  unsigned char* zrow = f8_lds;
+  unsigned char* strip = f8_lds + MOE_RB;
+
+  const int b = (int)blockIdx.y;
+  if (b >= *a.nblocks) return;
+  const MoeBlock blk = a.blocks[b];
+  const int expert = __builtin_amdgcn_readfirstlane(blk.expert), first = __builtin_amdgcn_readfirstlane(blk.first);
+  const int R = min(__builtin_amdgcn_readfirstlane(blk.rows), a.lds_rows);  // (a block has at most min(16, T k) rows)
+  const bool pair = R <= 2;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int i16 = lane & 15, kq = lane >> 4;
+  for (int j = tid; j < MOE_RB / 4; j += MOE_WAVES * 64) ((uint32_t*)zrow)[j] = 0u;
+  if (tid < MOE_BLOCK_ROWS) unsc_s[tid] = 0.f;
+
+  const uint8_t* blob = a.blobs + (size_t)expert * a.stride;
+  const u32x4* q[2] = {(const u32x4*)(blob + a.off_q[0]), (const u32x4*)(blob + a.off_q[1])};
+  const void* scales = blob + a.off_scale;
+  int tn[CB];
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) tn[cb] = (int)blockIdx.x + cb * a.half_tiles;
+
+  // nibble n -> the e4m3 byte of n - 8: -8 .. -1 = d0 ce cc ca c8 c4 c0 b8, 0 .. 7 = 00 38 40 44 48 4a 4c 4e
+  const LutArgs dig = {{{0xcacccED0u, 0xb8c0c4c8u, 0x44403800u, 0x4e4c4a48u}, {0, 0, 0, 0}, {0, 0, 0, 0}}, 1.f};
+
+  // this lane's A operand: the strip row of MFMA row i16 (digit 0 under the second packing, whose digit j lies
+  // `dstep` * j further), or the zero row; both at + kq * 16, so that tile and half offsets are immediates
+  const bool a_live = pair ? i16 < ND * R : i16 < R;
+  const unsigned char* a_row = (a_live ? strip + (size_t)(pair ? i16 : ND * i16) * MOE_RB : zrow) + kq * 16;
+  const int dstep = a_live ? MOE_RB : 0;
+  const unsigned char* z_row = zrow + kq * 16;
+  // scale_mode 1: 32-k block g of a half = lane quarters 2 g, 2 g + 1
+  const unsigned char* a_blk[2] = {kq < 2 ? a_row : z_row, kq < 2 ? z_row : a_row};
+  const int d_blk[2] = {kq < 2 ? dstep : 0, kq < 2 ? 0 : dstep};
+
+  float acc[4][CB];    // second packing: rows 4 kq + i of column i16
+  float tot[2][CB];    // first packing: rows 0, 1 of column i16, this lane quarter's digits
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    tot[0][cb] = tot[1][cb] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i][cb] = 0.f;
+  }
+  const float4_t fzero = {0.f, 0.f, 0.f, 0.f};
+
+  const int nchunks = (a.tiles_k + MOE_TPC - 1) / MOE_TPC;
+#pragma unroll 1
+  for (int c = 0; c < nchunks; ++c) {
+    // ---- this wave's tiles of the chunk: both planes' words and the scales, requested before the staging ----
+    u32x4 w[MOE_TPW][CB][2];
+    float sc[MOE_TPW][CB][NS];
+#pragma unroll
+    for (int ti = 0; ti < MOE_TPW; ++ti) {
+      const int kt = c * MOE_TPC + wid + ti * MOE_WAVES;
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) {
+        w[ti][cb][0] = w[ti][cb][1] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) sc[ti][cb][s] = 0.f;
+        if (kt >= a.tiles_k) continue;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+          w[ti][cb][p] = __builtin_nontemporal_load(q[p] + ((size_t)tn[cb] * a.tiles_k + kt) * 64 + lane);
+        if constexpr (SMODE == 0) {
+          const int grp = a.n_groups == 1 ? 0 : min(kt * 128 / a.group, a.n_groups - 1);
+          sc[ti][cb][0] = moe_scale(scales, ((size_t)tn[cb] * a.n_groups + grp) * 16 + i16, a.scale_type);
+        } else {
+          const size_t si = (((size_t)tn[cb] * a.tiles_k + kt) * 16 + i16) * 4;
+#pragma unroll
+          for (int s = 0; s < 4; ++s) sc[ti][cb][s] = moe_scale(scales, si + s, a.scale_type);
+        }
+      }
+    }
+
+    // ---- stage the chunk of the block's rows as digit rows ----
+    __syncthreads();  // the previous chunk's operand reads (first chunk: the zero row's stores) are done
+    const int k0 = c * MOE_KC;
+    const int xlen = max(0, min(MOE_KC, a.K - k0));
+    for (int m = wid; m < R; m += MOE_WAVES) {
+      float4_t xv[4];
+      if (GU && a.x_dtype != WOQ_F32) {
+        const int slot = __builtin_amdgcn_readfirstlane(a.sorted[first + m]);
+        const rsrc_t rx = make_rsrc((const uint16_t*)a.x + (size_t)(slot / a.top_k) * a.ldx + k0, xlen * 2);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint2 r = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rx, lane * 8 + j * 512, 0, 0));
+          const uint16_t hb[4] = {(uint16_t)r.x, (uint16_t)(r.x >> 16), (uint16_t)r.y, (uint16_t)(r.y >> 16)};
+          float f[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float fb = bf16_bits_to_f32(hb[i]), fh = f16_bits_to_f32(hb[i]);
+            f[i] = a.x_dtype == WOQ_BF16 ? fb : fh;
+          }
+          xv[j] = (float4_t){f[0], f[1], f[2], f[3]};
+        }
+      } else {
+        const int src = GU ? __builtin_amdgcn_readfirstlane(a.sorted[first + m]) / a.top_k : first + m;
+        const rsrc_t rx = make_rsrc((const float*)a.x + (size_t)src * a.ldx + k0, xlen * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + j * 1024, 0, 0));
+      }
+      float amax = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        amax = fmaxf(fmaxf(amax, fabsf(xv[j].x)), fmaxf(fabsf(xv[j].y), fmaxf(fabsf(xv[j].z), fabsf(xv[j].w))));
+      amax = wave_max_dpp(amax);
+      int e = 0;
+      if (amax > 0.f && amax < INFINITY) e = max(-100, min(100, __builtin_amdgcn_frexp_expf(amax)));
+      const float sfix = ldexpf(1.f, 21 - e);
+      if (lane == 0) unsc_s[m] = ldexpf(1.f, e - 21);
+      unsigned char* r0 = strip + (size_t)(ND * m) * MOE_RB + lane * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // amax < 2^e  =>  |x| 2^(21 - e) < 2^21: the fp32 sum with 1.5 * 2^23 has ulp 1 and the bits 0x4B000000 + v + 2^22
+        // (moe_gemm_kernel's staging); + 0x488888 - 0x4B000000 leaves u = v + 0x888888 < 2^24
+        constexpr uint32_t OFF = 0x00488888u - 0x4B000000u;
+        const uint32_t ua = __float_as_uint(fmaf(xv[j].x, sfix, 12582912.f)) + OFF;
+        const uint32_t ub = __float_as_uint(fmaf(xv[j].y, sfix, 12582912.f)) + OFF;
+        const uint32_t uc = __float_as_uint(fmaf(xv[j].z, sfix, 12582912.f)) + OFF;
+        const uint32_t ud = __float_as_uint(fmaf(xv[j].w, sfix, 12582912.f)) + OFF;
+        // byte n of (ua, ub, uc, ud) into one word: v_perm_b32(hi, lo, sel) picks bytes of {hi:lo}, 0x0c = zero
+        const uint32_t wb[3] = {
+            __builtin_amdgcn_perm(ub, ua, 0x0c0c0400u) | __builtin_amdgcn_perm(ud, uc, 0x04000c0cu),
+            __builtin_amdgcn_perm(ub, ua, 0x0c0c0501u) | __builtin_amdgcn_perm(ud, uc, 0x05010c0cu),
+            __builtin_amdgcn_perm(ub, ua, 0x0c0c0602u) | __builtin_amdgcn_perm(ud, uc, 0x06020c0cu)};
+#pragma unroll
+        for (int n = 0; n < 3; ++n) {
+          uint32_t lo[1], hi[1];
+          lut_quad<1>(dig, wb[n] & 0x0f0f0f0fu, lo);
+          lut_quad<1>(dig, (wb[n] >> 4) & 0x0f0f0f0fu, hi);
+          *(uint32_t*)(r0 + (size_t)(2 * n) * MOE_RB + j * 256) = lo[0];
+          *(uint32_t*)(r0 + (size_t)(2 * n + 1) * MOE_RB + j * 256) = hi[0];
+        }
+      }
+    }
+    __syncthreads();
+
+    if (pair) {
+      // D: lane quarter kq holds MFMA rows 4 kq + i = (activation row, digit); their weights 16^digit 2^(e - 21)
+      float c0[4], c1[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 4 * kq + i, m = r / ND, dg = r - m * ND;
+        const float p = ldexpf(1.f, 4 * dg);
+        c0[i] = (m == 0 && R > 0) ? p * unsc_s[0] : 0.f;
+        c1[i] = (m == 1 && R > 1) ? p * unsc_s[1] : 0.f;
+      }
+#pragma unroll
+      for (int ti = 0; ti < MOE_TPW; ++ti) {
+        const int tt = wid + ti * MOE_WAVES;  // tile of the chunk
+        if (c * MOE_TPC + tt >= a.tiles_k) continue;
+        float4_t d[CB][NS];
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+          for (int s = 0; s < NS; ++s) d[cb][s] = fzero;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          i64_t bq0[CB], bq1[CB];
+#pragma unroll
+          for (int cb = 0; cb < CB; ++cb) {
+            const u32x4 wh = w[ti][cb][0], wl = w[ti][cb][1];
+            moe_fp8_codes(h == 0 ? wh.x : wh.z, h == 0 ? wh.y : wh.w, h == 0 ? wl.x : wl.z, h == 0 ? wl.y : wl.w, bq0[cb],
+                          bq1[cb]);
+          }
+#pragma unroll
+          for (int g = 0; g < (SMODE == 1 ? 2 : 1); ++g) {
+            const unsigned char* ap = SMODE == 1 ? a_blk[g] : a_row;
+            const u32x4 av = *(const u32x4*)(ap + tt * 128 + h * 64);
+            const i64_t a_lo = (i64_t)(((unsigned long)av.y << 32) | av.x), a_hi = (i64_t)(((unsigned long)av.w << 32) | av.z);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+              float4_t& dd = d[cb][SMODE == 1 ? 2 * h + g : 0];
+              dd = moe_mfma_f8<E5M2>(a_lo, bq0[cb], dd);
+              dd = moe_mfma_f8<E5M2>(a_hi, bq1[cb], dd);
+            }
+          }
+        }
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+          for (int s = 0; s < NS; ++s) {
+            const float4_t dd = d[cb][s];
+            tot[0][cb] = fmaf(sc[ti][cb][s], fmaf(dd.x, c0[0], fmaf(dd.y, c0[1], fmaf(dd.z, c0[2], dd.w * c0[3]))), tot[0][cb]);
+            tot[1][cb] = fmaf(sc[ti][cb][s], fmaf(dd.x, c1[0], fmaf(dd.y, c1[1], fmaf(dd.z, c1[2], dd.w * c1[3]))), tot[1][cb]);
+          }
+      }
+    } else {
+      const float4_t un = *(const float4_t*)(unsc_s + 4 * kq);
+#pragma unroll
+      for (int ti = 0; ti < MOE_TPW; ++ti) {
+        const int tt = wid + ti * MOE_WAVES;
+        if (c * MOE_TPC + tt >= a.tiles_k) continue;
+        // sum_j 16^j S_j of one scale block, most significant digit first, into the running sums
+        auto fold = [&](const float4_t (&S)[ND], int cb, float s) {
+          float4_t f = S[ND - 1];
+#pragma unroll
+          for (int j = ND - 2; j >= 0; --j) f = f * 16.f + S[j];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[i][cb] = fmaf(s * un[i], f[i], acc[i][cb]);
+        };
+        if constexpr (SMODE == 0) {
+          float4_t S[CB][ND];
+#pragma unroll
+          for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int j = 0; j < ND; ++j) S[cb][j] = fzero;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            i64_t bq0[CB], bq1[CB];
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+              const u32x4 wh = w[ti][cb][0], wl = w[ti][cb][1];
+              moe_fp8_codes(h == 0 ? wh.x : wh.z, h == 0 ? wh.y : wh.w, h == 0 ? wl.x : wl.z, h == 0 ? wl.y : wl.w,
+                            bq0[cb], bq1[cb]);
+            }
+#pragma unroll
+            for (int j = 0; j < ND; ++j) {
+              const u32x4 av = *(const u32x4*)(a_row + j * dstep + tt * 128 + h * 64);
+              const i64_t a_lo = (i64_t)(((unsigned long)av.y << 32) | av.x), a_hi = (i64_t)(((unsigned long)av.w << 32) | av.z);
+#pragma unroll
+              for (int cb = 0; cb < CB; ++cb) {
+                S[cb][j] = moe_mfma_f8<E5M2>(a_lo, bq0[cb], S[cb][j]);
+                S[cb][j] = moe_mfma_f8<E5M2>(a_hi, bq1[cb], S[cb][j]);
+              }
+            }
+          }
+#pragma unroll
+          for (int cb = 0; cb < CB; ++cb) fold(S[cb], cb, sc[ti][cb][0]);
+        } else {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            i64_t bq0[CB], bq1[CB];
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+              const u32x4 wh = w[ti][cb][0], wl = w[ti][cb][1];
+              moe_fp8_codes(h == 0 ? wh.x : wh.z, h == 0 ? wh.y : wh.w, h == 0 ? wl.x : wl.z, h == 0 ? wl.y : wl.w,
+                            bq0[cb], bq1[cb]);
+            }
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+              float4_t S[CB][ND];
+#pragma unroll
+              for (int j = 0; j < ND; ++j) {
+                const u32x4 av = *(const u32x4*)(a_blk[g] + j * d_blk[g] + tt * 128 + h * 64);
+                const i64_t a_lo = (i64_t)(((unsigned long)av.y << 32) | av.x), a_hi = (i64_t)(((unsigned long)av.w << 32) | av.z);
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) {
+                  S[cb][j] = moe_mfma_f8<E5M2>(a_lo, bq0[cb], fzero);
+                  S[cb][j] = moe_mfma_f8<E5M2>(a_hi, bq1[cb], S[cb][j]);
+                }
+              }
+#pragma unroll
+              for (int cb = 0; cb < CB; ++cb) fold(S[cb], cb, sc[ti][cb][2 * h + g]);
+            }
+          }
+        }
+      }
+    }
+  }
+
+  // ---- the waves' partial sums, added in wave order; epilogue ----
+  if (pair) {
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+      const float t0 = reduce_kq(tot[0][cb]), t1 = reduce_kq(tot[1][cb]);
+      if (lane < 16) slab[wid][cb][0][lane] = t0, slab[wid][cb][1][lane] = t1;
+    }
+  } else {
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) slab[wid][cb][4 * kq + i][i16] = acc[i][cb];
+  }
+  __syncthreads();
+  const int row = tid >> 4, col = tid & 15;
+  if (row >= R) return;
+  float v[CB];
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    v[cb] = 0.f;
+#pragma unroll
+    for (int w2 = 0; w2 < MOE_WAVES; ++w2) v[cb] += slab[w2][cb][row][col];
+  }
+  const int n = (int)blockIdx.x * 16 + col;
+  if constexpr (GU) {
+    a.out[(size_t)(first + row) * a.ldo + n] = v[0] / (1.0f + expf(-v[0])) * v[CB - 1];  // n < I: I % 16 == 0
+  } else {
+    if (n < a.N) a.out[(size_t)(first + row) * a.ldo + n] = v[0];
+  }
+}
+
 // ---- 4. combine ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restrict__ y, const int32_t* __restrict__ pos_of,
                                                           const float* __restrict__ topk_w, int top_k, int H,
@@ -507,9 +863,21 @@ void moe_launch_kind(const MoeGemmArgs& a, int wk, dim3 grid, hipStream_t st) {
   }
 }
 
+template <bool GU, int SMODE, bool E5M2>
+int moe_launch_fp8(const MoeGemmArgs& a, dim3 grid, hipStream_t st) {
+  constexpr auto kern = moe_fp8_gemm_kernel<GU, SMODE, E5M2>;
+  if (const int rc = allow_dynamic_lds<kern>(moe_fp8_lds_bytes(MOE_BLOCK_ROWS))) return rc;
+  hipLaunchKernelGGL(kern, grid, dim3(MOE_WAVES * 64), moe_fp8_lds_bytes(a.lds_rows), st, a);
+  return 0;
+}
+
 // `wk`: the kernel's weight kind, from moe_gemm_args
 template <bool GU>
 int moe_launch_gemm(const MoeGemmArgs& a, bool smode1, bool asym, int wk, dim3 grid, hipStream_t st) {
+  if (wk == MOE_WK_FP8) {  // symmetric: moe_header_problem
+    if (smode1) return a.e5m2 ? moe_launch_fp8<GU, 1, true>(a, grid, st) : moe_launch_fp8<GU, 1, false>(a, grid, st);
+    return a.e5m2 ? moe_launch_fp8<GU, 0, true>(a, grid, st) : moe_launch_fp8<GU, 0, false>(a, grid, st);
+  }
   if (!smode1 && !asym) moe_launch_kind<GU, 0, false>(a, wk, grid, st);
   if (!smode1 && asym) moe_launch_kind<GU, 0, true>(a, wk, grid, st);
   if (smode1 && !asym) moe_launch_kind<GU, 1, false>(a, wk, grid, st);
@@ -526,7 +894,8 @@ MoeGemmArgs moe_gemm_args(const void* blobs, const woq_blob_header& h, size_t st
   a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.n_groups = h.n_groups, a.group = h.group;
   a.scale_type = (int)h.scale_type;
   const int ndig = lut_args_for(h.weight_type, h.compute_type, a.lut);  // 0, and an empty table, for the integer kinds
-  wk = p.kind == MOE_W_TABLE ? ndig : (p.kind == MOE_W_INT8 ? MOE_WK_INT8 : 0);
+  wk = p.kind == MOE_W_TABLE ? ndig : (p.kind == MOE_W_INT8 ? MOE_WK_INT8 : (p.kind == MOE_W_FP8 ? MOE_WK_FP8 : 0));
+  a.e5m2 = h.weight_type == WOQ_W_FP8_E5M2;
   return a;
 }
 
@@ -535,15 +904,23 @@ MoeGemmArgs moe_gemm_args(const void* blobs, const woq_blob_header& h, size_t st
 const char* moe_header_problem(const woq_blob_header& h, size_t stride, bool int4_only) {
   if (h.magic != WOQ_BLOB_MAGIC) return "QBits: woq_moe_forward: not a WQH1 packed weight";
   const bool table = woq_weight_is_table(h.weight_type);
-  // fp8 blobs are code bytes for the fp8 MFMA, another kernel
-  if (h.weight_type != WOQ_W_INT4_CLIP && (int4_only || (h.weight_type != WOQ_W_INT8 && !table)))
-    return "QBits: woq_moe_forward takes int4 / int3 / int2 expert blobs; other weight types run the per-expert loop";
+  const bool fp8 = woq_weight_is_fp8(h.weight_type);
+  if (h.weight_type != WOQ_W_INT4_CLIP && int4_only)
+    return "QBits: the engine's sparse layer takes int4 / int3 / int2 expert blobs";
+  if (h.weight_type != WOQ_W_INT4_CLIP && h.weight_type != WOQ_W_INT8 && !table && !fp8)
+    return "QBits: woq_moe_forward takes int4 / int3 / int2, nf4 / fp4, int8 and fp8 expert blobs";
   if (h.off_shuffle != 0) return "QBits: woq_moe_forward: act-order expert blobs are not built";
   if (h.K <= 0 || h.N <= 0 || h.Kpad % WOQ_TILE_K != 0 || h.Npad % WOQ_TILE_N != 0 || h.n_groups <= 0 || h.group <= 0 ||
       h.scale_mode > 1u || h.scale_type > (uint32_t)WOQ_F16)
     return "QBits: woq_moe_forward: corrupt blob header";
   if (h.scale_mode == 0 && h.n_groups > 1 && h.group % WOQ_TILE_K != 0) return "QBits: woq_moe_forward: corrupt blob header";
-  if (table && h.off_zp != 0) return "QBits: woq_moe_forward: corrupt blob header";  // the table types are symmetric
+  if ((table || fp8) && h.off_zp != 0) return "QBits: woq_moe_forward: corrupt blob header";  // these types are symmetric
+  if (fp8) {  // the composite's sections must lie where woq_fp8_headers puts them
+    woq_blob_header o, hi, lo;
+    if (woq_fp8_headers(&o, &hi, &lo, h.K, h.N, h.group, h.weight_type, h.scale_type, h.compute_type, 0) != 0 ||
+        o.off_q != h.off_q || o.off_scale != h.off_scale || o.total_bytes != h.total_bytes)
+      return "QBits: woq_moe_forward: corrupt blob header";
+  }
   if (h.weight_type == WOQ_W_INT8) {  // the composite's sections must lie where woq_int8_headers puts them
     woq_blob_header o, hi, lo;
     if (woq_int8_headers(&o, &hi, &lo, h.K, h.N, h.group, h.scale_type, h.compute_type, h.off_zp != 0, 0) != 0 ||
@@ -564,6 +941,14 @@ MoePlanes moe_blob_planes(const woq_blob_header& h) {
     p.off_q[0] = h.off_q + hi.off_q, p.off_q[1] = h.off_scale + lo.off_q;
     p.off_scale = h.off_scale + lo.off_scale;
     p.off_zp[0] = hi.off_zp ? h.off_q + hi.off_zp : 0, p.off_zp[1] = h.off_scale + lo.off_zp;
+    return p;
+  }
+  if (woq_weight_is_fp8(h.weight_type)) {  // both planes carry the scales s; no zero point is read
+    woq_blob_header o, hi, lo;
+    woq_fp8_headers(&o, &hi, &lo, h.K, h.N, h.group, h.weight_type, h.scale_type, h.compute_type, 0);
+    p.kind = MOE_W_FP8;
+    p.off_q[0] = h.off_q + hi.off_q, p.off_q[1] = h.off_scale + lo.off_q;
+    p.off_scale = h.off_scale + lo.off_scale;
     return p;
   }
   p.kind = woq_weight_is_table(h.weight_type) ? MOE_W_TABLE : MOE_W_INT4;
@@ -605,14 +990,19 @@ int launch_moe_forward(const MoeCall& m, hipStream_t st) {
   g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
   g.sorted = sorted, g.blocks = blocks, g.nblocks = nblocks;
   g.out = hbuf, g.ldo = I, g.half_tiles = I / 16;
-  moe_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, g_wk, dim3((unsigned)(I / 16), (unsigned)w.max_blocks), st);
+  g.lds_rows = std::min(MOE_BLOCK_ROWS, S);
+  if (const int rc = moe_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, g_wk,
+                                           dim3((unsigned)(I / 16), (unsigned)w.max_blocks), st))
+    return rc;
 
   MoeGemmArgs d = moe_gemm_args(m.down_blobs, dh, m.down_stride, d_wk);
   d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
   d.sorted = sorted, d.blocks = blocks, d.nblocks = nblocks;
   d.out = ybuf, d.ldo = H, d.half_tiles = 0;
-  moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, d_wk,
-                         dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks), st);
+  d.lds_rows = g.lds_rows;
+  if (const int rc = moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, d_wk,
+                                            dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks), st))
+    return rc;
 
   if (m.residual != nullptr) {
     if (const int rc = launch_moe_combine_residual(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, *m.residual, st)) return rc;

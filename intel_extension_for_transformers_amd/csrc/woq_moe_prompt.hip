@@ -29,7 +29,8 @@
 //       A tile's products are accumulated in fresh fp32 fragments and folded into the running fp32 accumulators with
 //     2^(e - 15)[row] * (scale | 2^E)[column]. The table types (nf4 / fp4) and the int8 composite differ in this step
 //     alone: moe_prompt_lut8 selects fp16(table[code]) per nibble, the int8 operand is 16 (hi - zhi) + (lo - zlo) of the
-//     two planes' words (exact in fp16); scales as for int4. One fp16 product per operand pair, fp32 accumulation: the contract of the
+//     two planes' words (exact in fp16), an fp8 code byte of the same two planes its exact fp16 value (moe_prompt_fp8);
+//     scales as for int4. One fp16 product per operand pair, fp32 accumulation: the contract of the
 //     dense prompt GEMM's bf16 / fp16 / int8 compute modes. Row tiles past the block's rows are skipped wave-uniformly.
 //  4. combine: woq_moe.hip's launch_moe_combine.
 // No split-K, no floating-point atomics, a fixed summation order: the same inputs give the same bytes.
@@ -146,6 +147,7 @@ struct MoePromptArgs {
   const int32_t* nblocks;
   float* out;  // gate/up: SiLU(g) * u [sorted slot][ldo]; down: y [sorted slot][ldo]
   int ldo, half_tiles;
+  bool e5m2;  // MOE_W_FP8: the codes are e5m2
 };
 
 template <int SMODE, int NP>
@@ -181,16 +183,37 @@ __device__ __forceinline__ h8 moe_prompt_lut8(const LutArgs& L, uint32_t w) {
                                         __builtin_amdgcn_perm(hi[1], hi[0], 0x07030501u)});
 }
 
+// 8 fp8 codes of one word of each nibble plane, code = (hi << 4) | (lo ^ 8) (include/woq_blob.h woq_fp8_headers), -> 8
+// fp16 in moe_prompt_dq8's element order. Byte b of a word holds k = b in its low nibble and k = b + 4 in its high one, so
+// the low nibbles give the codes of k 0..3 and the high ones those of k 4..7; v_perm_b32 puts codes (0, 2) | (4, 6) |
+// (1, 3) | (5, 7) into the HIGH bytes of a half pair. An e5m2 code is the high byte of the fp16 of the same value, exactly
+// (subnormals, both zeros). An e4m3 code s eeee mmm becomes s 0eeee mmm0000000: the fp16 of value 2^-8 — normal codes
+// through the exponent bias (15 against 7), subnormal ones (eeee = 0) as fp16 subnormals with the same significand, -0 as
+// -0 — and the packed multiply by 2^8 (times the relative scale under scale_mode 1: then the one rounding of the
+// operand) restores the value before it meets the MFMA; no operand is left subnormal by the format change itself.
+template <bool E5M2>
+__device__ __forceinline__ h8 moe_prompt_fp8(uint32_t hi, uint32_t lo, _Float16 mul) {
+  const uint32_t c03 = ((hi & 0x0f0f0f0fu) << 4) | ((lo & 0x0f0f0f0fu) ^ 0x08080808u);
+  const uint32_t c47 = (hi & 0xf0f0f0f0u) | (((lo >> 4) & 0x0f0f0f0fu) ^ 0x08080808u);
+  u32x4 t = {__builtin_amdgcn_perm(0u, c03, 0x020c000cu), __builtin_amdgcn_perm(0u, c47, 0x020c000cu),
+             __builtin_amdgcn_perm(0u, c03, 0x030c010cu), __builtin_amdgcn_perm(0u, c47, 0x030c010cu)};
+  if constexpr (!E5M2) t = (t & 0x80008000u) | ((t >> 1) & 0x3f803f80u);
+  return __builtin_bit_cast(h8, t) * mul;
+}
+
 // GU: the gate/up launch (gate tile + up tile per wave, SiLU * mul epilogue, rows gathered by token) | the down launch
 // WK (woq_host.h MoeWeightKind) picks the blob words -> fp16 B fragment step and nothing else:
 //   MOE_W_TABLE  fp16(table[code]) per nibble (moe_prompt_lut8): exact for fp4_e2m1, one rounding of the value otherwise
 //   MOE_W_INT8   16 (hi - zhi) + (lo - zlo) from the two planes' words, an integer of magnitude <= 255: exact in fp16
+//   MOE_W_FP8    the exact fp16 value of the code byte of the two planes' words (moe_prompt_fp8); MP_W_FP8_E5M2 its e5m2 form
 // either times the relative scale under scale_mode 1, as the int4 operand is.
+constexpr int MP_W_FP8_E5M2 = MOE_W_FP8 + 1;
 template <bool GU, int SMODE, bool ASYM, int WK>
 __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const MoePromptArgs a) {
   constexpr int NS = SMODE == 1 ? 2 : 1;  // scales of a tile, column and lane: its 32-k block of either 64-k half
-  constexpr int NP = WK == MOE_W_INT8 ? 2 : 1;
-  static_assert(!(WK == MOE_W_TABLE && ASYM), "the table types are symmetric");
+  constexpr bool FP8 = WK == MOE_W_FP8 || WK == MP_W_FP8_E5M2;
+  constexpr int NP = WK == MOE_W_INT8 || FP8 ? 2 : 1;
+  static_assert(!((WK == MOE_W_TABLE || FP8) && ASYM), "the table and fp8 types are symmetric");
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];  // [2][MP_IMAGE] images, [2][MP_ROWS] factors
   float* unsc = (float*)(smem + 2 * MP_IMAGE);
 
@@ -301,7 +324,7 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
   };
 
   // plane p carries zero points under ASYM; the int8 composite's LO plane (p == 1) always does
-  auto load_uz = [&](int p, size_t si) { return (ASYM || p == 1) ? (uint32_t)zps[p][si] : 8u; };
+  auto load_uz = [&](int p, size_t si) { return !FP8 && (ASYM || p == 1) ? (uint32_t)zps[p][si] : 8u; };
   auto load_b = [&](int kt, MoePromptB<SMODE, NP>& bw) {
 #pragma unroll
     for (int c = 0; c < MP_CT; ++c) {
@@ -370,6 +393,9 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
         const int s = SMODE == 0 ? 0 : (hp >> 1);
         if constexpr (WK == MOE_W_INT4) {
           bf[hp][c] = moe_prompt_dq8<SMODE == 1>(bw.w[c][0][hp], nlo[0][s], nhi[0][s], r2[s]);
+        } else if constexpr (FP8) {
+          constexpr bool E5M2 = WK == MP_W_FP8_E5M2;
+          bf[hp][c] = moe_prompt_fp8<E5M2>(bw.w[c][0][hp], bw.w[c][1][hp], r2[s].x * (_Float16)(E5M2 ? 1.f : 256.f));
         } else {
           h8 v;
           if constexpr (WK == MOE_W_TABLE)
@@ -496,7 +522,10 @@ int moe_prompt_launch_one(const MoePromptArgs& a, dim3 grid, hipStream_t st) {
 template <bool GU, int SMODE, bool ASYM>
 int moe_prompt_launch_kind(const MoePromptArgs& a, MoeWeightKind kind, dim3 grid, hipStream_t st) {
   if (kind == MOE_W_INT8) return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT8>(a, grid, st);
-  if constexpr (!ASYM) {  // moe_header_problem admits no table blob with zero points
+  if constexpr (!ASYM) {  // moe_header_problem admits no table or fp8 blob with zero points
+    if (kind == MOE_W_FP8)
+      return a.e5m2 ? moe_prompt_launch_one<GU, SMODE, false, MP_W_FP8_E5M2>(a, grid, st)
+                    : moe_prompt_launch_one<GU, SMODE, false, MOE_W_FP8>(a, grid, st);
     if (kind == MOE_W_TABLE) return moe_prompt_launch_one<GU, SMODE, false, MOE_W_TABLE>(a, grid, st);
   }
   return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT4>(a, grid, st);
@@ -532,6 +561,7 @@ MoePromptArgs moe_prompt_args(const void* blobs, const woq_blob_header& h, size_
   for (int i = 0; i < 2; ++i) a.off_q[i] = p.off_q[i], a.off_zp[i] = p.off_zp[i];
   a.off_scale = p.off_scale, kind = p.kind;
   if (kind == MOE_W_TABLE) a.lut = moe_prompt_lut(h.weight_type);
+  a.e5m2 = h.weight_type == WOQ_W_FP8_E5M2;
   a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.tiles_n = h.Npad / WOQ_TILE_N;
   a.n_groups = h.n_groups, a.group = h.group, a.scale_type = (int)h.scale_type;
   return a;

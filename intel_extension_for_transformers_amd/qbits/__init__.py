@@ -420,7 +420,7 @@ def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_b
     hidden_states [T, H] fp32 / bf16 / fp16 with unit column stride; top_k_index [T, k] int64 or int32 (an id outside
     [0, E) drops its slot); top_k_weights [T, k]; gate_up_blobs / down_blobs uint8 [E, stride]: E WQH1 blobs each
     (K = H, N = 2I, gate columns first | K = I, N = H) as `quantize_to_packed_weight` writes them: int4 / int3 / int2,
-    nf4 / fp4_e2m1 / fp4_e2m1_bnb or int8 (fp8 and act-order blobs are refused). Four launches and no
+    nf4 / fp4_e2m1 / fp4_e2m1_bnb, int8 or fp8_e4m3 / fp8_e5m2 (act-order blobs are refused). Four launches and no
     host synchronisation, whatever the routing; deterministic. `out` [T, H] (allocated in hidden_states' type when None);
     `workspace`: a uint8 device tensor of `moe_workspace` bytes (this module keeps one of its own when None).
     `form`: "grouped" (at most 16 rows a workgroup on the exact int8 fixed point, up to MOE_MAX_SLOTS slots: decode and

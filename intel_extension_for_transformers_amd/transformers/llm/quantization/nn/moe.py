@@ -8,11 +8,12 @@ so HF's `*SparseMoeBlock` and its router stay as they are. Every expert's two ma
 [E, stride]. Two forms compute the same block:
   grouped  one `qbits.moe_forward` call (csrc/woq_moe.hip: plan, gate/up, down, combine — four launches, the routing never
            reaches the host), for T <= `grouped_max_tokens` (below `prompt_min_tokens`): int4 / int3 / int2, the 4-bit
-           table types (nf4, fp4_e2m1, fp4_e2m1_bnb: digit planes on the same int8 MFMA) and the int8 composite;
+           table types (nf4, fp4_e2m1, fp4_e2m1_bnb: digit planes on the same int8 MFMA), the int8 composite, and
+           fp8_e4m3 / fp8_e5m2 (the code bytes as the B operand of the fp8 MFMA, the activation as six base-16 digits);
   prompt   the same call with form="prompt" (csrc/woq_moe_prompt.hip: 128-row blocks of one expert on the fp16 MFMA, six
            launches) from `prompt_min_tokens` rows up, in row chunks of at most `qbits.MOE_PROMPT_MAX_SLOTS` slots;
   loop     HF's per-expert loop with each `F.linear` a `qbits.woq_linear` on the expert's slice of the blob tensor: above
-           that limit, and for the weight types the grouped kernels do not take (fp8).
+           that limit, and for shapes the grouped kernels do not take (`grouped_supported`).
 """
 import logging
 
@@ -26,7 +27,7 @@ logger = logging.getLogger(__name__)
 
 # what the decode engine's sparse layer takes (runtime/engine.py _sparse_mlp)
 _ENGINE_WEIGHT_TYPES = ("int4_clip", "int4", "int3_clip", "int2_clip")
-_GROUPED_WEIGHT_TYPES = _ENGINE_WEIGHT_TYPES + ("nf4", "fp4_e2m1", "fp4_e2m1_bnb", "int8")
+_GROUPED_WEIGHT_TYPES = _ENGINE_WEIGHT_TYPES + ("nf4", "fp4_e2m1", "fp4_e2m1_bnb", "int8", "fp8_e4m3", "fp8_e5m2")
 _KINDS = ("gate_up_proj", "down_proj")
 _warned_act = False
 
@@ -60,13 +61,16 @@ class QuantizedMoEExpertsQBits(torch.nn.Module):
     # The largest T of tools/moe_rate.py's {1, 4, 16, 64, 256} at which the grouped form is not slower than the loop form
     # at both measured shapes (Mixtral-8x7B and Qwen3-30B-A3B, int4 g128): profiles/r22_moe_rate.txt.
     # int8 and nf4 experts: below the loop form at T = 256 at both shapes too (profiles/r25_moe_wtypes.txt L15, L24, L33,
-    # L42), so one value serves every kind.
+    # L42), so one value serves every kind. fp8 experts inherit it: grouped is below the loop form at T = 1 and 16 at both
+    # shapes and is not called from prompt_min_tokens up (profiles/r26_moe_fp8.txt; fp8_e4m3 g128 only, e5m2 unmeasured).
     grouped_max_tokens = 256
     # From this many rows the prompt form serves the call: the smallest T of tools/moe_rate.py's {64, 128, ..., 4096} from
     # which its median is below that of the form that served the T before (grouped up to 256, loop above), at both
     # measured shapes and by more than either's min-to-median spread (profiles/r23_moe_prompt_rate.txt). Not measured below.
     # int8 and nf4 experts: the prompt form is below the loop form at T = 64 / 256 / 1024 and passes the grouped form between
     # 16 and 64 (profiles/r25_moe_wtypes.txt L14-16, L23-25, L32-34, L41-43); the same value.
+    # fp8_e4m3 experts: at T = 64 the prompt form is 3.2x / 2.2x below the grouped form and far below the loop, at T = 16
+    # grouped leads the loop (profiles/r26_moe_fp8.txt); the inherited value stands, unmeasured between 16 and 64.
     prompt_min_tokens = 64
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, compute_dtype="fp32", weight_dtype="int4_clip", bits=4,

@@ -1,5 +1,5 @@
 """What one routed expert block costs at the Mixtral-8x7B shape (H 4096, I 14336, E 8, k 2) and the Qwen3-30B-A3B shape
-(H 2048, I 768, E 128, k 8), g128 symmetric weights of `--weight` (int4 by default; int8, nf4, fp4_e2m1, fp4_e2m1_bnb),
+(H 2048, I 768, E 128, k 8), g128 symmetric weights of `--weight` (int4 by default; int8, nf4, fp4_e2m1, fp4_e2m1_bnb, fp8_e4m3, fp8_e5m2),
 fp16 activations, T in {1, 4, 16, 64, 128, 256, 512, 1024, 2048, 4096} or `--tokens`
 (a shape whose k admits no more than 8192 tokens in one prompt-form call also runs that T and one chunked T beyond it),
 uniform random routing (k distinct experts per token, softmax weights):
@@ -42,7 +42,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--inner", type=int, default=4)
     ap.add_argument("--routings", type=int, default=8)
-    ap.add_argument("--weight", default="int4_clip", choices=["int4_clip", "int8", "nf4", "fp4_e2m1", "fp4_e2m1_bnb"])
+    ap.add_argument("--weight", default="int4_clip", choices=["int4_clip", "int8", "nf4", "fp4_e2m1", "fp4_e2m1_bnb", "fp8_e4m3", "fp8_e5m2"])
     ap.add_argument("--tokens", default="", help="comma-separated T instead of the default ladder")
     ap.add_argument("--prompt-from", type=int, default=PROMPT_FROM)
     ap.add_argument("--no-hf", action="store_true")
@@ -81,7 +81,7 @@ def main():
         with torch.no_grad():
             hf.gate_up_proj.normal_(std=0.02, generator=gen)
             hf.down_proj.normal_(std=0.02, generator=gen)
-        mod = QuantizedMoEExpertsQBits(E, H, I, weight_dtype=args.weight, bits=8 if args.weight == "int8" else 4,
+        mod = QuantizedMoEExpertsQBits(E, H, I, weight_dtype=args.weight, bits=8 if args.weight in ("int8", "fp8_e4m3", "fp8_e5m2") else 4,
                                        scale_dtype="fp16", blocksize=128, device="cuda")
         mod.set_fp_weights(hf.gate_up_proj.data, hf.down_proj.data)
         blob_bytes = mod.gate_up_blobs.shape[1] + mod.down_blobs.shape[1]
