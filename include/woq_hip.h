@@ -229,6 +229,27 @@ WOQ_API int woq_moe_prompt_forward(const void* x_dev, int x_dtype, int ldx, cons
                                    const woq_blob_header* gate_up_hdr, size_t gate_up_stride, const void* down_blobs_dev,
                                    const woq_blob_header* down_hdr, size_t down_stride, void* out_dev, int out_dtype,
                                    int ldo, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Backward of the same block with respect to its rows and its routing weights, through the frozen experts
+ * (csrc/woq_moe_bwd.hip, DESIGN.md "Backward of the routed expert block"): from grad_out [T, ldg] (fp32 / bf16 / fp16) and
+ * the forward's inputs, grad_x [T, ldgx] (fp32 / bf16 / fp16, rounded once) = sum_j dx_(t, j), j ascending, and grad_w
+ * (fp32 [T, top_k] dense, may be null) = <grad_out_t, y_(t, j)>; a dropped slot adds zero and has grad_w = 0. Nothing of
+ * the forward is kept: g and u are recomputed by the prompt form's gate/up product. Both transposed products read the
+ * blobs as they lie (the dense backward's tile per 128-row block of one expert, fp16 operands on
+ * v_mfma_f32_16x16x32_f16, fp32 accumulation, the weight as fp16((q - zp) fp16(s 2^-E)) with one 2^E per blob kind over
+ * all experts). int4 / int3 / int2 and int8, sym and asym, nf4 / fp4_e2m1 / fp4_e2m1_bnb, every group size and both scale
+ * modes; fp8 and act-order blobs fail with a "QBits:" message, as does anything else woq_moe_prompt_forward refuses,
+ * launching nothing. Nine launches and one 8-byte memset whose shapes do not depend on the routing; stream-ordered, no
+ * host synchronisation, no allocation, no floating-point atomics: the same inputs give the same bytes. At most 65536
+ * routed slots and 65535 rows a call. woq_moe_backward_workspace: bytes of device scratch (256-byte aligned) one call
+ * takes — the plan tables, two fp16 images [T top_k + 128][hidden | 2 inter rounded up to 64] with their row scales and
+ * fp32 rows [T top_k][2 inter + inter + hidden]; never an image of a weight. 0 for a shape outside the limits. */
+WOQ_API size_t woq_moe_backward_workspace(int T, int top_k, int E, int hidden, int inter);
+WOQ_API int woq_moe_backward(const void* grad_out_dev, int grad_dtype, int ldg, const void* x_dev, int x_dtype, int ldx,
+                             const void* topk_idx_dev, int idx_is_int64, const float* topk_w_dev, int T, int top_k, int E,
+                             const void* gate_up_blobs_dev, const woq_blob_header* gate_up_hdr, size_t gate_up_stride,
+                             const void* down_blobs_dev, const woq_blob_header* down_hdr, size_t down_stride,
+                             void* grad_x_dev, int grad_x_dtype, int ldgx, float* grad_w_dev /* fp32 [T, k], may be null */,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* replaces qbits.dequantize_packed_weight (qbits.cpp:102-111): blob -> fp32 [K,N] or [N,K]. The
  * geometry is passed by value (hdr = host copy of the blob header) so the call never reads device

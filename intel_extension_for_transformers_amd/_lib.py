@@ -116,6 +116,7 @@ EXPORTS = [
     "woq_h2o_decode_scratch_bytes", "woq_h2o_score_decode", "woq_h2o_score_prompt", "woq_h2o_select", "woq_h2o_compact",
     "woq_moe_workspace", "woq_moe_forward", "woq_moe_prompt_workspace", "woq_moe_prompt_forward",
     "woq_moe_route_scratch_bytes", "woq_moe_route", "woq_engine_set_layer_moe",
+    "woq_moe_backward_workspace", "woq_moe_backward",
 ]
 # include/woq_hip_experimental.h: measurement hooks and lab switches, outside WOQ_ABI_VERSION
 EXPERIMENTAL_EXPORTS = [
@@ -183,6 +184,10 @@ def lib():
     L.woq_moe_prompt_workspace.restype = cs
     L.woq_moe_prompt_workspace.argtypes = L.woq_moe_workspace.argtypes
     L.woq_moe_prompt_forward.argtypes = L.woq_moe_forward.argtypes
+    L.woq_moe_backward_workspace.restype = cs
+    L.woq_moe_backward_workspace.argtypes = L.woq_moe_workspace.argtypes
+    L.woq_moe_backward.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, ci, ci, vp, ctypes.POINTER(BlobHeader), cs, vp,
+                                   ctypes.POINTER(BlobHeader), cs, vp, ci, ci, vp, vp, cs, vp]
     L.woq_moe_route_scratch_bytes.restype = cs
     L.woq_moe_route_scratch_bytes.argtypes = []
     L.woq_moe_route.argtypes = [vp, ci, vp, cf, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -321,6 +321,24 @@ constexpr int MOE_PROMPT_MAX_SLOTS = 65536;   // routed slots of one call: 64 pl
 // plan (count, scan, scatter), gate/up, down, combine: six launches shaped by (T, top_k, E, hidden, inter) alone;
 // `workspace` of woq_moe_prompt_workspace bytes
 int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st);
+// Its plan alone, for the backward (woq_moe_bwd.hip): the tables lie at the front of a workspace, in
+// moe_prompt_plan_bytes(T, top_k, E) bytes; blocks[0 .. *nblocks) cover the sorted positions [0, valid slots) without a
+// gap, in order; max_blocks sizes the grids (a workgroup past *nblocks returns). counts / nseg: the plan's own scratch.
+struct MoePromptPlan {
+  int32_t* sorted; int32_t* pos_of; MoeBlock* blocks; int32_t* nblocks; int32_t* counts;
+  int max_blocks, nseg;
+};
+size_t moe_prompt_plan_bytes(int T, int top_k, int E);
+MoePromptPlan moe_prompt_plan_tables(void* workspace, int T, int top_k, int E);
+// count, scan, scatter over the S = T * top_k ids: three launches
+void launch_moe_prompt_plan(const void* topk_idx, bool idx_is_int64, int S, int E, const MoePromptPlan& p, hipStream_t st);
+// the gate/up product over a plan with the raw epilogue: gu[sorted slot][2 I] fp32 = [g | u], no SiLU (m: x, the
+// gate/up blobs and the down header for I; fp8 blobs are refused)
+int launch_moe_prompt_gate_up_raw(const MoeCall& m, const MoePromptPlan& p, float* gu, hipStream_t st);
+
+// ---- woq_moe_bwd.hip: backward of the routed expert block with respect to its rows and its routing weights ---------
+// rows of one call: what woq_moe_backward takes (the plan's limit)
+constexpr int MOE_BACKWARD_MAX_SLOTS = MOE_PROMPT_MAX_SLOTS;
 
 // ---- woq_moe_route.hip: the router of a sparse layer -----------------------------------------------------------------
 // include/woq_hip_experimental.h woq_moe_route, which this is: checks (a "QBits:" message, nothing launched), then

@@ -208,8 +208,11 @@ __device__ __forceinline__ h8 moe_prompt_fp8(uint32_t hi, uint32_t lo, _Float16 
 //   MOE_W_FP8    the exact fp16 value of the code byte of the two planes' words (moe_prompt_fp8); MP_W_FP8_E5M2 its e5m2 form
 // either times the relative scale under scale_mode 1, as the int4 operand is.
 constexpr int MP_W_FP8_E5M2 = MOE_W_FP8 + 1;
-template <bool GU, int SMODE, bool ASYM, int WK>
+// RAW (the backward's recompute, gate/up only): the epilogue stores the fp32 g and u themselves, row [g (I) | u (I)] of
+// [sorted slot][ldo = 2 I], instead of SiLU(g) * u
+template <bool GU, int SMODE, bool ASYM, int WK, bool RAW = false>
 __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const MoePromptArgs a) {
+  static_assert(GU || !RAW, "the raw epilogue belongs to the gate/up launch");
   constexpr int NS = SMODE == 1 ? 2 : 1;  // scales of a tile, column and lane: its 32-k block of either 64-k half
   constexpr bool FP8 = WK == MOE_W_FP8 || WK == MP_W_FP8_E5M2;
   constexpr int NP = WK == MOE_W_INT8 || FP8 ? 2 : 1;
@@ -476,7 +479,11 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
       float* orow = a.out + (size_t)(first + row) * a.ldo;
       if constexpr (GU) {
         const float g = acc[rt][0][j], u = acc[rt][1][j];
-        if (live[0]) orow[wt * 16 + i16] = g / (1.0f + expf(-g)) * u;  // wt < half_tiles: a column inside I
+        if constexpr (RAW) {
+          if (live[0]) orow[wt * 16 + i16] = g, orow[(a.half_tiles + wt) * 16 + i16] = u;
+        } else {
+          if (live[0]) orow[wt * 16 + i16] = g / (1.0f + expf(-g)) * u;  // wt < half_tiles: a column inside I
+        }
       } else {
 #pragma unroll
         for (int c = 0; c < MP_CT; ++c) {
@@ -488,7 +495,7 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
   }
 }
 
-struct MoePromptWorkspace {
+struct MoePromptWorkspace {  // the plan tables first: moe_prompt_plan_tables relies on it
   size_t sorted, pos_of, blocks, nblocks, counts, h, y, total;
   int max_blocks, nseg;
 };
@@ -513,28 +520,33 @@ bool moe_prompt_shape_ok(int T, int top_k, int E, int hidden, int inter) {
          (long long)T * top_k <= MOE_PROMPT_MAX_SLOTS;
 }
 
-template <bool GU, int SMODE, bool ASYM, int WK>
+template <bool GU, int SMODE, bool ASYM, int WK, bool RAW>
 int moe_prompt_launch_one(const MoePromptArgs& a, dim3 grid, hipStream_t st) {
-  if (const int rc = allow_dynamic_lds<moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK>>(MP_LDS)) return rc;
-  hipLaunchKernelGGL((moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK>), grid, dim3(MP_WAVES * 64), MP_LDS, st, a);
+  if (const int rc = allow_dynamic_lds<moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK, RAW>>(MP_LDS)) return rc;
+  hipLaunchKernelGGL((moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK, RAW>), grid, dim3(MP_WAVES * 64), MP_LDS, st, a);
   return 0;
 }
-template <bool GU, int SMODE, bool ASYM>
+template <bool GU, int SMODE, bool ASYM, bool RAW>
 int moe_prompt_launch_kind(const MoePromptArgs& a, MoeWeightKind kind, dim3 grid, hipStream_t st) {
-  if (kind == MOE_W_INT8) return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT8>(a, grid, st);
+  if (kind == MOE_W_INT8) return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT8, RAW>(a, grid, st);
   if constexpr (!ASYM) {  // moe_header_problem admits no table or fp8 blob with zero points
-    if (kind == MOE_W_FP8)
-      return a.e5m2 ? moe_prompt_launch_one<GU, SMODE, false, MP_W_FP8_E5M2>(a, grid, st)
-                    : moe_prompt_launch_one<GU, SMODE, false, MOE_W_FP8>(a, grid, st);
-    if (kind == MOE_W_TABLE) return moe_prompt_launch_one<GU, SMODE, false, MOE_W_TABLE>(a, grid, st);
+    if constexpr (!RAW) {  // the backward has no fused fp8 arm (woq_moe_backward refuses fp8 blobs)
+      if (kind == MOE_W_FP8)
+        return a.e5m2 ? moe_prompt_launch_one<GU, SMODE, false, MP_W_FP8_E5M2, false>(a, grid, st)
+                      : moe_prompt_launch_one<GU, SMODE, false, MOE_W_FP8, false>(a, grid, st);
+    }
+    if (kind == MOE_W_TABLE) return moe_prompt_launch_one<GU, SMODE, false, MOE_W_TABLE, RAW>(a, grid, st);
   }
-  return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT4>(a, grid, st);
+  if (RAW && kind == MOE_W_FP8) return fail("QBits: the raw gate/up product is not built for fp8 expert blobs");
+  return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT4, RAW>(a, grid, st);
 }
-template <bool GU>
+template <bool GU, bool RAW = false>
 int moe_prompt_launch_gemm(const MoePromptArgs& a, bool smode1, bool asym, MoeWeightKind kind, dim3 grid, hipStream_t st) {
   if (!smode1)
-    return asym ? moe_prompt_launch_kind<GU, 0, true>(a, kind, grid, st) : moe_prompt_launch_kind<GU, 0, false>(a, kind, grid, st);
-  return asym ? moe_prompt_launch_kind<GU, 1, true>(a, kind, grid, st) : moe_prompt_launch_kind<GU, 1, false>(a, kind, grid, st);
+    return asym ? moe_prompt_launch_kind<GU, 0, true, RAW>(a, kind, grid, st)
+                : moe_prompt_launch_kind<GU, 0, false, RAW>(a, kind, grid, st);
+  return asym ? moe_prompt_launch_kind<GU, 1, true, RAW>(a, kind, grid, st)
+              : moe_prompt_launch_kind<GU, 1, false, RAW>(a, kind, grid, st);
 }
 
 // the fp16 table of a table weight type as two byte planes (what lut_quad looks up): d[0][c / 4] byte c % 4 = the low
@@ -567,47 +579,67 @@ MoePromptArgs moe_prompt_args(const void* blobs, const woq_blob_header& h, size_
   return a;
 }
 
+// the gate/up launch over a plan; RAW: `out` receives [g | u] rows of 2 I, else SiLU(g) * u rows of I
+template <bool RAW>
+int moe_prompt_gate_up(const MoeCall& m, const MoePromptPlan& p, float* out, hipStream_t st) {
+  const woq_blob_header& gh = *m.gate_up_hdr;
+  const int I = m.down_hdr->K;
+  MoeWeightKind g_kind;
+  MoePromptArgs g = moe_prompt_args(m.gate_up_blobs, gh, m.gate_up_stride, g_kind);
+  g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
+  g.sorted = p.sorted, g.blocks = p.blocks, g.nblocks = p.nblocks;
+  g.out = out, g.ldo = RAW ? 2 * I : I, g.half_tiles = I / 16;
+  const unsigned gx = (unsigned)((I / 16 + MP_WAVES - 1) / MP_WAVES);
+  return moe_prompt_launch_gemm<true, RAW>(g, gh.scale_mode == 1, gh.off_zp != 0, g_kind,
+                                           dim3(gx, (unsigned)p.max_blocks), st);
+}
+
 }  // namespace
 
+size_t moe_prompt_plan_bytes(int T, int top_k, int E) { return moe_prompt_ws(T, top_k, E, 0, 0).h; }
+
+MoePromptPlan moe_prompt_plan_tables(void* workspace, int T, int top_k, int E) {
+  const MoePromptWorkspace w = moe_prompt_ws(T, top_k, E, 0, 0);
+  uint8_t* ws = (uint8_t*)workspace;
+  return MoePromptPlan{(int32_t*)(ws + w.sorted), (int32_t*)(ws + w.pos_of), (MoeBlock*)(ws + w.blocks),
+                       (int32_t*)(ws + w.nblocks), (int32_t*)(ws + w.counts), w.max_blocks, w.nseg};
+}
+
+void launch_moe_prompt_plan(const void* topk_idx, bool idx_is_int64, int S, int E, const MoePromptPlan& p, hipStream_t st) {
+  const dim3 pgrid((unsigned)p.nseg), pblock(MP_SEG);
+  if (idx_is_int64)
+    hipLaunchKernelGGL(moe_prompt_count_kernel<true>, pgrid, pblock, 0, st, topk_idx, S, E, p.counts, p.pos_of);
+  else
+    hipLaunchKernelGGL(moe_prompt_count_kernel<false>, pgrid, pblock, 0, st, topk_idx, S, E, p.counts, p.pos_of);
+  hipLaunchKernelGGL(moe_prompt_scan_kernel, dim3(1), pblock, 0, st, p.nseg, E, p.counts, p.blocks, p.nblocks);
+  if (idx_is_int64)
+    hipLaunchKernelGGL(moe_prompt_scatter_kernel<true>, pgrid, pblock, 0, st, topk_idx, S, E, p.counts, p.sorted, p.pos_of);
+  else
+    hipLaunchKernelGGL(moe_prompt_scatter_kernel<false>, pgrid, pblock, 0, st, topk_idx, S, E, p.counts, p.sorted, p.pos_of);
+}
+
+int launch_moe_prompt_gate_up_raw(const MoeCall& m, const MoePromptPlan& p, float* gu, hipStream_t st) {
+  return moe_prompt_gate_up<true>(m, p, gu, st);
+}
+
 int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st) {
-  const woq_blob_header& gh = *m.gate_up_hdr;
   const woq_blob_header& dh = *m.down_hdr;
   const int H = dh.N, I = dh.K;
   const MoePromptWorkspace w = moe_prompt_ws(m.T, m.top_k, m.E, H, I);
   uint8_t* ws = (uint8_t*)m.workspace;
-  int32_t* sorted = (int32_t*)(ws + w.sorted);
-  int32_t* pos_of = (int32_t*)(ws + w.pos_of);
-  MoeBlock* blocks = (MoeBlock*)(ws + w.blocks);
-  int32_t* nblocks = (int32_t*)(ws + w.nblocks);
-  int32_t* counts = (int32_t*)(ws + w.counts);
+  const MoePromptPlan plan = moe_prompt_plan_tables(ws, m.T, m.top_k, m.E);
+  const int32_t* pos_of = plan.pos_of;
   float* hbuf = (float*)(ws + w.h);
   float* ybuf = (float*)(ws + w.y);
-  const int S = m.T * m.top_k;
 
-  const dim3 pgrid((unsigned)w.nseg), pblock(MP_SEG);
-  if (m.idx_is_int64)
-    hipLaunchKernelGGL(moe_prompt_count_kernel<true>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, pos_of);
-  else
-    hipLaunchKernelGGL(moe_prompt_count_kernel<false>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, pos_of);
-  hipLaunchKernelGGL(moe_prompt_scan_kernel, dim3(1), pblock, 0, st, w.nseg, m.E, counts, blocks, nblocks);
-  if (m.idx_is_int64)
-    hipLaunchKernelGGL(moe_prompt_scatter_kernel<true>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, sorted, pos_of);
-  else
-    hipLaunchKernelGGL(moe_prompt_scatter_kernel<false>, pgrid, pblock, 0, st, m.topk_idx, S, m.E, counts, sorted, pos_of);
+  launch_moe_prompt_plan(m.topk_idx, m.idx_is_int64, m.T * m.top_k, m.E, plan, st);
 
-  MoeWeightKind g_kind, d_kind;
-  MoePromptArgs g = moe_prompt_args(m.gate_up_blobs, gh, m.gate_up_stride, g_kind);
-  g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
-  g.sorted = sorted, g.blocks = blocks, g.nblocks = nblocks;
-  g.out = hbuf, g.ldo = I, g.half_tiles = I / 16;
-  const unsigned gx = (unsigned)((I / 16 + MP_WAVES - 1) / MP_WAVES);
-  if (const int rc = moe_prompt_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, g_kind,
-                                                  dim3(gx, (unsigned)w.max_blocks), st))
-    return rc;
+  if (const int rc = moe_prompt_gate_up<false>(m, plan, hbuf, st)) return rc;
 
+  MoeWeightKind d_kind;
   MoePromptArgs d = moe_prompt_args(m.down_blobs, dh, m.down_stride, d_kind);
   d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
-  d.sorted = sorted, d.blocks = blocks, d.nblocks = nblocks;
+  d.sorted = plan.sorted, d.blocks = plan.blocks, d.nblocks = plan.nblocks;
   d.out = ybuf, d.ldo = H, d.half_tiles = 0;
   const unsigned dx = (unsigned)((d.tiles_n + MP_WAVES * MP_CT - 1) / (MP_WAVES * MP_CT));
   if (const int rc = moe_prompt_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, d_kind,

@@ -18,6 +18,7 @@ __all__ = [
     "check_isa_supported", "check_torch_compatibility", "rmsnorm", "rope", "silu_mul", "gelu", "gptq_sweep",
     "awq_scale_delta", "awq_clip_search", "autoround_forward", "autoround_step", "autoround_codes",
     "teq_forward", "teq_grad", "woq_linear_backward", "woq_linear_backward_workspace", "moe_forward", "moe_workspace", "MOE_PROMPT_MAX_SLOTS",
+    "moe_backward", "moe_backward_workspace", "MOE_BACKWARD_CHUNK_TOKENS",
 ]
 
 
@@ -475,6 +476,87 @@ def moe_forward(hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_b
                L.torch_dtype_code(out.dtype), ldo, _ptr(ws),
                0 if ws is None else ws.numel() * ws.element_size(), L.stream_ptr()))
     return out
+
+
+# Tokens of one woq_moe_backward call: longer calls go in chunks of whole tokens. The scratch of a chunk is about
+# top_k * (6 H + 16 I) bytes a token (two fp16 images, gu, dh' and dx in fp32): 508 KB at the Mixtral-8x7B expert shape
+# (H 4096, I 14336, top_k 2), so 529 MB for a full chunk there (woq_moe_backward_workspace(1024, 2, 8, 4096, 14336)), and
+# 202 MB at the Qwen3-30B-A3B shape (H 2048, I 768, top_k 8, E 128). csrc/woq_moe_bwd.hip.
+MOE_BACKWARD_CHUNK_TOKENS = 1024
+_moe_bwd_scratch = None  # moe_backward's own scratch, grown on demand: a steady training loop allocates nothing
+
+
+def moe_backward_workspace(t, top_k, e, hidden, inter):
+    """Bytes of scratch one `woq_moe_backward` call of `t` rows takes (woq_moe_backward_workspace, include/woq_hip.h);
+    0 = a shape it refuses."""
+    return int(L.lib().woq_moe_backward_workspace(int(t), int(top_k), int(e), int(hidden), int(inter)))
+
+
+def moe_backward(grad_out, hidden_states, top_k_index, top_k_weights, gate_up_blobs, down_blobs, grad_hidden=None,
+                 workspace=None):
+    """-> (grad_hidden [T, H], grad_weights fp32 [T, k]): the backward of `moe_forward` with respect to hidden_states and
+    top_k_weights through the frozen experts (woq_moe_backward, csrc/woq_moe_bwd.hip). grad_out and hidden_states [T, H]
+    fp32 / bf16 / fp16 device tensors with unit column stride; the routing and the blobs as `moe_forward` takes them, int4 /
+    int3 / int2, int8, nf4 / fp4 (fp8 and act-order blobs raise). Nothing of the forward is needed: g and u are recomputed.
+    grad_hidden is allocated in hidden_states' type when None; a dropped slot adds nothing to it and has grad_weights 0.
+    Deterministic. Calls of more than MOE_BACKWARD_CHUNK_TOKENS rows go in chunks of whole tokens (rows are independent,
+    so chunking is exact). `workspace`: a uint8 device tensor of `moe_backward_workspace` bytes for a chunk (this module
+    keeps one of its own when None)."""
+    global _moe_bwd_scratch
+    gh, dh = header_of(gate_up_blobs), header_of(down_blobs)
+    hidden, x, g = dh.N, hidden_states, grad_out
+    for name, v in (("grad_out", g), ("hidden_states", x)):
+        if not (v.is_cuda and v.device == gate_up_blobs.device == down_blobs.device):
+            raise RuntimeError("QBits: moe_backward: %s must be on the expert blobs' HIP device" % name)
+        if v.dtype not in _FAKE_QUANT_DTYPES:
+            raise RuntimeError("QBits: moe_backward takes %s in fp32 / bf16 / fp16, got %s" % (name, v.dtype))
+        if not (_rows_ok(v, hidden) and v.shape[0] == x.shape[0]):
+            raise RuntimeError("QBits: moe_backward takes %s [T, H=%d] with unit column stride, got shape %s stride %s"
+                               % (name, hidden, tuple(v.shape), tuple(v.stride())))
+    t = x.shape[0]
+    for b in (gate_up_blobs, down_blobs):
+        if not (b.dim() == 2 and b.is_contiguous() and b.element_size() == 1 and b.shape[0] == gate_up_blobs.shape[0]):
+            raise RuntimeError("QBits: moe_backward takes contiguous one-byte expert blob tensors [E, stride]")
+    idx = top_k_index
+    if idx.dim() != 2 or idx.shape[0] != t or idx.dtype not in (torch.int64, torch.int32) or idx.device != x.device:
+        raise RuntimeError("QBits: moe_backward takes top_k_index [T, k] int64 / int32 on the device")
+    idx = idx.contiguous()
+    k = idx.shape[1]
+    w = top_k_weights
+    if tuple(w.shape) != (t, k) or w.device != x.device or w.dtype not in _FAKE_QUANT_DTYPES:
+        raise RuntimeError("QBits: moe_backward takes top_k_weights [T, k] fp32 / bf16 / fp16 on the device")
+    w = w.detach().float().contiguous()
+    if grad_hidden is None:
+        grad_hidden = torch.empty(t, hidden, dtype=x.dtype, device=x.device)
+    if not (grad_hidden.is_cuda and grad_hidden.device == x.device and grad_hidden.dtype in _FAKE_QUANT_DTYPES
+            and _rows_ok(grad_hidden, hidden) and grad_hidden.shape[0] == t):
+        raise RuntimeError("QBits: moe_backward: grad_hidden must be a device tensor [T, H] fp32 / bf16 / fp16 with unit "
+                           "column stride")
+    # not cleared: moe_bwd_act_kernel writes every slot, a routed one through sorted[], a dropped one by its own index
+    grad_w = torch.empty(t, k, dtype=torch.float32, device=x.device)
+    if t == 0:
+        return grad_hidden, grad_w
+    e_n = gate_up_blobs.shape[0]
+    chunk = max(1, min(MOE_BACKWARD_CHUNK_TOKENS, MOE_PROMPT_MAX_SLOTS // k))
+    ws = workspace
+    if ws is None:
+        need = moe_backward_workspace(min(t, chunk), k, e_n, dh.N, dh.K)
+        if need and (_moe_bwd_scratch is None or _moe_bwd_scratch.numel() < need or _moe_bwd_scratch.device != x.device):
+            _moe_bwd_scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = _moe_bwd_scratch
+    elif not (ws.is_cuda and ws.device == x.device and ws.is_contiguous()):
+        raise RuntimeError("QBits: moe_backward: the workspace must be a contiguous tensor on the device")
+    ld = lambda v: v.stride(0) if v.shape[0] > 1 else max(v.stride(0), hidden)  # noqa: E731
+    for r in range(0, t, chunk):
+        s = slice(r, min(r + chunk, t))
+        gc, xc, oc = g[s], x[s], grad_hidden[s]
+        L.check(L.lib().woq_moe_backward(
+            _ptr(gc), L.torch_dtype_code(g.dtype), ld(gc), _ptr(xc), L.torch_dtype_code(x.dtype), ld(xc), _ptr(idx[s]),
+            int(idx.dtype == torch.int64), _ptr(w[s]), s.stop - r, k, e_n, _ptr(gate_up_blobs), ctypes.byref(gh),
+            gate_up_blobs.stride(0), _ptr(down_blobs), ctypes.byref(dh), down_blobs.stride(0), _ptr(oc),
+            L.torch_dtype_code(grad_hidden.dtype), ld(oc), _ptr(grad_w[s]), _ptr(ws),
+            0 if ws is None else ws.numel() * ws.element_size(), L.stream_ptr()))
+    return grad_hidden, grad_w
 
 
 def moe_route(x, router_w, top_k, renorm, norm_w=None, eps=0.0, plan=False):

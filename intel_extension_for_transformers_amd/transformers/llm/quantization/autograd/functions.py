@@ -14,6 +14,9 @@ names (intel_extension_for_transformers/transformers/llm/quantization/autograd/f
     blob as it lies (csrc/woq_linear_bwd.hip) where the reference dequantises the whole weight (:163-179). Under
     `QBITS_DEBUG`, and for fp8 weights (not built in the fused kernel), the backward is the reference's own statement.
     No gradient reaches the blob: the weights are frozen, as in QLoRA.
+  * `MoEExpertsKBit` (no reference counterpart): the same for `QuantizedMoEExpertsQBits`, the backward through the
+    frozen experts to hidden_states and top_k_weights by `qbits.moe_backward` (csrc/woq_moe_bwd.hip);
+    `moe_experts_ref_impl` is its dequantise-and-torch arm (fp8 experts, `QBITS_DEBUG`).
 """
 import os
 from enum import Enum
@@ -148,3 +151,57 @@ class MatMulKBit(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             grad_bias = grad_output.sum(0)
         return grad_a, None, None, grad_bias, None, None, None, None
+
+
+def moe_experts_ref_impl(experts, hidden_states, top_k_index, top_k_weights):
+    """The routed expert block as torch ops under autograd over per-expert `dequantize_packed_weight` (HF's
+    MixtralExperts.forward; an id outside [0, E) drops its slot): the arm of fp8 experts, of shapes
+    `grouped_supported()` refuses and of `QBITS_DEBUG`. Materialises K * N * 4 bytes per expert and kind it visits."""
+    e_n, inter = experts.num_experts, experts.intermediate_dim
+    x = hidden_states.float()
+    final = torch.zeros_like(x)
+    views = {kind: experts._expert_views(kind) for kind in ("gate_up_proj", "down_proj")}
+
+    def deq(kind, e, k, n):
+        w = torch.empty(k, n, dtype=torch.float32, device=x.device)
+        qbits.dequantize_packed_weight(views[kind][e], w, False, experts.compute_dtype, experts.weight_dtype,
+                                       experts.scale_dtype)
+        return w
+
+    for e in range(e_n):
+        token_idx, top_k_pos = torch.where(top_k_index == e)
+        if token_idx.numel() == 0:
+            continue
+        gate, up = (x[token_idx] @ deq("gate_up_proj", e, experts.hidden_dim, 2 * inter)).chunk(2, dim=-1)
+        cur = (torch.nn.functional.silu(gate) * up) @ deq("down_proj", e, inter, experts.hidden_dim)
+        final = final.index_add(0, token_idx, cur * top_k_weights[token_idx, top_k_pos, None].float())
+    return final.to(hidden_states.dtype)
+
+
+class MoEExpertsKBit(torch.autograd.Function):
+    """`QuantizedMoEExpertsQBits.forward` with a backward: out = the module's inference dispatch (grouped, prompt or loop
+    form, the same launches and bytes), saving hidden_states, top_k_index and top_k_weights and nothing of the block's
+    inside; backward -> (None, dX in hidden_states' dtype, None, dw in top_k_weights' dtype), each only if needed, from
+    one `qbits.moe_backward` (csrc/woq_moe_bwd.hip), which recomputes g and u. No gradient reaches the blobs."""
+
+    @staticmethod
+    def forward(ctx, experts, hidden_states, top_k_index, top_k_weights):
+        ctx.experts = experts
+        ctx.save_for_backward(hidden_states, top_k_index, top_k_weights)
+        return experts.inference_forward(hidden_states, top_k_index, top_k_weights)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        x, idx, w = ctx.saved_tensors
+        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[3]):
+            return None, None, None, None
+        fp = (torch.float32, torch.bfloat16, torch.float16)
+        g = grad_output if grad_output.dtype in fp else grad_output.float()
+        if g.stride(1) != 1 or (g.shape[0] > 1 and g.stride(0) < g.shape[1]):
+            g = g.contiguous()
+        xs = x if x.dtype in fp else x.float()
+        if xs.stride(1) != 1 or (xs.shape[0] > 1 and xs.stride(0) < xs.shape[1]):
+            xs = xs.contiguous()
+        gx, gw = qbits.moe_backward(g, xs, idx, w if w.dtype in fp else w.float(), ctx.experts.gate_up_blobs, ctx.experts.down_blobs)
+        return (None, gx.to(x.dtype) if ctx.needs_input_grad[1] else None, None,
+                gw.to(w.dtype) if ctx.needs_input_grad[3] else None)

@@ -14,12 +14,15 @@ so HF's `*SparseMoeBlock` and its router stay as they are. Every expert's two ma
            launches) from `prompt_min_tokens` rows up, in row chunks of at most `qbits.MOE_PROMPT_MAX_SLOTS` slots;
   loop     HF's per-expert loop with each `F.linear` a `qbits.woq_linear` on the expert's slice of the blob tensor: above
            that limit, and for shapes the grouped kernels do not take (`grouped_supported`).
+A `hidden_states` or `top_k_weights` that requires grad takes the training form: the same forward under
+`autograd.MoEExpertsKBit`, whose backward is one `qbits.moe_backward` (csrc/woq_moe_bwd.hip) through the frozen experts.
 """
 import logging
 
 import torch
 
 from ..... import qbits
+from ..autograd import MoEExpertsKBit, moe_experts_ref_impl, qbits_debug_enabled
 from ..calibration import is_moe_experts  # noqa: F401  (the walker's test, re-exported beside the module it selects)
 from .modules import QuantizedLinearQBits
 
@@ -89,6 +92,19 @@ class QuantizedMoEExpertsQBits(torch.nn.Module):
                 and self.hidden_dim % 4 == 0 and self.num_experts <= qbits.MOE_MAX_EXPERTS)
 
     def forward(self, hidden_states, top_k_index, top_k_weights):
+        """An input that asks for a gradient (in grad mode, hidden_states or top_k_weights requiring grad: the rule of
+        QuantizedLinearQBits.forward) takes the training form, the same forward with a backward through the frozen
+        experts: `MoEExpertsKBit` (qbits.moe_backward), or torch ops over dequantised experts for fp8 experts, shapes
+        `grouped_supported()` refuses and under QBITS_DEBUG. Every other call is `inference_forward`."""
+        if torch.is_grad_enabled() and (hidden_states.requires_grad or top_k_weights.requires_grad):
+            if self.gate_up_blobs.numel() == 0:
+                raise RuntimeError("QBits: QuantizedMoEExpertsQBits has no packed weights (call set_fp_weights first)")
+            if qbits_debug_enabled() or self.weight_dtype.startswith("fp8") or not self.grouped_supported():
+                return moe_experts_ref_impl(self, hidden_states, top_k_index, top_k_weights)
+            return MoEExpertsKBit.apply(self, hidden_states, top_k_index, top_k_weights)
+        return self.inference_forward(hidden_states, top_k_index, top_k_weights)
+
+    def inference_forward(self, hidden_states, top_k_index, top_k_weights):
         if self.gate_up_blobs.numel() == 0:
             raise RuntimeError("QBits: QuantizedMoEExpertsQBits has no packed weights (call set_fp_weights first)")
         t, k = hidden_states.shape[0], top_k_index.shape[-1]
