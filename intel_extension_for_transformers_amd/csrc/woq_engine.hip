@@ -440,7 +440,7 @@ static MoeCall engine_moe_call(const woq_engine* e, int l, int T, const float* x
 static int engine_moe_block(woq_engine* e, int l, hipStream_t st) {
   const woq_engine_config& c = e->cfg;
   const EngineMoe& m = e->layers[l].moe;
-  const MoeRoutePlan plan = moe_plan_tables(e->moe_ws, 1, m.top_k, m.E);
+  const MoeRoutePlan plan = moe_plan_tables(MOE_GROUPED, e->moe_ws, 1, m.top_k, m.E);
   int rc = launch_moe_route(e->hidden, c.hidden, e->layers[l].ln2, c.rms_eps, m.router, m.router_dtype, 1, c.hidden, m.E,
                             m.top_k, m.renorm, e->moe_xn, e->moe_idx, e->moe_w, e->moe_scratch, plan, st);
   if (rc) return rc;
@@ -449,7 +449,7 @@ static int engine_moe_block(woq_engine* e, int l, hipStream_t st) {
                            emit ? e->ssq_part : nullptr};
   MoeCall call = engine_moe_call(e, l, 1, e->moe_xn, e->moe_idx, e->moe_w, e->moe_ws, &res);
   call.plan_ready = true;
-  return launch_moe_forward(call, st);
+  return launch_moe_forward(call, MOE_GROUPED, st);
 }
 
 static int engine_mlp_block(woq_engine* e, int l, hipStream_t st) {
@@ -619,10 +619,12 @@ static int engine_prefill_reserve_lora(woq_engine* e, size_t rows) {
   return 0;
 }
 
+// the form a sparse layer's prompt pass over M rows takes
+static MoeForm engine_moe_form(int M) { return M < MOE_PROMPT_MIN_ROWS ? MOE_GROUPED : MOE_PROMPT; }
 // rows of one expert call of a sparse layer's prompt pass: all of them in the grouped form (below MOE_PROMPT_MIN_ROWS
 // rows its slot limit is never reached), whole tokens within the prompt form's slot limit otherwise
 static int engine_moe_chunk_rows(int M, int top_k) {
-  return M < MOE_PROMPT_MIN_ROWS ? M : std::min(M, std::max(1, MOE_PROMPT_MAX_SLOTS / top_k));
+  return engine_moe_form(M) == MOE_GROUPED ? M : std::min(M, std::max(1, MOE_PROMPT_MAX_SLOTS / top_k));
 }
 
 // the sparse layers' share of the prompt pass's buffers: xn, ids and weights of `rows` rows and the largest call's workspace
@@ -632,8 +634,7 @@ static int engine_prefill_reserve_moe(woq_engine* e, size_t rows) {
   for (const EngineLayer& w : e->layers) {
     if (!w.moe.on) continue;
     const int chunk = engine_moe_chunk_rows((int)rows, w.moe.top_k);
-    ws = std::max(ws, (int)rows < MOE_PROMPT_MIN_ROWS ? woq_moe_workspace(chunk, w.moe.top_k, w.moe.E, c.hidden, w.moe.inter)
-                                                      : woq_moe_prompt_workspace(chunk, w.moe.top_k, w.moe.E, c.hidden, w.moe.inter));
+    ws = std::max(ws, moe_workspace_bytes(engine_moe_form((int)rows), chunk, w.moe.top_k, w.moe.E, c.hidden, w.moe.inter));
   }
   if (rows <= e->pf_moe_rows && ws <= e->pf_moe_ws_bytes) return 0;
   WOQ_HIP(hipDeviceSynchronize());
@@ -666,7 +667,7 @@ static int engine_prefill_moe(woq_engine* e, int l, int M, hipStream_t st) {
     const MoeCall call = engine_moe_call(e, l, rows, e->pf_moe_xn + (size_t)r0 * c.hidden,
                                          e->pf_moe_idx + (size_t)r0 * m.top_k, e->pf_moe_w + (size_t)r0 * m.top_k,
                                          e->pf_moe_ws, &res);
-    rc = M < MOE_PROMPT_MIN_ROWS ? launch_moe_forward(call, st) : launch_moe_prompt_forward(call, st);
+    rc = launch_moe_forward(call, engine_moe_form(M), st);
     if (rc) return rc;
   }
   return 0;

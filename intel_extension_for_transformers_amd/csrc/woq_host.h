@@ -265,12 +265,21 @@ int launch_h2o_compact(void* kseq, void* vseq, float* score, const int32_t* dst,
                        int D, int max_ctx, const float* cs, const float* sn, int n_keep, int n_discard, int n_cached,
                        hipStream_t st);
 
-// ---- woq_moe.hip: the routed expert block of a sparse mixture-of-experts layer --------------------------------------
-constexpr int MOE_BLOCK_ROWS = 16;      // rows of one block of the plan's table: four MFMA row sets of four tokens
-constexpr int MOE_MAX_EXPERTS = 1024;   // the plan's histogram lives in LDS
-constexpr int MOE_MAX_SLOTS = 8192;     // routed slots T * top_k of one call: the plan keeps their ids in LDS
-// One call (include/woq_hip.h woq_moe_forward, which checks all of it): E blobs of each kind at a uniform stride under
-// one header, the routing on the device, `workspace` of woq_moe_workspace bytes.
+// ---- woq_moe.hip, woq_moe_prompt.hip: the routed expert block of a sparse mixture-of-experts layer, in two forms -------
+// MOE_GROUPED (woq_moe.hip): few rows per expert, table blocks of 16 rows, on the int8 / fp8 MFMA: decode and short
+// prompts. MOE_PROMPT (woq_moe_prompt.hip): many rows per expert, blocks of 128 rows, on the fp16 MFMA.
+enum MoeForm { MOE_GROUPED = 0, MOE_PROMPT = 1 };
+constexpr int MOE_BLOCK_ROWS = 16;      // rows of one block of the grouped plan's table: four MFMA row sets of four tokens
+constexpr int MOE_PROMPT_ROWS = 128;    // rows of one block of the prompt plan's table: the row tile of its product
+constexpr int MOE_MAX_EXPERTS = 1024;   // the plans' histograms live in LDS
+constexpr int MOE_MAX_SLOTS = 8192;     // routed slots T * top_k of one grouped call: the plan keeps their ids in LDS
+constexpr int MOE_PLAN_SEG = 1024;      // slots of one segment of the prompt plan = threads of a plan workgroup
+constexpr int MOE_PROMPT_MAX_SLOTS = 65536;   // routed slots of one prompt call: 64 plan segments
+constexpr int moe_max_slots(MoeForm form) { return form == MOE_PROMPT ? MOE_PROMPT_MAX_SLOTS : MOE_MAX_SLOTS; }
+// rows of the module's `prompt_min_tokens`: from this many rows the engine's prompt pass takes the prompt form
+constexpr int MOE_PROMPT_MIN_ROWS = 64;
+// One call (include/woq_hip.h woq_moe_forward / woq_moe_prompt_forward, which check all of it): E blobs of each kind at
+// a uniform stride under one header, the routing on the device, `workspace` of moe_workspace_bytes(form, ..) bytes.
 struct MoeCall {
   const void* x; int x_dtype, ldx;
   const void* topk_idx; bool idx_is_int64; const float* topk_w;
@@ -285,7 +294,7 @@ struct MoeCall {
   bool plan_ready = false;
   const struct MoeResidual* residual = nullptr;
 };
-// null when the grouped launches take expert blobs under this header at this stride, else the "QBits: ..." reason.
+// null when the products take expert blobs under this header at this stride, else the "QBits: ..." reason.
 // `int4_only` (the decode engine's sparse layer) also refuses the table types, the int8 composite and the fp8 types,
 // which woq_moe_forward / woq_moe_prompt_forward take.
 const char* moe_header_problem(const woq_blob_header& h, size_t stride, bool int4_only = true);
@@ -301,40 +310,55 @@ struct MoePlanes {
   size_t off_q[2], off_scale, off_zp[2];
 };
 MoePlanes moe_blob_planes(const woq_blob_header& h);  // h has passed moe_header_problem
-// plan, gate/up, down, combine: four launches shaped by (T, top_k, E, hidden, inter) alone, no host synchronisation
-int launch_moe_forward(const MoeCall& m, hipStream_t st);
-// a row of the plan's block table: `rows` sorted slots of one expert from sorted position `first`
+// a row of a plan's block table: `rows` sorted slots of one expert from sorted position `first`
 struct MoeBlock { int32_t expert, first, rows, pad; };
+// Where the sections of a form's workspace lie (byte offsets). The plan tables come first: blocks[0 .. *nblocks) cover
+// the sorted positions [0, valid slots) without a gap, in order; max_blocks sizes the grids (a workgroup past *nblocks
+// returns). counts (nseg segments of E words) is the prompt plan's own scratch, empty in the grouped form. Then the
+// fp32 rows h [sorted slot][inter] and y [sorted slot][hidden].
+struct MoeLayout {
+  size_t sorted, pos_of, blocks, nblocks, counts, h, y, total;
+  int max_blocks, nseg;
+};
+MoeLayout moe_layout(MoeForm form, int T, int top_k, int E, int hidden, int inter);
+// MoeLayout::total, or 0 for a shape outside the form's limits: woq_moe_workspace / woq_moe_prompt_workspace
+size_t moe_workspace_bytes(MoeForm form, int T, int top_k, int E, int hidden, int inter);
+// the prompt form's plan tables alone, which the backward (woq_moe_bwd.hip) puts at the front of its workspace
+size_t moe_prompt_plan_bytes(int T, int top_k, int E);
+// the plan tables of a form's workspace, as pointers
+struct MoeRoutePlan {
+  int32_t* sorted; int32_t* pos_of; MoeBlock* blocks; int32_t* nblocks; int32_t* counts;
+  int max_blocks, nseg;
+};
+MoeRoutePlan moe_plan_tables(MoeForm form, void* workspace, int T, int top_k, int E);
+// the prompt form's plan over the S = T * top_k ids — count, scan, scatter: three launches
+void launch_moe_prompt_plan(const void* topk_idx, bool idx_is_int64, int S, int E, const MoeRoutePlan& p, hipStream_t st);
+// One product of a form over a plan. MOE_GATE_UP: out[sorted slot][I] = SiLU(g) * u of the rows m.x gathered by token;
+// MOE_GATE_UP_RAW (the prompt form only, for the backward; fp8 blobs are refused): out[sorted slot][2 I] fp32 = [g | u],
+// no SiLU; MOE_DOWN: out[sorted slot][H] = h[sorted slot][I] through the down blobs.
+enum MoeRole { MOE_GATE_UP, MOE_GATE_UP_RAW, MOE_DOWN };
+int launch_moe_prompt_product(MoeRole role, const MoeCall& m, const MoeRoutePlan& p, const float* h, float* out,
+                              hipStream_t st);
+// plan (one launch, or the prompt form's three; none under plan_ready), gate/up, down, combine: launches shaped by
+// (T, top_k, E, hidden, inter) alone, no host synchronisation
+int launch_moe_forward(const MoeCall& m, MoeForm form, hipStream_t st);
 // out[t][n] = sum_j topk_w[t][j] * y[pos_of[t k + j]][n] (fp32 y [sorted slot][H]), j ascending, a dropped slot (-1)
 // contributing zero, rounded once to out_dtype: the last launch of both forms
 void launch_moe_combine(const float* y, const int32_t* pos_of, const float* topk_w, int T, int top_k, int H, void* out,
                         int out_dtype, int ldo, hipStream_t st);
-// where the grouped form's plan tables lie in a workspace of woq_moe_workspace(T, top_k, E, ..) bytes
-struct MoeRoutePlan { int32_t* sorted; int32_t* pos_of; MoeBlock* blocks; int32_t* nblocks; };
-MoeRoutePlan moe_plan_tables(void* workspace, int T, int top_k, int E);
-// rows of the module's `prompt_min_tokens`: from this many rows the engine's prompt pass takes the prompt form
-constexpr int MOE_PROMPT_MIN_ROWS = 64;
-
-// ---- woq_moe_prompt.hip: the same block for many rows per expert, on the fp16 MFMA ---------------------------------
-constexpr int MOE_PROMPT_ROWS = 128;          // rows of one block of its table: the row tile of the product
-constexpr int MOE_PROMPT_MAX_SLOTS = 65536;   // routed slots of one call: 64 plan segments of 1024
-// plan (count, scan, scatter), gate/up, down, combine: six launches shaped by (T, top_k, E, hidden, inter) alone;
-// `workspace` of woq_moe_prompt_workspace bytes
-int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st);
-// Its plan alone, for the backward (woq_moe_bwd.hip): the tables lie at the front of a workspace, in
-// moe_prompt_plan_bytes(T, top_k, E) bytes; blocks[0 .. *nblocks) cover the sorted positions [0, valid slots) without a
-// gap, in order; max_blocks sizes the grids (a workgroup past *nblocks returns). counts / nseg: the plan's own scratch.
-struct MoePromptPlan {
-  int32_t* sorted; int32_t* pos_of; MoeBlock* blocks; int32_t* nblocks; int32_t* counts;
-  int max_blocks, nseg;
+// The checks woq_moe_forward, woq_moe_prompt_forward and woq_moe_backward share, over the call as they received it: the
+// headers, the [K, N] relation, the dtypes, then — past a call of no rows — the limits, null pointers, leading
+// dimensions, alignment and the workspace size. What differs between them: the names inside the messages, the limits
+// (`workspace` returns 0 outside them) and the workspace's alignment.
+struct MoeEntry {
+  const char* fn;
+  size_t (*workspace)(int T, int top_k, int E, int hidden, int inter);
+  const char* workspace_fn;
+  int max_slots;
+  size_t workspace_align;
 };
-size_t moe_prompt_plan_bytes(int T, int top_k, int E);
-MoePromptPlan moe_prompt_plan_tables(void* workspace, int T, int top_k, int E);
-// count, scan, scatter over the S = T * top_k ids: three launches
-void launch_moe_prompt_plan(const void* topk_idx, bool idx_is_int64, int S, int E, const MoePromptPlan& p, hipStream_t st);
-// the gate/up product over a plan with the raw epilogue: gu[sorted slot][2 I] fp32 = [g | u], no SiLU (m: x, the
-// gate/up blobs and the down header for I; fp8 blobs are refused)
-int launch_moe_prompt_gate_up_raw(const MoeCall& m, const MoePromptPlan& p, float* gu, hipStream_t st);
+// 0: sound, go on | 1: refused, woq_last_error says why | -1: no rows, nothing to do
+int moe_entry_checks(const MoeEntry& e, const MoeCall& m, size_t workspace_bytes);
 
 // ---- woq_moe_bwd.hip: backward of the routed expert block with respect to its rows and its routing weights ---------
 // rows of one call: what woq_moe_backward takes (the plan's limit)

@@ -27,13 +27,16 @@
 // (scale_mode 1: each 64-k MFMA is issued twice, the other 32-k half's A operand read from a block of zeros). The
 // waves' partial sums meet in LDS and are added in wave order. fp8 blobs take launches 2 and 3 through a kernel of their
 // own on the fp8 MFMA, moe_fp8_gemm_kernel below.
+//
+// Also here, the host front of both forms (this one, MOE_GROUPED, and woq_moe_prompt.hip's MOE_PROMPT): the workspace
+// layout (moe_layout), the argument builder and role binders of the products (woq_moe.h), the forward driver
+// (launch_moe_forward) and the checks of the three entry points (moe_entry_checks; the backward's is woq_moe_bwd.hip).
 #include <math.h>
 
 #include <algorithm>
 #include <string>
 
-#include "woq_gemv_common.h"
-#include "woq_host.h"
+#include "woq_moe.h"
 
 namespace woq {
 namespace {
@@ -58,8 +61,7 @@ __global__ __launch_bounds__(MOE_PLAN_THREADS) void moe_plan_kernel(const void* 
   for (int e = tid; e < E; e += nthr) cnt[e] = 0;
   __syncthreads();
   for (int s = tid; s < S; s += nthr) {
-    const long long v = IDX64 ? (long long)((const int64_t*)topk_idx)[s] : (long long)((const int32_t*)topk_idx)[s];
-    const int e = (v >= 0 && v < (long long)E) ? (int)v : -1;
+    const int e = moe_slot_id<IDX64>(topk_idx, s, E);
     ids[s] = e;
     if (e >= 0)
       atomicAdd(&cnt[e], 1);  // an integer count: the result does not depend on the order
@@ -93,21 +95,6 @@ __global__ __launch_bounds__(MOE_PLAN_THREADS) void moe_plan_kernel(const void* 
 }
 
 // ---- 2 / 3. the grouped product --------------------------------------------------------------------------------------
-struct MoeGemmArgs {
-  const uint8_t* blobs;  // expert e's blob at blobs + e * stride
-  size_t stride, off_q[2], off_scale, off_zp[2];  // [plane]: woq_host.h MoePlanes
-  int K, N, tiles_k, n_groups, group, scale_type;
-  LutArgs lut;  // table kinds: the digit planes and wmul of lut_args_for, as the decode GEMV takes them
-  const void* x;  // gate/up: activations [T, ldx] of x_dtype; down: fp32 rows [sorted slot][ldx]
-  int x_dtype, ldx, top_k;
-  const int32_t* sorted;
-  const MoeBlock* blocks;
-  const int32_t* nblocks;
-  float* out;  // gate/up: SiLU(g) * u [sorted slot][ldo]; down: y [sorted slot][ldo]
-  int ldo, half_tiles;
-  int e5m2, lds_rows;  // fp8 blobs: the codes are e5m2 | the digit rows the launch's LDS holds: min(16, T k)
-};
-
 __device__ __forceinline__ float moe_scale(const void* s, size_t i, int st) {
   if (st == WOQ_F32) return ((const float*)s)[i];
   const uint16_t b = ((const uint16_t*)s)[i];
@@ -115,6 +102,64 @@ __device__ __forceinline__ float moe_scale(const void* s, size_t i, int st) {
 }
 
 constexpr int MOE_WK_INT8 = 4, MOE_WK_FP8 = 5;  // (fp8: moe_fp8_gemm_kernel below)
+
+// What moe_gemm_kernel and moe_fp8_gemm_kernel share: the staging of an activation row up to its gathered fixed-point
+// bytes. Their block prologues, chunk prefetches and cross-wave sums are written out in each: as shared functions they
+// cost the gate/up launches registers (profiles/r28_moe_refactor.txt).
+// Row m of the block, k0 .. k0 + 1023 of it, as fp32: lane l holds k0 + 256 j + 4 l .. + 3 in xv[j]. GU: the row of
+// a.x (of x_dtype) of the slot's token; else the slot's own fp32 row. Buffer loads return zero past the xlen elements
+// that lie inside K: that is what keeps the padding out of the sums
+template <bool GU>
+__device__ __forceinline__ void moe_load_row(const MoeGemmArgs& a, int first, int m, int k0, int xlen, int lane,
+                                             float4_t (&xv)[4]) {
+  const int src = GU ? __builtin_amdgcn_readfirstlane(a.sorted[first + m]) / a.top_k : first + m;
+  const size_t row_off = (size_t)src * a.ldx + k0;
+  if (GU && a.x_dtype != WOQ_F32) {
+    const rsrc_t rx = make_rsrc((const uint16_t*)a.x + row_off, xlen * 2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint2 r = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rx, lane * 8 + j * 512, 0, 0));
+      const uint16_t hb[4] = {(uint16_t)r.x, (uint16_t)(r.x >> 16), (uint16_t)r.y, (uint16_t)(r.y >> 16)};
+      float f[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float fb = bf16_bits_to_f32(hb[i]), fh = f16_bits_to_f32(hb[i]);
+        f[i] = a.x_dtype == WOQ_BF16 ? fb : fh;
+      }
+      xv[j] = (float4_t){f[0], f[1], f[2], f[3]};
+    }
+  } else {
+    const rsrc_t rx = make_rsrc((const float*)a.x + row_off, xlen * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + j * 1024, 0, 0));
+  }
+}
+
+// The exponent e of a staged row: amax < 2^e  =>  |x| * 2^(21 - e) < 2^21, so that the fp32 sum with 1.5 * 2^23 stays
+// inside [2^23, 2^24), where ulp = 1, and its mantissa IS round(x * 2^(21 - e)) + 2^22 (offset binary, 22 bits + sign)
+__device__ __forceinline__ int moe_row_exponent(const float4_t (&xv)[4]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    amax = fmaxf(fmaxf(amax, fabsf(xv[j].x)), fmaxf(fabsf(xv[j].y), fmaxf(fabsf(xv[j].z), fabsf(xv[j].w))));
+  amax = wave_max_dpp(amax);
+  int e = 0;
+  if (amax > 0.f && amax < INFINITY) e = max(-100, min(100, __builtin_amdgcn_frexp_expf(amax)));
+  return e;
+}
+// wb[n] = byte n of the four values' bits fl32(x * sfix + 1.5 * 2^23) + OFF, sfix = 2^(21 - e), gathered into one word:
+// v_perm_b32(hi, lo, sel) picks bytes of {hi:lo}, 0x0c = zero
+template <uint32_t OFF>
+__device__ __forceinline__ void moe_fixed_bytes(float4_t x, float sfix, uint32_t (&wb)[3]) {
+  const uint32_t va = __float_as_uint(fmaf(x.x, sfix, 12582912.f)) + OFF;
+  const uint32_t vb = __float_as_uint(fmaf(x.y, sfix, 12582912.f)) + OFF;
+  const uint32_t vc = __float_as_uint(fmaf(x.z, sfix, 12582912.f)) + OFF;
+  const uint32_t vd = __float_as_uint(fmaf(x.w, sfix, 12582912.f)) + OFF;
+  wb[0] = __builtin_amdgcn_perm(vb, va, 0x0c0c0400u) | __builtin_amdgcn_perm(vd, vc, 0x04000c0cu);
+  wb[1] = __builtin_amdgcn_perm(vb, va, 0x0c0c0501u) | __builtin_amdgcn_perm(vd, vc, 0x05010c0cu);
+  wb[2] = __builtin_amdgcn_perm(vb, va, 0x0c0c0602u) | __builtin_amdgcn_perm(vd, vc, 0x06020c0cu);
+}
 
 // GU: the gate/up launch (two column tiles, SiLU * mul epilogue, rows gathered by token) | the down launch
 // WK, the weight kind: 0 = int4 | 1, 2, 3 = a table type (nf4 / fp4) as that many digit planes | MOE_WK_INT8 = the int8
@@ -182,7 +227,7 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmA
     u32x4 w[MOE_TPW][CB][NP];
     float sc[MOE_TPW][CB][NS];
     int uz[MOE_TPW][CB][NS];  // zero point + 8; int8: 16 zhi + zlo + 8, the composite's zero point in LO-plane units
-    auto load_qparams = [&](int ti, int cb, int s, size_t si) {
+auto load_qparams = [&](int ti, int cb, int s, size_t si) {
       sc[ti][cb][s] = moe_scale(scales, si, a.scale_type);
       if constexpr (NDIG > 0) sc[ti][cb][s] *= a.lut.wmul;
       if constexpr (I8)
@@ -220,60 +265,18 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_gemm_kernel(const MoeGemmA
     const int xlen = max(0, min(MOE_KC, a.K - k0));
     for (int m = wid; m < R; m += MOE_WAVES) {
       float4_t xv[4];
-      if constexpr (GU) {
-        const int slot = __builtin_amdgcn_readfirstlane(a.sorted[first + m]);
-        const size_t row_off = (size_t)(slot / a.top_k) * a.ldx + k0;
-        if (a.x_dtype == WOQ_F32) {
-          const rsrc_t rx = make_rsrc((const float*)a.x + row_off, xlen * 4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + j * 1024, 0, 0));
-        } else {
-          const rsrc_t rx = make_rsrc((const uint16_t*)a.x + row_off, xlen * 2);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const uint2 r = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rx, lane * 8 + j * 512, 0, 0));
-            const uint16_t hb[4] = {(uint16_t)r.x, (uint16_t)(r.x >> 16), (uint16_t)r.y, (uint16_t)(r.y >> 16)};
-            float f[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float fb = bf16_bits_to_f32(hb[i]), fh = f16_bits_to_f32(hb[i]);
-              f[i] = a.x_dtype == WOQ_BF16 ? fb : fh;
-            }
-            xv[j] = (float4_t){f[0], f[1], f[2], f[3]};
-          }
-        }
-      } else {
-        const rsrc_t rx = make_rsrc((const float*)a.x + (size_t)(first + m) * a.ldx + k0, xlen * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + j * 1024, 0, 0));
-      }
-      float amax = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        amax = fmaxf(fmaxf(amax, fabsf(xv[j].x)), fmaxf(fabsf(xv[j].y), fmaxf(fabsf(xv[j].z), fabsf(xv[j].w))));
-      amax = wave_max_dpp(amax);
-      // amax < 2^e  =>  |x| * 2^(21 - e) < 2^21: the sum with 1.5 * 2^23 stays inside [2^23, 2^24), where ulp = 1, so its
-      // mantissa IS round(x * 2^(21 - e)) + 2^22 (offset binary, 22 bits + sign)
-      int e = 0;
-      if (amax > 0.f && amax < INFINITY) e = max(-100, min(100, __builtin_amdgcn_frexp_expf(amax)));
+      moe_load_row<GU>(a, first, m, k0, xlen, lane, xv);
+      const int e = moe_row_exponent(xv);
       const float sfix = ldexpf(1.f, 21 - e);
       if (lane == 0) unsc_s[m] = ldexpf(1.f, e - 25);  // undoes the fixed-point scale and the 16 * q weight bytes
       unsigned char* r0 = strip + (size_t)(3 * m) * MOE_RB + lane * 4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const uint32_t va = __float_as_uint(fmaf(xv[j].x, sfix, 12582912.f));
-        const uint32_t vb = __float_as_uint(fmaf(xv[j].y, sfix, 12582912.f));
-        const uint32_t vc = __float_as_uint(fmaf(xv[j].z, sfix, 12582912.f));
-        const uint32_t vd = __float_as_uint(fmaf(xv[j].w, sfix, 12582912.f));
-        // byte n of (va, vb, vc, vd) into one word: v_perm_b32(hi, lo, sel) picks bytes of {hi:lo}, 0x0c = zero
-        const uint32_t ab0 = __builtin_amdgcn_perm(vb, va, 0x0c0c0400u), cd0 = __builtin_amdgcn_perm(vd, vc, 0x04000c0cu);
-        const uint32_t ab1 = __builtin_amdgcn_perm(vb, va, 0x0c0c0501u), cd1 = __builtin_amdgcn_perm(vd, vc, 0x05010c0cu);
-        const uint32_t ab2 = __builtin_amdgcn_perm(vb, va, 0x0c0c0602u), cd2 = __builtin_amdgcn_perm(vd, vc, 0x06020c0cu);
-        *(uint32_t*)(r0 + j * 256) = (ab0 | cd0) ^ 0x80808080u;               // limb 0: b0 - 128
-        *(uint32_t*)(r0 + MOE_RB + j * 256) = (ab1 | cd1) ^ 0x80808080u;      // limb 1: b1 - 128
-        *(uint32_t*)(r0 + 2 * MOE_RB + j * 256) = ab2 | cd2;                  // limb 2: b2 in [0, 127]
+        uint32_t wb[3];
+        moe_fixed_bytes<0u>(xv[j], sfix, wb);
+        *(uint32_t*)(r0 + j * 256) = wb[0] ^ 0x80808080u;           // limb 0: b0 - 128
+        *(uint32_t*)(r0 + MOE_RB + j * 256) = wb[1] ^ 0x80808080u;  // limb 1: b1 - 128
+        *(uint32_t*)(r0 + 2 * MOE_RB + j * 256) = wb[2];            // limb 2: b2 in [0, 127]
       }
     }
     __syncthreads();
@@ -512,6 +515,20 @@ __device__ __forceinline__ void moe_fp8_codes(uint32_t h0, uint32_t h1, uint32_t
   const uint32_t b3 = (h1 & 0xf0f0f0f0u) | (((l1 >> 4) & 0x0f0f0f0fu) ^ 0x08080808u);
   bq0 = (i64_t)(((unsigned long)b1 << 32) | b0), bq1 = (i64_t)(((unsigned long)b3 << 32) | b2);
 }
+// the codes of 64-k half h of one tile, from its two planes' words w[cb][0 | 1], for every column tile
+template <int CB>
+__device__ __forceinline__ void moe_fp8_tile_codes(const u32x4 (&w)[CB][2], int h, i64_t (&bq0)[CB], i64_t (&bq1)[CB]) {
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    const u32x4 wh = w[cb][0], wl = w[cb][1];
+    moe_fp8_codes(h == 0 ? wh.x : wh.z, h == 0 ? wh.y : wh.w, h == 0 ? wl.x : wl.z, h == 0 ? wl.y : wl.w, bq0[cb], bq1[cb]);
+  }
+}
+// a lane's 16 digit bytes at p as the A operands of the two 32-k MFMAs of a 64-k half
+__device__ __forceinline__ void moe_fp8_a(const unsigned char* p, i64_t& a_lo, i64_t& a_hi) {
+  const u32x4 av = *(const u32x4*)p;
+  a_lo = (i64_t)(((unsigned long)av.y << 32) | av.x), a_hi = (i64_t)(((unsigned long)av.w << 32) | av.z);
+}
 
 template <bool GU, int SMODE, bool E5M2>
 __global__ __launch_bounds__(MOE_WAVES * 64) void moe_fp8_gemm_kernel(const MoeGemmArgs a) {
@@ -601,52 +618,16 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_fp8_gemm_kernel(const MoeG
     const int xlen = max(0, min(MOE_KC, a.K - k0));
     for (int m = wid; m < R; m += MOE_WAVES) {
       float4_t xv[4];
-      if (GU && a.x_dtype != WOQ_F32) {
-        const int slot = __builtin_amdgcn_readfirstlane(a.sorted[first + m]);
-        const rsrc_t rx = make_rsrc((const uint16_t*)a.x + (size_t)(slot / a.top_k) * a.ldx + k0, xlen * 2);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint2 r = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rx, lane * 8 + j * 512, 0, 0));
-          const uint16_t hb[4] = {(uint16_t)r.x, (uint16_t)(r.x >> 16), (uint16_t)r.y, (uint16_t)(r.y >> 16)};
-          float f[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float fb = bf16_bits_to_f32(hb[i]), fh = f16_bits_to_f32(hb[i]);
-            f[i] = a.x_dtype == WOQ_BF16 ? fb : fh;
-          }
-          xv[j] = (float4_t){f[0], f[1], f[2], f[3]};
-        }
-      } else {
-        const int src = GU ? __builtin_amdgcn_readfirstlane(a.sorted[first + m]) / a.top_k : first + m;
-        const rsrc_t rx = make_rsrc((const float*)a.x + (size_t)src * a.ldx + k0, xlen * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          xv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16 + j * 1024, 0, 0));
-      }
-      float amax = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        amax = fmaxf(fmaxf(amax, fabsf(xv[j].x)), fmaxf(fabsf(xv[j].y), fmaxf(fabsf(xv[j].z), fabsf(xv[j].w))));
-      amax = wave_max_dpp(amax);
-      int e = 0;
-      if (amax > 0.f && amax < INFINITY) e = max(-100, min(100, __builtin_amdgcn_frexp_expf(amax)));
+      moe_load_row<GU>(a, first, m, k0, xlen, lane, xv);
+      const int e = moe_row_exponent(xv);
       const float sfix = ldexpf(1.f, 21 - e);
       if (lane == 0) unsc_s[m] = ldexpf(1.f, e - 21);
       unsigned char* r0 = strip + (size_t)(ND * m) * MOE_RB + lane * 4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        // amax < 2^e  =>  |x| 2^(21 - e) < 2^21: the fp32 sum with 1.5 * 2^23 has ulp 1 and the bits 0x4B000000 + v + 2^22
-        // (moe_gemm_kernel's staging); + 0x488888 - 0x4B000000 leaves u = v + 0x888888 < 2^24
-        constexpr uint32_t OFF = 0x00488888u - 0x4B000000u;
-        const uint32_t ua = __float_as_uint(fmaf(xv[j].x, sfix, 12582912.f)) + OFF;
-        const uint32_t ub = __float_as_uint(fmaf(xv[j].y, sfix, 12582912.f)) + OFF;
-        const uint32_t uc = __float_as_uint(fmaf(xv[j].z, sfix, 12582912.f)) + OFF;
-        const uint32_t ud = __float_as_uint(fmaf(xv[j].w, sfix, 12582912.f)) + OFF;
-        // byte n of (ua, ub, uc, ud) into one word: v_perm_b32(hi, lo, sel) picks bytes of {hi:lo}, 0x0c = zero
-        const uint32_t wb[3] = {
-            __builtin_amdgcn_perm(ub, ua, 0x0c0c0400u) | __builtin_amdgcn_perm(ud, uc, 0x04000c0cu),
-            __builtin_amdgcn_perm(ub, ua, 0x0c0c0501u) | __builtin_amdgcn_perm(ud, uc, 0x05010c0cu),
-            __builtin_amdgcn_perm(ub, ua, 0x0c0c0602u) | __builtin_amdgcn_perm(ud, uc, 0x06020c0cu)};
+        // the bits of the fixed-point sum are 0x4B000000 + v + 2^22; + 0x488888 - 0x4B000000 leaves u = v + 0x888888 < 2^24
+        uint32_t wb[3];
+        moe_fixed_bytes<0x00488888u - 0x4B000000u>(xv[j], sfix, wb);
 #pragma unroll
         for (int n = 0; n < 3; ++n) {
           uint32_t lo[1], hi[1];
@@ -680,18 +661,11 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_fp8_gemm_kernel(const MoeG
           for (int s = 0; s < NS; ++s) d[cb][s] = fzero;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          i64_t bq0[CB], bq1[CB];
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb) {
-            const u32x4 wh = w[ti][cb][0], wl = w[ti][cb][1];
-            moe_fp8_codes(h == 0 ? wh.x : wh.z, h == 0 ? wh.y : wh.w, h == 0 ? wl.x : wl.z, h == 0 ? wl.y : wl.w, bq0[cb],
-                          bq1[cb]);
-          }
+          i64_t bq0[CB], bq1[CB], a_lo, a_hi;
+          moe_fp8_tile_codes(w[ti], h, bq0, bq1);
 #pragma unroll
           for (int g = 0; g < (SMODE == 1 ? 2 : 1); ++g) {
-            const unsigned char* ap = SMODE == 1 ? a_blk[g] : a_row;
-            const u32x4 av = *(const u32x4*)(ap + tt * 128 + h * 64);
-            const i64_t a_lo = (i64_t)(((unsigned long)av.y << 32) | av.x), a_hi = (i64_t)(((unsigned long)av.w << 32) | av.z);
+            moe_fp8_a((SMODE == 1 ? a_blk[g] : a_row) + tt * 128 + h * 64, a_lo, a_hi);
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
               float4_t& dd = d[cb][SMODE == 1 ? 2 * h + g : 0];
@@ -731,17 +705,11 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_fp8_gemm_kernel(const MoeG
             for (int j = 0; j < ND; ++j) S[cb][j] = fzero;
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            i64_t bq0[CB], bq1[CB];
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-              const u32x4 wh = w[ti][cb][0], wl = w[ti][cb][1];
-              moe_fp8_codes(h == 0 ? wh.x : wh.z, h == 0 ? wh.y : wh.w, h == 0 ? wl.x : wl.z, h == 0 ? wl.y : wl.w,
-                            bq0[cb], bq1[cb]);
-            }
+            i64_t bq0[CB], bq1[CB], a_lo, a_hi;
+            moe_fp8_tile_codes(w[ti], h, bq0, bq1);
 #pragma unroll
             for (int j = 0; j < ND; ++j) {
-              const u32x4 av = *(const u32x4*)(a_row + j * dstep + tt * 128 + h * 64);
-              const i64_t a_lo = (i64_t)(((unsigned long)av.y << 32) | av.x), a_hi = (i64_t)(((unsigned long)av.w << 32) | av.z);
+              moe_fp8_a(a_row + j * dstep + tt * 128 + h * 64, a_lo, a_hi);
 #pragma unroll
               for (int cb = 0; cb < CB; ++cb) {
                 S[cb][j] = moe_mfma_f8<E5M2>(a_lo, bq0[cb], S[cb][j]);
@@ -754,20 +722,14 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_fp8_gemm_kernel(const MoeG
         } else {
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            i64_t bq0[CB], bq1[CB];
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-              const u32x4 wh = w[ti][cb][0], wl = w[ti][cb][1];
-              moe_fp8_codes(h == 0 ? wh.x : wh.z, h == 0 ? wh.y : wh.w, h == 0 ? wl.x : wl.z, h == 0 ? wl.y : wl.w,
-                            bq0[cb], bq1[cb]);
-            }
+            i64_t bq0[CB], bq1[CB], a_lo, a_hi;
+            moe_fp8_tile_codes(w[ti], h, bq0, bq1);
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
               float4_t S[CB][ND];
 #pragma unroll
               for (int j = 0; j < ND; ++j) {
-                const u32x4 av = *(const u32x4*)(a_blk[g] + j * d_blk[g] + tt * 128 + h * 64);
-                const i64_t a_lo = (i64_t)(((unsigned long)av.y << 32) | av.x), a_hi = (i64_t)(((unsigned long)av.w << 32) | av.z);
+                moe_fp8_a(a_blk[g] + j * d_blk[g] + tt * 128 + h * 64, a_lo, a_hi);
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) {
                   S[cb][j] = moe_mfma_f8<E5M2>(a_lo, bq0[cb], fzero);
@@ -828,29 +790,6 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restric
   store_f32(out, (size_t)t * ldo + n, out_dtype, acc);
 }
 
-struct MoeWorkspace {
-  size_t sorted, pos_of, blocks, nblocks, h, y, total;
-  int max_blocks;
-};
-MoeWorkspace moe_workspace(int T, int top_k, int E, int hidden, int inter) {
-  MoeWorkspace w;
-  const size_t S = (size_t)T * top_k;
-  w.max_blocks = (int)((S + MOE_BLOCK_ROWS - 1) / MOE_BLOCK_ROWS + std::min<size_t>((size_t)E, S));
-  w.sorted = 0;
-  w.pos_of = w.sorted + woq_round_up(S * 4, 256);
-  w.blocks = w.pos_of + woq_round_up(S * 4, 256);
-  w.nblocks = w.blocks + woq_round_up((size_t)w.max_blocks * sizeof(MoeBlock), 256);
-  w.h = w.nblocks + 256;
-  w.y = w.h + woq_round_up(S * (size_t)inter * 4, 256);
-  w.total = w.y + woq_round_up(S * (size_t)hidden * 4, 256);
-  return w;
-}
-
-bool moe_shape_ok(int T, int top_k, int E, int hidden, int inter) {
-  return T > 0 && top_k > 0 && E > 0 && hidden > 0 && inter > 0 && E <= MOE_MAX_EXPERTS &&
-         (long long)T * top_k <= MOE_MAX_SLOTS;
-}
-
 template <bool GU, int SMODE, bool ASYM>
 void moe_launch_kind(const MoeGemmArgs& a, int wk, dim3 grid, hipStream_t st) {
   const dim3 block(MOE_WAVES * 64);
@@ -885,21 +824,60 @@ int moe_launch_gemm(const MoeGemmArgs& a, bool smode1, bool asym, int wk, dim3 g
   return 0;
 }
 
-MoeGemmArgs moe_gemm_args(const void* blobs, const woq_blob_header& h, size_t stride, int& wk) {
+void moe_launch_plan(const void* topk_idx, bool idx_is_int64, int S, int E, const MoeRoutePlan& p, hipStream_t st) {
+  const auto kern = idx_is_int64 ? moe_plan_kernel<true> : moe_plan_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(1), dim3(MOE_PLAN_THREADS), 0, st, topk_idx, S, E, p.sorted, p.pos_of, p.blocks, p.nblocks);
+}
+
+// the grouped form's launch_moe_prompt_product (which has no raw gate/up)
+int moe_launch_product(MoeRole role, const MoeCall& m, const MoeRoutePlan& p, const float* h, float* out, hipStream_t st) {
+  if (role == MOE_GATE_UP_RAW) return fail("QBits: the grouped form has no raw gate/up product");
+  const bool gu = role == MOE_GATE_UP;
+  const woq_blob_header& hdr = gu ? *m.gate_up_hdr : *m.down_hdr;
+  MoeWeightKind kind;
+  MoeGemmArgs a = moe_gemm_args(m, gu, kind);
+  const int ndig = lut_args_for(hdr.weight_type, hdr.compute_type, a.lut);  // 0, and an empty table, for the integer kinds
+  const int wk = kind == MOE_W_TABLE ? ndig : (kind == MOE_W_INT8 ? MOE_WK_INT8 : (kind == MOE_W_FP8 ? MOE_WK_FP8 : 0));
+  if (gu) {
+    moe_bind_gate_up(a, m, p, out, m.down_hdr->K);
+    return moe_launch_gemm<true>(a, hdr.scale_mode == 1, hdr.off_zp != 0, wk,
+                                 dim3((unsigned)a.half_tiles, (unsigned)p.max_blocks), st);
+  }
+  moe_bind_down(a, m, p, h, out);
+  return moe_launch_gemm<false>(a, hdr.scale_mode == 1, hdr.off_zp != 0, wk, dim3((unsigned)a.tiles_n, (unsigned)p.max_blocks),
+                                st);
+}
+
+}  // namespace
+
+MoeGemmArgs moe_gemm_args(const MoeCall& m, bool gate_up, MoeWeightKind& kind) {
+  const woq_blob_header& h = gate_up ? *m.gate_up_hdr : *m.down_hdr;
   MoeGemmArgs a = {};
-  a.blobs = (const uint8_t*)blobs, a.stride = stride;
+  a.blobs = (const uint8_t*)(gate_up ? m.gate_up_blobs : m.down_blobs);
+  a.stride = gate_up ? m.gate_up_stride : m.down_stride;
   const MoePlanes p = moe_blob_planes(h);
   for (int i = 0; i < 2; ++i) a.off_q[i] = p.off_q[i], a.off_zp[i] = p.off_zp[i];
-  a.off_scale = p.off_scale;
-  a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.n_groups = h.n_groups, a.group = h.group;
-  a.scale_type = (int)h.scale_type;
-  const int ndig = lut_args_for(h.weight_type, h.compute_type, a.lut);  // 0, and an empty table, for the integer kinds
-  wk = p.kind == MOE_W_TABLE ? ndig : (p.kind == MOE_W_INT8 ? MOE_WK_INT8 : (p.kind == MOE_W_FP8 ? MOE_WK_FP8 : 0));
+  a.off_scale = p.off_scale, kind = p.kind;
+  a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.tiles_n = h.Npad / WOQ_TILE_N;
+  a.n_groups = h.n_groups, a.group = h.group, a.scale_type = (int)h.scale_type;
   a.e5m2 = h.weight_type == WOQ_W_FP8_E5M2;
   return a;
 }
 
-}  // namespace
+static void moe_bind(MoeGemmArgs& a, const MoeCall& m, const MoeRoutePlan& p, float* out) {
+  a.top_k = m.top_k, a.sorted = p.sorted, a.blocks = p.blocks, a.nblocks = p.nblocks, a.out = out;
+  a.lds_rows = std::min(MOE_BLOCK_ROWS, m.T * m.top_k);
+}
+void moe_bind_gate_up(MoeGemmArgs& g, const MoeCall& m, const MoeRoutePlan& p, float* out, int ldo) {
+  moe_bind(g, m, p, out);
+  g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx;
+  g.ldo = ldo, g.half_tiles = m.down_hdr->K / 16;
+}
+void moe_bind_down(MoeGemmArgs& d, const MoeCall& m, const MoeRoutePlan& p, const float* h, float* y) {
+  moe_bind(d, m, p, y);
+  d.x = h, d.x_dtype = WOQ_F32, d.ldx = m.down_hdr->K;
+  d.ldo = m.down_hdr->N, d.half_tiles = 0;
+}
 
 const char* moe_header_problem(const woq_blob_header& h, size_t stride, bool int4_only) {
   if (h.magic != WOQ_BLOB_MAGIC) return "QBits: woq_moe_forward: not a WQH1 packed weight";
@@ -962,69 +940,105 @@ void launch_moe_combine(const float* y, const int32_t* pos_of, const float* topk
                      top_k, H, out, out_dtype, ldo);
 }
 
-int launch_moe_forward(const MoeCall& m, hipStream_t st) {
-  const woq_blob_header& gh = *m.gate_up_hdr;
-  const woq_blob_header& dh = *m.down_hdr;
-  const int H = dh.N, I = dh.K;
-  const MoeWorkspace w = moe_workspace(m.T, m.top_k, m.E, H, I);
+MoeLayout moe_layout(MoeForm form, int T, int top_k, int E, int hidden, int inter) {
+  MoeLayout w;
+  const size_t S = (size_t)T * top_k, rows = form == MOE_PROMPT ? MOE_PROMPT_ROWS : MOE_BLOCK_ROWS;
+  w.max_blocks = (int)((S + rows - 1) / rows + std::min<size_t>((size_t)E, S));
+  w.nseg = form == MOE_PROMPT ? (int)((S + MOE_PLAN_SEG - 1) / MOE_PLAN_SEG) : 0;
+  w.sorted = 0;
+  w.pos_of = w.sorted + woq_round_up(S * 4, 256);
+  w.blocks = w.pos_of + woq_round_up(S * 4, 256);
+  w.nblocks = w.blocks + woq_round_up((size_t)w.max_blocks * sizeof(MoeBlock), 256);
+  w.counts = w.nblocks + 256;
+  w.h = w.counts + woq_round_up((size_t)w.nseg * E * 4, 256);
+  w.y = w.h + woq_round_up(S * (size_t)inter * 4, 256);
+  w.total = w.y + woq_round_up(S * (size_t)hidden * 4, 256);
+  return w;
+}
+
+size_t moe_workspace_bytes(MoeForm form, int T, int top_k, int E, int hidden, int inter) {
+  const bool ok = T > 0 && top_k > 0 && E > 0 && hidden > 0 && inter > 0 && E <= MOE_MAX_EXPERTS &&
+                  (long long)T * top_k <= moe_max_slots(form);
+  return ok ? moe_layout(form, T, top_k, E, hidden, inter).total : 0;
+}
+
+size_t moe_prompt_plan_bytes(int T, int top_k, int E) { return moe_layout(MOE_PROMPT, T, top_k, E, 0, 0).h; }
+
+MoeRoutePlan moe_plan_tables(MoeForm form, void* workspace, int T, int top_k, int E) {
+  const MoeLayout w = moe_layout(form, T, top_k, E, 0, 0);
+  uint8_t* ws = (uint8_t*)workspace;
+  return MoeRoutePlan{(int32_t*)(ws + w.sorted), (int32_t*)(ws + w.pos_of), (MoeBlock*)(ws + w.blocks),
+                      (int32_t*)(ws + w.nblocks), (int32_t*)(ws + w.counts), w.max_blocks, w.nseg};
+}
+
+int launch_moe_forward(const MoeCall& m, MoeForm form, hipStream_t st) {
+  const int H = m.down_hdr->N, I = m.down_hdr->K;
+  const MoeLayout w = moe_layout(form, m.T, m.top_k, m.E, H, I);
   uint8_t* ws = (uint8_t*)m.workspace;
-  int32_t* sorted = (int32_t*)(ws + w.sorted);
-  int32_t* pos_of = (int32_t*)(ws + w.pos_of);
-  MoeBlock* blocks = (MoeBlock*)(ws + w.blocks);
-  int32_t* nblocks = (int32_t*)(ws + w.nblocks);
+  const MoeRoutePlan plan = moe_plan_tables(form, ws, m.T, m.top_k, m.E);
   float* hbuf = (float*)(ws + w.h);
   float* ybuf = (float*)(ws + w.y);
-  const int S = m.T * m.top_k;
+  const auto product = form == MOE_PROMPT ? launch_moe_prompt_product : moe_launch_product;
 
-  if (m.plan_ready)
-    ;  // (the router wrote the tables)
-  else if (m.idx_is_int64)
-    hipLaunchKernelGGL(moe_plan_kernel<true>, dim3(1), dim3(MOE_PLAN_THREADS), 0, st, m.topk_idx, S, m.E, sorted, pos_of,
-                       blocks, nblocks);
-  else
-    hipLaunchKernelGGL(moe_plan_kernel<false>, dim3(1), dim3(MOE_PLAN_THREADS), 0, st, m.topk_idx, S, m.E, sorted,
-                       pos_of, blocks, nblocks);
-
-  int g_wk, d_wk;
-  MoeGemmArgs g = moe_gemm_args(m.gate_up_blobs, gh, m.gate_up_stride, g_wk);
-  g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
-  g.sorted = sorted, g.blocks = blocks, g.nblocks = nblocks;
-  g.out = hbuf, g.ldo = I, g.half_tiles = I / 16;
-  g.lds_rows = std::min(MOE_BLOCK_ROWS, S);
-  if (const int rc = moe_launch_gemm<true>(g, gh.scale_mode == 1, gh.off_zp != 0, g_wk,
-                                           dim3((unsigned)(I / 16), (unsigned)w.max_blocks), st))
-    return rc;
-
-  MoeGemmArgs d = moe_gemm_args(m.down_blobs, dh, m.down_stride, d_wk);
-  d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
-  d.sorted = sorted, d.blocks = blocks, d.nblocks = nblocks;
-  d.out = ybuf, d.ldo = H, d.half_tiles = 0;
-  d.lds_rows = g.lds_rows;
-  if (const int rc = moe_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, d_wk,
-                                            dim3((unsigned)(dh.Npad / 16), (unsigned)w.max_blocks), st))
-    return rc;
-
+  if (!m.plan_ready)  // (else the router wrote the tables)
+    (form == MOE_PROMPT ? launch_moe_prompt_plan : moe_launch_plan)(m.topk_idx, m.idx_is_int64, m.T * m.top_k, m.E, plan, st);
+  if (const int rc = product(MOE_GATE_UP, m, plan, nullptr, hbuf, st)) return rc;
+  if (const int rc = product(MOE_DOWN, m, plan, hbuf, ybuf, st)) return rc;
   if (m.residual != nullptr) {
-    if (const int rc = launch_moe_combine_residual(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, *m.residual, st)) return rc;
+    if (const int rc = launch_moe_combine_residual(ybuf, plan.pos_of, m.topk_w, m.T, m.top_k, H, *m.residual, st)) return rc;
   } else {
-    launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
+    launch_moe_combine(ybuf, plan.pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
   }
   WOQ_HIP(hipGetLastError());
   return 0;
 }
 
-MoeRoutePlan moe_plan_tables(void* workspace, int T, int top_k, int E) {
-  const MoeWorkspace w = moe_workspace(T, top_k, E, 0, 0);
-  uint8_t* ws = (uint8_t*)workspace;
-  return MoeRoutePlan{(int32_t*)(ws + w.sorted), (int32_t*)(ws + w.pos_of), (MoeBlock*)(ws + w.blocks),
-                      (int32_t*)(ws + w.nblocks)};
+int moe_entry_checks(const MoeEntry& e, const MoeCall& m, size_t workspace_bytes) {
+  const std::string fn = std::string("QBits: ") + e.fn;
+  WOQ_CHECK(m.gate_up_hdr && m.down_hdr, fn + ": null header");
+  if (const char* p = moe_header_problem(*m.gate_up_hdr, m.gate_up_stride, false)) WOQ_FAIL(p);
+  if (const char* p = moe_header_problem(*m.down_hdr, m.down_stride, false)) WOQ_FAIL(p);
+  const int H = m.down_hdr->N, I = m.down_hdr->K;
+  WOQ_CHECK(m.gate_up_hdr->K == H && m.gate_up_hdr->N == 2 * I,
+            fn + ": gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");
+  WOQ_CHECK(I % 16 == 0,
+            fn + ": the intermediate size must be a multiple of 16 (gate tile tn pairs with up tile tn + inter / 16)");
+  WOQ_CHECK(H % 4 == 0, fn + ": the hidden size must be a multiple of 4");
+  auto dtype_ok = [](int d) { return d == WOQ_F32 || d == WOQ_BF16 || d == WOQ_F16; };
+  WOQ_CHECK(dtype_ok(m.x_dtype) && dtype_ok(m.out_dtype), "QBits: unsupported qbits data type.");
+  if (m.T <= 0) return -1;
+  const size_t need = e.workspace(m.T, m.top_k, m.E, H, I);
+  WOQ_CHECK(need != 0, fn + " takes at most " + std::to_string(MOE_MAX_EXPERTS) + " experts and " +
+                           std::to_string(e.max_slots) + " routed slots (T * top_k) per call");
+  WOQ_CHECK(m.x && m.topk_idx && m.topk_w && m.gate_up_blobs && m.down_blobs && m.out && m.workspace, fn + ": null tensor");
+  WOQ_CHECK(m.ldx >= H && m.ldo >= H, fn + ": leading dimension smaller than hidden");
+  WOQ_CHECK((uintptr_t)m.x % (4 * woq_dtype_size((uint32_t)m.x_dtype)) == 0 && m.ldx % 4 == 0,
+            fn + ": activation rows must be aligned to four elements");
+  WOQ_CHECK((uintptr_t)m.gate_up_blobs % 16 == 0 && (uintptr_t)m.down_blobs % 16 == 0 &&
+                (uintptr_t)m.workspace % e.workspace_align == 0,
+            fn + (e.workspace_align == 16 ? ": blobs and workspace must be 16-byte aligned"
+                                          : ": blobs must be 16-byte and the workspace 256-byte aligned"));
+  WOQ_CHECK(workspace_bytes >= need, fn + ": the workspace holds " + std::to_string(workspace_bytes) +
+                                         " bytes, this call needs " + std::to_string(need) + " (" + e.workspace_fn + ")");
+  return 0;
+}
+
+// woq_moe_forward and woq_moe_prompt_forward past their argument lists
+static int moe_forward_entry(MoeForm form, const MoeCall& m, size_t workspace_bytes, void* stream) {
+  static const MoeEntry entry[2] = {
+      {"woq_moe_forward", woq_moe_workspace, "woq_moe_workspace", MOE_MAX_SLOTS, 16},
+      {"woq_moe_prompt_forward", woq_moe_prompt_workspace, "woq_moe_prompt_workspace", MOE_PROMPT_MAX_SLOTS, 16}};
+  if (const int rc = moe_entry_checks(entry[form], m, workspace_bytes)) return rc < 0 ? 0 : rc;
+  return launch_moe_forward(m, form, (hipStream_t)stream);
 }
 
 }  // namespace woq
 
 extern "C" size_t woq_moe_workspace(int T, int top_k, int E, int hidden, int inter) {
-  if (!woq::moe_shape_ok(T, top_k, E, hidden, inter)) return 0;
-  return woq::moe_workspace(T, top_k, E, hidden, inter).total;
+  return woq::moe_workspace_bytes(woq::MOE_GROUPED, T, top_k, E, hidden, inter);
+}
+extern "C" size_t woq_moe_prompt_workspace(int T, int top_k, int E, int hidden, int inter) {
+  return woq::moe_workspace_bytes(woq::MOE_PROMPT, T, top_k, E, hidden, inter);
 }
 
 extern "C" int woq_moe_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,
@@ -1033,41 +1047,23 @@ extern "C" int woq_moe_forward(const void* x_dev, int x_dtype, int ldx, const vo
                                const woq_blob_header* down_hdr, size_t down_stride, void* out_dev, int out_dtype, int ldo,
                                void* workspace_dev, size_t workspace_bytes, void* stream) {
   WOQ_TRY
-  using namespace woq;
-  WOQ_CHECK(gate_up_hdr && down_hdr, "QBits: woq_moe_forward: null header");
-  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride, false)) WOQ_FAIL(p);
-  if (const char* p = moe_header_problem(*down_hdr, down_stride, false)) WOQ_FAIL(p);
-  const int H = down_hdr->N, I = down_hdr->K;
-  WOQ_CHECK(gate_up_hdr->K == H && gate_up_hdr->N == 2 * I,
-            "QBits: woq_moe_forward: gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");
-  WOQ_CHECK(I % 16 == 0, "QBits: woq_moe_forward: the intermediate size must be a multiple of 16 (gate tile tn pairs with up "
-                         "tile tn + inter / 16)");
-  WOQ_CHECK(H % 4 == 0, "QBits: woq_moe_forward: the hidden size must be a multiple of 4");
-  auto dtype_ok = [](int d) { return d == WOQ_F32 || d == WOQ_BF16 || d == WOQ_F16; };
-  WOQ_CHECK(dtype_ok(x_dtype) && dtype_ok(out_dtype), "QBits: unsupported qbits data type.");
-  if (T <= 0) return 0;
-  WOQ_CHECK(moe_shape_ok(T, top_k, E, H, I),
-            "QBits: woq_moe_forward takes at most " + std::to_string(MOE_MAX_EXPERTS) + " experts and " +
-                std::to_string(MOE_MAX_SLOTS) + " routed slots (T * top_k) per call");
-  WOQ_CHECK(x_dev && topk_idx_dev && topk_w_dev && gate_up_blobs_dev && down_blobs_dev && out_dev && workspace_dev,
-            "QBits: woq_moe_forward: null tensor");
-  WOQ_CHECK(ldx >= H && ldo >= H, "QBits: woq_moe_forward: leading dimension smaller than hidden");
-  const size_t xsz = woq_dtype_size((uint32_t)x_dtype);
-  WOQ_CHECK((uintptr_t)x_dev % (4 * xsz) == 0 && ((size_t)ldx * xsz) % (4 * xsz) == 0,
-            "QBits: woq_moe_forward: activation rows must be aligned to four elements");
-  WOQ_CHECK((uintptr_t)gate_up_blobs_dev % 16 == 0 && (uintptr_t)down_blobs_dev % 16 == 0 &&
-                (uintptr_t)workspace_dev % 16 == 0,
-            "QBits: woq_moe_forward: blobs and workspace must be 16-byte aligned");
-  const size_t need = moe_workspace(T, top_k, E, H, I).total;
-  WOQ_CHECK(workspace_bytes >= need, "QBits: woq_moe_forward: the workspace holds " + std::to_string(workspace_bytes) +
-                                         " bytes, this call needs " + std::to_string(need) + " (woq_moe_workspace)");
-  MoeCall m;
-  m.x = x_dev, m.x_dtype = x_dtype, m.ldx = ldx;
-  m.topk_idx = topk_idx_dev, m.idx_is_int64 = idx_is_int64 != 0, m.topk_w = topk_w_dev;
-  m.T = T, m.top_k = top_k, m.E = E;
-  m.gate_up_blobs = gate_up_blobs_dev, m.gate_up_hdr = gate_up_hdr, m.gate_up_stride = gate_up_stride;
-  m.down_blobs = down_blobs_dev, m.down_hdr = down_hdr, m.down_stride = down_stride;
-  m.out = out_dev, m.out_dtype = out_dtype, m.ldo = ldo, m.workspace = workspace_dev;
-  if (const int rc = launch_moe_forward(m, (hipStream_t)stream)) return rc;
+  const woq::MoeCall m = {x_dev, x_dtype, ldx, topk_idx_dev, idx_is_int64 != 0, topk_w_dev, T, top_k, E,
+                          gate_up_blobs_dev, gate_up_hdr, gate_up_stride, down_blobs_dev, down_hdr, down_stride,
+                          out_dev, out_dtype, ldo, workspace_dev};
+  if (const int rc = woq::moe_forward_entry(woq::MOE_GROUPED, m, workspace_bytes, stream)) return rc;
+  WOQ_END
+}
+
+extern "C" int woq_moe_prompt_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,
+                                      const float* topk_w_dev, int T, int top_k, int E, const void* gate_up_blobs_dev,
+                                      const woq_blob_header* gate_up_hdr, size_t gate_up_stride,
+                                      const void* down_blobs_dev, const woq_blob_header* down_hdr, size_t down_stride,
+                                      void* out_dev, int out_dtype, int ldo, void* workspace_dev, size_t workspace_bytes,
+                                      void* stream) {
+  WOQ_TRY
+  const woq::MoeCall m = {x_dev, x_dtype, ldx, topk_idx_dev, idx_is_int64 != 0, topk_w_dev, T, top_k, E,
+                          gate_up_blobs_dev, gate_up_hdr, gate_up_stride, down_blobs_dev, down_hdr, down_stride,
+                          out_dev, out_dtype, ldo, workspace_dev};
+  if (const int rc = woq::moe_forward_entry(woq::MOE_PROMPT, m, workspace_bytes, stream)) return rc;
   WOQ_END
 }

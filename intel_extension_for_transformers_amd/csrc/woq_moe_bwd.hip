@@ -25,8 +25,8 @@
 //       contributes nothing to the gradient; from 2^-14 down it keeps fewer than 11 bits. That is a group 2^14 ..
 //       2^24 times smaller than the largest of all experts of its kind; tests/moe_backward_reference.py charges it
 //       through the 2^-22 n max|dY| max|W| term, taken over all experts.
-//  5    recompute of g and u: moe_prompt_gemm_kernel with its RAW epilogue (launch_moe_prompt_gate_up_raw) -> fp32
-//       [sorted slot][2 I]. Always this product, whatever form served the forward: nothing but the call's inputs is kept.
+//  5    recompute of g and u: moe_prompt_gemm_kernel with its RAW epilogue (launch_moe_prompt_product, MOE_GATE_UP_RAW)
+//       -> fp32 [sorted slot][2 I]. Always this product, whatever form served the forward: nothing but the call's inputs is kept.
 //  6    product 1 (moe_bwd_product_kernel over the down blobs) -> dh' fp32 [sorted slot][I].
 //  7    activation backward (moe_bwd_act_kernel), a workgroup per sorted row: dw reduced in a fixed order (a thread's
 //       chunks ascending, the xor butterfly of a wave, the four waves as (0 + 1) + (2 + 3)) and stored through the slot
@@ -351,39 +351,26 @@ extern "C" int woq_moe_backward(const void* grad_out_dev, int grad_dtype, int ld
                                 size_t workspace_bytes, void* stream) {
   WOQ_TRY
   using namespace woq;
-  WOQ_CHECK(gate_up_hdr && down_hdr, "QBits: woq_moe_backward: null header");
-  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride, false)) WOQ_FAIL(p);
-  if (const char* p = moe_header_problem(*down_hdr, down_stride, false)) WOQ_FAIL(p);
-  WOQ_CHECK(!woq_weight_is_fp8(gate_up_hdr->weight_type) && !woq_weight_is_fp8(down_hdr->weight_type),
+  auto fp8 = [](const woq_blob_header* h) { return h != nullptr && woq_weight_is_fp8(h->weight_type); };
+  WOQ_CHECK(!fp8(gate_up_hdr) && !fp8(down_hdr),
             "QBits: woq_moe_backward: fp8 expert blobs are not built; they take the dequantise-and-matmul arm");
+  WOQ_CHECK(grad_dtype == WOQ_F32 || grad_dtype == WOQ_BF16 || grad_dtype == WOQ_F16, "QBits: unsupported qbits data type.");
+  if (T > 0) {  // (a call of no rows returns 0 from the shared checks, whatever its pointers)
+    WOQ_CHECK(grad_out_dev, "QBits: woq_moe_backward: null tensor");
+    WOQ_CHECK(!down_hdr || ldg >= down_hdr->N, "QBits: woq_moe_backward: leading dimension smaller than hidden");
+  }
+  MoeCall m = {x_dev, x_dtype, ldx, topk_idx_dev, idx_is_int64 != 0, topk_w_dev, T, top_k, E,
+               gate_up_blobs_dev, gate_up_hdr, gate_up_stride, down_blobs_dev, down_hdr, down_stride,
+               grad_x_dev, grad_x_dtype, ldgx, workspace_dev};
+  static const MoeEntry entry = {"woq_moe_backward", woq_moe_backward_workspace, "woq_moe_backward_workspace",
+                                 MOE_BACKWARD_MAX_SLOTS, 256};  // (its workspace function also holds T to 65535)
+  if (const int rc = moe_entry_checks(entry, m, workspace_bytes)) return rc < 0 ? 0 : rc;
   const int H = down_hdr->N, I = down_hdr->K;
-  WOQ_CHECK(gate_up_hdr->K == H && gate_up_hdr->N == 2 * I,
-            "QBits: woq_moe_backward: gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");
-  WOQ_CHECK(I % 16 == 0, "QBits: woq_moe_backward: the intermediate size must be a multiple of 16");
-  WOQ_CHECK(H % 4 == 0, "QBits: woq_moe_backward: the hidden size must be a multiple of 4");
-  auto dtype_ok = [](int d) { return d == WOQ_F32 || d == WOQ_BF16 || d == WOQ_F16; };
-  WOQ_CHECK(dtype_ok(grad_dtype) && dtype_ok(x_dtype) && dtype_ok(grad_x_dtype), "QBits: unsupported qbits data type.");
-  if (T <= 0) return 0;
-  WOQ_CHECK(moe_bwd_shape_ok(T, top_k, E, H, I),
-            "QBits: woq_moe_backward takes at most " + std::to_string(MOE_MAX_EXPERTS) + " experts and " +
-                std::to_string(MOE_BACKWARD_MAX_SLOTS) + " routed slots (T * top_k) per call");
-  WOQ_CHECK(grad_out_dev && x_dev && topk_idx_dev && topk_w_dev && gate_up_blobs_dev && down_blobs_dev && grad_x_dev &&
-                workspace_dev, "QBits: woq_moe_backward: null tensor");
-  WOQ_CHECK(ldg >= H && ldx >= H && ldgx >= H, "QBits: woq_moe_backward: leading dimension smaller than hidden");
-  const size_t xsz = woq_dtype_size((uint32_t)x_dtype);
-  WOQ_CHECK((uintptr_t)x_dev % (4 * xsz) == 0 && ldx % 4 == 0,
-            "QBits: woq_moe_backward: activation rows must be aligned to four elements");
-  WOQ_CHECK((uintptr_t)gate_up_blobs_dev % 16 == 0 && (uintptr_t)down_blobs_dev % 16 == 0 &&
-                (uintptr_t)workspace_dev % 256 == 0,
-            "QBits: woq_moe_backward: blobs must be 16-byte and the workspace 256-byte aligned");
   const MoeBwdWorkspace w = moe_bwd_ws(T, top_k, E, H, I);
-  WOQ_CHECK(workspace_bytes >= w.total, "QBits: woq_moe_backward: the workspace holds " + std::to_string(workspace_bytes) +
-                                            " bytes, this call needs " + std::to_string(w.total) +
-                                            " (woq_moe_backward_workspace)");
   hipStream_t st = (hipStream_t)stream;
   uint8_t* ws = (uint8_t*)workspace_dev;
   const int S = T * top_k, P = S + BWD_BM;
-  const MoePromptPlan plan = moe_prompt_plan_tables(ws, T, top_k, E);
+  const MoeRoutePlan plan = moe_plan_tables(MOE_PROMPT, ws, T, top_k, E);
   unsigned int* smax = (unsigned int*)(ws + w.smax);
   float* gu = (float*)(ws + w.gu);
   float* dhp = (float*)(ws + w.dhp);
@@ -409,11 +396,7 @@ extern "C" int woq_moe_backward(const void* grad_out_dev, int grad_dtype, int ld
   else
     hipLaunchKernelGGL(moe_bwd_pack_kernel<WOQ_F16>, pgrid, dim3(256), 0, st, pk);
 
-  MoeCall m = {};
-  m.x = x_dev, m.x_dtype = x_dtype, m.ldx = ldx, m.T = T, m.top_k = top_k, m.E = E;
-  m.gate_up_blobs = gate_up_blobs_dev, m.gate_up_hdr = gate_up_hdr, m.gate_up_stride = gate_up_stride;
-  m.down_blobs = down_blobs_dev, m.down_hdr = down_hdr, m.down_stride = down_stride;
-  if (const int rc = launch_moe_prompt_gate_up_raw(m, plan, gu, st)) return rc;
+  if (const int rc = launch_moe_prompt_product(MOE_GATE_UP_RAW, m, plan, nullptr, gu, st)) return rc;
 
   MoeBwdProductArgs p1 = {};
   p1.w = pk.w[0], p1.gp = pk.gp, p1.rs = pk.rs, p1.smax = smax;

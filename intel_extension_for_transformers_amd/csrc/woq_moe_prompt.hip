@@ -33,6 +33,8 @@
 //     scales as for int4. One fp16 product per operand pair, fp32 accumulation: the contract of the
 //     dense prompt GEMM's bf16 / fp16 / int8 compute modes. Row tiles past the block's rows are skipped wave-uniformly.
 //  4. combine: woq_moe.hip's launch_moe_combine.
+// The host front is woq_moe.hip's: the workspace layout, the entry points' checks and launch_moe_forward, which under
+// MOE_PROMPT calls launch_moe_prompt_plan and launch_moe_prompt_product below.
 // No split-K, no floating-point atomics, a fixed summation order: the same inputs give the same bytes.
 #include <math.h>
 #include <string.h>
@@ -40,8 +42,7 @@
 #include <algorithm>
 #include <string>
 
-#include "woq_gemv_common.h"
-#include "woq_host.h"
+#include "woq_moe.h"
 
 namespace woq {
 namespace {
@@ -49,7 +50,7 @@ namespace {
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-constexpr int MP_SEG = 1024;                          // slots of one plan segment = threads of a plan workgroup
+constexpr int MP_SEG = MOE_PLAN_SEG;                  // slots of one plan segment = threads of a plan workgroup
 constexpr int MP_ROWS = MOE_PROMPT_ROWS;              // rows of a table block
 constexpr int MP_WAVES = 4, MP_CT = 2;                // waves of a workgroup, column tiles of a wave
 constexpr int MP_IMAGE = MP_ROWS * WOQ_TILE_K * 2;    // bytes of one A image: 128 rows x 128 k fp16
@@ -57,12 +58,6 @@ constexpr int MP_LDS = 2 * MP_IMAGE + 2 * MP_ROWS * 4;  // two images + two sets
 static_assert(MP_ROWS == 128, "the staging map and the eight row tiles of a wave assume 128-row blocks");
 
 // ---- 1. plan ---------------------------------------------------------------------------------------------------------
-template <bool IDX64>
-__device__ __forceinline__ int moe_prompt_id(const void* topk_idx, int s, int E) {
-  const long long v = IDX64 ? (long long)((const int64_t*)topk_idx)[s] : (long long)((const int32_t*)topk_idx)[s];
-  return (v >= 0 && v < (long long)E) ? (int)v : -1;
-}
-
 template <bool IDX64>
 __global__ __launch_bounds__(MP_SEG) void moe_prompt_count_kernel(const void* __restrict__ topk_idx, int S, int E,
                                                                   int32_t* __restrict__ counts,
@@ -72,7 +67,7 @@ __global__ __launch_bounds__(MP_SEG) void moe_prompt_count_kernel(const void* __
   if (tid < E) cnt[tid] = 0;
   __syncthreads();
   if (s < S) {
-    const int e = moe_prompt_id<IDX64>(topk_idx, s, E);
+    const int e = moe_slot_id<IDX64>(topk_idx, s, E);
     if (e >= 0)
       atomicAdd(&cnt[e], 1);  // an integer count: the result does not depend on the order
     else
@@ -121,7 +116,7 @@ __global__ __launch_bounds__(MP_SEG) void moe_prompt_scatter_kernel(const void* 
   __shared__ int32_t ids[MP_SEG];
   const int tid = threadIdx.x, seg = blockIdx.x, s0 = seg * MP_SEG;
   const int n = min(MP_SEG, S - s0);
-  ids[tid] = tid < n ? moe_prompt_id<IDX64>(topk_idx, s0 + tid, E) : -1;
+  ids[tid] = tid < n ? moe_slot_id<IDX64>(topk_idx, s0 + tid, E) : -1;
   __syncthreads();
   if (tid >= E) return;
   int p = counts[(size_t)seg * E + tid];
@@ -135,21 +130,6 @@ __global__ __launch_bounds__(MP_SEG) void moe_prompt_scatter_kernel(const void* 
 }
 
 // ---- 2 / 3. the grouped product --------------------------------------------------------------------------------------
-struct MoePromptArgs {
-  const uint8_t* blobs;  // expert e's blob at blobs + e * stride
-  size_t stride, off_q[2], off_scale, off_zp[2];  // [plane]: woq_host.h MoePlanes
-  int K, N, tiles_k, tiles_n, n_groups, group, scale_type;
-  LutArgs lut;  // table kinds: the 16 table values as fp16, d[0] their low bytes and d[1] their high bytes (moe_prompt_lut)
-  const void* x;  // gate/up: activations [T, ldx] of x_dtype; down: fp32 rows [sorted slot][ldx]
-  int x_dtype, ldx, top_k;
-  const int32_t* sorted;
-  const MoeBlock* blocks;
-  const int32_t* nblocks;
-  float* out;  // gate/up: SiLU(g) * u [sorted slot][ldo]; down: y [sorted slot][ldo]
-  int ldo, half_tiles;
-  bool e5m2;  // MOE_W_FP8: the codes are e5m2
-};
-
 template <int SMODE, int NP>
 struct MoePromptB {  // one K tile of one wave's weight operand, as loaded; NP nibble planes
   u32x4 w[MP_CT][NP];
@@ -211,7 +191,7 @@ constexpr int MP_W_FP8_E5M2 = MOE_W_FP8 + 1;
 // RAW (the backward's recompute, gate/up only): the epilogue stores the fp32 g and u themselves, row [g (I) | u (I)] of
 // [sorted slot][ldo = 2 I], instead of SiLU(g) * u
 template <bool GU, int SMODE, bool ASYM, int WK, bool RAW = false>
-__global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const MoePromptArgs a) {
+__global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const MoeGemmArgs a) {
   static_assert(GU || !RAW, "the raw epilogue belongs to the gate/up launch");
   constexpr int NS = SMODE == 1 ? 2 : 1;  // scales of a tile, column and lane: its 32-k block of either 64-k half
   constexpr bool FP8 = WK == MOE_W_FP8 || WK == MP_W_FP8_E5M2;
@@ -495,39 +475,14 @@ __global__ __launch_bounds__(MP_WAVES * 64, 2) void moe_prompt_gemm_kernel(const
   }
 }
 
-struct MoePromptWorkspace {  // the plan tables first: moe_prompt_plan_tables relies on it
-  size_t sorted, pos_of, blocks, nblocks, counts, h, y, total;
-  int max_blocks, nseg;
-};
-MoePromptWorkspace moe_prompt_ws(int T, int top_k, int E, int hidden, int inter) {
-  MoePromptWorkspace w;
-  const size_t S = (size_t)T * top_k;
-  w.max_blocks = (int)((S + MP_ROWS - 1) / MP_ROWS + std::min<size_t>((size_t)E, S));
-  w.nseg = (int)((S + MP_SEG - 1) / MP_SEG);
-  w.sorted = 0;
-  w.pos_of = w.sorted + woq_round_up(S * 4, 256);
-  w.blocks = w.pos_of + woq_round_up(S * 4, 256);
-  w.nblocks = w.blocks + woq_round_up((size_t)w.max_blocks * sizeof(MoeBlock), 256);
-  w.counts = w.nblocks + 256;
-  w.h = w.counts + woq_round_up((size_t)w.nseg * E * 4, 256);
-  w.y = w.h + woq_round_up(S * (size_t)inter * 4, 256);
-  w.total = w.y + woq_round_up(S * (size_t)hidden * 4, 256);
-  return w;
-}
-
-bool moe_prompt_shape_ok(int T, int top_k, int E, int hidden, int inter) {
-  return T > 0 && top_k > 0 && E > 0 && hidden > 0 && inter > 0 && E <= MOE_MAX_EXPERTS &&
-         (long long)T * top_k <= MOE_PROMPT_MAX_SLOTS;
-}
-
 template <bool GU, int SMODE, bool ASYM, int WK, bool RAW>
-int moe_prompt_launch_one(const MoePromptArgs& a, dim3 grid, hipStream_t st) {
+int moe_prompt_launch_one(const MoeGemmArgs& a, dim3 grid, hipStream_t st) {
   if (const int rc = allow_dynamic_lds<moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK, RAW>>(MP_LDS)) return rc;
   hipLaunchKernelGGL((moe_prompt_gemm_kernel<GU, SMODE, ASYM, WK, RAW>), grid, dim3(MP_WAVES * 64), MP_LDS, st, a);
   return 0;
 }
 template <bool GU, int SMODE, bool ASYM, bool RAW>
-int moe_prompt_launch_kind(const MoePromptArgs& a, MoeWeightKind kind, dim3 grid, hipStream_t st) {
+int moe_prompt_launch_kind(const MoeGemmArgs& a, MoeWeightKind kind, dim3 grid, hipStream_t st) {
   if (kind == MOE_W_INT8) return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT8, RAW>(a, grid, st);
   if constexpr (!ASYM) {  // moe_header_problem admits no table or fp8 blob with zero points
     if constexpr (!RAW) {  // the backward has no fused fp8 arm (woq_moe_backward refuses fp8 blobs)
@@ -541,7 +496,7 @@ int moe_prompt_launch_kind(const MoePromptArgs& a, MoeWeightKind kind, dim3 grid
   return moe_prompt_launch_one<GU, SMODE, ASYM, MOE_W_INT4, RAW>(a, grid, st);
 }
 template <bool GU, bool RAW = false>
-int moe_prompt_launch_gemm(const MoePromptArgs& a, bool smode1, bool asym, MoeWeightKind kind, dim3 grid, hipStream_t st) {
+int moe_prompt_launch_gemm(const MoeGemmArgs& a, bool smode1, bool asym, MoeWeightKind kind, dim3 grid, hipStream_t st) {
   if (!smode1)
     return asym ? moe_prompt_launch_kind<GU, 0, true, RAW>(a, kind, grid, st)
                 : moe_prompt_launch_kind<GU, 0, false, RAW>(a, kind, grid, st);
@@ -566,46 +521,9 @@ LutArgs moe_prompt_lut(uint32_t weight_type) {
   return L;
 }
 
-MoePromptArgs moe_prompt_args(const void* blobs, const woq_blob_header& h, size_t stride, MoeWeightKind& kind) {
-  MoePromptArgs a = {};
-  a.blobs = (const uint8_t*)blobs, a.stride = stride;
-  const MoePlanes p = moe_blob_planes(h);
-  for (int i = 0; i < 2; ++i) a.off_q[i] = p.off_q[i], a.off_zp[i] = p.off_zp[i];
-  a.off_scale = p.off_scale, kind = p.kind;
-  if (kind == MOE_W_TABLE) a.lut = moe_prompt_lut(h.weight_type);
-  a.e5m2 = h.weight_type == WOQ_W_FP8_E5M2;
-  a.K = h.K, a.N = h.N, a.tiles_k = h.Kpad / WOQ_TILE_K, a.tiles_n = h.Npad / WOQ_TILE_N;
-  a.n_groups = h.n_groups, a.group = h.group, a.scale_type = (int)h.scale_type;
-  return a;
-}
-
-// the gate/up launch over a plan; RAW: `out` receives [g | u] rows of 2 I, else SiLU(g) * u rows of I
-template <bool RAW>
-int moe_prompt_gate_up(const MoeCall& m, const MoePromptPlan& p, float* out, hipStream_t st) {
-  const woq_blob_header& gh = *m.gate_up_hdr;
-  const int I = m.down_hdr->K;
-  MoeWeightKind g_kind;
-  MoePromptArgs g = moe_prompt_args(m.gate_up_blobs, gh, m.gate_up_stride, g_kind);
-  g.x = m.x, g.x_dtype = m.x_dtype, g.ldx = m.ldx, g.top_k = m.top_k;
-  g.sorted = p.sorted, g.blocks = p.blocks, g.nblocks = p.nblocks;
-  g.out = out, g.ldo = RAW ? 2 * I : I, g.half_tiles = I / 16;
-  const unsigned gx = (unsigned)((I / 16 + MP_WAVES - 1) / MP_WAVES);
-  return moe_prompt_launch_gemm<true, RAW>(g, gh.scale_mode == 1, gh.off_zp != 0, g_kind,
-                                           dim3(gx, (unsigned)p.max_blocks), st);
-}
-
 }  // namespace
 
-size_t moe_prompt_plan_bytes(int T, int top_k, int E) { return moe_prompt_ws(T, top_k, E, 0, 0).h; }
-
-MoePromptPlan moe_prompt_plan_tables(void* workspace, int T, int top_k, int E) {
-  const MoePromptWorkspace w = moe_prompt_ws(T, top_k, E, 0, 0);
-  uint8_t* ws = (uint8_t*)workspace;
-  return MoePromptPlan{(int32_t*)(ws + w.sorted), (int32_t*)(ws + w.pos_of), (MoeBlock*)(ws + w.blocks),
-                       (int32_t*)(ws + w.nblocks), (int32_t*)(ws + w.counts), w.max_blocks, w.nseg};
-}
-
-void launch_moe_prompt_plan(const void* topk_idx, bool idx_is_int64, int S, int E, const MoePromptPlan& p, hipStream_t st) {
+void launch_moe_prompt_plan(const void* topk_idx, bool idx_is_int64, int S, int E, const MoeRoutePlan& p, hipStream_t st) {
   const dim3 pgrid((unsigned)p.nseg), pblock(MP_SEG);
   if (idx_is_int64)
     hipLaunchKernelGGL(moe_prompt_count_kernel<true>, pgrid, pblock, 0, st, topk_idx, S, E, p.counts, p.pos_of);
@@ -618,93 +536,24 @@ void launch_moe_prompt_plan(const void* topk_idx, bool idx_is_int64, int S, int 
     hipLaunchKernelGGL(moe_prompt_scatter_kernel<false>, pgrid, pblock, 0, st, topk_idx, S, E, p.counts, p.sorted, p.pos_of);
 }
 
-int launch_moe_prompt_gate_up_raw(const MoeCall& m, const MoePromptPlan& p, float* gu, hipStream_t st) {
-  return moe_prompt_gate_up<true>(m, p, gu, st);
-}
-
-int launch_moe_prompt_forward(const MoeCall& m, hipStream_t st) {
-  const woq_blob_header& dh = *m.down_hdr;
-  const int H = dh.N, I = dh.K;
-  const MoePromptWorkspace w = moe_prompt_ws(m.T, m.top_k, m.E, H, I);
-  uint8_t* ws = (uint8_t*)m.workspace;
-  const MoePromptPlan plan = moe_prompt_plan_tables(ws, m.T, m.top_k, m.E);
-  const int32_t* pos_of = plan.pos_of;
-  float* hbuf = (float*)(ws + w.h);
-  float* ybuf = (float*)(ws + w.y);
-
-  launch_moe_prompt_plan(m.topk_idx, m.idx_is_int64, m.T * m.top_k, m.E, plan, st);
-
-  if (const int rc = moe_prompt_gate_up<false>(m, plan, hbuf, st)) return rc;
-
-  MoeWeightKind d_kind;
-  MoePromptArgs d = moe_prompt_args(m.down_blobs, dh, m.down_stride, d_kind);
-  d.x = hbuf, d.x_dtype = WOQ_F32, d.ldx = I, d.top_k = m.top_k;
-  d.sorted = plan.sorted, d.blocks = plan.blocks, d.nblocks = plan.nblocks;
-  d.out = ybuf, d.ldo = H, d.half_tiles = 0;
-  const unsigned dx = (unsigned)((d.tiles_n + MP_WAVES * MP_CT - 1) / (MP_WAVES * MP_CT));
-  if (const int rc = moe_prompt_launch_gemm<false>(d, dh.scale_mode == 1, dh.off_zp != 0, d_kind,
-                                                   dim3(dx, (unsigned)w.max_blocks), st))
-    return rc;
-
-  if (m.residual != nullptr) {
-    if (const int rc = launch_moe_combine_residual(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, *m.residual, st)) return rc;
-  } else {
-    launch_moe_combine(ybuf, pos_of, m.topk_w, m.T, m.top_k, H, m.out, m.out_dtype, m.ldo, st);
+int launch_moe_prompt_product(MoeRole role, const MoeCall& m, const MoeRoutePlan& p, const float* h, float* out,
+                              hipStream_t st) {
+  const bool gu = role != MOE_DOWN;
+  const woq_blob_header& hdr = gu ? *m.gate_up_hdr : *m.down_hdr;
+  MoeWeightKind kind;
+  MoeGemmArgs a = moe_gemm_args(m, gu, kind);
+  if (kind == MOE_W_TABLE) a.lut = moe_prompt_lut(hdr.weight_type);
+  const bool smode1 = hdr.scale_mode == 1, asym = hdr.off_zp != 0;
+  if (!gu) {
+    moe_bind_down(a, m, p, h, out);
+    const unsigned dx = (unsigned)((a.tiles_n + MP_WAVES * MP_CT - 1) / (MP_WAVES * MP_CT));
+    return moe_prompt_launch_gemm<false>(a, smode1, asym, kind, dim3(dx, (unsigned)p.max_blocks), st);
   }
-  WOQ_HIP(hipGetLastError());
-  return 0;
+  const int I = m.down_hdr->K;
+  moe_bind_gate_up(a, m, p, out, role == MOE_GATE_UP_RAW ? 2 * I : I);
+  const dim3 grid((unsigned)((I / 16 + MP_WAVES - 1) / MP_WAVES), (unsigned)p.max_blocks);
+  return role == MOE_GATE_UP_RAW ? moe_prompt_launch_gemm<true, true>(a, smode1, asym, kind, grid, st)
+                                 : moe_prompt_launch_gemm<true, false>(a, smode1, asym, kind, grid, st);
 }
 
 }  // namespace woq
-
-extern "C" size_t woq_moe_prompt_workspace(int T, int top_k, int E, int hidden, int inter) {
-  if (!woq::moe_prompt_shape_ok(T, top_k, E, hidden, inter)) return 0;
-  return woq::moe_prompt_ws(T, top_k, E, hidden, inter).total;
-}
-
-extern "C" int woq_moe_prompt_forward(const void* x_dev, int x_dtype, int ldx, const void* topk_idx_dev, int idx_is_int64,
-                                      const float* topk_w_dev, int T, int top_k, int E, const void* gate_up_blobs_dev,
-                                      const woq_blob_header* gate_up_hdr, size_t gate_up_stride,
-                                      const void* down_blobs_dev, const woq_blob_header* down_hdr, size_t down_stride,
-                                      void* out_dev, int out_dtype, int ldo, void* workspace_dev, size_t workspace_bytes,
-                                      void* stream) {
-  WOQ_TRY
-  using namespace woq;
-  WOQ_CHECK(gate_up_hdr && down_hdr, "QBits: woq_moe_prompt_forward: null header");
-  if (const char* p = moe_header_problem(*gate_up_hdr, gate_up_stride, false)) WOQ_FAIL(p);
-  if (const char* p = moe_header_problem(*down_hdr, down_stride, false)) WOQ_FAIL(p);
-  const int H = down_hdr->N, I = down_hdr->K;
-  WOQ_CHECK(gate_up_hdr->K == H && gate_up_hdr->N == 2 * I,
-            "QBits: woq_moe_prompt_forward: gate/up blobs must be [K = hidden, N = 2 * inter] against down blobs [K = inter, N = hidden]");
-  WOQ_CHECK(I % 16 == 0, "QBits: woq_moe_prompt_forward: the intermediate size must be a multiple of 16 (gate tile tn pairs "
-                         "with up tile tn + inter / 16)");
-  WOQ_CHECK(H % 4 == 0, "QBits: woq_moe_prompt_forward: the hidden size must be a multiple of 4");
-  auto dtype_ok = [](int d) { return d == WOQ_F32 || d == WOQ_BF16 || d == WOQ_F16; };
-  WOQ_CHECK(dtype_ok(x_dtype) && dtype_ok(out_dtype), "QBits: unsupported qbits data type.");
-  if (T <= 0) return 0;
-  WOQ_CHECK(moe_prompt_shape_ok(T, top_k, E, H, I),
-            "QBits: woq_moe_prompt_forward takes at most " + std::to_string(MOE_MAX_EXPERTS) + " experts and " +
-                std::to_string(MOE_PROMPT_MAX_SLOTS) + " routed slots (T * top_k) per call");
-  WOQ_CHECK(x_dev && topk_idx_dev && topk_w_dev && gate_up_blobs_dev && down_blobs_dev && out_dev && workspace_dev,
-            "QBits: woq_moe_prompt_forward: null tensor");
-  WOQ_CHECK(ldx >= H && ldo >= H, "QBits: woq_moe_prompt_forward: leading dimension smaller than hidden");
-  const size_t xsz = woq_dtype_size((uint32_t)x_dtype);
-  WOQ_CHECK((uintptr_t)x_dev % (4 * xsz) == 0 && ldx % 4 == 0,
-            "QBits: woq_moe_prompt_forward: activation rows must be aligned to four elements");
-  WOQ_CHECK((uintptr_t)gate_up_blobs_dev % 16 == 0 && (uintptr_t)down_blobs_dev % 16 == 0 &&
-                (uintptr_t)workspace_dev % 16 == 0,
-            "QBits: woq_moe_prompt_forward: blobs and workspace must be 16-byte aligned");
-  const size_t need = moe_prompt_ws(T, top_k, E, H, I).total;
-  WOQ_CHECK(workspace_bytes >= need, "QBits: woq_moe_prompt_forward: the workspace holds " +
-                                         std::to_string(workspace_bytes) + " bytes, this call needs " +
-                                         std::to_string(need) + " (woq_moe_prompt_workspace)");
-  MoeCall m;
-  m.x = x_dev, m.x_dtype = x_dtype, m.ldx = ldx;
-  m.topk_idx = topk_idx_dev, m.idx_is_int64 = idx_is_int64 != 0, m.topk_w = topk_w_dev;
-  m.T = T, m.top_k = top_k, m.E = E;
-  m.gate_up_blobs = gate_up_blobs_dev, m.gate_up_hdr = gate_up_hdr, m.gate_up_stride = gate_up_stride;
-  m.down_blobs = down_blobs_dev, m.down_hdr = down_hdr, m.down_stride = down_stride;
-  m.out = out_dev, m.out_dtype = out_dtype, m.ldo = ldo, m.workspace = workspace_dev;
-  if (const int rc = launch_moe_prompt_forward(m, (hipStream_t)stream)) return rc;
-  WOQ_END
-}

@@ -70,14 +70,15 @@ def _experts(shape, kind):
     return _BUILT[(shape, kind)]
 
 
-def _check(got, shape, kind, T, form, what):
+def _check(got, shape, kind, T, form, what, act="fp32"):
     _, Wgu, Wdn = _experts(shape, kind)
-    x, idx, w = P._inputs(shape, T, "fp32", "")
+    x, idx, w = P._inputs(shape, T, act, "")
     xf = x.float().numpy()
     if form == "prompt":
         ref, tol = PR.reference(xf, idx, w, Wgu, Wdn)
     else:
-        ref, _, B = MR.reference(xf, idx, w, Wgu, Wdn, (1 if KINDS[kind][1] == 32 else 0, False))
+        bits = K.DTYPES[act][1]  # (inert in the call below, whose own tolerance is dropped; charged by hand further down)
+        ref, _, B = MR.reference(xf, idx, w, Wgu, Wdn, (1 if KINDS[kind][1] == 32 else 0, False), bits)
         inter, x64, c, tol = Wdn[0].shape[0], xf.astype(np.float64), 1e-5, np.zeros(ref.shape)  # A8: MR.block's A, n U -> c
         for t in range(T):
             mag = np.zeros(ref.shape[1])
@@ -93,6 +94,8 @@ def _check(got, shape, kind, T, form, what):
                 mag += abs(float(w[t, j])) * np.abs(h @ Wdn[e])
             tol[t] += (idx.shape[1] + 1) * MR.U * mag
         tol = tol + 4 * B
+        if bits != 24:  # the one rounding of the output to its type, as MR.reference charges it
+            tol = tol + 2.0 ** -bits * np.abs(ref)
     if kind.startswith("all_"):
         tol = tol + 1e-5
     ratio = np.abs(got.float().cpu().numpy().astype(np.float64) - ref) / tol
@@ -100,11 +103,11 @@ def _check(got, shape, kind, T, form, what):
     assert np.isfinite(ratio).all() and ratio.max() <= 1.0, (what, shape, kind, T, float(ratio.max()))
 
 
-def _run(shape, kind, T, form):
+def _run(shape, kind, T, form, act="fp32"):
     from intel_extension_for_transformers_amd import qbits
 
     mod = _experts(shape, kind)[0]
-    x, idx, w = P._inputs(shape, T, "fp32", "")
+    x, idx, w = P._inputs(shape, T, act, "")
     return qbits.moe_forward(x.cuda(), torch.from_numpy(idx).cuda(), torch.from_numpy(w).cuda(), mod.gate_up_blobs,
                              mod.down_blobs, form=form)
 
@@ -117,6 +120,15 @@ RTN = [k for k in KINDS if not k.startswith("all_")]
 @pytest.mark.parametrize("shape", ["h256", "h128", "h1152"])
 def test_grouped_form_against_float64(shape, kind, T):
     _check(_run(shape, kind, T, "grouped"), shape, kind, T, "grouped", "grouped")
+
+
+@pytest.mark.parametrize("T", [1, 5])  # the pair packing | the row-set packing
+@pytest.mark.parametrize("act", ["bf16", "fp16"])
+def test_grouped_form_half_precision_rows_against_float64(act, T):
+    """the kernel's bf16 / fp16 row load; the output is of the activations' type, whose rounding joins the tolerance"""
+    got = _run("h128", "e4m3_g32", T, "grouped", act)
+    assert got.dtype == K.DTYPES[act][0]
+    _check(got, "h128", "e4m3_g32", T, "grouped", "grouped " + act, act)
 
 
 @pytest.mark.parametrize("T", [37, 300])
